@@ -22,19 +22,20 @@ same way with its own `single_gpu` and `speedup_vs_1gpu` — the frame north_sta
 `--weak` instead grows the frame with N (width x sqrt(N)).  `--dist` runs the N > 1 code path (nccl process group,
 all_gather_into_tensor, resolve of the gathered buffer) at world size 1, so that it executes on a one-GPU box.
 
-The JSON line carries, besides the driver's contract:
+The JSON line carries, besides the driver's contract (the records marked * only on request: `--others`, `--cpu-sample`, since
+their child runs and CPU renders take minutes after the timed steps):
   roofline       algorithmic bytes per launch (SURVEY §8(d) formula, event counts measured by the CPU
                  oracle on a bounded sample of the same workload) / mean kernel time from HIP events
-                 on the launch stream, against the 8 TB/s HBM peak; `traffic` is the memory-side figure of this launch: in the default
-                 run it is measured live - bench.py starts itself twice under rocprofv3 (--pmc FETCH_SIZE, then --pmc WRITE_SIZE, one
+                 on the launch stream, against the 8 TB/s HBM peak; `traffic` is the memory-side figure of this launch: with --others
+                 it is measured live - bench.py starts itself twice under rocprofv3 (--pmc FETCH_SIZE, then --pmc WRITE_SIZE, one
                  launch each) after the timed region; otherwise (other workloads, no rocprofv3) the committed passes named by
                  `traffic_source` are scaled to this launch.  `traffic_committed` keeps that replay beside the live figure.
-  cpu_baseline   the reference's own renderer (oracle/_ref/ref_driver, "reference": all hardware threads as the
+  cpu_baseline*  (--cpu-sample RESxSPP) the reference's own renderer (oracle/_ref/ref_driver, "reference": all hardware threads as the
                  reference starts them, plus `single_thread`) and our CPU restatement at one thread per core (`port`),
                  timed on this host's cores on bounded samples of the same workload.  Rank 0, N=1 only.
-  rccl_path_one_rank  (N = 1) the collective path of --gpus N run with one rank in a child process (`--dist`): proof in the line itself
+  rccl_path_one_rank*  (N = 1) the collective path of --gpus N run with one rank in a child process (`--dist`): proof in the line itself
                  that the RCCL calls of the one-process-per-GPU front end execute on the box the line was measured on.
-  other_configs  (N = 1) the other BASELINE configs' workloads, a few steps each after the timed region: config 3's
+  other_configs*  (N = 1) the other BASELINE configs' workloads, a few steps each after the timed region: config 3's
                  substitute scene (05_head1ss_sub volpathtrace), config 4's (06_gridsdf_synth implicit), config 5's frame
                  (03_volume 3840x1600), each with its own cold first call and roofline record.
 """
@@ -213,6 +214,31 @@ class Bench:
             elapsed = float(t.item())
         return elapsed
 
+    def dump_outputs(self, w, out_dir, budget=60 << 20):
+        """What the last step handed its caller, as .npy for output-for-output comparison of two builds: the resolved frame and,
+        at N = 1, the pixel state the launch leaves in HBM (hit counts; PCG32 {state, inc} as four 32-bit halves, exact in
+        float64).  Over `budget` bytes (the line promises at most 64 MB), a fixed seeded sample of pixels (row-major indices in pixels.npy) instead of the frame."""
+        np = self.np
+        arrays = {"frame": w.frame.cpu().numpy()}                          # (h, w, 4) float32
+        if self.world == 1:
+            st = w.scene.make_state(w.params)
+            self.vpt.state_download(w.layout, w.d_image.data_ptr(), w.d_hits.data_ptr(), w.d_rng.data_ptr(), st, self.stream)
+            self.torch.cuda.synchronize()
+            arrays["hits"] = st.hits.astype(np.float64)[..., None]           # (h, w, 1)
+            arrays["rngs"] = st.rngs.view(np.uint32).astype(np.float64)      # (h, w, 4): lo, hi of state, then of inc
+        npix = w.width * w.height
+        arrays = {k: a.reshape(npix, -1) for k, a in arrays.items()}
+        per_pixel = sum(a.itemsize * a.shape[1] for a in arrays.values())
+        if npix * per_pixel > budget:
+            pixels = np.sort(np.random.default_rng(0).choice(npix, budget // (per_pixel + 8), replace=False))
+            arrays = {k: a[pixels] for k, a in arrays.items()}
+            arrays["pixels"] = pixels.astype(np.float64)
+        else:
+            arrays = {k: a.reshape(w.height, w.width, -1) for k, a in arrays.items()}
+        os.makedirs(out_dir, exist_ok=True)
+        for k, a in arrays.items():
+            np.save(os.path.join(out_dir, k + ".npy"), a)
+
     def cold_call(self, w):
         """the first call on w's (fresh) scene handle: no wave costs known yet"""
         self.torch.cuda.synchronize()
@@ -372,13 +398,17 @@ def main():
     ap.add_argument("--scene", default=SCENE)
     ap.add_argument("--weak", action="store_true", help="grow the frame with N (width x sqrt(N)) instead of the fixed frame")
     ap.add_argument("--strong", action="store_true", help="(default, kept for older command lines) fixed frame for every N")
-    ap.add_argument("--cpu-sample", default="640x96", help="cpu baseline sample: <resolution>x<spp>; '0' disables")
+    ap.add_argument("--cpu-sample", default="0", help="cpu baseline sample: <resolution>x<spp>, e.g. 640x96; '0' (default) disables")
     ap.add_argument("--tile", type=int, default=8)
     ap.add_argument("--balance", action="store_true", help="add per-wave duration statistics of the last launch to the line")
     ap.add_argument("--no-cold", action="store_true", help="skip the cold first-call measurement (N = 1)")
-    ap.add_argument("--no-others", action="store_true", help="skip the other BASELINE configs (N = 1) / the config-5 record (N > 1)")
+    ap.add_argument("--others", action="store_true", help="add the other BASELINE configs, live rocprofv3 counter passes and the RCCL one-rank "
+                    "child (N = 1) / the config-5 record (N > 1): minutes of child runs after the timed steps")
+    ap.add_argument("--no-others", action="store_true", help="(default, kept for older command lines) no --others")
     ap.add_argument("--dist", action="store_true", help="N = 1: run the N > 1 code path (nccl group, all_gather_into_tensor) at world size 1")
     ap.add_argument("--dump-frame", default=None, help="write the resolved frame of the last step (float32 h x w x 4) to this .npy")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (frame; at N = 1 also hits, rngs) as DIR/<name>.npy, at most 64 MB")
     args = ap.parse_args()
 
     B = Bench(args)
@@ -390,6 +420,8 @@ def main():
     elapsed = B.timed(w, args.steps, args.warmup)
     if args.dump_frame and rank == 0:
         np.save(args.dump_frame, w.frame.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        B.dump_outputs(w, args.dump_outputs)
     balance = None
     if args.balance:   # load-balance figures of the last launch (after the timed region): per-wave durations
         c = w.dev.last_wave_costs().astype(np.float64) * 1e-5   # ticks of 100 MHz -> ms
@@ -407,7 +439,7 @@ def main():
     single = config5 = None
     if world > 1 and not args.weak:
         single = B.alone_on_rank0(args.scene, args.shader, args.bounces, resolution, args.spp, max(1, min(args.steps, 2)))
-        if default_workload and not args.no_others:
+        if default_workload and args.others:
             # BASELINE config[4]'s frame, the one ">= 6x at 8 GPUs" can hold on: 03_volume 3840x1600, 256 spp per step
             w5 = B.workload(SCENE, "volpathtrace", 64, 3840, 256)
             e5 = B.timed(w5, 2, 2)   # the first call measures tile costs (pilot), the second may split tiles: both warm-up
@@ -454,12 +486,12 @@ def main():
                 else:
                     rec["valu_live_error"] = sq.get("error", "counters missing")
             return rec
-        live_ok = world == 1 and default_workload and args.spp == 256 and not args.no_others and not args.dist
+        live_ok = world == 1 and default_workload and args.spp == 256 and args.others and not args.dist
         if live_ok:
             with_live_traffic(roofline, w, "vpt_mesh_kernel", ())
         cpu_baseline = B.cpu_baseline(w) if (world == 1 and args.cpu_sample != "0") else None
         others = None
-        if world == 1 and default_workload and not args.no_others:
+        if world == 1 and default_workload and args.others:
             others = []
             # Each at its BASELINE sample count per step (config 5's frame: 256 of its 4096): a lane runs its pixel's samples one after the other and a wave
             # ends with its slowest lane, so the share of a wave's time spent waiting for that lane falls with the length of the chain (config 3: 790 /
@@ -480,7 +512,7 @@ def main():
                                       ["--scene", path, "--shader", shader, "--bounces", str(bounces), "--resolution", str(res), "--spp", str(spp)])
                 del wo
         rccl_path = None
-        if world == 1 and default_workload and not args.no_others and not args.dist:
+        if world == 1 and default_workload and args.others and not args.dist:
             # the N > 1 code path with one rank, in a process of its own (a failure there must not cost the headline line):
             # nccl (= RCCL) process group, all_gather_into_tensor of the tile buffer and the resolve of the gathered buffer per step
             import subprocess
