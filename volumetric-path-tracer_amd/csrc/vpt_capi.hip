@@ -566,13 +566,19 @@ int vpt_scene_create(const vpt_scene_desc* desc, int device, vpt_scene** out) {
   // entries stay below the entries of the instance being traversed
   int need = (scene_depth + 2) + (max_shape_depth + 2);
   s->stack_cap = ((need > 8 ? need : 8) + 3) & ~3;
-  if ((size_t)s->stack_cap * VPT_BLOCK * sizeof(int) > 64 * 1024)
-    return fail(VPT_ERR_UNSUPPORTED, "BVH depth %d needs a %d-entry traversal stack; the LDS stack holds 64", need, s->stack_cap);
+  const int max_stack_cap = 64 * 1024 / (VPT_BLOCK * (int)sizeof(int));   // 256 entries with VPT_BLOCK = 64
+  if (s->stack_cap > max_stack_cap)
+    return fail(VPT_ERR_UNSUPPORTED, "BVH depth %d (scene %d + shapes %d) needs a %d-entry traversal stack; the LDS stack holds %d",
+                need, scene_depth, max_shape_depth, s->stack_cap, max_stack_cap);
   // quad-node traversal: worst case = three pending siblings per quad level of the scene BVH plus of the
   // deepest shape BVH, plus one free entry above the top (the branch-free push stores rejected candidates
   // there).  24 entries per lane = 12 KB per wave keep twelve waves on a CU (144 of 160 KB); whatever the
   // worst case needs beyond that lives in HBM (lane_stack2<true>).
   int need4 = scene_need4 + max_shape_need4 + 1;
+  // the group form of the node phase (vpt_mesh_kernel.hip.h: group_nodes) hands a ray's pop floor - the stack depth at instance entry, at
+  // most scene_need4 - to its helper lanes in the bits above VPT_FLOOR_SHIFT of one word: every stack position has to fit there
+  if ((long long)need4 > (0x7fffffffLL >> VPT_FLOOR_SHIFT))
+    return fail(VPT_ERR_UNSUPPORTED, "quad stack need %d does not fit the traversal's packed pop floor", need4);
   // With the mesh kernel's five parked words per lane (vpt_mesh_kernel.hip.h) a wave takes need4 * 512 + 1280 + 8 bytes of LDS,
   // granted in 1 280-byte steps: up to 22 entries twelve waves fit a CU's 160 KB, with 23 or 24 eleven do - still better than the
   // checked push / pop of the HBM-overflow variant (-7 %), which is for deeper trees only (22 entries in LDS, the rest in HBM).

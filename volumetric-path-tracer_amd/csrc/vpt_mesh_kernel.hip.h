@@ -195,6 +195,7 @@ VPT_DEV bool slab_pass_signed(float nx, float ny, float nz, float fx, float fy, 
 // needed C work ("sessions"): fewer transfers, but the rays outside a session waited for its longest member - 174 wave-level node
 // steps per 64 samples against the own form's 132 - and it LOST (276 ms, profiles/r04_k1_group_forms.txt).
 #define VPT_NONE (-2147483647 - 1)
+#define VPT_FLOOR_SHIFT 4   // group_nodes(): {csgn, slow} in the low 4 bits of the word a ray's state travels in, its pop floor above them
 #ifndef VPT_HOIST_MAX
 #define VPT_HOIST_MAX 16   // scenes with at most this many instances test all root boxes at the start of a query
 #endif
@@ -439,10 +440,12 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
     const float gtmax = pull(owner, tmax);
     int         gcur = pull(owner, cur), gsp = pull(owner, sp);
     const int   gwnb = pull(owner, wnb);
-    const int   gmisc = pull(owner, (shape_base >= 0 ? shape_base : 0) | csgn << 8 | (slow ? 2048 : 0));
+    // sign bits of the ray's direction, NaN-prone flag, pop floor of the ray's level (the stack depth at instance entry: the whole upper
+    // 28 bits, vpt_capi.hip checks at scene creation that the deepest worst case fits them)
+    const int   gmisc = pull(owner, csgn | (slow ? 8 : 0) | (shape_base >= 0 ? shape_base : 0) << VPT_FLOOR_SHIFT);
     if (!gact) gcur = VPT_NONE;
-    const int  gfloor = gmisc & 255, gcsgn = (gmisc >> 8) & 7;   // pop floor of the ray's level, sign bits of its direction
-    const bool gslow = (gmisc & 2048) != 0;                      // NaN-prone direction
+    const int  gfloor = gmisc >> VPT_FLOOR_SHIFT, gcsgn = gmisc & 7;
+    const bool gslow = (gmisc & 8) != 0;
     const STK  gstk = stk.of_lane(owner);
     while (__builtin_amdgcn_ballot_w64(gcur >= 0) != 0) {
       VPT_CNT_MASK(CNT_GNODE, __builtin_amdgcn_ballot_w64(gcur >= 0));
