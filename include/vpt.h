@@ -270,8 +270,8 @@ int vpt_render(vpt_scene* scene, const vpt_params* params, int nsamples, int wid
  *                         ones (same addresses, size, *samples_io > 0) the previous call on this handle downloaded
  *                         into, and a 64-bit checksum over every word of that part (taken after the download, re-taken
  *                         from the arrays now) is unchanged.  An in-place edit of any pixel, another state object, a
- *                         fresh make_state: uploaded, nothing to announce.  VPT_MULTI_RESIDENT=0 makes every call
- *                         upload everything; vpt_multi_uploaded_parts() tells what the last call did.
+ *                         fresh make_state: uploaded, nothing to announce.  vpt_multi_uploaded_parts() tells what
+ *                         the last call did.
  *   vpt_multi_get_state   devices -> host arrays, on demand
  *   vpt_multi_get_render  get_render of the resident state, assembled on devices[0]: the float4 tile buffers travel there
  *                         over xGMI by grouped RCCL send / receive (RCCL is bound on first use, a copy the process already

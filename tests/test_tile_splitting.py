@@ -79,7 +79,7 @@ def test_split_tiles_of_the_implicit_kernel_give_the_same_state(tmp_path, k):
     and whose scene rounds run in the group form - ends in the unsplit state; and the default policy, which finds nothing to gain on a full
     1280-wide frame (K2's partly filled waves are 0.82 / 0.67 / 0.63 as long as the full one: profiles/r04_k2_lane_histogram.txt), leaves it alone"""
     sdf = os.path.join(GOLDEN, "scenes", "06_gridsdf_synth", "gridsdf_synth.json")
-    base = _run(tmp_path, "base", {"VPT_K2_SPLIT": "0"}, 320, 1, 0, 16, 3, scene=sdf, shader="implicit", bounces=4)
+    base = _run(tmp_path, "base", {"VPT_SPLIT": "0"}, 320, 1, 0, 16, 3, scene=sdf, shader="implicit", bounces=4)
     split = _run(tmp_path, f"k{k}", {"VPT_SPLIT_K": str(k)}, 320, 1, 0, 16, 3, scene=sdf, shader="implicit", bounces=4)
     tiles = int(base["tiles"])
     assert list(base["waves"]) == [tiles] * 3

@@ -30,17 +30,9 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "vpt.h"
-
-int vpt_set_error(int code, const char* fmt, ...);   // vpt_capi.hip: records the message for vpt_last_error() on this thread
+#include "vpt_error.h"
 
 namespace {
-
-#define BVH_TRY(expr)                                                                                    \
-  do {                                                                                                   \
-    hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) return vpt_set_error(VPT_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));     \
-  } while (0)
 
 constexpr int BVH_MAX_PRIMS = 4;   // yocto_bvh.cpp:444
 
@@ -259,7 +251,7 @@ extern "C" int vpt_build_bvh(int device, const float* bboxes, int n, vpt_bvh_nod
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return vpt_set_error(VPT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
   if (device < 0 || device >= ndev) return vpt_set_error(VPT_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  BVH_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
 
   dev_buffers B;
   float *bb = nullptr, *ctr = nullptr, *boxes = nullptr;
@@ -268,33 +260,33 @@ extern "C" int vpt_build_bvh(int device, const float* bboxes, int n, vpt_bvh_nod
   tkeys* keys  = nullptr;
   vpt_bvh_node* out = nullptr;
   const size_t cap = 2 * (size_t)n;
-  BVH_TRY(B.alloc(&bb, 6 * (size_t)n));
-  BVH_TRY(B.alloc(&ctr, 3 * (size_t)n));
-  BVH_TRY(B.alloc(&boxes, 6 * cap));
-  BVH_TRY(B.alloc(&prims, (size_t)n));
-  BVH_TRY(B.alloc(&node_of, (size_t)n));
-  BVH_TRY(B.alloc(&flag, (size_t)n + 1));
-  BVH_TRY(B.alloc(&tscan, (size_t)n + 1));
-  BVH_TRY(B.alloc(&partner, (size_t)n));
-  BVH_TRY(B.alloc(&counter, 1));
-  BVH_TRY(B.alloc(&nodes, cap));
-  BVH_TRY(B.alloc(&keys, cap));
-  BVH_TRY(B.alloc(&out, cap));
+  HIP_TRY(B.alloc(&bb, 6 * (size_t)n));
+  HIP_TRY(B.alloc(&ctr, 3 * (size_t)n));
+  HIP_TRY(B.alloc(&boxes, 6 * cap));
+  HIP_TRY(B.alloc(&prims, (size_t)n));
+  HIP_TRY(B.alloc(&node_of, (size_t)n));
+  HIP_TRY(B.alloc(&flag, (size_t)n + 1));
+  HIP_TRY(B.alloc(&tscan, (size_t)n + 1));
+  HIP_TRY(B.alloc(&partner, (size_t)n));
+  HIP_TRY(B.alloc(&counter, 1));
+  HIP_TRY(B.alloc(&nodes, cap));
+  HIP_TRY(B.alloc(&keys, cap));
+  HIP_TRY(B.alloc(&out, cap));
   size_t scan_bytes = 0;
-  BVH_TRY(rocprim::exclusive_scan((void*)nullptr, scan_bytes, flag, tscan, 0, (size_t)n + 1, rocprim::plus<int>()));
+  HIP_TRY(rocprim::exclusive_scan((void*)nullptr, scan_bytes, flag, tscan, 0, (size_t)n + 1, rocprim::plus<int>()));
   char* scan_temp = nullptr;
-  BVH_TRY(B.alloc(&scan_temp, scan_bytes));
+  HIP_TRY(B.alloc(&scan_temp, scan_bytes));
 
   const int  TB = 256;
   const dim3 gn((n + TB - 1) / TB), gn1((n + 1 + TB - 1) / TB);
   auto blocks = [&](int count) { return dim3((count + TB - 1) / TB); };
-  BVH_TRY(hipMemcpy(bb, bboxes, 6 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(bb, bboxes, 6 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_centers, gn, dim3(TB), 0, 0, n, bb, ctr);
   hipLaunchKernelGGL(k_init, gn, dim3(TB), 0, 0, n, prims, node_of);
   tnode root = {0, n, -1, 0, -1, 0, 0, 0, 0.0f, 0, 0};
-  BVH_TRY(hipMemcpy(nodes, &root, sizeof(root), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(nodes, &root, sizeof(root), hipMemcpyHostToDevice));
   int count = 1;
-  BVH_TRY(hipMemcpy(counter, &count, 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(counter, &count, 4, hipMemcpyHostToDevice));
 
   std::vector<int> level_begin = {0};
   int lb = 0, le = 1;
@@ -305,12 +297,12 @@ extern "C" int vpt_build_bvh(int device, const float* bboxes, int n, vpt_bvh_nod
     hipLaunchKernelGGL(k_bounds, gn, dim3(TB), 0, 0, n, prims, node_of, bb, ctr, keys);
     hipLaunchKernelGGL(k_decide, blocks(ln), dim3(TB), 0, 0, lb, le, nodes, keys, prims, bb, ctr, boxes);
     hipLaunchKernelGGL(k_flags, gn1, dim3(TB), 0, 0, n, prims, node_of, nodes, ctr, flag);
-    BVH_TRY(rocprim::exclusive_scan((void*)scan_temp, scan_bytes, flag, tscan, 0, (size_t)n + 1, rocprim::plus<int>()));
+    HIP_TRY(rocprim::exclusive_scan((void*)scan_temp, scan_bytes, flag, tscan, 0, (size_t)n + 1, rocprim::plus<int>()));
     hipLaunchKernelGGL(k_children, blocks(ln), dim3(TB), 0, 0, lb, le, nodes, tscan, counter);
     hipLaunchKernelGGL(k_partners, gn, dim3(TB), 0, 0, n, node_of, nodes, flag, tscan, partner);
     hipLaunchKernelGGL(k_swap, gn, dim3(TB), 0, 0, n, prims, node_of, nodes, flag, tscan, partner);
-    BVH_TRY(hipGetLastError());
-    BVH_TRY(hipMemcpy(&count, counter, 4, hipMemcpyDeviceToHost));   // also the level's barrier for the host
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&count, counter, 4, hipMemcpyDeviceToHost));   // also the level's barrier for the host
     if ((size_t)count > cap) return vpt_set_error(VPT_ERR_HIP, "BVH build produced %d nodes for %d primitives", count, n);
     lb = le, le = count;
     level_begin.push_back(lb);
@@ -326,9 +318,9 @@ extern "C" int vpt_build_bvh(int device, const float* bboxes, int n, vpt_bvh_nod
     if (b > a) hipLaunchKernelGGL(k_pre, blocks(b - a), dim3(TB), 0, 0, a, b, nodes);
   }
   hipLaunchKernelGGL(k_emit, blocks(count), dim3(TB), 0, 0, count, nodes, boxes, out);
-  BVH_TRY(hipGetLastError());
-  BVH_TRY(hipMemcpy(nodes_out, out, (size_t)count * sizeof(vpt_bvh_node), hipMemcpyDeviceToHost));
-  BVH_TRY(hipMemcpy(primitives, prims, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(nodes_out, out, (size_t)count * sizeof(vpt_bvh_node), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(primitives, prims, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   *num_nodes = count;
   return VPT_OK;
 }

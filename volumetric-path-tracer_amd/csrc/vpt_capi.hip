@@ -24,6 +24,8 @@ VPT_K1_SPLIT_INSTANCES(VPT_K1_DECLARE, K_PATH)
 #endif
 #include <rocprim/rocprim.hpp>
 
+#include "vpt_error.h"
+
 // light_prims of the single-leaf mesh lights (vpt_device.h): one thread per (light, primitive of the leaf)
 __global__ void vpt_light_setup_kernel(DScene sc, float4* out) {
   int l = blockIdx.x, k = threadIdx.x;
@@ -115,9 +117,7 @@ static std::string& g_error_text() {   // the message of the last failure on the
   return text;
 }
 
-namespace {
-
-int fail(int code, const char* fmt, ...) {
+int vpt_set_error(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -126,11 +126,8 @@ int fail(int code, const char* fmt, ...) {
   g_error_text() = buf;
   return code;
 }
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return fail(VPT_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));        \
-  } while (0)
+
+namespace {
 
 // host-side float3 helpers for the load-time precomputation (same formulas as the reference)
 struct h3 { float x, y, z; };
@@ -233,17 +230,6 @@ int bvh_depth(const vpt_bvh_node* nodes, int count, int root, int depth, int lim
 
 }  // namespace
 
-// the same for the other translation units of the library (vpt_multi.cpp)
-int vpt_set_error(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_error_text() = buf;
-  return code;
-}
-
 struct vpt_scene {
   int                device = 0;
   DScene             d      = {};
@@ -312,7 +298,7 @@ int upload(vpt_scene* s, const T* host, long long count, const T** out) {
 
 #define REQUIRE(cond, ...)                                      \
   do {                                                          \
-    if (!(cond)) return fail(VPT_ERR_INVALID_ARG, __VA_ARGS__); \
+    if (!(cond)) return vpt_set_error(VPT_ERR_INVALID_ARG, __VA_ARGS__); \
   } while (0)
 
 int check_nodes(const vpt_bvh_node* nodes, long long count, long long nprims, const char* what) {
@@ -474,12 +460,12 @@ void vpt_scene_destroy(vpt_scene* s) {
 }
 
 int vpt_scene_create(const vpt_scene_desc* desc, int device, vpt_scene** out) {
-  if (!desc || !out) return fail(VPT_ERR_INVALID_ARG, "null argument");
+  if (!desc || !out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   if (int rc = validate(*desc)) return rc;
   int ndev = vpt_device_count();
-  if (ndev <= 0) return fail(VPT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(VPT_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
+  if (ndev <= 0) return vpt_set_error(VPT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+  if (device < 0 || device >= ndev) return vpt_set_error(VPT_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
   (void)hipGetLastError();   // start from a clean slate: an error left behind by an unrelated earlier call is not this call's
   HIP_TRY(hipSetDevice(device));
   const vpt_scene_desc& d = *desc;
@@ -568,7 +554,7 @@ int vpt_scene_create(const vpt_scene_desc* desc, int device, vpt_scene** out) {
   s->stack_cap = ((need > 8 ? need : 8) + 3) & ~3;
   const int max_stack_cap = 64 * 1024 / (VPT_BLOCK * (int)sizeof(int));   // 256 entries with VPT_BLOCK = 64
   if (s->stack_cap > max_stack_cap)
-    return fail(VPT_ERR_UNSUPPORTED, "BVH depth %d (scene %d + shapes %d) needs a %d-entry traversal stack; the LDS stack holds %d",
+    return vpt_set_error(VPT_ERR_UNSUPPORTED, "BVH depth %d (scene %d + shapes %d) needs a %d-entry traversal stack; the LDS stack holds %d",
                 need, scene_depth, max_shape_depth, s->stack_cap, max_stack_cap);
   // quad-node traversal: worst case = three pending siblings per quad level of the scene BVH plus of the
   // deepest shape BVH, plus one free entry above the top (the branch-free push stores rejected candidates
@@ -578,7 +564,7 @@ int vpt_scene_create(const vpt_scene_desc* desc, int device, vpt_scene** out) {
   // the group form of the node phase (vpt_mesh_kernel.hip.h: group_nodes) hands a ray's pop floor - the stack depth at instance entry, at
   // most scene_need4 - to its helper lanes in the bits above VPT_FLOOR_SHIFT of one word: every stack position has to fit there
   if ((long long)need4 > (0x7fffffffLL >> VPT_FLOOR_SHIFT))
-    return fail(VPT_ERR_UNSUPPORTED, "quad stack need %d does not fit the traversal's packed pop floor", need4);
+    return vpt_set_error(VPT_ERR_UNSUPPORTED, "quad stack need %d does not fit the traversal's packed pop floor", need4);
   // With the mesh kernel's five parked words per lane (vpt_mesh_kernel.hip.h) a wave takes need4 * 512 + 1280 + 8 bytes of LDS,
   // granted in 1 280-byte steps: up to 22 entries twelve waves fit a CU's 160 KB, with 23 or 24 eleven do - still better than the
   // checked push / pop of the HBM-overflow variant (-7 %), which is for deeper trees only (22 entries in LDS, the rest in HBM).
@@ -669,7 +655,7 @@ int vpt_scene_create(const vpt_scene_desc* desc, int device, vpt_scene** out) {
   }
   {
     const size_t scene_count = scene_wnodes.size();
-    if ((scene_count + shape_wnodes.size()) / 8 >= (1ull << 27)) return fail(VPT_ERR_UNSUPPORTED, "more than 2^27 quad nodes");
+    if ((scene_count + shape_wnodes.size()) / 8 >= (1ull << 27)) return vpt_set_error(VPT_ERR_UNSUPPORTED, "more than 2^27 quad nodes");
     std::vector<float4> wnodes = scene_wnodes;   // one allocation: [scene quad nodes][shape quad nodes]
     wnodes.insert(wnodes.end(), shape_wnodes.begin(), shape_wnodes.end());
     UP(upload(s, wnodes, &D.scene_wnodes));
@@ -877,10 +863,6 @@ int vpt_scene_create(const vpt_scene_desc* desc, int device, vpt_scene** out) {
       }
       D.sdf_bound_cx = (float)c[0], D.sdf_bound_cy = (float)c[1], D.sdf_bound_cz = (float)c[2], D.sdf_bound_r = (float)(rr * 1.01);
     }
-    if (getenv("VPT_NO_EARLY_OUT")) {   // A/B switch for the experiments of DESIGN.md: the marches then run to the reference's own end
-      D.sdf_bound_r = -1;
-      for (int i = 0; i < d.num_sdfs; i++) fn_rec[6 * (size_t)i + 5].w = -1;
-    }
     UP(upload(s, fn_rec, &D.sdf_fn_rec));
     UP(upload(s, grid_rec, &D.sdf_grid_rec));
   }
@@ -979,16 +961,16 @@ static int state_download(const vpt_layout* layout, const void* d_image, const v
 
 int vpt_state_upload(const vpt_layout* layout, const float* image_rgba, const int32_t* hits, const uint64_t* rng,
     void* d_image, void* d_hits, void* d_rng, void* stream) {
-  if (!layout || !image_rgba || !hits || !rng || !d_image || !d_hits || !d_rng) return fail(VPT_ERR_INVALID_ARG, "null argument");
-  if (layout->width <= 0 || layout->height <= 0) return fail(VPT_ERR_INVALID_ARG, "bad layout");
+  if (!layout || !image_rgba || !hits || !rng || !d_image || !d_hits || !d_rng) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (layout->width <= 0 || layout->height <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad layout");
   row_staging rows;
   return state_upload(layout, image_rgba, hits, rng, d_image, d_hits, d_rng, (hipStream_t)stream, rows);
 }
 
 int vpt_state_download(const vpt_layout* layout, const void* d_image, const void* d_hits, const void* d_rng,
     float* image_rgba, int32_t* hits, uint64_t* rng, void* stream) {
-  if (!layout || !image_rgba || !hits || !rng || !d_image || !d_hits || !d_rng) return fail(VPT_ERR_INVALID_ARG, "null argument");
-  if (layout->width <= 0 || layout->height <= 0) return fail(VPT_ERR_INVALID_ARG, "bad layout");
+  if (!layout || !image_rgba || !hits || !rng || !d_image || !d_hits || !d_rng) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (layout->width <= 0 || layout->height <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad layout");
   row_staging rows;
   return state_download(layout, d_image, d_hits, d_rng, image_rgba, hits, rng, (hipStream_t)stream, rows, false);
 }
@@ -1034,19 +1016,15 @@ static int sched_prepare(vpt_scene* s, long long waves, const long long key[10],
   return VPT_OK;
 }
 // order[] for the next launch from the costs the launch just enqueued on `st` will have written
-static float vpt_cost_horizon() {   // launches behind the running average (VPT_COST_HORIZON, calibration)
-  static const float h = [] { const char* e = getenv("VPT_COST_HORIZON"); return e ? (float)atof(e) : 6.0f; }();
-  return h < 1 ? 1 : h;
-}
+static constexpr float k_cost_horizon = 6;   // launches behind the running average
 static int sched_update(vpt_scene* s, long long waves, hipStream_t st, int nsamples = 0) {
   // nsamples > 0: d_cost holds the durations of a launch over that many samples: they enter the running average, whose order the next launch takes;
   // nsamples == 0: d_cost holds predictions (a fresh split table): they start a new average
-  static const bool averaging = [] { const char* e = getenv("VPT_COST_AVERAGE"); return !e || atoi(e) != 0; }();
-  if (nsamples <= 0 || !averaging) s->cost_weight = 0;
+  if (nsamples <= 0) s->cost_weight = 0;
   const float n = nsamples > 0 ? (float)nsamples : 1.0f;
   hipLaunchKernelGGL(vpt_cost_average_kernel, dim3((unsigned)((waves + 255) / 256)), dim3(256), 0, st, s->d_cost, s->d_cost_avg, s->d_cost_key, (int)waves, n, s->cost_weight);
   HIP_TRY(hipGetLastError());
-  if (nsamples > 0 && averaging) s->cost_weight = std::min(s->cost_weight + n, vpt_cost_horizon() * n);   // the last few launches
+  if (nsamples > 0) s->cost_weight = std::min(s->cost_weight + n, k_cost_horizon * n);   // the last few launches
   size_t bytes = s->sort_temp_bytes;
   HIP_TRY(rocprim::radix_sort_pairs_desc(s->sort_temp, bytes, s->d_cost_key, s->d_cost_sorted, s->d_iota, s->d_order, (size_t)waves, 0, 32, st));
   HIP_TRY(hipEventRecord(s->ev_order, st));
@@ -1071,13 +1049,8 @@ struct launch_ctx {
   ulonglong2*       rng;
   stack_cfg         stack;
 };
-static void schedule_key(const launch_ctx& L, long long key[10]) {
-  const DParams& pr = L.pr;
-  long long k[10] = {pr.nslots, pr.width, pr.height, L.params->shader, L.params->camera, L.params->bounces, pr.rank, pr.nranks, pr.tile_w, pr.tile_h};
-  memcpy(key, k, sizeof(k));
-}
 
-// ---- tile splitting (K1) --------------------------------------------------------------------------------------------
+// ---- tile splitting (K1, K2) ----------------------------------------------------------------------------------------
 // A wave runs all samples of its 64 pixels one after the other, so a launch cannot be shorter than its costliest tile.
 // On one GPU that tile (273 ms of a 280 ms launch on 03_volume) is level with total work / wave slots and nothing is
 // gained by shortening it; once the frame is shared among N GPUs the work per GPU falls with N and the chain does not.
@@ -1089,28 +1062,10 @@ static void schedule_key(const launch_ctx& L, long long key[10]) {
 // camera from the per-tile costs of an unsplit launch, when the launch is short of waves: the frame is shared among ranks
 // or holds fewer than three tiles per wave slot (1280x533 on one MI355X has 3.5 and never gains).  Pixels keep their own RNG streams and accumulators, so the result does
 // not depend on it.
-static double split_gain[7] = {1.0, 0.75, 0.57, 0.44, 0.34, 0.27, 0.20};   // duration of a 64 >> k lane wave of a costly tile / its full wave (round 4's
-                                                                           // kernel, whose partly filled waves use their empty lanes as helpers: 0.753 / 0.566 / 0.436 / 0.343 measured, was 0.81 / 0.62 / 0.45 / 0.35)
-static double split_gain_k2[7] = {1.0, 0.82, 0.67, 0.63, 0.60, 0.58, 0.56};   // the same for K2 (implicit shaders): 0.82 / 0.67 / 0.63 measured on 06_gridsdf_full (profiles/r04_k2_lane_histogram.txt), the rest extrapolated
-static double split_load0 = 0.46, split_margin = 0.98;   // load_factor's intercept; a split has to beat the unsplit launch by this factor
-static void split_tuning() {   // VPT_SPLIT_TUNE="g1,g2,g3,g4,g5,g6,load0,margin" (calibration runs only)
-  static bool once = [] {
-    if (const char* e = getenv("VPT_K2_SPLIT_TUNE")) {   // the same for the implicit kernels' table: "g1,g2,g3,g4,g5,g6"
-      double v[6];
-      if (sscanf(e, "%lf,%lf,%lf,%lf,%lf,%lf", v, v + 1, v + 2, v + 3, v + 4, v + 5) == 6)
-        for (int i = 0; i < 6; i++) split_gain_k2[i + 1] = v[i];
-    }
-    if (const char* e = getenv("VPT_SPLIT_TUNE")) {
-      double v[8];
-      if (sscanf(e, "%lf,%lf,%lf,%lf,%lf,%lf,%lf,%lf", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7) == 8) {
-        for (int i = 0; i < 6; i++) split_gain[i + 1] = v[i];
-        split_load0 = v[6], split_margin = v[7];
-      }
-    }
-    return true;
-  }();
-  (void)once;
-}
+static constexpr double split_gain[7] = {1.0, 0.75, 0.57, 0.44, 0.34, 0.27, 0.20};   // duration of a 64 >> k lane wave of a costly tile / its full wave (round 4's
+                                                                                    // kernel, whose partly filled waves use their empty lanes as helpers: 0.753 / 0.566 / 0.436 / 0.343 measured, was 0.81 / 0.62 / 0.45 / 0.35)
+static constexpr double split_gain_k2[7] = {1.0, 0.82, 0.67, 0.63, 0.60, 0.58, 0.56};   // the same for K2 (implicit shaders): 0.82 / 0.67 / 0.63 measured on 06_gridsdf_full (profiles/r04_k2_lane_histogram.txt), the rest extrapolated
+static constexpr double split_load0 = 0.46, split_margin = 0.98;   // load_factor's intercept; a split has to beat the unsplit launch by this factor
 static int split_mode() {   // VPT_SPLIT: 0 never, 1 always consider, unset: consider when the launch is short of waves
   static int v = [] { const char* e = getenv("VPT_SPLIT"); return e ? atoi(e) : -1; }();
   return v;
@@ -1120,7 +1075,7 @@ static int split_forced_k() {   // VPT_SPLIT_K (calibration): every tile as 2^k 
   return v;
 }
 // lane table and predicted wave costs for the split factors s->h_split_k; part_cost[t] = expected duration of one wave of tile t
-static int build_split_table(vpt_scene* s, const DParams& pr, const std::vector<double>& part_cost, hipStream_t st) {
+static int build_split_table(vpt_scene* s, const std::vector<double>& part_cost, hipStream_t st) {
   const std::vector<int>& k = s->h_split_k;
   const int ntiles = (int)k.size();
   long long waves = 0;
@@ -1148,8 +1103,6 @@ static int build_split_table(vpt_scene* s, const DParams& pr, const std::vector<
   HIP_TRY(hipMemcpy(s->d_lane_slot, table.data(), table.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(s->d_cost, wcost.data(), wcost.size() * 4, hipMemcpyHostToDevice));
   s->split_waves = (int)waves, s->split_tiles = nsplit;
-  if (getenv("VPT_SPLIT_VERBOSE"))
-    fprintf(stderr, "[vpt] split: %d of %d tiles -> %lld waves on %d slots (rank %d of %d)\n", nsplit, ntiles, waves, s->wave_slots_k1, pr.rank, pr.nranks);
   return sched_update(s, waves, st);   // order of the split launch from the predicted costs; measured ones take over afterwards
 }
 // makespan of longest-first list scheduling of `costs` (any order) on `slots` machines: what the hardware's dispatch of
@@ -1169,9 +1122,9 @@ static double lpt_makespan(std::vector<double>& costs, int slots) {
 // A wave also runs faster when fewer waves share its SIMD: the costliest tile of 03_volume takes 273 ms with all 3 072
 // slots busy and 187 ms when 1 340 waves are resident: duration ~ (0.46 + 0.54 * occupancy) * duration at 1
 static double load_factor(double waves, int slots) { return split_load0 + (1 - split_load0) * std::min(1.0, waves / slots); }
-static int decide_split(vpt_scene* s, const DParams& pr, int ntiles, int slots, hipStream_t st, const double* split_gain = ::split_gain) {
+// gain: split_gain (K1) or split_gain_k2 (K2)
+static int decide_split(vpt_scene* s, int ntiles, int slots, hipStream_t st, const double* gain) {
   s->split_decided = true, s->split_waves = 0, s->split_tiles = 0;
-  split_tuning();
   HIP_TRY(hipStreamSynchronize(st));
   std::vector<unsigned> cost((size_t)ntiles);
   HIP_TRY(hipMemcpy(cost.data(), s->d_cost, cost.size() * 4, hipMemcpyDeviceToHost));
@@ -1188,9 +1141,9 @@ static int decide_split(vpt_scene* s, const DParams& pr, int ntiles, int slots, 
     for (int t = 0; t < ntiles; t++) {
       if (cost[t] == 0) continue;
       int kt = 0;
-      while (kt < 6 && cost[t] * split_gain[kt] > S) kt++;
+      while (kt < 6 && cost[t] * gain[kt] > S) kt++;
       if (apply) k[t] = kt;
-      for (int p = 0; p < (1 << kt); p++) waves.push_back(cost[t] * split_gain[kt]);
+      for (int p = 0; p < (1 << kt); p++) waves.push_back(cost[t] * gain[kt]);
     }
     double f = load_factor((double)waves.size(), slots) / measured_at;
     for (double& w : waves) w *= f;
@@ -1201,75 +1154,75 @@ static int decide_split(vpt_scene* s, const DParams& pr, int ntiles, int slots, 
   } else {
     double best_S = cmax, best = plan(cmax, false);
     for (int i = 1; i <= 24; i++) {   // candidates from the costliest tile down to its 1-lane duration
-      double S = cmax * std::pow(split_gain[6], i / 24.0), span = plan(S, false);
+      double S = cmax * std::pow(gain[6], i / 24.0), span = plan(S, false);
       if (span < best * split_margin) best = span, best_S = S;   // a split has to pay at least 2 %
     }
     plan(best_S, true);
   }
   std::vector<double> part((size_t)ntiles);
-  for (int t = 0; t < ntiles; t++) part[t] = cost[t] * split_gain[k[t]];
-  return build_split_table(s, pr, part, st);
+  for (int t = 0; t < ntiles; t++) part[t] = cost[t] * gain[k[t]];
+  return build_split_table(s, part, st);
 }
 
-// K1 (mesh shaders).  Longest-wave-first order from the costs of the previous launch on this layout; without
-// them a pilot launch over 1/64 of the call's samples (1..16) measures them first - same arithmetic, batching is exact.
-template <int K>
-static int launch_mesh(const launch_ctx& L) {
-  vpt_scene* s = L.s;
-#if defined(VPT_EXPERIMENT_ONLY_K2)   // experiment builds (make variant): only the kernels under study are compiled (minutes -> seconds)
-  return fail(VPT_ERR_UNSUPPORTED, "this experiment build holds the implicit kernels only");
-#else
-#if defined(VPT_EXPERIMENT_ONLY_VOLPATH)
-  if (K != K_VOLPATH) return fail(VPT_ERR_UNSUPPORTED, "this experiment build holds the volpathtrace kernel only");
-#endif
-  long long key[10];
-  schedule_key(L, key);
+// The launch loop of K1 and K2.  Longest-wave-first order from the costs of the previous launch on this layout; without them
+// a pilot launch over 1/64 of the call's samples (1..16) measures them first - same arithmetic, batching is exact (K2 in tile
+// order: a first call ran at 216 against 302 Msamples/s on 06_gridsdf).  may_split / slots / gain: the kernel's tile-splitting
+// policy (above); launch(is_pilot, grid, pr, sch) launches the kernel instance for the part.
+template <typename Launch>
+static int run_launches(const launch_ctx& L, bool may_split, int slots, const double* gain, Launch&& launch) {
+  vpt_scene*      s = L.s;
+  const DParams&  p = L.pr;
+  const long long key[10] = {p.nslots, p.width, p.height, L.params->shader, L.params->camera, L.params->bounces, p.rank, p.nranks, p.tile_w, p.tile_h};
   if (int rc = sched_prepare(s, std::max<long long>(L.grid.x, s->split_waves), key, L.st)) return rc;
   if (int rc = sched_wait(s, L.st)) return rc;
-  size_t lds = (size_t)s->stack_lds4 * 2 * VPT_BLOCK * sizeof(int) + 5 * VPT_BLOCK * sizeof(float);   // (ref, t0) pairs + the parked words
-  int n = L.pr.nsamples, pilot = n / 64 < 1 ? 1 : n / 64 > 16 ? 16 : n / 64;
+  int n = p.nsamples, pilot = n / 64 < 1 ? 1 : n / 64 > 16 ? 16 : n / 64;
   int parts[2] = {(!s->order_valid && n >= 16) ? pilot : n, 0};
   parts[1] = n - parts[0];
-  const bool may_split = !L.stack.spill && (split_mode() == 1 || split_forced_k() >= 0 ||
-                                            (split_mode() < 0 && (L.pr.nranks > 1 || (long long)L.grid.x < 3ll * s->wave_slots_k1)));
   for (int part = 0; part < 2 && parts[part] > 0; part++) {
     DParams pr  = L.pr;
     pr.nsamples = parts[part];
-    bool is_pilot = parts[1] > 0 && part == 0;
+    const bool is_pilot = parts[1] > 0 && part == 0;
     // the costs of an unsplit launch over at least 8 samples decide, once, whether tiles are split from now on
     if (may_split && !s->split_decided && s->order_valid && s->full_costs) {
       // the decision waits for the stream and reads costs back on the host: that pause is bracketed by its own event pair and
       // subtracted by vpt_last_kernel_ms (a pilot launch that ran before it in this call stays counted)
       HIP_TRY(hipEventRecord(s->ev_host0, L.st));
-      if (int rc = decide_split(s, pr, (int)L.grid.x, s->wave_slots_k1, L.st)) return rc;
+      if (int rc = decide_split(s, (int)L.grid.x, slots, L.st, gain)) return rc;
       HIP_TRY(hipEventRecord(s->ev_host1, L.st));
       s->host_pause = true;
     }
     dim3 grid = s->split_waves > 0 ? dim3((unsigned)s->split_waves) : L.grid;
     sched_cfg sch = {s->order_valid ? s->d_order : nullptr, s->d_cost, s->split_waves > 0 ? s->d_lane_slot : nullptr};
-    // the instance compiled for the features this scene has (vpt_scene.hip.h: VPT_FEAT_*)
-    const int need = getenv("VPT_NO_LEAN") ? VPT_FEAT_ALL : s->light_features;
+    launch(is_pilot, grid, pr, sch);
+    if (s->split_waves == 0) s->full_costs = pr.nsamples >= 8;   // d_cost now holds per-tile durations over enough samples (a pilot of a call with >= 512 samples counts)
+    s->last_waves = (int)grid.x;
+    if (int rc = sched_update(s, grid.x, L.st, pr.nsamples)) return rc;
+  }
+  return VPT_OK;
+}
+
+// K1 (mesh shaders)
+template <int K>
+static int launch_mesh(const launch_ctx& L) {
+#if defined(VPT_EXPERIMENT_ONLY_K2)   // experiment builds (make variant): only the kernels under study are compiled (minutes -> seconds)
+  return vpt_set_error(VPT_ERR_UNSUPPORTED, "this experiment build holds the implicit kernels only");
+#else
+  vpt_scene* s = L.s;
+  size_t lds = (size_t)s->stack_lds4 * 2 * VPT_BLOCK * sizeof(int) + 5 * VPT_BLOCK * sizeof(float);   // (ref, t0) pairs + the parked words
+  const bool may_split = !L.stack.spill && (split_mode() == 1 || split_forced_k() >= 0 ||
+                                            (split_mode() < 0 && (L.pr.nranks > 1 || (long long)L.grid.x < 3ll * s->wave_slots_k1)));
+  // the instance compiled for the features this scene has (vpt_scene.hip.h: VPT_FEAT_*)
+  const int need = getenv("VPT_NO_LEAN") ? VPT_FEAT_ALL : s->light_features;
+  return run_launches(L, may_split, s->wave_slots_k1, split_gain, [&](bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, L.block, lds, L.st, s->d, pr, L.img, L.hit, L.rng, L.stack, sch); };
     auto launch_feat = [&](auto feat) {
       constexpr int F = decltype(feat)::value;
-#if defined(VPT_EXPERIMENT_ONLY_VOLPATH)   // experiment builds: the pilot runs the same instance (one kernel less to compile)
-      if (L.stack.spill) launch(vpt_mesh_kernel<K, true, F>);
-      else launch(vpt_mesh_kernel<K, false, F>);
-#else
       if (is_pilot && L.stack.spill) launch(vpt_mesh_pilot_kernel<K, true, F>);
       else if (is_pilot) launch(vpt_mesh_pilot_kernel<K, false, F>);
       else if (L.stack.spill) launch(vpt_mesh_kernel<K, true, F>);
       else launch(vpt_mesh_kernel<K, false, F>);
-#endif
     };
     // three instances: single-leaf mesh lights only / + emissive meshes with a BVH / everything (SDF lights too)
-#if defined(VPT_EXPERIMENT_ONLY_VOLPATH)
-    if (need != VPT_FEAT_SMALL_LIGHTS && (need & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SDF_LIGHTS)) != 0) return fail(VPT_ERR_UNSUPPORTED, "this experiment build holds the lean instance only");
-    if (s->d.tri_prims) {
-      if (L.stack.spill) launch(vpt_mesh_kernel<K, true, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_COMPACT_TRIS>);
-      else launch(vpt_mesh_kernel<K, false, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_COMPACT_TRIS>);
-    } else launch_feat(std::integral_constant<int, VPT_FEAT_SMALL_LIGHTS>{});
-#else
     // (+ the compact-record form of the first for the two path tracers on scenes of triangles; the pilot runs on the general records)
     if ((K == K_VOLPATH || K == K_PATH) && (need & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SDF_LIGHTS)) == 0 && s->d.tri_prims && !is_pilot) {
       if constexpr (K == K_VOLPATH || K == K_PATH) {
@@ -1279,76 +1232,39 @@ static int launch_mesh(const launch_ctx& L) {
     } else if ((need & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SDF_LIGHTS)) == 0) launch_feat(std::integral_constant<int, VPT_FEAT_SMALL_LIGHTS>{});
     else if ((need & VPT_FEAT_SDF_LIGHTS) == 0) launch_feat(std::integral_constant<int, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_LARGE_LIGHTS>{});
     else launch_feat(std::integral_constant<int, VPT_FEAT_ALL>{});
-#endif
-    if (s->split_waves == 0) s->full_costs = pr.nsamples >= 8;   // d_cost now holds per-tile durations over enough samples (a pilot of a call with >= 512 samples counts)
-    s->last_waves = (int)grid.x;
-    if (int rc = sched_update(s, grid.x, L.st, pr.nsamples)) return rc;
-  }
-  return VPT_OK;
+  });
 #endif
 }
-// K2 (implicit shaders): same schedule; without costs of a previous launch on this layout a pilot launch over 1/64 of the call's
-// samples (1..16) measures them first, as for K1 (in tile order a first call ran at 216 against 302 Msamples/s on 06_gridsdf)
+// K2 (implicit shaders).  Tile splitting is considered on every layout (unless VPT_SPLIT=0): K2's launches hold two waves per wave
+// slot at 1280 x 533, so the longest-first schedule ends well above both of its bounds (226 ms against a longest wave of 192 and 191
+// of work per slot); the costliest tiles as partly filled waves - whose scene rounds run in the group form: four lanes per ray - pack better.
 template <int K>
 static int launch_implicit(const launch_ctx& L) {
-  vpt_scene* s = L.s;
-#if defined(VPT_EXPERIMENT_ONLY_VOLPATH)
-  return fail(VPT_ERR_UNSUPPORTED, "this experiment build holds the volpathtrace kernel only");
-#else
-  long long key[10];
-  schedule_key(L, key);
-  if (int rc = sched_prepare(s, std::max<long long>(L.grid.x, s->split_waves), key, L.st)) return rc;
-  if (int rc = sched_wait(s, L.st)) return rc;
-  size_t    lds = (size_t)s->stack_cap * VPT_BLOCK * sizeof(int) +                                      // refs-only stack
+  vpt_scene* s   = L.s;
+  size_t     lds = (size_t)s->stack_cap * VPT_BLOCK * sizeof(int) +                                      // refs-only stack
                (6 * (size_t)s->d.num_sdfs + 7 * (size_t)s->d.num_vol_instances) * sizeof(float4);       // the SDF records
-  if (lds > 64 * 1024) return fail(VPT_ERR_UNSUPPORTED, "scene has too many SDFs for the implicit kernel's LDS copy of their records (%d + %d)", s->d.num_sdfs, s->d.num_vol_instances);
-  s->last_waves = (int)L.grid.x;
+  if (lds > 64 * 1024) return vpt_set_error(VPT_ERR_UNSUPPORTED, "scene has too many SDFs for the implicit kernel's LDS copy of their records (%d + %d)", s->d.num_sdfs, s->d.num_vol_instances);
   unsigned long long watchdog_ticks = VPT_K2_WATCHDOG_TICKS;
   if (const char* e = getenv("VPT_K2_WATCHDOG_MS")) watchdog_ticks = strtoull(e, nullptr, 10) * 100000ull;   // tests of the error path
   // the instance for the features this scene's lights have (VPT_FEAT_*): SDF scenes without emissive meshes run one without the mesh-light walks
   const bool lean = (s->light_features & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SMALL_LIGHTS)) == 0 && !getenv("VPT_NO_LEAN");
-  int n = L.pr.nsamples, pilot = n / 64 < 1 ? 1 : n / 64 > 16 ? 16 : n / 64;
-  int parts[2] = {(!s->order_valid && n >= 16 && !getenv("VPT_K2_NO_PILOT")) ? pilot : n, 0};
-  parts[1] = n - parts[0];
-  // tile splitting as for K1 (above): K2's launches hold two waves per wave slot at 1280 x 533, so the longest-first schedule ends well
-  // above both of its bounds (226 ms against a longest wave of 192 and 191 of work per slot); the costliest tiles as partly filled waves -
-  // whose scene rounds run in the group form: four lanes per ray - pack better.  VPT_K2_SPLIT=0 switches it off.
-  static const bool k2_split = [] { const char* e = getenv("VPT_K2_SPLIT"); return !e || atoi(e) != 0; }();
-  const bool may_split = k2_split && split_mode() != 0;
-  for (int part = 0; part < 2 && parts[part] > 0; part++) {
-    DParams pr  = L.pr;
-    pr.nsamples = parts[part];
-    const bool is_pilot = parts[1] > 0 && part == 0;
-    if (may_split && !s->split_decided && s->order_valid && s->full_costs) {
-      HIP_TRY(hipEventRecord(s->ev_host0, L.st));
-      if (int rc = decide_split(s, pr, (int)L.grid.x, s->wave_slots_k2, L.st, split_gain_k2)) return rc;
-      HIP_TRY(hipEventRecord(s->ev_host1, L.st));
-      s->host_pause = true;
-    }
-    dim3 grid = s->split_waves > 0 ? dim3((unsigned)s->split_waves) : L.grid;
-    sched_cfg sch = {s->order_valid ? s->d_order : nullptr, s->d_cost, s->split_waves > 0 ? s->d_lane_slot : nullptr};
+  return run_launches(L, split_mode() != 0, s->wave_slots_k2, split_gain_k2, [&](bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, L.block, lds, L.st, s->d, pr, L.img, L.hit, L.rng, s->stack_cap, sch, s->d_watchdog, watchdog_ticks); };
     if (is_pilot && lean) launch(vpt_render_pilot_kernel<K, VPT_FEAT_SDF_LIGHTS>);
     else if (is_pilot) launch(vpt_render_pilot_kernel<K, VPT_FEAT_ALL>);
     else if (lean) launch(vpt_render_kernel<K, VPT_FEAT_SDF_LIGHTS>);
     else launch(vpt_render_kernel<K, VPT_FEAT_ALL>);
-    if (s->split_waves == 0) s->full_costs = pr.nsamples >= 8;
-    s->last_waves = (int)grid.x;
-    if (int rc = sched_update(s, grid.x, L.st, pr.nsamples)) return rc;
-  }
-  return VPT_OK;
-#endif
+  });
 }
-
 
 extern "C" {
 
 int vpt_render_device(vpt_scene* s, const vpt_params* params, const vpt_layout* layout, int nsamples, void* d_image,
     void* d_hits, void* d_rng, void* stream) {
-  if (!s || !params || !layout || !d_image || !d_hits || !d_rng) return fail(VPT_ERR_INVALID_ARG, "null argument");
-  if (params->shader < 0 || params->shader > VPT_SHADER_IMPLICIT_NORMAL) return fail(VPT_ERR_UNKNOWN_SHADER, "sampler unknown");
-  if (params->camera < 0 || params->camera >= s->d.num_cameras) return fail(VPT_ERR_INVALID_ARG, "camera %d out of range", params->camera);
-  if (nsamples < 0 || params->bounces < 0) return fail(VPT_ERR_INVALID_ARG, "negative sample/bounce count");
+  if (!s || !params || !layout || !d_image || !d_hits || !d_rng) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (params->shader < 0 || params->shader > VPT_SHADER_IMPLICIT_NORMAL) return vpt_set_error(VPT_ERR_UNKNOWN_SHADER, "sampler unknown");
+  if (params->camera < 0 || params->camera >= s->d.num_cameras) return vpt_set_error(VPT_ERR_INVALID_ARG, "camera %d out of range", params->camera);
+  if (nsamples < 0 || params->bounces < 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "negative sample/bounce count");
   if (nsamples == 0) return VPT_OK;
   DParams pr;
   if (int rc = make_dparams(params, layout, nsamples, pr)) return rc;
@@ -1383,14 +1299,14 @@ int vpt_render_device(vpt_scene* s, const vpt_params* params, const vpt_layout* 
 }
 
 int vpt_scene_record_bytes(const vpt_scene* s, int* leaf_bytes, int* attribute_bytes) {
-  if (!s || !leaf_bytes || !attribute_bytes) return fail(VPT_ERR_INVALID_ARG, "null argument");
+  if (!s || !leaf_bytes || !attribute_bytes) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   *leaf_bytes = s->d.tri_prims ? 48 : 64, *attribute_bytes = s->d.tri_attrs ? 64 : 96;
   return VPT_OK;
 }
 
 int vpt_last_wave_costs(vpt_scene* s, unsigned* ticks, int capacity, int* count) {
-  if (!s || !count || capacity < 0 || (capacity > 0 && !ticks)) return fail(VPT_ERR_INVALID_ARG, "bad argument");
-  if (!s->timed) return fail(VPT_ERR_INVALID_ARG, "no launch recorded");
+  if (!s || !count || capacity < 0 || (capacity > 0 && !ticks)) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
+  if (!s->timed) return vpt_set_error(VPT_ERR_INVALID_ARG, "no launch recorded");
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipEventSynchronize(s->ev1));
   long long n = s->last_waves;   // waves of the last launch
@@ -1402,17 +1318,17 @@ int vpt_last_wave_costs(vpt_scene* s, unsigned* ticks, int capacity, int* count)
 
 // synchronous: waves of the implicit kernel that hit their watchdog since the scene was created (a defect, never a workload)
 int vpt_check_watchdog(vpt_scene* s) {
-  if (!s) return fail(VPT_ERR_INVALID_ARG, "null argument");
+  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   HIP_TRY(hipSetDevice(s->device));
   unsigned n = 0;
   HIP_TRY(hipMemcpy(&n, s->d_watchdog, 4, hipMemcpyDeviceToHost));
-  if (n) return fail(VPT_ERR_HIP, "%u wave(s) of the implicit kernel gave up after their watchdog time: the result is incomplete", n);
+  if (n) return vpt_set_error(VPT_ERR_HIP, "%u wave(s) of the implicit kernel gave up after their watchdog time: the result is incomplete", n);
   return VPT_OK;
 }
 
 int vpt_last_kernel_ms(vpt_scene* s, float* ms) {
-  if (!s || !ms) return fail(VPT_ERR_INVALID_ARG, "null argument");
-  if (!s->timed) return fail(VPT_ERR_INVALID_ARG, "no launch recorded");
+  if (!s || !ms) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (!s->timed) return vpt_set_error(VPT_ERR_INVALID_ARG, "no launch recorded");
   HIP_TRY(hipEventSynchronize(s->ev1));
   HIP_TRY(hipEventElapsedTime(ms, s->ev0, s->ev1));
   if (s->host_pause) {
@@ -1424,12 +1340,12 @@ int vpt_last_kernel_ms(vpt_scene* s, float* ms) {
 }
 
 int vpt_resolve_device(const vpt_layout* layout, const void* d_tiles_all_ranks, int samples, void* d_image_rowmajor, void* stream) {
-  if (!layout || !d_tiles_all_ranks || !d_image_rowmajor || samples <= 0) return fail(VPT_ERR_INVALID_ARG, "bad argument");
+  if (!layout || !d_tiles_all_ranks || !d_image_rowmajor || samples <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
   DParams    pr;
   vpt_params dummy = {};
   if (int rc = make_dparams(&dummy, layout, 0, pr)) return rc;
   long long total = (long long)pr.nslots * pr.nranks;
-  if (total >= (1LL << 31)) return fail(VPT_ERR_INVALID_ARG, "image too large");
+  if (total >= (1LL << 31)) return vpt_set_error(VPT_ERR_INVALID_ARG, "image too large");
   int blocks = (int)((total + 255) / 256);
   hipLaunchKernelGGL(vpt_resolve_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pr, (const float4*)d_tiles_all_ranks,
       1.0f / (float)samples, (float4*)d_image_rowmajor);
@@ -1438,12 +1354,12 @@ int vpt_resolve_device(const vpt_layout* layout, const void* d_tiles_all_ranks, 
 }
 
 int vpt_resolve_srgb8_device(const vpt_layout* layout, const void* d_tiles_all_ranks, int samples, void* d_rgba8_rowmajor, void* stream) {
-  if (!layout || !d_tiles_all_ranks || !d_rgba8_rowmajor || samples <= 0) return fail(VPT_ERR_INVALID_ARG, "bad argument");
+  if (!layout || !d_tiles_all_ranks || !d_rgba8_rowmajor || samples <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
   DParams    pr;
   vpt_params dummy = {};
   if (int rc = make_dparams(&dummy, layout, 0, pr)) return rc;
   long long total = (long long)pr.nslots * pr.nranks;
-  if (total >= (1LL << 31)) return fail(VPT_ERR_INVALID_ARG, "image too large");
+  if (total >= (1LL << 31)) return vpt_set_error(VPT_ERR_INVALID_ARG, "image too large");
   int blocks = (int)((total + 255) / 256);
   hipLaunchKernelGGL(vpt_resolve_srgb8_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pr, (const float4*)d_tiles_all_ranks,
       1.0f / (float)samples, (uchar4*)d_rgba8_rowmajor);
@@ -1453,9 +1369,9 @@ int vpt_resolve_srgb8_device(const vpt_layout* layout, const void* d_tiles_all_r
 
 int vpt_render(vpt_scene* s, const vpt_params* params, int nsamples, int width, int height, float* image_rgba,
     int32_t* hits, uint64_t* rng, int* samples_io) {
-  if (!s || !params || !image_rgba || !hits || !rng || !samples_io) return fail(VPT_ERR_INVALID_ARG, "null argument");
-  if (width <= 0 || height <= 0) return fail(VPT_ERR_INVALID_ARG, "bad image size");
-  if (params->shader < 0 || params->shader > VPT_SHADER_IMPLICIT_NORMAL) return fail(VPT_ERR_UNKNOWN_SHADER, "sampler unknown");
+  if (!s || !params || !image_rgba || !hits || !rng || !samples_io) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (width <= 0 || height <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad image size");
+  if (params->shader < 0 || params->shader > VPT_SHADER_IMPLICIT_NORMAL) return vpt_set_error(VPT_ERR_UNKNOWN_SHADER, "sampler unknown");
   int todo = params->samples - *samples_io;   // no-op once reached, yocto_pathtrace.cpp:1055
   if (nsamples < todo) todo = nsamples;
   if (todo <= 0) return VPT_OK;
@@ -1487,23 +1403,23 @@ int vpt_render(vpt_scene* s, const vpt_params* params, int nsamples, int width, 
 }
 
 int vpt_selftest_reciprocal(int device, unsigned long long* mismatches, unsigned long long* fallbacks) {
-  if (!mismatches || !fallbacks) return fail(VPT_ERR_INVALID_ARG, "null argument");
+  if (!mismatches || !fallbacks) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   HIP_TRY(hipSetDevice(device));
   unsigned long long* d = nullptr;
   HIP_TRY(hipMalloc((void**)&d, 16));
   HIP_TRY(hipMemset(d, 0, 16));
   hipLaunchKernelGGL(vpt_reciprocal_selftest_kernel, dim3(4096), dim3(256), 0, 0, d);
   unsigned long long h[2] = {0, 0};
-  int rc = hipMemcpy(h, d, 16, hipMemcpyDeviceToHost) == hipSuccess ? VPT_OK : fail(VPT_ERR_HIP, "reciprocal self-test failed to run");
+  int rc = hipMemcpy(h, d, 16, hipMemcpyDeviceToHost) == hipSuccess ? VPT_OK : vpt_set_error(VPT_ERR_HIP, "reciprocal self-test failed to run");
   (void)hipFree(d);
   *mismatches = h[0], *fallbacks = h[1];
   return rc;
 }
 
 int vpt_intersect(vpt_scene* s, int n, const float* rays, int instance, int32_t* ids, float* uvt) {
-  if (!s || !rays || !ids || !uvt || n < 0) return fail(VPT_ERR_INVALID_ARG, "bad argument");
-  if (instance < -1 || instance >= s->d.num_instances) return fail(VPT_ERR_INVALID_ARG, "instance %d out of range", instance);
-  if (instance >= 0 && s->h_slot_of[(size_t)instance] < 0) return fail(VPT_ERR_INVALID_ARG, "instance %d is not in the scene BVH", instance);
+  if (!s || !rays || !ids || !uvt || n < 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
+  if (instance < -1 || instance >= s->d.num_instances) return vpt_set_error(VPT_ERR_INVALID_ARG, "instance %d out of range", instance);
+  if (instance >= 0 && s->h_slot_of[(size_t)instance] < 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "instance %d is not in the scene BVH", instance);
   if (n == 0) return VPT_OK;
   HIP_TRY(hipSetDevice(s->device));
   float* d_rays = nullptr;
@@ -1513,7 +1429,7 @@ int vpt_intersect(vpt_scene* s, int n, const float* rays, int instance, int32_t*
   if (hipMalloc((void**)&d_rays, (size_t)n * 24) != hipSuccess || hipMalloc((void**)&d_ids, (size_t)n * 8) != hipSuccess ||
       hipMalloc((void**)&d_uvt, (size_t)n * 12) != hipSuccess || hipMemcpy(d_rays, rays, (size_t)n * 24, hipMemcpyHostToDevice) != hipSuccess) {
     release();
-    return fail(VPT_ERR_HIP, "vpt_intersect: device buffers");
+    return vpt_set_error(VPT_ERR_HIP, "vpt_intersect: device buffers");
   }
   int       blocks = (n + VPT_BLOCK - 1) / VPT_BLOCK;
   stack_cfg stack;
@@ -1527,7 +1443,7 @@ int vpt_intersect(vpt_scene* s, int n, const float* rays, int instance, int32_t*
   else launch(vpt_intersect_kernel<false, false>);
   bool ok = hipMemcpy(ids, d_ids, (size_t)n * 8, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(uvt, d_uvt, (size_t)n * 12, hipMemcpyDeviceToHost) == hipSuccess;
   release();
-  return ok ? VPT_OK : fail(VPT_ERR_HIP, "vpt_intersect failed to run");
+  return ok ? VPT_OK : vpt_set_error(VPT_ERR_HIP, "vpt_intersect failed to run");
 }
 
 // ---- known-answer-test entry points (include/vpt_kat.h) ------------------------------------------------------------
@@ -1535,14 +1451,14 @@ static const int k_kat_strides[VPT_KAT_OP_COUNT][2] = {{19, 22}, {15, 10}, {4, 4
     {6, 1}, {4, 3}, {6, 3}, {7, 4}, {4, 1}, {4, 1}};
 
 int vpt_kat_strides(int op, int* in_stride, int* out_stride) {
-  if (op < 0 || op >= VPT_KAT_OP_COUNT || !in_stride || !out_stride) return fail(VPT_ERR_INVALID_ARG, "unknown KAT op %d", op);
+  if (op < 0 || op >= VPT_KAT_OP_COUNT || !in_stride || !out_stride) return vpt_set_error(VPT_ERR_INVALID_ARG, "unknown KAT op %d", op);
   *in_stride = k_kat_strides[op][0], *out_stride = k_kat_strides[op][1];
   return VPT_OK;
 }
 
 int vpt_kat(vpt_scene* s, int op, int iparam, int n, const float* in, float* out) {
-  if (!s || n < 0 || (n > 0 && (!in || !out))) return fail(VPT_ERR_INVALID_ARG, "bad argument");
-  if (op < 0 || op >= VPT_KAT_OP_COUNT) return fail(VPT_ERR_INVALID_ARG, "unknown KAT op %d", op);
+  if (!s || n < 0 || (n > 0 && (!in || !out))) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
+  if (op < 0 || op >= VPT_KAT_OP_COUNT) return vpt_set_error(VPT_ERR_INVALID_ARG, "unknown KAT op %d", op);
   if (n == 0) return VPT_OK;
   const int si = k_kat_strides[op][0], so = k_kat_strides[op][1];
   const DScene& D = s->d;
@@ -1570,10 +1486,10 @@ int vpt_kat(vpt_scene* s, int op, int iparam, int n, const float* in, float* out
       case VPT_KAT_SDF_FUNCTION: ok = id_ok(a[0], D.num_sdfs); break;
       default: break;
     }
-    if (!ok) return fail(VPT_ERR_INVALID_ARG, "KAT op %d record %d: id out of range", op, i);
+    if (!ok) return vpt_set_error(VPT_ERR_INVALID_ARG, "KAT op %d record %d: id out of range", op, i);
   }
   if ((op == VPT_KAT_LIGHTS_PDF || op == VPT_KAT_LIGHTS_PDF_K2 || op == VPT_KAT_SPHERETRACE) && (iparam < 0 || iparam > (1 << 20)))
-    return fail(VPT_ERR_INVALID_ARG, "KAT op %d: iteration limit %d out of range", op, iparam);
+    return vpt_set_error(VPT_ERR_INVALID_ARG, "KAT op %d: iteration limit %d out of range", op, iparam);
   HIP_TRY(hipSetDevice(s->device));
   float *d_in = nullptr, *d_out = nullptr;
   int*   d_aux = nullptr;
@@ -1582,7 +1498,7 @@ int vpt_kat(vpt_scene* s, int op, int iparam, int n, const float* in, float* out
       hipMalloc((void**)&d_aux, (size_t)n * 4) != hipSuccess || hipMemcpy(d_in, in, (size_t)n * si * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(d_aux, aux.data(), (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) {
     release();
-    return fail(VPT_ERR_HIP, "vpt_kat: device buffers");
+    return vpt_set_error(VPT_ERR_HIP, "vpt_kat: device buffers");
   }
   int       blocks = (n + VPT_BLOCK - 1) / VPT_BLOCK;
   stack_cfg stack;
@@ -1593,11 +1509,11 @@ int vpt_kat(vpt_scene* s, int op, int iparam, int n, const float* in, float* out
   else hipLaunchKernelGGL(vpt_kat_kernel<false>, dim3(blocks), dim3(VPT_BLOCK), lds, 0, s->d, op, iparam, n, si, so, d_in, d_aux, d_out, stack, s->stack_cap);
   bool ok = hipGetLastError() == hipSuccess && hipMemcpy(out, d_out, (size_t)n * so * 4, hipMemcpyDeviceToHost) == hipSuccess;
   release();
-  return ok ? VPT_OK : fail(VPT_ERR_HIP, "vpt_kat failed to run");
+  return ok ? VPT_OK : vpt_set_error(VPT_ERR_HIP, "vpt_kat failed to run");
 }
 
 int vpt_spheretrace(vpt_scene* s, int n, const float* rays, int sdf, int maxiter, int32_t* ids, float* t) {
-  if (!s || n < 0 || (n > 0 && (!rays || !ids || !t))) return fail(VPT_ERR_INVALID_ARG, "bad argument");
+  if (!s || n < 0 || (n > 0 && (!rays || !ids || !t))) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
   std::vector<float> in((size_t)n * 7), out((size_t)n * 4);
   for (int i = 0; i < n; i++) {
     memcpy(&in[(size_t)i * 7], rays + (size_t)i * 6, 24);
@@ -1614,8 +1530,8 @@ int vpt_spheretrace(vpt_scene* s, int n, const float* rays, int sdf, int maxiter
 int vpt_eval_lobes(vpt_scene* s, int n, const float* in19, float* out22) { return vpt_kat(s, VPT_KAT_LOBES, 0, n, in19, out22); }
 
 int vpt_selftest_light_cdf(vpt_scene* s, int light, int n, unsigned long long* mismatches, int* indexed) {
-  if (!s || !mismatches || !indexed || n <= 0) return fail(VPT_ERR_INVALID_ARG, "bad argument");
-  if (light < 0 || light >= s->d.num_lights) return fail(VPT_ERR_INVALID_ARG, "light %d out of range", light);
+  if (!s || !mismatches || !indexed || n <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
+  if (light < 0 || light >= s->d.num_lights) return vpt_set_error(VPT_ERR_INVALID_ARG, "light %d out of range", light);
   HIP_TRY(hipSetDevice(s->device));
   DCdfIndex ix;
   HIP_TRY(hipMemcpy(&ix, s->d.light_index + light, sizeof(ix), hipMemcpyDeviceToHost));
@@ -1625,7 +1541,7 @@ int vpt_selftest_light_cdf(vpt_scene* s, int light, int n, unsigned long long* m
   HIP_TRY(hipMalloc((void**)&d, 8));
   HIP_TRY(hipMemset(d, 0, 8));
   hipLaunchKernelGGL(vpt_light_cdf_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, s->d, light, n, d);
-  int rc = hipMemcpy(mismatches, d, 8, hipMemcpyDeviceToHost) == hipSuccess ? VPT_OK : fail(VPT_ERR_HIP, "light CDF self-test failed to run");
+  int rc = hipMemcpy(mismatches, d, 8, hipMemcpyDeviceToHost) == hipSuccess ? VPT_OK : vpt_set_error(VPT_ERR_HIP, "light CDF self-test failed to run");
   (void)hipFree(d);
   return rc;
 }

@@ -13,8 +13,8 @@
 // hit count, RNG state of each of its pixels), taken by the device's thread when it stored the download and taken again
 // from the caller's arrays before the skip - one edited pixel anywhere, or another state object at another address,
 // is uploaded (round 3 compared 64 probe pixels only; tests/test_multi_gpu.py edits a pixel no probe looked at).
-// VPT_MULTI_RESIDENT=0 switches the skip off altogether.  Host staging is pinned (hipHostMalloc), one tile-major buffer
-// per device; the row-major <-> tile-major scatter runs in the per-device threads.
+// Host staging is pinned (hipHostMalloc), one tile-major buffer per device; the row-major <-> tile-major scatter runs in
+// the per-device threads.
 //
 // The one exchange is the frame assembly of vpt_multi_get_render: the float4 tile buffers travel to devices[0] over
 // xGMI with RCCL (grouped ncclSend / ncclRecv: ndev - 1 concurrent point-to-point transfers, no ring, no reduction) and
@@ -37,9 +37,7 @@
 #include <thread>
 #include <vector>
 
-#include "vpt.h"
-
-int vpt_set_error(int code, const char* fmt, ...);   // vpt_capi.hip: records the message for vpt_last_error() on this thread
+#include "vpt_error.h"
 
 namespace {
 
@@ -257,11 +255,6 @@ void download_part(vpt_multi* m, int i, float* image_rgba, int32_t* hits, uint64
   }
   p.mirror_sum = part_checksum(p, image_rgba, hits, rng), p.mirrored = true;
 }
-
-bool always_upload() {   // VPT_MULTI_RESIDENT=0: every host-pointer call uploads the caller's arrays (no checksum pass)
-  const char* e = getenv("VPT_MULTI_RESIDENT");
-  return e && !strcmp(e, "0");
-}
 }  // namespace
 
 extern "C" {
@@ -364,7 +357,7 @@ int vpt_multi_render(vpt_multi* m, const vpt_params* params, int nsamples, int w
   // The caller's arrays are the state, as in the reference: every part of them is uploaded unless the device provably holds it
   // already - the arrays are the very ones (same addresses, same size, same sample count) the last call downloaded into, and
   // the part's checksum over all of its words, re-taken now by the device's thread, is what that download stored.
-  const bool may_skip = !on_device && m->resident && !always_upload() && m->width == width && m->height == height && m->samples == *samples_io &&
+  const bool may_skip = !on_device && m->resident && m->width == width && m->height == height && m->samples == *samples_io &&
                         m->samples > 0 && m->mirror_image == image_rgba && m->mirror_hits == hits && m->mirror_rng == rng;
   if (!on_device && !may_skip) {
     if (int rc = size_for(m, width, height)) return rc;

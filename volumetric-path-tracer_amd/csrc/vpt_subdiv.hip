@@ -27,10 +27,8 @@
 #include <cmath>
 #include <vector>
 
-#include "vpt.h"
+#include "vpt_error.h"
 #include "vpt_scene.hip.h"
-
-int vpt_set_error(int code, const char* fmt, ...);   // vpt_capi.hip
 
 namespace {
 
@@ -161,26 +159,20 @@ int run_level(const vpt_subdiv_level& L, const float* vertices, float* new_verti
   int2*   d_edges = nullptr;
   int4 *  d_faces = nullptr, *d_tquads = nullptr;
   int *   d_val = nullptr, *d_off = nullptr, *d_items = nullptr;
-#define TRY(expr)                                                                                      \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return vpt_set_error(VPT_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-  TRY(buf.put((const vecD<D>*)vertices, (size_t)L.num_vertices, &d_vert));
-  TRY(buf.put((const vecD<D>*)nullptr, (size_t)nt, &d_tverts));
-  TRY(buf.put((const vecD<D>*)nullptr, (size_t)nt, &d_out));
-  TRY(buf.put((const int2*)L.edges, (size_t)L.num_edges, &d_edges));
-  TRY(buf.put((const int4*)L.faces, (size_t)L.num_faces, &d_faces));
-  TRY(buf.put((const int4*)L.new_faces, (size_t)L.num_new_faces, &d_tquads));
-  TRY(buf.put(L.valence, (size_t)nt, &d_val));
-  TRY(buf.put(L.offsets, (size_t)nt + 1, &d_off));
-  TRY(buf.put(L.items, (size_t)L.num_items, &d_items));
+  HIP_TRY(buf.put((const vecD<D>*)vertices, (size_t)L.num_vertices, &d_vert));
+  HIP_TRY(buf.put((const vecD<D>*)nullptr, (size_t)nt, &d_tverts));
+  HIP_TRY(buf.put((const vecD<D>*)nullptr, (size_t)nt, &d_out));
+  HIP_TRY(buf.put((const int2*)L.edges, (size_t)L.num_edges, &d_edges));
+  HIP_TRY(buf.put((const int4*)L.faces, (size_t)L.num_faces, &d_faces));
+  HIP_TRY(buf.put((const int4*)L.new_faces, (size_t)L.num_new_faces, &d_tquads));
+  HIP_TRY(buf.put(L.valence, (size_t)nt, &d_val));
+  HIP_TRY(buf.put(L.offsets, (size_t)nt + 1, &d_off));
+  HIP_TRY(buf.put(L.items, (size_t)L.num_items, &d_items));
   const int blocks = (nt + 255) / 256;
   hipLaunchKernelGGL(subdiv_points_kernel<D>, dim3(blocks), dim3(256), 0, 0, L.num_vertices, L.num_edges, L.num_faces, d_vert, d_edges, d_faces, d_tverts);
   hipLaunchKernelGGL(subdiv_average_kernel<D>, dim3(blocks), dim3(256), 0, 0, nt, d_tverts, d_tquads, d_val, d_off, d_items, d_out);
-  TRY(hipGetLastError());
-  TRY(hipMemcpy(new_vertices, d_out, (size_t)nt * sizeof(vecD<D>), hipMemcpyDeviceToHost));
-#undef TRY
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(new_vertices, d_out, (size_t)nt * sizeof(vecD<D>), hipMemcpyDeviceToHost));
   return VPT_OK;
 }
 
@@ -240,19 +232,14 @@ extern "C" int vpt_vertex_normals(int device, int32_t num_vertices, const float*
   device_buffers buf;
   float *d_pos = nullptr, *d_nrm = nullptr;
   int *  d_faces = nullptr, *d_off = nullptr, *d_items = nullptr;
-#define TRY(expr)                                                                                      \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return vpt_set_error(VPT_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-  TRY(buf.put(positions, (size_t)num_vertices * 3, &d_pos));
-  TRY(buf.put((const float*)nullptr, (size_t)num_vertices * 3, &d_nrm));
-  TRY(buf.put((const int*)faces, (size_t)num_faces * corners, &d_faces));
-  TRY(buf.put(offsets.data(), offsets.size(), &d_off));
-  TRY(buf.put(items.data(), items.size(), &d_items));
+  HIP_TRY(buf.put(positions, (size_t)num_vertices * 3, &d_pos));
+  HIP_TRY(buf.put((const float*)nullptr, (size_t)num_vertices * 3, &d_nrm));
+  HIP_TRY(buf.put((const int*)faces, (size_t)num_faces * corners, &d_faces));
+  HIP_TRY(buf.put(offsets.data(), offsets.size(), &d_off));
+  HIP_TRY(buf.put(items.data(), items.size(), &d_items));
   hipLaunchKernelGGL(vertex_normals_kernel, dim3((num_vertices + 255) / 256), dim3(256), 0, 0, num_vertices, corners, d_pos, d_faces, d_off, d_items, d_nrm);
-  TRY(hipGetLastError());
-  TRY(hipMemcpy(normals, d_nrm, (size_t)num_vertices * 12, hipMemcpyDeviceToHost));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(normals, d_nrm, (size_t)num_vertices * 12, hipMemcpyDeviceToHost));
   return VPT_OK;
 }
 
@@ -278,19 +265,18 @@ extern "C" int vpt_displace_vertices(int device, const vpt_texture* texture, con
     float srgb = b / 255.0f;
     lut[b]     = (srgb <= 0.04045) ? srgb / 12.92f : std::pow((srgb + 0.055f) / (1.0f + 0.055f), 2.4f);
   }
-  TRY(buf.put(positions, (size_t)num_vertices * 3, &d_pos));
-  TRY(buf.put(normals, (size_t)num_vertices * 3, &d_nrm));
-  TRY(buf.put(texcoords, (size_t)num_vertices * 2, &d_uv));
-  TRY(buf.put((const float*)nullptr, (size_t)num_vertices * 3, &d_out));
-  TRY(buf.put(lut, 256, &d_lut));
-  TRY(buf.put(&t, 1, &d_tex));
-  if (t.is_float) TRY(buf.put((const float4*)texels, (size_t)ntex, &d_texf));
-  else TRY(buf.put((const uchar4*)texels, (size_t)ntex, &d_texb));
+  HIP_TRY(buf.put(positions, (size_t)num_vertices * 3, &d_pos));
+  HIP_TRY(buf.put(normals, (size_t)num_vertices * 3, &d_nrm));
+  HIP_TRY(buf.put(texcoords, (size_t)num_vertices * 2, &d_uv));
+  HIP_TRY(buf.put((const float*)nullptr, (size_t)num_vertices * 3, &d_out));
+  HIP_TRY(buf.put(lut, 256, &d_lut));
+  HIP_TRY(buf.put(&t, 1, &d_tex));
+  if (t.is_float) HIP_TRY(buf.put((const float4*)texels, (size_t)ntex, &d_texf));
+  else HIP_TRY(buf.put((const uchar4*)texels, (size_t)ntex, &d_texb));
   DScene sc = {};   // the one table eval_texture follows: textures[0] over its texel pool and the decode table
   sc.num_textures = 1, sc.textures = d_tex, sc.texels_f = d_texf, sc.texels_b = d_texb, sc.srgb_lut = d_lut;
   hipLaunchKernelGGL(displace_kernel, dim3((num_vertices + 255) / 256), dim3(256), 0, 0, sc, num_vertices, t.is_float ? 0 : 1, displacement, d_pos, d_nrm, d_uv, d_out);
-  TRY(hipGetLastError());
-  TRY(hipMemcpy(new_positions, d_out, (size_t)num_vertices * 12, hipMemcpyDeviceToHost));
-#undef TRY
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(new_positions, d_out, (size_t)num_vertices * 12, hipMemcpyDeviceToHost));
   return VPT_OK;
 }
