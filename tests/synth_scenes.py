@@ -20,7 +20,7 @@ in the positive direction passes every box and visits the inner part of the chai
 
 Each function writes a scene JSON with OBJ shapes into `dirpath` and returns (path, facts); the facts are computed here from the same
 bounding boxes the loader builds its BVHs from (vpt.build_bvh(bboxes, device=None) is the host build the loader uses), with bvh_depth /
-quad_need mirroring bvh_depth / build_quad_nodes of vpt_capi.hip."""
+quad_need mirroring bvh_depth / build_quad_nodes of vpt_scene_prep.cpp."""
 import json
 import os
 
@@ -28,15 +28,15 @@ import numpy as np
 
 F = np.float32
 
-STACK_LIMIT = 256        # vpt_capi.hip: stack_cap (need rounded up to 4) * VPT_BLOCK (64) * 4 bytes must fit 64 KiB
+STACK_LIMIT = 256        # vpt_scene_prep.cpp: stack_cap (need rounded up to 4) * VPT_BLOCK (64) * 4 bytes must fit 64 KiB
 HOIST_MAX = 16           # vpt_mesh_kernel.hip.h VPT_HOIST_MAX
 REFERENCE_STACK = 128    # the reference's intersect_bvh keeps 128 nodes per BVH level: a binary depth of 127 at most (depth + 1 entries)
 CHAIN_RATIO = 0.77       # v_{i+1} / v_i of a chain (module docstring)
 
 
-# ---- BVH figures (vpt_capi.hip) -----------------------------------------------------------------------------------------------------
+# ---- BVH figures (vpt_scene_prep.cpp) ------------------------------------------------------------------------------------------------
 def bvh_depth(nodes) -> int:
-    """binary depth of the deepest leaf (root = 0); vpt_capi.hip bvh_depth"""
+    """binary depth of the deepest leaf (root = 0); vpt_scene_prep.cpp bvh_depth"""
     if len(nodes) == 0:
         return 0
     best, todo = 0, [(0, 0)]
@@ -51,7 +51,7 @@ def bvh_depth(nodes) -> int:
 
 def quad_need(nodes) -> int:
     """worst-case quad-stack entries of a traversal of this BVH: per quad level, the passing grandchildren but the first visited one,
-    plus the need of the deepest internal one; vpt_capi.hip build_quad_nodes (*need)"""
+    plus the need of the deepest internal one; vpt_scene_prep.cpp build_quad_nodes (*need)"""
     if len(nodes) == 0 or not nodes[0]["internal"]:
         return 0
 
@@ -98,7 +98,7 @@ def line_entry_depths(nodes) -> dict:
 
 
 def stack_need(scene_depth: int, max_shape_depth: int) -> int:
-    """the binary-stack figure the create-time limit is checked on (vpt_capi.hip: need <= 256 is accepted)"""
+    """the binary-stack figure the create-time limit is checked on (vpt_scene_prep.cpp: need <= 256 is accepted)"""
     return scene_depth + 2 + max_shape_depth + 2
 
 

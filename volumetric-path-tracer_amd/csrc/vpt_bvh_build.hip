@@ -30,6 +30,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "vpt_device_buffer.h"
 #include "vpt_error.h"
 
 namespace {
@@ -223,19 +224,6 @@ __global__ void k_emit(int count, const tnode* __restrict__ nodes, const float* 
   out[id] = o;
 }
 
-struct dev_buffers {   // freed on every exit path
-  std::vector<void*> ptrs;
-  ~dev_buffers() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  template <typename T>
-  hipError_t alloc(T** p, size_t count) {
-    hipError_t e = hipMalloc((void**)p, (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) ptrs.push_back(*p);
-    return e;
-  }
-};
-
 }  // namespace
 
 extern "C" int vpt_build_bvh(int device, const float* bboxes, int n, vpt_bvh_node* nodes_out, int capacity, int* num_nodes, int* primitives) {
@@ -253,29 +241,22 @@ extern "C" int vpt_build_bvh(int device, const float* bboxes, int n, vpt_bvh_nod
   if (device < 0 || device >= ndev) return vpt_set_error(VPT_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
   HIP_TRY(hipSetDevice(device));
 
-  dev_buffers B;
-  float *bb = nullptr, *ctr = nullptr, *boxes = nullptr;
-  int *  prims = nullptr, *node_of = nullptr, *flag = nullptr, *tscan = nullptr, *partner = nullptr, *counter = nullptr;
-  tnode* nodes = nullptr;
-  tkeys* keys  = nullptr;
-  vpt_bvh_node* out = nullptr;
-  const size_t cap = 2 * (size_t)n;
-  HIP_TRY(B.alloc(&bb, 6 * (size_t)n));
-  HIP_TRY(B.alloc(&ctr, 3 * (size_t)n));
-  HIP_TRY(B.alloc(&boxes, 6 * cap));
-  HIP_TRY(B.alloc(&prims, (size_t)n));
-  HIP_TRY(B.alloc(&node_of, (size_t)n));
-  HIP_TRY(B.alloc(&flag, (size_t)n + 1));
-  HIP_TRY(B.alloc(&tscan, (size_t)n + 1));
-  HIP_TRY(B.alloc(&partner, (size_t)n));
-  HIP_TRY(B.alloc(&counter, 1));
-  HIP_TRY(B.alloc(&nodes, cap));
-  HIP_TRY(B.alloc(&keys, cap));
-  HIP_TRY(B.alloc(&out, cap));
+  const size_t  cap = 2 * (size_t)n;
+  device_buffer d_bb, d_ctr, d_boxes, d_prims, d_node_of, d_flag, d_tscan, d_partner, d_counter, d_nodes, d_keys, d_out, d_scan_temp;   // freed on every exit path
+  if (d_bb.allocate(6 * (size_t)n * sizeof(float)) || d_ctr.allocate(3 * (size_t)n * sizeof(float)) || d_boxes.allocate(6 * cap * sizeof(float)) ||
+      d_prims.allocate((size_t)n * sizeof(int)) || d_node_of.allocate((size_t)n * sizeof(int)) || d_flag.allocate(((size_t)n + 1) * sizeof(int)) ||
+      d_tscan.allocate(((size_t)n + 1) * sizeof(int)) || d_partner.allocate((size_t)n * sizeof(int)) || d_counter.allocate(sizeof(int)) ||
+      d_nodes.allocate(cap * sizeof(tnode)) || d_keys.allocate(cap * sizeof(tkeys)) || d_out.allocate(cap * sizeof(vpt_bvh_node)))
+    return VPT_ERR_HIP;
+  float *bb = d_bb.get<float>(), *ctr = d_ctr.get<float>(), *boxes = d_boxes.get<float>();
+  int *  prims = d_prims.get<int>(), *node_of = d_node_of.get<int>(), *flag = d_flag.get<int>(), *tscan = d_tscan.get<int>(), *partner = d_partner.get<int>(), *counter = d_counter.get<int>();
+  tnode* nodes = d_nodes.get<tnode>();
+  tkeys* keys  = d_keys.get<tkeys>();
+  vpt_bvh_node* out = d_out.get<vpt_bvh_node>();
   size_t scan_bytes = 0;
   HIP_TRY(rocprim::exclusive_scan((void*)nullptr, scan_bytes, flag, tscan, 0, (size_t)n + 1, rocprim::plus<int>()));
-  char* scan_temp = nullptr;
-  HIP_TRY(B.alloc(&scan_temp, scan_bytes));
+  if (int rc = d_scan_temp.allocate(scan_bytes)) return rc;
+  char* scan_temp = d_scan_temp.get<char>();
 
   const int  TB = 256;
   const dim3 gn((n + TB - 1) / TB), gn1((n + 1 + TB - 1) / TB);

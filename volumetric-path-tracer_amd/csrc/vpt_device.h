@@ -1,5 +1,5 @@
-// vpt_device.h — device-resident scene layout shared by the C-ABI host code (vpt_capi.hip)
-// and the kernels (vpt_kernels.hip.inc).  All arrays live in HBM for the life of a vpt_scene;
+// vpt_device.h — device-resident scene layout shared by the host code that builds it (vpt_scene_prep.cpp,
+// uploaded by vpt_capi.hip) and the kernels (vpt_kernels.hip.h).  All arrays live in HBM for the life of a vpt_scene;
 // layouts are chosen for 16-byte vector loads (global_load_dwordx4) per lane:
 //
 //   bvh node      32 B  = 2 x float4   {min.xyz, max.x} {max.yz, start, num|axis<<16|internal<<24}
@@ -17,6 +17,20 @@
 #include <stdint.h>
 
 #include "vpt.h"
+
+#ifndef VPT_BLOCK
+#define VPT_BLOCK 64   // threads per workgroup = one wave64 = one 8x8 pixel tile: a wave that finishes frees its slot at once
+#endif
+#define VPT_FLOOR_SHIFT 4   // group_nodes() (vpt_mesh_kernel.hip.h): {csgn, slow} in the low 4 bits of the word a ray's state travels in, its pop floor above them
+
+// Scene features a kernel instance is compiled for (template parameter FEAT of the mesh kernels): code for a feature the
+// scene does not have costs registers in every path (the allocator serves the worst one), so vpt_capi.hip launches the
+// instance without it - 03_volume, whose lights are quads and an environment: 622 -> 676 Msamples/s.
+enum { VPT_FEAT_COMPACT_TRIS = 8,   // not a light feature: the instance reads DScene::tri_prims / tri_attrs (scenes whose shapes all hold triangles)
+       VPT_FEAT_LARGE_LIGHTS = 1,   // emissive meshes with a real BVH: sample_lights_pdf walks them with extra trips (ST_LPDF)
+       VPT_FEAT_SDF_LIGHTS   = 2,   // SDF lights: a sphere trace inside sample_lights_pdf
+       VPT_FEAT_SMALL_LIGHTS = 4,   // emissive meshes of a single BVH leaf (area-light quads): walked inline from their light records
+       VPT_FEAT_ALL          = 7 };
 
 enum { VPT_SHP_TRIANGLES = 1, VPT_SHP_NORMALS = 2, VPT_SHP_TEXCOORDS = 4, VPT_SHP_COLORS = 8 };
 

@@ -195,7 +195,6 @@ VPT_DEV bool slab_pass_signed(float nx, float ny, float nz, float fx, float fy, 
 // needed C work ("sessions"): fewer transfers, but the rays outside a session waited for its longest member - 174 wave-level node
 // steps per 64 samples against the own form's 132 - and it LOST (276 ms, profiles/r04_k1_group_forms.txt).
 #define VPT_NONE (-2147483647 - 1)
-#define VPT_FLOOR_SHIFT 4   // group_nodes(): {csgn, slow} in the low 4 bits of the word a ray's state travels in, its pop floor above them
 #ifndef VPT_HOIST_MAX
 #define VPT_HOIST_MAX 16   // scenes with at most this many instances test all root boxes at the start of a query
 #endif

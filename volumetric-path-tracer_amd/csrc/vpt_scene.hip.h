@@ -7,11 +7,6 @@
 #include "vpt_device.h"
 #include "vpt_math.hip.h"
 
-#ifndef VPT_BLOCK
-#define VPT_BLOCK 64   // threads per workgroup = one wave64 = one 8x8 pixel tile: a wave that finishes frees its slot at once
-#endif
-
-
 // Diagnostic build (-DVPT_COUNTERS): how often a wave executes each code section and with how many
 // active lanes.  Slot 2k counts wave executions, slot 2k+1 the lanes active in them.  Never in the product build.
 #ifdef VPT_COUNTERS
@@ -1092,14 +1087,7 @@ VPT_DEV st_hit spheretrace_one(const DScene& sc, f3 ro, f3 rd, int sdf_handle, i
 // ------------------------------------------------------------------------------------------------
 // lights, yocto_pathtrace.cpp:312-421
 // ------------------------------------------------------------------------------------------------
-// Scene features a kernel instance is compiled for (template parameter FEAT of the mesh kernels): code for a feature the
-// scene does not have costs registers in every path (the allocator serves the worst one), so vpt_capi.hip launches the
-// instance without it - 03_volume, whose lights are quads and an environment: 622 -> 676 Msamples/s.
-enum { VPT_FEAT_COMPACT_TRIS = 8,   // not a light feature: the instance reads DScene::tri_prims / tri_attrs (scenes whose shapes all hold triangles)
-       VPT_FEAT_LARGE_LIGHTS = 1,   // emissive meshes with a real BVH: sample_lights_pdf walks them with extra trips (ST_LPDF)
-       VPT_FEAT_SDF_LIGHTS   = 2,   // SDF lights: a sphere trace inside sample_lights_pdf
-       VPT_FEAT_SMALL_LIGHTS = 4,   // emissive meshes of a single BVH leaf (area-light quads): walked inline from their light records
-       VPT_FEAT_ALL          = 7 };
+// Scene features a kernel instance is compiled for: VPT_FEAT_* (vpt_device.h)
 template <int FEAT = VPT_FEAT_ALL>
 VPT_DEV f3 sample_lights(const DScene& sc, f3 position, float rl, float rel, f2 ruv) {
   int           light_id = sample_uniform(sc.num_lights, rl);

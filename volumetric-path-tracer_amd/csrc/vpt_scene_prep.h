@@ -1,0 +1,43 @@
+// vpt_scene_prep.h — host half of vpt_scene_create: a vpt_scene_desc checked and turned into the tables of the device
+// layout (vpt_device.h), in host memory.  No device call: vpt_capi.hip uploads the tables, one allocation each.
+#pragma once
+#include <vector>
+
+#include "vpt_device.h"
+
+// host copies of a few index tables: range checks of the batch entry points (vpt_intersect, vpt_kat)
+struct host_mirrors {
+  std::vector<int> slot_of;   // instance -> scene-BVH primitive slot (-1: not in the scene BVH); also a device table
+  std::vector<int> inst_shape, shape_elems, shape_elem_offset;
+  std::vector<int> prim_slot;   // [shape elem_offset + element] -> slot in leaf_prims / leaf_attrs
+};
+
+struct scene_tables {
+  // the scalar fields of DScene: counts, scene_root_*, group_forms, sdf_bound_*, sdf_num_planes; the table pointers stay null
+  DScene d = {};
+  // geometry: vertex pools, shapes and their elements, leaf records and their vertex attributes in BVH leaf order
+  std::vector<float4> positions, normals, colors;
+  std::vector<float2> texcoords;
+  std::vector<DShape> shapes;
+  std::vector<int4>   elems;
+  std::vector<float4> leaf_prims, leaf_attrs;
+  std::vector<float4> tri_prims, tri_attrs;   // the compact records: empty unless every shape holds triangles
+  // quad nodes of all BVHs in one table: the scene's first (scene_wnodes float4s), then the shapes'
+  std::vector<float4> wnodes;
+  size_t              scene_wnodes = 0;
+  std::vector<float4> enter;
+  std::vector<DInstance> instances;
+  std::vector<float4> env_inv, sdf_inv;
+  std::vector<float>  srgb_lut;
+  std::vector<DCdfIndex> light_index;   // + its pool and guide table
+  std::vector<float>     light_index_pool;
+  std::vector<int2>      light_guide;
+  std::vector<float4>    light_rec, sdf_fn_rec, sdf_grid_rec;
+  // traversal stacks: binary-BVH walk of the implicit kernels (refs only); quad-node traversal entries in LDS / in HBM
+  int stack_cap = 16, stack_lds4 = 8, stack_spill4 = 0;
+  int light_features = 0;   // VPT_FEAT_* bits this scene's lights need from the mesh kernels
+  host_mirrors h;
+};
+
+// validate(desc), then every table; VPT_ERR_INVALID_ARG for a bad descriptor, VPT_ERR_UNSUPPORTED for a scene past a traversal limit
+int prepare_scene(const vpt_scene_desc& desc, scene_tables& out);

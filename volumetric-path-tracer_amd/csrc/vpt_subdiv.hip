@@ -27,6 +27,7 @@
 #include <cmath>
 #include <vector>
 
+#include "vpt_device_buffer.h"
 #include "vpt_error.h"
 #include "vpt_scene.hip.h"
 
@@ -135,39 +136,28 @@ __global__ void __launch_bounds__(256) displace_kernel(DScene sc, int nv, int by
   out[3 * v] = p.x, out[3 * v + 1] = p.y, out[3 * v + 2] = p.z;
 }
 
-struct device_buffers {   // freed on every path
-  std::vector<void*> all;
-  ~device_buffers() {
-    for (void* p : all) (void)hipFree(p);
-  }
-  template <typename T>
-  hipError_t put(const T* host, size_t count, T** out) {
-    void*      d = nullptr;
-    hipError_t e = hipMalloc(&d, count ? count * sizeof(T) : 16);
-    if (e != hipSuccess) return e;
-    all.push_back(d);
-    *out = (T*)d;
-    return host && count ? hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
-  }
-};
+// `count` items in `buf`, copied from `host` unless it is null; *out: the device copy.  Fails with VPT_ERR_HIP only
+template <typename T>
+int put(device_buffer& buf, const T* host, size_t count, T** out) {
+  if (int rc = buf.allocate(count * sizeof(T))) return rc;
+  *out = buf.get<T>();
+  if (host && count) HIP_TRY(hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice));
+  return VPT_OK;
+}
 
 template <int D>
 int run_level(const vpt_subdiv_level& L, const float* vertices, float* new_vertices) {
   const int nt = L.num_vertices + L.num_edges + L.num_faces;
-  device_buffers buf;
+  device_buffer buf[9];   // freed on every path
   vecD<D> *d_vert = nullptr, *d_tverts = nullptr, *d_out = nullptr;
   int2*   d_edges = nullptr;
   int4 *  d_faces = nullptr, *d_tquads = nullptr;
   int *   d_val = nullptr, *d_off = nullptr, *d_items = nullptr;
-  HIP_TRY(buf.put((const vecD<D>*)vertices, (size_t)L.num_vertices, &d_vert));
-  HIP_TRY(buf.put((const vecD<D>*)nullptr, (size_t)nt, &d_tverts));
-  HIP_TRY(buf.put((const vecD<D>*)nullptr, (size_t)nt, &d_out));
-  HIP_TRY(buf.put((const int2*)L.edges, (size_t)L.num_edges, &d_edges));
-  HIP_TRY(buf.put((const int4*)L.faces, (size_t)L.num_faces, &d_faces));
-  HIP_TRY(buf.put((const int4*)L.new_faces, (size_t)L.num_new_faces, &d_tquads));
-  HIP_TRY(buf.put(L.valence, (size_t)nt, &d_val));
-  HIP_TRY(buf.put(L.offsets, (size_t)nt + 1, &d_off));
-  HIP_TRY(buf.put(L.items, (size_t)L.num_items, &d_items));
+  if (put(buf[0], (const vecD<D>*)vertices, (size_t)L.num_vertices, &d_vert) || put(buf[1], (const vecD<D>*)nullptr, (size_t)nt, &d_tverts) ||
+      put(buf[2], (const vecD<D>*)nullptr, (size_t)nt, &d_out) || put(buf[3], (const int2*)L.edges, (size_t)L.num_edges, &d_edges) ||
+      put(buf[4], (const int4*)L.faces, (size_t)L.num_faces, &d_faces) || put(buf[5], (const int4*)L.new_faces, (size_t)L.num_new_faces, &d_tquads) ||
+      put(buf[6], L.valence, (size_t)nt, &d_val) || put(buf[7], L.offsets, (size_t)nt + 1, &d_off) || put(buf[8], L.items, (size_t)L.num_items, &d_items))
+    return VPT_ERR_HIP;
   const int blocks = (nt + 255) / 256;
   hipLaunchKernelGGL(subdiv_points_kernel<D>, dim3(blocks), dim3(256), 0, 0, L.num_vertices, L.num_edges, L.num_faces, d_vert, d_edges, d_faces, d_tverts);
   hipLaunchKernelGGL(subdiv_average_kernel<D>, dim3(blocks), dim3(256), 0, 0, nt, d_tverts, d_tquads, d_val, d_off, d_items, d_out);
@@ -229,14 +219,13 @@ extern "C" int vpt_vertex_normals(int device, int32_t num_vertices, const float*
     for (int c = 0; c < corners; c++)
       if (adds(faces + (size_t)corners * i, c)) items[(size_t)fill[(size_t)faces[(size_t)corners * i + c]]++] = i;
   if (hipSetDevice(device) != hipSuccess) return vpt_set_error(VPT_ERR_NO_DEVICE, "no device %d", device);
-  device_buffers buf;
+  device_buffer buf[5];   // freed on every path
   float *d_pos = nullptr, *d_nrm = nullptr;
   int *  d_faces = nullptr, *d_off = nullptr, *d_items = nullptr;
-  HIP_TRY(buf.put(positions, (size_t)num_vertices * 3, &d_pos));
-  HIP_TRY(buf.put((const float*)nullptr, (size_t)num_vertices * 3, &d_nrm));
-  HIP_TRY(buf.put((const int*)faces, (size_t)num_faces * corners, &d_faces));
-  HIP_TRY(buf.put(offsets.data(), offsets.size(), &d_off));
-  HIP_TRY(buf.put(items.data(), items.size(), &d_items));
+  if (put(buf[0], positions, (size_t)num_vertices * 3, &d_pos) || put(buf[1], (const float*)nullptr, (size_t)num_vertices * 3, &d_nrm) ||
+      put(buf[2], (const int*)faces, (size_t)num_faces * corners, &d_faces) || put(buf[3], offsets.data(), offsets.size(), &d_off) ||
+      put(buf[4], items.data(), items.size(), &d_items))
+    return VPT_ERR_HIP;
   hipLaunchKernelGGL(vertex_normals_kernel, dim3((num_vertices + 255) / 256), dim3(256), 0, 0, num_vertices, corners, d_pos, d_faces, d_off, d_items, d_nrm);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(normals, d_nrm, (size_t)num_vertices * 12, hipMemcpyDeviceToHost));
@@ -252,7 +241,7 @@ extern "C" int vpt_displace_vertices(int device, const vpt_texture* texture, con
   const long long ntex = (long long)texture->width * texture->height;
   if (texture->width < 0 || texture->height < 0 || ntex > (1ll << 30) || (ntex > 0 && !texels)) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad texture");
   if (hipSetDevice(device) != hipSuccess) return vpt_set_error(VPT_ERR_NO_DEVICE, "no device %d", device);
-  device_buffers buf;
+  device_buffer buf[7];   // freed on every path
   float *d_pos = nullptr, *d_nrm = nullptr, *d_uv = nullptr, *d_out = nullptr, *d_lut = nullptr;
   vpt_texture* d_tex = nullptr;
   float4*      d_texf = nullptr;
@@ -265,14 +254,11 @@ extern "C" int vpt_displace_vertices(int device, const vpt_texture* texture, con
     float srgb = b / 255.0f;
     lut[b]     = (srgb <= 0.04045) ? srgb / 12.92f : std::pow((srgb + 0.055f) / (1.0f + 0.055f), 2.4f);
   }
-  HIP_TRY(buf.put(positions, (size_t)num_vertices * 3, &d_pos));
-  HIP_TRY(buf.put(normals, (size_t)num_vertices * 3, &d_nrm));
-  HIP_TRY(buf.put(texcoords, (size_t)num_vertices * 2, &d_uv));
-  HIP_TRY(buf.put((const float*)nullptr, (size_t)num_vertices * 3, &d_out));
-  HIP_TRY(buf.put(lut, 256, &d_lut));
-  HIP_TRY(buf.put(&t, 1, &d_tex));
-  if (t.is_float) HIP_TRY(buf.put((const float4*)texels, (size_t)ntex, &d_texf));
-  else HIP_TRY(buf.put((const uchar4*)texels, (size_t)ntex, &d_texb));
+  if (put(buf[0], positions, (size_t)num_vertices * 3, &d_pos) || put(buf[1], normals, (size_t)num_vertices * 3, &d_nrm) ||
+      put(buf[2], texcoords, (size_t)num_vertices * 2, &d_uv) || put(buf[3], (const float*)nullptr, (size_t)num_vertices * 3, &d_out) ||
+      put(buf[4], lut, 256, &d_lut) || put(buf[5], &t, 1, &d_tex) ||
+      (t.is_float ? put(buf[6], (const float4*)texels, (size_t)ntex, &d_texf) : put(buf[6], (const uchar4*)texels, (size_t)ntex, &d_texb)))
+    return VPT_ERR_HIP;
   DScene sc = {};   // the one table eval_texture follows: textures[0] over its texel pool and the decode table
   sc.num_textures = 1, sc.textures = d_tex, sc.texels_f = d_texf, sc.texels_b = d_texb, sc.srgb_lut = d_lut;
   hipLaunchKernelGGL(displace_kernel, dim3((num_vertices + 255) / 256), dim3(256), 0, 0, sc, num_vertices, t.is_float ? 0 : 1, displacement, d_pos, d_nrm, d_uv, d_out);
