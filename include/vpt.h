@@ -37,7 +37,8 @@ typedef enum vpt_status {
   VPT_ERR_NO_DEVICE     = -2, /* no gfx950 device / HIP runtime unavailable                */
   VPT_ERR_HIP           = -3, /* a HIP call failed (message has hipGetErrorString)         */
   VPT_ERR_UNKNOWN_SHADER = -4, /* reference: get_shader throws "sampler unknown" (cpp:947) */
-  VPT_ERR_UNSUPPORTED   = -5  /* scene feature outside the hot-path scope (points/lines)   */
+  VPT_ERR_UNSUPPORTED   = -5  /* scene outside the hot-path scope: a traversal limit, or a
+                                  shape that mixes points / lines with faces or with each other */
 } vpt_status;
 
 /* pathtrace_shader_type, yocto_pathtrace.h:74-84 (same order, same names) */
@@ -85,8 +86,9 @@ typedef struct vpt_bvh_node {
 } vpt_bvh_node;
 
 /* shape_data, yocto_shape.h:74-87 — offsets into the pooled vertex / element arrays.
- * Element indices stay shape-local (add *_offset when fetching).  Exactly one of
- * num_triangles / num_quads is non-zero on the hot path; points/lines are out of scope. */
+ * Element indices stay shape-local (add *_offset when fetching).  At most one of
+ * num_triangles / num_quads is non-zero; a shape of points or lines has neither and is
+ * described by its entry in vpt_scene_curves::shape_curves. */
 typedef struct vpt_shape {
   int32_t num_vertices;
   int32_t position_offset;  /* into positions[] (float3 units)                */
@@ -171,6 +173,18 @@ typedef struct vpt_light {
   int64_t cdf_offset; /* into light_cdf[] */
 } vpt_light;
 
+/* The points / lines of a shape (shape_data::points, lines, radius; yocto_shape.h:74-87), in the side array
+ * vpt_scene_curves::shape_curves (below).  A shape holds points OR lines OR faces: a shape that mixes them has no single
+ * behaviour in the reference (its BVH tests points first, its eval_* functions triangles first) and is refused
+ * with VPT_ERR_UNSUPPORTED.  Indices stay shape-local, as for faces.  Shapes of points or lines are never lights
+ * (make_lights, yocto_pathtrace.cpp:992): an emissive one emits when hit and is never sampled. */
+typedef struct vpt_shape_curves {
+  int32_t num_points, point_offset;  /* into points[] (int units)                                  */
+  int32_t num_lines, line_offset;    /* into lines[]  (int2 units)                                 */
+  int32_t radius_offset;             /* into radius[] (num_vertices floats), -1 if absent: only a
+                                        shape without points and lines may omit it                 */
+} vpt_shape_curves;
+
 /* The flattened (scene_data, bvh_scene, pathtrace_lights) triple. */
 typedef struct vpt_scene_desc {
   int32_t num_cameras;       const vpt_camera*          cameras;
@@ -204,6 +218,17 @@ typedef struct vpt_scene_desc {
   int64_t num_shape_bvh_nodes;  const vpt_bvh_node* shape_bvh_nodes; /* pooled */
   int64_t num_shape_bvh_prims;  const int32_t*      shape_bvh_prims; /* pooled, element ids */
 } vpt_scene_desc;
+
+/* The points and lines of a scene, BESIDE its descriptor: vpt_scene_desc keeps the layout that binaries built against earlier
+ * versions of this header fill in, and vpt_scene_create / vpt_multi_create keep meaning "no shape has points or lines".
+ * shape_curves: one entry per shape of the descriptor (desc->num_shapes); the pools are shared by all shapes.  The shape BVH of a
+ * points / lines shape is built over point_bounds(p, r) / line_bounds(p0, p1, r0, r1) (yocto_bvh.cpp:537-549). */
+typedef struct vpt_scene_curves {
+  const vpt_shape_curves* shape_curves;
+  int64_t num_points;     const int32_t* points;     /* int    */
+  int64_t num_lines;      const int32_t* lines;      /* int2   */
+  int64_t num_radius;     const float*   radius;     /* float  */
+} vpt_scene_curves;
 
 /* pathtrace_params, yocto_pathtrace.h:87-99 (fields the path reads) */
 typedef struct vpt_params {
@@ -245,6 +270,8 @@ const char* vpt_version(void);
  * inverse(frame, non_rigid=true) per instance with the reference's adjoint/determinant
  * formula (yocto_math.h:2802-2808, 2948-2956), uploads to `device`.                      */
 int  vpt_scene_create(const vpt_scene_desc* desc, int device, vpt_scene** out);
+/* the same for a scene whose shapes may hold points or lines (curves == NULL: vpt_scene_create) */
+int  vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* curves, int device, vpt_scene** out);
 void vpt_scene_destroy(vpt_scene* scene);
 
 /* ---- the drop-in for pathtrace_samples() --------------------------------------------
@@ -281,6 +308,7 @@ int vpt_render(vpt_scene* scene, const vpt_params* params, int nsamples, int wid
  * Like vpt_render, a render fails with VPT_ERR_HIP if a wave of the implicit kernel gave up on its watchdog. */
 typedef struct vpt_multi vpt_multi;
 int  vpt_multi_create(const vpt_scene_desc* desc, const int* devices, int ndev, vpt_multi** out);
+int  vpt_multi_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* curves, const int* devices, int ndev, vpt_multi** out);
 void vpt_multi_destroy(vpt_multi* m);
 int  vpt_multi_device_count(const vpt_multi* m);
 /* how vpt_multi_get_render moves the parts: "rccl", "peer-copy" (several devices, no RCCL) or "local" (one device) */

@@ -91,6 +91,7 @@ hip.vpt_last_error.restype = C.c_char_p
 hip.vpt_version.restype = C.c_char_p
 hip.vpt_device_count.restype = C.c_int
 hip.vpt_scene_create.argtypes = [_p, C.c_int, C.POINTER(_p)]
+hip.vpt_scene_create_curves.argtypes = [_p, _p, C.c_int, C.POINTER(_p)]
 hip.vpt_scene_destroy.argtypes = [_p]
 hip.vpt_scene_destroy.restype = None
 hip.vpt_render.argtypes = [_p, C.POINTER(VptParams), C.c_int, C.c_int, C.c_int, _p, _p, _p, C.POINTER(C.c_int)]
@@ -106,6 +107,7 @@ hip.vpt_build_bvh.argtypes = [C.c_int, _p, C.c_int, _p, C.c_int, C.POINTER(C.c_i
 hip.vpt_last_wave_costs.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int)]
 hip.vpt_scene_record_bytes.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 hip.vpt_multi_create.argtypes = [_p, C.POINTER(C.c_int), C.c_int, C.POINTER(_p)]
+hip.vpt_multi_create_curves.argtypes = [_p, _p, C.POINTER(C.c_int), C.c_int, C.POINTER(_p)]
 hip.vpt_multi_destroy.argtypes = [_p]
 hip.vpt_multi_destroy.restype = None
 hip.vpt_multi_device_count.argtypes = [_p]
@@ -135,6 +137,8 @@ host.vpth_scene_free.argtypes = [_p]
 host.vpth_scene_free.restype = None
 host.vpth_scene_desc.argtypes = [_p]
 host.vpth_scene_desc.restype = _p
+host.vpth_scene_curves.argtypes = [_p]
+host.vpth_scene_curves.restype = _p
 host.vpth_state_size.argtypes = [_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 host.vpth_make_state.argtypes = [_p, C.c_int, C.c_int, _p, _p, _p]
 host.vpth_scene_stats.argtypes = [_p, C.c_char_p, C.c_int]
@@ -240,6 +244,11 @@ class HostScene:
         """address of the vpt_scene_desc (valid while this object lives)"""
         return host.vpth_scene_desc(self.handle)
 
+    @property
+    def curves(self) -> Optional[int]:
+        """address of the vpt_scene_curves beside the descriptor, None when no shape has points or lines"""
+        return host.vpth_scene_curves(self.handle)
+
     def stats(self) -> str:
         buf = C.create_string_buffer(1 << 20)
         n = host.vpth_scene_stats(self.handle, buf, len(buf))
@@ -274,7 +283,7 @@ class DeviceScene:
     def __init__(self, scene: HostScene, device: int = 0):
         self.host_scene = scene  # keep the flattened arrays alive until the upload finished
         out = _p()
-        _check(hip.vpt_scene_create(scene.desc, device, C.byref(out)), "vpt_scene_create")
+        _check(hip.vpt_scene_create_curves(scene.desc, scene.curves, device, C.byref(out)), "vpt_scene_create")
         self.handle = out
         self.device = device
 
@@ -363,7 +372,7 @@ class MultiDeviceScene:
         self.host_scene = scene
         devs = (C.c_int * len(devices))(*devices)
         out = _p()
-        _check(hip.vpt_multi_create(scene.desc, devs, len(devices), C.byref(out)), "vpt_multi_create")
+        _check(hip.vpt_multi_create_curves(scene.desc, scene.curves, devs, len(devices), C.byref(out)), "vpt_multi_create")
         self.handle = out
 
     def pathtrace_samples(self, state: PathtraceState, params: PathtraceParams, count: int = 1) -> None:

@@ -16,10 +16,17 @@
 
 #include "vpt_implicit_kernel.hip.h"
 #include "vpt_kat_kernels.hip.h"
-#ifdef VPT_SPLIT_TUS   // the path tracers' instances of K1 are compiled in vpt_k1_volpath.hip / vpt_k1_path.hip
 #include "vpt_k1_instances.hip.h"
+#ifdef VPT_SPLIT_TUS   // the path tracers' instances of K1 are compiled in vpt_k1_volpath.hip / vpt_k1_path.hip / vpt_k1_curves.hip
 VPT_K1_SPLIT_INSTANCES(VPT_K1_DECLARE, K_VOLPATH)
 VPT_K1_SPLIT_INSTANCES(VPT_K1_DECLARE, K_PATH)
+VPT_K1_CURVES_INSTANCES(VPT_K1_DECLARE, K_VOLPATH)   // vpt_k1_curves.hip
+VPT_K1_CURVES_INSTANCES(VPT_K1_DECLARE, K_PATH)
+VPT_K1_CURVES_INSTANCES(VPT_K1_DECLARE, K_NAIVE)
+VPT_K1_CURVES_INSTANCES(VPT_K1_DECLARE, K_EYELIGHT)
+VPT_K1_CURVES_INSTANCES(VPT_K1_DECLARE, K_DEBUG)
+extern template __global__ void vpt_intersect_curves_kernel<true>(DScene, int, const float*, int, int*, float*, stack_cfg);
+extern template __global__ void vpt_intersect_curves_kernel<false>(DScene, int, const float*, int, int*, float*, stack_cfg);
 #endif
 #include <rocprim/rocprim.hpp>
 
@@ -169,6 +176,7 @@ struct vpt_scene {
   bool       timed = false;
   device_buffer d_watchdog;   // unsigned: waves of the implicit kernel that gave up (must stay 0; vpt_implicit_kernel.hip.h)
   int        light_features = 0;      // VPT_FEAT_* bits this scene's lights need from the mesh kernels
+  bool       curves = false;          // some instanced shape holds points or lines: the VPT_FEAT_CURVES instances of K1
   host_mirrors h;   // range checks of vpt_intersect, vpt_kat
 };
 
@@ -226,11 +234,13 @@ void vpt_scene_destroy(vpt_scene* s) {
   delete s;
 }
 
-int vpt_scene_create(const vpt_scene_desc* desc, int device, vpt_scene** out) {
+int vpt_scene_create(const vpt_scene_desc* desc, int device, vpt_scene** out) { return vpt_scene_create_curves(desc, nullptr, device, out); }
+
+int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* curves, int device, vpt_scene** out) {
   if (!desc || !out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   scene_tables t;   // every host-side refusal happens here, before any device call
-  if (int rc = prepare_scene(*desc, t)) return rc;
+  if (int rc = prepare_scene(*desc, curves, t)) return rc;
   int ndev = vpt_device_count();
   if (ndev <= 0) return vpt_set_error(VPT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
   if (device < 0 || device >= ndev) return vpt_set_error(VPT_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
@@ -263,6 +273,7 @@ int vpt_scene_create(const vpt_scene_desc* desc, int device, vpt_scene** out) {
 #undef UP
   D.shape_wnodes = D.scene_wnodes + t.scene_wnodes;
   s->stack_cap = t.stack_cap, s->stack_lds4 = t.stack_lds4, s->stack_spill4 = t.stack_spill4, s->light_features = t.light_features;
+  s->curves = t.curves;
   s->h = std::move(t.h);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -594,7 +605,9 @@ static int launch_mesh(const launch_ctx& L) {
     };
     // three instances: single-leaf mesh lights only / + emissive meshes with a BVH / everything (SDF lights too)
     // (+ the compact-record form of the first for the two path tracers on scenes of triangles; the pilot runs on the general records)
-    if ((K == K_VOLPATH || K == K_PATH) && (need & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SDF_LIGHTS)) == 0 && s->d.tri_prims && !is_pilot) {
+    // (a scene with points or lines: the one instance with every light feature and the point / line tests, vpt_k1_curves.hip)
+    if (s->curves) launch_feat(std::integral_constant<int, VPT_FEAT_ALL | VPT_FEAT_CURVES>{});
+    else if ((K == K_VOLPATH || K == K_PATH) && (need & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SDF_LIGHTS)) == 0 && s->d.tri_prims && !is_pilot) {
       if constexpr (K == K_VOLPATH || K == K_PATH) {
         if (L.stack.spill) launch(vpt_mesh_kernel<K, true, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_COMPACT_TRIS>);
         else launch(vpt_mesh_kernel<K, false, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_COMPACT_TRIS>);
@@ -795,7 +808,10 @@ int vpt_intersect(vpt_scene* s, int n, const float* rays, int instance, int32_t*
   if (int rc = stack_config(s, (long long)blocks * VPT_BLOCK, stack)) return rc;
   size_t lds = (size_t)s->stack_lds4 * 2 * VPT_BLOCK * sizeof(int);
   auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(VPT_BLOCK), lds, 0, s->d, n, d_rays.get<const float>(), instance, d_ids.get<int>(), d_uvt.get<float>(), stack); };
-  if (s->d.tri_prims) {   // a scene of triangles: through the short leaf records, as its path tracers go
+  if (s->curves) {   // points or lines: the leaf tests of the VPT_FEAT_CURVES instances
+    if (stack.spill) launch(vpt_intersect_curves_kernel<true>);
+    else launch(vpt_intersect_curves_kernel<false>);
+  } else if (s->d.tri_prims) {   // a scene of triangles: through the short leaf records, as its path tracers go
     if (stack.spill) launch(vpt_intersect_kernel<true, true>);
     else launch(vpt_intersect_kernel<false, true>);
   } else if (stack.spill) launch(vpt_intersect_kernel<true, false>);

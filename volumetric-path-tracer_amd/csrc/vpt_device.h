@@ -4,7 +4,8 @@
 //
 //   bvh node      32 B  = 2 x float4   {min.xyz, max.x} {max.yz, start, num|axis<<16|internal<<24}
 //   leaf record   64 B  = 4 x float4   the 4 corner positions of one quad (a triangle repeats its
-//                                      last corner) stored IN BVH LEAF ORDER, element id in p0.w:
+//                                      last corner; points and lines: VPT_LEAF_POINT below)
+//                                      stored IN BVH LEAF ORDER, element id in p0.w:
 //                                      a leaf's <=4 primitives are one contiguous <=256 B run, and
 //                                      the reference's prims[] -> quads[] -> positions[] double
 //                                      indirection (yocto_bvh.cpp:780-789) is gone from traversal
@@ -30,9 +31,17 @@ enum { VPT_FEAT_COMPACT_TRIS = 8,   // not a light feature: the instance reads D
        VPT_FEAT_LARGE_LIGHTS = 1,   // emissive meshes with a real BVH: sample_lights_pdf walks them with extra trips (ST_LPDF)
        VPT_FEAT_SDF_LIGHTS   = 2,   // SDF lights: a sphere trace inside sample_lights_pdf
        VPT_FEAT_SMALL_LIGHTS = 4,   // emissive meshes of a single BVH leaf (area-light quads): walked inline from their light records
-       VPT_FEAT_ALL          = 7 };
+       VPT_FEAT_ALL          = 7,
+       VPT_FEAT_CURVES       = 16 };  // not a light feature: some instanced shape holds points or lines (leaf records of kind 1 / 2 below)
 
-enum { VPT_SHP_TRIANGLES = 1, VPT_SHP_NORMALS = 2, VPT_SHP_TEXCOORDS = 4, VPT_SHP_COLORS = 8 };
+enum { VPT_SHP_TRIANGLES = 1, VPT_SHP_NORMALS = 2, VPT_SHP_TEXCOORDS = 4, VPT_SHP_COLORS = 8, VPT_SHP_POINTS = 16, VPT_SHP_LINES = 32 };
+
+// Leaf records of points and lines (instances compiled with VPT_FEAT_CURVES): the same 4 x float4 slot, element id in p0.w, the
+// record's kind in p3.w (int bits: 0 triangle / quad, VPT_LEAF_POINT, VPT_LEAF_LINE; faces leave it 0):
+//   point  {p, elem} {r, 0, 0, 0} {0, 0, 0, 0} {0, 0, 0, kind}
+//   line   {p0, elem} {p1, 0} {r0, r1, 0, 0} {0, 0, 0, kind}
+// leaf_attrs holds the one or two vertices' normals (corners 0, 1) and texcoords like a face's.
+enum { VPT_LEAF_POINT = 1, VPT_LEAF_LINE = 2 };
 
 struct DInstance {       // 128 B
   float4 inv[3];         // inverse(frame, non_rigid=true): rows packed as x,y,z columns + o: see pack

@@ -210,7 +210,7 @@ VPT_DEV bool slab_pass_signed(float nx, float ny, float nz, float fx, float fy, 
 #ifdef VPT_TRAVERSE_GUARD
 __device__ unsigned g_vpt_guard_trips;   // diagnostic build: queries that were cut short after VPT_TRAVERSE_GUARD loop rounds (must stay 0)
 #endif
-template <bool COMPACT = false, class STK>
+template <bool COMPACT = false, bool CURVES = false, class STK>
 VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_instance, const STK& stk) {
   constexpr int LS = COMPACT ? 3 : 4;   // float4 per leaf record
   hit_t r;
@@ -410,8 +410,12 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
       float4 r0 = n0, r1 = n1, r2 = n2, r3 = n3;
       rec += LS;
       n0 = rec[0], n1 = rec[1], n2 = rec[2], n3 = rec[LS - 1];
-      if (intersect_quad(co, cd, tmin, tmax, xyz(r0), xyz(r1), xyz(r2), xyz(r3), r.uv, tmax))   // (an accepted hit's distance IS the new tmax)
-        r.instance = cur_inst, r.prim = leafb + start + k;
+      if constexpr (CURVES) {   // points, lines or faces: the record's kind decides (vpt_device.h: VPT_LEAF_POINT)
+        if (intersect_record(co, cd, tmin, tmax, r0, r1, r2, r3, r.uv, tmax)) r.instance = cur_inst, r.prim = leafb + start + k;
+      } else {
+        if (intersect_quad(co, cd, tmin, tmax, xyz(r0), xyz(r1), xyz(r2), xyz(r3), r.uv, tmax))   // (an accepted hit's distance IS the new tmax)
+          r.instance = cur_inst, r.prim = leafb + start + k;
+      }
     }
     // A hit with a NaN distance (a triangle of denormal size met exactly at a corner: 0 * inf) leaves tmax = NaN, and the reference's
     // fmin(far, tmax) = (far < tmax) ? far : tmax then fails every later box test.  The hardware min / max of the fast box forms drop a
@@ -528,12 +532,23 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
       f2    uv = mk2(0, 0);
       float t = 0;
       bool  hit = false;
-      if (b + j < num && !bad) {
-        const float4* rec = leaf_rec<COMPACT>(sc, gleafb + start + b + j);
-        float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[LS - 1];
-        hit  = intersect_quad(gco, gcd, tmin, gtmax, xyz(r0), xyz(r1), xyz(r2), xyz(r3), uv, t);
+      if constexpr (CURVES) {   // a point or line record: the group hands the leaf to its owner's own form, like a NaN
+        bool curve = false;
+        if (b + j < num && !bad) {
+          const float4* rec = leaf_rec<COMPACT>(sc, gleafb + start + b + j);
+          float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[LS - 1];
+          curve = __float_as_int(r3.w) != 0;
+          if (!curve) hit = intersect_quad(gco, gcd, tmin, gtmax, xyz(r0), xyz(r1), xyz(r2), xyz(r3), uv, t);
+        }
+        bad = bad || quad_or((hit && t != t) || curve ? 1 : 0) != 0;
+      } else {
+        if (b + j < num && !bad) {
+          const float4* rec = leaf_rec<COMPACT>(sc, gleafb + start + b + j);
+          float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[LS - 1];
+          hit  = intersect_quad(gco, gcd, tmin, gtmax, xyz(r0), xyz(r1), xyz(r2), xyz(r3), uv, t);
+        }
+        bad = bad || quad_or(hit && t != t ? 1 : 0) != 0;
       }
-      bad = bad || quad_or(hit && t != t ? 1 : 0) != 0;
       // smallest t of the four, on a tie the later primitive (a hit's t is finite: t <= tmax <= flt_max)
       float key = hit && !bad ? t : __builtin_inff();
       int   idx = j;
@@ -711,9 +726,17 @@ VPT_DEV float large_light_hop(const DScene& sc, int light_id, const hit_t& h, f3
 
 // The shading point of a surface hit: eval_shading_position, eval_shading_normal and eval_material
 // (yocto_scene.cpp:460-579) in one go.  `prim` is the hit's slot in leaf_prims / leaf_attrs.
-template <bool COMPACT = false>
+template <bool COMPACT = false, bool CURVES = false>
 VPT_DEV void eval_surface_point(const DScene& sc, const DInstance& inst, const vpt_material& mat, int prim, int element, f2 uv,
     f3 outgoing, f3& position, f3& normal, mpoint& m) {
+  if constexpr (CURVES) {   // points and lines: the general path through the element's vertices (vpt_scene.hip.h: curve_*)
+    if (inst.shape_flags & (VPT_SHP_POINTS | VPT_SHP_LINES)) {
+      position = curve_shading_position(sc, inst, element, uv);
+      normal   = curve_shading_normal(sc, inst, element, uv, outgoing);
+      m        = eval_material_at(sc, mat, curve_texcoord(sc, inst, element, uv), curve_color(sc, inst, element, uv));
+      return;
+    }
+  }
   f2 texcoord;
   f4 color_shp = mk4(1, 1, 1, 1);
   if ((inst.shape_flags & (VPT_SHP_NORMALS | VPT_SHP_COLORS)) == VPT_SHP_NORMALS) {
@@ -825,7 +848,7 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
     const bool lpdf_query = HAS_LARGE && query && state == ST_LPDF;
     const int  qinst      = lpdf_query ? sc.lights[lp_light].instance : -1;
     VPT_T0(TM_QUERY);
-    hit_t h = traverse<(FEAT & VPT_FEAT_COMPACT_TRIS) != 0>(sc, query, lpdf_query ? lp_pos : ray.o, ray.d, qinst, stk);
+    hit_t h = traverse<(FEAT & VPT_FEAT_COMPACT_TRIS) != 0, (FEAT & VPT_FEAT_CURVES) != 0>(sc, query, lpdf_query ? lp_pos : ray.o, ray.d, qinst, stk);
     VPT_T1(TM_QUERY);
     if constexpr (!HAS_LARGE) {
       // without light walks that span trips (ST_LPDF) a pending MIS evaluation never outlives its trip: say so, or its seven words
@@ -850,7 +873,18 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
         finish = true;
       } else if constexpr (SH == K_DEBUG) {   // shade_normal / texcoord / color, cpp:893-930
         const DInstance& inst = sc.instances[h.instance];
-        if (pr.shader == VPT_SHADER_NORMAL) radiance = eval_shading_normal(sc, inst, h.element, h.uv, -ray.d);
+        bool curve = false;
+        if constexpr ((FEAT & VPT_FEAT_CURVES) != 0) {   // points and lines (vpt_scene.hip.h: curve_*)
+          if (inst.shape_flags & (VPT_SHP_POINTS | VPT_SHP_LINES)) {
+            curve = true;
+            const f2 t = curve_texcoord(sc, inst, h.element, h.uv);
+            if (pr.shader == VPT_SHADER_NORMAL) radiance = curve_shading_normal(sc, inst, h.element, h.uv, -ray.d);
+            else if (pr.shader == VPT_SHADER_TEXCOORD) radiance = mk3(t.x, t.y, 0);
+            else radiance = eval_material_at(sc, sc.materials[inst.material], t, curve_color(sc, inst, h.element, h.uv)).color;
+          }
+        }
+        if (curve) {
+        } else if (pr.shader == VPT_SHADER_NORMAL) radiance = eval_shading_normal(sc, inst, h.element, h.uv, -ray.d);
         else if (pr.shader == VPT_SHADER_TEXCOORD) {
           f2 t     = eval_texcoord(sc, inst, h.element, h.uv);
           radiance = mk3(t.x, t.y, 0);
@@ -883,7 +917,7 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
         if (!in_volume) {
           const DInstance& inst = sc.instances[h.instance];
           VPT_T0(TM_SURF_GEOM);
-          eval_surface_point<(FEAT & VPT_FEAT_COMPACT_TRIS) != 0>(sc, inst, sc.materials[inst.material], h.prim, h.element, h.uv, outgoing, position, normal, m);
+          eval_surface_point<(FEAT & VPT_FEAT_COMPACT_TRIS) != 0, (FEAT & VPT_FEAT_CURVES) != 0>(sc, inst, sc.materials[inst.material], h.prim, h.element, h.uv, outgoing, position, normal, m);
           VPT_T1(TM_SURF_GEOM);
           if (m.opacity < 1 && rand1f(rng) >= m.opacity) {
             ray = make_ray(position + ray.d * 1e-2f, ray.d);   // bounce -= 1; continue

@@ -260,6 +260,10 @@ void download_part(vpt_multi* m, int i, float* image_rgba, int32_t* hits, uint64
 extern "C" {
 
 int vpt_multi_create(const vpt_scene_desc* desc, const int* devices, int ndev, vpt_multi** out) {
+  return vpt_multi_create_curves(desc, nullptr, devices, ndev, out);
+}
+
+int vpt_multi_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* curves, const int* devices, int ndev, vpt_multi** out) {
   if (!desc || !devices || !out || ndev < 1 || ndev > 64) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
   *out = nullptr;
   auto m = new vpt_multi{};
@@ -269,7 +273,7 @@ int vpt_multi_create(const vpt_scene_desc* desc, const int* devices, int ndev, v
     auto& p  = m->parts[(size_t)i];
     p.device = devices[i];
     if (!seen.insert(devices[i]).second) m->distinct = false;
-    if (int rc = vpt_scene_create(desc, devices[i], &p.scene)) {   // validates, uploads; sets the error text
+    if (int rc = vpt_scene_create_curves(desc, curves, devices[i], &p.scene)) {   // validates, uploads; sets the error text
       vpt_multi_destroy(m);
       return rc;
     }

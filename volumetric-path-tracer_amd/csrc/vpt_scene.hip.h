@@ -114,6 +114,40 @@ VPT_DEV bool intersect_bbox(f3 ro, f3 dinv, float tmin_, float tmax_, f3 bmin, f
   return t0 <= t1;
 }
 
+// intersect_point(ray, p, r, uv, dist), yocto_geometry.h:683-702: the distance to the ray's closest approach, uv = {0, 0}
+VPT_DEV bool intersect_point(f3 ro, f3 rd, float tmin, float tmax, f3 p, float r, f2& uv, float& dist) {
+  f3    w = p - ro;
+  float t = dot(w, rd) / dot(rd, rd);
+  if (t < tmin || t > tmax) return false;
+  f3 rp = ro + rd * t, prp = p - rp;
+  if (dot(prp, prp) > r * r) return false;
+  uv = mk2(0, 0), dist = t;
+  return true;
+}
+// intersect_line(ray, p0, p1, r0, r1, uv, dist), yocto_geometry.h:705-746, same operation order: det == 0 misses,
+// uv = {s, sqrt(d2) / r} with s the clamped segment parameter
+VPT_DEV bool intersect_line(f3 ro, f3 rd, float tmin, float tmax, f3 p0, f3 p1, float r0, float r1, f2& uv, float& dist) {
+  f3    u = rd, v = p1 - p0, w = ro - p0;
+  float a = dot(u, u), b = dot(u, v), c = dot(v, v), d = dot(u, w), e = dot(v, w);
+  float det = a * c - b * b;
+  if (det == 0) return false;
+  float t = (b * e - c * d) / det, s = (a * e - b * d) / det;
+  if (t < tmin || t > tmax) return false;
+  s = clampf(s, 0.0f, 1.0f);
+  f3    pr = ro + rd * t, pl = p0 + (p1 - p0) * s, prl = pr - pl;
+  float d2 = dot(prl, prl), r = r0 * (1 - s) + r1 * s;
+  if (d2 > r * r) return false;
+  uv = mk2(s, sqrtf(d2) / r), dist = t;
+  return true;
+}
+// one leaf record of a scene with points or lines (vpt_device.h: VPT_LEAF_POINT / VPT_LEAF_LINE in p3.w, 0 for a face)
+VPT_DEV bool intersect_record(f3 ro, f3 rd, float tmin, float tmax, float4 r0, float4 r1, float4 r2, float4 r3, f2& uv, float& dist) {
+  const int kind = __float_as_int(r3.w);
+  if (kind == VPT_LEAF_POINT) return intersect_point(ro, rd, tmin, tmax, xyz(r0), r1.x, uv, dist);
+  if (kind == VPT_LEAF_LINE) return intersect_line(ro, rd, tmin, tmax, xyz(r0), xyz(r1), r2.x, r2.y, uv, dist);
+  return intersect_quad(ro, rd, tmin, tmax, xyz(r0), xyz(r1), xyz(r2), xyz(r3), uv, dist);
+}
+
 // a primitive slot's records (vpt_device.h: leaf_prims / leaf_attrs, or tri_prims / tri_attrs in the instances compiled for COMPACT)
 template <bool COMPACT>
 VPT_DEV const float4* leaf_rec(const DScene& sc, int slot) {
@@ -372,6 +406,54 @@ VPT_DEV mpoint eval_material_at(const DScene& sc, const vpt_material& m, f2 texc
 VPT_DEV mpoint eval_material(const DScene& sc, const DInstance& inst, int element, f2 uv) {
   return eval_material_at(sc, sc.materials[inst.material], eval_texcoord(sc, inst, element, uv), eval_color(sc, inst, element, uv));
 }
+// The shading point of a hit on points or lines (instances compiled with VPT_FEAT_CURVES; the shape's flags say which):
+// eval_shading_position, eval_shading_normal and eval_material of yocto_scene.cpp:279-379, 460-526 through the element's
+// vertex indices (elems repeat the last vertex: {p, p, p, p} / {x, y, y, y}).  Lines: position and attributes interpolated
+// along uv.x, normal orthonormalize(outgoing, eval_normal) (no normal map, no flip, no refractive case).  Points: the
+// shape-space position WITHOUT the instance frame (eval_position(shape, ...), yocto_scene.cpp:468), the "HACK: sphere"
+// normal from uv through the frame, attributes of the one vertex.
+VPT_DEV f3 curve_shading_normal(const DScene& sc, const DInstance& inst, int element, f2 uv, f3 outgoing) {
+  const frame f = unpack_frame(inst.fwd[0], inst.fwd[1], inst.fwd[2]);
+  if (inst.shape_flags & VPT_SHP_POINTS)
+    return transform_direction(f, mk3(cosf(2 * VPT_PI * uv.x) * sinf(VPT_PI * uv.y), sinf(2 * VPT_PI * uv.x) * sinf(VPT_PI * uv.y), cosf(VPT_PI * uv.y)));
+  const DShape& sh = sc.shapes[inst.shape];
+  int4 e = sc.elems[sh.elem_offset + element];
+  f3   n;
+  if (sh.normal_offset < 0) {   // eval_element_normal: transform_normal(frame, line_tangent(p0, p1))
+    const float4* pos = sc.positions + sh.vertex_offset;
+    n = transform_direction(f, normalize(xyz(pos[e.y]) - xyz(pos[e.x])));
+  } else {
+    const float4* nrm = sc.normals + sh.normal_offset;
+    n = transform_direction(f, normalize(xyz(nrm[e.x]) * (1 - uv.x) + xyz(nrm[e.y]) * uv.x));
+  }
+  return orthonormalize(outgoing, n);
+}
+VPT_DEV f2 curve_texcoord(const DScene& sc, const DInstance& inst, int element, f2 uv) {
+  const DShape& sh = sc.shapes[inst.shape];
+  if (sh.texcoord_offset < 0) return uv;
+  int4 e = sc.elems[sh.elem_offset + element];
+  const float2* tc = sc.texcoords + sh.texcoord_offset;
+  float2 a = tc[e.x], b = tc[e.y];
+  if (inst.shape_flags & VPT_SHP_POINTS) return mk2(a.x, a.y);
+  return mk2(a.x, a.y) * (1 - uv.x) + mk2(b.x, b.y) * uv.x;
+}
+VPT_DEV f4 curve_color(const DScene& sc, const DInstance& inst, int element, f2 uv) {
+  const DShape& sh = sc.shapes[inst.shape];
+  if (sh.color_offset < 0) return mk4(1, 1, 1, 1);
+  int4 e = sc.elems[sh.elem_offset + element];
+  const float4* col = sc.colors + sh.color_offset;
+  float4 a = col[e.x], b = col[e.y];
+  if (inst.shape_flags & VPT_SHP_POINTS) return mk4(a.x, a.y, a.z, a.w);
+  return mk4(a.x, a.y, a.z, a.w) * (1 - uv.x) + mk4(b.x, b.y, b.z, b.w) * uv.x;
+}
+VPT_DEV f3 curve_shading_position(const DScene& sc, const DInstance& inst, int element, f2 uv) {
+  const DShape& sh = sc.shapes[inst.shape];
+  int4 e = sc.elems[sh.elem_offset + element];
+  const float4* pos = sc.positions + sh.vertex_offset;
+  if (inst.shape_flags & VPT_SHP_POINTS) return xyz(pos[e.x]);
+  return transform_point(unpack_frame(inst.fwd[0], inst.fwd[1], inst.fwd[2]), xyz(pos[e.x]) * (1 - uv.x) + xyz(pos[e.y]) * uv.x);
+}
+
 // eval_position + eval_normal + eval_texcoord (yocto_scene.cpp:279-379) of a hit from its primitive slot: the same
 // corner choice (pick_corners), the same interpolation, the same values - fetched from leaf_prims / leaf_attrs.
 // Only for shapes with vertex normals and without vertex colours (the callers check shape_flags).

@@ -123,7 +123,18 @@ int check_nodes(const vpt_bvh_node* nodes, long long count, long long nprims, co
   return VPT_OK;
 }
 
-int validate(const vpt_scene_desc& d) {
+// the points / lines entry of shape i (all zero when the descriptor has no side array)
+vpt_shape_curves curves_of(const vpt_scene_curves& cs, int i) {
+  vpt_shape_curves c = {0, 0, 0, 0, -1};
+  if (cs.shape_curves) c = cs.shape_curves[i];
+  return c;
+}
+bool has_curves(const vpt_scene_curves& cs, int i) {
+  vpt_shape_curves c = curves_of(cs, i);
+  return c.num_points != 0 || c.num_lines != 0;
+}
+
+int validate(const vpt_scene_desc& d, const vpt_scene_curves& cs) {
   REQUIRE(d.num_cameras > 0 && d.cameras, "scene has no cameras");
 #define TABLE(n, p) REQUIRE((n) >= 0 && ((n) == 0 || (p) != nullptr), "table %s is null", #p)
   TABLE(d.num_instances, d.instances); TABLE(d.num_shapes, d.shapes); TABLE(d.num_materials, d.materials);
@@ -135,6 +146,7 @@ int validate(const vpt_scene_desc& d) {
   TABLE(d.num_light_cdf, d.light_cdf); TABLE(d.num_scene_bvh_nodes, d.scene_bvh_nodes);
   TABLE(d.num_scene_bvh_prims, d.scene_bvh_prims); TABLE(d.num_shape_bvh_nodes, d.shape_bvh_nodes);
   TABLE(d.num_shape_bvh_prims, d.shape_bvh_prims);
+  TABLE(cs.num_points, cs.points); TABLE(cs.num_lines, cs.lines); TABLE(cs.num_radius, cs.radius);
 #undef TABLE
   auto tex_ok = [&](int t) { return t >= -1 && t < d.num_textures; };
   for (int i = 0; i < d.num_shapes; i++) {
@@ -147,6 +159,24 @@ int validate(const vpt_scene_desc& d) {
     REQUIRE(s.num_quads >= 0 && s.quad_offset >= 0 && (long long)s.quad_offset + s.num_quads <= d.num_quads, "shape %d: quads out of range", i);
     REQUIRE(s.num_triangles == 0 || s.num_quads == 0, "shape %d: both triangles and quads", i);
     long long nel = s.num_triangles ? s.num_triangles : s.num_quads;
+    const vpt_shape_curves c = curves_of(cs, i);
+    REQUIRE(c.num_points >= 0 && c.point_offset >= 0 && (long long)c.point_offset + c.num_points <= cs.num_points, "shape %d: points out of range", i);
+    REQUIRE(c.num_lines >= 0 && c.line_offset >= 0 && (long long)c.line_offset + c.num_lines <= cs.num_lines, "shape %d: lines out of range", i);
+    if (c.num_points || c.num_lines) {
+      // the reference's BVH tests points, then lines, then faces; its eval_* functions faces first: a mixed shape has no single behaviour
+      if ((c.num_points != 0) + (c.num_lines != 0) + (nel != 0) > 1)
+        return vpt_set_error(VPT_ERR_UNSUPPORTED, "shape %d mixes points, lines and faces", i);
+      REQUIRE(c.radius_offset >= 0 && (long long)c.radius_offset + s.num_vertices <= cs.num_radius, "shape %d: radius out of range", i);
+      for (long long k = 0; k < c.num_points; k++) {
+        int v = cs.points[c.point_offset + k];
+        REQUIRE(v >= 0 && v < s.num_vertices, "shape %d: point vertex index out of range", i);
+      }
+      for (long long k = 0; k < 2LL * c.num_lines; k++) {
+        int v = cs.lines[2LL * c.line_offset + k];
+        REQUIRE(v >= 0 && v < s.num_vertices, "shape %d: line vertex index out of range", i);
+      }
+      nel = c.num_points ? c.num_points : c.num_lines;
+    }
     for (long long k = 0; k < 3LL * s.num_triangles; k++) {
       int v = d.triangles[3LL * s.triangle_offset + k];
       REQUIRE(v >= 0 && v < s.num_vertices, "shape %d: triangle vertex index out of range", i);
@@ -224,7 +254,7 @@ int validate(const vpt_scene_desc& d) {
 }
 
 // vertex pools, shapes and elements, leaf records and their vertex attributes, the compact records of a scene of triangles
-void build_geometry(const vpt_scene_desc& d, scene_tables& t) {
+void build_geometry(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_tables& t) {
   t.positions.resize((size_t)d.num_positions), t.normals.resize((size_t)d.num_normals), t.colors.resize((size_t)d.num_colors);
   t.texcoords.resize((size_t)d.num_texcoords);
   for (long long i = 0; i < d.num_positions; i++) t.positions[i] = make_float4(d.positions[3 * i], d.positions[3 * i + 1], d.positions[3 * i + 2], 0);
@@ -241,11 +271,20 @@ void build_geometry(const vpt_scene_desc& d, scene_tables& t) {
     o.num_nodes = sh.num_bvh_nodes, o.node_offset = sh.bvh_node_offset;
     o.is_triangles = sh.num_triangles != 0;
     o.num_elems = o.is_triangles ? sh.num_triangles : sh.num_quads;
+    const vpt_shape_curves cv = curves_of(cs, i);
+    const int kind = cv.num_points ? VPT_LEAF_POINT : cv.num_lines ? VPT_LEAF_LINE : 0;
+    if (kind) o.num_elems = kind == VPT_LEAF_POINT ? cv.num_points : cv.num_lines;
     o.elem_offset = (int)t.elems.size(), o.leaf_offset = (int)(leafs.size() / 4);
     o.vertex_offset = sh.position_offset, o.normal_offset = sh.normal_offset;
     o.texcoord_offset = sh.texcoord_offset, o.color_offset = sh.color_offset;
     for (int e = 0; e < o.num_elems; e++) {
-      if (o.is_triangles) {
+      if (kind == VPT_LEAF_POINT) {   // elements of points and lines repeat their last vertex, like a triangle's
+        int p = cs.points[(long long)cv.point_offset + e];
+        t.elems.push_back(make_int4(p, p, p, p));
+      } else if (kind == VPT_LEAF_LINE) {
+        const int32_t* l = cs.lines + 2LL * (cv.line_offset + e);
+        t.elems.push_back(make_int4(l[0], l[1], l[1], l[1]));
+      } else if (o.is_triangles) {
         const int32_t* tr = d.triangles + 3LL * (sh.triangle_offset + e);
         t.elems.push_back(make_int4(tr[0], tr[1], tr[2], tr[2]));
       } else {
@@ -260,12 +299,21 @@ void build_geometry(const vpt_scene_desc& d, scene_tables& t) {
       int  e = d.shape_bvh_prims[sh.bvh_prim_offset + k];
       t.h.prim_slot[(size_t)o.elem_offset + e] = o.leaf_offset + k;
       int4 q = t.elems[(size_t)o.elem_offset + e];
-      for (int c = 0; c < 4; c++) {
-        int    v = c == 0 ? q.x : c == 1 ? q.y : c == 2 ? q.z : q.w;
-        float4 p = t.positions[(size_t)sh.position_offset + v];
-        int    tag = c == 0 ? e : 0;
-        memcpy(&p.w, &tag, 4);
-        leafs.push_back(p);
+      if (kind) {   // vpt_device.h: VPT_LEAF_POINT / VPT_LEAF_LINE
+        const float* rad = cs.radius + cv.radius_offset;
+        float4 p0 = t.positions[(size_t)sh.position_offset + q.x], p1 = t.positions[(size_t)sh.position_offset + q.y];
+        float4 r[4] = {p0, kind == VPT_LEAF_LINE ? p1 : make_float4(rad[q.x], 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
+        if (kind == VPT_LEAF_LINE) r[1].w = 0, r[2] = make_float4(rad[q.x], rad[q.y], 0, 0);
+        memcpy(&r[0].w, &e, 4), memcpy(&r[3].w, &kind, 4);
+        for (int c = 0; c < 4; c++) leafs.push_back(r[c]);
+      } else {
+        for (int c = 0; c < 4; c++) {
+          int    v = c == 0 ? q.x : c == 1 ? q.y : c == 2 ? q.z : q.w;
+          float4 p = t.positions[(size_t)sh.position_offset + v];
+          int    tag = c == 0 ? e : 0;
+          memcpy(&p.w, &tag, 4);
+          leafs.push_back(p);
+        }
       }
       // the corners' normals, then their texcoords (zeros where the shape has none: never read then)
       float tc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -354,7 +402,7 @@ int build_quad_nodes_and_stacks(const vpt_scene_desc& d, scene_tables& t) {
 }
 
 // instance records, the enter records of the scene-BVH slots, and the inverse frames of environments and SDFs
-void build_instances(const vpt_scene_desc& d, scene_tables& t) {
+void build_instances(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_tables& t) {
   t.instances.resize((size_t)d.num_instances);
   for (int i = 0; i < d.num_instances; i++) {
     DInstance& in = t.instances[i];
@@ -365,7 +413,9 @@ void build_instances(const vpt_scene_desc& d, scene_tables& t) {
     in.shape = d.instances[i].shape, in.material = d.instances[i].material;
     const vpt_shape& sh = d.shapes[d.instances[i].shape];
     in.shape_flags = (sh.num_triangles != 0 ? VPT_SHP_TRIANGLES : 0) | (sh.normal_offset >= 0 ? VPT_SHP_NORMALS : 0) |
-                     (sh.texcoord_offset >= 0 ? VPT_SHP_TEXCOORDS : 0) | (sh.color_offset >= 0 ? VPT_SHP_COLORS : 0);
+                     (sh.texcoord_offset >= 0 ? VPT_SHP_TEXCOORDS : 0) | (sh.color_offset >= 0 ? VPT_SHP_COLORS : 0) |
+                     (curves_of(cs, in.shape).num_points ? VPT_SHP_POINTS : 0) | (curves_of(cs, in.shape).num_lines ? VPT_SHP_LINES : 0);
+    t.curves = t.curves || has_curves(cs, in.shape);
     in.translation_only = f.x.x == 1 && f.x.y == 0 && f.x.z == 0 && f.y.x == 0 && f.y.y == 1 && f.y.z == 0 &&
                           f.z.x == 0 && f.z.y == 0 && f.z.z == 1;
     t.h.inst_shape.push_back(d.instances[i].shape);
@@ -576,17 +626,19 @@ void build_sdf_records(const vpt_scene_desc& d, scene_tables& t) {
 
 }  // namespace
 
-int prepare_scene(const vpt_scene_desc& d, scene_tables& t) {
-  if (int rc = validate(d)) return rc;
+int prepare_scene(const vpt_scene_desc& d, const vpt_scene_curves* curves, scene_tables& t) {
+  const vpt_scene_curves none = {};
+  const vpt_scene_curves& cs = curves ? *curves : none;
+  if (int rc = validate(d, cs)) return rc;
   DScene& D = t.d;
   D.num_cameras = d.num_cameras, D.num_instances = d.num_instances, D.num_shapes = d.num_shapes;
   D.num_materials = d.num_materials, D.num_textures = d.num_textures, D.num_environments = d.num_environments;
   D.num_volumes = d.num_volumes, D.num_vol_instances = d.num_vol_instances, D.num_sdfs = d.num_sdfs;
   D.num_lights = d.num_lights, D.num_scene_nodes = d.num_scene_bvh_nodes, D.num_scene_prims = d.num_scene_bvh_prims;
   D.group_forms = getenv("VPT_NO_GROUP_FORMS") ? 0 : 1;   // A/B switch of the tests: the two forms of a phase must give the same bits
-  build_geometry(d, t);
+  build_geometry(d, cs, t);
   if (int rc = build_quad_nodes_and_stacks(d, t)) return rc;
-  build_instances(d, t);
+  build_instances(d, cs, t);
   // sRGB decode LUT: byte_to_float then srgb_to_rgb, yocto_color.h:212-227, evaluated with the host powf
   t.srgb_lut.resize(256);
   for (int b = 0; b < 256; b++) {

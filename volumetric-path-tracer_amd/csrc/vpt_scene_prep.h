@@ -36,8 +36,10 @@ struct scene_tables {
   // traversal stacks: binary-BVH walk of the implicit kernels (refs only); quad-node traversal entries in LDS / in HBM
   int stack_cap = 16, stack_lds4 = 8, stack_spill4 = 0;
   int light_features = 0;   // VPT_FEAT_* bits this scene's lights need from the mesh kernels
+  bool curves = false;      // some instanced shape holds points or lines: the mesh kernels' VPT_FEAT_CURVES instances
   host_mirrors h;
 };
 
-// validate(desc), then every table; VPT_ERR_INVALID_ARG for a bad descriptor, VPT_ERR_UNSUPPORTED for a scene past a traversal limit
-int prepare_scene(const vpt_scene_desc& desc, scene_tables& out);
+// validate(desc, curves), then every table (curves may be null: no shape has points or lines); VPT_ERR_INVALID_ARG for a bad descriptor, VPT_ERR_UNSUPPORTED for a scene past a traversal
+// limit or with a shape that mixes points, lines and faces
+int prepare_scene(const vpt_scene_desc& desc, const vpt_scene_curves* curves, scene_tables& out);

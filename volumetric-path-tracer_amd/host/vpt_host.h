@@ -25,6 +25,7 @@ inline const int invalidid = -1;
 struct vec2f { float x = 0, y = 0; };
 struct vec3f { float x = 0, y = 0, z = 0; };
 struct vec4f { float x = 0, y = 0, z = 0, w = 0; };
+struct vec2i { int x = 0, y = 0; };
 struct vec3i { int x = 0, y = 0, z = 0; };
 struct vec4i { int x = 0, y = 0, z = 0, w = 0; };
 struct vec4b { uint8_t x = 0, y = 0, z = 0, w = 0; };
@@ -58,13 +59,15 @@ struct material_data {
       scattering_tex = invalidid, normal_tex = invalidid;
 };
 struct shape_data {
-  vector<int>   points    = {};  // out of hot-path scope: load keeps them, flatten rejects them
+  vector<int>   points    = {};
+  vector<vec2i> lines     = {};
   vector<vec3i> triangles = {};
   vector<vec4i> quads     = {};
   vector<vec3f> positions = {};
   vector<vec3f> normals   = {};
   vector<vec2f> texcoords = {};
   vector<vec4f> colors    = {};
+  vector<float> radius    = {};
 };
 struct instance_data {
   frame3f frame = {};
@@ -231,13 +234,16 @@ struct flat_scene {
   vector<vpt_volume_instance> vol_instances; vector<vpt_sdf> sdfs; vector<vpt_light> lights;
   vector<vec3f> positions, normals; vector<vec2f> texcoords; vector<vec4f> colors;
   vector<vec3i> triangles; vector<vec4i> quads;
+  vector<vpt_shape_curves> shape_curves; vector<int> points; vector<vec2i> lines; vector<float> radius;
+  vpt_scene_curves curves = {};   // points and lines beside desc (include/vpt.h); shape_curves null: no shape has any
+  const vpt_scene_curves* curves_or_null() const { return curves.shape_curves ? &curves : nullptr; }
   vector<vec4f> texels_f; vector<vec4b> texels_b; vector<float> voxels, light_cdf;
   vector<bvh_node> scene_nodes, shape_nodes; vector<int> scene_prims, shape_prims;
   flat_scene() = default;
   flat_scene(const flat_scene&) = delete;
   flat_scene& operator=(const flat_scene&) = delete;
 };
-// Throws std::invalid_argument for features outside the hot-path scope (points, lines).
+// Throws std::invalid_argument for a shape that mixes points, lines and faces (vpt.h: vpt_shape_curves).
 void flatten_scene(flat_scene& flat, const scene_data& scene, const bvh_scene& bvh,
     const pathtrace_lights& lights);
 vpt_params to_abi(const pathtrace_params& params);

@@ -135,6 +135,7 @@ int vpth_build_bvh_host(const float* bboxes, int n, vpt_bvh_node* nodes, int* nu
 }
 void vpth_scene_free(void* h) { delete (host_scene*)h; }
 const vpt_scene_desc* vpth_scene_desc(void* h) { return &((host_scene*)h)->flat->desc; }
+const vpt_scene_curves* vpth_scene_curves(void* h) { return ((host_scene*)h)->flat->curves_or_null(); }   // null: no points or lines
 
 // make_state dimensions (yocto_pathtrace.cpp:964-970)
 int vpth_state_size(void* h, int camera, int resolution, int* width, int* height) {
@@ -189,7 +190,15 @@ int vpth_scene_stats(void* hh, char* buf, int buflen) {
         sh.quads.size(), (unsigned long long)fnv1a(sh.positions), (unsigned long long)fnv1a(sh.normals),
         (unsigned long long)fnv1a(sh.texcoords), (unsigned long long)fnv1a(sh.triangles),
         (unsigned long long)fnv1a(sh.quads), b.nodes.size(), (unsigned long long)fnv1a(b.nodes),
-        (unsigned long long)fnv1a(b.primitives), i + 1 < h.scene.shapes.size() ? "," : "");
+        (unsigned long long)fnv1a(b.primitives), "");
+    // shapes of points or lines only: the lines of a scene of faces stay those of oracle/ref_driver.cpp --stats
+    if (!sh.points.empty() || !sh.lines.empty() || !sh.radius.empty()) {
+      s.erase(s.size() - 2);   // "}\n"
+      add(", \"points\": %zu, \"lines\": %zu, \"radius\": %zu, \"points_fnv\": \"%016llx\", \"lines_fnv\": \"%016llx\", \"radius_fnv\": \"%016llx\"}\n",
+          sh.points.size(), sh.lines.size(), sh.radius.size(), (unsigned long long)fnv1a(sh.points), (unsigned long long)fnv1a(sh.lines),
+          (unsigned long long)fnv1a(sh.radius));
+    }
+    if (i + 1 < h.scene.shapes.size()) s.insert(s.size() - 1, ",");
   }
   add(" ],\n \"textures\": [\n");
   for (size_t i = 0; i < h.scene.textures.size(); i++) {

@@ -139,7 +139,25 @@ bvh_data build_bvh_host(const float* bboxes, int n) {
 static bvh_data make_shape_bvh(const shape_data& shape, int device) {
   auto bvh    = bvh_data{};
   auto bboxes = vector<bbox3f>{};
-  if (!shape.triangles.empty()) {
+  // point_bounds(p, r) / line_bounds(p0, p1, r0, r1), yocto_geometry.h:461-471, in the reference's order: points, lines, faces
+  auto sub = [](const vec3f& p, float r) { return vec3f{p.x - r, p.y - r, p.z - r}; };
+  auto add = [](const vec3f& p, float r) { return vec3f{p.x + r, p.y + r, p.z + r}; };
+  if (!shape.points.empty()) {
+    bboxes.resize(shape.points.size());
+    for (size_t i = 0; i < bboxes.size(); i++) {
+      auto& p = shape.positions[shape.points[i]];
+      auto  r = shape.radius[shape.points[i]];
+      bboxes[i] = {vmin(sub(p, r), add(p, r)), vmax(sub(p, r), add(p, r))};
+    }
+  } else if (!shape.lines.empty()) {
+    bboxes.resize(shape.lines.size());
+    for (size_t i = 0; i < bboxes.size(); i++) {
+      auto& l = shape.lines[i];
+      auto &p0 = shape.positions[l.x], &p1 = shape.positions[l.y];
+      auto  r0 = shape.radius[l.x], r1 = shape.radius[l.y];
+      bboxes[i] = {vmin(sub(p0, r0), sub(p1, r1)), vmax(add(p0, r0), add(p1, r1))};
+    }
+  } else if (!shape.triangles.empty()) {
     bboxes.resize(shape.triangles.size());
     for (size_t i = 0; i < bboxes.size(); i++) {
       auto& t = shape.triangles[i];
@@ -292,8 +310,19 @@ void flatten_scene(flat_scene& flat, const scene_data& scene, const bvh_scene& b
   }
   for (size_t s = 0; s < scene.shapes.size(); s++) {
     auto& shape = scene.shapes[s];
-    if (!shape.points.empty())
-      throw std::invalid_argument{"point/line shapes are outside the hot-path scope"};
+    // a shape of points or lines holds nothing else: the reference's BVH tests points first, its eval_* functions faces first
+    auto kinds = (int)!shape.points.empty() + (int)!shape.lines.empty() + (int)(!shape.triangles.empty() || !shape.quads.empty());
+    if (kinds > 1 && (!shape.points.empty() || !shape.lines.empty()))
+      throw std::invalid_argument{"a shape that mixes points, lines and faces is not supported"};
+    if ((!shape.points.empty() || !shape.lines.empty()) && shape.radius.size() != shape.positions.size())
+      throw std::invalid_argument{"a shape of points or lines needs one radius per vertex"};
+    auto& c         = flat.shape_curves.emplace_back();
+    c.num_points    = (int)shape.points.size(), c.point_offset = (int)flat.points.size();
+    c.num_lines     = (int)shape.lines.size(), c.line_offset = (int)flat.lines.size();
+    c.radius_offset = shape.radius.empty() ? -1 : (int)flat.radius.size();
+    flat.points.insert(flat.points.end(), shape.points.begin(), shape.points.end());
+    flat.lines.insert(flat.lines.end(), shape.lines.begin(), shape.lines.end());
+    flat.radius.insert(flat.radius.end(), shape.radius.begin(), shape.radius.end());
     auto& d           = flat.shapes.emplace_back();
     d.num_vertices    = (int)shape.positions.size();
     d.position_offset = (int)flat.positions.size();
@@ -398,7 +427,18 @@ void flatten_scene(flat_scene& flat, const scene_data& scene, const bvh_scene& b
   VPT_SET(num_scene_bvh_prims, scene_bvh_prims, scene_prims);
   VPT_SET(num_shape_bvh_nodes, shape_bvh_nodes, shape_nodes);
   VPT_SET(num_shape_bvh_prims, shape_bvh_prims, shape_prims);
+  // the side struct (include/vpt.h: vpt_scene_curves) only when some shape has points or lines: a scene of faces is created as before
+  auto any_curves = false;
+  for (auto& c : flat.shape_curves) any_curves |= c.num_points > 0 || c.num_lines > 0;
 #undef VPT_SET
+  flat.curves = {};
+  if (any_curves) {
+    auto& c = flat.curves;
+    c.shape_curves = flat.shape_curves.data();
+    c.num_points = (int64_t)flat.points.size(), c.points = flat.points.empty() ? nullptr : flat.points.data();
+    c.num_lines = (int64_t)flat.lines.size(), c.lines = flat.lines.empty() ? nullptr : (const int32_t*)flat.lines.data();
+    c.num_radius = (int64_t)flat.radius.size(), c.radius = flat.radius.empty() ? nullptr : flat.radius.data();
+  }
 }
 
 // =============================================================================================
@@ -459,7 +499,8 @@ uint64_t scene_fingerprint(const scene_data& scene, const bvh_scene& bvh, const 
   h = mix_table(h, scene.cameras), h = mix_table(h, scene.instances), h = mix_table(h, scene.materials);
   h = mix_table(h, scene.environments), h = mix_table(h, scene.vol_instances), h = mix_table(h, scene.sdfs);
   h = mix(h, scene.shapes.size()), h = mix(h, scene.textures.size()), h = mix(h, scene.volumes.size());
-  for (auto& s : scene.shapes) h = mix_array(h, s.positions), h = mix(h, s.triangles.size()), h = mix(h, s.quads.size());
+  for (auto& s : scene.shapes) h = mix_array(h, s.positions), h = mix(h, s.triangles.size()), h = mix(h, s.quads.size()),
+                              h = mix(h, s.points.size()), h = mix(h, s.lines.size()), h = mix_array(h, s.radius);
   for (auto& t : scene.textures) h = mix(mix(h, (uint64_t)t.width), (uint64_t)t.height), h = mix_array(h, t.pixelsb), h = mix_array(h, t.pixelsf);
   for (auto& v : scene.volumes) h = mix_array(h, v.vol);
   h = mix_array(h, bvh.nodes), h = mix_array(h, bvh.primitives), h = mix(h, bvh.shapes.size());
@@ -497,9 +538,9 @@ void pathtrace_samples(pathtrace_state& state, const scene_data& scene, const bv
       auto flat = flat_scene{};
       flatten_scene(flat, scene, bvh, lights);
       auto fresh = std::make_unique<device_entry>();
-      if (vpt_multi_create(&flat.desc, device_list().data(), (int)device_list().size(), &fresh->handle) != VPT_OK) {
+      if (vpt_multi_create_curves(&flat.desc, flat.curves_or_null(), device_list().data(), (int)device_list().size(), &fresh->handle) != VPT_OK) {
         device_cache().erase(&scene);
-        throw std::runtime_error{string{"vpt_multi_create: "} + vpt_last_error()};
+        throw std::runtime_error{string{"vpt_multi_create_curves: "} + vpt_last_error()};
       }
       fresh->fingerprint = print;
       entry              = std::move(fresh);

@@ -373,6 +373,10 @@ static bool load_ply_shape(const string& filename, shape_data& shape, string& er
         if (flip_texcoord)
           for (auto& uv : shape.texcoords) uv.y = 1 - uv.y;
       }
+      if (e.find("radius") && !e.find("radius")->is_list) {   // get_radius, yocto_modelio.cpp:1157-1159
+        shape.radius.resize(n);
+        get({"radius"}, n, shape.radius.data(), 1);
+      }
       if (e.find("red") && e.find("green") && e.find("blue")) {
         shape.colors.resize(n);
         get({"red", "green", "blue"}, n, &shape.colors[0].x, 4);
@@ -402,6 +406,14 @@ static bool load_ply_shape(const string& filename, shape_data& shape, string& er
         }
         cur += (size_t)n;
       }
+    } else if (e.name == "line") {   // get_lines, yocto_modelio.cpp:1212-1227: a polyline of n vertices is n - 1 segments
+      auto prop = e.find("vertex_indices");
+      if (!prop || !prop->is_list) continue;
+      auto cur = (size_t)0;
+      for (auto n : prop->list_sizes) {
+        for (auto c = 1; c < n; c++) shape.lines.push_back({(int)prop->values[cur + (size_t)c - 1], (int)prop->values[cur + (size_t)c]});
+        cur += (size_t)n;
+      }
     } else if (e.name == "point") {
       if (auto prop = e.find("vertex_indices"))
         for (auto v : prop->values) shape.points.push_back((int)v);
@@ -414,7 +426,12 @@ static bool load_ply_shape(const string& filename, shape_data& shape, string& er
   for (auto& q : shape.quads)
     if (q.x < 0 || q.y < 0 || q.z < 0 || q.w < 0 || q.x >= nv || q.y >= nv || q.z >= nv || q.w >= nv)
       return read_error();
-  if (shape.points.empty() && shape.triangles.empty() && shape.quads.empty()) {
+  for (auto p : shape.points)
+    if (p < 0 || p >= nv) return read_error();
+  for (auto& l : shape.lines)
+    if (l.x < 0 || l.y < 0 || l.x >= nv || l.y >= nv) return read_error();
+  if (!shape.radius.empty() && shape.radius.size() != shape.positions.size()) return read_error();
+  if (shape.points.empty() && shape.lines.empty() && shape.triangles.empty() && shape.quads.empty()) {
     error = filename + ": empty shape";
     return false;
   }
@@ -435,6 +452,7 @@ struct obj_raw {
   vector<vec2f>       texcoords;
   vector<obj_vertex>  vertices;
   vector<obj_element> elements;
+  int                 materials = 0;   // usemtl statements (only counted: a shape of lines or points may hold one)
 };
 void skip_ws(const char*& p, const char* end) {
   while (p < end && (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n')) p++;
@@ -510,6 +528,8 @@ bool load_obj_raw(const string& filename, obj_raw& obj, string& error) {
       auto v = vec2f{};
       if (!parse_float(p, end, v.x) || !parse_float(p, end, v.y)) return parse_error();
       obj.texcoords.push_back(v);
+    } else if (cmd == "usemtl") {
+      obj.materials++;
     } else if (cmd == "f" || cmd == "l" || cmd == "p") {
       auto& element = obj.elements.emplace_back();
       element.etype = cmd[0];
@@ -587,13 +607,27 @@ bool load_obj_shape(const string& filename, shape_data& shape, string& error, bo
       cur += element.size;
     }
   }
+  // get_lines / get_points (yocto_modelio.cpp:2402-2434): `l` elements are polylines split into segments, every corner of a
+  // `p` element reads the element's FIRST vertex.  Like get_fvquads they skip an element of another kind without advancing
+  // their vertex cursor, so they only read the right vertices when every element is of their kind: a shape with `l` or `p`
+  // elements is accepted only when all its elements are of that one kind under at most one usemtl, and refused otherwise
+  // (no fixture pins the reference's shifted reads).  A face shape with `l` / `p` elements keeps them, and flatten refuses it.
+  auto curves = false, faces = false, lines = true, points = true;
+  for (auto& e : obj.elements) curves |= e.etype != 'f', faces |= e.etype == 'f', lines &= e.etype == 'l', points &= e.etype == 'p';
+  if (curves && !faces && !((lines || points) && obj.materials <= 1)) {
+    error = filename + ": a shape of lines or points must hold one element kind under one material";
+    return false;
+  }
   auto cur = 0;
-  for (auto& element : obj.elements) {   // point and line elements: outside the hot-path scope, kept so that flatten rejects the shape
-    if (element.etype != 'f')
-      for (auto c = 0; c < element.size; c++) shape.points.push_back(obj.vertices[(size_t)(cur + c)].position - 1);
+  for (auto& element : obj.elements) {
+    if (element.etype == 'l')
+      for (auto c = 1; c < element.size; c++)
+        shape.lines.push_back({obj.vertices[(size_t)(cur + c - 1)].position - 1, obj.vertices[(size_t)(cur + c)].position - 1});
+    else if (element.etype == 'p')
+      for (auto c = 0; c < element.size; c++) shape.points.push_back(obj.vertices[(size_t)cur].position - 1);
     cur += element.size;
   }
-  if (shape.points.empty() && shape.triangles.empty() && shape.quads.empty()) {
+  if (shape.points.empty() && shape.lines.empty() && shape.triangles.empty() && shape.quads.empty()) {
     error = filename + ": empty shape";
     return false;
   }
@@ -1006,6 +1040,9 @@ bool load_scene(const string& filename, scene_data& scene, string& error) {
   };
   for (size_t i = 0; i < scene.shapes.size(); i++)
     if (!load_shape(path_join(dirname, shape_uris[i]), scene.shapes[i], error, true)) return dependent_error();
+  // add_missing_radius (yocto_sceneio.cpp:2071-2076, called at the end of load_json_scene)
+  for (auto& shape : scene.shapes)
+    if ((!shape.points.empty() || !shape.lines.empty()) && shape.radius.empty()) shape.radius.assign(shape.positions.size(), 0.001f);
   for (size_t i = 0; i < scene.volumes.size(); i++)
     if (!load_volume(path_join(dirname, volume_uris[i]), scene.volumes[i], volume_binary[i], error)) return dependent_error();
   for (size_t i = 0; i < scene.subdivs.size(); i++)
