@@ -356,6 +356,43 @@ int vpt_resolve_device(const vpt_layout* layout, const void* d_tiles_all_ranks, 
 int vpt_resolve_srgb8_device(const vpt_layout* layout, const void* d_tiles_all_ranks, int samples,
                              void* d_rgba8_rowmajor, void* stream);
 
+/* ---- adaptive sampling: every pixel renders until its noise meets a target ---------------------------
+ * A pixel that stops after k samples holds exactly the state k consecutive reference calls leave (image, rng, hits == k):
+ * pixels are independent and batching is exact, so the numerical contract holds per pixel.  Rendering goes in rounds; each
+ * round renders min(step, params->samples - hits) samples for every pixel still rendering (the same count for all of them:
+ * hits[] is uniform on entry and they have rendered every round).  The pixels left are packed 64 to a wave, in tile-major order.
+ * The rule, after round n (n = 1, 2, ...) of m samples, for each pixel p still rendering:
+ *   L = (image.x + image.y + image.z) / 3               (the pixel's radiance sum, float32, in that order)
+ *   b = (L - lum_prev) / m, then lum_prev = L          (lum_prev starts as L of the entry state)
+ *   Welford over the rounds' means:  delta = b - mean;  mean += delta / n;  m2 += delta * (b - mean)   (mean, m2 start at 0)
+ *   p stops when hits[p] >= params->samples (the per-pixel cap), or when
+ *     threshold > 0  and  n >= 2  and  hits[p] >= min_samples  and  m2 / (n * (n - 1)) <= (threshold * max(mean, 1/256))^2
+ *   i.e. the standard error of the pixel's mean luminance is within `threshold` of that mean, with a floor for dark pixels.
+ * Every value is float32 (n and n - 1 converted to float before their product); threshold == 0 never stops a pixel early. */
+typedef struct vpt_adaptive {
+  float   threshold;    /* relative standard error at which a pixel stops (rule above); 0: never stops early */
+  int32_t min_samples;  /* no pixel stops early with fewer hits; 1 <= min_samples <= params->samples        */
+  int32_t step;         /* samples per round for every pixel still rendering (>= 1)                         */
+} vpt_adaptive;
+/* Host pathtrace_state, like vpt_render; params->samples is the per-pixel cap; all hits[] must be equal on entry
+ * (VPT_ERR_INVALID_ARG otherwise); *samples_io becomes max(hits); *rendered (nullable) the samples actually taken.
+ * Like vpt_render it fails with VPT_ERR_HIP if a wave of the implicit kernel gave up on its watchdog. */
+int vpt_render_adaptive(vpt_scene* scene, const vpt_params* params, const vpt_adaptive* adaptive, int width, int height,
+                        float* image_rgba, int32_t* hits, uint64_t* rng, int* samples_io, int64_t* rendered);
+/* The same on device-resident tile-major state of one rank (vpt_layout), asynchronous on `stream` apart from one small
+ * read-back per round (the count of pixels still rendering, which sizes the next launch and ends the loop at 0) and the
+ * watchdog check after each round of the implicit kernels.  hits[] must be equal over the rank's pixels on entry (checked on
+ * the device before anything renders: VPT_ERR_INVALID_ARG).  *rounds, *rendered (both nullable): rounds run, samples taken.
+ * The rounds bypass the launch schedule of vpt_render_device (no pilot, no longest-first order, no tile splitting, no wave
+ * costs recorded): the handle's record for the layout is left as it was.  vpt_last_kernel_ms covers the whole call. */
+int vpt_render_device_adaptive(vpt_scene* scene, const vpt_params* params, const vpt_adaptive* adaptive, const vpt_layout* layout,
+                               void* d_image, void* d_hits, void* d_rng, void* stream, int* rounds, int64_t* rendered);
+/* get_render with each pixel's own sample count: gathered tile-major float4 sums and int32 hit counts of ALL ranks
+ * ([nranks][slots] each) -> row-major image[p] * (1.0f / hits[p]), 0 where hits[p] == 0.  With uniform hits it gives the
+ * bits of vpt_resolve_device (the same multiplication by the same reciprocal). */
+int vpt_resolve_hits_device(const vpt_layout* layout, const void* d_tiles_all_ranks, const void* d_hits_all_ranks,
+                            void* d_image_rowmajor, void* stream);
+
 /* per-launch profile of the last vpt_render_device on this scene (HIP events on `stream`); synchronises with that
  * launch.  Like vpt_render it returns VPT_ERR_HIP if a wave of the implicit kernel gave up on its watchdog (a wave
  * that has not finished after 300 s leaves the kernel instead of holding the GPU: a defect, never a workload). */

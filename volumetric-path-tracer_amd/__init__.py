@@ -50,6 +50,10 @@ class VptLayout(C.Structure):  # vpt_layout
                 ("tile_h", C.c_int32), ("rank", C.c_int32), ("nranks", C.c_int32)]
 
 
+class VptAdaptive(C.Structure):  # vpt_adaptive
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_int32), ("step", C.c_int32)]
+
+
 @dataclass
 class PathtraceParams:
     """pathtrace_params, yocto_pathtrace.h:87-99 (same names, same defaults)."""
@@ -101,6 +105,11 @@ hip.vpt_state_upload.argtypes = [C.POINTER(VptLayout), _p, _p, _p, _p, _p, _p, _
 hip.vpt_state_download.argtypes = [C.POINTER(VptLayout), _p, _p, _p, _p, _p, _p, _p]
 hip.vpt_render_device.argtypes = [_p, C.POINTER(VptParams), C.POINTER(VptLayout), C.c_int, _p, _p, _p, _p]
 hip.vpt_resolve_device.argtypes = [C.POINTER(VptLayout), _p, C.c_int, _p, _p]
+hip.vpt_render_adaptive.argtypes = [_p, C.POINTER(VptParams), C.POINTER(VptAdaptive), C.c_int, C.c_int, _p, _p, _p, C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int64)]
+hip.vpt_render_device_adaptive.argtypes = [_p, C.POINTER(VptParams), C.POINTER(VptAdaptive), C.POINTER(VptLayout), _p, _p, _p, _p,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+hip.vpt_resolve_hits_device.argtypes = [C.POINTER(VptLayout), _p, _p, _p, _p]
 hip.vpt_last_kernel_ms.argtypes = [_p, C.POINTER(C.c_float)]
 hip.vpt_intersect.argtypes = [_p, C.c_int, _p, C.c_int, _p, _p]
 hip.vpt_build_bvh.argtypes = [C.c_int, _p, C.c_int, _p, C.c_int, C.POINTER(C.c_int), _p]
@@ -297,7 +306,33 @@ class DeviceScene:
                               state.hits.ctypes.data, state.rngs.ctypes.data, C.byref(samples)), "vpt_render")
         state.samples = samples.value
 
+    def pathtrace_adaptive(self, state: PathtraceState, params: PathtraceParams, threshold: float, min_samples: int = 16,
+                           step: int = 32):
+        """adaptive sampling (vpt_render_adaptive, include/vpt.h): every pixel renders in rounds of `step` samples until the relative
+        standard error of its mean luminance is within `threshold` (0: never stops early), never below `min_samples` and at most
+        params.samples; state.hits must be equal on entry.  state.samples becomes max(hits).  Returns (rounds, samples taken)."""
+        abi, ad = params.to_abi(), VptAdaptive(threshold, min_samples, step)
+        samples, rendered = C.c_int(state.samples), C.c_int64(0)
+        for a in (state.image, state.hits, state.rngs):
+            assert a.flags["C_CONTIGUOUS"]
+        entry = int(state.hits.flat[0]) if state.hits.size else 0
+        _check(hip.vpt_render_adaptive(self.handle, C.byref(abi), C.byref(ad), state.width, state.height, state.image.ctypes.data,
+                                       state.hits.ctypes.data, state.rngs.ctypes.data, C.byref(samples), C.byref(rendered)),
+               "vpt_render_adaptive")
+        state.samples = samples.value
+        # the pixel that rendered longest was in every round; each of its rounds but the last took `step` samples
+        return -(-max(0, state.samples - entry) // step), rendered.value
+
     # -- device-resident state (pointers are raw device addresses, e.g. torch.Tensor.data_ptr()) ----
+    def render_device_adaptive(self, params: PathtraceParams, layout: VptLayout, d_image: int, d_hits: int, d_rng: int, threshold: float,
+                               min_samples: int = 16, step: int = 32, stream: int = 0):
+        """vpt_render_device_adaptive on this rank's tile-major state: returns (rounds, samples taken)"""
+        abi, ad = params.to_abi(), VptAdaptive(threshold, min_samples, step)
+        rounds, rendered = C.c_int(0), C.c_int64(0)
+        _check(hip.vpt_render_device_adaptive(self.handle, C.byref(abi), C.byref(ad), C.byref(layout), d_image, d_hits, d_rng, stream,
+                                              C.byref(rounds), C.byref(rendered)), "vpt_render_device_adaptive")
+        return rounds.value, rendered.value
+
     def render_device(self, params: PathtraceParams, layout: VptLayout, nsamples: int, d_image: int, d_hits: int,
                       d_rng: int, stream: int = 0) -> None:
         abi = params.to_abi()
@@ -447,6 +482,11 @@ def resolve_device(layout: VptLayout, d_tiles_all: int, samples: int, d_rows: in
     _check(hip.vpt_resolve_device(C.byref(layout), d_tiles_all, samples, d_rows, stream), "vpt_resolve_device")
 
 
+def resolve_hits_device(layout: VptLayout, d_tiles_all: int, d_hits_all: int, d_rows: int, stream: int = 0):
+    """get_render with each pixel's own sample count on the device (vpt_resolve_hits_device): row-major float4"""
+    _check(hip.vpt_resolve_hits_device(C.byref(layout), d_tiles_all, d_hits_all, d_rows, stream), "vpt_resolve_hits_device")
+
+
 def resolve_srgb8_device(layout: VptLayout, d_tiles_all: int, samples: int, d_rgba8: int, stream: int = 0):
     """get_render + rgb_to_srgb + float_to_byte on the device (row-major RGBA8)"""
     _check(hip.vpt_resolve_srgb8_device(C.byref(layout), d_tiles_all, samples, d_rgba8, stream), "vpt_resolve_srgb8_device")
@@ -455,6 +495,14 @@ def resolve_srgb8_device(layout: VptLayout, d_tiles_all: int, samples: int, d_rg
 def get_render(state: PathtraceState) -> np.ndarray:
     """get_render, yocto_pathtrace.cpp:1105-1116: image * (1/samples) in float32"""
     return state.image * np.float32(np.float32(1.0) / np.float32(state.samples))
+
+
+def get_render_hits(state: PathtraceState) -> np.ndarray:
+    """get_render with each pixel's own sample count: image * float32(1 / hits), 0 where hits == 0 (after pathtrace_adaptive)"""
+    hits = state.hits.astype(np.float32)
+    with np.errstate(divide="ignore"):
+        scale = np.where(state.hits > 0, np.float32(1.0) / hits, np.float32(0.0)).astype(np.float32)
+    return np.where((state.hits > 0)[..., None], state.image * scale[..., None], np.float32(0.0)).astype(np.float32)
 
 
 def selftest_reciprocal(device: int = 0):

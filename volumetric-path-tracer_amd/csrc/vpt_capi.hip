@@ -30,6 +30,7 @@ extern template __global__ void vpt_intersect_curves_kernel<false>(DScene, int, 
 #endif
 #include <rocprim/rocprim.hpp>
 
+#include "vpt_adaptive.h"
 #include "vpt_device_buffer.h"
 #include "vpt_error.h"
 #include "vpt_scene_prep.h"
@@ -214,6 +215,8 @@ int make_dparams(const vpt_params* p, const vpt_layout* l, int nsamples, DParams
 }
 
 }  // namespace
+
+int vpt_make_dparams(const vpt_params* p, const vpt_layout* l, int nsamples, DParams& out) { return make_dparams(p, l, nsamples, out); }
 
 extern "C" {
 
@@ -582,62 +585,96 @@ static int run_launches(const launch_ctx& L, bool may_split, int slots, const do
   return VPT_OK;
 }
 
-// K1 (mesh shaders)
+// K1 (mesh shaders): the instance compiled for the features this scene has (vpt_scene.hip.h: VPT_FEAT_*), launched over `grid`
+// with the schedule `sch` - by run_launches (vpt_render_device) and by the rounds of vpt_render_device_adaptive
+template <int K>
+static void launch_mesh_instance(const launch_ctx& L, bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
+#if !defined(VPT_EXPERIMENT_ONLY_K2)
+  vpt_scene* s = L.s;
+  size_t lds = (size_t)s->stack_lds4 * 2 * VPT_BLOCK * sizeof(int) + 5 * VPT_BLOCK * sizeof(float);   // (ref, t0) pairs + the parked words
+  const int need = getenv("VPT_NO_LEAN") ? VPT_FEAT_ALL : s->light_features;
+  auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, L.block, lds, L.st, s->d, pr, L.img, L.hit, L.rng, L.stack, sch); };
+  auto launch_feat = [&](auto feat) {
+    constexpr int F = decltype(feat)::value;
+    if (is_pilot && L.stack.spill) launch(vpt_mesh_pilot_kernel<K, true, F>);
+    else if (is_pilot) launch(vpt_mesh_pilot_kernel<K, false, F>);
+    else if (L.stack.spill) launch(vpt_mesh_kernel<K, true, F>);
+    else launch(vpt_mesh_kernel<K, false, F>);
+  };
+  // three instances: single-leaf mesh lights only / + emissive meshes with a BVH / everything (SDF lights too)
+  // (+ the compact-record form of the first for the two path tracers on scenes of triangles; the pilot runs on the general records)
+  // (a scene with points or lines: the one instance with every light feature and the point / line tests, vpt_k1_curves.hip)
+  if (s->curves) launch_feat(std::integral_constant<int, VPT_FEAT_ALL | VPT_FEAT_CURVES>{});
+  else if ((K == K_VOLPATH || K == K_PATH) && (need & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SDF_LIGHTS)) == 0 && s->d.tri_prims && !is_pilot) {
+    if constexpr (K == K_VOLPATH || K == K_PATH) {
+      if (L.stack.spill) launch(vpt_mesh_kernel<K, true, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_COMPACT_TRIS>);
+      else launch(vpt_mesh_kernel<K, false, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_COMPACT_TRIS>);
+    }
+  } else if ((need & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SDF_LIGHTS)) == 0) launch_feat(std::integral_constant<int, VPT_FEAT_SMALL_LIGHTS>{});
+  else if ((need & VPT_FEAT_SDF_LIGHTS) == 0) launch_feat(std::integral_constant<int, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_LARGE_LIGHTS>{});
+  else launch_feat(std::integral_constant<int, VPT_FEAT_ALL>{});
+#endif
+}
 template <int K>
 static int launch_mesh(const launch_ctx& L) {
 #if defined(VPT_EXPERIMENT_ONLY_K2)   // experiment builds (make variant): only the kernels under study are compiled (minutes -> seconds)
   return vpt_set_error(VPT_ERR_UNSUPPORTED, "this experiment build holds the implicit kernels only");
 #else
   vpt_scene* s = L.s;
-  size_t lds = (size_t)s->stack_lds4 * 2 * VPT_BLOCK * sizeof(int) + 5 * VPT_BLOCK * sizeof(float);   // (ref, t0) pairs + the parked words
   const bool may_split = !L.stack.spill && (split_mode() == 1 || split_forced_k() >= 0 ||
                                             (split_mode() < 0 && (L.pr.nranks > 1 || (long long)L.grid.x < 3ll * s->wave_slots_k1)));
-  // the instance compiled for the features this scene has (vpt_scene.hip.h: VPT_FEAT_*)
-  const int need = getenv("VPT_NO_LEAN") ? VPT_FEAT_ALL : s->light_features;
   return run_launches(L, may_split, s->wave_slots_k1, split_gain, [&](bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
-    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, L.block, lds, L.st, s->d, pr, L.img, L.hit, L.rng, L.stack, sch); };
-    auto launch_feat = [&](auto feat) {
-      constexpr int F = decltype(feat)::value;
-      if (is_pilot && L.stack.spill) launch(vpt_mesh_pilot_kernel<K, true, F>);
-      else if (is_pilot) launch(vpt_mesh_pilot_kernel<K, false, F>);
-      else if (L.stack.spill) launch(vpt_mesh_kernel<K, true, F>);
-      else launch(vpt_mesh_kernel<K, false, F>);
-    };
-    // three instances: single-leaf mesh lights only / + emissive meshes with a BVH / everything (SDF lights too)
-    // (+ the compact-record form of the first for the two path tracers on scenes of triangles; the pilot runs on the general records)
-    // (a scene with points or lines: the one instance with every light feature and the point / line tests, vpt_k1_curves.hip)
-    if (s->curves) launch_feat(std::integral_constant<int, VPT_FEAT_ALL | VPT_FEAT_CURVES>{});
-    else if ((K == K_VOLPATH || K == K_PATH) && (need & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SDF_LIGHTS)) == 0 && s->d.tri_prims && !is_pilot) {
-      if constexpr (K == K_VOLPATH || K == K_PATH) {
-        if (L.stack.spill) launch(vpt_mesh_kernel<K, true, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_COMPACT_TRIS>);
-        else launch(vpt_mesh_kernel<K, false, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_COMPACT_TRIS>);
-      }
-    } else if ((need & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SDF_LIGHTS)) == 0) launch_feat(std::integral_constant<int, VPT_FEAT_SMALL_LIGHTS>{});
-    else if ((need & VPT_FEAT_SDF_LIGHTS) == 0) launch_feat(std::integral_constant<int, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_LARGE_LIGHTS>{});
-    else launch_feat(std::integral_constant<int, VPT_FEAT_ALL>{});
+    launch_mesh_instance<K>(L, is_pilot, grid, pr, sch);
   });
 #endif
 }
-// K2 (implicit shaders).  Tile splitting is considered on every layout (unless VPT_SPLIT=0): K2's launches hold two waves per wave
+// K2 (implicit shaders): LDS of a launch (the refs-only stack + the scene's SDF records); VPT_ERR_UNSUPPORTED when they do not fit
+static int implicit_lds(const vpt_scene* s, size_t& lds) {
+  lds = (size_t)s->stack_cap * VPT_BLOCK * sizeof(int) +                                      // refs-only stack
+        (6 * (size_t)s->d.num_sdfs + 7 * (size_t)s->d.num_vol_instances) * sizeof(float4);   // the SDF records
+  if (lds > 64 * 1024) return vpt_set_error(VPT_ERR_UNSUPPORTED, "scene has too many SDFs for the implicit kernel's LDS copy of their records (%d + %d)", s->d.num_sdfs, s->d.num_vol_instances);
+  return VPT_OK;
+}
+// the instance for the features this scene's lights have (VPT_FEAT_*): SDF scenes without emissive meshes run one without the mesh-light walks
+template <int K>
+static void launch_implicit_instance(const launch_ctx& L, bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
+  vpt_scene* s = L.s;
+  size_t     lds = 0;
+  (void)implicit_lds(s, lds);   // checked by the callers before they launch
+  unsigned long long watchdog_ticks = VPT_K2_WATCHDOG_TICKS;
+  if (const char* e = getenv("VPT_K2_WATCHDOG_MS")) watchdog_ticks = strtoull(e, nullptr, 10) * 100000ull;   // tests of the error path
+  const bool lean = (s->light_features & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SMALL_LIGHTS)) == 0 && !getenv("VPT_NO_LEAN");
+  auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, L.block, lds, L.st, s->d, pr, L.img, L.hit, L.rng, s->stack_cap, sch, s->d_watchdog.get<unsigned>(), watchdog_ticks); };
+  if (is_pilot && lean) launch(vpt_render_pilot_kernel<K, VPT_FEAT_SDF_LIGHTS>);
+  else if (is_pilot) launch(vpt_render_pilot_kernel<K, VPT_FEAT_ALL>);
+  else if (lean) launch(vpt_render_kernel<K, VPT_FEAT_SDF_LIGHTS>);
+  else launch(vpt_render_kernel<K, VPT_FEAT_ALL>);
+}
+// K2.  Tile splitting is considered on every layout (unless VPT_SPLIT=0): K2's launches hold two waves per wave
 // slot at 1280 x 533, so the longest-first schedule ends well above both of its bounds (226 ms against a longest wave of 192 and 191
 // of work per slot); the costliest tiles as partly filled waves - whose scene rounds run in the group form: four lanes per ray - pack better.
 template <int K>
 static int launch_implicit(const launch_ctx& L) {
-  vpt_scene* s   = L.s;
-  size_t     lds = (size_t)s->stack_cap * VPT_BLOCK * sizeof(int) +                                      // refs-only stack
-               (6 * (size_t)s->d.num_sdfs + 7 * (size_t)s->d.num_vol_instances) * sizeof(float4);       // the SDF records
-  if (lds > 64 * 1024) return vpt_set_error(VPT_ERR_UNSUPPORTED, "scene has too many SDFs for the implicit kernel's LDS copy of their records (%d + %d)", s->d.num_sdfs, s->d.num_vol_instances);
-  unsigned long long watchdog_ticks = VPT_K2_WATCHDOG_TICKS;
-  if (const char* e = getenv("VPT_K2_WATCHDOG_MS")) watchdog_ticks = strtoull(e, nullptr, 10) * 100000ull;   // tests of the error path
-  // the instance for the features this scene's lights have (VPT_FEAT_*): SDF scenes without emissive meshes run one without the mesh-light walks
-  const bool lean = (s->light_features & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SMALL_LIGHTS)) == 0 && !getenv("VPT_NO_LEAN");
-  return run_launches(L, split_mode() != 0, s->wave_slots_k2, split_gain_k2, [&](bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
-    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, L.block, lds, L.st, s->d, pr, L.img, L.hit, L.rng, s->stack_cap, sch, s->d_watchdog.get<unsigned>(), watchdog_ticks); };
-    if (is_pilot && lean) launch(vpt_render_pilot_kernel<K, VPT_FEAT_SDF_LIGHTS>);
-    else if (is_pilot) launch(vpt_render_pilot_kernel<K, VPT_FEAT_ALL>);
-    else if (lean) launch(vpt_render_kernel<K, VPT_FEAT_SDF_LIGHTS>);
-    else launch(vpt_render_kernel<K, VPT_FEAT_ALL>);
+  size_t lds = 0;
+  if (int rc = implicit_lds(L.s, lds)) return rc;
+  return run_launches(L, split_mode() != 0, L.s->wave_slots_k2, split_gain_k2, [&](bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
+    launch_implicit_instance<K>(L, is_pilot, grid, pr, sch);
   });
+}
+// one launch of the kernel instance for params->shader over `grid` with the schedule `sch` (no pilot): the rounds of
+// vpt_render_device_adaptive go through the same instance table as vpt_render_device
+static void launch_instance(const launch_ctx& L, dim3 grid, const DParams& pr, const sched_cfg& sch) {
+  switch (L.params->shader) {
+    case VPT_SHADER_VOLPATHTRACE: launch_mesh_instance<K_VOLPATH>(L, false, grid, pr, sch); break;
+    case VPT_SHADER_PATHTRACE: launch_mesh_instance<K_PATH>(L, false, grid, pr, sch); break;
+    case VPT_SHADER_NAIVE: launch_mesh_instance<K_NAIVE>(L, false, grid, pr, sch); break;
+    case VPT_SHADER_EYELIGHT: launch_mesh_instance<K_EYELIGHT>(L, false, grid, pr, sch); break;
+    case VPT_SHADER_NORMAL:
+    case VPT_SHADER_TEXCOORD:
+    case VPT_SHADER_COLOR: launch_mesh_instance<K_DEBUG>(L, false, grid, pr, sch); break;
+    case VPT_SHADER_IMPLICIT: launch_implicit_instance<K_IMPLICIT>(L, false, grid, pr, sch); break;
+    case VPT_SHADER_IMPLICIT_NORMAL: launch_implicit_instance<K_IMPLICIT_NORMAL>(L, false, grid, pr, sch); break;
+  }
 }
 
 extern "C" {
@@ -750,6 +787,128 @@ int vpt_resolve_srgb8_device(const vpt_layout* layout, const void* d_tiles_all_r
   return VPT_OK;
 }
 
+}  // extern "C"
+
+// the scene handle's staging of a host state for `lay` (one rank, 8x8 tiles): allocated once per frame size
+static int stage_host_state(vpt_scene* s, const vpt_layout& lay) {
+  long long slots = vpt_layout_slots(&lay), pixels = (long long)lay.width * lay.height;
+  if (slots < 0) return VPT_ERR_INVALID_ARG;
+  if (s->staged_slots != slots || s->staged_pixels != pixels) {
+    s->staged_slots = s->staged_pixels = 0;
+    if (s->s_image.allocate((size_t)slots * 16) || s->s_hits.allocate((size_t)slots * 4) || s->s_rng.allocate((size_t)slots * 16) ||
+        s->r_image.allocate((size_t)pixels * 16) || s->r_hits.allocate((size_t)pixels * 4) || s->r_rng.allocate((size_t)pixels * 16))
+      return VPT_ERR_HIP;
+    s->staged_slots = slots, s->staged_pixels = pixels;
+  }
+  return VPT_OK;
+}
+
+// the arguments of an adaptive render, checked before anything touches the device
+static int check_adaptive(const vpt_scene* s, const vpt_params* params, const vpt_adaptive* a) {
+  if (!params || !a) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (!std::isfinite(a->threshold) || a->threshold < 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "adaptive threshold must be finite and >= 0");
+  if (a->step < 1) return vpt_set_error(VPT_ERR_INVALID_ARG, "adaptive step must be >= 1");
+  if (params->samples < 1) return vpt_set_error(VPT_ERR_INVALID_ARG, "params->samples (the per-pixel cap) must be >= 1");
+  if (a->min_samples < 1 || a->min_samples > params->samples)
+    return vpt_set_error(VPT_ERR_INVALID_ARG, "adaptive min_samples must be in 1 .. params->samples (%d)", params->samples);
+  if (params->bounces < 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "negative bounce count");
+  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null scene");
+  if (params->shader < 0 || params->shader > VPT_SHADER_IMPLICIT_NORMAL) return vpt_set_error(VPT_ERR_UNKNOWN_SHADER, "sampler unknown");
+  if (params->camera < 0 || params->camera >= s->d.num_cameras) return vpt_set_error(VPT_ERR_INVALID_ARG, "camera %d out of range", params->camera);
+#if defined(VPT_EXPERIMENT_ONLY_K2)
+  if (params->shader < VPT_SHADER_IMPLICIT) return vpt_set_error(VPT_ERR_UNSUPPORTED, "this experiment build holds the implicit kernels only");
+#endif
+  return VPT_OK;
+}
+
+extern "C" {
+
+// Adaptive sampling (include/vpt.h): rounds of one launch each over the pixels still rendering, packed 64 to a wave
+// through sched_cfg::lane_slot by the kernels of vpt_adaptive.hip.  No pilot, no order, no costs, no tile splitting: the handle's
+// launch schedule for the layout stays as vpt_render_device left it.
+int vpt_render_device_adaptive(vpt_scene* s, const vpt_params* params, const vpt_adaptive* a, const vpt_layout* layout, void* d_image,
+    void* d_hits, void* d_rng, void* stream, int* rounds, int64_t* rendered) {
+  if (rounds) *rounds = 0;
+  if (rendered) *rendered = 0;
+  if (int rc = check_adaptive(s, params, a)) return rc;
+  if (!layout || !d_image || !d_hits || !d_rng) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  DParams pr;
+  if (int rc = make_dparams(params, layout, 0, pr)) return rc;
+  const bool implicit = params->shader >= VPT_SHADER_IMPLICIT;
+  size_t     lds      = 0;
+  if (implicit)
+    if (int rc = implicit_lds(s, lds)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t     st   = (hipStream_t)stream;
+  const long long full = (pr.nslots + VPT_BLOCK - 1) / VPT_BLOCK;
+  stack_cfg stack;   // the spilled stacks are indexed by global lane: sized for the full layout, a compacted grid is never larger
+  if (int rc = stack_config(s, full * VPT_BLOCK, stack)) return rc;
+  device_buffer d_stats, d_wave_count, d_lane_slot, d_info;   // scratch of this call (vpt_adaptive.h)
+  if (int rc = d_stats.allocate((size_t)pr.nslots * 16)) return rc;
+  if (int rc = d_wave_count.allocate((size_t)full * 4)) return rc;
+  if (int rc = d_lane_slot.allocate((size_t)pr.nslots * 4)) return rc;
+  if (int rc = d_info.allocate(16)) return rc;
+  const adaptive_buffers b = {d_stats.get<float4>(), d_wave_count.get<int>(), d_lane_slot.get<int>(), d_info.get<int>()};
+  auto img = (float4*)d_image;
+  auto hit = (int*)d_hits;
+  auto rng = (ulonglong2*)d_rng;
+  int  info[4] = {0, 0, 0, 0};
+  auto read_info = [&]() -> int {   // the one read-back of a round: what sizes the next launch
+    HIP_TRY(hipMemcpyAsync(info, b.info, sizeof(info), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return VPT_OK;
+  };
+  HIP_TRY(hipEventRecord(s->ev0, st));
+  s->host_pause = false;
+  if (int rc = adaptive_update(pr, img, hit, b, 0, 0, *a, params->samples, st)) return rc;
+  if (int rc = read_info()) return rc;
+  if (info[1] < info[2]) return vpt_set_error(VPT_ERR_INVALID_ARG, "hits[] must be equal on entry (found %d .. %d)", info[1], info[2]);
+  const launch_ctx L = {s, params, pr, dim3((unsigned)full), dim3(VPT_BLOCK), st, img, hit, rng, stack};
+  int       h = info[1], n = 0;   // hits of every pixel still rendering, rounds so far
+  long long taken = 0;
+  for (int active = info[0]; active > 0 && h < params->samples; active = info[0]) {
+    DParams rp  = pr;
+    rp.nsamples = std::min(a->step, params->samples - h);
+    const sched_cfg sch = {nullptr, nullptr, b.lane_slot};
+    launch_instance(L, dim3((unsigned)((active + VPT_BLOCK - 1) / VPT_BLOCK)), rp, sch);
+    HIP_TRY(hipGetLastError());
+    taken += (long long)active * rp.nsamples, h += rp.nsamples, n++;
+    if (int rc = adaptive_update(pr, img, hit, b, n, rp.nsamples, *a, params->samples, st)) return rc;
+    if (int rc = read_info()) return rc;
+    if (implicit)
+      if (int rc = vpt_check_watchdog(s)) return rc;
+  }
+  HIP_TRY(hipEventRecord(s->ev1, st));
+  s->timed = true;
+  if (rounds) *rounds = n;
+  if (rendered) *rendered = taken;
+  return VPT_OK;
+}
+
+int vpt_render_adaptive(vpt_scene* s, const vpt_params* params, const vpt_adaptive* a, int width, int height, float* image_rgba,
+    int32_t* hits, uint64_t* rng, int* samples_io, int64_t* rendered) {
+  if (rendered) *rendered = 0;
+  if (int rc = check_adaptive(s, params, a)) return rc;
+  if (!image_rgba || !hits || !rng || !samples_io) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (width <= 0 || height <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad image size");
+  const long long pixels = (long long)width * height;
+  for (long long i = 1; i < pixels; i++)
+    if (hits[i] != hits[0]) return vpt_set_error(VPT_ERR_INVALID_ARG, "hits[] must be equal on entry (pixel %lld has %d, pixel 0 %d)", i, hits[i], hits[0]);
+  *samples_io = hits[0];
+  if (hits[0] >= params->samples) return VPT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  vpt_layout lay = {width, height, 8, 8, 0, 1};
+  if (int rc = stage_host_state(s, lay)) return rc;
+  void *t_image = s->s_image.get(), *t_hits = s->s_hits.get(), *t_rng = s->s_rng.get();
+  void *r_image = s->r_image.get(), *r_hits = s->r_hits.get(), *r_rng = s->r_rng.get();
+  if (int rc = state_upload(&lay, image_rgba, hits, rng, t_image, t_hits, t_rng, nullptr, r_image, r_hits, r_rng)) return rc;
+  if (int rc = vpt_render_device_adaptive(s, params, a, &lay, t_image, t_hits, t_rng, nullptr, nullptr, rendered)) return rc;
+  if (int rc = state_download(&lay, t_image, t_hits, t_rng, image_rgba, hits, rng, nullptr, r_image, r_hits, r_rng, true)) return rc;
+  if (int rc = vpt_check_watchdog(s)) return rc;
+  *samples_io = *std::max_element(hits, hits + pixels);
+  return VPT_OK;
+}
+
 int vpt_render(vpt_scene* s, const vpt_params* params, int nsamples, int width, int height, float* image_rgba,
     int32_t* hits, uint64_t* rng, int* samples_io) {
   if (!s || !params || !image_rgba || !hits || !rng || !samples_io) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
@@ -760,15 +919,7 @@ int vpt_render(vpt_scene* s, const vpt_params* params, int nsamples, int width, 
   if (todo <= 0) return VPT_OK;
   HIP_TRY(hipSetDevice(s->device));
   vpt_layout lay = {width, height, 8, 8, 0, 1};
-  long long  slots = vpt_layout_slots(&lay), pixels = (long long)width * height;
-  if (slots < 0) return VPT_ERR_INVALID_ARG;
-  if (s->staged_slots != slots || s->staged_pixels != pixels) {
-    s->staged_slots = s->staged_pixels = 0;
-    if (s->s_image.allocate((size_t)slots * 16) || s->s_hits.allocate((size_t)slots * 4) || s->s_rng.allocate((size_t)slots * 16) ||
-        s->r_image.allocate((size_t)pixels * 16) || s->r_hits.allocate((size_t)pixels * 4) || s->r_rng.allocate((size_t)pixels * 16))
-      return VPT_ERR_HIP;
-    s->staged_slots = slots, s->staged_pixels = pixels;
-  }
+  if (int rc = stage_host_state(s, lay)) return rc;
   void *t_image = s->s_image.get(), *t_hits = s->s_hits.get(), *t_rng = s->s_rng.get();
   void *r_image = s->r_image.get(), *r_hits = s->r_hits.get(), *r_rng = s->r_rng.get();
   if (int rc = state_upload(&lay, image_rgba, hits, rng, t_image, t_hits, t_rng, nullptr, r_image, r_hits, r_rng)) return rc;

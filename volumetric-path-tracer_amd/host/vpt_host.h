@@ -223,6 +223,25 @@ void pathtrace_release(const scene_data& scene);
 void pathtrace_set_devices(const vector<int>& devices);
 color_image get_render(const pathtrace_state& state);
 void        get_render(color_image& render, const pathtrace_state& state);
+// Extension: adaptive sampling (vpt_render_adaptive of include/vpt.h, whose rule decides when a pixel stops).  Every pixel renders
+// in rounds of `step` samples until its noise meets `threshold` (relative standard error of its mean luminance; 0: never stops early),
+// never before `min_samples` and at most params.samples; state.hits[] must be equal on entry (a fresh state: 0).  Renders on the
+// first GPU of pathtrace_set_devices' list and refuses a list of several (std::invalid_argument).  state.samples becomes the largest
+// hits[p]; the pixels keep their own counts, so the image is read with get_render_hits.
+struct pathtrace_adaptive_params {
+  float threshold   = 0;
+  int   min_samples = 16;
+  int   step        = 32;   // fewer rounds, fewer launch tails; a 32-spp round of the headline frame takes ~34 ms
+};
+struct pathtrace_adaptive_stats {
+  int     rounds  = 0;   // rounds rendered
+  int64_t samples = 0;   // samples taken over all pixels
+};
+pathtrace_adaptive_stats pathtrace_adaptive(pathtrace_state& state, const scene_data& scene, const bvh_scene& bvh,
+    const pathtrace_lights& lights, const pathtrace_params& params, const pathtrace_adaptive_params& adaptive);
+// get_render with each pixel's own sample count: image[p] * (1 / hits[p]), 0 where hits[p] == 0
+color_image get_render_hits(const pathtrace_state& state);
+void        get_render_hits(color_image& render, const pathtrace_state& state);
 
 // ---- flattening to the C-ABI ----------------------------------------------------------------
 struct flat_scene {

@@ -451,9 +451,11 @@ namespace {
 // heads of the big arrays); a mismatch rebuilds it.
 struct device_entry {
   vpt_multi* handle = nullptr;
+  vpt_scene* single = nullptr;   // pathtrace_adaptive's copy on one GPU (vpt_render_adaptive), made on first use
   uint64_t   fingerprint = 0;
   ~device_entry() {
     if (handle) vpt_multi_destroy(handle);
+    if (single) vpt_scene_destroy(single);
   }
 };
 std::mutex                                                   cache_mutex;
@@ -509,6 +511,17 @@ uint64_t scene_fingerprint(const scene_data& scene, const bvh_scene& bvh, const 
   for (auto& l : lights.lights) h = mix(mix(mix(h, (uint64_t)l.instance), (uint64_t)l.environment), (uint64_t)l.sdf), h = mix_array(h, l.elements_cdf);
   return h;
 }
+// the cache entry of `scene` (cache_mutex held): a fresh one, without device copies, when the fingerprint changed
+device_entry& cached_entry(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights) {
+  auto& entry = device_cache()[&scene];
+  auto  print = scene_fingerprint(scene, bvh, lights);
+  if (!entry || entry->fingerprint != print) {
+    entry.reset();
+    entry              = std::make_unique<device_entry>();
+    entry->fingerprint = print;
+  }
+  return *entry;
+}
 }  // namespace
 
 void pathtrace_release(const scene_data& scene) {
@@ -531,21 +544,17 @@ void pathtrace_samples(pathtrace_state& state, const scene_data& scene, const bv
   auto handle = (vpt_multi*)nullptr;
   {
     auto  lock  = std::lock_guard{cache_mutex};
-    auto& entry = device_cache()[&scene];
-    auto  print = scene_fingerprint(scene, bvh, lights);
-    if (!entry || entry->fingerprint != print) {
-      entry.reset();
+    auto& entry = cached_entry(scene, bvh, lights);
+    if (!entry.handle) {
       auto flat = flat_scene{};
       flatten_scene(flat, scene, bvh, lights);
-      auto fresh = std::make_unique<device_entry>();
-      if (vpt_multi_create_curves(&flat.desc, flat.curves_or_null(), device_list().data(), (int)device_list().size(), &fresh->handle) != VPT_OK) {
+      if (vpt_multi_create_curves(&flat.desc, flat.curves_or_null(), device_list().data(), (int)device_list().size(), &entry.handle) != VPT_OK) {
+        entry.handle = nullptr;
         device_cache().erase(&scene);
         throw std::runtime_error{string{"vpt_multi_create_curves: "} + vpt_last_error()};
       }
-      fresh->fingerprint = print;
-      entry              = std::move(fresh);
     }
-    handle = entry->handle;
+    handle = entry.handle;
   }
   auto abi = to_abi(params);
   static_assert(sizeof(rng_state) == 16 && sizeof(vec4f) == 16, "state layout");
@@ -574,6 +583,56 @@ color_image get_render(const pathtrace_state& state) {
   auto image = color_image{state.width, state.height, true, {}};
   image.pixels.resize((size_t)state.width * state.height);
   get_render(image, state);
+  return image;
+}
+
+pathtrace_adaptive_stats pathtrace_adaptive(pathtrace_state& state, const scene_data& scene, const bvh_scene& bvh,
+    const pathtrace_lights& lights, const pathtrace_params& params, const pathtrace_adaptive_params& adaptive) {
+  if ((int)params.shader < 0 || (int)params.shader > (int)pathtrace_shader_type::implicit_normal)
+    throw std::runtime_error{"sampler unknown"};  // reference cpp:947-950
+  auto handle = (vpt_scene*)nullptr;
+  {
+    auto lock = std::lock_guard{cache_mutex};
+    if (device_list().size() != 1) throw std::invalid_argument{"adaptive sampling renders on one GPU"};
+    auto& entry = cached_entry(scene, bvh, lights);
+    if (!entry.single) {
+      auto flat = flat_scene{};
+      flatten_scene(flat, scene, bvh, lights);
+      if (vpt_scene_create_curves(&flat.desc, flat.curves_or_null(), device_list()[0], &entry.single) != VPT_OK) {
+        entry.single = nullptr;
+        device_cache().erase(&scene);
+        throw std::runtime_error{string{"vpt_scene_create_curves: "} + vpt_last_error()};
+      }
+    }
+    handle = entry.single;
+  }
+  auto abi   = to_abi(params);
+  auto ad    = vpt_adaptive{adaptive.threshold, adaptive.min_samples, adaptive.step};
+  auto stats = pathtrace_adaptive_stats{};
+  auto entry = state.hits.empty() ? 0 : state.hits[0];   // equal for all pixels (vpt_render_adaptive checks)
+  if (vpt_render_adaptive(handle, &abi, &ad, state.width, state.height, (float*)state.image.data(), state.hits.data(),
+          (uint64_t*)state.rngs.data(), &state.samples, &stats.samples) != VPT_OK)
+    throw std::runtime_error{string{"vpt_render_adaptive: "} + vpt_last_error()};
+  // the pixel that rendered longest was in every round, and each of its rounds but the last took `step` samples
+  if (adaptive.step > 0 && state.samples > entry) stats.rounds = (state.samples - entry + adaptive.step - 1) / adaptive.step;
+  return stats;
+}
+
+void get_render_hits(color_image& image, const pathtrace_state& state) {
+  if (image.width != state.width || image.height != state.height)
+    throw std::invalid_argument{"image should have the same size"};
+  if (!image.linear) throw std::invalid_argument{"expected linear image"};
+  for (size_t i = 0; i < state.image.size(); i++) {
+    auto& p         = state.image[i];
+    auto  h         = state.hits[i];
+    auto  scale     = h > 0 ? 1.0f / (float)h : 0.0f;
+    image.pixels[i] = h > 0 ? vec4f{p.x * scale, p.y * scale, p.z * scale, p.w * scale} : vec4f{0, 0, 0, 0};
+  }
+}
+color_image get_render_hits(const pathtrace_state& state) {
+  auto image = color_image{state.width, state.height, true, {}};
+  image.pixels.resize((size_t)state.width * state.height);
+  get_render_hits(image, state);
   return image;
 }
 

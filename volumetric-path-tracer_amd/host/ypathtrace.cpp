@@ -7,8 +7,12 @@
 // pathtrace_samples, save.  Rendering happens on the GPU through include/vpt.h; two extensions: --gpus N (tiles dealt
 // round-robin over N GPUs, same image), --batch n (samples per kernel launch; default: all in one, same image) and --gpubvh
 // (the BVHs built on the GPU by vpt_build_bvh: the same trees), --gputess (the float32 half of tesselate_surfaces on the GPU by
-// vpt_subdivide_vertices: the same meshes).
+// vpt_subdivide_vertices: the same meshes), --adaptive t (adaptive sampling, vpt_render_adaptive: every pixel renders in rounds of
+// --adaptivestep samples until the relative standard error of its mean is within t, never below --adaptivemin samples, at most --samples;
+// the image is written from each pixel's own sample count).
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,7 +25,7 @@ using namespace vpt;
 namespace {
 
 struct option {
-  enum kind_t { string_k, int_k, bool_k, shader_k } kind;
+  enum kind_t { string_k, int_k, bool_k, shader_k, float_k } kind;   // float_k: finite and >= 0
   int         lo, hi;   // int_k: inclusive range (lo > hi: unbounded)
   const char* usage;
 };
@@ -41,6 +45,9 @@ const std::vector<std::pair<string, option>> options = {
     {"batch", {option::int_k, 0, 4096, "Samples per kernel launch, 0 = all. (extension)"}},
     {"gpubvh", {option::bool_k, 1, 0, "Build the BVHs on the GPU: same trees. (extension)"}},
     {"gputess", {option::bool_k, 1, 0, "Subdivision vertex arithmetic on the GPU: same meshes. (extension)"}},
+    {"adaptive", {option::float_k, 1, 0, "Adaptive sampling: relative noise at which a pixel stops, 0 = off. (extension)"}},
+    {"adaptivemin", {option::int_k, 1, 4096, "Adaptive sampling: fewest samples before a pixel stops. (extension)"}},
+    {"adaptivestep", {option::int_k, 1, 4096, "Adaptive sampling: samples per round. (extension)"}},
 };
 const option* find_option(const string& name) {
   for (auto& [n, o] : options)
@@ -51,7 +58,10 @@ const option* find_option(const string& name) {
 string usage() {
   auto text = string{"usage: ypathtrace [options]\nRaytrace scenes.\n\noptions:\n"};
   for (auto& [name, o] : options) {
-    auto line = "  --" + name + (o.kind == option::bool_k ? "/--no-" + name : o.kind == option::int_k ? " <integer>" : " <string>");
+    auto line = "  --" + name + (o.kind == option::bool_k  ? "/--no-" + name
+                                 : o.kind == option::int_k ? " <integer>"
+                                 : o.kind == option::float_k ? " <float>"
+                                                             : " <string>");
     line.resize(line.size() < 32 ? 32 : line.size() + 1, ' ');
     text += line + o.usage + "\n";
     if (o.kind == option::shader_k) {
@@ -79,6 +89,10 @@ void check_value(const string& name, const option& o, const string& text) {
     auto v   = strtol(text.c_str(), &end, 10);
     if (end == text.c_str() || *end != 0) cli_error("bad value for " + name);
     if (o.lo <= o.hi && (v < o.lo || v > o.hi)) cli_error("bad value for " + name);
+  } else if (o.kind == option::float_k) {
+    auto end = (char*)nullptr;
+    auto v   = strtof(text.c_str(), &end);
+    if (end == text.c_str() || *end != 0 || !std::isfinite(v) || v < 0) cli_error("bad value for " + name);
   } else if (o.kind == option::bool_k) {
     if (text != "true" && text != "false") cli_error("bad value for " + name);
   } else if (o.kind == option::shader_k) {
@@ -144,6 +158,12 @@ int main(int argc, const char** argv) {
   get_int("resolution", params.resolution), get_int("samples", params.samples), get_int("bounces", params.bounces);
   get_int("stmaxiter", params.spheretrace_maxiter), get_int("camera", params.camera), get_int("batch", batch), get_int("gpus", gpus);
   get_bool("noparallel", params.noparallel), get_bool("noimplicitmis", params.noimplicit_mis);
+  auto adaptive = pathtrace_adaptive_params{};
+  if (values.count("adaptive")) adaptive.threshold = strtof(values["adaptive"].c_str(), nullptr);
+  adaptive.min_samples = std::min(adaptive.min_samples, params.samples);   // the default never exceeds the cap; an explicit value must not
+  get_int("adaptivemin", adaptive.min_samples), get_int("adaptivestep", adaptive.step);
+  if (adaptive.min_samples > params.samples) cli_error("bad value for adaptivemin");
+  if (adaptive.threshold > 0 && gpus > 1) print_fatal("--adaptive renders on one GPU: it cannot be combined with --gpus " + std::to_string(gpus));
   auto interactive = false, gpubvh = false, gputess = false;
   get_bool("interactive", interactive), get_bool("gpubvh", gpubvh), get_bool("gputess", gputess);
   if (interactive) print_fatal("--interactive is not supported by the GPU build");
@@ -167,6 +187,15 @@ int main(int argc, const char** argv) {
       pathtrace_set_devices(devices);
     }
     auto t0 = std::chrono::steady_clock::now();
+    if (adaptive.threshold > 0) {   // rounds of --adaptivestep samples until every pixel is clean enough or at --samples
+      auto stats = pathtrace_adaptive(state, scene, bvh, lights, params, adaptive);
+      auto secs  = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      auto full  = (double)state.width * state.height * params.samples;
+      printf("adaptive: %d rounds, %lld samples taken of %.0f (%.1f %%) in %.3f s (%.2f Msamples/s)\n", stats.rounds, (long long)stats.samples,
+          full, 100.0 * (double)stats.samples / full, secs, (double)stats.samples / secs * 1e-6);
+      if (!save_image(output, get_render_hits(state), error)) print_fatal(error);
+      return 0;
+    }
     // one launch per `batch` samples (default: all); identical to that many single calls
     if (batch <= 0) batch = params.samples;
     while (state.samples < params.samples) pathtrace_samples(state, scene, bvh, lights, params, batch);
