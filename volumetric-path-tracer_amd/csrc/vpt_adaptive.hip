@@ -2,7 +2,6 @@
 // After every round of the loop in vpt_capi.hip: the noise estimate of each pixel still rendering, the stop decision, and a
 // stable compaction of the pixels left into the lane -> slot table the render kernels read (sched_cfg::lane_slot), so that
 // they run 64 to a wave and converged pixels leave the launch.  Plain C++, vector stores only.
-#define VPT_INSTANCES_TU   // slot_to_pixel only: the elementwise state kernels of vpt_kernels.hip.h live in vpt_capi.hip
 #include "vpt_kernels.hip.h"
 #include "vpt_adaptive.h"
 

@@ -1,5 +1,6 @@
 // vpt_capi.hip — implementation of the C-ABI in include/vpt.h: upload of the scene tables vpt_scene_prep.cpp builds
-// (the device layout of vpt_device.h), kernel launches, state movement.
+// (the device layout of vpt_device.h), kernel launches, state movement.  The kernels are declared in vpt_launch.h and
+// compiled in the kernel units it lists; this unit holds none of their bodies (only rocPRIM's sort is compiled here).
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see __graft_entry__.py).
 // There is NO CPU fallback in this library: without a gfx950 device every compute entry point
 // fails with VPT_ERR_NO_DEVICE.
@@ -14,112 +15,14 @@
 #include <string>
 #include <vector>
 
-#include "vpt_implicit_kernel.hip.h"
-#include "vpt_kat_kernels.hip.h"
-#include "vpt_k1_instances.hip.h"
-#ifdef VPT_SPLIT_TUS   // the path tracers' instances of K1 are compiled in vpt_k1_volpath.hip / vpt_k1_path.hip / vpt_k1_curves.hip
-VPT_K1_SPLIT_INSTANCES(VPT_K1_DECLARE, K_VOLPATH)
-VPT_K1_SPLIT_INSTANCES(VPT_K1_DECLARE, K_PATH)
-VPT_K1_CURVES_INSTANCES(VPT_K1_DECLARE, K_VOLPATH)   // vpt_k1_curves.hip
-VPT_K1_CURVES_INSTANCES(VPT_K1_DECLARE, K_PATH)
-VPT_K1_CURVES_INSTANCES(VPT_K1_DECLARE, K_NAIVE)
-VPT_K1_CURVES_INSTANCES(VPT_K1_DECLARE, K_EYELIGHT)
-VPT_K1_CURVES_INSTANCES(VPT_K1_DECLARE, K_DEBUG)
-extern template __global__ void vpt_intersect_curves_kernel<true>(DScene, int, const float*, int, int*, float*, stack_cfg);
-extern template __global__ void vpt_intersect_curves_kernel<false>(DScene, int, const float*, int, int*, float*, stack_cfg);
-#endif
 #include <rocprim/rocprim.hpp>
 
 #include "vpt_adaptive.h"
 #include "vpt_device_buffer.h"
 #include "vpt_error.h"
+#include "vpt_kat.h"
+#include "vpt_launch.h"
 #include "vpt_scene_prep.h"
-
-// light_prims of the single-leaf mesh lights (vpt_device.h): one thread per (light, primitive of the leaf)
-__global__ void vpt_light_setup_kernel(DScene sc, float4* out) {
-  int l = blockIdx.x, k = threadIdx.x;
-  if (l >= sc.num_lights || k >= 4) return;
-  float4 r7 = sc.light_rec[8 * l + 7];
-  if ((__float_as_int(r7.w) & 255) != VPT_LIGHT_SMALL_MESH || k >= ((__float_as_int(r7.w) >> 8) & 15)) return;
-  const DInstance& inst = sc.instances[sc.lights[l].instance];
-  const DShape&    sh   = sc.shapes[inst.shape];
-  const float4*    leaf = sc.leaf_prims + 4 * ((long long)sh.leaf_offset + ((~sh.root_ref) >> 4) + k);
-  f3 n = eval_element_normal(sc, inst, __float_as_int(leaf[0].w));
-  for (int c = 0; c < 4; c++) out[20 * l + 5 * k + c] = leaf[c];
-  out[20 * l + 5 * k + 4] = make_float4(n.x, n.y, n.z, __int_as_float(sh.is_triangles ? 1 : 0));
-}
-
-// search_light_cdf against the plain binary search on the same CDF: values at, just below and just above CDF
-// entries, uniform ones, and the ends of the range; out[0] = mismatches
-__global__ void vpt_light_cdf_selftest_kernel(DScene sc, int light_id, int n, unsigned long long* out) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const vpt_light& light = sc.lights[light_id];
-  const float*     cdf   = sc.light_cdf + light.cdf_offset;
-  const int        len   = light.cdf_len;
-  float back = cdf[len - 1];
-  // the wave votes inside search_light_cdf: keep all lanes in, flag the surplus ones instead of returning
-  bool     live = i < n;
-  unsigned h    = (unsigned)i * 2654435761u + 12345u;
-  h ^= h >> 15, h *= 2246822519u, h ^= h >> 13;
-  float v = cdf[h % (unsigned)len];
-  switch (i & 7) {
-    case 0: break;
-    case 1: v = __uint_as_float(__float_as_uint(v) - (v > 0 ? 1u : 0u)); break;
-    case 2: v = __uint_as_float(__float_as_uint(v) + 1u); break;
-    case 3: v = 0.0f; break;
-    case 4: v = back; break;
-    default: v = back * ((h >> 8) * (1.0f / 16777216.0f)); break;
-  }
-  float r = clampf(v, 0.0f, back - 0.00001f);
-  int a = search_light_cdf(sc, light_id, r);
-  int lo = 0, cnt = len;   // std::upper_bound, as sample_discrete
-  while (cnt > 0) {
-    int half = cnt >> 1;
-    if (!(r < cdf[lo + half])) lo += half + 1, cnt -= half + 1;
-    else cnt = half;
-  }
-  int b = lo < len ? lo : len - 1;
-  if (live && a != b) atomicAdd(&out[0], 1ull);
-}
-
-// Launch schedule: a wave's duration varies by +-17 % from one launch to the next on the same tile (it depends on which waves shared its SIMD:
-// profiles/r04_k2_lane_histogram.txt), and longest-first scheduling on such estimates ends well above its bound (K2: 225 ms against 203).  The order is
-// therefore taken from a running average of the duration PER SAMPLE (weight = samples seen, capped), whose bit pattern - positive floats - is the sort key.
-__global__ void vpt_cost_average_kernel(const unsigned* __restrict__ cost, float* __restrict__ avg, unsigned* __restrict__ key, int n, float nsamples, float weight) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float per_sample = (float)cost[i] / nsamples;
-  float a = weight > 0 ? (avg[i] * weight + per_sample * nsamples) / (weight + nsamples) : per_sample;
-  avg[i] = a;
-  key[i] = __float_as_uint(a);
-}
-
-// vpt_intersect: one lane per ray through the production traversal (COMPACT: the leaf records of a scene of triangles, as the path tracers read them)
-template <bool SPILL, bool COMPACT>
-__global__ void __launch_bounds__(VPT_BLOCK, VPT_WAVES_PER_SIMD) vpt_intersect_kernel(DScene sc, int n, const float* rays, int instance,
-    int* ids, float* uvt, stack_cfg stack) {
-  extern __shared__ int lds_stack[];
-  const lane_stack2<SPILL> stk = make_lane_stack<SPILL>(lds_stack, stack);
-  int i = blockIdx.x * VPT_BLOCK + threadIdx.x;
-  const bool live = i < n;   // the whole wave goes through the query (traverse(): the group forms need every lane); surplus lanes carry no ray
-  if (!live) i = 0;
-  hit_t h = traverse<COMPACT>(sc, live, mk3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), mk3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]), instance, stk);
-  if (!live) return;
-  ids[2 * i] = h.hit ? h.instance : -1, ids[2 * i + 1] = h.hit ? h.element : -1;
-  uvt[3 * i] = h.hit ? h.uv.x : 0, uvt[3 * i + 1] = h.hit ? h.uv.y : 0, uvt[3 * i + 2] = h.hit ? h.distance : 0;
-}
-
-// all 2^32 operands of rcp_newton (vpt_mesh_kernel.hip.h) against the IEEE quotient; out[0] = mismatches, out[1] = out of range
-__global__ void vpt_reciprocal_selftest_kernel(unsigned long long* out) {
-  unsigned long long bad = 0, skipped = 0;
-  for (unsigned long long b = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; b < (1ull << 32); b += (unsigned long long)gridDim.x * blockDim.x) {
-    float x = __uint_as_float((unsigned)b), a = __builtin_fabsf(x);
-    if (!rcp_in_range(a, a)) { skipped++; continue; }
-    if (__float_as_uint(rcp_newton(x)) != __float_as_uint(1.0f / x)) bad++;
-  }
-  if (bad) atomicAdd(&out[0], bad);
-  if (skipped) atomicAdd(&out[1], skipped);
-}
 
 static std::string& g_error_text() {   // the message of the last failure on the calling thread (vpt_last_error)
   thread_local std::string text;
@@ -589,7 +492,6 @@ static int run_launches(const launch_ctx& L, bool may_split, int slots, const do
 // with the schedule `sch` - by run_launches (vpt_render_device) and by the rounds of vpt_render_device_adaptive
 template <int K>
 static void launch_mesh_instance(const launch_ctx& L, bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
-#if !defined(VPT_EXPERIMENT_ONLY_K2)
   vpt_scene* s = L.s;
   size_t lds = (size_t)s->stack_lds4 * 2 * VPT_BLOCK * sizeof(int) + 5 * VPT_BLOCK * sizeof(float);   // (ref, t0) pairs + the parked words
   const int need = getenv("VPT_NO_LEAN") ? VPT_FEAT_ALL : s->light_features;
@@ -613,20 +515,15 @@ static void launch_mesh_instance(const launch_ctx& L, bool is_pilot, dim3 grid, 
   } else if ((need & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SDF_LIGHTS)) == 0) launch_feat(std::integral_constant<int, VPT_FEAT_SMALL_LIGHTS>{});
   else if ((need & VPT_FEAT_SDF_LIGHTS) == 0) launch_feat(std::integral_constant<int, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_LARGE_LIGHTS>{});
   else launch_feat(std::integral_constant<int, VPT_FEAT_ALL>{});
-#endif
 }
 template <int K>
 static int launch_mesh(const launch_ctx& L) {
-#if defined(VPT_EXPERIMENT_ONLY_K2)   // experiment builds (make variant): only the kernels under study are compiled (minutes -> seconds)
-  return vpt_set_error(VPT_ERR_UNSUPPORTED, "this experiment build holds the implicit kernels only");
-#else
   vpt_scene* s = L.s;
   const bool may_split = !L.stack.spill && (split_mode() == 1 || split_forced_k() >= 0 ||
                                             (split_mode() < 0 && (L.pr.nranks > 1 || (long long)L.grid.x < 3ll * s->wave_slots_k1)));
   return run_launches(L, may_split, s->wave_slots_k1, split_gain, [&](bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
     launch_mesh_instance<K>(L, is_pilot, grid, pr, sch);
   });
-#endif
 }
 // K2 (implicit shaders): LDS of a launch (the refs-only stack + the scene's SDF records); VPT_ERR_UNSUPPORTED when they do not fit
 static int implicit_lds(const vpt_scene* s, size_t& lds) {
@@ -815,9 +712,6 @@ static int check_adaptive(const vpt_scene* s, const vpt_params* params, const vp
   if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null scene");
   if (params->shader < 0 || params->shader > VPT_SHADER_IMPLICIT_NORMAL) return vpt_set_error(VPT_ERR_UNKNOWN_SHADER, "sampler unknown");
   if (params->camera < 0 || params->camera >= s->d.num_cameras) return vpt_set_error(VPT_ERR_INVALID_ARG, "camera %d out of range", params->camera);
-#if defined(VPT_EXPERIMENT_ONLY_K2)
-  if (params->shader < VPT_SHADER_IMPLICIT) return vpt_set_error(VPT_ERR_UNSUPPORTED, "this experiment build holds the implicit kernels only");
-#endif
   return VPT_OK;
 }
 
@@ -1063,48 +957,5 @@ int vpt_selftest_light_cdf(vpt_scene* s, int light, int n, unsigned long long* m
   hipLaunchKernelGGL(vpt_light_cdf_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, s->d, light, n, d.get<unsigned long long>());
   return hipMemcpy(mismatches, d.get(), 8, hipMemcpyDeviceToHost) == hipSuccess ? VPT_OK : vpt_set_error(VPT_ERR_HIP, "light CDF self-test failed to run");
 }
-
-#ifdef VPT_WAVE_TIMES
-int vpt_debug_wave_times(unsigned long long* out, int nwaves) {
-  HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vpt_wave_times), sizeof(unsigned long long) * 2 * (size_t)nwaves));
-  return VPT_OK;
-}
-int vpt_debug_wave_hw(unsigned* out, int nwaves) {
-  HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vpt_wave_hw), sizeof(unsigned) * (size_t)nwaves));
-  return VPT_OK;
-}
-#endif
-
-#ifdef VPT_K2_STATS
-// diagnostic build only: read (and optionally clear) K2's lane statistics (vpt_implicit_kernel.hip.h)
-int vpt_debug_k2_stats(unsigned long long* out24, int reset) {
-  if (out24) HIP_TRY(hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_k2_stats), sizeof(unsigned long long) * 24));
-  if (reset) {
-    unsigned long long zero[24] = {};
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_k2_stats), zero, sizeof(zero)));
-  }
-  return VPT_OK;
-}
-#endif
-
-#ifdef VPT_COUNTERS
-// diagnostic build only: read (and optionally clear) the section counters of vpt_mesh_kernel.hip.h
-int vpt_debug_hist(unsigned long long* out24, int reset) {
-  if (out24) HIP_TRY(hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_vpt_hist), sizeof(unsigned long long) * 24));
-  if (reset) {
-    unsigned long long zero[24] = {};
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_vpt_hist), zero, sizeof(zero)));
-  }
-  return VPT_OK;
-}
-int vpt_debug_counts(unsigned long long* out64, int reset) {
-  if (out64) HIP_TRY(hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_vpt_cnt), sizeof(unsigned long long) * 64));
-  if (reset) {
-    unsigned long long zero[64] = {};
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_vpt_cnt), zero, sizeof(zero)));
-  }
-  return VPT_OK;
-}
-#endif
 
 }  // extern "C"

@@ -19,9 +19,7 @@
 
 #include "vpt.h"
 
-#ifndef VPT_BLOCK
 #define VPT_BLOCK 64   // threads per workgroup = one wave64 = one 8x8 pixel tile: a wave that finishes frees its slot at once
-#endif
 #define VPT_FLOOR_SHIFT 4   // group_nodes() (vpt_mesh_kernel.hip.h): {csgn, slow} in the low 4 bits of the word a ray's state travels in, its pop floor above them
 
 // Scene features a kernel instance is compiled for (template parameter FEAT of the mesh kernels): code for a feature the

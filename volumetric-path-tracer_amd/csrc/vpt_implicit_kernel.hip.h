@@ -50,49 +50,13 @@
 #pragma once
 #include "vpt_mesh_kernel.hip.h"
 
-#ifndef VPT_K2_WAVES
-#define VPT_K2_WAVES 5       // waves per SIMD (round 3, with the settings below: 4: 324, 5: 341, 6: 284 Msamples/s on 06_gridsdf_full; round 2's kernel lost at 5)
-#endif
-#ifndef VPT_K2_SHADE_AT
+// (VPT_K2_WAVES and VPT_K2_WATCHDOG_TICKS, which the host needs as well: vpt_launch.h)
 #define VPT_K2_SHADE_AT 20   // lanes waiting for the shading block before the wave runs it (round 2: 8: -11 %, 16: -4 %, 24: best, 32: -5 %; round 3 with the light-march head inline: 16: -3 %, 20: +1 %, 32: -1 %)
-#endif
-#ifndef VPT_K2_WATCHDOG_TICKS
-#define VPT_K2_WATCHDOG_TICKS 30000000000ull   // 300 s: two orders of magnitude above the longest wave of any test workload (the launch passes it as an argument; VPT_K2_WATCHDOG_MS overrides it for the tests of the error path)
-#endif
-#ifndef VPT_K2_LIGHT_INLINE
-#define VPT_K2_LIGHT_INLINE 3   // (0: 299, 2: 313, 3: 333, 4: 315-320, 6: 334 Msamples/s on 06_gridsdf_full; 07_sdfunction_synth 121 -> 136) n > 0: the first n steps of an SDF light's pdf march run inside the shading block (55 % of the marches end within two steps: the ray recedes from the light), the rest as M_LIGHT trips; < 0: the whole march inline (round 2: 145 against 179 Msamples/s); 0: all of it as M_LIGHT trips
-#endif
-#ifndef VPT_K2_LIGHT_AT
+#define VPT_K2_LIGHT_INLINE 3   // (0: 299, 2: 313, 3: 333, 4: 315-320, 6: 334 Msamples/s on 06_gridsdf_full; 07_sdfunction_synth 121 -> 136) this many first steps of an SDF light's pdf march run inside the shading block (55 % of the marches end within two steps: the ray recedes from the light), the rest as M_LIGHT trips (round 2: the whole march inline: 145 against 179 Msamples/s; 0: all of it as M_LIGHT trips)
 #define VPT_K2_LIGHT_AT 4       // lanes in M_LIGHT before the wave spends a round on light-march steps while other lanes march the scene (round 2: 1: 178, 8: 204, 16: 204 Msamples/s; round 3, marches that survive their inline head: 06_gridsdf_full 1: 287, 2: 303, 4: 324, 8: 333; 07_sdfunction_synth 4: 150, 8: 136 - 4 is the better sum)
-#endif
-#ifndef VPT_K2_LIGHT_STEPS
 #define VPT_K2_LIGHT_STEPS 16   // light-march steps per light round (32: 341, 16: 347 Msamples/s)
-#endif
-#ifndef VPT_K2_LIGHT_EXIT
-#define VPT_K2_LIGHT_EXIT 0     // leave a light round as soon as none of its marches is alive
-#endif
-#ifndef VPT_K2_GROUP_MAX
 #define VPT_K2_GROUP_MAX 16  // scene-march rounds with at most this many marching rays run four lanes per ray (0: never)
-#endif
-#ifndef VPT_K2_STEPS
 #define VPT_K2_STEPS 12      // march steps between two looks at the wave's state (round 2: 2: -5 %, 4: -1.5 %, 8: best; end of round 4, 512 samples per launch: 8: 408 / 175.7, 12: 416.5 / 177.2, 16: 416.5 / 177.0, 24: 415.3 / 173.1 Msamples/s on 06_gridsdf_full / 07_sdfunction_synth)
-#endif
-
-// Diagnostic build (-DVPT_K2_STATS): where the lanes of a wave are, trip by trip (profiles/tools/k2_stats.py).  Never in the product build.
-#ifdef VPT_K2_STATS
-__device__ unsigned long long g_k2_stats[24];
-enum { KS_TRIPS, KS_SCENE_ROUNDS, KS_SCENE_LANES, KS_LIGHT_ROUNDS, KS_LIGHT_LANES, KS_SHADE_ROUNDS, KS_SHADE_LANES, KS_DONE_LANES,
-  KS_WAIT_LANES_AT_MARCH, KS_LIGHT_LANES_AT_SCENE, KS_SCENE_LANES_AT_SHADE, KS_CLK_SCENE, KS_CLK_LIGHT, KS_CLK_SHADE, KS_CLK_TOTAL,
-  KS_SCENE_LE8, KS_SCENE_LE16, KS_SCENE_LE32, KS_SCENE_LANES_LE16, KS_SCENE_LANES_LE32, KS_COUNT };
-#define K2_STAT(k, v) stats[k] += (unsigned long long)(v)
-// shader-clock stamp that the scheduler cannot move (diagnostic build only)
-#define K2_CLOCK(var) unsigned long long var; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) : : "memory")
-#define K2_LAP(k, a, b) stats[k] += (b) - (a)
-#else
-#define K2_STAT(k, v)
-#define K2_CLOCK(var)
-#define K2_LAP(k, a, b)
-#endif
 
 enum { M_NEW = 0, M_SCENE = 1, M_HIT = 2, M_MISS = 3, M_LIGHT = 4, M_LIGHTS = 5, M_DONE = 6 };
 
@@ -249,10 +213,6 @@ __device__ __forceinline__ void implicit_kernel_body(const DScene& sc, const DPa
   float mis_pdf = 0, lp_sum = 0;
   int   lp_light = 0;
 
-#ifdef VPT_K2_STATS
-  unsigned long long stats[KS_COUNT] = {};
-#endif
-  K2_CLOCK(cstart);
   bool gave_up = false;
   while (true) {
     // every wave reaches an exit: the state machine ends when all lanes are M_DONE; should a defect ever keep it from
@@ -264,21 +224,14 @@ __device__ __forceinline__ void implicit_kernel_body(const DScene& sc, const DPa
     unsigned long long marching = __builtin_amdgcn_ballot_w64(mode == M_SCENE || mode == M_LIGHT);
     unsigned long long waiting  = __builtin_amdgcn_ballot_w64(mode == M_NEW || mode == M_HIT || mode == M_MISS || mode == M_LIGHTS);
     if ((marching | waiting) == 0) break;   // every lane M_DONE
-    K2_STAT(KS_TRIPS, 1);
-    K2_STAT(KS_DONE_LANES, 64 - __popcll(marching | waiting));
 
     if (marching != 0 && __popcll(waiting) < shade_at) {
       // ---- march steps ------------------------------------------------------------------------------
-      K2_STAT(KS_WAIT_LANES_AT_MARCH, __popcll(waiting));
-      K2_CLOCK(c0);
       const unsigned long long ms = __builtin_amdgcn_ballot_w64(mode == M_SCENE);
       if (VPT_K2_GROUP_MAX > 0 && sc.group_forms != 0 && ms != 0 && __popcll(ms) <= VPT_K2_GROUP_MAX) {
         // A small set of marching rays (a quarter of the scene rounds hold <= 16, a fifth <= 8: profiles/r04_k2_lane_histogram.txt): ray k of the
         // set on lanes 4k .. 4k+3 - whoever owns them: lanes whose pixel is finished, lanes that wait for the shading block - each lane
         // evaluating a quarter of the scene's SDFs per step (eval_sdf_scene_group); the ray's t sequence is the reference's, step for step
-        K2_STAT(KS_SCENE_ROUNDS, 1);
-        K2_STAT(KS_SCENE_LANES, __popcll(ms));
-        K2_STAT(KS_SCENE_LE16, 1);
         const int  lane = threadIdx.x, gj = lane & 3;
         const bool mine = (ms >> lane) & 1;
         const int  rank = lanes_below(ms), nrays = __popcll(ms);
@@ -298,14 +251,6 @@ __device__ __forceinline__ void implicit_kernel_body(const DScene& sc, const DPa
           if (nmode == M_HIT) hit_id = nhi >= 0 ? nhi : ~nhs;
         }
       } else if (ms != 0) {
-        K2_STAT(KS_SCENE_ROUNDS, 1);
-        K2_STAT(KS_SCENE_LANES, __popcll(__builtin_amdgcn_ballot_w64(mode == M_SCENE)));
-        K2_STAT(KS_SCENE_LE8, __popcll(__builtin_amdgcn_ballot_w64(mode == M_SCENE)) <= 8);
-        K2_STAT(KS_SCENE_LE16, __popcll(__builtin_amdgcn_ballot_w64(mode == M_SCENE)) <= 16);
-        K2_STAT(KS_SCENE_LE32, __popcll(__builtin_amdgcn_ballot_w64(mode == M_SCENE)) <= 32);
-        K2_STAT(KS_SCENE_LANES_LE16, __popcll(__builtin_amdgcn_ballot_w64(mode == M_SCENE)) <= 16 ? __popcll(__builtin_amdgcn_ballot_w64(mode == M_SCENE)) : 0);
-        K2_STAT(KS_SCENE_LANES_LE32, __popcll(__builtin_amdgcn_ballot_w64(mode == M_SCENE)) <= 32 ? __popcll(__builtin_amdgcn_ballot_w64(mode == M_SCENE)) : 0);
-        K2_STAT(KS_LIGHT_LANES_AT_SCENE, __popcll(__builtin_amdgcn_ballot_w64(mode == M_LIGHT)));
         for (int k = 0; k < VPT_K2_STEPS; k++)
           if (mode == M_SCENE) {
             int hi = -1, hs = -1;
@@ -313,16 +258,10 @@ __device__ __forceinline__ void implicit_kernel_body(const DScene& sc, const DPa
             if (mode == M_HIT) hit_id = hi >= 0 ? hi : ~hs;
           }
       }
-      K2_CLOCK(c1);
-      K2_LAP(KS_CLK_SCENE, c0, c1);
       // SDF-light marches: cheap steps (one analytic SDF), several per trip; lanes of one light at a time so that the
       // light's record is wave-uniform (scalar loads)
       unsigned long long lm = __builtin_amdgcn_ballot_w64(mode == M_LIGHT);
       if (__popcll(lm) < light_at && __builtin_amdgcn_ballot_w64(mode == M_SCENE) != 0) lm = 0;   // too few: let them wait for company
-      if (lm != 0) {
-        K2_STAT(KS_LIGHT_ROUNDS, 1);
-        K2_STAT(KS_LIGHT_LANES, __popcll(lm));
-      }
       while (lm != 0) {
         int  l    = __builtin_amdgcn_readlane(lp_light, __ffsll((long long)lm) - 1);   // the light of the first lane still to serve
         bool mine = mode == M_LIGHT && lp_light == l;
@@ -331,21 +270,14 @@ __device__ __forceinline__ void implicit_kernel_body(const DScene& sc, const DPa
           float area = sc.light_cdf[light.cdf_offset + light.cdf_len - 1];
           for (int k = 0; k < VPT_K2_LIGHT_STEPS; k++) {
             if (mode == M_LIGHT && !light_march_step(recs, light.sdf, area, ro, rd, maxiter, t, it, lp_sum)) mode = M_LIGHTS, lp_light++;
-            if (VPT_K2_LIGHT_EXIT && __builtin_amdgcn_ballot_w64(mode == M_LIGHT) == 0) break;   // every march of this light has ended
           }
         }
         lm &= ~__builtin_amdgcn_ballot_w64(mine);
       }
-      K2_CLOCK(c2);
-      K2_LAP(KS_CLK_LIGHT, c1, c2);
       continue;
     }
-    K2_CLOCK(c3);
 
     // ---- shading block: the lanes that wait for it ---------------------------------------------------
-    K2_STAT(KS_SHADE_ROUNDS, 1);
-    K2_STAT(KS_SHADE_LANES, __popcll(waiting));
-    K2_STAT(KS_SCENE_LANES_AT_SHADE, __popcll(marching));
     bool finish = false, next_vertex = false;   // next_vertex: a path vertex was completed, the new ray is in (ro, rd)
     if (mode == M_MISS) {   // cpp:444-447 / 545
       if constexpr (SH == K_IMPLICIT) radiance = radiance + weight * eval_environment(sc, rd);
@@ -412,15 +344,14 @@ __device__ __forceinline__ void implicit_kernel_body(const DScene& sc, const DPa
           int    kind = __float_as_int(r7.w) & 255;
           if (kind == VPT_LIGHT_SDF) {
             t = VPT_RAY_EPS, it = 0;
-            if (VPT_K2_LIGHT_INLINE != 0) {   // the march's first steps (all of them if < 0) here, in the shading block
-              const vpt_light& light = sc.lights[lp_light];
-              float area = sc.light_cdf[light.cdf_offset + light.cdf_len - 1];
-              bool  alive = true;
-              for (int k = 0; alive && (VPT_K2_LIGHT_INLINE < 0 || k < VPT_K2_LIGHT_INLINE); k++) alive = light_march_step(recs, light.sdf, area, ro, rd, maxiter, t, it, lp_sum);
-              if (!alive) {
-                lp_light++;
-                continue;
-              }
+            // the march's first steps here, in the shading block
+            const vpt_light& light = sc.lights[lp_light];
+            float area = sc.light_cdf[light.cdf_offset + light.cdf_len - 1];
+            bool  alive = true;
+            for (int k = 0; alive && k < VPT_K2_LIGHT_INLINE; k++) alive = light_march_step(recs, light.sdf, area, ro, rd, maxiter, t, it, lp_sum);
+            if (!alive) {
+              lp_light++;
+              continue;
             }
             mode = M_LIGHT;   // needs (the rest of) a march: hand over
             break;
@@ -469,8 +400,6 @@ __device__ __forceinline__ void implicit_kernel_body(const DScene& sc, const DPa
         if (SH == K_IMPLICIT && nb <= 0) mode = M_MISS, weight = mk3(0, 0, 0);   // no bounce allowed: the reference's loop body never runs (radiance 0, alpha 1)
       }
     }
-    K2_CLOCK(c4);
-    K2_LAP(KS_CLK_SHADE, c3, c4);
   }
 
   if (gave_up && threadIdx.x == 0 && watchdog) atomicAdd(watchdog, 1u);
@@ -481,36 +410,22 @@ __device__ __forceinline__ void implicit_kernel_body(const DScene& sc, const DPa
     r_out.x = rng.state, r_out.y = rng.inc;
     rngs[slot] = r_out;
   }
-#ifdef VPT_K2_STATS
-  K2_CLOCK(cend);
-  K2_LAP(KS_CLK_TOTAL, cstart, cend);
-  if (threadIdx.x == 0)
-    for (int k = 0; k < KS_COUNT; k++) atomicAdd(&g_k2_stats[k], stats[k]);
-#endif
   if (sched.cost && threadIdx.x == 0) {
     unsigned long long dt = clock_ticks(__float_as_int(acc.x)) - wave_start;   // after the last sample was accumulated
     sched.cost[wave] = dt < 0xffffffffull ? (unsigned)dt : 0xffffffffu;
-#ifdef VPT_WAVE_TIMES
-    if (wave < 65536) {   // diagnostic build: the launch's occupancy timeline (profiles/tools/wave_slots.py), as K1 records it
-      g_vpt_wave_times[2 * wave] = wave_start, g_vpt_wave_times[2 * wave + 1] = wave_start + dt;
-      unsigned hw, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      g_vpt_wave_hw[wave] = (xcc & 0xf) << 16 | (hw & 0xffff);
-    }
-#endif
   }
 }
 
+// the kernels (launch bounds: vpt_launch.h; instances: vpt_k2.hip)
 template <int SH, int FEAT>
-__global__ void __launch_bounds__(VPT_BLOCK, VPT_K2_WAVES) vpt_render_kernel(DScene sc, DParams pr, float4* __restrict__ image,
+__global__ void vpt_render_kernel(DScene sc, DParams pr, float4* __restrict__ image,
     int* __restrict__ hits, ulonglong2* __restrict__ rngs, int stack_cap, sched_cfg sched, unsigned* __restrict__ watchdog, unsigned long long watchdog_ticks) {
   implicit_kernel_body<SH, FEAT>(sc, pr, image, hits, rngs, stack_cap, sched, watchdog, watchdog_ticks);
 }
 // The same kernel under another name: the short launch that measures per-wave costs when none are known yet (vpt_capi.hip),
 // kept apart so that profiles of vpt_render_kernel only hold full launches (as vpt_mesh_pilot_kernel for K1).
 template <int SH, int FEAT>
-__global__ void __launch_bounds__(VPT_BLOCK, VPT_K2_WAVES) vpt_render_pilot_kernel(DScene sc, DParams pr, float4* __restrict__ image,
+__global__ void vpt_render_pilot_kernel(DScene sc, DParams pr, float4* __restrict__ image,
     int* __restrict__ hits, ulonglong2* __restrict__ rngs, int stack_cap, sched_cfg sched, unsigned* __restrict__ watchdog, unsigned long long watchdog_ticks) {
   implicit_kernel_body<SH, FEAT>(sc, pr, image, hits, rngs, stack_cap, sched, watchdog, watchdog_ticks);
 }

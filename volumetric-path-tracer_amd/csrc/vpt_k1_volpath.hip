@@ -1,4 +1,3 @@
-// K1's instances for volpathtrace: see vpt_k1_instances.hip.h
-#define VPT_INSTANCES_TU
-#include "vpt_k1_instances.hip.h"
+// K1's instances for volpathtrace (the list: vpt_k1_instances.hip.h)
+#include "vpt_mesh_kernel.hip.h"
 VPT_K1_SPLIT_INSTANCES(VPT_K1_DEFINE, K_VOLPATH)

@@ -36,8 +36,9 @@ VPT_DEV float kat_lights_pdf_k1(const DScene& sc, bool live, f3 position, f3 dir
   return sum * ((float)1 / (float)sc.num_lights);
 }
 
+// launch bounds: vpt_launch.h; instances: vpt_kernels.hip
 template <bool SPILL>
-__global__ void __launch_bounds__(VPT_BLOCK, VPT_WAVES_PER_SIMD) vpt_kat_kernel(DScene sc, int op, int iparam, int n, int si, int so,
+__global__ void vpt_kat_kernel(DScene sc, int op, int iparam, int n, int si, int so,
     const float* __restrict__ in, const int* __restrict__ aux, float* __restrict__ out, stack_cfg stack, int stack_cap) {
   extern __shared__ int lds_stack[];
   const lane_stack2<SPILL> stk4 = make_lane_stack<SPILL>(lds_stack, stack);   // quad-node traversal (K1)

@@ -42,15 +42,7 @@
 #pragma once
 #include "vpt_kernels.hip.h"
 
-// (ref, t0) stack of one lane: the first `cap` entries live in LDS (entry-major: conflict-free), deeper
-// ones in a per-launch HBM array (entry-major too: coalesced).  `cap` covers what traversals use in
-// practice; the HBM part only makes the worst case (three pending siblings on every quad level) safe.
-struct stack_cfg {
-  int        cap;      // entries per lane in LDS
-  int        spill;    // entries per lane in HBM
-  int2*      mem;      // spill * lanes entries
-  long long  lanes;    // lanes of the launch (= entry stride)
-};
+// (ref, t0) stack of one lane (stack_cfg, vpt_launch.h): the first `cap` entries live in LDS, deeper ones in HBM
 template <bool SPILL>
 struct lane_stack2 {
   int*      base;   // &lds[threadIdx.x]; entry e: ref at base[(2e)*VPT_BLOCK], t0 at base[(2e+1)*VPT_BLOCK]
@@ -195,21 +187,8 @@ VPT_DEV bool slab_pass_signed(float nx, float ny, float nz, float fx, float fy, 
 // needed C work ("sessions"): fewer transfers, but the rays outside a session waited for its longest member - 174 wave-level node
 // steps per 64 samples against the own form's 132 - and it LOST (276 ms, profiles/r04_k1_group_forms.txt).
 #define VPT_NONE (-2147483647 - 1)
-#ifndef VPT_HOIST_MAX
 #define VPT_HOIST_MAX 16   // scenes with at most this many instances test all root boxes at the start of a query
-#endif
-#ifndef VPT_COOP_MAX
 #define VPT_COOP_MAX 16    // a phase with at most this many rays runs in its group form (four lanes per ray); 0: own forms only
-#endif
-#ifndef VPT_COOP_NODES
-#define VPT_COOP_NODES VPT_COOP_MAX   // (experiments: the group form of one phase only)
-#endif
-#ifndef VPT_COOP_LEAVES
-#define VPT_COOP_LEAVES VPT_COOP_MAX
-#endif
-#ifdef VPT_TRAVERSE_GUARD
-__device__ unsigned g_vpt_guard_trips;   // diagnostic build: queries that were cut short after VPT_TRAVERSE_GUARD loop rounds (must stay 0)
-#endif
 template <bool COMPACT = false, bool CURVES = false, class STK>
 VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_instance, const STK& stk) {
   constexpr int LS = COMPACT ? 3 : 4;   // float4 per leaf record
@@ -235,7 +214,6 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
     while (sp > base) {
       int   ref;
       float t0;
-      VPT_CNT(CNT_POP);
       sp--;
       if (lds_only) stk.load_lds(sp, ref, t0);
       else stk.load(sp, ref, t0);
@@ -256,7 +234,6 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
       int slot = pend >> 4;
       pend += 15;   // first slot + 1, count - 1
       if (!((reach >> (slot & 31)) & 1)) continue;
-      VPT_CNT(CNT_ENTER);
       const float4* e = sc.scene_enter + 6 * (long long)slot;
       float4 e2 = e[2], e3 = e[3], e4 = e[4], e5 = e[5];
       bool   general = !__float_as_int(e5.z) || wslow;
@@ -326,7 +303,6 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
 
   // ---- own form of A: one quad-node step of this lane's ray ------------------------------------------------------------
   auto own_node_step = [&]() {
-    VPT_CNT(CNT_NODE);
     const float4* q = sc.scene_wnodes + 8 * (long long)(wnb + cur);
     // rows of the node: lo.x lo.y lo.z hi.x hi.y hi.z (four children each).  The near plane of an axis is
     // the lo row for a positive direction, the hi row for a negative one: fetch them by the ray's signs
@@ -400,13 +376,11 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
   // ---- own form of B: the primitives of the shape leaf `cur`, in order ---------------------------------------------------
   auto own_leaf = [&]() {
     int code = ~cur, start = code >> 4, num = code & 15;
-    VPT_CNT(CNT_LEAF);
     // software-pipelined: the next primitive's record is in flight while this one is tested (a leaf's
     // records are contiguous; one past the last primitive of the pool is still inside the padded array)
     const float4* rec = leaf_rec<COMPACT>(sc, leafb + start);
     float4 n0 = rec[0], n1 = rec[1], n2 = rec[2], n3 = rec[LS - 1];   // (a compact record ends after its third corner: p3 = p2, the reference's triangle)
     for (int k = 0; k < num; k++) {
-      VPT_CNT(CNT_PRIM);
       float4 r0 = n0, r1 = n1, r2 = n2, r3 = n3;
       rec += LS;
       n0 = rec[0], n1 = rec[1], n2 = rec[2], n3 = rec[LS - 1];
@@ -424,13 +398,9 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
     cur = pop_valid();
   };
 
-#ifdef VPT_TRAVERSE_GUARD
-  int guard = 0;
-#endif
   // ---- phase A of a small set: the rays of the lanes in `m` (at most 16, each on a quad node) on four lanes each, until every one of
   // them holds a leaf or nothing (the loop the own form runs lane by lane: same steps, same order, a quarter of the work per lane) ----
   auto group_nodes = [&](unsigned long long m) {
-    VPT_CNT_MASK(CNT_SESSION, m);   // "lanes" of this counter = rays handed over
     const int  lane = threadIdx.x, j = lane & 3;
     const bool mine = (m >> lane) & 1;
     const int  rank = lanes_below(m), n = __popcll(m);
@@ -451,11 +421,6 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
     const bool gslow = (gmisc & 8) != 0;
     const STK  gstk = stk.of_lane(owner);
     while (__builtin_amdgcn_ballot_w64(gcur >= 0) != 0) {
-      VPT_CNT_MASK(CNT_GNODE, __builtin_amdgcn_ballot_w64(gcur >= 0));
-      VPT_HIST(__popcll(__builtin_amdgcn_ballot_w64(gcur >= 0)) >> 2);
-#ifdef VPT_TRAVERSE_GUARD
-      if (++guard > VPT_TRAVERSE_GUARD) gcur = VPT_NONE;   // (the outer loop reports it)
-#endif
       if (gcur >= 0) {
         const float* q = (const float*)(sc.scene_wnodes + 8 * (long long)(gwnb + gcur));
         float lox = q[j], loy = q[4 + j], loz = q[8 + j], hix = q[12 + j], hiy = q[16 + j], hiz = q[20 + j];
@@ -519,7 +484,6 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
     int        owner = quad_lane0(__builtin_amdgcn_ds_permute(mine ? rank << 4 : 4, lane));
     const bool gact  = (lane >> 2) < n;
     if (!gact) owner = lane;
-    VPT_CNT_MASK(CNT_GLEAF, m);
     const f3 gco = pull(owner, co), gcd = pull(owner, cd);
     float    gtmax = pull(owner, tmax);
     const int gcode = pull(owner, ~cur), gleafb = pull(owner, leafb);
@@ -573,38 +537,25 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
   };
 
   while (true) {
-    VPT_CNT(CNT_OUTER);
-#ifdef VPT_TRAVERSE_GUARD
-    if (++guard > VPT_TRAVERSE_GUARD) {
-      if (!done) atomicAdd(&g_vpt_guard_trips, 1u);
-      break;
-    }
-#endif
     // ---- A: quad nodes, until no lane holds one.  More than VPT_COOP_MAX rays: every lane steps its own; fewer: four lanes per ray ----------
-    VPT_T0(TM_NODES);
     const unsigned long long ma = __builtin_amdgcn_ballot_w64(!done && cur >= 0);
     if (ma != 0) {
-      if (VPT_COOP_NODES > 0 && whole_wave && __popcll(ma) <= VPT_COOP_NODES) group_nodes(ma);
+      if (VPT_COOP_MAX > 0 && whole_wave && __popcll(ma) <= VPT_COOP_MAX) group_nodes(ma);
       else if (!done && cur >= 0) own_node_step();
-      VPT_T1(TM_NODES);
       continue;
     }
-    VPT_T1(TM_NODES);
     // ---- B: shape leaves --------------------------------------------------------------------------------------------------------------
-    VPT_T0(TM_PRIMS);
     {
       const bool at_leaf = !done && cur != VPT_NONE && shape_base >= 0;   // (cur < 0 for every lane here)
       const unsigned long long mb = __builtin_amdgcn_ballot_w64(at_leaf);
       bool own = at_leaf;
-      if (VPT_COOP_LEAVES > 0 && whole_wave && mb != 0 && __popcll(mb) <= VPT_COOP_LEAVES) {
+      if (VPT_COOP_MAX > 0 && whole_wave && mb != 0 && __popcll(mb) <= VPT_COOP_MAX) {
         own = group_leaves(mb);
         if (at_leaf && !own) cur = pop_valid();
       }
       if (own) own_leaf();
     }
-    VPT_T1(TM_PRIMS);
     // ---- C: a level is exhausted or a scene leaf is reached ---------------------------------------------------------------------
-    VPT_T0(TM_ENTER);
     if (!done && cur < 0 && (cur == VPT_NONE || shape_base < 0)) {
       bool go = true;
       if (cur == VPT_NONE) {
@@ -619,7 +570,6 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
         if (cur == VPT_NONE && shape_base < 0) done = true;
       }
     }
-    VPT_T1(TM_ENTER);
     if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
   }
   r.hit = r.instance >= 0;
@@ -756,15 +706,6 @@ VPT_DEV void eval_surface_point(const DScene& sc, const DInstance& inst, const v
 
 enum { ST_NEW = 0, ST_MAIN = 1, ST_LPDF = 2 };
 
-#ifndef VPT_WAVES_PER_SIMD
-#define VPT_WAVES_PER_SIMD 2
-#endif
-
-#ifdef VPT_WAVE_TIMES
-// diagnostic build: start / end of every wave on the 100 MHz wall clock, to draw the launch's occupancy timeline
-__device__ unsigned long long g_vpt_wave_times[2 * 65536];
-__device__ unsigned g_vpt_wave_hw[65536];   // XCC_ID << 16 | HW_ID[15:0] (wave, simd, pipe, cu, sh, se)
-#endif
 
 template <int SH, bool SPILL, int FEAT>
 VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __restrict__ image, int* __restrict__ hits,
@@ -774,9 +715,6 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
   __shared__ unsigned long long s_wave_start;   // the start stamp, parked in LDS (clock_ticks, vpt_math.hip.h)
   if (threadIdx.x == 0) s_wave_start = clock_ticks(blockIdx.x);
   const int wave = sched.order ? sched.order[blockIdx.x] : (int)blockIdx.x;
-#ifdef VPT_COUNTERS
-  if (threadIdx.x < 16) s_vpt_time[threadIdx.x] = 0;
-#endif
 
   int slot = wave * VPT_BLOCK + threadIdx.x;
   if (sched.lane_slot) slot = sched.lane_slot[slot];   // a split tile: this wave holds every 2^k-th pixel of it in its first lanes
@@ -816,13 +754,10 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
   bool  mis_toggle = false;
 
   if (slot < 0) sample = pr.nsamples;   // a lane without a pixel has nothing to render: it starts where the others end
-  VPT_T0(TM_KERNEL);
   while (true) {
     const bool alive = !(state == ST_NEW && sample == pr.nsamples);   // this lane's pixel still has samples to render
     if (__builtin_amdgcn_ballot_w64(alive) == 0) break;   // wave-uniform: every lane stays until the tile is finished
     if (alive && state == ST_NEW) {
-      VPT_CNT(CNT_GENERATE);
-      VPT_T0(TM_GENERATE);
       const vpt_camera& cam = sc.cameras[pr.camera];
       float u, v;
       if (pr.preview) {
@@ -839,7 +774,6 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
       ray      = eval_camera(cam, mk2(u, v), lens);
       radiance = mk3(0, 0, 0), weight = mk3(1, 1, 1);
       alpha = 0, bounce = 0, in_medium = false, state = ST_MAIN;
-      VPT_T1(TM_GENERATE);
     }
 
     // ---- the one BVH query of this trip: the whole wave is in the call, lanes without a ray as helpers ---------------
@@ -847,16 +781,13 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
     bool finish = alive && !query;   // the path ran out of bounces
     const bool lpdf_query = HAS_LARGE && query && state == ST_LPDF;
     const int  qinst      = lpdf_query ? sc.lights[lp_light].instance : -1;
-    VPT_T0(TM_QUERY);
     hit_t h = traverse<(FEAT & VPT_FEAT_COMPACT_TRIS) != 0, (FEAT & VPT_FEAT_CURVES) != 0>(sc, query, lpdf_query ? lp_pos : ray.o, ray.d, qinst, stk);
-    VPT_T1(TM_QUERY);
     if constexpr (!HAS_LARGE) {
       // without light walks that span trips (ST_LPDF) a pending MIS evaluation never outlives its trip: say so, or its seven words
       // stay allocated through every BVH query
       mis_f = mk3(0, 0, 0), mis_pdf = 0, lp_sum = 0, lp_light = 0, mis_toggle = false;
     }
     if (query) {
-      VPT_CNT(CNT_TRIP);
 
       bool advance_lights = false;   // continue the light-pdf walk at lp_light
       if (lpdf_query) {
@@ -901,7 +832,6 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
         f2     l_ruv = mk2(0, 0);
         float  l_rel = 0, l_rl = 0;
         mpoint m;
-        VPT_T0(TM_MEDIUM);
         if constexpr (SH == K_VOLPATH) {
           if (in_medium) {   // cpp:586-596 — rd is drawn before rl
             float rd       = rand1f(rng);
@@ -912,13 +842,9 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
             h.distance = distance;
           }
         }
-        VPT_T1(TM_MEDIUM);
-        VPT_T0(TM_SURFACE);
         if (!in_volume) {
           const DInstance& inst = sc.instances[h.instance];
-          VPT_T0(TM_SURF_GEOM);
           eval_surface_point<(FEAT & VPT_FEAT_COMPACT_TRIS) != 0, (FEAT & VPT_FEAT_CURVES) != 0>(sc, inst, sc.materials[inst.material], h.prim, h.element, h.uv, outgoing, position, normal, m);
-          VPT_T1(TM_SURF_GEOM);
           if (m.opacity < 1 && rand1f(rng) >= m.opacity) {
             ray = make_ray(position + ray.d * 1e-2f, ray.d);   // bounce -= 1; continue
           } else {
@@ -975,7 +901,6 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
                 }
                 scatter = 1;
               } else {
-                VPT_T0(TM_SURF_DELTA);
                 float rnl = rand1f(rng);
                 incoming  = sample_delta(m, normal, outgoing, rnl);
                 weight    = weight * (eval_delta(m, normal, outgoing, incoming) / sample_delta_pdf(m, normal, outgoing, incoming));
@@ -990,13 +915,10 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
                 ray = make_ray(position, incoming);
                 if (!survive(weight, bounce, rng)) finish = true;
                 bounce++;
-                VPT_T1(TM_SURF_DELTA);
               }
             }
           }
         }
-        VPT_T1(TM_SURFACE);
-        VPT_T0(TM_VOLUME);
         if (in_volume) if constexpr (SH == K_VOLPATH) {   // volume event, cpp:654-673
           position = ray_point(ray, h.distance);
           radiance = radiance + weight * eval_emission(med_emission, position, outgoing);   // (sic) cpp:660
@@ -1015,12 +937,8 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
           }
           scatter = 2;
         }
-        VPT_T1(TM_VOLUME);
         if constexpr (HAS_MIS) {
-          VPT_T0(TM_SAMPLE_LIGHTS);
           if (want_lights) incoming = sample_lights<FEAT>(sc, position, l_rl, l_rel, l_ruv);
-          VPT_T1(TM_SAMPLE_LIGHTS);
-          VPT_T0(TM_SCATTER_EVAL);
           if (scatter == 1) {   // cpp:626-648
             if (is_zero3(incoming)) finish = true;
             else {
@@ -1039,13 +957,11 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
             ray        = make_ray(position, incoming);
             lp_sum = 0, lp_light = 0, advance_lights = true;
           }
-          VPT_T1(TM_SCATTER_EVAL);
         }
       }
 
       if constexpr (HAS_MIS) {
         if (advance_lights) {   // sample_lights_pdf's loop over lights, resumable (cpp:353-421)
-          VPT_T0(TM_LIGHTS_PDF);
           state = ST_MAIN;
           while (lp_light < sc.num_lights) {
             float4 r6 = sc.light_rec[8 * lp_light + 6], r7 = sc.light_rec[8 * lp_light + 7];
@@ -1067,7 +983,6 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
             if (!survive(weight, bounce, rng)) finish = true;
             bounce++;
           }
-          VPT_T1(TM_LIGHTS_PDF);
         }
       }
     }
@@ -1081,11 +996,6 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
     }
   }
 
-  VPT_T1(TM_KERNEL);
-#ifdef VPT_COUNTERS
-  if ((threadIdx.x & 63) == 0)   // lane 0 owns a pixel whenever the wave does (padding lanes sit at the end)
-    for (int k = 0; k < 16; k++) atomicAdd(&g_vpt_cnt[32 + k], s_vpt_time[k]);
-#endif
   if (slot >= 0) {
     image[slot] = make_float4(park[0], park[VPT_BLOCK], park[2 * VPT_BLOCK], park[3 * VPT_BLOCK]);
     hits[slot] += pr.nsamples;
@@ -1097,27 +1007,19 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
     const unsigned long long wave_start = s_wave_start;
     unsigned long long dt = clock_ticks(slot) - wave_start;   // after the last sample was accumulated
     sched.cost[wave] = dt < 0xffffffffull ? (unsigned)dt : 0xffffffffu;
-#ifdef VPT_WAVE_TIMES
-    if (wave < 65536) {
-      g_vpt_wave_times[2 * wave] = wave_start, g_vpt_wave_times[2 * wave + 1] = wave_start + dt;
-      unsigned hw, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      g_vpt_wave_hw[wave] = (xcc & 0xf) << 16 | (hw & 0xffff);
-    }
-#endif
   }
 }
 
+// the kernels (launch bounds: vpt_launch.h; instances: vpt_k1_*.hip)
 template <int SH, bool SPILL, int FEAT>
-__global__ void __launch_bounds__(VPT_BLOCK, VPT_WAVES_PER_SIMD) vpt_mesh_kernel(DScene sc, DParams pr,
+__global__ void vpt_mesh_kernel(DScene sc, DParams pr,
     float4* __restrict__ image, int* __restrict__ hits, ulonglong2* __restrict__ rngs, stack_cfg stack, sched_cfg sched) {
   mesh_kernel_body<SH, SPILL, FEAT>(sc, pr, image, hits, rngs, stack, sched);
 }
 // The same kernel under another name: the one-sample launch that measures per-wave costs when none are
 // known yet (vpt_capi.hip).  Kept apart so that profiles of vpt_mesh_kernel only hold full launches.
 template <int SH, bool SPILL, int FEAT>
-__global__ void __launch_bounds__(VPT_BLOCK, VPT_WAVES_PER_SIMD) vpt_mesh_pilot_kernel(DScene sc, DParams pr,
+__global__ void vpt_mesh_pilot_kernel(DScene sc, DParams pr,
     float4* __restrict__ image, int* __restrict__ hits, ulonglong2* __restrict__ rngs, stack_cfg stack, sched_cfg sched) {
   mesh_kernel_body<SH, SPILL, FEAT>(sc, pr, image, hits, rngs, stack, sched);
 }

@@ -7,53 +7,6 @@
 #include "vpt_device.h"
 #include "vpt_math.hip.h"
 
-// Diagnostic build (-DVPT_COUNTERS): how often a wave executes each code section and with how many
-// active lanes.  Slot 2k counts wave executions, slot 2k+1 the lanes active in them.  Never in the product build.
-#ifdef VPT_COUNTERS
-__device__ unsigned long long g_vpt_cnt[64];
-VPT_DEV void vpt_cnt(int k) {
-  unsigned long long m = __builtin_amdgcn_ballot_w64(true);
-  if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) {
-    atomicAdd(&g_vpt_cnt[2 * k], 1ull);
-    atomicAdd(&g_vpt_cnt[2 * k + 1], (unsigned long long)__popcll(m));
-  }
-}
-#define VPT_CNT(k) vpt_cnt(k)
-// the same with a caller-made lane mask (group forms: the lanes of the groups that take part, not the lanes switched on)
-VPT_DEV void vpt_cnt_mask(int k, unsigned long long part) {
-  unsigned long long m = __builtin_amdgcn_ballot_w64(true);
-  if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) {
-    atomicAdd(&g_vpt_cnt[2 * k], 1ull);
-    atomicAdd(&g_vpt_cnt[2 * k + 1], (unsigned long long)__popcll(part));
-  }
-}
-#define VPT_CNT_MASK(k, part) vpt_cnt_mask(k, part)
-// histogram of a small count (slots 0 .. 23 of g_vpt_hist): rays in a group-form node step
-__device__ unsigned long long g_vpt_hist[24];
-VPT_DEV void vpt_hist(int n) {
-  unsigned long long m = __builtin_amdgcn_ballot_w64(true);
-  if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(&g_vpt_hist[n < 23 ? n : 23], 1ull);
-}
-#define VPT_HIST(n) vpt_hist(n)
-// wave-level elapsed cycles per section: slot 32 + k of g_vpt_cnt (accumulated in LDS, flushed at kernel end)
-__shared__ unsigned long long s_vpt_time[16];
-VPT_DEV void vpt_time_add(int k, unsigned long long t0) {
-  unsigned long long dt = __builtin_readcyclecounter() - t0;
-  unsigned long long m  = __builtin_amdgcn_ballot_w64(true);
-  if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(&s_vpt_time[k], dt);
-}
-#define VPT_T0(k) unsigned long long vpt_t0_##k = __builtin_readcyclecounter()
-#define VPT_T1(k) vpt_time_add(k, vpt_t0_##k)
-#else
-#define VPT_CNT(k)
-#define VPT_CNT_MASK(k, part)
-#define VPT_HIST(n)
-#define VPT_T0(k)
-#define VPT_T1(k)
-#endif
-enum { TM_NODES = 0, TM_PRIMS, TM_ENTER, TM_QUERY, TM_TRIP, TM_LIGHTS_PDF, TM_SAMPLE_LIGHTS, TM_SURFACE, TM_VOLUME, TM_GENERATE, TM_KERNEL, TM_CDF, TM_SCATTER_EVAL, TM_MEDIUM, TM_SURF_GEOM, TM_SURF_DELTA };
-enum { CNT_NODE = 0, CNT_PRIM, CNT_ENTER, CNT_OUTER, CNT_TRIP, CNT_POP, CNT_MISS, CNT_SURFACE, CNT_VOLUME, CNT_LIGHTS, CNT_GENERATE, CNT_LEAF, CNT_SESSION, CNT_GNODE, CNT_GLEAF, CNT_WNODE };
-
 // ------------------------------------------------------------------------------------------------
 // per-lane traversal stack in LDS: entry e of lane t lives at lds[e * VPT_BLOCK + t], so the 64
 // lanes of a wave touch 64 consecutive dwords (conflict-free ds_read_b32 / ds_write_b32).
@@ -1000,12 +953,9 @@ VPT_DEV f3 sample_phasefunction(float g, f3 outgoing, f2 rn) {
 //    (L > 0: L; L = +0: +0 by IEEE addition).  With a zero half-extent b the argument is the same one step earlier (|x| - b = ±0).
 // Checked bit for bit against the reference's sd_* tables and eval_sdf_scene tables (tests/test_kat.py, tolerance 0).
 // One box distance is 6 + 2 selects and compares less per component: the scene of config 4 evaluates six boxes per march step.
-#ifndef VPT_SD_HW
-#define VPT_SD_HW 1
-#endif
-VPT_DEV float sd_inside(float a, float b, float c) { return VPT_SD_HW ? hw_min(hw_max3(a, b, c), 0.0f) : fmin_(fmax_(a, fmax_(b, c)), 0.0f); }
-VPT_DEV f3 sd_outside(f3 d) { return VPT_SD_HW ? mk3(hw_max(d.x, 0.0f), hw_max(d.y, 0.0f), hw_max(d.z, 0.0f)) : vmaxs(d, 0.0f); }
-VPT_DEV f3 sd_abs(f3 a) { return VPT_SD_HW ? mk3(__builtin_fabsf(a.x), __builtin_fabsf(a.y), __builtin_fabsf(a.z)) : vabs(a); }
+VPT_DEV float sd_inside(float a, float b, float c) { return hw_min(hw_max3(a, b, c), 0.0f); }
+VPT_DEV f3 sd_outside(f3 d) { return mk3(hw_max(d.x, 0.0f), hw_max(d.y, 0.0f), hw_max(d.z, 0.0f)); }
+VPT_DEV f3 sd_abs(f3 a) { return mk3(__builtin_fabsf(a.x), __builtin_fabsf(a.y), __builtin_fabsf(a.z)); }
 VPT_DEV float sd_box(f3 p, f3 b) {
   f3 d = sd_abs(p) - b;
   return sd_inside(d.x, d.y, d.z) + length(sd_outside(d));
@@ -1177,9 +1127,7 @@ VPT_DEV f3 sample_lights(const DScene& sc, f3 position, float rl, float rel, f2 
   float4        r6 = rec[6], r7 = rec[7];
   int           kind = __float_as_int(r7.w) & 255;
   // the one CDF search of this call: emissive mesh -> element, textured environment -> texel
-  VPT_T0(TM_CDF);
   int pick = (kind == VPT_LIGHT_SMALL_MESH || kind == VPT_LIGHT_LARGE_MESH || kind == VPT_LIGHT_ENV_TEX) ? sample_light_cdf(sc, light_id, rel) : 0;
-  VPT_T1(TM_CDF);
   if ((FEAT & VPT_FEAT_SMALL_LIGHTS) && kind == VPT_LIGHT_SMALL_MESH) {
     // eval_position (yocto_scene.cpp:279-303) from the light's own copy of its <= 4 primitives
     const float4* prims = sc.light_prims + 20 * (long long)light_id;
