@@ -393,6 +393,70 @@ int vpt_render_device_adaptive(vpt_scene* scene, const vpt_params* params, const
 int vpt_resolve_hits_device(const vpt_layout* layout, const void* d_tiles_all_ranks, const void* d_hits_all_ranks,
                             void* d_image_rowmajor, void* stream);
 
+/* ---- denoising: an edge-avoiding à-trous wavelet filter guided by first-hit renders ----------------------
+ * The body of the reference's denoise_render(denoised, render, albedo, normal) (yocto_trace.h:176-190), which without
+ * OpenImageDenoise copies its input: here the spatial filter of SVGF (Dammertz et al. 2010, Schied et al. 2017).  It reads
+ * resolved row-major images and writes another; no pathtrace_state is touched.  All images are row-major width x height:
+ *   color     float4, a resolved render (get_render, get_render_hits, vpt_resolve_device, vpt_resolve_hits_device, ...)
+ *   normal    float4, nullable: a resolved render of the `normal` (`implicit_normal`) shader; w is the coverage
+ *   albedo    float4, nullable: a resolved render of the `color` shader
+ *   variance  float,  nullable: an estimate of the variance of each pixel's mean luminance
+ * The rule.  Every value is float32, every operation one of + - * / sqrt abs max, taken in the order written, none fused, and no
+ * libm function: the host mirror (host/vpt_denoise.cpp), a numpy replay (tests/test_denoise_host.py) and the kernels give the
+ * same bits.
+ *   lum(c)   = ((c.x + c.y) + c.z) / 3
+ *   d2(a, b) = (((a.x-b.x)^2 + (a.y-b.y)^2) + (a.z-b.z)^2) + (a.w-b.w)^2
+ *   h[-2..2] = 1/16, 1/4, 3/8, 1/4, 1/16
+ *   box3(f)[p] = (sum of f over the 3x3 taps of p inside the image, dy outer -1..1, dx inner -1..1, starting at 0) / (their
+ *                count, summed as float 1s)
+ *   v_0 = variance if given, else max(0, box3(lum * lum) - box3(lum) * box3(lum)) of color   (the spatial seed)
+ *   c_0 = color
+ *   rn = 1 / (sigma_normal * sigma_normal);  ra = 1 / (sigma_albedo * sigma_albedo)
+ *   pass k = 0 .. iterations-1, stride s = 2^k, for every pixel p:
+ *     r = 1 / (sigma_luminance * sqrt(v_k[p]) + 1e-4)
+ *     taps q = p + s * (dx, dy), dy outer -2..2, dx inner -2..2; a tap outside the image is skipped
+ *       x = abs(lum(c_k[p]) - lum(c_k[q])) * r
+ *       x = x + d2(normal[p], normal[q]) * rn     if normal is given
+ *       x = x + d2(albedo[p], albedo[q]) * ra     if albedo is given
+ *       u = max(1 - x / 4, 0);  w = (h[dy] * h[dx]) * ((u * u) * (u * u))
+ *       W = W + w;  C = C + w * c_k[q] (x, y, z each);  V = V + (w * w) * v_k[q]       (W, C, V start at 0)
+ *     c_{k+1}[p].xyz = C / W;  c_{k+1}[p].w = c_k[p].w;  v_{k+1}[p] = V / (W * W)     (W >= 9/64: the centre tap has x = 0)
+ *   out = c_iterations                                                                 (so out.w == color.w)
+ * (The three quotients of a tap are products with reciprocals taken once per pixel or per call: a pass is bound by arithmetic, not by
+ * memory, and a correctly rounded float32 division costs about ten instructions - DESIGN.md §11 has the times of both.)
+ * ((u*u)*(u*u) stands where a Gaussian filter has exp(-x): it is 0 from x = 4 on, so a tap across an edge of the guides adds
+ * exactly nothing.)  The half variance, from two points of one sample chain - S_a the radiance sums after the first a samples, S_n
+ * after all n, 0 < a < n; samples a+1..n are independent of 1..a, so it costs no extra sample:
+ *   A = S_a / a;  B = (S_n - S_a) / (n - a)   (x, y, z each; a, n - a as float);  g = (lum(A) - lum(B)) / 2;  variance = box3(g * g)
+ * Defaults: iterations 5, sigma_luminance 4, sigma_normal 0.35, sigma_albedo 0.1. */
+typedef struct vpt_denoise_params {
+  int32_t iterations;        /* passes, 1..8; pass k has stride 2^k                         */
+  float   sigma_luminance;   /* each finite and > 0                                         */
+  float   sigma_normal;
+  float   sigma_albedo;
+} vpt_denoise_params;
+#define VPT_DENOISE_DEFAULT_ITERATIONS 5
+#define VPT_DENOISE_DEFAULT_SIGMA_LUMINANCE 4.0f
+#define VPT_DENOISE_DEFAULT_SIGMA_NORMAL 0.35f
+#define VPT_DENOISE_DEFAULT_SIGMA_ALBEDO 0.1f
+/* bytes of the scratch buffer one vpt_denoise_device call needs (two colour and two variance images); -1 for a bad size */
+int64_t vpt_denoise_scratch_bytes(int width, int height);
+/* Device pointers, asynchronous on `stream`: no allocation, read-back or synchronisation inside.  d_out (float4 image) and
+ * d_scratch may alias neither an input nor each other (VPT_ERR_INVALID_ARG); the inputs are left unchanged.  Passes of stride 1
+ * and 2 take their taps from a tile staged in LDS, larger strides from global memory (csrc/vpt_denoise.hip): same bits;
+ * VPT_DENOISE_PLAIN=1 in the environment, read per call, keeps every pass on the global-memory form. */
+int vpt_denoise_device(const vpt_denoise_params* params, int width, int height, const void* d_color, const void* d_normal,
+                       const void* d_albedo, const void* d_variance, void* d_out, void* d_scratch, void* stream);
+/* the half variance above on two row-major float4 sum images, asynchronous on `stream` */
+int vpt_half_variance_device(int width, int height, const void* d_sum_a, int a, const void* d_sum_n, int n, void* d_variance,
+                             void* stream);
+/* The same two on host arrays: synchronous, on GPU `device`, buffers owned by the call.  Arguments are checked before a
+ * device is looked for (VPT_ERR_INVALID_ARG, the message names the argument); then VPT_ERR_NO_DEVICE without a GPU or for a
+ * negative `device`. */
+int vpt_denoise(const vpt_denoise_params* params, int device, int width, int height, const float* color, const float* normal,
+                const float* albedo, const float* variance, float* out);
+int vpt_half_variance(int device, int width, int height, const float* sum_a, int a, const float* sum_n, int n, float* variance);
+
 /* per-launch profile of the last vpt_render_device on this scene (HIP events on `stream`); synchronises with that
  * launch.  Like vpt_render it returns VPT_ERR_HIP if a wave of the implicit kernel gave up on its watchdog (a wave
  * that has not finished after 300 s leaves the kernel instead of holding the GPU: a defect, never a workload). */

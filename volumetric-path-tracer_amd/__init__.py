@@ -53,6 +53,14 @@ class VptAdaptive(C.Structure):  # vpt_adaptive
     _fields_ = [("threshold", C.c_float), ("min_samples", C.c_int32), ("step", C.c_int32)]
 
 
+class VptDenoise(C.Structure):  # vpt_denoise_params
+    _fields_ = [("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float)]
+
+
+# defaults of the denoising filter (include/vpt.h: VPT_DENOISE_DEFAULT_*)
+DENOISE_ITERATIONS, DENOISE_SIGMA_LUMINANCE, DENOISE_SIGMA_NORMAL, DENOISE_SIGMA_ALBEDO = 5, 4.0, 0.35, 0.1
+
+
 @dataclass
 class PathtraceParams:
     """pathtrace_params, yocto_pathtrace.h:87-99 (same names, same defaults)."""
@@ -109,6 +117,12 @@ hip.vpt_render_adaptive.argtypes = [_p, C.POINTER(VptParams), C.POINTER(VptAdapt
 hip.vpt_render_device_adaptive.argtypes = [_p, C.POINTER(VptParams), C.POINTER(VptAdaptive), C.POINTER(VptLayout), _p, _p, _p, _p,
                                            C.POINTER(C.c_int), C.POINTER(C.c_int64)]
 hip.vpt_resolve_hits_device.argtypes = [C.POINTER(VptLayout), _p, _p, _p, _p]
+hip.vpt_denoise_scratch_bytes.argtypes = [C.c_int, C.c_int]
+hip.vpt_denoise_scratch_bytes.restype = C.c_int64
+hip.vpt_denoise_device.argtypes = [C.POINTER(VptDenoise), C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p]
+hip.vpt_half_variance_device.argtypes = [C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p, _p]
+hip.vpt_denoise.argtypes = [C.POINTER(VptDenoise), C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p]
+hip.vpt_half_variance.argtypes = [C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
 hip.vpt_last_kernel_ms.argtypes = [_p, C.POINTER(C.c_float)]
 hip.vpt_intersect.argtypes = [_p, C.c_int, _p, C.c_int, _p, _p]
 hip.vpt_build_bvh.argtypes = [C.c_int, _p, C.c_int, _p, C.c_int, C.POINTER(C.c_int), _p]
@@ -152,6 +166,8 @@ host.vpth_make_state.argtypes = [_p, C.c_int, C.c_int, _p, _p, _p]
 host.vpth_scene_stats.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_rebuild_bvh_device.argtypes = [_p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_build_bvh_host.argtypes = [_p, C.c_int, _p, C.POINTER(C.c_int), _p]
+host.vpth_denoise.argtypes = [C.c_int, C.c_int, _p, _p, _p, _p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _p, C.c_char_p, C.c_int]
+host.vpth_half_variance.argtypes = [C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_char_p, C.c_int]
 host.vpth_linear_to_srgb8.argtypes = [C.c_int, C.c_int, _p, C.c_int, _p]
 host.vpth_linear_to_srgb8.restype = None
 host.vpth_encode_jpeg_q75.argtypes = [C.c_int, C.c_int, _p, _p, C.c_int64]
@@ -502,6 +518,90 @@ def get_render_hits(state: PathtraceState) -> np.ndarray:
     with np.errstate(divide="ignore"):
         scale = np.where(state.hits > 0, np.float32(1.0) / hits, np.float32(0.0)).astype(np.float32)
     return np.where((state.hits > 0)[..., None], state.image * scale[..., None], np.float32(0.0)).astype(np.float32)
+
+
+def _image4(a, shape=None) -> np.ndarray:
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 3 or a.shape[2] != 4 or (shape is not None and a.shape != shape):
+        raise VptError(f"expected a (height, width, 4) float32 image{'' if shape is None else ' of shape ' + str(shape)}, got {a.shape}")
+    return a
+
+
+def denoise_render(render: np.ndarray, albedo: Optional[np.ndarray] = None, normal: Optional[np.ndarray] = None,
+                   variance: Optional[np.ndarray] = None, *, iterations: int = DENOISE_ITERATIONS,
+                   sigma_luminance: float = DENOISE_SIGMA_LUMINANCE, sigma_normal: float = DENOISE_SIGMA_NORMAL,
+                   sigma_albedo: float = DENOISE_SIGMA_ALBEDO, device: Optional[int] = None) -> np.ndarray:
+    """denoise_render (include/vpt.h: the rule of vpt_denoise_params): the guided à-trous filter over an (h, w, 4) float32 resolved
+    render.  albedo / normal: resolved renders of the `color` / `normal` (`implicit_normal`) shaders; variance: (h, w) float32 estimate
+    of the variance of each pixel's mean luminance (None: the spatial seed).  device None: the host C++ mirror; else that GPU
+    (vpt_denoise) - same bits.  The inputs are left unchanged; out[..., 3] == render[..., 3]."""
+    render = _image4(render)
+    h, w, _ = render.shape
+    albedo = None if albedo is None else _image4(albedo, render.shape)
+    normal = None if normal is None else _image4(normal, render.shape)
+    if variance is not None:
+        variance = np.ascontiguousarray(variance, np.float32)
+        if variance.shape != (h, w):
+            raise VptError(f"expected a variance of shape {(h, w)}, got {variance.shape}")
+    out = np.zeros_like(render)
+    err = C.create_string_buffer(512)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    if host.vpth_denoise(w, h, render.ctypes.data, ptr(normal), ptr(albedo), ptr(variance), iterations, sigma_luminance, sigma_normal,
+                         sigma_albedo, -1 if device is None else device, out.ctypes.data, err, len(err)) != 0:
+        raise VptError(err.value.decode())
+    return out
+
+
+def half_variance(sum_a: np.ndarray, a: int, sum_n: np.ndarray, n: int, device: Optional[int] = None) -> np.ndarray:
+    """the variance of each pixel's mean luminance from the radiance sums (PathtraceState.image) after the first `a` samples and
+    after all `n` of one chain, 0 < a < n (include/vpt.h): (h, w) float32.  device None: host loops; else that GPU - same bits."""
+    sum_a = _image4(sum_a)
+    sum_n = _image4(sum_n, sum_a.shape)
+    h, w, _ = sum_a.shape
+    out = np.zeros((h, w), np.float32)
+    err = C.create_string_buffer(512)
+    if host.vpth_half_variance(w, h, sum_a.ctypes.data, a, sum_n.ctypes.data, n, -1 if device is None else device, out.ctypes.data,
+                               err, len(err)) != 0:
+        raise VptError(err.value.decode())
+    return out
+
+
+def pathtrace_guides(scene: HostScene, dev, params: PathtraceParams, samples: int = 16):
+    """the two guide renders of denoise_render on `dev` (a DeviceScene or MultiDeviceScene of `scene`): (normal, albedo) as resolved
+    (h, w, 4) float32 images - `samples` passes of the `normal` and the `color` shader over a fresh make_state; for the implicit
+    shaders: `implicit_normal`, and albedo None"""
+    implicit = params.shader in ("implicit", "implicit_normal")
+
+    def render(shader):
+        p = PathtraceParams(params.camera, params.resolution, shader, samples, params.bounces, params.noparallel, params.noimplicit_mis,
+                            params.spheretrace_maxiter)
+        st = scene.make_state(p)
+        dev.pathtrace_samples(st, p, samples)
+        return get_render(st)
+
+    return render("implicit_normal" if implicit else "normal"), None if implicit else render("color")
+
+
+def denoise_scratch_bytes(width: int, height: int) -> int:
+    n = hip.vpt_denoise_scratch_bytes(width, height)
+    if n < 0:
+        raise VptError(hip.vpt_last_error().decode())
+    return n
+
+
+def denoise_device(width: int, height: int, d_color: int, d_normal: Optional[int], d_albedo: Optional[int], d_variance: Optional[int],
+                   d_out: int, d_scratch: int, *, iterations: int = DENOISE_ITERATIONS, sigma_luminance: float = DENOISE_SIGMA_LUMINANCE,
+                   sigma_normal: float = DENOISE_SIGMA_NORMAL, sigma_albedo: float = DENOISE_SIGMA_ALBEDO, stream: int = 0) -> None:
+    """vpt_denoise_device over raw device pointers (row-major float4 images, float variance; None: not given), asynchronous on
+    `stream`; d_scratch holds denoise_scratch_bytes(width, height) bytes"""
+    par = VptDenoise(iterations, sigma_luminance, sigma_normal, sigma_albedo)
+    _check(hip.vpt_denoise_device(C.byref(par), width, height, d_color, d_normal, d_albedo, d_variance, d_out, d_scratch, stream),
+           "vpt_denoise_device")
+
+
+def half_variance_device(width: int, height: int, d_sum_a: int, a: int, d_sum_n: int, n: int, d_variance: int, stream: int = 0) -> None:
+    """vpt_half_variance_device over raw device pointers (row-major float4 sums in, float variance out), asynchronous on `stream`"""
+    _check(hip.vpt_half_variance_device(width, height, d_sum_a, a, d_sum_n, n, d_variance, stream), "vpt_half_variance_device")
 
 
 def selftest_reciprocal(device: int = 0):

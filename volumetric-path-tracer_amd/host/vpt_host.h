@@ -242,6 +242,32 @@ pathtrace_adaptive_stats pathtrace_adaptive(pathtrace_state& state, const scene_
 // get_render with each pixel's own sample count: image[p] * (1 / hits[p]), 0 where hits[p] == 0
 color_image get_render_hits(const pathtrace_state& state);
 void        get_render_hits(color_image& render, const pathtrace_state& state);
+// Extension: denoise_render, which the reference declares beside get_albedo / get_normal and, without OpenImageDenoise, fills with a
+// copy (yocto_trace.h:176-190, yocto_trace.cpp:1602-1604).  Here: the edge-avoiding à-trous filter whose rule include/vpt.h states
+// word for word (vpt_denoise_params), on the CPU - the restatement the HIP kernels are held to bit for bit, usable without a GPU.
+// `albedo` / `normal` are resolved renders of the `color` / `normal` (`implicit_normal`) shaders, `variance` an estimate of the variance of
+// each pixel's mean luminance; an empty image / vector means "not given" (no variance: the spatial seed).  denoised.w == render.w.
+struct denoise_params {
+  int   iterations      = VPT_DENOISE_DEFAULT_ITERATIONS;
+  float sigma_luminance = VPT_DENOISE_DEFAULT_SIGMA_LUMINANCE;
+  float sigma_normal    = VPT_DENOISE_DEFAULT_SIGMA_NORMAL;
+  float sigma_albedo    = VPT_DENOISE_DEFAULT_SIGMA_ALBEDO;
+};
+void denoise_render(color_image& denoised, const color_image& render, const color_image& albedo, const color_image& normal,
+    const vector<float>& variance = {}, const denoise_params& params = {});
+// the same on GPU `device` (vpt_denoise): same bits; throws std::runtime_error with vpt_last_error() if that fails
+void denoise_render_device(color_image& denoised, const color_image& render, const color_image& albedo, const color_image& normal,
+    const vector<float>& variance = {}, const denoise_params& params = {}, int device = 0);
+// The variance of each pixel's mean luminance from two points of one sample chain: the radiance sums (pathtrace_state::image) after
+// the first a samples and after all n, 0 < a < n (rule: include/vpt.h).  device < 0: host loops; else GPU `device`: same bits.
+vector<float> half_variance(int width, int height, const vector<vec4f>& sum_a, int a, const vector<vec4f>& sum_n, int n, int device = -1);
+// The two guide renders of `params`' camera and resolution: a fresh make_state, `samples` passes of the `normal` and the `color` shader
+// through pathtrace_samples, get_render.  For the implicit shaders: `implicit_normal`, and no albedo (left empty).
+struct denoise_guides {
+  color_image normal = {}, albedo = {};
+};
+denoise_guides pathtrace_guides(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights, const pathtrace_params& params,
+    int samples = 16);
 
 // ---- flattening to the C-ABI ----------------------------------------------------------------
 struct flat_scene {

@@ -239,6 +239,41 @@ void vpth_linear_to_srgb8(int width, int height, const float* image_sum, int sam
   auto ldr = linear_to_srgb8(img);
   memcpy(rgba8, ldr.data(), ldr.size() * 4);
 }
+// denoise_render on row-major float4 images (normal / albedo / variance nullable): the host mirror (device < 0) or vpt_denoise on that GPU
+int vpth_denoise(int width, int height, const float* color, const float* normal, const float* albedo, const float* variance, int iterations,
+    float sigma_luminance, float sigma_normal, float sigma_albedo, int device, float* out, char* err, int errlen) {
+  try {
+    if (width < 1 || height < 1 || !color || !out) throw std::invalid_argument{"bad image"};
+    auto n     = (size_t)width * height;
+    auto image = [&](const float* p) {
+      auto img = color_image{p ? width : 0, p ? height : 0, true, {}};
+      if (p) img.pixels.assign((const vec4f*)p, (const vec4f*)p + n);
+      return img;
+    };
+    auto var = variance ? vector<float>(variance, variance + n) : vector<float>{};
+    auto res = color_image{};
+    auto par = denoise_params{iterations, sigma_luminance, sigma_normal, sigma_albedo};
+    if (device < 0) denoise_render(res, image(color), image(albedo), image(normal), var, par);
+    else denoise_render_device(res, image(color), image(albedo), image(normal), var, par, device);
+    memcpy(out, res.pixels.data(), n * 16);
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
+}
+// half_variance on two row-major float4 sum images: host loops (device < 0) or vpt_half_variance on that GPU
+int vpth_half_variance(int width, int height, const float* sum_a, int a, const float* sum_n, int n, int device, float* variance, char* err, int errlen) {
+  try {
+    if (width < 1 || height < 1 || !sum_a || !sum_n || !variance) throw std::invalid_argument{"bad image"};
+    auto px  = (size_t)width * height;
+    auto out = half_variance(width, height, vector<vec4f>((const vec4f*)sum_a, (const vec4f*)sum_a + px), a,
+        vector<vec4f>((const vec4f*)sum_n, (const vec4f*)sum_n + px), n, device);
+    memcpy(variance, out.data(), px * 4);
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
+}
 // returns the encoded size; call with out == nullptr to query
 int64_t vpth_encode_jpeg_q75(int width, int height, const uint8_t* rgba8, uint8_t* out, int64_t outlen) {
   auto px = vector<vec4b>((size_t)width * height);

@@ -9,7 +9,9 @@
 // (the BVHs built on the GPU by vpt_build_bvh: the same trees), --gputess (the float32 half of tesselate_surfaces on the GPU by
 // vpt_subdivide_vertices: the same meshes), --adaptive t (adaptive sampling, vpt_render_adaptive: every pixel renders in rounds of
 // --adaptivestep samples until the relative standard error of its mean is within t, never below --adaptivemin samples, at most --samples;
-// the image is written from each pixel's own sample count).
+// the image is written from each pixel's own sample count), --denoise (denoise_render: the guided à-trous filter of include/vpt.h over
+// the finished render, on GPU 0; its guides are --denoiseguides samples of the `normal` and `color` shaders, its variance comes from the two
+// halves of the sample chain, or from the image itself after --adaptive; --denoiseiters and --denoisesigma* set its parameters).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -25,7 +27,7 @@ using namespace vpt;
 namespace {
 
 struct option {
-  enum kind_t { string_k, int_k, bool_k, shader_k, float_k } kind;   // float_k: finite and >= 0
+  enum kind_t { string_k, int_k, bool_k, shader_k, float_k, posfloat_k } kind;   // float_k: finite and >= 0; posfloat_k: finite and > 0
   int         lo, hi;   // int_k: inclusive range (lo > hi: unbounded)
   const char* usage;
 };
@@ -48,6 +50,12 @@ const std::vector<std::pair<string, option>> options = {
     {"adaptive", {option::float_k, 1, 0, "Adaptive sampling: relative noise at which a pixel stops, 0 = off. (extension)"}},
     {"adaptivemin", {option::int_k, 1, 4096, "Adaptive sampling: fewest samples before a pixel stops. (extension)"}},
     {"adaptivestep", {option::int_k, 1, 4096, "Adaptive sampling: samples per round. (extension)"}},
+    {"denoise", {option::bool_k, 1, 0, "Denoise the render with the guided a-trous filter. (extension)"}},
+    {"denoiseiters", {option::int_k, 1, 8, "Denoising: filter passes, pass k has stride 2^k. (extension)"}},
+    {"denoiseguides", {option::int_k, 1, 4096, "Denoising: samples of the normal and albedo guides. (extension)"}},
+    {"denoisesigmalum", {option::posfloat_k, 1, 0, "Denoising: luminance tolerance in standard deviations. (extension)"}},
+    {"denoisesigmanormal", {option::posfloat_k, 1, 0, "Denoising: tolerance of the normal guide. (extension)"}},
+    {"denoisesigmaalbedo", {option::posfloat_k, 1, 0, "Denoising: tolerance of the albedo guide. (extension)"}},
 };
 const option* find_option(const string& name) {
   for (auto& [n, o] : options)
@@ -60,7 +68,7 @@ string usage() {
   for (auto& [name, o] : options) {
     auto line = "  --" + name + (o.kind == option::bool_k  ? "/--no-" + name
                                  : o.kind == option::int_k ? " <integer>"
-                                 : o.kind == option::float_k ? " <float>"
+                                 : o.kind == option::float_k || o.kind == option::posfloat_k ? " <float>"
                                                              : " <string>");
     line.resize(line.size() < 32 ? 32 : line.size() + 1, ' ');
     text += line + o.usage + "\n";
@@ -93,6 +101,10 @@ void check_value(const string& name, const option& o, const string& text) {
     auto end = (char*)nullptr;
     auto v   = strtof(text.c_str(), &end);
     if (end == text.c_str() || *end != 0 || !std::isfinite(v) || v < 0) cli_error("bad value for " + name);
+  } else if (o.kind == option::posfloat_k) {
+    auto end = (char*)nullptr;
+    auto v   = strtof(text.c_str(), &end);
+    if (end == text.c_str() || *end != 0 || !std::isfinite(v) || !(v > 0)) cli_error("bad value for " + name);
   } else if (o.kind == option::bool_k) {
     if (text != "true" && text != "false") cli_error("bad value for " + name);
   } else if (o.kind == option::shader_k) {
@@ -164,8 +176,16 @@ int main(int argc, const char** argv) {
   get_int("adaptivemin", adaptive.min_samples), get_int("adaptivestep", adaptive.step);
   if (adaptive.min_samples > params.samples) cli_error("bad value for adaptivemin");
   if (adaptive.threshold > 0 && gpus > 1) print_fatal("--adaptive renders on one GPU: it cannot be combined with --gpus " + std::to_string(gpus));
-  auto interactive = false, gpubvh = false, gputess = false;
-  get_bool("interactive", interactive), get_bool("gpubvh", gpubvh), get_bool("gputess", gputess);
+  auto interactive = false, gpubvh = false, gputess = false, denoise = false;
+  get_bool("interactive", interactive), get_bool("gpubvh", gpubvh), get_bool("gputess", gputess), get_bool("denoise", denoise);
+  auto filter = denoise_params{};
+  auto guide_samples = 16;
+  get_int("denoiseiters", filter.iterations), get_int("denoiseguides", guide_samples);
+  auto get_float = [&](const char* name, float& v) {
+    if (values.count(name)) v = strtof(values[name].c_str(), nullptr);
+  };
+  get_float("denoisesigmalum", filter.sigma_luminance), get_float("denoisesigmanormal", filter.sigma_normal);
+  get_float("denoisesigmaalbedo", filter.sigma_albedo);
   if (interactive) print_fatal("--interactive is not supported by the GPU build");
   if (values.count("shader"))
     for (size_t k = 0; k < pathtrace_shader_names.size(); k++)
@@ -186,6 +206,18 @@ int main(int argc, const char** argv) {
       for (auto d = 0; d < gpus; d++) devices.push_back(d);
       pathtrace_set_devices(devices);
     }
+    // --denoise: guides, filter on GPU 0, save; the line it prints follows the render's own
+    auto denoise_and_save = [&](const color_image& render, const vector<float>& variance) {
+      auto t1     = std::chrono::steady_clock::now();
+      auto guides = pathtrace_guides(scene, bvh, lights, params, guide_samples);
+      auto t2     = std::chrono::steady_clock::now();
+      auto clean  = color_image{};
+      denoise_render_device(clean, render, guides.albedo, guides.normal, variance, filter, 0);
+      auto t3 = std::chrono::steady_clock::now();
+      printf("denoised: guides %d spp in %.3f s, filter %d passes (%s variance) in %.3f s\n", guide_samples,
+          std::chrono::duration<double>(t2 - t1).count(), filter.iterations, variance.empty() ? "spatial" : "half", std::chrono::duration<double>(t3 - t2).count());
+      if (!save_image(output, clean, error)) print_fatal(error);
+    };
     auto t0 = std::chrono::steady_clock::now();
     if (adaptive.threshold > 0) {   // rounds of --adaptivestep samples until every pixel is clean enough or at --samples
       auto stats = pathtrace_adaptive(state, scene, bvh, lights, params, adaptive);
@@ -193,16 +225,25 @@ int main(int argc, const char** argv) {
       auto full  = (double)state.width * state.height * params.samples;
       printf("adaptive: %d rounds, %lld samples taken of %.0f (%.1f %%) in %.3f s (%.2f Msamples/s)\n", stats.rounds, (long long)stats.samples,
           full, 100.0 * (double)stats.samples / full, secs, (double)stats.samples / secs * 1e-6);
-      if (!save_image(output, get_render_hits(state), error)) print_fatal(error);
+      if (denoise) denoise_and_save(get_render_hits(state), {});   // pixels hold their own sample counts: the spatial seed
+      else if (!save_image(output, get_render_hits(state), error)) print_fatal(error);
       return 0;
     }
     // one launch per `batch` samples (default: all); identical to that many single calls
     if (batch <= 0) batch = params.samples;
+    // --denoise stops once at half the samples to keep the radiance sums for the half variance (same final state: batching is exact)
+    auto half = denoise ? params.samples / 2 : 0;
+    auto sum_half = vector<vec4f>{};
+    while (state.samples < half) pathtrace_samples(state, scene, bvh, lights, params, std::min(batch, half - state.samples));
+    if (half > 0) sum_half = state.image;
     while (state.samples < params.samples) pathtrace_samples(state, scene, bvh, lights, params, batch);
     auto secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     printf("rendered %dx%d x %d spp in %.3f s (%.2f Msamples/s)\n", state.width, state.height, state.samples, secs,
         (double)state.width * state.height * state.samples / secs * 1e-6);
-    if (!save_image(output, get_render(state), error)) print_fatal(error);
+    if (denoise) {
+      auto variance = half > 0 ? half_variance(state.width, state.height, sum_half, half, state.image, state.samples, 0) : vector<float>{};
+      denoise_and_save(get_render(state), variance);
+    } else if (!save_image(output, get_render(state), error)) print_fatal(error);
   } catch (const std::exception& e) {
     print_fatal(e.what());
   }
