@@ -274,6 +274,56 @@ int  vpt_scene_create(const vpt_scene_desc* desc, int device, vpt_scene** out);
 int  vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* curves, int device, vpt_scene** out);
 void vpt_scene_destroy(vpt_scene* scene);
 
+/* ---- editing a resident scene: cameras, frames, materials, vertices; BVHs refitted on the device -----------
+ * The counterpart of the reference's update_bvh(bvh, scene, updated_instances, updated_shapes) (yocto_bvh.h:100-103,
+ * yocto_bvh.cpp:509-524, 613-689) for a scene that lives on a GPU.  Topology, node ids, primitive order, leaf slots and every
+ * count stay as they were at creation; boxes, records and frames are recomputed.  After vpt_scene_update(s, edit) every table on
+ * the device holds the bytes vpt_scene_create would upload for the edited descriptor carrying the refitted BVH arrays, so every
+ * render, vpt_intersect and vpt_kat call gives the bits of a fresh handle made from that descriptor.
+ *  - Order of a refit = the reference's: edited shapes first, then the scene BVH from ALL instances (yocto_bvh.cpp:680-689:
+ *    `updated_instances` is ignored by its non-Embree path and the scene BVH is refitted on every call); done here whenever the
+ *    edit names an instance or a shape.
+ *  - Boxes: leaf node = invalidb3f merged with its primitives' bounds in slot order; internal node = invalidb3f merged with
+ *    child `start`, then `start + 1` (yocto_bvh.cpp:510-524).  Primitive bounds are triangle_bounds / quad_bounds /
+ *    point_bounds(p, r) / line_bounds(p0, p1, r0, r1) (yocto_geometry.h:461-479), instance bounds transform_bbox(frame, shape
+ *    root box) over the eight corners in the reference's order (yocto_geometry.h:441-451; transform_point with its own operation
+ *    order, no contraction).  min / max are the reference's select forms ((a < b) ? a : b), applied in that order: with signed
+ *    zeros the order decides the bits, so fminf / fmaxf or a reduction in another order are not equivalent.  An instance of a shape
+ *    without BVH nodes gets invalidb3f, as in make_bvh (yocto_bvh.cpp:601-603; the reference's refit reads nodes[0] of an empty
+ *    vector there).
+ *  - Validation before anything is written: ids in range and not repeated within one list, every float of the edit finite,
+ *    material types and texture ids under the rules of vpt_scene_create.  A refused edit leaves the scene exactly as it was
+ *    (VPT_ERR_INVALID_ARG; the message names the entry).  A failure of the device after validation (VPT_ERR_HIP) is another matter:
+ *    the tables may be half written and the handle is good for vpt_scene_destroy only.
+ *  - What an edit may not do (VPT_ERR_UNSUPPORTED, scene unchanged): turn a material's emission from zero to non-zero or back
+ *    (the light list and the kernel instances are fixed at creation); move the vertices of a shape that a light's instance uses
+ *    (its element CDF is the caller's light_cdf, made from areas); change counts, indices, radii, textures, volumes or SDFs (the
+ *    edit has no field for them).  Moving an emissive INSTANCE is allowed (the CDF is over shape-local areas).
+ *  - Synchronisation: the call waits for the device's outstanding work (it rewrites tables launches read) and has completed when
+ *    it returns.  It touches no pathtrace_state: restarting accumulation is the caller's business, as in the reference's
+ *    reset_display.  It forgets the handle's launch-schedule record and tile-splitting decision (the camera index may be the
+ *    same, the picture is not); results never depended on that record.
+ *  - The traversal limits decided at creation (stack sizes) depend on topology only and stay valid. */
+typedef struct vpt_scene_edit {
+  int32_t num_cameras;      const int32_t* camera_ids;      const vpt_camera*   cameras;
+  int32_t num_instances;    const int32_t* instance_ids;    const vpt_frame*    instance_frames;
+  int32_t num_environments; const int32_t* environment_ids; const vpt_frame*    environment_frames;
+  int32_t num_materials;    const int32_t* material_ids;    const vpt_material* materials;
+  int32_t num_shapes;       const int32_t* shape_ids;       /* shapes whose vertices move                                  */
+  const float* const* shape_positions;   /* per entry: that shape's num_vertices float3                                    */
+  const float* const* shape_normals;     /* per entry: num_vertices float3 or NULL (keep); the array itself may be NULL    */
+} vpt_scene_edit;
+int vpt_scene_update(vpt_scene* scene, const vpt_scene_edit* edit);
+/* The BVHs as the device holds them now, in the reference's layout (the descriptor's scene_bvh_nodes / shape_bvh_nodes): for
+ * callers that keep a host copy, and for the tests.  *_capacity in nodes, at least the descriptor's counts; a null array is skipped. */
+int vpt_scene_get_bvh(vpt_scene* scene, vpt_bvh_node* scene_nodes, int scene_capacity, vpt_bvh_node* shape_nodes, int64_t shape_capacity);
+/* What the last vpt_scene_update on this handle cost (measurements, tests): kernel launches, bytes of payload sent to the device, and
+ * the time between two events on the device's null stream, one recorded before the first and one after the last launch of the refit -
+ * the payload is on the device before the first, so the span holds launches only (0 for an edit of cameras, materials and environments:
+ * it launches nothing).  VPT_UPDATE_NO_FUSE=1 in the environment, read per call, runs the refit with one launch per level throughout
+ * instead of finishing the narrow top levels of a tree in one launch: same bits (the tests' and the measurements' A/B switch). */
+int vpt_scene_update_stats(const vpt_scene* scene, int* launches, int64_t* bytes, float* device_ms);
+
 /* ---- the drop-in for pathtrace_samples() --------------------------------------------
  * Host, row-major (idx = j*width + i) caller-owned state, exactly pathtrace_state
  * (yocto_pathtrace.h:57-64): image float4[w*h], hits int32[w*h], rng {u64 state, u64 inc}[w*h].
@@ -310,6 +360,9 @@ typedef struct vpt_multi vpt_multi;
 int  vpt_multi_create(const vpt_scene_desc* desc, const int* devices, int ndev, vpt_multi** out);
 int  vpt_multi_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* curves, const int* devices, int ndev, vpt_multi** out);
 void vpt_multi_destroy(vpt_multi* m);
+/* vpt_scene_update with the same edit on every device of `m`, one after the other; an edit the first device refuses has changed
+ * none.  The resident tile state is left as it is. */
+int  vpt_multi_update(vpt_multi* m, const vpt_scene_edit* edit);
 int  vpt_multi_device_count(const vpt_multi* m);
 /* how vpt_multi_get_render moves the parts: "rccl", "peer-copy" (several devices, no RCCL) or "local" (one device) */
 const char* vpt_multi_transport(const vpt_multi* m);

@@ -57,6 +57,95 @@ class VptDenoise(C.Structure):  # vpt_denoise_params
     _fields_ = [("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float)]
 
 
+class VptFrame(C.Structure):  # vpt_frame: x, y, z, o
+    _fields_ = [("x", C.c_float * 3), ("y", C.c_float * 3), ("z", C.c_float * 3), ("o", C.c_float * 3)]
+
+
+class VptCamera(C.Structure):  # vpt_camera
+    _fields_ = [("frame", VptFrame), ("orthographic", C.c_int32), ("lens", C.c_float), ("film", C.c_float), ("aspect", C.c_float),
+                ("focus", C.c_float), ("aperture", C.c_float)]
+
+
+class VptMaterial(C.Structure):  # vpt_material
+    _fields_ = [("type", C.c_int32), ("emission", C.c_float * 3), ("color", C.c_float * 3), ("roughness", C.c_float),
+                ("metallic", C.c_float), ("ior", C.c_float), ("scattering", C.c_float * 3), ("scanisotropy", C.c_float),
+                ("trdepth", C.c_float), ("opacity", C.c_float), ("emission_tex", C.c_int32), ("color_tex", C.c_int32),
+                ("roughness_tex", C.c_int32), ("scattering_tex", C.c_int32), ("normal_tex", C.c_int32)]
+
+
+class VptSceneEdit(C.Structure):  # vpt_scene_edit
+    _fields_ = [("num_cameras", C.c_int32), ("camera_ids", C.c_void_p), ("cameras", C.c_void_p),
+                ("num_instances", C.c_int32), ("instance_ids", C.c_void_p), ("instance_frames", C.c_void_p),
+                ("num_environments", C.c_int32), ("environment_ids", C.c_void_p), ("environment_frames", C.c_void_p),
+                ("num_materials", C.c_int32), ("material_ids", C.c_void_p), ("materials", C.c_void_p),
+                ("num_shapes", C.c_int32), ("shape_ids", C.c_void_p), ("shape_positions", C.c_void_p), ("shape_normals", C.c_void_p)]
+
+
+MATERIAL_TYPES = ["matte", "glossy", "reflective", "transparent", "refractive", "subsurface", "volumetric", "gltfpbr"]
+
+
+class SceneEdit:
+    """What vpt_scene_update takes (include/vpt.h: vpt_scene_edit), as dictionaries id -> value: cameras (VptCamera), instances and
+    environments ((12,) float32 frames x, y, z, o), materials (VptMaterial), shapes ((positions, normals or None) as (n, 3) float32).
+    HostScene's setters fill one; DeviceScene.update / MultiDeviceScene.update apply it."""
+
+    def __init__(self, cameras=None, instances=None, environments=None, materials=None, shapes=None):
+        self.cameras, self.instances, self.environments = dict(cameras or {}), dict(instances or {}), dict(environments or {})
+        self.materials, self.shapes = dict(materials or {}), dict(shapes or {})
+
+    def empty(self) -> bool:
+        return not (self.cameras or self.instances or self.environments or self.materials or self.shapes)
+
+    def merge(self, other: "SceneEdit") -> "SceneEdit":
+        """this edit followed by `other` (later values win)"""
+        out = SceneEdit(self.cameras, self.instances, self.environments, self.materials, self.shapes)
+        for name in ("cameras", "instances", "environments", "materials"):
+            getattr(out, name).update(getattr(other, name))
+        for k, (pos, nrm) in other.shapes.items():
+            out.shapes[k] = (pos, nrm if nrm is not None or k not in out.shapes else out.shapes[k][1])
+        return out
+
+    def to_abi(self):
+        """(VptSceneEdit, objects that keep its arrays alive)"""
+        keep, abi = [], VptSceneEdit()
+
+        def ids(d):
+            a = np.array(list(d.keys()), np.int32)
+            keep.append(a)
+            return a.ctypes.data
+
+        def structs(d, T):
+            a = (T * max(1, len(d)))(*d.values())
+            keep.append(a)
+            return C.cast(a, C.c_void_p).value
+
+        def frames(d):
+            a = np.ascontiguousarray(np.array([np.asarray(f, np.float32).reshape(12) for f in d.values()], np.float32).reshape(-1, 12))
+            keep.append(a)
+            return a.ctypes.data
+
+        abi.num_cameras, abi.camera_ids, abi.cameras = len(self.cameras), ids(self.cameras), structs(self.cameras, VptCamera)
+        abi.num_instances, abi.instance_ids, abi.instance_frames = len(self.instances), ids(self.instances), frames(self.instances)
+        abi.num_environments, abi.environment_ids, abi.environment_frames = len(self.environments), ids(self.environments), frames(self.environments)
+        abi.num_materials, abi.material_ids, abi.materials = len(self.materials), ids(self.materials), structs(self.materials, VptMaterial)
+        n = len(self.shapes)
+        pos, nrm = (C.c_void_p * max(1, n))(), (C.c_void_p * max(1, n))()
+        for i, (p, q) in enumerate(self.shapes.values()):
+            p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+            keep.append(p)
+            pos[i] = p.ctypes.data
+            if q is not None:
+                q = np.ascontiguousarray(q, np.float32).reshape(-1, 3)
+                if q.shape != p.shape:
+                    raise VptError("normals of a shape edit must match its positions")
+                keep.append(q)
+                nrm[i] = q.ctypes.data
+        keep += [pos, nrm]
+        abi.num_shapes, abi.shape_ids = n, ids(self.shapes)
+        abi.shape_positions, abi.shape_normals = C.cast(pos, C.c_void_p).value, C.cast(nrm, C.c_void_p).value
+        return abi, keep
+
+
 # defaults of the denoising filter (include/vpt.h: VPT_DENOISE_DEFAULT_*; DESIGN.md §11)
 DENOISE_ITERATIONS, DENOISE_SIGMA_LUMINANCE, DENOISE_SIGMA_NORMAL, DENOISE_SIGMA_ALBEDO = 5, 4.0, 0.35, 0.1
 
@@ -105,6 +194,10 @@ hip.vpt_scene_create.argtypes = [_p, C.c_int, C.POINTER(_p)]
 hip.vpt_scene_create_curves.argtypes = [_p, _p, C.c_int, C.POINTER(_p)]
 hip.vpt_scene_destroy.argtypes = [_p]
 hip.vpt_scene_destroy.restype = None
+hip.vpt_scene_update.argtypes = [_p, C.POINTER(VptSceneEdit)]
+hip.vpt_multi_update.argtypes = [_p, C.POINTER(VptSceneEdit)]
+hip.vpt_scene_get_bvh.argtypes = [_p, _p, C.c_int, _p, C.c_int64]
+hip.vpt_scene_update_stats.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
 hip.vpt_render.argtypes = [_p, C.POINTER(VptParams), C.c_int, C.c_int, C.c_int, _p, _p, _p, C.POINTER(C.c_int)]
 hip.vpt_layout_slots.argtypes = [C.POINTER(VptLayout)]
 hip.vpt_layout_slots.restype = C.c_int64
@@ -156,6 +249,11 @@ host.vpth_vertex_normals.argtypes = [_p, C.c_int, _p, C.c_int, C.c_int, C.c_int,
 host.vpth_displace_vertices.argtypes = [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, C.c_int, C.c_int, _p, C.c_char_p, C.c_int]
 host.vpth_catmullclark.argtypes = [_p, C.c_int, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.POINTER(C.c_int), _p, C.POINTER(C.c_int), C.c_char_p, C.c_int]
 host.vpth_scene_free.argtypes = [_p]
+host.vpth_scene_count.argtypes = [_p, C.c_int]
+host.vpth_scene_get_item.argtypes = [_p, C.c_int, C.c_int, _p, C.c_int64]
+host.vpth_scene_get_item.restype = C.c_int64
+host.vpth_scene_set_item.argtypes = [_p, C.c_int, C.c_int, _p, C.c_int64, C.c_char_p, C.c_int]
+host.vpth_scene_update_bvh.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_free.restype = None
 host.vpth_scene_desc.argtypes = [_p]
 host.vpth_scene_desc.restype = _p
@@ -186,6 +284,15 @@ def device_count() -> int:
 BVH_NODE = np.dtype([("bbox_min", np.float32, 3), ("bbox_max", np.float32, 3), ("start", np.int32), ("num", np.int16), ("axis", np.int8),
                      ("internal", np.uint8)])
 assert BVH_NODE.itemsize == 32
+
+
+class VptSceneDescBvh(C.Structure):
+    """the last four tables of vpt_scene_desc (the two-level BVH); OFFSET: where they start (10 int32 + pointer tables, then 10
+    int64 + pointer pools: every pair takes 16 bytes)"""
+    _fields_ = [("num_scene_bvh_nodes", C.c_int32), ("scene_bvh_nodes", C.c_void_p), ("num_scene_bvh_prims", C.c_int32),
+                ("scene_bvh_prims", C.c_void_p), ("num_shape_bvh_nodes", C.c_int64), ("shape_bvh_nodes", C.c_void_p),
+                ("num_shape_bvh_prims", C.c_int64), ("shape_bvh_prims", C.c_void_p)]
+    OFFSET = 20 * 16
 
 
 def build_bvh(bboxes: np.ndarray, device: Optional[int] = 0):
@@ -280,6 +387,116 @@ class HostScene:
             raise VptError("stats buffer too small")
         return buf.value.decode()
 
+    # -- editing (the host side of vpt_scene_update, include/vpt.h).  Getters return copies; setters replace an item in the scene and
+    #    in the descriptor and note it in the pending SceneEdit; update_bvh() refits the BVHs and hands that edit out --------------
+    _CAMERA, _INSTANCE, _ENVIRONMENT, _MATERIAL, _POSITIONS, _NORMALS = range(6)
+
+    def count(self, kind: str) -> int:
+        """number of "cameras", "instances", "environments", "materials" or "shapes"""
+        return host.vpth_scene_count(self.handle, {"cameras": 0, "instances": 1, "environments": 2, "materials": 3, "shapes": 4}[kind])
+
+    def _get(self, kind: int, index: int, out, nbytes=None):
+        n = host.vpth_scene_get_item(self.handle, kind, index, None, 0)
+        if n < 0:
+            raise VptError(f"item {index} out of range")
+        if out is None:
+            out = np.zeros(n // 4, np.float32)
+        ptr = out.ctypes.data if isinstance(out, np.ndarray) else C.addressof(out)
+        host.vpth_scene_get_item(self.handle, kind, index, ptr, n)
+        return out
+
+    def _set(self, kind: int, index: int, value) -> None:
+        if isinstance(value, np.ndarray):
+            ptr, n = value.ctypes.data, value.nbytes
+        else:
+            ptr, n = C.addressof(value), C.sizeof(value)
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_set_item(self.handle, kind, index, ptr, n, err, len(err)) != 0:
+            raise VptError(err.value.decode())
+
+    def _pending(self) -> SceneEdit:
+        if getattr(self, "_edit", None) is None:
+            self._edit = SceneEdit()
+        return self._edit
+
+    def camera(self, index: int) -> VptCamera:
+        return self._get(self._CAMERA, index, VptCamera())
+
+    def instance_frame(self, index: int) -> np.ndarray:
+        """(12,) float32: x, y, z, o"""
+        return self._get(self._INSTANCE, index, np.zeros(12, np.float32))
+
+    def environment_frame(self, index: int) -> np.ndarray:
+        return self._get(self._ENVIRONMENT, index, np.zeros(12, np.float32))
+
+    def material(self, index: int) -> VptMaterial:
+        return self._get(self._MATERIAL, index, VptMaterial())
+
+    def instance_ids(self, index: int):
+        """(shape, material) of an instance"""
+        a = self._get(6, index, np.zeros(2, np.int32))
+        return int(a[0]), int(a[1])
+
+    def shape_positions(self, index: int) -> np.ndarray:
+        return self._get(self._POSITIONS, index, None).reshape(-1, 3)
+
+    def shape_normals(self, index: int) -> np.ndarray:
+        """(n, 3) float32; (0, 3) for a shape without normals"""
+        return self._get(self._NORMALS, index, None).reshape(-1, 3)
+
+    def shape_arrays(self, index: int) -> dict:
+        """every array of a shape as loaded and tesselated: positions, normals (n, 3), texcoords (n, 2), colors (n, 4), radius (n,)
+        float32; triangles (m, 3), quads (m, 4), points (m,), lines (m, 2) int32 (empty where the shape has none)"""
+        f = lambda kind, width: self._get(kind, index, None).reshape(-1, width) if width else self._get(kind, index, None)
+        i = lambda kind, width: self._get(kind, index, None).view(np.int32).reshape((-1, width) if width else (-1,))
+        return {"positions": f(4, 3), "normals": f(5, 3), "texcoords": f(7, 2), "colors": f(8, 4), "radius": f(9, 0),
+                "triangles": i(10, 3), "quads": i(11, 4), "points": i(12, 0), "lines": i(13, 2)}
+
+    def set_camera(self, index: int, camera: VptCamera) -> None:
+        self._set(self._CAMERA, index, camera)
+        self._pending().cameras[index] = self.camera(index)
+
+    def set_instance_frame(self, index: int, frame) -> None:
+        frame = np.ascontiguousarray(frame, np.float32).reshape(12)
+        self._set(self._INSTANCE, index, frame)
+        self._pending().instances[index] = frame.copy()
+
+    def set_environment_frame(self, index: int, frame) -> None:
+        frame = np.ascontiguousarray(frame, np.float32).reshape(12)
+        self._set(self._ENVIRONMENT, index, frame)
+        self._pending().environments[index] = frame.copy()
+
+    def set_material(self, index: int, material: VptMaterial) -> None:
+        self._set(self._MATERIAL, index, material)
+        self._pending().materials[index] = self.material(index)
+
+    def set_shape_positions(self, index: int, positions, normals=None) -> None:
+        """the vertices of a shape (same count), and its normals when given"""
+        positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        self._set(self._POSITIONS, index, positions)
+        if normals is not None:
+            normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+            self._set(self._NORMALS, index, normals)
+            normals = normals.copy()
+        elif index in self._pending().shapes:
+            normals = self._pending().shapes[index][1]
+        self._pending().shapes[index] = (positions.copy(), normals)
+
+    def update_bvh(self) -> SceneEdit:
+        """update_bvh of the reference over what the setters changed since the last call (a refit: topology and primitive order stay);
+        desc / stats() describe the edited scene afterwards.  Returns the SceneEdit for DeviceScene.update."""
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_update_bvh(self.handle, err, len(err)) != 0:
+            raise VptError(err.value.decode())
+        edit, self._edit = self._pending(), None
+        return edit
+
+    def bvh_nodes(self):
+        """(scene nodes, pooled shape nodes) of the descriptor as BVH_NODE arrays (copies)"""
+        d = VptSceneDescBvh.from_address(self.desc + VptSceneDescBvh.OFFSET)
+        grab = lambda ptr, n: np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (n * 32,)).view(BVH_NODE).copy() if n else np.zeros(0, BVH_NODE)
+        return grab(d.scene_bvh_nodes, d.num_scene_bvh_nodes), grab(d.shape_bvh_nodes, d.num_shape_bvh_nodes)
+
     def make_state(self, params: PathtraceParams) -> PathtraceState:
         """make_state, yocto_pathtrace.cpp:960-980"""
         w, h = C.c_int(), C.c_int()
@@ -354,6 +571,25 @@ class DeviceScene:
         _check(hip.vpt_render_device(self.handle, C.byref(abi), C.byref(layout), nsamples, d_image, d_hits, d_rng,
                                      stream), "vpt_render_device")
 
+    def update(self, edit: SceneEdit) -> None:
+        """vpt_scene_update (include/vpt.h): the edit applied to the resident scene, BVHs refitted on the device.  Afterwards the
+        handle renders the bits of a DeviceScene made from the host scene after the same edit and update_bvh()."""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_scene_update(self.handle, C.byref(abi)), "vpt_scene_update")
+        del keep
+
+    def get_bvh(self):
+        """(scene nodes, pooled shape nodes) as the device holds them, BVH_NODE arrays (vpt_scene_get_bvh)"""
+        a, b = self.host_scene.bvh_nodes()
+        _check(hip.vpt_scene_get_bvh(self.handle, a.ctypes.data, len(a), b.ctypes.data, len(b)), "vpt_scene_get_bvh")
+        return a, b
+
+    def update_stats(self):
+        """(kernel launches, payload bytes, device ms of the refit) of the last update"""
+        n, b, ms = C.c_int(0), C.c_int64(0), C.c_float(0)
+        _check(hip.vpt_scene_update_stats(self.handle, C.byref(n), C.byref(b), C.byref(ms)), "vpt_scene_update_stats")
+        return n.value, b.value, ms.value
+
     def intersect(self, rays: np.ndarray, instance: int = -1):
         """intersect_bvh for an (n, 6) float32 array of rays {o, d}: returns (ids (n, 2) int32, uvt (n, 3) float32)"""
         rays = np.ascontiguousarray(rays, np.float32)
@@ -424,6 +660,12 @@ class MultiDeviceScene:
         out = _p()
         _check(hip.vpt_multi_create_curves(scene.desc, scene.curves, devs, len(devices), C.byref(out)), "vpt_multi_create")
         self.handle = out
+
+    def update(self, edit: SceneEdit) -> None:
+        """vpt_multi_update: the same edit on every device; the resident tile state is left as it is"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_multi_update(self.handle, C.byref(abi)), "vpt_multi_update")
+        del keep
 
     def pathtrace_samples(self, state: PathtraceState, params: PathtraceParams, count: int = 1) -> None:
         """host state in, host state out (the contract of vpt_render); a device's part of the upload is skipped only while `state`'s

@@ -23,6 +23,7 @@
 #include "vpt_kat.h"
 #include "vpt_launch.h"
 #include "vpt_scene_prep.h"
+#include "vpt_scene_update.h"
 
 static std::string& g_error_text() {   // the message of the last failure on the calling thread (vpt_last_error)
   thread_local std::string text;
@@ -82,6 +83,8 @@ struct vpt_scene {
   int        light_features = 0;      // VPT_FEAT_* bits this scene's lights need from the mesh kernels
   bool       curves = false;          // some instanced shape holds points or lines: the VPT_FEAT_CURVES instances of K1
   host_mirrors h;   // range checks of vpt_intersect, vpt_kat
+  long long     num_shape_nodes = 0;   // nodes of d.shape_nodes (vpt_scene_get_bvh)
+  scene_updater upd;                   // vpt_scene_update: levels and quad-slot tables, built on the first update
 };
 
 namespace {
@@ -117,6 +120,15 @@ int make_dparams(const vpt_params* p, const vpt_layout* l, int nsamples, DParams
   return VPT_OK;
 }
 
+// light_prims: corners and element normals of the single-leaf mesh lights, by the device's own eval_element_normal
+int light_setup(vpt_scene* s) {
+  if (s->d.num_lights <= 0) return VPT_OK;
+  hipLaunchKernelGGL(vpt_light_setup_kernel, dim3(s->d.num_lights), dim3(64), 0, 0, s->d, const_cast<float4*>(s->d.light_prims));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  return VPT_OK;
+}
+
 }  // namespace
 
 int vpt_make_dparams(const vpt_params* p, const vpt_layout* l, int nsamples, DParams& out) { return make_dparams(p, l, nsamples, out); }
@@ -135,7 +147,7 @@ int vpt_device_count(void) {
 void vpt_scene_destroy(vpt_scene* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);   // the scene's buffers are freed on its device when it goes
-  for (hipEvent_t e : {s->ev_order, s->ev0, s->ev1, s->ev_host0, s->ev_host1})
+  for (hipEvent_t e : {s->ev_order, s->ev0, s->ev1, s->ev_host0, s->ev_host1, s->upd.ev0, s->upd.ev1})
     if (e) (void)hipEventDestroy(e);
   delete s;
 }
@@ -179,17 +191,13 @@ int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* 
 #undef UP
   D.shape_wnodes = D.scene_wnodes + t.scene_wnodes;
   s->stack_cap = t.stack_cap, s->stack_lds4 = t.stack_lds4, s->stack_spill4 = t.stack_spill4, s->light_features = t.light_features;
-  s->curves = t.curves;
+  s->curves = t.curves, s->num_shape_nodes = d.num_shape_bvh_nodes;
   s->h = std::move(t.h);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
   s->wave_slots_k1 = prop.multiProcessorCount * 4 * VPT_WAVES_PER_SIMD;
   s->wave_slots_k2 = prop.multiProcessorCount * 4 * VPT_K2_WAVES;
-  if (d.num_lights > 0) {   // element normals of the single-leaf mesh lights, by the device's own eval_element_normal
-    hipLaunchKernelGGL(vpt_light_setup_kernel, dim3(d.num_lights), dim3(64), 0, 0, s->d, const_cast<float4*>(D.light_prims));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-  }
+  if ((rc = light_setup(s)) != VPT_OK) return rc;
   for (hipEvent_t* e : {&s->ev0, &s->ev1, &s->ev_host0, &s->ev_host1}) HIP_TRY(hipEventCreate(e));
   if ((rc = s->d_watchdog.allocate(4)) != VPT_OK) return rc;
   HIP_TRY(hipMemset(s->d_watchdog.get(), 0, 4));
@@ -280,6 +288,10 @@ static int stack_config(vpt_scene* s, long long lanes, stack_cfg& cfg) {
   return VPT_OK;
 }
 
+// the measured costs, the order made from them and the tile-splitting decision go (the buffers stay)
+static void sched_forget(vpt_scene* s) {
+  s->order_valid = false, s->split_decided = false, s->full_costs = false, s->split_waves = 0, s->split_tiles = 0, s->cost_weight = 0;
+}
 // Buffers of the launch schedule for `waves` waves; a change of layout / camera / shader forgets the measured costs.
 static int sched_prepare(vpt_scene* s, long long waves, const long long key[10], hipStream_t st) {
   if (waves > s->sched_waves) {
@@ -296,8 +308,7 @@ static int sched_prepare(vpt_scene* s, long long waves, const long long key[10],
     if (int rc = s->sort_temp.allocate(bytes)) return rc;
     s->sort_temp_bytes = bytes, s->sched_waves = waves;
   }
-  if (memcmp(key, s->sched_key, sizeof(s->sched_key)) != 0)
-    s->order_valid = false, s->split_decided = false, s->full_costs = false, s->split_waves = 0, s->split_tiles = 0, s->cost_weight = 0, memcpy(s->sched_key, key, sizeof(s->sched_key));
+  if (memcmp(key, s->sched_key, sizeof(s->sched_key)) != 0) sched_forget(s), memcpy(s->sched_key, key, sizeof(s->sched_key));
   (void)st;
   return VPT_OK;
 }
@@ -618,6 +629,36 @@ int vpt_render_device(vpt_scene* s, const vpt_params* params, const vpt_layout* 
 int vpt_scene_record_bytes(const vpt_scene* s, int* leaf_bytes, int* attribute_bytes) {
   if (!s || !leaf_bytes || !attribute_bytes) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   *leaf_bytes = s->d.tri_prims ? 48 : 64, *attribute_bytes = s->d.tri_attrs ? 64 : 96;
+  return VPT_OK;
+}
+
+// ---- editing a resident scene (include/vpt.h; the work is vpt_scene_update.hip's) ---------------------------------------------
+int vpt_scene_update(vpt_scene* s, const vpt_scene_edit* edit) {
+  if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call rewrites
+  if (int rc = scene_update_apply(s->d, s->h, s->num_shape_nodes, s->upd, *edit)) return rc;
+  if (edit->num_instances > 0 || edit->num_shapes > 0)
+    if (int rc = light_setup(s)) return rc;   // light_prims hold world-space normals of the moved lights
+  sched_forget(s);   // the camera index may be the same, the picture is not
+  return VPT_OK;
+}
+
+int vpt_scene_get_bvh(vpt_scene* s, vpt_bvh_node* scene_nodes, int scene_capacity, vpt_bvh_node* shape_nodes, int64_t shape_capacity) {
+  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  REQUIRE(!scene_nodes || scene_capacity >= s->d.num_scene_nodes, "scene_capacity %d < %d scene bvh nodes", scene_capacity, s->d.num_scene_nodes);
+  REQUIRE(!shape_nodes || shape_capacity >= s->num_shape_nodes, "shape_capacity %lld < %lld shape bvh nodes", (long long)shape_capacity, s->num_shape_nodes);
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (scene_nodes && s->d.num_scene_nodes) HIP_TRY(hipMemcpy(scene_nodes, s->d.scene_nodes, (size_t)s->d.num_scene_nodes * sizeof(vpt_bvh_node), hipMemcpyDeviceToHost));
+  if (shape_nodes && s->num_shape_nodes) HIP_TRY(hipMemcpy(shape_nodes, s->d.shape_nodes, (size_t)s->num_shape_nodes * sizeof(vpt_bvh_node), hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+
+// what the last vpt_scene_update on this handle launched and sent (profiles/tools/scene_update_measure.py)
+int vpt_scene_update_stats(const vpt_scene* s, int* launches, int64_t* bytes, float* device_ms) {
+  if (!s || !launches || !bytes || !device_ms) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  *launches = s->upd.last_launches, *bytes = s->upd.last_bytes, *device_ms = s->upd.last_ms;
   return VPT_OK;
 }
 

@@ -316,6 +316,14 @@ void vpt_multi_destroy(vpt_multi* m) {
   delete m;
 }
 
+int vpt_multi_update(vpt_multi* m, const vpt_scene_edit* edit) {
+  if (!m || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  // every device holds the same scene: an edit the first one refuses has changed none
+  for (auto& p : m->parts)
+    if (int rc = vpt_scene_update(p.scene, edit)) return rc;
+  return VPT_OK;
+}
+
 int vpt_multi_device_count(const vpt_multi* m) { return m ? (int)m->parts.size() : 0; }
 
 const char* vpt_multi_transport(const vpt_multi* m) { return !m ? "" : m->use_rccl ? "rccl" : m->parts.size() > 1 ? "peer-copy" : "local"; }

@@ -49,6 +49,32 @@ void pack_frame(const hframe& f, float4* out) {
 // Returns the reference of the root and its box, appends to `out`; *need = worst-case number of stack
 // entries a traversal of this BVH holds at once (three pending siblings per quad level).
 constexpr int VPT_NONE_REF = -2147483647 - 1;
+// the (up to) four binary nodes behind the slots of the quad node made from internal binary node i (-1: empty slot), and the split axes
+void quad_slots_of(const vpt_bvh_node* nodes, int i, int slot[4], int axes[3]) {
+  axes[0] = nodes[i].axis, axes[1] = axes[2] = 0;
+  for (int side = 0; side < 2; side++) {
+    int c = nodes[i].start + side;
+    if (nodes[c].internal) slot[2 * side] = nodes[c].start, slot[2 * side + 1] = nodes[c].start + 1, axes[1 + side] = nodes[c].axis;
+    else slot[2 * side] = c, slot[2 * side + 1] = -1;
+  }
+}
+// binary nodes that become quad nodes, in depth-first preorder (a node's subtree stays close to it): order[n] = the binary node of
+// quad node n, quad_of[i] = the quad node of binary node i (-1: none).  A BVH without nodes or whose root is a leaf has no quad nodes.
+void quad_order(const vpt_bvh_node* nodes, int count, std::vector<int>& order, std::vector<int>& quad_of) {
+  order.clear(), quad_of.assign((size_t)(count > 0 ? count : 0), -1);
+  if (count <= 0 || !nodes[0].internal) return;
+  std::vector<int> todo{0};
+  while (!todo.empty()) {
+    int i = todo.back();
+    todo.pop_back();
+    quad_of[(size_t)i] = (int)order.size();
+    order.push_back(i);
+    int slot[4], axes[3];
+    quad_slots_of(nodes, i, slot, axes);
+    for (int k = 3; k >= 0; k--)
+      if (slot[k] >= 0 && nodes[slot[k]].internal) todo.push_back(slot[k]);
+  }
+}
 int build_quad_nodes(const vpt_bvh_node* nodes, int count, std::vector<float4>& out, float root_box[6], int* need) {
   for (int k = 0; k < 6; k++) root_box[k] = 0;
   *need = 0;
@@ -56,26 +82,9 @@ int build_quad_nodes(const vpt_bvh_node* nodes, int count, std::vector<float4>& 
   for (int k = 0; k < 3; k++) root_box[k] = nodes[0].bbox_min[k], root_box[3 + k] = nodes[0].bbox_max[k];
   auto leaf_code = [&](int i) { return ~((nodes[i].start << 4) | (nodes[i].num & 15)); };
   if (!nodes[0].internal) return leaf_code(0);
-  // binary nodes that become quad nodes, in depth-first preorder (a node's subtree stays close to it)
-  std::vector<int> quad_of((size_t)count, -1), order, todo{0};
-  auto slots_of = [&](int i, int slot[4], int axes[3]) {
-    axes[0] = nodes[i].axis, axes[1] = axes[2] = 0;
-    for (int side = 0; side < 2; side++) {
-      int c = nodes[i].start + side;
-      if (nodes[c].internal) slot[2 * side] = nodes[c].start, slot[2 * side + 1] = nodes[c].start + 1, axes[1 + side] = nodes[c].axis;
-      else slot[2 * side] = c, slot[2 * side + 1] = -1;
-    }
-  };
-  while (!todo.empty()) {
-    int i = todo.back();
-    todo.pop_back();
-    quad_of[(size_t)i] = (int)order.size();
-    order.push_back(i);
-    int slot[4], axes[3];
-    slots_of(i, slot, axes);
-    for (int k = 3; k >= 0; k--)
-      if (slot[k] >= 0 && nodes[slot[k]].internal) todo.push_back(slot[k]);
-  }
+  std::vector<int> quad_of, order;
+  quad_order(nodes, count, order, quad_of);
+  auto slots_of = [&](int i, int slot[4], int axes[3]) { quad_slots_of(nodes, i, slot, axes); };
   size_t base = out.size();
   out.resize(base + 8 * order.size());
   std::vector<int> node_need(order.size(), 0);
@@ -205,9 +214,7 @@ int validate(const vpt_scene_desc& d, const vpt_scene_curves& cs) {
   for (int i = 0; i < d.num_instances; i++) textured[(size_t)d.instances[i].material] = 1;
   for (int i = 0; i < d.num_materials; i++) {
     const vpt_material& m = d.materials[i];
-    REQUIRE(m.type >= 0 && m.type <= VPT_MAT_GLTFPBR, "material %d: bad type", i);
-    if (!textured[(size_t)i]) continue;
-    REQUIRE(tex_ok(m.emission_tex) && tex_ok(m.color_tex) && tex_ok(m.roughness_tex) && tex_ok(m.scattering_tex) && tex_ok(m.normal_tex), "material %d: texture id out of range", i);
+    if (int rc = prep_check_material(m, i, d.num_textures, textured[(size_t)i] != 0)) return rc;
   }
   for (int i = 0; i < d.num_textures; i++) {
     const vpt_texture& t = d.textures[i];
@@ -292,7 +299,7 @@ void build_geometry(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_t
         t.elems.push_back(make_int4(q[0], q[1], q[2], q[3]));
       }
     }
-    t.h.shape_elems.push_back(o.num_elems), t.h.shape_elem_offset.push_back(o.elem_offset);
+    t.h.shape_elems.push_back(o.num_elems), t.h.shape_elem_offset.push_back(o.elem_offset), t.h.shape_vertices.push_back(sh.num_vertices);
     t.h.prim_slot.resize(t.elems.size(), -1);
     // leaf records in BVH primitive order: slot k holds element prims[k]'s corners
     for (int k = 0; k < o.num_elems; k++) {
@@ -343,7 +350,8 @@ void build_geometry(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_t
   }
 }
 
-// quad nodes of every BVH, the shapes' roots and stack needs, and the traversal stacks sized from them
+// quad nodes of every BVH, the shapes' roots and stack needs, and the traversal stacks sized from them.  The stack sizes and the
+// VPT_FLOOR_SHIFT check depend on the trees' topology only: vpt_scene_update refits boxes and keeps topology, so they stay valid.
 int build_quad_nodes_and_stacks(const vpt_scene_desc& d, scene_tables& t) {
   std::vector<float4> shape_wnodes;
   int max_shape_depth = 0, max_shape_need4 = 0;
@@ -406,18 +414,14 @@ void build_instances(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_
   t.instances.resize((size_t)d.num_instances);
   for (int i = 0; i < d.num_instances; i++) {
     DInstance& in = t.instances[i];
-    hframe f = to_h(d.instances[i].frame);
     in = {};
-    pack_frame(hinverse(f, true), in.inv);
-    pack_frame(f, in.fwd);
+    prep_instance_frames(d.instances[i].frame, in.inv, in.fwd, &in.translation_only);
     in.shape = d.instances[i].shape, in.material = d.instances[i].material;
     const vpt_shape& sh = d.shapes[d.instances[i].shape];
     in.shape_flags = (sh.num_triangles != 0 ? VPT_SHP_TRIANGLES : 0) | (sh.normal_offset >= 0 ? VPT_SHP_NORMALS : 0) |
                      (sh.texcoord_offset >= 0 ? VPT_SHP_TEXCOORDS : 0) | (sh.color_offset >= 0 ? VPT_SHP_COLORS : 0) |
                      (curves_of(cs, in.shape).num_points ? VPT_SHP_POINTS : 0) | (curves_of(cs, in.shape).num_lines ? VPT_SHP_LINES : 0);
     t.curves = t.curves || has_curves(cs, in.shape);
-    in.translation_only = f.x.x == 1 && f.x.y == 0 && f.x.z == 0 && f.y.x == 0 && f.y.y == 1 && f.y.z == 0 &&
-                          f.z.x == 0 && f.z.y == 0 && f.z.z == 1;
     t.h.inst_shape.push_back(d.instances[i].shape);
   }
   t.enter.resize((size_t)d.num_scene_bvh_prims * 6);
@@ -427,6 +431,7 @@ void build_instances(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_
     const DInstance& in = t.instances[(size_t)id];
     const DShape&    sh = t.shapes[(size_t)in.shape];
     float4* e = &t.enter[6 * (size_t)k];
+    // (vpt_scene_update.hip rewrites e0..e2, the root box and translation_only of a resident scene in place: keep the two in step)
     e[0] = in.inv[0], e[1] = in.inv[1], e[2] = in.inv[2];
     e[3] = make_float4(sh.root_box[0], sh.root_box[1], sh.root_box[2], sh.root_box[3]);
     // the quad nodes of all BVHs live in one array, the scene's first: a level is named by the index of its first node
@@ -437,7 +442,10 @@ void build_instances(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_
     t.h.slot_of[(size_t)id] = k;
   }
   t.env_inv.resize((size_t)d.num_environments * 3), t.sdf_inv.resize((size_t)d.num_sdfs * 3);
-  for (int i = 0; i < d.num_environments; i++) pack_frame(hinverse(to_h(d.environments[i].frame), false), &t.env_inv[3 * (size_t)i]);
+  for (int i = 0; i < d.num_environments; i++) {
+    float4 fwd[3];
+    prep_environment_frames(d.environments[i].frame, &t.env_inv[3 * (size_t)i], fwd);
+  }
   for (int i = 0; i < d.num_sdfs; i++) pack_frame(hinverse(to_h(d.sdfs[i].frame), false), &t.sdf_inv[3 * (size_t)i]);
 }
 
@@ -514,8 +522,7 @@ void build_lights(const vpt_scene_desc& d, scene_tables& t) {
     } else if (l.environment != VPT_INVALID) {
       kind = VPT_LIGHT_ENV_TEX;
       const vpt_texture& tx = d.textures[d.environments[l.environment].emission_tex];
-      for (int k = 0; k < 3; k++) r[k] = t.env_inv[3 * (size_t)l.environment + k];
-      pack_frame(to_h(d.environments[l.environment].frame), &r[3]);
+      prep_environment_frames(d.environments[l.environment].frame, &r[0], &r[3]);
       int dims[2] = {tx.width, tx.height};
       memcpy(&r[6].x, dims, 8);
       r[6].z = total;
@@ -625,6 +632,34 @@ void build_sdf_records(const vpt_scene_desc& d, scene_tables& t) {
 }
 
 }  // namespace
+
+void prep_instance_frames(const vpt_frame& frame, float4 inv[3], float4 fwd[3], int* translation_only) {
+  hframe f = to_h(frame);
+  pack_frame(hinverse(f, true), inv);
+  pack_frame(f, fwd);
+  *translation_only = f.x.x == 1 && f.x.y == 0 && f.x.z == 0 && f.y.x == 0 && f.y.y == 1 && f.y.z == 0 &&
+                      f.z.x == 0 && f.z.y == 0 && f.z.z == 1;
+}
+void prep_environment_frames(const vpt_frame& frame, float4 inv[3], float4 fwd[3]) {
+  pack_frame(hinverse(to_h(frame), false), inv);
+  pack_frame(to_h(frame), fwd);
+}
+int prep_check_material(const vpt_material& m, int i, int num_textures, bool textured) {
+  auto tex_ok = [&](int t) { return t >= -1 && t < num_textures; };
+  REQUIRE(m.type >= 0 && m.type <= VPT_MAT_GLTFPBR, "material %d: bad type", i);
+  if (!textured) return VPT_OK;
+  REQUIRE(tex_ok(m.emission_tex) && tex_ok(m.color_tex) && tex_ok(m.roughness_tex) && tex_ok(m.scattering_tex) && tex_ok(m.normal_tex), "material %d: texture id out of range", i);
+  return VPT_OK;
+}
+void prep_quad_slots(const vpt_bvh_node* nodes, int count, std::vector<int>& slots) {
+  std::vector<int> order, quad_of;
+  quad_order(nodes, count, order, quad_of);
+  for (int i : order) {
+    int slot[4], axes[3];
+    quad_slots_of(nodes, i, slot, axes);
+    slots.insert(slots.end(), slot, slot + 4);
+  }
+}
 
 int prepare_scene(const vpt_scene_desc& d, const vpt_scene_curves* curves, scene_tables& t) {
   const vpt_scene_curves none = {};

@@ -9,6 +9,7 @@
 struct host_mirrors {
   std::vector<int> slot_of;   // instance -> scene-BVH primitive slot (-1: not in the scene BVH); also a device table
   std::vector<int> inst_shape, shape_elems, shape_elem_offset;
+  std::vector<int> shape_vertices;   // vertices per shape (vpt_scene_update: the size of a vertex edit)
   std::vector<int> prim_slot;   // [shape elem_offset + element] -> slot in leaf_prims / leaf_attrs
 };
 
@@ -43,3 +44,12 @@ struct scene_tables {
 // validate(desc, curves), then every table (curves may be null: no shape has points or lines); VPT_ERR_INVALID_ARG for a bad descriptor, VPT_ERR_UNSUPPORTED for a scene past a traversal
 // limit or with a shape that mixes points, lines and faces
 int prepare_scene(const vpt_scene_desc& desc, const vpt_scene_curves* curves, scene_tables& out);
+
+// Pieces of the layout that vpt_scene_update (vpt_scene_update.hip) needs for a resident scene, so that the tables keep one description:
+// the packed inverse (adjoint over determinant) and forward frame of an instance with its translation_only flag; of an environment
+// (rigid inverse); the rule of validate() for one material; and, per quad node of a BVH in the order build_quad_nodes emits them,
+// the four binary nodes its slots hold (appended to `slots`, -1: empty slot).
+void prep_instance_frames(const vpt_frame& frame, float4 inv[3], float4 fwd[3], int* translation_only);
+void prep_environment_frames(const vpt_frame& frame, float4 inv[3], float4 fwd[3]);
+int  prep_check_material(const vpt_material& m, int index, int num_textures, bool textured);
+void prep_quad_slots(const vpt_bvh_node* nodes, int count, std::vector<int>& slots);

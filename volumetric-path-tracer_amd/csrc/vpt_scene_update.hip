@@ -1,0 +1,527 @@
+// vpt_scene_update.hip — editing a resident scene (include/vpt.h: vpt_scene_update): validation of a
+// vpt_scene_edit and the kernels that rewrite the tables K1 and K2 read.  Only the edit's own payload crosses PCIe (cameras,
+// materials, frames with their host-made inverses, moved vertices); leaf records, node boxes, quad nodes, root boxes, enter
+// records, light records and instance boxes are derived on the device from what is resident.  The layouts are those of
+// vpt_device.h as vpt_scene_prep.cpp builds them: every kernel here copies or recomputes VALUES inside records whose shape,
+// order and integer fields creation decided.
+// The refit rule (include/vpt.h) is the reference's refit_bvh (yocto_bvh.cpp:510-524): select-form min / max in slot order,
+// children `start` then `start + 1`.  Levels run deepest first, one launch per level with stream order as the only barrier; the
+// narrow top levels run in one single-workgroup launch with __syncthreads() between levels.  No float atomics, no hand-off
+// between workgroups inside a launch.
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "vpt_error.h"
+#include "vpt_launch.h"
+#include "vpt_scene_update.h"
+
+namespace {
+
+struct box3 { float lo[3], hi[3]; };
+__device__ inline float sel_min(float a, float b) { return (a < b) ? a : b; }   // yocto_math.h:1355-1356: not fminf
+__device__ inline float sel_max(float a, float b) { return (a > b) ? a : b; }
+__device__ inline box3 invalid_box() {
+  const float m = 3.402823466e+38f;
+  return {{m, m, m}, {-m, -m, -m}};
+}
+__device__ inline box3 merge(box3 a, const box3& b) {
+  for (int c = 0; c < 3; c++) a.lo[c] = sel_min(a.lo[c], b.lo[c]), a.hi[c] = sel_max(a.hi[c], b.hi[c]);
+  return a;
+}
+__device__ inline box3 merge_point(box3 a, float x, float y, float z) {
+  a.lo[0] = sel_min(a.lo[0], x), a.lo[1] = sel_min(a.lo[1], y), a.lo[2] = sel_min(a.lo[2], z);
+  a.hi[0] = sel_max(a.hi[0], x), a.hi[1] = sel_max(a.hi[1], y), a.hi[2] = sel_max(a.hi[2], z);
+  return a;
+}
+// a binary node is 2 x float4: {min.xyz, max.x} {max.yz, start, num | axis << 16 | internal << 24}
+__device__ inline box3 node_box(const float4* nodes, long long i) {
+  float4 a = nodes[2 * i], b = nodes[2 * i + 1];
+  return {{a.x, a.y, a.z}, {a.w, b.x, b.y}};
+}
+__device__ inline void store_node_box(float4* nodes, long long i, const box3& b) {
+  nodes[2 * i] = make_float4(b.lo[0], b.lo[1], b.lo[2], b.hi[0]);
+  float4 t = nodes[2 * i + 1];
+  t.x = b.hi[1], t.y = b.hi[2];
+  nodes[2 * i + 1] = t;
+}
+__device__ inline int node_start(const float4* nodes, long long i) { return __float_as_int(nodes[2 * i + 1].z); }
+__device__ inline int node_meta(const float4* nodes, long long i) { return __float_as_int(nodes[2 * i + 1].w); }
+
+// the bounds of the primitive in one leaf record (vpt_device.h): quad_bounds over the four corners (a triangle repeats its last
+// corner: min(p2, p2) == p2, the bits of triangle_bounds), point_bounds, line_bounds
+__device__ inline box3 record_bounds(const float4* r) {
+  float4 p0 = r[0], p1 = r[1], p2 = r[2], p3 = r[3];
+  const int kind = __float_as_int(p3.w);
+  box3 b;
+  if (kind == VPT_LEAF_POINT) {
+    const float rad = p1.x;
+    const float a[3] = {p0.x - rad, p0.y - rad, p0.z - rad}, c[3] = {p0.x + rad, p0.y + rad, p0.z + rad};
+    for (int k = 0; k < 3; k++) b.lo[k] = sel_min(a[k], c[k]), b.hi[k] = sel_max(a[k], c[k]);
+  } else if (kind == VPT_LEAF_LINE) {
+    const float r0 = p2.x, r1 = p2.y;
+    const float a0[3] = {p0.x - r0, p0.y - r0, p0.z - r0}, a1[3] = {p1.x - r1, p1.y - r1, p1.z - r1};
+    const float c0[3] = {p0.x + r0, p0.y + r0, p0.z + r0}, c1[3] = {p1.x + r1, p1.y + r1, p1.z + r1};
+    for (int k = 0; k < 3; k++) b.lo[k] = sel_min(a0[k], a1[k]), b.hi[k] = sel_max(c0[k], c1[k]);
+  } else {
+    const float q0[3] = {p0.x, p0.y, p0.z}, q1[3] = {p1.x, p1.y, p1.z}, q2[3] = {p2.x, p2.y, p2.z}, q3[3] = {p3.x, p3.y, p3.z};
+    for (int k = 0; k < 3; k++)
+      b.lo[k] = sel_min(q0[k], sel_min(q1[k], sel_min(q2[k], q3[k]))), b.hi[k] = sel_max(q0[k], sel_max(q1[k], sel_max(q2[k], q3[k])));
+  }
+  return b;
+}
+
+// ---- kernels --------------------------------------------------------------------------------------------------------------
+// float3 in, the pools' float4 out (w = 0, as build_geometry leaves it)
+__global__ void upd_scatter_vertices_kernel(float4* __restrict__ pool, const float* __restrict__ src, int n) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) pool[i] = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], 0);
+}
+
+// One thread per leaf slot of a shape: the corners through elems and positions into every form the scene keeps of the record.
+// Element id (p0.w), record kind (p3.w), radii and texcoords are creation's and stay.
+__global__ void upd_leaf_records_kernel(DShape sh, const int4* __restrict__ elems, const float4* __restrict__ positions, const float4* __restrict__ normals,
+    float4* __restrict__ leaf_prims, float4* __restrict__ leaf_attrs, float4* __restrict__ tri_prims, float4* __restrict__ tri_attrs) {
+  int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= sh.num_elems) return;
+  const long long slot = (long long)sh.leaf_offset + k;
+  float4* r = leaf_prims + 4 * slot;
+  const int e = __float_as_int(r[0].w), kind = __float_as_int(r[3].w);
+  const int4 q = elems[(long long)sh.elem_offset + e];
+  const int v[4] = {q.x, q.y, q.z, q.w};
+  const float4* P = positions + sh.vertex_offset;
+  const int corners = kind == VPT_LEAF_POINT ? 1 : kind == VPT_LEAF_LINE ? 2 : 4;
+  for (int c = 0; c < corners; c++) {
+    float4 p = P[v[c]];
+    p.w = c == 0 ? __int_as_float(e) : c == 3 ? __int_as_float(kind) : 0.0f;   // faces: p3.w is the kind, 0
+    r[c] = p;
+  }
+  float4* a = leaf_attrs + 6 * slot;
+  if (sh.normal_offset >= 0)
+    for (int c = 0; c < 4; c++) a[c] = normals[(long long)sh.normal_offset + v[c]];
+  if (tri_prims) {   // the compact records of a scene of triangles, beside the general ones (vpt_device.h)
+    for (int c = 0; c < 3; c++) tri_prims[3 * slot + c] = r[c];
+    if (sh.normal_offset >= 0)
+      for (int c = 0; c < 3; c++) {
+        float4 t = tri_attrs[4 * slot + c], n = a[c];
+        tri_attrs[4 * slot + c] = make_float4(n.x, n.y, n.z, t.w);
+      }
+  }
+}
+
+// DShape::root_box of every shape from its root node
+__global__ void upd_shape_roots_kernel(DShape* __restrict__ shapes, int num_shapes, const float4* __restrict__ shape_nodes) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= num_shapes || shapes[i].num_nodes <= 0) return;
+  box3 b = node_box(shape_nodes, shapes[i].node_offset);
+  for (int c = 0; c < 3; c++) shapes[i].root_box[c] = b.lo[c], shapes[i].root_box[3 + c] = b.hi[c];
+}
+
+// leaves of a shape BVH: invalidb3f merged with the primitives' bounds in slot order
+__global__ void upd_refit_shape_leaves_kernel(float4* __restrict__ nodes, long long base, int count, const float4* __restrict__ leaf_prims, long long leaf_offset) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const int meta = node_meta(nodes, base + i);
+  if ((meta >> 24) & 255) return;
+  const int start = node_start(nodes, base + i), num = meta & 0xffff;
+  box3 b = invalid_box();
+  for (int k = 0; k < num; k++) b = merge(b, record_bounds(leaf_prims + 4 * (leaf_offset + start + k)));
+  store_node_box(nodes, base + i, b);
+}
+// leaves of the scene BVH: the instances' boxes through scene_prims
+__global__ void upd_refit_scene_leaves_kernel(float4* __restrict__ nodes, int count, const int* __restrict__ prims, const float4* __restrict__ inst_box) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const int meta = node_meta(nodes, i);
+  if ((meta >> 24) & 255) return;
+  const int start = node_start(nodes, i), num = meta & 0xffff;
+  box3 b = invalid_box();
+  for (int k = 0; k < num; k++) b = merge(b, node_box(inst_box, prims[start + k]));
+  store_node_box(nodes, i, b);
+}
+__device__ inline void refit_internal(float4* nodes, long long base, int i) {
+  const long long c = base + node_start(nodes, base + i);
+  store_node_box(nodes, base + i, merge(merge(invalid_box(), node_box(nodes, c)), node_box(nodes, c + 1)));
+}
+// one level of internal nodes (their children are leaves or belong to a level an earlier launch finished)
+__global__ void upd_refit_level_kernel(float4* nodes, long long base, const int* __restrict__ order, int count) {
+  int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < count) refit_internal(nodes, base, order[t]);
+}
+// The levels above `levels` (exclusive), deepest first, by ONE workgroup: first[l] .. first[l + 1] index `order`.
+enum { UPD_TOP_LEVELS = 24, UPD_TOP_WIDTH = 256 };
+struct top_levels { int first[UPD_TOP_LEVELS + 1]; };
+__global__ void __launch_bounds__(UPD_TOP_WIDTH) upd_refit_top_kernel(float4* nodes, long long base, const int* __restrict__ order, top_levels lv, int levels) {
+  for (int l = levels - 1; l >= 0; l--) {
+    for (int t = lv.first[l] + (int)threadIdx.x; t < lv.first[l + 1]; t += UPD_TOP_WIDTH) refit_internal(nodes, base, order[t]);
+    __syncthreads();   // the level's boxes are written before the one above reads them (one workgroup: workgroup scope is enough)
+  }
+}
+
+// quad nodes (build_quad_nodes): lo.x[4], lo.y[4], lo.z[4], hi.x[4], hi.y[4], hi.z[4] gathered from the binary nodes behind the
+// four slots; empty slots keep their zeros, references and axes are untouched
+__global__ void upd_quad_gather_kernel(float4* __restrict__ wnodes, const int4* __restrict__ slots, int count, const float4* __restrict__ nodes, long long base) {
+  int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= count) return;
+  const int4 s4 = slots[n];
+  const int  s[4] = {s4.x, s4.y, s4.z, s4.w};
+  float v[6][4];
+  for (int c = 0; c < 6; c++) {
+    float4 q = wnodes[8 * (long long)n + c];
+    v[c][0] = q.x, v[c][1] = q.y, v[c][2] = q.z, v[c][3] = q.w;
+  }
+  for (int k = 0; k < 4; k++) {
+    if (s[k] < 0) continue;
+    box3 b = node_box(nodes, base + s[k]);
+    for (int c = 0; c < 3; c++) v[c][k] = b.lo[c], v[3 + c][k] = b.hi[c];
+  }
+  for (int c = 0; c < 6; c++) wnodes[8 * (long long)n + c] = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+}
+
+struct inst_payload {   // one edited instance: the frames prep_instance_frames packs
+  float4 inv[3], fwd[3];
+  int    id, translation_only, pad[2];
+};
+__global__ void upd_scatter_instances_kernel(DInstance* __restrict__ instances, const inst_payload* __restrict__ in, int n) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  DInstance& d = instances[in[i].id];
+  for (int k = 0; k < 3; k++) d.inv[k] = in[i].inv[k], d.fwd[k] = in[i].fwd[k];
+  d.translation_only = in[i].translation_only;
+}
+// transform_bbox(frame, root box), yocto_geometry.h:441-451: the eight corners, z fastest, each through transform_point
+// (f.x * p.x + f.y * p.y + f.z * p.z + f.o, yocto_math.h:3097), merged into invalidb3f in that order
+__global__ void upd_instance_boxes_kernel(const DInstance* __restrict__ instances, int n, const DShape* __restrict__ shapes, float4* __restrict__ inst_box) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const DInstance& in = instances[i];
+  const DShape&    sh = shapes[in.shape];
+  box3 b = invalid_box();
+  if (sh.num_nodes > 0) {
+    // packed frame: {x.x, x.y, x.z, y.x} {y.y, y.z, z.x, z.y} {z.z, o.x, o.y, o.z}
+    const float4 f0 = in.fwd[0], f1 = in.fwd[1], f2 = in.fwd[2];
+    const float fx[3] = {f0.x, f0.y, f0.z}, fy[3] = {f0.w, f1.x, f1.y}, fz[3] = {f1.z, f1.w, f2.x}, fo[3] = {f2.y, f2.z, f2.w};
+    for (int cx = 0; cx < 2; cx++)
+      for (int cy = 0; cy < 2; cy++)
+        for (int cz = 0; cz < 2; cz++) {
+          const float px = sh.root_box[cx ? 3 : 0], py = sh.root_box[cy ? 4 : 1], pz = sh.root_box[cz ? 5 : 2];
+          float w[3];
+          for (int c = 0; c < 3; c++) w[c] = ((fx[c] * px + fy[c] * py) + fz[c] * pz) + fo[c];
+          b = merge_point(b, w[0], w[1], w[2]);
+        }
+  }
+  inst_box[2 * i]     = make_float4(b.lo[0], b.lo[1], b.lo[2], b.hi[0]);
+  inst_box[2 * i + 1] = make_float4(b.hi[1], b.hi[2], 0, 0);
+}
+// enter records (build_instances): e0..e2 inverse frame, e3 / e4.xy the shape's root box, e5.z translation_only; the rest is topology
+__global__ void upd_enter_records_kernel(float4* __restrict__ enter, int slots, const DInstance* __restrict__ instances, const DShape* __restrict__ shapes) {
+  int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= slots) return;
+  float4* e = enter + 6 * (long long)k;
+  const DInstance& in = instances[__float_as_int(e[5].y)];
+  const DShape&    sh = shapes[in.shape];
+  e[0] = in.inv[0], e[1] = in.inv[1], e[2] = in.inv[2];
+  e[3] = make_float4(sh.root_box[0], sh.root_box[1], sh.root_box[2], sh.root_box[3]);
+  float4 e4 = e[4], e5 = e[5];
+  e4.x = sh.root_box[4], e4.y = sh.root_box[5], e5.z = __int_as_float(in.translation_only);
+  e[4] = e4, e[5] = e5;
+}
+// light records of mesh lights (build_lights): frames of the instance, root box of its shape; area, kind and count stay
+__global__ void upd_light_records_kernel(float4* __restrict__ light_rec, const vpt_light* __restrict__ lights, int n, const DInstance* __restrict__ instances,
+    const DShape* __restrict__ shapes) {
+  int l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= n || lights[l].instance < 0) return;
+  const DInstance& in = instances[lights[l].instance];
+  const DShape&    sh = shapes[in.shape];
+  float4* r = light_rec + 8 * (long long)l;
+  for (int k = 0; k < 3; k++) r[k] = in.inv[k], r[3 + k] = in.fwd[k];
+  r[6] = make_float4(sh.root_box[0], sh.root_box[1], sh.root_box[2], r[6].w);
+  r[7] = make_float4(sh.root_box[3], sh.root_box[4], sh.root_box[5], r[7].w);
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------
+constexpr int BLOCK = 256;
+inline unsigned blocks_for(long long n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
+template <typename T>
+T* mut(const T* p) { return const_cast<T*>(p); }   // the scene owns its tables: DScene names them const for the render kernels
+
+// internal nodes by depth.  validate() made every child index larger than its parent's, so one forward pass gives every depth.
+void make_levels(const vpt_bvh_node* nodes, int count, bvh_levels& lv, std::vector<int>& order) {
+  lv.first.clear(), lv.offset = (long long)order.size();
+  std::vector<int> depth((size_t)(count > 0 ? count : 0), 0);
+  int deepest = -1;
+  for (int i = 0; i < count; i++) {
+    if (!nodes[i].internal) continue;
+    for (int c = nodes[i].start; c <= nodes[i].start + 1; c++)
+      if (depth[(size_t)c] < depth[(size_t)i] + 1) depth[(size_t)c] = depth[(size_t)i] + 1;
+    if (depth[(size_t)i] > deepest) deepest = depth[(size_t)i];
+  }
+  if (deepest < 0) return;
+  lv.first.assign((size_t)deepest + 2, 0);
+  for (int i = 0; i < count; i++)
+    if (nodes[i].internal) lv.first[(size_t)depth[(size_t)i] + 1]++;
+  for (size_t l = 1; l < lv.first.size(); l++) lv.first[l] += lv.first[l - 1];
+  std::vector<int> at(lv.first.begin(), lv.first.end() - 1);
+  order.resize((size_t)lv.offset + (size_t)lv.first.back());
+  for (int i = 0; i < count; i++)
+    if (nodes[i].internal) order[(size_t)lv.offset + (size_t)at[(size_t)depth[(size_t)i]]++] = i;
+}
+
+template <typename T>
+int read_back(std::vector<T>& out, const T* dev, size_t count) {
+  out.resize(count);
+  if (count) HIP_TRY(hipMemcpy(out.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+
+// everything an update needs beyond the tables themselves, from what the device holds (once per handle)
+int updater_init(const DScene& d, long long num_shape_nodes, scene_updater& u) {
+  std::vector<DInstance>    instances;
+  std::vector<vpt_bvh_node> scene_nodes, shape_nodes;
+  if (int rc = read_back(u.materials, d.materials, (size_t)d.num_materials)) return rc;
+  if (int rc = read_back(u.shapes, d.shapes, (size_t)d.num_shapes)) return rc;
+  if (int rc = read_back(u.lights, d.lights, (size_t)d.num_lights)) return rc;
+  if (int rc = read_back(instances, d.instances, (size_t)d.num_instances)) return rc;
+  if (int rc = read_back(scene_nodes, (const vpt_bvh_node*)d.scene_nodes, (size_t)d.num_scene_nodes)) return rc;
+  if (int rc = read_back(shape_nodes, (const vpt_bvh_node*)d.shape_nodes, (size_t)num_shape_nodes)) return rc;
+  std::vector<float4> light_rec;
+  if (int rc = read_back(light_rec, d.light_rec, 8 * (size_t)d.num_lights)) return rc;
+  u.light_kind.assign((size_t)d.num_lights, VPT_LIGHT_NONE);   // fixed at creation (build_lights): the tag of the record's last word
+  for (int l = 0; l < d.num_lights; l++) {
+    int tag;
+    memcpy(&tag, &light_rec[8 * (size_t)l + 7].w, 4);
+    u.light_kind[(size_t)l] = tag & 255;
+  }
+  u.textured.assign((size_t)d.num_materials, 0), u.shape_lit.assign((size_t)d.num_shapes, 0);
+  for (const DInstance& in : instances) u.textured[(size_t)in.material] = 1;
+  for (const vpt_light& l : u.lights)
+    if (l.instance >= 0) u.shape_lit[(size_t)instances[(size_t)l.instance].shape] = 1;
+  std::vector<int> order, slots;
+  make_levels(scene_nodes.data(), d.num_scene_nodes, u.scene_levels, order);
+  prep_quad_slots(scene_nodes.data(), d.num_scene_nodes, slots);
+  u.scene_quads = (long long)slots.size() / 4;
+  if (u.scene_quads != (d.shape_wnodes - d.scene_wnodes) / 8) return vpt_set_error(VPT_ERR_HIP, "scene update: the scene's quad nodes do not match its binary nodes");
+  u.shape_levels.assign((size_t)d.num_shapes, {}), u.shape_quads.assign((size_t)d.num_shapes, 0);
+  for (int i = 0; i < d.num_shapes; i++) {
+    const DShape& sh = u.shapes[(size_t)i];
+    if ((long long)slots.size() / 4 != u.scene_quads + sh.wnode_offset) return vpt_set_error(VPT_ERR_HIP, "scene update: shape %d: quad nodes do not match its binary nodes", i);
+    make_levels(shape_nodes.data() + sh.node_offset, sh.num_nodes, u.shape_levels[(size_t)i], order);
+    prep_quad_slots(shape_nodes.data() + sh.node_offset, sh.num_nodes, slots);
+    u.shape_quads[(size_t)i] = (long long)slots.size() / 4 - (u.scene_quads + sh.wnode_offset);
+  }
+  if (int rc = u.d_order.allocate(order.size() * sizeof(int))) return rc;
+  if (int rc = u.d_quad_slots.allocate(slots.size() * sizeof(int))) return rc;
+  if (int rc = u.d_inst_box.allocate((size_t)d.num_instances * 2 * sizeof(float4))) return rc;
+  if (!order.empty()) HIP_TRY(hipMemcpy(u.d_order.get(), order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (!slots.empty()) HIP_TRY(hipMemcpy(u.d_quad_slots.get(), slots.data(), slots.size() * sizeof(int), hipMemcpyHostToDevice));
+  u.ready = true;
+  return VPT_OK;
+}
+
+bool finite_all(const float* p, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+// ids of one list: non-null, in range, no repeats
+int check_ids(const char* what, int n, const int32_t* ids, const void* payload, int limit) {
+  REQUIRE(n >= 0 && (n == 0 || (ids && payload)), "edit: %s list is null or has a negative count", what);
+  std::vector<char> seen((size_t)limit, 0);
+  for (int i = 0; i < n; i++) {
+    REQUIRE(ids[i] >= 0 && ids[i] < limit, "edit: %s entry %d: id %d out of range (%d)", what, i, ids[i], limit);
+    REQUIRE(!seen[(size_t)ids[i]], "edit: %s entry %d: id %d repeated", what, i, ids[i]);
+    seen[(size_t)ids[i]] = 1;
+  }
+  return VPT_OK;
+}
+bool emissive(const vpt_material& m) { return !(m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0); }   // make_lights, yocto_pathtrace.cpp:990
+
+int validate_edit(const DScene& d, const host_mirrors& h, const scene_updater& u, const vpt_scene_edit& e) {
+  if (int rc = check_ids("camera", e.num_cameras, e.camera_ids, e.cameras, d.num_cameras)) return rc;
+  if (int rc = check_ids("instance", e.num_instances, e.instance_ids, e.instance_frames, d.num_instances)) return rc;
+  if (int rc = check_ids("environment", e.num_environments, e.environment_ids, e.environment_frames, d.num_environments)) return rc;
+  if (int rc = check_ids("material", e.num_materials, e.material_ids, e.materials, d.num_materials)) return rc;
+  if (int rc = check_ids("shape", e.num_shapes, e.shape_ids, e.shape_positions, d.num_shapes)) return rc;
+  for (int i = 0; i < e.num_cameras; i++) {
+    const vpt_camera& c = e.cameras[i];
+    REQUIRE(finite_all(c.frame.x, 12) && finite_all(&c.lens, 5), "edit: camera entry %d: a value is not finite", i);
+  }
+  for (int i = 0; i < e.num_instances; i++) REQUIRE(finite_all(e.instance_frames[i].x, 12), "edit: instance entry %d: a frame value is not finite", i);
+  for (int i = 0; i < e.num_environments; i++) REQUIRE(finite_all(e.environment_frames[i].x, 12), "edit: environment entry %d: a frame value is not finite", i);
+  for (int i = 0; i < e.num_materials; i++) {
+    const vpt_material& m = e.materials[i];
+    const int id = e.material_ids[i];
+    REQUIRE(finite_all(m.emission, 3) && finite_all(m.color, 3) && finite_all(&m.roughness, 3) && finite_all(m.scattering, 3) && finite_all(&m.scanisotropy, 3),
+        "edit: material entry %d: a value is not finite", i);
+    if (int rc = prep_check_material(m, id, d.num_textures, u.textured[(size_t)id] != 0)) return rc;
+    if (emissive(m) != emissive(u.materials[(size_t)id]))
+      return vpt_set_error(VPT_ERR_UNSUPPORTED, "edit: material entry %d: emission of material %d changes between zero and non-zero (the light list is fixed at creation)", i, id);
+  }
+  for (int i = 0; i < e.num_shapes; i++) {
+    const int id = e.shape_ids[i];
+    const size_t n = 3 * (size_t)h.shape_vertices[(size_t)id];
+    REQUIRE(e.shape_positions[i], "edit: shape entry %d: null positions", i);
+    REQUIRE(finite_all(e.shape_positions[i], n), "edit: shape entry %d: a position is not finite", i);
+    const float* nrm = e.shape_normals ? e.shape_normals[i] : nullptr;
+    if (nrm) {
+      REQUIRE(u.shapes[(size_t)id].normal_offset >= 0, "edit: shape entry %d: shape %d has no normals", i, id);
+      REQUIRE(finite_all(nrm, n), "edit: shape entry %d: a normal is not finite", i);
+    }
+    if (u.shape_lit[(size_t)id])
+      return vpt_set_error(VPT_ERR_UNSUPPORTED, "edit: shape entry %d: shape %d belongs to a light's instance (its element cdf is made from the areas)", i, id);
+  }
+  return VPT_OK;
+}
+
+#define LAUNCH(u, kernel, n, ...)                                                                     \
+  do {                                                                                                \
+    if ((n) > 0) {                                                                                    \
+      hipLaunchKernelGGL(kernel, dim3(blocks_for(n)), dim3(BLOCK), 0, 0, __VA_ARGS__);                \
+      HIP_TRY(hipGetLastError());                                                                     \
+      (u).last_launches++;                                                                            \
+    }                                                                                                 \
+  } while (0)
+
+// The edit's bulk payload (moved vertices, instance frames) goes to the device in ONE copy: collected at 16-byte aligned offsets of a
+// host block, sent to the staging buffer, read by the scatter kernels that follow on stream 0 - no synchronisation in between.
+struct payload {
+  std::vector<char> host;
+  size_t add(const void* src, size_t bytes) {
+    const size_t at = (host.size() + 15) & ~(size_t)15;
+    host.resize(at + bytes);
+    memcpy(host.data() + at, src, bytes);
+    return at;
+  }
+};
+int send(scene_updater& u, const payload& p) {
+  if (p.host.size() > u.stage_bytes) {
+    u.stage_bytes = 0;
+    if (int rc = u.d_stage.allocate(p.host.size())) return rc;   // the call began with the device idle: nothing reads the buffer that goes
+    u.stage_bytes = p.host.size();
+  }
+  if (!p.host.empty()) HIP_TRY(hipMemcpy(u.d_stage.get(), p.host.data(), p.host.size(), hipMemcpyHostToDevice));
+  u.last_bytes += (long long)p.host.size();
+  return VPT_OK;
+}
+
+// internal nodes of one BVH, deepest level first: a launch per level down to the narrow top, which one workgroup finishes
+int refit_internal_levels(scene_updater& u, float4* nodes, long long base, const bvh_levels& lv) {
+  if (lv.first.empty()) return VPT_OK;
+  const int  levels = (int)lv.first.size() - 1;
+  const int* order  = u.d_order.get<int>() + lv.offset;
+  int top = 0;   // levels [0, top) are narrow: one launch
+  const bool fuse = !getenv("VPT_UPDATE_NO_FUSE");   // A/B switch of the tests and measurements, read per call: a launch per level throughout - same bits
+  while (fuse && top < levels && top < UPD_TOP_LEVELS && lv.first[(size_t)top + 1] - lv.first[(size_t)top] <= UPD_TOP_WIDTH) top++;
+  for (int l = levels - 1; l >= top; l--) {
+    const int count = lv.first[(size_t)l + 1] - lv.first[(size_t)l];
+    LAUNCH(u, upd_refit_level_kernel, count, nodes, base, order + lv.first[(size_t)l], count);
+  }
+  if (top > 0) {
+    top_levels t = {};
+    for (int l = 0; l <= top; l++) t.first[l] = lv.first[(size_t)l];
+    hipLaunchKernelGGL(upd_refit_top_kernel, dim3(1), dim3(UPD_TOP_WIDTH), 0, 0, nodes, base, order, t, top);
+    HIP_TRY(hipGetLastError());
+    u.last_launches++;
+  }
+  return VPT_OK;
+}
+
+}  // namespace
+
+int scene_update_apply(DScene& d, const host_mirrors& h, long long num_shape_nodes, scene_updater& u, const vpt_scene_edit& e) {
+  if (!u.ready)
+    if (int rc = updater_init(d, num_shape_nodes, u)) return rc;
+  if (int rc = validate_edit(d, h, u, e)) return rc;   // every refusal happens here: nothing has been written
+  u.last_launches = 0, u.last_bytes = 0, u.last_ms = 0;
+  if (!u.ev0) {
+    HIP_TRY(hipEventCreate(&u.ev0));
+    HIP_TRY(hipEventCreate(&u.ev1));
+  }
+
+  // cameras, materials, environments: the payload itself (and the host-made inverse frame) into the tables
+  for (int i = 0; i < e.num_cameras; i++) {
+    HIP_TRY(hipMemcpy(mut(d.cameras) + e.camera_ids[i], &e.cameras[i], sizeof(vpt_camera), hipMemcpyHostToDevice));
+    u.last_bytes += sizeof(vpt_camera);
+  }
+  for (int i = 0; i < e.num_materials; i++) {
+    HIP_TRY(hipMemcpy(mut(d.materials) + e.material_ids[i], &e.materials[i], sizeof(vpt_material), hipMemcpyHostToDevice));
+    u.last_bytes += sizeof(vpt_material);
+    u.materials[(size_t)e.material_ids[i]] = e.materials[i];
+  }
+  for (int i = 0; i < e.num_environments; i++) {
+    const int id = e.environment_ids[i];
+    float4 inv[3], fwd[3];
+    prep_environment_frames(e.environment_frames[i], inv, fwd);
+    HIP_TRY(hipMemcpy(&mut(d.environments)[id].frame, &e.environment_frames[i], sizeof(vpt_frame), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(mut(d.env_inv) + 3 * (size_t)id, inv, sizeof(inv), hipMemcpyHostToDevice));
+    u.last_bytes += sizeof(vpt_frame) + sizeof(inv);
+    for (int l = 0; l < d.num_lights; l++) {   // light records of a textured environment hold both frames (build_lights); a constant one's stay zero
+      const vpt_light& lt = u.lights[(size_t)l];
+      if (lt.instance >= 0 || lt.sdf >= 0 || lt.environment != id) continue;
+      if (u.light_kind[(size_t)l] != VPT_LIGHT_ENV_TEX) continue;
+      float4 both[6] = {inv[0], inv[1], inv[2], fwd[0], fwd[1], fwd[2]};
+      HIP_TRY(hipMemcpy(mut(d.light_rec) + 8 * (size_t)l, both, sizeof(both), hipMemcpyHostToDevice));
+      u.last_bytes += sizeof(both);
+    }
+  }
+  if (e.num_instances == 0 && e.num_shapes == 0) return VPT_OK;
+
+  // the bulk payload in one copy: positions / normals of the edited shapes, frames of the edited instances
+  payload pay;
+  std::vector<size_t> at_pos((size_t)e.num_shapes, 0), at_nrm((size_t)e.num_shapes, 0);
+  for (int i = 0; i < e.num_shapes; i++) {
+    const size_t bytes = (size_t)h.shape_vertices[(size_t)e.shape_ids[i]] * 12;
+    at_pos[(size_t)i] = pay.add(e.shape_positions[i], bytes);
+    if (e.shape_normals && e.shape_normals[i]) at_nrm[(size_t)i] = pay.add(e.shape_normals[i], bytes);
+  }
+  std::vector<inst_payload> frames((size_t)e.num_instances);
+  for (int i = 0; i < e.num_instances; i++) {
+    frames[(size_t)i] = {};
+    frames[(size_t)i].id = e.instance_ids[i];
+    prep_instance_frames(e.instance_frames[i], frames[(size_t)i].inv, frames[(size_t)i].fwd, &frames[(size_t)i].translation_only);
+  }
+  const size_t at_frames = pay.add(frames.data(), frames.size() * sizeof(inst_payload));
+  if (int rc = send(u, pay)) return rc;
+  const char* staged = u.d_stage.get<char>();
+  HIP_TRY(hipEventRecord(u.ev0, 0));
+
+  // 1. edited shapes: vertices, leaf records, shape BVH, its quad nodes
+  float4* shape_nodes = mut(d.shape_nodes);
+  for (int i = 0; i < e.num_shapes; i++) {
+    const int     id = e.shape_ids[i];
+    const DShape& sh = u.shapes[(size_t)id];
+    const int     nv = h.shape_vertices[(size_t)id];
+    LAUNCH(u, upd_scatter_vertices_kernel, nv, mut(d.positions) + sh.vertex_offset, (const float*)(staged + at_pos[(size_t)i]), nv);
+    if (e.shape_normals && e.shape_normals[i])
+      LAUNCH(u, upd_scatter_vertices_kernel, nv, mut(d.normals) + sh.normal_offset, (const float*)(staged + at_nrm[(size_t)i]), nv);
+    LAUNCH(u, upd_leaf_records_kernel, sh.num_elems, sh, d.elems, d.positions, d.normals, mut(d.leaf_prims), mut(d.leaf_attrs), mut(d.tri_prims), mut(d.tri_attrs));
+    LAUNCH(u, upd_refit_shape_leaves_kernel, sh.num_nodes, shape_nodes, (long long)sh.node_offset, sh.num_nodes, d.leaf_prims, (long long)sh.leaf_offset);
+    if (int rc = refit_internal_levels(u, shape_nodes, sh.node_offset, u.shape_levels[(size_t)id])) return rc;
+    const long long q0 = u.scene_quads + sh.wnode_offset, quads = u.shape_quads[(size_t)id];
+    LAUNCH(u, upd_quad_gather_kernel, quads, mut(d.scene_wnodes) + 8 * q0, u.d_quad_slots.get<int4>() + q0, (int)quads, d.shape_nodes, (long long)sh.node_offset);
+  }
+  if (e.num_shapes > 0) LAUNCH(u, upd_shape_roots_kernel, d.num_shapes, mut(d.shapes), d.num_shapes, d.shape_nodes);
+
+  // 2. edited instances: frames
+  LAUNCH(u, upd_scatter_instances_kernel, e.num_instances, mut(d.instances), (const inst_payload*)(staged + at_frames), e.num_instances);
+
+  // 3. the scene BVH from ALL instances, what hangs on frames and root boxes, the scene's quad nodes
+  float4* scene_nodes = mut(d.scene_nodes);
+  LAUNCH(u, upd_instance_boxes_kernel, d.num_instances, d.instances, d.num_instances, d.shapes, u.d_inst_box.get<float4>());
+  LAUNCH(u, upd_enter_records_kernel, d.num_scene_prims, mut(d.scene_enter), d.num_scene_prims, d.instances, d.shapes);
+  LAUNCH(u, upd_light_records_kernel, d.num_lights, mut(d.light_rec), d.lights, d.num_lights, d.instances, d.shapes);
+  LAUNCH(u, upd_refit_scene_leaves_kernel, d.num_scene_nodes, scene_nodes, d.num_scene_nodes, d.scene_prims, u.d_inst_box.get<float4>());
+  if (int rc = refit_internal_levels(u, scene_nodes, 0, u.scene_levels)) return rc;
+  LAUNCH(u, upd_quad_gather_kernel, u.scene_quads, mut(d.scene_wnodes), u.d_quad_slots.get<int4>(), (int)u.scene_quads, d.scene_nodes, 0LL);
+  HIP_TRY(hipEventRecord(u.ev1, 0));
+  if (d.num_scene_nodes > 0) {   // the six scene_root_* floats the kernels receive by value
+    vpt_bvh_node root;
+    HIP_TRY(hipMemcpy(&root, d.scene_nodes, sizeof(root), hipMemcpyDeviceToHost));
+    d.scene_root_lo_x = root.bbox_min[0], d.scene_root_lo_y = root.bbox_min[1], d.scene_root_lo_z = root.bbox_min[2];
+    d.scene_root_hi_x = root.bbox_max[0], d.scene_root_hi_y = root.bbox_max[1], d.scene_root_hi_z = root.bbox_max[2];
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipEventElapsedTime(&u.last_ms, u.ev0, u.ev1));
+  return VPT_OK;
+}

@@ -173,6 +173,12 @@ pathtrace_state  make_state(const scene_data& scene, const pathtrace_params& par
 bvh_scene        make_bvh(const scene_data& scene, const pathtrace_params& params);
 // Extension: the same trees (node for node, hash-equal) built on GPU `device` by vpt_build_bvh; throws if that fails.
 bvh_scene        make_bvh_device(const scene_data& scene, const pathtrace_params& params, int device = 0);
+// update_bvh(bvh, scene, updated_instances, updated_shapes) of the reference (yocto_bvh.h:100-103, yocto_bvh.cpp:509-524, 613-689): a
+// refit.  Topology, node ids and primitive order stay; the boxes of the named shapes' BVHs, then of the scene BVH (from ALL
+// instances: the reference does not read `updated_instances` either) are recomputed from invalidb3f with the bounds routines of
+// make_bvh.  An instance of a shape without nodes gets invalidb3f as in make_bvh (the reference reads nodes[0] of an empty vector).
+// The device counterpart is vpt_scene_update (include/vpt.h).
+void             update_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& updated_instances, const vector<int>& updated_shapes);
 // build_bvh over `n` boxes {min.xyz, max.xyz} on the host (what make_bvh runs per shape and for the instances)
 bvh_data         build_bvh_host(const float* bboxes, int n);
 pathtrace_lights make_lights(const scene_data& scene, const pathtrace_params& params);
@@ -215,7 +221,7 @@ void pathtrace_samples(pathtrace_state& state, const scene_data& scene, const bv
     const pathtrace_lights& lights, const pathtrace_params& params, int count);
 // Drop the cached device copy of `scene`.  pathtrace_samples notices by itself a scene rebuilt at the same address and every
 // in-place edit of the small tables (cameras, instances, materials, environments, volume instances, SDFs, lights: hashed in full
-// on each call); in-place edits of BULK data - vertex arrays, texels, voxels, BVH nodes, light CDFs - are only sampled at head
+// on each call; a camera edited in place goes to the resident copy through vpt_scene_update, anything else makes a new copy); in-place edits of BULK data - vertex arrays, texels, voxels, BVH nodes, light CDFs - are only sampled at head
 // and tail and have to be announced with this call.
 void pathtrace_release(const scene_data& scene);
 // Extension: the GPUs pathtrace_samples renders on (default {0}).  With more than one, the frame's 8x8 tiles are dealt
@@ -301,6 +307,8 @@ bool load_subdiv(const string& filename, subdiv_data& subdiv, string& error);
 bool load_texture(const string& filename, texture_data& texture, string& error);
 bool load_volume(const string& filename, volume_data& vol, bool binary, string& error);
 bool save_image(const string& filename, const color_image& image, string& error);
+// a JSON array of camera objects with the keys of a scene file's "cameras" entries (ypathtrace --cameras); not empty
+bool load_cameras(const string& filename, vector<camera_data>& cameras, string& error);
 // the members of a --config file (yocto_cli.cpp:912-945) as (option name, value text) pairs
 bool load_cli_config(const string& filename, vector<std::pair<string, string>>& options, string& error);
 // output quantisation (yocto_color.h:207-231, yocto_image.cpp:870-874)

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <set>
 
 #include "vpt_host.h"
 
@@ -16,6 +17,7 @@ struct host_scene {
   bvh_scene        bvh;
   pathtrace_lights lights;
   std::unique_ptr<flat_scene> flat = std::make_unique<flat_scene>();
+  std::set<int> edited_instances, edited_shapes;   // since the last vpth_scene_update_bvh
 };
 void set_error(char* err, int errlen, const string& msg) {
   if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", msg.c_str());
@@ -132,6 +134,103 @@ int vpth_build_bvh_host(const float* bboxes, int n, vpt_bvh_node* nodes, int* nu
   if (n > 0) memcpy(primitives, bvh.primitives.data(), (size_t)n * sizeof(int32_t));
   *num_nodes = (int)bvh.nodes.size();
   return 0;
+}
+// ---- editing a loaded scene (the host side of vpt_scene_update, include/vpt.h) -----------------------------------------------
+// kinds of item: 0 camera (vpt_camera), 1 instance frame (vpt_frame), 2 environment frame (vpt_frame), 3 material (vpt_material),
+// 4 positions / 5 normals of a shape (float3 per vertex), 6 {shape, material} of an instance (two int32, read only);
+// read only, of a shape: 7 texcoords (float2), 8 colors (float4), 9 radius (float), 10 triangles (int3), 11 quads (int4), 12 points (int), 13 lines (int2)
+int vpth_scene_count(void* hh, int kind) {
+  auto& sc = ((host_scene*)hh)->scene;
+  switch (kind) {
+    case 0: return (int)sc.cameras.size();
+    case 1: return (int)sc.instances.size();
+    case 2: return (int)sc.environments.size();
+    case 3: return (int)sc.materials.size();
+    case 4: case 5: case 7: case 8: case 9: case 10: case 11: case 12: case 13: return (int)sc.shapes.size();
+    case 6: return (int)sc.instances.size();
+    default: return -1;
+  }
+}
+// copies item `id` to `out` when it fits `capacity` bytes; returns its size in bytes, -1 for a bad kind or id
+int64_t vpth_scene_get_item(void* hh, int kind, int id, void* out, int64_t capacity) {
+  auto& h = *(host_scene*)hh;
+  if (id < 0 || id >= vpth_scene_count(hh, kind)) return -1;
+  auto& flat = *h.flat;   // the flattened forms are the ABI's structs
+  const void* src = nullptr;
+  int64_t     n   = 0;
+  switch (kind) {
+    case 0: src = &flat.cameras[id], n = sizeof(vpt_camera); break;
+    case 1: src = &flat.instances[id].frame, n = sizeof(vpt_frame); break;
+    case 2: src = &flat.environments[id].frame, n = sizeof(vpt_frame); break;
+    case 3: src = &flat.materials[id], n = sizeof(vpt_material); break;
+    case 4: src = h.scene.shapes[id].positions.data(), n = (int64_t)h.scene.shapes[id].positions.size() * 12; break;
+    case 5: src = h.scene.shapes[id].normals.data(), n = (int64_t)h.scene.shapes[id].normals.size() * 12; break;
+    case 6: src = &flat.instances[id].shape, n = 8; break;
+    case 7: src = h.scene.shapes[id].texcoords.data(), n = (int64_t)h.scene.shapes[id].texcoords.size() * 8; break;
+    case 8: src = h.scene.shapes[id].colors.data(), n = (int64_t)h.scene.shapes[id].colors.size() * 16; break;
+    case 9: src = h.scene.shapes[id].radius.data(), n = (int64_t)h.scene.shapes[id].radius.size() * 4; break;
+    case 10: src = h.scene.shapes[id].triangles.data(), n = (int64_t)h.scene.shapes[id].triangles.size() * 12; break;
+    case 11: src = h.scene.shapes[id].quads.data(), n = (int64_t)h.scene.shapes[id].quads.size() * 16; break;
+    case 12: src = h.scene.shapes[id].points.data(), n = (int64_t)h.scene.shapes[id].points.size() * 4; break;
+    case 13: src = h.scene.shapes[id].lines.data(), n = (int64_t)h.scene.shapes[id].lines.size() * 8; break;
+  }
+  if (out && capacity >= n && n > 0) memcpy(out, src, (size_t)n);
+  return n;
+}
+// Replaces item `id` in the scene containers and in the flattened descriptor; the BVHs follow at vpth_scene_update_bvh.
+int vpth_scene_set_item(void* hh, int kind, int id, const void* in, int64_t bytes, char* err, int errlen) {
+  auto& h = *(host_scene*)hh;
+  if (kind > 5 || id < 0 || id >= vpth_scene_count(hh, kind) || !in) return set_error(err, errlen, "bad item kind, id or pointer"), -1;
+  if (bytes != vpth_scene_get_item(hh, kind, id, nullptr, 0)) return set_error(err, errlen, "item size does not match (counts cannot change)"), -1;
+  auto frame_of = [](const vpt_frame& f) {
+    auto r = frame3f{};
+    memcpy((void*)&r, &f, sizeof(f));
+    return r;
+  };
+  switch (kind) {
+    case 0: {
+      auto& c = h.scene.cameras[id];
+      auto& d = *(const vpt_camera*)in;
+      c.frame = frame_of(d.frame), c.orthographic = d.orthographic != 0, c.lens = d.lens, c.film = d.film, c.aspect = d.aspect, c.focus = d.focus, c.aperture = d.aperture;
+    } break;
+    case 1: h.scene.instances[id].frame = frame_of(*(const vpt_frame*)in), h.edited_instances.insert(id); break;
+    case 2: h.scene.environments[id].frame = frame_of(*(const vpt_frame*)in); break;
+    case 3: {
+      auto& m = h.scene.materials[id];
+      auto& d = *(const vpt_material*)in;
+      if (d.type < 0 || d.type > VPT_MAT_GLTFPBR) return set_error(err, errlen, "bad material type"), -1;
+      m.type = (material_type)d.type;
+      memcpy((void*)&m.emission, d.emission, 12), memcpy((void*)&m.color, d.color, 12), memcpy((void*)&m.scattering, d.scattering, 12);
+      m.roughness = d.roughness, m.metallic = d.metallic, m.ior = d.ior, m.scanisotropy = d.scanisotropy, m.trdepth = d.trdepth, m.opacity = d.opacity;
+      m.emission_tex = d.emission_tex, m.color_tex = d.color_tex, m.roughness_tex = d.roughness_tex, m.scattering_tex = d.scattering_tex, m.normal_tex = d.normal_tex;
+    } break;
+    case 4: memcpy((void*)h.scene.shapes[id].positions.data(), in, (size_t)bytes), h.edited_shapes.insert(id); break;
+    case 5: memcpy((void*)h.scene.shapes[id].normals.data(), in, (size_t)bytes); break;
+  }
+  auto& flat = *h.flat;   // the descriptor's own copy of the item, so that it reads back at once; the BVH arrays wait for update_bvh
+  switch (kind) {
+    case 0: flat.cameras[id] = *(const vpt_camera*)in; break;
+    case 1: flat.instances[id].frame = *(const vpt_frame*)in; break;
+    case 2: flat.environments[id].frame = *(const vpt_frame*)in; break;
+    case 3: flat.materials[id] = *(const vpt_material*)in; break;
+    case 4: memcpy((void*)(flat.positions.data() + flat.shapes[id].position_offset), in, (size_t)bytes); break;
+    case 5: memcpy((void*)(flat.normals.data() + flat.shapes[id].normal_offset), in, (size_t)bytes); break;
+  }
+  return 0;
+}
+// update_bvh over the instances and shapes edited since the last call, then the flattened descriptor again (its address changes)
+int vpth_scene_update_bvh(void* hh, char* err, int errlen) {
+  try {
+    auto& h = *(host_scene*)hh;
+    update_bvh(h.bvh, h.scene, {h.edited_instances.begin(), h.edited_instances.end()}, {h.edited_shapes.begin(), h.edited_shapes.end()});
+    h.edited_instances.clear(), h.edited_shapes.clear();
+    auto flat = std::make_unique<flat_scene>();
+    flatten_scene(*flat, h.scene, h.bvh, h.lights);
+    h.flat = std::move(flat);
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
 }
 void vpth_scene_free(void* h) { delete (host_scene*)h; }
 const vpt_scene_desc* vpth_scene_desc(void* h) { return &((host_scene*)h)->flat->desc; }

@@ -136,8 +136,8 @@ bvh_data build_bvh_host(const float* bboxes, int n) {
   return bvh;
 }
 
-static bvh_data make_shape_bvh(const shape_data& shape, int device) {
-  auto bvh    = bvh_data{};
+// the primitives' bounds of a shape, in the reference's order: points, lines, triangles, quads (yocto_bvh.cpp:536-565, 620-649)
+static vector<bbox3f> shape_bboxes(const shape_data& shape) {
   auto bboxes = vector<bbox3f>{};
   // point_bounds(p, r) / line_bounds(p0, p1, r0, r1), yocto_geometry.h:461-471, in the reference's order: points, lines, faces
   auto sub = [](const vec3f& p, float r) { return vec3f{p.x - r, p.y - r, p.z - r}; };
@@ -173,14 +173,16 @@ static bvh_data make_shape_bvh(const shape_data& shape, int device) {
       bboxes[i] = {vmin(p0, vmin(p1, vmin(p2, p3))), vmax(p0, vmax(p1, vmax(p2, p3)))};
     }
   }
-  build_nodes_on(device, bvh, bboxes);
+  return bboxes;
+}
+static bvh_data make_shape_bvh(const shape_data& shape, int device) {
+  auto bvh = bvh_data{};
+  build_nodes_on(device, bvh, shape_bboxes(shape));
   return bvh;
 }
 
-static bvh_scene make_bvh_on(int device, const scene_data& scene) {
-  auto bvh = bvh_data{};
-  bvh.shapes.resize(scene.shapes.size());
-  for (size_t i = 0; i < scene.shapes.size(); i++) bvh.shapes[i] = make_shape_bvh(scene.shapes[i], device);
+// the instances' bounds: transform_bbox(frame, root box of the shape's BVH); invalidb3f for a shape without nodes
+static vector<bbox3f> instance_bboxes(const scene_data& scene, const bvh_data& bvh) {
   auto bboxes = vector<bbox3f>(scene.instances.size());
   for (size_t i = 0; i < bboxes.size(); i++) {
     auto& instance = scene.instances[i];
@@ -197,8 +199,40 @@ static bvh_scene make_bvh_on(int device, const scene_data& scene) {
         }
     bboxes[i] = box;
   }
-  build_nodes_on(device, bvh, bboxes);
+  return bboxes;
+}
+
+static bvh_scene make_bvh_on(int device, const scene_data& scene) {
+  auto bvh = bvh_data{};
+  bvh.shapes.resize(scene.shapes.size());
+  for (size_t i = 0; i < scene.shapes.size(); i++) bvh.shapes[i] = make_shape_bvh(scene.shapes[i], device);
+  build_nodes_on(device, bvh, instance_bboxes(scene, bvh));
   return bvh;
+}
+
+// refit_bvh, yocto_bvh.cpp:510-524: nodes in reverse order (children follow their parent), every box from invalidb3f
+static void refit_nodes(bvh_data& bvh, const vector<bbox3f>& bboxes) {
+  for (auto nodeid = (int)bvh.nodes.size() - 1; nodeid >= 0; nodeid--) {
+    auto& node = bvh.nodes[nodeid];
+    auto  box  = bbox3f{};
+    if (node.internal) {
+      for (auto idx = 0; idx < 2; idx++) {
+        auto& child = bvh.nodes[node.start + idx];
+        box = merge(box, bbox3f{{child.bbox_min[0], child.bbox_min[1], child.bbox_min[2]}, {child.bbox_max[0], child.bbox_max[1], child.bbox_max[2]}});
+      }
+    } else {
+      for (auto idx = 0; idx < node.num; idx++) box = merge(box, bboxes[bvh.primitives[node.start + idx]]);
+    }
+    node.bbox_min[0] = box.min.x, node.bbox_min[1] = box.min.y, node.bbox_min[2] = box.min.z;
+    node.bbox_max[0] = box.max.x, node.bbox_max[1] = box.max.y, node.bbox_max[2] = box.max.z;
+  }
+}
+// update_bvh, yocto_bvh.cpp:680-689: the edited shapes, then the scene BVH from all instances (`updated_instances` is not read
+// by the reference's own refit either)
+void update_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& updated_instances, const vector<int>& updated_shapes) {
+  (void)updated_instances;
+  for (auto shape : updated_shapes) refit_nodes(bvh.shapes.at(shape), shape_bboxes(scene.shapes.at(shape)));
+  refit_nodes(bvh, instance_bboxes(scene, bvh));
 }
 bvh_scene make_bvh(const scene_data& scene, const pathtrace_params&) { return make_bvh_on(-1, scene); }
 bvh_scene make_bvh_device(const scene_data& scene, const pathtrace_params&, int device) {
@@ -453,6 +487,7 @@ struct device_entry {
   vpt_multi* handle = nullptr;
   vpt_scene* single = nullptr;   // pathtrace_adaptive's copy on one GPU (vpt_render_adaptive), made on first use
   uint64_t   fingerprint = 0;
+  uint64_t   cameras     = 0;    // fingerprint of the cameras table alone: a change of it is an edit of the resident copy
   ~device_entry() {
     if (handle) vpt_multi_destroy(handle);
     if (single) vpt_scene_destroy(single);
@@ -495,10 +530,12 @@ uint64_t mix_table(uint64_t h, const vector<T>& v) {   // small tables (a few KB
 // instances, SDFs, light ids - are hashed in full, so an in-place edit of any of them (a moved instance, a changed material or
 // camera) rebuilds the copy on the next call, as the reference - which reads the live scene - would show it.  The bulk arrays
 // (vertex data, texels, voxels, BVH nodes, light CDFs) are sampled at head and tail only: editing them in place between two calls
-// needs pathtrace_release(scene) (vpt_host.h).
+// needs pathtrace_release(scene) (vpt_host.h).  The cameras have a fingerprint of their own: a camera edited in place (the
+// reference's viewer does it on every mouse drag, apps/ypathtrace/ypathtrace.cpp:269-297) goes to the resident copy through
+// vpt_scene_update instead of making a new one.
 uint64_t scene_fingerprint(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights) {
   auto h = 0xcbf29ce484222325ull;
-  h = mix_table(h, scene.cameras), h = mix_table(h, scene.instances), h = mix_table(h, scene.materials);
+  h = mix(h, scene.cameras.size()), h = mix_table(h, scene.instances), h = mix_table(h, scene.materials);
   h = mix_table(h, scene.environments), h = mix_table(h, scene.vol_instances), h = mix_table(h, scene.sdfs);
   h = mix(h, scene.shapes.size()), h = mix(h, scene.textures.size()), h = mix(h, scene.volumes.size());
   for (auto& s : scene.shapes) h = mix_array(h, s.positions), h = mix(h, s.triangles.size()), h = mix(h, s.quads.size()),
@@ -515,10 +552,28 @@ uint64_t scene_fingerprint(const scene_data& scene, const bvh_scene& bvh, const 
 device_entry& cached_entry(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights) {
   auto& entry = device_cache()[&scene];
   auto  print = scene_fingerprint(scene, bvh, lights);
+  auto  cams  = mix_table(0xcbf29ce484222325ull, scene.cameras);
   if (!entry || entry->fingerprint != print) {
     entry.reset();
     entry              = std::make_unique<device_entry>();
-    entry->fingerprint = print;
+    entry->fingerprint = print, entry->cameras = cams;
+  } else if (entry->cameras != cams) {
+    auto ids = vector<int32_t>{};
+    auto abi = vector<vpt_camera>{};
+    for (auto& c : scene.cameras) {
+      ids.push_back((int32_t)ids.size());
+      auto& d = abi.emplace_back();
+      d.frame = to_abi(c.frame), d.orthographic = c.orthographic, d.lens = c.lens, d.film = c.film;
+      d.aspect = c.aspect, d.focus = c.focus, d.aperture = c.aperture;
+    }
+    auto edit = vpt_scene_edit{};
+    edit.num_cameras = (int32_t)ids.size(), edit.camera_ids = ids.data(), edit.cameras = abi.data();
+    if ((entry->handle && vpt_multi_update(entry->handle, &edit) != VPT_OK) || (entry->single && vpt_scene_update(entry->single, &edit) != VPT_OK)) {
+      entry.reset();   // the copy may be half edited: it goes
+      device_cache().erase(&scene);
+      throw std::runtime_error{string{"vpt_scene_update: "} + vpt_last_error()};
+    }
+    entry->cameras = cams;
   }
   return *entry;
 }

@@ -924,6 +924,13 @@ bool load_volume(const string& filename, volume_data& vol, bool binary, string& 
 // ---------------------------------------------------------------------------------------------
 // JSON scene 4.2
 // ---------------------------------------------------------------------------------------------
+// one entry of a scene file's "cameras" (also the entries of a --cameras file, load_cameras)
+static void read_camera(const json_value& e, camera_data& camera) {
+  get_opt(e, "frame", camera.frame), get_opt(e, "orthographic", camera.orthographic);
+  get_opt(e, "lens", camera.lens), get_opt(e, "aspect", camera.aspect), get_opt(e, "film", camera.film);
+  get_opt(e, "focus", camera.focus), get_opt(e, "aperture", camera.aperture);
+}
+
 bool load_scene(const string& filename, scene_data& scene, string& error) {
   scene    = {};
   auto ext = path_extension(filename);
@@ -956,12 +963,7 @@ bool load_scene(const string& filename, scene_data& scene, string& error) {
       if (g->kind != json_value::array_k) throw std::runtime_error{"json"};
       return g->items;
     };
-    for (auto& e : group("cameras")) {
-      auto& camera = scene.cameras.emplace_back();
-      get_opt(e, "frame", camera.frame), get_opt(e, "orthographic", camera.orthographic);
-      get_opt(e, "lens", camera.lens), get_opt(e, "aspect", camera.aspect), get_opt(e, "film", camera.film);
-      get_opt(e, "focus", camera.focus), get_opt(e, "aperture", camera.aperture);
-    }
+    for (auto& e : group("cameras")) read_camera(e, scene.cameras.emplace_back());
     for (auto& e : group("textures")) {
       scene.textures.emplace_back();
       get_opt(e, "uri", texture_uris.emplace_back());
@@ -1145,6 +1147,26 @@ bool save_image(const string& filename, const color_image& image, string& error)
     return false;
   }
   fclose(f);
+  return true;
+}
+
+// A JSON array of camera objects with the keys of a scene file's "cameras" entries (ypathtrace --cameras)
+bool load_cameras(const string& filename, vector<camera_data>& cameras, string& error) {
+  cameras.clear();
+  auto data = vector<uint8_t>{};
+  if (!read_file(filename, data, error)) return false;
+  try {
+    auto parser = json_parser{(const char*)data.data(), (const char*)data.data() + data.size()};
+    auto js     = parser.parse();
+    if (js.kind != json_value::array_k || js.items.empty()) throw std::runtime_error{"json"};
+    for (auto& e : js.items) {
+      if (e.kind != json_value::object_k) throw std::runtime_error{"json"};
+      read_camera(e, cameras.emplace_back());
+    }
+  } catch (const std::exception&) {
+    error = filename + ": parse error";
+    return false;
+  }
   return true;
 }
 

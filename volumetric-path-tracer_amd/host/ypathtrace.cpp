@@ -11,7 +11,10 @@
 // --adaptivestep samples until the relative standard error of its mean is within t, never below --adaptivemin samples, at most --samples;
 // the image is written from each pixel's own sample count), --denoise (denoise_render: the guided à-trous filter of include/vpt.h over
 // the finished render, on GPU 0; its guides are --denoiseguides samples of the `normal` and `color` shaders, its variance comes from the two
-// halves of the sample chain, or from the image itself after --adaptive; --denoiseiters and --denoisesigma* set its parameters).
+// halves of the sample chain, or from the image itself after --adaptive; --denoiseiters and --denoisesigma* set its parameters),
+// --cameras FILE (a JSON array of camera objects with the keys of a scene file's "cameras" entries: the scene is loaded and sent to
+// the GPUs once; for entry k the camera --camera selects is replaced in the resident scene through vpt_scene_update, a fresh state is
+// rendered and saved as <stem>.<k, four digits><extension> of --output).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -50,6 +53,7 @@ const std::vector<std::pair<string, option>> options = {
     {"adaptive", {option::float_k, 1, 0, "Adaptive sampling: relative noise at which a pixel stops, 0 = off. (extension)"}},
     {"adaptivemin", {option::int_k, 1, 4096, "Adaptive sampling: fewest samples before a pixel stops. (extension)"}},
     {"adaptivestep", {option::int_k, 1, 4096, "Adaptive sampling: samples per round. (extension)"}},
+    {"cameras", {option::string_k, 1, 0, "Render one frame per camera of this JSON array, the scene staying on the GPU. (extension)"}},
     {"denoise", {option::bool_k, 1, 0, "Denoise the render with the guided a-trous filter. (extension)"}},
     {"denoiseiters", {option::int_k, 1, 8, "Denoising: filter passes, pass k has stride 2^k. (extension)"}},
     {"denoiseguides", {option::int_k, 1, 4096, "Denoising: samples of the normal and albedo guides. (extension)"}},
@@ -200,7 +204,9 @@ int main(int argc, const char** argv) {
     else tesselate_surfaces(scene);
     auto bvh    = gpubvh ? make_bvh_device(scene, params, 0) : make_bvh(scene, params);
     auto lights = make_lights(scene, params);
-    auto state  = make_state(scene, params);
+    auto frames = vector<camera_data>{};   // --cameras: one frame each; else the scene's own camera, once
+    if (values.count("cameras") && !load_cameras(values["cameras"], frames, error)) print_fatal(error);
+    auto base_output = output;
     if (gpus > 1) {
       auto devices = vector<int>{};
       for (auto d = 0; d < gpus; d++) devices.push_back(d);
@@ -218,32 +224,47 @@ int main(int argc, const char** argv) {
           std::chrono::duration<double>(t2 - t1).count(), filter.iterations, variance.empty() ? "spatial" : "half", std::chrono::duration<double>(t3 - t2).count());
       if (!save_image(output, clean, error)) print_fatal(error);
     };
-    auto t0 = std::chrono::steady_clock::now();
-    if (adaptive.threshold > 0) {   // rounds of --adaptivestep samples until every pixel is clean enough or at --samples
-      auto stats = pathtrace_adaptive(state, scene, bvh, lights, params, adaptive);
-      auto secs  = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      auto full  = (double)state.width * state.height * params.samples;
-      printf("adaptive: %d rounds, %lld samples taken of %.0f (%.1f %%) in %.3f s (%.2f Msamples/s)\n", stats.rounds, (long long)stats.samples,
-          full, 100.0 * (double)stats.samples / full, secs, (double)stats.samples / secs * 1e-6);
-      if (denoise) denoise_and_save(get_render_hits(state), {});   // pixels hold their own sample counts: the spatial seed
-      else if (!save_image(output, get_render_hits(state), error)) print_fatal(error);
-      return 0;
+    // one frame: a fresh state of the selected camera rendered as the options say and saved to `output`
+    auto render_frame = [&]() {
+      auto state = make_state(scene, params);
+      auto t0 = std::chrono::steady_clock::now();
+      if (adaptive.threshold > 0) {   // rounds of --adaptivestep samples until every pixel is clean enough or at --samples
+        auto stats = pathtrace_adaptive(state, scene, bvh, lights, params, adaptive);
+        auto secs  = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        auto full  = (double)state.width * state.height * params.samples;
+        printf("adaptive: %d rounds, %lld samples taken of %.0f (%.1f %%) in %.3f s (%.2f Msamples/s)\n", stats.rounds, (long long)stats.samples,
+            full, 100.0 * (double)stats.samples / full, secs, (double)stats.samples / secs * 1e-6);
+        if (denoise) denoise_and_save(get_render_hits(state), {});   // pixels hold their own sample counts: the spatial seed
+        else if (!save_image(output, get_render_hits(state), error)) print_fatal(error);
+        return;
+      }
+      // one launch per `batch` samples (default: all); identical to that many single calls
+      if (batch <= 0) batch = params.samples;
+      // --denoise stops once at half the samples to keep the radiance sums for the half variance (same final state: batching is exact)
+      auto half = denoise ? params.samples / 2 : 0;
+      auto sum_half = vector<vec4f>{};
+      while (state.samples < half) pathtrace_samples(state, scene, bvh, lights, params, std::min(batch, half - state.samples));
+      if (half > 0) sum_half = state.image;
+      while (state.samples < params.samples) pathtrace_samples(state, scene, bvh, lights, params, batch);
+      auto secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      printf("rendered %dx%d x %d spp in %.3f s (%.2f Msamples/s)\n", state.width, state.height, state.samples, secs,
+          (double)state.width * state.height * state.samples / secs * 1e-6);
+      if (denoise) {
+        auto variance = half > 0 ? half_variance(state.width, state.height, sum_half, half, state.image, state.samples, 0) : vector<float>{};
+        denoise_and_save(get_render(state), variance);
+      } else if (!save_image(output, get_render(state), error)) print_fatal(error);
+    };
+    if (frames.empty()) render_frame();
+    for (size_t frame = 0; frame < frames.size(); frame++) {
+      // --cameras: the camera edited in place - pathtrace_samples sends it to the resident scene (vpt_scene_update)
+      scene.cameras[params.camera] = frames[frame];
+      char number[16];
+      snprintf(number, sizeof(number), ".%04d", (int)frame);
+      auto dot = base_output.find_last_of("./\\");
+      auto ext = dot != string::npos && base_output[dot] == '.' ? dot : base_output.size();
+      output   = base_output.substr(0, ext) + number + base_output.substr(ext);
+      render_frame();
     }
-    // one launch per `batch` samples (default: all); identical to that many single calls
-    if (batch <= 0) batch = params.samples;
-    // --denoise stops once at half the samples to keep the radiance sums for the half variance (same final state: batching is exact)
-    auto half = denoise ? params.samples / 2 : 0;
-    auto sum_half = vector<vec4f>{};
-    while (state.samples < half) pathtrace_samples(state, scene, bvh, lights, params, std::min(batch, half - state.samples));
-    if (half > 0) sum_half = state.image;
-    while (state.samples < params.samples) pathtrace_samples(state, scene, bvh, lights, params, batch);
-    auto secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    printf("rendered %dx%d x %d spp in %.3f s (%.2f Msamples/s)\n", state.width, state.height, state.samples, secs,
-        (double)state.width * state.height * state.samples / secs * 1e-6);
-    if (denoise) {
-      auto variance = half > 0 ? half_variance(state.width, state.height, sum_half, half, state.image, state.samples, 0) : vector<float>{};
-      denoise_and_save(get_render(state), variance);
-    } else if (!save_image(output, get_render(state), error)) print_fatal(error);
   } catch (const std::exception& e) {
     print_fatal(e.what());
   }
