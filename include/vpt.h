@@ -510,6 +510,111 @@ int vpt_denoise(const vpt_denoise_params* params, int device, int width, int hei
                 const float* albedo, const float* variance, float* out);
 int vpt_half_variance(int device, int width, int height, const float* sum_a, int a, const float* sum_n, int n, float* variance);
 
+/* ---- progressive rendering: a session whose state, image and display stay on one GPU -----------------------
+ * The headless body of the reference's run_interactive (apps/ypathtrace/ypathtrace.cpp:90-304): reset_display (:144-194), the
+ * worker's frame loop (:180-193) and the edits (:253-266, :292-296), without a window.  Three device stages, then the session.
+ *
+ * vpt_state_init_device: make_state (yocto_pathtrace.cpp:960-980) into this rank's tile-major slots.  The rule, for the pixel with
+ * row-major index idx = j * width + i:
+ *   g   = make_rng(1301081) advanced by idx steps            (the master stream in front of the pixel's draw)
+ *   r   = the PCG32 output of g's state                      (what the (idx + 1)-th _advance_rng returns)
+ *   rng = make_rng(961748941, (r % 2^31) / 2 + 1);  image = 0;  hits = 0
+ * PCG32's state update is an LCG, so "advanced by idx steps" is the jump state' = A^idx state + inc (A^idx - 1) / (A - 1) mod 2^64
+ * (csrc/vpt_rng_jump.h: square-and-multiply, at most 64 rounds): a wave takes one jump to the first pixel of its 8x8 block and every
+ * lane one step of the LCG (A^k, c_k), k = row * width + column inside the block, from a 64-entry table the host makes per call.
+ * Integers only: the bits of the host's make_state followed by vpt_state_upload.  Padding slots and the slots of other ranks are
+ * left as they are, as vpt_state_upload leaves them.  Asynchronous on `stream`; no allocation.
+ *
+ * vpt_tonemap_device: tonemap(vec4f, exposure, filmic, srgb) of yocto_color.h:306-316 over a row-major float4 image, into a float4
+ * display image, an RGBA8 image (float_to_byte, :207-211, of all four channels) or both (either pointer may be null, not both).
+ * The rule, per pixel c, every value float32, every operation in the order written, none fused:
+ *   e = exp2f(exposure), taken once per call on the host     (the reference takes the same value per pixel)
+ *   if exposure != 0:  c.xyz = c.xyz * e
+ *   if filmic:         h = c * 0.6f;  ldr = ((h * h) * 2.51f + h * 0.03f) / (((h * h) * 2.43f + h * 0.59f) + 0.14f);
+ *                      c = (0 < ldr) ? ldr : 0              (x, y, z each; the reference's max in select form: a NaN becomes 0)
+ *   if srgb:           c = (c <= 0.0031308f) ? 12.92f * c : (1 + 0.055f) * powf(c, 1 / 2.4f) - 0.055f     (rgb_to_srgb, :228-231)
+ *   c.w passes through;  byte = clamp(int(c * 256), 0, 255)
+ * Without srgb the stage holds no libm call and gives the bits of the host mirror (tonemap_image of host/vpt_host.h) and of the
+ * reference; with srgb the device's powf stands where they have glibc's, as in vpt_resolve_srgb8_device, whose routine this is:
+ * a byte may differ by one count (DESIGN.md §13 has the measured distances).  Values whose int(a * 256) is undefined in the
+ * reference (not finite, outside int) give what that routine gives.  The accurate-fit branch of tonemap_filmic, which no caller of
+ * the reference reaches, is not restated.
+ *
+ * vpt_upscale_device: the preview replicated to full size (ypathtrace.cpp:164-169):
+ *   out[j * width + i] = preview[min(j / pratio, ph - 1) * pw + min(i / pratio, pw - 1)] */
+typedef struct vpt_display_params {
+  float   exposure;   /* finite                                       */
+  int32_t filmic;     /* 0 / 1                                        */
+  int32_t srgb;       /* 0 / 1; the reference's displays use 1        */
+} vpt_display_params;
+int vpt_state_init_device(const vpt_layout* layout, void* d_image, void* d_hits, void* d_rng, void* stream);
+int vpt_tonemap_device(const vpt_display_params* display, int width, int height, const void* d_linear, void* d_display_f,
+                       void* d_rgba8, void* stream);
+int vpt_upscale_device(int pratio, int pw, int ph, const void* d_preview, int width, int height, void* d_out, void* stream);
+/* vpt_tonemap_device on host arrays: synchronous, on GPU `device`, buffers owned by the call.  Arguments are checked before a device
+ * is looked for (VPT_ERR_INVALID_ARG, the message names the argument); then VPT_ERR_NO_DEVICE without a GPU or for a negative `device`. */
+int vpt_tonemap(const vpt_display_params* display, int device, int width, int height, const float* linear, float* display_f,
+                uint8_t* rgba8);
+/* the resident camera `camera` of a scene (after the edits it has taken) and the device it lives on */
+int vpt_scene_get_camera(vpt_scene* scene, int camera, vpt_camera* out);
+int vpt_scene_get_device(const vpt_scene* scene);
+
+/* A session belongs to one vpt_scene and so to one device.  It owns the tile-major pathtrace_state of a one-rank 8x8 layout, the
+ * preview's state, the row-major linear `image`, the float4 and RGBA8 `display`, a stream, and - with denoise = 1 - the guides,
+ * the variance, the filtered image and the filter's scratch.  Nothing of these crosses PCIe unless a read-out call asks for it.
+ * NOT thread-safe; while a session lives, calls on its scene handle must not overlap with calls on the session.
+ *  vpt_session_create   width / height by make_state's rule from the resident camera (yocto_pathtrace.cpp:964-970); refuses pratio
+ *                       outside 1..64 (the reference's slider) and resolution / pratio < 1 (VPT_ERR_INVALID_ARG), a bad shader
+ *                       (VPT_ERR_UNKNOWN_SHADER).  The session starts as after vpt_session_reset.
+ *  vpt_session_reset    reset_display: the state initialised on the device; the preview - a fresh state of resolution / pratio,
+ *                       samples = 1 (the pixel-centre branch), through vpt_render_device, resolved and replicated into `image`;
+ *                       `display` = tone map of `image`; samples = 0.  With non-null params it adopts them first, and allocates
+ *                       again if the size changes.  With denoise = 1 it also renders the guides: guide_samples passes of `normal`
+ *                       and `color` (`implicit_normal` and no albedo for the implicit shaders, as pathtrace_guides chooses) over
+ *                       states initialised on the device, resolved with vpt_resolve_device.
+ *  vpt_session_advance  min(nsamples, render.samples - samples) passes on the resident state, get_render into `image`, the filter
+ *                       if denoise = 1, the tone map into `display`; a no-op at the cap.  For the implicit shaders it waits for
+ *                       the passes and returns VPT_ERR_HIP when the watchdog fired, as vpt_render does; else it is asynchronous on
+ *                       the session's stream and the read-out calls wait.
+ *  vpt_session_set_display  tone-maps the image held (the filtered one where the display shows it) with the new parameters
+ *                       (ypathtrace.cpp:259-266): nothing renders, state and samples stay.
+ *  vpt_session_edit     vpt_scene_update, then a reset (:292-296); an edit that vpt_scene_update refuses leaves the session as it was.
+ *  read-out             get_display (either pointer nullable: 4 or 16 B per pixel), get_image (the unfiltered linear image),
+ *                       get_denoised (the filtered one; VPT_ERR_INVALID_ARG unless denoise = 1 and an advance has run since the last
+ *                       reset), get_state (the pathtrace_state, row-major), size, samples.
+ *  vpt_session_stats    what the last call on the session cost: kernel launches it enqueued itself (the render and filter entry points
+ *                       it calls count one each), bytes it sent to the device (kernel arguments apart) and bytes it fetched.
+ * Contract: after a reset and advances of k samples in total, get_state returns the bits of make_state + vpt_render(k), in any
+ * batching; after a reset alone, `image` has the bits of the upscale of get_render of a vpt_render preview; `display` is the tone
+ * map of `image`, or with denoise = 1 after an advance of the filtered image: display = tonemap(denoise(image, normal, albedo,
+ * variance)).  The preview frame is never filtered.
+ * Variance rule (denoise = 1): a starts at 0 at a reset.  At the start of an advance that begins at s > 0 samples, if s >= 2 a, the
+ * radiance sums are copied (S_a) and a = s.  After the advance, at n > a samples: variance = vpt_half_variance_device(S_a, a, S_n, n)
+ * if a > 0, else the filter's spatial seed.  The filter, the half variance and the guides are bit-exact, so the filtered image has
+ * the bits of the host pipeline on the same inputs (pathtrace_guides, half_variance, denoise_render). */
+typedef struct vpt_session_params {
+  vpt_params         render;
+  int32_t            pratio;          /* preview ratio, 1..64 (pathtrace_params::pratio, default 8)   */
+  vpt_display_params display;
+  int32_t            denoise;         /* 0 / 1: the display shows the filtered image                  */
+  vpt_denoise_params filter;          /* read when denoise = 1                                        */
+  int32_t            guide_samples;   /* >= 1 when denoise = 1                                        */
+} vpt_session_params;
+typedef struct vpt_session vpt_session;
+int  vpt_session_create(vpt_scene* scene, const vpt_session_params* params, vpt_session** out);
+void vpt_session_destroy(vpt_session* session);
+int  vpt_session_reset(vpt_session* session, const vpt_session_params* params_or_null);
+int  vpt_session_advance(vpt_session* session, int nsamples);
+int  vpt_session_set_display(vpt_session* session, const vpt_display_params* display);
+int  vpt_session_edit(vpt_session* session, const vpt_scene_edit* edit);
+int  vpt_session_get_display(vpt_session* session, uint8_t* rgba8, float* display_f);
+int  vpt_session_get_image(vpt_session* session, float* linear);
+int  vpt_session_get_denoised(vpt_session* session, float* linear);
+int  vpt_session_get_state(vpt_session* session, float* image_rgba, int32_t* hits, uint64_t* rng, int* samples);
+int  vpt_session_size(const vpt_session* session, int* width, int* height);
+int  vpt_session_samples(const vpt_session* session);
+int  vpt_session_stats(const vpt_session* session, int* launches, int64_t* bytes_to_device, int64_t* bytes_to_host);
+
 /* per-launch profile of the last vpt_render_device on this scene (HIP events on `stream`); synchronises with that
  * launch.  Like vpt_render it returns VPT_ERR_HIP if a wave of the implicit kernel gave up on its watchdog (a wave
  * that has not finished after 300 s leaves the kernel instead of holding the GPU: a defect, never a workload). */

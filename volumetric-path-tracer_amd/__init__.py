@@ -57,6 +57,15 @@ class VptDenoise(C.Structure):  # vpt_denoise_params
     _fields_ = [("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float)]
 
 
+class VptDisplay(C.Structure):  # vpt_display_params
+    _fields_ = [("exposure", C.c_float), ("filmic", C.c_int32), ("srgb", C.c_int32)]
+
+
+class VptSessionParams(C.Structure):  # vpt_session_params
+    _fields_ = [("render", VptParams), ("pratio", C.c_int32), ("display", VptDisplay), ("denoise", C.c_int32), ("filter", VptDenoise),
+                ("guide_samples", C.c_int32)]
+
+
 class VptFrame(C.Structure):  # vpt_frame: x, y, z, o
     _fields_ = [("x", C.c_float * 3), ("y", C.c_float * 3), ("z", C.c_float * 3), ("o", C.c_float * 3)]
 
@@ -171,6 +180,17 @@ class PathtraceParams:
 
 
 @dataclass
+class DisplayParams:
+    """vpt_display_params: the tone map of a display (pathtrace_params::exposure, filmic; tonemap's srgb flag)."""
+    exposure: float = 0.0
+    filmic: bool = False
+    srgb: bool = True
+
+    def to_abi(self) -> VptDisplay:
+        return VptDisplay(self.exposure, int(self.filmic), int(self.srgb))
+
+
+@dataclass
 class PathtraceState:
     """pathtrace_state, yocto_pathtrace.h:57-64: row-major host arrays."""
     width: int
@@ -216,6 +236,26 @@ hip.vpt_denoise_device.argtypes = [C.POINTER(VptDenoise), C.c_int, C.c_int, _p, 
 hip.vpt_half_variance_device.argtypes = [C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p, _p]
 hip.vpt_denoise.argtypes = [C.POINTER(VptDenoise), C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p]
 hip.vpt_half_variance.argtypes = [C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
+hip.vpt_state_init_device.argtypes = [C.POINTER(VptLayout), _p, _p, _p, _p]
+hip.vpt_tonemap_device.argtypes = [C.POINTER(VptDisplay), C.c_int, C.c_int, _p, _p, _p, _p]
+hip.vpt_upscale_device.argtypes = [C.c_int, C.c_int, C.c_int, _p, C.c_int, C.c_int, _p, _p]
+hip.vpt_tonemap.argtypes = [C.POINTER(VptDisplay), C.c_int, C.c_int, C.c_int, _p, _p, _p]
+hip.vpt_scene_get_camera.argtypes = [_p, C.c_int, C.POINTER(VptCamera)]
+hip.vpt_scene_get_device.argtypes = [_p]
+hip.vpt_session_create.argtypes = [_p, C.POINTER(VptSessionParams), C.POINTER(_p)]
+hip.vpt_session_destroy.argtypes = [_p]
+hip.vpt_session_destroy.restype = None
+hip.vpt_session_reset.argtypes = [_p, C.POINTER(VptSessionParams)]
+hip.vpt_session_advance.argtypes = [_p, C.c_int]
+hip.vpt_session_set_display.argtypes = [_p, C.POINTER(VptDisplay)]
+hip.vpt_session_edit.argtypes = [_p, C.POINTER(VptSceneEdit)]
+hip.vpt_session_get_display.argtypes = [_p, _p, _p]
+hip.vpt_session_get_image.argtypes = [_p, _p]
+hip.vpt_session_get_denoised.argtypes = [_p, _p]
+hip.vpt_session_get_state.argtypes = [_p, _p, _p, _p, C.POINTER(C.c_int)]
+hip.vpt_session_size.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+hip.vpt_session_samples.argtypes = [_p]
+hip.vpt_session_stats.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
 hip.vpt_last_kernel_ms.argtypes = [_p, C.POINTER(C.c_float)]
 hip.vpt_intersect.argtypes = [_p, C.c_int, _p, C.c_int, _p, _p]
 hip.vpt_build_bvh.argtypes = [C.c_int, _p, C.c_int, _p, C.c_int, C.POINTER(C.c_int), _p]
@@ -266,6 +306,9 @@ host.vpth_scene_rebuild_bvh_device.argtypes = [_p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_build_bvh_host.argtypes = [_p, C.c_int, _p, C.POINTER(C.c_int), _p]
 host.vpth_denoise.argtypes = [C.c_int, C.c_int, _p, _p, _p, _p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _p, C.c_char_p, C.c_int]
 host.vpth_half_variance.argtypes = [C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_char_p, C.c_int]
+host.vpth_tonemap.argtypes = [C.c_int64, _p, C.c_float, C.c_int, C.c_int, _p, _p]
+host.vpth_upscale_preview.argtypes = [C.c_int, C.c_int, C.c_int, _p, C.c_int, C.c_int, _p]
+host.vpth_make_state_jump.argtypes = [C.c_int, C.c_int, _p]
 host.vpth_linear_to_srgb8.argtypes = [C.c_int, C.c_int, _p, C.c_int, _p]
 host.vpth_linear_to_srgb8.restype = None
 host.vpth_encode_jpeg_q75.argtypes = [C.c_int, C.c_int, _p, _p, C.c_int64]
@@ -844,6 +887,162 @@ def denoise_device(width: int, height: int, d_color: int, d_normal: Optional[int
 def half_variance_device(width: int, height: int, d_sum_a: int, a: int, d_sum_n: int, n: int, d_variance: int, stream: int = 0) -> None:
     """vpt_half_variance_device over raw device pointers (row-major float4 sums in, float variance out), asynchronous on `stream`"""
     _check(hip.vpt_half_variance_device(width, height, d_sum_a, a, d_sum_n, n, d_variance, stream), "vpt_half_variance_device")
+
+
+def state_init_device(layout: VptLayout, d_image: int, d_hits: int, d_rng: int, stream: int = 0) -> None:
+    """vpt_state_init_device: make_state into this rank's tile-major slots on the device (raw device pointers), asynchronous"""
+    _check(hip.vpt_state_init_device(C.byref(layout), d_image, d_hits, d_rng, stream), "vpt_state_init_device")
+
+
+def make_state_jump(width: int, height: int) -> np.ndarray:
+    """make_state's rngs, (h, w, 2) uint64, every pixel by a jump of the master stream (csrc/vpt_rng_jump.h, host side)"""
+    out = np.zeros((height, width, 2), np.uint64)
+    if host.vpth_make_state_jump(width, height, out.ctypes.data) != 0:
+        raise VptError("make_state_jump failed")
+    return out
+
+
+def tonemap_image(image: np.ndarray, exposure: float = 0.0, filmic: bool = False, srgb: bool = True, as_bytes: bool = False,
+                  device: Optional[int] = None) -> np.ndarray:
+    """tonemap_image of the reference (yocto_image.h:242-250; rule: include/vpt.h, vpt_tonemap_device) over an (h, w, 4) float32
+    linear image: (h, w, 4) float32, or uint8 through float_to_byte with as_bytes.  device None: the host C++ mirror; else that GPU
+    (vpt_tonemap) - the same bits without srgb, the device's powf with it."""
+    image = _image4(image)
+    h, w, _ = image.shape
+    out = np.zeros((h, w, 4), np.uint8 if as_bytes else np.float32)
+    f, b = (None, out.ctypes.data) if as_bytes else (out.ctypes.data, None)
+    if device is None:
+        if host.vpth_tonemap(h * w, image.ctypes.data, exposure, int(filmic), int(srgb), f, b) != 0:
+            raise VptError("tonemap_image failed")
+    else:
+        par = VptDisplay(exposure, int(filmic), int(srgb))
+        _check(hip.vpt_tonemap(C.byref(par), device, w, h, image.ctypes.data, f, b), "vpt_tonemap")
+    return out
+
+
+def tonemap_device(width: int, height: int, d_linear: int, d_display_f: Optional[int], d_rgba8: Optional[int], display: DisplayParams,
+                   stream: int = 0) -> None:
+    """vpt_tonemap_device over raw device pointers (row-major float4 in; float4 and / or RGBA8 out), asynchronous on `stream`"""
+    par = display.to_abi()
+    _check(hip.vpt_tonemap_device(C.byref(par), width, height, d_linear, d_display_f, d_rgba8, stream), "vpt_tonemap_device")
+
+
+def upscale_preview(preview: np.ndarray, pratio: int, width: int, height: int) -> np.ndarray:
+    """the preview replicated to full size (apps/ypathtrace/ypathtrace.cpp:164-169), host side: (height, width, 4) float32"""
+    preview = _image4(preview)
+    out = np.zeros((height, width, 4), np.float32)
+    if host.vpth_upscale_preview(pratio, preview.shape[1], preview.shape[0], preview.ctypes.data, width, height, out.ctypes.data) != 0:
+        raise VptError("upscale_preview: bad preview, size or ratio")
+    return out
+
+
+def upscale_device(pratio: int, pw: int, ph: int, d_preview: int, width: int, height: int, d_out: int, stream: int = 0) -> None:
+    """vpt_upscale_device over raw device pointers (row-major float4), asynchronous on `stream`"""
+    _check(hip.vpt_upscale_device(pratio, pw, ph, d_preview, width, height, d_out, stream), "vpt_upscale_device")
+
+
+class RenderSession:
+    """vpt_session (include/vpt.h): a progressive render of one camera whose state, linear image and display stay on the GPU of `dev`
+    (a DeviceScene).  reset() is the reference's reset_display (preview included), advance(n) renders n more samples and refreshes the
+    display; display() / image() / state() fetch.  While it lives, `dev` must not be used from another thread."""
+
+    def __init__(self, dev: "DeviceScene", params: PathtraceParams, pratio: int = 8, display: Optional[DisplayParams] = None,
+                 denoise: bool = False, guide_samples: int = 16, iterations: int = DENOISE_ITERATIONS,
+                 sigma_luminance: float = DENOISE_SIGMA_LUMINANCE, sigma_normal: float = DENOISE_SIGMA_NORMAL,
+                 sigma_albedo: float = DENOISE_SIGMA_ALBEDO):
+        self.dev, self.handle = dev, None
+        self._filter = VptDenoise(iterations, sigma_luminance, sigma_normal, sigma_albedo)
+        abi = self._abi(params, pratio, display or DisplayParams(), denoise, guide_samples)
+        out = _p()
+        _check(hip.vpt_session_create(dev.handle, C.byref(abi), C.byref(out)), "vpt_session_create")
+        self.handle = out
+
+    def _abi(self, params, pratio, display, denoise, guide_samples) -> VptSessionParams:
+        self.params, self.pratio, self.display_params, self.denoise, self.guide_samples = params, pratio, display, denoise, guide_samples
+        return VptSessionParams(params.to_abi(), pratio, display.to_abi(), int(denoise), self._filter, guide_samples)
+
+    def reset(self, params: Optional[PathtraceParams] = None, pratio: Optional[int] = None, display: Optional[DisplayParams] = None,
+              denoise: Optional[bool] = None, guide_samples: Optional[int] = None) -> None:
+        """reset_display; any argument given replaces the session's (a new size re-allocates)"""
+        if params is None and pratio is None and display is None and denoise is None and guide_samples is None:
+            _check(hip.vpt_session_reset(self.handle, None), "vpt_session_reset")
+            return
+        pick = lambda new, old: old if new is None else new
+        old = (self.params, self.pratio, self.display_params, self.denoise, self.guide_samples)
+        abi = self._abi(pick(params, old[0]), pick(pratio, old[1]), pick(display, old[2]), pick(denoise, old[3]), pick(guide_samples, old[4]))
+        rc = hip.vpt_session_reset(self.handle, C.byref(abi))
+        if rc != 0:
+            self.params, self.pratio, self.display_params, self.denoise, self.guide_samples = old
+        _check(rc, "vpt_session_reset")
+
+    def advance(self, nsamples: int = 1) -> int:
+        """min(nsamples, params.samples - samples) more samples, then image and display; returns the samples reached"""
+        _check(hip.vpt_session_advance(self.handle, nsamples), "vpt_session_advance")
+        return self.samples
+
+    def set_display(self, display: DisplayParams) -> None:
+        """tone-maps the image held again; nothing renders"""
+        abi = display.to_abi()
+        _check(hip.vpt_session_set_display(self.handle, C.byref(abi)), "vpt_session_set_display")
+        self.display_params = display
+
+    def edit(self, edit: SceneEdit) -> None:
+        """vpt_scene_update on the session's scene with the SceneEdit of HostScene.update_bvh(), then a reset; a refused edit
+        leaves the session as it was"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_session_edit(self.handle, C.byref(abi)), "vpt_session_edit")
+        del keep
+
+    @property
+    def size(self):
+        w, h = C.c_int(), C.c_int()
+        _check(hip.vpt_session_size(self.handle, C.byref(w), C.byref(h)), "vpt_session_size")
+        return w.value, h.value
+
+    @property
+    def samples(self) -> int:
+        return hip.vpt_session_samples(self.handle)
+
+    def display(self, as_bytes: bool = True) -> np.ndarray:
+        """the display: (h, w, 4) uint8 (4 B per pixel fetched) or, with as_bytes False, float32 (16 B)"""
+        w, h = self.size
+        out = np.zeros((h, w, 4), np.uint8 if as_bytes else np.float32)
+        _check(hip.vpt_session_get_display(self.handle, out.ctypes.data if as_bytes else None, None if as_bytes else out.ctypes.data),
+               "vpt_session_get_display")
+        return out
+
+    def image(self, denoised: bool = False) -> np.ndarray:
+        """the linear image (the preview after a reset, get_render after an advance), unfiltered; denoised: the filtered one"""
+        w, h = self.size
+        out = np.zeros((h, w, 4), np.float32)
+        if denoised:
+            _check(hip.vpt_session_get_denoised(self.handle, out.ctypes.data), "vpt_session_get_denoised")
+        else:
+            _check(hip.vpt_session_get_image(self.handle, out.ctypes.data), "vpt_session_get_image")
+        return out
+
+    def state(self) -> PathtraceState:
+        w, h = self.size
+        st = PathtraceState(w, h, 0, np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.int32), np.zeros((h, w, 2), np.uint64))
+        n = C.c_int(0)
+        _check(hip.vpt_session_get_state(self.handle, st.image.ctypes.data, st.hits.ctypes.data, st.rngs.ctypes.data, C.byref(n)),
+               "vpt_session_get_state")
+        st.samples = n.value
+        return st
+
+    def stats(self):
+        """(kernel launches, bytes to the device, bytes to the host) of the last call on the session"""
+        n, up, down = C.c_int(0), C.c_int64(0), C.c_int64(0)
+        _check(hip.vpt_session_stats(self.handle, C.byref(n), C.byref(up), C.byref(down)), "vpt_session_stats")
+        return n.value, up.value, down.value
+
+    def close(self) -> None:
+        if getattr(self, "handle", None) and hip is not None:
+            hip.vpt_session_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        self.close()
 
 
 def selftest_reciprocal(device: int = 0):

@@ -626,6 +626,16 @@ int vpt_render_device(vpt_scene* s, const vpt_params* params, const vpt_layout* 
   return VPT_OK;
 }
 
+// the resident camera, for callers that size a frame from it (vpt_session, vpt_session.hip)
+int vpt_scene_get_camera(vpt_scene* s, int camera, vpt_camera* out) {
+  if (!s || !out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (camera < 0 || camera >= s->d.num_cameras) return vpt_set_error(VPT_ERR_INVALID_ARG, "camera %d out of range", camera);
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipMemcpy(out, s->d.cameras + camera, sizeof(vpt_camera), hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+int vpt_scene_get_device(const vpt_scene* s) { return s ? s->device : vpt_set_error(VPT_ERR_INVALID_ARG, "null argument"); }
+
 int vpt_scene_record_bytes(const vpt_scene* s, int* leaf_bytes, int* attribute_bytes) {
   if (!s || !leaf_bytes || !attribute_bytes) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   *leaf_bytes = s->d.tri_prims ? 48 : 64, *attribute_bytes = s->d.tri_attrs ? 64 : 96;

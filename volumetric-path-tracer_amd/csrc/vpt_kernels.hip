@@ -1,6 +1,7 @@
 // vpt_kernels.hip — the kernels outside K1 and K2 (declared in vpt_launch.h): vpt_intersect, the known-answer-test kernel and the
 // self-tests, the light setup of vpt_scene_create, the launch schedule's cost average, and the elementwise state kernels.
 #include "vpt_kat_kernels.hip.h"
+#include "vpt_srgb.hip.h"
 
 // vpt_kat (vpt_kat_kernels.hip.h)
 template __global__ void vpt_kat_kernel<true>(DScene, int, int, int, int, int, const float*, const int*, float*, stack_cfg, int);
@@ -120,10 +121,8 @@ __global__ void vpt_resolve_kernel(DParams pr, const float4* tiles_all, float sc
 }
 
 // The output stage of a preview on the device: get_render (cpp:1105-1116) followed by rgb_to_srgb
-// (yocto_color.h:228-231) and float_to_byte (:207-211, clamp(int(a * 256), 0, 255)); alpha is quantised
-// linearly, as save_image does.  powf is ocml's here and glibc's in the reference: a byte can differ by one
-// where the curve lands within an ulp of a multiple of 1/256 (the parity pipeline keeps using the host
-// routine, vpth_linear_to_srgb8).
+// (yocto_color.h:228-231) and float_to_byte (:207-211), both in vpt_srgb.hip.h; alpha is quantised
+// linearly, as save_image does.
 __global__ void vpt_resolve_srgb8_kernel(DParams pr, const float4* tiles_all, float scale, uchar4* rows_rgba8) {
   int g = blockIdx.x * blockDim.x + threadIdx.x;   // global slot over all ranks
   if (g >= pr.nslots * pr.nranks) return;
@@ -132,11 +131,6 @@ __global__ void vpt_resolve_srgb8_kernel(DParams pr, const float4* tiles_all, fl
   int px, py;
   if (!slot_to_pixel(q, g - q.rank * pr.nslots, px, py)) return;
   float4 v = tiles_all[g];
-  auto curve = [](float rgb) { return (rgb <= 0.0031308f) ? 12.92f * rgb : (1 + 0.055f) * powf(rgb, 1 / 2.4f) - 0.055f; };
-  auto quant = [](float a) {
-    int b = (int)(a * 256);
-    return (unsigned char)(b < 0 ? 0 : (b > 255 ? 255 : b));
-  };
   rows_rgba8[(long long)py * pr.width + px] =
-      make_uchar4(quant(curve(v.x * scale)), quant(curve(v.y * scale)), quant(curve(v.z * scale)), quant(v.w * scale));
+      make_uchar4(srgb_quant(srgb_curve(v.x * scale)), srgb_quant(srgb_curve(v.y * scale)), srgb_quant(srgb_curve(v.z * scale)), srgb_quant(v.w * scale));
 }

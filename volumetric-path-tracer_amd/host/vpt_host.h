@@ -275,6 +275,48 @@ struct denoise_guides {
 denoise_guides pathtrace_guides(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights, const pathtrace_params& params,
     int samples = 16);
 
+// ---- display: tone mapping, the preview, progressive sessions (include/vpt.h: vpt_session) ---------------------
+// tonemap_image of the reference (yocto_image.h:242-250, yocto_image.cpp:877-888): tonemap(hdr, exposure, filmic, srgb) of
+// yocto_color.h:306-316 per pixel, to floats or through float_to_byte (:207-211) to bytes.  Host arithmetic in the reference's order -
+// the restatement vpt_tonemap_device is held to (bit for bit without srgb; with it the device's powf differs from libm's by ulps).
+void tonemap_image(vector<vec4f>& ldr, const vector<vec4f>& hdr, float exposure, bool filmic = false, bool srgb = true);
+void tonemap_image(vector<vec4b>& ldr, const vector<vec4f>& hdr, float exposure, bool filmic = false, bool srgb = true);
+// the preview replicated to full size (apps/ypathtrace/ypathtrace.cpp:164-169): out[j * width + i] = preview[min(j / pratio, ph - 1)][min(i / pratio, pw - 1)]
+void upscale_preview(color_image& out, const color_image& preview, int pratio, int width, int height);
+// make_state's rngs for a width x height frame, every pixel by a jump of the master stream (csrc/vpt_rng_jump.h, which the kernel of
+// vpt_state_init_device compiles too) instead of make_state's sequential draws: the same bits.  For the tests; make_state stays as it is.
+vector<rng_state> make_state_rngs_jump(int width, int height);
+// A progressive render of one camera on one GPU: vpt_session over the scene flattened and sent to `device` once.  reset() is the
+// reference's reset_display (preview included), advance(n) n more samples and a fresh display; nothing but what display() / image() /
+// state() fetch crosses PCIe.  Every member throws std::runtime_error with vpt_last_error() where the C-ABI fails.
+struct render_session_params {
+  pathtrace_params render   = {};   // pratio, exposure and filmic are read here
+  bool             denoise  = false;
+  denoise_params   filter   = {};
+  int              guide_samples = 16;
+};
+class render_session {
+ public:
+  render_session(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights, const render_session_params& params, int device = 0);
+  ~render_session();
+  render_session(const render_session&)            = delete;
+  render_session& operator=(const render_session&) = delete;
+  void reset();
+  void reset(const render_session_params& params);
+  void advance(int nsamples);
+  void set_display(float exposure, bool filmic);
+  int  width() const;
+  int  height() const;
+  int  samples() const;
+  vector<vec4b>   display();                 // RGBA8, the device's tone map
+  color_image     image(bool denoised = false);   // the linear image (get_render or the preview); denoised: the filtered one
+  pathtrace_state state();
+
+ private:
+  vpt_scene*   scene_   = nullptr;
+  vpt_session* session_ = nullptr;
+};
+
 // ---- flattening to the C-ABI ----------------------------------------------------------------
 struct flat_scene {
   vpt_scene_desc desc = {};

@@ -373,6 +373,47 @@ int vpth_half_variance(int width, int height, const float* sum_a, int a, const f
     return set_error(err, errlen, e.what()), -1;
   }
 }
+// tonemap_image on a row-major float4 image of n pixels: floats to display_f and / or bytes to rgba8 (either may be null)
+int vpth_tonemap(int64_t n, const float* linear, float exposure, int filmic, int srgb, float* display_f, uint8_t* rgba8) {
+  if (n < 0 || !linear || (!display_f && !rgba8)) return -1;
+  auto hdr = vector<vec4f>((const vec4f*)linear, (const vec4f*)linear + n);
+  if (display_f) {
+    auto ldr = vector<vec4f>{};
+    tonemap_image(ldr, hdr, exposure, filmic != 0, srgb != 0);
+    memcpy(display_f, ldr.data(), (size_t)n * 16);
+  }
+  if (rgba8) {
+    auto ldr = vector<vec4b>{};
+    tonemap_image(ldr, hdr, exposure, filmic != 0, srgb != 0);
+    memcpy(rgba8, ldr.data(), (size_t)n * 4);
+  }
+  return 0;
+}
+// the preview (pw x ph float4) replicated into out (width x height float4)
+int vpth_upscale_preview(int pratio, int pw, int ph, const float* preview, int width, int height, float* out) {
+  try {
+    if (pw < 1 || ph < 1 || !preview || !out) return -1;
+    auto src = color_image{pw, ph, true, {}};
+    src.pixels.assign((const vec4f*)preview, (const vec4f*)preview + (size_t)pw * ph);
+    auto dst = color_image{};
+    upscale_preview(dst, src, pratio, width, height);
+    memcpy(out, dst.pixels.data(), dst.pixels.size() * 16);
+    return 0;
+  } catch (...) {
+    return -1;
+  }
+}
+// make_state's rngs {state, inc} of a width x height frame by jumps of the master stream (csrc/vpt_rng_jump.h)
+int vpth_make_state_jump(int width, int height, uint64_t* rng) {
+  try {
+    if (!rng) return -1;
+    auto rngs = make_state_rngs_jump(width, height);
+    memcpy(rng, rngs.data(), rngs.size() * 16);
+    return 0;
+  } catch (...) {
+    return -1;
+  }
+}
 // returns the encoded size; call with out == nullptr to query
 int64_t vpth_encode_jpeg_q75(int width, int height, const uint8_t* rgba8, uint8_t* out, int64_t outlen) {
   auto px = vector<vec4b>((size_t)width * height);

@@ -14,7 +14,11 @@
 // halves of the sample chain, or from the image itself after --adaptive; --denoiseiters and --denoisesigma* set its parameters),
 // --cameras FILE (a JSON array of camera objects with the keys of a scene file's "cameras" entries: the scene is loaded and sent to
 // the GPUs once; for entry k the camera --camera selects is replaced in the resident scene through vpt_scene_update, a fresh state is
-// rendered and saved as <stem>.<k, four digits><extension> of --output).
+// rendered and saved as <stem>.<k, four digits><extension> of --output), --progressive N (the headless body of the reference's
+// run_interactive, through a vpt_session on GPU 0: the preview of --pratio is written as <stem>.000000<extension>, the device's display after
+// every N samples as <stem>.<samples, six digits><extension>, the finished image as --output; --exposure and --filmic are the display's
+// tone-mapping parameters; with --denoise the display shows the filtered image.  With --exposure 0 and without --filmic, --output holds
+// the bytes of the offline run with the same arguments: the same state, the same host 8-bit stage).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -30,7 +34,7 @@ using namespace vpt;
 namespace {
 
 struct option {
-  enum kind_t { string_k, int_k, bool_k, shader_k, float_k, posfloat_k } kind;   // float_k: finite and >= 0; posfloat_k: finite and > 0
+  enum kind_t { string_k, int_k, bool_k, shader_k, float_k, posfloat_k, anyfloat_k } kind;   // float_k: finite and >= 0; posfloat_k: finite and > 0; anyfloat_k: finite
   int         lo, hi;   // int_k: inclusive range (lo > hi: unbounded)
   const char* usage;
 };
@@ -60,6 +64,10 @@ const std::vector<std::pair<string, option>> options = {
     {"denoisesigmalum", {option::posfloat_k, 1, 0, "Denoising: luminance tolerance in standard deviations. (extension)"}},
     {"denoisesigmanormal", {option::posfloat_k, 1, 0, "Denoising: tolerance of the normal guide. (extension)"}},
     {"denoisesigmaalbedo", {option::posfloat_k, 1, 0, "Denoising: tolerance of the albedo guide. (extension)"}},
+    {"progressive", {option::int_k, 1, 4096, "Render progressively on the GPU, a display frame every N samples. (extension)"}},
+    {"pratio", {option::int_k, 1, 64, "Progressive: preview ratio."}},
+    {"exposure", {option::anyfloat_k, 1, 0, "Progressive: display exposure."}},
+    {"filmic", {option::bool_k, 1, 0, "Progressive: filmic tone mapping."}},
 };
 const option* find_option(const string& name) {
   for (auto& [n, o] : options)
@@ -72,7 +80,7 @@ string usage() {
   for (auto& [name, o] : options) {
     auto line = "  --" + name + (o.kind == option::bool_k  ? "/--no-" + name
                                  : o.kind == option::int_k ? " <integer>"
-                                 : o.kind == option::float_k || o.kind == option::posfloat_k ? " <float>"
+                                 : o.kind == option::float_k || o.kind == option::posfloat_k || o.kind == option::anyfloat_k ? " <float>"
                                                              : " <string>");
     line.resize(line.size() < 32 ? 32 : line.size() + 1, ' ');
     text += line + o.usage + "\n";
@@ -109,6 +117,10 @@ void check_value(const string& name, const option& o, const string& text) {
     auto end = (char*)nullptr;
     auto v   = strtof(text.c_str(), &end);
     if (end == text.c_str() || *end != 0 || !std::isfinite(v) || !(v > 0)) cli_error("bad value for " + name);
+  } else if (o.kind == option::anyfloat_k) {
+    auto end = (char*)nullptr;
+    auto v   = strtof(text.c_str(), &end);
+    if (end == text.c_str() || *end != 0 || !std::isfinite(v)) cli_error("bad value for " + name);
   } else if (o.kind == option::bool_k) {
     if (text != "true" && text != "false") cli_error("bad value for " + name);
   } else if (o.kind == option::shader_k) {
@@ -191,6 +203,15 @@ int main(int argc, const char** argv) {
   get_float("denoisesigmalum", filter.sigma_luminance), get_float("denoisesigmanormal", filter.sigma_normal);
   get_float("denoisesigmaalbedo", filter.sigma_albedo);
   if (interactive) print_fatal("--interactive is not supported by the GPU build");
+  auto progressive = 0;
+  get_int("progressive", progressive), get_int("pratio", params.pratio), get_float("exposure", params.exposure), get_bool("filmic", params.filmic);
+  if (!progressive)
+    for (auto name : {"exposure", "filmic", "pratio"})
+      if (values.count(name)) cli_error(string{"option "} + name + " needs --progressive");
+  if (progressive && gpus > 1) cli_error("option progressive renders on one GPU: it cannot be combined with gpus " + std::to_string(gpus));
+  if (progressive && adaptive.threshold > 0) cli_error("option progressive cannot be combined with adaptive");
+  if (progressive && values.count("cameras")) cli_error("option progressive cannot be combined with cameras");
+  if (progressive && params.resolution / params.pratio < 1) cli_error("bad value for pratio");
   if (values.count("shader"))
     for (size_t k = 0; k < pathtrace_shader_names.size(); k++)
       if (pathtrace_shader_names[k] == values["shader"]) params.shader = (pathtrace_shader_type)k;
@@ -254,6 +275,44 @@ int main(int argc, const char** argv) {
         denoise_and_save(get_render(state), variance);
       } else if (!save_image(output, get_render(state), error)) print_fatal(error);
     };
+    // --progressive: reset_display and the worker's loop of run_interactive on a session; the displays are the device's
+    auto numbered = [&](int number) {
+      char text[16];
+      snprintf(text, sizeof(text), ".%06d", number);
+      auto dot = base_output.find_last_of("./\\");
+      auto ext = dot != string::npos && base_output[dot] == '.' ? dot : base_output.size();
+      return base_output.substr(0, ext) + text + base_output.substr(ext);
+    };
+    auto save_display = [&](render_session& session, const string& name) {
+      auto bytes = session.display();
+      auto ldr   = color_image{session.width(), session.height(), false, {}};
+      ldr.pixels.resize(bytes.size());
+      auto unit = [](uint8_t b) { return ((float)b + 0.5f) / 256; };   // save_image quantises it back to b
+      for (size_t i = 0; i < bytes.size(); i++) ldr.pixels[i] = {unit(bytes[i].x), unit(bytes[i].y), unit(bytes[i].z), unit(bytes[i].w)};
+      if (!save_image(name, ldr, error)) print_fatal(error);
+    };
+    if (progressive) {
+      auto sp = render_session_params{params, denoise, filter, guide_samples};
+      auto t0 = std::chrono::steady_clock::now();
+      auto session = render_session{scene, bvh, lights, sp, 0};
+      save_display(session, numbered(0));
+      auto shown = 0;
+      while (session.samples() < params.samples) {
+        session.advance(progressive);
+        save_display(session, numbered(session.samples())), shown++;
+      }
+      auto secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      printf("rendered %dx%d x %d spp progressively in %.3f s (preview 1/%d, %d display frames)\n", session.width(), session.height(),
+          session.samples(), secs, params.pratio, shown);
+      auto image = session.image(denoise);
+      if (params.exposure != 0 || params.filmic) {   // the host tone map; else the offline path's own 8-bit stage
+        auto mapped = color_image{image.width, image.height, false, {}};
+        tonemap_image(mapped.pixels, image.pixels, params.exposure, params.filmic, true);
+        image = mapped;
+      }
+      if (!save_image(output, image, error)) print_fatal(error);
+      return 0;
+    }
     if (frames.empty()) render_frame();
     for (size_t frame = 0; frame < frames.size(); frame++) {
       // --cameras: the camera edited in place - pathtrace_samples sends it to the resident scene (vpt_scene_update)
