@@ -70,6 +70,10 @@ int vpt_spheretrace(vpt_scene* scene, int n, const float* rays, int sdf, int max
 /* VPT_KAT_LOBES with its record layout. */
 int vpt_eval_lobes(vpt_scene* scene, int n, const float* in19, float* out22);
 
+/* The tile-splitting policy (include/vpt.h) on `ntiles` per-tile costs of an unsplit launch, on the host: no device is touched.
+ * k_out[t]: tile t runs as 2^k waves; *waves_out: waves of the launch that results (ntiles when no tile is split). */
+int vpt_split_plan(int kernel /* 0: K1, 1: K2 */, const unsigned* costs, int ntiles, int wave_slots, int forced_k /* -1: the policy */, int* k_out, int* waves_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Tile splitting (vpt_capi.hip): one virtual rank of an N-GPU job on this GPU.
+"""Tile splitting (vpt_schedule.hip, vpt_split_policy.cpp): one virtual rank of an N-GPU job on this GPU.
   split_calibration.py <nranks> <spp> [rank [scene file [shader [bounces [resolution]]]]]   -> kernel ms, longest wave, slot time of the steady-state launch, state hash
 Environment: VPT_SPLIT (0 / 1), VPT_SPLIT_K (force every tile to 2^k waves)."""
 import hashlib

@@ -1,4 +1,4 @@
-"""Tile splitting (include/vpt.h, vpt_capi.hip): when a layout shares the frame among ranks, the mesh kernels run the
+"""Tile splitting (include/vpt.h, vpt_schedule.hip, vpt_split_policy.cpp): when a layout shares the frame among ranks, the mesh kernels run the
 costliest tiles as several partly filled waves so that a launch is not as long as its costliest tile.  It is a change of
 schedule only: every pixel keeps its own RNG stream and accumulator, so the state must be bit-identical with and without
 it - checked here on one GPU with virtual ranks and with small frames, across the call in which the decision is taken (call 1: pilot + unsplit

@@ -281,6 +281,7 @@ hip.vpt_kat_strides.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 hip.vpt_kat.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, _p]
 hip.vpt_spheretrace.argtypes = [_p, C.c_int, _p, C.c_int, C.c_int, _p, _p]
 hip.vpt_eval_lobes.argtypes = [_p, C.c_int, _p, _p]
+hip.vpt_split_plan.argtypes = [C.c_int, _p, C.c_int, C.c_int, C.c_int, _p, C.POINTER(C.c_int)]
 host.vpth_scene_load.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
 host.vpth_scene_load.restype = _p
 host.vpth_scene_load_ex.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int]

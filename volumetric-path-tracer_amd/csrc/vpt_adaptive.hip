@@ -153,9 +153,8 @@ int adaptive_update(const DParams& pr, const float4* image, const int* hits, con
 extern "C" int vpt_resolve_hits_device(const vpt_layout* layout, const void* d_tiles_all_ranks, const void* d_hits_all_ranks,
     void* d_image_rowmajor, void* stream) {
   if (!layout || !d_tiles_all_ranks || !d_hits_all_ranks || !d_image_rowmajor) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  DParams    pr;
-  vpt_params dummy = {};
-  if (int rc = vpt_make_dparams(&dummy, layout, 0, pr)) return rc;
+  DParams pr;
+  if (int rc = vpt_layout_dparams(layout, pr)) return rc;
   long long total = (long long)pr.nslots * pr.nranks;
   if (total >= (1LL << 31)) return vpt_set_error(VPT_ERR_INVALID_ARG, "image too large");
   hipLaunchKernelGGL(vpt_resolve_hits_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pr,

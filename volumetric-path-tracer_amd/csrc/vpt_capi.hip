@@ -1,6 +1,6 @@
 // vpt_capi.hip — implementation of the C-ABI in include/vpt.h: upload of the scene tables vpt_scene_prep.cpp builds
 // (the device layout of vpt_device.h), kernel launches, state movement.  The kernels are declared in vpt_launch.h and
-// compiled in the kernel units it lists; this unit holds none of their bodies (only rocPRIM's sort is compiled here).
+// compiled in the kernel units it lists; this unit holds none of their bodies.  The launch schedule is vpt_schedule.hip's.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see __graft_entry__.py).
 // There is NO CPU fallback in this library: without a gfx950 device every compute entry point
 // fails with VPT_ERR_NO_DEVICE.
@@ -10,18 +10,15 @@
 #include <cstring>
 #include <algorithm>
 #include <type_traits>
-#include <queue>
-#include <functional>
 #include <string>
 #include <vector>
-
-#include <rocprim/rocprim.hpp>
 
 #include "vpt_adaptive.h"
 #include "vpt_device_buffer.h"
 #include "vpt_error.h"
 #include "vpt_kat.h"
 #include "vpt_launch.h"
+#include "vpt_schedule.h"
 #include "vpt_scene_prep.h"
 #include "vpt_scene_update.h"
 
@@ -40,6 +37,11 @@ int vpt_set_error(int code, const char* fmt, ...) {
   return code;
 }
 
+// the image / hits / rng arrays of a pathtrace state on the device: in tile-major slots (what the kernels render into) or as
+// row-major pixels (what the host holds); two types, so that the two cannot be swapped in a call
+struct tile_state { void *image, *hits, *rng; };
+struct row_state { void *image, *hits, *rng; };
+
 struct vpt_scene {
   int                        device = 0;
   DScene                     d      = {};
@@ -48,36 +50,12 @@ struct vpt_scene {
   int                        stack_lds4 = 8, stack_spill4 = 0;   // quad-node traversal: (ref, t0) entries in LDS / in HBM
   device_buffer              spill;
   long long                  spill_lanes = 0;
-  // launch schedule of the mesh kernel (sched_cfg): per-wave cost of the last launch, waves by descending cost
-  device_buffer d_cost, d_cost_sorted, d_cost_key;   // unsigned
-  device_buffer d_cost_avg;            // float: running average of a wave's duration per sample (vpt_cost_average_kernel)
-  float         cost_weight = 0;       // samples behind that average (0: none yet)
-  device_buffer d_order, d_iota;       // int
-  hipEvent_t  ev_order = nullptr;       // recorded after the sort that writes d_order
-  hipStream_t order_stream = nullptr;   // the stream that sort ran on
-
-  device_buffer sort_temp;
-  size_t        sort_temp_bytes = 0;
-  // tile splitting (launch_mesh): tiles whose pixels run as 2^k partly filled waves, so that a launch is not as long as its costliest tile
-  device_buffer d_lane_slot;   // int
-  long long lane_cap = 0;
-  int       split_waves = 0, split_tiles = 0;   // waves of the split launch (0: no table), tiles that were split
-  std::vector<int> h_split_k;                   // per tile: it runs as 2^k waves
-  bool      full_costs = false;                 // d_cost holds per-tile durations of an unsplit launch over >= 8 samples
-  int       wave_slots_k1 = 3072;               // wave slots of the chip for K1 (CUs x 4 SIMDs x 3)
-  int       wave_slots_k2 = 5120;               // ... for K2 (x VPT_K2_WAVES)
-  bool      split_decided = false;              // the decision for sched_key has been taken (costs of an unsplit launch were available)
-  int       last_waves = 0;                     // grid of the last kernel launch (vpt_last_wave_costs)
-  long long sched_waves = 0;       // waves the buffers are sized for
-  bool      order_valid = false;   // d_order describes the layout of sched_key
-  long long sched_key[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  launch_schedule sched;   // per-wave costs, launch order, tile splitting (vpt_schedule.h)
   // staging for the host-state entry point vpt_render()
   device_buffer s_image, s_hits, s_rng;   // tile-major state
   device_buffer r_image, r_hits, r_rng;   // row-major mirror
   long long  staged_pixels = 0, staged_slots = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t ev_host0 = nullptr, ev_host1 = nullptr;   // around a host-side pause inside a call (decide_split): not kernel time
-  bool       host_pause = false;                       // the last call recorded that pair
   bool       timed = false;
   device_buffer d_watchdog;   // unsigned: waves of the implicit kernel that gave up (must stay 0; vpt_implicit_kernel.hip.h)
   int        light_features = 0;      // VPT_FEAT_* bits this scene's lights need from the mesh kernels
@@ -131,7 +109,10 @@ int light_setup(vpt_scene* s) {
 
 }  // namespace
 
-int vpt_make_dparams(const vpt_params* p, const vpt_layout* l, int nsamples, DParams& out) { return make_dparams(p, l, nsamples, out); }
+int vpt_layout_dparams(const vpt_layout* l, DParams& out) {
+  vpt_params none = {};
+  return make_dparams(&none, l, 0, out);
+}
 
 extern "C" {
 
@@ -147,7 +128,7 @@ int vpt_device_count(void) {
 void vpt_scene_destroy(vpt_scene* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);   // the scene's buffers are freed on its device when it goes
-  for (hipEvent_t e : {s->ev_order, s->ev0, s->ev1, s->ev_host0, s->ev_host1, s->upd.ev0, s->upd.ev1})
+  for (hipEvent_t e : {s->ev0, s->ev1, s->upd.ev0, s->upd.ev1})
     if (e) (void)hipEventDestroy(e);
   delete s;
 }
@@ -195,13 +176,11 @@ int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* 
   s->h = std::move(t.h);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
-  s->wave_slots_k1 = prop.multiProcessorCount * 4 * VPT_WAVES_PER_SIMD;
-  s->wave_slots_k2 = prop.multiProcessorCount * 4 * VPT_K2_WAVES;
+  s->sched.compute_units = prop.multiProcessorCount;
   if ((rc = light_setup(s)) != VPT_OK) return rc;
-  for (hipEvent_t* e : {&s->ev0, &s->ev1, &s->ev_host0, &s->ev_host1}) HIP_TRY(hipEventCreate(e));
+  for (hipEvent_t* e : {&s->ev0, &s->ev1}) HIP_TRY(hipEventCreate(e));
   if ((rc = s->d_watchdog.allocate(4)) != VPT_OK) return rc;
   HIP_TRY(hipMemset(s->d_watchdog.get(), 0, 4));
-  HIP_TRY(hipEventCreateWithFlags(&s->ev_order, hipEventDisableTiming));
   HIP_TRY(hipDeviceSynchronize());
   *out = s;
   s    = nullptr;   // release the guard
@@ -209,70 +188,44 @@ int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* 
 }
 
 int64_t vpt_layout_slots(const vpt_layout* layout) {
-  DParams   pr;
-  vpt_params dummy = {};
-  if (make_dparams(&dummy, layout, 0, pr) != VPT_OK) return -1;
+  DParams pr;
+  if (vpt_layout_dparams(layout, pr) != VPT_OK) return -1;
   return pr.nslots;
 }
 
-static int permute(const vpt_layout* layout, int to_tiles, void* t_image, void* t_hits, void* t_rng, void* r_image,
-    void* r_hits, void* r_rng, hipStream_t stream) {
-  DParams    pr;
-  vpt_params dummy = {};
-  if (int rc = make_dparams(&dummy, layout, 0, pr)) return rc;
-  int blocks = (pr.nslots + 255) / 256;
-  hipLaunchKernelGGL(vpt_permute_kernel, dim3(blocks), dim3(256), 0, stream, pr, to_tiles, (float4*)t_image, (int*)t_hits,
-      (ulonglong2*)t_rng, (float4*)r_image, (int*)r_hits, (ulonglong2*)r_rng);
+// The host <-> tile-major conversions go through a row-major device copy of the frame: `staged` (the scene handle's in vpt_render,
+// allocated once per frame size; on a download it still holds the uploaded frame), else allocated for the call and, on a download,
+// filled from the caller's arrays so that pixels owned by other ranks keep their values.  The host arrays are written only when !to_tiles.
+static int move_state(const vpt_layout* layout, bool to_tiles, float* image_rgba, int32_t* hits, uint64_t* rng, tile_state t,
+    const row_state* staged, hipStream_t st) {
+  if (!layout || !image_rgba || !hits || !rng || !t.image || !t.hits || !t.rng) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (layout->width <= 0 || layout->height <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad layout");
+  const size_t  n = (size_t)layout->width * layout->height;
+  device_buffer r_image, r_hits, r_rng;
+  if (!staged && (r_image.allocate(n * 16) || r_hits.allocate(n * 4) || r_rng.allocate(n * 16))) return VPT_ERR_HIP;
+  const row_state r = staged ? *staged : row_state{r_image.get(), r_hits.get(), r_rng.get()};
+  const struct { void *rows, *host; size_t bytes; } parts[3] = {{r.image, image_rgba, n * 16}, {r.hits, hits, n * 4}, {r.rng, rng, n * 16}};
+  if (to_tiles || !staged)
+    for (const auto& p : parts) HIP_TRY(hipMemcpyAsync(p.rows, p.host, p.bytes, hipMemcpyHostToDevice, st));
+  DParams pr;
+  if (int rc = vpt_layout_dparams(layout, pr)) return rc;
+  hipLaunchKernelGGL(vpt_permute_kernel, dim3((pr.nslots + 255) / 256), dim3(256), 0, st, pr, (int)to_tiles, (float4*)t.image, (int*)t.hits,
+      (ulonglong2*)t.rng, (float4*)r.image, (int*)r.hits, (ulonglong2*)r.rng);
   HIP_TRY(hipGetLastError());
-  return VPT_OK;
-}
-
-// the host <-> tile-major conversions go through a row-major device copy of the frame (r_image, r_hits, r_rng): the scene
-// handle's in vpt_render (allocated once per frame size), else allocated for the call
-static int state_upload(const vpt_layout* layout, const float* image_rgba, const int32_t* hits, const uint64_t* rng,
-    void* d_image, void* d_hits, void* d_rng, hipStream_t st, void* r_image, void* r_hits, void* r_rng) {
-  size_t n = (size_t)layout->width * layout->height;
-  HIP_TRY(hipMemcpyAsync(r_image, image_rgba, n * 16, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(r_hits, hits, n * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(r_rng, rng, n * 16, hipMemcpyHostToDevice, st));
-  if (int rc = permute(layout, 1, d_image, d_hits, d_rng, r_image, r_hits, r_rng, st)) return rc;
-  HIP_TRY(hipStreamSynchronize(st));
-  return VPT_OK;
-}
-static int state_download(const vpt_layout* layout, const void* d_image, const void* d_hits, const void* d_rng,
-    float* image_rgba, int32_t* hits, uint64_t* rng, hipStream_t st, void* r_image, void* r_hits, void* r_rng, bool rows_hold_the_frame) {
-  size_t n = (size_t)layout->width * layout->height;
-  if (!rows_hold_the_frame) {   // start from the caller's arrays so that pixels owned by other ranks keep their values
-    HIP_TRY(hipMemcpyAsync(r_image, image_rgba, n * 16, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(r_hits, hits, n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(r_rng, rng, n * 16, hipMemcpyHostToDevice, st));
-  }
-  if (int rc = permute(layout, 0, (void*)d_image, (void*)d_hits, (void*)d_rng, r_image, r_hits, r_rng, st)) return rc;
-  HIP_TRY(hipMemcpyAsync(image_rgba, r_image, n * 16, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(hits, r_hits, n * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(rng, r_rng, n * 16, hipMemcpyDeviceToHost, st));
+  if (!to_tiles)
+    for (const auto& p : parts) HIP_TRY(hipMemcpyAsync(p.host, p.rows, p.bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return VPT_OK;
 }
 
 int vpt_state_upload(const vpt_layout* layout, const float* image_rgba, const int32_t* hits, const uint64_t* rng,
     void* d_image, void* d_hits, void* d_rng, void* stream) {
-  if (!layout || !image_rgba || !hits || !rng || !d_image || !d_hits || !d_rng) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  if (layout->width <= 0 || layout->height <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad layout");
-  const size_t  n = (size_t)layout->width * layout->height;
-  device_buffer r_image, r_hits, r_rng;
-  if (r_image.allocate(n * 16) || r_hits.allocate(n * 4) || r_rng.allocate(n * 16)) return VPT_ERR_HIP;
-  return state_upload(layout, image_rgba, hits, rng, d_image, d_hits, d_rng, (hipStream_t)stream, r_image.get(), r_hits.get(), r_rng.get());
+  return move_state(layout, true, (float*)image_rgba, (int32_t*)hits, (uint64_t*)rng, {d_image, d_hits, d_rng}, nullptr, (hipStream_t)stream);
 }
 
 int vpt_state_download(const vpt_layout* layout, const void* d_image, const void* d_hits, const void* d_rng,
     float* image_rgba, int32_t* hits, uint64_t* rng, void* stream) {
-  if (!layout || !image_rgba || !hits || !rng || !d_image || !d_hits || !d_rng) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  if (layout->width <= 0 || layout->height <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad layout");
-  const size_t  n = (size_t)layout->width * layout->height;
-  device_buffer r_image, r_hits, r_rng;
-  if (r_image.allocate(n * 16) || r_hits.allocate(n * 4) || r_rng.allocate(n * 16)) return VPT_ERR_HIP;
-  return state_download(layout, d_image, d_hits, d_rng, image_rgba, hits, rng, (hipStream_t)stream, r_image.get(), r_hits.get(), r_rng.get(), false);
+  return move_state(layout, false, image_rgba, hits, rng, {(void*)d_image, (void*)d_hits, (void*)d_rng}, nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -288,60 +241,9 @@ static int stack_config(vpt_scene* s, long long lanes, stack_cfg& cfg) {
   return VPT_OK;
 }
 
-// the measured costs, the order made from them and the tile-splitting decision go (the buffers stay)
-static void sched_forget(vpt_scene* s) {
-  s->order_valid = false, s->split_decided = false, s->full_costs = false, s->split_waves = 0, s->split_tiles = 0, s->cost_weight = 0;
-}
-// Buffers of the launch schedule for `waves` waves; a change of layout / camera / shader forgets the measured costs.
-static int sched_prepare(vpt_scene* s, long long waves, const long long key[10], hipStream_t st) {
-  if (waves > s->sched_waves) {
-    s->sched_waves = 0, s->order_valid = false, s->cost_weight = 0;
-    for (device_buffer* b : {&s->d_cost, &s->d_cost_sorted, &s->d_cost_key, &s->d_cost_avg, &s->d_order, &s->d_iota})
-      if (int rc = b->allocate(waves * 4)) return rc;
-    HIP_TRY(hipMemset(s->d_cost.get(), 0, waves * 4));   // waves that own no pixel never write theirs
-    std::vector<int> iota((size_t)waves);
-    for (long long i = 0; i < waves; i++) iota[(size_t)i] = (int)i;
-    HIP_TRY(hipMemcpy(s->d_iota.get(), iota.data(), waves * 4, hipMemcpyHostToDevice));
-    size_t bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs_desc((void*)nullptr, bytes, s->d_cost.get<unsigned>(), s->d_cost_sorted.get<unsigned>(), s->d_iota.get<int>(),
-        s->d_order.get<int>(), (size_t)waves));
-    if (int rc = s->sort_temp.allocate(bytes)) return rc;
-    s->sort_temp_bytes = bytes, s->sched_waves = waves;
-  }
-  if (memcmp(key, s->sched_key, sizeof(s->sched_key)) != 0) sched_forget(s), memcpy(s->sched_key, key, sizeof(s->sched_key));
-  (void)st;
-  return VPT_OK;
-}
-// order[] for the next launch from the costs the launch just enqueued on `st` will have written
-static constexpr float k_cost_horizon = 6;   // launches behind the running average
-static int sched_update(vpt_scene* s, long long waves, hipStream_t st, int nsamples = 0) {
-  // nsamples > 0: d_cost holds the durations of a launch over that many samples: they enter the running average, whose order the next launch takes;
-  // nsamples == 0: d_cost holds predictions (a fresh split table): they start a new average
-  if (nsamples <= 0) s->cost_weight = 0;
-  const float n = nsamples > 0 ? (float)nsamples : 1.0f;
-  hipLaunchKernelGGL(vpt_cost_average_kernel, dim3((unsigned)((waves + 255) / 256)), dim3(256), 0, st, s->d_cost.get<unsigned>(), s->d_cost_avg.get<float>(),
-      s->d_cost_key.get<unsigned>(), (int)waves, n, s->cost_weight);
-  HIP_TRY(hipGetLastError());
-  if (nsamples > 0) s->cost_weight = std::min(s->cost_weight + n, k_cost_horizon * n);   // the last few launches
-  size_t bytes = s->sort_temp_bytes;
-  HIP_TRY(rocprim::radix_sort_pairs_desc(s->sort_temp.get(), bytes, s->d_cost_key.get<unsigned>(), s->d_cost_sorted.get<unsigned>(), s->d_iota.get<int>(),
-      s->d_order.get<int>(), (size_t)waves, 0, 32, st));
-  HIP_TRY(hipEventRecord(s->ev_order, st));
-  s->order_valid = true, s->order_stream = st;
-  return VPT_OK;
-}
-// d_order / d_cost are written on the stream of the previous launch: a launch on another stream waits for that sort
-static int sched_wait(vpt_scene* s, hipStream_t st) {
-  if (s->order_valid && s->order_stream != st) HIP_TRY(hipStreamWaitEvent(st, s->ev_order, 0));
-  return VPT_OK;
-}
-
-// everything one vpt_render_device call hands to the kernel launchers
+// what a call that renders hands to the kernel launchers, whatever the grid and the sample count of a launch
 struct launch_ctx {
   vpt_scene*        s;
-  const vpt_params* params;
-  const DParams&    pr;
-  dim3              grid, block;
   hipStream_t       st;
   float4*           img;
   int*              hit;
@@ -349,164 +251,14 @@ struct launch_ctx {
   stack_cfg         stack;
 };
 
-// ---- tile splitting (K1, K2) ----------------------------------------------------------------------------------------
-// A wave runs all samples of its 64 pixels one after the other, so a launch cannot be shorter than its costliest tile.
-// On one GPU that tile (273 ms of a 280 ms launch on 03_volume) is level with total work / wave slots and nothing is
-// gained by shortening it; once the frame is shared among N GPUs the work per GPU falls with N and the chain does not.
-// A tile can be run as 2^k waves that hold every 2^k-th pixel in their first 64 >> k lanes: fewer live lanes diverge
-// less, the wave's trips get faster (g[k] below, measured on MI355X: DESIGN.md §5) - at 2^k g[k] times the slot time.
-// Policy (decide_split): for a range of candidate spans S every tile is split just enough for its waves to fit S and the
-// resulting launch is simulated (longest-first list scheduling on the chip's wave slots, durations scaled by how full the
-// chip is); the shortest simulated launch wins if it beats the unsplit one by 2 %.  Taken once per layout / shader /
-// camera from the per-tile costs of an unsplit launch, when the launch is short of waves: the frame is shared among ranks
-// or holds fewer than three tiles per wave slot (1280x533 on one MI355X has 3.5 and never gains).  Pixels keep their own RNG streams and accumulators, so the result does
-// not depend on it.
-static constexpr double split_gain[7] = {1.0, 0.75, 0.57, 0.44, 0.34, 0.27, 0.20};   // duration of a 64 >> k lane wave of a costly tile / its full wave (round 4's
-                                                                                    // kernel, whose partly filled waves use their empty lanes as helpers: 0.753 / 0.566 / 0.436 / 0.343 measured, was 0.81 / 0.62 / 0.45 / 0.35)
-static constexpr double split_gain_k2[7] = {1.0, 0.82, 0.67, 0.63, 0.60, 0.58, 0.56};   // the same for K2 (implicit shaders): 0.82 / 0.67 / 0.63 measured on 06_gridsdf_full (profiles/r04_k2_lane_histogram.txt), the rest extrapolated
-static constexpr double split_load0 = 0.46, split_margin = 0.98;   // load_factor's intercept; a split has to beat the unsplit launch by this factor
-static int split_mode() {   // VPT_SPLIT: 0 never, 1 always consider, unset: consider when the launch is short of waves
-  static int v = [] { const char* e = getenv("VPT_SPLIT"); return e ? atoi(e) : -1; }();
-  return v;
-}
-static int split_forced_k() {   // VPT_SPLIT_K (calibration): every tile as 2^k waves
-  static int v = [] { const char* e = getenv("VPT_SPLIT_K"); return e ? atoi(e) : -1; }();
-  return v;
-}
-// lane table and predicted wave costs for the split factors s->h_split_k; part_cost[t] = expected duration of one wave of tile t
-static int build_split_table(vpt_scene* s, const std::vector<double>& part_cost, hipStream_t st) {
-  const std::vector<int>& k = s->h_split_k;
-  const int ntiles = (int)k.size();
-  long long waves = 0;
-  int       nsplit = 0;
-  for (int t = 0; t < ntiles; t++) waves += 1ll << k[t], nsplit += k[t] > 0;
-  s->split_waves = 0, s->split_tiles = 0;
-  if (nsplit == 0 || waves > (1ll << 24)) return VPT_OK;
-  std::vector<int>      table((size_t)waves * VPT_BLOCK, -1);
-  std::vector<unsigned> wcost((size_t)waves);
-  long long w = 0;
-  for (int t = 0; t < ntiles; t++)
-    for (int part = 0; part < (1 << k[t]); part++, w++) {
-      wcost[(size_t)w] = (unsigned)part_cost[t];
-      for (int lane = 0; lane < (VPT_BLOCK >> k[t]); lane++) table[(size_t)w * VPT_BLOCK + lane] = t * VPT_BLOCK + (lane << k[t]) + part;
-    }
-  if ((long long)table.size() > s->lane_cap) {
-    s->lane_cap = 0;
-    if (int rc = s->d_lane_slot.allocate(table.size() * 4)) return rc;
-    s->lane_cap = (long long)table.size();
-  }
-  long long key[10];
-  memcpy(key, s->sched_key, sizeof(key));
-  if (int rc = sched_prepare(s, waves, key, st)) return rc;   // may reallocate d_cost / d_order for the larger wave count
-  HIP_TRY(hipMemcpy(s->d_lane_slot.get(), table.data(), table.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s->d_cost.get(), wcost.data(), wcost.size() * 4, hipMemcpyHostToDevice));
-  s->split_waves = (int)waves, s->split_tiles = nsplit;
-  return sched_update(s, waves, st);   // order of the split launch from the predicted costs; measured ones take over afterwards
-}
-// makespan of longest-first list scheduling of `costs` (any order) on `slots` machines: what the hardware's dispatch of
-// the launch in d_order amounts to
-static double lpt_makespan(std::vector<double>& costs, int slots) {
-  std::sort(costs.begin(), costs.end(), std::greater<double>());
-  std::priority_queue<double, std::vector<double>, std::greater<double>> load;
-  double span = 0;
-  for (size_t i = 0; i < costs.size(); i++) {
-    double at = 0;
-    if ((int)load.size() >= slots) at = load.top(), load.pop();
-    load.push(at + costs[i]);
-    span = std::max(span, at + costs[i]);
-  }
-  return span;
-}
-// A wave also runs faster when fewer waves share its SIMD: the costliest tile of 03_volume takes 273 ms with all 3 072
-// slots busy and 187 ms when 1 340 waves are resident: duration ~ (0.46 + 0.54 * occupancy) * duration at 1
-static double load_factor(double waves, int slots) { return split_load0 + (1 - split_load0) * std::min(1.0, waves / slots); }
-// gain: split_gain (K1) or split_gain_k2 (K2)
-static int decide_split(vpt_scene* s, int ntiles, int slots, hipStream_t st, const double* gain) {
-  s->split_decided = true, s->split_waves = 0, s->split_tiles = 0;
-  HIP_TRY(hipStreamSynchronize(st));
-  std::vector<unsigned> cost((size_t)ntiles);
-  HIP_TRY(hipMemcpy(cost.data(), s->d_cost.get(), cost.size() * 4, hipMemcpyDeviceToHost));
-  std::vector<int>& k = s->h_split_k;
-  k.assign((size_t)ntiles, 0);
-  double cmax = 0;
-  int    live = 0;
-  for (unsigned c : cost) cmax = std::max(cmax, (double)c), live += c > 0;
-  if (cmax <= 0) return VPT_OK;
-  const double measured_at = load_factor(live, slots);   // the costs were measured with `live` waves resident
-  std::vector<double> waves;
-  auto plan = [&](double S, bool apply) {   // predicted span when every tile is split just enough for its waves to fit S
-    waves.clear();
-    for (int t = 0; t < ntiles; t++) {
-      if (cost[t] == 0) continue;
-      int kt = 0;
-      while (kt < 6 && cost[t] * gain[kt] > S) kt++;
-      if (apply) k[t] = kt;
-      for (int p = 0; p < (1 << kt); p++) waves.push_back(cost[t] * gain[kt]);
-    }
-    double f = load_factor((double)waves.size(), slots) / measured_at;
-    for (double& w : waves) w *= f;
-    return lpt_makespan(waves, slots);
-  };
-  if (split_forced_k() >= 0) {
-    for (int t = 0; t < ntiles; t++) k[t] = std::min(split_forced_k(), 6);
-  } else {
-    double best_S = cmax, best = plan(cmax, false);
-    for (int i = 1; i <= 24; i++) {   // candidates from the costliest tile down to its 1-lane duration
-      double S = cmax * std::pow(gain[6], i / 24.0), span = plan(S, false);
-      if (span < best * split_margin) best = span, best_S = S;   // a split has to pay at least 2 %
-    }
-    plan(best_S, true);
-  }
-  std::vector<double> part((size_t)ntiles);
-  for (int t = 0; t < ntiles; t++) part[t] = cost[t] * gain[k[t]];
-  return build_split_table(s, part, st);
-}
-
-// The launch loop of K1 and K2.  Longest-wave-first order from the costs of the previous launch on this layout; without them
-// a pilot launch over 1/64 of the call's samples (1..16) measures them first - same arithmetic, batching is exact (K2 in tile
-// order: a first call ran at 216 against 302 Msamples/s on 06_gridsdf).  may_split / slots / gain: the kernel's tile-splitting
-// policy (above); launch(is_pilot, grid, pr, sch) launches the kernel instance for the part.
-template <typename Launch>
-static int run_launches(const launch_ctx& L, bool may_split, int slots, const double* gain, Launch&& launch) {
-  vpt_scene*      s = L.s;
-  const DParams&  p = L.pr;
-  const long long key[10] = {p.nslots, p.width, p.height, L.params->shader, L.params->camera, L.params->bounces, p.rank, p.nranks, p.tile_w, p.tile_h};
-  if (int rc = sched_prepare(s, std::max<long long>(L.grid.x, s->split_waves), key, L.st)) return rc;
-  if (int rc = sched_wait(s, L.st)) return rc;
-  int n = p.nsamples, pilot = n / 64 < 1 ? 1 : n / 64 > 16 ? 16 : n / 64;
-  int parts[2] = {(!s->order_valid && n >= 16) ? pilot : n, 0};
-  parts[1] = n - parts[0];
-  for (int part = 0; part < 2 && parts[part] > 0; part++) {
-    DParams pr  = L.pr;
-    pr.nsamples = parts[part];
-    const bool is_pilot = parts[1] > 0 && part == 0;
-    // the costs of an unsplit launch over at least 8 samples decide, once, whether tiles are split from now on
-    if (may_split && !s->split_decided && s->order_valid && s->full_costs) {
-      // the decision waits for the stream and reads costs back on the host: that pause is bracketed by its own event pair and
-      // subtracted by vpt_last_kernel_ms (a pilot launch that ran before it in this call stays counted)
-      HIP_TRY(hipEventRecord(s->ev_host0, L.st));
-      if (int rc = decide_split(s, (int)L.grid.x, slots, L.st, gain)) return rc;
-      HIP_TRY(hipEventRecord(s->ev_host1, L.st));
-      s->host_pause = true;
-    }
-    dim3 grid = s->split_waves > 0 ? dim3((unsigned)s->split_waves) : L.grid;
-    sched_cfg sch = {s->order_valid ? s->d_order.get<int>() : nullptr, s->d_cost.get<unsigned>(), s->split_waves > 0 ? s->d_lane_slot.get<int>() : nullptr};
-    launch(is_pilot, grid, pr, sch);
-    if (s->split_waves == 0) s->full_costs = pr.nsamples >= 8;   // d_cost now holds per-tile durations over enough samples (a pilot of a call with >= 512 samples counts)
-    s->last_waves = (int)grid.x;
-    if (int rc = sched_update(s, grid.x, L.st, pr.nsamples)) return rc;
-  }
-  return VPT_OK;
-}
-
 // K1 (mesh shaders): the instance compiled for the features this scene has (vpt_scene.hip.h: VPT_FEAT_*), launched over `grid`
-// with the schedule `sch` - by run_launches (vpt_render_device) and by the rounds of vpt_render_device_adaptive
+// with the schedule `sch` - by launch_schedule::run (vpt_render_device) and by the rounds of vpt_render_device_adaptive
 template <int K>
 static void launch_mesh_instance(const launch_ctx& L, bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
   vpt_scene* s = L.s;
   size_t lds = (size_t)s->stack_lds4 * 2 * VPT_BLOCK * sizeof(int) + 5 * VPT_BLOCK * sizeof(float);   // (ref, t0) pairs + the parked words
   const int need = getenv("VPT_NO_LEAN") ? VPT_FEAT_ALL : s->light_features;
-  auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, L.block, lds, L.st, s->d, pr, L.img, L.hit, L.rng, L.stack, sch); };
+  auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(VPT_BLOCK), lds, L.st, s->d, pr, L.img, L.hit, L.rng, L.stack, sch); };
   auto launch_feat = [&](auto feat) {
     constexpr int F = decltype(feat)::value;
     if (is_pilot && L.stack.spill) launch(vpt_mesh_pilot_kernel<K, true, F>);
@@ -527,20 +279,12 @@ static void launch_mesh_instance(const launch_ctx& L, bool is_pilot, dim3 grid, 
   else if ((need & VPT_FEAT_SDF_LIGHTS) == 0) launch_feat(std::integral_constant<int, VPT_FEAT_SMALL_LIGHTS | VPT_FEAT_LARGE_LIGHTS>{});
   else launch_feat(std::integral_constant<int, VPT_FEAT_ALL>{});
 }
-template <int K>
-static int launch_mesh(const launch_ctx& L) {
-  vpt_scene* s = L.s;
-  const bool may_split = !L.stack.spill && (split_mode() == 1 || split_forced_k() >= 0 ||
-                                            (split_mode() < 0 && (L.pr.nranks > 1 || (long long)L.grid.x < 3ll * s->wave_slots_k1)));
-  return run_launches(L, may_split, s->wave_slots_k1, split_gain, [&](bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
-    launch_mesh_instance<K>(L, is_pilot, grid, pr, sch);
-  });
-}
 // K2 (implicit shaders): LDS of a launch (the refs-only stack + the scene's SDF records); VPT_ERR_UNSUPPORTED when they do not fit
-static int implicit_lds(const vpt_scene* s, size_t& lds) {
-  lds = (size_t)s->stack_cap * VPT_BLOCK * sizeof(int) +                                      // refs-only stack
+static int implicit_lds(const vpt_scene* s, size_t* bytes = nullptr) {
+  const size_t lds = (size_t)s->stack_cap * VPT_BLOCK * sizeof(int) +                                      // refs-only stack
         (6 * (size_t)s->d.num_sdfs + 7 * (size_t)s->d.num_vol_instances) * sizeof(float4);   // the SDF records
   if (lds > 64 * 1024) return vpt_set_error(VPT_ERR_UNSUPPORTED, "scene has too many SDFs for the implicit kernel's LDS copy of their records (%d + %d)", s->d.num_sdfs, s->d.num_vol_instances);
+  if (bytes) *bytes = lds;
   return VPT_OK;
 }
 // the instance for the features this scene's lights have (VPT_FEAT_*): SDF scenes without emissive meshes run one without the mesh-light walks
@@ -548,41 +292,43 @@ template <int K>
 static void launch_implicit_instance(const launch_ctx& L, bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
   vpt_scene* s = L.s;
   size_t     lds = 0;
-  (void)implicit_lds(s, lds);   // checked by the callers before they launch
+  (void)implicit_lds(s, &lds);   // checked by the callers before they launch
   unsigned long long watchdog_ticks = VPT_K2_WATCHDOG_TICKS;
   if (const char* e = getenv("VPT_K2_WATCHDOG_MS")) watchdog_ticks = strtoull(e, nullptr, 10) * 100000ull;   // tests of the error path
   const bool lean = (s->light_features & (VPT_FEAT_LARGE_LIGHTS | VPT_FEAT_SMALL_LIGHTS)) == 0 && !getenv("VPT_NO_LEAN");
-  auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, L.block, lds, L.st, s->d, pr, L.img, L.hit, L.rng, s->stack_cap, sch, s->d_watchdog.get<unsigned>(), watchdog_ticks); };
+  auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(VPT_BLOCK), lds, L.st, s->d, pr, L.img, L.hit, L.rng, s->stack_cap, sch, s->d_watchdog.get<unsigned>(), watchdog_ticks); };
   if (is_pilot && lean) launch(vpt_render_pilot_kernel<K, VPT_FEAT_SDF_LIGHTS>);
   else if (is_pilot) launch(vpt_render_pilot_kernel<K, VPT_FEAT_ALL>);
   else if (lean) launch(vpt_render_kernel<K, VPT_FEAT_SDF_LIGHTS>);
   else launch(vpt_render_kernel<K, VPT_FEAT_ALL>);
 }
-// K2.  Tile splitting is considered on every layout (unless VPT_SPLIT=0): K2's launches hold two waves per wave
-// slot at 1280 x 533, so the longest-first schedule ends well above both of its bounds (226 ms against a longest wave of 192 and 191
-// of work per slot); the costliest tiles as partly filled waves - whose scene rounds run in the group form: four lanes per ray - pack better.
-template <int K>
-static int launch_implicit(const launch_ctx& L) {
-  size_t lds = 0;
-  if (int rc = implicit_lds(L.s, lds)) return rc;
-  return run_launches(L, split_mode() != 0, L.s->wave_slots_k2, split_gain_k2, [&](bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
-    launch_implicit_instance<K>(L, is_pilot, grid, pr, sch);
-  });
-}
-// one launch of the kernel instance for params->shader over `grid` with the schedule `sch` (no pilot): the rounds of
-// vpt_render_device_adaptive go through the same instance table as vpt_render_device
-static void launch_instance(const launch_ctx& L, dim3 grid, const DParams& pr, const sched_cfg& sch) {
-  switch (L.params->shader) {
-    case VPT_SHADER_VOLPATHTRACE: launch_mesh_instance<K_VOLPATH>(L, false, grid, pr, sch); break;
-    case VPT_SHADER_PATHTRACE: launch_mesh_instance<K_PATH>(L, false, grid, pr, sch); break;
-    case VPT_SHADER_NAIVE: launch_mesh_instance<K_NAIVE>(L, false, grid, pr, sch); break;
-    case VPT_SHADER_EYELIGHT: launch_mesh_instance<K_EYELIGHT>(L, false, grid, pr, sch); break;
-    case VPT_SHADER_NORMAL:
-    case VPT_SHADER_TEXCOORD:
-    case VPT_SHADER_COLOR: launch_mesh_instance<K_DEBUG>(L, false, grid, pr, sch); break;
-    case VPT_SHADER_IMPLICIT: launch_implicit_instance<K_IMPLICIT>(L, false, grid, pr, sch); break;
-    case VPT_SHADER_IMPLICIT_NORMAL: launch_implicit_instance<K_IMPLICIT_NORMAL>(L, false, grid, pr, sch); break;
+// the launcher of the kernel instances of `shader`: the one table of vpt_render_device and of the rounds of
+// vpt_render_device_adaptive (both have checked the shader's range)
+using instance_launcher = void (*)(const launch_ctx&, bool is_pilot, dim3 grid, const DParams&, const sched_cfg&);
+static instance_launcher launcher_of(int shader) {
+  switch (shader) {
+    case VPT_SHADER_VOLPATHTRACE: return launch_mesh_instance<K_VOLPATH>;
+    case VPT_SHADER_PATHTRACE: return launch_mesh_instance<K_PATH>;
+    case VPT_SHADER_NAIVE: return launch_mesh_instance<K_NAIVE>;
+    case VPT_SHADER_EYELIGHT: return launch_mesh_instance<K_EYELIGHT>;
+    case VPT_SHADER_IMPLICIT: return launch_implicit_instance<K_IMPLICIT>;
+    case VPT_SHADER_IMPLICIT_NORMAL: return launch_implicit_instance<K_IMPLICIT_NORMAL>;
+    default: return launch_mesh_instance<K_DEBUG>;   // VPT_SHADER_NORMAL, _TEXCOORD, _COLOR
   }
+}
+
+// vpt_resolve_device / vpt_resolve_srgb8_device: the accumulators of every rank's tiles, over `samples`, as row-major pixels
+template <typename Kernel, typename Pixel>
+static int resolve(Kernel kernel, const vpt_layout* layout, const void* d_tiles_all_ranks, int samples, Pixel* d_rowmajor, void* stream) {
+  if (!layout || !d_tiles_all_ranks || !d_rowmajor || samples <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
+  DParams pr;
+  if (int rc = vpt_layout_dparams(layout, pr)) return rc;
+  long long total = (long long)pr.nslots * pr.nranks;
+  if (total >= (1LL << 31)) return vpt_set_error(VPT_ERR_INVALID_ARG, "image too large");
+  int blocks = (int)((total + 255) / 256);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pr, (const float4*)d_tiles_all_ranks, 1.0f / (float)samples, d_rowmajor);
+  HIP_TRY(hipGetLastError());
+  return VPT_OK;
 }
 
 extern "C" {
@@ -598,28 +344,29 @@ int vpt_render_device(vpt_scene* s, const vpt_params* params, const vpt_layout* 
   if (int rc = make_dparams(params, layout, nsamples, pr)) return rc;
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)stream;
-  dim3   grid((pr.nslots + VPT_BLOCK - 1) / VPT_BLOCK), block(VPT_BLOCK);
+  dim3   grid((pr.nslots + VPT_BLOCK - 1) / VPT_BLOCK);
   stack_cfg stack;
   if (int rc = stack_config(s, (long long)grid.x * VPT_BLOCK, stack)) return rc;
-  auto   img = (float4*)d_image;
-  auto   hit = (int*)d_hits;
-  auto   rng = (ulonglong2*)d_rng;
+  // K1 considers tile splitting when the launch is short of waves (vpt_split_policy.cpp).  K2 considers it on every layout (unless
+  // VPT_SPLIT=0): K2's launches hold two waves per wave slot at 1280 x 533, so the longest-first schedule ends well above both of
+  // its bounds (226 ms against a longest wave of 192 and 191 of work per slot); the costliest tiles as partly filled waves - whose
+  // scene rounds run in the group form: four lanes per ray - pack better.
+  const bool k2 = params->shader >= VPT_SHADER_IMPLICIT;
+  if (k2)
+    if (int rc = implicit_lds(s)) return rc;   // the scene's SDF records must fit the kernel's LDS
+  const bool may_split = k2 ? split_mode() != 0
+                            : !stack.spill && (split_mode() == 1 || split_forced_k() >= 0 ||
+                                               (split_mode() < 0 && (pr.nranks > 1 || (long long)grid.x < 3ll * s->sched.wave_slots(false))));
+  const long long key[10] = {pr.nslots, pr.width, pr.height, params->shader, params->camera, params->bounces, pr.rank, pr.nranks, pr.tile_w, pr.tile_h};
   HIP_TRY(hipEventRecord(s->ev0, st));
-  s->host_pause = false;
-  launch_ctx L = {s, params, pr, grid, block, st, img, hit, rng, stack};
-  int rc = VPT_OK;
-  switch (params->shader) {
-    case VPT_SHADER_VOLPATHTRACE: rc = launch_mesh<K_VOLPATH>(L); break;
-    case VPT_SHADER_PATHTRACE: rc = launch_mesh<K_PATH>(L); break;
-    case VPT_SHADER_NAIVE: rc = launch_mesh<K_NAIVE>(L); break;
-    case VPT_SHADER_EYELIGHT: rc = launch_mesh<K_EYELIGHT>(L); break;
-    case VPT_SHADER_NORMAL:
-    case VPT_SHADER_TEXCOORD:
-    case VPT_SHADER_COLOR: rc = launch_mesh<K_DEBUG>(L); break;
-    case VPT_SHADER_IMPLICIT: rc = launch_implicit<K_IMPLICIT>(L); break;
-    case VPT_SHADER_IMPLICIT_NORMAL: rc = launch_implicit<K_IMPLICIT_NORMAL>(L); break;
-  }
-  if (rc != VPT_OK) return rc;
+  const launch_ctx L = {s, st, (float4*)d_image, (int*)d_hits, (ulonglong2*)d_rng, stack};
+  if (int rc = s->sched.run(key, grid, nsamples, st, may_split, k2,
+          [&](bool is_pilot, dim3 part_grid, int part_samples, const sched_cfg& sch) {
+            DParams part = pr;
+            part.nsamples = part_samples;
+            launcher_of(params->shader)(L, is_pilot, part_grid, part, sch);
+          }))
+    return rc;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(s->ev1, st));
   s->timed = true;
@@ -650,7 +397,7 @@ int vpt_scene_update(vpt_scene* s, const vpt_scene_edit* edit) {
   if (int rc = scene_update_apply(s->d, s->h, s->num_shape_nodes, s->upd, *edit)) return rc;
   if (edit->num_instances > 0 || edit->num_shapes > 0)
     if (int rc = light_setup(s)) return rc;   // light_prims hold world-space normals of the moved lights
-  sched_forget(s);   // the camera index may be the same, the picture is not
+  s->sched.forget();   // the camera index may be the same, the picture is not
   return VPT_OK;
 }
 
@@ -677,11 +424,7 @@ int vpt_last_wave_costs(vpt_scene* s, unsigned* ticks, int capacity, int* count)
   if (!s->timed) return vpt_set_error(VPT_ERR_INVALID_ARG, "no launch recorded");
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipEventSynchronize(s->ev1));
-  long long n = s->last_waves;   // waves of the last launch
-  *count = (int)n;
-  if (n > capacity) n = capacity;
-  if (n > 0) HIP_TRY(hipMemcpy(ticks, s->d_cost.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
-  return VPT_OK;
+  return s->sched.last_wave_costs(ticks, capacity, count);
 }
 
 // synchronous: waves of the implicit kernel that hit their watchdog since the scene was created (a defect, never a workload)
@@ -699,47 +442,30 @@ int vpt_last_kernel_ms(vpt_scene* s, float* ms) {
   if (!s->timed) return vpt_set_error(VPT_ERR_INVALID_ARG, "no launch recorded");
   HIP_TRY(hipEventSynchronize(s->ev1));
   HIP_TRY(hipEventElapsedTime(ms, s->ev0, s->ev1));
-  if (s->host_pause) {
-    float pause = 0;
-    HIP_TRY(hipEventElapsedTime(&pause, s->ev_host0, s->ev_host1));
-    *ms -= pause;
-  }
+  float pause = 0;
+  if (int rc = s->sched.paused_ms(&pause)) return rc;
+  *ms -= pause;
   return vpt_check_watchdog(s);
 }
 
 int vpt_resolve_device(const vpt_layout* layout, const void* d_tiles_all_ranks, int samples, void* d_image_rowmajor, void* stream) {
-  if (!layout || !d_tiles_all_ranks || !d_image_rowmajor || samples <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
-  DParams    pr;
-  vpt_params dummy = {};
-  if (int rc = make_dparams(&dummy, layout, 0, pr)) return rc;
-  long long total = (long long)pr.nslots * pr.nranks;
-  if (total >= (1LL << 31)) return vpt_set_error(VPT_ERR_INVALID_ARG, "image too large");
-  int blocks = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(vpt_resolve_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pr, (const float4*)d_tiles_all_ranks,
-      1.0f / (float)samples, (float4*)d_image_rowmajor);
-  HIP_TRY(hipGetLastError());
-  return VPT_OK;
+  return resolve(vpt_resolve_kernel, layout, d_tiles_all_ranks, samples, (float4*)d_image_rowmajor, stream);
 }
 
 int vpt_resolve_srgb8_device(const vpt_layout* layout, const void* d_tiles_all_ranks, int samples, void* d_rgba8_rowmajor, void* stream) {
-  if (!layout || !d_tiles_all_ranks || !d_rgba8_rowmajor || samples <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
-  DParams    pr;
-  vpt_params dummy = {};
-  if (int rc = make_dparams(&dummy, layout, 0, pr)) return rc;
-  long long total = (long long)pr.nslots * pr.nranks;
-  if (total >= (1LL << 31)) return vpt_set_error(VPT_ERR_INVALID_ARG, "image too large");
-  int blocks = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(vpt_resolve_srgb8_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pr, (const float4*)d_tiles_all_ranks,
-      1.0f / (float)samples, (uchar4*)d_rgba8_rowmajor);
-  HIP_TRY(hipGetLastError());
-  return VPT_OK;
+  return resolve(vpt_resolve_srgb8_kernel, layout, d_tiles_all_ranks, samples, (uchar4*)d_rgba8_rowmajor, stream);
 }
 
 }  // extern "C"
 
-// the scene handle's staging of a host state for `lay` (one rank, 8x8 tiles): allocated once per frame size
-static int stage_host_state(vpt_scene* s, const vpt_layout& lay) {
-  long long slots = vpt_layout_slots(&lay), pixels = (long long)lay.width * lay.height;
+// vpt_render / vpt_render_adaptive: the host state through the scene handle's staging (one rank, 8x8 tiles; allocated once per frame
+// size), render(layout, tiles) on it, and back.  The row-major staging still holds the frame that was uploaded, and the
+// single-rank layout owns every pixel, so the download starts from it.
+template <typename Render>
+static int render_host_state(vpt_scene* s, int width, int height, float* image_rgba, int32_t* hits, uint64_t* rng, Render&& render) {
+  HIP_TRY(hipSetDevice(s->device));
+  vpt_layout lay = {width, height, 8, 8, 0, 1};
+  long long  slots = vpt_layout_slots(&lay), pixels = (long long)width * height;
   if (slots < 0) return VPT_ERR_INVALID_ARG;
   if (s->staged_slots != slots || s->staged_pixels != pixels) {
     s->staged_slots = s->staged_pixels = 0;
@@ -748,7 +474,12 @@ static int stage_host_state(vpt_scene* s, const vpt_layout& lay) {
       return VPT_ERR_HIP;
     s->staged_slots = slots, s->staged_pixels = pixels;
   }
-  return VPT_OK;
+  const tile_state t = {s->s_image.get(), s->s_hits.get(), s->s_rng.get()};
+  const row_state  r = {s->r_image.get(), s->r_hits.get(), s->r_rng.get()};
+  if (int rc = move_state(&lay, true, image_rgba, hits, rng, t, &r, nullptr)) return rc;
+  if (int rc = render(&lay, t)) return rc;
+  if (int rc = move_state(&lay, false, image_rgba, hits, rng, t, &r, nullptr)) return rc;
+  return vpt_check_watchdog(s);
 }
 
 // the arguments of an adaptive render, checked before anything touches the device
@@ -780,9 +511,8 @@ int vpt_render_device_adaptive(vpt_scene* s, const vpt_params* params, const vpt
   DParams pr;
   if (int rc = make_dparams(params, layout, 0, pr)) return rc;
   const bool implicit = params->shader >= VPT_SHADER_IMPLICIT;
-  size_t     lds      = 0;
   if (implicit)
-    if (int rc = implicit_lds(s, lds)) return rc;
+    if (int rc = implicit_lds(s)) return rc;
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t     st   = (hipStream_t)stream;
   const long long full = (pr.nslots + VPT_BLOCK - 1) / VPT_BLOCK;
@@ -794,9 +524,7 @@ int vpt_render_device_adaptive(vpt_scene* s, const vpt_params* params, const vpt
   if (int rc = d_lane_slot.allocate((size_t)pr.nslots * 4)) return rc;
   if (int rc = d_info.allocate(16)) return rc;
   const adaptive_buffers b = {d_stats.get<float4>(), d_wave_count.get<int>(), d_lane_slot.get<int>(), d_info.get<int>()};
-  auto img = (float4*)d_image;
-  auto hit = (int*)d_hits;
-  auto rng = (ulonglong2*)d_rng;
+  const launch_ctx L = {s, st, (float4*)d_image, (int*)d_hits, (ulonglong2*)d_rng, stack};
   int  info[4] = {0, 0, 0, 0};
   auto read_info = [&]() -> int {   // the one read-back of a round: what sizes the next launch
     HIP_TRY(hipMemcpyAsync(info, b.info, sizeof(info), hipMemcpyDeviceToHost, st));
@@ -804,21 +532,20 @@ int vpt_render_device_adaptive(vpt_scene* s, const vpt_params* params, const vpt
     return VPT_OK;
   };
   HIP_TRY(hipEventRecord(s->ev0, st));
-  s->host_pause = false;
-  if (int rc = adaptive_update(pr, img, hit, b, 0, 0, *a, params->samples, st)) return rc;
+  s->sched.no_pause();
+  if (int rc = adaptive_update(pr, L.img, L.hit, b, 0, 0, *a, params->samples, st)) return rc;
   if (int rc = read_info()) return rc;
   if (info[1] < info[2]) return vpt_set_error(VPT_ERR_INVALID_ARG, "hits[] must be equal on entry (found %d .. %d)", info[1], info[2]);
-  const launch_ctx L = {s, params, pr, dim3((unsigned)full), dim3(VPT_BLOCK), st, img, hit, rng, stack};
   int       h = info[1], n = 0;   // hits of every pixel still rendering, rounds so far
   long long taken = 0;
   for (int active = info[0]; active > 0 && h < params->samples; active = info[0]) {
     DParams rp  = pr;
     rp.nsamples = std::min(a->step, params->samples - h);
     const sched_cfg sch = {nullptr, nullptr, b.lane_slot};
-    launch_instance(L, dim3((unsigned)((active + VPT_BLOCK - 1) / VPT_BLOCK)), rp, sch);
+    launcher_of(params->shader)(L, false, dim3((unsigned)((active + VPT_BLOCK - 1) / VPT_BLOCK)), rp, sch);
     HIP_TRY(hipGetLastError());
     taken += (long long)active * rp.nsamples, h += rp.nsamples, n++;
-    if (int rc = adaptive_update(pr, img, hit, b, n, rp.nsamples, *a, params->samples, st)) return rc;
+    if (int rc = adaptive_update(pr, L.img, L.hit, b, n, rp.nsamples, *a, params->samples, st)) return rc;
     if (int rc = read_info()) return rc;
     if (implicit)
       if (int rc = vpt_check_watchdog(s)) return rc;
@@ -841,15 +568,10 @@ int vpt_render_adaptive(vpt_scene* s, const vpt_params* params, const vpt_adapti
     if (hits[i] != hits[0]) return vpt_set_error(VPT_ERR_INVALID_ARG, "hits[] must be equal on entry (pixel %lld has %d, pixel 0 %d)", i, hits[i], hits[0]);
   *samples_io = hits[0];
   if (hits[0] >= params->samples) return VPT_OK;
-  HIP_TRY(hipSetDevice(s->device));
-  vpt_layout lay = {width, height, 8, 8, 0, 1};
-  if (int rc = stage_host_state(s, lay)) return rc;
-  void *t_image = s->s_image.get(), *t_hits = s->s_hits.get(), *t_rng = s->s_rng.get();
-  void *r_image = s->r_image.get(), *r_hits = s->r_hits.get(), *r_rng = s->r_rng.get();
-  if (int rc = state_upload(&lay, image_rgba, hits, rng, t_image, t_hits, t_rng, nullptr, r_image, r_hits, r_rng)) return rc;
-  if (int rc = vpt_render_device_adaptive(s, params, a, &lay, t_image, t_hits, t_rng, nullptr, nullptr, rendered)) return rc;
-  if (int rc = state_download(&lay, t_image, t_hits, t_rng, image_rgba, hits, rng, nullptr, r_image, r_hits, r_rng, true)) return rc;
-  if (int rc = vpt_check_watchdog(s)) return rc;
+  if (int rc = render_host_state(s, width, height, image_rgba, hits, rng, [&](const vpt_layout* lay, tile_state t) {
+        return vpt_render_device_adaptive(s, params, a, lay, t.image, t.hits, t.rng, nullptr, nullptr, rendered);
+      }))
+    return rc;
   *samples_io = *std::max_element(hits, hits + pixels);
   return VPT_OK;
 }
@@ -862,16 +584,10 @@ int vpt_render(vpt_scene* s, const vpt_params* params, int nsamples, int width, 
   int todo = params->samples - *samples_io;   // no-op once reached, yocto_pathtrace.cpp:1055
   if (nsamples < todo) todo = nsamples;
   if (todo <= 0) return VPT_OK;
-  HIP_TRY(hipSetDevice(s->device));
-  vpt_layout lay = {width, height, 8, 8, 0, 1};
-  if (int rc = stage_host_state(s, lay)) return rc;
-  void *t_image = s->s_image.get(), *t_hits = s->s_hits.get(), *t_rng = s->s_rng.get();
-  void *r_image = s->r_image.get(), *r_hits = s->r_hits.get(), *r_rng = s->r_rng.get();
-  if (int rc = state_upload(&lay, image_rgba, hits, rng, t_image, t_hits, t_rng, nullptr, r_image, r_hits, r_rng)) return rc;
-  if (int rc = vpt_render_device(s, params, &lay, todo, t_image, t_hits, t_rng, nullptr)) return rc;
-  // the row-major staging still holds the frame that was uploaded, and this single-rank layout owns every pixel
-  if (int rc = state_download(&lay, t_image, t_hits, t_rng, image_rgba, hits, rng, nullptr, r_image, r_hits, r_rng, true)) return rc;
-  if (int rc = vpt_check_watchdog(s)) return rc;
+  if (int rc = render_host_state(s, width, height, image_rgba, hits, rng, [&](const vpt_layout* lay, tile_state t) {
+        return vpt_render_device(s, params, lay, todo, t.image, t.hits, t.rng, nullptr);
+      }))
+    return rc;
   *samples_io += todo;
   return VPT_OK;
 }

@@ -180,7 +180,7 @@ __device__ __forceinline__ void implicit_kernel_body(const DScene& sc, const DPa
   const int wave = sched.order ? sched.order[blockIdx.x] : (int)blockIdx.x;
 
   int slot = wave * VPT_BLOCK + threadIdx.x;
-  if (sched.lane_slot) slot = sched.lane_slot[slot];   // a split tile (vpt_capi.hip): this wave holds every 2^k-th pixel of it in its first lanes
+  if (sched.lane_slot) slot = sched.lane_slot[slot];   // a split tile (vpt_schedule.hip): this wave holds every 2^k-th pixel of it in its first lanes
   int px = 0, py = 0;
   const bool owner = slot >= 0 && slot < pr.nslots && slot_to_pixel(pr, slot, px, py);   // padding lanes own no pixel: they stay M_DONE
   if (__builtin_amdgcn_ballot_w64(owner) == 0) return;
@@ -422,7 +422,7 @@ __global__ void vpt_render_kernel(DScene sc, DParams pr, float4* __restrict__ im
     int* __restrict__ hits, ulonglong2* __restrict__ rngs, int stack_cap, sched_cfg sched, unsigned* __restrict__ watchdog, unsigned long long watchdog_ticks) {
   implicit_kernel_body<SH, FEAT>(sc, pr, image, hits, rngs, stack_cap, sched, watchdog, watchdog_ticks);
 }
-// The same kernel under another name: the short launch that measures per-wave costs when none are known yet (vpt_capi.hip),
+// The same kernel under another name: the short launch that measures per-wave costs when none are known yet (vpt_schedule.h),
 // kept apart so that profiles of vpt_render_kernel only hold full launches (as vpt_mesh_pilot_kernel for K1).
 template <int SH, int FEAT>
 __global__ void vpt_render_pilot_kernel(DScene sc, DParams pr, float4* __restrict__ image,

@@ -1,4 +1,4 @@
-// vpt_launch.h — the kernels the host launches (vpt_capi.hip): declarations only, with their launch bounds, the types of their
+// vpt_launch.h — the kernels the host launches (vpt_capi.hip, vpt_schedule.hip): declarations only, with their launch bounds, the types of their
 // arguments and the launch constants both sides need.  vpt_capi.hip sees no kernel body: each kernel is defined, and its instances
 // instantiated, in exactly one kernel unit, so that a host-side edit recompiles no kernel and no kernel is compiled twice:
 //   vpt_k1_volpath.hip, vpt_k1_path.hip   K1 (vpt_mesh_kernel.hip.h) for the two path tracers        (the instance lists:
@@ -35,7 +35,7 @@ struct sched_cfg {
   const int* order;       // blockIdx.x -> wave index, or null: identity
   unsigned*  cost;        // per wave: duration of this launch in 100 MHz ticks, or null
   const int* lane_slot;   // [wave][64] -> state slot of the lane (-1: none), or null: slot = wave * 64 + lane (one tile per wave).
-                          // Set when costly tiles run as several partly filled waves (vpt_capi.hip: tile splitting)
+                          // Set when costly tiles run as several partly filled waves (vpt_schedule.hip: tile splitting)
 };
 
 // ---- K1: the mesh shaders (vpt_mesh_kernel.hip.h); the pilot is the same kernel under another name --------------------------

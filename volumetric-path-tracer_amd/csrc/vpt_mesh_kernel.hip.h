@@ -1017,7 +1017,7 @@ __global__ void vpt_mesh_kernel(DScene sc, DParams pr,
   mesh_kernel_body<SH, SPILL, FEAT>(sc, pr, image, hits, rngs, stack, sched);
 }
 // The same kernel under another name: the one-sample launch that measures per-wave costs when none are
-// known yet (vpt_capi.hip).  Kept apart so that profiles of vpt_mesh_kernel only hold full launches.
+// known yet (vpt_schedule.h).  Kept apart so that profiles of vpt_mesh_kernel only hold full launches.
 template <int SH, bool SPILL, int FEAT>
 __global__ void vpt_mesh_pilot_kernel(DScene sc, DParams pr,
     float4* __restrict__ image, int* __restrict__ hits, ulonglong2* __restrict__ rngs, stack_cfg stack, sched_cfg sched) {

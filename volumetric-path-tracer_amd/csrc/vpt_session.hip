@@ -10,7 +10,7 @@
 #include <cstring>
 #include <utility>
 
-#include "vpt_adaptive.h"   // vpt_make_dparams
+#include "vpt_adaptive.h"   // vpt_layout_dparams
 #include "vpt_device_buffer.h"
 #include "vpt_error.h"
 #include "vpt_kernels.hip.h"   // slot_to_pixel
@@ -107,9 +107,8 @@ extern "C" {
 
 int vpt_state_init_device(const vpt_layout* layout, void* d_image, void* d_hits, void* d_rng, void* stream) {
   REQUIRE(layout && d_image && d_hits && d_rng, "null argument");
-  DParams    pr;
-  vpt_params dummy = {};
-  if (int rc = vpt_make_dparams(&dummy, layout, 0, pr)) return rc;
+  DParams pr;
+  if (int rc = vpt_layout_dparams(layout, pr)) return rc;
   jump_table      tab;
   const vpt_pcg32 master = vpt_pcg32_make(VPT_STATE_MASTER_SEED, 1);
   for (int q = 0; q < 64; q++) tab.e[q] = vpt_pcg32_jump(master.inc, (uint64_t)(q >> 3) * (uint64_t)pr.width + (uint64_t)(q & 7));
@@ -452,9 +451,8 @@ int vpt_session_get_state(vpt_session* s, float* image_rgba, int32_t* hits, uint
     if (int rc = s->r_rng.allocate(n * 16)) return rc;
     s->r_pixels = (long long)n;
   }
-  DParams    pr;
-  vpt_params dummy = {};
-  if (int rc = vpt_make_dparams(&dummy, &s->lay, 0, pr)) return rc;
+  DParams pr;
+  if (int rc = vpt_layout_dparams(&s->lay, pr)) return rc;
   // the one-rank layout owns every pixel: the row-major staging is written in full
   hipLaunchKernelGGL(vpt_permute_kernel, dim3((pr.nslots + 255) / 256), dim3(256), 0, s->st, pr, 0, s->s_image.get<float4>(), s->s_hits.get<int>(),
       s->s_rng.get<ulonglong2>(), s->r_image.get<float4>(), s->r_hits.get<int>(), s->r_rng.get<ulonglong2>());
