@@ -324,6 +324,44 @@ int vpt_scene_get_bvh(vpt_scene* scene, vpt_bvh_node* scene_nodes, int scene_cap
  * instead of finishing the narrow top levels of a tree in one launch: same bits (the tests' and the measurements' A/B switch). */
 int vpt_scene_update_stats(const vpt_scene* scene, int* launches, int64_t* bytes, float* device_ms);
 
+/* ---- edits that change the lights: the light tables rebuilt on the device ------------------------------------------
+ * vpt_scene_update_lights takes the edit of vpt_scene_update under the same validation with its two refusals about lights lifted:
+ * a material's emission may switch between zero and non-zero, and the vertices of a shape that a light's instance uses may move.
+ * vpt_scene_update itself is unchanged and keeps refusing both.
+ *  - The refit runs exactly as in vpt_scene_update (edited shapes first, then the scene BVH).  Afterwards every light table on the
+ *    device - lights, light_cdf, the light records, light_prims, the search index with its pool, the guide table, num_lights -
+ *    holds the bytes vpt_scene_create would upload for the edited descriptor carrying make_lights of the edited scene, so every
+ *    render, vpt_intersect and vpt_kat call gives the bits of a fresh handle.
+ *  - The list = make_lights (yocto_pathtrace.cpp:983-1049): instances in id order whose material has emission != 0 and whose shape
+ *    holds triangles or quads (shapes of points or lines never become lights); then the environments in id order (the edit has no
+ *    field for their emission or texture: their entries and CDFs are kept byte for byte); then SDFs in id order whose material is
+ *    emissive, cdf = {whd.x * whd.y}.  An empty list is valid.  cdf_offset = the sum of the earlier lengths.
+ *  - The element CDF: cdf[0] = area_0, cdf[i] = area_i + cdf[i - 1], float32, in element order; triangle_area = length(cross(p1 - p0,
+ *    p2 - p0)) / 2, quad_area = triangle_area(p0, p1, p3) + triangle_area(p2, p3, p1) (yocto_geometry.h:506-518); no operation fused,
+ *    the square root correctly rounded.  Float addition is not associative: the additions run in the reference's order, a serial
+ *    chain per light (lights side by side), never a tree or a block scan.  A mesh light's CDF is recomputed only when the light is
+ *    new or its shape is in the edit; every other CDF, the environment's included, moves device to device.  Nothing proportional to
+ *    an element or texel count crosses PCIe: vpt_scene_update_stats counts the edit's payload plus a few words per light.
+ *  - The search structures of the recomputed lights are those of creation: an index only for more than 64 non-decreasing entries
+ *    (NaN: none), 16-ary levels padded with +inf, the guide table with the same double-precision bounds, nextafter widening and
+ *    upper_bound brackets.  A light whose CDF moved keeps its index, offsets rebased.
+ *  - The kernel instances follow the new list (the features the lights need are recomputed): an all-triangle scene that gains an
+ *    emissive mesh with a BVH leaves the compact-record instance, K2's lean instance follows the same rule.  Stack sizes depend on
+ *    topology and stay.
+ *  - An edit without consequence for the lights - the list stays as it is and no moved shape belongs to one of its lights - does
+ *    exactly what vpt_scene_update does: the same launches, the same bytes.
+ *  - Synchronisation, failure semantics and the forgetting of the launch-schedule record: those of vpt_scene_update.
+ *  - VPT_LIGHTS_PLAIN=1 in the environment, read per call, runs the running sum as one lane per light straight from global memory
+ *    instead of the wave form (64 areas per load, the chain through a cross-lane move): same bits (the tests' and the measurements'
+ *    A/B switch). */
+int vpt_scene_update_lights(vpt_scene* scene, const vpt_scene_edit* edit);
+/* The light list and the CDF pool as the device holds them now, for callers that keep a host copy, and for the tests.  Capacities
+ * in entries; a null array is skipped; *num_lights / *num_cdf (either may be null) are set even when a capacity is too small. */
+int vpt_scene_get_lights(vpt_scene* scene, vpt_light* lights, int light_capacity, int* num_lights, float* cdf, int64_t cdf_capacity, int64_t* num_cdf);
+/* FNV-1a (64 bit) over six things read back from the device: the light list, the CDF pool, the light records, light_prims, the
+ * search index followed by its pool, the guide table.  For the tests: an updated handle against a fresh one. */
+int vpt_scene_light_tables_hash(vpt_scene* scene, uint64_t out[6]);
+
 /* ---- the drop-in for pathtrace_samples() --------------------------------------------
  * Host, row-major (idx = j*width + i) caller-owned state, exactly pathtrace_state
  * (yocto_pathtrace.h:57-64): image float4[w*h], hits int32[w*h], rng {u64 state, u64 inc}[w*h].
@@ -363,6 +401,8 @@ void vpt_multi_destroy(vpt_multi* m);
 /* vpt_scene_update with the same edit on every device of `m`, one after the other; an edit the first device refuses has changed
  * none.  The resident tile state is left as it is. */
 int  vpt_multi_update(vpt_multi* m, const vpt_scene_edit* edit);
+/* vpt_scene_update_lights in the same way */
+int  vpt_multi_update_lights(vpt_multi* m, const vpt_scene_edit* edit);
 int  vpt_multi_device_count(const vpt_multi* m);
 /* how vpt_multi_get_render moves the parts: "rccl", "peer-copy" (several devices, no RCCL) or "local" (one device) */
 const char* vpt_multi_transport(const vpt_multi* m);
@@ -607,6 +647,8 @@ int  vpt_session_reset(vpt_session* session, const vpt_session_params* params_or
 int  vpt_session_advance(vpt_session* session, int nsamples);
 int  vpt_session_set_display(vpt_session* session, const vpt_display_params* display);
 int  vpt_session_edit(vpt_session* session, const vpt_scene_edit* edit);
+/* the same through vpt_scene_update_lights: an edit that switches a light on or off, or moves an emitter's vertices */
+int  vpt_session_edit_lights(vpt_session* session, const vpt_scene_edit* edit);
 int  vpt_session_get_display(vpt_session* session, uint8_t* rgba8, float* display_f);
 int  vpt_session_get_image(vpt_session* session, float* linear);
 int  vpt_session_get_denoised(vpt_session* session, float* linear);

@@ -216,6 +216,11 @@ hip.vpt_scene_destroy.argtypes = [_p]
 hip.vpt_scene_destroy.restype = None
 hip.vpt_scene_update.argtypes = [_p, C.POINTER(VptSceneEdit)]
 hip.vpt_multi_update.argtypes = [_p, C.POINTER(VptSceneEdit)]
+hip.vpt_scene_update_lights.argtypes = [_p, C.POINTER(VptSceneEdit)]
+hip.vpt_multi_update_lights.argtypes = [_p, C.POINTER(VptSceneEdit)]
+hip.vpt_session_edit_lights.argtypes = [_p, C.POINTER(VptSceneEdit)]
+hip.vpt_scene_get_lights.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int), _p, C.c_int64, C.POINTER(C.c_int64)]
+hip.vpt_scene_light_tables_hash.argtypes = [_p, _p]
 hip.vpt_scene_get_bvh.argtypes = [_p, _p, C.c_int, _p, C.c_int64]
 hip.vpt_scene_update_stats.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
 hip.vpt_render.argtypes = [_p, C.POINTER(VptParams), C.c_int, C.c_int, C.c_int, _p, _p, _p, C.POINTER(C.c_int)]
@@ -295,6 +300,7 @@ host.vpth_scene_get_item.argtypes = [_p, C.c_int, C.c_int, _p, C.c_int64]
 host.vpth_scene_get_item.restype = C.c_int64
 host.vpth_scene_set_item.argtypes = [_p, C.c_int, C.c_int, _p, C.c_int64, C.c_char_p, C.c_int]
 host.vpth_scene_update_bvh.argtypes = [_p, C.c_char_p, C.c_int]
+host.vpth_scene_update_lights.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_free.restype = None
 host.vpth_scene_desc.argtypes = [_p]
 host.vpth_scene_desc.restype = _p
@@ -337,6 +343,17 @@ class VptSceneDescBvh(C.Structure):
                 ("scene_bvh_prims", C.c_void_p), ("num_shape_bvh_nodes", C.c_int64), ("shape_bvh_nodes", C.c_void_p),
                 ("num_shape_bvh_prims", C.c_int64), ("shape_bvh_prims", C.c_void_p)]
     OFFSET = 20 * 16
+
+
+LIGHT = np.dtype([("instance", np.int32), ("environment", np.int32), ("sdf", np.int32), ("cdf_len", np.int32), ("cdf_offset", np.int64)])   # vpt_light
+assert LIGHT.itemsize == 24
+
+
+class VptSceneDescLights(C.Structure):
+    """vpt_scene_desc up to its CDF pool, for the two tables of the lights: the tenth {int32 count, pointer} pair and the tenth
+    {int64 count, pointer} pool"""
+    _fields_ = [("tables", C.c_byte * (9 * 16)), ("num_lights", C.c_int32), ("lights", C.c_void_p), ("pools", C.c_byte * (9 * 16)),
+                ("num_light_cdf", C.c_int64), ("light_cdf", C.c_void_p)]
 
 
 def build_bvh(bboxes: np.ndarray, device: Optional[int] = 0):
@@ -535,6 +552,21 @@ class HostScene:
         edit, self._edit = self._pending(), None
         return edit
 
+    def update_lights(self) -> SceneEdit:
+        """update_bvh(), then make_lights of the edited scene (an emission switched on or off, an emitter's vertices moved): desc /
+        stats() carry the new light list and CDFs.  Returns the SceneEdit for DeviceScene.update_lights."""
+        edit = self.update_bvh()
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_update_lights(self.handle, err, len(err)) != 0:
+            raise VptError(err.value.decode())
+        return edit
+
+    def lights(self):
+        """(light list as a LIGHT array, CDF pool as float32) of the descriptor (copies)"""
+        d = VptSceneDescLights.from_address(self.desc)
+        grab = lambda ptr, n, dtype: np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (n * dtype.itemsize,)).view(dtype).copy() if n else np.zeros(0, dtype)
+        return grab(d.lights, d.num_lights, LIGHT), grab(d.light_cdf, d.num_light_cdf, np.dtype(np.float32))
+
     def bvh_nodes(self):
         """(scene nodes, pooled shape nodes) of the descriptor as BVH_NODE arrays (copies)"""
         d = VptSceneDescBvh.from_address(self.desc + VptSceneDescBvh.OFFSET)
@@ -621,6 +653,28 @@ class DeviceScene:
         abi, keep = edit.to_abi()
         _check(hip.vpt_scene_update(self.handle, C.byref(abi)), "vpt_scene_update")
         del keep
+
+    def update_lights(self, edit: SceneEdit) -> None:
+        """vpt_scene_update_lights (include/vpt.h): update() for an edit that may switch a material's emission between zero and non-zero
+        or move the vertices of an emitter; the light tables are rebuilt on the device.  Afterwards the handle renders the bits of a
+        DeviceScene made from the host scene after the same edit and update_lights()."""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_scene_update_lights(self.handle, C.byref(abi)), "vpt_scene_update_lights")
+        del keep
+
+    def get_lights(self):
+        """(light list as a LIGHT array, CDF pool as float32) as the device holds them (vpt_scene_get_lights)"""
+        n, m = C.c_int(0), C.c_int64(0)
+        _check(hip.vpt_scene_get_lights(self.handle, None, 0, C.byref(n), None, 0, C.byref(m)), "vpt_scene_get_lights")
+        lights, cdf = np.zeros(n.value, LIGHT), np.zeros(m.value, np.float32)
+        _check(hip.vpt_scene_get_lights(self.handle, lights.ctypes.data, len(lights), None, cdf.ctypes.data, len(cdf), None), "vpt_scene_get_lights")
+        return lights, cdf
+
+    def light_tables_hash(self):
+        """FNV-1a of the six light tables on the device (vpt_scene_light_tables_hash): lights, cdf, records, prims, index + pool, guide"""
+        out = np.zeros(6, np.uint64)
+        _check(hip.vpt_scene_light_tables_hash(self.handle, out.ctypes.data), "vpt_scene_light_tables_hash")
+        return tuple(int(x) for x in out)
 
     def get_bvh(self):
         """(scene nodes, pooled shape nodes) as the device holds them, BVH_NODE arrays (vpt_scene_get_bvh)"""
@@ -709,6 +763,12 @@ class MultiDeviceScene:
         """vpt_multi_update: the same edit on every device; the resident tile state is left as it is"""
         abi, keep = edit.to_abi()
         _check(hip.vpt_multi_update(self.handle, C.byref(abi)), "vpt_multi_update")
+        del keep
+
+    def update_lights(self, edit: SceneEdit) -> None:
+        """vpt_multi_update_lights: DeviceScene.update_lights with the same edit on every device"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_multi_update_lights(self.handle, C.byref(abi)), "vpt_multi_update_lights")
         del keep
 
     def pathtrace_samples(self, state: PathtraceState, params: PathtraceParams, count: int = 1) -> None:
@@ -992,6 +1052,12 @@ class RenderSession:
         leaves the session as it was"""
         abi, keep = edit.to_abi()
         _check(hip.vpt_session_edit(self.handle, C.byref(abi)), "vpt_session_edit")
+        del keep
+
+    def edit_lights(self, edit: SceneEdit) -> None:
+        """edit() through vpt_scene_update_lights, with the SceneEdit of HostScene.update_lights()"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_session_edit_lights(self.handle, C.byref(abi)), "vpt_session_edit_lights")
         del keep
 
     @property

@@ -18,6 +18,7 @@
 #include "vpt_error.h"
 #include "vpt_kat.h"
 #include "vpt_launch.h"
+#include "vpt_light_update.h"
 #include "vpt_schedule.h"
 #include "vpt_scene_prep.h"
 #include "vpt_scene_update.h"
@@ -63,6 +64,7 @@ struct vpt_scene {
   host_mirrors h;   // range checks of vpt_intersect, vpt_kat
   long long     num_shape_nodes = 0;   // nodes of d.shape_nodes (vpt_scene_get_bvh)
   scene_updater upd;                   // vpt_scene_update: levels and quad-slot tables, built on the first update
+  light_updater lights_upd;            // vpt_scene_update_lights: sizes of the pooled light tables, mirrors built on the first rebuild
 };
 
 namespace {
@@ -173,6 +175,7 @@ int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* 
   D.shape_wnodes = D.scene_wnodes + t.scene_wnodes;
   s->stack_cap = t.stack_cap, s->stack_lds4 = t.stack_lds4, s->stack_spill4 = t.stack_spill4, s->light_features = t.light_features;
   s->curves = t.curves, s->num_shape_nodes = d.num_shape_bvh_nodes;
+  s->lights_upd.num_cdf = d.num_light_cdf, s->lights_upd.num_pool = (long long)t.light_index_pool.size(), s->lights_upd.num_guide = (long long)t.light_guide.size();
   s->h = std::move(t.h);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -390,14 +393,56 @@ int vpt_scene_record_bytes(const vpt_scene* s, int* leaf_bytes, int* attribute_b
 }
 
 // ---- editing a resident scene (include/vpt.h; the work is vpt_scene_update.hip's) ---------------------------------------------
-int vpt_scene_update(vpt_scene* s, const vpt_scene_edit* edit) {
+// lights: vpt_scene_update_lights - the two refusals about lights are lifted and the light tables follow the edit
+static int scene_update(vpt_scene* s, const vpt_scene_edit* edit, bool lights) {
   if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call rewrites
-  if (int rc = scene_update_apply(s->d, s->h, s->num_shape_nodes, s->upd, *edit)) return rc;
-  if (edit->num_instances > 0 || edit->num_shapes > 0)
+  if (int rc = scene_update_apply(s->d, s->h, s->num_shape_nodes, s->upd, *edit, lights)) return rc;
+  bool rebuilt = false;
+  if (lights)
+    if (int rc = light_update_apply(s->d, s->h, s->upd, s->lights_upd, s->tables, *edit, &s->light_features, &rebuilt)) return rc;
+  if (rebuilt || edit->num_instances > 0 || edit->num_shapes > 0)
     if (int rc = light_setup(s)) return rc;   // light_prims hold world-space normals of the moved lights
   s->sched.forget();   // the camera index may be the same, the picture is not
+  return VPT_OK;
+}
+int vpt_scene_update(vpt_scene* s, const vpt_scene_edit* edit) { return scene_update(s, edit, false); }
+int vpt_scene_update_lights(vpt_scene* s, const vpt_scene_edit* edit) { return scene_update(s, edit, true); }
+
+// the light list and the CDF pool as the device holds them now
+int vpt_scene_get_lights(vpt_scene* s, vpt_light* lights, int light_capacity, int* num_lights, float* cdf, int64_t cdf_capacity, int64_t* num_cdf) {
+  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (num_lights) *num_lights = s->d.num_lights;
+  if (num_cdf) *num_cdf = s->lights_upd.num_cdf;
+  REQUIRE(!lights || light_capacity >= s->d.num_lights, "light_capacity %d < %d lights", light_capacity, s->d.num_lights);
+  REQUIRE(!cdf || cdf_capacity >= s->lights_upd.num_cdf, "cdf_capacity %lld < %lld cdf entries", (long long)cdf_capacity, s->lights_upd.num_cdf);
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (lights && s->d.num_lights) HIP_TRY(hipMemcpy(lights, s->d.lights, (size_t)s->d.num_lights * sizeof(vpt_light), hipMemcpyDeviceToHost));
+  if (cdf && s->lights_upd.num_cdf) HIP_TRY(hipMemcpy(cdf, s->d.light_cdf, (size_t)s->lights_upd.num_cdf * sizeof(float), hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+
+// FNV-1a over the six light tables read back from the device: lights, light_cdf, light_rec, light_prims, light_index + its pool, light_guide
+int vpt_scene_light_tables_hash(vpt_scene* s, uint64_t out[6]) {
+  if (!s || !out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t nl = (size_t)s->d.num_lights;
+  const struct { const void* table; size_t bytes; int slot; } parts[7] = {
+      {s->d.lights, nl * sizeof(vpt_light), 0}, {s->d.light_cdf, (size_t)s->lights_upd.num_cdf * sizeof(float), 1}, {s->d.light_rec, 8 * nl * sizeof(float4), 2},
+      {s->d.light_prims, 20 * nl * sizeof(float4), 3}, {s->d.light_index, nl * sizeof(DCdfIndex), 4},
+      {s->d.light_index_pool, (size_t)s->lights_upd.num_pool * sizeof(float), 4}, {s->d.light_guide, (size_t)s->lights_upd.num_guide * sizeof(int2), 5}};
+  for (int k = 0; k < 6; k++) out[k] = 14695981039346656037ull;
+  std::vector<unsigned char> host;
+  for (const auto& p : parts) {
+    host.resize(p.bytes);
+    if (p.bytes) HIP_TRY(hipMemcpy(host.data(), p.table, p.bytes, hipMemcpyDeviceToHost));
+    uint64_t hash = out[p.slot];
+    for (unsigned char b : host) hash = (hash ^ b) * 1099511628211ull;
+    out[p.slot] = hash;
+  }
   return VPT_OK;
 }
 

@@ -1,0 +1,25 @@
+// vpt_light_update.h — rebuilding the light tables of a resident scene (include/vpt.h: vpt_scene_update_lights):
+// what a vpt_scene keeps for it and the call vpt_capi.hip forwards to.  Kernels and host logic: vpt_light_update.hip.
+#pragma once
+#include <vector>
+
+#include "vpt_device_buffer.h"
+#include "vpt_scene_update.h"
+
+struct light_updater {
+  // entries of the three pooled light tables the device holds now (set at creation, kept by every rebuild)
+  long long num_cdf = 0, num_pool = 0, num_guide = 0;
+  // host copies of the small tables the list and the layout are decided from, read back on the first rebuild of a handle
+  bool ready = false;
+  std::vector<DCdfIndex> index;   // DScene::light_index
+  std::vector<vpt_sdf>   sdfs;    // DScene::sdfs: material and whd of an SDF light
+  device_buffer d_jobs, d_result, d_tags;   // the recomputed lights' descriptors, {sorted, last entry} per job, record tags per light
+};
+
+// After scene_update_apply(.., lights = true) has written the edit: the light list of the edited scene (make_lights) from the host
+// mirrors, and - when the list changed or an edited shape belongs to one of its lights - every light table on the device rebuilt to
+// the bytes vpt_scene_create would upload.  Tables that change are allocated anew and take the place of their predecessor in
+// `tables`; d's pointers and num_lights, u's light mirrors and *light_features follow.  *rebuilt: false for an edit without
+// consequence for the lights (nothing was launched or sent).  Stream 0; the device has finished when the call returns.
+int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light_updater& lu, std::vector<device_buffer>& tables,
+    const vpt_scene_edit& edit, int* light_features, bool* rebuilt);

@@ -23,6 +23,7 @@ struct scene_updater {
   std::vector<vpt_light>    lights;
   std::vector<int>          light_kind;      // VPT_LIGHT_* of every light record
   std::vector<char>         shape_lit;       // some light's instance uses the shape
+  std::vector<int>          inst_material, inst_flags;   // DInstance::material / shape_flags: the light list of an edited scene (vpt_light_update.hip)
   bvh_levels                scene_levels;
   std::vector<bvh_levels>   shape_levels;
   device_buffer d_order;        // int
@@ -41,4 +42,6 @@ struct scene_updater {
 
 // Validates `edit` against the scene (nothing is written before it has passed), then rewrites the tables on the current device,
 // stream 0; returns after the device has finished.  d.scene_root_* are refreshed.  num_shape_nodes: nodes of DScene::shape_nodes.
-int scene_update_apply(DScene& d, const host_mirrors& h, long long num_shape_nodes, scene_updater& u, const vpt_scene_edit& edit);
+// lights: the caller rebuilds the light tables afterwards (vpt_scene_update_lights, vpt_light_update.h), so an emission that
+// switches between zero and non-zero and moved vertices of a light's shape pass validation.
+int scene_update_apply(DScene& d, const host_mirrors& h, long long num_shape_nodes, scene_updater& u, const vpt_scene_edit& edit, bool lights = false);

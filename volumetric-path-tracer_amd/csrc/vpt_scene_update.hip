@@ -294,7 +294,7 @@ int updater_init(const DScene& d, long long num_shape_nodes, scene_updater& u) {
     u.light_kind[(size_t)l] = tag & 255;
   }
   u.textured.assign((size_t)d.num_materials, 0), u.shape_lit.assign((size_t)d.num_shapes, 0);
-  for (const DInstance& in : instances) u.textured[(size_t)in.material] = 1;
+  for (const DInstance& in : instances) u.textured[(size_t)in.material] = 1, u.inst_material.push_back(in.material), u.inst_flags.push_back(in.shape_flags);
   for (const vpt_light& l : u.lights)
     if (l.instance >= 0) u.shape_lit[(size_t)instances[(size_t)l.instance].shape] = 1;
   std::vector<int> order, slots;
@@ -337,7 +337,7 @@ int check_ids(const char* what, int n, const int32_t* ids, const void* payload, 
 }
 bool emissive(const vpt_material& m) { return !(m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0); }   // make_lights, yocto_pathtrace.cpp:990
 
-int validate_edit(const DScene& d, const host_mirrors& h, const scene_updater& u, const vpt_scene_edit& e) {
+int validate_edit(const DScene& d, const host_mirrors& h, const scene_updater& u, const vpt_scene_edit& e, bool lights) {
   if (int rc = check_ids("camera", e.num_cameras, e.camera_ids, e.cameras, d.num_cameras)) return rc;
   if (int rc = check_ids("instance", e.num_instances, e.instance_ids, e.instance_frames, d.num_instances)) return rc;
   if (int rc = check_ids("environment", e.num_environments, e.environment_ids, e.environment_frames, d.num_environments)) return rc;
@@ -355,7 +355,7 @@ int validate_edit(const DScene& d, const host_mirrors& h, const scene_updater& u
     REQUIRE(finite_all(m.emission, 3) && finite_all(m.color, 3) && finite_all(&m.roughness, 3) && finite_all(m.scattering, 3) && finite_all(&m.scanisotropy, 3),
         "edit: material entry %d: a value is not finite", i);
     if (int rc = prep_check_material(m, id, d.num_textures, u.textured[(size_t)id] != 0)) return rc;
-    if (emissive(m) != emissive(u.materials[(size_t)id]))
+    if (!lights && emissive(m) != emissive(u.materials[(size_t)id]))
       return vpt_set_error(VPT_ERR_UNSUPPORTED, "edit: material entry %d: emission of material %d changes between zero and non-zero (the light list is fixed at creation)", i, id);
   }
   for (int i = 0; i < e.num_shapes; i++) {
@@ -368,7 +368,7 @@ int validate_edit(const DScene& d, const host_mirrors& h, const scene_updater& u
       REQUIRE(u.shapes[(size_t)id].normal_offset >= 0, "edit: shape entry %d: shape %d has no normals", i, id);
       REQUIRE(finite_all(nrm, n), "edit: shape entry %d: a normal is not finite", i);
     }
-    if (u.shape_lit[(size_t)id])
+    if (!lights && u.shape_lit[(size_t)id])
       return vpt_set_error(VPT_ERR_UNSUPPORTED, "edit: shape entry %d: shape %d belongs to a light's instance (its element cdf is made from the areas)", i, id);
   }
   return VPT_OK;
@@ -429,10 +429,10 @@ int refit_internal_levels(scene_updater& u, float4* nodes, long long base, const
 
 }  // namespace
 
-int scene_update_apply(DScene& d, const host_mirrors& h, long long num_shape_nodes, scene_updater& u, const vpt_scene_edit& e) {
+int scene_update_apply(DScene& d, const host_mirrors& h, long long num_shape_nodes, scene_updater& u, const vpt_scene_edit& e, bool lights) {
   if (!u.ready)
     if (int rc = updater_init(d, num_shape_nodes, u)) return rc;
-  if (int rc = validate_edit(d, h, u, e)) return rc;   // every refusal happens here: nothing has been written
+  if (int rc = validate_edit(d, h, u, e, lights)) return rc;   // every refusal happens here: nothing has been written
   u.last_launches = 0, u.last_bytes = 0, u.last_ms = 0;
   if (!u.ev0) {
     HIP_TRY(hipEventCreate(&u.ev0));

@@ -392,16 +392,18 @@ int vpt_session_set_display(vpt_session* s, const vpt_display_params* display) {
   return tonemap_display(s);
 }
 
-int vpt_session_edit(vpt_session* s, const vpt_scene_edit* edit) {
+static int session_edit(vpt_session* s, const vpt_scene_edit* edit, bool lights) {
   REQUIRE(s && edit, "null argument");
   begin_call(s);
-  if (int rc = vpt_scene_update(s->scene, edit)) return rc;   // a refused edit has changed nothing, here or there
+  if (int rc = lights ? vpt_scene_update_lights(s->scene, edit) : vpt_scene_update(s->scene, edit)) return rc;   // a refused edit has changed nothing, here or there
   int     launches = 0;
   int64_t bytes    = 0;
   float   ms       = 0;
   if (vpt_scene_update_stats(s->scene, &launches, &bytes, &ms) == VPT_OK) s->launches += launches, s->up += bytes;
   return reset(s, s->p);
 }
+int vpt_session_edit(vpt_session* s, const vpt_scene_edit* edit) { return session_edit(s, edit, false); }
+int vpt_session_edit_lights(vpt_session* s, const vpt_scene_edit* edit) { return session_edit(s, edit, true); }
 
 int vpt_session_get_display(vpt_session* s, uint8_t* rgba8, float* display_f) {
   REQUIRE(s, "null session");

@@ -232,6 +232,20 @@ int vpth_scene_update_bvh(void* hh, char* err, int errlen) {
     return set_error(err, errlen, e.what()), -1;
   }
 }
+// make_lights of the scene as the setters left it (an emission switched on or off, an emitter's vertices moved), then the flattened
+// descriptor again: the host side of vpt_scene_update_lights.  The BVHs are vpth_scene_update_bvh's business.
+int vpth_scene_update_lights(void* hh, char* err, int errlen) {
+  try {
+    auto& h  = *(host_scene*)hh;
+    h.lights = make_lights(h.scene, pathtrace_params{});
+    auto flat = std::make_unique<flat_scene>();
+    flatten_scene(*flat, h.scene, h.bvh, h.lights);
+    h.flat = std::move(flat);
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
+}
 void vpth_scene_free(void* h) { delete (host_scene*)h; }
 const vpt_scene_desc* vpth_scene_desc(void* h) { return &((host_scene*)h)->flat->desc; }
 const vpt_scene_curves* vpth_scene_curves(void* h) { return ((host_scene*)h)->flat->curves_or_null(); }   // null: no points or lines
