@@ -358,6 +358,14 @@ int vpt_scene_update_lights(vpt_scene* scene, const vpt_scene_edit* edit);
 /* The light list and the CDF pool as the device holds them now, for callers that keep a host copy, and for the tests.  Capacities
  * in entries; a null array is skipped; *num_lights / *num_cdf (either may be null) are set even when a capacity is too small. */
 int vpt_scene_get_lights(vpt_scene* scene, vpt_light* lights, int light_capacity, int* num_lights, float* cdf, int64_t cdf_capacity, int64_t* num_cdf);
+/* The medium records as the device holds them now, for the tests: 12 floats per material = density.xyz, scattering.xyz, emission.xyz,
+ * scanisotropy, 0, 0 - what a volumetric path carries of a material once it is inside (made on the device at creation, remade by
+ * vpt_scene_update / vpt_scene_update_lights when materials change).  capacity in materials; a null array is skipped; *num_materials
+ * (may be null) is set even when the capacity is too small.  *varying (may be null): 1 for a scene where a material of a volumetric
+ * type has a colour, emission or scattering texture or sits on a shape with vertex colours - its media vary over the surface, and it
+ * renders with the kernel instance that carries a path's medium along instead of reading these records.  VPT_MEDIUM_REGS=1 in the
+ * environment, read per launch, renders any scene that way: same bits (the tests' A/B switch). */
+int vpt_scene_get_media(vpt_scene* scene, float* records, int capacity, int* num_materials, int* varying);
 /* FNV-1a (64 bit) over six things read back from the device: the light list, the CDF pool, the light records, light_prims, the
  * search index followed by its pool, the guide table.  For the tests: an updated handle against a fresh one. */
 int vpt_scene_light_tables_hash(vpt_scene* scene, uint64_t out[6]);

@@ -221,6 +221,7 @@ hip.vpt_multi_update_lights.argtypes = [_p, C.POINTER(VptSceneEdit)]
 hip.vpt_session_edit_lights.argtypes = [_p, C.POINTER(VptSceneEdit)]
 hip.vpt_scene_get_lights.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int), _p, C.c_int64, C.POINTER(C.c_int64)]
 hip.vpt_scene_light_tables_hash.argtypes = [_p, _p]
+hip.vpt_scene_get_media.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 hip.vpt_scene_get_bvh.argtypes = [_p, _p, C.c_int, _p, C.c_int64]
 hip.vpt_scene_update_stats.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
 hip.vpt_render.argtypes = [_p, C.POINTER(VptParams), C.c_int, C.c_int, C.c_int, _p, _p, _p, C.POINTER(C.c_int)]
@@ -669,6 +670,20 @@ class DeviceScene:
         lights, cdf = np.zeros(n.value, LIGHT), np.zeros(m.value, np.float32)
         _check(hip.vpt_scene_get_lights(self.handle, lights.ctypes.data, len(lights), None, cdf.ctypes.data, len(cdf), None), "vpt_scene_get_lights")
         return lights, cdf
+
+    def get_media(self):
+        """the medium records of the device, float32 [materials, 12] (vpt_scene_get_media): density, scattering, emission, scanisotropy, 0, 0"""
+        n = C.c_int(0)
+        _check(hip.vpt_scene_get_media(self.handle, None, 0, C.byref(n), None), "vpt_scene_get_media")
+        out = np.zeros((n.value, 12), np.float32)
+        _check(hip.vpt_scene_get_media(self.handle, out.ctypes.data, len(out), None, None), "vpt_scene_get_media")
+        return out
+
+    def media_vary(self) -> bool:
+        """the scene's media vary over the surface (vpt_scene_get_media): it renders with K1's general instance"""
+        v = C.c_int(0)
+        _check(hip.vpt_scene_get_media(self.handle, None, 0, None, C.byref(v)), "vpt_scene_get_media")
+        return bool(v.value)
 
     def light_tables_hash(self):
         """FNV-1a of the six light tables on the device (vpt_scene_light_tables_hash): lights, cdf, records, prims, index + pool, guide"""

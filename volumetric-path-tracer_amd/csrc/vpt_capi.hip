@@ -61,6 +61,7 @@ struct vpt_scene {
   device_buffer d_watchdog;   // unsigned: waves of the implicit kernel that gave up (must stay 0; vpt_implicit_kernel.hip.h)
   int        light_features = 0;      // VPT_FEAT_* bits this scene's lights need from the mesh kernels
   bool       curves = false;          // some instanced shape holds points or lines: the VPT_FEAT_CURVES instances of K1
+  bool       varying_media = false;   // vpt_scene_prep.h: prep_media_vary - K1's general instance, which carries a path's medium in registers
   host_mirrors h;   // range checks of vpt_intersect, vpt_kat
   long long     num_shape_nodes = 0;   // nodes of d.shape_nodes (vpt_scene_get_bvh)
   scene_updater upd;                   // vpt_scene_update: levels and quad-slot tables, built on the first update
@@ -104,6 +105,16 @@ int make_dparams(const vpt_params* p, const vpt_layout* l, int nsamples, DParams
 int light_setup(vpt_scene* s) {
   if (s->d.num_lights <= 0) return VPT_OK;
   hipLaunchKernelGGL(vpt_light_setup_kernel, dim3(s->d.num_lights), dim3(64), 0, 0, s->d, const_cast<float4*>(s->d.light_prims));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  return VPT_OK;
+}
+
+// the medium records behind the light records, by the device's own eval_material_at: at creation and whenever an edit has
+// rewritten materials or rebuilt the table
+int medium_setup(vpt_scene* s) {
+  if (s->d.num_materials <= 0) return VPT_OK;
+  hipLaunchKernelGGL(vpt_medium_setup_kernel, dim3((s->d.num_materials + 63) / 64), dim3(64), 0, 0, s->d, const_cast<float4*>(s->d.light_rec) + 8 * (size_t)s->d.num_lights);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   return VPT_OK;
@@ -174,13 +185,14 @@ int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* 
 #undef UP
   D.shape_wnodes = D.scene_wnodes + t.scene_wnodes;
   s->stack_cap = t.stack_cap, s->stack_lds4 = t.stack_lds4, s->stack_spill4 = t.stack_spill4, s->light_features = t.light_features;
-  s->curves = t.curves, s->num_shape_nodes = d.num_shape_bvh_nodes;
+  s->curves = t.curves, s->varying_media = t.varying_media, s->num_shape_nodes = d.num_shape_bvh_nodes;
   s->lights_upd.num_cdf = d.num_light_cdf, s->lights_upd.num_pool = (long long)t.light_index_pool.size(), s->lights_upd.num_guide = (long long)t.light_guide.size();
   s->h = std::move(t.h);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
   s->sched.compute_units = prop.multiProcessorCount;
   if ((rc = light_setup(s)) != VPT_OK) return rc;
+  if ((rc = medium_setup(s)) != VPT_OK) return rc;
   for (hipEvent_t* e : {&s->ev0, &s->ev1}) HIP_TRY(hipEventCreate(e));
   if ((rc = s->d_watchdog.allocate(4)) != VPT_OK) return rc;
   HIP_TRY(hipMemset(s->d_watchdog.get(), 0, 4));
@@ -260,7 +272,9 @@ template <int K>
 static void launch_mesh_instance(const launch_ctx& L, bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
   vpt_scene* s = L.s;
   size_t lds = (size_t)s->stack_lds4 * 2 * VPT_BLOCK * sizeof(int) + 5 * VPT_BLOCK * sizeof(float);   // (ref, t0) pairs + the parked words
-  const int need = getenv("VPT_NO_LEAN") ? VPT_FEAT_ALL : s->light_features;
+  // (the general instance also for a scene whose media vary over the surface: the others read a medium from its material's record;
+  // VPT_MEDIUM_REGS=1, read per launch, sends any scene there - same bits: the tests' and the measurements' A/B switch)
+  const int need = getenv("VPT_NO_LEAN") || getenv("VPT_MEDIUM_REGS") || s->varying_media ? VPT_FEAT_ALL : s->light_features;
   auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(VPT_BLOCK), lds, L.st, s->d, pr, L.img, L.hit, L.rng, L.stack, sch); };
   auto launch_feat = [&](auto feat) {
     constexpr int F = decltype(feat)::value;
@@ -404,6 +418,10 @@ static int scene_update(vpt_scene* s, const vpt_scene_edit* edit, bool lights) {
     if (int rc = light_update_apply(s->d, s->h, s->upd, s->lights_upd, s->tables, *edit, &s->light_features, &rebuilt)) return rc;
   if (rebuilt || edit->num_instances > 0 || edit->num_shapes > 0)
     if (int rc = light_setup(s)) return rc;   // light_prims hold world-space normals of the moved lights
+  if (rebuilt || edit->num_materials > 0) {   // the medium records follow the materials, and the table they sit in when it is made anew
+    if (int rc = medium_setup(s)) return rc;
+    s->varying_media = prep_media_vary(s->upd.materials.data(), s->d.num_materials, s->upd.inst_material.data(), s->upd.inst_flags.data(), s->d.num_instances);
+  }
   s->sched.forget();   // the camera index may be the same, the picture is not
   return VPT_OK;
 }
@@ -421,6 +439,19 @@ int vpt_scene_get_lights(vpt_scene* s, vpt_light* lights, int light_capacity, in
   HIP_TRY(hipDeviceSynchronize());
   if (lights && s->d.num_lights) HIP_TRY(hipMemcpy(lights, s->d.lights, (size_t)s->d.num_lights * sizeof(vpt_light), hipMemcpyDeviceToHost));
   if (cdf && s->lights_upd.num_cdf) HIP_TRY(hipMemcpy(cdf, s->d.light_cdf, (size_t)s->lights_upd.num_cdf * sizeof(float), hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+
+// the medium records as the device holds them now
+int vpt_scene_get_media(vpt_scene* s, float* records, int capacity, int* num_materials, int* varying) {
+  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (num_materials) *num_materials = s->d.num_materials;
+  if (varying) *varying = s->varying_media ? 1 : 0;
+  REQUIRE(!records || capacity >= s->d.num_materials, "capacity %d < %d materials", capacity, s->d.num_materials);
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (records && s->d.num_materials)
+    HIP_TRY(hipMemcpy(records, s->d.light_rec + 8 * (size_t)s->d.num_lights, 3 * (size_t)s->d.num_materials * sizeof(float4), hipMemcpyDeviceToHost));
   return VPT_OK;
 }
 

@@ -138,6 +138,10 @@ struct DScene {
   // [7] = {root box hi.xyz, kind | count << 8} with kind = VPT_LIGHT_*.  light_prims: for single-leaf mesh lights,
   // 4 x 5 float4 per light: the leaf's primitives as corner positions (element id in p0.w) + the element's
   // world-space normal (eval_element_normal), computed on the device at scene creation.
+  // Behind the records of the lights, in the same table: the medium records, 3 float4 per material = {density.xyz, scattering.x}
+  // {scattering.yz, emission.xy} {emission.z, scanisotropy, 0, 0}: what a path that enters the material's volume carries along
+  // (eval_material_at without textures or vertex colours, by vpt_medium_setup_kernel), read by K1 behind a material id
+  // (vpt_mesh_kernel.hip.h: `med`).  light_rec + 8 * num_lights + 3 * material: a base pointer the shading half holds anyway.
   // Vertex attributes per primitive slot, parallel to leaf_prims: 6 float4 = the four corners' normals, then
   // their texcoords as 4 x float2.  A hit carries its slot, so position, normal and texcoord of the shading
   // point are one fetch level away instead of instances[] -> shapes[] -> elems[] -> positions/normals/texcoords[].

@@ -21,6 +21,21 @@ __global__ void vpt_light_setup_kernel(DScene sc, float4* out) {
   out[20 * l + 5 * k + 4] = make_float4(n.x, n.y, n.z, __int_as_float(sh.is_triangles ? 1 : 0));
 }
 
+// medium records (vpt_device.h): one thread per material.  The kernels' own eval_material_at, compiled with their flags, without
+// textures' or vertex colours' say (a scene where they have one renders with the instance that does not read the records): the
+// bits a path copies at a hit on the material.  The texture ids are dropped, not followed: those of a material no mesh instance
+// uses (an SDF's) are not range-checked (prep_check_material)
+__global__ void vpt_medium_setup_kernel(DScene sc, float4* out) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= sc.num_materials) return;
+  vpt_material mat = sc.materials[i];
+  mat.emission_tex = mat.color_tex = mat.roughness_tex = mat.scattering_tex = VPT_INVALID;
+  const mpoint m = eval_material_at(sc, mat, mk2(0, 0), mk4(1, 1, 1, 1));
+  out[3 * i]     = make_float4(m.density.x, m.density.y, m.density.z, m.scattering.x);
+  out[3 * i + 1] = make_float4(m.scattering.y, m.scattering.z, m.emission.x, m.emission.y);
+  out[3 * i + 2] = make_float4(m.emission.z, m.scanisotropy, 0, 0);
+}
+
 // search_light_cdf against the plain binary search on the same CDF: values at, just below and just above CDF
 // entries, uniform ones, and the ends of the range; out[0] = mismatches
 __global__ void vpt_light_cdf_selftest_kernel(DScene sc, int light_id, int n, unsigned long long* out) {

@@ -80,6 +80,7 @@ __global__ void vpt_light_cdf_selftest_kernel(DScene sc, int light_id, int n, un
 
 // ---- scene setup, launch schedule, state layout and output resolve (vpt_kernels.hip) -------------------------------------------
 __global__ void vpt_light_setup_kernel(DScene sc, float4* out);
+__global__ void vpt_medium_setup_kernel(DScene sc, float4* out);
 __global__ void vpt_cost_average_kernel(const unsigned* __restrict__ cost, float* __restrict__ avg, unsigned* __restrict__ key, int n, float nsamples, float weight);
 __global__ void vpt_permute_kernel(DParams pr, int to_tiles, float4* tiles_image, int* tiles_hits, ulonglong2* tiles_rng,
     float4* rows_image, int* rows_hits, ulonglong2* rows_rng);

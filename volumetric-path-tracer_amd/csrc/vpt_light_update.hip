@@ -363,7 +363,7 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
   if (int rc = send(u, lights_buf, lights)) return rc;
   if (int rc = send(u, index_buf, index)) return rc;
   if (int rc = send(u, lu.d_tags, tags)) return rc;
-  if (int rc = rec_buf.allocate(8 * (size_t)nl * sizeof(float4))) return rc;
+  if (int rc = rec_buf.allocate((8 * (size_t)nl + 3 * (size_t)d.num_materials) * sizeof(float4))) return rc;   // + the medium records: the caller refills them
   if (int rc = prims_buf.allocate(20 * (size_t)nl * sizeof(float4))) return rc;
   HIP_TRY(hipMemset(prims_buf.get(), 0, 20 * (size_t)nl * sizeof(float4) + (nl ? 0 : 16)));
   for (int l = 0; l < nl; l++)

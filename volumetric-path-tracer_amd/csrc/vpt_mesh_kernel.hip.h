@@ -744,7 +744,14 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
   f3    radiance = mk3(0, 0, 0), weight = mk3(1, 1, 1);
   float alpha  = 0;
   int   bounce = 0, sample = 0, state = ST_NEW;
-  bool  in_medium = false;
+  // The medium the path is in, as one word: 0 = none, else the material's id + 1 in the low half.  What the path tracer needs of
+  // it (density, scattering, emission, anisotropy: ten floats) is read from the material's medium record behind the light records
+  // (vpt_device.h) after the query, by the lanes that are in a medium - about a third of the trips - instead of staying in registers
+  // through every BVH query.  Trip-spanning instances (HAS_LARGE) keep the medium a pending MIS evaluation enters in the high half
+  // until the weight is finished.  MED_REGS: the general instance carries the ten values themselves, copied at the entry hit, for
+  // scenes whose media vary over the surface (vpt_capi.hip routes them here).
+  constexpr bool MED_REGS = (FEAT & VPT_FEAT_ALL) == VPT_FEAT_ALL;
+  unsigned med = 0;
   f3    med_density = mk3(0, 0, 0), med_scattering = mk3(0, 0, 0), med_emission = mk3(0, 0, 0);
   float med_g = 0;
   // pending MIS evaluation: f / (0.5 pdf + 0.5 sum_lights) is finished after the light-pdf walk
@@ -773,7 +780,7 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
       lens.y   = rand1f(rng);
       ray      = eval_camera(cam, mk2(u, v), lens);
       radiance = mk3(0, 0, 0), weight = mk3(1, 1, 1);
-      alpha = 0, bounce = 0, in_medium = false, state = ST_MAIN;
+      alpha = 0, bounce = 0, med = 0, state = ST_MAIN;
     }
 
     // ---- the one BVH query of this trip: the whole wave is in the call, lanes without a ray as helpers ---------------
@@ -786,6 +793,10 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
       // without light walks that span trips (ST_LPDF) a pending MIS evaluation never outlives its trip: say so, or its seven words
       // stay allocated through every BVH query
       mis_f = mk3(0, 0, 0), mis_pdf = 0, lp_sum = 0, lp_light = 0, mis_toggle = false;
+    }
+    if constexpr (!MED_REGS) {
+      // the same for the medium's values: read from its record below by the lanes that are in one, never carried into the next query
+      med_density = mk3(0, 0, 0), med_scattering = mk3(0, 0, 0), med_emission = mk3(0, 0, 0), med_g = 0;
     }
     if (query) {
 
@@ -832,8 +843,14 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
         f2     l_ruv = mk2(0, 0);
         float  l_rel = 0, l_rl = 0;
         mpoint m;
+        unsigned entered = 1;   // the medium a path enters at this trip's surface hit, as `med` names it (MED_REGS: a flag)
         if constexpr (SH == K_VOLPATH) {
-          if (in_medium) {   // cpp:586-596 — rd is drawn before rl
+          if ((med & 0xffff) != 0) {   // cpp:586-596 — rd is drawn before rl
+            if constexpr (!MED_REGS) {   // the medium's record: nothing of it is live across traverse()
+              const float4* rec = sc.light_rec + 8 * sc.num_lights + 3 * ((int)(med & 0xffff) - 1);
+              const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+              med_density = mk3(r0.x, r0.y, r0.z), med_scattering = mk3(r0.w, r1.x, r1.y), med_emission = mk3(r1.z, r1.w, r2.x), med_g = r2.y;
+            }
             float rd       = rand1f(rng);
             float rl       = rand1f(rng);
             float distance = sample_transmittance(med_density, h.distance, rl, rd);
@@ -885,6 +902,7 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
               bounce++;
             } else {   // pathtrace / volpathtrace, cpp:619-651
               vol_boundary = SH == K_VOLPATH && is_volumetric_type(sc.materials[inst.material].type);
+              if constexpr (!MED_REGS) entered = (unsigned)inst.material + 1;
               if (!is_delta(m)) {
                 if (rand1f(rng) < 0.5f) {
                   f2 rn;
@@ -905,11 +923,11 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
                 incoming  = sample_delta(m, normal, outgoing, rnl);
                 weight    = weight * (eval_delta(m, normal, outgoing, incoming) / sample_delta_pdf(m, normal, outgoing, incoming));
                 if (vol_boundary && dot(normal, outgoing) * dot(normal, incoming) < 0) {
-                  if (!in_medium) {
-                    in_medium   = true;
-                    med_density = m.density, med_scattering = m.scattering, med_emission = m.emission, med_g = m.scanisotropy;
+                  if ((med & 0xffff) == 0) {
+                    med = entered;
+                    if constexpr (MED_REGS) med_density = m.density, med_scattering = m.scattering, med_emission = m.emission, med_g = m.scanisotropy;
                   } else {
-                    in_medium = false;
+                    med = 0;
                   }
                 }
                 ray = make_ray(position, incoming);
@@ -945,8 +963,10 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
               mis_f      = eval_bsdfcos(m, normal, outgoing, incoming);
               mis_pdf    = sample_bsdfcos_pdf(m, normal, outgoing, incoming);
               mis_toggle = vol_boundary && dot(normal, outgoing) * dot(normal, incoming) < 0;
-              if (mis_toggle && !in_medium)   // entering: the medium slot is free, fill it now
-                med_density = m.density, med_scattering = m.scattering, med_emission = m.emission, med_g = m.scanisotropy;
+              if (mis_toggle && (med & 0xffff) == 0) {   // entering: the medium slot is free, fill it now
+                med = entered << 16;
+                if constexpr (MED_REGS) med_density = m.density, med_scattering = m.scattering, med_emission = m.emission, med_g = m.scanisotropy;
+              }
               ray = make_ray(position, incoming);
               lp_sum = 0, lp_light = 0, advance_lights = true;
             }
@@ -979,7 +999,7 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
           if (state == ST_MAIN) {   // all lights visited: finish the MIS weight (cpp:630-634 / 668-671)
             float lights_pdf = lp_sum * ((float)1 / (float)sc.num_lights);
             weight = weight * (mis_f / (0.5f * mis_pdf + 0.5f * lights_pdf));
-            if (mis_toggle) in_medium = !in_medium;   // cpp:642-648
+            if (mis_toggle) med = (med & 0xffff) != 0 ? 0 : med >> 16;   // cpp:642-648: leaving / entering the pending medium
             if (!survive(weight, bounce, rng)) finish = true;
             bounce++;
           }

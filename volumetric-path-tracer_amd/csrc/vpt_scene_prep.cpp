@@ -498,7 +498,7 @@ void build_lights(const vpt_scene_desc& d, scene_tables& t) {
     }
   }
 
-  t.light_rec.assign(8 * (size_t)d.num_lights, make_float4(0, 0, 0, 0));
+  t.light_rec.assign(8 * (size_t)d.num_lights + 3 * (size_t)d.num_materials, make_float4(0, 0, 0, 0));   // + the medium records, filled on the device
   for (int i = 0; i < d.num_lights; i++) {
     const vpt_light& l = d.lights[i];
     float4* r = &t.light_rec[8 * (size_t)i];
@@ -651,6 +651,16 @@ int prep_check_material(const vpt_material& m, int i, int num_textures, bool tex
   REQUIRE(tex_ok(m.emission_tex) && tex_ok(m.color_tex) && tex_ok(m.roughness_tex) && tex_ok(m.scattering_tex) && tex_ok(m.normal_tex), "material %d: texture id out of range", i);
   return VPT_OK;
 }
+bool prep_media_vary(const vpt_material* materials, int num_materials, const int* inst_material, const int* inst_flags, int num_instances) {
+  if (num_materials > 65534) return true;
+  for (int i = 0; i < num_instances; i++) {
+    const vpt_material& m = materials[inst_material[i]];
+    if (m.type != VPT_MAT_REFRACTIVE && m.type != VPT_MAT_VOLUMETRIC && m.type != VPT_MAT_SUBSURFACE) continue;   // is_volumetric_type
+    if (m.color_tex != VPT_INVALID || m.emission_tex != VPT_INVALID || m.scattering_tex != VPT_INVALID || (inst_flags[i] & VPT_SHP_COLORS)) return true;
+  }
+  return false;
+}
+
 void prep_quad_slots(const vpt_bvh_node* nodes, int count, std::vector<int>& slots) {
   std::vector<int> order, quad_of;
   quad_order(nodes, count, order, quad_of);
@@ -674,6 +684,11 @@ int prepare_scene(const vpt_scene_desc& d, const vpt_scene_curves* curves, scene
   build_geometry(d, cs, t);
   if (int rc = build_quad_nodes_and_stacks(d, t)) return rc;
   build_instances(d, cs, t);
+  {
+    std::vector<int> inst_material, inst_flags;
+    for (const DInstance& in : t.instances) inst_material.push_back(in.material), inst_flags.push_back(in.shape_flags);
+    t.varying_media = prep_media_vary(d.materials, d.num_materials, inst_material.data(), inst_flags.data(), d.num_instances);
+  }
   // sRGB decode LUT: byte_to_float then srgb_to_rgb, yocto_color.h:212-227, evaluated with the host powf
   t.srgb_lut.resize(256);
   for (int b = 0; b < 256; b++) {

@@ -38,6 +38,7 @@ struct scene_tables {
   int stack_cap = 16, stack_lds4 = 8, stack_spill4 = 0;
   int light_features = 0;   // VPT_FEAT_* bits this scene's lights need from the mesh kernels
   bool curves = false;      // some instanced shape holds points or lines: the mesh kernels' VPT_FEAT_CURVES instances
+  bool varying_media = false;   // prep_media_vary() of the scene
   host_mirrors h;
 };
 
@@ -53,3 +54,7 @@ void prep_instance_frames(const vpt_frame& frame, float4 inv[3], float4 fwd[3], 
 void prep_environment_frames(const vpt_frame& frame, float4 inv[3], float4 fwd[3]);
 int  prep_check_material(const vpt_material& m, int index, int num_textures, bool textured);
 void prep_quad_slots(const vpt_bvh_node* nodes, int count, std::vector<int>& slots);
+// Whether the medium behind some instance is more than a function of its material (vpt_device.h: medium records): a material of a
+// volumetric type with a colour, emission or scattering texture or on a shape with vertex colours - or more materials than the
+// path state's 16-bit id holds.  Such scenes render with K1's general instance, which carries the medium in registers.
+bool prep_media_vary(const vpt_material* materials, int num_materials, const int* inst_material, const int* inst_flags, int num_instances);
