@@ -75,9 +75,10 @@ struct DShape {          // 80 B
 enum { VPT_LIGHT_SMALL_MESH = 0, VPT_LIGHT_LARGE_MESH = 1, VPT_LIGHT_ENV_TEX = 2, VPT_LIGHT_ENV_CONST = 3, VPT_LIGHT_SDF = 4, VPT_LIGHT_NONE = 5 };
 
 // On top of it a guide table (the "cutpoint" method): the clamped sample r falls into bucket
-// b = min(int(r * guide_scale), guide_buckets - 1); light_guide[guide_offset + b] = {lo, hi} brackets
+// b = min(max(int(r * guide_scale), 0), guide_buckets - 1); light_guide[guide_offset + b] = {lo, hi} brackets
 // upper_bound for every r of that bucket (bounds widened on the host by more than the rounding of
-// r * guide_scale).  When hi - lo <= 16 the answer is lo + #{cdf[lo .. lo+15] <= r}: two dependent fetches
+// r * guide_scale).  The lower clamp is for a CDF whose last entry is below 1e-5: sample_discrete's upper bound
+// back - 0.00001f is negative there, so is every r, and the answer is element 0, which bucket 0 brackets.  When hi - lo <= 16 the answer is lo + #{cdf[lo .. lo+15] <= r}: two dependent fetches
 // instead of six; longer brackets (dark stretches of an environment map) take the 16-ary levels.
 struct DCdfIndex {
   int   levels;        // 0: no index (short or non-monotone CDF: plain binary search); else number of levels incl. level 0

@@ -529,8 +529,11 @@ VPT_DEV int search_light_cdf(const DScene& sc, int light_id, float r) {
   const int        n     = light.cdf_len;
   const DCdfIndex& ix    = sc.light_index[light_id];
   if (ix.guide_buckets > 0) {   // bracket from the guide table; short brackets are resolved with one 16-wide fetch
+    // clamped from BOTH sides: a light whose total area is below 1e-5 has back - 0.00001f < 0, so r (and b) is negative
+    // for every sample, far below the int range for a tiny back (the conversion saturates).  Bucket 0's bracket starts
+    // at 0 and no CDF entry is <= a negative r: element 0, what the reference's upper_bound returns
     int  b  = (int)(r * ix.guide_scale);
-    int2 lh = sc.light_guide[ix.guide_offset + (b < ix.guide_buckets ? b : ix.guide_buckets - 1)];
+    int2 lh = sc.light_guide[ix.guide_offset + clampi(b, 0, ix.guide_buckets - 1)];
     if (__builtin_amdgcn_ballot_w64(lh.y - lh.x > 16) == 0) {
       const float* g = sc.light_index_pool + ix.offset[0] + lh.x;   // level 0 = the CDF, padded with +inf
       int cnt = 0;
