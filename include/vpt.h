@@ -370,6 +370,57 @@ int vpt_scene_get_media(vpt_scene* scene, float* records, int capacity, int* num
  * search index followed by its pool, the guide table.  For the tests: an updated handle against a fresh one. */
 int vpt_scene_light_tables_hash(vpt_scene* scene, uint64_t out[6]);
 
+/* ---- edits of environments and textures; the environment CDF rebuilt on the device -----------------------------------
+ * vpt_scene_edit keeps its layout (older binaries fill it in); what it has no field for comes in a struct of its own.  An
+ * environment entry replaces that environment's frame, emission and emission_tex; a texture entry replaces ALL texels of one
+ * texture: width, height, linear and is_float describe the NEW contents, offset is the first texel inside THIS EDIT's pools
+ * (texels_f: float4, texels_b: uchar4).  Counts stay fixed: no texture or environment is added.
+ * After vpt_scene_update_textures(s, edit) every table on the device that a render, vpt_intersect or vpt_kat call reads holds what
+ * vpt_scene_create would hold for the edited descriptor carrying the host's make_lights of the edited scene:
+ * vpt_scene_light_tables_hash equals a fresh handle's on all six tables, vpt_scene_get_lights the host mirror's byte for byte, and
+ * every render is bit-identical.  The layout of the texel pools is not part of the contract: nothing observable depends on a
+ * texture's offset.  vpt_scene_update and vpt_scene_update_lights are unchanged and keep leaving environment entries alone.
+ *  - The list = make_lights (yocto_pathtrace.cpp:1015-1032): an environment is a light iff its emission is not {0, 0, 0}; the
+ *    environments come after the instance lights, in id order, before the SDF lights; an environment with a texture has cdf_len =
+ *    width * height, otherwise 0.  Emission zero <-> non-zero therefore adds or removes a light and rebases every later cdf_offset;
+ *    a scale between two non-zero values leaves every light table as it is and changes the environment's entry only.  Records
+ *    follow vpt_scene_create: VPT_LIGHT_ENV_CONST / VPT_LIGHT_ENV_TEX, both frames, {width, height} and the CDF's total.
+ *  - Textures: the same width, height and is_float overwrite the texture's range of its pool in place.  New dimensions or a new
+ *    format give the texture fresh room at the end of a pool allocated anew, the old pool moved device to device; the range the
+ *    texture leaves stays unused until vpt_scene_destroy (pools are never compacted).  A texture that a material names may be
+ *    edited: the kernels read a texture's entry at use.  Only a light's CDF depends on texels: an edit of a texture that no
+ *    emissive environment's emission_tex names launches nothing beyond the copies.
+ *  - The environment CDF is recomputed when the environment's light is new, its emission_tex changed, or that texture is in the
+ *    edit.  For idx in row-major order, i = idx % width, j = idx / width:
+ *        w[idx] = max4(texel) * sin_row[j],   cdf[0] = w[0],   cdf[idx] = w[idx] + cdf[idx - 1]
+ *    all in float32 with nothing fused.  max4 = max(max(max(x, y), z), w) with max(a, b) = (a > b) ? a : b (yocto_math.h:1356, 1824;
+ *    alpha takes part; with NaN the select form decides, so fmaxf is not equivalent).  The texel is lookup_texture WITHOUT as_linear:
+ *    a float4 as it is, a uchar4 as b / 255.0f per channel (a correctly rounded division, not the sRGB table).  sin_row[j] =
+ *    sin((j + 0.5f) * pif / height) is computed ON THE HOST, where make_lights computes it, and sent as `height` floats: the device's
+ *    sine is not the host's, and a 1-ulp difference moves the CDF.  One float per row is the only thing beyond the edit's own payload
+ *    and a few words per light that crosses PCIe.  The running sum is the serial chain of vpt_scene_update_lights (VPT_LIGHTS_PLAIN=1:
+ *    its plain form), never a tree or a block scan; the index, the guide table and the {sorted, last entry} read-back are that
+ *    call's too: a CDF that is not non-decreasing (a negative or NaN texel) gets no index, exactly as at creation.  Every other
+ *    light's CDF, index and guide table move device to device.
+ *  - vpt_scene_update_stats afterwards: launches of the weight, running-sum, index, guide and record kernels; bytes = the edit's
+ *    texels (16 or 4 each) + 24 per texture entry + 112 per environment entry (the entry and its inverse frame) + 4 * height per
+ *    recomputed environment + 96 per environment light whose frame alone changed, and, when the light tables are rebuilt, per light
+ *    84 (list entry 24, index header 56, record tag 4) + 128 per environment light (its record) + 4 per SDF light + 32 per
+ *    recomputed CDF (job 24, result 8).  Nothing else is sent.  Device time: from before the first to after the last launch.
+ *  - Validation before anything is written (VPT_ERR_INVALID_ARG, the message names the entry, the scene is untouched): ids in
+ *    range and not repeated within a list; every float of an environment entry finite; emission_tex -1 or a texture id; width and
+ *    height >= 0 with width * height < 2^31; offset >= 0 and offset + width * height inside the edit's pool; an emissive
+ *    environment's texture must hold at least one texel, as at creation.
+ *  - Synchronisation, the VPT_ERR_HIP semantics and the forgetting of the launch-schedule record: those of vpt_scene_update. */
+typedef struct vpt_texture_edit {
+  int32_t num_environments; const int32_t* environment_ids; const vpt_environment* environments; /* frame, emission, emission_tex */
+  int32_t num_textures;     const int32_t* texture_ids;     const vpt_texture* textures;
+      /* width, height, linear, is_float of the NEW contents; offset = first texel inside this edit's pools */
+  int64_t num_texels_f; const float*   texels_f;   /* float4 */
+  int64_t num_texels_b; const uint8_t* texels_b;   /* uchar4 */
+} vpt_texture_edit;
+int vpt_scene_update_textures(vpt_scene* scene, const vpt_texture_edit* edit);
+
 /* ---- the drop-in for pathtrace_samples() --------------------------------------------
  * Host, row-major (idx = j*width + i) caller-owned state, exactly pathtrace_state
  * (yocto_pathtrace.h:57-64): image float4[w*h], hits int32[w*h], rng {u64 state, u64 inc}[w*h].
@@ -411,6 +462,8 @@ void vpt_multi_destroy(vpt_multi* m);
 int  vpt_multi_update(vpt_multi* m, const vpt_scene_edit* edit);
 /* vpt_scene_update_lights in the same way */
 int  vpt_multi_update_lights(vpt_multi* m, const vpt_scene_edit* edit);
+/* vpt_scene_update_textures in the same way */
+int  vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit);
 int  vpt_multi_device_count(const vpt_multi* m);
 /* how vpt_multi_get_render moves the parts: "rccl", "peer-copy" (several devices, no RCCL) or "local" (one device) */
 const char* vpt_multi_transport(const vpt_multi* m);
@@ -657,6 +710,8 @@ int  vpt_session_set_display(vpt_session* session, const vpt_display_params* dis
 int  vpt_session_edit(vpt_session* session, const vpt_scene_edit* edit);
 /* the same through vpt_scene_update_lights: an edit that switches a light on or off, or moves an emitter's vertices */
 int  vpt_session_edit_lights(vpt_session* session, const vpt_scene_edit* edit);
+/* vpt_scene_update_textures, then a reset; a refused edit leaves the session as it was */
+int  vpt_session_edit_textures(vpt_session* session, const vpt_texture_edit* edit);
 int  vpt_session_get_display(vpt_session* session, uint8_t* rgba8, float* display_f);
 int  vpt_session_get_image(vpt_session* session, float* linear);
 int  vpt_session_get_denoised(vpt_session* session, float* linear);

@@ -90,6 +90,20 @@ class VptSceneEdit(C.Structure):  # vpt_scene_edit
                 ("num_shapes", C.c_int32), ("shape_ids", C.c_void_p), ("shape_positions", C.c_void_p), ("shape_normals", C.c_void_p)]
 
 
+class VptEnvironment(C.Structure):  # vpt_environment
+    _fields_ = [("frame", VptFrame), ("emission", C.c_float * 3), ("emission_tex", C.c_int32)]
+
+
+class VptTexture(C.Structure):  # vpt_texture
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("linear", C.c_int32), ("is_float", C.c_int32), ("offset", C.c_int64)]
+
+
+class VptTextureEdit(C.Structure):  # vpt_texture_edit
+    _fields_ = [("num_environments", C.c_int32), ("environment_ids", C.c_void_p), ("environments", C.c_void_p),
+                ("num_textures", C.c_int32), ("texture_ids", C.c_void_p), ("textures", C.c_void_p),
+                ("num_texels_f", C.c_int64), ("texels_f", C.c_void_p), ("num_texels_b", C.c_int64), ("texels_b", C.c_void_p)]
+
+
 MATERIAL_TYPES = ["matte", "glossy", "reflective", "transparent", "refractive", "subsurface", "volumetric", "gltfpbr"]
 
 
@@ -152,6 +166,48 @@ class SceneEdit:
         keep += [pos, nrm]
         abi.num_shapes, abi.shape_ids = n, ids(self.shapes)
         abi.shape_positions, abi.shape_normals = C.cast(pos, C.c_void_p).value, C.cast(nrm, C.c_void_p).value
+        return abi, keep
+
+
+class TextureEdit:
+    """What vpt_scene_update_textures takes (include/vpt.h: vpt_texture_edit), as dictionaries id -> value: environments
+    (VptEnvironment: frame, emission, emission_tex) and textures ((texels (h, w, 4) float32 or uint8, linear)).  HostScene's
+    set_environment / set_texture fill one; DeviceScene.update_textures / MultiDeviceScene.update_textures apply it."""
+
+    def __init__(self, environments=None, textures=None):
+        self.environments, self.textures = dict(environments or {}), dict(textures or {})
+
+    def empty(self) -> bool:
+        return not (self.environments or self.textures)
+
+    def payload_bytes(self) -> int:
+        """bytes of the edit itself as vpt_scene_update_stats counts them: texels, 24 per texture entry, 112 per environment entry"""
+        return sum(np.asarray(t).nbytes + 24 for t, _ in self.textures.values()) + 112 * len(self.environments)
+
+    def to_abi(self):
+        """(VptTextureEdit, objects that keep its arrays alive)"""
+        keep, abi = [], VptTextureEdit()
+        env_ids = np.array(list(self.environments.keys()), np.int32)
+        envs = (VptEnvironment * max(1, len(self.environments)))(*self.environments.values())
+        tex_ids = np.array(list(self.textures.keys()), np.int32)
+        entries = (VptTexture * max(1, len(self.textures)))()
+        pool = {True: [], False: []}
+        count = {True: 0, False: 0}
+        for k, (texels, linear) in enumerate(self.textures.values()):
+            texels = np.ascontiguousarray(texels)
+            if texels.ndim != 3 or texels.shape[2] != 4 or texels.dtype not in (np.float32, np.uint8):
+                raise VptError("texels of a texture edit are (h, w, 4) float32 or uint8")
+            is_float = texels.dtype == np.float32
+            entries[k] = VptTexture(texels.shape[1], texels.shape[0], int(bool(linear)), int(is_float), count[is_float])
+            pool[is_float].append(texels.reshape(-1, 4))
+            count[is_float] += texels.shape[0] * texels.shape[1]
+        texels_f = np.ascontiguousarray(np.concatenate(pool[True])) if pool[True] else np.zeros((0, 4), np.float32)
+        texels_b = np.ascontiguousarray(np.concatenate(pool[False])) if pool[False] else np.zeros((0, 4), np.uint8)
+        keep += [env_ids, envs, tex_ids, entries, texels_f, texels_b]
+        abi.num_environments, abi.environment_ids, abi.environments = len(self.environments), env_ids.ctypes.data, C.cast(envs, C.c_void_p).value
+        abi.num_textures, abi.texture_ids, abi.textures = len(self.textures), tex_ids.ctypes.data, C.cast(entries, C.c_void_p).value
+        abi.num_texels_f, abi.texels_f = len(texels_f), texels_f.ctypes.data
+        abi.num_texels_b, abi.texels_b = len(texels_b), texels_b.ctypes.data
         return abi, keep
 
 
@@ -219,6 +275,9 @@ hip.vpt_multi_update.argtypes = [_p, C.POINTER(VptSceneEdit)]
 hip.vpt_scene_update_lights.argtypes = [_p, C.POINTER(VptSceneEdit)]
 hip.vpt_multi_update_lights.argtypes = [_p, C.POINTER(VptSceneEdit)]
 hip.vpt_session_edit_lights.argtypes = [_p, C.POINTER(VptSceneEdit)]
+hip.vpt_scene_update_textures.argtypes = [_p, C.POINTER(VptTextureEdit)]
+hip.vpt_multi_update_textures.argtypes = [_p, C.POINTER(VptTextureEdit)]
+hip.vpt_session_edit_textures.argtypes = [_p, C.POINTER(VptTextureEdit)]
 hip.vpt_scene_get_lights.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int), _p, C.c_int64, C.POINTER(C.c_int64)]
 hip.vpt_scene_light_tables_hash.argtypes = [_p, _p]
 hip.vpt_scene_get_media.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -303,6 +362,11 @@ host.vpth_scene_set_item.argtypes = [_p, C.c_int, C.c_int, _p, C.c_int64, C.c_ch
 host.vpth_scene_update_bvh.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_update_lights.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_free.restype = None
+host.vpth_scene_get_environment.argtypes = [_p, C.c_int, C.POINTER(VptEnvironment)]
+host.vpth_scene_set_environment.argtypes = [_p, C.c_int, C.POINTER(VptEnvironment), C.c_char_p, C.c_int]
+host.vpth_scene_get_texture.argtypes = [_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _p, C.c_int64]
+host.vpth_scene_set_texture.argtypes = [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_char_p, C.c_int]
+host.vpth_scene_update_textures.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_desc.argtypes = [_p]
 host.vpth_scene_desc.restype = _p
 host.vpth_scene_curves.argtypes = [_p]
@@ -562,6 +626,64 @@ class HostScene:
             raise VptError(err.value.decode())
         return edit
 
+    # -- environments and textures (the host side of vpt_scene_update_textures): the setters change the scene and note the change in
+    #    the pending TextureEdit; desc, lights() and stats() follow at update_textures(), which hands that edit out ----------------
+    def environment(self, index: int) -> VptEnvironment:
+        out = VptEnvironment()
+        if host.vpth_scene_get_environment(self.handle, index, C.byref(out)) != 0:
+            raise VptError(f"environment {index} out of range")
+        return out
+
+    def set_environment(self, index: int, emission=None, emission_tex=None) -> None:
+        """emission (three floats) and / or emission_tex (-1: none) of an environment; its frame is set_environment_frame's"""
+        env = self.environment(index)
+        if emission is not None:
+            env.emission[0], env.emission[1], env.emission[2] = [float(c) for c in emission]
+        if emission_tex is not None:
+            env.emission_tex = int(emission_tex)
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_set_environment(self.handle, index, C.byref(env), err, len(err)) != 0:
+            raise VptError(err.value.decode())
+        self._pending_textures().environments[index] = self.environment(index)
+
+    def texture(self, index: int):
+        """(texels (h, w, 4) float32 or uint8, linear) of a texture (a copy)"""
+        w, h, linear, is_float = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        if host.vpth_scene_get_texture(self.handle, index, C.byref(w), C.byref(h), C.byref(linear), C.byref(is_float), None, 0) != 0:
+            raise VptError(f"texture {index} out of range")
+        texels = np.zeros((h.value, w.value, 4), np.float32 if is_float.value else np.uint8)
+        host.vpth_scene_get_texture(self.handle, index, C.byref(w), C.byref(h), C.byref(linear), C.byref(is_float), texels.ctypes.data, texels.nbytes)
+        return texels, bool(linear.value)
+
+    def set_texture(self, index: int, texels, linear=None) -> None:
+        """all texels of a texture: an (h, w, 4) array, float32 or uint8 - any size, either format; linear None: as it was"""
+        texels = np.ascontiguousarray(texels)
+        if texels.ndim != 3 or texels.shape[2] != 4 or texels.dtype not in (np.float32, np.uint8):
+            raise VptError("texels are (h, w, 4) float32 or uint8")
+        if linear is None:
+            linear = self.texture(index)[1]
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_set_texture(self.handle, index, texels.shape[1], texels.shape[0], int(bool(linear)), int(texels.dtype == np.float32),
+                                       texels.ctypes.data, err, len(err)) != 0:
+            raise VptError(err.value.decode())
+        self._pending_textures().textures[index] = (texels.copy(), bool(linear))
+
+    def _pending_textures(self) -> TextureEdit:
+        if getattr(self, "_texture_edit", None) is None:
+            self._texture_edit = TextureEdit()
+        return self._texture_edit
+
+    def update_textures(self) -> TextureEdit:
+        """make_lights of the scene as set_environment / set_texture left it: desc, lights() and stats() carry the edited textures,
+        environments, light list and CDFs.  Returns the TextureEdit for DeviceScene.update_textures."""
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_update_textures(self.handle, err, len(err)) != 0:
+            raise VptError(err.value.decode())
+        edit, self._texture_edit = self._pending_textures(), None
+        for index in edit.environments:   # an entry carries the frame too: the one the scene holds now, not the one it held at the setter
+            edit.environments[index] = self.environment(index)
+        return edit
+
     def lights(self):
         """(light list as a LIGHT array, CDF pool as float32) of the descriptor (copies)"""
         d = VptSceneDescLights.from_address(self.desc)
@@ -661,6 +783,14 @@ class DeviceScene:
         DeviceScene made from the host scene after the same edit and update_lights()."""
         abi, keep = edit.to_abi()
         _check(hip.vpt_scene_update_lights(self.handle, C.byref(abi)), "vpt_scene_update_lights")
+        del keep
+
+    def update_textures(self, edit: TextureEdit) -> None:
+        """vpt_scene_update_textures (include/vpt.h): environments' emission and texture, and textures' texels; an environment's CDF
+        is rebuilt on the device from the texels.  Afterwards the handle renders the bits of a DeviceScene made from the host scene
+        after the same edit and update_textures()."""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_scene_update_textures(self.handle, C.byref(abi)), "vpt_scene_update_textures")
         del keep
 
     def get_lights(self):
@@ -784,6 +914,12 @@ class MultiDeviceScene:
         """vpt_multi_update_lights: DeviceScene.update_lights with the same edit on every device"""
         abi, keep = edit.to_abi()
         _check(hip.vpt_multi_update_lights(self.handle, C.byref(abi)), "vpt_multi_update_lights")
+        del keep
+
+    def update_textures(self, edit: TextureEdit) -> None:
+        """vpt_multi_update_textures: DeviceScene.update_textures with the same edit on every device"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_multi_update_textures(self.handle, C.byref(abi)), "vpt_multi_update_textures")
         del keep
 
     def pathtrace_samples(self, state: PathtraceState, params: PathtraceParams, count: int = 1) -> None:
@@ -1073,6 +1209,12 @@ class RenderSession:
         """edit() through vpt_scene_update_lights, with the SceneEdit of HostScene.update_lights()"""
         abi, keep = edit.to_abi()
         _check(hip.vpt_session_edit_lights(self.handle, C.byref(abi)), "vpt_session_edit_lights")
+        del keep
+
+    def edit_textures(self, edit: TextureEdit) -> None:
+        """edit() through vpt_scene_update_textures, with the TextureEdit of HostScene.update_textures()"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_session_edit_textures(self.handle, C.byref(abi)), "vpt_session_edit_textures")
         del keep
 
     @property

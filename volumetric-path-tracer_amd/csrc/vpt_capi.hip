@@ -22,6 +22,7 @@
 #include "vpt_schedule.h"
 #include "vpt_scene_prep.h"
 #include "vpt_scene_update.h"
+#include "vpt_texture_update.h"
 
 static std::string& g_error_text() {   // the message of the last failure on the calling thread (vpt_last_error)
   thread_local std::string text;
@@ -66,6 +67,7 @@ struct vpt_scene {
   long long     num_shape_nodes = 0;   // nodes of d.shape_nodes (vpt_scene_get_bvh)
   scene_updater upd;                   // vpt_scene_update: levels and quad-slot tables, built on the first update
   light_updater lights_upd;            // vpt_scene_update_lights: sizes of the pooled light tables, mirrors built on the first rebuild
+  texture_updater textures_upd;        // vpt_scene_update_textures: sizes of the texel pools, mirrors built on the first edit
 };
 
 namespace {
@@ -187,6 +189,7 @@ int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* 
   s->stack_cap = t.stack_cap, s->stack_lds4 = t.stack_lds4, s->stack_spill4 = t.stack_spill4, s->light_features = t.light_features;
   s->curves = t.curves, s->varying_media = t.varying_media, s->num_shape_nodes = d.num_shape_bvh_nodes;
   s->lights_upd.num_cdf = d.num_light_cdf, s->lights_upd.num_pool = (long long)t.light_index_pool.size(), s->lights_upd.num_guide = (long long)t.light_guide.size();
+  s->textures_upd.num_texels_f = d.num_texels_f, s->textures_upd.num_texels_b = d.num_texels_b;
   s->h = std::move(t.h);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -427,6 +430,21 @@ static int scene_update(vpt_scene* s, const vpt_scene_edit* edit, bool lights) {
 }
 int vpt_scene_update(vpt_scene* s, const vpt_scene_edit* edit) { return scene_update(s, edit, false); }
 int vpt_scene_update_lights(vpt_scene* s, const vpt_scene_edit* edit) { return scene_update(s, edit, true); }
+
+// environments and textures (the work is vpt_texture_update.hip's); the light tables follow when an environment's light does
+int vpt_scene_update_textures(vpt_scene* s, const vpt_texture_edit* edit) {
+  if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call rewrites
+  bool rebuilt = false;
+  if (int rc = texture_update_apply(s->d, s->h, s->num_shape_nodes, s->upd, s->lights_upd, s->textures_upd, s->tables, *edit, &s->light_features, &rebuilt)) return rc;
+  if (rebuilt) {   // light_prims and the medium records sit in tables made anew
+    if (int rc = light_setup(s)) return rc;
+    if (int rc = medium_setup(s)) return rc;
+  }
+  s->sched.forget();
+  return VPT_OK;
+}
 
 // the light list and the CDF pool as the device holds them now
 int vpt_scene_get_lights(vpt_scene* s, vpt_light* lights, int light_capacity, int* num_lights, float* cdf, int64_t cdf_capacity, int64_t* num_cdf) {

@@ -5,6 +5,8 @@
 // light that is new or whose shape moved gets its areas, its running sum, its 16-ary levels and its guide table from the kernels
 // below.  What does cross: a few words per light (its list entry, its index header, its record tag, the descriptor of its job,
 // and {sorted, last entry} back).
+// An edit of environments or textures (vpt_scene_update_textures, vpt_texture_update.hip) comes through here too: an environment whose
+// CDF has to be made anew is a job like a mesh light's, with the weight of its texels where a mesh light has the areas of its elements.
 // Arithmetic = the reference's, operation by operation (-ffp-contract=off, correctly rounded / and sqrt): the areas of
 // yocto_geometry.h:506-518, cdf[i] = area_i + cdf[i - 1] in element order.  Float addition is not associative, so the running sum
 // is a serial chain per light: no tree, no block scan.
@@ -17,12 +19,15 @@
 #include "vpt_error.h"
 #include "vpt_light_update.h"
 #include "vpt_math.hip.h"
+#include "vpt_texture_update.h"
+#include "vpt_update_helpers.h"
 
 namespace {
 
-struct light_job {   // one mesh light whose CDF is recomputed
+enum { JOB_QUADS = 0, JOB_TRIANGLES = 1, JOB_TEXELS = 2 };   // areas of a mesh light's elements / weights of an environment's texels
+struct light_job {   // one light whose CDF is recomputed
   long long cdf_offset;
-  int       elem_offset, vertex_offset, num_elems, is_triangles;
+  int       elem_offset, vertex_offset, num_elems, kind;
 };
 struct job_result { int sorted; float back; };
 
@@ -34,12 +39,12 @@ __global__ void lit_areas_kernel(const light_job* __restrict__ jobs, int first_j
     float* __restrict__ cdf) {
   const light_job j = jobs[first_job + blockIdx.y];
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= j.num_elems) return;
+  if (e >= j.num_elems || j.kind == JOB_TEXELS) return;
   const int4    q = elems[(long long)j.elem_offset + e];
   const float4* P = positions + j.vertex_offset;
   const f3 p0 = xyz(P[q.x]), p1 = xyz(P[q.y]), p2 = xyz(P[q.z]);
   float a;
-  if (j.is_triangles) a = triangle_area(p0, p1, p2);
+  if (j.kind == JOB_TRIANGLES) a = triangle_area(p0, p1, p2);
   else {   // quad_area, yocto_geometry.h:512-518
     const f3 p3 = xyz(P[q.w]);
     a = triangle_area(p0, p1, p3) + triangle_area(p2, p3, p1);
@@ -145,14 +150,18 @@ __global__ void lit_guide_kernel(int2* __restrict__ guide, int buckets, float sc
   guide[b] = make_int2(lo, hi);
 }
 
-// light records (build_lights) of mesh and SDF lights; an environment's record moved as it was
+// light records (build_lights) of mesh and SDF lights; an environment's record moved as it was, or (env_totals) sent by the host
+// without the one word that comes from the CDF: the total of a textured environment
 __global__ void lit_records_kernel(float4* __restrict__ rec, const vpt_light* __restrict__ lights, const int* __restrict__ tags, int n,
-    const float* __restrict__ cdf, const DInstance* __restrict__ instances, const DShape* __restrict__ shapes) {
+    const float* __restrict__ cdf, const DInstance* __restrict__ instances, const DShape* __restrict__ shapes, int env_totals) {
   const int l = blockIdx.x * blockDim.x + threadIdx.x;
   if (l >= n) return;
   const int tag = tags[l], kind = tag & 255;
-  if (kind == VPT_LIGHT_ENV_TEX || kind == VPT_LIGHT_ENV_CONST) return;
   float4* r = rec + 8 * (long long)l;
+  if (kind == VPT_LIGHT_ENV_TEX || kind == VPT_LIGHT_ENV_CONST) {
+    if (env_totals && kind == VPT_LIGHT_ENV_TEX && lights[l].cdf_len > 0) r[6].z = cdf[lights[l].cdf_offset + lights[l].cdf_len - 1];
+    return;
+  }
   for (int k = 0; k < 8; k++) r[k] = make_float4(0, 0, 0, 0);
   const vpt_light lt = lights[l];
   if (lt.instance >= 0) {
@@ -205,27 +214,17 @@ int move(void* to, const void* from, size_t bytes) {
   if (bytes) HIP_TRY(hipMemcpy(to, from, bytes, hipMemcpyDeviceToDevice));
   return VPT_OK;
 }
-// `fresh` takes the place of the table at `old` among the scene's allocations
-void adopt(std::vector<device_buffer>& tables, const void* old, device_buffer&& fresh) {
-  for (device_buffer& t : tables)
-    if (t.get() == old) {
-      t = std::move(fresh);
-      return;
-    }
-  tables.push_back(std::move(fresh));
-}
-
 struct entry {   // one light of the new list
   vpt_light l;
   int  from;        // its place in the old list, -1: new
-  bool recompute;   // a mesh light that is new or whose shape moved
+  bool recompute;   // a mesh light that is new or whose shape moved; an environment whose light, texture or texels are new
   int  tag;         // kind | count << 8 of its record
 };
 
 }  // namespace
 
 int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light_updater& lu, std::vector<device_buffer>& tables,
-    const vpt_scene_edit& e, int* light_features, bool* rebuilt) {
+    const vpt_scene_edit& e, int* light_features, bool* rebuilt, const std::vector<env_light>* envs) {
   *rebuilt = false;
   if (!lu.ready) {
     lu.index.resize((size_t)d.num_lights), lu.sdfs.resize((size_t)d.num_sdfs);
@@ -236,11 +235,12 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
 
   // 1. the list (make_lights): emissive instances of faces, the environments that were lights, emissive SDFs - each in id order
   const std::vector<vpt_light>& old = u.lights;
-  std::vector<int>  old_of_instance((size_t)d.num_instances, -1), old_of_sdf((size_t)d.num_sdfs, -1);
+  std::vector<int>  old_of_instance((size_t)d.num_instances, -1), old_of_sdf((size_t)d.num_sdfs, -1), old_of_env((size_t)d.num_environments, -1);
   std::vector<char> moved((size_t)d.num_shapes, 0);
   for (size_t l = 0; l < old.size(); l++) {
     if (old[l].instance >= 0) old_of_instance[(size_t)old[l].instance] = (int)l;
     else if (old[l].sdf >= 0) old_of_sdf[(size_t)old[l].sdf] = (int)l;
+    else if (old[l].environment >= 0) old_of_env[(size_t)old[l].environment] = (int)l;
   }
   for (int i = 0; i < e.num_shapes; i++) moved[(size_t)e.shape_ids[i]] = 1;
   std::vector<entry> list;
@@ -254,12 +254,21 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
     list.push_back({{i, VPT_INVALID, VPT_INVALID, sh.num_elems, 0}, from, from < 0 || moved[(size_t)shape] != 0,
         small ? VPT_LIGHT_SMALL_MESH | (((~sh.root_ref) & 15) << 8) : VPT_LIGHT_LARGE_MESH});
   }
-  for (size_t l = 0; l < old.size(); l++)   // the edit has no field for an environment's emission or texture
-    if (old[l].instance < 0 && old[l].sdf < 0) list.push_back({old[l], (int)l, false, u.light_kind[l]});
+  std::vector<int> env_of;   // the entry of `envs` behind a light of the new list, -1: none
+  if (envs) {                // vpt_scene_update_textures: the environments as the edit leaves them
+    for (size_t k = 0; k < envs->size(); k++) {
+      const env_light& ev = (*envs)[k];
+      env_of.resize(list.size(), -1), env_of.push_back((int)k);
+      list.push_back({{VPT_INVALID, ev.environment, VPT_INVALID, ev.cdf_len, 0}, old_of_env[(size_t)ev.environment], ev.recompute, ev.tag});
+    }
+  } else
+    for (size_t l = 0; l < old.size(); l++)   // the edit has no field for an environment's emission or texture
+      if (old[l].instance < 0 && old[l].sdf < 0) list.push_back({old[l], (int)l, false, u.light_kind[l]});
   for (int i = 0; i < d.num_sdfs; i++)
     if (emissive(u.materials[(size_t)lu.sdfs[(size_t)i].material])) list.push_back({{VPT_INVALID, VPT_INVALID, i, 1, 0}, old_of_sdf[(size_t)i], false, VPT_LIGHT_SDF});
   bool same = list.size() == old.size();
-  for (size_t l = 0; same && l < list.size(); l++) same = list[l].from == (int)l && !list[l].recompute;
+  for (size_t l = 0; same && l < list.size(); l++) same = list[l].from == (int)l && !list[l].recompute && list[l].l.cdf_len == old[l].cdf_len;
+  env_of.resize(list.size(), -1);
   if (same) return VPT_OK;   // no consequence for the lights: the update has done all there is to do
   *rebuilt = true;
 
@@ -278,10 +287,14 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
       const float area = lu.sdfs[(size_t)en.l.sdf].whd[0] * lu.sdfs[(size_t)en.l.sdf].whd[1];
       HIP_TRY(hipMemcpy(cdf + en.l.cdf_offset, &area, sizeof(float), hipMemcpyHostToDevice));
       u.last_bytes += sizeof(float);
+    } else if (en.recompute && en.l.instance < 0) {   // an environment: one weight per texel
+      jobs.push_back({en.l.cdf_offset, 0, 0, en.l.cdf_len, JOB_TEXELS});
+      job_light.push_back(l);
     } else if (en.recompute) {
       const DShape& sh = u.shapes[(size_t)h.inst_shape[(size_t)en.l.instance]];
-      jobs.push_back({en.l.cdf_offset, sh.elem_offset, sh.vertex_offset, sh.num_elems, sh.is_triangles});
+      jobs.push_back({en.l.cdf_offset, sh.elem_offset, sh.vertex_offset, sh.num_elems, sh.is_triangles ? JOB_TRIANGLES : JOB_QUADS});
       job_light.push_back(l);
+    } else if (en.l.cdf_len == 0) {   // an environment without a texture
     } else if (int rc = move(cdf + en.l.cdf_offset, d.light_cdf + old[(size_t)en.from].cdf_offset, (size_t)en.l.cdf_len * sizeof(float))) return rc;
   }
   const int njobs = (int)jobs.size();
@@ -293,10 +306,17 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
     for (int first = 0; first < njobs; first += 65535) {   // grid.y is a 16-bit count
       const int count = njobs - first < 65535 ? njobs - first : 65535;
       int most = 0;
-      for (int k = first; k < first + count; k++) most = jobs[(size_t)k].num_elems > most ? jobs[(size_t)k].num_elems : most;
+      for (int k = first; k < first + count; k++)
+        if (jobs[(size_t)k].kind != JOB_TEXELS) most = jobs[(size_t)k].num_elems > most ? jobs[(size_t)k].num_elems : most;
+      if (most == 0) continue;   // texel jobs only
       hipLaunchKernelGGL(lit_areas_kernel, dim3(blocks_for(most), (unsigned)count), dim3(BLOCK), 0, 0, d_jobs, first, d.elems, d.positions, cdf);
       LAUNCHED(u);
     }
+    for (int k = 0; k < njobs; k++)
+      if (jobs[(size_t)k].kind == JOB_TEXELS) {
+        if (int rc = launch_texel_weights((*envs)[(size_t)env_of[(size_t)job_light[(size_t)k]]], cdf + jobs[(size_t)k].cdf_offset)) return rc;
+        u.last_launches++;
+      }
     if (getenv("VPT_LIGHTS_PLAIN")) hipLaunchKernelGGL(lit_scan_plain_kernel, dim3(blocks_for(njobs)), dim3(BLOCK), 0, 0, d_jobs, njobs, cdf, lu.d_result.get<job_result>());
     else hipLaunchKernelGGL(lit_scan_wave_kernel, dim3((unsigned)njobs), dim3(64), 0, 0, d_jobs, cdf, lu.d_result.get<job_result>());
     LAUNCHED(u);
@@ -324,7 +344,7 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
       if (!(r.back > 0) || !std::isfinite(scale) || M < 16) continue;
       ix.guide_offset = (int)num_guide, ix.guide_buckets = (int)M, ix.guide_scale = scale;
       num_guide += M;
-    } else if (en.from >= 0 && lu.index[(size_t)en.from].levels > 0) {
+    } else if (en.from >= 0 && n > 0 && lu.index[(size_t)en.from].levels > 0) {   // (n = 0: an environment that lost its texture)
       const DCdfIndex& was = lu.index[(size_t)en.from];
       index_layout(n, num_pool, ix, f);
       num_pool = f.end;
@@ -367,11 +387,14 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
   if (int rc = prims_buf.allocate(20 * (size_t)nl * sizeof(float4))) return rc;
   HIP_TRY(hipMemset(prims_buf.get(), 0, 20 * (size_t)nl * sizeof(float4) + (nl ? 0 : 16)));
   for (int l = 0; l < nl; l++)
-    if (list[(size_t)l].l.instance < 0 && list[(size_t)l].l.sdf < 0)
+    if (env_of[(size_t)l] >= 0) {
+      HIP_TRY(hipMemcpy(rec_buf.get<float4>() + 8 * (size_t)l, (*envs)[(size_t)env_of[(size_t)l]].record, 8 * sizeof(float4), hipMemcpyHostToDevice));
+      u.last_bytes += 8 * sizeof(float4);
+    } else if (list[(size_t)l].l.instance < 0 && list[(size_t)l].l.sdf < 0)
       if (int rc = move(rec_buf.get<float4>() + 8 * (size_t)l, d.light_rec + 8 * (size_t)list[(size_t)l].from, 8 * sizeof(float4))) return rc;
   if (nl > 0) {
     hipLaunchKernelGGL(lit_records_kernel, dim3(blocks_for(nl)), dim3(BLOCK), 0, 0, rec_buf.get<float4>(), lights_buf.get<vpt_light>(), lu.d_tags.get<int>(), nl, cdf,
-        d.instances, d.shapes);
+        d.instances, d.shapes, envs ? 1 : 0);
     LAUNCHED(u);
   }
   HIP_TRY(hipDeviceSynchronize());   // nothing reads the old tables any more

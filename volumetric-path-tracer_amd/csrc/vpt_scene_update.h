@@ -18,6 +18,7 @@ struct scene_updater {
   bool ready = false;
   // host copies of the small tables validation reads
   std::vector<vpt_material> materials;
+  std::vector<vpt_environment> environments;   // kept current by every edit of a frame here and of an entry in vpt_scene_update_textures
   std::vector<char>         textured;        // material bound to a mesh instance: its texture ids are range-checked
   std::vector<DShape>       shapes;
   std::vector<vpt_light>    lights;

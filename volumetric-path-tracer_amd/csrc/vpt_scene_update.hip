@@ -16,6 +16,7 @@
 #include "vpt_error.h"
 #include "vpt_launch.h"
 #include "vpt_scene_update.h"
+#include "vpt_update_helpers.h"
 
 namespace {
 
@@ -243,8 +244,6 @@ __global__ void upd_light_records_kernel(float4* __restrict__ light_rec, const v
 // ---- host -----------------------------------------------------------------------------------------------------------------
 constexpr int BLOCK = 256;
 inline unsigned blocks_for(long long n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-template <typename T>
-T* mut(const T* p) { return const_cast<T*>(p); }   // the scene owns its tables: DScene names them const for the render kernels
 
 // internal nodes by depth.  validate() made every child index larger than its parent's, so one forward pass gives every depth.
 void make_levels(const vpt_bvh_node* nodes, int count, bvh_levels& lv, std::vector<int>& order) {
@@ -280,6 +279,7 @@ int updater_init(const DScene& d, long long num_shape_nodes, scene_updater& u) {
   std::vector<DInstance>    instances;
   std::vector<vpt_bvh_node> scene_nodes, shape_nodes;
   if (int rc = read_back(u.materials, d.materials, (size_t)d.num_materials)) return rc;
+  if (int rc = read_back(u.environments, d.environments, (size_t)d.num_environments)) return rc;
   if (int rc = read_back(u.shapes, d.shapes, (size_t)d.num_shapes)) return rc;
   if (int rc = read_back(u.lights, d.lights, (size_t)d.num_lights)) return rc;
   if (int rc = read_back(instances, d.instances, (size_t)d.num_instances)) return rc;
@@ -319,22 +319,6 @@ int updater_init(const DScene& d, long long num_shape_nodes, scene_updater& u) {
   return VPT_OK;
 }
 
-bool finite_all(const float* p, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-// ids of one list: non-null, in range, no repeats
-int check_ids(const char* what, int n, const int32_t* ids, const void* payload, int limit) {
-  REQUIRE(n >= 0 && (n == 0 || (ids && payload)), "edit: %s list is null or has a negative count", what);
-  std::vector<char> seen((size_t)limit, 0);
-  for (int i = 0; i < n; i++) {
-    REQUIRE(ids[i] >= 0 && ids[i] < limit, "edit: %s entry %d: id %d out of range (%d)", what, i, ids[i], limit);
-    REQUIRE(!seen[(size_t)ids[i]], "edit: %s entry %d: id %d repeated", what, i, ids[i]);
-    seen[(size_t)ids[i]] = 1;
-  }
-  return VPT_OK;
-}
 bool emissive(const vpt_material& m) { return !(m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0); }   // make_lights, yocto_pathtrace.cpp:990
 
 int validate_edit(const DScene& d, const host_mirrors& h, const scene_updater& u, const vpt_scene_edit& e, bool lights) {
@@ -456,6 +440,7 @@ int scene_update_apply(DScene& d, const host_mirrors& h, long long num_shape_nod
     HIP_TRY(hipMemcpy(&mut(d.environments)[id].frame, &e.environment_frames[i], sizeof(vpt_frame), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(mut(d.env_inv) + 3 * (size_t)id, inv, sizeof(inv), hipMemcpyHostToDevice));
     u.last_bytes += sizeof(vpt_frame) + sizeof(inv);
+    u.environments[(size_t)id].frame = e.environment_frames[i];
     for (int l = 0; l < d.num_lights; l++) {   // light records of a textured environment hold both frames (build_lights); a constant one's stay zero
       const vpt_light& lt = u.lights[(size_t)l];
       if (lt.instance >= 0 || lt.sdf >= 0 || lt.environment != id) continue;

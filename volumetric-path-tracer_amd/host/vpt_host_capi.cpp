@@ -246,6 +246,64 @@ int vpth_scene_update_lights(void* hh, char* err, int errlen) {
     return set_error(err, errlen, e.what()), -1;
   }
 }
+// ---- environments and textures (the host side of vpt_scene_update_textures, include/vpt.h) ------------------------------------
+int vpth_scene_get_environment(void* hh, int id, vpt_environment* out) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (id < 0 || id >= (int)sc.environments.size() || !out) return -1;
+  auto& e = sc.environments[id];
+  memcpy(&out->frame, &e.frame, sizeof(vpt_frame)), memcpy(out->emission, &e.emission, 12);
+  out->emission_tex = e.emission_tex;
+  return 0;
+}
+// frame, emission and emission_tex of an environment; desc and stats() follow at vpth_scene_update_textures
+int vpth_scene_set_environment(void* hh, int id, const vpt_environment* in, char* err, int errlen) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (id < 0 || id >= (int)sc.environments.size() || !in) return set_error(err, errlen, "environment id out of range or null pointer"), -1;
+  auto frame = (const float*)&in->frame;
+  for (auto k = 0; k < 12; k++)
+    if (!std::isfinite(frame[k])) return set_error(err, errlen, "a frame value is not finite"), -1;
+  for (auto v : in->emission)
+    if (!std::isfinite(v)) return set_error(err, errlen, "an emission value is not finite"), -1;
+  if (in->emission_tex < -1 || in->emission_tex >= (int)sc.textures.size()) return set_error(err, errlen, "emission_tex is neither -1 nor a texture"), -1;
+  // an emissive environment's texture holds texels: vpt_scene_create and vpt_scene_update_textures refuse the scene otherwise
+  auto lit = !(in->emission[0] == 0 && in->emission[1] == 0 && in->emission[2] == 0);
+  if (lit && in->emission_tex >= 0 && (int64_t)sc.textures[in->emission_tex].width * sc.textures[in->emission_tex].height == 0)
+    return set_error(err, errlen, "the emission texture of an emissive environment has no texels"), -1;
+  auto& e = sc.environments[id];
+  memcpy((void*)&e.frame, &in->frame, sizeof(vpt_frame)), memcpy((void*)&e.emission, in->emission, 12);
+  e.emission_tex = in->emission_tex;
+  return 0;
+}
+// width, height, linear, is_float of a texture, and its texels (float4 or uchar4) when they fit `capacity` bytes
+int vpth_scene_get_texture(void* hh, int id, int* width, int* height, int* linear, int* is_float, void* texels, int64_t capacity) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (id < 0 || id >= (int)sc.textures.size()) return -1;
+  auto& t = sc.textures[id];
+  *width = t.width, *height = t.height, *linear = t.linear, *is_float = !t.pixelsf.empty();
+  auto bytes = (int64_t)(*is_float ? t.pixelsf.size() * 16 : t.pixelsb.size() * 4);
+  if (texels && capacity >= bytes && bytes > 0) memcpy(texels, *is_float ? (const void*)t.pixelsf.data() : (const void*)t.pixelsb.data(), (size_t)bytes);
+  return 0;
+}
+// all texels of a texture replaced (any size, either format); desc and stats() follow at vpth_scene_update_textures
+int vpth_scene_set_texture(void* hh, int id, int width, int height, int linear, int is_float, const void* texels, char* err, int errlen) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (id < 0 || id >= (int)sc.textures.size()) return set_error(err, errlen, "texture id out of range"), -1;
+  if (width < 0 || height < 0 || (int64_t)width * height >= (1ll << 31)) return set_error(err, errlen, "bad texture size"), -1;
+  auto n = (size_t)width * (size_t)height;
+  if (n > 0 && !texels) return set_error(err, errlen, "null texels"), -1;
+  if (is_float && n == 0) return set_error(err, errlen, "a float texture needs at least one texel (an empty one reads as bytes)"), -1;
+  for (auto& e : sc.environments)
+    if (n == 0 && e.emission_tex == id && !(e.emission.x == 0 && e.emission.y == 0 && e.emission.z == 0))
+      return set_error(err, errlen, "an emissive environment names this texture: it needs at least one texel"), -1;
+  auto& t = sc.textures[id];
+  t.width = width, t.height = height, t.linear = linear != 0;
+  t.pixelsf.clear(), t.pixelsb.clear();
+  if (is_float) t.pixelsf.assign((const vec4f*)texels, (const vec4f*)texels + n);
+  else t.pixelsb.assign((const vec4b*)texels, (const vec4b*)texels + n);
+  return 0;
+}
+// make_lights of the scene as the setters above left it, then the flattened descriptor again (its address changes)
+int vpth_scene_update_textures(void* hh, char* err, int errlen) { return vpth_scene_update_lights(hh, err, errlen); }
 void vpth_scene_free(void* h) { delete (host_scene*)h; }
 const vpt_scene_desc* vpth_scene_desc(void* h) { return &((host_scene*)h)->flat->desc; }
 const vpt_scene_curves* vpth_scene_curves(void* h) { return ((host_scene*)h)->flat->curves_or_null(); }   // null: no points or lines
