@@ -800,6 +800,49 @@ int vpt_vertex_normals(int device, int32_t num_vertices, const float* positions,
 int vpt_displace_vertices(int device, const vpt_texture* texture, const void* texels, float displacement, int32_t num_vertices,
                           const float* positions, const float* normals, const float* texcoords, float* new_positions);
 
+/* ---- baking a mesh into a signed-distance voxel grid -----------------------------------------------------------
+ * The load-time producer of the `volume<float>` grids the implicit shaders render (the reference only loads them: load_volume,
+ * yocto_sceneio.cpp:885-967).  The rule, which csrc/vpt_bake_rule.h states operation by operation for the kernel and for the host
+ * mirror (host/vpt_bake.cpp: the same bits):
+ *  - Sample point.  Voxel (i, j, k) is sampled at origin + (float)i * step per axis: float32, unfused.  voxels[x + y*W + z*W*H].
+ *  - Value.  voxel = s * sqrt(d2): d2 the smallest squared distance from the sample point p to any kept triangle, s = -1 if
+ *    dot(p - c, n) < 0 and +1 otherwise, c the closest point of the winning triangle, n the pseudonormal of the feature c lies on
+ *    (Baerentzen & Aanaes 2005): the face, one of its three edges or one of its three vertices.  A point on the surface gives +0.
+ *  - Closest point.  The seven-region test of Ericson, Real-Time Collision Detection §5.1.5, float32, nothing fused, regions tested in
+ *    the order vertex A, vertex B, edge AB, vertex C, edge AC, edge BC, face with the book's comparisons (<= 0, >= 0); the two edge
+ *    parameters and the face's 1 / (va + vb + vc) are IEEE divisions; d2 = dot(p - c, p - c) summed x, y, z left to right.
+ *  - Winner.  The lexicographic minimum of (d2, triangle index in the caller's order): the value depends on no visiting order, BVH
+ *    shape or thread count.  A candidate whose d2 is NaN never wins (its comparisons are false).
+ *  - Dropped triangles.  A triangle whose float32 cross product (b - a) x (c - a), unfused, is exactly {0, 0, 0} takes no part in
+ *    distances or normals and is counted in dropped_triangles.  If none is left: VPT_ERR_INVALID_ARG.
+ *  - Feature normals.  Computed on the host only, in double, once per bake, by vpt_bake_feature_normals (plain C++, no device call:
+ *    the host's libm is the only one involved), 21 floats per triangle rounded to float32: face, edge ab, edge bc, edge ca, vertex a,
+ *    b, c.  Face: the unit normal.  Edge: the sum of the unit face normals of every kept triangle on that edge.  Vertex: the sum over
+ *    incident kept triangles of (angle at the vertex) * (unit face normal), the angle by acos of the clamped cosine.  Nothing is
+ *    normalised: only the sign is read.  Adjacency is by POSITION BITS, not by index: two vertices whose three floats have the same
+ *    bit patterns (after -0 becomes +0) are one vertex, so UV seams and per-face duplicated vertices do not open the surface.
+ *    A dropped triangle's 21 floats are 0 and kept[t] = 0.
+ *  - Validation, before any device call (VPT_ERR_INVALID_ARG, the message names the entry; `voxels` / `normals` untouched): non-null
+ *    pointers, num_triangles >= 1, indices in range, every position, origin and step float finite, whd >= 1 with a product < 2^31.
+ *    vpt_bake_feature_normals validates the whole descriptor too.
+ *  - Stack.  The kernel walks a BVH over the kept triangles (the project's builder) with a per-lane stack of fixed capacity; the depth
+ *    of the built tree is computed on the host, and a tree that needs more gives VPT_ERR_UNSUPPORTED with no kernel launched
+ *    (stats->launches == 0), as vpt_scene_create does for its stacks.
+ *  - VPT_BAKE_BRUTE=1 in the environment, read per call: no BVH, every voxel over every kept triangle.  The same bits (the tests' and
+ *    the measurement's A/B switch).
+ *  - Synchronous.  stats (nullable): bvh_nodes / bvh_depth (root = 0) of the tree (0 in the brute form), launches = bake kernels
+ *    launched, device_ms = their time by HIP events. */
+typedef struct vpt_bake_desc {
+  int32_t num_vertices;  const float*   positions;  /* float3, grid-local space */
+  int32_t num_triangles; const int32_t* triangles;  /* int3 */
+  int32_t whd[3];                                   /* voxels per axis, each >= 1, product < 2^31 */
+  float   origin[3], step[3];                       /* sample point of voxel (i,j,k), float32, unfused:
+                                                       origin + (float)i * step  per axis */
+} vpt_bake_desc;
+typedef struct vpt_bake_stats { int32_t dropped_triangles, bvh_nodes, bvh_depth, launches; float device_ms; } vpt_bake_stats;
+int vpt_bake_sdf(int device, const vpt_bake_desc* desc, float* voxels /* x + y*W + z*W*H */, vpt_bake_stats* stats /* may be NULL */);
+int vpt_bake_feature_normals(const vpt_bake_desc* desc, float* normals /* 21 floats per triangle */, int32_t* kept /* 1/0 per triangle, may be NULL */);
+
 /* Device self-test of an arithmetic shortcut the kernels rely on for bit-exact parity: the reference divides
  * (1 / d per ray, yocto_bvh.cpp:806-808; 1 / det per triangle, yocto_geometry.h:690), the kernels use
  * v_rcp_f32 + one Newton step where every lane's operand has a biased exponent in 1..250.  Runs all 2^32 bit

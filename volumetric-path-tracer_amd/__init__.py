@@ -107,6 +107,16 @@ class VptTextureEdit(C.Structure):  # vpt_texture_edit
 MATERIAL_TYPES = ["matte", "glossy", "reflective", "transparent", "refractive", "subsurface", "volumetric", "gltfpbr"]
 
 
+class VptBakeDesc(C.Structure):  # vpt_bake_desc
+    _fields_ = [("num_vertices", C.c_int32), ("positions", C.c_void_p), ("num_triangles", C.c_int32), ("triangles", C.c_void_p),
+                ("whd", C.c_int32 * 3), ("origin", C.c_float * 3), ("step", C.c_float * 3)]
+
+
+class VptBakeStats(C.Structure):  # vpt_bake_stats
+    _fields_ = [("dropped_triangles", C.c_int32), ("bvh_nodes", C.c_int32), ("bvh_depth", C.c_int32), ("launches", C.c_int32),
+                ("device_ms", C.c_float)]
+
+
 class SceneEdit:
     """What vpt_scene_update takes (include/vpt.h: vpt_scene_edit), as dictionaries id -> value: cameras (VptCamera), instances and
     environments ((12,) float32 frames x, y, z, o), materials (VptMaterial), shapes ((positions, normals or None) as (n, 3) float32).
@@ -324,6 +334,8 @@ hip.vpt_session_stats.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), 
 hip.vpt_last_kernel_ms.argtypes = [_p, C.POINTER(C.c_float)]
 hip.vpt_intersect.argtypes = [_p, C.c_int, _p, C.c_int, _p, _p]
 hip.vpt_build_bvh.argtypes = [C.c_int, _p, C.c_int, _p, C.c_int, C.POINTER(C.c_int), _p]
+hip.vpt_bake_sdf.argtypes = [C.c_int, C.POINTER(VptBakeDesc), _p, C.POINTER(VptBakeStats)]
+hip.vpt_bake_feature_normals.argtypes = [C.POINTER(VptBakeDesc), _p, _p]
 hip.vpt_last_wave_costs.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int)]
 hip.vpt_scene_record_bytes.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 hip.vpt_multi_create.argtypes = [_p, C.POINTER(C.c_int), C.c_int, C.POINTER(_p)]
@@ -378,6 +390,14 @@ host.vpth_scene_rebuild_bvh_device.argtypes = [_p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_build_bvh_host.argtypes = [_p, C.c_int, _p, C.POINTER(C.c_int), _p]
 host.vpth_denoise.argtypes = [C.c_int, C.c_int, _p, _p, _p, _p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _p, C.c_char_p, C.c_int]
 host.vpth_half_variance.argtypes = [C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_char_p, C.c_int]
+host.vpth_bake_triangles.argtypes = [_p, C.c_int, C.c_int, _p, C.POINTER(C.c_int)]
+host.vpth_bake_grid.argtypes = [_p, C.c_int, _p, C.c_int, _p, _p, _p, C.c_int, _p, C.POINTER(VptBakeStats), C.c_char_p, C.c_int]
+host.vpth_fit_volume.argtypes = [_p, _p, _p, C.c_int, C.POINTER(C.c_float), _p, _p, _p, C.c_char_p, C.c_int]
+host.vpth_bake_volume.argtypes = [_p, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int, _p, C.POINTER(C.c_float), _p, C.POINTER(VptBakeStats),
+                                  C.c_char_p, C.c_int]
+host.vpth_scene_get_volume.argtypes = [_p, C.c_int, _p, C.POINTER(C.c_float), _p, C.c_int64]
+host.vpth_scene_get_volume.restype = C.c_int64
+host.vpth_save_volume.argtypes = [C.c_char_p, _p, C.c_float, _p, C.c_char_p, C.c_int]
 host.vpth_tonemap.argtypes = [C.c_int64, _p, C.c_float, C.c_int, C.c_int, _p, _p]
 host.vpth_upscale_preview.argtypes = [C.c_int, C.c_int, C.c_int, _p, C.c_int, C.c_int, _p]
 host.vpth_make_state_jump.argtypes = [C.c_int, C.c_int, _p]
@@ -482,6 +502,104 @@ def displace_vertices(texels: np.ndarray, linear: bool, displacement: float, pos
     return out
 
 
+def bake_triangles(faces: np.ndarray) -> np.ndarray:
+    """the (m, 3) int32 triangles a bake takes from (n, 3) triangles or (n, 4) quads: a quad is split as the reference's geometry code
+    does, (x, y, w) and (z, w, y); a quad with z == w is the triangle (x, y, z)"""
+    faces = np.ascontiguousarray(faces, np.int32)
+    if faces.ndim != 2 or faces.shape[1] not in (3, 4):
+        raise VptError(f"expected (n, 3) or (n, 4) faces, got {faces.shape}")
+    out = np.zeros((max(1, 2 * len(faces)), 3), np.int32)
+    count = C.c_int()
+    if host.vpth_bake_triangles(faces.ctypes.data, len(faces), faces.shape[1], out.ctypes.data, C.byref(count)) != 0:
+        raise VptError("bake_triangles: bad faces")
+    return out[:count.value].copy()
+
+
+def _bake_stats(st: VptBakeStats) -> dict:
+    return {name: getattr(st, name) for name, _ in VptBakeStats._fields_}
+
+
+def _whd3(whd) -> np.ndarray:
+    whd = np.ascontiguousarray(np.broadcast_to(np.asarray(whd), (3,)), np.int32)
+    return whd
+
+
+def bake_sdf_grid(positions: np.ndarray, triangles: np.ndarray, whd, origin, step, device: Optional[int] = 0):
+    """vpt_bake_sdf (include/vpt.h) over an explicit grid: voxel (i, j, k) of whd = (w, h, d) is sampled at origin + (i, j, k) * step in the
+    mesh's space.  (voxels of shape (d, h, w) float32, stats).  device None: the host mirror (16 CPU threads, every triangle per voxel);
+    else that GPU - the same bits."""
+    positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    triangles = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+    whd = _whd3(whd)
+    origin = np.ascontiguousarray(np.broadcast_to(np.asarray(origin, np.float32), (3,)), np.float32)
+    step = np.ascontiguousarray(np.broadcast_to(np.asarray(step, np.float32), (3,)), np.float32)
+    n = int(whd[0]) * int(whd[1]) * int(whd[2])
+    voxels = np.zeros(n if (whd >= 1).all() and n < 2 ** 31 else 1, np.float32)
+    st = VptBakeStats()
+    err = C.create_string_buffer(512)
+    if host.vpth_bake_grid(positions.ctypes.data, len(positions), triangles.ctypes.data, len(triangles), whd.ctypes.data, origin.ctypes.data,
+                           step.ctypes.data, -1 if device is None else device, voxels.ctypes.data, C.byref(st), err, len(err)) != 0:
+        raise VptError(err.value.decode())
+    return voxels.reshape(int(whd[2]), int(whd[1]), int(whd[0])), _bake_stats(st)
+
+
+def fit_volume(bmin, bmax, whd, padding: int = 2):
+    """the grid of whd voxels around the box [bmin, bmax] that the renderer's lookup reads back in place (vpt_host.h: fit_volume):
+    (res, origin, step, frame) - step = res * W / (W - 1) per axis, the box centred with `padding` voxels to spare on each side,
+    frame the (4, 3) instance frame with o = -origin."""
+    bmin = np.ascontiguousarray(bmin, np.float32).reshape(3)
+    bmax = np.ascontiguousarray(bmax, np.float32).reshape(3)
+    whd = _whd3(whd)
+    res = C.c_float()
+    origin, step, frame = np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros((4, 3), np.float32)
+    err = C.create_string_buffer(512)
+    if host.vpth_fit_volume(bmin.ctypes.data, bmax.ctypes.data, whd.ctypes.data, padding, C.byref(res), origin.ctypes.data, step.ctypes.data,
+                            frame.ctypes.data, err, len(err)) != 0:
+        raise VptError(err.value.decode())
+    return res.value, origin, step, frame
+
+
+def save_volume(path: str, voxels: np.ndarray, res: float) -> None:
+    """the binary .sdf file the scene loader reads ("binary": true): int32 w h d, float res, 16 floats, the voxels; voxels of shape (d, h, w)"""
+    voxels = np.ascontiguousarray(voxels, np.float32)
+    if voxels.ndim != 3:
+        raise VptError(f"expected (d, h, w) voxels, got {voxels.shape}")
+    whd = np.array(voxels.shape[::-1], np.int32)
+    err = C.create_string_buffer(512)
+    if host.vpth_save_volume(os.fsencode(path), whd.ctypes.data, C.c_float(res), voxels.ctypes.data, err, len(err)) != 0:
+        raise VptError(err.value.decode())
+
+
+@dataclass
+class BakedVolume:
+    """bake_sdf's result: the grid and the vol_instances entry that puts it back where the mesh was"""
+    voxels: np.ndarray   # (d, h, w) float32
+    res: float
+    frame: np.ndarray    # (4, 3) float32: x, y, z, o
+    scalef: float
+    stats: dict
+
+    def save(self, path: str) -> None:
+        save_volume(path, self.voxels, self.res)
+
+
+def bake_sdf(positions: np.ndarray, faces: np.ndarray, whd, padding: int = 2, device: Optional[int] = 0) -> BakedVolume:
+    """A mesh ((m, 3) float32 positions, (n, 3) triangles or (n, 4) quads) baked into a signed-distance grid of whd = (w, h, d) voxels (one
+    int: a cube) fitted around it with `padding` voxels to spare (fit_volume), by the rule of include/vpt.h (vpt_bake_sdf): negative
+    inside.  device: GPU index, or None for the host mirror - the same bits."""
+    positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    triangles = bake_triangles(faces)
+    whd = _whd3(whd)
+    n = int(whd[0]) * int(whd[1]) * int(whd[2])
+    voxels = np.zeros(n if (whd >= 1).all() and n < 2 ** 31 else 1, np.float32)
+    res, frame, st = C.c_float(), np.zeros((4, 3), np.float32), VptBakeStats()
+    err = C.create_string_buffer(512)
+    if host.vpth_bake_volume(positions.ctypes.data, len(positions), triangles.ctypes.data, len(triangles), whd.ctypes.data, padding,
+                             -1 if device is None else device, voxels.ctypes.data, C.byref(res), frame.ctypes.data, C.byref(st), err, len(err)) != 0:
+        raise VptError(err.value.decode())
+    return BakedVolume(voxels.reshape(int(whd[2]), int(whd[1]), int(whd[0])), res.value, frame, 1.0, _bake_stats(st))
+
+
 class HostScene:
     """load_scene + tesselate_surfaces + make_bvh + make_lights, flattened for the C-ABI."""
 
@@ -577,6 +695,16 @@ class HostScene:
         i = lambda kind, width: self._get(kind, index, None).view(np.int32).reshape((-1, width) if width else (-1,))
         return {"positions": f(4, 3), "normals": f(5, 3), "texcoords": f(7, 2), "colors": f(8, 4), "radius": f(9, 0),
                 "triangles": i(10, 3), "quads": i(11, 4), "points": i(12, 0), "lines": i(13, 2)}
+
+    def volume(self, index: int):
+        """volume `index` as loaded: (voxels of shape (d, h, w) float32, res)"""
+        whd, res = np.zeros(3, np.int32), C.c_float()
+        n = host.vpth_scene_get_volume(self.handle, index, whd.ctypes.data, C.byref(res), None, 0)
+        if n < 0:
+            raise VptError(f"volume {index} out of range")
+        voxels = np.zeros(n, np.float32)
+        host.vpth_scene_get_volume(self.handle, index, whd.ctypes.data, C.byref(res), voxels.ctypes.data, n)
+        return voxels.reshape(int(whd[2]), int(whd[1]), int(whd[0])), res.value
 
     def set_camera(self, index: int, camera: VptCamera) -> None:
         self._set(self._CAMERA, index, camera)

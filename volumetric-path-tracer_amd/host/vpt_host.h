@@ -317,6 +317,39 @@ class render_session {
   vpt_session* session_ = nullptr;
 };
 
+// ---- baking a mesh into a signed-distance grid (include/vpt.h: vpt_bake_sdf; host/vpt_bake.cpp) ---------------------------------
+// Extension: the producer of the volume<float> grids the implicit shaders render (the reference only loads them).
+// fit_volume: the grid of `whd` voxels around the box [bmin, bmax] that the renderer's lookup (eval_sdf / eval_volume,
+// yocto_sdfs.cpp:30-49, 92-127) reads back in place: that lookup puts voxel i of an axis at i * (res * W) / (W - 1) and knows one scalar
+// `res` for all three, so step_a = (res * (float)W_a) / (float)(W_a - 1) with the smallest res for which the box plus `padding` voxels
+// on each side fits on every axis, the box centred.  whd >= 2 * padding + 3 per axis, padding >= 0 (std::invalid_argument otherwise).
+// instance: identity axes, frame.o = -origin, scalef = 1 (the reference reads the grid at transform_point(frame, world point)).
+struct volume_fit {
+  float           res    = 0;
+  vec3f           origin = {}, step = {};
+  volume_instance instance = {};
+};
+volume_fit fit_volume(const vec3f& bmin, const vec3f& bmax, const vec3i& whd, int padding = 2);
+// the triangles of a shape: its own, and its quads split as the reference's geometry code does, (x, y, w) and (z, w, y); a quad
+// with z == w is the triangle (x, y, z)
+vector<vec3i> bake_triangles(const shape_data& shape);
+// the host mirror of vpt_bake_sdf: the rule header over every voxel and every kept triangle on `threads` CPU threads (1..16), the same
+// bits as the device; throws std::invalid_argument with the C-ABI's message for a descriptor it refuses (voxels untouched)
+void bake_sdf(vector<float>& voxels, const vector<vec3f>& positions, const vector<vec3i>& triangles, const vec3i& whd, const vec3f& origin,
+    const vec3f& step, vpt_bake_stats* stats = nullptr, int threads = 16);
+// the same on GPU `device` (vpt_bake_sdf); throws std::runtime_error with vpt_last_error() if that fails
+void bake_sdf_device(vector<float>& voxels, const vector<vec3f>& positions, const vector<vec3i>& triangles, const vec3i& whd,
+    const vec3f& origin, const vec3f& step, int device, vpt_bake_stats* stats = nullptr);
+// fit_volume around the mesh, then bake_sdf (device < 0) or bake_sdf_device: the volume and the instance that puts it where the mesh was
+struct baked_volume {
+  volume_data     volume   = {};
+  volume_instance instance = {};
+  vpt_bake_stats  stats    = {};
+};
+baked_volume bake_volume(const vector<vec3f>& positions, const vector<vec3i>& triangles, const vec3i& whd, int padding = 2, int device = -1);
+// the binary .sdf layout load_volume reads: int32 w h d, float res, 16 floats (the identity; no reader uses them), the voxels
+bool save_volume(const string& filename, const volume_data& vol, string& error);
+
 // ---- flattening to the C-ABI ----------------------------------------------------------------
 struct flat_scene {
   vpt_scene_desc desc = {};

@@ -495,4 +495,87 @@ int64_t vpth_encode_jpeg_q75(int width, int height, const uint8_t* rgba8, uint8_
   return (int64_t)bytes.size();
 }
 
+// ---- baking a mesh into a signed-distance grid (include/vpt.h: vpt_bake_sdf; vpt_host.h: bake_sdf) ------------------------------------
+// faces (int4 quads, z == w: a triangle; or int3) to the triangles the bake takes: out has room for 2 * nfaces triangles
+int vpth_bake_triangles(const int32_t* faces, int nfaces, int corners, int32_t* out, int* count) {
+  if (nfaces < 0 || (nfaces > 0 && !faces) || !out || !count || (corners != 3 && corners != 4)) return -1;
+  auto shape = shape_data{};
+  if (corners == 3) shape.triangles.assign((const vec3i*)faces, (const vec3i*)faces + nfaces);
+  else shape.quads.assign((const vec4i*)faces, (const vec4i*)faces + nfaces);
+  auto triangles = bake_triangles(shape);
+  memcpy(out, triangles.data(), triangles.size() * sizeof(vec3i));
+  *count = (int)triangles.size();
+  return 0;
+}
+// bake_sdf over an explicit grid: the host mirror (device < 0) or vpt_bake_sdf on that GPU; voxels: whd[0] * whd[1] * whd[2] floats, untouched on failure
+int vpth_bake_grid(const float* positions, int nverts, const int32_t* triangles, int ntris, const int32_t* whd, const float* origin, const float* step,
+    int device, float* voxels, vpt_bake_stats* stats, char* err, int errlen) {
+  try {
+    if (nverts < 0 || ntris < 0 || (nverts > 0 && !positions) || (ntris > 0 && !triangles) || !whd || !origin || !step || !voxels)
+      throw std::invalid_argument{"bake_sdf: null pointer or negative count"};
+    auto pos = vector<vec3f>((const vec3f*)positions, (const vec3f*)positions + nverts);
+    auto tri = vector<vec3i>((const vec3i*)triangles, (const vec3i*)triangles + ntris);
+    auto out = vector<float>{};
+    auto st  = vpt_bake_stats{};
+    if (device < 0) bake_sdf(out, pos, tri, {whd[0], whd[1], whd[2]}, {origin[0], origin[1], origin[2]}, {step[0], step[1], step[2]}, &st);
+    else bake_sdf_device(out, pos, tri, {whd[0], whd[1], whd[2]}, {origin[0], origin[1], origin[2]}, {step[0], step[1], step[2]}, device, &st);
+    memcpy(voxels, out.data(), out.size() * 4);
+    if (stats) *stats = st;
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
+}
+int vpth_fit_volume(const float* bmin, const float* bmax, const int32_t* whd, int padding, float* res, float* origin, float* step, float* frame,
+    char* err, int errlen) {
+  try {
+    auto fit = fit_volume({bmin[0], bmin[1], bmin[2]}, {bmax[0], bmax[1], bmax[2]}, {whd[0], whd[1], whd[2]}, padding);
+    *res = fit.res;
+    memcpy(origin, &fit.origin, 12), memcpy(step, &fit.step, 12), memcpy(frame, &fit.instance.frame, 48);
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
+}
+// bake_volume: fit_volume around the triangles, then the bake; frame: the 12 floats of the instance's frame
+int vpth_bake_volume(const float* positions, int nverts, const int32_t* triangles, int ntris, const int32_t* whd, int padding, int device, float* voxels,
+    float* res, float* frame, vpt_bake_stats* stats, char* err, int errlen) {
+  try {
+    if (nverts < 0 || ntris < 0 || (nverts > 0 && !positions) || (ntris > 0 && !triangles) || !whd || !voxels || !res || !frame)
+      throw std::invalid_argument{"bake_volume: null pointer or negative count"};
+    auto baked = bake_volume(vector<vec3f>((const vec3f*)positions, (const vec3f*)positions + nverts),
+        vector<vec3i>((const vec3i*)triangles, (const vec3i*)triangles + ntris), {whd[0], whd[1], whd[2]}, padding, device);
+    memcpy(voxels, baked.volume.vol.data(), baked.volume.vol.size() * 4);
+    *res = baked.volume.res;
+    memcpy(frame, &baked.instance.frame, 48);
+    if (stats) *stats = baked.stats;
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
+}
+// a loaded scene's volume `id`: whd (three int32) and res; its voxels to `voxels` when `capacity` floats hold them; returns their number, -1 for a bad id
+int64_t vpth_scene_get_volume(void* hh, int id, int32_t* whd, float* res, float* voxels, int64_t capacity) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (id < 0 || id >= (int)sc.volumes.size() || !whd || !res) return -1;
+  auto& v = sc.volumes[id];
+  whd[0] = v.whd.x, whd[1] = v.whd.y, whd[2] = v.whd.z, *res = v.res;
+  auto n = (int64_t)v.whd.x * v.whd.y * v.whd.z;
+  if (voxels && capacity >= n && (int64_t)v.vol.size() >= n) memcpy(voxels, v.vol.data(), (size_t)n * 4);
+  return n;
+}
+int vpth_save_volume(const char* filename, const int32_t* whd, float res, const float* voxels, char* err, int errlen) {
+  try {
+    if (!filename || !whd || !voxels || whd[0] < 1 || whd[1] < 1 || whd[2] < 1) throw std::invalid_argument{"save_volume: null pointer or empty volume"};
+    auto vol = volume_data{};
+    vol.whd = {whd[0], whd[1], whd[2]}, vol.res = res;
+    vol.vol.assign(voxels, voxels + (size_t)whd[0] * whd[1] * whd[2]);
+    auto error = string{};
+    if (!save_volume(filename, vol, error)) throw std::runtime_error{error};
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
+}
+
 }  // extern "C"

@@ -18,7 +18,10 @@
 // run_interactive, through a vpt_session on GPU 0: the preview of --pratio is written as <stem>.000000<extension>, the device's display after
 // every N samples as <stem>.<samples, six digits><extension>, the finished image as --output; --exposure and --filmic are the display's
 // tone-mapping parameters; with --denoise the display shows the filtered image.  With --exposure 0 and without --filmic, --output holds
-// the bytes of the offline run with the same arguments: the same state, the same host 8-bit stage).
+// the bytes of the offline run with the same arguments: the same state, the same host 8-bit stage), --bake-sdf FILE (no scene is
+// rendered: the shape file is loaded through the host loader, baked by vpt_bake_sdf on GPU 0 - or by the host mirror with --bake-host,
+// same bytes - into a grid of --bake-res voxels per axis fitted around it with --bake-padding voxels to spare, and written to --output
+// as the binary .sdf the scene loader reads; `res` and a vol_instances entry that puts the grid where the shape was go to stdout).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -68,6 +71,10 @@ const std::vector<std::pair<string, option>> options = {
     {"pratio", {option::int_k, 1, 64, "Progressive: preview ratio."}},
     {"exposure", {option::anyfloat_k, 1, 0, "Progressive: display exposure."}},
     {"filmic", {option::bool_k, 1, 0, "Progressive: filmic tone mapping."}},
+    {"bake-sdf", {option::string_k, 1, 0, "Bake this shape file (PLY, OBJ) into a signed-distance grid written to --output; renders nothing. (extension)"}},
+    {"bake-res", {option::int_k, 1, 1024, "Baking: voxels per axis."}},
+    {"bake-padding", {option::int_k, 0, 64, "Baking: voxels to spare around the shape on each side."}},
+    {"bake-host", {option::bool_k, 1, 0, "Baking: run the host mirror instead of the GPU: same file."}},
 };
 const option* find_option(const string& name) {
   for (auto& [n, o] : options)
@@ -215,6 +222,37 @@ int main(int argc, const char** argv) {
   if (values.count("shader"))
     for (size_t k = 0; k < pathtrace_shader_names.size(); k++)
       if (pathtrace_shader_names[k] == values["shader"]) params.shader = (pathtrace_shader_type)k;
+
+  for (auto name : {"bake-res", "bake-padding", "bake-host"})
+    if (values.count(name) && !values.count("bake-sdf")) cli_error(string{"option "} + name + " needs --bake-sdf");
+  if (values.count("bake-sdf")) {
+    auto res = 0, padding = 2;
+    auto on_host = false;
+    get_int("bake-res", res), get_int("bake-padding", padding), get_bool("bake-host", on_host);
+    if (!values.count("bake-res")) cli_error("missing value for bake-res");
+    if (res < 2 * padding + 3) cli_error("bad value for bake-res");
+    if (!values.count("output")) cli_error("missing value for output");
+    try {
+      auto error = string{};
+      auto shape = shape_data{};
+      if (!load_shape(values["bake-sdf"], shape, error, true)) print_fatal(error);
+      auto triangles = bake_triangles(shape);
+      if (triangles.empty()) print_fatal(values["bake-sdf"] + ": the shape has no triangles or quads");
+      auto t0    = std::chrono::steady_clock::now();
+      auto baked = bake_volume(shape.positions, triangles, {res, res, res}, padding, on_host ? -1 : 0);
+      auto secs  = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (!save_volume(output, baked.volume, error)) print_fatal(error);
+      auto& f = baked.instance.frame;
+      printf("baked: %zu triangles (%d dropped) into %d x %d x %d voxels in %.3f s (%s)\n", triangles.size(), baked.stats.dropped_triangles, res, res,
+          res, secs, on_host ? "host mirror" : "GPU 0");
+      printf("res: %.9g\n", baked.volume.res);
+      printf("{\"name\": \"baked\", \"volume\": 0, \"material\": 0, \"scale\": %.9g, \"frame\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g]}\n",
+          baked.instance.scalef, f.x.x, f.x.y, f.x.z, f.y.x, f.y.y, f.y.z, f.z.x, f.z.y, f.z.z, f.o.x, f.o.y, f.o.z);
+      return 0;
+    } catch (const std::exception& e) {
+      print_fatal(e.what());
+    }
+  }
 
   try {
     auto error = string{};
