@@ -297,8 +297,8 @@ void vpt_scene_destroy(vpt_scene* scene);
  *    the tables may be half written and the handle is good for vpt_scene_destroy only.
  *  - What an edit may not do (VPT_ERR_UNSUPPORTED, scene unchanged): turn a material's emission from zero to non-zero or back
  *    (the light list and the kernel instances are fixed at creation); move the vertices of a shape that a light's instance uses
- *    (its element CDF is the caller's light_cdf, made from areas); change counts, indices, radii, textures, volumes or SDFs (the
- *    edit has no field for them).  Moving an emissive INSTANCE is allowed (the CDF is over shape-local areas).
+ *    (its element CDF is the caller's light_cdf, made from areas); change counts, indices or radii (the edit has no field for them;
+ *    textures are vpt_scene_update_textures', volumes and SDFs vpt_scene_update_volumes').  Moving an emissive INSTANCE is allowed (the CDF is over shape-local areas).
  *  - Synchronisation: the call waits for the device's outstanding work (it rewrites tables launches read) and has completed when
  *    it returns.  It touches no pathtrace_state: restarting accumulation is the caller's business, as in the reference's
  *    reset_display.  It forgets the handle's launch-schedule record and tile-splitting decision (the camera index may be the
@@ -421,6 +421,71 @@ typedef struct vpt_texture_edit {
 } vpt_texture_edit;
 int vpt_scene_update_textures(vpt_scene* scene, const vpt_texture_edit* edit);
 
+/* ---- edits of volumes, grid instances and SDFs; baking into the resident voxel pool -----------------------------------
+ * The `implicit` side of a resident scene: the voxel grids, the instances that place them and the analytic SDFs.  A struct of its own,
+ * as for textures: vpt_scene_edit keeps its layout.  Counts stay fixed: no volume, instance or SDF is added or removed, so the LDS
+ * budget of the implicit kernels' record copy, checked at creation, stays valid.
+ * After vpt_scene_update_volumes(s, edit) every table on the device that a render, vpt_intersect or vpt_kat call reads holds what
+ * vpt_scene_create would hold for the edited descriptor carrying the host's make_lights of the edited scene: every render is
+ * bit-identical to a fresh handle's and vpt_scene_light_tables_hash equals a fresh handle's on all six tables.  The layout of the voxel
+ * pool is not part of the contract: nothing observable depends on a volume's offset (vpt_scene_get_volumes reports the resident one).
+ *  - Instances and SDFs.  An instance entry replaces frame, volume, material and scalef; an SDF entry replaces the whole vpt_sdf, type
+ *    included.  The evaluation records (frame, sizes, the identity tag, dimensions, res and the two-word voxel offset of a grid
+ *    instance), the inverse frames, the per-record bounding balls, the scene's bounding ball and the count of planes are remade by
+ *    the function vpt_scene_create calls (vpt_scene_prep.h: prep_sdf_records), for ALL records, from host mirrors of the three small
+ *    tables read back on the first edit of a handle: a res, dimension or offset change of a volume therefore reaches the record of every
+ *    instance that names it.
+ *  - Voxels from the host (offset >= 0).  whd and res describe the volume AFTER the edit; the entry writes the box region_lo ..
+ *    region_lo + region_whd of it from edit->voxels + offset, region order, x fastest.  The same whd overwrites in place and any region
+ *    box inside the grid is allowed (an empty one changes res alone).  A new whd requires the region to be the whole grid and mode
+ *    REPLACE: the volume gets fresh room at the end of a pool allocated anew, the old pool moved device to device; the room the volume
+ *    leaves stays unused until vpt_scene_destroy (the pool is never compacted).  The payload crosses PCIe once, into a staging buffer; a
+ *    kernel writes the region from there.
+ *  - VPT_VOXELS_UNION is the reference's op_union (yocto_sdfs.h:82) with a the resident and b the incoming value: (a < b) ? a : b - a
+ *    select, never fminf: with a NaN on either side the select decides (a NaN resident value is replaced, a NaN incoming value stays).
+ *  - Voxels baked (offset == -1).  bake is a vpt_bake_desc under the rules of vpt_bake_sdf with bake->whd equal to the entry's whd;
+ *    origin and step are the caller's (fit_volume).  The values have the bits of vpt_bake_sdf for that descriptor - the same kernel
+ *    body, instantiated with the pool as its destination: it runs only the bricks that touch the region, writes only the lanes inside
+ *    it, and in UNION mode selects against the resident value.  No voxel crosses PCIe in either direction.  The host preparation
+ *    (validation, feature normals, the tree through vpt_build_bvh, the depth check, the records) is vpt_bake_sdf's; a tree deeper than
+ *    the kernel's stack gives VPT_ERR_UNSUPPORTED before anything is written.  VPT_BAKE_BRUTE=1 works as there.
+ *  - Lights.  An SDF is a light iff its material is emissive (the materials as the handle holds them); its CDF is {whd.x * whd.y}.  When
+ *    the edit changes which SDFs are lights (an entry's material) or the whd of an SDF that is a light, the light tables are rebuilt
+ *    by the code of vpt_scene_update_lights, every other light's CDF, index and guide table moving device to device.  Otherwise
+ *    nothing of the lights is touched.
+ *  - Validation before anything is written (VPT_ERR_INVALID_ARG, the message names the entry, the scene is untouched): ids in range
+ *    and not repeated within a list; every float finite (frames, scalef, whd, p, res; voxels are data and may hold anything); type in
+ *    0..5; material and volume ids in range; whd >= 0 with a product below 2^31; the region inside whd; mode REPLACE or UNION; a new
+ *    whd only with the whole grid and REPLACE; offset + region size inside the edit's pool; a bake descriptor valid and of the entry's
+ *    whd.  (A volume id cannot be named by a host entry and a bake entry at once: ids are not repeated.)
+ *  - vpt_scene_update_stats afterwards: launches = region kernels + bake kernels + those of a light rebuild; bytes = 4 per host voxel
+ *    + 24 per volume entry + 60 per instance entry + 84 per SDF entry + the remade record tables (144 per SDF: 96 record, 48 inverse
+ *    frame; 112 per grid instance) + per bake entry 32 per tree node and the size of its triangle records - not one voxel - + what a
+ *    light rebuild sends (vpt_scene_update_textures).  Device time: from before the first to after the last launch.
+ *  - Synchronisation, the VPT_ERR_HIP semantics and the forgetting of the launch-schedule record: those of vpt_scene_update. */
+enum { VPT_VOXELS_REPLACE = 0, VPT_VOXELS_UNION = 1 };
+struct vpt_bake_desc;   /* below: baking a mesh into a signed-distance voxel grid */
+typedef struct vpt_volume_source {
+  int32_t whd[3]; float res;            /* the volume AFTER the edit */
+  int32_t region_lo[3], region_whd[3];  /* the box of voxels this entry writes */
+  int32_t mode;                         /* VPT_VOXELS_REPLACE / VPT_VOXELS_UNION */
+  int64_t offset;                       /* first voxel inside edit->voxels (region order, x fastest); -1: baked */
+  const struct vpt_bake_desc* bake;     /* offset == -1: bake->whd must equal whd; origin / step are the caller's (fit_volume) */
+} vpt_volume_source;
+typedef struct vpt_volume_edit {
+  int32_t num_vol_instances; const int32_t* vol_instance_ids; const vpt_volume_instance* vol_instances;
+  int32_t num_sdfs;          const int32_t* sdf_ids;          const vpt_sdf* sdfs;
+  int32_t num_volumes;       const int32_t* volume_ids;       const vpt_volume_source* volumes;
+  int64_t num_voxels;        const float* voxels;
+} vpt_volume_edit;
+int vpt_scene_update_volumes(vpt_scene* scene, const vpt_volume_edit* edit);
+/* The three small tables as the device holds them now, for callers that keep a host copy, and for the tests.  Capacities in
+ * entries, at least the scene's counts; a null array is skipped.  A volume's offset is the resident pool's. */
+int vpt_scene_get_volumes(vpt_scene* scene, vpt_volume* volumes, int volume_capacity, vpt_volume_instance* vol_instances, int instance_capacity,
+                          vpt_sdf* sdfs, int sdf_capacity);
+/* the voxels of one volume as the device holds them (x + y*W + z*W*H); capacity in voxels, at least the volume's W*H*D */
+int vpt_scene_get_voxels(vpt_scene* scene, int volume, float* voxels, int64_t capacity);
+
 /* ---- the drop-in for pathtrace_samples() --------------------------------------------
  * Host, row-major (idx = j*width + i) caller-owned state, exactly pathtrace_state
  * (yocto_pathtrace.h:57-64): image float4[w*h], hits int32[w*h], rng {u64 state, u64 inc}[w*h].
@@ -464,6 +529,8 @@ int  vpt_multi_update(vpt_multi* m, const vpt_scene_edit* edit);
 int  vpt_multi_update_lights(vpt_multi* m, const vpt_scene_edit* edit);
 /* vpt_scene_update_textures in the same way */
 int  vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit);
+/* vpt_scene_update_volumes in the same way (a bake entry is prepared and baked once per device) */
+int  vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit);
 int  vpt_multi_device_count(const vpt_multi* m);
 /* how vpt_multi_get_render moves the parts: "rccl", "peer-copy" (several devices, no RCCL) or "local" (one device) */
 const char* vpt_multi_transport(const vpt_multi* m);
@@ -712,6 +779,8 @@ int  vpt_session_edit(vpt_session* session, const vpt_scene_edit* edit);
 int  vpt_session_edit_lights(vpt_session* session, const vpt_scene_edit* edit);
 /* vpt_scene_update_textures, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_edit_textures(vpt_session* session, const vpt_texture_edit* edit);
+/* vpt_scene_update_volumes, then a reset; a refused edit leaves the session as it was */
+int  vpt_session_edit_volumes(vpt_session* session, const vpt_volume_edit* edit);
 int  vpt_session_get_display(vpt_session* session, uint8_t* rgba8, float* display_f);
 int  vpt_session_get_image(vpt_session* session, float* linear);
 int  vpt_session_get_denoised(vpt_session* session, float* linear);

@@ -104,6 +104,32 @@ class VptTextureEdit(C.Structure):  # vpt_texture_edit
                 ("num_texels_f", C.c_int64), ("texels_f", C.c_void_p), ("num_texels_b", C.c_int64), ("texels_b", C.c_void_p)]
 
 
+class VptVolume(C.Structure):  # vpt_volume
+    _fields_ = [("whd", C.c_int32 * 3), ("res", C.c_float), ("offset", C.c_int64)]
+
+
+class VptVolumeInstance(C.Structure):  # vpt_volume_instance
+    _fields_ = [("frame", VptFrame), ("volume", C.c_int32), ("material", C.c_int32), ("scalef", C.c_float)]
+
+
+class VptSdf(C.Structure):  # vpt_sdf
+    _fields_ = [("frame", VptFrame), ("type", C.c_int32), ("material", C.c_int32), ("whd", C.c_float * 3), ("p", C.c_float * 4)]
+
+
+class VptVolumeSource(C.Structure):  # vpt_volume_source
+    _fields_ = [("whd", C.c_int32 * 3), ("res", C.c_float), ("region_lo", C.c_int32 * 3), ("region_whd", C.c_int32 * 3), ("mode", C.c_int32),
+                ("offset", C.c_int64), ("bake", C.c_void_p)]
+
+
+class VptVolumeEdit(C.Structure):  # vpt_volume_edit
+    _fields_ = [("num_vol_instances", C.c_int32), ("vol_instance_ids", C.c_void_p), ("vol_instances", C.c_void_p),
+                ("num_sdfs", C.c_int32), ("sdf_ids", C.c_void_p), ("sdfs", C.c_void_p),
+                ("num_volumes", C.c_int32), ("volume_ids", C.c_void_p), ("volumes", C.c_void_p),
+                ("num_voxels", C.c_int64), ("voxels", C.c_void_p)]
+
+
+SDF_TYPES = ["bbox", "box", "capped_cone", "plane", "sphere", "torus"]
+VOXELS_REPLACE, VOXELS_UNION = 0, 1
 MATERIAL_TYPES = ["matte", "glossy", "reflective", "transparent", "refractive", "subsurface", "volumetric", "gltfpbr"]
 
 
@@ -221,6 +247,71 @@ class TextureEdit:
         return abi, keep
 
 
+@dataclass
+class VolumeSource:
+    """One volume entry of a VolumeEdit (include/vpt.h: vpt_volume_source): whd (w, h, d) and res of the volume AFTER the edit, the box
+    region_lo .. region_lo + region_whd it writes, the mode, and where the values come from: voxels (a float32 array of shape region
+    (d, h, w)), or a bake (positions (n, 3), triangles (m, 3), origin, step: the grid of bake_sdf_grid over whd)."""
+    whd: tuple
+    res: float
+    region_lo: tuple
+    region_whd: tuple
+    mode: int = VOXELS_REPLACE
+    voxels: Optional[np.ndarray] = None
+    bake: Optional[tuple] = None   # (positions, triangles, origin, step)
+
+
+class VolumeEdit:
+    """What vpt_scene_update_volumes takes (include/vpt.h: vpt_volume_edit), as dictionaries id -> value: vol_instances
+    (VptVolumeInstance), sdfs (VptSdf) and volumes (VolumeSource).  HostScene's set_volume_instance / set_sdf / set_volume /
+    bake_volume fill one; DeviceScene.update_volumes / MultiDeviceScene.update_volumes / RenderSession.edit_volumes apply it."""
+
+    def __init__(self, vol_instances=None, sdfs=None, volumes=None):
+        self.vol_instances, self.sdfs, self.volumes = dict(vol_instances or {}), dict(sdfs or {}), dict(volumes or {})
+
+    def empty(self) -> bool:
+        return not (self.vol_instances or self.sdfs or self.volumes)
+
+    def to_abi(self):
+        """(VptVolumeEdit, objects that keep its arrays alive)"""
+        keep, abi = [], VptVolumeEdit()
+        inst_ids = np.array(list(self.vol_instances.keys()), np.int32)
+        insts = (VptVolumeInstance * max(1, len(self.vol_instances)))(*self.vol_instances.values())
+        sdf_ids = np.array(list(self.sdfs.keys()), np.int32)
+        sdfs = (VptSdf * max(1, len(self.sdfs)))(*self.sdfs.values())
+        vol_ids = np.array(list(self.volumes.keys()), np.int32)
+        entries = (VptVolumeSource * max(1, len(self.volumes)))()
+        pool, count = [], 0
+        for k, src in enumerate(self.volumes.values()):
+            e = entries[k]
+            e.whd[:], e.res = [int(v) for v in src.whd], float(src.res)
+            e.region_lo[:], e.region_whd[:], e.mode = [int(v) for v in src.region_lo], [int(v) for v in src.region_whd], int(src.mode)
+            if src.bake is not None:
+                positions, triangles, origin, step = src.bake
+                positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+                triangles = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+                desc = VptBakeDesc(len(positions), positions.ctypes.data, len(triangles), triangles.ctypes.data)
+                desc.whd[:] = [int(v) for v in src.whd]
+                desc.origin[:] = [float(v) for v in np.broadcast_to(np.asarray(origin, np.float32), (3,))]
+                desc.step[:] = [float(v) for v in np.broadcast_to(np.asarray(step, np.float32), (3,))]
+                keep += [positions, triangles, desc]
+                e.offset, e.bake = -1, C.addressof(desc)
+            else:
+                voxels = np.ascontiguousarray(src.voxels, np.float32)
+                if voxels.shape != tuple(int(v) for v in src.region_whd)[::-1]:
+                    raise VptError(f"voxels of a volume edit have the region's shape (d, h, w) = {tuple(src.region_whd)[::-1]}, got {voxels.shape}")
+                e.offset, e.bake = count, None
+                pool.append(voxels.reshape(-1))
+                count += voxels.size
+        voxels = np.ascontiguousarray(np.concatenate(pool)) if pool else np.zeros(0, np.float32)
+        keep += [inst_ids, insts, sdf_ids, sdfs, vol_ids, entries, voxels]
+        abi.num_vol_instances, abi.vol_instance_ids, abi.vol_instances = len(self.vol_instances), inst_ids.ctypes.data, C.cast(insts, C.c_void_p).value
+        abi.num_sdfs, abi.sdf_ids, abi.sdfs = len(self.sdfs), sdf_ids.ctypes.data, C.cast(sdfs, C.c_void_p).value
+        abi.num_volumes, abi.volume_ids, abi.volumes = len(self.volumes), vol_ids.ctypes.data, C.cast(entries, C.c_void_p).value
+        abi.num_voxels, abi.voxels = len(voxels), voxels.ctypes.data
+        return abi, keep
+
+
 # defaults of the denoising filter (include/vpt.h: VPT_DENOISE_DEFAULT_*; DESIGN.md §11)
 DENOISE_ITERATIONS, DENOISE_SIGMA_LUMINANCE, DENOISE_SIGMA_NORMAL, DENOISE_SIGMA_ALBEDO = 5, 4.0, 0.35, 0.1
 
@@ -288,6 +379,11 @@ hip.vpt_session_edit_lights.argtypes = [_p, C.POINTER(VptSceneEdit)]
 hip.vpt_scene_update_textures.argtypes = [_p, C.POINTER(VptTextureEdit)]
 hip.vpt_multi_update_textures.argtypes = [_p, C.POINTER(VptTextureEdit)]
 hip.vpt_session_edit_textures.argtypes = [_p, C.POINTER(VptTextureEdit)]
+hip.vpt_scene_update_volumes.argtypes = [_p, C.POINTER(VptVolumeEdit)]
+hip.vpt_multi_update_volumes.argtypes = [_p, C.POINTER(VptVolumeEdit)]
+hip.vpt_session_edit_volumes.argtypes = [_p, C.POINTER(VptVolumeEdit)]
+hip.vpt_scene_get_volumes.argtypes = [_p, _p, C.c_int, _p, C.c_int, _p, C.c_int]
+hip.vpt_scene_get_voxels.argtypes = [_p, C.c_int, _p, C.c_int64]
 hip.vpt_scene_get_lights.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int), _p, C.c_int64, C.POINTER(C.c_int64)]
 hip.vpt_scene_light_tables_hash.argtypes = [_p, _p]
 hip.vpt_scene_get_media.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -379,6 +475,13 @@ host.vpth_scene_set_environment.argtypes = [_p, C.c_int, C.POINTER(VptEnvironmen
 host.vpth_scene_get_texture.argtypes = [_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _p, C.c_int64]
 host.vpth_scene_set_texture.argtypes = [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_char_p, C.c_int]
 host.vpth_scene_update_textures.argtypes = [_p, C.c_char_p, C.c_int]
+host.vpth_scene_count_implicit.argtypes = [_p, C.c_int]
+host.vpth_scene_get_vol_instance.argtypes = [_p, C.c_int, C.POINTER(VptVolumeInstance)]
+host.vpth_scene_set_vol_instance.argtypes = [_p, C.c_int, C.POINTER(VptVolumeInstance), C.c_char_p, C.c_int]
+host.vpth_scene_get_sdf.argtypes = [_p, C.c_int, C.POINTER(VptSdf)]
+host.vpth_scene_set_sdf.argtypes = [_p, C.c_int, C.POINTER(VptSdf), C.c_char_p, C.c_int]
+host.vpth_scene_set_volume.argtypes = [_p, C.c_int, _p, C.c_float, _p, _p, C.c_int, _p, C.c_char_p, C.c_int]
+host.vpth_scene_update_volumes.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_desc.argtypes = [_p]
 host.vpth_scene_desc.restype = _p
 host.vpth_scene_curves.argtypes = [_p]
@@ -432,6 +535,19 @@ class VptSceneDescBvh(C.Structure):
 
 LIGHT = np.dtype([("instance", np.int32), ("environment", np.int32), ("sdf", np.int32), ("cdf_len", np.int32), ("cdf_offset", np.int64)])   # vpt_light
 assert LIGHT.itemsize == 24
+
+
+class VptSceneDescImplicit(C.Structure):
+    """the three tables of vpt_scene_desc behind the implicit shaders: its seventh to ninth {int32 count, pointer} pairs"""
+    _fields_ = [("num_volumes", C.c_int32), ("volumes", C.c_void_p), ("num_vol_instances", C.c_int32), ("vol_instances", C.c_void_p),
+                ("num_sdfs", C.c_int32), ("sdfs", C.c_void_p)]
+    OFFSET = 6 * 16
+
+
+class VptSceneDescVoxels(C.Structure):
+    """the voxel pool of vpt_scene_desc: its ninth {int64 count, pointer} pool"""
+    _fields_ = [("num_voxels", C.c_int64), ("voxels", C.c_void_p)]
+    OFFSET = 10 * 16 + 8 * 16
 
 
 class VptSceneDescLights(C.Structure):
@@ -617,6 +733,7 @@ class HostScene:
     @property
     def desc(self) -> int:
         """address of the vpt_scene_desc (valid while this object lives)"""
+        self._run_bakes()
         return host.vpth_scene_desc(self.handle)
 
     @property
@@ -625,6 +742,7 @@ class HostScene:
         return host.vpth_scene_curves(self.handle)
 
     def stats(self) -> str:
+        self._run_bakes()
         buf = C.create_string_buffer(1 << 20)
         n = host.vpth_scene_stats(self.handle, buf, len(buf))
         if n < 0:
@@ -697,7 +815,8 @@ class HostScene:
                 "triangles": i(10, 3), "quads": i(11, 4), "points": i(12, 0), "lines": i(13, 2)}
 
     def volume(self, index: int):
-        """volume `index` as loaded: (voxels of shape (d, h, w) float32, res)"""
+        """volume `index` as the scene holds it: (voxels of shape (d, h, w) float32, res)"""
+        self._run_bakes()
         whd, res = np.zeros(3, np.int32), C.c_float()
         n = host.vpth_scene_get_volume(self.handle, index, whd.ctypes.data, C.byref(res), None, 0)
         if n < 0:
@@ -812,6 +931,141 @@ class HostScene:
             edit.environments[index] = self.environment(index)
         return edit
 
+    # -- volumes, grid instances and SDFs (the host side of vpt_scene_update_volumes): the setters change the scene and note the change
+    #    in the pending VolumeEdit; desc, lights() and stats() follow at update_volumes(), which hands that edit out -------------------
+    def count_implicit(self, kind: str) -> int:
+        """number of "volumes", "vol_instances" or "sdfs"""
+        return host.vpth_scene_count_implicit(self.handle, {"volumes": 0, "vol_instances": 1, "sdfs": 2}[kind])
+
+    def volume_instance(self, index: int) -> VptVolumeInstance:
+        out = VptVolumeInstance()
+        if host.vpth_scene_get_vol_instance(self.handle, index, C.byref(out)) != 0:
+            raise VptError(f"volume instance {index} out of range")
+        return out
+
+    def set_volume_instance(self, index: int, frame=None, volume=None, material=None, scalef=None) -> None:
+        """frame ((12,) float32: x, y, z, o), volume, material and / or scalef of a grid instance; None: as it was"""
+        vi = self.volume_instance(index)
+        if frame is not None:
+            C.memmove(C.byref(vi.frame), np.ascontiguousarray(frame, np.float32).reshape(12).ctypes.data, 48)
+        if volume is not None:
+            vi.volume = int(volume)
+        if material is not None:
+            vi.material = int(material)
+        if scalef is not None:
+            vi.scalef = float(scalef)
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_set_vol_instance(self.handle, index, C.byref(vi), err, len(err)) != 0:
+            raise VptError(err.value.decode())
+        self._pending_volumes().vol_instances[index] = self.volume_instance(index)
+
+    def sdf(self, index: int) -> VptSdf:
+        out = VptSdf()
+        if host.vpth_scene_get_sdf(self.handle, index, C.byref(out)) != 0:
+            raise VptError(f"sdf {index} out of range")
+        return out
+
+    def set_sdf(self, index: int, sdf: Optional[VptSdf] = None, frame=None, type=None, material=None, whd=None, p=None) -> None:
+        """an analytic SDF: a whole VptSdf, or the named fields of the one the scene holds (type: an index into SDF_TYPES or its name)"""
+        f = self.sdf(index) if sdf is None else sdf
+        if frame is not None:
+            C.memmove(C.byref(f.frame), np.ascontiguousarray(frame, np.float32).reshape(12).ctypes.data, 48)
+        if type is not None:
+            f.type = SDF_TYPES.index(type) if isinstance(type, str) else int(type)
+        if material is not None:
+            f.material = int(material)
+        if whd is not None:
+            f.whd[:] = [float(v) for v in whd]
+        if p is not None:
+            f.p[:] = ([float(v) for v in p] + [0.0] * 4)[:4]
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_set_sdf(self.handle, index, C.byref(f), err, len(err)) != 0:
+            raise VptError(err.value.decode())
+        self._pending_volumes().sdfs[index] = self.sdf(index)
+
+    def _write_volume(self, index: int, src: VolumeSource, voxels: np.ndarray) -> None:
+        whd, lo, size = (np.array([int(v) for v in a], np.int32) for a in (src.whd, src.region_lo, src.region_whd))
+        voxels = np.ascontiguousarray(voxels, np.float32)
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_set_volume(self.handle, index, whd.ctypes.data, C.c_float(src.res), lo.ctypes.data, size.ctypes.data, int(src.mode),
+                                      voxels.ctypes.data, err, len(err)) != 0:
+            raise VptError(err.value.decode())
+
+    def _note_volume(self, index: int, src: VolumeSource) -> None:
+        if index in self._pending_volumes().volumes:
+            raise VptError(f"volume {index} is already in the pending edit: hand it out with update_volumes() first")
+        self._pending_volumes().volumes[index] = src
+
+    def set_volume(self, index: int, voxels, res: Optional[float] = None, region=None, mode: int = VOXELS_REPLACE) -> None:
+        """voxels of a volume, float32 of shape (d, h, w).  region None: all of them - any size (a new size moves the volume to fresh
+        room on the device); region = (lo, whd), each (x, y, z): that box of the grid as it is, voxels of the box's shape.  mode
+        VOXELS_UNION: (resident < incoming) ? resident : incoming, the reference's op_union.  res None: as it was."""
+        self._run_bakes()
+        voxels = np.ascontiguousarray(voxels, np.float32)
+        if voxels.ndim != 3:
+            raise VptError(f"expected (d, h, w) voxels, got {voxels.shape}")
+        old, old_res = self.volume(index)
+        whd = voxels.shape[::-1] if region is None else old.shape[::-1]
+        lo, size = ((0, 0, 0), whd) if region is None else region
+        src = VolumeSource(tuple(whd), old_res if res is None else float(res), tuple(lo), tuple(size), mode, voxels.copy())
+        if voxels.shape != tuple(int(v) for v in src.region_whd)[::-1]:
+            raise VptError(f"voxels of region {tuple(size)} have shape {tuple(size)[::-1]}, got {voxels.shape}")
+        self._note_volume(index, src)
+        try:
+            self._write_volume(index, src, voxels)
+        except VptError:
+            del self._pending_volumes().volumes[index]   # refused: nothing was written, nothing is pending
+            raise
+
+    def bake_volume(self, index: int, positions, faces, whd=None, res: Optional[float] = None, origin=None, step=None, region=None,
+                    mode: int = VOXELS_REPLACE) -> None:
+        """a mesh ((n, 3) positions, triangles or quads) baked into volume `index` by the rule of vpt_bake_sdf - on the device, into
+        the resident pool, at DeviceScene.update_volumes; the host copy runs bake_sdf_grid(device=None) only when it is read.  whd None:
+        the volume's; origin / step None: the grid the renderer's lookup reads back in place with the volume at the origin of its
+        instance (origin 0, step = res * W / (W - 1) per axis); region and mode as in set_volume."""
+        self._run_bakes()
+        old, old_res = self.volume(index)
+        whd = tuple(int(v) for v in (old.shape[::-1] if whd is None else _whd3(whd)))
+        res = old_res if res is None else float(res)
+        if origin is None:
+            origin = np.zeros(3, np.float32)
+        if step is None:
+            step = np.array([np.float32(res) * np.float32(w) / np.float32(max(1, w - 1)) for w in whd], np.float32)
+        lo, size = ((0, 0, 0), whd) if region is None else region
+        positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3).copy()
+        src = VolumeSource(whd, res, tuple(lo), tuple(size), mode, None, (positions, bake_triangles(faces), np.asarray(origin, np.float32).copy(),
+                                                                      np.asarray(step, np.float32).copy()))
+        self._note_volume(index, src)
+        self._lazy_bakes = getattr(self, "_lazy_bakes", []) + [(index, src)]
+
+    def _run_bakes(self) -> None:
+        """the host copy of the volumes bake_volume named: the host mirror of the bake, run when the copy is read"""
+        todo, self._lazy_bakes = getattr(self, "_lazy_bakes", []), []
+        for index, src in todo:
+            positions, triangles, origin, step = src.bake
+            grid, _ = bake_sdf_grid(positions, triangles, src.whd, origin, step, device=None)
+            lo, size = src.region_lo, src.region_whd
+            box = grid[lo[2]:lo[2] + size[2], lo[1]:lo[1] + size[1], lo[0]:lo[0] + size[0]]
+            self._write_volume(index, src, box)
+        if todo:
+            err = C.create_string_buffer(512)
+            if host.vpth_scene_update_volumes(self.handle, err, len(err)) != 0:
+                raise VptError(err.value.decode())
+
+    def _pending_volumes(self) -> VolumeEdit:
+        if getattr(self, "_volume_edit", None) is None:
+            self._volume_edit = VolumeEdit()
+        return self._volume_edit
+
+    def update_volumes(self) -> VolumeEdit:
+        """make_lights of the scene as set_volume_instance / set_sdf / set_volume / bake_volume left it: desc, lights() and stats() carry
+        the edited volumes, instances, SDFs, light list and CDFs.  Returns the VolumeEdit for DeviceScene.update_volumes."""
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_update_volumes(self.handle, err, len(err)) != 0:
+            raise VptError(err.value.decode())
+        edit, self._volume_edit = self._pending_volumes(), None
+        return edit
+
     def lights(self):
         """(light list as a LIGHT array, CDF pool as float32) of the descriptor (copies)"""
         d = VptSceneDescLights.from_address(self.desc)
@@ -920,6 +1174,32 @@ class DeviceScene:
         abi, keep = edit.to_abi()
         _check(hip.vpt_scene_update_textures(self.handle, C.byref(abi)), "vpt_scene_update_textures")
         del keep
+
+    def update_volumes(self, edit: VolumeEdit) -> None:
+        """vpt_scene_update_volumes (include/vpt.h): grid instances, SDFs and volumes' voxels, from the host or baked on the device into
+        the resident pool.  Afterwards the handle renders the bits of a DeviceScene made from the host scene after the same edit and
+        update_volumes()."""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_scene_update_volumes(self.handle, C.byref(abi)), "vpt_scene_update_volumes")
+        del keep
+
+    def get_volumes(self):
+        """(volumes, vol_instances, sdfs) as the device holds them, ctypes arrays of VptVolume, VptVolumeInstance, VptSdf
+        (vpt_scene_get_volumes); a volume's offset is the resident pool's"""
+        nv, ni, ns = (self.host_scene.count_implicit(k) for k in ("volumes", "vol_instances", "sdfs"))
+        vols, insts, sdfs = (VptVolume * max(1, nv))(), (VptVolumeInstance * max(1, ni))(), (VptSdf * max(1, ns))()
+        _check(hip.vpt_scene_get_volumes(self.handle, C.cast(vols, _p), nv, C.cast(insts, _p), ni, C.cast(sdfs, _p), ns), "vpt_scene_get_volumes")
+        return list(vols)[:nv], list(insts)[:ni], list(sdfs)[:ns]
+
+    def get_voxels(self, index: int) -> np.ndarray:
+        """the voxels of a volume as the device holds them, float32 of shape (d, h, w) (vpt_scene_get_voxels)"""
+        vols, _, _ = self.get_volumes()
+        if not 0 <= index < len(vols):
+            raise VptError(f"volume {index} out of range")
+        w, h, d = vols[index].whd
+        out = np.zeros((d, h, w), np.float32)
+        _check(hip.vpt_scene_get_voxels(self.handle, index, out.ctypes.data, out.size), "vpt_scene_get_voxels")
+        return out
 
     def get_lights(self):
         """(light list as a LIGHT array, CDF pool as float32) as the device holds them (vpt_scene_get_lights)"""
@@ -1048,6 +1328,12 @@ class MultiDeviceScene:
         """vpt_multi_update_textures: DeviceScene.update_textures with the same edit on every device"""
         abi, keep = edit.to_abi()
         _check(hip.vpt_multi_update_textures(self.handle, C.byref(abi)), "vpt_multi_update_textures")
+        del keep
+
+    def update_volumes(self, edit: VolumeEdit) -> None:
+        """vpt_multi_update_volumes: DeviceScene.update_volumes with the same edit on every device"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_multi_update_volumes(self.handle, C.byref(abi)), "vpt_multi_update_volumes")
         del keep
 
     def pathtrace_samples(self, state: PathtraceState, params: PathtraceParams, count: int = 1) -> None:
@@ -1343,6 +1629,12 @@ class RenderSession:
         """edit() through vpt_scene_update_textures, with the TextureEdit of HostScene.update_textures()"""
         abi, keep = edit.to_abi()
         _check(hip.vpt_session_edit_textures(self.handle, C.byref(abi)), "vpt_session_edit_textures")
+        del keep
+
+    def edit_volumes(self, edit: VolumeEdit) -> None:
+        """edit() through vpt_scene_update_volumes, with the VolumeEdit of HostScene.update_volumes()"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_session_edit_volumes(self.handle, C.byref(abi)), "vpt_session_edit_volumes")
         del keep
 
     @property

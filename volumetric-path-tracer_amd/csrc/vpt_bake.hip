@@ -15,6 +15,7 @@
 #include <cstring>
 #include <vector>
 
+#include "vpt_bake.h"
 #include "vpt_bake_prep.h"
 #include "vpt_bake_rule.h"
 #include "vpt_device_buffer.h"
@@ -39,16 +40,22 @@ __device__ __forceinline__ float box_distance2(vpt_bake_f3 p, float4 q0, float4 
 
 // nodes == nullptr: the brute form, every record in turn.  records: in BVH slot order (leaf primitives start .. start + num - 1),
 // or in the caller's order in the brute form.
-__global__ __launch_bounds__(64) void bake_kernel(bake_grid g, const float4* __restrict__ nodes, int num_nodes,
+// REGION (vpt_scene_update_volumes: the destination is a volume's place in a resident voxel pool): the grid holds the bricks that
+// touch the box r.lo .. r.hi, a lane outside the box does nothing, and in UNION mode the voxel is selected against the resident
+// value.  A voxel's arithmetic does not know its brick: the same bits as the whole-grid instance.
+template <bool REGION>
+__global__ __launch_bounds__(64) void bake_kernel(bake_grid g, bake_region r, const float4* __restrict__ nodes, int num_nodes,
     const vpt_bake_record* __restrict__ records, int num_records, float reach, float* __restrict__ voxels) {
   __shared__ int stack[BAKE_STACK * 64];
   const int lane = threadIdx.x;
-  const int bricks_x = (g.w + 3) >> 2, bricks_y = (g.h + 3) >> 2;
+  const int first_x = REGION ? r.lo[0] >> 2 : 0, first_y = REGION ? r.lo[1] >> 2 : 0, first_z = REGION ? r.lo[2] >> 2 : 0;
+  const int bricks_x = (((REGION ? r.hi[0] : g.w) + 3) >> 2) - first_x, bricks_y = (((REGION ? r.hi[1] : g.h) + 3) >> 2) - first_y;
   const int brick = blockIdx.x;
-  const int x = ((brick % bricks_x) << 2) + (lane & 3);
-  const int y = (((brick / bricks_x) % bricks_y) << 2) + ((lane >> 2) & 3);
-  const int z = ((brick / (bricks_x * bricks_y)) << 2) + (lane >> 4);
-  if (x < g.w && y < g.h && z < g.d) {   // lanes outside the grid stay in the wave and do nothing
+  const int x = ((first_x + brick % bricks_x) << 2) + (lane & 3);
+  const int y = ((first_y + (brick / bricks_x) % bricks_y) << 2) + ((lane >> 2) & 3);
+  const int z = ((first_z + brick / (bricks_x * bricks_y)) << 2) + (lane >> 4);
+  const bool inside = REGION ? x >= r.lo[0] && x < r.hi[0] && y >= r.lo[1] && y < r.hi[1] && z >= r.lo[2] && z < r.hi[2] : x < g.w && y < g.h && z < g.d;
+  if (inside) {   // lanes outside the grid (the region) stay in the wave and do nothing
     const vpt_bake_f3 p = {vpt_bake_sample(g.origin[0], g.step[0], x), vpt_bake_sample(g.origin[1], g.step[1], y),
         vpt_bake_sample(g.origin[2], g.step[2], z)};
     vpt_bake_best best = vpt_bake_none();
@@ -78,7 +85,13 @@ __global__ __launch_bounds__(64) void bake_kernel(bake_grid g, const float4* __r
         node = stack[64 * --sp + lane];
       }
     }
-    voxels[(size_t)x + (size_t)y * g.w + (size_t)z * g.w * g.h] = best.slot < 0 ? vpt_bake_no_winner() : vpt_bake_value(p, records[best.slot]);
+    const size_t at = (size_t)x + (size_t)y * g.w + (size_t)z * g.w * g.h;
+    float v = best.slot < 0 ? vpt_bake_no_winner() : vpt_bake_value(p, records[best.slot]);
+    if (REGION && r.mode == VPT_VOXELS_UNION) {   // op_union, yocto_sdfs.h:82: the select, not fminf
+      const float a = voxels[at];
+      v = (a < v) ? a : v;
+    }
+    voxels[at] = v;
   }
 }
 
@@ -99,11 +112,9 @@ int tree_depth(const std::vector<vpt_bvh_node>& nodes, int count) {
 
 }  // namespace
 
-extern "C" int vpt_bake_sdf(int device, const vpt_bake_desc* desc, float* voxels, vpt_bake_stats* stats) {
-  const char* entry = "vpt_bake_sdf";
-  if (stats) *stats = vpt_bake_stats{};
-  if (int rc = vpt_bake_validate(desc, entry)) return rc;
-  REQUIRE(voxels, "%s: null voxels", entry);
+int bake_prepare(int device, const vpt_bake_desc* desc, const char* entry, bake_job& job) {
+  job.stats = vpt_bake_stats{}, job.bytes = 0;
+  vpt_bake_stats* stats = &job.stats;
   const int nt = desc->num_triangles;
   std::vector<float>   normals(21 * (size_t)nt);
   std::vector<int32_t> keep(nt);
@@ -111,7 +122,6 @@ extern "C" int vpt_bake_sdf(int device, const vpt_bake_desc* desc, float* voxels
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return vpt_set_error(VPT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
   REQUIRE(device >= 0 && device < ndev, "%s: device %d out of range (%d devices)", entry, device, ndev);
-
   std::vector<int32_t> kept;   // the caller's indices of the kept triangles, ascending
   for (int t = 0; t < nt; t++)
     if (keep[t]) kept.push_back(t);
@@ -153,11 +163,11 @@ extern "C" int vpt_bake_sdf(int device, const vpt_bake_desc* desc, float* voxels
     for (int i = 0; i < num_nodes; i++)
       if (!nodes[i].internal && (nodes[i].start < 0 || nodes[i].num < 0 || nodes[i].start + nodes[i].num > nk))
         return vpt_set_error(VPT_ERR_HIP, "%s: the BVH build returned a leaf outside the primitive array", entry);
-    if (stats) stats->dropped_triangles = nt - nk, stats->bvh_nodes = num_nodes, stats->bvh_depth = depth;
+    stats->dropped_triangles = nt - nk, stats->bvh_nodes = num_nodes, stats->bvh_depth = depth;
     if (depth > BAKE_STACK)
       return vpt_set_error(VPT_ERR_UNSUPPORTED, "%s: BVH depth %d needs a %d-entry traversal stack; the LDS stack holds %d", entry, depth, depth, BAKE_STACK);
   }
-  if (stats) stats->dropped_triangles = nt - nk;
+  stats->dropped_triangles = nt - nk;
   std::vector<vpt_bake_record> records(nk);
   for (int slot = 0; slot < nk; slot++) {
     REQUIRE(order[slot] >= 0 && order[slot] < nk, "%s: the BVH build returned primitive %d of %d", entry, order[slot], nk);
@@ -165,17 +175,45 @@ extern "C" int vpt_bake_sdf(int device, const vpt_bake_desc* desc, float* voxels
   }
 
   HIP_TRY(hipSetDevice(device));
-  const size_t  nvox = (size_t)desc->whd[0] * desc->whd[1] * desc->whd[2];
-  device_buffer d_nodes, d_records, d_voxels;
-  if (d_nodes.allocate((size_t)num_nodes * sizeof(vpt_bvh_node)) || d_records.allocate((size_t)nk * sizeof(vpt_bake_record)) ||
-      d_voxels.allocate(nvox * sizeof(float)))
-    return VPT_ERR_HIP;
-  if (num_nodes) HIP_TRY(hipMemcpy(d_nodes.get(), nodes.data(), (size_t)num_nodes * sizeof(vpt_bvh_node), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_records.get(), records.data(), (size_t)nk * sizeof(vpt_bake_record), hipMemcpyHostToDevice));
+  if (job.nodes.allocate((size_t)num_nodes * sizeof(vpt_bvh_node)) || job.records.allocate((size_t)nk * sizeof(vpt_bake_record))) return VPT_ERR_HIP;
+  if (num_nodes) HIP_TRY(hipMemcpy(job.nodes.get(), nodes.data(), (size_t)num_nodes * sizeof(vpt_bvh_node), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(job.records.get(), records.data(), (size_t)nk * sizeof(vpt_bake_record), hipMemcpyHostToDevice));
+  job.num_nodes = num_nodes, job.num_records = nk, job.reach = reach, job.brute = brute;
+  job.bytes = (long long)((size_t)num_nodes * sizeof(vpt_bvh_node) + (size_t)nk * sizeof(vpt_bake_record));
+  return VPT_OK;
+}
+
+int bake_launch(const bake_job& job, const vpt_bake_desc* desc, float* d_voxels, const bake_region* region, int* launched) {
   bake_grid g;
   g.w = desc->whd[0], g.h = desc->whd[1], g.d = desc->whd[2];
   for (int k = 0; k < 3; k++) g.origin[k] = desc->origin[k], g.step[k] = desc->step[k];
-  const long long bricks = (long long)((g.w + 3) / 4) * ((g.h + 3) / 4) * ((g.d + 3) / 4);   // every brick holds a voxel: fewer than 2^31
+  bake_region r = {{0, 0, 0}, {g.w, g.h, g.d}, VPT_VOXELS_REPLACE};
+  if (region) r = *region;
+  long long bricks = 1;   // every brick holds a voxel of the grid: fewer than 2^31
+  for (int k = 0; k < 3; k++) {
+    if (r.hi[k] <= r.lo[k]) return VPT_OK;   // an empty region
+    bricks *= ((r.hi[k] + 3) >> 2) - (r.lo[k] >> 2);
+  }
+  const float4* nodes = job.brute ? nullptr : job.nodes.get<float4>();
+  if (region) hipLaunchKernelGGL(bake_kernel<true>, dim3((unsigned)bricks), dim3(64), 0, 0, g, r, nodes, job.num_nodes, job.records.get<vpt_bake_record>(), job.num_records, job.reach, d_voxels);
+  else hipLaunchKernelGGL(bake_kernel<false>, dim3((unsigned)bricks), dim3(64), 0, 0, g, r, nodes, job.num_nodes, job.records.get<vpt_bake_record>(), job.num_records, job.reach, d_voxels);
+  HIP_TRY(hipGetLastError());
+  if (launched) ++*launched;
+  return VPT_OK;
+}
+
+extern "C" int vpt_bake_sdf(int device, const vpt_bake_desc* desc, float* voxels, vpt_bake_stats* stats) {
+  const char* entry = "vpt_bake_sdf";
+  if (stats) *stats = vpt_bake_stats{};
+  if (int rc = vpt_bake_validate(desc, entry)) return rc;
+  REQUIRE(voxels, "%s: null voxels", entry);
+  bake_job job;
+  const int rc = bake_prepare(device, desc, entry, job);
+  if (stats) *stats = job.stats;   // of a tree that is too deep as well
+  if (rc) return rc;
+  const size_t  nvox = (size_t)desc->whd[0] * desc->whd[1] * desc->whd[2];
+  device_buffer d_voxels;
+  if (d_voxels.allocate(nvox * sizeof(float))) return VPT_ERR_HIP;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIP_TRY(hipEventCreate(&e0));
   if (hipError_t e = hipEventCreate(&e1); e != hipSuccess) {
@@ -184,15 +222,13 @@ extern "C" int vpt_bake_sdf(int device, const vpt_bake_desc* desc, float* voxels
   }
   float      ms = 0;
   hipError_t err = hipEventRecord(e0, 0);
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(bake_kernel, dim3((unsigned)bricks), dim3(64), 0, 0, g, brute ? nullptr : d_nodes.get<float4>(), num_nodes,
-        d_records.get<vpt_bake_record>(), nk, reach, d_voxels.get<float>());
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess) err = hipEventRecord(e1, 0);
-  if (err == hipSuccess) err = hipEventSynchronize(e1);
-  if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+  int        launch_rc = VPT_OK;   // bake_launch has recorded HIP's own message
+  if (err == hipSuccess) launch_rc = bake_launch(job, desc, d_voxels.get<float>(), nullptr, nullptr);
+  if (err == hipSuccess && launch_rc == VPT_OK) err = hipEventRecord(e1, 0);
+  if (err == hipSuccess && launch_rc == VPT_OK) err = hipEventSynchronize(e1);
+  if (err == hipSuccess && launch_rc == VPT_OK) err = hipEventElapsedTime(&ms, e0, e1);
   (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
+  if (launch_rc != VPT_OK) return launch_rc;
   if (err != hipSuccess) return vpt_set_error(VPT_ERR_HIP, "%s: bake kernel: %s", entry, hipGetErrorString(err));
   if (stats) stats->launches = 1, stats->device_ms = ms;
   HIP_TRY(hipMemcpy(voxels, d_voxels.get(), nvox * sizeof(float), hipMemcpyDeviceToHost));

@@ -23,6 +23,7 @@
 #include "vpt_scene_prep.h"
 #include "vpt_scene_update.h"
 #include "vpt_texture_update.h"
+#include "vpt_volume_update.h"
 
 static std::string& g_error_text() {   // the message of the last failure on the calling thread (vpt_last_error)
   thread_local std::string text;
@@ -68,6 +69,7 @@ struct vpt_scene {
   scene_updater upd;                   // vpt_scene_update: levels and quad-slot tables, built on the first update
   light_updater lights_upd;            // vpt_scene_update_lights: sizes of the pooled light tables, mirrors built on the first rebuild
   texture_updater textures_upd;        // vpt_scene_update_textures: sizes of the texel pools, mirrors built on the first edit
+  volume_updater volumes_upd;          // vpt_scene_update_volumes: size of the voxel pool, mirrors built on the first edit
 };
 
 namespace {
@@ -190,6 +192,7 @@ int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* 
   s->curves = t.curves, s->varying_media = t.varying_media, s->num_shape_nodes = d.num_shape_bvh_nodes;
   s->lights_upd.num_cdf = d.num_light_cdf, s->lights_upd.num_pool = (long long)t.light_index_pool.size(), s->lights_upd.num_guide = (long long)t.light_guide.size();
   s->textures_upd.num_texels_f = d.num_texels_f, s->textures_upd.num_texels_b = d.num_texels_b;
+  s->volumes_upd.num_voxels = d.num_voxels;
   s->h = std::move(t.h);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -443,6 +446,49 @@ int vpt_scene_update_textures(vpt_scene* s, const vpt_texture_edit* edit) {
     if (int rc = medium_setup(s)) return rc;
   }
   s->sched.forget();
+  return VPT_OK;
+}
+
+// volumes, grid instances and SDFs (the work is vpt_volume_update.hip's); the light tables follow when the SDF lights do
+int vpt_scene_update_volumes(vpt_scene* s, const vpt_volume_edit* edit) {
+  if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call rewrites
+  bool rebuilt = false;
+  if (int rc = volume_update_apply(s->d, s->h, s->num_shape_nodes, s->upd, s->lights_upd, s->volumes_upd, s->tables, *edit, s->device, &s->light_features, &rebuilt)) return rc;
+  if (rebuilt) {   // light_prims and the medium records sit in tables made anew
+    if (int rc = light_setup(s)) return rc;
+    if (int rc = medium_setup(s)) return rc;
+  }
+  s->sched.forget();
+  return VPT_OK;
+}
+
+// the three small tables and a volume's voxels as the device holds them now
+int vpt_scene_get_volumes(vpt_scene* s, vpt_volume* volumes, int volume_capacity, vpt_volume_instance* vol_instances, int instance_capacity, vpt_sdf* sdfs,
+    int sdf_capacity) {
+  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  REQUIRE(!volumes || volume_capacity >= s->d.num_volumes, "volume_capacity %d < %d volumes", volume_capacity, s->d.num_volumes);
+  REQUIRE(!vol_instances || instance_capacity >= s->d.num_vol_instances, "instance_capacity %d < %d volume instances", instance_capacity, s->d.num_vol_instances);
+  REQUIRE(!sdfs || sdf_capacity >= s->d.num_sdfs, "sdf_capacity %d < %d sdfs", sdf_capacity, s->d.num_sdfs);
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (volumes && s->d.num_volumes) HIP_TRY(hipMemcpy(volumes, s->d.volumes, (size_t)s->d.num_volumes * sizeof(vpt_volume), hipMemcpyDeviceToHost));
+  if (vol_instances && s->d.num_vol_instances)
+    HIP_TRY(hipMemcpy(vol_instances, s->d.vol_instances, (size_t)s->d.num_vol_instances * sizeof(vpt_volume_instance), hipMemcpyDeviceToHost));
+  if (sdfs && s->d.num_sdfs) HIP_TRY(hipMemcpy(sdfs, s->d.sdfs, (size_t)s->d.num_sdfs * sizeof(vpt_sdf), hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+int vpt_scene_get_voxels(vpt_scene* s, int volume, float* voxels, int64_t capacity) {
+  if (!s || !voxels) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  REQUIRE(volume >= 0 && volume < s->d.num_volumes, "volume %d out of range (%d)", volume, s->d.num_volumes);
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  vpt_volume v;
+  HIP_TRY(hipMemcpy(&v, s->d.volumes + volume, sizeof(v), hipMemcpyDeviceToHost));
+  const long long n = (long long)v.whd[0] * v.whd[1] * v.whd[2];
+  REQUIRE(capacity >= n, "capacity %lld < %lld voxels", (long long)capacity, n);
+  if (n) HIP_TRY(hipMemcpy(voxels, s->d.voxels + v.offset, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
   return VPT_OK;
 }
 

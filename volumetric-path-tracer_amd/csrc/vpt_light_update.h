@@ -38,5 +38,8 @@ struct env_light {
 // envs: null for vpt_scene_update_lights - the environments that were lights stay, entries, CDFs and records byte for byte; else the
 // environment lights of the edited scene in id order: a recomputed one is a job like a mesh light's, of texel weights instead of areas
 // (launch_texel_weights, vpt_texture_update.h), and every one's record is sent.
+// sdf_resized: null, or per SDF whether an edit of lu.sdfs (vpt_scene_update_volumes, vpt_volume_update.h) changed its whd: an SDF light
+// among them has another CDF entry, so the tables are rebuilt although the list stays.
 int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light_updater& lu, std::vector<device_buffer>& tables,
-    const vpt_scene_edit& edit, int* light_features, bool* rebuilt, const std::vector<env_light>* envs = nullptr);
+    const vpt_scene_edit& edit, int* light_features, bool* rebuilt, const std::vector<env_light>* envs = nullptr,
+    const std::vector<char>* sdf_resized = nullptr);

@@ -224,7 +224,7 @@ struct entry {   // one light of the new list
 }  // namespace
 
 int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light_updater& lu, std::vector<device_buffer>& tables,
-    const vpt_scene_edit& e, int* light_features, bool* rebuilt, const std::vector<env_light>* envs) {
+    const vpt_scene_edit& e, int* light_features, bool* rebuilt, const std::vector<env_light>* envs, const std::vector<char>* sdf_resized) {
   *rebuilt = false;
   if (!lu.ready) {
     lu.index.resize((size_t)d.num_lights), lu.sdfs.resize((size_t)d.num_sdfs);
@@ -268,6 +268,7 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
     if (emissive(u.materials[(size_t)lu.sdfs[(size_t)i].material])) list.push_back({{VPT_INVALID, VPT_INVALID, i, 1, 0}, old_of_sdf[(size_t)i], false, VPT_LIGHT_SDF});
   bool same = list.size() == old.size();
   for (size_t l = 0; same && l < list.size(); l++) same = list[l].from == (int)l && !list[l].recompute && list[l].l.cdf_len == old[l].cdf_len;
+  for (size_t l = 0; same && sdf_resized && l < list.size(); l++) same = list[l].l.sdf < 0 || !(*sdf_resized)[(size_t)list[l].l.sdf];   // its one CDF entry is whd.x * whd.y
   env_of.resize(list.size(), -1);
   if (same) return VPT_OK;   // no consequence for the lights: the update has done all there is to do
   *rebuilt = true;

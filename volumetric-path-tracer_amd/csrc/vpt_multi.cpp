@@ -338,6 +338,13 @@ int vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit) {
   return VPT_OK;
 }
 
+int vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit) {
+  if (!m || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  for (auto& p : m->parts)   // as vpt_multi_update: validation is the same on every device
+    if (int rc = vpt_scene_update_volumes(p.scene, edit)) return rc;
+  return VPT_OK;
+}
+
 int vpt_multi_device_count(const vpt_multi* m) { return m ? (int)m->parts.size() : 0; }
 
 const char* vpt_multi_transport(const vpt_multi* m) { return !m ? "" : m->use_rccl ? "rccl" : m->parts.size() > 1 ? "peer-copy" : "local"; }

@@ -409,7 +409,7 @@ int build_quad_nodes_and_stacks(const vpt_scene_desc& d, scene_tables& t) {
   return VPT_OK;
 }
 
-// instance records, the enter records of the scene-BVH slots, and the inverse frames of environments and SDFs
+// instance records, the enter records of the scene-BVH slots, and the inverse frames of environments
 void build_instances(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_tables& t) {
   t.instances.resize((size_t)d.num_instances);
   for (int i = 0; i < d.num_instances; i++) {
@@ -441,12 +441,11 @@ void build_instances(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_
     memcpy(&e[5], &tail[2], 16);
     t.h.slot_of[(size_t)id] = k;
   }
-  t.env_inv.resize((size_t)d.num_environments * 3), t.sdf_inv.resize((size_t)d.num_sdfs * 3);
+  t.env_inv.resize((size_t)d.num_environments * 3);
   for (int i = 0; i < d.num_environments; i++) {
     float4 fwd[3];
     prep_environment_frames(d.environments[i].frame, &t.env_inv[3 * (size_t)i], fwd);
   }
-  for (int i = 0; i < d.num_sdfs; i++) pack_frame(hinverse(to_h(d.sdfs[i].frame), false), &t.sdf_inv[3 * (size_t)i]);
 }
 
 // the features the lights need, the 16-ary search index and guide table over each light's CDF (vpt_device.h: DCdfIndex), light records
@@ -532,105 +531,6 @@ void build_lights(const vpt_scene_desc& d, scene_tables& t) {
   }
 }
 
-// SDF evaluation records (vpt_scene.hip.h "SDF records") and the balls the escaping-ray early-out needs.  The
-// constants are folded with the reference's own float operations (yocto_sdfs.cpp:33-38, yocto_sceneio.cpp:3697);
-// the balls are test-independent geometry, computed in double with a 5 % margin.  Only rigid frames get a ball
-// (a scaling frame turns SDF values into something other than world distances): radius -1 switches the early-out off.
-void build_sdf_records(const vpt_scene_desc& d, scene_tables& t) {
-  auto rigid = [](const vpt_frame& f) {
-    double c[3][3] = {{f.x[0], f.x[1], f.x[2]}, {f.y[0], f.y[1], f.y[2]}, {f.z[0], f.z[1], f.z[2]}};
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) {
-        double dp = c[i][0] * c[j][0] + c[i][1] * c[j][1] + c[i][2] * c[j][2];
-        if (std::fabs(dp - (i == j ? 1.0 : 0.0)) > 1e-5) return false;
-      }
-    return true;
-  };
-  auto identity3 = [](const vpt_frame& f) {
-    return f.x[0] == 1 && f.x[1] == 0 && f.x[2] == 0 && f.y[0] == 0 && f.y[1] == 1 && f.y[2] == 0 && f.z[0] == 0 && f.z[1] == 0 && f.z[2] == 1;
-  };
-  // world position of a local point: the SDFs apply the FORWARD frame to world points (yocto_sdfs.cpp:13), so world = R^T (local - o)
-  auto to_world = [](const vpt_frame& f, const double l[3], double w[3]) {
-    double v[3] = {l[0] - f.o[0], l[1] - f.o[1], l[2] - f.o[2]};
-    w[0] = f.x[0] * v[0] + f.y[0] * v[1] + f.z[0] * v[2];   // rows of R^T = the frame's x, y, z taken component-wise
-    w[1] = f.x[1] * v[0] + f.y[1] * v[1] + f.z[1] * v[2];
-    w[2] = f.x[2] * v[0] + f.y[2] * v[1] + f.z[2] * v[2];
-  };
-  struct ball { double c[3], r; };
-  std::vector<ball> balls;
-  bool all_bounded_rigid = true;
-  int  planes = 0;
-  t.sdf_fn_rec.assign(6 * (size_t)d.num_sdfs, make_float4(0, 0, 0, 0)), t.sdf_grid_rec.assign(7 * (size_t)d.num_vol_instances, make_float4(0, 0, 0, 0));
-  for (int i = 0; i < d.num_sdfs; i++) {
-    const vpt_sdf& f = d.sdfs[i];
-    float4* r = &t.sdf_fn_rec[6 * (size_t)i];
-    pack_frame(to_h(f.frame), r);
-    r[3] = make_float4(f.p[0], f.p[1], f.p[2], f.p[3]);
-    r[4] = make_float4(f.whd[0] * 0.5f, f.whd[1] * 0.5f, f.whd[2] * 0.5f, 0);
-    int tag = f.type | ((identity3(f.frame) ? 1 : 0) << 8);
-    memcpy(&r[4].w, &tag, 4);
-    double lc[3] = {0, 0, 0}, lr = -1;   // local centre / radius of a ball around the shape
-    switch (f.type) {
-      case VPT_SDF_BOX: lc[0] = f.whd[0] * 0.5, lc[1] = f.whd[1] * 0.5, lc[2] = f.whd[2] * 0.5, lr = std::sqrt(lc[0] * lc[0] + lc[1] * lc[1] + lc[2] * lc[2]); break;
-      case VPT_SDF_BBOX: lr = std::sqrt((double)f.p[1] * f.p[1] + (double)f.p[2] * f.p[2] + (double)f.p[3] * f.p[3]) + 2.0 * std::fabs((double)f.p[0]); break;
-      case VPT_SDF_SPHERE: lr = std::fabs((double)f.p[0]); break;
-      case VPT_SDF_TORUS: lr = std::fabs((double)f.p[0]) + std::fabs((double)f.p[1]); break;
-      case VPT_SDF_CAPPED_CONE: lr = std::sqrt((double)f.p[0] * f.p[0] + std::max((double)f.p[1] * f.p[1], (double)f.p[2] * f.p[2])); break;
-      default: break;   // plane: unbounded
-    }
-    r[5] = make_float4(0, 0, 0, -1);
-    if (f.type == VPT_SDF_PLANE) planes++;
-    else if (lr > 0 && std::isfinite(lr) && rigid(f.frame)) {
-      ball b;
-      to_world(f.frame, lc, b.c);
-      b.r = lr * 1.05 + 1e-6;
-      balls.push_back(b);
-      r[5] = make_float4((float)b.c[0], (float)b.c[1], (float)b.c[2], (float)b.r);
-    } else all_bounded_rigid = false;
-  }
-  for (int i = 0; i < d.num_vol_instances; i++) {
-    const vpt_volume_instance& vi = d.vol_instances[i];
-    const vpt_volume&          vol = d.volumes[vi.volume];
-    float4* r = &t.sdf_grid_rec[7 * (size_t)i];
-    pack_frame(to_h(vi.frame), r);
-    // bbox_max = origin + (vol.res * grid_res) * scalef; bbox_size = bbox_max - origin   (yocto_sdfs.cpp:33-36, float)
-    float size[3];
-    for (int k = 0; k < 3; k++) {
-      float origin = vi.frame.o[k], grid_res = (float)vol.whd[k];
-      float bbox_max = origin + (vol.res * grid_res) * vi.scalef;
-      size[k] = bbox_max - origin;
-    }
-    r[3] = make_float4(size[0], size[1], size[2], vi.scalef);
-    r[4] = make_float4(size[0] * 0.5f, size[1] * 0.5f, size[2] * 0.5f, 0);
-    int tr = identity3(vi.frame) ? 1 : 0;
-    memcpy(&r[4].w, &tr, 4);
-    int dims[3] = {vol.whd[0], vol.whd[1], vol.whd[2]};
-    memcpy(&r[5], dims, 12);
-    r[5].w = vol.res;
-    int off[2] = {(int)(vol.offset & 0xffffffffll), (int)(vol.offset >> 32)};
-    memcpy(&r[6], off, 8);
-    double lc[3] = {size[0] * 0.5, size[1] * 0.5, size[2] * 0.5}, lr = std::sqrt(lc[0] * lc[0] + lc[1] * lc[1] + lc[2] * lc[2]);
-    if (lr > 0 && std::isfinite(lr) && rigid(vi.frame)) {
-      ball b;
-      to_world(vi.frame, lc, b.c);
-      b.r = lr * 1.05 + 1e-6;
-      balls.push_back(b);
-    } else all_bounded_rigid = false;
-  }
-  DScene& D = t.d;
-  D.sdf_bound_cx = D.sdf_bound_cy = D.sdf_bound_cz = 0, D.sdf_bound_r = -1, D.sdf_num_planes = planes;
-  if (all_bounded_rigid && !balls.empty()) {
-    double c[3] = {0, 0, 0}, rr = 0;
-    for (const ball& b : balls)
-      for (int k = 0; k < 3; k++) c[k] += b.c[k] / (double)balls.size();
-    for (const ball& b : balls) {
-      double dist = std::sqrt((b.c[0] - c[0]) * (b.c[0] - c[0]) + (b.c[1] - c[1]) * (b.c[1] - c[1]) + (b.c[2] - c[2]) * (b.c[2] - c[2]));
-      rr = std::max(rr, dist + b.r);
-    }
-    D.sdf_bound_cx = (float)c[0], D.sdf_bound_cy = (float)c[1], D.sdf_bound_cz = (float)c[2], D.sdf_bound_r = (float)(rr * 1.01);
-  }
-}
-
 }  // namespace
 
 void prep_instance_frames(const vpt_frame& frame, float4 inv[3], float4 fwd[3], int* translation_only) {
@@ -659,6 +559,109 @@ bool prep_media_vary(const vpt_material* materials, int num_materials, const int
     if (m.color_tex != VPT_INVALID || m.emission_tex != VPT_INVALID || m.scattering_tex != VPT_INVALID || (inst_flags[i] & VPT_SHP_COLORS)) return true;
   }
   return false;
+}
+
+// SDF evaluation records (vpt_scene.hip.h "SDF records") and the balls the escaping-ray early-out needs.  The
+// constants are folded with the reference's own float operations (yocto_sdfs.cpp:33-38, yocto_sceneio.cpp:3697);
+// the balls are test-independent geometry, computed in double with a 5 % margin.  Only rigid frames get a ball
+// (a scaling frame turns SDF values into something other than world distances): radius -1 switches the early-out off.
+// The inverse frames of the SDFs (rigid) come with them.  vpt_scene_create and vpt_scene_update_volumes both call this, for all
+// records of a scene at once (the scene's ball depends on every one), so the two cannot drift apart.
+void prep_sdf_records(const vpt_sdf* sdfs, int num_sdfs, const vpt_volume* volumes, const vpt_volume_instance* vol_instances, int num_vol_instances,
+    std::vector<float4>& sdf_inv, std::vector<float4>& sdf_fn_rec, std::vector<float4>& sdf_grid_rec, DScene& D) {
+  auto rigid = [](const vpt_frame& f) {
+    double c[3][3] = {{f.x[0], f.x[1], f.x[2]}, {f.y[0], f.y[1], f.y[2]}, {f.z[0], f.z[1], f.z[2]}};
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) {
+        double dp = c[i][0] * c[j][0] + c[i][1] * c[j][1] + c[i][2] * c[j][2];
+        if (std::fabs(dp - (i == j ? 1.0 : 0.0)) > 1e-5) return false;
+      }
+    return true;
+  };
+  auto identity3 = [](const vpt_frame& f) {
+    return f.x[0] == 1 && f.x[1] == 0 && f.x[2] == 0 && f.y[0] == 0 && f.y[1] == 1 && f.y[2] == 0 && f.z[0] == 0 && f.z[1] == 0 && f.z[2] == 1;
+  };
+  // world position of a local point: the SDFs apply the FORWARD frame to world points (yocto_sdfs.cpp:13), so world = R^T (local - o)
+  auto to_world = [](const vpt_frame& f, const double l[3], double w[3]) {
+    double v[3] = {l[0] - f.o[0], l[1] - f.o[1], l[2] - f.o[2]};
+    w[0] = f.x[0] * v[0] + f.y[0] * v[1] + f.z[0] * v[2];   // rows of R^T = the frame's x, y, z taken component-wise
+    w[1] = f.x[1] * v[0] + f.y[1] * v[1] + f.z[1] * v[2];
+    w[2] = f.x[2] * v[0] + f.y[2] * v[1] + f.z[2] * v[2];
+  };
+  struct ball { double c[3], r; };
+  std::vector<ball> balls;
+  bool all_bounded_rigid = true;
+  int  planes = 0;
+  sdf_fn_rec.assign(6 * (size_t)num_sdfs, make_float4(0, 0, 0, 0)), sdf_grid_rec.assign(7 * (size_t)num_vol_instances, make_float4(0, 0, 0, 0));
+  sdf_inv.resize(3 * (size_t)num_sdfs);
+  for (int i = 0; i < num_sdfs; i++) pack_frame(hinverse(to_h(sdfs[i].frame), false), &sdf_inv[3 * (size_t)i]);
+  for (int i = 0; i < num_sdfs; i++) {
+    const vpt_sdf& f = sdfs[i];
+    float4* r = &sdf_fn_rec[6 * (size_t)i];
+    pack_frame(to_h(f.frame), r);
+    r[3] = make_float4(f.p[0], f.p[1], f.p[2], f.p[3]);
+    r[4] = make_float4(f.whd[0] * 0.5f, f.whd[1] * 0.5f, f.whd[2] * 0.5f, 0);
+    int tag = f.type | ((identity3(f.frame) ? 1 : 0) << 8);
+    memcpy(&r[4].w, &tag, 4);
+    double lc[3] = {0, 0, 0}, lr = -1;   // local centre / radius of a ball around the shape
+    switch (f.type) {
+      case VPT_SDF_BOX: lc[0] = f.whd[0] * 0.5, lc[1] = f.whd[1] * 0.5, lc[2] = f.whd[2] * 0.5, lr = std::sqrt(lc[0] * lc[0] + lc[1] * lc[1] + lc[2] * lc[2]); break;
+      case VPT_SDF_BBOX: lr = std::sqrt((double)f.p[1] * f.p[1] + (double)f.p[2] * f.p[2] + (double)f.p[3] * f.p[3]) + 2.0 * std::fabs((double)f.p[0]); break;
+      case VPT_SDF_SPHERE: lr = std::fabs((double)f.p[0]); break;
+      case VPT_SDF_TORUS: lr = std::fabs((double)f.p[0]) + std::fabs((double)f.p[1]); break;
+      case VPT_SDF_CAPPED_CONE: lr = std::sqrt((double)f.p[0] * f.p[0] + std::max((double)f.p[1] * f.p[1], (double)f.p[2] * f.p[2])); break;
+      default: break;   // plane: unbounded
+    }
+    r[5] = make_float4(0, 0, 0, -1);
+    if (f.type == VPT_SDF_PLANE) planes++;
+    else if (lr > 0 && std::isfinite(lr) && rigid(f.frame)) {
+      ball b;
+      to_world(f.frame, lc, b.c);
+      b.r = lr * 1.05 + 1e-6;
+      balls.push_back(b);
+      r[5] = make_float4((float)b.c[0], (float)b.c[1], (float)b.c[2], (float)b.r);
+    } else all_bounded_rigid = false;
+  }
+  for (int i = 0; i < num_vol_instances; i++) {
+    const vpt_volume_instance& vi = vol_instances[i];
+    const vpt_volume&          vol = volumes[vi.volume];
+    float4* r = &sdf_grid_rec[7 * (size_t)i];
+    pack_frame(to_h(vi.frame), r);
+    // bbox_max = origin + (vol.res * grid_res) * scalef; bbox_size = bbox_max - origin   (yocto_sdfs.cpp:33-36, float)
+    float size[3];
+    for (int k = 0; k < 3; k++) {
+      float origin = vi.frame.o[k], grid_res = (float)vol.whd[k];
+      float bbox_max = origin + (vol.res * grid_res) * vi.scalef;
+      size[k] = bbox_max - origin;
+    }
+    r[3] = make_float4(size[0], size[1], size[2], vi.scalef);
+    r[4] = make_float4(size[0] * 0.5f, size[1] * 0.5f, size[2] * 0.5f, 0);
+    int tr = identity3(vi.frame) ? 1 : 0;
+    memcpy(&r[4].w, &tr, 4);
+    int dims[3] = {vol.whd[0], vol.whd[1], vol.whd[2]};
+    memcpy(&r[5], dims, 12);
+    r[5].w = vol.res;
+    int off[2] = {(int)(vol.offset & 0xffffffffll), (int)(vol.offset >> 32)};
+    memcpy(&r[6], off, 8);
+    double lc[3] = {size[0] * 0.5, size[1] * 0.5, size[2] * 0.5}, lr = std::sqrt(lc[0] * lc[0] + lc[1] * lc[1] + lc[2] * lc[2]);
+    if (lr > 0 && std::isfinite(lr) && rigid(vi.frame)) {
+      ball b;
+      to_world(vi.frame, lc, b.c);
+      b.r = lr * 1.05 + 1e-6;
+      balls.push_back(b);
+    } else all_bounded_rigid = false;
+  }
+  D.sdf_bound_cx = D.sdf_bound_cy = D.sdf_bound_cz = 0, D.sdf_bound_r = -1, D.sdf_num_planes = planes;
+  if (all_bounded_rigid && !balls.empty()) {
+    double c[3] = {0, 0, 0}, rr = 0;
+    for (const ball& b : balls)
+      for (int k = 0; k < 3; k++) c[k] += b.c[k] / (double)balls.size();
+    for (const ball& b : balls) {
+      double dist = std::sqrt((b.c[0] - c[0]) * (b.c[0] - c[0]) + (b.c[1] - c[1]) * (b.c[1] - c[1]) + (b.c[2] - c[2]) * (b.c[2] - c[2]));
+      rr = std::max(rr, dist + b.r);
+    }
+    D.sdf_bound_cx = (float)c[0], D.sdf_bound_cy = (float)c[1], D.sdf_bound_cz = (float)c[2], D.sdf_bound_r = (float)(rr * 1.01);
+  }
 }
 
 void prep_quad_slots(const vpt_bvh_node* nodes, int count, std::vector<int>& slots) {
@@ -696,6 +699,6 @@ int prepare_scene(const vpt_scene_desc& d, const vpt_scene_curves* curves, scene
     t.srgb_lut[b] = (srgb <= 0.04045) ? srgb / 12.92f : std::pow((srgb + 0.055f) / (1.0f + 0.055f), 2.4f);
   }
   build_lights(d, t);
-  build_sdf_records(d, t);
+  prep_sdf_records(d.sdfs, d.num_sdfs, d.volumes, d.vol_instances, d.num_vol_instances, t.sdf_inv, t.sdf_fn_rec, t.sdf_grid_rec, t.d);
   return VPT_OK;
 }

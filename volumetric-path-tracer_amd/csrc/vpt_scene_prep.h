@@ -58,3 +58,8 @@ void prep_quad_slots(const vpt_bvh_node* nodes, int count, std::vector<int>& slo
 // volumetric type with a colour, emission or scattering texture or on a shape with vertex colours - or more materials than the
 // path state's 16-bit id holds.  Such scenes render with K1's general instance, which carries the medium in registers.
 bool prep_media_vary(const vpt_material* materials, int num_materials, const int* inst_material, const int* inst_flags, int num_instances);
+// The SDF side of the layout, for vpt_scene_create and for vpt_scene_update_volumes (vpt_volume_update.hip): the inverse frames of
+// the SDFs (3 float4 each), the evaluation records of the SDFs (6 float4 each) and of the grid instances (7 float4 each, the
+// volume's offset in two words), and in D the scene's bounding ball (sdf_bound_*) and sdf_num_planes.  Always every record of a scene.
+void prep_sdf_records(const vpt_sdf* sdfs, int num_sdfs, const vpt_volume* volumes, const vpt_volume_instance* vol_instances, int num_vol_instances,
+    std::vector<float4>& sdf_inv, std::vector<float4>& sdf_fn_rec, std::vector<float4>& sdf_grid_rec, DScene& D);

@@ -304,6 +304,101 @@ int vpth_scene_set_texture(void* hh, int id, int width, int height, int linear, 
 }
 // make_lights of the scene as the setters above left it, then the flattened descriptor again (its address changes)
 int vpth_scene_update_textures(void* hh, char* err, int errlen) { return vpth_scene_update_lights(hh, err, errlen); }
+// ---- volumes, grid instances and SDFs (the host side of vpt_scene_update_volumes, include/vpt.h) ------------------------------
+// kind: 0 volumes, 1 volume instances, 2 SDFs
+int vpth_scene_count_implicit(void* hh, int kind) {
+  auto& sc = ((host_scene*)hh)->scene;
+  return kind == 0 ? (int)sc.volumes.size() : kind == 1 ? (int)sc.vol_instances.size() : kind == 2 ? (int)sc.sdfs.size() : -1;
+}
+int vpth_scene_get_vol_instance(void* hh, int id, vpt_volume_instance* out) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (id < 0 || id >= (int)sc.vol_instances.size() || !out) return -1;
+  auto& i = sc.vol_instances[id];
+  memcpy(&out->frame, &i.frame, sizeof(vpt_frame));
+  out->volume = i.volume, out->material = i.material, out->scalef = i.scalef;
+  return 0;
+}
+// frame, volume, material and scalef of a grid instance; desc and stats() follow at vpth_scene_update_volumes
+int vpth_scene_set_vol_instance(void* hh, int id, const vpt_volume_instance* in, char* err, int errlen) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (id < 0 || id >= (int)sc.vol_instances.size() || !in) return set_error(err, errlen, "volume instance id out of range or null pointer"), -1;
+  auto frame = (const float*)&in->frame;
+  for (auto k = 0; k < 12; k++)
+    if (!std::isfinite(frame[k])) return set_error(err, errlen, "a frame value is not finite"), -1;
+  if (!std::isfinite(in->scalef)) return set_error(err, errlen, "scalef is not finite"), -1;
+  if (in->volume < 0 || in->volume >= (int)sc.volumes.size()) return set_error(err, errlen, "volume id out of range"), -1;
+  if (in->material < 0 || in->material >= (int)sc.materials.size()) return set_error(err, errlen, "material id out of range"), -1;
+  auto& i = sc.vol_instances[id];
+  memcpy((void*)&i.frame, &in->frame, sizeof(vpt_frame));
+  i.volume = in->volume, i.material = in->material, i.scalef = in->scalef;
+  return 0;
+}
+int vpth_scene_get_sdf(void* hh, int id, vpt_sdf* out) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (id < 0 || id >= (int)sc.sdfs.size() || !out) return -1;
+  auto& s = sc.sdfs[id];
+  memcpy(&out->frame, &s.frame, sizeof(vpt_frame));
+  out->type = (int)s.type, out->material = s.material;
+  memcpy(out->whd, &s.whd, 12), memcpy(out->p, s.p, 16);
+  return 0;
+}
+// the whole SDF, type included
+int vpth_scene_set_sdf(void* hh, int id, const vpt_sdf* in, char* err, int errlen) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (id < 0 || id >= (int)sc.sdfs.size() || !in) return set_error(err, errlen, "sdf id out of range or null pointer"), -1;
+  auto frame = (const float*)&in->frame;
+  for (auto k = 0; k < 12; k++)
+    if (!std::isfinite(frame[k])) return set_error(err, errlen, "a frame value is not finite"), -1;
+  for (auto k = 0; k < 3; k++)
+    if (!std::isfinite(in->whd[k])) return set_error(err, errlen, "a whd value is not finite"), -1;
+  for (auto k = 0; k < 4; k++)
+    if (!std::isfinite(in->p[k])) return set_error(err, errlen, "a parameter is not finite"), -1;
+  if (in->type < 0 || in->type > VPT_SDF_TORUS) return set_error(err, errlen, "sdf type is not one of 0..5"), -1;
+  if (in->material < 0 || in->material >= (int)sc.materials.size()) return set_error(err, errlen, "material id out of range"), -1;
+  auto& s = sc.sdfs[id];
+  memcpy((void*)&s.frame, &in->frame, sizeof(vpt_frame));
+  s.type = (sdf_type)in->type, s.material = in->material;
+  memcpy((void*)&s.whd, in->whd, 12), memcpy(s.p, in->p, 16);
+  return 0;
+}
+// The box region_lo .. region_lo + region_whd of volume `id` written from `voxels` (region order, x fastest), whd and res the volume's
+// AFTER the call: the same whd writes in place, a new one needs the whole grid and mode 0.  mode 1: op_union(resident, incoming) =
+// (a < b) ? a : b, the select (yocto_sdfs.h:82).  The rules of vpt_scene_update_volumes.
+int vpth_scene_set_volume(void* hh, int id, const int32_t* whd, float res, const int32_t* lo, const int32_t* size, int mode, const float* voxels, char* err,
+    int errlen) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (id < 0 || id >= (int)sc.volumes.size() || !whd || !lo || !size) return set_error(err, errlen, "volume id out of range or null pointer"), -1;
+  if (!std::isfinite(res)) return set_error(err, errlen, "res is not finite"), -1;
+  if (whd[0] < 0 || whd[1] < 0 || whd[2] < 0) return set_error(err, errlen, "bad volume size"), -1;
+  if (whd[0] > 0 && whd[1] > 0 && whd[2] > 0) {   // a product below 2^31, factor by factor: no partial product can overflow
+    auto count = (int64_t)1;
+    for (auto k = 0; k < 3; k++)
+      if ((count *= whd[k]) >= (1ll << 31)) return set_error(err, errlen, "bad volume size: 2^31 voxels or more"), -1;
+  }
+  for (auto k = 0; k < 3; k++)
+    if (lo[k] < 0 || size[k] < 0 || (int64_t)lo[k] + size[k] > whd[k]) return set_error(err, errlen, "the region leaves the grid"), -1;
+  if (mode != VPT_VOXELS_REPLACE && mode != VPT_VOXELS_UNION) return set_error(err, errlen, "mode is neither REPLACE nor UNION"), -1;
+  auto& v = sc.volumes[id];
+  auto  n = (size_t)size[0] * (size_t)size[1] * (size_t)size[2];
+  if (n > 0 && !voxels) return set_error(err, errlen, "null voxels"), -1;
+  if (whd[0] != v.whd.x || whd[1] != v.whd.y || whd[2] != v.whd.z) {
+    if (size[0] != whd[0] || size[1] != whd[1] || size[2] != whd[2] || mode != VPT_VOXELS_REPLACE)
+      return set_error(err, errlen, "a new whd needs the whole grid as its region, in REPLACE mode"), -1;
+    v.whd = {whd[0], whd[1], whd[2]};
+    v.vol.assign((size_t)whd[0] * (size_t)whd[1] * (size_t)whd[2], 0.0f);
+  }
+  v.res = res;
+  for (auto z = 0; z < size[2]; z++)
+    for (auto y = 0; y < size[1]; y++)
+      for (auto x = 0; x < size[0]; x++) {
+        auto& a = v.vol[(size_t)(lo[0] + x) + (size_t)(lo[1] + y) * (size_t)whd[0] + (size_t)(lo[2] + z) * (size_t)whd[0] * (size_t)whd[1]];
+        auto  b = voxels[(size_t)x + (size_t)y * (size_t)size[0] + (size_t)z * (size_t)size[0] * (size_t)size[1]];
+        a = mode == VPT_VOXELS_UNION ? ((a < b) ? a : b) : b;
+      }
+  return 0;
+}
+// make_lights of the scene as the setters above left it (an SDF is a light iff its material is emissive), then the flattened descriptor again
+int vpth_scene_update_volumes(void* hh, char* err, int errlen) { return vpth_scene_update_lights(hh, err, errlen); }
 void vpth_scene_free(void* h) { delete (host_scene*)h; }
 const vpt_scene_desc* vpth_scene_desc(void* h) { return &((host_scene*)h)->flat->desc; }
 const vpt_scene_curves* vpth_scene_curves(void* h) { return ((host_scene*)h)->flat->curves_or_null(); }   // null: no points or lines
