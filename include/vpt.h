@@ -433,7 +433,7 @@ int vpt_scene_update_textures(vpt_scene* scene, const vpt_texture_edit* edit);
  *    included.  The evaluation records (frame, sizes, the identity tag, dimensions, res and the two-word voxel offset of a grid
  *    instance), the inverse frames, the per-record bounding balls, the scene's bounding ball and the count of planes are remade by
  *    the function vpt_scene_create calls (vpt_scene_prep.h: prep_sdf_records), for ALL records, from host mirrors of the three small
- *    tables read back on the first edit of a handle: a res, dimension or offset change of a volume therefore reaches the record of every
+ *    tables made when the handle is created and kept current by every edit: a res, dimension or offset change of a volume therefore reaches the record of every
  *    instance that names it.
  *  - Voxels from the host (offset >= 0).  whd and res describe the volume AFTER the edit; the entry writes the box region_lo ..
  *    region_lo + region_whd of it from edit->voxels + offset, region order, x fastest.  The same whd overwrites in place and any region

@@ -385,33 +385,41 @@ def test_a_tree_too_deep_is_unsupported_and_nothing_is_written(vpt, untouched, o
 
 
 # ---- beside the other updates, in a session, on a vpt_multi --------------------------------------------------------------------------
-@pytest.mark.parametrize("volumes_first", [True, False])
-def test_other_updates_on_the_same_handle(vpt, originals, volumes_first):
-    """update_volumes between update (the camera), update_lights (a material's emission: the lamp's, so the SDF light goes) and
-    update_textures (the sky dimmed) - and the reverse order"""
+KINDS = ("update", "update_lights", "update_textures", "update_volumes")
+
+
+@pytest.mark.parametrize("first", KINDS)
+def test_other_updates_on_the_same_handle(vpt, originals, first):
+    """update (the camera), update_lights (a material's emission: the lamp's, so the SDF light goes), update_textures (the sky dimmed)
+    and update_volumes on one handle: each kind as the first edit the fresh handle sees, the other three after it in that order"""
     import scene_edits as E
     A = vpt.DeviceScene(vpt.HostScene(path(V.GRID)), 0)
     host = vpt.HostScene(path(V.GRID))
 
-    def volumes():
-        for name in ("region_grid", "inst_turn_grid", "light_on_grid"):
-            V.apply(vpt, name, host, after_step=A.update_volumes, original=originals[V.GRID][0])
-
-    def others():
+    def update():
         E.edit_camera(host)
         A.update(host.update_bvh())
+
+    def update_lights():
         m = host.material(V.LAMP_MATERIAL)
         m.emission[:] = [0.0, 0.0, 0.0]
         host.set_material(V.LAMP_MATERIAL, m)
         A.update_lights(host.update_lights())
+
+    def update_textures():
         host.set_environment(0, emission=(0.25, 0.25, 0.25))
         A.update_textures(host.update_textures())
 
-    for step in ((volumes, others) if volumes_first else (others, volumes)):
-        step()
-    assert_same_everything(vpt, A, vpt.DeviceScene(host, 0), host, f"volumes_first={volumes_first}")
+    def update_volumes():
+        for name in ("region_grid", "inst_turn_grid", "light_on_grid"):
+            V.apply(vpt, name, host, after_step=A.update_volumes, original=originals[V.GRID][0])
+
+    steps = {"update": update, "update_lights": update_lights, "update_textures": update_textures, "update_volumes": update_volumes}
+    for kind in [first] + [k for k in KINDS if k != first]:
+        steps[kind]()
+    assert_same_everything(vpt, A, vpt.DeviceScene(host, 0), host, f"first={first}")
     V.apply(vpt, "grow_grid", host, after_step=A.update_volumes, original=originals[V.GRID][0])
-    assert_same_everything(vpt, A, vpt.DeviceScene(host, 0), host, f"volumes_first={volumes_first}, then grow")
+    assert_same_everything(vpt, A, vpt.DeviceScene(host, 0), host, f"first={first}, then grow")
 
 
 def test_session_edit_volumes(vpt, originals):

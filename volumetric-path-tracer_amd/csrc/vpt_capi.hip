@@ -19,6 +19,7 @@
 #include "vpt_kat.h"
 #include "vpt_launch.h"
 #include "vpt_light_update.h"
+#include "vpt_resident.h"
 #include "vpt_schedule.h"
 #include "vpt_scene_prep.h"
 #include "vpt_scene_update.h"
@@ -45,10 +46,7 @@ int vpt_set_error(int code, const char* fmt, ...) {
 struct tile_state { void *image, *hits, *rng; };
 struct row_state { void *image, *hits, *rng; };
 
-struct vpt_scene {
-  int                        device = 0;
-  DScene                     d      = {};
-  std::vector<device_buffer> tables;   // one allocation per table of d
+struct vpt_scene : resident {   // the tables and what edits them (vpt_resident.h), and the render side
   int                        stack_cap = 16;    // binary-BVH walk of the implicit kernels' mesh-light pdf: refs only
   int                        stack_lds4 = 8, stack_spill4 = 0;   // quad-node traversal: (ref, t0) entries in LDS / in HBM
   device_buffer              spill;
@@ -61,15 +59,7 @@ struct vpt_scene {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool       timed = false;
   device_buffer d_watchdog;   // unsigned: waves of the implicit kernel that gave up (must stay 0; vpt_implicit_kernel.hip.h)
-  int        light_features = 0;      // VPT_FEAT_* bits this scene's lights need from the mesh kernels
   bool       curves = false;          // some instanced shape holds points or lines: the VPT_FEAT_CURVES instances of K1
-  bool       varying_media = false;   // vpt_scene_prep.h: prep_media_vary - K1's general instance, which carries a path's medium in registers
-  host_mirrors h;   // range checks of vpt_intersect, vpt_kat
-  long long     num_shape_nodes = 0;   // nodes of d.shape_nodes (vpt_scene_get_bvh)
-  scene_updater upd;                   // vpt_scene_update: levels and quad-slot tables, built on the first update
-  light_updater lights_upd;            // vpt_scene_update_lights: sizes of the pooled light tables, mirrors built on the first rebuild
-  texture_updater textures_upd;        // vpt_scene_update_textures: sizes of the texel pools, mirrors built on the first edit
-  volume_updater volumes_upd;          // vpt_scene_update_volumes: size of the voxel pool, mirrors built on the first edit
 };
 
 namespace {
@@ -145,7 +135,7 @@ int vpt_device_count(void) {
 void vpt_scene_destroy(vpt_scene* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);   // the scene's buffers are freed on its device when it goes
-  for (hipEvent_t e : {s->ev0, s->ev1, s->upd.ev0, s->upd.ev1})
+  for (hipEvent_t e : {s->ev0, s->ev1, s->upd_ev0, s->upd_ev1})
     if (e) (void)hipEventDestroy(e);
   delete s;
 }
@@ -190,10 +180,7 @@ int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* 
   D.shape_wnodes = D.scene_wnodes + t.scene_wnodes;
   s->stack_cap = t.stack_cap, s->stack_lds4 = t.stack_lds4, s->stack_spill4 = t.stack_spill4, s->light_features = t.light_features;
   s->curves = t.curves, s->varying_media = t.varying_media, s->num_shape_nodes = d.num_shape_bvh_nodes;
-  s->lights_upd.num_cdf = d.num_light_cdf, s->lights_upd.num_pool = (long long)t.light_index_pool.size(), s->lights_upd.num_guide = (long long)t.light_guide.size();
-  s->textures_upd.num_texels_f = d.num_texels_f, s->textures_upd.num_texels_b = d.num_texels_b;
-  s->volumes_upd.num_voxels = d.num_voxels;
-  s->h = std::move(t.h);
+  s->h = std::move(t.h), s->m = std::move(t.m);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
   s->sched.compute_units = prop.multiProcessorCount;
@@ -412,57 +399,46 @@ int vpt_scene_record_bytes(const vpt_scene* s, int* leaf_bytes, int* attribute_b
   return VPT_OK;
 }
 
-// ---- editing a resident scene (include/vpt.h; the work is vpt_scene_update.hip's) ---------------------------------------------
-// lights: vpt_scene_update_lights - the two refusals about lights are lifted and the light tables follow the edit
-static int scene_update(vpt_scene* s, const vpt_scene_edit* edit, bool lights) {
+}  // extern "C"
+
+// ---- editing a resident scene (include/vpt.h; the work is the four update units') --------------------------------------------
+static bool moves_geometry(const vpt_scene_edit& e) { return e.num_instances > 0 || e.num_shapes > 0; }
+static bool writes_materials(const vpt_scene_edit& e) { return e.num_materials > 0; }
+template <typename Edit> static bool moves_geometry(const Edit&) { return false; }   // environments, textures, volumes, SDFs
+template <typename Edit> static bool writes_materials(const Edit&) { return false; }
+
+// One edit, from the idle device it needs to the tables that only this unit's kernels fill.  apply(resident&, edit, &rebuilt): the
+// unit's work; rebuilt: the light tables were made anew - light_prims and the medium records sit in fresh allocations.
+template <typename Edit, typename Apply>
+static int edit_scene(vpt_scene* s, const Edit* edit, Apply apply) {
   if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call rewrites
-  if (int rc = scene_update_apply(s->d, s->h, s->num_shape_nodes, s->upd, *edit, lights)) return rc;
   bool rebuilt = false;
-  if (lights)
-    if (int rc = light_update_apply(s->d, s->h, s->upd, s->lights_upd, s->tables, *edit, &s->light_features, &rebuilt)) return rc;
-  if (rebuilt || edit->num_instances > 0 || edit->num_shapes > 0)
+  if (int rc = apply(*s, *edit, &rebuilt)) return rc;
+  if (rebuilt || moves_geometry(*edit))
     if (int rc = light_setup(s)) return rc;   // light_prims hold world-space normals of the moved lights
-  if (rebuilt || edit->num_materials > 0) {   // the medium records follow the materials, and the table they sit in when it is made anew
+  if (rebuilt || writes_materials(*edit))     // the medium records follow the materials
     if (int rc = medium_setup(s)) return rc;
-    s->varying_media = prep_media_vary(s->upd.materials.data(), s->d.num_materials, s->upd.inst_material.data(), s->upd.inst_flags.data(), s->d.num_instances);
-  }
   s->sched.forget();   // the camera index may be the same, the picture is not
   return VPT_OK;
 }
-int vpt_scene_update(vpt_scene* s, const vpt_scene_edit* edit) { return scene_update(s, edit, false); }
-int vpt_scene_update_lights(vpt_scene* s, const vpt_scene_edit* edit) { return scene_update(s, edit, true); }
 
-// environments and textures (the work is vpt_texture_update.hip's); the light tables follow when an environment's light does
-int vpt_scene_update_textures(vpt_scene* s, const vpt_texture_edit* edit) {
-  if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call rewrites
-  bool rebuilt = false;
-  if (int rc = texture_update_apply(s->d, s->h, s->num_shape_nodes, s->upd, s->lights_upd, s->textures_upd, s->tables, *edit, &s->light_features, &rebuilt)) return rc;
-  if (rebuilt) {   // light_prims and the medium records sit in tables made anew
-    if (int rc = light_setup(s)) return rc;
-    if (int rc = medium_setup(s)) return rc;
-  }
-  s->sched.forget();
-  return VPT_OK;
-}
+extern "C" {
 
-// volumes, grid instances and SDFs (the work is vpt_volume_update.hip's); the light tables follow when the SDF lights do
-int vpt_scene_update_volumes(vpt_scene* s, const vpt_volume_edit* edit) {
-  if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call rewrites
-  bool rebuilt = false;
-  if (int rc = volume_update_apply(s->d, s->h, s->num_shape_nodes, s->upd, s->lights_upd, s->volumes_upd, s->tables, *edit, s->device, &s->light_features, &rebuilt)) return rc;
-  if (rebuilt) {   // light_prims and the medium records sit in tables made anew
-    if (int rc = light_setup(s)) return rc;
-    if (int rc = medium_setup(s)) return rc;
-  }
-  s->sched.forget();
-  return VPT_OK;
+int vpt_scene_update(vpt_scene* s, const vpt_scene_edit* edit) {
+  return edit_scene(s, edit, [](resident& r, const vpt_scene_edit& e, bool*) { return scene_update_apply(r, e); });
 }
+// the two refusals about lights are lifted and the light tables follow the edit
+int vpt_scene_update_lights(vpt_scene* s, const vpt_scene_edit* edit) {
+  return edit_scene(s, edit, [](resident& r, const vpt_scene_edit& e, bool* rebuilt) {
+    const int rc = scene_update_apply(r, e, true);
+    return rc ? rc : light_update_apply(r, e, rebuilt);
+  });
+}
+// the light tables follow when an environment's light does / when the SDF lights do
+int vpt_scene_update_textures(vpt_scene* s, const vpt_texture_edit* edit) { return edit_scene(s, edit, texture_update_apply); }
+int vpt_scene_update_volumes(vpt_scene* s, const vpt_volume_edit* edit) { return edit_scene(s, edit, volume_update_apply); }
 
 // the three small tables and a volume's voxels as the device holds them now
 int vpt_scene_get_volumes(vpt_scene* s, vpt_volume* volumes, int volume_capacity, vpt_volume_instance* vol_instances, int instance_capacity, vpt_sdf* sdfs,
@@ -496,13 +472,13 @@ int vpt_scene_get_voxels(vpt_scene* s, int volume, float* voxels, int64_t capaci
 int vpt_scene_get_lights(vpt_scene* s, vpt_light* lights, int light_capacity, int* num_lights, float* cdf, int64_t cdf_capacity, int64_t* num_cdf) {
   if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   if (num_lights) *num_lights = s->d.num_lights;
-  if (num_cdf) *num_cdf = s->lights_upd.num_cdf;
+  if (num_cdf) *num_cdf = s->m.num_cdf;
   REQUIRE(!lights || light_capacity >= s->d.num_lights, "light_capacity %d < %d lights", light_capacity, s->d.num_lights);
-  REQUIRE(!cdf || cdf_capacity >= s->lights_upd.num_cdf, "cdf_capacity %lld < %lld cdf entries", (long long)cdf_capacity, s->lights_upd.num_cdf);
+  REQUIRE(!cdf || cdf_capacity >= s->m.num_cdf, "cdf_capacity %lld < %lld cdf entries", (long long)cdf_capacity, s->m.num_cdf);
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipDeviceSynchronize());
   if (lights && s->d.num_lights) HIP_TRY(hipMemcpy(lights, s->d.lights, (size_t)s->d.num_lights * sizeof(vpt_light), hipMemcpyDeviceToHost));
-  if (cdf && s->lights_upd.num_cdf) HIP_TRY(hipMemcpy(cdf, s->d.light_cdf, (size_t)s->lights_upd.num_cdf * sizeof(float), hipMemcpyDeviceToHost));
+  if (cdf && s->m.num_cdf) HIP_TRY(hipMemcpy(cdf, s->d.light_cdf, (size_t)s->m.num_cdf * sizeof(float), hipMemcpyDeviceToHost));
   return VPT_OK;
 }
 
@@ -526,9 +502,9 @@ int vpt_scene_light_tables_hash(vpt_scene* s, uint64_t out[6]) {
   HIP_TRY(hipDeviceSynchronize());
   const size_t nl = (size_t)s->d.num_lights;
   const struct { const void* table; size_t bytes; int slot; } parts[7] = {
-      {s->d.lights, nl * sizeof(vpt_light), 0}, {s->d.light_cdf, (size_t)s->lights_upd.num_cdf * sizeof(float), 1}, {s->d.light_rec, 8 * nl * sizeof(float4), 2},
+      {s->d.lights, nl * sizeof(vpt_light), 0}, {s->d.light_cdf, (size_t)s->m.num_cdf * sizeof(float), 1}, {s->d.light_rec, 8 * nl * sizeof(float4), 2},
       {s->d.light_prims, 20 * nl * sizeof(float4), 3}, {s->d.light_index, nl * sizeof(DCdfIndex), 4},
-      {s->d.light_index_pool, (size_t)s->lights_upd.num_pool * sizeof(float), 4}, {s->d.light_guide, (size_t)s->lights_upd.num_guide * sizeof(int2), 5}};
+      {s->d.light_index_pool, (size_t)s->m.num_pool * sizeof(float), 4}, {s->d.light_guide, (size_t)s->m.num_guide * sizeof(int2), 5}};
   for (int k = 0; k < 6; k++) out[k] = 14695981039346656037ull;
   std::vector<unsigned char> host;
   for (const auto& p : parts) {
@@ -555,7 +531,7 @@ int vpt_scene_get_bvh(vpt_scene* s, vpt_bvh_node* scene_nodes, int scene_capacit
 // what the last vpt_scene_update on this handle launched and sent (profiles/tools/scene_update_measure.py)
 int vpt_scene_update_stats(const vpt_scene* s, int* launches, int64_t* bytes, float* device_ms) {
   if (!s || !launches || !bytes || !device_ms) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  *launches = s->upd.last_launches, *bytes = s->upd.last_bytes, *device_ms = s->upd.last_ms;
+  *launches = s->last_launches, *bytes = s->last_bytes, *device_ms = s->last_ms;
   return VPT_OK;
 }
 

@@ -178,7 +178,6 @@ __global__ void lit_records_kernel(float4* __restrict__ rec, const vpt_light* __
 // ---- host -----------------------------------------------------------------------------------------------------------------
 constexpr int BLOCK = 256;
 inline unsigned blocks_for(long long n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-bool emissive(const vpt_material& m) { return !(m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0); }   // make_lights, yocto_pathtrace.cpp:990
 
 #define LAUNCHED(u)                \
   do {                             \
@@ -203,13 +202,6 @@ bool index_layout(long long n, long long at, DCdfIndex& ix, index_fill& f) {
   return true;
 }
 
-template <typename T>
-int send(scene_updater& u, device_buffer& to, const std::vector<T>& host) {
-  if (int rc = to.allocate(host.size() * sizeof(T))) return rc;
-  if (!host.empty()) HIP_TRY(hipMemcpy(to.get(), host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-  u.last_bytes += (long long)(host.size() * sizeof(T));
-  return VPT_OK;
-}
 int move(void* to, const void* from, size_t bytes) {
   if (bytes) HIP_TRY(hipMemcpy(to, from, bytes, hipMemcpyDeviceToDevice));
   return VPT_OK;
@@ -223,15 +215,11 @@ struct entry {   // one light of the new list
 
 }  // namespace
 
-int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light_updater& lu, std::vector<device_buffer>& tables,
-    const vpt_scene_edit& e, int* light_features, bool* rebuilt, const std::vector<env_light>* envs, const std::vector<char>* sdf_resized) {
+int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, const std::vector<env_light>* envs, const std::vector<char>* sdf_resized) {
   *rebuilt = false;
-  if (!lu.ready) {
-    lu.index.resize((size_t)d.num_lights), lu.sdfs.resize((size_t)d.num_sdfs);
-    if (d.num_lights) HIP_TRY(hipMemcpy(lu.index.data(), d.light_index, lu.index.size() * sizeof(DCdfIndex), hipMemcpyDeviceToHost));
-    if (d.num_sdfs) HIP_TRY(hipMemcpy(lu.sdfs.data(), d.sdfs, lu.sdfs.size() * sizeof(vpt_sdf), hipMemcpyDeviceToHost));
-    lu.ready = true;
-  }
+  DScene&             d = r.d;
+  const host_mirrors& h = r.h;
+  edit_mirrors&       u = r.m;
 
   // 1. the list (make_lights): emissive instances of faces, the environments that were lights, emissive SDFs - each in id order
   const std::vector<vpt_light>& old = u.lights;
@@ -265,7 +253,7 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
     for (size_t l = 0; l < old.size(); l++)   // the edit has no field for an environment's emission or texture
       if (old[l].instance < 0 && old[l].sdf < 0) list.push_back({old[l], (int)l, false, u.light_kind[l]});
   for (int i = 0; i < d.num_sdfs; i++)
-    if (emissive(u.materials[(size_t)lu.sdfs[(size_t)i].material])) list.push_back({{VPT_INVALID, VPT_INVALID, i, 1, 0}, old_of_sdf[(size_t)i], false, VPT_LIGHT_SDF});
+    if (emissive(u.materials[(size_t)u.sdfs[(size_t)i].material])) list.push_back({{VPT_INVALID, VPT_INVALID, i, 1, 0}, old_of_sdf[(size_t)i], false, VPT_LIGHT_SDF});
   bool same = list.size() == old.size();
   for (size_t l = 0; same && l < list.size(); l++) same = list[l].from == (int)l && !list[l].recompute && list[l].l.cdf_len == old[l].cdf_len;
   for (size_t l = 0; same && sdf_resized && l < list.size(); l++) same = list[l].l.sdf < 0 || !(*sdf_resized)[(size_t)list[l].l.sdf];   // its one CDF entry is whd.x * whd.y
@@ -285,9 +273,8 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
   for (int l = 0; l < nl; l++) {
     const entry& en = list[(size_t)l];
     if (en.l.sdf >= 0) {   // make_lights: cdf = {whd.x * whd.y}
-      const float area = lu.sdfs[(size_t)en.l.sdf].whd[0] * lu.sdfs[(size_t)en.l.sdf].whd[1];
-      HIP_TRY(hipMemcpy(cdf + en.l.cdf_offset, &area, sizeof(float), hipMemcpyHostToDevice));
-      u.last_bytes += sizeof(float);
+      const float area = u.sdfs[(size_t)en.l.sdf].whd[0] * u.sdfs[(size_t)en.l.sdf].whd[1];
+      if (int rc = send(r, cdf + en.l.cdf_offset, &area, 1)) return rc;
     } else if (en.recompute && en.l.instance < 0) {   // an environment: one weight per texel
       jobs.push_back({en.l.cdf_offset, 0, 0, en.l.cdf_len, JOB_TEXELS});
       job_light.push_back(l);
@@ -301,9 +288,9 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
   const int njobs = (int)jobs.size();
   std::vector<job_result> results((size_t)njobs);
   if (njobs > 0) {
-    if (int rc = send(u, lu.d_jobs, jobs)) return rc;
-    if (int rc = lu.d_result.allocate((size_t)njobs * sizeof(job_result))) return rc;
-    const light_job* d_jobs = lu.d_jobs.get<light_job>();
+    if (int rc = send(r, r.d_jobs, jobs)) return rc;
+    if (int rc = r.d_result.allocate((size_t)njobs * sizeof(job_result))) return rc;
+    const light_job* d_jobs = r.d_jobs.get<light_job>();
     for (int first = 0; first < njobs; first += 65535) {   // grid.y is a 16-bit count
       const int count = njobs - first < 65535 ? njobs - first : 65535;
       int most = 0;
@@ -311,18 +298,17 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
         if (jobs[(size_t)k].kind != JOB_TEXELS) most = jobs[(size_t)k].num_elems > most ? jobs[(size_t)k].num_elems : most;
       if (most == 0) continue;   // texel jobs only
       hipLaunchKernelGGL(lit_areas_kernel, dim3(blocks_for(most), (unsigned)count), dim3(BLOCK), 0, 0, d_jobs, first, d.elems, d.positions, cdf);
-      LAUNCHED(u);
+      LAUNCHED(r);
     }
     for (int k = 0; k < njobs; k++)
       if (jobs[(size_t)k].kind == JOB_TEXELS) {
-        if (int rc = launch_texel_weights((*envs)[(size_t)env_of[(size_t)job_light[(size_t)k]]], cdf + jobs[(size_t)k].cdf_offset)) return rc;
-        u.last_launches++;
+        if (int rc = launch_texel_weights(r, (*envs)[(size_t)env_of[(size_t)job_light[(size_t)k]]], cdf + jobs[(size_t)k].cdf_offset)) return rc;
       }
-    if (getenv("VPT_LIGHTS_PLAIN")) hipLaunchKernelGGL(lit_scan_plain_kernel, dim3(blocks_for(njobs)), dim3(BLOCK), 0, 0, d_jobs, njobs, cdf, lu.d_result.get<job_result>());
-    else hipLaunchKernelGGL(lit_scan_wave_kernel, dim3((unsigned)njobs), dim3(64), 0, 0, d_jobs, cdf, lu.d_result.get<job_result>());
-    LAUNCHED(u);
-    HIP_TRY(hipMemcpy(results.data(), lu.d_result.get(), results.size() * sizeof(job_result), hipMemcpyDeviceToHost));
-    u.last_bytes += (long long)(results.size() * sizeof(job_result));
+    if (getenv("VPT_LIGHTS_PLAIN")) hipLaunchKernelGGL(lit_scan_plain_kernel, dim3(blocks_for(njobs)), dim3(BLOCK), 0, 0, d_jobs, njobs, cdf, r.d_result.get<job_result>());
+    else hipLaunchKernelGGL(lit_scan_wave_kernel, dim3((unsigned)njobs), dim3(64), 0, 0, d_jobs, cdf, r.d_result.get<job_result>());
+    LAUNCHED(r);
+    HIP_TRY(hipMemcpy(results.data(), r.d_result.get(), results.size() * sizeof(job_result), hipMemcpyDeviceToHost));
+    r.last_bytes += (long long)(results.size() * sizeof(job_result));
   }
 
   // 3. the search structures: a light whose CDF moved keeps its index with the offsets rebased, a recomputed one gets build_lights'
@@ -345,8 +331,8 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
       if (!(r.back > 0) || !std::isfinite(scale) || M < 16) continue;
       ix.guide_offset = (int)num_guide, ix.guide_buckets = (int)M, ix.guide_scale = scale;
       num_guide += M;
-    } else if (en.from >= 0 && n > 0 && lu.index[(size_t)en.from].levels > 0) {   // (n = 0: an environment that lost its texture)
-      const DCdfIndex& was = lu.index[(size_t)en.from];
+    } else if (en.from >= 0 && n > 0 && u.light_index[(size_t)en.from].levels > 0) {   // (n = 0: an environment that lost its texture)
+      const DCdfIndex& was = u.light_index[(size_t)en.from];
       index_layout(n, num_pool, ix, f);
       num_pool = f.end;
       if (was.guide_buckets > 0) ix.guide_offset = (int)num_guide, ix.guide_buckets = was.guide_buckets, ix.guide_scale = was.guide_scale, num_guide += was.guide_buckets;
@@ -364,13 +350,13 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
     int2*  guide = guide_buf.get<int2>() + ix.guide_offset;
     if (en.recompute) {
       hipLaunchKernelGGL(lit_index_levels_kernel, dim3(blocks_for(f.end - f.offset[0])), dim3(BLOCK), 0, 0, pool, f, cdf + en.l.cdf_offset, en.l.cdf_len);
-      LAUNCHED(u);
+      LAUNCHED(r);
       if (ix.guide_buckets > 0) {
         hipLaunchKernelGGL(lit_guide_kernel, dim3(blocks_for(ix.guide_buckets)), dim3(BLOCK), 0, 0, guide, ix.guide_buckets, ix.guide_scale, cdf + en.l.cdf_offset, en.l.cdf_len);
-        LAUNCHED(u);
+        LAUNCHED(r);
       }
     } else {
-      const DCdfIndex& was = lu.index[(size_t)en.from];
+      const DCdfIndex& was = u.light_index[(size_t)en.from];
       if (int rc = move(pool + f.offset[0], d.light_index_pool + was.offset[0], (size_t)(f.end - f.offset[0]) * sizeof(float))) return rc;
       if (int rc = move(guide, d.light_guide + was.guide_offset, (size_t)ix.guide_buckets * sizeof(int2))) return rc;
     }
@@ -381,22 +367,21 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
   std::vector<int>       tags((size_t)nl);
   for (int l = 0; l < nl; l++) lights[(size_t)l] = list[(size_t)l].l, tags[(size_t)l] = list[(size_t)l].tag;
   device_buffer lights_buf, index_buf, rec_buf, prims_buf;
-  if (int rc = send(u, lights_buf, lights)) return rc;
-  if (int rc = send(u, index_buf, index)) return rc;
-  if (int rc = send(u, lu.d_tags, tags)) return rc;
+  if (int rc = send(r, lights_buf, lights)) return rc;
+  if (int rc = send(r, index_buf, index)) return rc;
+  if (int rc = send(r, r.d_tags, tags)) return rc;
   if (int rc = rec_buf.allocate((8 * (size_t)nl + 3 * (size_t)d.num_materials) * sizeof(float4))) return rc;   // + the medium records: the caller refills them
   if (int rc = prims_buf.allocate(20 * (size_t)nl * sizeof(float4))) return rc;
   HIP_TRY(hipMemset(prims_buf.get(), 0, 20 * (size_t)nl * sizeof(float4) + (nl ? 0 : 16)));
   for (int l = 0; l < nl; l++)
     if (env_of[(size_t)l] >= 0) {
-      HIP_TRY(hipMemcpy(rec_buf.get<float4>() + 8 * (size_t)l, (*envs)[(size_t)env_of[(size_t)l]].record, 8 * sizeof(float4), hipMemcpyHostToDevice));
-      u.last_bytes += 8 * sizeof(float4);
+      if (int rc = send(r, rec_buf.get<float4>() + 8 * (size_t)l, (*envs)[(size_t)env_of[(size_t)l]].record, 8)) return rc;
     } else if (list[(size_t)l].l.instance < 0 && list[(size_t)l].l.sdf < 0)
       if (int rc = move(rec_buf.get<float4>() + 8 * (size_t)l, d.light_rec + 8 * (size_t)list[(size_t)l].from, 8 * sizeof(float4))) return rc;
   if (nl > 0) {
-    hipLaunchKernelGGL(lit_records_kernel, dim3(blocks_for(nl)), dim3(BLOCK), 0, 0, rec_buf.get<float4>(), lights_buf.get<vpt_light>(), lu.d_tags.get<int>(), nl, cdf,
+    hipLaunchKernelGGL(lit_records_kernel, dim3(blocks_for(nl)), dim3(BLOCK), 0, 0, rec_buf.get<float4>(), lights_buf.get<vpt_light>(), r.d_tags.get<int>(), nl, cdf,
         d.instances, d.shapes, envs ? 1 : 0);
-    LAUNCHED(u);
+    LAUNCHED(r);
   }
   HIP_TRY(hipDeviceSynchronize());   // nothing reads the old tables any more
 
@@ -405,8 +390,8 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
   d.lights = lights_buf.get<vpt_light>(), d.light_cdf = cdf, d.light_index = index_buf.get<DCdfIndex>(), d.light_index_pool = pool_buf.get<float>();
   d.light_guide = guide_buf.get<int2>(), d.light_rec = rec_buf.get<float4>(), d.light_prims = prims_buf.get<float4>(), d.num_lights = nl;
   device_buffer* fresh[7] = {&lights_buf, &cdf_buf, &index_buf, &pool_buf, &guide_buf, &rec_buf, &prims_buf};
-  for (int k = 0; k < 7; k++) adopt(tables, was[k], std::move(*fresh[k]));
-  lu.num_cdf = num_cdf, lu.num_pool = num_pool, lu.num_guide = num_guide, lu.index = index;
+  for (int k = 0; k < 7; k++) adopt(r.tables, was[k], std::move(*fresh[k]));
+  u.num_cdf = num_cdf, u.num_pool = num_pool, u.num_guide = num_guide, u.light_index = index;
   u.lights = lights, u.light_kind.assign((size_t)nl, VPT_LIGHT_NONE), u.shape_lit.assign((size_t)d.num_shapes, 0);
   int features = 0;
   for (int l = 0; l < nl; l++) {
@@ -415,6 +400,6 @@ int light_update_apply(DScene& d, const host_mirrors& h, scene_updater& u, light
     if (lights[(size_t)l].instance >= 0) u.shape_lit[(size_t)h.inst_shape[(size_t)lights[(size_t)l].instance]] = 1;
     features |= kind == VPT_LIGHT_LARGE_MESH ? VPT_FEAT_LARGE_LIGHTS : kind == VPT_LIGHT_SMALL_MESH ? VPT_FEAT_SMALL_LIGHTS : kind == VPT_LIGHT_SDF ? VPT_FEAT_SDF_LIGHTS : 0;
   }
-  *light_features = features;
+  r.light_features = features;
   return VPT_OK;
 }

@@ -1,0 +1,50 @@
+// vpt_resident.h — the part of a vpt_scene that the edits of a resident scene work on (include/vpt.h: vpt_scene_update, _lights,
+// _textures, _volumes): the tables on the device, their host mirrors, and what an edit keeps between calls.  vpt_capi.hip's
+// vpt_scene is a `resident` plus its render side (schedule, staging, stacks); the four update units see only this.
+#pragma once
+#include <vector>
+
+#include "vpt_device_buffer.h"
+#include "vpt_scene_prep.h"
+
+// The internal nodes of one BVH by depth: nodes of depth l are order[first[l] .. first[l + 1]) of refit_tables::d_order (ids
+// local to the BVH).  A refit walks the levels deepest first.
+struct bvh_levels {
+  std::vector<int> first;        // depth + 1 entries; empty: no internal node
+  long long        offset = 0;   // of this BVH's part of d_order
+};
+
+// What a refit needs beyond the scene's own tables.  The one thing built late: by the first edit of a handle that moves an
+// instance or a vertex (vpt_scene_update.hip), from the node arrays the device holds - topology never changes - and kept.
+struct refit_tables {
+  bool ready = false;
+  bvh_levels              scene_levels;
+  std::vector<bvh_levels> shape_levels;
+  device_buffer d_order;        // int
+  device_buffer d_quad_slots;   // int4 per quad node of DScene::scene_wnodes: the binary nodes behind its slots (prep_quad_slots), local to the BVH
+  long long     scene_quads = 0;   // quad nodes of the scene BVH (the shapes' follow at DShape::wnode_offset)
+  std::vector<long long> shape_quads;   // per shape
+  device_buffer d_inst_box;     // 2 float4 per instance: transform_bbox(frame, shape root box)
+};
+
+struct resident {
+  int                        device = 0;
+  DScene                     d      = {};
+  std::vector<device_buffer> tables;   // one allocation per table of d
+  host_mirrors h;                      // range checks of vpt_intersect, vpt_kat; sizes of a vertex edit
+  edit_mirrors m;                      // as vpt_scene_create made them, as the last edit left them
+  long long    num_shape_nodes = 0;    // nodes of d.shape_nodes
+  int          light_features  = 0;      // VPT_FEAT_* bits this scene's lights need from the mesh kernels
+  bool         varying_media   = false;  // prep_media_vary of m.materials: K1's general instance, which carries a path's medium in registers
+  refit_tables refit;
+  // buffers of an edit on its way to the tables, kept from call to call
+  device_buffer d_stage;   // vpt_scene_update: moved vertices and frames
+  size_t        stage_bytes = 0;
+  device_buffer d_jobs, d_result, d_tags;   // a light rebuild: the recomputed lights' descriptors, {sorted, last entry} per job, record tags per light
+  device_buffer d_sin;     // sin((j + 0.5f) * pif / height) per row of the recomputed environments, made on the host
+  // what the last edit did (vpt_scene_update_stats): begin_update (vpt_update_helpers.h) starts them, launches and sends count themselves
+  int        last_launches = 0;
+  long long  last_bytes    = 0;
+  float      last_ms       = 0;   // device time between the two events (stream 0)
+  hipEvent_t upd_ev0 = nullptr, upd_ev1 = nullptr;   // made by the first edit, destroyed by vpt_scene_destroy
+};

@@ -531,6 +531,27 @@ void build_lights(const vpt_scene_desc& d, scene_tables& t) {
   }
 }
 
+// what the edits of the resident scene keep on the host (edit_mirrors): the descriptor's small tables and what the tables above say
+// about them, while both are at hand
+void build_edit_mirrors(const vpt_scene_desc& d, scene_tables& t) {
+  edit_mirrors& m = t.m;
+  m.materials.assign(d.materials, d.materials + d.num_materials), m.environments.assign(d.environments, d.environments + d.num_environments);
+  m.textures.assign(d.textures, d.textures + d.num_textures), m.lights.assign(d.lights, d.lights + d.num_lights);
+  m.sdfs.assign(d.sdfs, d.sdfs + d.num_sdfs), m.volumes.assign(d.volumes, d.volumes + d.num_volumes);
+  m.vol_instances.assign(d.vol_instances, d.vol_instances + d.num_vol_instances);
+  m.shapes = t.shapes, m.light_index = t.light_index;
+  m.textured.assign((size_t)d.num_materials, 0), m.shape_lit.assign((size_t)d.num_shapes, 0);
+  for (const DInstance& in : t.instances) m.textured[(size_t)in.material] = 1, m.inst_material.push_back(in.material), m.inst_flags.push_back(in.shape_flags);
+  for (int l = 0; l < d.num_lights; l++) {
+    int tag;
+    memcpy(&tag, &t.light_rec[8 * (size_t)l + 7].w, 4);
+    m.light_kind.push_back(tag & 255);
+    if (d.lights[l].instance >= 0) m.shape_lit[(size_t)t.instances[(size_t)d.lights[l].instance].shape] = 1;
+  }
+  m.num_cdf = d.num_light_cdf, m.num_pool = (long long)t.light_index_pool.size(), m.num_guide = (long long)t.light_guide.size();
+  m.num_texels_f = d.num_texels_f, m.num_texels_b = d.num_texels_b, m.num_voxels = d.num_voxels;
+}
+
 }  // namespace
 
 void prep_instance_frames(const vpt_frame& frame, float4 inv[3], float4 fwd[3], int* translation_only) {
@@ -687,11 +708,6 @@ int prepare_scene(const vpt_scene_desc& d, const vpt_scene_curves* curves, scene
   build_geometry(d, cs, t);
   if (int rc = build_quad_nodes_and_stacks(d, t)) return rc;
   build_instances(d, cs, t);
-  {
-    std::vector<int> inst_material, inst_flags;
-    for (const DInstance& in : t.instances) inst_material.push_back(in.material), inst_flags.push_back(in.shape_flags);
-    t.varying_media = prep_media_vary(d.materials, d.num_materials, inst_material.data(), inst_flags.data(), d.num_instances);
-  }
   // sRGB decode LUT: byte_to_float then srgb_to_rgb, yocto_color.h:212-227, evaluated with the host powf
   t.srgb_lut.resize(256);
   for (int b = 0; b < 256; b++) {
@@ -700,5 +716,7 @@ int prepare_scene(const vpt_scene_desc& d, const vpt_scene_curves* curves, scene
   }
   build_lights(d, t);
   prep_sdf_records(d.sdfs, d.num_sdfs, d.volumes, d.vol_instances, d.num_vol_instances, t.sdf_inv, t.sdf_fn_rec, t.sdf_grid_rec, t.d);
+  build_edit_mirrors(d, t);
+  t.varying_media = prep_media_vary(d.materials, d.num_materials, t.m.inst_material.data(), t.m.inst_flags.data(), d.num_instances);
   return VPT_OK;
 }

@@ -13,6 +13,27 @@ struct host_mirrors {
   std::vector<int> prim_slot;   // [shape elem_offset + element] -> slot in leaf_prims / leaf_attrs
 };
 
+// Host copies of the small tables an edit of the resident scene is checked against and its light list is decided from
+// (vpt_resident.h), and the entry counts of the pooled tables.  Made here, from the descriptor and the tables, moved into the
+// handle with host_mirrors and kept current by every edit: never read back from the device.
+struct edit_mirrors {
+  std::vector<vpt_material>    materials;
+  std::vector<vpt_environment> environments;
+  std::vector<vpt_texture>     textures;     // a texture is an emitter's when the emission_tex of an environment with non-zero emission names it
+  std::vector<char>            textured;     // material bound to a mesh instance: its texture ids are range-checked
+  std::vector<DShape>          shapes;       // offsets, counts and root_ref (root_box: creation's, the device refits its own)
+  std::vector<int>             inst_material, inst_flags;   // DInstance::material / shape_flags
+  std::vector<vpt_light>       lights;
+  std::vector<int>             light_kind;   // VPT_LIGHT_* of every light record (the tag of its last word)
+  std::vector<char>            shape_lit;    // some light's instance uses the shape
+  std::vector<DCdfIndex>       light_index;
+  std::vector<vpt_sdf>         sdfs;
+  std::vector<vpt_volume>          volumes;
+  std::vector<vpt_volume_instance> vol_instances;
+  // entries of the pooled tables the device holds now: a texture, a volume or a light that needs more room gets it in a pool made anew
+  long long num_cdf = 0, num_pool = 0, num_guide = 0, num_texels_f = 0, num_texels_b = 0, num_voxels = 0;
+};
+
 struct scene_tables {
   // the scalar fields of DScene: counts, scene_root_*, group_forms, sdf_bound_*, sdf_num_planes; the table pointers stay null
   DScene d = {};
@@ -40,6 +61,7 @@ struct scene_tables {
   bool curves = false;      // some instanced shape holds points or lines: the mesh kernels' VPT_FEAT_CURVES instances
   bool varying_media = false;   // prep_media_vary() of the scene
   host_mirrors h;
+  edit_mirrors m;
 };
 
 // validate(desc, curves), then every table (curves may be null: no shape has points or lines); VPT_ERR_INVALID_ARG for a bad descriptor, VPT_ERR_UNSUPPORTED for a scene past a traversal

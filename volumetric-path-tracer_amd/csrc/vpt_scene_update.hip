@@ -274,29 +274,12 @@ int read_back(std::vector<T>& out, const T* dev, size_t count) {
   return VPT_OK;
 }
 
-// everything an update needs beyond the tables themselves, from what the device holds (once per handle)
-int updater_init(const DScene& d, long long num_shape_nodes, scene_updater& u) {
-  std::vector<DInstance>    instances;
+// what a refit needs beyond the tables themselves, from the node arrays the device holds (once per handle, before its first refit)
+int refit_tables_init(const resident& r, refit_tables& u) {
+  const DScene& d = r.d;
   std::vector<vpt_bvh_node> scene_nodes, shape_nodes;
-  if (int rc = read_back(u.materials, d.materials, (size_t)d.num_materials)) return rc;
-  if (int rc = read_back(u.environments, d.environments, (size_t)d.num_environments)) return rc;
-  if (int rc = read_back(u.shapes, d.shapes, (size_t)d.num_shapes)) return rc;
-  if (int rc = read_back(u.lights, d.lights, (size_t)d.num_lights)) return rc;
-  if (int rc = read_back(instances, d.instances, (size_t)d.num_instances)) return rc;
   if (int rc = read_back(scene_nodes, (const vpt_bvh_node*)d.scene_nodes, (size_t)d.num_scene_nodes)) return rc;
-  if (int rc = read_back(shape_nodes, (const vpt_bvh_node*)d.shape_nodes, (size_t)num_shape_nodes)) return rc;
-  std::vector<float4> light_rec;
-  if (int rc = read_back(light_rec, d.light_rec, 8 * (size_t)d.num_lights)) return rc;
-  u.light_kind.assign((size_t)d.num_lights, VPT_LIGHT_NONE);   // fixed at creation (build_lights): the tag of the record's last word
-  for (int l = 0; l < d.num_lights; l++) {
-    int tag;
-    memcpy(&tag, &light_rec[8 * (size_t)l + 7].w, 4);
-    u.light_kind[(size_t)l] = tag & 255;
-  }
-  u.textured.assign((size_t)d.num_materials, 0), u.shape_lit.assign((size_t)d.num_shapes, 0);
-  for (const DInstance& in : instances) u.textured[(size_t)in.material] = 1, u.inst_material.push_back(in.material), u.inst_flags.push_back(in.shape_flags);
-  for (const vpt_light& l : u.lights)
-    if (l.instance >= 0) u.shape_lit[(size_t)instances[(size_t)l.instance].shape] = 1;
+  if (int rc = read_back(shape_nodes, (const vpt_bvh_node*)d.shape_nodes, (size_t)r.num_shape_nodes)) return rc;
   std::vector<int> order, slots;
   make_levels(scene_nodes.data(), d.num_scene_nodes, u.scene_levels, order);
   prep_quad_slots(scene_nodes.data(), d.num_scene_nodes, slots);
@@ -304,7 +287,7 @@ int updater_init(const DScene& d, long long num_shape_nodes, scene_updater& u) {
   if (u.scene_quads != (d.shape_wnodes - d.scene_wnodes) / 8) return vpt_set_error(VPT_ERR_HIP, "scene update: the scene's quad nodes do not match its binary nodes");
   u.shape_levels.assign((size_t)d.num_shapes, {}), u.shape_quads.assign((size_t)d.num_shapes, 0);
   for (int i = 0; i < d.num_shapes; i++) {
-    const DShape& sh = u.shapes[(size_t)i];
+    const DShape& sh = r.m.shapes[(size_t)i];
     if ((long long)slots.size() / 4 != u.scene_quads + sh.wnode_offset) return vpt_set_error(VPT_ERR_HIP, "scene update: shape %d: quad nodes do not match its binary nodes", i);
     make_levels(shape_nodes.data() + sh.node_offset, sh.num_nodes, u.shape_levels[(size_t)i], order);
     prep_quad_slots(shape_nodes.data() + sh.node_offset, sh.num_nodes, slots);
@@ -319,9 +302,10 @@ int updater_init(const DScene& d, long long num_shape_nodes, scene_updater& u) {
   return VPT_OK;
 }
 
-bool emissive(const vpt_material& m) { return !(m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0); }   // make_lights, yocto_pathtrace.cpp:990
-
-int validate_edit(const DScene& d, const host_mirrors& h, const scene_updater& u, const vpt_scene_edit& e, bool lights) {
+int validate_edit(const resident& r, const vpt_scene_edit& e, bool lights) {
+  const DScene&       d = r.d;
+  const host_mirrors& h = r.h;
+  const edit_mirrors& u = r.m;
   if (int rc = check_ids("camera", e.num_cameras, e.camera_ids, e.cameras, d.num_cameras)) return rc;
   if (int rc = check_ids("instance", e.num_instances, e.instance_ids, e.instance_frames, d.num_instances)) return rc;
   if (int rc = check_ids("environment", e.num_environments, e.environment_ids, e.environment_frames, d.num_environments)) return rc;
@@ -378,7 +362,7 @@ struct payload {
     return at;
   }
 };
-int send(scene_updater& u, const payload& p) {
+int stage(resident& u, const payload& p) {
   if (p.host.size() > u.stage_bytes) {
     u.stage_bytes = 0;
     if (int rc = u.d_stage.allocate(p.host.size())) return rc;   // the call began with the device idle: nothing reads the buffer that goes
@@ -390,10 +374,10 @@ int send(scene_updater& u, const payload& p) {
 }
 
 // internal nodes of one BVH, deepest level first: a launch per level down to the narrow top, which one workgroup finishes
-int refit_internal_levels(scene_updater& u, float4* nodes, long long base, const bvh_levels& lv) {
+int refit_internal_levels(resident& u, float4* nodes, long long base, const bvh_levels& lv) {
   if (lv.first.empty()) return VPT_OK;
   const int  levels = (int)lv.first.size() - 1;
-  const int* order  = u.d_order.get<int>() + lv.offset;
+  const int* order  = u.refit.d_order.get<int>() + lv.offset;
   int top = 0;   // levels [0, top) are narrow: one launch
   const bool fuse = !getenv("VPT_UPDATE_NO_FUSE");   // A/B switch of the tests and measurements, read per call: a launch per level throughout - same bits
   while (fuse && top < levels && top < UPD_TOP_LEVELS && lv.first[(size_t)top + 1] - lv.first[(size_t)top] <= UPD_TOP_WIDTH) top++;
@@ -413,44 +397,40 @@ int refit_internal_levels(scene_updater& u, float4* nodes, long long base, const
 
 }  // namespace
 
-int scene_update_apply(DScene& d, const host_mirrors& h, long long num_shape_nodes, scene_updater& u, const vpt_scene_edit& e, bool lights) {
-  if (!u.ready)
-    if (int rc = updater_init(d, num_shape_nodes, u)) return rc;
-  if (int rc = validate_edit(d, h, u, e, lights)) return rc;   // every refusal happens here: nothing has been written
-  u.last_launches = 0, u.last_bytes = 0, u.last_ms = 0;
-  if (!u.ev0) {
-    HIP_TRY(hipEventCreate(&u.ev0));
-    HIP_TRY(hipEventCreate(&u.ev1));
-  }
+int scene_update_apply(resident& r, const vpt_scene_edit& e, bool lights) {
+  if (int rc = validate_edit(r, e, lights)) return rc;   // every refusal happens here: nothing has been written
+  const bool refit = e.num_instances > 0 || e.num_shapes > 0;
+  if (refit && !r.refit.ready)
+    if (int rc = refit_tables_init(r, r.refit)) return rc;
+  if (int rc = begin_update(r)) return rc;
+  DScene&             d = r.d;
+  const host_mirrors& h = r.h;
+  edit_mirrors&       m = r.m;
 
   // cameras, materials, environments: the payload itself (and the host-made inverse frame) into the tables
-  for (int i = 0; i < e.num_cameras; i++) {
-    HIP_TRY(hipMemcpy(mut(d.cameras) + e.camera_ids[i], &e.cameras[i], sizeof(vpt_camera), hipMemcpyHostToDevice));
-    u.last_bytes += sizeof(vpt_camera);
-  }
+  for (int i = 0; i < e.num_cameras; i++)
+    if (int rc = send(r, d.cameras + e.camera_ids[i], &e.cameras[i], 1)) return rc;
   for (int i = 0; i < e.num_materials; i++) {
-    HIP_TRY(hipMemcpy(mut(d.materials) + e.material_ids[i], &e.materials[i], sizeof(vpt_material), hipMemcpyHostToDevice));
-    u.last_bytes += sizeof(vpt_material);
-    u.materials[(size_t)e.material_ids[i]] = e.materials[i];
+    if (int rc = send(r, d.materials + e.material_ids[i], &e.materials[i], 1)) return rc;
+    m.materials[(size_t)e.material_ids[i]] = e.materials[i];
   }
+  if (e.num_materials > 0) r.varying_media = prep_media_vary(m.materials.data(), d.num_materials, m.inst_material.data(), m.inst_flags.data(), d.num_instances);
   for (int i = 0; i < e.num_environments; i++) {
     const int id = e.environment_ids[i];
     float4 inv[3], fwd[3];
     prep_environment_frames(e.environment_frames[i], inv, fwd);
-    HIP_TRY(hipMemcpy(&mut(d.environments)[id].frame, &e.environment_frames[i], sizeof(vpt_frame), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(mut(d.env_inv) + 3 * (size_t)id, inv, sizeof(inv), hipMemcpyHostToDevice));
-    u.last_bytes += sizeof(vpt_frame) + sizeof(inv);
-    u.environments[(size_t)id].frame = e.environment_frames[i];
+    if (int rc = send(r, &d.environments[id].frame, &e.environment_frames[i], 1)) return rc;
+    if (int rc = send(r, d.env_inv + 3 * (size_t)id, inv, 3)) return rc;
+    m.environments[(size_t)id].frame = e.environment_frames[i];
     for (int l = 0; l < d.num_lights; l++) {   // light records of a textured environment hold both frames (build_lights); a constant one's stay zero
-      const vpt_light& lt = u.lights[(size_t)l];
+      const vpt_light& lt = m.lights[(size_t)l];
       if (lt.instance >= 0 || lt.sdf >= 0 || lt.environment != id) continue;
-      if (u.light_kind[(size_t)l] != VPT_LIGHT_ENV_TEX) continue;
-      float4 both[6] = {inv[0], inv[1], inv[2], fwd[0], fwd[1], fwd[2]};
-      HIP_TRY(hipMemcpy(mut(d.light_rec) + 8 * (size_t)l, both, sizeof(both), hipMemcpyHostToDevice));
-      u.last_bytes += sizeof(both);
+      if (m.light_kind[(size_t)l] != VPT_LIGHT_ENV_TEX) continue;
+      const float4 both[6] = {inv[0], inv[1], inv[2], fwd[0], fwd[1], fwd[2]};
+      if (int rc = send(r, d.light_rec + 8 * (size_t)l, both, 6)) return rc;
     }
   }
-  if (e.num_instances == 0 && e.num_shapes == 0) return VPT_OK;
+  if (!refit) return VPT_OK;
 
   // the bulk payload in one copy: positions / normals of the edited shapes, frames of the edited instances
   payload pay;
@@ -467,39 +447,40 @@ int scene_update_apply(DScene& d, const host_mirrors& h, long long num_shape_nod
     prep_instance_frames(e.instance_frames[i], frames[(size_t)i].inv, frames[(size_t)i].fwd, &frames[(size_t)i].translation_only);
   }
   const size_t at_frames = pay.add(frames.data(), frames.size() * sizeof(inst_payload));
-  if (int rc = send(u, pay)) return rc;
-  const char* staged = u.d_stage.get<char>();
-  HIP_TRY(hipEventRecord(u.ev0, 0));
+  if (int rc = stage(r, pay)) return rc;
+  const char*         staged = r.d_stage.get<char>();
+  const refit_tables& u      = r.refit;
+  HIP_TRY(hipEventRecord(r.upd_ev0, 0));
 
   // 1. edited shapes: vertices, leaf records, shape BVH, its quad nodes
   float4* shape_nodes = mut(d.shape_nodes);
   for (int i = 0; i < e.num_shapes; i++) {
     const int     id = e.shape_ids[i];
-    const DShape& sh = u.shapes[(size_t)id];
+    const DShape& sh = m.shapes[(size_t)id];
     const int     nv = h.shape_vertices[(size_t)id];
-    LAUNCH(u, upd_scatter_vertices_kernel, nv, mut(d.positions) + sh.vertex_offset, (const float*)(staged + at_pos[(size_t)i]), nv);
+    LAUNCH(r, upd_scatter_vertices_kernel, nv, mut(d.positions) + sh.vertex_offset, (const float*)(staged + at_pos[(size_t)i]), nv);
     if (e.shape_normals && e.shape_normals[i])
-      LAUNCH(u, upd_scatter_vertices_kernel, nv, mut(d.normals) + sh.normal_offset, (const float*)(staged + at_nrm[(size_t)i]), nv);
-    LAUNCH(u, upd_leaf_records_kernel, sh.num_elems, sh, d.elems, d.positions, d.normals, mut(d.leaf_prims), mut(d.leaf_attrs), mut(d.tri_prims), mut(d.tri_attrs));
-    LAUNCH(u, upd_refit_shape_leaves_kernel, sh.num_nodes, shape_nodes, (long long)sh.node_offset, sh.num_nodes, d.leaf_prims, (long long)sh.leaf_offset);
-    if (int rc = refit_internal_levels(u, shape_nodes, sh.node_offset, u.shape_levels[(size_t)id])) return rc;
+      LAUNCH(r, upd_scatter_vertices_kernel, nv, mut(d.normals) + sh.normal_offset, (const float*)(staged + at_nrm[(size_t)i]), nv);
+    LAUNCH(r, upd_leaf_records_kernel, sh.num_elems, sh, d.elems, d.positions, d.normals, mut(d.leaf_prims), mut(d.leaf_attrs), mut(d.tri_prims), mut(d.tri_attrs));
+    LAUNCH(r, upd_refit_shape_leaves_kernel, sh.num_nodes, shape_nodes, (long long)sh.node_offset, sh.num_nodes, d.leaf_prims, (long long)sh.leaf_offset);
+    if (int rc = refit_internal_levels(r, shape_nodes, sh.node_offset, u.shape_levels[(size_t)id])) return rc;
     const long long q0 = u.scene_quads + sh.wnode_offset, quads = u.shape_quads[(size_t)id];
-    LAUNCH(u, upd_quad_gather_kernel, quads, mut(d.scene_wnodes) + 8 * q0, u.d_quad_slots.get<int4>() + q0, (int)quads, d.shape_nodes, (long long)sh.node_offset);
+    LAUNCH(r, upd_quad_gather_kernel, quads, mut(d.scene_wnodes) + 8 * q0, u.d_quad_slots.get<int4>() + q0, (int)quads, d.shape_nodes, (long long)sh.node_offset);
   }
-  if (e.num_shapes > 0) LAUNCH(u, upd_shape_roots_kernel, d.num_shapes, mut(d.shapes), d.num_shapes, d.shape_nodes);
+  if (e.num_shapes > 0) LAUNCH(r, upd_shape_roots_kernel, d.num_shapes, mut(d.shapes), d.num_shapes, d.shape_nodes);
 
   // 2. edited instances: frames
-  LAUNCH(u, upd_scatter_instances_kernel, e.num_instances, mut(d.instances), (const inst_payload*)(staged + at_frames), e.num_instances);
+  LAUNCH(r, upd_scatter_instances_kernel, e.num_instances, mut(d.instances), (const inst_payload*)(staged + at_frames), e.num_instances);
 
   // 3. the scene BVH from ALL instances, what hangs on frames and root boxes, the scene's quad nodes
   float4* scene_nodes = mut(d.scene_nodes);
-  LAUNCH(u, upd_instance_boxes_kernel, d.num_instances, d.instances, d.num_instances, d.shapes, u.d_inst_box.get<float4>());
-  LAUNCH(u, upd_enter_records_kernel, d.num_scene_prims, mut(d.scene_enter), d.num_scene_prims, d.instances, d.shapes);
-  LAUNCH(u, upd_light_records_kernel, d.num_lights, mut(d.light_rec), d.lights, d.num_lights, d.instances, d.shapes);
-  LAUNCH(u, upd_refit_scene_leaves_kernel, d.num_scene_nodes, scene_nodes, d.num_scene_nodes, d.scene_prims, u.d_inst_box.get<float4>());
-  if (int rc = refit_internal_levels(u, scene_nodes, 0, u.scene_levels)) return rc;
-  LAUNCH(u, upd_quad_gather_kernel, u.scene_quads, mut(d.scene_wnodes), u.d_quad_slots.get<int4>(), (int)u.scene_quads, d.scene_nodes, 0LL);
-  HIP_TRY(hipEventRecord(u.ev1, 0));
+  LAUNCH(r, upd_instance_boxes_kernel, d.num_instances, d.instances, d.num_instances, d.shapes, u.d_inst_box.get<float4>());
+  LAUNCH(r, upd_enter_records_kernel, d.num_scene_prims, mut(d.scene_enter), d.num_scene_prims, d.instances, d.shapes);
+  LAUNCH(r, upd_light_records_kernel, d.num_lights, mut(d.light_rec), d.lights, d.num_lights, d.instances, d.shapes);
+  LAUNCH(r, upd_refit_scene_leaves_kernel, d.num_scene_nodes, scene_nodes, d.num_scene_nodes, d.scene_prims, u.d_inst_box.get<float4>());
+  if (int rc = refit_internal_levels(r, scene_nodes, 0, u.scene_levels)) return rc;
+  LAUNCH(r, upd_quad_gather_kernel, u.scene_quads, mut(d.scene_wnodes), u.d_quad_slots.get<int4>(), (int)u.scene_quads, d.scene_nodes, 0LL);
+  HIP_TRY(hipEventRecord(r.upd_ev1, 0));
   if (d.num_scene_nodes > 0) {   // the six scene_root_* floats the kernels receive by value
     vpt_bvh_node root;
     HIP_TRY(hipMemcpy(&root, d.scene_nodes, sizeof(root), hipMemcpyDeviceToHost));
@@ -507,6 +488,6 @@ int scene_update_apply(DScene& d, const host_mirrors& h, long long num_shape_nod
     d.scene_root_hi_x = root.bbox_max[0], d.scene_root_hi_y = root.bbox_max[1], d.scene_root_hi_z = root.bbox_max[2];
   }
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipEventElapsedTime(&u.last_ms, u.ev0, u.ev1));
+  HIP_TRY(hipEventElapsedTime(&r.last_ms, r.upd_ev0, r.upd_ev1));
   return VPT_OK;
 }

@@ -38,8 +38,7 @@ __global__ void tex_weights_byte_kernel(const uchar4* __restrict__ texels, const
 constexpr int   BLOCK = 256;
 constexpr float pif   = (float)3.14159265358979323846;
 
-bool emissive(const vpt_environment& e) { return !(e.emission[0] == 0 && e.emission[1] == 0 && e.emission[2] == 0); }   // make_lights, yocto_pathtrace.cpp:1017
-int validate_edit(const DScene& d, const texture_updater& tu, const std::vector<vpt_environment>& environments, const vpt_texture_edit& e) {
+int validate_edit(const DScene& d, const edit_mirrors& m, const vpt_texture_edit& e) {
   if (int rc = check_ids("environment", e.num_environments, e.environment_ids, e.environments, d.num_environments)) return rc;
   if (int rc = check_ids("texture", e.num_textures, e.texture_ids, e.textures, d.num_textures)) return rc;
   REQUIRE(e.num_texels_f >= 0 && (e.num_texels_f == 0 || e.texels_f), "edit: the float texel pool is null or has a negative count");
@@ -59,8 +58,8 @@ int validate_edit(const DScene& d, const texture_updater& tu, const std::vector<
         t.is_float ? "float" : "byte");
   }
   // the scene as the edit leaves it: an emissive environment's texture holds texels (vpt_scene_create: cdf length = texel count > 0)
-  std::vector<vpt_environment> envs = environments;
-  std::vector<vpt_texture>     texs = tu.textures;
+  std::vector<vpt_environment> envs = m.environments;
+  std::vector<vpt_texture>     texs = m.textures;
   for (int i = 0; i < e.num_environments; i++) envs[(size_t)e.environment_ids[i]] = e.environments[i];
   for (int i = 0; i < e.num_textures; i++) texs[(size_t)e.texture_ids[i]] = e.textures[i];
   for (int i = 0; i < d.num_environments; i++) {
@@ -72,84 +71,62 @@ int validate_edit(const DScene& d, const texture_updater& tu, const std::vector<
   return VPT_OK;
 }
 
-// a pool of `have` texels grown by `more`: allocated anew, the old texels moved device to device
-template <typename T>
-int grow_pool(std::vector<device_buffer>& tables, const T*& pool, long long have, long long more) {
-  device_buffer fresh;
-  if (int rc = fresh.allocate((size_t)(have + more) * sizeof(T))) return rc;
-  if (have > 0) HIP_TRY(hipMemcpy(fresh.get(), pool, (size_t)have * sizeof(T), hipMemcpyDeviceToDevice));
-  const void* old = pool;
-  pool = fresh.get<const T>();
-  adopt(tables, old, std::move(fresh));
-  return VPT_OK;
-}
-
 }  // namespace
 
-int launch_texel_weights(const env_light& env, float* cdf) {
+int launch_texel_weights(resident& r, const env_light& env, float* cdf) {
   const int      n      = env.cdf_len;
   const unsigned blocks = (unsigned)(((long long)n + BLOCK - 1) / BLOCK);
   if (env.is_float) hipLaunchKernelGGL(tex_weights_float_kernel, dim3(blocks), dim3(BLOCK), 0, 0, (const float4*)env.texels, env.sin_row, env.width, n, cdf);
   else hipLaunchKernelGGL(tex_weights_byte_kernel, dim3(blocks), dim3(BLOCK), 0, 0, (const uchar4*)env.texels, env.sin_row, env.width, n, cdf);
   HIP_TRY(hipGetLastError());
+  r.last_launches++;
   return VPT_OK;
 }
 
-int texture_update_apply(DScene& d, const host_mirrors& h, long long num_shape_nodes, scene_updater& u, light_updater& lu, texture_updater& tu,
-    std::vector<device_buffer>& tables, const vpt_texture_edit& e, int* light_features, bool* rebuilt) {
+int texture_update_apply(resident& r, const vpt_texture_edit& e, bool* rebuilt) {
   *rebuilt = false;
-  if (!tu.ready) {
-    tu.textures.resize((size_t)d.num_textures);
-    if (d.num_textures) HIP_TRY(hipMemcpy(tu.textures.data(), d.textures, tu.textures.size() * sizeof(vpt_texture), hipMemcpyDeviceToHost));
-    tu.ready = true;
-  }
-  const vpt_scene_edit none = {};
-  if (!u.ready)
-    if (int rc = scene_update_apply(d, h, num_shape_nodes, u, none, true)) return rc;   // the handle's mirrors, on first use
-  if (int rc = validate_edit(d, tu, u.environments, e)) return rc;   // every refusal happens here: nothing has been written
-  if (int rc = scene_update_apply(d, h, num_shape_nodes, u, none, true)) return rc;   // writes nothing: the counters start at zero
+  DScene&       d = r.d;
+  edit_mirrors& m = r.m;
+  if (int rc = validate_edit(d, m, e)) return rc;   // every refusal happens here: nothing has been written
+  if (int rc = begin_update(r)) return rc;
 
   // 1. textures: in place where the room is the same, else at the end of a pool that grows
-  std::vector<vpt_texture> textures = tu.textures;
+  std::vector<vpt_texture> textures = m.textures;
   std::vector<char>        edited((size_t)d.num_textures, 0);
   long long more_f = 0, more_b = 0;
   for (int i = 0; i < e.num_textures; i++) {
     const int          id  = e.texture_ids[i];
-    const vpt_texture& was = tu.textures[(size_t)id];
+    const vpt_texture& was = m.textures[(size_t)id];
     vpt_texture&       t   = textures[(size_t)id];
     t = e.textures[i], t.is_float = t.is_float != 0, t.offset = was.offset, edited[(size_t)id] = 1;
     if (t.width == was.width && t.height == was.height && t.is_float == (was.is_float != 0)) continue;
     long long& more = t.is_float ? more_f : more_b;
-    t.offset = (t.is_float ? tu.num_texels_f : tu.num_texels_b) + more;
+    t.offset = (t.is_float ? m.num_texels_f : m.num_texels_b) + more;
     more += (long long)t.width * t.height;
   }
   if (more_f > 0)
-    if (int rc = grow_pool(tables, d.texels_f, tu.num_texels_f, more_f)) return rc;
+    if (int rc = grow_pool(r, d.texels_f, m.num_texels_f, more_f)) return rc;
   if (more_b > 0)
-    if (int rc = grow_pool(tables, d.texels_b, tu.num_texels_b, more_b)) return rc;
-  tu.num_texels_f += more_f, tu.num_texels_b += more_b;
+    if (int rc = grow_pool(r, d.texels_b, m.num_texels_b, more_b)) return rc;
   for (int i = 0; i < e.num_textures; i++) {
     const int          id = e.texture_ids[i];
     const vpt_texture& t  = textures[(size_t)id];
     const size_t       n  = (size_t)t.width * (size_t)t.height;
-    if (n > 0) {
-      if (t.is_float) HIP_TRY(hipMemcpy(mut(d.texels_f) + t.offset, e.texels_f + 4 * e.textures[i].offset, n * sizeof(float4), hipMemcpyHostToDevice));
-      else HIP_TRY(hipMemcpy(mut(d.texels_b) + t.offset, e.texels_b + 4 * e.textures[i].offset, n * sizeof(uchar4), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(mut(d.textures) + id, &t, sizeof(vpt_texture), hipMemcpyHostToDevice));
-    u.last_bytes += (long long)(n * (t.is_float ? sizeof(float4) : sizeof(uchar4)) + sizeof(vpt_texture));
+    if (t.is_float) {
+      if (int rc = send(r, d.texels_f + t.offset, (const float4*)e.texels_f + e.textures[i].offset, n)) return rc;
+    } else if (int rc = send(r, d.texels_b + t.offset, (const uchar4*)e.texels_b + e.textures[i].offset, n)) return rc;
+    if (int rc = send(r, d.textures + id, &t, 1)) return rc;
   }
 
   // 2. environments: the entry and its inverse frame
-  const std::vector<vpt_environment> before = u.environments;
+  const std::vector<vpt_environment> before = m.environments;
   std::vector<vpt_environment> environments = before;
   for (int i = 0; i < e.num_environments; i++) {
     const int id = e.environment_ids[i];
     float4 inv[3], fwd[3];
     prep_environment_frames(e.environments[i].frame, inv, fwd);
-    HIP_TRY(hipMemcpy(mut(d.environments) + id, &e.environments[i], sizeof(vpt_environment), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(mut(d.env_inv) + 3 * (size_t)id, inv, sizeof(inv), hipMemcpyHostToDevice));
-    u.last_bytes += sizeof(vpt_environment) + sizeof(inv);
+    if (int rc = send(r, d.environments + id, &e.environments[i], 1)) return rc;
+    if (int rc = send(r, d.env_inv + 3 * (size_t)id, inv, 3)) return rc;
     environments[(size_t)id] = e.environments[i];
   }
 
@@ -189,29 +166,26 @@ int texture_update_apply(DScene& d, const host_mirrors& h, long long num_shape_n
       for (int j = 0; j < height; j++) sines.push_back(std::sin(((float)j + 0.5f) * pif / (float)height));
     }
     if (!sines.empty()) {
-      if (int rc = tu.d_sin.allocate(sines.size() * sizeof(float))) return rc;
-      HIP_TRY(hipMemcpy(tu.d_sin.get(), sines.data(), sines.size() * sizeof(float), hipMemcpyHostToDevice));
-      u.last_bytes += (long long)(sines.size() * sizeof(float));
+      if (int rc = send(r, r.d_sin, sines)) return rc;
       for (size_t k = 0; k < envs.size(); k++)
-        if (envs[k].recompute) envs[k].sin_row = tu.d_sin.get<float>() + at[k];
+        if (envs[k].recompute) envs[k].sin_row = r.d_sin.get<float>() + at[k];
     }
-    HIP_TRY(hipEventRecord(u.ev0, 0));
-    if (int rc = light_update_apply(d, h, u, lu, tables, none, light_features, rebuilt, &envs)) return rc;
-    HIP_TRY(hipEventRecord(u.ev1, 0));
-    HIP_TRY(hipEventSynchronize(u.ev1));
-    HIP_TRY(hipEventElapsedTime(&u.last_ms, u.ev0, u.ev1));
+    HIP_TRY(hipEventRecord(r.upd_ev0, 0));
+    if (int rc = light_update_apply(r, vpt_scene_edit{}, rebuilt, &envs)) return rc;   // no vertex moved
+    HIP_TRY(hipEventRecord(r.upd_ev1, 0));
+    HIP_TRY(hipEventSynchronize(r.upd_ev1));
+    HIP_TRY(hipEventElapsedTime(&r.last_ms, r.upd_ev0, r.upd_ev1));
     if (!*rebuilt)   // the list stays: of the records only the frames of a textured environment can have changed (build_lights)
       for (int l = 0; l < d.num_lights; l++) {
-        const vpt_light& lt = u.lights[(size_t)l];
-        if (lt.instance >= 0 || lt.sdf >= 0 || u.light_kind[(size_t)l] != VPT_LIGHT_ENV_TEX) continue;
+        const vpt_light& lt = m.lights[(size_t)l];
+        if (lt.instance >= 0 || lt.sdf >= 0 || m.light_kind[(size_t)l] != VPT_LIGHT_ENV_TEX) continue;
         if (!memcmp(&environments[(size_t)lt.environment].frame, &before[(size_t)lt.environment].frame, sizeof(vpt_frame))) continue;
         float4 both[6];
         prep_environment_frames(environments[(size_t)lt.environment].frame, &both[0], &both[3]);
-        HIP_TRY(hipMemcpy(mut(d.light_rec) + 8 * (size_t)l, both, sizeof(both), hipMemcpyHostToDevice));
-        u.last_bytes += sizeof(both);
+        if (int rc = send(r, d.light_rec + 8 * (size_t)l, both, 6)) return rc;
       }
   }
   HIP_TRY(hipDeviceSynchronize());
-  tu.textures = textures, u.environments = environments;
+  m.textures = textures, m.environments = environments;
   return VPT_OK;
 }

@@ -1,5 +1,6 @@
-// vpt_update_helpers.h — what the three update paths of a resident scene share (vpt_scene_update.hip, vpt_light_update.hip,
-// vpt_texture_update.hip): the checks of an edit's lists and floats, and the handling of the handle's tables.
+// vpt_update_helpers.h — what the four update paths of a resident scene share (vpt_scene_update.hip, vpt_light_update.hip,
+// vpt_texture_update.hip, vpt_volume_update.hip): the checks of an edit's lists and floats, the start of an edit, and the handling
+// of the handle's tables - counted sends, pools that grow.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -9,6 +10,7 @@
 
 #include "vpt_device_buffer.h"
 #include "vpt_error.h"
+#include "vpt_resident.h"
 
 template <typename T>
 inline T* mut(const T* p) { return const_cast<T*>(p); }   // the scene owns its tables: DScene names them const for the render kernels
@@ -29,6 +31,34 @@ inline int check_ids(const char* what, int n, const int32_t* ids, const void* pa
   }
   return VPT_OK;
 }
+// make_lights, yocto_pathtrace.cpp:990 and :1017
+inline bool emissive(const vpt_material& m) { return !(m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0); }
+inline bool emissive(const vpt_environment& e) { return !(e.emission[0] == 0 && e.emission[1] == 0 && e.emission[2] == 0); }
+
+// An edit has passed validation and is about to write: the counters of vpt_scene_update_stats start at zero, the events exist.
+inline int begin_update(resident& r) {
+  r.last_launches = 0, r.last_bytes = 0, r.last_ms = 0;
+  if (!r.upd_ev0) {
+    HIP_TRY(hipEventCreate(&r.upd_ev0));
+    HIP_TRY(hipEventCreate(&r.upd_ev1));
+  }
+  return VPT_OK;
+}
+
+// `count` entries from the host into their place in a table of the scene, counted
+template <typename T>
+inline int send(resident& r, const T* to, const T* host, size_t count) {
+  if (count) HIP_TRY(hipMemcpy(mut(to), host, count * sizeof(T), hipMemcpyHostToDevice));
+  r.last_bytes += (long long)(count * sizeof(T));
+  return VPT_OK;
+}
+// a buffer allocated for `host` and filled with it, counted
+template <typename T>
+inline int send(resident& r, device_buffer& to, const std::vector<T>& host) {
+  if (int rc = to.allocate(host.size() * sizeof(T))) return rc;
+  return send(r, to.get<const T>(), host.data(), host.size());
+}
+
 // `fresh` takes the place of the table at `old` among the scene's allocations
 inline void adopt(std::vector<device_buffer>& tables, const void* old, device_buffer&& fresh) {
   for (device_buffer& t : tables)
@@ -37,4 +67,16 @@ inline void adopt(std::vector<device_buffer>& tables, const void* old, device_bu
       return;
     }
   tables.push_back(std::move(fresh));
+}
+// a pool of `have` entries (texels, voxels) grown by `more`: allocated anew, the old entries moved device to device
+template <typename T>
+inline int grow_pool(resident& r, const T*& pool, long long& have, long long more) {
+  device_buffer fresh;
+  if (int rc = fresh.allocate((size_t)(have + more) * sizeof(T))) return rc;
+  if (have > 0) HIP_TRY(hipMemcpy(fresh.get(), pool, (size_t)have * sizeof(T), hipMemcpyDeviceToDevice));
+  const void* old = pool;
+  pool = fresh.get<const T>();
+  adopt(r.tables, old, std::move(fresh));
+  have += more;
+  return VPT_OK;
 }

@@ -32,7 +32,6 @@ __global__ void vol_region_kernel(float* __restrict__ grid, int w, int h, int lo
 
 constexpr int BLOCK = 256;
 
-bool emissive(const vpt_material& m) { return !(m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0); }   // make_lights, yocto_pathtrace.cpp:990
 // of dimensions already known to be >= 0 and to multiply to less than 2^31 (voxel_count_ok)
 long long product(const int32_t v[3]) { return (long long)v[0] * v[1] * v[2]; }
 // whd >= 0 with a product below 2^31, factor by factor: every partial product stays below 2^62, so nothing overflows on the way
@@ -48,7 +47,7 @@ bool voxel_count_ok(const int32_t v[3]) {
 }
 bool same3(const int32_t a[3], const int32_t b[3]) { return a[0] == b[0] && a[1] == b[1] && a[2] == b[2]; }
 
-int validate_edit(const DScene& d, const volume_updater& vu, const vpt_volume_edit& e) {
+int validate_edit(const DScene& d, const edit_mirrors& m, const vpt_volume_edit& e) {
   if (int rc = check_ids("vol_instance", e.num_vol_instances, e.vol_instance_ids, e.vol_instances, d.num_vol_instances)) return rc;
   if (int rc = check_ids("sdf", e.num_sdfs, e.sdf_ids, e.sdfs, d.num_sdfs)) return rc;
   if (int rc = check_ids("volume", e.num_volumes, e.volume_ids, e.volumes, d.num_volumes)) return rc;
@@ -67,7 +66,7 @@ int validate_edit(const DScene& d, const volume_updater& vu, const vpt_volume_ed
   }
   for (int i = 0; i < e.num_volumes; i++) {
     const vpt_volume_source& v   = e.volumes[i];
-    const vpt_volume&        was = vu.volumes[(size_t)e.volume_ids[i]];
+    const vpt_volume&        was = m.volumes[(size_t)e.volume_ids[i]];
     REQUIRE(std::isfinite(v.res), "edit: volume entry %d: res is not finite", i);
     REQUIRE(v.whd[0] >= 0 && v.whd[1] >= 0 && v.whd[2] >= 0, "edit: volume entry %d: negative whd (%d x %d x %d)", i, v.whd[0], v.whd[1], v.whd[2]);
     REQUIRE(voxel_count_ok(v.whd), "edit: volume entry %d: 2^31 voxels or more", i);
@@ -91,40 +90,13 @@ int validate_edit(const DScene& d, const volume_updater& vu, const vpt_volume_ed
   return VPT_OK;
 }
 
-template <typename T>
-int send(scene_updater& u, const T* to, const T* host, size_t count) {
-  if (count) HIP_TRY(hipMemcpy(mut(to), host, count * sizeof(T), hipMemcpyHostToDevice));
-  u.last_bytes += (long long)(count * sizeof(T));
-  return VPT_OK;
-}
-
-// the handle's mirrors, on first use
-int volume_update_mirrors(const DScene& d, const host_mirrors& h, long long num_shape_nodes, scene_updater& u, light_updater& lu, volume_updater& vu,
-    std::vector<device_buffer>& tables, int* light_features) {
-  const vpt_scene_edit none = {};
-  DScene& dd = const_cast<DScene&>(d);   // an empty edit writes nothing
-  if (!u.ready)
-    if (int rc = scene_update_apply(dd, h, num_shape_nodes, u, none, true)) return rc;
-  if (!lu.ready) {   // an empty edit: the mirrors (the SDFs among them) and nothing else
-    bool rebuilt = false;
-    if (int rc = light_update_apply(dd, h, u, lu, tables, none, light_features, &rebuilt)) return rc;
-  }
-  if (!vu.ready) {
-    vu.volumes.resize((size_t)d.num_volumes), vu.vol_instances.resize((size_t)d.num_vol_instances);
-    if (d.num_volumes) HIP_TRY(hipMemcpy(vu.volumes.data(), d.volumes, vu.volumes.size() * sizeof(vpt_volume), hipMemcpyDeviceToHost));
-    if (d.num_vol_instances) HIP_TRY(hipMemcpy(vu.vol_instances.data(), d.vol_instances, vu.vol_instances.size() * sizeof(vpt_volume_instance), hipMemcpyDeviceToHost));
-    vu.ready = true;
-  }
-  return VPT_OK;
-}
-
 }  // namespace
 
-int volume_update_apply(DScene& d, const host_mirrors& h, long long num_shape_nodes, scene_updater& u, light_updater& lu, volume_updater& vu,
-    std::vector<device_buffer>& tables, const vpt_volume_edit& e, int device, int* light_features, bool* rebuilt) {
+int volume_update_apply(resident& r, const vpt_volume_edit& e, bool* rebuilt) {
   *rebuilt = false;
-  if (int rc = volume_update_mirrors(d, h, num_shape_nodes, u, lu, vu, tables, light_features)) return rc;
-  if (int rc = validate_edit(d, vu, e)) return rc;
+  DScene&       d = r.d;
+  edit_mirrors& m = r.m;
+  if (int rc = validate_edit(d, m, e)) return rc;
   // the bakes' host half and their uploads into buffers of their own: a tree that is too deep is refused here, the scene untouched
   std::vector<std::unique_ptr<bake_job>> bakes((size_t)(e.num_volumes > 0 ? e.num_volumes : 0));
   for (int i = 0; i < e.num_volumes; i++) {
@@ -132,45 +104,37 @@ int volume_update_apply(DScene& d, const host_mirrors& h, long long num_shape_no
     char entry[64];
     snprintf(entry, sizeof(entry), "edit: volume entry %d: bake", i);
     bakes[(size_t)i] = std::make_unique<bake_job>();
-    if (int rc = bake_prepare(device, e.volumes[i].bake, entry, *bakes[(size_t)i])) return rc;
+    if (int rc = bake_prepare(r.device, e.volumes[i].bake, entry, *bakes[(size_t)i])) return rc;
   }
-  const vpt_scene_edit none = {};
-  if (int rc = scene_update_apply(d, h, num_shape_nodes, u, none, true)) return rc;   // writes nothing: the counters start at zero
+  if (int rc = begin_update(r)) return rc;
 
   // 1. volumes: in place where whd stays, else at the end of a pool that grows
-  std::vector<vpt_volume> volumes = vu.volumes;
+  std::vector<vpt_volume> volumes = m.volumes;
   long long more = 0;
   for (int i = 0; i < e.num_volumes; i++) {
     const vpt_volume_source& src = e.volumes[i];
     vpt_volume&              v   = volumes[(size_t)e.volume_ids[i]];
     const bool regrown = !same3(src.whd, v.whd);
     memcpy(v.whd, src.whd, sizeof(v.whd)), v.res = src.res;
-    if (regrown) v.offset = vu.num_voxels + more, more += product(src.whd);
+    if (regrown) v.offset = m.num_voxels + more, more += product(src.whd);
   }
-  if (more > 0) {
-    device_buffer fresh;
-    if (int rc = fresh.allocate((size_t)(vu.num_voxels + more) * sizeof(float))) return rc;
-    if (vu.num_voxels > 0) HIP_TRY(hipMemcpy(fresh.get(), d.voxels, (size_t)vu.num_voxels * sizeof(float), hipMemcpyDeviceToDevice));
-    const void* old = d.voxels;
-    d.voxels = fresh.get<const float>();
-    adopt(tables, old, std::move(fresh));
-    vu.num_voxels += more;
-  }
+  if (more > 0)
+    if (int rc = grow_pool(r, d.voxels, m.num_voxels, more)) return rc;
   device_buffer stage;   // the edit's voxels on their way into the pool: gone when the call returns (it ends with the device idle)
   if (e.num_voxels > 0) {
     if (int rc = stage.allocate((size_t)e.num_voxels * sizeof(float))) return rc;
     HIP_TRY(hipMemcpy(stage.get(), e.voxels, (size_t)e.num_voxels * sizeof(float), hipMemcpyHostToDevice));
   }
-  HIP_TRY(hipEventRecord(u.ev0, 0));
+  HIP_TRY(hipEventRecord(r.upd_ev0, 0));
   for (int i = 0; i < e.num_volumes; i++) {
     const vpt_volume_source& src = e.volumes[i];
     const vpt_volume&        v   = volumes[(size_t)e.volume_ids[i]];
     float* grid = mut(d.voxels) + v.offset;
     if (src.offset == -1) {
-      const bake_region r = {{src.region_lo[0], src.region_lo[1], src.region_lo[2]},
+      const bake_region region = {{src.region_lo[0], src.region_lo[1], src.region_lo[2]},
           {src.region_lo[0] + src.region_whd[0], src.region_lo[1] + src.region_whd[1], src.region_lo[2] + src.region_whd[2]}, src.mode};
-      if (int rc = bake_launch(*bakes[(size_t)i], src.bake, grid, &r, &u.last_launches)) return rc;
-      u.last_bytes += bakes[(size_t)i]->bytes;
+      if (int rc = bake_launch(*bakes[(size_t)i], src.bake, grid, &region, &r.last_launches)) return rc;
+      r.last_bytes += bakes[(size_t)i]->bytes;
       continue;
     }
     const long long n = product(src.region_whd);
@@ -178,43 +142,43 @@ int volume_update_apply(DScene& d, const host_mirrors& h, long long num_shape_no
     hipLaunchKernelGGL(vol_region_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, 0, grid, v.whd[0], v.whd[1], src.region_lo[0], src.region_lo[1],
         src.region_lo[2], src.region_whd[0], src.region_whd[1], (unsigned)n, src.mode, stage.get<float>() + src.offset);
     HIP_TRY(hipGetLastError());
-    u.last_launches++, u.last_bytes += n * (long long)sizeof(float);
+    r.last_launches++, r.last_bytes += n * (long long)sizeof(float);
   }
-  HIP_TRY(hipEventRecord(u.ev1, 0));
+  HIP_TRY(hipEventRecord(r.upd_ev1, 0));
 
   // 2. the small tables as the edit leaves them, and every record from them
-  std::vector<vpt_volume_instance> vol_instances = vu.vol_instances;
-  std::vector<vpt_sdf>             sdfs          = lu.sdfs;
+  std::vector<vpt_volume_instance> vol_instances = m.vol_instances;
+  std::vector<vpt_sdf>             sdfs          = m.sdfs;
   std::vector<char>                resized((size_t)d.num_sdfs, 0);
   bool lights_differ = false;
   for (int i = 0; i < e.num_vol_instances; i++) vol_instances[(size_t)e.vol_instance_ids[i]] = e.vol_instances[i];
   for (int i = 0; i < e.num_sdfs; i++) {
     vpt_sdf& f = sdfs[(size_t)e.sdf_ids[i]];
-    const bool was_lit = emissive(u.materials[(size_t)f.material]), lit = emissive(u.materials[(size_t)e.sdfs[i].material]);
+    const bool was_lit = emissive(m.materials[(size_t)f.material]), lit = emissive(m.materials[(size_t)e.sdfs[i].material]);
     resized[(size_t)e.sdf_ids[i]] = memcmp(f.whd, e.sdfs[i].whd, 8) != 0;   // the CDF entry is whd.x * whd.y
     lights_differ = lights_differ || was_lit != lit || (lit && resized[(size_t)e.sdf_ids[i]]);
     f = e.sdfs[i];
   }
   for (int i = 0; i < e.num_volumes; i++)
-    if (int rc = send(u, d.volumes + e.volume_ids[i], &volumes[(size_t)e.volume_ids[i]], 1)) return rc;
+    if (int rc = send(r, d.volumes + e.volume_ids[i], &volumes[(size_t)e.volume_ids[i]], 1)) return rc;
   for (int i = 0; i < e.num_vol_instances; i++)
-    if (int rc = send(u, d.vol_instances + e.vol_instance_ids[i], &e.vol_instances[i], 1)) return rc;
+    if (int rc = send(r, d.vol_instances + e.vol_instance_ids[i], &e.vol_instances[i], 1)) return rc;
   for (int i = 0; i < e.num_sdfs; i++)
-    if (int rc = send(u, d.sdfs + e.sdf_ids[i], &e.sdfs[i], 1)) return rc;
+    if (int rc = send(r, d.sdfs + e.sdf_ids[i], &e.sdfs[i], 1)) return rc;
   std::vector<float4> sdf_inv, fn_rec, grid_rec;
   prep_sdf_records(sdfs.data(), d.num_sdfs, volumes.data(), vol_instances.data(), d.num_vol_instances, sdf_inv, fn_rec, grid_rec, d);
-  if (int rc = send(u, d.sdf_inv, sdf_inv.data(), sdf_inv.size())) return rc;
-  if (int rc = send(u, d.sdf_fn_rec, fn_rec.data(), fn_rec.size())) return rc;
-  if (int rc = send(u, d.sdf_grid_rec, grid_rec.data(), grid_rec.size())) return rc;
-  vu.volumes = volumes, vu.vol_instances = vol_instances, lu.sdfs = sdfs;
+  if (int rc = send(r, d.sdf_inv, sdf_inv.data(), sdf_inv.size())) return rc;
+  if (int rc = send(r, d.sdf_fn_rec, fn_rec.data(), fn_rec.size())) return rc;
+  if (int rc = send(r, d.sdf_grid_rec, grid_rec.data(), grid_rec.size())) return rc;
+  m.volumes = volumes, m.vol_instances = vol_instances, m.sdfs = sdfs;
 
   // 3. the lights: only when the SDF lights of the edited scene are others, or one of them has another whd
   if (lights_differ) {
-    if (int rc = light_update_apply(d, h, u, lu, tables, none, light_features, rebuilt, nullptr, &resized)) return rc;
-    HIP_TRY(hipEventRecord(u.ev1, 0));
+    if (int rc = light_update_apply(r, vpt_scene_edit{}, rebuilt, nullptr, &resized)) return rc;   // no vertex moved
+    HIP_TRY(hipEventRecord(r.upd_ev1, 0));
   }
-  HIP_TRY(hipEventSynchronize(u.ev1));
-  HIP_TRY(hipEventElapsedTime(&u.last_ms, u.ev0, u.ev1));
+  HIP_TRY(hipEventSynchronize(r.upd_ev1));
+  HIP_TRY(hipEventElapsedTime(&r.last_ms, r.upd_ev0, r.upd_ev1));
   HIP_TRY(hipDeviceSynchronize());
   return VPT_OK;
 }
