@@ -315,7 +315,8 @@ typedef struct vpt_scene_edit {
 } vpt_scene_edit;
 int vpt_scene_update(vpt_scene* scene, const vpt_scene_edit* edit);
 /* The BVHs as the device holds them now, in the reference's layout (the descriptor's scene_bvh_nodes / shape_bvh_nodes): for
- * callers that keep a host copy, and for the tests.  *_capacity in nodes, at least the descriptor's counts; a null array is skipped. */
+ * callers that keep a host copy, and for the tests.  *_capacity in nodes, at least the current counts (vpt_scene_get_bvh_counts; the
+ * descriptor's for a handle that vpt_scene_rebuild_bvh never touched); a null array is skipped. */
 int vpt_scene_get_bvh(vpt_scene* scene, vpt_bvh_node* scene_nodes, int scene_capacity, vpt_bvh_node* shape_nodes, int64_t shape_capacity);
 /* What the last vpt_scene_update on this handle cost (measurements, tests): kernel launches, bytes of payload sent to the device, and
  * the time between two events on the device's null stream, one recorded before the first and one after the last launch of the refit -
@@ -486,6 +487,50 @@ int vpt_scene_get_volumes(vpt_scene* scene, vpt_volume* volumes, int volume_capa
 /* the voxels of one volume as the device holds them (x + y*W + z*W*H); capacity in voxels, at least the volume's W*H*D */
 int vpt_scene_get_voxels(vpt_scene* scene, int volume, float* voxels, int64_t capacity);
 
+/* ---- the BVHs of a resident scene built anew on the device ------------------------------------------------------------
+ * The four edits above keep a tree's topology as creation left it: vpt_scene_update is the reference's update_bvh, a refit.  After a
+ * real deformation, or after instances have been rearranged, boxes and renders stay correct but the tree no longer fits the geometry.
+ * vpt_scene_rebuild_bvh is the reference's make_bvh (yocto_bvh.cpp:526-611) for a scene that lives on a GPU.
+ * After the call every table on the device holds the bytes vpt_scene_create would upload for a descriptor that satisfies three
+ * conditions:
+ *  - The named shapes' shape_bvh_nodes / shape_bvh_prims are what the reference's make_bvh builds from the shape's current vertices
+ *    on the device.  The element boxes are those of yocto_bvh.cpp:537-549 (point_bounds, line_bounds, triangle_bounds, quad_bounds,
+ *    with the select-form min / max of vpt_scene_update).  The build is build_bvh(..., highquality = false): split_middle, at most
+ *    four primitives per leaf, node ids in the reference's creation order, libstdc++'s std::partition - the rule of vpt_build_bvh.
+ *  - The scene BVH is what make_bvh builds over transform_bbox(frame, shape root box) of the current instances, ALL of them, in
+ *    instance order.  An instance of a shape without nodes gets invalidb3f, as in yocto_bvh.cpp:601-603.
+ *  - The shape node pool and the quad-node pool are laid out contiguously in shape order, as the host's flatten lays them out.  The
+ *    node counts change, so node_offset, num_nodes, the quad-node offset and the root reference of every later shape follow.
+ * So renders, vpt_intersect, vpt_kat, vpt_scene_get_bvh and vpt_scene_light_tables_hash give the bits of a fresh handle made from
+ * that descriptor.  Element counts stay: a shape has exactly as many leaf slots before and after; its records move to their new slots.
+ *  - what->scene non-zero builds the scene BVH anew; it is forced when num_shapes > 0, as make_bvh would.  num_shapes == 0 and
+ *    scene == 0 is valid and does nothing.
+ *  - Refusals.  Validation comes first: a null argument, an id out of range or an id repeated gives VPT_ERR_INVALID_ARG.  The
+ *    traversal limits vpt_scene_create decides are decided anew from the new trees, by the same function: the 256-entry LDS stack of
+ *    the binary walk, the packed pop floor of the quad traversal, 2^27 quad nodes; a tree past them gives VPT_ERR_UNSUPPORTED.  A
+ *    refused call leaves the scene exactly as it was: everything is built into new buffers, and pointers, counts and mirrors are
+ *    swapped only after the last check.  A device failure after validation (VPT_ERR_HIP) leaves the handle good for
+ *    vpt_scene_destroy only, as in vpt_scene_update.
+ *  - The stack sizes of the handle follow the new trees: the HBM part of the traversal stacks may appear, grow or go.
+ *    VPT_STACK_LDS and VPT_DEBUG are read as at creation.  The next vpt_scene_update makes its refit tables anew.
+ *  - What crosses PCIe: down, the new node arrays (32 B per node of the shape pool and of the scene BVH) and primitive orders (4 B
+ *    per element of a named shape and per instance); up, the tables that depend on topology alone, made on the host from that one
+ *    read-back by the functions of vpt_scene_create (quad nodes, 128 B each; the integer words of the enter records, 96 B per
+ *    instance; the slot of every instance; the shape records, 80 B each).  No vertex, leaf record or element box crosses.
+ *    vpt_scene_update_stats reports the launches, the bytes of both directions in one sum, and the device time of the call.
+ *  - Synchronisation and the forgetting of the launch-schedule record: those of vpt_scene_update. */
+typedef struct vpt_bvh_rebuild {
+  int32_t num_shapes; const int32_t* shape_ids;  /* shape BVHs to build anew; ids in range, none repeated */
+  int32_t scene;                                 /* non-zero: build the scene BVH anew; forced when num_shapes > 0, as make_bvh would */
+} vpt_bvh_rebuild;
+int vpt_scene_rebuild_bvh(vpt_scene* scene, const vpt_bvh_rebuild* what);
+/* The node counts as the device holds them now: what vpt_scene_get_bvh's capacities must reach (for a handle that was never rebuilt,
+ * the descriptor's counts).  shape_node_offsets: per shape, the first node of its BVH in the pool; may be NULL. */
+int vpt_scene_get_bvh_counts(vpt_scene* scene, int32_t* scene_nodes, int64_t* shape_nodes, int64_t* shape_node_offsets /* per shape, may be NULL */);
+/* The primitive orders as the device holds them now: the scene's (one entry per scene-BVH slot: num_instances after a rebuild) and the
+ * shapes', pooled at each shape's element offset (the element id in every leaf slot).  Capacities in entries; a null array is skipped. */
+int vpt_scene_get_bvh_prims(vpt_scene* scene, int32_t* scene_prims, int capacity, int32_t* shape_prims, int64_t shape_capacity);
+
 /* ---- the drop-in for pathtrace_samples() --------------------------------------------
  * Host, row-major (idx = j*width + i) caller-owned state, exactly pathtrace_state
  * (yocto_pathtrace.h:57-64): image float4[w*h], hits int32[w*h], rng {u64 state, u64 inc}[w*h].
@@ -531,6 +576,8 @@ int  vpt_multi_update_lights(vpt_multi* m, const vpt_scene_edit* edit);
 int  vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit);
 /* vpt_scene_update_volumes in the same way (a bake entry is prepared and baked once per device) */
 int  vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit);
+/* vpt_scene_rebuild_bvh in the same way: every device builds its own trees; the arrays are equal by construction */
+int  vpt_multi_rebuild_bvh(vpt_multi* m, const vpt_bvh_rebuild* what);
 int  vpt_multi_device_count(const vpt_multi* m);
 /* how vpt_multi_get_render moves the parts: "rccl", "peer-copy" (several devices, no RCCL) or "local" (one device) */
 const char* vpt_multi_transport(const vpt_multi* m);
@@ -781,6 +828,8 @@ int  vpt_session_edit_lights(vpt_session* session, const vpt_scene_edit* edit);
 int  vpt_session_edit_textures(vpt_session* session, const vpt_texture_edit* edit);
 /* vpt_scene_update_volumes, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_edit_volumes(vpt_session* session, const vpt_volume_edit* edit);
+/* vpt_scene_rebuild_bvh, then a reset (the picture is the same, its accumulation restarts as after the session's other edits); a refused call leaves the session as it was */
+int  vpt_session_rebuild_bvh(vpt_session* session, const vpt_bvh_rebuild* what);
 int  vpt_session_get_display(vpt_session* session, uint8_t* rgba8, float* display_f);
 int  vpt_session_get_image(vpt_session* session, float* linear);
 int  vpt_session_get_denoised(vpt_session* session, float* linear);

@@ -143,6 +143,27 @@ class VptBakeStats(C.Structure):  # vpt_bake_stats
                 ("device_ms", C.c_float)]
 
 
+class VptBvhRebuild(C.Structure):  # vpt_bvh_rebuild
+    _fields_ = [("num_shapes", C.c_int32), ("shape_ids", C.POINTER(C.c_int32)), ("scene", C.c_int32)]
+
+
+class BvhRebuild:
+    """What vpt_scene_rebuild_bvh takes (include/vpt.h: vpt_bvh_rebuild): the shapes whose BVHs are built anew, and whether the scene
+    BVH is (it is whenever a shape is named).  HostScene.rebuild_bvh makes one; DeviceScene.rebuild_bvh / MultiDeviceScene.rebuild_bvh /
+    RenderSession.rebuild_bvh apply it."""
+
+    def __init__(self, shapes=(), scene: bool = True):
+        self.shapes, self.scene = tuple(int(i) for i in shapes), bool(scene)
+
+    def empty(self) -> bool:
+        return not self.shapes and not self.scene
+
+    def to_abi(self):
+        """(VptBvhRebuild, the array it points into: keep it alive across the call)"""
+        ids = (C.c_int32 * max(1, len(self.shapes)))(*self.shapes)
+        return VptBvhRebuild(len(self.shapes), C.cast(ids, C.POINTER(C.c_int32)) if self.shapes else None, int(self.scene)), ids
+
+
 class SceneEdit:
     """What vpt_scene_update takes (include/vpt.h: vpt_scene_edit), as dictionaries id -> value: cameras (VptCamera), instances and
     environments ((12,) float32 frames x, y, z, o), materials (VptMaterial), shapes ((positions, normals or None) as (n, 3) float32).
@@ -388,6 +409,11 @@ hip.vpt_scene_get_lights.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int), _p, C.
 hip.vpt_scene_light_tables_hash.argtypes = [_p, _p]
 hip.vpt_scene_get_media.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 hip.vpt_scene_get_bvh.argtypes = [_p, _p, C.c_int, _p, C.c_int64]
+hip.vpt_scene_rebuild_bvh.argtypes = [_p, C.POINTER(VptBvhRebuild)]
+hip.vpt_multi_rebuild_bvh.argtypes = [_p, C.POINTER(VptBvhRebuild)]
+hip.vpt_session_rebuild_bvh.argtypes = [_p, C.POINTER(VptBvhRebuild)]
+hip.vpt_scene_get_bvh_counts.argtypes = [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _p]
+hip.vpt_scene_get_bvh_prims.argtypes = [_p, _p, C.c_int, _p, C.c_int64]
 hip.vpt_scene_update_stats.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
 hip.vpt_render.argtypes = [_p, C.POINTER(VptParams), C.c_int, C.c_int, C.c_int, _p, _p, _p, C.POINTER(C.c_int)]
 hip.vpt_layout_slots.argtypes = [C.POINTER(VptLayout)]
@@ -468,6 +494,7 @@ host.vpth_scene_get_item.argtypes = [_p, C.c_int, C.c_int, _p, C.c_int64]
 host.vpth_scene_get_item.restype = C.c_int64
 host.vpth_scene_set_item.argtypes = [_p, C.c_int, C.c_int, _p, C.c_int64, C.c_char_p, C.c_int]
 host.vpth_scene_update_bvh.argtypes = [_p, C.c_char_p, C.c_int]
+host.vpth_scene_rebuild_bvh.argtypes = [_p, _p, C.c_int, C.c_int, C.c_char_p, C.c_int]
 host.vpth_scene_update_lights.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_free.restype = None
 host.vpth_scene_get_environment.argtypes = [_p, C.c_int, C.POINTER(VptEnvironment)]
@@ -873,6 +900,20 @@ class HostScene:
             raise VptError(err.value.decode())
         return edit
 
+    def rebuild_bvh(self, shapes=None, scene: bool = True) -> "BvhRebuild":
+        """make_bvh of the reference again, on the scene as it is now, for the shapes named (ids; "all": every shape; None: none) and
+        - `scene`, or whenever a shape is named - for the scene BVH: topology, node counts and primitive orders change; desc / stats()
+        describe the rebuilt scene afterwards.  A pending edit is handed out with update_bvh() first.  Returns the BvhRebuild for
+        DeviceScene.rebuild_bvh."""
+        if getattr(self, "_edit", None) is not None and not self._edit.empty():
+            raise VptError("rebuild_bvh: hand the pending edit out with update_bvh() first")
+        ids = list(range(self.count("shapes"))) if isinstance(shapes, str) and shapes == "all" else [int(i) for i in (shapes or ())]
+        arr = np.ascontiguousarray(ids, np.int32)
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_rebuild_bvh(self.handle, arr.ctypes.data if len(arr) else None, len(arr), int(bool(scene)), err, len(err)) != 0:
+            raise VptError(err.value.decode())
+        return BvhRebuild(ids, scene)
+
     # -- environments and textures (the host side of vpt_scene_update_textures): the setters change the scene and note the change in
     #    the pending TextureEdit; desc, lights() and stats() follow at update_textures(), which hands that edit out ----------------
     def environment(self, index: int) -> VptEnvironment:
@@ -1078,6 +1119,12 @@ class HostScene:
         grab = lambda ptr, n: np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (n * 32,)).view(BVH_NODE).copy() if n else np.zeros(0, BVH_NODE)
         return grab(d.scene_bvh_nodes, d.num_scene_bvh_nodes), grab(d.shape_bvh_nodes, d.num_shape_bvh_nodes)
 
+    def bvh_prims(self):
+        """(scene primitive order, pooled shape primitive orders) of the descriptor as int32 arrays (copies)"""
+        d = VptSceneDescBvh.from_address(self.desc + VptSceneDescBvh.OFFSET)
+        grab = lambda ptr, n: np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int32)), (n,)).copy() if n else np.zeros(0, np.int32)
+        return grab(d.scene_bvh_prims, d.num_scene_bvh_prims), grab(d.shape_bvh_prims, d.num_shape_bvh_prims)
+
     def make_state(self, params: PathtraceParams) -> PathtraceState:
         """make_state, yocto_pathtrace.cpp:960-980"""
         w, h = C.c_int(), C.c_int()
@@ -1229,10 +1276,33 @@ class DeviceScene:
         _check(hip.vpt_scene_light_tables_hash(self.handle, out.ctypes.data), "vpt_scene_light_tables_hash")
         return tuple(int(x) for x in out)
 
+    def rebuild_bvh(self, rebuild: "BvhRebuild") -> None:
+        """vpt_scene_rebuild_bvh (include/vpt.h): the named shapes' BVHs and the scene BVH built anew on the device from what is
+        resident.  Afterwards the handle renders the bits of a DeviceScene made from the host scene after the same
+        HostScene.rebuild_bvh()."""
+        abi, keep = rebuild.to_abi()
+        _check(hip.vpt_scene_rebuild_bvh(self.handle, C.byref(abi)), "vpt_scene_rebuild_bvh")
+        del keep
+
+    def get_bvh_counts(self):
+        """(scene nodes, pooled shape nodes, first node of every shape as int64) as the device holds them (vpt_scene_get_bvh_counts)"""
+        a, b = C.c_int32(0), C.c_int64(0)
+        offsets = np.zeros(max(1, self.host_scene.count("shapes")), np.int64)
+        _check(hip.vpt_scene_get_bvh_counts(self.handle, C.byref(a), C.byref(b), offsets.ctypes.data), "vpt_scene_get_bvh_counts")
+        return a.value, b.value, offsets[:self.host_scene.count("shapes")]
+
     def get_bvh(self):
-        """(scene nodes, pooled shape nodes) as the device holds them, BVH_NODE arrays (vpt_scene_get_bvh)"""
-        a, b = self.host_scene.bvh_nodes()
+        """(scene nodes, pooled shape nodes) as the device holds them, BVH_NODE arrays at the current counts (vpt_scene_get_bvh)"""
+        na, nb, _ = self.get_bvh_counts()
+        a, b = np.zeros(na, BVH_NODE), np.zeros(nb, BVH_NODE)
         _check(hip.vpt_scene_get_bvh(self.handle, a.ctypes.data, len(a), b.ctypes.data, len(b)), "vpt_scene_get_bvh")
+        return a, b
+
+    def get_bvh_prims(self):
+        """(scene primitive order, pooled shape primitive orders) as the device holds them, int32 (vpt_scene_get_bvh_prims)"""
+        _, shape_prims = self.host_scene.bvh_prims()   # element counts never change: the pooled size is the descriptor's
+        a, b = np.zeros(self.host_scene.count("instances"), np.int32), np.zeros(len(shape_prims), np.int32)
+        _check(hip.vpt_scene_get_bvh_prims(self.handle, a.ctypes.data, len(a), b.ctypes.data, len(b)), "vpt_scene_get_bvh_prims")
         return a, b
 
     def update_stats(self):
@@ -1334,6 +1404,12 @@ class MultiDeviceScene:
         """vpt_multi_update_volumes: DeviceScene.update_volumes with the same edit on every device"""
         abi, keep = edit.to_abi()
         _check(hip.vpt_multi_update_volumes(self.handle, C.byref(abi)), "vpt_multi_update_volumes")
+        del keep
+
+    def rebuild_bvh(self, rebuild: "BvhRebuild") -> None:
+        """vpt_multi_rebuild_bvh: DeviceScene.rebuild_bvh on every device (each builds its own trees: equal by construction)"""
+        abi, keep = rebuild.to_abi()
+        _check(hip.vpt_multi_rebuild_bvh(self.handle, C.byref(abi)), "vpt_multi_rebuild_bvh")
         del keep
 
     def pathtrace_samples(self, state: PathtraceState, params: PathtraceParams, count: int = 1) -> None:
@@ -1635,6 +1711,12 @@ class RenderSession:
         """edit() through vpt_scene_update_volumes, with the VolumeEdit of HostScene.update_volumes()"""
         abi, keep = edit.to_abi()
         _check(hip.vpt_session_edit_volumes(self.handle, C.byref(abi)), "vpt_session_edit_volumes")
+        del keep
+
+    def rebuild_bvh(self, rebuild: "BvhRebuild") -> None:
+        """vpt_scene_rebuild_bvh on the session's scene with the BvhRebuild of HostScene.rebuild_bvh(), then a reset"""
+        abi, keep = rebuild.to_abi()
+        _check(hip.vpt_session_rebuild_bvh(self.handle, C.byref(abi)), "vpt_session_rebuild_bvh")
         del keep
 
     @property

@@ -21,6 +21,9 @@
 //    pre(X) = internal nodes visited before X: pre(right) = pre(P) + 1, pre(left) = pre(P) + 1 + icount(right), and the
 //    children of X sit at 1 + 2 pre(X), 2 + 2 pre(X).  Two sweeps over the levels (up for icount, down for pre).
 //
+// Two parts: bvh_build_core (vpt_bvh_build.h) takes boxes that are on the device and leaves nodes and primitive order there -
+// vpt_scene_rebuild_bvh (vpt_bvh_rebuild.hip) runs it on boxes made from a resident scene - and vpt_build_bvh wraps it with the
+// copies from and to the host.
 // Work per level: O(n) threads, a handful of 64-bit atomics per live primitive, one rocPRIM scan.  The host reads back
 // one counter per level (the number of nodes the level created).
 #include <hip/hip_runtime.h>
@@ -30,6 +33,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "vpt_bvh_build.h"
 #include "vpt_device_buffer.h"
 #include "vpt_error.h"
 
@@ -59,10 +63,11 @@ __device__ __forceinline__ unsigned long long max_key(float f, int pos) { return
 __device__ __forceinline__ int min_pos(unsigned long long k) { return (int)(0xffffffffu - (unsigned)(k & 0xffffffffull)); }
 __device__ __forceinline__ int max_pos(unsigned long long k) { return (int)(k & 0xffffffffull); }
 
-__global__ void k_centers(int n, const float* __restrict__ bb, float* __restrict__ ctr) {
+// (bb: box p = the six floats at bb + stride * p)
+__global__ void k_centers(int n, const float* __restrict__ bb, int stride, float* __restrict__ ctr) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  for (int c = 0; c < 3; c++) ctr[3 * i + c] = (bb[6 * i + c] + bb[6 * i + 3 + c]) / 2;   // center(bbox), yocto_geometry.h: (min + max) / 2
+  for (int c = 0; c < 3; c++) ctr[3 * i + c] = (bb[(size_t)stride * i + c] + bb[(size_t)stride * i + 3 + c]) / 2;   // center(bbox), yocto_geometry.h: (min + max) / 2
 }
 __global__ void k_init(int n, int* prims, int* node_of) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -90,7 +95,7 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
   }
   return v;
 }
-__global__ void k_bounds(int n, const int* __restrict__ prims, const int* __restrict__ node_of, const float* __restrict__ bb,
+__global__ void k_bounds(int n, const int* __restrict__ prims, const int* __restrict__ node_of, const float* __restrict__ bb, int stride,
     const float* __restrict__ ctr, tkeys* keys) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   int t = i < n ? node_of[i] : -1;
@@ -101,8 +106,8 @@ __global__ void k_bounds(int n, const int* __restrict__ prims, const int* __rest
   if (t >= 0) {
     int p = prims[i];
     for (int c = 0; c < 3; c++) {
-      k[c]     = min_key(bb[6 * p + c], i);
-      k[3 + c] = max_key(bb[6 * p + 3 + c], i);
+      k[c]     = min_key(bb[(size_t)stride * p + c], i);
+      k[3 + c] = max_key(bb[(size_t)stride * p + 3 + c], i);
       k[6 + c] = min_key(ctr[3 * p + c], i);
       k[9 + c] = max_key(ctr[3 * p + c], i);
     }
@@ -119,14 +124,14 @@ __global__ void k_bounds(int n, const int* __restrict__ prims, const int* __rest
   }
 }
 // the node's box (bits of the winning elements) and split_middle's choice of axis and plane
-__global__ void k_decide(int lb, int le, tnode* nodes, const tkeys* keys, const int* __restrict__ prims, const float* __restrict__ bb,
+__global__ void k_decide(int lb, int le, tnode* nodes, const tkeys* keys, const int* __restrict__ prims, const float* __restrict__ bb, int stride,
     const float* __restrict__ ctr, float* boxes) {
   int t = lb + blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= le) return;
   tnode& nd = nodes[t];
   for (int c = 0; c < 3; c++) {
-    boxes[6 * t + c]     = bb[6 * prims[min_pos(keys[t].k[c])] + c];
-    boxes[6 * t + 3 + c] = bb[6 * prims[max_pos(keys[t].k[3 + c])] + 3 + c];
+    boxes[6 * t + c]     = bb[(size_t)stride * prims[min_pos(keys[t].k[c])] + c];
+    boxes[6 * t + 3 + c] = bb[(size_t)stride * prims[max_pos(keys[t].k[3 + c])] + 3 + c];
   }
   nd.child = -1, nd.axis = 0, nd.swap = 0, nd.mid = (nd.start + nd.end) / 2, nd.split = 0;
   if (nd.end - nd.start <= BVH_MAX_PRIMS) return;   // a leaf
@@ -224,46 +229,55 @@ __global__ void k_emit(int count, const tnode* __restrict__ nodes, const float* 
   out[id] = o;
 }
 
+vpt_bvh_node empty_root() {   // the reference's root of an empty build: an invalid box, a leaf without primitives
+  vpt_bvh_node o;
+  for (int c = 0; c < 3; c++) o.bbox_min[c] = 3.402823466e+38f, o.bbox_max[c] = -3.402823466e+38f;
+  o.start = 0, o.num = 0, o.axis = 0, o.internal = 0;
+  return o;
+}
+
 }  // namespace
 
-extern "C" int vpt_build_bvh(int device, const float* bboxes, int n, vpt_bvh_node* nodes_out, int capacity, int* num_nodes, int* primitives) {
-  if (n < 0 || !nodes_out || !num_nodes || (n > 0 && (!bboxes || !primitives))) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
-  if (capacity < (n > 0 ? 2 * n - 1 : 1)) return vpt_set_error(VPT_ERR_INVALID_ARG, "node capacity %d < %d (2 n - 1)", capacity, n > 0 ? 2 * n - 1 : 1);
-  if (n == 0) {   // the reference's root of an empty build: an invalid box, a leaf without primitives
-    vpt_bvh_node o;
-    for (int c = 0; c < 3; c++) o.bbox_min[c] = 3.402823466e+38f, o.bbox_max[c] = -3.402823466e+38f;
-    o.start = 0, o.num = 0, o.axis = 0, o.internal = 0;
-    nodes_out[0] = o, *num_nodes = 1;
+int bvh_build_scratch::reserve(int max_boxes) {
+  if (max_boxes <= reserved) return VPT_OK;
+  reserved = -1;
+  const size_t n = (size_t)(max_boxes > 0 ? max_boxes : 1), cap = 2 * n;
+  if (ctr.allocate(3 * n * sizeof(float)) || boxes.allocate(6 * cap * sizeof(float)) || prims.allocate(n * sizeof(int)) || node_of.allocate(n * sizeof(int)) ||
+      flag.allocate((n + 1) * sizeof(int)) || tscan.allocate((n + 1) * sizeof(int)) || partner.allocate(n * sizeof(int)) || counter.allocate(sizeof(int)) ||
+      tnodes.allocate(cap * sizeof(tnode)) || keys.allocate(cap * sizeof(tkeys)) || out.allocate(cap * sizeof(vpt_bvh_node)))
+    return VPT_ERR_HIP;
+  scan_bytes = 0;   // of the largest scan; rocPRIM's need does not shrink with the size
+  HIP_TRY(rocprim::exclusive_scan((void*)nullptr, scan_bytes, flag.get<int>(), tscan.get<int>(), 0, n + 1, rocprim::plus<int>()));
+  if (int rc = scan_temp.allocate(scan_bytes)) return rc;
+  reserved = max_boxes;
+  return VPT_OK;
+}
+
+int bvh_build_core(bvh_build_scratch& s, const float* bb, int stride, int n, int* count_out, int* launches) {
+  if (n < 0 || stride < 6 || !count_out || (n > 0 && !bb)) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
+  if (int rc = s.reserve(n)) return rc;
+  vpt_bvh_node* out = s.out.get<vpt_bvh_node>();
+  if (n == 0) {
+    const vpt_bvh_node o = empty_root();
+    HIP_TRY(hipMemcpy(out, &o, sizeof(o), hipMemcpyHostToDevice));
+    *count_out = 1;
     return VPT_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return vpt_set_error(VPT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return vpt_set_error(VPT_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  HIP_TRY(hipSetDevice(device));
-
-  const size_t  cap = 2 * (size_t)n;
-  device_buffer d_bb, d_ctr, d_boxes, d_prims, d_node_of, d_flag, d_tscan, d_partner, d_counter, d_nodes, d_keys, d_out, d_scan_temp;   // freed on every exit path
-  if (d_bb.allocate(6 * (size_t)n * sizeof(float)) || d_ctr.allocate(3 * (size_t)n * sizeof(float)) || d_boxes.allocate(6 * cap * sizeof(float)) ||
-      d_prims.allocate((size_t)n * sizeof(int)) || d_node_of.allocate((size_t)n * sizeof(int)) || d_flag.allocate(((size_t)n + 1) * sizeof(int)) ||
-      d_tscan.allocate(((size_t)n + 1) * sizeof(int)) || d_partner.allocate((size_t)n * sizeof(int)) || d_counter.allocate(sizeof(int)) ||
-      d_nodes.allocate(cap * sizeof(tnode)) || d_keys.allocate(cap * sizeof(tkeys)) || d_out.allocate(cap * sizeof(vpt_bvh_node)))
-    return VPT_ERR_HIP;
-  float *bb = d_bb.get<float>(), *ctr = d_ctr.get<float>(), *boxes = d_boxes.get<float>();
-  int *  prims = d_prims.get<int>(), *node_of = d_node_of.get<int>(), *flag = d_flag.get<int>(), *tscan = d_tscan.get<int>(), *partner = d_partner.get<int>(), *counter = d_counter.get<int>();
-  tnode* nodes = d_nodes.get<tnode>();
-  tkeys* keys  = d_keys.get<tkeys>();
-  vpt_bvh_node* out = d_out.get<vpt_bvh_node>();
-  size_t scan_bytes = 0;
-  HIP_TRY(rocprim::exclusive_scan((void*)nullptr, scan_bytes, flag, tscan, 0, (size_t)n + 1, rocprim::plus<int>()));
-  if (int rc = d_scan_temp.allocate(scan_bytes)) return rc;
-  char* scan_temp = d_scan_temp.get<char>();
+  const size_t cap = 2 * (size_t)n;
+  float *ctr = s.ctr.get<float>(), *boxes = s.boxes.get<float>();
+  int *  prims = s.prims.get<int>(), *node_of = s.node_of.get<int>(), *flag = s.flag.get<int>(), *tscan = s.tscan.get<int>(), *partner = s.partner.get<int>(), *counter = s.counter.get<int>();
+  tnode* nodes = s.tnodes.get<tnode>();
+  tkeys* keys  = s.keys.get<tkeys>();
+  char*  scan_temp = s.scan_temp.get<char>();
+  size_t scan_bytes = s.scan_bytes;
+  int    launched = 0;
 
   const int  TB = 256;
   const dim3 gn((n + TB - 1) / TB), gn1((n + 1 + TB - 1) / TB);
   auto blocks = [&](int count) { return dim3((count + TB - 1) / TB); };
-  HIP_TRY(hipMemcpy(bb, bboxes, 6 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_centers, gn, dim3(TB), 0, 0, n, bb, ctr);
+  hipLaunchKernelGGL(k_centers, gn, dim3(TB), 0, 0, n, bb, stride, ctr);
   hipLaunchKernelGGL(k_init, gn, dim3(TB), 0, 0, n, prims, node_of);
+  launched += 2;
   tnode root = {0, n, -1, 0, -1, 0, 0, 0, 0.0f, 0, 0};
   HIP_TRY(hipMemcpy(nodes, &root, sizeof(root), hipMemcpyHostToDevice));
   int count = 1;
@@ -275,16 +289,17 @@ extern "C" int vpt_build_bvh(int device, const float* bboxes, int n, vpt_bvh_nod
     if (level_begin.size() > 4096) return vpt_set_error(VPT_ERR_HIP, "BVH build did not terminate");
     int ln = le - lb;
     hipLaunchKernelGGL(k_reset_keys, blocks(ln), dim3(TB), 0, 0, lb, le, keys);
-    hipLaunchKernelGGL(k_bounds, gn, dim3(TB), 0, 0, n, prims, node_of, bb, ctr, keys);
-    hipLaunchKernelGGL(k_decide, blocks(ln), dim3(TB), 0, 0, lb, le, nodes, keys, prims, bb, ctr, boxes);
+    hipLaunchKernelGGL(k_bounds, gn, dim3(TB), 0, 0, n, prims, node_of, bb, stride, ctr, keys);
+    hipLaunchKernelGGL(k_decide, blocks(ln), dim3(TB), 0, 0, lb, le, nodes, keys, prims, bb, stride, ctr, boxes);
     hipLaunchKernelGGL(k_flags, gn1, dim3(TB), 0, 0, n, prims, node_of, nodes, ctr, flag);
     HIP_TRY(rocprim::exclusive_scan((void*)scan_temp, scan_bytes, flag, tscan, 0, (size_t)n + 1, rocprim::plus<int>()));
     hipLaunchKernelGGL(k_children, blocks(ln), dim3(TB), 0, 0, lb, le, nodes, tscan, counter);
     hipLaunchKernelGGL(k_partners, gn, dim3(TB), 0, 0, n, node_of, nodes, flag, tscan, partner);
     hipLaunchKernelGGL(k_swap, gn, dim3(TB), 0, 0, n, prims, node_of, nodes, flag, tscan, partner);
+    launched += 8;   // (the scan counted as one)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(&count, counter, 4, hipMemcpyDeviceToHost));   // also the level's barrier for the host
-    if ((size_t)count > cap) return vpt_set_error(VPT_ERR_HIP, "BVH build produced %d nodes for %d primitives", count, n);
+    if (count < le || (size_t)count > cap) return vpt_set_error(VPT_ERR_HIP, "BVH build produced %d nodes for %d primitives", count, n);
     lb = le, le = count;
     level_begin.push_back(lb);
   }
@@ -292,16 +307,46 @@ extern "C" int vpt_build_bvh(int device, const float* bboxes, int n, vpt_bvh_nod
   const int nlevels = (int)level_begin.size() - 1;
   for (int l = nlevels - 1; l >= 0; l--) {
     int a = level_begin[l], b = level_begin[l + 1];
-    if (b > a) hipLaunchKernelGGL(k_icount, blocks(b - a), dim3(TB), 0, 0, a, b, nodes);
+    if (b <= a) continue;
+    hipLaunchKernelGGL(k_icount, blocks(b - a), dim3(TB), 0, 0, a, b, nodes);
+    launched++;
   }
   for (int l = 0; l < nlevels; l++) {
     int a = level_begin[l], b = level_begin[l + 1];
-    if (b > a) hipLaunchKernelGGL(k_pre, blocks(b - a), dim3(TB), 0, 0, a, b, nodes);
+    if (b <= a) continue;
+    hipLaunchKernelGGL(k_pre, blocks(b - a), dim3(TB), 0, 0, a, b, nodes);
+    launched++;
   }
   hipLaunchKernelGGL(k_emit, blocks(count), dim3(TB), 0, 0, count, nodes, boxes, out);
+  launched++;
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(nodes_out, out, (size_t)count * sizeof(vpt_bvh_node), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(primitives, prims, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipDeviceSynchronize());
+  *count_out = count;
+  if (launches) *launches += launched;
+  return VPT_OK;
+}
+
+extern "C" int vpt_build_bvh(int device, const float* bboxes, int n, vpt_bvh_node* nodes_out, int capacity, int* num_nodes, int* primitives) {
+  if (n < 0 || !nodes_out || !num_nodes || (n > 0 && (!bboxes || !primitives))) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");
+  if (capacity < (n > 0 ? 2 * n - 1 : 1)) return vpt_set_error(VPT_ERR_INVALID_ARG, "node capacity %d < %d (2 n - 1)", capacity, n > 0 ? 2 * n - 1 : 1);
+  if (n == 0) {
+    nodes_out[0] = empty_root(), *num_nodes = 1;
+    return VPT_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return vpt_set_error(VPT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+  if (device < 0 || device >= ndev) return vpt_set_error(VPT_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
+  HIP_TRY(hipSetDevice(device));
+
+  device_buffer     d_bb;   // freed, like the scratch, on every exit path
+  bvh_build_scratch s;
+  if (int rc = d_bb.allocate(6 * (size_t)n * sizeof(float))) return rc;
+  if (int rc = s.reserve(n)) return rc;
+  HIP_TRY(hipMemcpy(d_bb.get(), bboxes, 6 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  int count = 0;
+  if (int rc = bvh_build_core(s, d_bb.get<float>(), 6, n, &count)) return rc;
+  HIP_TRY(hipMemcpy(nodes_out, s.nodes(), (size_t)count * sizeof(vpt_bvh_node), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(primitives, s.primitives(), (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   *num_nodes = count;
   return VPT_OK;
 }

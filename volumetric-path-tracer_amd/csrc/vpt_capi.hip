@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "vpt_adaptive.h"
+#include "vpt_bvh_rebuild.h"
 #include "vpt_device_buffer.h"
 #include "vpt_error.h"
 #include "vpt_kat.h"
@@ -525,6 +526,41 @@ int vpt_scene_get_bvh(vpt_scene* s, vpt_bvh_node* scene_nodes, int scene_capacit
   HIP_TRY(hipDeviceSynchronize());
   if (scene_nodes && s->d.num_scene_nodes) HIP_TRY(hipMemcpy(scene_nodes, s->d.scene_nodes, (size_t)s->d.num_scene_nodes * sizeof(vpt_bvh_node), hipMemcpyDeviceToHost));
   if (shape_nodes && s->num_shape_nodes) HIP_TRY(hipMemcpy(shape_nodes, s->d.shape_nodes, (size_t)s->num_shape_nodes * sizeof(vpt_bvh_node), hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+
+// the BVHs built anew (vpt_bvh_rebuild.hip); the render side follows: stack sizes, the HBM part of the stacks, light_prims
+int vpt_scene_rebuild_bvh(vpt_scene* s, const vpt_bvh_rebuild* what) {
+  if (!s || !what) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call replaces
+  bvh_rebuild_stacks st;
+  if (int rc = bvh_rebuild_apply(*s, *what, st)) return rc;
+  if (!st.rebuilt) return VPT_OK;
+  if (st.stack_spill4 != s->stack_spill4) s->spill_lanes = 0;   // the HBM part is sized per entry: made anew by the next launch
+  s->stack_cap = st.stack_cap, s->stack_lds4 = st.stack_lds4, s->stack_spill4 = st.stack_spill4;
+  if (int rc = light_setup(s)) return rc;   // light_prims read the leaf records, which have moved
+  s->sched.forget();
+  return VPT_OK;
+}
+int vpt_scene_get_bvh_counts(vpt_scene* s, int32_t* scene_nodes, int64_t* shape_nodes, int64_t* shape_node_offsets) {
+  if (!s || !scene_nodes || !shape_nodes) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  *scene_nodes = s->d.num_scene_nodes, *shape_nodes = s->num_shape_nodes;
+  if (shape_node_offsets)
+    for (int i = 0; i < s->d.num_shapes; i++) shape_node_offsets[i] = s->m.shapes[(size_t)i].node_offset;
+  return VPT_OK;
+}
+// the shapes' order is read from the leaf records themselves (the element id in p0.w of every slot): what the traversal reports
+int vpt_scene_get_bvh_prims(vpt_scene* s, int32_t* scene_prims, int capacity, int32_t* shape_prims, int64_t shape_capacity) {
+  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  const long long slots = (long long)s->h.prim_slot.size();
+  REQUIRE(!scene_prims || capacity >= s->d.num_scene_prims, "capacity %d < %d scene bvh primitives", capacity, s->d.num_scene_prims);
+  REQUIRE(!shape_prims || shape_capacity >= slots, "shape_capacity %lld < %lld shape bvh primitives", (long long)shape_capacity, slots);
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (scene_prims && s->d.num_scene_prims) HIP_TRY(hipMemcpy(scene_prims, s->d.scene_prims, (size_t)s->d.num_scene_prims * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (shape_prims && slots)
+    HIP_TRY(hipMemcpy2D(shape_prims, sizeof(int32_t), (const char*)s->d.leaf_prims + 12, 4 * sizeof(float4), sizeof(int32_t), (size_t)slots, hipMemcpyDeviceToHost));
   return VPT_OK;
 }
 

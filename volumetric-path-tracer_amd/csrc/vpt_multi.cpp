@@ -345,6 +345,13 @@ int vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit) {
   return VPT_OK;
 }
 
+int vpt_multi_rebuild_bvh(vpt_multi* m, const vpt_bvh_rebuild* what) {
+  if (!m || !what) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  for (auto& p : m->parts)   // as vpt_multi_update: every device holds the same scene, so the first one's refusal is everyone's
+    if (int rc = vpt_scene_rebuild_bvh(p.scene, what)) return rc;
+  return VPT_OK;
+}
+
 int vpt_multi_device_count(const vpt_multi* m) { return m ? (int)m->parts.size() : 0; }
 
 const char* vpt_multi_transport(const vpt_multi* m) { return !m ? "" : m->use_rccl ? "rccl" : m->parts.size() > 1 ? "peer-copy" : "local"; }

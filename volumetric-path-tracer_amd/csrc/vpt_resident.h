@@ -1,5 +1,5 @@
 // vpt_resident.h — the part of a vpt_scene that the edits of a resident scene work on (include/vpt.h: vpt_scene_update, _lights,
-// _textures, _volumes): the tables on the device, their host mirrors, and what an edit keeps between calls.  vpt_capi.hip's
+// _textures, _volumes, and vpt_scene_rebuild_bvh): the tables on the device, their host mirrors, and what an edit keeps between calls.  vpt_capi.hip's
 // vpt_scene is a `resident` plus its render side (schedule, staging, stacks); the four update units see only this.
 #pragma once
 #include <vector>
@@ -15,7 +15,8 @@ struct bvh_levels {
 };
 
 // What a refit needs beyond the scene's own tables.  The one thing built late: by the first edit of a handle that moves an
-// instance or a vertex (vpt_scene_update.hip), from the node arrays the device holds - topology never changes - and kept.
+// instance or a vertex (vpt_scene_update.hip), from the node arrays the device holds, and kept until the topology changes:
+// vpt_scene_rebuild_bvh (vpt_bvh_rebuild.hip) clears `ready`, and the next refit makes them from the new trees.
 struct refit_tables {
   bool ready = false;
   bvh_levels              scene_levels;

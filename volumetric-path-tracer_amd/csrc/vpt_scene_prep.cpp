@@ -350,65 +350,6 @@ void build_geometry(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_t
   }
 }
 
-// quad nodes of every BVH, the shapes' roots and stack needs, and the traversal stacks sized from them.  The stack sizes and the
-// VPT_FLOOR_SHIFT check depend on the trees' topology only: vpt_scene_update refits boxes and keeps topology, so they stay valid.
-int build_quad_nodes_and_stacks(const vpt_scene_desc& d, scene_tables& t) {
-  std::vector<float4> shape_wnodes;
-  int max_shape_depth = 0, max_shape_need4 = 0;
-  for (int i = 0; i < d.num_shapes; i++) {
-    const vpt_shape& sh = d.shapes[i];
-    DShape& o = t.shapes[i];
-    o.wnode_offset = (int)(shape_wnodes.size() / 8);
-    int need4 = 0;
-    o.root_ref     = build_quad_nodes(d.shape_bvh_nodes + sh.bvh_node_offset, sh.num_bvh_nodes, shape_wnodes, o.root_box, &need4);
-    int depth = o.num_nodes ? bvh_depth(d.shape_bvh_nodes + sh.bvh_node_offset, sh.num_bvh_nodes, 0, 0, 4096) : 0;
-    o.stack_need = depth + 2;
-    if (depth > max_shape_depth) max_shape_depth = depth;
-    if (need4 > max_shape_need4) max_shape_need4 = need4;
-  }
-  DScene& D = t.d;
-  int scene_depth = d.num_scene_bvh_nodes ? bvh_depth(d.scene_bvh_nodes, d.num_scene_bvh_nodes, 0, 0, 4096) : 0;
-  float scene_box[6];
-  int scene_need4 = 0;
-  D.scene_root_ref = build_quad_nodes(d.scene_bvh_nodes, d.num_scene_bvh_nodes, t.wnodes, scene_box, &scene_need4);
-  D.scene_root_lo_x = scene_box[0], D.scene_root_lo_y = scene_box[1], D.scene_root_lo_z = scene_box[2];
-  D.scene_root_hi_x = scene_box[3], D.scene_root_hi_y = scene_box[4], D.scene_root_hi_z = scene_box[5];
-  // stack entries alive at once: one pending sibling per level (+ the two just pushed), scene level
-  // entries stay below the entries of the instance being traversed
-  int need = (scene_depth + 2) + (max_shape_depth + 2);
-  t.stack_cap = ((need > 8 ? need : 8) + 3) & ~3;
-  const int max_stack_cap = 64 * 1024 / (VPT_BLOCK * (int)sizeof(int));   // 256 entries with VPT_BLOCK = 64
-  if (t.stack_cap > max_stack_cap)
-    return vpt_set_error(VPT_ERR_UNSUPPORTED, "BVH depth %d (scene %d + shapes %d) needs a %d-entry traversal stack; the LDS stack holds %d",
-                need, scene_depth, max_shape_depth, t.stack_cap, max_stack_cap);
-  // quad-node traversal: worst case = three pending siblings per quad level of the scene BVH plus of the
-  // deepest shape BVH, plus one free entry above the top (the branch-free push stores rejected candidates
-  // there).  24 entries per lane = 12 KB per wave keep twelve waves on a CU (144 of 160 KB); whatever the
-  // worst case needs beyond that lives in HBM (lane_stack2<true>).
-  int need4 = scene_need4 + max_shape_need4 + 1;
-  // the group form of the node phase (vpt_mesh_kernel.hip.h: group_nodes) hands a ray's pop floor - the stack depth at instance entry, at
-  // most scene_need4 - to its helper lanes in the bits above VPT_FLOOR_SHIFT of one word: every stack position has to fit there
-  if ((long long)need4 > (0x7fffffffLL >> VPT_FLOOR_SHIFT))
-    return vpt_set_error(VPT_ERR_UNSUPPORTED, "quad stack need %d does not fit the traversal's packed pop floor", need4);
-  // With the mesh kernel's five parked words per lane (vpt_mesh_kernel.hip.h) a wave takes need4 * 512 + 1280 + 8 bytes of LDS,
-  // granted in 1 280-byte steps: up to 22 entries twelve waves fit a CU's 160 KB, with 23 or 24 eleven do - still better than the
-  // checked push / pop of the HBM-overflow variant (-7 %), which is for deeper trees only (22 entries in LDS, the rest in HBM).
-  t.stack_lds4 = need4 < 8 ? 8 : need4 > 24 ? 22 : need4;
-  if (const char* e = getenv("VPT_STACK_LDS")) {   // tuning experiments: force a smaller LDS part (the rest spills to HBM)
-    int v = atoi(e);
-    if (v >= 4 && v < t.stack_lds4) t.stack_lds4 = v;
-  }
-  t.stack_spill4 = need4 > t.stack_lds4 ? need4 - t.stack_lds4 : 0;
-  if (getenv("VPT_DEBUG"))
-    fprintf(stderr, "[vpt] binary depth scene %d shape %d; quad stack need scene %d + shape %d + 1 -> %d in LDS + %d in HBM\n",
-        scene_depth, max_shape_depth, scene_need4, max_shape_need4, t.stack_lds4, t.stack_spill4);
-  // one table: [scene quad nodes][shape quad nodes]
-  t.scene_wnodes = t.wnodes.size();
-  if ((t.scene_wnodes + shape_wnodes.size()) / 8 >= (1ull << 27)) return vpt_set_error(VPT_ERR_UNSUPPORTED, "more than 2^27 quad nodes");
-  t.wnodes.insert(t.wnodes.end(), shape_wnodes.begin(), shape_wnodes.end());
-  return VPT_OK;
-}
-
 // instance records, the enter records of the scene-BVH slots, and the inverse frames of environments
 void build_instances(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_tables& t) {
   t.instances.resize((size_t)d.num_instances);
@@ -434,11 +375,8 @@ void build_instances(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_
     // (vpt_scene_update.hip rewrites e0..e2, the root box and translation_only of a resident scene in place: keep the two in step)
     e[0] = in.inv[0], e[1] = in.inv[1], e[2] = in.inv[2];
     e[3] = make_float4(sh.root_box[0], sh.root_box[1], sh.root_box[2], sh.root_box[3]);
-    // the quad nodes of all BVHs live in one array, the scene's first: a level is named by the index of its first node
-    int tail[6] = {sh.root_ref, (int)(t.scene_wnodes / 8) + sh.wnode_offset, sh.leaf_offset, id, in.translation_only, sh.num_nodes};
     e[4] = make_float4(sh.root_box[4], sh.root_box[5], 0, 0);
-    memcpy(&e[4].z, &tail[0], 8);
-    memcpy(&e[5], &tail[2], 16);
+    prep_enter_tail(e, sh, (int)(t.scene_wnodes / 8), id, in.translation_only);
     t.h.slot_of[(size_t)id] = k;
   }
   t.env_inv.resize((size_t)d.num_environments * 3);
@@ -685,6 +623,73 @@ void prep_sdf_records(const vpt_sdf* sdfs, int num_sdfs, const vpt_volume* volum
   }
 }
 
+void prep_enter_tail(float4* e, const DShape& sh, int scene_quads, int instance, int translation_only) {
+  // the quad nodes of all BVHs live in one array, the scene's first: a level is named by the index of its first node
+  int tail[6] = {sh.root_ref, scene_quads + sh.wnode_offset, sh.leaf_offset, instance, translation_only, sh.num_nodes};
+  memcpy(&e[4].z, &tail[0], 8);
+  memcpy(&e[5], &tail[2], 16);
+}
+
+// quad nodes of every BVH, the shapes' roots and stack needs, and the traversal stacks sized from them.  The stack sizes and the
+// VPT_FLOOR_SHIFT check depend on the trees' topology only: vpt_scene_update refits boxes and keeps topology, so they stay valid;
+// vpt_scene_rebuild_bvh (vpt_bvh_rebuild.hip) changes topology and calls this again, on the node arrays it built (vpt_scene_prep.h).
+int prep_quad_nodes_and_stacks(const vpt_scene_desc& d, scene_tables& t) {
+  std::vector<float4> shape_wnodes;
+  int max_shape_depth = 0, max_shape_need4 = 0;
+  for (int i = 0; i < d.num_shapes; i++) {
+    const vpt_shape& sh = d.shapes[i];
+    DShape& o = t.shapes[i];
+    o.wnode_offset = (int)(shape_wnodes.size() / 8);
+    int need4 = 0;
+    o.root_ref     = build_quad_nodes(d.shape_bvh_nodes + sh.bvh_node_offset, sh.num_bvh_nodes, shape_wnodes, o.root_box, &need4);
+    int depth = o.num_nodes ? bvh_depth(d.shape_bvh_nodes + sh.bvh_node_offset, sh.num_bvh_nodes, 0, 0, 4096) : 0;
+    o.stack_need = depth + 2;
+    if (depth > max_shape_depth) max_shape_depth = depth;
+    if (need4 > max_shape_need4) max_shape_need4 = need4;
+  }
+  DScene& D = t.d;
+  int scene_depth = d.num_scene_bvh_nodes ? bvh_depth(d.scene_bvh_nodes, d.num_scene_bvh_nodes, 0, 0, 4096) : 0;
+  float scene_box[6];
+  int scene_need4 = 0;
+  D.scene_root_ref = build_quad_nodes(d.scene_bvh_nodes, d.num_scene_bvh_nodes, t.wnodes, scene_box, &scene_need4);
+  D.scene_root_lo_x = scene_box[0], D.scene_root_lo_y = scene_box[1], D.scene_root_lo_z = scene_box[2];
+  D.scene_root_hi_x = scene_box[3], D.scene_root_hi_y = scene_box[4], D.scene_root_hi_z = scene_box[5];
+  // stack entries alive at once: one pending sibling per level (+ the two just pushed), scene level
+  // entries stay below the entries of the instance being traversed
+  int need = (scene_depth + 2) + (max_shape_depth + 2);
+  t.stack_cap = ((need > 8 ? need : 8) + 3) & ~3;
+  const int max_stack_cap = 64 * 1024 / (VPT_BLOCK * (int)sizeof(int));   // 256 entries with VPT_BLOCK = 64
+  if (t.stack_cap > max_stack_cap)
+    return vpt_set_error(VPT_ERR_UNSUPPORTED, "BVH depth %d (scene %d + shapes %d) needs a %d-entry traversal stack; the LDS stack holds %d",
+                need, scene_depth, max_shape_depth, t.stack_cap, max_stack_cap);
+  // quad-node traversal: worst case = three pending siblings per quad level of the scene BVH plus of the
+  // deepest shape BVH, plus one free entry above the top (the branch-free push stores rejected candidates
+  // there).  24 entries per lane = 12 KB per wave keep twelve waves on a CU (144 of 160 KB); whatever the
+  // worst case needs beyond that lives in HBM (lane_stack2<true>).
+  int need4 = scene_need4 + max_shape_need4 + 1;
+  // the group form of the node phase (vpt_mesh_kernel.hip.h: group_nodes) hands a ray's pop floor - the stack depth at instance entry, at
+  // most scene_need4 - to its helper lanes in the bits above VPT_FLOOR_SHIFT of one word: every stack position has to fit there
+  if ((long long)need4 > (0x7fffffffLL >> VPT_FLOOR_SHIFT))
+    return vpt_set_error(VPT_ERR_UNSUPPORTED, "quad stack need %d does not fit the traversal's packed pop floor", need4);
+  // With the mesh kernel's five parked words per lane (vpt_mesh_kernel.hip.h) a wave takes need4 * 512 + 1280 + 8 bytes of LDS,
+  // granted in 1 280-byte steps: up to 22 entries twelve waves fit a CU's 160 KB, with 23 or 24 eleven do - still better than the
+  // checked push / pop of the HBM-overflow variant (-7 %), which is for deeper trees only (22 entries in LDS, the rest in HBM).
+  t.stack_lds4 = need4 < 8 ? 8 : need4 > 24 ? 22 : need4;
+  if (const char* e = getenv("VPT_STACK_LDS")) {   // tuning experiments: force a smaller LDS part (the rest spills to HBM)
+    int v = atoi(e);
+    if (v >= 4 && v < t.stack_lds4) t.stack_lds4 = v;
+  }
+  t.stack_spill4 = need4 > t.stack_lds4 ? need4 - t.stack_lds4 : 0;
+  if (getenv("VPT_DEBUG"))
+    fprintf(stderr, "[vpt] binary depth scene %d shape %d; quad stack need scene %d + shape %d + 1 -> %d in LDS + %d in HBM\n",
+        scene_depth, max_shape_depth, scene_need4, max_shape_need4, t.stack_lds4, t.stack_spill4);
+  // one table: [scene quad nodes][shape quad nodes]
+  t.scene_wnodes = t.wnodes.size();
+  if ((t.scene_wnodes + shape_wnodes.size()) / 8 >= (1ull << 27)) return vpt_set_error(VPT_ERR_UNSUPPORTED, "more than 2^27 quad nodes");
+  t.wnodes.insert(t.wnodes.end(), shape_wnodes.begin(), shape_wnodes.end());
+  return VPT_OK;
+}
+
 void prep_quad_slots(const vpt_bvh_node* nodes, int count, std::vector<int>& slots) {
   std::vector<int> order, quad_of;
   quad_order(nodes, count, order, quad_of);
@@ -706,7 +711,7 @@ int prepare_scene(const vpt_scene_desc& d, const vpt_scene_curves* curves, scene
   D.num_lights = d.num_lights, D.num_scene_nodes = d.num_scene_bvh_nodes, D.num_scene_prims = d.num_scene_bvh_prims;
   D.group_forms = getenv("VPT_NO_GROUP_FORMS") ? 0 : 1;   // A/B switch of the tests: the two forms of a phase must give the same bits
   build_geometry(d, cs, t);
-  if (int rc = build_quad_nodes_and_stacks(d, t)) return rc;
+  if (int rc = prep_quad_nodes_and_stacks(d, t)) return rc;
   build_instances(d, cs, t);
   // sRGB decode LUT: byte_to_float then srgb_to_rgb, yocto_color.h:212-227, evaluated with the host powf
   t.srgb_lut.resize(256);

@@ -76,6 +76,16 @@ void prep_instance_frames(const vpt_frame& frame, float4 inv[3], float4 fwd[3], 
 void prep_environment_frames(const vpt_frame& frame, float4 inv[3], float4 fwd[3]);
 int  prep_check_material(const vpt_material& m, int index, int num_textures, bool textured);
 void prep_quad_slots(const vpt_bvh_node* nodes, int count, std::vector<int>& slots);
+// What hangs on the TOPOLOGY of the BVHs, for vpt_scene_create and for vpt_scene_rebuild_bvh (vpt_bvh_rebuild.hip), which calls it with a
+// descriptor that carries nothing but the node arrays it built: the quad nodes of every BVH (out.wnodes: the scene's, out.scene_wnodes
+// float4s, then the shapes' in shape order), wnode_offset / root_ref / root_box / stack_need of every out.shapes[i], out.d.scene_root_*,
+// and the stack sizes out.stack_cap / stack_lds4 / stack_spill4 (VPT_STACK_LDS and VPT_DEBUG are read here).  Reads of `desc`:
+// num_shapes, shapes[i].bvh_node_offset / num_bvh_nodes, shape_bvh_nodes, scene_bvh_nodes, num_scene_bvh_nodes; of `out`: shapes[i].num_nodes.
+// VPT_ERR_UNSUPPORTED for trees past a traversal limit: the 256-entry LDS stack, the packed pop floor, 2^27 quad nodes.
+int prep_quad_nodes_and_stacks(const vpt_scene_desc& desc, scene_tables& out);
+// the integer words of the enter record `e` (6 float4) of the scene-BVH slot that holds `instance`: e4.zw = root_ref, first quad node of
+// the shape in the one quad-node array (scene_quads = the scene BVH's own); e5 = leaf_offset, instance, translation_only, num_nodes
+void prep_enter_tail(float4* e, const DShape& shape, int scene_quads, int instance, int translation_only);
 // Whether the medium behind some instance is more than a function of its material (vpt_device.h: medium records): a material of a
 // volumetric type with a colour, emission or scattering texture or on a shape with vertex colours - or more materials than the
 // path state's 16-bit id holds.  Such scenes render with K1's general instance, which carries the medium in registers.

@@ -130,6 +130,18 @@ __global__ void upd_refit_shape_leaves_kernel(float4* __restrict__ nodes, long l
   for (int k = 0; k < num; k++) b = merge(b, record_bounds(leaf_prims + 4 * (leaf_offset + start + k)));
   store_node_box(nodes, base + i, b);
 }
+// the bounds of a shape's elements in ELEMENT order, the input of a rebuild (vpt_bvh_rebuild.hip), from its leaf records: slot k holds
+// element p0.w; old_slot[element] = k, the map the rebuild gathers the records through
+__global__ void upd_element_boxes_kernel(const float4* __restrict__ leaf_prims, long long leaf_offset, int num_elems, float* __restrict__ boxes, int* __restrict__ old_slot) {
+  int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= num_elems) return;
+  const float4* r = leaf_prims + 4 * (leaf_offset + k);
+  const int e = __float_as_int(r[0].w);
+  if (e < 0 || e >= num_elems) return;   // (creation checked the primitive order)
+  const box3 b = record_bounds(r);
+  for (int c = 0; c < 3; c++) boxes[6 * (long long)e + c] = b.lo[c], boxes[6 * (long long)e + 3 + c] = b.hi[c];
+  old_slot[e] = k;
+}
 // leaves of the scene BVH: the instances' boxes through scene_prims
 __global__ void upd_refit_scene_leaves_kernel(float4* __restrict__ nodes, int count, const int* __restrict__ prims, const float4* __restrict__ inst_box) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -396,6 +408,28 @@ int refit_internal_levels(resident& u, float4* nodes, long long base, const bvh_
 }
 
 }  // namespace
+
+// the pieces a rebuild shares with the refit (vpt_scene_update.h), on the tables the caller names
+int upd_element_boxes(resident& r, const DShape& sh, float* boxes, int* old_slot) {
+  LAUNCH(r, upd_element_boxes_kernel, sh.num_elems, r.d.leaf_prims, (long long)sh.leaf_offset, sh.num_elems, boxes, old_slot);
+  return VPT_OK;
+}
+int upd_shape_roots(resident& r, DShape* shapes, const float4* shape_nodes) {
+  LAUNCH(r, upd_shape_roots_kernel, r.d.num_shapes, shapes, r.d.num_shapes, shape_nodes);
+  return VPT_OK;
+}
+int upd_instance_boxes(resident& r, const DShape* shapes, float4* inst_box) {
+  LAUNCH(r, upd_instance_boxes_kernel, r.d.num_instances, r.d.instances, r.d.num_instances, shapes, inst_box);
+  return VPT_OK;
+}
+int upd_enter_records(resident& r, float4* enter, int slots, const DShape* shapes) {
+  LAUNCH(r, upd_enter_records_kernel, slots, enter, slots, r.d.instances, shapes);
+  return VPT_OK;
+}
+int upd_light_records(resident& r, const DShape* shapes) {
+  LAUNCH(r, upd_light_records_kernel, r.d.num_lights, mut(r.d.light_rec), r.d.lights, r.d.num_lights, r.d.instances, shapes);
+  return VPT_OK;
+}
 
 int scene_update_apply(resident& r, const vpt_scene_edit& e, bool lights) {
   if (int rc = validate_edit(r, e, lights)) return rc;   // every refusal happens here: nothing has been written

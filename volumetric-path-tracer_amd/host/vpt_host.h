@@ -179,6 +179,10 @@ bvh_scene        make_bvh_device(const scene_data& scene, const pathtrace_params
 // make_bvh.  An instance of a shape without nodes gets invalidb3f as in make_bvh (the reference reads nodes[0] of an empty vector).
 // The device counterpart is vpt_scene_update (include/vpt.h).
 void             update_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& updated_instances, const vector<int>& updated_shapes);
+// make_bvh again for part of a scene (the host side of vpt_scene_rebuild_bvh, include/vpt.h): the named shapes' BVHs from their current
+// vertices, then - `scene_level`, forced when a shape is named - the scene BVH over the current instances and roots.  Throws
+// std::invalid_argument for a shape id out of range or repeated.
+void             rebuild_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& shapes, bool scene_level);
 // build_bvh over `n` boxes {min.xyz, max.xyz} on the host (what make_bvh runs per shape and for the instances)
 bvh_data         build_bvh_host(const float* bboxes, int n);
 pathtrace_lights make_lights(const scene_data& scene, const pathtrace_params& params);

@@ -232,6 +232,22 @@ int vpth_scene_update_bvh(void* hh, char* err, int errlen) {
     return set_error(err, errlen, e.what()), -1;
   }
 }
+// rebuild_bvh (make_bvh again for the named shapes and, `scene` non-zero or a shape named, for the scene level) on the CURRENT host
+// scene, then the flattened descriptor again (its address changes): the host side of vpt_scene_rebuild_bvh
+int vpth_scene_rebuild_bvh(void* hh, const int32_t* shape_ids, int n, int scene, char* err, int errlen) {
+  try {
+    auto& h = *(host_scene*)hh;
+    if (n < 0 || (n > 0 && !shape_ids)) return set_error(err, errlen, "null or negative shape list"), -1;
+    rebuild_bvh(h.bvh, h.scene, vector<int>(shape_ids, shape_ids + n), scene != 0);
+    for (auto i = 0; i < n; i++) h.edited_shapes.erase(shape_ids[i]);   // their boxes are current
+    auto flat = std::make_unique<flat_scene>();
+    flatten_scene(*flat, h.scene, h.bvh, h.lights);
+    h.flat = std::move(flat);
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
+}
 // make_lights of the scene as the setters left it (an emission switched on or off, an emitter's vertices moved), then the flattened
 // descriptor again: the host side of vpt_scene_update_lights.  The BVHs are vpth_scene_update_bvh's business.
 int vpth_scene_update_lights(void* hh, char* err, int errlen) {

@@ -234,6 +234,19 @@ void update_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& upda
   for (auto shape : updated_shapes) refit_nodes(bvh.shapes.at(shape), shape_bboxes(scene.shapes.at(shape)));
   refit_nodes(bvh, instance_bboxes(scene, bvh));
 }
+void rebuild_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& shapes, bool scene_level) {
+  auto seen = vector<char>(scene.shapes.size(), 0);
+  for (auto shape : shapes) {
+    if (shape < 0 || shape >= (int)scene.shapes.size()) throw std::invalid_argument{"rebuild_bvh: shape id out of range"};
+    if (seen[(size_t)shape]) throw std::invalid_argument{"rebuild_bvh: shape id repeated"};
+    seen[(size_t)shape] = 1;
+  }
+  for (auto shape : shapes) bvh.shapes[(size_t)shape] = make_shape_bvh(scene.shapes[(size_t)shape], -1);
+  if (!scene_level && shapes.empty()) return;
+  auto top = bvh_data{};
+  build_nodes(top, instance_bboxes(scene, bvh));
+  bvh.nodes = std::move(top.nodes), bvh.primitives = std::move(top.primitives);
+}
 bvh_scene make_bvh(const scene_data& scene, const pathtrace_params&) { return make_bvh_on(-1, scene); }
 bvh_scene make_bvh_device(const scene_data& scene, const pathtrace_params&, int device) {
   if (device < 0) throw std::invalid_argument{"make_bvh_device: negative device"};
