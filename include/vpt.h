@@ -531,6 +531,59 @@ int vpt_scene_get_bvh_counts(vpt_scene* scene, int32_t* scene_nodes, int64_t* sh
  * shapes', pooled at each shape's element offset (the element id in every leaf slot).  Capacities in entries; a null array is skipped. */
 int vpt_scene_get_bvh_prims(vpt_scene* scene, int32_t* scene_prims, int capacity, int32_t* shape_prims, int64_t shape_capacity);
 
+/* ---- instances of a resident scene added, removed and re-pointed on the device ------------------------------------------
+ * The edits above keep the set of instances as creation left it.  vpt_scene_update_instances changes it: the instance table changes
+ * length and numbering, and everything keyed by an instance id follows.  Shapes, elements, materials, textures, volumes and SDFs stay.
+ * After the call every table on the device holds the bytes vpt_scene_create would upload for a descriptor that satisfies three
+ * conditions:
+ *  - Instances.  The old list with the `set` entries replaced (frame, shape and material), the removed entries erased and the added
+ *    ones appended in the order given.  Survivors keep their relative order and the ids close up, exactly as
+ *    scene.instances.erase + push_back would leave the reference's scene_data.
+ *  - Scene BVH.  What make_bvh (build_bvh, highquality = false; the rule of vpt_build_bvh) builds over transform_bbox(frame, shape root
+ *    box) of ALL instances of the new list, in the new id order.  The shape root boxes are the ones the device holds now - they may
+ *    have been refitted or rebuilt - and the shape BVHs are not touched.  An instance of a shape without nodes gets invalidb3f.
+ *  - Lights.  make_lights of the new scene under the rule of vpt_scene_update_lights: emissive instances of faces in the new id order,
+ *    then the environments' and the SDFs' lights, which keep their entries, CDFs and records byte for byte.
+ * So renders, vpt_intersect (scene and single-instance query), vpt_kat, vpt_scene_get_bvh*, vpt_scene_light_tables_hash and
+ * vpt_scene_instance_tables_hash give the bits of a fresh handle made from that descriptor.
+ *  - Order of application.  `set` first (on current ids), then `remove` (current ids), then `add`.  An edit with all three counts zero
+ *    is valid and does nothing: no launch, no bytes.
+ *  - Validation before anything is written (VPT_ERR_INVALID_ARG, scene untouched): a null list with a non-zero count or a negative
+ *    count; an id out of range or repeated within its list; an id both set and removed; a shape or material out of range; a frame
+ *    value that is not finite; the material rule of vpt_scene_create - a material that becomes bound to a mesh instance for the first
+ *    time has its texture ids range-checked, as creation checks the materials of instances.  Zero instances after the edit is valid,
+ *    as it is for vpt_scene_create: the scene BVH has no nodes and no primitives.
+ *  - Refusals after building (VPT_ERR_UNSUPPORTED, scene untouched).  The traversal limits vpt_scene_create decides are decided anew
+ *    for the new scene BVH together with the shapes' trees, by the same function: the 256-entry LDS stack of the binary walk, the
+ *    packed pop floor of the quad traversal, 2^27 quad nodes.  Everything is built into buffers of the call; pointers, counts and
+ *    mirrors are swapped only after the last check.  A device failure after validation (VPT_ERR_HIP) leaves the handle good for
+ *    vpt_scene_destroy only.
+ *  - Lights under renumbering.  A surviving emissive instance keeps its CDF, its search index (offsets rebased) and its guide table,
+ *    all moved device to device; a CDF is computed only for an instance that is new, newly emissive, or whose shape changed through
+ *    `set`.  vpt_light::instance, the light records and light_prims are made anew for the new numbering.
+ *  - The kernel instances follow the new scene: whether an instanced shape holds points or lines, whether media vary over a surface,
+ *    the light features.  The stack sizes follow the new scene BVH as after vpt_scene_rebuild_bvh.  The next vpt_scene_update makes
+ *    its refit tables anew.
+ *  - What crosses PCIe.  Down, in one copy: 4 B per removed id and per set id (each of the two lists padded to 16 B) and 128 B per set
+ *    or added instance (the record creation would upload, its inverse made on the host); then the tables that depend on the scene BVH's topology, made on the host by the functions of
+ *    vpt_scene_create: the scene's quad nodes (128 B each), the integer words of the enter records (96 B per instance), the slot of
+ *    every instance (4 B); when the lights change, a few words per light (32 B list entry, 56 B index header, 4 B tag, 24 B job
+ *    descriptor of a recomputed one).  Up: the scene BVH's nodes (32 B each) and primitive order (4 B per instance), and 8 B per
+ *    recomputed light.  Nothing proportional to vertices, elements, leaf records, texels, voxels or CDF entries crosses, and no node
+ *    or quad node of a shape does: the shapes' part of the quad-node table moves device to device.
+ *    vpt_scene_update_stats reports the launches, the bytes of both directions in one sum, and the device time of the call.
+ *  - Synchronisation and the forgetting of the launch-schedule record: those of vpt_scene_update. */
+typedef struct vpt_instance_edit {
+  int32_t num_remove; const int32_t* remove_ids;                     /* current ids, none repeated */
+  int32_t num_set;    const int32_t* set_ids; const vpt_instance* set; /* current ids, none repeated, none also removed: frame, shape and material replaced */
+  int32_t num_add;    const vpt_instance* add;                       /* appended after the survivors, in this order */
+} vpt_instance_edit;
+int vpt_scene_update_instances(vpt_scene* scene, const vpt_instance_edit* edit);
+/* forward frame, shape, material of every instance as the device holds them; capacity in entries; `out` may be NULL (the count only) */
+int vpt_scene_get_instances(vpt_scene* scene, vpt_instance* out, int capacity, int* num_instances);
+/* FNV-1a over four tables read back from the device: the instance records (128 B each), scene_enter, slot_of_instance, scene_prims */
+int vpt_scene_instance_tables_hash(vpt_scene* scene, uint64_t out[4]);
+
 /* ---- the drop-in for pathtrace_samples() --------------------------------------------
  * Host, row-major (idx = j*width + i) caller-owned state, exactly pathtrace_state
  * (yocto_pathtrace.h:57-64): image float4[w*h], hits int32[w*h], rng {u64 state, u64 inc}[w*h].
@@ -578,6 +631,8 @@ int  vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit);
 int  vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit);
 /* vpt_scene_rebuild_bvh in the same way: every device builds its own trees; the arrays are equal by construction */
 int  vpt_multi_rebuild_bvh(vpt_multi* m, const vpt_bvh_rebuild* what);
+/* vpt_scene_update_instances in the same way: every device renumbers and builds its own tables; they are equal by construction */
+int  vpt_multi_update_instances(vpt_multi* m, const vpt_instance_edit* edit);
 int  vpt_multi_device_count(const vpt_multi* m);
 /* how vpt_multi_get_render moves the parts: "rccl", "peer-copy" (several devices, no RCCL) or "local" (one device) */
 const char* vpt_multi_transport(const vpt_multi* m);
@@ -830,6 +885,8 @@ int  vpt_session_edit_textures(vpt_session* session, const vpt_texture_edit* edi
 int  vpt_session_edit_volumes(vpt_session* session, const vpt_volume_edit* edit);
 /* vpt_scene_rebuild_bvh, then a reset (the picture is the same, its accumulation restarts as after the session's other edits); a refused call leaves the session as it was */
 int  vpt_session_rebuild_bvh(vpt_session* session, const vpt_bvh_rebuild* what);
+/* vpt_scene_update_instances, then a reset; a refused edit leaves the session as it was */
+int  vpt_session_edit_instances(vpt_session* session, const vpt_instance_edit* edit);
 int  vpt_session_get_display(vpt_session* session, uint8_t* rgba8, float* display_f);
 int  vpt_session_get_image(vpt_session* session, float* linear);
 int  vpt_session_get_denoised(vpt_session* session, float* linear);

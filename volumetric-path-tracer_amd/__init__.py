@@ -164,6 +164,50 @@ class BvhRebuild:
         return VptBvhRebuild(len(self.shapes), C.cast(ids, C.POINTER(C.c_int32)) if self.shapes else None, int(self.scene)), ids
 
 
+class VptInstance(C.Structure):  # vpt_instance
+    _fields_ = [("frame", VptFrame), ("shape", C.c_int32), ("material", C.c_int32)]
+
+
+class VptInstanceEdit(C.Structure):  # vpt_instance_edit
+    _fields_ = [("num_remove", C.c_int32), ("remove_ids", C.c_void_p), ("num_set", C.c_int32), ("set_ids", C.c_void_p), ("set", C.c_void_p),
+                ("num_add", C.c_int32), ("add", C.c_void_p)]
+
+
+INSTANCE = np.dtype([("frame", np.float32, 12), ("shape", np.int32), ("material", np.int32)])   # vpt_instance
+assert INSTANCE.itemsize == C.sizeof(VptInstance) == 56
+
+
+class InstanceEdit:
+    """What vpt_scene_update_instances takes (include/vpt.h: vpt_instance_edit): `set`, a dictionary current id -> (frame (12,) float32,
+    shape, material) that replaces those instances; `remove`, current ids erased after that (ids close up); `add`, a list of (frame,
+    shape, material) appended after the survivors.  HostScene.update_instances makes one; DeviceScene.update_instances /
+    MultiDeviceScene.update_instances / RenderSession.edit_instances apply it."""
+
+    def __init__(self, remove=(), set=None, add=()):
+        item = lambda v: (np.ascontiguousarray(v[0], np.float32).reshape(12).copy(), int(v[1]), int(v[2]))
+        self.remove = tuple(int(i) for i in remove)
+        self.set = {int(k): item(v) for k, v in dict(set or {}).items()}
+        self.add = [item(v) for v in add]
+
+    def empty(self) -> bool:
+        return not (self.remove or self.set or self.add)
+
+    @staticmethod
+    def _records(items) -> np.ndarray:
+        out = np.zeros(len(items), INSTANCE)
+        for i, (frame, shape, material) in enumerate(items):
+            out[i] = (frame, shape, material)
+        return out
+
+    def to_abi(self):
+        """(VptInstanceEdit, the arrays it points into: keep them alive across the call)"""
+        remove, set_ids = np.array(self.remove, np.int32), np.array(list(self.set.keys()), np.int32)
+        set_rec, add_rec = self._records(list(self.set.values())), self._records(self.add)
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        abi = VptInstanceEdit(len(remove), ptr(remove), len(set_ids), ptr(set_ids), ptr(set_rec), len(add_rec), ptr(add_rec))
+        return abi, [remove, set_ids, set_rec, add_rec]
+
+
 class SceneEdit:
     """What vpt_scene_update takes (include/vpt.h: vpt_scene_edit), as dictionaries id -> value: cameras (VptCamera), instances and
     environments ((12,) float32 frames x, y, z, o), materials (VptMaterial), shapes ((positions, normals or None) as (n, 3) float32).
@@ -412,6 +456,11 @@ hip.vpt_scene_get_bvh.argtypes = [_p, _p, C.c_int, _p, C.c_int64]
 hip.vpt_scene_rebuild_bvh.argtypes = [_p, C.POINTER(VptBvhRebuild)]
 hip.vpt_multi_rebuild_bvh.argtypes = [_p, C.POINTER(VptBvhRebuild)]
 hip.vpt_session_rebuild_bvh.argtypes = [_p, C.POINTER(VptBvhRebuild)]
+hip.vpt_scene_update_instances.argtypes = [_p, C.POINTER(VptInstanceEdit)]
+hip.vpt_multi_update_instances.argtypes = [_p, C.POINTER(VptInstanceEdit)]
+hip.vpt_session_edit_instances.argtypes = [_p, C.POINTER(VptInstanceEdit)]
+hip.vpt_scene_get_instances.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int)]
+hip.vpt_scene_instance_tables_hash.argtypes = [_p, _p]
 hip.vpt_scene_get_bvh_counts.argtypes = [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _p]
 hip.vpt_scene_get_bvh_prims.argtypes = [_p, _p, C.c_int, _p, C.c_int64]
 hip.vpt_scene_update_stats.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
@@ -495,6 +544,7 @@ host.vpth_scene_get_item.restype = C.c_int64
 host.vpth_scene_set_item.argtypes = [_p, C.c_int, C.c_int, _p, C.c_int64, C.c_char_p, C.c_int]
 host.vpth_scene_update_bvh.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_rebuild_bvh.argtypes = [_p, _p, C.c_int, C.c_int, C.c_char_p, C.c_int]
+host.vpth_scene_edit_instances.argtypes = [_p, _p, C.c_int, _p, _p, C.c_int, _p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_scene_update_lights.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_free.restype = None
 host.vpth_scene_get_environment.argtypes = [_p, C.c_int, C.POINTER(VptEnvironment)]
@@ -857,6 +907,7 @@ class HostScene:
         self._pending().cameras[index] = self.camera(index)
 
     def set_instance_frame(self, index: int, frame) -> None:
+        self._no_pending_instances("set_instance_frame")
         frame = np.ascontiguousarray(frame, np.float32).reshape(12)
         self._set(self._INSTANCE, index, frame)
         self._pending().instances[index] = frame.copy()
@@ -872,6 +923,7 @@ class HostScene:
 
     def set_shape_positions(self, index: int, positions, normals=None) -> None:
         """the vertices of a shape (same count), and its normals when given"""
+        self._no_pending_instances("set_shape_positions")
         positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
         self._set(self._POSITIONS, index, positions)
         if normals is not None:
@@ -907,12 +959,89 @@ class HostScene:
         DeviceScene.rebuild_bvh."""
         if getattr(self, "_edit", None) is not None and not self._edit.empty():
             raise VptError("rebuild_bvh: hand the pending edit out with update_bvh() first")
+        self._no_pending_instances("rebuild_bvh")
         ids = list(range(self.count("shapes"))) if isinstance(shapes, str) and shapes == "all" else [int(i) for i in (shapes or ())]
         arr = np.ascontiguousarray(ids, np.int32)
         err = C.create_string_buffer(512)
         if host.vpth_scene_rebuild_bvh(self.handle, arr.ctypes.data if len(arr) else None, len(arr), int(bool(scene)), err, len(err)) != 0:
             raise VptError(err.value.decode())
         return BvhRebuild(ids, scene)
+
+    # -- the set of instances (the host side of vpt_scene_update_instances): add_instance / remove_instances / set_instance note a
+    #    change, ids naming the list as it is now; update_instances() applies them to the scene - set, then remove, then add - builds
+    #    the scene BVH and the lights anew and hands the InstanceEdit out.  The ids of a pending SceneEdit name the old list, so the
+    #    two kinds of change do not mix: each is handed out before the other begins ------------------------------------------------
+    def _pending_instances(self) -> InstanceEdit:
+        if getattr(self, "_inst_edit", None) is None:
+            self._inst_edit = InstanceEdit()
+        return self._inst_edit
+
+    def _no_pending_instances(self, what: str) -> None:
+        if getattr(self, "_inst_edit", None) is not None and not self._inst_edit.empty():
+            raise VptError(f"{what}: hand the pending instance changes out with update_instances() first")
+
+    def _begin_instance_change(self, what: str) -> InstanceEdit:
+        if getattr(self, "_edit", None) is not None and (self._edit.instances or self._edit.shapes):
+            raise VptError(f"{what}: hand the pending edit out with update_bvh() first (its ids name the instances as they are now)")
+        return self._pending_instances()
+
+    def _check_instance(self, what: str, frame, shape: int, material: int):
+        frame = np.ascontiguousarray(frame, np.float32).reshape(-1)
+        if frame.size != 12 or not np.all(np.isfinite(frame)):
+            raise VptError(f"{what}: a frame is twelve finite floats (x, y, z, o)")
+        if not 0 <= int(shape) < self.count("shapes"):
+            raise VptError(f"{what}: shape {shape} out of range")
+        if not 0 <= int(material) < self.count("materials"):
+            raise VptError(f"{what}: material {material} out of range")
+        return frame.copy(), int(shape), int(material)
+
+    def add_instance(self, frame, shape: int, material: int) -> int:
+        """notes a new instance, appended at update_instances(); returns the id it has afterwards (given the removals noted so far)"""
+        pend = self._begin_instance_change("add_instance")
+        pend.add.append(self._check_instance("add_instance", frame, shape, material))
+        return self.count("instances") - len(pend.remove) + len(pend.add) - 1
+
+    def remove_instances(self, ids) -> None:
+        """notes instances (current ids) to erase at update_instances(): the survivors keep their order, the ids close up"""
+        pend = self._begin_instance_change("remove_instances")
+        ids = [int(i) for i in ids]
+        for i in ids:
+            if not 0 <= i < self.count("instances"):
+                raise VptError(f"remove_instances: instance {i} out of range")
+            if i in pend.set:
+                raise VptError(f"remove_instances: instance {i} is also set")
+        if len(set(ids)) != len(ids) or set(ids) & set(pend.remove):
+            raise VptError("remove_instances: an id is repeated")
+        pend.remove = pend.remove + tuple(ids)
+
+    def set_instance(self, index: int, frame=None, shape: Optional[int] = None, material: Optional[int] = None) -> None:
+        """notes another frame, shape or material (None: as it is) for instance `index` (current id), applied at update_instances()"""
+        pend = self._begin_instance_change("set_instance")
+        index = int(index)
+        if not 0 <= index < self.count("instances"):
+            raise VptError(f"set_instance: instance {index} out of range")
+        if index in pend.remove:
+            raise VptError(f"set_instance: instance {index} is also removed")
+        was = pend.set[index] if index in pend.set else (self.instance_frame(index),) + self.instance_ids(index)
+        pend.set[index] = self._check_instance("set_instance", was[0] if frame is None else frame, was[1] if shape is None else shape,
+                                               was[2] if material is None else material)
+
+    def update_instances(self) -> InstanceEdit:
+        """edit_instances of the host library over what add_instance / remove_instances / set_instance noted since the last call:
+        erase / replace / push_back on the scene's instances, the scene BVH built anew (make_bvh's scene level), make_lights; desc /
+        stats() describe the edited scene afterwards.  Returns the InstanceEdit for DeviceScene.update_instances."""
+        if getattr(self, "_edit", None) is not None and (self._edit.instances or self._edit.shapes):
+            raise VptError("update_instances: hand the pending edit out with update_bvh() first")
+        edit, self._inst_edit = self._pending_instances(), None
+        if edit.empty():
+            return edit
+        abi, keep = edit.to_abi()
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_edit_instances(self.handle, abi.remove_ids, abi.num_remove, abi.set_ids, abi.set, abi.num_set, abi.add, abi.num_add,
+                                          err, len(err)) != 0:
+            raise VptError(err.value.decode())
+        del keep
+        return edit
 
     # -- environments and textures (the host side of vpt_scene_update_textures): the setters change the scene and note the change in
     #    the pending TextureEdit; desc, lights() and stats() follow at update_textures(), which hands that edit out ----------------
@@ -1284,6 +1413,28 @@ class DeviceScene:
         _check(hip.vpt_scene_rebuild_bvh(self.handle, C.byref(abi)), "vpt_scene_rebuild_bvh")
         del keep
 
+    def update_instances(self, edit: InstanceEdit) -> None:
+        """vpt_scene_update_instances (include/vpt.h): instances re-pointed, removed and added on the device; the scene BVH and the
+        lights follow.  Afterwards the handle renders the bits of a DeviceScene made from the host scene after the same
+        HostScene.update_instances()."""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_scene_update_instances(self.handle, C.byref(abi)), "vpt_scene_update_instances")
+        del keep
+
+    def get_instances(self) -> np.ndarray:
+        """the instances as the device holds them, an INSTANCE array: forward frame, shape, material (vpt_scene_get_instances)"""
+        n = C.c_int(0)
+        _check(hip.vpt_scene_get_instances(self.handle, None, 0, C.byref(n)), "vpt_scene_get_instances")
+        out = np.zeros(n.value, INSTANCE)
+        _check(hip.vpt_scene_get_instances(self.handle, out.ctypes.data if len(out) else None, len(out), None), "vpt_scene_get_instances")
+        return out
+
+    def instance_tables_hash(self):
+        """FNV-1a of the four tables keyed by instance id (vpt_scene_instance_tables_hash): instances, enter records, slots, scene prims"""
+        out = np.zeros(4, np.uint64)
+        _check(hip.vpt_scene_instance_tables_hash(self.handle, out.ctypes.data), "vpt_scene_instance_tables_hash")
+        return tuple(int(x) for x in out)
+
     def get_bvh_counts(self):
         """(scene nodes, pooled shape nodes, first node of every shape as int64) as the device holds them (vpt_scene_get_bvh_counts)"""
         a, b = C.c_int32(0), C.c_int64(0)
@@ -1301,7 +1452,9 @@ class DeviceScene:
     def get_bvh_prims(self):
         """(scene primitive order, pooled shape primitive orders) as the device holds them, int32 (vpt_scene_get_bvh_prims)"""
         _, shape_prims = self.host_scene.bvh_prims()   # element counts never change: the pooled size is the descriptor's
-        a, b = np.zeros(self.host_scene.count("instances"), np.int32), np.zeros(len(shape_prims), np.int32)
+        n = C.c_int(0)                                 # the instances' count may: update_instances
+        _check(hip.vpt_scene_get_instances(self.handle, None, 0, C.byref(n)), "vpt_scene_get_instances")
+        a, b = np.zeros(n.value, np.int32), np.zeros(len(shape_prims), np.int32)
         _check(hip.vpt_scene_get_bvh_prims(self.handle, a.ctypes.data, len(a), b.ctypes.data, len(b)), "vpt_scene_get_bvh_prims")
         return a, b
 
@@ -1410,6 +1563,12 @@ class MultiDeviceScene:
         """vpt_multi_rebuild_bvh: DeviceScene.rebuild_bvh on every device (each builds its own trees: equal by construction)"""
         abi, keep = rebuild.to_abi()
         _check(hip.vpt_multi_rebuild_bvh(self.handle, C.byref(abi)), "vpt_multi_rebuild_bvh")
+        del keep
+
+    def update_instances(self, edit: InstanceEdit) -> None:
+        """vpt_multi_update_instances: DeviceScene.update_instances with the same edit on every device"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_multi_update_instances(self.handle, C.byref(abi)), "vpt_multi_update_instances")
         del keep
 
     def pathtrace_samples(self, state: PathtraceState, params: PathtraceParams, count: int = 1) -> None:
@@ -1717,6 +1876,13 @@ class RenderSession:
         """vpt_scene_rebuild_bvh on the session's scene with the BvhRebuild of HostScene.rebuild_bvh(), then a reset"""
         abi, keep = rebuild.to_abi()
         _check(hip.vpt_session_rebuild_bvh(self.handle, C.byref(abi)), "vpt_session_rebuild_bvh")
+        del keep
+
+    def edit_instances(self, edit: InstanceEdit) -> None:
+        """vpt_scene_update_instances on the session's scene with the InstanceEdit of HostScene.update_instances(), then a reset; a
+        refused edit leaves the session as it was"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_session_edit_instances(self.handle, C.byref(abi)), "vpt_session_edit_instances")
         del keep
 
     @property

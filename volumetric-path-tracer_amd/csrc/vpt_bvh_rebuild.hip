@@ -78,6 +78,51 @@ int copy_on_device(void* to, const void* from, size_t bytes) {
 
 }  // namespace
 
+int scene_level_build(resident& r, bvh_build_scratch& core, const DInstance* instances, int ninst, const DShape* shapes, scene_level& lv) {
+  lv.num_instances = ninst;
+  if (int rc = lv.inst_box.allocate((size_t)ninst * 2 * sizeof(float4))) return rc;
+  if (int rc = upd_instance_boxes(r, instances, ninst, shapes, lv.inst_box.get<float4>())) return rc;
+  if (int rc = bvh_build_core(core, lv.inst_box.get<float>(), 8, ninst, &lv.count, &r.last_launches)) return rc;
+  if (int rc = lv.nodes.allocate((size_t)lv.count * sizeof(vpt_bvh_node))) return rc;
+  if (int rc = lv.prims.allocate((size_t)ninst * sizeof(int))) return rc;
+  if (int rc = copy_on_device(lv.nodes.get(), core.nodes(), (size_t)lv.count * sizeof(vpt_bvh_node))) return rc;
+  if (int rc = copy_on_device(lv.prims.get(), core.primitives(), (size_t)ninst * sizeof(int))) return rc;
+  if (int rc = fetch(r, lv.h_nodes, lv.nodes.get(), (size_t)lv.count)) return rc;
+  if (int rc = fetch(r, lv.h_prims, lv.prims.get(), (size_t)ninst)) return rc;
+  for (int k = 0; k < ninst; k++)
+    if (lv.h_prims[(size_t)k] < 0 || lv.h_prims[(size_t)k] >= ninst) return vpt_set_error(VPT_ERR_HIP, "bvh rebuild: the scene's primitive order is not a permutation");
+  return VPT_OK;
+}
+
+int scene_level_enter(resident& r, scene_level& lv, const scene_tables& t, const int* inst_shape, const DInstance* instances, const DShape* shapes) {
+  const int ninst = lv.num_instances, scene_quads = (int)(t.scene_wnodes / 8);
+  std::vector<float4> enter((size_t)ninst * 6, make_float4(0, 0, 0, 0));
+  lv.slot_of.assign((size_t)ninst, -1);
+  for (int k = 0; k < ninst; k++) {
+    const int id = lv.h_prims[(size_t)k];
+    prep_enter_tail(&enter[6 * (size_t)k], t.shapes[(size_t)inst_shape[(size_t)id]], scene_quads, id, 0);
+    lv.slot_of[(size_t)id] = k;
+  }
+  if (int rc = send(r, lv.enter, enter)) return rc;
+  if (int rc = send(r, lv.d_slot_of, lv.slot_of)) return rc;
+  return upd_enter_records(r, lv.enter.get<float4>(), ninst, instances, shapes);
+}
+
+void scene_level_swap(resident& r, scene_level& lv, const scene_tables& t) {
+  DScene& d = r.d;
+  const struct { const void* old; device_buffer* fresh; } swaps[5] = {{d.scene_nodes, &lv.nodes}, {d.scene_prims, &lv.prims}, {d.scene_wnodes, &lv.wnodes},
+      {d.scene_enter, &lv.enter}, {d.slot_of_instance, &lv.d_slot_of}};
+  d.scene_nodes = lv.nodes.get<const float4>(), d.scene_prims = lv.prims.get<const int>();
+  d.scene_wnodes = lv.wnodes.get<const float4>(), d.shape_wnodes = d.scene_wnodes + t.scene_wnodes;
+  d.scene_enter = lv.enter.get<const float4>(), d.slot_of_instance = lv.d_slot_of.get<const int>();
+  for (const auto& s : swaps) adopt(r.tables, s.old, std::move(*s.fresh));
+  d.num_scene_nodes = lv.count, d.num_scene_prims = lv.num_instances, d.scene_root_ref = t.d.scene_root_ref;
+  d.scene_root_lo_x = t.d.scene_root_lo_x, d.scene_root_lo_y = t.d.scene_root_lo_y, d.scene_root_lo_z = t.d.scene_root_lo_z;
+  d.scene_root_hi_x = t.d.scene_root_hi_x, d.scene_root_hi_y = t.d.scene_root_hi_y, d.scene_root_hi_z = t.d.scene_root_hi_z;
+  r.h.slot_of = lv.slot_of;
+  r.refit.ready = false;   // levels and quad slots belong to the old trees: the next refit makes them anew
+}
+
 int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks& stacks) {
   DScene&       d = r.d;
   host_mirrors& h = r.h;
@@ -141,25 +186,12 @@ int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks&
   if (int rc = upd_shape_roots(r, n_shapes.get<DShape>(), n_shape_nodes.get<float4>())) return rc;
 
   // 3. the scene BVH over ALL instances (make_bvh's scene level holds every instance)
-  device_buffer d_inst_box, n_scene_nodes, n_scene_prims;
-  if (int rc = d_inst_box.allocate((size_t)ninst * 2 * sizeof(float4))) return rc;
-  if (int rc = upd_instance_boxes(r, n_shapes.get<DShape>(), d_inst_box.get<float4>())) return rc;
-  int scene_count = 0;
-  if (int rc = bvh_build_core(core, d_inst_box.get<float>(), 8, ninst, &scene_count, &r.last_launches)) return rc;
-  if (int rc = n_scene_nodes.allocate((size_t)scene_count * sizeof(vpt_bvh_node))) return rc;
-  if (int rc = n_scene_prims.allocate((size_t)ninst * sizeof(int))) return rc;
-  if (int rc = copy_on_device(n_scene_nodes.get(), core.nodes(), (size_t)scene_count * sizeof(vpt_bvh_node))) return rc;
-  if (int rc = copy_on_device(n_scene_prims.get(), core.primitives(), (size_t)ninst * sizeof(int))) return rc;
-
   // 4. the one read-back: node arrays (32 B per node) and the scene's primitive order; the topology-only tables from them, by
   // creation's own function - which also decides the traversal limits.  A tree past them is refused here, the scene untouched.
-  std::vector<vpt_bvh_node> h_shape_nodes, h_scene_nodes;
-  std::vector<int>          h_scene_prims;
+  scene_level lv;
+  if (int rc = scene_level_build(r, core, d.instances, ninst, n_shapes.get<DShape>(), lv)) return rc;
+  std::vector<vpt_bvh_node> h_shape_nodes;
   if (int rc = fetch(r, h_shape_nodes, n_shape_nodes.get(), (size_t)total)) return rc;
-  if (int rc = fetch(r, h_scene_nodes, n_scene_nodes.get(), (size_t)scene_count)) return rc;
-  if (int rc = fetch(r, h_scene_prims, n_scene_prims.get(), (size_t)ninst)) return rc;
-  for (int k = 0; k < ninst; k++)
-    if (h_scene_prims[(size_t)k] < 0 || h_scene_prims[(size_t)k] >= ninst) return vpt_set_error(VPT_ERR_HIP, "bvh rebuild: the scene's primitive order is not a permutation");
   for (const built_shape& b : built)
     for (int e : b.prims)
       if (e < 0 || e >= (int)b.prims.size()) return vpt_set_error(VPT_ERR_HIP, "bvh rebuild: shape %d: the primitive order is not a permutation", b.id);
@@ -168,25 +200,14 @@ int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks&
   vpt_scene_desc desc = {};
   desc.num_shapes = nshapes, desc.shapes = desc_shapes.data();
   desc.num_shape_bvh_nodes = total, desc.shape_bvh_nodes = h_shape_nodes.data();
-  desc.num_scene_bvh_nodes = scene_count, desc.scene_bvh_nodes = h_scene_nodes.data();
+  desc.num_scene_bvh_nodes = lv.count, desc.scene_bvh_nodes = lv.h_nodes.data();
   scene_tables t;
   t.d = d, t.shapes = shapes;
   if (int rc = prep_quad_nodes_and_stacks(desc, t)) return rc;
-  const int scene_quads = (int)(t.scene_wnodes / 8);
-  // enter records: the integer words here, frames and root boxes by the refit's kernel; the slot of every instance
-  std::vector<float4> enter((size_t)ninst * 6, make_float4(0, 0, 0, 0));
-  std::vector<int>    slot_of((size_t)ninst, -1);
-  for (int k = 0; k < ninst; k++) {
-    const int id = h_scene_prims[(size_t)k];
-    prep_enter_tail(&enter[6 * (size_t)k], t.shapes[(size_t)h.inst_shape[(size_t)id]], scene_quads, id, 0);
-    slot_of[(size_t)id] = k;
-  }
-  device_buffer n_wnodes, n_enter, n_slot_of;
-  if (int rc = send(r, n_wnodes, t.wnodes)) return rc;
-  if (int rc = send(r, n_enter, enter)) return rc;
-  if (int rc = send(r, n_slot_of, slot_of)) return rc;
+  // enter records: the integer words on the host, frames and root boxes by the refit's kernel; the slot of every instance
+  if (int rc = send(r, lv.wnodes, t.wnodes)) return rc;
   if (int rc = send(r, n_shapes.get<const DShape>(), t.shapes.data(), t.shapes.size())) return rc;   // + wnode_offset, root_ref, stack_need
-  if (int rc = upd_enter_records(r, n_enter.get<float4>(), ninst, n_shapes.get<DShape>())) return rc;
+  if (int rc = scene_level_enter(r, lv, t, h.inst_shape.data(), d.instances, n_shapes.get<DShape>())) return rc;
 
   // ---- the last check has passed: from here on the scene's own tables are written ------------------------------------------
   // 5. leaf records of the rebuilt shapes into their new order: gathered into a temporary, moved back device to device
@@ -208,18 +229,12 @@ int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks&
   }
 
   // 6. the swap: tables, counts, mirrors
-  const float4* old_wnodes = d.scene_wnodes;
-  const struct { const void* old; device_buffer* fresh; } swaps[7] = {{d.shape_nodes, &n_shape_nodes}, {d.scene_nodes, &n_scene_nodes}, {d.scene_prims, &n_scene_prims},
-      {old_wnodes, &n_wnodes}, {d.scene_enter, &n_enter}, {d.slot_of_instance, &n_slot_of}, {d.shapes, &n_shapes}};
-  d.shape_nodes = n_shape_nodes.get<const float4>(), d.scene_nodes = n_scene_nodes.get<const float4>(), d.scene_prims = n_scene_prims.get<const int>();
-  d.scene_wnodes = n_wnodes.get<const float4>(), d.shape_wnodes = d.scene_wnodes + t.scene_wnodes;
-  d.scene_enter = n_enter.get<const float4>(), d.slot_of_instance = n_slot_of.get<const int>(), d.shapes = n_shapes.get<const DShape>();
-  for (const auto& s : swaps) adopt(r.tables, s.old, std::move(*s.fresh));
-  d.num_scene_nodes = scene_count, d.num_scene_prims = ninst, d.scene_root_ref = t.d.scene_root_ref;
-  d.scene_root_lo_x = t.d.scene_root_lo_x, d.scene_root_lo_y = t.d.scene_root_lo_y, d.scene_root_lo_z = t.d.scene_root_lo_z;
-  d.scene_root_hi_x = t.d.scene_root_hi_x, d.scene_root_hi_y = t.d.scene_root_hi_y, d.scene_root_hi_z = t.d.scene_root_hi_z;
-  r.num_shape_nodes = total, m.shapes = t.shapes, h.slot_of = slot_of;
-  r.refit.ready = false;   // levels and quad slots belong to the old trees: the next refit makes them anew
+  const void* old_shape_nodes = d.shape_nodes, *old_shapes = d.shapes;
+  d.shape_nodes = n_shape_nodes.get<const float4>(), d.shapes = n_shapes.get<const DShape>();
+  adopt(r.tables, old_shape_nodes, std::move(n_shape_nodes)), adopt(r.tables, old_shapes, std::move(n_shapes));
+  scene_level_swap(r, lv, t);
+  r.num_shape_nodes = total, m.shapes = t.shapes;
+  r.num_shape_wnodes = (long long)t.shape_wnodes, r.shape_depth = t.shape_depth, r.shape_need4 = t.shape_need4;
   stacks.rebuilt = true, stacks.stack_cap = t.stack_cap, stacks.stack_lds4 = t.stack_lds4, stacks.stack_spill4 = t.stack_spill4;
 
   // 7. what hangs on the shapes' root boxes outside the BVHs: the mesh lights' records

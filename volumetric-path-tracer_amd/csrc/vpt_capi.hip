@@ -16,6 +16,7 @@
 #include "vpt_adaptive.h"
 #include "vpt_bvh_rebuild.h"
 #include "vpt_device_buffer.h"
+#include "vpt_instance_update.h"
 #include "vpt_error.h"
 #include "vpt_kat.h"
 #include "vpt_launch.h"
@@ -181,6 +182,7 @@ int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* 
   D.shape_wnodes = D.scene_wnodes + t.scene_wnodes;
   s->stack_cap = t.stack_cap, s->stack_lds4 = t.stack_lds4, s->stack_spill4 = t.stack_spill4, s->light_features = t.light_features;
   s->curves = t.curves, s->varying_media = t.varying_media, s->num_shape_nodes = d.num_shape_bvh_nodes;
+  s->num_shape_wnodes = (long long)t.shape_wnodes, s->shape_depth = t.shape_depth, s->shape_need4 = t.shape_need4;
   s->h = std::move(t.h), s->m = std::move(t.m);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -541,6 +543,58 @@ int vpt_scene_rebuild_bvh(vpt_scene* s, const vpt_bvh_rebuild* what) {
   s->stack_cap = st.stack_cap, s->stack_lds4 = st.stack_lds4, s->stack_spill4 = st.stack_spill4;
   if (int rc = light_setup(s)) return rc;   // light_prims read the leaf records, which have moved
   s->sched.forget();
+  return VPT_OK;
+}
+// the set of instances changed (vpt_instance_update.hip); the render side follows: stack sizes, the kernel instances, light_prims
+int vpt_scene_update_instances(vpt_scene* s, const vpt_instance_edit* edit) {
+  if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call replaces
+  bvh_rebuild_stacks     st;
+  instance_update_result res;
+  if (int rc = instance_update_apply(*s, *edit, st, res)) return rc;
+  if (!st.rebuilt) return VPT_OK;
+  if (st.stack_spill4 != s->stack_spill4) s->spill_lanes = 0;   // the HBM part is sized per entry: made anew by the next launch
+  s->stack_cap = st.stack_cap, s->stack_lds4 = st.stack_lds4, s->stack_spill4 = st.stack_spill4;
+  s->curves = res.curves;
+  if (int rc = light_setup(s)) return rc;   // light_prims name instances and hold world-space normals
+  if (res.lights_rebuilt)
+    if (int rc = medium_setup(s)) return rc;   // the medium records sit behind the light records, which were made anew
+  s->sched.forget();
+  return VPT_OK;
+}
+int vpt_scene_get_instances(vpt_scene* s, vpt_instance* out, int capacity, int* num_instances) {
+  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (num_instances) *num_instances = s->d.num_instances;
+  if (!out) return VPT_OK;
+  REQUIRE(capacity >= s->d.num_instances, "capacity %d < %d instances", capacity, s->d.num_instances);
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<DInstance> host((size_t)s->d.num_instances);
+  if (!host.empty()) HIP_TRY(hipMemcpy(host.data(), s->d.instances, host.size() * sizeof(DInstance), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < host.size(); i++) {
+    static_assert(sizeof(vpt_frame) == 3 * sizeof(float4), "a packed frame is the frame's twelve floats in order");
+    memcpy(&out[i].frame, host[i].fwd, sizeof(vpt_frame));
+    out[i].shape = host[i].shape, out[i].material = host[i].material;
+  }
+  return VPT_OK;
+}
+// FNV-1a over the tables keyed by instance id, read back from the device: instances, scene_enter, slot_of_instance, scene_prims
+int vpt_scene_instance_tables_hash(vpt_scene* s, uint64_t out[4]) {
+  if (!s || !out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t ni = (size_t)s->d.num_instances, np = (size_t)s->d.num_scene_prims;
+  const struct { const void* table; size_t bytes; } parts[4] = {{s->d.instances, ni * sizeof(DInstance)}, {s->d.scene_enter, 6 * np * sizeof(float4)},
+      {s->d.slot_of_instance, ni * sizeof(int)}, {s->d.scene_prims, np * sizeof(int)}};
+  std::vector<unsigned char> host;
+  for (int k = 0; k < 4; k++) {
+    host.resize(parts[k].bytes);
+    if (parts[k].bytes) HIP_TRY(hipMemcpy(host.data(), parts[k].table, parts[k].bytes, hipMemcpyDeviceToHost));
+    uint64_t hash = 14695981039346656037ull;
+    for (unsigned char b : host) hash = (hash ^ b) * 1099511628211ull;
+    out[k] = hash;
+  }
   return VPT_OK;
 }
 int vpt_scene_get_bvh_counts(vpt_scene* s, int32_t* scene_nodes, int64_t* shape_nodes, int64_t* shape_node_offsets) {

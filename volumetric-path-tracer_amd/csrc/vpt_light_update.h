@@ -31,5 +31,9 @@ struct env_light {
 // (launch_texel_weights, vpt_texture_update.h), and every one's record is sent.
 // sdf_resized: null, or per SDF whether an edit of r.m.sdfs (vpt_scene_update_volumes, vpt_volume_update.h) changed its whd: an SDF light
 // among them has another CDF entry, so the tables are rebuilt although the list stays.
+// old_instance: null, or - after vpt_scene_update_instances (vpt_instance_update.h) has renumbered the instances and brought r.d and
+// the mirrors up to date, all but the light mirrors - per instance of the new list its id in the old one, -1 for one that is new or
+// whose shape is another now: a surviving light keeps its CDF, index and guide table under its new id, and the tables are rebuilt
+// whenever a light's instance word moved, even where the list is the same by position.
 int light_update_apply(resident& r, const vpt_scene_edit& edit, bool* rebuilt, const std::vector<env_light>* envs = nullptr,
-    const std::vector<char>* sdf_resized = nullptr);
+    const std::vector<char>* sdf_resized = nullptr, const std::vector<int>* old_instance = nullptr);

@@ -215,7 +215,8 @@ struct entry {   // one light of the new list
 
 }  // namespace
 
-int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, const std::vector<env_light>* envs, const std::vector<char>* sdf_resized) {
+int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, const std::vector<env_light>* envs, const std::vector<char>* sdf_resized,
+    const std::vector<int>* old_instance) {
   *rebuilt = false;
   DScene&             d = r.d;
   const host_mirrors& h = r.h;
@@ -223,7 +224,10 @@ int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, cons
 
   // 1. the list (make_lights): emissive instances of faces, the environments that were lights, emissive SDFs - each in id order
   const std::vector<vpt_light>& old = u.lights;
-  std::vector<int>  old_of_instance((size_t)d.num_instances, -1), old_of_sdf((size_t)d.num_sdfs, -1), old_of_env((size_t)d.num_environments, -1);
+  int old_instances = d.num_instances;   // (the instances were renumbered: the old list and the map name old ids)
+  for (size_t l = 0; old_instance && l < old.size(); l++) old_instances = old[l].instance >= old_instances ? old[l].instance + 1 : old_instances;
+  for (size_t i = 0; old_instance && i < old_instance->size(); i++) old_instances = (*old_instance)[i] >= old_instances ? (*old_instance)[i] + 1 : old_instances;
+  std::vector<int>  old_of_instance((size_t)old_instances, -1), old_of_sdf((size_t)d.num_sdfs, -1), old_of_env((size_t)d.num_environments, -1);
   std::vector<char> moved((size_t)d.num_shapes, 0);
   for (size_t l = 0; l < old.size(); l++) {
     if (old[l].instance >= 0) old_of_instance[(size_t)old[l].instance] = (int)l;
@@ -238,7 +242,8 @@ int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, cons
     const DShape& sh    = u.shapes[(size_t)shape];
     if ((u.inst_flags[(size_t)i] & (VPT_SHP_POINTS | VPT_SHP_LINES)) || sh.num_elems <= 0) continue;   // points and lines are never lights
     const bool small = sh.root_ref < 0 && ((~sh.root_ref) & 15) <= 4;   // build_lights: one leaf of <= 4 primitives is walked inline
-    const int  from  = old_of_instance[(size_t)i];
+    const int  was   = old_instance ? (*old_instance)[(size_t)i] : i;   // -1: a new instance, or one whose shape is another now
+    const int  from  = was >= 0 ? old_of_instance[(size_t)was] : -1;
     list.push_back({{i, VPT_INVALID, VPT_INVALID, sh.num_elems, 0}, from, from < 0 || moved[(size_t)shape] != 0,
         small ? VPT_LIGHT_SMALL_MESH | (((~sh.root_ref) & 15) << 8) : VPT_LIGHT_LARGE_MESH});
   }
@@ -256,6 +261,8 @@ int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, cons
     if (emissive(u.materials[(size_t)u.sdfs[(size_t)i].material])) list.push_back({{VPT_INVALID, VPT_INVALID, i, 1, 0}, old_of_sdf[(size_t)i], false, VPT_LIGHT_SDF});
   bool same = list.size() == old.size();
   for (size_t l = 0; same && l < list.size(); l++) same = list[l].from == (int)l && !list[l].recompute && list[l].l.cdf_len == old[l].cdf_len;
+  // the same lights by position may be other instance ids after a renumbering: vpt_light::instance, the records and light_prims name them
+  for (size_t l = 0; same && old_instance && l < list.size(); l++) same = list[l].l.instance == old[l].instance;
   for (size_t l = 0; same && sdf_resized && l < list.size(); l++) same = list[l].l.sdf < 0 || !(*sdf_resized)[(size_t)list[l].l.sdf];   // its one CDF entry is whd.x * whd.y
   env_of.resize(list.size(), -1);
   if (same) return VPT_OK;   // no consequence for the lights: the update has done all there is to do

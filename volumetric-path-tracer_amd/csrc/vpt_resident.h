@@ -35,6 +35,8 @@ struct resident {
   host_mirrors h;                      // range checks of vpt_intersect, vpt_kat; sizes of a vertex edit
   edit_mirrors m;                      // as vpt_scene_create made them, as the last edit left them
   long long    num_shape_nodes = 0;    // nodes of d.shape_nodes
+  long long    num_shape_wnodes = 0;   // float4s of d.shape_wnodes; with the two below, what prep_quad_nodes_and_stacks found of the shapes'
+  int          shape_depth = 0, shape_need4 = 0;   // trees: an edit that builds the scene BVH alone decides the traversal limits from them
   int          light_features  = 0;      // VPT_FEAT_* bits this scene's lights need from the mesh kernels
   bool         varying_media   = false;  // prep_media_vary of m.materials: K1's general instance, which carries a path's medium in registers
   refit_tables refit;

@@ -353,15 +353,19 @@ void build_geometry(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_t
 // instance records, the enter records of the scene-BVH slots, and the inverse frames of environments
 void build_instances(const vpt_scene_desc& d, const vpt_scene_curves& cs, scene_tables& t) {
   t.instances.resize((size_t)d.num_instances);
+  t.m.shape_flags.resize((size_t)d.num_shapes);   // of every shape, instanced or not: vpt_scene_update_instances may bind it later
+  for (int i = 0; i < d.num_shapes; i++) {
+    const vpt_shape& sh = d.shapes[i];
+    t.m.shape_flags[(size_t)i] = (sh.num_triangles != 0 ? VPT_SHP_TRIANGLES : 0) | (sh.normal_offset >= 0 ? VPT_SHP_NORMALS : 0) |
+                                 (sh.texcoord_offset >= 0 ? VPT_SHP_TEXCOORDS : 0) | (sh.color_offset >= 0 ? VPT_SHP_COLORS : 0) |
+                                 (curves_of(cs, i).num_points ? VPT_SHP_POINTS : 0) | (curves_of(cs, i).num_lines ? VPT_SHP_LINES : 0);
+  }
   for (int i = 0; i < d.num_instances; i++) {
     DInstance& in = t.instances[i];
     in = {};
     prep_instance_frames(d.instances[i].frame, in.inv, in.fwd, &in.translation_only);
     in.shape = d.instances[i].shape, in.material = d.instances[i].material;
-    const vpt_shape& sh = d.shapes[d.instances[i].shape];
-    in.shape_flags = (sh.num_triangles != 0 ? VPT_SHP_TRIANGLES : 0) | (sh.normal_offset >= 0 ? VPT_SHP_NORMALS : 0) |
-                     (sh.texcoord_offset >= 0 ? VPT_SHP_TEXCOORDS : 0) | (sh.color_offset >= 0 ? VPT_SHP_COLORS : 0) |
-                     (curves_of(cs, in.shape).num_points ? VPT_SHP_POINTS : 0) | (curves_of(cs, in.shape).num_lines ? VPT_SHP_LINES : 0);
+    in.shape_flags = t.m.shape_flags[(size_t)in.shape];
     t.curves = t.curves || has_curves(cs, in.shape);
     t.h.inst_shape.push_back(d.instances[i].shape);
   }
@@ -633,10 +637,10 @@ void prep_enter_tail(float4* e, const DShape& sh, int scene_quads, int instance,
 // quad nodes of every BVH, the shapes' roots and stack needs, and the traversal stacks sized from them.  The stack sizes and the
 // VPT_FLOOR_SHIFT check depend on the trees' topology only: vpt_scene_update refits boxes and keeps topology, so they stay valid;
 // vpt_scene_rebuild_bvh (vpt_bvh_rebuild.hip) changes topology and calls this again, on the node arrays it built (vpt_scene_prep.h).
-int prep_quad_nodes_and_stacks(const vpt_scene_desc& d, scene_tables& t) {
+int prep_quad_nodes_and_stacks(const vpt_scene_desc& d, scene_tables& t, bool shapes_kept) {
   std::vector<float4> shape_wnodes;
-  int max_shape_depth = 0, max_shape_need4 = 0;
-  for (int i = 0; i < d.num_shapes; i++) {
+  int max_shape_depth = shapes_kept ? t.shape_depth : 0, max_shape_need4 = shapes_kept ? t.shape_need4 : 0;
+  for (int i = 0; i < d.num_shapes && !shapes_kept; i++) {
     const vpt_shape& sh = d.shapes[i];
     DShape& o = t.shapes[i];
     o.wnode_offset = (int)(shape_wnodes.size() / 8);
@@ -685,7 +689,8 @@ int prep_quad_nodes_and_stacks(const vpt_scene_desc& d, scene_tables& t) {
         scene_depth, max_shape_depth, scene_need4, max_shape_need4, t.stack_lds4, t.stack_spill4);
   // one table: [scene quad nodes][shape quad nodes]
   t.scene_wnodes = t.wnodes.size();
-  if ((t.scene_wnodes + shape_wnodes.size()) / 8 >= (1ull << 27)) return vpt_set_error(VPT_ERR_UNSUPPORTED, "more than 2^27 quad nodes");
+  if (!shapes_kept) t.shape_wnodes = shape_wnodes.size(), t.shape_depth = max_shape_depth, t.shape_need4 = max_shape_need4;
+  if ((t.scene_wnodes + t.shape_wnodes) / 8 >= (1ull << 27)) return vpt_set_error(VPT_ERR_UNSUPPORTED, "more than 2^27 quad nodes");
   t.wnodes.insert(t.wnodes.end(), shape_wnodes.begin(), shape_wnodes.end());
   return VPT_OK;
 }

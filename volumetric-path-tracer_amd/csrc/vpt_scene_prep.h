@@ -23,6 +23,7 @@ struct edit_mirrors {
   std::vector<char>            textured;     // material bound to a mesh instance: its texture ids are range-checked
   std::vector<DShape>          shapes;       // offsets, counts and root_ref (root_box: creation's, the device refits its own)
   std::vector<int>             inst_material, inst_flags;   // DInstance::material / shape_flags
+  std::vector<int>             shape_flags;   // VPT_SHP_* of every shape: the shape_flags of an instance that is bound to it later
   std::vector<vpt_light>       lights;
   std::vector<int>             light_kind;   // VPT_LIGHT_* of every light record (the tag of its last word)
   std::vector<char>            shape_lit;    // some light's instance uses the shape
@@ -46,7 +47,8 @@ struct scene_tables {
   std::vector<float4> tri_prims, tri_attrs;   // the compact records: empty unless every shape holds triangles
   // quad nodes of all BVHs in one table: the scene's first (scene_wnodes float4s), then the shapes'
   std::vector<float4> wnodes;
-  size_t              scene_wnodes = 0;
+  size_t              scene_wnodes = 0, shape_wnodes = 0;   // float4s of the two parts
+  int                 shape_depth = 0, shape_need4 = 0;    // the deepest shape BVH, the largest quad-stack need of a shape
   std::vector<float4> enter;
   std::vector<DInstance> instances;
   std::vector<float4> env_inv, sdf_inv;
@@ -82,7 +84,10 @@ void prep_quad_slots(const vpt_bvh_node* nodes, int count, std::vector<int>& slo
 // and the stack sizes out.stack_cap / stack_lds4 / stack_spill4 (VPT_STACK_LDS and VPT_DEBUG are read here).  Reads of `desc`:
 // num_shapes, shapes[i].bvh_node_offset / num_bvh_nodes, shape_bvh_nodes, scene_bvh_nodes, num_scene_bvh_nodes; of `out`: shapes[i].num_nodes.
 // VPT_ERR_UNSUPPORTED for trees past a traversal limit: the 256-entry LDS stack, the packed pop floor, 2^27 quad nodes.
-int prep_quad_nodes_and_stacks(const vpt_scene_desc& desc, scene_tables& out);
+// shapes_kept (vpt_scene_update_instances, vpt_instance_update.hip: only the scene BVH is new): the shapes' part is not made -
+// out.wnodes holds the scene's quad nodes alone, out.shapes is not written - and what the limits need to know of the shapes is read
+// from out.shape_depth / shape_need4 / shape_wnodes, which every call without the flag leaves there.
+int prep_quad_nodes_and_stacks(const vpt_scene_desc& desc, scene_tables& out, bool shapes_kept = false);
 // the integer words of the enter record `e` (6 float4) of the scene-BVH slot that holds `instance`: e4.zw = root_ref, first quad node of
 // the shape in the one quad-node array (scene_quads = the scene BVH's own); e5 = leaf_offset, instance, translation_only, num_nodes
 void prep_enter_tail(float4* e, const DShape& shape, int scene_quads, int instance, int translation_only);

@@ -418,12 +418,12 @@ int upd_shape_roots(resident& r, DShape* shapes, const float4* shape_nodes) {
   LAUNCH(r, upd_shape_roots_kernel, r.d.num_shapes, shapes, r.d.num_shapes, shape_nodes);
   return VPT_OK;
 }
-int upd_instance_boxes(resident& r, const DShape* shapes, float4* inst_box) {
-  LAUNCH(r, upd_instance_boxes_kernel, r.d.num_instances, r.d.instances, r.d.num_instances, shapes, inst_box);
+int upd_instance_boxes(resident& r, const DInstance* instances, int num_instances, const DShape* shapes, float4* inst_box) {
+  LAUNCH(r, upd_instance_boxes_kernel, num_instances, instances, num_instances, shapes, inst_box);
   return VPT_OK;
 }
-int upd_enter_records(resident& r, float4* enter, int slots, const DShape* shapes) {
-  LAUNCH(r, upd_enter_records_kernel, slots, enter, slots, r.d.instances, shapes);
+int upd_enter_records(resident& r, float4* enter, int slots, const DInstance* instances, const DShape* shapes) {
+  LAUNCH(r, upd_enter_records_kernel, slots, enter, slots, instances, shapes);
   return VPT_OK;
 }
 int upd_light_records(resident& r, const DShape* shapes) {

@@ -183,6 +183,13 @@ void             update_bvh(bvh_scene& bvh, const scene_data& scene, const vecto
 // vertices, then - `scene_level`, forced when a shape is named - the scene BVH over the current instances and roots.  Throws
 // std::invalid_argument for a shape id out of range or repeated.
 void             rebuild_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& shapes, bool scene_level);
+// The set of instances changed (the host side of vpt_scene_update_instances, include/vpt.h): `set` entries replace the instances named
+// by current ids, then the instances of `remove` (current ids) are erased - survivors keep their order, ids close up - then `add` is
+// appended; the scene BVH is built anew over the new list (rebuild_bvh(bvh, scene, {}, true): the shapes' trees stay) and the lights
+// are make_lights of the new scene.  Throws std::invalid_argument for an id out of range or repeated, an id both set and removed, or
+// a shape or material out of range; the scene is untouched then.
+void             edit_instances(scene_data& scene, bvh_scene& bvh, pathtrace_lights& lights, const vector<int>& remove, const vector<int>& set_ids,
+                const vector<instance_data>& set, const vector<instance_data>& add);
 // build_bvh over `n` boxes {min.xyz, max.xyz} on the host (what make_bvh runs per shape and for the instances)
 bvh_data         build_bvh_host(const float* bboxes, int n);
 pathtrace_lights make_lights(const scene_data& scene, const pathtrace_params& params);

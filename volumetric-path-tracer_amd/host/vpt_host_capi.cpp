@@ -248,6 +248,34 @@ int vpth_scene_rebuild_bvh(void* hh, const int32_t* shape_ids, int n, int scene,
     return set_error(err, errlen, e.what()), -1;
   }
 }
+// edit_instances (set on current ids, then remove, then add; the scene BVH built anew, make_lights) and the flattened descriptor again
+// (its address changes): the host side of vpt_scene_update_instances.  Refused while a frame or vertex edit waits for update_bvh: its
+// ids name the old list.
+int vpth_scene_edit_instances(void* hh, const int32_t* remove_ids, int num_remove, const int32_t* set_ids, const vpt_instance* set, int num_set,
+    const vpt_instance* add, int num_add, char* err, int errlen) {
+  try {
+    auto& h = *(host_scene*)hh;
+    if (num_remove < 0 || num_set < 0 || num_add < 0 || (num_remove > 0 && !remove_ids) || (num_set > 0 && (!set_ids || !set)) || (num_add > 0 && !add))
+      return set_error(err, errlen, "null or negative instance list"), -1;
+    if (!h.edited_instances.empty() || !h.edited_shapes.empty()) return set_error(err, errlen, "an edit of frames or vertices is pending: update_bvh first"), -1;
+    auto convert = [](const vpt_instance* in, int n) {
+      auto out = vector<instance_data>((size_t)n);
+      for (auto i = 0; i < n; i++) {
+        memcpy((void*)&out[(size_t)i].frame, &in[i].frame, sizeof(vpt_frame));
+        out[(size_t)i].shape = in[i].shape, out[(size_t)i].material = in[i].material;
+      }
+      return out;
+    };
+    edit_instances(h.scene, h.bvh, h.lights, vector<int>(remove_ids, remove_ids + num_remove), vector<int>(set_ids, set_ids + num_set), convert(set, num_set),
+        convert(add, num_add));
+    auto flat = std::make_unique<flat_scene>();
+    flatten_scene(*flat, h.scene, h.bvh, h.lights);
+    h.flat = std::move(flat);
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
+}
 // make_lights of the scene as the setters left it (an emission switched on or off, an emitter's vertices moved), then the flattened
 // descriptor again: the host side of vpt_scene_update_lights.  The BVHs are vpth_scene_update_bvh's business.
 int vpth_scene_update_lights(void* hh, char* err, int errlen) {

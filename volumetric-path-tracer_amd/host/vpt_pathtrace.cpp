@@ -258,6 +258,34 @@ bvh_scene make_bvh_device(const scene_data& scene, const pathtrace_params&, int 
 // =============================================================================================
 // make_lights — serial float32 running sums.  yocto_pathtrace.cpp:983-1049
 // =============================================================================================
+void edit_instances(scene_data& scene, bvh_scene& bvh, pathtrace_lights& lights, const vector<int>& remove, const vector<int>& set_ids,
+    const vector<instance_data>& set, const vector<instance_data>& add) {
+  const auto n = (int)scene.instances.size();
+  if (set_ids.size() != set.size()) throw std::invalid_argument{"edit_instances: set ids and instances differ in number"};
+  auto removed = vector<char>((size_t)n, 0), is_set = vector<char>((size_t)n, 0);
+  for (auto id : remove) {
+    if (id < 0 || id >= n) throw std::invalid_argument{"edit_instances: removed id out of range"};
+    if (removed[(size_t)id]) throw std::invalid_argument{"edit_instances: removed id repeated"};
+    removed[(size_t)id] = 1;
+  }
+  for (auto id : set_ids) {
+    if (id < 0 || id >= n) throw std::invalid_argument{"edit_instances: set id out of range"};
+    if (is_set[(size_t)id]) throw std::invalid_argument{"edit_instances: set id repeated"};
+    if (removed[(size_t)id]) throw std::invalid_argument{"edit_instances: an id is both set and removed"};
+    is_set[(size_t)id] = 1;
+  }
+  for (auto* list : {&set, &add})
+    for (auto& in : *list) {
+      if (in.shape < 0 || in.shape >= (int)scene.shapes.size()) throw std::invalid_argument{"edit_instances: shape out of range"};
+      if (in.material < 0 || in.material >= (int)scene.materials.size()) throw std::invalid_argument{"edit_instances: material out of range"};
+    }
+  for (auto i = (size_t)0; i < set.size(); i++) scene.instances[(size_t)set_ids[i]] = set[i];
+  for (auto id = n - 1; id >= 0; id--)   // erase from the back: the ids of the list are the current ones throughout
+    if (removed[(size_t)id]) scene.instances.erase(scene.instances.begin() + id);
+  for (auto& in : add) scene.instances.push_back(in);
+  rebuild_bvh(bvh, scene, {}, true);
+  lights = make_lights(scene, pathtrace_params{});
+}
 pathtrace_lights make_lights(const scene_data& scene, const pathtrace_params&) {
   auto lights = pathtrace_lights{};
   for (auto handle = 0; handle < (int)scene.instances.size(); handle++) {
