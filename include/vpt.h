@@ -584,6 +584,80 @@ int vpt_scene_get_instances(vpt_scene* scene, vpt_instance* out, int capacity, i
 /* FNV-1a over four tables read back from the device: the instance records (128 B each), scene_enter, slot_of_instance, scene_prims */
 int vpt_scene_instance_tables_hash(vpt_scene* scene, uint64_t out[4]);
 
+/* ---- shapes of a resident scene added, removed and replaced on the device -----------------------------------------------
+ * The edits above keep the meshes as creation left them: how many vertices and elements a shape has, and of what kind.
+ * vpt_scene_update_shapes changes the shape list: the per-shape pools change length and layout, and what is keyed by a shape id or by an
+ * offset into a pool follows.  Materials, textures, volumes and SDFs stay, and so does the number of instances.
+ * After the call every table on the device holds the bytes vpt_scene_create would upload for a descriptor built as follows:
+ *  - Shape list.  The old list with the `set` entries replaced, the removed entries erased and the added ones appended.  Survivors keep
+ *    their order and the ids close up.  `set` is applied first, on current ids, then `remove` (current ids), then `add`, as for
+ *    vpt_scene_update_instances.
+ *  - Renumbered instances.  Every instance's `shape` follows the renumbering; its shape_flags are those of the shape it names now.
+ *  - Pools.  Vertex, element, node, quad-node and leaf pools are contiguous in shape order, as the host mirror's flatten lays them out.
+ *    A scene whose pools are not (a descriptor made by other means) is refused with VPT_ERR_UNSUPPORTED before anything is built.
+ *  - BVHs of `set` and added shapes.  What make_bvh builds from their elements: the boxes of yocto_bvh.cpp:537-549 (point_bounds,
+ *    line_bounds, triangle_bounds, quad_bounds), build_bvh with highquality = false.
+ *  - BVHs of untouched shapes.  The trees the device holds now, refitted or rebuilt ones included.
+ *  - Scene BVH.  Built anew over all instances when, and only when, num_set > 0: a replaced shape has another root box.  Otherwise
+ *    the nodes and the primitive order stay, and only the integer words of the enter records follow the new offsets.
+ *  - Lights.  make_lights of the new scene under the rule of vpt_scene_update_lights.  A mesh light on a `set` shape gets a CDF of the
+ *    new length and the kind (single leaf of at most four elements, or tree) of its new BVH; every other light keeps its CDF.
+ * So renders, both forms of vpt_intersect, vpt_kat, vpt_scene_get_bvh*, vpt_scene_light_tables_hash, vpt_scene_instance_tables_hash
+ * and vpt_scene_shape_tables_hash give the bits of a fresh handle made from that descriptor.
+ *  - An edit with all three counts zero is valid and does nothing: no launch, no bytes.
+ *  - One shape (vpt_shape_data).  Indices are local to the shape, as in the descriptor.  Exactly one kind of element, or none: triangles,
+ *    quads, points or lines.  normals, texcoords and colors are NULL or hold num_vertices entries; radius is required with points or lines
+ *    and ignored otherwise.
+ *  - Validation before anything is written (VPT_ERR_INVALID_ARG, scene untouched): a null list with a non-zero count or a negative
+ *    count; an id out of range or repeated within its list; an id both set and removed; a vertex index out of range; both triangles and
+ *    quads; points or lines without radius; a float that is not finite; a removed shape that an instance still names (the caller removes
+ *    or re-points its instances through vpt_scene_update_instances first); a pool whose new entry count does not fit the 32-bit offsets
+ *    of the shape records.  A shape that mixes points, lines and faces is refused with VPT_ERR_UNSUPPORTED, as by vpt_scene_create.
+ *  - Refusals after building (VPT_ERR_UNSUPPORTED, scene untouched).  The traversal limits of vpt_scene_create are decided anew by the
+ *    same function from the new shapes' trees, what the handle keeps of the untouched ones (depth and quad-stack need per shape) and
+ *    the scene BVH: removing the deepest shape lowers the stack sizes as a fresh creation would.  Everything is built into buffers of the
+ *    call; pointers, counts and mirrors are swapped only after the last check.  A device failure after validation (VPT_ERR_HIP)
+ *    leaves the handle good for vpt_scene_destroy only.
+ *  - Compact triangle records (vpt_scene_record_bytes) exist while every shape holds triangles and VPT_NO_COMPACT_TRIANGLES is unset:
+ *    they are dropped when a shape of another kind (or an empty one) enters and made on the device from the general records when the
+ *    last such shape leaves or becomes triangles.  The kernel instances follow the new scene: points or lines among the instanced
+ *    shapes, media that vary over a surface (a replaced shape may gain or lose vertex colours), the light features.  The next
+ *    vpt_scene_update makes its refit tables anew.
+ *  - What crosses PCIe.  Down: the payload of the `set` and added shapes in one copy, every array padded to 16 B - 12 B per position
+ *    and per normal, 8 B per texcoord, 16 B per colour, 4 B per radius, 12 / 16 / 4 / 8 B per triangle / quad / point / line; 128 B per
+ *    quad node of a `set` or added shape; 80 B per shape of the new list, a second time when the scene BVH is built (the instance boxes
+ *    need the root boxes before the quad nodes are numbered); 8 B per shape of the old list (new id and flags); 96 + 4 B per
+ *    instance (the integer words of the enter records, the slots); 128 B per quad node of the scene BVH when it is built; the lights'
+ *    words of vpt_scene_update_instances.  Up: 32 B per node and 4 B per element of `set` and added shapes; 32 B per scene node and 4 B
+ *    per instance when the scene BVH is built; 8 B per recomputed light.  Nothing is proportional to vertices, elements, nodes, quad
+ *    nodes or leaf records of an untouched shape - they move device to device, one copy per pool and run of adjacent survivors - nor
+ *    to texels, voxels or CDF entries of an untouched light.  vpt_scene_update_stats reports launches, bytes and device time.
+ *  - Synchronisation and the forgetting of the launch-schedule record: those of vpt_scene_update. */
+typedef struct vpt_shape_data {          /* one shape, indices shape-local, as in the descriptor */
+  int32_t num_vertices;
+  const float* positions;                /* float3, required when num_vertices > 0 */
+  const float* normals;                  /* float3 or NULL */
+  const float* texcoords;                /* float2 or NULL */
+  const float* colors;                   /* float4 or NULL */
+  const float* radius;                   /* float or NULL; required with points or lines */
+  int32_t num_triangles; const int32_t* triangles;   /* int3 */
+  int32_t num_quads;     const int32_t* quads;       /* int4 */
+  int32_t num_points;    const int32_t* points;      /* int  */
+  int32_t num_lines;     const int32_t* lines;       /* int2 */
+} vpt_shape_data;
+typedef struct vpt_shape_edit {
+  int32_t num_remove; const int32_t* remove_ids;                          /* current ids, none repeated, none named by an instance */
+  int32_t num_set;    const int32_t* set_ids; const vpt_shape_data* set;  /* current ids, none repeated, none also removed: the whole mesh replaced */
+  int32_t num_add;    const vpt_shape_data* add;                          /* appended after the survivors, in this order */
+} vpt_shape_edit;
+int vpt_scene_update_shapes(vpt_scene* scene, const vpt_shape_edit* edit);
+/* FNV-1a over eight groups of tables read back from the device: the shape records (80 B each); positions, normals, texcoords and
+ * colors in one chain; elems; leaf_prims (with its 8 trailing float4); leaf_attrs; tri_prims then tri_attrs in one chain (0 where the
+ * scene has none); shape_nodes; the shapes' quad nodes */
+int vpt_scene_shape_tables_hash(vpt_scene* scene, uint64_t out[8]);
+/* the number of shapes and the entries of the pooled element and vertex tables as the device holds them; any pointer may be NULL */
+int vpt_scene_get_shape_counts(vpt_scene* scene, int32_t* num_shapes, int64_t* num_elements, int64_t* num_vertices);
+
 /* ---- the drop-in for pathtrace_samples() --------------------------------------------
  * Host, row-major (idx = j*width + i) caller-owned state, exactly pathtrace_state
  * (yocto_pathtrace.h:57-64): image float4[w*h], hits int32[w*h], rng {u64 state, u64 inc}[w*h].
@@ -633,6 +707,8 @@ int  vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit);
 int  vpt_multi_rebuild_bvh(vpt_multi* m, const vpt_bvh_rebuild* what);
 /* vpt_scene_update_instances in the same way: every device renumbers and builds its own tables; they are equal by construction */
 int  vpt_multi_update_instances(vpt_multi* m, const vpt_instance_edit* edit);
+/* vpt_scene_update_shapes in the same way: every device lays out its own pools and builds its own trees; they are equal by construction */
+int  vpt_multi_update_shapes(vpt_multi* m, const vpt_shape_edit* edit);
 int  vpt_multi_device_count(const vpt_multi* m);
 /* how vpt_multi_get_render moves the parts: "rccl", "peer-copy" (several devices, no RCCL) or "local" (one device) */
 const char* vpt_multi_transport(const vpt_multi* m);
@@ -887,6 +963,8 @@ int  vpt_session_edit_volumes(vpt_session* session, const vpt_volume_edit* edit)
 int  vpt_session_rebuild_bvh(vpt_session* session, const vpt_bvh_rebuild* what);
 /* vpt_scene_update_instances, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_edit_instances(vpt_session* session, const vpt_instance_edit* edit);
+/* vpt_scene_update_shapes, then a reset; a refused edit leaves the session as it was */
+int  vpt_session_edit_shapes(vpt_session* session, const vpt_shape_edit* edit);
 int  vpt_session_get_display(vpt_session* session, uint8_t* rgba8, float* display_f);
 int  vpt_session_get_image(vpt_session* session, float* linear);
 int  vpt_session_get_denoised(vpt_session* session, float* linear);

@@ -208,6 +208,75 @@ class InstanceEdit:
         return abi, [remove, set_ids, set_rec, add_rec]
 
 
+class VptShapeData(C.Structure):  # vpt_shape_data
+    _fields_ = [("num_vertices", C.c_int32), ("positions", C.c_void_p), ("normals", C.c_void_p), ("texcoords", C.c_void_p), ("colors", C.c_void_p),
+                ("radius", C.c_void_p), ("num_triangles", C.c_int32), ("triangles", C.c_void_p), ("num_quads", C.c_int32), ("quads", C.c_void_p),
+                ("num_points", C.c_int32), ("points", C.c_void_p), ("num_lines", C.c_int32), ("lines", C.c_void_p)]
+
+
+class VptShapeEdit(C.Structure):  # vpt_shape_edit
+    _fields_ = [("num_remove", C.c_int32), ("remove_ids", C.c_void_p), ("num_set", C.c_int32), ("set_ids", C.c_void_p), ("set", C.c_void_p),
+                ("num_add", C.c_int32), ("add", C.c_void_p)]
+
+
+assert C.sizeof(VptShapeData) == 112 and C.sizeof(VptShapeEdit) == 56
+
+MESH_FLOATS = {"positions": 3, "normals": 3, "texcoords": 2, "colors": 4, "radius": 0}     # floats per vertex (0: a plain array)
+MESH_ELEMENTS = {"triangles": 3, "quads": 4, "points": 0, "lines": 2}                        # indices per element
+
+
+def mesh(positions, triangles=None, quads=None, points=None, lines=None, normals=None, texcoords=None, colors=None, radius=None) -> dict:
+    """one shape as vpt_shape_data takes it: a dictionary of contiguous float32 / int32 arrays, None (or empty) for what the shape has not"""
+    given = dict(positions=positions, triangles=triangles, quads=quads, points=points, lines=lines, normals=normals, texcoords=texcoords, colors=colors, radius=radius)
+    out = {}
+    for key, width in MESH_FLOATS.items():
+        a = given[key]
+        out[key] = None if a is None or len(a) == 0 else np.ascontiguousarray(a, np.float32).reshape((-1, width) if width else (-1,)).copy()
+    for key, width in MESH_ELEMENTS.items():
+        a = given[key]
+        out[key] = None if a is None or len(a) == 0 else np.ascontiguousarray(a, np.int32).reshape((-1, width) if width else (-1,)).copy()
+    return out
+
+
+class ShapeEdit:
+    """What vpt_scene_update_shapes takes (include/vpt.h: vpt_shape_edit): `set`, a dictionary current id -> mesh (the dictionary mesh()
+    makes) that replaces those shapes whole; `remove`, current ids erased after that (ids close up, the instances' shape ids follow; no
+    instance may name a removed shape); `add`, a list of meshes appended after the survivors.  HostScene.update_shapes makes one;
+    DeviceScene.update_shapes / MultiDeviceScene.update_shapes / RenderSession.edit_shapes apply it.
+    Importing an object into a running scene is a ShapeEdit followed by an InstanceEdit: add_shape(...) returns the id the shape has after
+    update_shapes(); once that edit is handed out, add_instance(frame, id, material) and update_instances() put it in place."""
+
+    def __init__(self, remove=(), set=None, add=()):
+        self.remove = tuple(int(i) for i in remove)
+        self.set = {int(k): mesh(**v) for k, v in dict(set or {}).items()}
+        self.add = [mesh(**v) for v in add]
+
+    def empty(self) -> bool:
+        return not (self.remove or self.set or self.add)
+
+    @staticmethod
+    def _records(meshes):
+        out = (VptShapeData * max(len(meshes), 1))()
+        ptr = lambda a: None if a is None else a.ctypes.data
+        for rec, m in zip(out, meshes):
+            rec.num_vertices = 0 if m["positions"] is None else len(m["positions"])
+            for key in MESH_FLOATS:
+                setattr(rec, key, ptr(m[key]))
+            for key in MESH_ELEMENTS:
+                setattr(rec, "num_" + key, 0 if m[key] is None else len(m[key]))
+                setattr(rec, key, ptr(m[key]))
+        return out
+
+    def to_abi(self):
+        """(VptShapeEdit, the arrays it points into: keep them alive across the call)"""
+        remove, set_ids = np.array(self.remove, np.int32), np.array(list(self.set.keys()), np.int32)
+        set_rec, add_rec = self._records(list(self.set.values())), self._records(self.add)
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        abi = VptShapeEdit(len(remove), ptr(remove), len(set_ids), ptr(set_ids), C.addressof(set_rec) if self.set else None, len(self.add),
+                           C.addressof(add_rec) if self.add else None)
+        return abi, [remove, set_ids, set_rec, add_rec, self.set, self.add]
+
+
 class SceneEdit:
     """What vpt_scene_update takes (include/vpt.h: vpt_scene_edit), as dictionaries id -> value: cameras (VptCamera), instances and
     environments ((12,) float32 frames x, y, z, o), materials (VptMaterial), shapes ((positions, normals or None) as (n, 3) float32).
@@ -461,6 +530,11 @@ hip.vpt_multi_update_instances.argtypes = [_p, C.POINTER(VptInstanceEdit)]
 hip.vpt_session_edit_instances.argtypes = [_p, C.POINTER(VptInstanceEdit)]
 hip.vpt_scene_get_instances.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int)]
 hip.vpt_scene_instance_tables_hash.argtypes = [_p, _p]
+hip.vpt_scene_update_shapes.argtypes = [_p, C.POINTER(VptShapeEdit)]
+hip.vpt_multi_update_shapes.argtypes = [_p, C.POINTER(VptShapeEdit)]
+hip.vpt_session_edit_shapes.argtypes = [_p, C.POINTER(VptShapeEdit)]
+hip.vpt_scene_shape_tables_hash.argtypes = [_p, _p]
+hip.vpt_scene_get_shape_counts.argtypes = [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
 hip.vpt_scene_get_bvh_counts.argtypes = [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _p]
 hip.vpt_scene_get_bvh_prims.argtypes = [_p, _p, C.c_int, _p, C.c_int64]
 hip.vpt_scene_update_stats.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
@@ -545,6 +619,7 @@ host.vpth_scene_set_item.argtypes = [_p, C.c_int, C.c_int, _p, C.c_int64, C.c_ch
 host.vpth_scene_update_bvh.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_rebuild_bvh.argtypes = [_p, _p, C.c_int, C.c_int, C.c_char_p, C.c_int]
 host.vpth_scene_edit_instances.argtypes = [_p, _p, C.c_int, _p, _p, C.c_int, _p, C.c_int, C.c_char_p, C.c_int]
+host.vpth_scene_edit_shapes.argtypes = [_p, _p, C.c_int, _p, _p, C.c_int, _p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_scene_update_lights.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_free.restype = None
 host.vpth_scene_get_environment.argtypes = [_p, C.c_int, C.POINTER(VptEnvironment)]
@@ -979,10 +1054,14 @@ class HostScene:
     def _no_pending_instances(self, what: str) -> None:
         if getattr(self, "_inst_edit", None) is not None and not self._inst_edit.empty():
             raise VptError(f"{what}: hand the pending instance changes out with update_instances() first")
+        if getattr(self, "_shape_edit", None) is not None and not self._shape_edit.empty():
+            raise VptError(f"{what}: hand the pending shape changes out with update_shapes() first")
 
     def _begin_instance_change(self, what: str) -> InstanceEdit:
         if getattr(self, "_edit", None) is not None and (self._edit.instances or self._edit.shapes):
             raise VptError(f"{what}: hand the pending edit out with update_bvh() first (its ids name the instances as they are now)")
+        if getattr(self, "_shape_edit", None) is not None and not self._shape_edit.empty():
+            raise VptError(f"{what}: hand the pending shape changes out with update_shapes() first")
         return self._pending_instances()
 
     def _check_instance(self, what: str, frame, shape: int, material: int):
@@ -1032,6 +1111,8 @@ class HostScene:
         stats() describe the edited scene afterwards.  Returns the InstanceEdit for DeviceScene.update_instances."""
         if getattr(self, "_edit", None) is not None and (self._edit.instances or self._edit.shapes):
             raise VptError("update_instances: hand the pending edit out with update_bvh() first")
+        if getattr(self, "_shape_edit", None) is not None and not self._shape_edit.empty():
+            raise VptError("update_instances: hand the pending shape changes out with update_shapes() first")
         edit, self._inst_edit = self._pending_instances(), None
         if edit.empty():
             return edit
@@ -1042,6 +1123,92 @@ class HostScene:
             raise VptError(err.value.decode())
         del keep
         return edit
+
+    # -- the shape list (the host side of vpt_scene_update_shapes): add_shape / set_shape / remove_shapes note a change, ids naming the
+    #    list as it is now; update_shapes() applies them to the scene - set, then remove, then add - builds the new shapes' BVHs (and the
+    #    scene BVH when a shape was replaced) and the lights anew and hands the ShapeEdit out.  The ids of a pending SceneEdit or
+    #    InstanceEdit name the old list, so the kinds of change do not mix: each is handed out before another begins ---------------------
+    def _begin_shape_change(self, what: str) -> ShapeEdit:
+        if getattr(self, "_edit", None) is not None and (self._edit.instances or self._edit.shapes):
+            raise VptError(f"{what}: hand the pending edit out with update_bvh() first (its ids name the shapes as they are now)")
+        if getattr(self, "_inst_edit", None) is not None and not self._inst_edit.empty():
+            raise VptError(f"{what}: hand the pending instance changes out with update_instances() first")
+        if getattr(self, "_shape_edit", None) is None:
+            self._shape_edit = ShapeEdit()
+        return self._shape_edit
+
+    @staticmethod
+    def _check_mesh(what: str, m: dict) -> dict:
+        nv = 0 if m["positions"] is None else len(m["positions"])
+        kinds = [k for k in MESH_ELEMENTS if m[k] is not None]
+        if len(kinds) > 1:
+            raise VptError(f"{what}: a shape holds one kind of element, not {' and '.join(kinds)}")
+        for key in MESH_FLOATS:
+            if m[key] is not None and (len(m[key]) != nv or not np.all(np.isfinite(m[key]))):
+                raise VptError(f"{what}: {key} must be finite and one per vertex")
+        for key in kinds:
+            if m[key].min() < 0 or m[key].max() >= nv:
+                raise VptError(f"{what}: a vertex index of {key} is out of range")
+        if (m["points"] is not None or m["lines"] is not None) and m["radius"] is None:
+            raise VptError(f"{what}: a shape of points or lines needs one radius per vertex")
+        return m
+
+    def add_shape(self, positions, triangles=None, quads=None, points=None, lines=None, normals=None, texcoords=None, colors=None, radius=None) -> int:
+        """notes a new shape, appended at update_shapes(); returns the id it has afterwards (given the removals noted so far)"""
+        pend = self._begin_shape_change("add_shape")
+        pend.add.append(self._check_mesh("add_shape", mesh(positions, triangles, quads, points, lines, normals, texcoords, colors, radius)))
+        return self.count("shapes") - len(pend.remove) + len(pend.add) - 1
+
+    def set_shape(self, index: int, positions, triangles=None, quads=None, points=None, lines=None, normals=None, texcoords=None, colors=None,
+                  radius=None) -> None:
+        """notes another mesh - the whole of it - for shape `index` (current id), applied at update_shapes()"""
+        pend = self._begin_shape_change("set_shape")
+        index = int(index)
+        if not 0 <= index < self.count("shapes"):
+            raise VptError(f"set_shape: shape {index} out of range")
+        if index in pend.remove:
+            raise VptError(f"set_shape: shape {index} is also removed")
+        pend.set[index] = self._check_mesh("set_shape", mesh(positions, triangles, quads, points, lines, normals, texcoords, colors, radius))
+
+    def remove_shapes(self, ids) -> None:
+        """notes shapes (current ids) to erase at update_shapes(): the survivors keep their order, the ids close up and the instances'
+        shape ids follow.  No instance may name a removed shape: remove or re-point its instances first (update_instances)."""
+        pend = self._begin_shape_change("remove_shapes")
+        ids = [int(i) for i in ids]
+        for i in ids:
+            if not 0 <= i < self.count("shapes"):
+                raise VptError(f"remove_shapes: shape {i} out of range")
+            if i in pend.set:
+                raise VptError(f"remove_shapes: shape {i} is also set")
+        if len(set(ids)) != len(ids) or set(ids) & set(pend.remove):
+            raise VptError("remove_shapes: an id is repeated")
+        named = {self.instance_ids(i)[0] for i in range(self.count("instances"))}
+        if named & set(ids):
+            raise VptError(f"remove_shapes: shapes {sorted(named & set(ids))} are still named by instances")
+        pend.remove = pend.remove + tuple(ids)
+
+    def update_shapes(self) -> ShapeEdit:
+        """edit_shapes of the host library over what add_shape / set_shape / remove_shapes noted since the last call: replace / erase /
+        push_back on the scene's shapes, the instances' shape ids renumbered, make_bvh of the new shapes (the scene BVH too when a shape
+        was replaced), make_lights; desc / stats() describe the edited scene afterwards.  Returns the ShapeEdit for
+        DeviceScene.update_shapes."""
+        if getattr(self, "_edit", None) is not None and (self._edit.instances or self._edit.shapes):
+            raise VptError("update_shapes: hand the pending edit out with update_bvh() first")
+        self._no_pending_instances_only("update_shapes")
+        edit, self._shape_edit = (self._shape_edit if getattr(self, "_shape_edit", None) is not None else ShapeEdit()), None
+        if edit.empty():
+            return edit
+        abi, keep = edit.to_abi()
+        err = C.create_string_buffer(512)
+        if host.vpth_scene_edit_shapes(self.handle, abi.remove_ids, abi.num_remove, abi.set_ids, abi.set, abi.num_set, abi.add, abi.num_add,
+                                       err, len(err)) != 0:
+            raise VptError(err.value.decode())
+        del keep
+        return edit
+
+    def _no_pending_instances_only(self, what: str) -> None:
+        if getattr(self, "_inst_edit", None) is not None and not self._inst_edit.empty():
+            raise VptError(f"{what}: hand the pending instance changes out with update_instances() first")
 
     # -- environments and textures (the host side of vpt_scene_update_textures): the setters change the scene and note the change in
     #    the pending TextureEdit; desc, lights() and stats() follow at update_textures(), which hands that edit out ----------------
@@ -1421,6 +1588,27 @@ class DeviceScene:
         _check(hip.vpt_scene_update_instances(self.handle, C.byref(abi)), "vpt_scene_update_instances")
         del keep
 
+    def update_shapes(self, edit: ShapeEdit) -> None:
+        """vpt_scene_update_shapes (include/vpt.h): shapes replaced, removed and added on the device; pools, BVHs, instances and lights
+        follow.  Afterwards the handle renders the bits of a DeviceScene made from the host scene after the same
+        HostScene.update_shapes()."""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_scene_update_shapes(self.handle, C.byref(abi)), "vpt_scene_update_shapes")
+        del keep
+
+    def shape_tables_hash(self):
+        """FNV-1a of the eight groups of tables laid out in shape order (vpt_scene_shape_tables_hash): shapes, vertex pools, elems,
+        leaf_prims, leaf_attrs, the compact records (0: none), shape nodes, shape quad nodes"""
+        out = np.zeros(8, np.uint64)
+        _check(hip.vpt_scene_shape_tables_hash(self.handle, out.ctypes.data), "vpt_scene_shape_tables_hash")
+        return tuple(int(x) for x in out)
+
+    def get_shape_counts(self):
+        """(shapes, pooled elements, pooled vertices) as the device holds them (vpt_scene_get_shape_counts)"""
+        a, b, c = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        _check(hip.vpt_scene_get_shape_counts(self.handle, C.byref(a), C.byref(b), C.byref(c)), "vpt_scene_get_shape_counts")
+        return a.value, b.value, c.value
+
     def get_instances(self) -> np.ndarray:
         """the instances as the device holds them, an INSTANCE array: forward frame, shape, material (vpt_scene_get_instances)"""
         n = C.c_int(0)
@@ -1438,9 +1626,10 @@ class DeviceScene:
     def get_bvh_counts(self):
         """(scene nodes, pooled shape nodes, first node of every shape as int64) as the device holds them (vpt_scene_get_bvh_counts)"""
         a, b = C.c_int32(0), C.c_int64(0)
-        offsets = np.zeros(max(1, self.host_scene.count("shapes")), np.int64)
+        shapes = self.get_shape_counts()[0]   # the device's count: update_shapes changes it
+        offsets = np.zeros(max(1, shapes), np.int64)
         _check(hip.vpt_scene_get_bvh_counts(self.handle, C.byref(a), C.byref(b), offsets.ctypes.data), "vpt_scene_get_bvh_counts")
-        return a.value, b.value, offsets[:self.host_scene.count("shapes")]
+        return a.value, b.value, offsets[:shapes]
 
     def get_bvh(self):
         """(scene nodes, pooled shape nodes) as the device holds them, BVH_NODE arrays at the current counts (vpt_scene_get_bvh)"""
@@ -1451,10 +1640,9 @@ class DeviceScene:
 
     def get_bvh_prims(self):
         """(scene primitive order, pooled shape primitive orders) as the device holds them, int32 (vpt_scene_get_bvh_prims)"""
-        _, shape_prims = self.host_scene.bvh_prims()   # element counts never change: the pooled size is the descriptor's
-        n = C.c_int(0)                                 # the instances' count may: update_instances
+        n = C.c_int(0)                                 # the counts are the device's: update_instances and update_shapes change them
         _check(hip.vpt_scene_get_instances(self.handle, None, 0, C.byref(n)), "vpt_scene_get_instances")
-        a, b = np.zeros(n.value, np.int32), np.zeros(len(shape_prims), np.int32)
+        a, b = np.zeros(n.value, np.int32), np.zeros(self.get_shape_counts()[1], np.int32)
         _check(hip.vpt_scene_get_bvh_prims(self.handle, a.ctypes.data, len(a), b.ctypes.data, len(b)), "vpt_scene_get_bvh_prims")
         return a, b
 
@@ -1569,6 +1757,12 @@ class MultiDeviceScene:
         """vpt_multi_update_instances: DeviceScene.update_instances with the same edit on every device"""
         abi, keep = edit.to_abi()
         _check(hip.vpt_multi_update_instances(self.handle, C.byref(abi)), "vpt_multi_update_instances")
+        del keep
+
+    def update_shapes(self, edit: ShapeEdit) -> None:
+        """vpt_multi_update_shapes: DeviceScene.update_shapes with the same edit on every device"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_multi_update_shapes(self.handle, C.byref(abi)), "vpt_multi_update_shapes")
         del keep
 
     def pathtrace_samples(self, state: PathtraceState, params: PathtraceParams, count: int = 1) -> None:
@@ -1883,6 +2077,13 @@ class RenderSession:
         refused edit leaves the session as it was"""
         abi, keep = edit.to_abi()
         _check(hip.vpt_session_edit_instances(self.handle, C.byref(abi)), "vpt_session_edit_instances")
+        del keep
+
+    def edit_shapes(self, edit: ShapeEdit) -> None:
+        """vpt_scene_update_shapes on the session's scene with the ShapeEdit of HostScene.update_shapes(), then a reset; a refused edit
+        leaves the session as it was"""
+        abi, keep = edit.to_abi()
+        _check(hip.vpt_session_edit_shapes(self.handle, C.byref(abi)), "vpt_session_edit_shapes")
         del keep
 
     @property

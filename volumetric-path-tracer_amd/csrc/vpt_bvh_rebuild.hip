@@ -120,6 +120,7 @@ void scene_level_swap(resident& r, scene_level& lv, const scene_tables& t) {
   d.scene_root_lo_x = t.d.scene_root_lo_x, d.scene_root_lo_y = t.d.scene_root_lo_y, d.scene_root_lo_z = t.d.scene_root_lo_z;
   d.scene_root_hi_x = t.d.scene_root_hi_x, d.scene_root_hi_y = t.d.scene_root_hi_y, d.scene_root_hi_z = t.d.scene_root_hi_z;
   r.h.slot_of = lv.slot_of;
+  r.scene_depth = t.scene_depth, r.scene_need4 = t.scene_need4;
   r.refit.ready = false;   // levels and quad slots belong to the old trees: the next refit makes them anew
 }
 
@@ -234,7 +235,7 @@ int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks&
   adopt(r.tables, old_shape_nodes, std::move(n_shape_nodes)), adopt(r.tables, old_shapes, std::move(n_shapes));
   scene_level_swap(r, lv, t);
   r.num_shape_nodes = total, m.shapes = t.shapes;
-  r.num_shape_wnodes = (long long)t.shape_wnodes, r.shape_depth = t.shape_depth, r.shape_need4 = t.shape_need4;
+  r.num_shape_wnodes = (long long)t.shape_wnodes, r.shape_depth = t.shape_depths, r.shape_need4 = t.shape_need4s, r.shape_quads = t.shape_quads;
   stacks.rebuilt = true, stacks.stack_cap = t.stack_cap, stacks.stack_lds4 = t.stack_lds4, stacks.stack_spill4 = t.stack_spill4;
 
   // 7. what hangs on the shapes' root boxes outside the BVHs: the mesh lights' records

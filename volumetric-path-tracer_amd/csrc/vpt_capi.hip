@@ -25,6 +25,7 @@
 #include "vpt_schedule.h"
 #include "vpt_scene_prep.h"
 #include "vpt_scene_update.h"
+#include "vpt_shape_update.h"
 #include "vpt_texture_update.h"
 #include "vpt_volume_update.h"
 
@@ -182,7 +183,9 @@ int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* 
   D.shape_wnodes = D.scene_wnodes + t.scene_wnodes;
   s->stack_cap = t.stack_cap, s->stack_lds4 = t.stack_lds4, s->stack_spill4 = t.stack_spill4, s->light_features = t.light_features;
   s->curves = t.curves, s->varying_media = t.varying_media, s->num_shape_nodes = d.num_shape_bvh_nodes;
-  s->num_shape_wnodes = (long long)t.shape_wnodes, s->shape_depth = t.shape_depth, s->shape_need4 = t.shape_need4;
+  s->num_shape_wnodes = (long long)t.shape_wnodes, s->shape_depth = t.shape_depths, s->shape_need4 = t.shape_need4s, s->shape_quads = t.shape_quads;
+  s->scene_depth = t.scene_depth, s->scene_need4 = t.scene_need4;
+  s->num_positions = d.num_positions, s->num_normals = d.num_normals, s->num_texcoords = d.num_texcoords, s->num_colors = d.num_colors;
   s->h = std::move(t.h), s->m = std::move(t.m);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -561,6 +564,55 @@ int vpt_scene_update_instances(vpt_scene* s, const vpt_instance_edit* edit) {
   if (res.lights_rebuilt)
     if (int rc = medium_setup(s)) return rc;   // the medium records sit behind the light records, which were made anew
   s->sched.forget();
+  return VPT_OK;
+}
+// the shape list changed (vpt_shape_update.hip); the render side follows: stack sizes, the kernel instances, light_prims
+int vpt_scene_update_shapes(vpt_scene* s, const vpt_shape_edit* edit) {
+  if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call replaces
+  bvh_rebuild_stacks  st;
+  shape_update_result res;
+  if (int rc = shape_update_apply(*s, *edit, st, res)) return rc;
+  if (!st.rebuilt) return VPT_OK;
+  if (st.stack_spill4 != s->stack_spill4) s->spill_lanes = 0;   // the HBM part is sized per entry: made anew by the next launch
+  s->stack_cap = st.stack_cap, s->stack_lds4 = st.stack_lds4, s->stack_spill4 = st.stack_spill4;
+  s->curves = res.curves;
+  if (int rc = light_setup(s)) return rc;   // light_prims read the leaf records through the shape table: both are new
+  if (res.lights_rebuilt)
+    if (int rc = medium_setup(s)) return rc;   // the medium records sit behind the light records, which were made anew
+  s->sched.forget();
+  return VPT_OK;
+}
+// FNV-1a over the tables laid out in shape order, read back from the device (include/vpt.h names the eight groups)
+int vpt_scene_shape_tables_hash(vpt_scene* s, uint64_t out[8]) {
+  if (!s || !out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t slots = s->h.prim_slot.size();
+  const struct { const void* table; size_t bytes; int slot; } parts[12] = {{s->d.shapes, (size_t)s->d.num_shapes * sizeof(DShape), 0},
+      {s->d.positions, (size_t)s->num_positions * sizeof(float4), 1}, {s->d.normals, (size_t)s->num_normals * sizeof(float4), 1},
+      {s->d.texcoords, (size_t)s->num_texcoords * sizeof(float2), 1}, {s->d.colors, (size_t)s->num_colors * sizeof(float4), 1},
+      {s->d.elems, slots * sizeof(int4), 2}, {s->d.leaf_prims, (4 * slots + 8) * sizeof(float4), 3}, {s->d.leaf_attrs, 6 * slots * sizeof(float4), 4},
+      {s->d.tri_prims, s->d.tri_prims ? (3 * slots + 8) * sizeof(float4) : 0, 5}, {s->d.tri_attrs, s->d.tri_attrs ? 4 * slots * sizeof(float4) : 0, 5},
+      {s->d.shape_nodes, (size_t)s->num_shape_nodes * sizeof(vpt_bvh_node), 6}, {s->d.shape_wnodes, (size_t)s->num_shape_wnodes * sizeof(float4), 7}};
+  for (int k = 0; k < 8; k++) out[k] = 14695981039346656037ull;
+  std::vector<unsigned char> host;
+  for (const auto& p : parts) {
+    host.resize(p.bytes);
+    if (p.bytes) HIP_TRY(hipMemcpy(host.data(), p.table, p.bytes, hipMemcpyDeviceToHost));
+    uint64_t hash = out[p.slot];
+    for (unsigned char b : host) hash = (hash ^ b) * 1099511628211ull;
+    out[p.slot] = hash;
+  }
+  if (!s->d.tri_prims) out[5] = 0;
+  return VPT_OK;
+}
+int vpt_scene_get_shape_counts(vpt_scene* s, int32_t* num_shapes, int64_t* num_elements, int64_t* num_vertices) {
+  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (num_shapes) *num_shapes = s->d.num_shapes;
+  if (num_elements) *num_elements = (int64_t)s->h.prim_slot.size();
+  if (num_vertices) *num_vertices = s->num_positions;
   return VPT_OK;
 }
 int vpt_scene_get_instances(vpt_scene* s, vpt_instance* out, int capacity, int* num_instances) {

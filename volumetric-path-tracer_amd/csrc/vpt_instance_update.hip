@@ -194,7 +194,7 @@ int instance_update_apply(resident& r, const vpt_instance_edit& e, bvh_rebuild_s
   desc.num_scene_bvh_nodes = lv.count, desc.scene_bvh_nodes = lv.h_nodes.data();
   scene_tables t;
   t.d = d, t.shapes = m.shapes;
-  t.shape_wnodes = (size_t)r.num_shape_wnodes, t.shape_depth = r.shape_depth, t.shape_need4 = r.shape_need4;
+  t.shape_wnodes = (size_t)r.num_shape_wnodes, t.shape_depth = most_of(r.shape_depth), t.shape_need4 = most_of(r.shape_need4);
   if (int rc = prep_quad_nodes_and_stacks(desc, t, true)) return rc;
   // the quad-node table: the scene's part from the host, the shapes' part as it is, device to device
   if (int rc = lv.wnodes.allocate((t.scene_wnodes + t.shape_wnodes) * sizeof(float4))) return rc;

@@ -357,6 +357,12 @@ int vpt_multi_update_instances(vpt_multi* m, const vpt_instance_edit* edit) {
     if (int rc = vpt_scene_update_instances(p.scene, edit)) return rc;
   return VPT_OK;
 }
+int vpt_multi_update_shapes(vpt_multi* m, const vpt_shape_edit* edit) {
+  if (!m || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  for (auto& p : m->parts)   // as vpt_multi_update: every device holds the same scene, so the first one's refusal is everyone's
+    if (int rc = vpt_scene_update_shapes(p.scene, edit)) return rc;
+  return VPT_OK;
+}
 
 int vpt_multi_device_count(const vpt_multi* m) { return m ? (int)m->parts.size() : 0; }
 

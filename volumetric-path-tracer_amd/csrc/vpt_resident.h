@@ -2,6 +2,7 @@
 // _textures, _volumes, and vpt_scene_rebuild_bvh): the tables on the device, their host mirrors, and what an edit keeps between calls.  vpt_capi.hip's
 // vpt_scene is a `resident` plus its render side (schedule, staging, stacks); the four update units see only this.
 #pragma once
+#include <algorithm>
 #include <vector>
 
 #include "vpt_device_buffer.h"
@@ -28,6 +29,8 @@ struct refit_tables {
   device_buffer d_inst_box;     // 2 float4 per instance: transform_bbox(frame, shape root box)
 };
 
+inline int most_of(const std::vector<int>& v) { return v.empty() ? 0 : std::max(0, *std::max_element(v.begin(), v.end())); }
+
 struct resident {
   int                        device = 0;
   DScene                     d      = {};
@@ -35,8 +38,12 @@ struct resident {
   host_mirrors h;                      // range checks of vpt_intersect, vpt_kat; sizes of a vertex edit
   edit_mirrors m;                      // as vpt_scene_create made them, as the last edit left them
   long long    num_shape_nodes = 0;    // nodes of d.shape_nodes
-  long long    num_shape_wnodes = 0;   // float4s of d.shape_wnodes; with the two below, what prep_quad_nodes_and_stacks found of the shapes'
-  int          shape_depth = 0, shape_need4 = 0;   // trees: an edit that builds the scene BVH alone decides the traversal limits from them
+  long long    num_shape_wnodes = 0;   // float4s of d.shape_wnodes; with the vectors below, what prep_quad_nodes_and_stacks found of the
+  // shapes' trees, per shape: binary depth, quad-stack need, quad nodes.  An edit that builds the scene BVH alone decides the traversal
+  // limits from their maxima (vpt_instance_update.hip); one that changes the shape list keeps the untouched shapes' (vpt_shape_update.hip)
+  std::vector<int> shape_depth, shape_need4, shape_quads;
+  int          scene_depth = 0, scene_need4 = 0;   // the same of the scene BVH, for an edit that keeps it
+  long long    num_positions = 0, num_normals = 0, num_texcoords = 0, num_colors = 0;   // entries of the four vertex pools
   int          light_features  = 0;      // VPT_FEAT_* bits this scene's lights need from the mesh kernels
   bool         varying_media   = false;  // prep_media_vary of m.materials: K1's general instance, which carries a path's medium in registers
   refit_tables refit;

@@ -166,34 +166,19 @@ int validate(const vpt_scene_desc& d, const vpt_scene_curves& cs) {
     REQUIRE(s.color_offset == -1 || (s.color_offset >= 0 && (long long)s.color_offset + s.num_vertices <= d.num_colors), "shape %d: colors out of range", i);
     REQUIRE(s.num_triangles >= 0 && s.triangle_offset >= 0 && (long long)s.triangle_offset + s.num_triangles <= d.num_triangles, "shape %d: triangles out of range", i);
     REQUIRE(s.num_quads >= 0 && s.quad_offset >= 0 && (long long)s.quad_offset + s.num_quads <= d.num_quads, "shape %d: quads out of range", i);
-    REQUIRE(s.num_triangles == 0 || s.num_quads == 0, "shape %d: both triangles and quads", i);
     long long nel = s.num_triangles ? s.num_triangles : s.num_quads;
     const vpt_shape_curves c = curves_of(cs, i);
     REQUIRE(c.num_points >= 0 && c.point_offset >= 0 && (long long)c.point_offset + c.num_points <= cs.num_points, "shape %d: points out of range", i);
     REQUIRE(c.num_lines >= 0 && c.line_offset >= 0 && (long long)c.line_offset + c.num_lines <= cs.num_lines, "shape %d: lines out of range", i);
     if (c.num_points || c.num_lines) {
-      // the reference's BVH tests points, then lines, then faces; its eval_* functions faces first: a mixed shape has no single behaviour
-      if ((c.num_points != 0) + (c.num_lines != 0) + (nel != 0) > 1)
-        return vpt_set_error(VPT_ERR_UNSUPPORTED, "shape %d mixes points, lines and faces", i);
-      REQUIRE(c.radius_offset >= 0 && (long long)c.radius_offset + s.num_vertices <= cs.num_radius, "shape %d: radius out of range", i);
-      for (long long k = 0; k < c.num_points; k++) {
-        int v = cs.points[c.point_offset + k];
-        REQUIRE(v >= 0 && v < s.num_vertices, "shape %d: point vertex index out of range", i);
-      }
-      for (long long k = 0; k < 2LL * c.num_lines; k++) {
-        int v = cs.lines[2LL * c.line_offset + k];
-        REQUIRE(v >= 0 && v < s.num_vertices, "shape %d: line vertex index out of range", i);
-      }
+      REQUIRE((c.num_points != 0) + (c.num_lines != 0) + (nel != 0) > 1 || (c.radius_offset >= 0 && (long long)c.radius_offset + s.num_vertices <= cs.num_radius),
+          "shape %d: radius out of range", i);
       nel = c.num_points ? c.num_points : c.num_lines;
     }
-    for (long long k = 0; k < 3LL * s.num_triangles; k++) {
-      int v = d.triangles[3LL * s.triangle_offset + k];
-      REQUIRE(v >= 0 && v < s.num_vertices, "shape %d: triangle vertex index out of range", i);
-    }
-    for (long long k = 0; k < 4LL * s.num_quads; k++) {
-      int v = d.quads[4LL * s.quad_offset + k];
-      REQUIRE(v >= 0 && v < s.num_vertices, "shape %d: quad vertex index out of range", i);
-    }
+    if (int rc = prep_check_shape_elements(i, s.num_vertices, s.num_triangles ? d.triangles + 3LL * s.triangle_offset : nullptr, s.num_triangles,
+            s.num_quads ? d.quads + 4LL * s.quad_offset : nullptr, s.num_quads, c.num_points ? cs.points + c.point_offset : nullptr, c.num_points,
+            c.num_lines ? cs.lines + 2LL * c.line_offset : nullptr, c.num_lines))
+      return rc;
     REQUIRE(s.num_bvh_nodes >= 0 && s.bvh_node_offset >= 0 && (long long)s.bvh_node_offset + s.num_bvh_nodes <= d.num_shape_bvh_nodes, "shape %d: bvh nodes out of range", i);
     REQUIRE(s.bvh_prim_offset >= 0 && (long long)s.bvh_prim_offset + nel <= d.num_shape_bvh_prims, "shape %d: bvh prims out of range", i);
     if (int rc = check_nodes(d.shape_bvh_nodes + s.bvh_node_offset, s.num_bvh_nodes, nel, "shape")) return rc;
@@ -514,6 +499,18 @@ int prep_check_material(const vpt_material& m, int i, int num_textures, bool tex
   REQUIRE(tex_ok(m.emission_tex) && tex_ok(m.color_tex) && tex_ok(m.roughness_tex) && tex_ok(m.scattering_tex) && tex_ok(m.normal_tex), "material %d: texture id out of range", i);
   return VPT_OK;
 }
+int prep_check_shape_elements(int i, int num_vertices, const int32_t* triangles, int num_triangles, const int32_t* quads, int num_quads, const int32_t* points,
+    int num_points, const int32_t* lines, int num_lines) {
+  REQUIRE(num_triangles == 0 || num_quads == 0, "shape %d: both triangles and quads", i);
+  // the reference's BVH tests points, then lines, then faces; its eval_* functions faces first: a mixed shape has no single behaviour
+  if ((num_points || num_lines) && (num_points != 0) + (num_lines != 0) + (num_triangles != 0 || num_quads != 0) > 1)
+    return vpt_set_error(VPT_ERR_UNSUPPORTED, "shape %d mixes points, lines and faces", i);
+  const struct { const int32_t* v; long long n; const char* what; } lists[4] = {{points, num_points, "point"}, {lines, 2LL * num_lines, "line"},
+      {triangles, 3LL * num_triangles, "triangle"}, {quads, 4LL * num_quads, "quad"}};
+  for (const auto& l : lists)
+    for (long long k = 0; k < l.n; k++) REQUIRE(l.v[k] >= 0 && l.v[k] < num_vertices, "shape %d: %s vertex index out of range", i, l.what);
+  return VPT_OK;
+}
 bool prep_media_vary(const vpt_material* materials, int num_materials, const int* inst_material, const int* inst_flags, int num_instances) {
   if (num_materials > 65534) return true;
   for (int i = 0; i < num_instances; i++) {
@@ -637,27 +634,37 @@ void prep_enter_tail(float4* e, const DShape& sh, int scene_quads, int instance,
 // quad nodes of every BVH, the shapes' roots and stack needs, and the traversal stacks sized from them.  The stack sizes and the
 // VPT_FLOOR_SHIFT check depend on the trees' topology only: vpt_scene_update refits boxes and keeps topology, so they stay valid;
 // vpt_scene_rebuild_bvh (vpt_bvh_rebuild.hip) changes topology and calls this again, on the node arrays it built (vpt_scene_prep.h).
-int prep_quad_nodes_and_stacks(const vpt_scene_desc& d, scene_tables& t, bool shapes_kept) {
+int prep_quad_nodes_and_stacks(const vpt_scene_desc& d, scene_tables& t, bool shapes_kept, const char* shape_made, bool scene_kept) {
   std::vector<float4> shape_wnodes;
   int max_shape_depth = shapes_kept ? t.shape_depth : 0, max_shape_need4 = shapes_kept ? t.shape_need4 : 0;
+  long long shape_quads = 0;   // quad nodes of all shapes, the kept ones of a partial call included
+  if (!shapes_kept && !shape_made) t.shape_depths.assign((size_t)d.num_shapes, 0), t.shape_need4s.assign((size_t)d.num_shapes, 0), t.shape_quads.assign((size_t)d.num_shapes, 0);
   for (int i = 0; i < d.num_shapes && !shapes_kept; i++) {
-    const vpt_shape& sh = d.shapes[i];
     DShape& o = t.shapes[i];
-    o.wnode_offset = (int)(shape_wnodes.size() / 8);
-    int need4 = 0;
-    o.root_ref     = build_quad_nodes(d.shape_bvh_nodes + sh.bvh_node_offset, sh.num_bvh_nodes, shape_wnodes, o.root_box, &need4);
-    int depth = o.num_nodes ? bvh_depth(d.shape_bvh_nodes + sh.bvh_node_offset, sh.num_bvh_nodes, 0, 0, 4096) : 0;
-    o.stack_need = depth + 2;
-    if (depth > max_shape_depth) max_shape_depth = depth;
-    if (need4 > max_shape_need4) max_shape_need4 = need4;
+    if (shape_quads > 0x7fffffffLL) return vpt_set_error(VPT_ERR_UNSUPPORTED, "more than 2^27 quad nodes");
+    o.wnode_offset = (int)shape_quads;
+    if (!shape_made || shape_made[i]) {
+      const vpt_shape& sh = d.shapes[i];
+      const size_t before = shape_wnodes.size();
+      int need4 = 0;
+      o.root_ref     = build_quad_nodes(d.shape_bvh_nodes + sh.bvh_node_offset, sh.num_bvh_nodes, shape_wnodes, o.root_box, &need4);
+      int depth = o.num_nodes ? bvh_depth(d.shape_bvh_nodes + sh.bvh_node_offset, sh.num_bvh_nodes, 0, 0, 4096) : 0;
+      o.stack_need = depth + 2;
+      t.shape_depths[(size_t)i] = depth, t.shape_need4s[(size_t)i] = need4, t.shape_quads[(size_t)i] = (int)((shape_wnodes.size() - before) / 8);
+    }
+    shape_quads += t.shape_quads[(size_t)i];
+    if (t.shape_depths[(size_t)i] > max_shape_depth) max_shape_depth = t.shape_depths[(size_t)i];
+    if (t.shape_need4s[(size_t)i] > max_shape_need4) max_shape_need4 = t.shape_need4s[(size_t)i];
   }
   DScene& D = t.d;
-  int scene_depth = d.num_scene_bvh_nodes ? bvh_depth(d.scene_bvh_nodes, d.num_scene_bvh_nodes, 0, 0, 4096) : 0;
-  float scene_box[6];
-  int scene_need4 = 0;
-  D.scene_root_ref = build_quad_nodes(d.scene_bvh_nodes, d.num_scene_bvh_nodes, t.wnodes, scene_box, &scene_need4);
-  D.scene_root_lo_x = scene_box[0], D.scene_root_lo_y = scene_box[1], D.scene_root_lo_z = scene_box[2];
-  D.scene_root_hi_x = scene_box[3], D.scene_root_hi_y = scene_box[4], D.scene_root_hi_z = scene_box[5];
+  if (!scene_kept) {
+    t.scene_depth = d.num_scene_bvh_nodes ? bvh_depth(d.scene_bvh_nodes, d.num_scene_bvh_nodes, 0, 0, 4096) : 0;
+    float scene_box[6];
+    D.scene_root_ref = build_quad_nodes(d.scene_bvh_nodes, d.num_scene_bvh_nodes, t.wnodes, scene_box, &t.scene_need4);
+    D.scene_root_lo_x = scene_box[0], D.scene_root_lo_y = scene_box[1], D.scene_root_lo_z = scene_box[2];
+    D.scene_root_hi_x = scene_box[3], D.scene_root_hi_y = scene_box[4], D.scene_root_hi_z = scene_box[5];
+  }
+  const int scene_depth = t.scene_depth, scene_need4 = t.scene_need4;
   // stack entries alive at once: one pending sibling per level (+ the two just pushed), scene level
   // entries stay below the entries of the instance being traversed
   int need = (scene_depth + 2) + (max_shape_depth + 2);
@@ -688,8 +695,8 @@ int prep_quad_nodes_and_stacks(const vpt_scene_desc& d, scene_tables& t, bool sh
     fprintf(stderr, "[vpt] binary depth scene %d shape %d; quad stack need scene %d + shape %d + 1 -> %d in LDS + %d in HBM\n",
         scene_depth, max_shape_depth, scene_need4, max_shape_need4, t.stack_lds4, t.stack_spill4);
   // one table: [scene quad nodes][shape quad nodes]
-  t.scene_wnodes = t.wnodes.size();
-  if (!shapes_kept) t.shape_wnodes = shape_wnodes.size(), t.shape_depth = max_shape_depth, t.shape_need4 = max_shape_need4;
+  if (!scene_kept) t.scene_wnodes = t.wnodes.size();
+  if (!shapes_kept) t.shape_wnodes = 8 * (size_t)shape_quads, t.shape_depth = max_shape_depth, t.shape_need4 = max_shape_need4;
   if ((t.scene_wnodes + t.shape_wnodes) / 8 >= (1ull << 27)) return vpt_set_error(VPT_ERR_UNSUPPORTED, "more than 2^27 quad nodes");
   t.wnodes.insert(t.wnodes.end(), shape_wnodes.begin(), shape_wnodes.end());
   return VPT_OK;

@@ -49,6 +49,8 @@ struct scene_tables {
   std::vector<float4> wnodes;
   size_t              scene_wnodes = 0, shape_wnodes = 0;   // float4s of the two parts
   int                 shape_depth = 0, shape_need4 = 0;    // the deepest shape BVH, the largest quad-stack need of a shape
+  std::vector<int>    shape_depths, shape_need4s, shape_quads;   // the same per shape, and its quad nodes: the maxima are over these
+  int                 scene_depth = 0, scene_need4 = 0;    // of the scene BVH
   std::vector<float4> enter;
   std::vector<DInstance> instances;
   std::vector<float4> env_inv, sdf_inv;
@@ -87,7 +89,17 @@ void prep_quad_slots(const vpt_bvh_node* nodes, int count, std::vector<int>& slo
 // shapes_kept (vpt_scene_update_instances, vpt_instance_update.hip: only the scene BVH is new): the shapes' part is not made -
 // out.wnodes holds the scene's quad nodes alone, out.shapes is not written - and what the limits need to know of the shapes is read
 // from out.shape_depth / shape_need4 / shape_wnodes, which every call without the flag leaves there.
-int prep_quad_nodes_and_stacks(const vpt_scene_desc& desc, scene_tables& out, bool shapes_kept = false);
+// shape_made (vpt_scene_update_shapes, vpt_shape_update.hip: some shapes are new, the others keep their trees), one flag per shape:
+// quad nodes, root_ref, root_box and stack_need are made for the flagged shapes alone - out.wnodes holds theirs, in shape order, behind
+// the scene's - while a kept shape's depth, need and number of quad nodes are read from out.shape_depths / shape_need4s / shape_quads,
+// which every call without shapes_kept leaves there per shape; wnode_offset is numbered for all, out.shape_wnodes counts all.
+// scene_kept (the same unit, when the scene BVH stays): nothing of the scene BVH is made or read from `desc`; out.scene_depth,
+// scene_need4 and scene_wnodes, which every other call leaves there, are read instead, and out.d.scene_root_* is not written.
+int prep_quad_nodes_and_stacks(const vpt_scene_desc& desc, scene_tables& out, bool shapes_kept = false, const char* shape_made = nullptr, bool scene_kept = false);
+// validate()'s rules for the elements of one shape, for vpt_scene_create and for the shapes of a vpt_shape_edit: not both triangles and
+// quads; points, lines and faces not mixed (VPT_ERR_UNSUPPORTED); every vertex index in range.  The lists are the shape's own; i names it.
+int prep_check_shape_elements(int i, int num_vertices, const int32_t* triangles, int num_triangles, const int32_t* quads, int num_quads, const int32_t* points,
+    int num_points, const int32_t* lines, int num_lines);
 // the integer words of the enter record `e` (6 float4) of the scene-BVH slot that holds `instance`: e4.zw = root_ref, first quad node of
 // the shape in the one quad-node array (scene_quads = the scene BVH's own); e5 = leaf_offset, instance, translation_only, num_nodes
 void prep_enter_tail(float4* e, const DShape& shape, int scene_quads, int instance, int translation_only);

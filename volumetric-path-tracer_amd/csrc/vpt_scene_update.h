@@ -14,14 +14,15 @@ int scene_update_apply(resident& r, const vpt_scene_edit& edit, bool lights = fa
 // scene's layout; the instances, lights and leaf records are the scene's own.
 //  - upd_element_boxes: the bounds of a shape's elements in element order (6 floats each) from its leaf records, with the bound
 //    functions of the leaf refit, and old_slot[element] = the slot (local to the shape) that holds it
-//  - upd_shape_roots: DShape::root_box of every shape with nodes from its root node
+//  - upd_shape_roots: DShape::root_box of every shape with nodes from its root node (num_shapes < 0: the scene's count; vpt_scene_update_shapes,
+//    vpt_shape_update.hip, hands in a table of another length)
 //  - upd_instance_boxes: transform_bbox(frame, shape root box) per instance of `instances` (2 float4: the six floats first), invalidb3f
 //    for a shape without nodes
 //  - upd_enter_records: frames, root boxes and translation_only of `slots` enter records whose integer words are in place, from `instances`
 //    (the scene's own table, or the new one of vpt_scene_update_instances)
 //  - upd_light_records: frames and root boxes of the mesh lights' records
 int upd_element_boxes(resident& r, const DShape& shape, float* boxes, int* old_slot);
-int upd_shape_roots(resident& r, DShape* shapes, const float4* shape_nodes);
+int upd_shape_roots(resident& r, DShape* shapes, const float4* shape_nodes, int num_shapes = -1);
 int upd_instance_boxes(resident& r, const DInstance* instances, int num_instances, const DShape* shapes, float4* inst_box);
 int upd_enter_records(resident& r, float4* enter, int slots, const DInstance* instances, const DShape* shapes);
 int upd_light_records(resident& r, const DShape* shapes);

@@ -15,14 +15,12 @@
 
 #include "vpt_error.h"
 #include "vpt_launch.h"
+#include "vpt_record_bounds.hip.h"
 #include "vpt_scene_update.h"
 #include "vpt_update_helpers.h"
 
 namespace {
 
-struct box3 { float lo[3], hi[3]; };
-__device__ inline float sel_min(float a, float b) { return (a < b) ? a : b; }   // yocto_math.h:1355-1356: not fminf
-__device__ inline float sel_max(float a, float b) { return (a > b) ? a : b; }
 __device__ inline box3 invalid_box() {
   const float m = 3.402823466e+38f;
   return {{m, m, m}, {-m, -m, -m}};
@@ -49,29 +47,6 @@ __device__ inline void store_node_box(float4* nodes, long long i, const box3& b)
 }
 __device__ inline int node_start(const float4* nodes, long long i) { return __float_as_int(nodes[2 * i + 1].z); }
 __device__ inline int node_meta(const float4* nodes, long long i) { return __float_as_int(nodes[2 * i + 1].w); }
-
-// the bounds of the primitive in one leaf record (vpt_device.h): quad_bounds over the four corners (a triangle repeats its last
-// corner: min(p2, p2) == p2, the bits of triangle_bounds), point_bounds, line_bounds
-__device__ inline box3 record_bounds(const float4* r) {
-  float4 p0 = r[0], p1 = r[1], p2 = r[2], p3 = r[3];
-  const int kind = __float_as_int(p3.w);
-  box3 b;
-  if (kind == VPT_LEAF_POINT) {
-    const float rad = p1.x;
-    const float a[3] = {p0.x - rad, p0.y - rad, p0.z - rad}, c[3] = {p0.x + rad, p0.y + rad, p0.z + rad};
-    for (int k = 0; k < 3; k++) b.lo[k] = sel_min(a[k], c[k]), b.hi[k] = sel_max(a[k], c[k]);
-  } else if (kind == VPT_LEAF_LINE) {
-    const float r0 = p2.x, r1 = p2.y;
-    const float a0[3] = {p0.x - r0, p0.y - r0, p0.z - r0}, a1[3] = {p1.x - r1, p1.y - r1, p1.z - r1};
-    const float c0[3] = {p0.x + r0, p0.y + r0, p0.z + r0}, c1[3] = {p1.x + r1, p1.y + r1, p1.z + r1};
-    for (int k = 0; k < 3; k++) b.lo[k] = sel_min(a0[k], a1[k]), b.hi[k] = sel_max(c0[k], c1[k]);
-  } else {
-    const float q0[3] = {p0.x, p0.y, p0.z}, q1[3] = {p1.x, p1.y, p1.z}, q2[3] = {p2.x, p2.y, p2.z}, q3[3] = {p3.x, p3.y, p3.z};
-    for (int k = 0; k < 3; k++)
-      b.lo[k] = sel_min(q0[k], sel_min(q1[k], sel_min(q2[k], q3[k]))), b.hi[k] = sel_max(q0[k], sel_max(q1[k], sel_max(q2[k], q3[k])));
-  }
-  return b;
-}
 
 // ---- kernels --------------------------------------------------------------------------------------------------------------
 // float3 in, the pools' float4 out (w = 0, as build_geometry leaves it)
@@ -414,8 +389,9 @@ int upd_element_boxes(resident& r, const DShape& sh, float* boxes, int* old_slot
   LAUNCH(r, upd_element_boxes_kernel, sh.num_elems, r.d.leaf_prims, (long long)sh.leaf_offset, sh.num_elems, boxes, old_slot);
   return VPT_OK;
 }
-int upd_shape_roots(resident& r, DShape* shapes, const float4* shape_nodes) {
-  LAUNCH(r, upd_shape_roots_kernel, r.d.num_shapes, shapes, r.d.num_shapes, shape_nodes);
+int upd_shape_roots(resident& r, DShape* shapes, const float4* shape_nodes, int num_shapes) {
+  if (num_shapes < 0) num_shapes = r.d.num_shapes;
+  LAUNCH(r, upd_shape_roots_kernel, num_shapes, shapes, num_shapes, shape_nodes);
   return VPT_OK;
 }
 int upd_instance_boxes(resident& r, const DInstance* instances, int num_instances, const DShape* shapes, float4* inst_box) {

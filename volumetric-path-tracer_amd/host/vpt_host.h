@@ -190,6 +190,15 @@ void             rebuild_bvh(bvh_scene& bvh, const scene_data& scene, const vect
 // a shape or material out of range; the scene is untouched then.
 void             edit_instances(scene_data& scene, bvh_scene& bvh, pathtrace_lights& lights, const vector<int>& remove, const vector<int>& set_ids,
                 const vector<instance_data>& set, const vector<instance_data>& add);
+// The shape list changed (the host side of vpt_scene_update_shapes, include/vpt.h): `set` entries replace the shapes named by current
+// ids, then the shapes of `remove` (current ids) are erased - from the back; survivors keep their order, ids close up, every
+// instance's shape id follows - then `add` is appended; make_bvh builds the trees of the replaced and the added shapes, the scene BVH
+// is built anew when, and only when, a shape was replaced, and the lights are make_lights of the new scene.  Throws
+// std::invalid_argument, the scene untouched, for an id out of range or repeated, an id both set and removed, a removed shape that an
+// instance still names, or a shape vpt_scene_create would refuse (a vertex index out of range, both triangles and quads, points or
+// lines mixed with other elements or without one radius per vertex, an attribute that differs from the positions in number).
+void             edit_shapes(scene_data& scene, bvh_scene& bvh, pathtrace_lights& lights, const vector<int>& remove, const vector<int>& set_ids,
+                const vector<shape_data>& set, const vector<shape_data>& add);
 // build_bvh over `n` boxes {min.xyz, max.xyz} on the host (what make_bvh runs per shape and for the instances)
 bvh_data         build_bvh_host(const float* bboxes, int n);
 pathtrace_lights make_lights(const scene_data& scene, const pathtrace_params& params);

@@ -276,6 +276,56 @@ int vpth_scene_edit_instances(void* hh, const int32_t* remove_ids, int num_remov
     return set_error(err, errlen, e.what()), -1;
   }
 }
+// edit_shapes (set on current ids, then remove, then add; make_bvh of the new shapes, the scene BVH when a shape was replaced,
+// make_lights) and the flattened descriptor again (its address changes): the host side of vpt_scene_update_shapes.  Refused while a
+// frame or vertex edit waits for update_bvh: its ids name the old list.
+int vpth_scene_edit_shapes(void* hh, const int32_t* remove_ids, int num_remove, const int32_t* set_ids, const vpt_shape_data* set, int num_set,
+    const vpt_shape_data* add, int num_add, char* err, int errlen) {
+  try {
+    auto& h = *(host_scene*)hh;
+    if (num_remove < 0 || num_set < 0 || num_add < 0 || (num_remove > 0 && !remove_ids) || (num_set > 0 && (!set_ids || !set)) || (num_add > 0 && !add))
+      return set_error(err, errlen, "null or negative shape list"), -1;
+    if (!h.edited_instances.empty() || !h.edited_shapes.empty()) return set_error(err, errlen, "an edit of frames or vertices is pending: update_bvh first"), -1;
+    auto convert = [](const vpt_shape_data* in, int n) {
+      auto out = vector<shape_data>((size_t)n);
+      for (auto i = 0; i < n; i++) {
+        auto& s  = in[i];
+        auto& o  = out[(size_t)i];
+        if (s.num_vertices < 0 || s.num_triangles < 0 || s.num_quads < 0 || s.num_points < 0 || s.num_lines < 0) throw std::invalid_argument{"negative count in a shape"};
+        if ((s.num_vertices > 0 && !s.positions) || (s.num_triangles > 0 && !s.triangles) || (s.num_quads > 0 && !s.quads) || (s.num_points > 0 && !s.points) ||
+            (s.num_lines > 0 && !s.lines))
+          throw std::invalid_argument{"null array with a non-zero count in a shape"};
+        auto nv  = (size_t)s.num_vertices;
+        auto all = [](const float* p, size_t n) {
+          for (size_t k = 0; k < n; k++)
+            if (!std::isfinite(p[k])) throw std::invalid_argument{"a value of a shape is not finite"};
+        };
+        auto fill = [&](auto& to, const float* from, size_t width) {
+          if (!from || nv == 0) return;
+          all(from, width * nv);
+          to.resize(nv);
+          memcpy((void*)to.data(), from, 4 * width * nv);
+        };
+        fill(o.positions, s.positions, 3), fill(o.normals, s.normals, 3), fill(o.texcoords, s.texcoords, 2), fill(o.colors, s.colors, 4);
+        if (s.num_points || s.num_lines) fill(o.radius, s.radius, 1);
+        o.triangles.resize((size_t)s.num_triangles), o.quads.resize((size_t)s.num_quads), o.points.resize((size_t)s.num_points), o.lines.resize((size_t)s.num_lines);
+        if (s.num_triangles) memcpy((void*)o.triangles.data(), s.triangles, 12 * (size_t)s.num_triangles);
+        if (s.num_quads) memcpy((void*)o.quads.data(), s.quads, 16 * (size_t)s.num_quads);
+        if (s.num_points) memcpy((void*)o.points.data(), s.points, 4 * (size_t)s.num_points);
+        if (s.num_lines) memcpy((void*)o.lines.data(), s.lines, 8 * (size_t)s.num_lines);
+      }
+      return out;
+    };
+    edit_shapes(h.scene, h.bvh, h.lights, vector<int>(remove_ids, remove_ids + num_remove), vector<int>(set_ids, set_ids + num_set), convert(set, num_set),
+        convert(add, num_add));
+    auto flat = std::make_unique<flat_scene>();
+    flatten_scene(*flat, h.scene, h.bvh, h.lights);
+    h.flat = std::move(flat);
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
+}
 // make_lights of the scene as the setters left it (an emission switched on or off, an emitter's vertices moved), then the flattened
 // descriptor again: the host side of vpt_scene_update_lights.  The BVHs are vpth_scene_update_bvh's business.
 int vpth_scene_update_lights(void* hh, char* err, int errlen) {

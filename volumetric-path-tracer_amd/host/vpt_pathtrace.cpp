@@ -286,6 +286,63 @@ void edit_instances(scene_data& scene, bvh_scene& bvh, pathtrace_lights& lights,
   rebuild_bvh(bvh, scene, {}, true);
   lights = make_lights(scene, pathtrace_params{});
 }
+void edit_shapes(scene_data& scene, bvh_scene& bvh, pathtrace_lights& lights, const vector<int>& remove, const vector<int>& set_ids,
+    const vector<shape_data>& set, const vector<shape_data>& add) {
+  const auto n = (int)scene.shapes.size();
+  if (set_ids.size() != set.size()) throw std::invalid_argument{"edit_shapes: set ids and shapes differ in number"};
+  if (bvh.shapes.size() != scene.shapes.size()) throw std::invalid_argument{"edit_shapes: bvh does not belong to this scene"};
+  auto removed = vector<char>((size_t)n, 0), is_set = vector<char>((size_t)n, 0);
+  for (auto id : remove) {
+    if (id < 0 || id >= n) throw std::invalid_argument{"edit_shapes: removed id out of range"};
+    if (removed[(size_t)id]) throw std::invalid_argument{"edit_shapes: removed id repeated"};
+    removed[(size_t)id] = 1;
+  }
+  for (auto id : set_ids) {
+    if (id < 0 || id >= n) throw std::invalid_argument{"edit_shapes: set id out of range"};
+    if (is_set[(size_t)id]) throw std::invalid_argument{"edit_shapes: set id repeated"};
+    if (removed[(size_t)id]) throw std::invalid_argument{"edit_shapes: an id is both set and removed"};
+    is_set[(size_t)id] = 1;
+  }
+  for (auto& in : scene.instances)
+    if (removed[(size_t)in.shape]) throw std::invalid_argument{"edit_shapes: a removed shape is still named by an instance"};
+  for (auto* list : {&set, &add})
+    for (auto& shape : *list) {   // the rules of vpt_scene_create for one shape
+      auto nv = (int)shape.positions.size();
+      if (!shape.triangles.empty() && !shape.quads.empty()) throw std::invalid_argument{"edit_shapes: both triangles and quads"};
+      if ((int)!shape.points.empty() + (int)!shape.lines.empty() + (int)(!shape.triangles.empty() || !shape.quads.empty()) > 1)
+        throw std::invalid_argument{"edit_shapes: a shape that mixes points, lines and faces is not supported"};
+      if ((!shape.points.empty() || !shape.lines.empty()) && shape.radius.size() != shape.positions.size())
+        throw std::invalid_argument{"edit_shapes: a shape of points or lines needs one radius per vertex"};
+      if ((!shape.normals.empty() && shape.normals.size() != shape.positions.size()) || (!shape.texcoords.empty() && shape.texcoords.size() != shape.positions.size()) ||
+          (!shape.colors.empty() && shape.colors.size() != shape.positions.size()))
+        throw std::invalid_argument{"edit_shapes: a vertex attribute differs from the positions in number"};
+      auto ok = [nv](int v) { return v >= 0 && v < nv; };
+      for (auto v : shape.points)
+        if (!ok(v)) throw std::invalid_argument{"edit_shapes: point vertex index out of range"};
+      for (auto& l : shape.lines)
+        if (!ok(l.x) || !ok(l.y)) throw std::invalid_argument{"edit_shapes: line vertex index out of range"};
+      for (auto& t : shape.triangles)
+        if (!ok(t.x) || !ok(t.y) || !ok(t.z)) throw std::invalid_argument{"edit_shapes: triangle vertex index out of range"};
+      for (auto& q : shape.quads)
+        if (!ok(q.x) || !ok(q.y) || !ok(q.z) || !ok(q.w)) throw std::invalid_argument{"edit_shapes: quad vertex index out of range"};
+    }
+  for (auto i = (size_t)0; i < set.size(); i++) scene.shapes[(size_t)set_ids[i]] = set[i];
+  auto new_of_old = vector<int>((size_t)n, -1);
+  for (auto id = 0, next = 0; id < n; id++)
+    if (!removed[(size_t)id]) new_of_old[(size_t)id] = next++;
+  for (auto id = n - 1; id >= 0; id--)   // erase from the back: the ids of the list are the current ones throughout
+    if (removed[(size_t)id]) scene.shapes.erase(scene.shapes.begin() + id), bvh.shapes.erase(bvh.shapes.begin() + id);
+  for (auto& shape : add) scene.shapes.push_back(shape), bvh.shapes.emplace_back();
+  for (auto& in : scene.instances) in.shape = new_of_old[(size_t)in.shape];
+  for (auto& sd : scene.subdivs)
+    if (sd.shape >= 0 && sd.shape < n) sd.shape = new_of_old[(size_t)sd.shape];
+  // make_bvh for the replaced and the added shapes; the scene BVH only when a shape was replaced (another root box) - an added shape
+  // has no instance yet and a removed one had none, so the untouched trees and the scene's keep the form they have, refitted or not
+  for (auto id : set_ids) bvh.shapes[(size_t)new_of_old[(size_t)id]] = make_shape_bvh(scene.shapes[(size_t)new_of_old[(size_t)id]], -1);
+  for (auto id = scene.shapes.size() - add.size(); id < scene.shapes.size(); id++) bvh.shapes[id] = make_shape_bvh(scene.shapes[id], -1);
+  if (!set.empty()) rebuild_bvh(bvh, scene, {}, true);
+  lights = make_lights(scene, pathtrace_params{});
+}
 pathtrace_lights make_lights(const scene_data& scene, const pathtrace_params&) {
   auto lights = pathtrace_lights{};
   for (auto handle = 0; handle < (int)scene.instances.size(); handle++) {
