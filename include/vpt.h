@@ -524,6 +524,14 @@ typedef struct vpt_bvh_rebuild {
   int32_t scene;                                 /* non-zero: build the scene BVH anew; forced when num_shapes > 0, as make_bvh would */
 } vpt_bvh_rebuild;
 int vpt_scene_rebuild_bvh(vpt_scene* scene, const vpt_bvh_rebuild* what);
+/* vpt_scene_rebuild_bvh with the trees of the reference's high-quality build: `quality` is VPT_BVH_MIDDLE (vpt_scene_rebuild_bvh itself)
+ * or VPT_BVH_SAH (the rule at vpt_build_bvh_quality, below).  The contract is the one above with highquality = quality: after the call
+ * every table holds the bytes vpt_scene_create would upload for a descriptor whose named shapes' trees, and whose scene tree when it is
+ * built, are build_bvh(..., highquality = quality).  Refusals, limits (creation's own function, on the new trees), the swap after the last
+ * check and the PCIe accounting are those above; another quality gives VPT_ERR_INVALID_ARG before anything is built.
+ * What follows from the other contracts: a refit (vpt_scene_update) keeps the topology, so SAH trees survive it; vpt_scene_update_instances
+ * and a `set` in vpt_scene_update_shapes build with the middle split, as their rules say - the handle remembers no quality. */
+int vpt_scene_rebuild_bvh_quality(vpt_scene* scene, const vpt_bvh_rebuild* what, int quality);
 /* The node counts as the device holds them now: what vpt_scene_get_bvh's capacities must reach (for a handle that was never rebuilt,
  * the descriptor's counts).  shape_node_offsets: per shape, the first node of its BVH in the pool; may be NULL. */
 int vpt_scene_get_bvh_counts(vpt_scene* scene, int32_t* scene_nodes, int64_t* shape_nodes, int64_t* shape_node_offsets /* per shape, may be NULL */);
@@ -705,6 +713,7 @@ int  vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit);
 int  vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit);
 /* vpt_scene_rebuild_bvh in the same way: every device builds its own trees; the arrays are equal by construction */
 int  vpt_multi_rebuild_bvh(vpt_multi* m, const vpt_bvh_rebuild* what);
+int  vpt_multi_rebuild_bvh_quality(vpt_multi* m, const vpt_bvh_rebuild* what, int quality);   /* vpt_scene_rebuild_bvh_quality on every device */
 /* vpt_scene_update_instances in the same way: every device renumbers and builds its own tables; they are equal by construction */
 int  vpt_multi_update_instances(vpt_multi* m, const vpt_instance_edit* edit);
 /* vpt_scene_update_shapes in the same way: every device lays out its own pools and builds its own trees; they are equal by construction */
@@ -961,6 +970,7 @@ int  vpt_session_edit_textures(vpt_session* session, const vpt_texture_edit* edi
 int  vpt_session_edit_volumes(vpt_session* session, const vpt_volume_edit* edit);
 /* vpt_scene_rebuild_bvh, then a reset (the picture is the same, its accumulation restarts as after the session's other edits); a refused call leaves the session as it was */
 int  vpt_session_rebuild_bvh(vpt_session* session, const vpt_bvh_rebuild* what);
+int  vpt_session_rebuild_bvh_quality(vpt_session* session, const vpt_bvh_rebuild* what, int quality);   /* vpt_scene_rebuild_bvh_quality, then a reset */
 /* vpt_scene_update_instances, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_edit_instances(vpt_session* session, const vpt_instance_edit* edit);
 /* vpt_scene_update_shapes, then a reset; a refused edit leaves the session as it was */
@@ -1017,6 +1027,31 @@ int vpt_intersect(vpt_scene* scene, int n, const float* rays, int instance, int3
  * arrays).  nodes: room for `capacity` >= max(1, 2 n - 1) entries; *num_nodes = entries written; primitives: n ints.
  * Synchronous.  SURVEY §8(f) row 4 (load-time callers of the hot path). */
 int vpt_build_bvh(int device, const float* bboxes, int n, vpt_bvh_node* nodes, int capacity, int* num_nodes, int32_t* primitives);
+
+/* The same build with the reference's other branch: build_bvh(bvh, bboxes, highquality = quality).  VPT_BVH_MIDDLE is vpt_build_bvh
+ * (split_middle); VPT_BVH_SAH is split_sah (yocto_bvh.cpp:317-373), which no caller of the reference switches on because 45 passes
+ * over every node's primitives are too slow on a CPU.  Another quality gives VPT_ERR_INVALID_ARG before anything is built.
+ * The SAH rule is that of vpt_build_bvh except for how an internal node (more than 4 primitives) chooses `axis` and `split`:
+ *  - cbbox is the box of the node's primitive centres, csize = cbbox.max - cbbox.min.  All three sizes zero: the node is cut in halves
+ *    on axis 0, as in vpt_build_bvh.
+ *  - Otherwise the search starts with min_cost = flt_max, split = 0.0f, axis = 0, and runs saxis = 0, 1, 2 outside and b = 1 .. 15
+ *    inside: bsplit = cbbox.min[saxis] + ((float)b * csize[saxis]) / 16.0f.  Left is every primitive of the node whose centre on saxis
+ *    is < bsplit, right is the rest; left_bbox and right_bbox are the merges of their boxes, starting from the invalid box
+ *    (min = flt_max, max = -flt_max).
+ *  - area(x) = ((1e-12f + (2 * sx) * sy) + (2 * sx) * sz) + (2 * sy) * sz with s = x.max - x.min.
+ *    cost = (1 + ((float)left_n * area(left_bbox)) / area(cbbox)) + ((float)right_n * area(right_bbox)) / area(cbbox), where
+ *    area(cbbox) is the area of the CENTRE box, as the reference has it.
+ *  - A candidate wins only when cost < min_cost (strict): the first of equal costs wins, and a NaN or infinite cost never wins.  An
+ *    empty side gives 0 * inf = NaN.  When no candidate wins the node is partitioned at 0.0f on axis 0.
+ *  - Then the same std::partition by centre[axis] < split and the same halves fallback when one side is empty; node ids and primitive
+ *    order follow as in vpt_build_bvh.
+ *  - Every value is float32, nothing is fused, divisions are IEEE.
+ * The device evaluates the 45 candidates of a node from 16 bins per axis (a primitive's bin is the number of borders its centre is not
+ * below; candidate b is the sum and merge of bins 0 .. b-1, and of the rest) - the same counts and boxes whenever a node's 15 borders
+ * do not decrease with b; a node where they do (a NaN or overflowing csize) is evaluated candidate by candidate.  DESIGN.md §22. */
+#define VPT_BVH_MIDDLE 0
+#define VPT_BVH_SAH 1
+int vpt_build_bvh_quality(int device, const float* bboxes, int n, int quality, vpt_bvh_node* nodes, int capacity, int* num_nodes, int32_t* primitives);
 
 /* The float32 half of one level of the reference's Catmull-Clark subdivision (tesselate_catmullclark,
  * libs/yocto_pathtrace/yocto_pathtrace.cpp:1119-1226) on the device.  The caller supplies the level's

@@ -150,10 +150,11 @@ class VptBvhRebuild(C.Structure):  # vpt_bvh_rebuild
 class BvhRebuild:
     """What vpt_scene_rebuild_bvh takes (include/vpt.h: vpt_bvh_rebuild): the shapes whose BVHs are built anew, and whether the scene
     BVH is (it is whenever a shape is named).  HostScene.rebuild_bvh makes one; DeviceScene.rebuild_bvh / MultiDeviceScene.rebuild_bvh /
-    RenderSession.rebuild_bvh apply it."""
+    RenderSession.rebuild_bvh apply it.  quality: BVH_MIDDLE (0, the reference's highquality = false) or BVH_SAH (1, split_sah: the rule
+    at vpt_build_bvh_quality in include/vpt.h), carried to the device with the request."""
 
-    def __init__(self, shapes=(), scene: bool = True):
-        self.shapes, self.scene = tuple(int(i) for i in shapes), bool(scene)
+    def __init__(self, shapes=(), scene: bool = True, *, quality: int = 0):
+        self.shapes, self.scene, self.quality = tuple(int(i) for i in shapes), bool(scene), int(quality)
 
     def empty(self) -> bool:
         return not self.shapes and not self.scene
@@ -525,6 +526,9 @@ hip.vpt_scene_get_bvh.argtypes = [_p, _p, C.c_int, _p, C.c_int64]
 hip.vpt_scene_rebuild_bvh.argtypes = [_p, C.POINTER(VptBvhRebuild)]
 hip.vpt_multi_rebuild_bvh.argtypes = [_p, C.POINTER(VptBvhRebuild)]
 hip.vpt_session_rebuild_bvh.argtypes = [_p, C.POINTER(VptBvhRebuild)]
+hip.vpt_scene_rebuild_bvh_quality.argtypes = [_p, C.POINTER(VptBvhRebuild), C.c_int]
+hip.vpt_multi_rebuild_bvh_quality.argtypes = [_p, C.POINTER(VptBvhRebuild), C.c_int]
+hip.vpt_session_rebuild_bvh_quality.argtypes = [_p, C.POINTER(VptBvhRebuild), C.c_int]
 hip.vpt_scene_update_instances.argtypes = [_p, C.POINTER(VptInstanceEdit)]
 hip.vpt_multi_update_instances.argtypes = [_p, C.POINTER(VptInstanceEdit)]
 hip.vpt_session_edit_instances.argtypes = [_p, C.POINTER(VptInstanceEdit)]
@@ -579,6 +583,7 @@ hip.vpt_session_stats.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), 
 hip.vpt_last_kernel_ms.argtypes = [_p, C.POINTER(C.c_float)]
 hip.vpt_intersect.argtypes = [_p, C.c_int, _p, C.c_int, _p, _p]
 hip.vpt_build_bvh.argtypes = [C.c_int, _p, C.c_int, _p, C.c_int, C.POINTER(C.c_int), _p]
+hip.vpt_build_bvh_quality.argtypes = [C.c_int, _p, C.c_int, C.c_int, _p, C.c_int, C.POINTER(C.c_int), _p]
 hip.vpt_bake_sdf.argtypes = [C.c_int, C.POINTER(VptBakeDesc), _p, C.POINTER(VptBakeStats)]
 hip.vpt_bake_feature_normals.argtypes = [C.POINTER(VptBakeDesc), _p, _p]
 hip.vpt_last_wave_costs.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int)]
@@ -618,6 +623,7 @@ host.vpth_scene_get_item.restype = C.c_int64
 host.vpth_scene_set_item.argtypes = [_p, C.c_int, C.c_int, _p, C.c_int64, C.c_char_p, C.c_int]
 host.vpth_scene_update_bvh.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_rebuild_bvh.argtypes = [_p, _p, C.c_int, C.c_int, C.c_char_p, C.c_int]
+host.vpth_scene_rebuild_bvh_quality.argtypes = [_p, _p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]
 host.vpth_scene_edit_instances.argtypes = [_p, _p, C.c_int, _p, _p, C.c_int, _p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_scene_edit_shapes.argtypes = [_p, _p, C.c_int, _p, _p, C.c_int, _p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_scene_update_lights.argtypes = [_p, C.c_char_p, C.c_int]
@@ -643,6 +649,8 @@ host.vpth_make_state.argtypes = [_p, C.c_int, C.c_int, _p, _p, _p]
 host.vpth_scene_stats.argtypes = [_p, C.c_char_p, C.c_int]
 host.vpth_scene_rebuild_bvh_device.argtypes = [_p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_build_bvh_host.argtypes = [_p, C.c_int, _p, C.POINTER(C.c_int), _p]
+host.vpth_scene_rebuild_bvh_device_quality.argtypes = [_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
+host.vpth_build_bvh_host_quality.argtypes = [_p, C.c_int, C.c_int, _p, C.POINTER(C.c_int), _p]
 host.vpth_denoise.argtypes = [C.c_int, C.c_int, _p, _p, _p, _p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _p, C.c_char_p, C.c_int]
 host.vpth_half_variance.argtypes = [C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int, _p, C.c_char_p, C.c_int]
 host.vpth_bake_triangles.argtypes = [_p, C.c_int, C.c_int, _p, C.POINTER(C.c_int)]
@@ -709,18 +717,24 @@ class VptSceneDescLights(C.Structure):
                 ("num_light_cdf", C.c_int64), ("light_cdf", C.c_void_p)]
 
 
-def build_bvh(bboxes: np.ndarray, device: Optional[int] = 0):
-    """build_bvh(bvh, bboxes, false) of the reference over n boxes {min.xyz, max.xyz}: (nodes, primitives).  device = GPU index
-    (vpt_build_bvh) or None for the host build the loader uses (same arrays)."""
+BVH_MIDDLE, BVH_SAH = 0, 1   # VPT_BVH_MIDDLE, VPT_BVH_SAH
+
+
+def build_bvh(bboxes: np.ndarray, device: Optional[int] = 0, *, quality: int = 0):
+    """build_bvh(bvh, bboxes, highquality = quality) of the reference over n boxes {min.xyz, max.xyz}: (nodes, primitives).  device = GPU
+    index (vpt_build_bvh_quality) or None for the host build the loader uses (same arrays).  quality: BVH_MIDDLE or BVH_SAH."""
+    if quality not in (BVH_MIDDLE, BVH_SAH):
+        raise VptError(f"build_bvh: unknown quality {quality!r}")
     bboxes = np.ascontiguousarray(bboxes, np.float32).reshape(-1, 6)
     n = len(bboxes)
     nodes = np.zeros(max(1, 2 * n), BVH_NODE)
     prims = np.zeros(max(1, n), np.int32)
     count = C.c_int()
     if device is None:
-        host.vpth_build_bvh_host(bboxes.ctypes.data, n, nodes.ctypes.data, C.byref(count), prims.ctypes.data)
+        if host.vpth_build_bvh_host_quality(bboxes.ctypes.data, n, quality, nodes.ctypes.data, C.byref(count), prims.ctypes.data) != 0:
+            raise VptError("vpth_build_bvh_host_quality: bad argument")
     else:
-        _check(hip.vpt_build_bvh(device, bboxes.ctypes.data, n, nodes.ctypes.data, len(nodes), C.byref(count), prims.ctypes.data), "vpt_build_bvh")
+        _check(hip.vpt_build_bvh_quality(device, bboxes.ctypes.data, n, quality, nodes.ctypes.data, len(nodes), C.byref(count), prims.ctypes.data), "vpt_build_bvh_quality")
     return nodes[:count.value].copy(), prims[:n].copy()
 
 
@@ -871,16 +885,21 @@ def bake_sdf(positions: np.ndarray, faces: np.ndarray, whd, padding: int = 2, de
 class HostScene:
     """load_scene + tesselate_surfaces + make_bvh + make_lights, flattened for the C-ABI."""
 
-    def __init__(self, filename: str, bvh_device: Optional[int] = None, tess_device: Optional[int] = None):
-        """bvh_device: build the BVHs on that GPU (make_bvh_device / vpt_build_bvh) instead of on the host - same arrays;
-        tess_device: the vertex arithmetic of tesselate_surfaces on that GPU (vpt_subdivide_vertices) - same mesh"""
+    def __init__(self, filename: str, bvh_device: Optional[int] = None, tess_device: Optional[int] = None, *, bvh_quality: int = 0):
+        """bvh_device: build the BVHs on that GPU (make_bvh_device / vpt_build_bvh_quality) instead of on the host - same arrays;
+        tess_device: the vertex arithmetic of tesselate_surfaces on that GPU (vpt_subdivide_vertices) - same mesh;
+        bvh_quality: BVH_MIDDLE, or BVH_SAH for make_bvh(..., highquality = true) - every tree is built at that quality after loading"""
+        if bvh_quality not in (BVH_MIDDLE, BVH_SAH):
+            raise VptError(f"HostScene: unknown bvh_quality {bvh_quality!r}")
         err = C.create_string_buffer(1024)
         self.handle = host.vpth_scene_load_ex(os.fsencode(filename), -1 if tess_device is None else tess_device, err, len(err))
         if not self.handle:
             raise VptError(err.value.decode())
         self.filename = filename
-        if bvh_device is not None and host.vpth_scene_rebuild_bvh_device(self.handle, bvh_device, err, len(err)) != 0:
+        if bvh_device is not None and host.vpth_scene_rebuild_bvh_device_quality(self.handle, bvh_device, bvh_quality, err, len(err)) != 0:
             raise VptError(err.value.decode())
+        if bvh_device is None and bvh_quality != BVH_MIDDLE:
+            self.rebuild_bvh("all", quality=bvh_quality)
 
     @property
     def desc(self) -> int:
@@ -1027,20 +1046,22 @@ class HostScene:
             raise VptError(err.value.decode())
         return edit
 
-    def rebuild_bvh(self, shapes=None, scene: bool = True) -> "BvhRebuild":
+    def rebuild_bvh(self, shapes=None, scene: bool = True, *, quality: int = 0) -> "BvhRebuild":
         """make_bvh of the reference again, on the scene as it is now, for the shapes named (ids; "all": every shape; None: none) and
         - `scene`, or whenever a shape is named - for the scene BVH: topology, node counts and primitive orders change; desc / stats()
         describe the rebuilt scene afterwards.  A pending edit is handed out with update_bvh() first.  Returns the BvhRebuild for
-        DeviceScene.rebuild_bvh."""
+        DeviceScene.rebuild_bvh.  quality: BVH_MIDDLE or BVH_SAH for every tree this call builds; the others keep theirs."""
+        if quality not in (BVH_MIDDLE, BVH_SAH):
+            raise VptError(f"rebuild_bvh: unknown quality {quality!r}")
         if getattr(self, "_edit", None) is not None and not self._edit.empty():
             raise VptError("rebuild_bvh: hand the pending edit out with update_bvh() first")
         self._no_pending_instances("rebuild_bvh")
         ids = list(range(self.count("shapes"))) if isinstance(shapes, str) and shapes == "all" else [int(i) for i in (shapes or ())]
         arr = np.ascontiguousarray(ids, np.int32)
         err = C.create_string_buffer(512)
-        if host.vpth_scene_rebuild_bvh(self.handle, arr.ctypes.data if len(arr) else None, len(arr), int(bool(scene)), err, len(err)) != 0:
+        if host.vpth_scene_rebuild_bvh_quality(self.handle, arr.ctypes.data if len(arr) else None, len(arr), int(bool(scene)), quality, err, len(err)) != 0:
             raise VptError(err.value.decode())
-        return BvhRebuild(ids, scene)
+        return BvhRebuild(ids, scene, quality=quality)
 
     # -- the set of instances (the host side of vpt_scene_update_instances): add_instance / remove_instances / set_instance note a
     #    change, ids naming the list as it is now; update_instances() applies them to the scene - set, then remove, then add - builds
@@ -1577,7 +1598,7 @@ class DeviceScene:
         resident.  Afterwards the handle renders the bits of a DeviceScene made from the host scene after the same
         HostScene.rebuild_bvh()."""
         abi, keep = rebuild.to_abi()
-        _check(hip.vpt_scene_rebuild_bvh(self.handle, C.byref(abi)), "vpt_scene_rebuild_bvh")
+        _check(hip.vpt_scene_rebuild_bvh_quality(self.handle, C.byref(abi), rebuild.quality), "vpt_scene_rebuild_bvh_quality")
         del keep
 
     def update_instances(self, edit: InstanceEdit) -> None:
@@ -1750,7 +1771,7 @@ class MultiDeviceScene:
     def rebuild_bvh(self, rebuild: "BvhRebuild") -> None:
         """vpt_multi_rebuild_bvh: DeviceScene.rebuild_bvh on every device (each builds its own trees: equal by construction)"""
         abi, keep = rebuild.to_abi()
-        _check(hip.vpt_multi_rebuild_bvh(self.handle, C.byref(abi)), "vpt_multi_rebuild_bvh")
+        _check(hip.vpt_multi_rebuild_bvh_quality(self.handle, C.byref(abi), rebuild.quality), "vpt_multi_rebuild_bvh_quality")
         del keep
 
     def update_instances(self, edit: InstanceEdit) -> None:
@@ -2069,7 +2090,7 @@ class RenderSession:
     def rebuild_bvh(self, rebuild: "BvhRebuild") -> None:
         """vpt_scene_rebuild_bvh on the session's scene with the BvhRebuild of HostScene.rebuild_bvh(), then a reset"""
         abi, keep = rebuild.to_abi()
-        _check(hip.vpt_session_rebuild_bvh(self.handle, C.byref(abi)), "vpt_session_rebuild_bvh")
+        _check(hip.vpt_session_rebuild_bvh_quality(self.handle, C.byref(abi), rebuild.quality), "vpt_session_rebuild_bvh_quality")
         del keep
 
     def edit_instances(self, edit: InstanceEdit) -> None:

@@ -16,7 +16,8 @@ struct bvh_rebuild_stacks {
 // device into buffers of their own, decides the traversal limits from the new trees (VPT_ERR_UNSUPPORTED: the scene is as it was)
 // and only then reorders the leaf records and swaps tables, counts and mirrors.  Returns after the device has finished;
 // r.refit.ready is cleared.  The caller runs the light setup afterwards (light_prims follow the leaf records).
-int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& what, bvh_rebuild_stacks& stacks);
+// quality: VPT_BVH_MIDDLE or VPT_BVH_SAH for every tree the call builds (another value: VPT_ERR_INVALID_ARG, first of all).
+int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& what, bvh_rebuild_stacks& stacks, int quality = VPT_BVH_MIDDLE);
 
 // The scene level of a rebuild, shared with vpt_scene_update_instances (vpt_instance_update.hip): the scene BVH over a table of
 // instances, in buffers of the call until scene_level_swap hands them to the scene.
@@ -29,7 +30,7 @@ struct scene_level {
 };
 // instance boxes from `instances` and the root boxes of `shapes` (both on the device), K6's core over them, nodes and primitive order
 // into buffers of their own, and the read-back of both (checked: the order is a permutation)
-int scene_level_build(resident& r, bvh_build_scratch& core, const DInstance* instances, int num_instances, const DShape* shapes, scene_level& lv);
+int scene_level_build(resident& r, bvh_build_scratch& core, const DInstance* instances, int num_instances, const DShape* shapes, scene_level& lv, int quality = VPT_BVH_MIDDLE);
 // enter records and slot_of_instance: the integer words on the host (prep_enter_tail, from t.shapes and the quad nodes of t), sent,
 // then frames and root boxes by the refit's kernel.  inst_shape: the shape of every instance of the table, on the host.
 int scene_level_enter(resident& r, scene_level& lv, const scene_tables& t, const int* inst_shape, const DInstance* instances, const DShape* shapes);

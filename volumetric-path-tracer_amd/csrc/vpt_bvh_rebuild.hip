@@ -78,11 +78,11 @@ int copy_on_device(void* to, const void* from, size_t bytes) {
 
 }  // namespace
 
-int scene_level_build(resident& r, bvh_build_scratch& core, const DInstance* instances, int ninst, const DShape* shapes, scene_level& lv) {
+int scene_level_build(resident& r, bvh_build_scratch& core, const DInstance* instances, int ninst, const DShape* shapes, scene_level& lv, int quality) {
   lv.num_instances = ninst;
   if (int rc = lv.inst_box.allocate((size_t)ninst * 2 * sizeof(float4))) return rc;
   if (int rc = upd_instance_boxes(r, instances, ninst, shapes, lv.inst_box.get<float4>())) return rc;
-  if (int rc = bvh_build_core(core, lv.inst_box.get<float>(), 8, ninst, &lv.count, &r.last_launches)) return rc;
+  if (int rc = bvh_build_core(core, lv.inst_box.get<float>(), 8, ninst, &lv.count, &r.last_launches, quality)) return rc;
   if (int rc = lv.nodes.allocate((size_t)lv.count * sizeof(vpt_bvh_node))) return rc;
   if (int rc = lv.prims.allocate((size_t)ninst * sizeof(int))) return rc;
   if (int rc = copy_on_device(lv.nodes.get(), core.nodes(), (size_t)lv.count * sizeof(vpt_bvh_node))) return rc;
@@ -124,7 +124,8 @@ void scene_level_swap(resident& r, scene_level& lv, const scene_tables& t) {
   r.refit.ready = false;   // levels and quad slots belong to the old trees: the next refit makes them anew
 }
 
-int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks& stacks) {
+int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks& stacks, int quality) {
+  if (quality != VPT_BVH_MIDDLE && quality != VPT_BVH_SAH) return vpt_set_error(VPT_ERR_INVALID_ARG, "unknown bvh quality %d", quality);
   DScene&       d = r.d;
   host_mirrors& h = r.h;
   edit_mirrors& m = r.m;
@@ -144,7 +145,7 @@ int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks&
   most = std::max(most, most_elems);
   bvh_build_scratch core;
   device_buffer     d_boxes, d_old_slot;
-  if (int rc = core.reserve(most)) return rc;
+  if (int rc = core.reserve(most, quality)) return rc;
   if (int rc = d_boxes.allocate(6 * (size_t)most_elems * sizeof(float))) return rc;
   if (int rc = d_old_slot.allocate((size_t)most_elems * sizeof(int))) return rc;
   HIP_TRY(hipEventRecord(r.upd_ev0, 0));
@@ -158,7 +159,7 @@ int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks&
     const int     n  = sh.num_elems;
     b.id = w.shape_ids[i], built_of[(size_t)b.id] = i;
     if (int rc = upd_element_boxes(r, sh, d_boxes.get<float>(), d_old_slot.get<int>())) return rc;
-    if (int rc = bvh_build_core(core, d_boxes.get<float>(), 6, n, &b.count, &r.last_launches)) return rc;
+    if (int rc = bvh_build_core(core, d_boxes.get<float>(), 6, n, &b.count, &r.last_launches, quality)) return rc;
     if (int rc = b.nodes.allocate((size_t)b.count * sizeof(vpt_bvh_node))) return rc;
     if (int rc = b.source.allocate((size_t)n * sizeof(int))) return rc;
     if (int rc = copy_on_device(b.nodes.get(), core.nodes(), (size_t)b.count * sizeof(vpt_bvh_node))) return rc;
@@ -190,7 +191,7 @@ int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks&
   // 4. the one read-back: node arrays (32 B per node) and the scene's primitive order; the topology-only tables from them, by
   // creation's own function - which also decides the traversal limits.  A tree past them is refused here, the scene untouched.
   scene_level lv;
-  if (int rc = scene_level_build(r, core, d.instances, ninst, n_shapes.get<DShape>(), lv)) return rc;
+  if (int rc = scene_level_build(r, core, d.instances, ninst, n_shapes.get<DShape>(), lv, quality)) return rc;
   std::vector<vpt_bvh_node> h_shape_nodes;
   if (int rc = fetch(r, h_shape_nodes, n_shape_nodes.get(), (size_t)total)) return rc;
   for (const built_shape& b : built)

@@ -535,12 +535,14 @@ int vpt_scene_get_bvh(vpt_scene* s, vpt_bvh_node* scene_nodes, int scene_capacit
 }
 
 // the BVHs built anew (vpt_bvh_rebuild.hip); the render side follows: stack sizes, the HBM part of the stacks, light_prims
-int vpt_scene_rebuild_bvh(vpt_scene* s, const vpt_bvh_rebuild* what) {
+int vpt_scene_rebuild_bvh(vpt_scene* s, const vpt_bvh_rebuild* what) { return vpt_scene_rebuild_bvh_quality(s, what, VPT_BVH_MIDDLE); }
+int vpt_scene_rebuild_bvh_quality(vpt_scene* s, const vpt_bvh_rebuild* what, int quality) {
   if (!s || !what) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (quality != VPT_BVH_MIDDLE && quality != VPT_BVH_SAH) return vpt_set_error(VPT_ERR_INVALID_ARG, "unknown bvh quality %d", quality);
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call replaces
   bvh_rebuild_stacks st;
-  if (int rc = bvh_rebuild_apply(*s, *what, st)) return rc;
+  if (int rc = bvh_rebuild_apply(*s, *what, st, quality)) return rc;
   if (!st.rebuilt) return VPT_OK;
   if (st.stack_spill4 != s->stack_spill4) s->spill_lanes = 0;   // the HBM part is sized per entry: made anew by the next launch
   s->stack_cap = st.stack_cap, s->stack_lds4 = st.stack_lds4, s->stack_spill4 = st.stack_spill4;

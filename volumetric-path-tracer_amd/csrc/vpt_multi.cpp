@@ -345,10 +345,11 @@ int vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit) {
   return VPT_OK;
 }
 
-int vpt_multi_rebuild_bvh(vpt_multi* m, const vpt_bvh_rebuild* what) {
+int vpt_multi_rebuild_bvh(vpt_multi* m, const vpt_bvh_rebuild* what) { return vpt_multi_rebuild_bvh_quality(m, what, VPT_BVH_MIDDLE); }
+int vpt_multi_rebuild_bvh_quality(vpt_multi* m, const vpt_bvh_rebuild* what, int quality) {
   if (!m || !what) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   for (auto& p : m->parts)   // as vpt_multi_update: every device holds the same scene, so the first one's refusal is everyone's
-    if (int rc = vpt_scene_rebuild_bvh(p.scene, what)) return rc;
+    if (int rc = vpt_scene_rebuild_bvh_quality(p.scene, what, quality)) return rc;
   return VPT_OK;
 }
 int vpt_multi_update_instances(vpt_multi* m, const vpt_instance_edit* edit) {

@@ -394,12 +394,12 @@ int vpt_session_set_display(vpt_session* s, const vpt_display_params* display) {
 
 // one of the edits of a resident scene (which: 0 vpt_scene_update, 1 _lights, 2 _textures, 3 _volumes, 4 vpt_scene_rebuild_bvh,
 // 5 vpt_scene_update_instances, 6 vpt_scene_update_shapes), then a reset
-static int session_edit(vpt_session* s, const void* edit, int which) {
+static int session_edit(vpt_session* s, const void* edit, int which, int quality = VPT_BVH_MIDDLE) {
   REQUIRE(s && edit, "null argument");
   begin_call(s);
   if (int rc = which == 6 ? vpt_scene_update_shapes(s->scene, (const vpt_shape_edit*)edit)
                : which == 5 ? vpt_scene_update_instances(s->scene, (const vpt_instance_edit*)edit)
-               : which == 4 ? vpt_scene_rebuild_bvh(s->scene, (const vpt_bvh_rebuild*)edit)
+               : which == 4 ? vpt_scene_rebuild_bvh_quality(s->scene, (const vpt_bvh_rebuild*)edit, quality)
                : which == 3 ? vpt_scene_update_volumes(s->scene, (const vpt_volume_edit*)edit)
                : which == 2 ? vpt_scene_update_textures(s->scene, (const vpt_texture_edit*)edit)
                : which == 1 ? vpt_scene_update_lights(s->scene, (const vpt_scene_edit*)edit)
@@ -416,6 +416,7 @@ int vpt_session_edit_lights(vpt_session* s, const vpt_scene_edit* edit) { return
 int vpt_session_edit_textures(vpt_session* s, const vpt_texture_edit* edit) { return session_edit(s, edit, 2); }
 int vpt_session_edit_volumes(vpt_session* s, const vpt_volume_edit* edit) { return session_edit(s, edit, 3); }
 int vpt_session_rebuild_bvh(vpt_session* s, const vpt_bvh_rebuild* what) { return session_edit(s, what, 4); }
+int vpt_session_rebuild_bvh_quality(vpt_session* s, const vpt_bvh_rebuild* what, int quality) { return session_edit(s, what, 4, quality); }
 int vpt_session_edit_instances(vpt_session* s, const vpt_instance_edit* edit) { return session_edit(s, edit, 5); }
 int vpt_session_edit_shapes(vpt_session* s, const vpt_shape_edit* edit) { return session_edit(s, edit, 6); }
 

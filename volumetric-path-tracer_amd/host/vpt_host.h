@@ -170,9 +170,12 @@ struct color_image {
 };
 
 pathtrace_state  make_state(const scene_data& scene, const pathtrace_params& params);
-bvh_scene        make_bvh(const scene_data& scene, const pathtrace_params& params);
-// Extension: the same trees (node for node, hash-equal) built on GPU `device` by vpt_build_bvh; throws if that fails.
-bvh_scene        make_bvh_device(const scene_data& scene, const pathtrace_params& params, int device = 0);
+// `quality`: VPT_BVH_MIDDLE (the reference's highquality = false, what every caller of the reference uses) or VPT_BVH_SAH (highquality =
+// true: split_sah, the rule at vpt_build_bvh_quality in include/vpt.h), for every tree of the scene; another value throws
+// std::invalid_argument.  The host build is the plain form of the rule: 45 passes over a node's primitives.
+bvh_scene        make_bvh(const scene_data& scene, const pathtrace_params& params, int quality = VPT_BVH_MIDDLE);
+// Extension: the same trees (node for node, hash-equal) built on GPU `device` by vpt_build_bvh_quality; throws if that fails.
+bvh_scene        make_bvh_device(const scene_data& scene, const pathtrace_params& params, int device = 0, int quality = VPT_BVH_MIDDLE);
 // update_bvh(bvh, scene, updated_instances, updated_shapes) of the reference (yocto_bvh.h:100-103, yocto_bvh.cpp:509-524, 613-689): a
 // refit.  Topology, node ids and primitive order stay; the boxes of the named shapes' BVHs, then of the scene BVH (from ALL
 // instances: the reference does not read `updated_instances` either) are recomputed from invalidb3f with the bounds routines of
@@ -181,8 +184,9 @@ bvh_scene        make_bvh_device(const scene_data& scene, const pathtrace_params
 void             update_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& updated_instances, const vector<int>& updated_shapes);
 // make_bvh again for part of a scene (the host side of vpt_scene_rebuild_bvh, include/vpt.h): the named shapes' BVHs from their current
 // vertices, then - `scene_level`, forced when a shape is named - the scene BVH over the current instances and roots.  Throws
-// std::invalid_argument for a shape id out of range or repeated.
-void             rebuild_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& shapes, bool scene_level);
+// std::invalid_argument for a shape id out of range or repeated, or an unknown quality.  Every tree the call builds is built at
+// `quality`; the trees it leaves alone keep theirs.
+void             rebuild_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& shapes, bool scene_level, int quality = VPT_BVH_MIDDLE);
 // The set of instances changed (the host side of vpt_scene_update_instances, include/vpt.h): `set` entries replace the instances named
 // by current ids, then the instances of `remove` (current ids) are erased - survivors keep their order, ids close up - then `add` is
 // appended; the scene BVH is built anew over the new list (rebuild_bvh(bvh, scene, {}, true): the shapes' trees stay) and the lights
@@ -200,7 +204,7 @@ void             edit_instances(scene_data& scene, bvh_scene& bvh, pathtrace_lig
 void             edit_shapes(scene_data& scene, bvh_scene& bvh, pathtrace_lights& lights, const vector<int>& remove, const vector<int>& set_ids,
                 const vector<shape_data>& set, const vector<shape_data>& add);
 // build_bvh over `n` boxes {min.xyz, max.xyz} on the host (what make_bvh runs per shape and for the instances)
-bvh_data         build_bvh_host(const float* bboxes, int n);
+bvh_data         build_bvh_host(const float* bboxes, int n, int quality = VPT_BVH_MIDDLE);
 pathtrace_lights make_lights(const scene_data& scene, const pathtrace_params& params);
 // tesselate_surfaces (yocto_pathtrace.cpp:1119-1280): Catmull-Clark subdivision of every subdiv's cage (positions with
 // creased boundaries, texcoords with locked boundaries), split_facevarying, quads_to_triangles, displacement along the

@@ -115,10 +115,11 @@ int vpth_displace_vertices(const void* texels, int width, int height, int is_flo
   }
 }
 // rebuild the scene's BVHs on GPU `device` (make_bvh_device) and flatten again; 0 on success
-int vpth_scene_rebuild_bvh_device(void* hh, int device, char* err, int errlen) {
+// (quality: VPT_BVH_MIDDLE or VPT_BVH_SAH for every tree; another value is refused, the scene untouched)
+int vpth_scene_rebuild_bvh_device_quality(void* hh, int device, int quality, char* err, int errlen) {
   try {
     auto& h = *(host_scene*)hh;
-    h.bvh   = make_bvh_device(h.scene, pathtrace_params{}, device);
+    h.bvh   = make_bvh_device(h.scene, pathtrace_params{}, device, quality);
     auto flat = std::make_unique<flat_scene>();
     flatten_scene(*flat, h.scene, h.bvh, h.lights);
     h.flat = std::move(flat);   // the address vpth_scene_desc handed out before is gone: callers fetch it again
@@ -127,7 +128,18 @@ int vpth_scene_rebuild_bvh_device(void* hh, int device, char* err, int errlen) {
     return set_error(err, errlen, e.what()), -1;
   }
 }
-// build_bvh over n boxes on the host (the checker of vpt_build_bvh in tests): nodes has room for max(1, 2 n) entries
+int vpth_scene_rebuild_bvh_device(void* hh, int device, char* err, int errlen) { return vpth_scene_rebuild_bvh_device_quality(hh, device, VPT_BVH_MIDDLE, err, errlen); }
+// build_bvh over n boxes on the host (the checker of vpt_build_bvh_quality in tests): nodes has room for max(1, 2 n) entries; -1 for
+// an unknown quality or a bad pointer, nothing written
+int vpth_build_bvh_host_quality(const float* bboxes, int n, int quality, vpt_bvh_node* nodes, int* num_nodes, int32_t* primitives) {
+  if (n < 0 || !nodes || !num_nodes || (n > 0 && (!bboxes || !primitives))) return -1;
+  if (quality != VPT_BVH_MIDDLE && quality != VPT_BVH_SAH) return -1;
+  auto bvh = build_bvh_host(bboxes, n, quality);
+  memcpy(nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(vpt_bvh_node));
+  if (n > 0) memcpy(primitives, bvh.primitives.data(), (size_t)n * sizeof(int32_t));
+  *num_nodes = (int)bvh.nodes.size();
+  return 0;
+}
 int vpth_build_bvh_host(const float* bboxes, int n, vpt_bvh_node* nodes, int* num_nodes, int32_t* primitives) {
   auto bvh = build_bvh_host(bboxes, n);
   memcpy(nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(vpt_bvh_node));
@@ -234,11 +246,16 @@ int vpth_scene_update_bvh(void* hh, char* err, int errlen) {
 }
 // rebuild_bvh (make_bvh again for the named shapes and, `scene` non-zero or a shape named, for the scene level) on the CURRENT host
 // scene, then the flattened descriptor again (its address changes): the host side of vpt_scene_rebuild_bvh
+int vpth_scene_rebuild_bvh_quality(void* hh, const int32_t* shape_ids, int n, int scene, int quality, char* err, int errlen);
 int vpth_scene_rebuild_bvh(void* hh, const int32_t* shape_ids, int n, int scene, char* err, int errlen) {
+  return vpth_scene_rebuild_bvh_quality(hh, shape_ids, n, scene, VPT_BVH_MIDDLE, err, errlen);
+}
+// (every tree the call builds at `quality`: VPT_BVH_MIDDLE or VPT_BVH_SAH; another value is refused, the scene untouched)
+int vpth_scene_rebuild_bvh_quality(void* hh, const int32_t* shape_ids, int n, int scene, int quality, char* err, int errlen) {
   try {
     auto& h = *(host_scene*)hh;
     if (n < 0 || (n > 0 && !shape_ids)) return set_error(err, errlen, "null or negative shape list"), -1;
-    rebuild_bvh(h.bvh, h.scene, vector<int>(shape_ids, shape_ids + n), scene != 0);
+    rebuild_bvh(h.bvh, h.scene, vector<int>(shape_ids, shape_ids + n), scene != 0, quality);
     for (auto i = 0; i < n; i++) h.edited_shapes.erase(shape_ids[i]);   // their boxes are current
     auto flat = std::make_unique<flat_scene>();
     flatten_scene(*flat, h.scene, h.bvh, h.lights);

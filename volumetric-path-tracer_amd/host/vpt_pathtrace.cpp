@@ -58,9 +58,39 @@ pathtrace_state make_state(const scene_data& scene, const pathtrace_params& para
 }
 
 // =============================================================================================
-// make_bvh — middle split, <=4 prims per leaf.  yocto_bvh.cpp:411-441, 447-507, 521-611
+// make_bvh — middle split (quality 0) or SAH split (quality 1), <=4 prims per leaf.  yocto_bvh.cpp:317-373, 411-441, 447-507, 521-611
 // =============================================================================================
-static void build_nodes(bvh_data& bvh, const vector<bbox3f>& bboxes) {
+static void check_quality(int quality, const char* who) {
+  if (quality != VPT_BVH_MIDDLE && quality != VPT_BVH_SAH) throw std::invalid_argument{string{who} + ": unknown bvh quality"};
+}
+// split_sah's search (include/vpt.h: vpt_build_bvh_quality), the plain form: 45 candidate planes, one pass over the node's primitives
+// each.  cbox: the box of the node's centres, not all of its sizes zero.  Returns the axis and, in `split`, the plane; {0, 0.0f} when
+// no candidate's cost is below flt_max (an empty side gives 0 * inf = NaN, which never wins).
+static int sah_search(const int* prims, int start, int end, const vector<bbox3f>& bboxes, const vector<vec3f>& centers, const bbox3f& cbox, float& split) {
+  auto area = [](const bbox3f& b) {
+    auto size = b.max - b.min;
+    return 1e-12f + 2 * size.x * size.y + 2 * size.x * size.z + 2 * size.y * size.z;
+  };
+  auto csize = cbox.max - cbox.min;
+  auto axis = 0;
+  auto min_cost = flt_max;
+  split = 0.0f;
+  for (auto saxis = 0; saxis < 3; saxis++) {
+    for (auto b = 1; b < 16; b++) {
+      auto bsplit = comp(cbox.min, saxis) + (float)b * comp(csize, saxis) / 16.0f;
+      auto left = bbox3f{}, right = bbox3f{};
+      auto nleft = 0, nright = 0;
+      for (auto i = start; i < end; i++) {
+        if (comp(centers[prims[i]], saxis) < bsplit) left = merge(left, bboxes[prims[i]]), nleft++;
+        else right = merge(right, bboxes[prims[i]]), nright++;
+      }
+      auto cost = 1 + (float)nleft * area(left) / area(cbox) + (float)nright * area(right) / area(cbox);
+      if (cost < min_cost) min_cost = cost, split = bsplit, axis = saxis;
+    }
+  }
+  return axis;
+}
+static void build_nodes(bvh_data& bvh, const vector<bbox3f>& bboxes, int quality = VPT_BVH_MIDDLE) {
   const int max_prims = 4;  // yocto_bvh.cpp:444
   auto      n         = (int)bboxes.size();
   bvh.nodes.clear();
@@ -94,10 +124,15 @@ static void build_nodes(bvh_data& bvh, const vector<bbox3f>& bboxes) {
     auto csize = cbox.max - cbox.min;
     auto mid = (start + end) / 2, axis = 0;
     if (!(csize == vec3f{0, 0, 0})) {
-      if (csize.x >= csize.y && csize.x >= csize.z) axis = 0;
-      if (csize.y >= csize.x && csize.y >= csize.z) axis = 1;
-      if (csize.z >= csize.x && csize.z >= csize.y) axis = 2;
-      auto split = comp(center(cbox), axis);
+      auto split = 0.0f;
+      if (quality == VPT_BVH_SAH) {
+        axis = sah_search(prims, start, end, bboxes, centers, cbox, split);
+      } else {
+        if (csize.x >= csize.y && csize.x >= csize.z) axis = 0;
+        if (csize.y >= csize.x && csize.y >= csize.z) axis = 1;
+        if (csize.z >= csize.x && csize.z >= csize.y) axis = 2;
+        split = comp(center(cbox), axis);
+      }
       mid = (int)(std::partition(prims + start, prims + end,
                       [&](int prim) { return comp(centers[prim], axis) < split; }) -
                   prims);
@@ -117,22 +152,23 @@ static void build_nodes(bvh_data& bvh, const vector<bbox3f>& bboxes) {
 }
 
 // the nodes of one tree: on the host (build_nodes) or on a GPU (vpt_build_bvh: the same arrays)
-static void build_nodes_on(int device, bvh_data& bvh, const vector<bbox3f>& bboxes) {
-  if (device < 0) return build_nodes(bvh, bboxes);
+static void build_nodes_on(int device, bvh_data& bvh, const vector<bbox3f>& bboxes, int quality) {
+  if (device < 0) return build_nodes(bvh, bboxes, quality);
   static_assert(sizeof(bbox3f) == 6 * sizeof(float), "bbox layout");
   auto n = (int)bboxes.size(), count = 0;
   bvh.nodes.assign((size_t)std::max(1, 2 * n), bvh_node{});
   bvh.primitives.assign((size_t)n, 0);
-  if (vpt_build_bvh(device, (const float*)bboxes.data(), n, bvh.nodes.data(), (int)bvh.nodes.size(), &count, bvh.primitives.data()) != VPT_OK)
+  if (vpt_build_bvh_quality(device, (const float*)bboxes.data(), n, quality, bvh.nodes.data(), (int)bvh.nodes.size(), &count, bvh.primitives.data()) != VPT_OK)
     throw std::runtime_error{string{"make_bvh_device: "} + vpt_last_error()};
   bvh.nodes.resize((size_t)count);
   bvh.nodes.shrink_to_fit();
 }
-bvh_data build_bvh_host(const float* bboxes, int n) {
+bvh_data build_bvh_host(const float* bboxes, int n, int quality) {
+  check_quality(quality, "build_bvh_host");
   auto boxes = vector<bbox3f>((size_t)n);
   if (n > 0) memcpy((void*)boxes.data(), bboxes, (size_t)n * sizeof(bbox3f));
   auto bvh = bvh_data{};
-  build_nodes(bvh, boxes);
+  build_nodes(bvh, boxes, quality);
   return bvh;
 }
 
@@ -175,9 +211,9 @@ static vector<bbox3f> shape_bboxes(const shape_data& shape) {
   }
   return bboxes;
 }
-static bvh_data make_shape_bvh(const shape_data& shape, int device) {
+static bvh_data make_shape_bvh(const shape_data& shape, int device, int quality) {
   auto bvh = bvh_data{};
-  build_nodes_on(device, bvh, shape_bboxes(shape));
+  build_nodes_on(device, bvh, shape_bboxes(shape), quality);
   return bvh;
 }
 
@@ -202,11 +238,11 @@ static vector<bbox3f> instance_bboxes(const scene_data& scene, const bvh_data& b
   return bboxes;
 }
 
-static bvh_scene make_bvh_on(int device, const scene_data& scene) {
+static bvh_scene make_bvh_on(int device, const scene_data& scene, int quality) {
   auto bvh = bvh_data{};
   bvh.shapes.resize(scene.shapes.size());
-  for (size_t i = 0; i < scene.shapes.size(); i++) bvh.shapes[i] = make_shape_bvh(scene.shapes[i], device);
-  build_nodes_on(device, bvh, instance_bboxes(scene, bvh));
+  for (size_t i = 0; i < scene.shapes.size(); i++) bvh.shapes[i] = make_shape_bvh(scene.shapes[i], device, quality);
+  build_nodes_on(device, bvh, instance_bboxes(scene, bvh), quality);
   return bvh;
 }
 
@@ -234,23 +270,28 @@ void update_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& upda
   for (auto shape : updated_shapes) refit_nodes(bvh.shapes.at(shape), shape_bboxes(scene.shapes.at(shape)));
   refit_nodes(bvh, instance_bboxes(scene, bvh));
 }
-void rebuild_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& shapes, bool scene_level) {
+void rebuild_bvh(bvh_scene& bvh, const scene_data& scene, const vector<int>& shapes, bool scene_level, int quality) {
+  check_quality(quality, "rebuild_bvh");
   auto seen = vector<char>(scene.shapes.size(), 0);
   for (auto shape : shapes) {
     if (shape < 0 || shape >= (int)scene.shapes.size()) throw std::invalid_argument{"rebuild_bvh: shape id out of range"};
     if (seen[(size_t)shape]) throw std::invalid_argument{"rebuild_bvh: shape id repeated"};
     seen[(size_t)shape] = 1;
   }
-  for (auto shape : shapes) bvh.shapes[(size_t)shape] = make_shape_bvh(scene.shapes[(size_t)shape], -1);
+  for (auto shape : shapes) bvh.shapes[(size_t)shape] = make_shape_bvh(scene.shapes[(size_t)shape], -1, quality);
   if (!scene_level && shapes.empty()) return;
   auto top = bvh_data{};
-  build_nodes(top, instance_bboxes(scene, bvh));
+  build_nodes(top, instance_bboxes(scene, bvh), quality);
   bvh.nodes = std::move(top.nodes), bvh.primitives = std::move(top.primitives);
 }
-bvh_scene make_bvh(const scene_data& scene, const pathtrace_params&) { return make_bvh_on(-1, scene); }
-bvh_scene make_bvh_device(const scene_data& scene, const pathtrace_params&, int device) {
+bvh_scene make_bvh(const scene_data& scene, const pathtrace_params&, int quality) {
+  check_quality(quality, "make_bvh");
+  return make_bvh_on(-1, scene, quality);
+}
+bvh_scene make_bvh_device(const scene_data& scene, const pathtrace_params&, int device, int quality) {
   if (device < 0) throw std::invalid_argument{"make_bvh_device: negative device"};
-  return make_bvh_on(device, scene);
+  check_quality(quality, "make_bvh_device");
+  return make_bvh_on(device, scene, quality);
 }
 
 // tesselate_surfaces: host/vpt_tesselate.cpp
@@ -338,8 +379,8 @@ void edit_shapes(scene_data& scene, bvh_scene& bvh, pathtrace_lights& lights, co
     if (sd.shape >= 0 && sd.shape < n) sd.shape = new_of_old[(size_t)sd.shape];
   // make_bvh for the replaced and the added shapes; the scene BVH only when a shape was replaced (another root box) - an added shape
   // has no instance yet and a removed one had none, so the untouched trees and the scene's keep the form they have, refitted or not
-  for (auto id : set_ids) bvh.shapes[(size_t)new_of_old[(size_t)id]] = make_shape_bvh(scene.shapes[(size_t)new_of_old[(size_t)id]], -1);
-  for (auto id = scene.shapes.size() - add.size(); id < scene.shapes.size(); id++) bvh.shapes[id] = make_shape_bvh(scene.shapes[id], -1);
+  for (auto id : set_ids) bvh.shapes[(size_t)new_of_old[(size_t)id]] = make_shape_bvh(scene.shapes[(size_t)new_of_old[(size_t)id]], -1, VPT_BVH_MIDDLE);
+  for (auto id = scene.shapes.size() - add.size(); id < scene.shapes.size(); id++) bvh.shapes[id] = make_shape_bvh(scene.shapes[id], -1, VPT_BVH_MIDDLE);
   if (!set.empty()) rebuild_bvh(bvh, scene, {}, true);
   lights = make_lights(scene, pathtrace_params{});
 }

@@ -6,7 +6,8 @@
 // The run itself is the reference's run_offline sequence (:41-87): load, tesselate, bvh, lights, state, N x
 // pathtrace_samples, save.  Rendering happens on the GPU through include/vpt.h; two extensions: --gpus N (tiles dealt
 // round-robin over N GPUs, same image), --batch n (samples per kernel launch; default: all in one, same image) and --gpubvh
-// (the BVHs built on the GPU by vpt_build_bvh: the same trees), --gputess (the float32 half of tesselate_surfaces on the GPU by
+// (the BVHs built on the GPU by vpt_build_bvh: the same trees), --highqualitybvh (the reference's SAH build, make_bvh(scene, true), on the
+// host or with --gpubvh on the GPU: include/vpt.h, vpt_build_bvh_quality), --gputess (the float32 half of tesselate_surfaces on the GPU by
 // vpt_subdivide_vertices: the same meshes), --adaptive t (adaptive sampling, vpt_render_adaptive: every pixel renders in rounds of
 // --adaptivestep samples until the relative standard error of its mean is within t, never below --adaptivemin samples, at most --samples;
 // the image is written from each pixel's own sample count), --denoise (denoise_render: the guided à-trous filter of include/vpt.h over
@@ -56,6 +57,7 @@ const std::vector<std::pair<string, option>> options = {
     {"gpus", {option::int_k, 1, 64, "GPUs to spread the frame's tiles over. (extension)"}},
     {"batch", {option::int_k, 0, 4096, "Samples per kernel launch, 0 = all. (extension)"}},
     {"gpubvh", {option::bool_k, 1, 0, "Build the BVHs on the GPU: same trees. (extension)"}},
+    {"highqualitybvh", {option::bool_k, 1, 0, "Use high quality BVH: the reference's SAH build. (extension)"}},
     {"gputess", {option::bool_k, 1, 0, "Subdivision vertex arithmetic on the GPU: same meshes. (extension)"}},
     {"adaptive", {option::float_k, 1, 0, "Adaptive sampling: relative noise at which a pixel stops, 0 = off. (extension)"}},
     {"adaptivemin", {option::int_k, 1, 4096, "Adaptive sampling: fewest samples before a pixel stops. (extension)"}},
@@ -199,8 +201,9 @@ int main(int argc, const char** argv) {
   get_int("adaptivemin", adaptive.min_samples), get_int("adaptivestep", adaptive.step);
   if (adaptive.min_samples > params.samples) cli_error("bad value for adaptivemin");
   if (adaptive.threshold > 0 && gpus > 1) print_fatal("--adaptive renders on one GPU: it cannot be combined with --gpus " + std::to_string(gpus));
-  auto interactive = false, gpubvh = false, gputess = false, denoise = false;
+  auto interactive = false, gpubvh = false, gputess = false, denoise = false, highqualitybvh = false;
   get_bool("interactive", interactive), get_bool("gpubvh", gpubvh), get_bool("gputess", gputess), get_bool("denoise", denoise);
+  get_bool("highqualitybvh", highqualitybvh);
   auto filter = denoise_params{};
   auto guide_samples = 16;
   get_int("denoiseiters", filter.iterations), get_int("denoiseguides", guide_samples);
@@ -261,7 +264,8 @@ int main(int argc, const char** argv) {
     if (params.camera >= (int)scene.cameras.size()) cli_error("bad value for camera");
     if (gputess) tesselate_surfaces_device(scene, 0);
     else tesselate_surfaces(scene);
-    auto bvh    = gpubvh ? make_bvh_device(scene, params, 0) : make_bvh(scene, params);
+    auto quality = highqualitybvh ? VPT_BVH_SAH : VPT_BVH_MIDDLE;
+    auto bvh     = gpubvh ? make_bvh_device(scene, params, 0, quality) : make_bvh(scene, params, quality);
     auto lights = make_lights(scene, params);
     auto frames = vector<camera_data>{};   // --cameras: one frame each; else the scene's own camera, once
     if (values.count("cameras") && !load_cameras(values["cameras"], frames, error)) print_fatal(error);
