@@ -795,6 +795,39 @@ int vpt_render_adaptive(vpt_scene* scene, const vpt_params* params, const vpt_ad
  * costs recorded): the handle's record for the layout is left as it was.  vpt_last_kernel_ms covers the whole call. */
 int vpt_render_device_adaptive(vpt_scene* scene, const vpt_params* params, const vpt_adaptive* adaptive, const vpt_layout* layout,
                                void* d_image, void* d_hits, void* d_rng, void* stream, int* rounds, int64_t* rendered);
+/* The same loop as an object, so that it can stop after any round and go on in a later call.
+ * vpt_render_device_adaptive is create + rounds(INT_MAX) + destroy.
+ *  create   the checks of vpt_render_device_adaptive and its round 0: statistics initialised, min / max of hits[] read back,
+ *           unequal hits refused (VPT_ERR_INVALID_ARG, no run is made).  The run keeps the pointers, the stream, copies of params
+ *           and adaptive, and its own scratch, sized for the full layout.
+ *  rounds   up to max_rounds more rounds of min(step, params->samples - hits) samples, each followed by the 16-byte read-back (and
+ *           the watchdog check for the implicit kernels), exactly the rounds the one-call form runs.  *rounds_done, *rendered: of this
+ *           call; *active: pixels still rendering afterwards (all three nullable).  It returns at once, with 0 rounds and nothing
+ *           enqueued, when no pixel is active or the cap is reached.  The schedule record is left alone.  vpt_last_kernel_ms covers
+ *           create and the rounds of the first call that runs any; after a later call, that call's rounds.
+ *  progress rounds, samples and active pixels so far, and the hit count of the pixels that rendered every round (each nullable).
+ *  noise_device / stats_device   the run's tile-major statistics as row-major width x height planes of this rank's pixels (others
+ *           are left as they are), asynchronous on `stream`, which must be ordered after the run's own.  The rule, for the pixel p
+ *           of every slot that owns one, with step = adaptive->step and m2, mean the Welford values of the rule above:
+ *             n_p     = (hits[p] + step - 1) / step        (integer: the rounds p rendered; it presumes the run began at hits 0)
+ *             se2[p]  = m2 / ((float)n_p * (float)(n_p - 1))   if n_p >= 2, else 0      (float32; the left side of the stop rule)
+ *             hits_out[p] = hits[p]                       (d_hits_rowmajor, nullable)
+ *           stats_device writes mean and m2 themselves.  A pixel that stopped keeps the statistics of its last round.
+ *  destroy  waits for the run's stream and frees the scratch; the state buffers are the caller's.
+ * A run is tied to its scene handle as the handle was when the run was created: ANY edit or rebuild of the scene
+ * (vpt_scene_update*, vpt_scene_rebuild_bvh*) ends the run's validity - destroy it before the edit and create another after. */
+typedef struct vpt_adaptive_run vpt_adaptive_run;
+int  vpt_adaptive_run_create(vpt_scene* scene, const vpt_params* params, const vpt_adaptive* adaptive, const vpt_layout* layout,
+                             void* d_image, void* d_hits, void* d_rng, void* stream, vpt_adaptive_run** out);
+int  vpt_adaptive_run_rounds(vpt_adaptive_run* run, int max_rounds, int* rounds_done, int64_t* rendered, int* active);
+int  vpt_adaptive_run_progress(const vpt_adaptive_run* run, int* rounds, int64_t* rendered, int* active, int* max_hits);
+int  vpt_adaptive_run_noise_device(vpt_adaptive_run* run, void* d_se2_rowmajor, void* d_hits_rowmajor, void* stream);
+int  vpt_adaptive_run_stats_device(vpt_adaptive_run* run, void* d_mean_rowmajor, void* d_m2_rowmajor, void* stream);
+void vpt_adaptive_run_destroy(vpt_adaptive_run* run);
+/* box3 of a row-major float plane, the rule stated with the denoiser below: out[p] = (sum of in over the 3x3 taps of p inside the
+ * image, dy outer -1..1, dx inner -1..1, starting at 0) / (their count, summed as float 1s).  Asynchronous on `stream`; out may
+ * not alias in.  The variance a session hands to its filter in adaptive mode is vpt_box3_device(se2). */
+int  vpt_box3_device(int width, int height, const void* d_in, void* d_out, void* stream);
 /* get_render with each pixel's own sample count: gathered tile-major float4 sums and int32 hit counts of ALL ranks
  * ([nranks][slots] each) -> row-major image[p] * (1.0f / hits[p]), 0 where hits[p] == 0.  With uniform hits it gives the
  * bits of vpt_resolve_device (the same multiplication by the same reciprocal). */
@@ -982,6 +1015,36 @@ int  vpt_session_get_state(vpt_session* session, float* image_rgba, int32_t* hit
 int  vpt_session_size(const vpt_session* session, int* width, int* height);
 int  vpt_session_samples(const vpt_session* session);
 int  vpt_session_stats(const vpt_session* session, int* launches, int64_t* bytes_to_device, int64_t* bytes_to_host);
+/* ---- adaptive sampling in a session ------------------------------------------------------------------------
+ * vpt_session_set_adaptive adopts the settings and resets; NULL switches the mode off (and resets).  Checked like
+ * vpt_render_adaptive: threshold finite and >= 0, step >= 1, 1 <= min_samples <= render.samples (VPT_ERR_INVALID_ARG; a refused
+ * call leaves the session exactly as it was).  While the mode is on, a vpt_session_reset whose params have samples < min_samples
+ * is refused in the same way.  The mode survives resets and edits; render.samples is the per-pixel cap.
+ * A reset (and so every vpt_session_edit* and rebuild, before the scene changes) drops the vpt_adaptive_run; the first advance
+ * afterwards creates it, so a reset costs what it costs without the mode.
+ * vpt_session_advance(s, nsamples) in adaptive mode runs ceil(nsamples / step) whole rounds (vpt_adaptive_run_rounds), fewer when
+ * every pixel has stopped or the cap is reached - never a partial round, so the rounds do not depend on how advances are batched -
+ * then image = vpt_resolve_hits_device(state), the filter if denoise = 1, the tone map.  It waits once per round for the 16-byte
+ * read-back (counted in bytes_to_host).  When no pixel is active it is a no-op: 0 launches, state, image and displays untouched.
+ * vpt_session_samples returns the largest hit count.
+ * Variance rule with denoise = 1 in adaptive mode: S_a and S_n are not used.  After an advance, with R rounds run since the reset:
+ * variance = vpt_box3_device(se2) of vpt_adaptive_run_noise_device if R >= 2, else the filter's spatial seed (no variance given).
+ * Read-out, each VPT_ERR_INVALID_ARG while the mode is off:
+ *   progress            rounds run since the reset, samples taken, pixels still rendering (each nullable)
+ *   get_hits            the hit counts, row-major int32 (zeros before the first advance)
+ *   get_noise           se2 and variance = box3(se2) as above, row-major float, either nullable, not both; refused before the first
+ *                       advance after a reset that ran a round
+ *   get_adaptive_stats  the Welford mean and m2 of every pixel, row-major float: the inputs of the se2 rule; refused likewise
+ * Contract: after a reset and advances that ran R rounds in total, in any split into calls, get_state returns the bits of
+ * make_state + vpt_render_adaptive with the same vpt_adaptive and params.samples = min(render.samples, R * step) - or, where that
+ * is below min_samples, of make_state + vpt_render(R * step); `image` has the bits of get_render_hits of that state; `display` is
+ * the tone map of `image`, or of the filtered image.  With threshold 0 the session is bit-identical in state, image and display
+ * to one without the mode advanced by the same sample count, the variance handed to the filter excepted. */
+int  vpt_session_set_adaptive(vpt_session* session, const vpt_adaptive* adaptive_or_null);
+int  vpt_session_progress(const vpt_session* session, int* rounds, int64_t* rendered, int* active);
+int  vpt_session_get_hits(vpt_session* session, int32_t* hits_rowmajor);
+int  vpt_session_get_noise(vpt_session* session, float* se2, float* variance);
+int  vpt_session_get_adaptive_stats(vpt_session* session, float* mean, float* m2);
 
 /* per-launch profile of the last vpt_render_device on this scene (HIP events on `stream`); synchronises with that
  * launch.  Like vpt_render it returns VPT_ERR_HIP if a wave of the implicit kernel gave up on its watchdog (a wave

@@ -580,6 +580,19 @@ hip.vpt_session_get_state.argtypes = [_p, _p, _p, _p, C.POINTER(C.c_int)]
 hip.vpt_session_size.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 hip.vpt_session_samples.argtypes = [_p]
 hip.vpt_session_stats.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+hip.vpt_adaptive_run_create.argtypes = [_p, C.POINTER(VptParams), C.POINTER(VptAdaptive), C.POINTER(VptLayout), _p, _p, _p, _p, C.POINTER(_p)]
+hip.vpt_adaptive_run_rounds.argtypes = [_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+hip.vpt_adaptive_run_progress.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+hip.vpt_adaptive_run_noise_device.argtypes = [_p, _p, _p, _p]
+hip.vpt_adaptive_run_stats_device.argtypes = [_p, _p, _p, _p]
+hip.vpt_adaptive_run_destroy.argtypes = [_p]
+hip.vpt_adaptive_run_destroy.restype = None
+hip.vpt_box3_device.argtypes = [C.c_int, C.c_int, _p, _p, _p]
+hip.vpt_session_set_adaptive.argtypes = [_p, C.POINTER(VptAdaptive)]
+hip.vpt_session_progress.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+hip.vpt_session_get_hits.argtypes = [_p, _p]
+hip.vpt_session_get_noise.argtypes = [_p, _p, _p]
+hip.vpt_session_get_adaptive_stats.argtypes = [_p, _p, _p]
 hip.vpt_last_kernel_ms.argtypes = [_p, C.POINTER(C.c_float)]
 hip.vpt_intersect.argtypes = [_p, C.c_int, _p, C.c_int, _p, _p]
 hip.vpt_build_bvh.argtypes = [C.c_int, _p, C.c_int, _p, C.c_int, C.POINTER(C.c_int), _p]
@@ -1510,6 +1523,12 @@ class DeviceScene:
                                               C.byref(rounds), C.byref(rendered)), "vpt_render_device_adaptive")
         return rounds.value, rendered.value
 
+    def adaptive_run(self, params: PathtraceParams, layout: VptLayout, d_image: int, d_hits: int, d_rng: int, threshold: float,
+                     min_samples: int = 16, step: int = 32, stream: int = 0) -> "AdaptiveRun":
+        """vpt_adaptive_run_create: render_device_adaptive as an object whose rounds() can stop and go on.  Any edit or rebuild of this
+        scene ends the run's validity: close it first."""
+        return AdaptiveRun(self, params, layout, d_image, d_hits, d_rng, threshold, min_samples, step, stream)
+
     def render_device(self, params: PathtraceParams, layout: VptLayout, nsamples: int, d_image: int, d_hits: int,
                       d_rng: int, stream: int = 0) -> None:
         abi = params.to_abi()
@@ -1732,6 +1751,53 @@ class DeviceScene:
 
     def __del__(self):
         self.close()
+
+
+class AdaptiveRun:
+    """vpt_adaptive_run (include/vpt.h): the round loop of an adaptive render on device-resident tile-major state, resumable.  The
+    pointers are raw device addresses and stay the caller's."""
+
+    def __init__(self, dev: "DeviceScene", params: PathtraceParams, layout: VptLayout, d_image: int, d_hits: int, d_rng: int,
+                 threshold: float, min_samples: int = 16, step: int = 32, stream: int = 0):
+        self.dev, self.handle = dev, None
+        abi, ad, out = params.to_abi(), VptAdaptive(threshold, min_samples, step), _p()
+        _check(hip.vpt_adaptive_run_create(dev.handle, C.byref(abi), C.byref(ad), C.byref(layout), d_image, d_hits, d_rng, stream,
+                                           C.byref(out)), "vpt_adaptive_run_create")
+        self.handle = out
+
+    def rounds(self, max_rounds: int = 2**31 - 1):
+        """up to max_rounds more rounds: (rounds run, samples taken, pixels still rendering); (0, 0, active) when there is nothing to do"""
+        done, rendered, active = C.c_int(0), C.c_int64(0), C.c_int(0)
+        _check(hip.vpt_adaptive_run_rounds(self.handle, min(max_rounds, 2**31 - 1), C.byref(done), C.byref(rendered), C.byref(active)),
+               "vpt_adaptive_run_rounds")
+        return done.value, rendered.value, active.value
+
+    def progress(self):
+        """(rounds, samples taken, pixels still rendering, hits of the pixels that rendered every round) so far"""
+        n, rendered, active, hits = C.c_int(0), C.c_int64(0), C.c_int(0), C.c_int(0)
+        _check(hip.vpt_adaptive_run_progress(self.handle, C.byref(n), C.byref(rendered), C.byref(active), C.byref(hits)),
+               "vpt_adaptive_run_progress")
+        return n.value, rendered.value, active.value, hits.value
+
+    def noise_device(self, d_se2: int, d_hits: Optional[int] = None, stream: int = 0) -> None:
+        """the squared standard error (and the hits) as row-major planes on the device"""
+        _check(hip.vpt_adaptive_run_noise_device(self.handle, d_se2, d_hits, stream), "vpt_adaptive_run_noise_device")
+
+    def stats_device(self, d_mean: int, d_m2: int, stream: int = 0) -> None:
+        _check(hip.vpt_adaptive_run_stats_device(self.handle, d_mean, d_m2, stream), "vpt_adaptive_run_stats_device")
+
+    def close(self) -> None:
+        if getattr(self, "handle", None) and hip is not None:
+            hip.vpt_adaptive_run_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        self.close()
+
+
+def box3_device(width: int, height: int, d_in: int, d_out: int, stream: int = 0) -> None:
+    """vpt_box3_device: the denoiser's box3 of a row-major float plane"""
+    _check(hip.vpt_box3_device(width, height, d_in, d_out, stream), "vpt_box3_device")
 
 
 class MultiDeviceScene:
@@ -2025,13 +2091,58 @@ class RenderSession:
     def __init__(self, dev: "DeviceScene", params: PathtraceParams, pratio: int = 8, display: Optional[DisplayParams] = None,
                  denoise: bool = False, guide_samples: int = 16, iterations: int = DENOISE_ITERATIONS,
                  sigma_luminance: float = DENOISE_SIGMA_LUMINANCE, sigma_normal: float = DENOISE_SIGMA_NORMAL,
-                 sigma_albedo: float = DENOISE_SIGMA_ALBEDO):
-        self.dev, self.handle = dev, None
+                 sigma_albedo: float = DENOISE_SIGMA_ALBEDO, adaptive=None):
+        self.dev, self.handle, self.adaptive = dev, None, None
         self._filter = VptDenoise(iterations, sigma_luminance, sigma_normal, sigma_albedo)
         abi = self._abi(params, pratio, display or DisplayParams(), denoise, guide_samples)
         out = _p()
         _check(hip.vpt_session_create(dev.handle, C.byref(abi), C.byref(out)), "vpt_session_create")
         self.handle = out
+        if adaptive is not None:  # (threshold, min_samples, step)
+            self.set_adaptive(*adaptive)
+
+    def set_adaptive(self, threshold: Optional[float], min_samples: int = 16, step: int = 32) -> None:
+        """vpt_session_set_adaptive: adaptive sampling with these settings from now on (params.samples is the per-pixel cap), and a
+        reset; set_adaptive(None) switches it off.  A refused call leaves the session as it was."""
+        if threshold is None:
+            _check(hip.vpt_session_set_adaptive(self.handle, None), "vpt_session_set_adaptive")
+            self.adaptive = None
+            return
+        ad = VptAdaptive(threshold, min_samples, step)
+        _check(hip.vpt_session_set_adaptive(self.handle, C.byref(ad)), "vpt_session_set_adaptive")
+        self.adaptive = (threshold, min_samples, step)
+
+    def progress(self):
+        """adaptive mode: (rounds run since the reset, samples taken, pixels still rendering)"""
+        n, rendered, active = C.c_int(0), C.c_int64(0), C.c_int(0)
+        _check(hip.vpt_session_progress(self.handle, C.byref(n), C.byref(rendered), C.byref(active)), "vpt_session_progress")
+        return n.value, rendered.value, active.value
+
+    def converged(self) -> bool:
+        """adaptive mode: no pixel is still rendering"""
+        return self.progress()[2] == 0
+
+    def hits(self) -> np.ndarray:
+        """adaptive mode: the samples every pixel has taken, (h, w) int32"""
+        w, h = self.size
+        out = np.zeros((h, w), np.int32)
+        _check(hip.vpt_session_get_hits(self.handle, out.ctypes.data), "vpt_session_get_hits")
+        return out
+
+    def noise(self):
+        """adaptive mode, after an advance: (se2, variance), (h, w) float32 each - the squared standard error of every pixel's mean
+        luminance over its rounds, and its box3, which the filter is handed from the second round on"""
+        w, h = self.size
+        se2, var = np.zeros((h, w), np.float32), np.zeros((h, w), np.float32)
+        _check(hip.vpt_session_get_noise(self.handle, se2.ctypes.data, var.ctypes.data), "vpt_session_get_noise")
+        return se2, var
+
+    def adaptive_stats(self):
+        """adaptive mode, after an advance: the Welford (mean, m2) of every pixel's rounds, (h, w) float32 each"""
+        w, h = self.size
+        mean, m2 = np.zeros((h, w), np.float32), np.zeros((h, w), np.float32)
+        _check(hip.vpt_session_get_adaptive_stats(self.handle, mean.ctypes.data, m2.ctypes.data), "vpt_session_get_adaptive_stats")
+        return mean, m2
 
     def _abi(self, params, pratio, display, denoise, guide_samples) -> VptSessionParams:
         self.params, self.pratio, self.display_params, self.denoise, self.guide_samples = params, pratio, display, denoise, guide_samples
@@ -2052,7 +2163,8 @@ class RenderSession:
         _check(rc, "vpt_session_reset")
 
     def advance(self, nsamples: int = 1) -> int:
-        """min(nsamples, params.samples - samples) more samples, then image and display; returns the samples reached"""
+        """min(nsamples, params.samples - samples) more samples, then image and display; returns the samples reached.  In adaptive
+        mode: ceil(nsamples / step) whole rounds over the pixels still rendering; returns the largest hit count."""
         _check(hip.vpt_session_advance(self.handle, nsamples), "vpt_session_advance")
         return self.samples
 

@@ -1,7 +1,10 @@
-// vpt_adaptive.hip — adaptive sampling on the device (include/vpt.h: vpt_render_device_adaptive, vpt_resolve_hits_device).
+// vpt_adaptive.hip — adaptive sampling on the device (include/vpt.h: vpt_adaptive_run, vpt_render_device_adaptive,
+// vpt_resolve_hits_device, vpt_box3_device).
 // After every round of the loop in vpt_capi.hip: the noise estimate of each pixel still rendering, the stop decision, and a
 // stable compaction of the pixels left into the lane -> slot table the render kernels read (sched_cfg::lane_slot), so that
-// they run 64 to a wave and converged pixels leave the launch.  Plain C++, vector stores only.
+// they run 64 to a wave and converged pixels leave the launch.  For a session: the statistics as row-major planes
+// and the box3 that makes the filter's variance of them.  Plain C++, vector stores only.
+#include <cstdint>
 #include "vpt_kernels.hip.h"
 #include "vpt_adaptive.h"
 
@@ -130,6 +133,67 @@ __global__ void vpt_resolve_hits_kernel(DParams pr, const float4* __restrict__ t
     out = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
   }
   rows_image[(long long)py * pr.width + px] = out;
+}
+
+// The statistics of a run as row-major planes (include/vpt.h: vpt_adaptive_run_noise_device).  One lane per tile-major slot, whole
+// waves inside or outside the layout as in the update kernel; a lane whose slot owns no pixel writes nothing.  Each plane is
+// optional: a null pointer is the same for every lane, so the branches are uniform.
+__global__ void __launch_bounds__(k_block) vpt_adaptive_noise_kernel(DParams pr, const float4* __restrict__ stats,
+    const int* __restrict__ hits, int step, float* __restrict__ se2, int* __restrict__ hits_out, float* __restrict__ mean_out,
+    float* __restrict__ m2_out) {
+  const int slot = blockIdx.x * k_block + threadIdx.x;
+  if (slot - (int)(threadIdx.x & 63) >= pr.nslots) return;   // the whole wave is past the layout
+  int px, py;
+  if (!slot_to_pixel(pr, slot, px, py)) return;   // padding, or another rank's
+  const float4    st = stats[slot];
+  const int       h  = hits[slot];
+  const int       n  = (h + step - 1) / step;   // rounds this pixel rendered (the run started from hits 0)
+  const long long p  = (long long)py * pr.width + px;
+  if (se2) se2[p] = n >= 2 ? st.z / ((float)n * (float)(n - 1)) : 0.0f;
+  if (hits_out) hits_out[p] = h;
+  if (mean_out) mean_out[p] = st.y;
+  if (m2_out) m2_out[p] = st.z;
+}
+
+// box3 of a row-major float plane by the denoiser's rule (include/vpt.h; csrc/vpt_denoise.hip takes it the same way inside its two
+// variance seeds): dy outer, dx inner, taps outside the image skipped, the count summed as 1s.  A wave is 64 pixels of one row.
+__global__ void __launch_bounds__(k_block) vpt_box3_kernel(const float* __restrict__ in, float* __restrict__ out, int width, int height) {
+  const int px = blockIdx.x * 64 + (threadIdx.x & 63), py = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (px >= width || py >= height) return;
+  float sum = 0, count = 0;
+#pragma unroll
+  for (int dy = -1; dy <= 1; dy++) {
+    const int qy = py + dy;
+    if (qy < 0 || qy >= height) continue;
+#pragma unroll
+    for (int dx = -1; dx <= 1; dx++) {
+      const int qx = px + dx;
+      if (qx < 0 || qx >= width) continue;
+      sum = sum + in[(size_t)qy * width + qx], count = count + 1.0f;
+    }
+  }
+  out[(size_t)py * width + px] = sum / count;
+}
+
+extern "C" int vpt_box3_device(int width, int height, const void* d_in, void* d_out, void* stream) {
+  REQUIRE(width >= 1 && height >= 1, "bad image size: width %d, height %d", width, height);
+  REQUIRE((long long)width * height <= (1LL << 28), "image too large: width %d, height %d", width, height);   // as vpt_denoise: every index fits
+  REQUIRE(d_in, "null in");
+  REQUIRE(d_out, "null out");
+  const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out, bytes = (uintptr_t)width * height * 4;
+  REQUIRE(!(a < b + bytes && b < a + bytes), "out aliases in");
+  hipLaunchKernelGGL(vpt_box3_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(k_block), 0, (hipStream_t)stream, (const float*)d_in,
+      (float*)d_out, width, height);
+  HIP_TRY(hipGetLastError());
+  return VPT_OK;
+}
+
+int adaptive_noise(const DParams& pr, const adaptive_buffers& b, const int* hits, int step, float* se2, int* hits_out, float* mean_out,
+    float* m2_out, hipStream_t st) {
+  hipLaunchKernelGGL(vpt_adaptive_noise_kernel, dim3((pr.nslots + k_block - 1) / k_block), dim3(k_block), 0, st, pr, (const float4*)b.stats, hits,
+      step, se2, hits_out, mean_out, m2_out);
+  HIP_TRY(hipGetLastError());
+  return VPT_OK;
 }
 
 int adaptive_update(const DParams& pr, const float4* image, const int* hits, const adaptive_buffers& b, int n, int m,

@@ -9,6 +9,8 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
+#include <climits>
+#include <memory>
 #include <type_traits>
 #include <string>
 #include <vector>
@@ -742,6 +744,30 @@ static int render_host_state(vpt_scene* s, int width, int height, float* image_r
   return vpt_check_watchdog(s);
 }
 
+// vpt_adaptive_run (include/vpt.h): what the round loop of an adaptive render holds between rounds
+struct vpt_adaptive_run {
+  vpt_scene*       s = nullptr;
+  vpt_params       params = {};
+  vpt_adaptive     a = {};
+  DParams          pr = {};
+  hipStream_t      st = nullptr;
+  float4*          img = nullptr;
+  int*             hit = nullptr;
+  ulonglong2*      rng = nullptr;
+  bool             implicit = false;
+  device_buffer    d_stats, d_wave_count, d_lane_slot, d_info;   // vpt_adaptive.h, sized for the full layout
+  adaptive_buffers b = {};
+  int              info[4] = {0, 0, 0, 0};   // the last read-back: {pixels still rendering, min hits, max hits on entry, unused}
+  int              h = 0, n = 0;             // hits of every pixel still rendering, rounds so far
+  long long        taken = 0;                // samples so far
+  bool             timing_open = false;      // ev0 was recorded by create and no round has run since
+  int read_info() {   // the one read-back of a round: what sizes the next launch
+    HIP_TRY(hipMemcpyAsync(info, b.info, sizeof(info), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return VPT_OK;
+  }
+};
+
 // the arguments of an adaptive render, checked before anything touches the device
 static int check_adaptive(const vpt_scene* s, const vpt_params* params, const vpt_adaptive* a) {
   if (!params || !a) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
@@ -759,59 +785,129 @@ static int check_adaptive(const vpt_scene* s, const vpt_params* params, const vp
 
 extern "C" {
 
-// Adaptive sampling (include/vpt.h): rounds of one launch each over the pixels still rendering, packed 64 to a wave
-// through sched_cfg::lane_slot by the kernels of vpt_adaptive.hip.  No pilot, no order, no costs, no tile splitting: the handle's
-// launch schedule for the layout stays as vpt_render_device left it.
+// Adaptive sampling (include/vpt.h): rounds of one launch each over the pixels still rendering, packed 64 to a
+// wave through sched_cfg::lane_slot by the kernels of vpt_adaptive.hip.  No pilot, no order, no costs, no tile splitting: the handle's
+// launch schedule for the layout stays as vpt_render_device left it.  A run holds what the round loop holds, so that the loop can
+// stop after any round and go on in a later call.
+int vpt_adaptive_run_create(vpt_scene* s, const vpt_params* params, const vpt_adaptive* a, const vpt_layout* layout, void* d_image,
+    void* d_hits, void* d_rng, void* stream, vpt_adaptive_run** out) {
+  if (!out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  if (int rc = check_adaptive(s, params, a)) return rc;
+  if (!layout || !d_image || !d_hits || !d_rng) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  std::unique_ptr<vpt_adaptive_run> r(new vpt_adaptive_run{});
+  if (int rc = make_dparams(params, layout, 0, r->pr)) return rc;
+  r->s = s, r->params = *params, r->a = *a, r->st = (hipStream_t)stream;
+  r->img = (float4*)d_image, r->hit = (int*)d_hits, r->rng = (ulonglong2*)d_rng;
+  r->implicit = params->shader >= VPT_SHADER_IMPLICIT;
+  if (r->implicit)
+    if (int rc = implicit_lds(s)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const DParams&  pr   = r->pr;
+  const long long full = (pr.nslots + VPT_BLOCK - 1) / VPT_BLOCK;
+  stack_cfg stack;   // the spilled stacks are indexed by global lane: sized for the full layout, a compacted grid is never larger
+  if (int rc = stack_config(s, full * VPT_BLOCK, stack)) return rc;
+  if (int rc = r->d_stats.allocate((size_t)pr.nslots * 16)) return rc;
+  if (int rc = r->d_wave_count.allocate((size_t)full * 4)) return rc;
+  if (int rc = r->d_lane_slot.allocate((size_t)pr.nslots * 4)) return rc;
+  if (int rc = r->d_info.allocate(16)) return rc;
+  r->b = {r->d_stats.get<float4>(), r->d_wave_count.get<int>(), r->d_lane_slot.get<int>(), r->d_info.get<int>()};
+  HIP_TRY(hipEventRecord(s->ev0, r->st));
+  s->sched.no_pause();
+  if (int rc = adaptive_update(pr, r->img, r->hit, r->b, 0, 0, r->a, params->samples, r->st)) return rc;
+  if (int rc = r->read_info()) return rc;
+  if (r->info[1] < r->info[2])
+    return vpt_set_error(VPT_ERR_INVALID_ARG, "hits[] must be equal on entry (found %d .. %d)", r->info[1], r->info[2]);
+  r->h = r->info[1], r->timing_open = true;
+  *out = r.release();
+  return VPT_OK;
+}
+
+int vpt_adaptive_run_rounds(vpt_adaptive_run* r, int max_rounds, int* rounds_done, int64_t* rendered, int* active) {
+  if (rounds_done) *rounds_done = 0;
+  if (rendered) *rendered = 0;
+  if (active) *active = 0;
+  if (!r) return vpt_set_error(VPT_ERR_INVALID_ARG, "null run");
+  if (max_rounds < 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "negative round count");
+  vpt_scene* s   = r->s;
+  const int  cap = r->params.samples;
+  if (active) *active = r->info[0];
+  if (max_rounds == 0 || r->info[0] <= 0 || r->h >= cap) return VPT_OK;   // nothing is enqueued
+  HIP_TRY(hipSetDevice(s->device));
+  const DParams& pr = r->pr;
+  stack_cfg      stack;   // taken per call: a larger launch on the handle in between may have moved the spilled stacks
+  if (int rc = stack_config(s, (long long)((pr.nslots + VPT_BLOCK - 1) / VPT_BLOCK) * VPT_BLOCK, stack)) return rc;
+  const launch_ctx L = {s, r->st, r->img, r->hit, r->rng, stack};
+  if (!r->timing_open) {   // the first call's timing starts where the run was created; a later call's at its own first round
+    HIP_TRY(hipEventRecord(s->ev0, r->st));
+    s->sched.no_pause();
+  }
+  r->timing_open = false;
+  int       done  = 0;
+  long long taken = 0;
+  for (int act = r->info[0]; done < max_rounds && act > 0 && r->h < cap; act = r->info[0]) {
+    DParams rp  = pr;
+    rp.nsamples = std::min(r->a.step, cap - r->h);
+    const sched_cfg sch = {nullptr, nullptr, r->b.lane_slot};
+    launcher_of(r->params.shader)(L, false, dim3((unsigned)((act + VPT_BLOCK - 1) / VPT_BLOCK)), rp, sch);
+    HIP_TRY(hipGetLastError());
+    taken += (long long)act * rp.nsamples, r->h += rp.nsamples, r->n++, done++;
+    if (int rc = adaptive_update(pr, r->img, r->hit, r->b, r->n, rp.nsamples, r->a, cap, r->st)) return rc;
+    if (int rc = r->read_info()) return rc;
+    if (r->implicit)
+      if (int rc = vpt_check_watchdog(s)) return rc;
+  }
+  HIP_TRY(hipEventRecord(s->ev1, r->st));
+  s->timed = true;
+  r->taken += taken;
+  if (rounds_done) *rounds_done = done;
+  if (rendered) *rendered = taken;
+  if (active) *active = r->info[0];
+  return VPT_OK;
+}
+
+int vpt_adaptive_run_progress(const vpt_adaptive_run* r, int* rounds, int64_t* rendered, int* active, int* max_hits) {
+  if (!r) return vpt_set_error(VPT_ERR_INVALID_ARG, "null run");
+  if (rounds) *rounds = r->n;
+  if (rendered) *rendered = r->taken;
+  if (active) *active = r->h >= r->params.samples ? 0 : r->info[0];
+  if (max_hits) *max_hits = r->h;
+  return VPT_OK;
+}
+
+int vpt_adaptive_run_noise_device(vpt_adaptive_run* r, void* d_se2_rowmajor, void* d_hits_rowmajor, void* stream) {
+  if (!r || !d_se2_rowmajor) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(r->s->device));
+  return adaptive_noise(r->pr, r->b, r->hit, r->a.step, (float*)d_se2_rowmajor, (int*)d_hits_rowmajor, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int vpt_adaptive_run_stats_device(vpt_adaptive_run* r, void* d_mean_rowmajor, void* d_m2_rowmajor, void* stream) {
+  if (!r || !d_mean_rowmajor || !d_m2_rowmajor) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(r->s->device));
+  return adaptive_noise(r->pr, r->b, r->hit, r->a.step, nullptr, nullptr, (float*)d_mean_rowmajor, (float*)d_m2_rowmajor, (hipStream_t)stream);
+}
+
+void vpt_adaptive_run_destroy(vpt_adaptive_run* r) {
+  if (!r) return;
+  (void)hipSetDevice(r->s->device);
+  (void)hipStreamSynchronize(r->st);   // nothing reads the scratch when it goes
+  delete r;
+}
+
 int vpt_render_device_adaptive(vpt_scene* s, const vpt_params* params, const vpt_adaptive* a, const vpt_layout* layout, void* d_image,
     void* d_hits, void* d_rng, void* stream, int* rounds, int64_t* rendered) {
   if (rounds) *rounds = 0;
   if (rendered) *rendered = 0;
-  if (int rc = check_adaptive(s, params, a)) return rc;
-  if (!layout || !d_image || !d_hits || !d_rng) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  DParams pr;
-  if (int rc = make_dparams(params, layout, 0, pr)) return rc;
-  const bool implicit = params->shader >= VPT_SHADER_IMPLICIT;
-  if (implicit)
-    if (int rc = implicit_lds(s)) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  hipStream_t     st   = (hipStream_t)stream;
-  const long long full = (pr.nslots + VPT_BLOCK - 1) / VPT_BLOCK;
-  stack_cfg stack;   // the spilled stacks are indexed by global lane: sized for the full layout, a compacted grid is never larger
-  if (int rc = stack_config(s, full * VPT_BLOCK, stack)) return rc;
-  device_buffer d_stats, d_wave_count, d_lane_slot, d_info;   // scratch of this call (vpt_adaptive.h)
-  if (int rc = d_stats.allocate((size_t)pr.nslots * 16)) return rc;
-  if (int rc = d_wave_count.allocate((size_t)full * 4)) return rc;
-  if (int rc = d_lane_slot.allocate((size_t)pr.nslots * 4)) return rc;
-  if (int rc = d_info.allocate(16)) return rc;
-  const adaptive_buffers b = {d_stats.get<float4>(), d_wave_count.get<int>(), d_lane_slot.get<int>(), d_info.get<int>()};
-  const launch_ctx L = {s, st, (float4*)d_image, (int*)d_hits, (ulonglong2*)d_rng, stack};
-  int  info[4] = {0, 0, 0, 0};
-  auto read_info = [&]() -> int {   // the one read-back of a round: what sizes the next launch
-    HIP_TRY(hipMemcpyAsync(info, b.info, sizeof(info), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return VPT_OK;
-  };
-  HIP_TRY(hipEventRecord(s->ev0, st));
-  s->sched.no_pause();
-  if (int rc = adaptive_update(pr, L.img, L.hit, b, 0, 0, *a, params->samples, st)) return rc;
-  if (int rc = read_info()) return rc;
-  if (info[1] < info[2]) return vpt_set_error(VPT_ERR_INVALID_ARG, "hits[] must be equal on entry (found %d .. %d)", info[1], info[2]);
-  int       h = info[1], n = 0;   // hits of every pixel still rendering, rounds so far
-  long long taken = 0;
-  for (int active = info[0]; active > 0 && h < params->samples; active = info[0]) {
-    DParams rp  = pr;
-    rp.nsamples = std::min(a->step, params->samples - h);
-    const sched_cfg sch = {nullptr, nullptr, b.lane_slot};
-    launcher_of(params->shader)(L, false, dim3((unsigned)((active + VPT_BLOCK - 1) / VPT_BLOCK)), rp, sch);
-    HIP_TRY(hipGetLastError());
-    taken += (long long)active * rp.nsamples, h += rp.nsamples, n++;
-    if (int rc = adaptive_update(pr, L.img, L.hit, b, n, rp.nsamples, *a, params->samples, st)) return rc;
-    if (int rc = read_info()) return rc;
-    if (implicit)
-      if (int rc = vpt_check_watchdog(s)) return rc;
+  vpt_adaptive_run* r = nullptr;
+  if (int rc = vpt_adaptive_run_create(s, params, a, layout, d_image, d_hits, d_rng, stream, &r)) return rc;
+  struct guard { vpt_adaptive_run* r; ~guard() { vpt_adaptive_run_destroy(r); } } g{r};
+  int     n     = 0;
+  int64_t taken = 0;
+  if (int rc = vpt_adaptive_run_rounds(r, INT_MAX, &n, &taken, nullptr)) return rc;
+  if (n == 0) {   // nothing to render: the call's timing still closes, as it always has
+    HIP_TRY(hipEventRecord(s->ev1, (hipStream_t)stream));
+    s->timed = true;
   }
-  HIP_TRY(hipEventRecord(s->ev1, st));
-  s->timed = true;
   if (rounds) *rounds = n;
   if (rendered) *rendered = taken;
   return VPT_OK;

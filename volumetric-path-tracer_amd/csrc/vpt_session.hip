@@ -183,6 +183,12 @@ struct vpt_session {
   device_buffer normal, albedo, variance, sum_a, sum_n, filtered, scratch;
   bool          denoise_allocated = false, has_albedo = false, filtered_valid = false;
   int           a = 0;   // samples behind sum_a (0: none)
+  // adaptive mode (vpt_session_set_adaptive): the run lives from the first advance after a reset to the next reset
+  bool              adaptive = false;
+  vpt_adaptive      ad       = {};
+  vpt_adaptive_run* run      = nullptr;
+  device_buffer     a_se2, a_var, a_hits, a_mean, a_m2;   // row-major planes of the run's statistics
+  long long         a_pixels = 0;
   // what the last call cost
   int     launches = 0;
   int64_t up = 0, down = 0;
@@ -220,6 +226,18 @@ int check_session_params(const vpt_session_params* p) {
 }
 
 void begin_call(vpt_session* s) { s->launches = 0, s->up = 0, s->down = 0; }
+
+void drop_run(vpt_session* s) {
+  if (s->run) vpt_adaptive_run_destroy(s->run);
+  s->run = nullptr;
+}
+// vpt_session_set_adaptive's conditions, against the per-pixel cap `samples`
+int check_session_adaptive(const vpt_adaptive* a, int samples) {
+  REQUIRE(std::isfinite(a->threshold) && a->threshold >= 0, "adaptive threshold must be finite and >= 0");
+  REQUIRE(a->step >= 1, "adaptive step must be >= 1");
+  REQUIRE(a->min_samples >= 1 && a->min_samples <= samples, "adaptive min_samples must be in 1 .. render.samples (%d)", samples);
+  return VPT_OK;
+}
 
 int allocate(vpt_session* s, int width, int height, int pw, int ph, bool denoise) {
   s->width = s->height = 0, s->denoise_allocated = false, s->r_pixels = 0;
@@ -272,6 +290,7 @@ int reset(vpt_session* s, const vpt_session_params& np) {
   REQUIRE(width >= 1 && height >= 1 && pw >= 1 && ph >= 1, "camera aspect %g leaves an empty frame (%d x %d, preview %d x %d)", (double)cam.aspect,
       width, height, pw, ph);
   HIP_TRY(hipStreamSynchronize(s->st));   // nothing of the previous frame is in flight when its buffers go
+  drop_run(s);                            // an adaptive run ends here; the first advance makes the next
   if (width != s->width || height != s->height || pw != s->pw || ph != s->ph || (np.denoise != 0) != s->denoise_allocated)
     if (int rc = allocate(s, width, height, pw, ph, np.denoise != 0)) return rc;
   s->p = np, s->samples = 0, s->a = 0, s->filtered_valid = false, s->has_albedo = false;
@@ -307,6 +326,44 @@ int fetch(vpt_session* s, void* host, const device_buffer& from, size_t bytes) {
   return VPT_OK;
 }
 
+// vpt_session_advance in adaptive mode (include/vpt.h): whole rounds of the run, the per-pixel resolve, the noise planes, the filter
+// with the handed-over variance, the tone map
+int advance_adaptive(vpt_session* s, int nsamples) {
+  const int want = (int)(((long long)nsamples + s->ad.step - 1) / s->ad.step);
+  if (want <= 0) return VPT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  void *img = s->s_image.get(), *hit = s->s_hits.get(), *rng = s->s_rng.get();
+  const size_t n = (size_t)s->width * s->height;
+  if (!s->run) {
+    if (s->a_pixels != (long long)n) {
+      s->a_pixels = 0;
+      for (device_buffer* b : {&s->a_se2, &s->a_var, &s->a_hits, &s->a_mean, &s->a_m2})
+        if (int rc = b->allocate(n * 4)) return rc;
+      s->a_pixels = (long long)n;
+    }
+    if (int rc = vpt_adaptive_run_create(s->scene, &s->p.render, &s->ad, &s->lay, img, hit, rng, s->st, &s->run)) return rc;
+    s->launches++, s->down += 16;
+  }
+  int     done = 0, active = 0, rounds = 0, hits = 0;
+  int64_t taken = 0;
+  if (int rc = vpt_adaptive_run_rounds(s->run, want, &done, &taken, &active)) return rc;
+  if (done == 0) return VPT_OK;   // every pixel has stopped: nothing was enqueued, state and displays stay
+  s->launches += done, s->down += (implicit_shader(s->p.render.shader) ? 20 : 16) * (int64_t)done;   // the read-back, the watchdog's word
+  if (int rc = vpt_adaptive_run_progress(s->run, &rounds, nullptr, nullptr, &hits)) return rc;
+  s->samples = hits;
+  if (int rc = vpt_resolve_hits_device(&s->lay, img, hit, s->image.get(), s->st)) return rc;
+  if (int rc = vpt_adaptive_run_noise_device(s->run, s->a_se2.get(), s->a_hits.get(), s->st)) return rc;
+  if (int rc = vpt_box3_device(s->width, s->height, s->a_se2.get(), s->a_var.get(), s->st)) return rc;
+  s->launches += 3;
+  if (s->p.denoise) {
+    if (int rc = vpt_denoise_device(&s->p.filter, s->width, s->height, s->image.get(), s->normal.get(), s->has_albedo ? s->albedo.get() : nullptr,
+            rounds >= 2 ? s->a_var.get() : nullptr, s->filtered.get(), s->scratch.get(), s->st))
+      return rc;
+    s->filtered_valid = true, s->launches++;
+  }
+  return tonemap_display(s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -331,6 +388,7 @@ int vpt_session_create(vpt_scene* scene, const vpt_session_params* params, vpt_s
 void vpt_session_destroy(vpt_session* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);   // the buffers are freed on the session's device
+  drop_run(s);
   if (s->st) (void)hipStreamSynchronize(s->st), (void)hipStreamDestroy(s->st);
   delete s;
 }
@@ -339,6 +397,8 @@ int vpt_session_reset(vpt_session* s, const vpt_session_params* params_or_null) 
   REQUIRE(s, "null session");
   if (params_or_null)
     if (int rc = check_session_params(params_or_null)) return rc;
+  if (params_or_null && s->adaptive)
+    if (int rc = check_session_adaptive(&s->ad, params_or_null->render.samples)) return rc;
   HIP_TRY(hipSetDevice(s->device));
   begin_call(s);
   const vpt_session_params np = params_or_null ? *params_or_null : s->p;
@@ -350,6 +410,7 @@ int vpt_session_advance(vpt_session* s, int nsamples) {
   REQUIRE(nsamples >= 0, "negative sample count");
   REQUIRE(s->width > 0, "the session holds no frame (a reset failed)");
   begin_call(s);
+  if (s->adaptive) return advance_adaptive(s, nsamples);
   const int todo = std::min(nsamples, s->p.render.samples - s->samples);   // a no-op once reached, yocto_pathtrace.cpp:1055
   if (todo <= 0) return VPT_OK;
   HIP_TRY(hipSetDevice(s->device));
@@ -480,6 +541,75 @@ int vpt_session_get_state(vpt_session* s, float* image_rgba, int32_t* hits, uint
   if (int rc = fetch(s, rng, s->r_rng, n * 16)) return rc;
   HIP_TRY(hipStreamSynchronize(s->st));
   *samples = s->samples;
+  return VPT_OK;
+}
+
+int vpt_session_set_adaptive(vpt_session* s, const vpt_adaptive* a) {
+  REQUIRE(s, "null session");
+  if (a)
+    if (int rc = check_session_adaptive(a, s->p.render.samples)) return rc;
+  REQUIRE(s->width > 0, "the session holds no frame (a reset failed)");
+  HIP_TRY(hipSetDevice(s->device));
+  begin_call(s);
+  s->adaptive = a != nullptr;
+  if (a) s->ad = *a;
+  return reset(s, s->p);
+}
+
+int vpt_session_progress(const vpt_session* s, int* rounds, int64_t* rendered, int* active) {
+  REQUIRE(s, "null session");
+  REQUIRE(s->adaptive, "the session is not in adaptive mode");
+  if (s->run) return vpt_adaptive_run_progress(s->run, rounds, rendered, active, nullptr);
+  if (rounds) *rounds = 0;
+  if (rendered) *rendered = 0;
+  if (active) *active = s->width * s->height;   // nothing has rendered: every pixel is to
+  return VPT_OK;
+}
+
+int vpt_session_get_hits(vpt_session* s, int32_t* hits) {
+  REQUIRE(s && hits, "null argument");
+  REQUIRE(s->adaptive, "the session is not in adaptive mode");
+  REQUIRE(s->width > 0, "the session holds no frame (a reset failed)");
+  begin_call(s);
+  const size_t n = (size_t)s->width * s->height;
+  if (!s->run) {
+    memset(hits, 0, n * 4);
+    return VPT_OK;
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  if (int rc = fetch(s, hits, s->a_hits, n * 4)) return rc;
+  HIP_TRY(hipStreamSynchronize(s->st));
+  return VPT_OK;
+}
+
+int vpt_session_get_noise(vpt_session* s, float* se2, float* variance) {
+  REQUIRE(s, "null session");
+  REQUIRE(se2 || variance, "null se2 and variance: nothing to fetch");
+  REQUIRE(s->adaptive, "the session is not in adaptive mode");
+  REQUIRE(s->run, "no noise estimate: no advance has run since the last reset");
+  HIP_TRY(hipSetDevice(s->device));
+  begin_call(s);
+  const size_t n = (size_t)s->width * s->height;
+  if (se2)
+    if (int rc = fetch(s, se2, s->a_se2, n * 4)) return rc;
+  if (variance)
+    if (int rc = fetch(s, variance, s->a_var, n * 4)) return rc;
+  HIP_TRY(hipStreamSynchronize(s->st));
+  return VPT_OK;
+}
+
+int vpt_session_get_adaptive_stats(vpt_session* s, float* mean, float* m2) {
+  REQUIRE(s && mean && m2, "null argument");
+  REQUIRE(s->adaptive, "the session is not in adaptive mode");
+  REQUIRE(s->run, "no statistics: no advance has run since the last reset");
+  HIP_TRY(hipSetDevice(s->device));
+  begin_call(s);
+  const size_t n = (size_t)s->width * s->height;
+  if (int rc = vpt_adaptive_run_stats_device(s->run, s->a_mean.get(), s->a_m2.get(), s->st)) return rc;
+  s->launches++;
+  if (int rc = fetch(s, mean, s->a_mean, n * 4)) return rc;
+  if (int rc = fetch(s, m2, s->a_m2, n * 4)) return rc;
+  HIP_TRY(hipStreamSynchronize(s->st));
   return VPT_OK;
 }
 

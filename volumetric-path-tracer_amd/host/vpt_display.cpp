@@ -111,6 +111,21 @@ void render_session::set_display(float exposure, bool filmic) {
   auto display = vpt_display_params{exposure, filmic ? 1 : 0, 1};
   if (vpt_session_set_display(session_, &display) != VPT_OK) fail("vpt_session_set_display");
 }
+void render_session::set_adaptive(const pathtrace_adaptive_params& adaptive) {
+  auto abi = vpt_adaptive{adaptive.threshold, adaptive.min_samples, adaptive.step};
+  if (vpt_session_set_adaptive(session_, adaptive.threshold < 0 ? nullptr : &abi) != VPT_OK) fail("vpt_session_set_adaptive");
+}
+render_session::progress_stats render_session::progress() const {
+  auto out = progress_stats{};
+  if (vpt_session_progress(session_, &out.rounds, &out.samples, &out.active) != VPT_OK) fail("vpt_session_progress");
+  return out;
+}
+bool        render_session::converged() const { return progress().active == 0; }
+vector<int> render_session::hits() {
+  auto out = vector<int>((size_t)width() * height());
+  if (vpt_session_get_hits(session_, out.data()) != VPT_OK) fail("vpt_session_get_hits");
+  return out;
+}
 int render_session::width() const {
   auto w = 0, h = 0;
   vpt_session_size(session_, &w, &h);

@@ -329,6 +329,18 @@ class render_session {
   void reset(const render_session_params& params);
   void advance(int nsamples);
   void set_display(float exposure, bool filmic);
+  // adaptive sampling in the session (vpt_session_set_adaptive): these settings from now on, params.render.samples being the per-pixel
+  // cap, and a reset; a threshold < 0 switches the mode off.  advance(n) then runs ceil(n / step) whole rounds over the pixels still
+  // rendering, samples() is the largest hit count, and image() holds every pixel over its own count.
+  void set_adaptive(const pathtrace_adaptive_params& adaptive);
+  struct progress_stats {
+    int     rounds  = 0;   // rounds run since the reset
+    int64_t samples = 0;   // samples taken over all pixels
+    int     active  = 0;   // pixels still rendering
+  };
+  progress_stats progress() const;    // adaptive mode only
+  bool           converged() const;   // adaptive mode only: no pixel is still rendering
+  vector<int>    hits();              // adaptive mode only: the samples every pixel has taken, row-major
   int  width() const;
   int  height() const;
   int  samples() const;

@@ -70,6 +70,7 @@ const std::vector<std::pair<string, option>> options = {
     {"denoisesigmanormal", {option::posfloat_k, 1, 0, "Denoising: tolerance of the normal guide. (extension)"}},
     {"denoisesigmaalbedo", {option::posfloat_k, 1, 0, "Denoising: tolerance of the albedo guide. (extension)"}},
     {"progressive", {option::int_k, 1, 4096, "Render progressively on the GPU, a display frame every N samples. (extension)"}},
+    {"converge", {option::float_k, 1, 0, "Progressive: stop a pixel at this relative noise and the render when all have stopped; a round per display frame. (extension)"}},
     {"pratio", {option::int_k, 1, 64, "Progressive: preview ratio."}},
     {"exposure", {option::anyfloat_k, 1, 0, "Progressive: display exposure."}},
     {"filmic", {option::bool_k, 1, 0, "Progressive: filmic tone mapping."}},
@@ -216,7 +217,7 @@ int main(int argc, const char** argv) {
   auto progressive = 0;
   get_int("progressive", progressive), get_int("pratio", params.pratio), get_float("exposure", params.exposure), get_bool("filmic", params.filmic);
   if (!progressive)
-    for (auto name : {"exposure", "filmic", "pratio"})
+    for (auto name : {"exposure", "filmic", "pratio", "converge"})
       if (values.count(name)) cli_error(string{"option "} + name + " needs --progressive");
   if (progressive && gpus > 1) cli_error("option progressive renders on one GPU: it cannot be combined with gpus " + std::to_string(gpus));
   if (progressive && adaptive.threshold > 0) cli_error("option progressive cannot be combined with adaptive");
@@ -339,7 +340,19 @@ int main(int argc, const char** argv) {
       auto session = render_session{scene, bvh, lights, sp, 0};
       save_display(session, numbered(0));
       auto shown = 0;
-      while (session.samples() < params.samples) {
+      if (values.count("converge")) {   // adaptive rounds of N samples, one per display frame, until every pixel has stopped
+        auto converge = pathtrace_adaptive_params{strtof(values["converge"].c_str(), nullptr), adaptive.min_samples, progressive};
+        session.set_adaptive(converge);
+        while (!session.converged() && session.samples() < params.samples) {
+          session.advance(progressive);
+          save_display(session, numbered(session.samples())), shown++;
+        }
+        auto stats = session.progress();
+        auto full  = (double)session.width() * session.height() * params.samples;
+        printf("converge: %d rounds, %lld samples taken of %.0f (%.1f %%), %d pixels still rendering\n", stats.rounds, (long long)stats.samples,
+            full, 100.0 * (double)stats.samples / full, stats.active);
+      }
+      while (!values.count("converge") && session.samples() < params.samples) {
         session.advance(progressive);
         save_display(session, numbered(session.samples())), shown++;
       }
