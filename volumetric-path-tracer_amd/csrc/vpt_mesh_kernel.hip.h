@@ -189,6 +189,30 @@ VPT_DEV bool slab_pass_signed(float nx, float ny, float nz, float fx, float fy, 
 #define VPT_NONE (-2147483647 - 1)
 #define VPT_HOIST_MAX 16   // scenes with at most this many instances test all root boxes at the start of a query
 #define VPT_COOP_MAX 16    // a phase with at most this many rays runs in its group form (four lanes per ray); 0: own forms only
+
+// The pop of the group form of A: entries of `stk` above `floor` are popped until one passes the reference's pop-time box test against
+// `tmax` (file header); VPT_NONE when the level is exhausted.  The top entry is accepted most of the time: its {ref, t0} are read together
+// (one paired LDS read) and tested in straight-line code, and only a rejected one enters the loop.  The order of reads and the accepted
+// entry are the loop's.  (The own form keeps the plain loop, pop_valid: peeled, the lean instance spills two more registers.)
+template <class STK>
+VPT_DEV int pop_passing(const STK& stk, int& sp, int floor, float tmax) {
+  if (sp <= floor) return VPT_NONE;
+  const bool  lds_only = stk.room_for(sp, 0);   // sp only falls from here on
+  const float tk = tmax * VPT_BOX_K;
+  int   ref;
+  float t0;
+  sp--;
+  if (lds_only) stk.load_lds(sp, ref, t0);
+  else stk.load(sp, ref, t0);
+  if (t0 <= tk) return ref;
+  while (sp > floor) {
+    sp--;
+    if (lds_only) stk.load_lds(sp, ref, t0);
+    else stk.load(sp, ref, t0);
+    if (t0 <= tk) return ref;
+  }
+  return VPT_NONE;
+}
 template <bool COMPACT = false, bool CURVES = false, class STK>
 VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_instance, const STK& stk) {
   constexpr int LS = COMPACT ? 3 : 4;   // float4 per leaf record
@@ -303,10 +327,10 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
 
   // ---- own form of A: one quad-node step of this lane's ray ------------------------------------------------------------
   auto own_node_step = [&]() {
-    const float4* q = sc.scene_wnodes + 8 * (long long)(wnb + cur);
+    const float4* q = sc.scene_wnodes + 8 * (unsigned long long)(unsigned)(wnb + cur);   // (cur >= 0: no sign to extend)
     // rows of the node: lo.x lo.y lo.z hi.x hi.y hi.z (four children each).  The near plane of an axis is
     // the lo row for a positive direction, the hi row for a negative one: fetch them by the ray's signs
-    int    ix = (csgn & 1) ? 3 : 0, iy = (csgn & 2) ? 4 : 1, iz = (csgn & 4) ? 5 : 2;
+    unsigned ix = (csgn & 1) ? 3 : 0, iy = (csgn & 2) ? 4 : 1, iz = (csgn & 4) ? 5 : 2;
     float4 nx = q[ix], fx = q[3 - ix], ny = q[iy], fy = q[5 - iy], nz = q[iz], fz = q[7 - iz], qr = q[6];
     int    meta = __float_as_int(q[7].x);
     float4 anx = make_float4((nx.x - co.x) * cinv.x, (nx.y - co.x) * cinv.x, (nx.z - co.x) * cinv.x, (nx.w - co.x) * cinv.x);
@@ -420,16 +444,21 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
     const int  gfloor = gmisc >> VPT_FLOOR_SHIFT, gcsgn = gmisc & 7;
     const bool gslow = (gmisc & 8) != 0;
     const STK  gstk = stk.of_lane(owner);
-    while (__builtin_amdgcn_ballot_w64(gcur >= 0) != 0) {
-      if (gcur >= 0) {
-        const float* q = (const float*)(sc.scene_wnodes + 8 * (long long)(gwnb + gcur));
+    // what a call does not change is formed once: the level's first node (a step adds 128 bytes times gcur to it, without a sign to extend)
+    // and the choice of the slab form (with a slow ray that has left the loop, the others take the reference's form where the fast one
+    // would have done: the same bits)
+    const float* const gq0 = (const float*)(sc.scene_wnodes + 8 * (long long)gwnb);
+    const bool any_gslow = __builtin_amdgcn_ballot_w64(gact && gslow) != 0;
+    if (gcur >= 0) {
+      do {   // one test at the bottom, one exit: a group that holds a leaf or nothing stays switched off until the last one does
+        const float* q = gq0 + 32 * (unsigned long long)(unsigned)gcur;
         float lox = q[j], loy = q[4 + j], loz = q[8 + j], hix = q[12 + j], hiy = q[16 + j], hiz = q[20 + j];
         int   ref = __float_as_int(q[24 + j]), meta = __float_as_int(q[28]);
         float ax = (lox - gco.x) * gcinv.x, ay = (loy - gco.y) * gcinv.y, az = (loz - gco.z) * gcinv.z;
         float bx = (hix - gco.x) * gcinv.x, by = (hiy - gco.y) * gcinv.y, bz = (hiz - gco.z) * gcinv.z;
         float t0;
         bool  pass;
-        if (__builtin_amdgcn_ballot_w64(gslow) != 0) pass = slab_pass(mk3(ax, ay, az), mk3(bx, by, bz), tmin, gtmax, t0);   // the reference's form
+        if (any_gslow) pass = slab_pass(mk3(ax, ay, az), mk3(bx, by, bz), tmin, gtmax, t0);   // the reference's form
         else {   // no product can be NaN: min / max of the two products per axis in any association (as slab_pass_signed)
           t0       = hw_max3(hw_max(hw_min(ax, bx), hw_min(ay, by)), hw_min(az, bz), tmin);
           float t1 = hw_min3(hw_min(hw_max(ax, bx), hw_max(ay, by)), hw_max(az, bz), gtmax) * VPT_BOX_K;
@@ -452,22 +481,8 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
         const int next = quad_or(present && k == kfirst ? rj : 0);
         gsp += pv ? __builtin_popcount(pv) - 1 : 0;
         gcur = next;
-        if (!pv) {   // pop_valid on the owner's column; the four lanes of a group read the same entries
-          gcur = VPT_NONE;
-          const bool lds_only = gstk.room_for(gsp, 0);
-          while (gsp > gfloor) {
-            int   pref;
-            float pt0;
-            gsp--;
-            if (lds_only) gstk.load_lds(gsp, pref, pt0);
-            else gstk.load(gsp, pref, pt0);
-            if (pt0 <= gtmax * VPT_BOX_K) {
-              gcur = pref;
-              break;
-            }
-          }
-        }
-      }
+        if (!pv) gcur = pop_passing(gstk, gsp, gfloor, gtmax);   // pop_valid on the owner's column; the four lanes of a group read the same entries
+      } while (gcur >= 0);
     }
     // hand back: the owner of ray k reads lane 4k
     const int src = mine ? rank << 2 : 0;
