@@ -764,6 +764,47 @@ int vpt_resolve_device(const vpt_layout* layout, const void* d_tiles_all_ranks, 
 int vpt_resolve_srgb8_device(const vpt_layout* layout, const void* d_tiles_all_ranks, int samples,
                              void* d_rgba8_rowmajor, void* stream);
 
+/* ---- first-hit AOVs in one pass: denoising guides, depth, ids ------------------------------------------
+ * The three debug shaders draw no random number after the camera ray (yocto_pathtrace.cpp:893-930), so from equal hits / rng they
+ * trace the same rays.  vpt_render_aov_device traces each of them once: per sample and slot -> pixel (px, py) it draws u, v and the
+ * lens sample exactly as vpt_render_device does (the pixel-centre branch of params->samples == 1 draws no jitter), evaluates
+ * eval_camera, runs ONE intersect_bvh(bvh, scene, ray) and gives every plane that is not null this sample's value:
+ *   normal, albedo, texcoord  float4 per slot, sums: what `normal`, `color`, `texcoord` add to `image` (alpha 1); {0,0,0,0} on a miss
+ *   depth                     float4 per slot, sums: {distance, 0, 0, 1} on a hit, {0,0,0,0} on a miss
+ *   ids, uvt                  int32 x2 and float x3 per slot, vpt_intersect's format: {instance, element} and {u, v, distance},
+ *                             {-1, -1} and zeros on a miss.  Written only by the sample that finds hits[slot] == 0 - the state's
+ *                             first sample; later samples leave them alone, so they do not depend on how a render is batched.
+ * A sample's value that is not finite counts as zeros, decided per plane as for `image` (cpp:1087-1089).  Shapes of points or lines
+ * give the values the debug shaders give on them.  hits and rng advance exactly as under a debug shader.  The planes are tile-major in
+ * the layout's slots like `image` (the float planes resolve through vpt_resolve_device, ids / uvt through vpt_resolve_ids_device);
+ * padding slots and other ranks' slots are never touched.
+ * Contract: from equal hits / rng a plane has the bits of `image` after vpt_render_device with the matching debug shader, hits and rng
+ * are equal afterwards, and any batching of nsamples gives the same bits in every plane.  With params->samples == 1, ids / uvt are
+ * those of vpt_intersect on the pixel-centre rays.  The pass reports what intersect_bvh sees: no SDF, no voxel grid.
+ * vpt_render_aov_device: asynchronous on `stream`, one plain launch (no schedule, no pilot, no tile splitting); it allocates nothing
+ * beyond what vpt_render_device would; nsamples == 0 is a no-op; params->shader is ignored.  VPT_ERR_INVALID_ARG when every plane is
+ * null or uvt is given without ids.  The planes must be distinct buffers that do not overlap each other, hits or rng: each is updated
+ * on its own (two planes at one address are refused; a partial overlap is the caller's to avoid).
+ * vpt_resolve_ids_device: the gathered ids / uvt of ALL ranks ([nranks][slots]) -> row-major; d_uvt and d_uvt_rowmajor null together.
+ * vpt_render_aov: the same on host arrays - `planes` holds HOST pointers to row-major planes (in and out: the float planes are sums),
+ * hits / rng are those of a row-major pathtrace_state (in and out); min(nsamples, params->samples - *samples_io) samples, a no-op at
+ * the cap.  Synchronous; buffers owned by the call.  Arguments are checked before a device is looked for, the scene last
+ * (VPT_ERR_INVALID_ARG, the message names the argument). */
+typedef struct vpt_aov_planes {
+  void* normal;     /* float4 per slot (pixel), or NULL */
+  void* albedo;
+  void* texcoord;
+  void* depth;
+  void* ids;        /* int32 x2 */
+  void* uvt;        /* float x3; needs ids */
+} vpt_aov_planes;
+int vpt_render_aov_device(vpt_scene* scene, const vpt_params* params, const vpt_layout* layout, int nsamples,
+                          const vpt_aov_planes* planes, void* d_hits, void* d_rng, void* stream);
+int vpt_resolve_ids_device(const vpt_layout* layout, const void* d_ids, const void* d_uvt, void* d_ids_rowmajor,
+                           void* d_uvt_rowmajor, void* stream);
+int vpt_render_aov(vpt_scene* scene, const vpt_params* params, int nsamples, int width, int height,
+                   const vpt_aov_planes* planes, int32_t* hits, uint64_t* rng, int* samples_io);
+
 /* ---- adaptive sampling: every pixel renders until its noise meets a target ---------------------------
  * A pixel that stops after k samples holds exactly the state k consecutive reference calls leave (image, rng, hits == k):
  * pixels are independent and batching is exact, so the numerical contract holds per pixel.  Rendering goes in rounds; each
@@ -959,7 +1000,8 @@ int vpt_scene_get_device(const vpt_scene* scene);
  *                       `display` = tone map of `image`; samples = 0.  With non-null params it adopts them first, and allocates
  *                       again if the size changes.  With denoise = 1 it also renders the guides: guide_samples passes of `normal`
  *                       and `color` (`implicit_normal` and no albedo for the implicit shaders, as pathtrace_guides chooses) over
- *                       states initialised on the device, resolved with vpt_resolve_device.
+ *                       states initialised on the device, resolved with vpt_resolve_device (the mesh shaders' two guides come from
+ *                       one first-hit pass with those bits: below).
  *  vpt_session_advance  min(nsamples, render.samples - samples) passes on the resident state, get_render into `image`, the filter
  *                       if denoise = 1, the tone map into `display`; a no-op at the cap.  For the implicit shaders it waits for
  *                       the passes and returns VPT_ERR_HIP when the watchdog fired, as vpt_render does; else it is asynchronous on
@@ -1015,6 +1057,31 @@ int  vpt_session_get_state(vpt_session* session, float* image_rgba, int32_t* hit
 int  vpt_session_size(const vpt_session* session, int* width, int* height);
 int  vpt_session_samples(const vpt_session* session);
 int  vpt_session_stats(const vpt_session* session, int* launches, int64_t* bytes_to_device, int64_t* bytes_to_host);
+/* ---- what is under a pixel, and the guides -----------------------------------------------------------------
+ * With denoise = 1 and a mesh shader, a reset renders both guides in ONE first-hit pass (vpt_render_aov_device: normal + albedo over a
+ * state initialised on the device) and resolves each: the bits of the two separate renders, half their traversals.
+ *   get_guides   the row-major guides, float4 per pixel, either pointer nullable, not both; VPT_ERR_INVALID_ARG unless denoise = 1
+ *                (and for `albedo` under an implicit shader, which has none).
+ * The id frame: {instance, element} and {u, v, distance} of every pixel, vpt_intersect's format and bits on the rays through the pixel
+ * centres at full resolution - one sample of vpt_render_aov_device with samples = 1 over hits / rng of its own, initialised on the
+ * device.  It is made by the first pick or get_ids after a reset (3 launches, buffers allocated then; the scene's instance table is
+ * read with it, vpt_scene_get_instances, and counted in that call's bytes_to_host) and kept until the next reset.  Every edit resets,
+ * so it never names what the scene no longer holds.
+ *   pick         the hit under pixel (x, y): one launch that packs {hit, instance, element, u, v, distance} and one copy of those 24
+ *                bytes; shape and material are those of vpt_scene_get_instances()[instance] (-1 on a miss, like instance and
+ *                element).  x / y outside the frame: VPT_ERR_INVALID_ARG.
+ *   get_ids      the whole frame, row-major: ids int32 x2 and uvt float x3 per pixel, either pointer nullable, not both.
+ * pick and get_ids return VPT_ERR_UNSUPPORTED when the session's shader is implicit or implicit_normal: what the user sees there
+ * is not what the mesh BVH holds. */
+typedef struct vpt_pick {
+  int32_t hit;                  /* 0 / 1 */
+  int32_t instance, element;
+  int32_t shape, material;
+  float   u, v, distance;
+} vpt_pick;
+int  vpt_session_get_guides(vpt_session* session, float* normal, float* albedo);
+int  vpt_session_pick(vpt_session* session, int x, int y, vpt_pick* out);
+int  vpt_session_get_ids(vpt_session* session, int32_t* ids, float* uvt);
 /* ---- adaptive sampling in a session ------------------------------------------------------------------------
  * vpt_session_set_adaptive adopts the settings and resets; NULL switches the mode off (and resets).  Checked like
  * vpt_render_adaptive: threshold finite and >= 0, step >= 1, 1 <= min_samples <= render.samples (VPT_ERR_INVALID_ARG; a refused

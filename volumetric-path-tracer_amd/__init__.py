@@ -66,6 +66,18 @@ class VptSessionParams(C.Structure):  # vpt_session_params
                 ("guide_samples", C.c_int32)]
 
 
+AOV_PLANES = ("normal", "albedo", "texcoord", "depth", "ids", "uvt")
+
+
+class VptAovPlanes(C.Structure):  # vpt_aov_planes: any of them None
+    _fields_ = [(name, C.c_void_p) for name in AOV_PLANES]
+
+
+class VptPick(C.Structure):  # vpt_pick
+    _fields_ = [("hit", C.c_int32), ("instance", C.c_int32), ("element", C.c_int32), ("shape", C.c_int32), ("material", C.c_int32),
+                ("u", C.c_float), ("v", C.c_float), ("distance", C.c_float)]
+
+
 class VptFrame(C.Structure):  # vpt_frame: x, y, z, o
     _fields_ = [("x", C.c_float * 3), ("y", C.c_float * 3), ("z", C.c_float * 3), ("o", C.c_float * 3)]
 
@@ -593,6 +605,12 @@ hip.vpt_session_progress.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int64
 hip.vpt_session_get_hits.argtypes = [_p, _p]
 hip.vpt_session_get_noise.argtypes = [_p, _p, _p]
 hip.vpt_session_get_adaptive_stats.argtypes = [_p, _p, _p]
+hip.vpt_render_aov_device.argtypes = [_p, C.POINTER(VptParams), C.POINTER(VptLayout), C.c_int, C.POINTER(VptAovPlanes), _p, _p, _p]
+hip.vpt_resolve_ids_device.argtypes = [C.POINTER(VptLayout), _p, _p, _p, _p, _p]
+hip.vpt_render_aov.argtypes = [_p, C.POINTER(VptParams), C.c_int, C.c_int, C.c_int, C.POINTER(VptAovPlanes), _p, _p, C.POINTER(C.c_int)]
+hip.vpt_session_get_guides.argtypes = [_p, _p, _p]
+hip.vpt_session_pick.argtypes = [_p, C.c_int, C.c_int, C.POINTER(VptPick)]
+hip.vpt_session_get_ids.argtypes = [_p, _p, _p]
 hip.vpt_last_kernel_ms.argtypes = [_p, C.POINTER(C.c_float)]
 hip.vpt_intersect.argtypes = [_p, C.c_int, _p, C.c_int, _p, _p]
 hip.vpt_build_bvh.argtypes = [C.c_int, _p, C.c_int, _p, C.c_int, C.POINTER(C.c_int), _p]
@@ -1535,6 +1553,42 @@ class DeviceScene:
         _check(hip.vpt_render_device(self.handle, C.byref(abi), C.byref(layout), nsamples, d_image, d_hits, d_rng,
                                      stream), "vpt_render_device")
 
+    def render_aov_device(self, params: PathtraceParams, layout: VptLayout, nsamples: int, planes: dict, d_hits: int, d_rng: int,
+                          stream: int = 0) -> None:
+        """vpt_render_aov_device on this rank's tile-major slots: `planes` maps names of AOV_PLANES to raw device pointers"""
+        unknown = set(planes) - set(AOV_PLANES)
+        if unknown:
+            raise VptError(f"unknown AOV plane {sorted(unknown)[0]!r}: expected one of {AOV_PLANES}")
+        abi, pl = params.to_abi(), VptAovPlanes(**{k: v for k, v in planes.items() if v})
+        _check(hip.vpt_render_aov_device(self.handle, C.byref(abi), C.byref(layout), nsamples, C.byref(pl), d_hits, d_rng, stream),
+               "vpt_render_aov_device")
+
+    def render_aovs(self, state: PathtraceState, params: PathtraceParams, count: int = 1, planes=AOV_PLANES, into: Optional[dict] = None) -> dict:
+        """the first-hit pass (vpt_render_aov, include/vpt.h) over the hits / rngs of `state` (its image is left alone): `count` more
+        samples, at most params.samples in all, traced once for every plane named in `planes`.  Returns {name: array}: the sums
+        normal / albedo / texcoord / depth as (h, w, 4) float32 - divide by state.samples, as get_render does - and ids (h, w, 2) int32,
+        uvt (h, w, 3) float32 of the state's first sample.  `into`: the dict an earlier call returned, to go on from (batching is exact)."""
+        shapes = {"ids": ((2,), np.int32), "uvt": ((3,), np.float32)}
+        out = {}
+        for name in planes:
+            if name not in AOV_PLANES:
+                raise VptError(f"unknown AOV plane {name!r}: expected one of {AOV_PLANES}")
+            tail, dtype = shapes.get(name, ((4,), np.float32))
+            shape = (state.height, state.width) + tail
+            a = into.get(name) if into else None
+            if a is None:
+                a = np.zeros(shape, dtype)
+            elif a.shape != shape or a.dtype != dtype or not a.flags["C_CONTIGUOUS"]:
+                raise VptError(f"plane {name!r}: expected a contiguous {np.dtype(dtype).name} array of shape {shape}")
+            out[name] = a
+        for a in (state.hits, state.rngs):
+            assert a.flags["C_CONTIGUOUS"]
+        abi, pl, samples = params.to_abi(), VptAovPlanes(**{k: a.ctypes.data for k, a in out.items()}), C.c_int(state.samples)
+        _check(hip.vpt_render_aov(self.handle, C.byref(abi), count, state.width, state.height, C.byref(pl), state.hits.ctypes.data,
+                                  state.rngs.ctypes.data, C.byref(samples)), "vpt_render_aov")
+        state.samples = samples.value
+        return out
+
     def update(self, edit: SceneEdit) -> None:
         """vpt_scene_update (include/vpt.h): the edit applied to the resident scene, BVHs refitted on the device.  Afterwards the
         handle renders the bits of a DeviceScene made from the host scene after the same edit and update_bvh()."""
@@ -1934,6 +1988,11 @@ def resolve_srgb8_device(layout: VptLayout, d_tiles_all: int, samples: int, d_rg
     _check(hip.vpt_resolve_srgb8_device(C.byref(layout), d_tiles_all, samples, d_rgba8, stream), "vpt_resolve_srgb8_device")
 
 
+def resolve_ids_device(layout: VptLayout, d_ids_all: int, d_uvt_all: Optional[int], d_ids_rows: int, d_uvt_rows: Optional[int], stream: int = 0):
+    """vpt_resolve_ids_device: the ids / uvt planes of all ranks, tile-major -> row-major (the uvt pair None together)"""
+    _check(hip.vpt_resolve_ids_device(C.byref(layout), d_ids_all, d_uvt_all, d_ids_rows, d_uvt_rows, stream), "vpt_resolve_ids_device")
+
+
 def get_render(state: PathtraceState) -> np.ndarray:
     """get_render, yocto_pathtrace.cpp:1105-1116: image * (1/samples) in float32"""
     return state.image * np.float32(np.float32(1.0) / np.float32(state.samples))
@@ -1998,6 +2057,13 @@ def pathtrace_guides(scene: HostScene, dev, params: PathtraceParams, samples: in
     (h, w, 4) float32 images - `samples` passes of the `normal` and the `color` shader over a fresh make_state; for the implicit
     shaders: `implicit_normal`, and albedo None"""
     implicit = params.shader in ("implicit", "implicit_normal")
+    if not implicit and isinstance(dev, DeviceScene):  # both from one first-hit pass: the same rays traced once, the same bits
+        p = PathtraceParams(params.camera, params.resolution, "normal", samples, params.bounces, params.noparallel, params.noimplicit_mis,
+                            params.spheretrace_maxiter)
+        st = scene.make_state(p)
+        sums = dev.render_aovs(st, p, samples, ("normal", "albedo"))
+        scale = np.float32(np.float32(1.0) / np.float32(st.samples))
+        return sums["normal"] * scale, sums["albedo"] * scale
 
     def render(shader):
         p = PathtraceParams(params.camera, params.resolution, shader, samples, params.bounces, params.noparallel, params.noimplicit_mis,
@@ -2255,6 +2321,32 @@ class RenderSession:
                "vpt_session_get_state")
         st.samples = n.value
         return st
+
+    def guides(self):
+        """denoise = True: the guides the filter reads, (normal, albedo) as resolved (h, w, 4) float32 images; albedo None for the
+        implicit shaders"""
+        w, h = self.size
+        has_albedo = self.params.shader not in ("implicit", "implicit_normal")
+        normal, albedo = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32) if has_albedo else None
+        _check(hip.vpt_session_get_guides(self.handle, normal.ctypes.data, albedo.ctypes.data if has_albedo else None), "vpt_session_get_guides")
+        return normal, albedo
+
+    def pick(self, x: int, y: int) -> Optional[dict]:
+        """what is under pixel (x, y) of the frame on display (vpt_session_pick): None on a miss, else a dict of instance, element,
+        shape, material, u, v, distance.  24 bytes cross PCIe; the first pick or ids() after a reset makes the id frame."""
+        out = VptPick()
+        _check(hip.vpt_session_pick(self.handle, x, y, C.byref(out)), "vpt_session_pick")
+        if not out.hit:
+            return None
+        return {name: getattr(out, name) for name in ("instance", "element", "shape", "material", "u", "v", "distance")}
+
+    def ids(self):
+        """the id frame (vpt_session_get_ids): (ids, uvt) = (h, w, 2) int32 {instance, element} (-1 on a miss) and (h, w, 3) float32
+        {u, v, distance} of the rays through the pixel centres, in vpt_intersect's format"""
+        w, h = self.size
+        ids, uvt = np.zeros((h, w, 2), np.int32), np.zeros((h, w, 3), np.float32)
+        _check(hip.vpt_session_get_ids(self.handle, ids.ctypes.data, uvt.ctypes.data), "vpt_session_get_ids")
+        return ids, uvt
 
     def stats(self):
         """(kernel launches, bytes to the device, bytes to the host) of the last call on the session"""

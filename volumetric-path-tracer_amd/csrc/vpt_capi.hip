@@ -720,6 +720,110 @@ int vpt_resolve_srgb8_device(const vpt_layout* layout, const void* d_tiles_all_r
 
 }  // extern "C"
 
+// the conditions on the planes of a first-hit pass (include/vpt.h), device or host pointers alike
+static int check_aov_planes(const vpt_aov_planes* p) {
+  REQUIRE(p, "null planes");
+  REQUIRE(p->normal || p->albedo || p->texcoord || p->depth || p->ids || p->uvt, "planes: every plane is null, nothing to render");
+  REQUIRE(p->ids || !p->uvt, "planes: uvt is given without ids");
+  const void* const   given[6] = {p->normal, p->albedo, p->texcoord, p->depth, p->ids, p->uvt};
+  static const char* const name[6] = {"normal", "albedo", "texcoord", "depth", "ids", "uvt"};
+  for (int a = 0; a < 6; a++)   // the kernel updates each plane on its own: two of them in one buffer would lose updates
+    for (int b = a + 1; b < 6; b++) REQUIRE(!given[a] || given[a] != given[b], "planes: %s and %s share a buffer", name[a], name[b]);
+  return VPT_OK;
+}
+static aov_planes device_planes(const vpt_aov_planes& p) {
+  return {(float4*)p.normal, (float4*)p.albedo, (float4*)p.texcoord, (float4*)p.depth, (int2*)p.ids, (float*)p.uvt};
+}
+
+extern "C" {
+
+int vpt_render_aov_device(vpt_scene* s, const vpt_params* params, const vpt_layout* layout, int nsamples, const vpt_aov_planes* planes,
+    void* d_hits, void* d_rng, void* stream) {
+  if (int rc = check_aov_planes(planes)) return rc;
+  REQUIRE(s && params && layout && d_hits && d_rng, "null argument");
+  REQUIRE(params->camera >= 0 && params->camera < s->d.num_cameras, "camera %d out of range", params->camera);
+  REQUIRE(nsamples >= 0, "negative sample count");
+  if (nsamples == 0) return VPT_OK;
+  DParams pr;
+  if (int rc = make_dparams(params, layout, nsamples, pr)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const dim3 grid((pr.nslots + VPT_BLOCK - 1) / VPT_BLOCK);
+  stack_cfg  stack;
+  if (int rc = stack_config(s, (long long)grid.x * VPT_BLOCK, stack)) return rc;
+  const size_t lds = (size_t)s->stack_lds4 * 2 * VPT_BLOCK * sizeof(int);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(VPT_BLOCK), lds, (hipStream_t)stream, s->d, pr, device_planes(*planes), (int*)d_hits, (ulonglong2*)d_rng, stack);
+  };
+  if (s->curves) {
+    if (stack.spill) launch(vpt_aov_kernel<true, true>);
+    else launch(vpt_aov_kernel<false, true>);
+  } else if (stack.spill) launch(vpt_aov_kernel<true, false>);
+  else launch(vpt_aov_kernel<false, false>);
+  HIP_TRY(hipGetLastError());
+  return VPT_OK;
+}
+
+int vpt_resolve_ids_device(const vpt_layout* layout, const void* d_ids, const void* d_uvt, void* d_ids_rowmajor, void* d_uvt_rowmajor, void* stream) {
+  REQUIRE(layout && d_ids && d_ids_rowmajor, "null argument");
+  REQUIRE((d_uvt != nullptr) == (d_uvt_rowmajor != nullptr), "d_uvt and d_uvt_rowmajor must be null together");
+  DParams pr;
+  if (int rc = vpt_layout_dparams(layout, pr)) return rc;
+  const long long total = (long long)pr.nslots * pr.nranks;
+  REQUIRE(total < (1LL << 31), "image too large");
+  hipLaunchKernelGGL(vpt_resolve_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pr, (const int2*)d_ids,
+      (const float*)d_uvt, (int2*)d_ids_rowmajor, (float*)d_uvt_rowmajor);
+  HIP_TRY(hipGetLastError());
+  return VPT_OK;
+}
+
+int vpt_render_aov(vpt_scene* s, const vpt_params* params, int nsamples, int width, int height, const vpt_aov_planes* planes, int32_t* hits,
+    uint64_t* rng, int* samples_io) {
+  if (int rc = check_aov_planes(planes)) return rc;
+  REQUIRE(params, "null params");
+  REQUIRE(hits, "null hits");
+  REQUIRE(rng, "null rng");
+  REQUIRE(samples_io, "null samples_io");
+  REQUIRE(width >= 1 && height >= 1 && width < 32768 && height < 32768, "bad image size: width %d, height %d", width, height);
+  REQUIRE(nsamples >= 0, "nsamples %d is negative", nsamples);
+  REQUIRE(s, "null scene");
+  REQUIRE(params->camera >= 0 && params->camera < s->d.num_cameras, "camera %d out of range", params->camera);
+  const int todo = std::min(nsamples, params->samples - *samples_io);   // no-op once reached, as vpt_render
+  if (todo <= 0) return VPT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  const vpt_layout lay = {width, height, 8, 8, 0, 1};
+  DParams          pr;
+  if (int rc = vpt_layout_dparams(&lay, pr)) return rc;
+  const size_t slots = (size_t)pr.nslots, n = (size_t)width * height;
+  // per plane: bytes per entry, the host array, tile-major and row-major device copies
+  struct part { size_t bytes; void* host; device_buffer tiles, rows; };
+  part parts[8] = {{16, planes->normal}, {16, planes->albedo}, {16, planes->texcoord}, {16, planes->depth}, {8, planes->ids}, {12, planes->uvt},
+      {4, hits}, {16, rng}};
+  for (part& p : parts) {
+    if (!p.host) continue;
+    if (int rc = p.tiles.allocate(slots * p.bytes)) return rc;
+    if (int rc = p.rows.allocate(n * p.bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(p.rows.get(), p.host, n * p.bytes, hipMemcpyHostToDevice, nullptr));
+  }
+  const vpt_aov_planes tiles = {parts[0].tiles.get(), parts[1].tiles.get(), parts[2].tiles.get(), parts[3].tiles.get(), parts[4].tiles.get(), parts[5].tiles.get()};
+  const vpt_aov_planes rows  = {parts[0].rows.get(), parts[1].rows.get(), parts[2].rows.get(), parts[3].rows.get(), parts[4].rows.get(), parts[5].rows.get()};
+  auto permute = [&](int to_tiles) {
+    hipLaunchKernelGGL(vpt_aov_permute_kernel, dim3((pr.nslots + 255) / 256), dim3(256), 0, nullptr, pr, to_tiles, device_planes(tiles),
+        parts[6].tiles.get<int>(), parts[7].tiles.get<ulonglong2>(), device_planes(rows), parts[6].rows.get<int>(), parts[7].rows.get<ulonglong2>());
+  };
+  permute(1);
+  HIP_TRY(hipGetLastError());
+  if (int rc = vpt_render_aov_device(s, params, &lay, todo, &tiles, parts[6].tiles.get(), parts[7].tiles.get(), nullptr)) return rc;
+  permute(0);
+  HIP_TRY(hipGetLastError());
+  for (part& p : parts)
+    if (p.host) HIP_TRY(hipMemcpyAsync(p.host, p.rows.get(), n * p.bytes, hipMemcpyDeviceToHost, nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  *samples_io += todo;
+  return VPT_OK;
+}
+
+}  // extern "C"
+
 // vpt_render / vpt_render_adaptive: the host state through the scene handle's staging (one rank, 8x8 tiles; allocated once per frame
 // size), render(layout, tiles) on it, and back.  The row-major staging still holds the frame that was uploaded, and the
 // single-rank layout owns every pixel, so the download starts from it.

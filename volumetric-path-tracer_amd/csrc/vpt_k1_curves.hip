@@ -1,5 +1,6 @@
-// K1's instances for scenes with points or lines, all five mesh families (the list: vpt_k1_instances.hip.h)
-#include "vpt_mesh_kernel.hip.h"
+// K1's instances for scenes with points or lines, all five mesh families (the list: vpt_k1_instances.hip.h), + vpt_intersect and the
+// first-hit pass on such scenes
+#include "vpt_aov_kernel.hip.h"
 VPT_K1_CURVES_INSTANCES(VPT_K1_DEFINE, K_VOLPATH)
 VPT_K1_CURVES_INSTANCES(VPT_K1_DEFINE, K_PATH)
 VPT_K1_CURVES_INSTANCES(VPT_K1_DEFINE, K_NAIVE)
@@ -21,3 +22,7 @@ __global__ void vpt_intersect_curves_kernel(DScene sc, int n, const float* rays,
 }
 template __global__ void vpt_intersect_curves_kernel<true>(DScene, int, const float*, int, int*, float*, stack_cfg);
 template __global__ void vpt_intersect_curves_kernel<false>(DScene, int, const float*, int, int*, float*, stack_cfg);
+
+// vpt_render_aov_device for scenes with points or lines: the first-hit pass over the same traversal
+VPT_AOV_DEFINE(true, true)
+VPT_AOV_DEFINE(false, true)

@@ -5,6 +5,7 @@
 //   vpt_k1_curves.hip                     K1 for scenes with points or lines, + vpt_intersect on them   vpt_k1_instances.hip.h)
 //   vpt_k1_simple.hip                     K1 for naive, eyelight and the debug shaders
 //   vpt_k2.hip                            K2 (vpt_implicit_kernel.hip.h)
+//   vpt_aov.hip                           the first-hit pass (vpt_aov_kernel.hip.h) and the layout kernels of its id planes
 //   vpt_kernels.hip                       vpt_intersect, the KAT kernel, the self-tests, light setup, launch schedule, state layout
 // The launch bounds live here only: a definition inherits them from these declarations.
 #pragma once
@@ -77,6 +78,22 @@ __global__ void __launch_bounds__(VPT_BLOCK, VPT_WAVES_PER_SIMD) vpt_kat_kernel(
     const float* __restrict__ in, const int* __restrict__ aux, float* __restrict__ out, stack_cfg stack, int stack_cap);
 __global__ void vpt_reciprocal_selftest_kernel(unsigned long long* out);
 __global__ void vpt_light_cdf_selftest_kernel(DScene sc, int light_id, int n, unsigned long long* out);
+
+// ---- the first-hit pass (vpt_aov_kernel.hip.h; instances: vpt_aov.hip, and vpt_k1_curves.hip for scenes with points or lines) ----
+// the planes of include/vpt.h's vpt_aov_planes as the kernels see them: tile-major, one entry per state slot, any of them null
+struct aov_planes {
+  float4 *normal, *albedo, *texcoord, *depth;   // sums over the samples
+  int2*   ids;                                  // {instance, element} of the state's first sample
+  float*  uvt;                                  // 3 per slot: {u, v, distance} of the same
+};
+template <bool SPILL, bool CURVES>
+__global__ void __launch_bounds__(VPT_BLOCK, VPT_WAVES_PER_SIMD) vpt_aov_kernel(DScene sc, DParams pr, aov_planes pl, int* __restrict__ hits,
+    ulonglong2* __restrict__ rngs, stack_cfg stack);
+// ids / uvt of all ranks ([nranks][nslots]) -> row-major (vpt_resolve_ids_device); uvt nullable
+__global__ void vpt_resolve_ids_kernel(DParams pr, const int2* ids_all, const float* uvt_all, int2* rows_ids, float* rows_uvt);
+// row-major host-order planes, hits and rng <-> this rank's tile-major slots (vpt_render_aov); null planes are skipped
+__global__ void vpt_aov_permute_kernel(DParams pr, int to_tiles, aov_planes tiles, int* tiles_hits, ulonglong2* tiles_rng, aov_planes rows,
+    int* rows_hits, ulonglong2* rows_rng);
 
 // ---- scene setup, launch schedule, state layout and output resolve (vpt_kernels.hip) -------------------------------------------
 __global__ void vpt_light_setup_kernel(DScene sc, float4* out);

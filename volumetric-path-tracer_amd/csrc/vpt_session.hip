@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstring>
 #include <utility>
+#include <vector>
 
 #include "vpt_adaptive.h"   // vpt_layout_dparams
 #include "vpt_device_buffer.h"
@@ -43,7 +44,16 @@ __global__ void __launch_bounds__(k_block) vpt_state_init_kernel(DParams pr, jum
   if (!slot_to_pixel(pr, slot, px, py)) return;   // padding, or another rank's
   const vpt_lcg_jump k = tab.e[slot & 63];
   const vpt_pcg32    r = vpt_state_pixel_rng(k.mul * s0 + k.add);
-  image[slot] = make_float4(0, 0, 0, 0), hits[slot] = 0, rngs[slot] = make_ulonglong2(r.state, r.inc);
+  if (image) image[slot] = make_float4(0, 0, 0, 0);   // (null: the state of a first-hit pass, which has planes instead)
+  hits[slot] = 0, rngs[slot] = make_ulonglong2(r.state, r.inc);
+}
+
+// the 24 bytes of a pick: {hit, instance, element} and {u, v, distance} of one pixel of the row-major id frame
+__global__ void vpt_pick_kernel(const int2* __restrict__ ids, const float* __restrict__ uvt, long long pixel, int* __restrict__ out) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int2 id = ids[pixel];
+  out[0] = id.x >= 0 ? 1 : 0, out[1] = id.x, out[2] = id.y;
+  for (int c = 0; c < 3; c++) out[3 + c] = __float_as_int(uvt[3 * pixel + c]);
 }
 
 // ---- tonemap(vec4f, exposure, filmic, srgb), yocto_color.h:306-316 --------------------------------------------------------------
@@ -101,12 +111,8 @@ int check_tonemap(const vpt_display_params* d, int width, int height, const void
   return VPT_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vpt_state_init_device(const vpt_layout* layout, void* d_image, void* d_hits, void* d_rng, void* stream) {
-  REQUIRE(layout && d_image && d_hits && d_rng, "null argument");
+// vpt_state_init_device; d_image may be null here (hits and rng alone: the state a first-hit pass runs over)
+int state_init(const vpt_layout* layout, void* d_image, void* d_hits, void* d_rng, void* stream) {
   DParams pr;
   if (int rc = vpt_layout_dparams(layout, pr)) return rc;
   jump_table      tab;
@@ -116,6 +122,15 @@ int vpt_state_init_device(const vpt_layout* layout, void* d_image, void* d_hits,
       (unsigned long long)master.state, (unsigned long long)master.inc, (float4*)d_image, (int*)d_hits, (ulonglong2*)d_rng);
   HIP_TRY(hipGetLastError());
   return VPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vpt_state_init_device(const vpt_layout* layout, void* d_image, void* d_hits, void* d_rng, void* stream) {
+  REQUIRE(layout && d_image && d_hits && d_rng, "null argument");
+  return state_init(layout, d_image, d_hits, d_rng, stream);
 }
 
 int vpt_tonemap_device(const vpt_display_params* display, int width, int height, const void* d_linear, void* d_display_f, void* d_rgba8,
@@ -181,6 +196,7 @@ struct vpt_session {
   long long          r_pixels = 0;
   // denoise = 1
   device_buffer normal, albedo, variance, sum_a, sum_n, filtered, scratch;
+  device_buffer g_albedo;   // tile-major sums of the albedo guide (the normal guide's are rendered in s_image)
   bool          denoise_allocated = false, has_albedo = false, filtered_valid = false;
   int           a = 0;   // samples behind sum_a (0: none)
   // adaptive mode (vpt_session_set_adaptive): the run lives from the first advance after a reset to the next reset
@@ -189,6 +205,12 @@ struct vpt_session {
   vpt_adaptive_run* run      = nullptr;
   device_buffer     a_se2, a_var, a_hits, a_mean, a_m2;   // row-major planes of the run's statistics
   long long         a_pixels = 0;
+  // the id frame behind pick and get_ids: made on first use after a reset, kept until the next one (every edit resets)
+  device_buffer            i_hits, i_rng, i_ids, i_uvt;   // the state and the planes of its one-sample pass, tile-major
+  device_buffer            ids, uvt, pick;                // row-major; the 24 bytes of a pick
+  long long                i_pixels = 0, i_slots = 0;     // what they were allocated for (0: nothing)
+  bool                     ids_valid = false;
+  std::vector<vpt_instance> instances;                    // the scene's instance table as of the id frame: a pick's shape and material
   // what the last call cost
   int     launches = 0;
   int64_t up = 0, down = 0;
@@ -240,7 +262,7 @@ int check_session_adaptive(const vpt_adaptive* a, int samples) {
 }
 
 int allocate(vpt_session* s, int width, int height, int pw, int ph, bool denoise) {
-  s->width = s->height = 0, s->denoise_allocated = false, s->r_pixels = 0;
+  s->width = s->height = 0, s->denoise_allocated = false, s->r_pixels = 0, s->i_pixels = s->i_slots = 0;   // a new frame: the lazily made buffers go with the old one
   const vpt_layout lay = {width, height, 8, 8, 0, 1}, play = {pw, ph, 8, 8, 0, 1};
   const long long  slots = vpt_layout_slots(&lay), pslots = vpt_layout_slots(&play);
   if (slots < 0 || pslots < 0) return VPT_ERR_INVALID_ARG;
@@ -253,11 +275,11 @@ int allocate(vpt_session* s, int width, int height, int pw, int ph, bool denoise
     if (int rc = b->allocate(bytes)) return rc;
   if (denoise) {
     const sized filter[] = {{&s->normal, n * 16}, {&s->albedo, n * 16}, {&s->variance, n * 4}, {&s->sum_a, n * 16}, {&s->sum_n, n * 16},
-        {&s->filtered, n * 16}, {&s->scratch, (size_t)vpt_denoise_scratch_bytes(width, height)}};
+        {&s->filtered, n * 16}, {&s->scratch, (size_t)vpt_denoise_scratch_bytes(width, height)}, {&s->g_albedo, (size_t)slots * 16}};
     for (auto& [b, bytes] : filter)
       if (int rc = b->allocate(bytes)) return rc;
   } else {
-    for (device_buffer* b : {&s->normal, &s->albedo, &s->variance, &s->sum_a, &s->sum_n, &s->filtered, &s->scratch}) *b = device_buffer();
+    for (device_buffer* b : {&s->normal, &s->albedo, &s->variance, &s->sum_a, &s->sum_n, &s->filtered, &s->scratch, &s->g_albedo}) *b = device_buffer();
   }
   s->lay = lay, s->play = play, s->width = width, s->height = height, s->pw = pw, s->ph = ph, s->denoise_allocated = denoise;
   return VPT_OK;
@@ -280,6 +302,55 @@ int render_guide(vpt_session* s, int shader, void* d_out) {
   return vpt_resolve_device(&s->lay, s->s_image.get(), p.samples, d_out, s->st);
 }
 
+// both guides of the mesh shaders from one first-hit pass (include/vpt.h: vpt_render_aov_device): `normal` and `color` trace the same
+// rays from the same streams, so one traversal per sample serves both; the bits are those of two calls of render_guide
+int render_mesh_guides(vpt_session* s) {
+  vpt_params p = s->p.render;
+  p.samples    = s->p.guide_samples;
+  if (int rc = vpt_state_init_device(&s->lay, s->s_image.get(), s->s_hits.get(), s->s_rng.get(), s->st)) return rc;   // zeroes s_image
+  HIP_TRY(hipMemsetAsync(s->g_albedo.get(), 0, (size_t)vpt_layout_slots(&s->lay) * 16, s->st));
+  const vpt_aov_planes planes = {s->s_image.get(), s->g_albedo.get(), nullptr, nullptr, nullptr, nullptr};
+  if (int rc = vpt_render_aov_device(s->scene, &p, &s->lay, p.samples, &planes, s->s_hits.get(), s->s_rng.get(), s->st)) return rc;
+  if (int rc = vpt_resolve_device(&s->lay, s->s_image.get(), p.samples, s->normal.get(), s->st)) return rc;
+  s->launches += 4;
+  return vpt_resolve_device(&s->lay, s->g_albedo.get(), p.samples, s->albedo.get(), s->st);
+}
+
+// the id frame (include/vpt.h: vpt_session_pick): one sample in the pixel-centre branch at full resolution over a state of its own
+int ensure_ids(vpt_session* s) {
+  REQUIRE(s->width > 0, "the session holds no frame (a reset failed)");
+  if (implicit_shader(s->p.render.shader))
+    return vpt_set_error(VPT_ERR_UNSUPPORTED, "the session renders an implicit shader: its picture is not what the mesh BVH holds");
+  if (s->ids_valid) return VPT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t n = (size_t)s->width * s->height, slots = (size_t)vpt_layout_slots(&s->lay);
+  // the state and the planes hold one entry per tile-major SLOT: frames of equal pixel counts can differ in it (105 x 40 and 100 x 42)
+  if (s->i_pixels != (long long)n || s->i_slots != (long long)slots) {
+    s->i_pixels = s->i_slots = 0;
+    using sized = std::pair<device_buffer*, size_t>;
+    const sized frame[] = {{&s->i_hits, slots * 4}, {&s->i_rng, slots * 16}, {&s->i_ids, slots * 8}, {&s->i_uvt, slots * 12}, {&s->ids, n * 8},
+        {&s->uvt, n * 12}, {&s->pick, 24}};
+    for (auto& [b, bytes] : frame)
+      if (int rc = b->allocate(bytes)) return rc;
+    s->i_pixels = (long long)n, s->i_slots = (long long)slots;
+  }
+  vpt_params p = s->p.render;
+  p.samples    = 1;
+  if (int rc = state_init(&s->lay, nullptr, s->i_hits.get(), s->i_rng.get(), s->st)) return rc;
+  const vpt_aov_planes planes = {nullptr, nullptr, nullptr, nullptr, s->i_ids.get(), s->i_uvt.get()};
+  if (int rc = vpt_render_aov_device(s->scene, &p, &s->lay, 1, &planes, s->i_hits.get(), s->i_rng.get(), s->st)) return rc;
+  if (int rc = vpt_resolve_ids_device(&s->lay, s->i_ids.get(), s->i_uvt.get(), s->ids.get(), s->uvt.get(), s->st)) return rc;
+  s->launches += 3;
+  // a pick's shape and material are those of the instance table as it stands now: read once per id frame
+  int count = 0;
+  if (int rc = vpt_scene_get_instances(s->scene, nullptr, 0, &count)) return rc;
+  s->instances.resize((size_t)count);
+  if (int rc = vpt_scene_get_instances(s->scene, s->instances.data(), count, nullptr)) return rc;
+  s->down += (int64_t)count * (int64_t)sizeof(vpt_instance);
+  s->ids_valid = true;
+  return VPT_OK;
+}
+
 int reset(vpt_session* s, const vpt_session_params& np) {
   vpt_camera cam;
   if (int rc = vpt_scene_get_camera(s->scene, np.render.camera, &cam)) return rc;
@@ -293,12 +364,12 @@ int reset(vpt_session* s, const vpt_session_params& np) {
   drop_run(s);                            // an adaptive run ends here; the first advance makes the next
   if (width != s->width || height != s->height || pw != s->pw || ph != s->ph || (np.denoise != 0) != s->denoise_allocated)
     if (int rc = allocate(s, width, height, pw, ph, np.denoise != 0)) return rc;
-  s->p = np, s->samples = 0, s->a = 0, s->filtered_valid = false, s->has_albedo = false;
+  s->p = np, s->samples = 0, s->a = 0, s->filtered_valid = false, s->has_albedo = false, s->ids_valid = false;
   if (np.denoise) {
-    const bool implicit = implicit_shader(np.render.shader);
-    if (int rc = render_guide(s, implicit ? VPT_SHADER_IMPLICIT_NORMAL : VPT_SHADER_NORMAL, s->normal.get())) return rc;
-    if (!implicit) {
-      if (int rc = render_guide(s, VPT_SHADER_COLOR, s->albedo.get())) return rc;
+    if (implicit_shader(np.render.shader)) {
+      if (int rc = render_guide(s, VPT_SHADER_IMPLICIT_NORMAL, s->normal.get())) return rc;
+    } else {
+      if (int rc = render_mesh_guides(s)) return rc;
       s->has_albedo = true;
     }
   }
@@ -541,6 +612,59 @@ int vpt_session_get_state(vpt_session* s, float* image_rgba, int32_t* hits, uint
   if (int rc = fetch(s, rng, s->r_rng, n * 16)) return rc;
   HIP_TRY(hipStreamSynchronize(s->st));
   *samples = s->samples;
+  return VPT_OK;
+}
+
+int vpt_session_get_guides(vpt_session* s, float* normal, float* albedo) {
+  REQUIRE(s, "null session");
+  REQUIRE(normal || albedo, "null normal and albedo: nothing to fetch");
+  REQUIRE(s->width > 0, "the session holds no frame (a reset failed)");
+  REQUIRE(s->p.denoise, "no guides: the session needs denoise = 1");
+  REQUIRE(!albedo || s->has_albedo, "no albedo guide: the implicit shaders have none");
+  HIP_TRY(hipSetDevice(s->device));
+  begin_call(s);
+  const size_t n = (size_t)s->width * s->height;
+  if (normal)
+    if (int rc = fetch(s, normal, s->normal, n * 16)) return rc;
+  if (albedo)
+    if (int rc = fetch(s, albedo, s->albedo, n * 16)) return rc;
+  HIP_TRY(hipStreamSynchronize(s->st));
+  return VPT_OK;
+}
+
+int vpt_session_get_ids(vpt_session* s, int32_t* ids, float* uvt) {
+  REQUIRE(s, "null session");
+  REQUIRE(ids || uvt, "null ids and uvt: nothing to fetch");
+  HIP_TRY(hipSetDevice(s->device));
+  begin_call(s);
+  if (int rc = ensure_ids(s)) return rc;
+  const size_t n = (size_t)s->width * s->height;
+  if (ids)
+    if (int rc = fetch(s, ids, s->ids, n * 8)) return rc;
+  if (uvt)
+    if (int rc = fetch(s, uvt, s->uvt, n * 12)) return rc;
+  HIP_TRY(hipStreamSynchronize(s->st));
+  return VPT_OK;
+}
+
+int vpt_session_pick(vpt_session* s, int x, int y, vpt_pick* out) {
+  REQUIRE(s && out, "null argument");
+  REQUIRE(s->width > 0, "the session holds no frame (a reset failed)");
+  REQUIRE(x >= 0 && x < s->width && y >= 0 && y < s->height, "pixel (%d, %d) outside the %d x %d frame", x, y, s->width, s->height);
+  HIP_TRY(hipSetDevice(s->device));
+  begin_call(s);
+  if (int rc = ensure_ids(s)) return rc;
+  hipLaunchKernelGGL(vpt_pick_kernel, dim3(1), dim3(64), 0, s->st, s->ids.get<const int2>(), s->uvt.get<const float>(), (long long)y * s->width + x,
+      s->pick.get<int>());
+  HIP_TRY(hipGetLastError());
+  s->launches++;
+  struct { int32_t hit, instance, element; float u, v, distance; } rec;
+  static_assert(sizeof(rec) == 24, "the 24 bytes of a pick");
+  HIP_TRY(hipMemcpyAsync(&rec, s->pick.get(), sizeof(rec), hipMemcpyDeviceToHost, s->st));
+  s->down += (int64_t)sizeof(rec);
+  HIP_TRY(hipStreamSynchronize(s->st));
+  *out = {rec.hit, rec.instance, rec.element, -1, -1, rec.u, rec.v, rec.distance};
+  if (rec.hit && (size_t)rec.instance < s->instances.size()) out->shape = s->instances[(size_t)rec.instance].shape, out->material = s->instances[(size_t)rec.instance].material;
   return VPT_OK;
 }
 

@@ -143,9 +143,13 @@ denoise_guides pathtrace_guides(const scene_data& scene, const bvh_scene& bvh, c
     pathtrace_samples(state, scene, bvh, lights, p, samples);
     return get_render(state);
   };
-  auto guides   = denoise_guides{};
-  guides.normal = render(implicit ? pathtrace_shader_type::implicit_normal : pathtrace_shader_type::normal);
-  if (!implicit) guides.albedo = render(pathtrace_shader_type::color);
+  auto guides = denoise_guides{};
+  if (implicit) {
+    guides.normal = render(pathtrace_shader_type::implicit_normal);
+  } else {   // both guides trace the same rays: one first-hit pass
+    auto aovs     = pathtrace_aovs(scene, bvh, lights, params, samples, aov_normal | aov_albedo);
+    guides.normal = std::move(aovs.normal), guides.albedo = std::move(aovs.albedo);
+  }
   return guides;
 }
 

@@ -291,8 +291,23 @@ void denoise_render_device(color_image& denoised, const color_image& render, con
 // The variance of each pixel's mean luminance from two points of one sample chain: the radiance sums (pathtrace_state::image) after
 // the first a samples and after all n, 0 < a < n (rule: include/vpt.h).  device < 0: host loops; else GPU `device`: same bits.
 vector<float> half_variance(int width, int height, const vector<vec4f>& sum_a, int a, const vector<vec4f>& sum_n, int n, int device = -1);
-// The two guide renders of `params`' camera and resolution: a fresh make_state, `samples` passes of the `normal` and the `color` shader
-// through pathtrace_samples, get_render.  For the implicit shaders: `implicit_normal`, and no albedo (left empty).
+// Extension: the first-hit AOVs of `params`' camera and resolution in one pass (include/vpt.h: vpt_render_aov): a fresh make_state,
+// `samples` samples of one scene copy on the first device of pathtrace_set_devices, every ray traced once.  normal / albedo / texcoord
+// have the bits of get_render after `samples` passes of the `normal` / `color` / `texcoord` shader; depth is {mean distance over the
+// samples, 0, 0, coverage}; ids / uvt are {instance, element} and {u, v, distance} of each pixel's first sample (-1, -1 and zeros on a
+// miss).  params.shader is ignored; SDFs and voxel grids are not seen.  Throws std::runtime_error with vpt_last_error() on failure.
+// `planes`: which of them to render (aov_ids brings uvt along); the others are left empty.
+enum aov_plane : unsigned { aov_normal = 1, aov_albedo = 2, aov_texcoord = 4, aov_depth = 8, aov_ids = 16, aov_all = 31 };
+struct pathtrace_aov_images {
+  color_image   normal = {}, albedo = {}, texcoord = {}, depth = {};
+  vector<vec2i> ids = {};
+  vector<vec3f> uvt = {};
+};
+pathtrace_aov_images pathtrace_aovs(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights, const pathtrace_params& params,
+    int samples = 16, unsigned planes = aov_all);
+// The two guide renders of `params`' camera and resolution: a fresh make_state, `samples` passes of the `normal` and the `color` shader,
+// get_render - for the mesh shaders both out of one pathtrace_aovs pass (the same bits).  For the implicit shaders: `implicit_normal`
+// through pathtrace_samples, and no albedo (left empty).
 struct denoise_guides {
   color_image normal = {}, albedo = {};
 };

@@ -716,7 +716,54 @@ device_entry& cached_entry(const scene_data& scene, const bvh_scene& bvh, const 
   }
   return *entry;
 }
+// the copy of `scene` on the first device alone (cache_mutex held), made on first use: pathtrace_adaptive, pathtrace_aovs
+vpt_scene* single_scene(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights) {
+  auto& entry = cached_entry(scene, bvh, lights);
+  if (!entry.single) {
+    auto flat = flat_scene{};
+    flatten_scene(flat, scene, bvh, lights);
+    if (vpt_scene_create_curves(&flat.desc, flat.curves_or_null(), device_list()[0], &entry.single) != VPT_OK) {
+      entry.single = nullptr;
+      device_cache().erase(&scene);
+      throw std::runtime_error{string{"vpt_scene_create_curves: "} + vpt_last_error()};
+    }
+  }
+  return entry.single;
+}
 }  // namespace
+
+pathtrace_aov_images pathtrace_aovs(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights, const pathtrace_params& params,
+    int samples, unsigned planes) {
+  if (samples < 1) throw std::invalid_argument{"aov samples must be >= 1"};
+  if ((planes & aov_all) == 0) throw std::invalid_argument{"no aov plane asked for"};
+  auto handle = (vpt_scene*)nullptr;
+  {
+    auto lock = std::lock_guard{cache_mutex};
+    handle    = single_scene(scene, bvh, lights);
+  }
+  auto p    = params;
+  p.shader  = pathtrace_shader_type::normal, p.samples = samples;
+  auto state = make_state(scene, p);
+  auto n     = (size_t)state.width * state.height;
+  auto out   = pathtrace_aov_images{};
+  auto abi   = vpt_aov_planes{};
+  auto sums  = [&](unsigned bit, color_image& image) -> void* {
+    if (!(planes & bit)) return nullptr;
+    image = color_image{state.width, state.height, true, vector<vec4f>(n)};
+    return image.pixels.data();
+  };
+  abi.normal = sums(aov_normal, out.normal), abi.albedo = sums(aov_albedo, out.albedo);
+  abi.texcoord = sums(aov_texcoord, out.texcoord), abi.depth = sums(aov_depth, out.depth);
+  if (planes & aov_ids) out.ids.resize(n), out.uvt.resize(n), abi.ids = out.ids.data(), abi.uvt = out.uvt.data();
+  static_assert(sizeof(vec2i) == 8 && sizeof(vec3f) == 12 && sizeof(vec4f) == 16, "plane layout");
+  auto pabi = to_abi(p);
+  if (vpt_render_aov(handle, &pabi, samples, state.width, state.height, &abi, state.hits.data(), (uint64_t*)state.rngs.data(), &state.samples) != VPT_OK)
+    throw std::runtime_error{string{"vpt_render_aov: "} + vpt_last_error()};
+  auto scale = 1.0f / (float)state.samples;   // get_render
+  for (auto image : {&out.normal, &out.albedo, &out.texcoord, &out.depth})
+    for (auto& q : image->pixels) q = {q.x * scale, q.y * scale, q.z * scale, q.w * scale};
+  return out;
+}
 
 void pathtrace_release(const scene_data& scene) {
   auto lock = std::lock_guard{cache_mutex};
@@ -788,17 +835,7 @@ pathtrace_adaptive_stats pathtrace_adaptive(pathtrace_state& state, const scene_
   {
     auto lock = std::lock_guard{cache_mutex};
     if (device_list().size() != 1) throw std::invalid_argument{"adaptive sampling renders on one GPU"};
-    auto& entry = cached_entry(scene, bvh, lights);
-    if (!entry.single) {
-      auto flat = flat_scene{};
-      flatten_scene(flat, scene, bvh, lights);
-      if (vpt_scene_create_curves(&flat.desc, flat.curves_or_null(), device_list()[0], &entry.single) != VPT_OK) {
-        entry.single = nullptr;
-        device_cache().erase(&scene);
-        throw std::runtime_error{string{"vpt_scene_create_curves: "} + vpt_last_error()};
-      }
-    }
-    handle = entry.single;
+    handle = single_scene(scene, bvh, lights);
   }
   auto abi   = to_abi(params);
   auto ad    = vpt_adaptive{adaptive.threshold, adaptive.min_samples, adaptive.step};
