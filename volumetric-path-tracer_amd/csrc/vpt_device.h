@@ -98,10 +98,14 @@ struct DScene {
   const int*    scene_prims;
   const float4* shape_nodes;   // 2 per node, pooled
   const float4* leaf_prims;    // 4 per slot, pooled
-  // "wide" nodes for the unified traversal: one 64-byte record per INTERNAL node holding BOTH child
-  // boxes and child references, so a visit costs one fetch and culled children are never fetched.
-  //   q0 = {L.min.xyz, L.max.x} q1 = {L.max.yz, R.min.xy} q2 = {R.min.z, R.max.xyz}
-  //   q3 = {ref0, ref1, axis, -} (ints); ref >= 0: internal wide node; ref < 0: leaf, ~ref = start<<4 | num
+  // quad nodes for the unified traversal (vpt_scene_prep.cpp: build_quad_nodes): one 128-byte record per internal node at even
+  // depth of the binary BVH, holding the boxes and references of its (up to) four grandchildren, so a visit costs one fetch.
+  //   words  0 .. 23  lo.x[4] lo.y[4] lo.z[4] hi.x[4] hi.y[4] hi.z[4]      (slots 0, 1: children of child 0; 2, 3: of child 1)
+  //   words 24 .. 27  ref[4] (ints); ref >= 0: quad node of the same BVH; ref < 0: leaf, ~ref = start << 4 | num; INT_MIN: empty slot
+  //   word  28        low 16 bits: axis | axis of child 0 << 2 | axis of child 1 << 4 (a leaf child: 0)
+  //   words 28 + j    high 16 bits: the visit rank of slot j in the reference's order, two bits per octant of the ray's direction
+  //                   (bits 16 + 2 s .. 17 + 2 s for s = sign_bits): rank = ((grp ^ gn) << 1) | ((j & 1) ^ (grp ? g1 : g0)) with
+  //                   grp = j >> 1 and gn, g0, g1 = bit `axis`, `axis of child 0`, `axis of child 1` of s.  Low 16 bits of words 29 .. 31: 0.
   const float4* scene_wnodes;   // ONE array: the scene's quad nodes, then the shapes' (traverse() names a level by its first node's index)
   const float4* shape_wnodes;   // = scene_wnodes + 8 * (number of scene quad nodes)
   // "enter records": everything the traversal needs to enter the instance stored at a scene-BVH

@@ -172,7 +172,7 @@ VPT_DEV bool slab_pass_signed(float nx, float ny, float nz, float fx, float fy, 
 // ray's state travels there by ds_bpermute and its results back - with the SAME loop shape as the own form (phase A until no ray of
 // the set holds a node, then phase B once), so the wave takes the same number of steps, each a fraction of the work:
 //   A  lane c of a group loads and tests grandchild c of the quad node (8 dwords and ~25 instructions instead of 29 dwords and
-//      ~75); the reference's visit order is a 2-bit rank per lane computed from the three split axes and the ray's signs, the
+//      ~75); the reference's visit order is a 2-bit rank per lane read from the slot's table in the node by the ray's signs, the
 //      four (pass, rank) pairs meet by DPP quad_perm, each lane stores its own candidate into the OWNER's LDS stack column
 //      at the position its rank gives it, and the first-visited one becomes the group's next node;
 //   B  the (<= 4) primitives of a leaf are tested one per lane against the tmax at leaf entry and reduced to the reference's
@@ -292,6 +292,7 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
       // with any tmax (t1 = min(far, tmax) * k only shrinks), so phase C skips those instances without fetching
       // their records; the others are tested again there against the current tmax, as the reference does.
       // Entering instances one lane at a time is the most divergent part of a query (13 of 64 lanes active).
+      // (The pre-pass is only a filter: a `reach` bit left set means "phase C tests this instance", as the reference does.)
       if (sc.num_scene_prims <= VPT_HOIST_MAX && cur != VPT_NONE) {
         bool any_slow = __builtin_amdgcn_ballot_w64(wslow) != 0;
         reach = 0;
@@ -442,6 +443,7 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
     const int   gmisc = pull(owner, csgn | (slow ? 8 : 0) | (shape_base >= 0 ? shape_base : 0) << VPT_FLOOR_SHIFT);
     if (!gact) gcur = VPT_NONE;
     const int  gfloor = gmisc >> VPT_FLOOR_SHIFT, gcsgn = gmisc & 7;
+    const unsigned krank_shift = 16u + 2u * (unsigned)gcsgn;   // where the rank of the ray's octant sits in a slot's table (below)
     const bool gslow = (gmisc & 8) != 0;
     const STK  gstk = stk.of_lane(owner);
     // what a call does not change is formed once: the level's first node (a step adds 128 bytes times gcur to it, without a sign to extend)
@@ -453,7 +455,7 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
       do {   // one test at the bottom, one exit: a group that holds a leaf or nothing stays switched off until the last one does
         const float* q = gq0 + 32 * (unsigned long long)(unsigned)gcur;
         float lox = q[j], loy = q[4 + j], loz = q[8 + j], hix = q[12 + j], hiy = q[16 + j], hiz = q[20 + j];
-        int   ref = __float_as_int(q[24 + j]), meta = __float_as_int(q[28]);
+        int   ref = __float_as_int(q[24 + j]), meta = __float_as_int(q[CURVES ? 28 : 28 + j]);
         float ax = (lox - gco.x) * gcinv.x, ay = (loy - gco.y) * gcinv.y, az = (loz - gco.z) * gcinv.z;
         float bx = (hix - gco.x) * gcinv.x, by = (hiy - gco.y) * gcinv.y, bz = (hiz - gco.z) * gcinv.z;
         float t0;
@@ -466,10 +468,16 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
         }
         const int  rj = pass ? ref : VPT_NONE;   // an empty slot holds VPT_NONE itself
         const bool present = rj != VPT_NONE;
-        // visit rank of grandchild j in the reference's order [group by the node's axis][member by the child's axis]
-        const int gn = (gcsgn >> (meta & 3)) & 1, g0 = (gcsgn >> ((meta >> 2) & 3)) & 1, g1 = (gcsgn >> ((meta >> 4) & 3)) & 1;
-        const int grp = j >> 1;
-        const int k = ((grp ^ gn) << 1) | ((j & 1) ^ (grp ? g1 : g0));
+        // visit rank of grandchild j in the reference's order [group by the node's axis][member by the child's axis]: a function of the
+        // node's three axes, the slot and the ray's octant, read from the slot's table in the node (vpt_device.h: two bits per octant)
+        // The instances for points and lines derive it from the axes and the sign bits (the same two bits: the table is this formula):
+        // with the table they spill 8 B more per lane and were measured 2.6 % slower on 09_curves_synth
+        int k;
+        if constexpr (CURVES) {
+          const int gn = (gcsgn >> (meta & 3)) & 1, g0 = (gcsgn >> ((meta >> 2) & 3)) & 1, g1 = (gcsgn >> ((meta >> 4) & 3)) & 1;
+          const int grp = j >> 1;
+          k = ((grp ^ gn) << 1) | ((j & 1) ^ (grp ? g1 : g0));
+        } else k = (int)(((unsigned)meta >> krank_shift) & 3u);   // (one bit-field extract)
         const int pv = quad_or(present ? 1 << k : 0);              // passing children by visit rank
         const int kfirst = pv ? __builtin_ctz(pv) : 4;
         // the first-visited one is the next node (popped next with the same tmax: its pop test is a tautology); the others are

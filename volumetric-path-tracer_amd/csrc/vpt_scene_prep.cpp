@@ -44,7 +44,10 @@ void pack_frame(const hframe& f, float4* out) {
 // Quad nodes (vpt_device.h): one 128-byte record per internal node at even depth, holding the boxes and
 // references of its (up to) four grandchildren in the binary BVH: slots 0,1 = children of child 0 (or
 // child 0 itself when it is a leaf, slot 1 empty), slots 2,3 likewise for child 1.  Layout: lo.x[4],
-// lo.y[4], lo.z[4], hi.x[4], hi.y[4], hi.z[4], ref[4], {axis | axis0 << 2 | axis1 << 4, 0, 0, 0}.
+// lo.y[4], lo.z[4], hi.x[4], hi.y[4], hi.z[4], ref[4], meta[4].  Low 16 bits of meta[0]: axis | axis0 << 2 | axis1 << 4, of
+// meta[1 .. 3]: 0.  High 16 bits of meta[j]: the visit rank of slot j in the reference's order, two bits for each of the 8 sign
+// octants of a ray's direction (bits 16 + 2 s, s = sign_bits): a function of the three axes, tabulated here so that the group form
+// of the node step reads it with the word it loads anyway (this function is the row's only writer: edits rewrite rows 0 .. 5).
 // ref >= 0: quad node (relative to this BVH), ~ref = start << 4 | count: leaf, VPT_NONE_REF: empty slot.
 // Returns the reference of the root and its box, appends to `out`; *need = worst-case number of stack
 // entries a traversal of this BVH holds at once (three pending siblings per quad level).
@@ -107,7 +110,15 @@ int build_quad_nodes(const vpt_bvh_node* nodes, int count, std::vector<float4>& 
     float4* q = &out[base + 8 * n];
     for (int c = 0; c < 6; c++) q[c] = make_float4(box[c][0], box[c][1], box[c][2], box[c][3]);
     memcpy(&q[6], ref, 16);
-    int meta[4] = {axes[0] | (axes[1] << 2) | (axes[2] << 4), 0, 0, 0};
+    // visit ranks: for octant s of a ray's direction (bit a set: negative along axis a) the reference reaches the child on the far
+    // side of the node's axis last, and likewise one level down; a leaf child counts as axis 0 (its second slot is empty)
+    unsigned meta[4] = {(unsigned)(axes[0] | (axes[1] << 2) | (axes[2] << 4)), 0, 0, 0};
+    for (int j = 0; j < 4; j++)
+      for (int s = 0; s < 8; s++) {
+        const int gn = (s >> axes[0]) & 1, g0 = (s >> axes[1]) & 1, g1 = (s >> axes[2]) & 1, grp = j >> 1;
+        const unsigned k = (unsigned)(((grp ^ gn) << 1) | ((j & 1) ^ (grp ? g1 : g0)));
+        meta[j] |= k << (16 + 2 * s);
+      }
     memcpy(&q[7], meta, 16);
   }
   *need = node_need[0];
