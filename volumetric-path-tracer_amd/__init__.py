@@ -1589,36 +1589,34 @@ class DeviceScene:
         state.samples = samples.value
         return out
 
+    def _edit(self, name: str, edit, *extra) -> None:
+        """the C-ABI's edit entry point `name` on this handle, the arrays `edit` points into kept alive across the call"""
+        abi, keep = edit.to_abi()
+        _check(getattr(hip, name)(self.handle, C.byref(abi), *extra), name)
+        del keep
+
     def update(self, edit: SceneEdit) -> None:
         """vpt_scene_update (include/vpt.h): the edit applied to the resident scene, BVHs refitted on the device.  Afterwards the
         handle renders the bits of a DeviceScene made from the host scene after the same edit and update_bvh()."""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_scene_update(self.handle, C.byref(abi)), "vpt_scene_update")
-        del keep
+        self._edit("vpt_scene_update", edit)
 
     def update_lights(self, edit: SceneEdit) -> None:
         """vpt_scene_update_lights (include/vpt.h): update() for an edit that may switch a material's emission between zero and non-zero
         or move the vertices of an emitter; the light tables are rebuilt on the device.  Afterwards the handle renders the bits of a
         DeviceScene made from the host scene after the same edit and update_lights()."""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_scene_update_lights(self.handle, C.byref(abi)), "vpt_scene_update_lights")
-        del keep
+        self._edit("vpt_scene_update_lights", edit)
 
     def update_textures(self, edit: TextureEdit) -> None:
         """vpt_scene_update_textures (include/vpt.h): environments' emission and texture, and textures' texels; an environment's CDF
         is rebuilt on the device from the texels.  Afterwards the handle renders the bits of a DeviceScene made from the host scene
         after the same edit and update_textures()."""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_scene_update_textures(self.handle, C.byref(abi)), "vpt_scene_update_textures")
-        del keep
+        self._edit("vpt_scene_update_textures", edit)
 
     def update_volumes(self, edit: VolumeEdit) -> None:
         """vpt_scene_update_volumes (include/vpt.h): grid instances, SDFs and volumes' voxels, from the host or baked on the device into
         the resident pool.  Afterwards the handle renders the bits of a DeviceScene made from the host scene after the same edit and
         update_volumes()."""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_scene_update_volumes(self.handle, C.byref(abi)), "vpt_scene_update_volumes")
-        del keep
+        self._edit("vpt_scene_update_volumes", edit)
 
     def get_volumes(self):
         """(volumes, vol_instances, sdfs) as the device holds them, ctypes arrays of VptVolume, VptVolumeInstance, VptSdf
@@ -1670,25 +1668,19 @@ class DeviceScene:
         """vpt_scene_rebuild_bvh (include/vpt.h): the named shapes' BVHs and the scene BVH built anew on the device from what is
         resident.  Afterwards the handle renders the bits of a DeviceScene made from the host scene after the same
         HostScene.rebuild_bvh()."""
-        abi, keep = rebuild.to_abi()
-        _check(hip.vpt_scene_rebuild_bvh_quality(self.handle, C.byref(abi), rebuild.quality), "vpt_scene_rebuild_bvh_quality")
-        del keep
+        self._edit("vpt_scene_rebuild_bvh_quality", rebuild, rebuild.quality)
 
     def update_instances(self, edit: InstanceEdit) -> None:
         """vpt_scene_update_instances (include/vpt.h): instances re-pointed, removed and added on the device; the scene BVH and the
         lights follow.  Afterwards the handle renders the bits of a DeviceScene made from the host scene after the same
         HostScene.update_instances()."""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_scene_update_instances(self.handle, C.byref(abi)), "vpt_scene_update_instances")
-        del keep
+        self._edit("vpt_scene_update_instances", edit)
 
     def update_shapes(self, edit: ShapeEdit) -> None:
         """vpt_scene_update_shapes (include/vpt.h): shapes replaced, removed and added on the device; pools, BVHs, instances and lights
         follow.  Afterwards the handle renders the bits of a DeviceScene made from the host scene after the same
         HostScene.update_shapes()."""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_scene_update_shapes(self.handle, C.byref(abi)), "vpt_scene_update_shapes")
-        del keep
+        self._edit("vpt_scene_update_shapes", edit)
 
     def shape_tables_hash(self):
         """FNV-1a of the eight groups of tables laid out in shape order (vpt_scene_shape_tables_hash): shapes, vertex pools, elems,
@@ -1864,47 +1856,39 @@ class MultiDeviceScene:
         _check(hip.vpt_multi_create_curves(scene.desc, scene.curves, devs, len(devices), C.byref(out)), "vpt_multi_create")
         self.handle = out
 
+    def _edit(self, name: str, edit, *extra) -> None:
+        """the C-ABI's edit entry point `name` on this handle, the arrays `edit` points into kept alive across the call"""
+        abi, keep = edit.to_abi()
+        _check(getattr(hip, name)(self.handle, C.byref(abi), *extra), name)
+        del keep
+
     def update(self, edit: SceneEdit) -> None:
         """vpt_multi_update: the same edit on every device; the resident tile state is left as it is"""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_multi_update(self.handle, C.byref(abi)), "vpt_multi_update")
-        del keep
+        self._edit("vpt_multi_update", edit)
 
     def update_lights(self, edit: SceneEdit) -> None:
         """vpt_multi_update_lights: DeviceScene.update_lights with the same edit on every device"""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_multi_update_lights(self.handle, C.byref(abi)), "vpt_multi_update_lights")
-        del keep
+        self._edit("vpt_multi_update_lights", edit)
 
     def update_textures(self, edit: TextureEdit) -> None:
         """vpt_multi_update_textures: DeviceScene.update_textures with the same edit on every device"""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_multi_update_textures(self.handle, C.byref(abi)), "vpt_multi_update_textures")
-        del keep
+        self._edit("vpt_multi_update_textures", edit)
 
     def update_volumes(self, edit: VolumeEdit) -> None:
         """vpt_multi_update_volumes: DeviceScene.update_volumes with the same edit on every device"""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_multi_update_volumes(self.handle, C.byref(abi)), "vpt_multi_update_volumes")
-        del keep
+        self._edit("vpt_multi_update_volumes", edit)
 
     def rebuild_bvh(self, rebuild: "BvhRebuild") -> None:
         """vpt_multi_rebuild_bvh: DeviceScene.rebuild_bvh on every device (each builds its own trees: equal by construction)"""
-        abi, keep = rebuild.to_abi()
-        _check(hip.vpt_multi_rebuild_bvh_quality(self.handle, C.byref(abi), rebuild.quality), "vpt_multi_rebuild_bvh_quality")
-        del keep
+        self._edit("vpt_multi_rebuild_bvh_quality", rebuild, rebuild.quality)
 
     def update_instances(self, edit: InstanceEdit) -> None:
         """vpt_multi_update_instances: DeviceScene.update_instances with the same edit on every device"""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_multi_update_instances(self.handle, C.byref(abi)), "vpt_multi_update_instances")
-        del keep
+        self._edit("vpt_multi_update_instances", edit)
 
     def update_shapes(self, edit: ShapeEdit) -> None:
         """vpt_multi_update_shapes: DeviceScene.update_shapes with the same edit on every device"""
-        abi, keep = edit.to_abi()
-        _check(hip.vpt_multi_update_shapes(self.handle, C.byref(abi)), "vpt_multi_update_shapes")
-        del keep
+        self._edit("vpt_multi_update_shapes", edit)
 
     def pathtrace_samples(self, state: PathtraceState, params: PathtraceParams, count: int = 1) -> None:
         """host state in, host state out (the contract of vpt_render); a device's part of the upload is skipped only while `state`'s

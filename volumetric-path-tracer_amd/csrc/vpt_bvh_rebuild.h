@@ -6,18 +6,13 @@
 #include "vpt_bvh_build.h"
 #include "vpt_resident.h"
 
-// the traversal stacks the new trees need: vpt_capi.hip's render side takes them over
-struct bvh_rebuild_stacks {
-  bool rebuilt = false;   // the call built something (false: an empty request, nothing changed)
-  int  stack_cap = 16, stack_lds4 = 8, stack_spill4 = 0;
-};
-
 // Validates `what` (nothing is written before it has passed), builds the named shapes' BVHs and the scene BVH on the current
 // device into buffers of their own, decides the traversal limits from the new trees (VPT_ERR_UNSUPPORTED: the scene is as it was)
 // and only then reorders the leaf records and swaps tables, counts and mirrors.  Returns after the device has finished;
-// r.refit.ready is cleared.  The caller runs the light setup afterwards (light_prims follow the leaf records).
+// r.refit.ready is cleared.  out: changed and topology with the traversal stacks the new trees need, or - an empty request - untouched;
+// the caller runs the light setup afterwards (light_prims follow the leaf records).
 // quality: VPT_BVH_MIDDLE or VPT_BVH_SAH for every tree the call builds (another value: VPT_ERR_INVALID_ARG, first of all).
-int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& what, bvh_rebuild_stacks& stacks, int quality = VPT_BVH_MIDDLE);
+int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& what, edit_outcome& out, int quality = VPT_BVH_MIDDLE);
 
 // The scene level of a rebuild, shared with vpt_scene_update_instances (vpt_instance_update.hip): the scene BVH over a table of
 // instances, in buffers of the call until scene_level_swap hands them to the scene.

@@ -19,9 +19,6 @@
 
 namespace {
 
-constexpr int BLOCK = 256;
-inline unsigned blocks_for(long long n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 // source[k] = the old slot of the element the new slot k holds (both local to the shape)
 __global__ void rb_source_slots_kernel(int n, const int* __restrict__ prims, const int* __restrict__ old_slot, int* __restrict__ source) {
   int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -49,32 +46,11 @@ __global__ void rb_gather_records_kernel(int n, const int* __restrict__ source, 
   for (int c = 0; c < 4; c++) out[4 * (long long)k + c] = tri_attrs[4 * from + c];
 }
 
-#define RB_LAUNCH(r, kernel, n, ...)                                                     \
-  do {                                                                                   \
-    if ((n) > 0) {                                                                       \
-      hipLaunchKernelGGL(kernel, dim3(blocks_for(n)), dim3(BLOCK), 0, 0, __VA_ARGS__);   \
-      HIP_TRY(hipGetLastError());                                                        \
-      (r).last_launches++;                                                               \
-    }                                                                                    \
-  } while (0)
-
 struct built_shape {   // one named shape's new tree, on the device until the swap
   int              id = 0, count = 0;
   device_buffer    nodes, source;   // vpt_bvh_node[count]; int[num_elems]: old slot per new slot
   std::vector<int> prims;           // the new primitive order, read back
 };
-
-template <typename T>
-int fetch(resident& r, std::vector<T>& out, const void* dev, size_t count) {   // device to host, counted
-  out.resize(count);
-  if (count) HIP_TRY(hipMemcpy(out.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost));
-  r.last_bytes += (long long)(count * sizeof(T));
-  return VPT_OK;
-}
-int copy_on_device(void* to, const void* from, size_t bytes) {
-  if (bytes) HIP_TRY(hipMemcpy(to, from, bytes, hipMemcpyDeviceToDevice));
-  return VPT_OK;
-}
 
 }  // namespace
 
@@ -124,17 +100,13 @@ void scene_level_swap(resident& r, scene_level& lv, const scene_tables& t) {
   r.refit.ready = false;   // levels and quad slots belong to the old trees: the next refit makes them anew
 }
 
-int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks& stacks, int quality) {
+int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, edit_outcome& out, int quality) {
   if (quality != VPT_BVH_MIDDLE && quality != VPT_BVH_SAH) return vpt_set_error(VPT_ERR_INVALID_ARG, "unknown bvh quality %d", quality);
   DScene&       d = r.d;
   host_mirrors& h = r.h;
   edit_mirrors& m = r.m;
   // every refusal about the request happens here: nothing has been written
-  {
-    static const char some = 0;   // check_ids wants a payload beside the ids: the request has none
-    if (int rc = check_ids("shape", w.num_shapes, w.shape_ids, &some, d.num_shapes)) return rc;
-  }
-  stacks.rebuilt = false;
+  if (int rc = check_ids("shape", w.num_shapes, w.shape_ids, d.num_shapes)) return rc;
   if (w.num_shapes == 0 && !w.scene) return VPT_OK;
   if (int rc = begin_update(r)) return rc;
   const int ninst = d.num_instances, nshapes = d.num_shapes;
@@ -163,7 +135,7 @@ int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks&
     if (int rc = b.nodes.allocate((size_t)b.count * sizeof(vpt_bvh_node))) return rc;
     if (int rc = b.source.allocate((size_t)n * sizeof(int))) return rc;
     if (int rc = copy_on_device(b.nodes.get(), core.nodes(), (size_t)b.count * sizeof(vpt_bvh_node))) return rc;
-    RB_LAUNCH(r, rb_source_slots_kernel, n, n, core.primitives(), d_old_slot.get<int>(), b.source.get<int>());
+    LAUNCH(r, rb_source_slots_kernel, n, n, core.primitives(), d_old_slot.get<int>(), b.source.get<int>());
     if (int rc = fetch(r, b.prims, core.primitives(), (size_t)n)) return rc;   // (after the launch above in stream order)
   }
 
@@ -220,7 +192,7 @@ int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks&
     const DShape&   sh = m.shapes[(size_t)b.id];
     const long long n = sh.num_elems, at = sh.leaf_offset;
     float4*         tmp = d_tmp.get<float4>();
-    RB_LAUNCH(r, rb_gather_records_kernel, n, (int)n, b.source.get<int>(), at, d.leaf_prims, d.leaf_attrs, d.tri_prims, d.tri_attrs, tmp);
+    LAUNCH(r, rb_gather_records_kernel, n, (int)n, b.source.get<int>(), at, d.leaf_prims, d.leaf_attrs, d.tri_prims, d.tri_attrs, tmp);
     if (int rc = copy_on_device(mut(d.leaf_prims) + 4 * at, tmp, (size_t)(4 * n) * sizeof(float4))) return rc;
     if (int rc = copy_on_device(mut(d.leaf_attrs) + 6 * at, tmp + 4 * n, (size_t)(6 * n) * sizeof(float4))) return rc;
     if (tris) {
@@ -237,12 +209,10 @@ int bvh_rebuild_apply(resident& r, const vpt_bvh_rebuild& w, bvh_rebuild_stacks&
   scene_level_swap(r, lv, t);
   r.num_shape_nodes = total, m.shapes = t.shapes;
   r.num_shape_wnodes = (long long)t.shape_wnodes, r.shape_depth = t.shape_depths, r.shape_need4 = t.shape_need4s, r.shape_quads = t.shape_quads;
-  stacks.rebuilt = true, stacks.stack_cap = t.stack_cap, stacks.stack_lds4 = t.stack_lds4, stacks.stack_spill4 = t.stack_spill4;
+  out.changed = out.topology = true, out.stack_cap = t.stack_cap, out.stack_lds4 = t.stack_lds4, out.stack_spill4 = t.stack_spill4;
 
   // 7. what hangs on the shapes' root boxes outside the BVHs: the mesh lights' records
   if (int rc = upd_light_records(r, d.shapes)) return rc;
-  HIP_TRY(hipEventRecord(r.upd_ev1, 0));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipEventElapsedTime(&r.last_ms, r.upd_ev0, r.upd_ev1));
-  return VPT_OK;
+  if (int rc = mark_end(r)) return rc;
+  return finish_update(r);
 }

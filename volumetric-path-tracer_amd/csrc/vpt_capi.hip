@@ -391,14 +391,6 @@ int vpt_render_device(vpt_scene* s, const vpt_params* params, const vpt_layout* 
   return VPT_OK;
 }
 
-// the resident camera, for callers that size a frame from it (vpt_session, vpt_session.hip)
-int vpt_scene_get_camera(vpt_scene* s, int camera, vpt_camera* out) {
-  if (!s || !out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  if (camera < 0 || camera >= s->d.num_cameras) return vpt_set_error(VPT_ERR_INVALID_ARG, "camera %d out of range", camera);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipMemcpy(out, s->d.cameras + camera, sizeof(vpt_camera), hipMemcpyDeviceToHost));
-  return VPT_OK;
-}
 int vpt_scene_get_device(const vpt_scene* s) { return s ? s->device : vpt_set_error(VPT_ERR_INVALID_ARG, "null argument"); }
 
 int vpt_scene_record_bytes(const vpt_scene* s, int* leaf_bytes, int* attribute_bytes) {
@@ -409,24 +401,33 @@ int vpt_scene_record_bytes(const vpt_scene* s, int* leaf_bytes, int* attribute_b
 
 }  // extern "C"
 
-// ---- editing a resident scene (include/vpt.h; the work is the four update units') --------------------------------------------
+// ---- editing a resident scene (include/vpt.h; the work is the update units') -------------------------------------------------
+const resident& resident_of(const vpt_scene* s) { return *s; }   // for vpt_scene_inspect.hip, which reads the tables back
+
 static bool moves_geometry(const vpt_scene_edit& e) { return e.num_instances > 0 || e.num_shapes > 0; }
 static bool writes_materials(const vpt_scene_edit& e) { return e.num_materials > 0; }
 template <typename Edit> static bool moves_geometry(const Edit&) { return false; }   // environments, textures, volumes, SDFs
 template <typename Edit> static bool writes_materials(const Edit&) { return false; }
 
-// One edit, from the idle device it needs to the tables that only this unit's kernels fill.  apply(resident&, edit, &rebuilt): the
-// unit's work; rebuilt: the light tables were made anew - light_prims and the medium records sit in fresh allocations.
+// One edit, from the idle device it needs to what the render side owes it afterwards.  apply(resident&, edit, edit_outcome&): the
+// unit's work (vpt_resident.h says what it reports).
 template <typename Edit, typename Apply>
 static int edit_scene(vpt_scene* s, const Edit* edit, Apply apply) {
   if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call rewrites
-  bool rebuilt = false;
-  if (int rc = apply(*s, *edit, &rebuilt)) return rc;
-  if (rebuilt || moves_geometry(*edit))
-    if (int rc = light_setup(s)) return rc;   // light_prims hold world-space normals of the moved lights
-  if (rebuilt || writes_materials(*edit))     // the medium records follow the materials
+  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call rewrites or replaces
+  edit_outcome out = {false, false, false, s->stack_cap, s->stack_lds4, s->stack_spill4, s->curves};
+  if (int rc = apply(*s, *edit, out)) return rc;
+  if (!out.changed) return VPT_OK;   // an empty request: the schedule and the counters of the last edit stay
+  if (out.topology) {   // new trees or lists: the stack sizes and the kernel instances follow
+    if (out.stack_spill4 != s->stack_spill4) s->spill_lanes = 0;   // the HBM part is sized per entry: made anew by the next launch
+    s->stack_cap = out.stack_cap, s->stack_lds4 = out.stack_lds4, s->stack_spill4 = out.stack_spill4;
+    s->curves = out.curves;
+  }
+  // light_prims hold world-space normals of the moved lights, name instances and read the leaf records through the shape table
+  if (out.lights_rebuilt || out.topology || moves_geometry(*edit))
+    if (int rc = light_setup(s)) return rc;
+  if (out.lights_rebuilt || writes_materials(*edit))   // the medium records follow the materials and sit behind the light records
     if (int rc = medium_setup(s)) return rc;
   s->sched.forget();   // the camera index may be the same, the picture is not
   return VPT_OK;
@@ -435,251 +436,25 @@ static int edit_scene(vpt_scene* s, const Edit* edit, Apply apply) {
 extern "C" {
 
 int vpt_scene_update(vpt_scene* s, const vpt_scene_edit* edit) {
-  return edit_scene(s, edit, [](resident& r, const vpt_scene_edit& e, bool*) { return scene_update_apply(r, e); });
+  return edit_scene(s, edit, [](resident& r, const vpt_scene_edit& e, edit_outcome& out) { return scene_update_apply(r, e, out); });
 }
 // the two refusals about lights are lifted and the light tables follow the edit
 int vpt_scene_update_lights(vpt_scene* s, const vpt_scene_edit* edit) {
-  return edit_scene(s, edit, [](resident& r, const vpt_scene_edit& e, bool* rebuilt) {
-    const int rc = scene_update_apply(r, e, true);
-    return rc ? rc : light_update_apply(r, e, rebuilt);
+  return edit_scene(s, edit, [](resident& r, const vpt_scene_edit& e, edit_outcome& out) {
+    const int rc = scene_update_apply(r, e, out, true);
+    return rc ? rc : light_update_apply(r, e, &out.lights_rebuilt);
   });
 }
 // the light tables follow when an environment's light does / when the SDF lights do
 int vpt_scene_update_textures(vpt_scene* s, const vpt_texture_edit* edit) { return edit_scene(s, edit, texture_update_apply); }
 int vpt_scene_update_volumes(vpt_scene* s, const vpt_volume_edit* edit) { return edit_scene(s, edit, volume_update_apply); }
-
-// the three small tables and a volume's voxels as the device holds them now
-int vpt_scene_get_volumes(vpt_scene* s, vpt_volume* volumes, int volume_capacity, vpt_volume_instance* vol_instances, int instance_capacity, vpt_sdf* sdfs,
-    int sdf_capacity) {
-  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  REQUIRE(!volumes || volume_capacity >= s->d.num_volumes, "volume_capacity %d < %d volumes", volume_capacity, s->d.num_volumes);
-  REQUIRE(!vol_instances || instance_capacity >= s->d.num_vol_instances, "instance_capacity %d < %d volume instances", instance_capacity, s->d.num_vol_instances);
-  REQUIRE(!sdfs || sdf_capacity >= s->d.num_sdfs, "sdf_capacity %d < %d sdfs", sdf_capacity, s->d.num_sdfs);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (volumes && s->d.num_volumes) HIP_TRY(hipMemcpy(volumes, s->d.volumes, (size_t)s->d.num_volumes * sizeof(vpt_volume), hipMemcpyDeviceToHost));
-  if (vol_instances && s->d.num_vol_instances)
-    HIP_TRY(hipMemcpy(vol_instances, s->d.vol_instances, (size_t)s->d.num_vol_instances * sizeof(vpt_volume_instance), hipMemcpyDeviceToHost));
-  if (sdfs && s->d.num_sdfs) HIP_TRY(hipMemcpy(sdfs, s->d.sdfs, (size_t)s->d.num_sdfs * sizeof(vpt_sdf), hipMemcpyDeviceToHost));
-  return VPT_OK;
-}
-int vpt_scene_get_voxels(vpt_scene* s, int volume, float* voxels, int64_t capacity) {
-  if (!s || !voxels) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  REQUIRE(volume >= 0 && volume < s->d.num_volumes, "volume %d out of range (%d)", volume, s->d.num_volumes);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  vpt_volume v;
-  HIP_TRY(hipMemcpy(&v, s->d.volumes + volume, sizeof(v), hipMemcpyDeviceToHost));
-  const long long n = (long long)v.whd[0] * v.whd[1] * v.whd[2];
-  REQUIRE(capacity >= n, "capacity %lld < %lld voxels", (long long)capacity, n);
-  if (n) HIP_TRY(hipMemcpy(voxels, s->d.voxels + v.offset, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  return VPT_OK;
-}
-
-// the light list and the CDF pool as the device holds them now
-int vpt_scene_get_lights(vpt_scene* s, vpt_light* lights, int light_capacity, int* num_lights, float* cdf, int64_t cdf_capacity, int64_t* num_cdf) {
-  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  if (num_lights) *num_lights = s->d.num_lights;
-  if (num_cdf) *num_cdf = s->m.num_cdf;
-  REQUIRE(!lights || light_capacity >= s->d.num_lights, "light_capacity %d < %d lights", light_capacity, s->d.num_lights);
-  REQUIRE(!cdf || cdf_capacity >= s->m.num_cdf, "cdf_capacity %lld < %lld cdf entries", (long long)cdf_capacity, s->m.num_cdf);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (lights && s->d.num_lights) HIP_TRY(hipMemcpy(lights, s->d.lights, (size_t)s->d.num_lights * sizeof(vpt_light), hipMemcpyDeviceToHost));
-  if (cdf && s->m.num_cdf) HIP_TRY(hipMemcpy(cdf, s->d.light_cdf, (size_t)s->m.num_cdf * sizeof(float), hipMemcpyDeviceToHost));
-  return VPT_OK;
-}
-
-// the medium records as the device holds them now
-int vpt_scene_get_media(vpt_scene* s, float* records, int capacity, int* num_materials, int* varying) {
-  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  if (num_materials) *num_materials = s->d.num_materials;
-  if (varying) *varying = s->varying_media ? 1 : 0;
-  REQUIRE(!records || capacity >= s->d.num_materials, "capacity %d < %d materials", capacity, s->d.num_materials);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (records && s->d.num_materials)
-    HIP_TRY(hipMemcpy(records, s->d.light_rec + 8 * (size_t)s->d.num_lights, 3 * (size_t)s->d.num_materials * sizeof(float4), hipMemcpyDeviceToHost));
-  return VPT_OK;
-}
-
-// FNV-1a over the six light tables read back from the device: lights, light_cdf, light_rec, light_prims, light_index + its pool, light_guide
-int vpt_scene_light_tables_hash(vpt_scene* s, uint64_t out[6]) {
-  if (!s || !out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t nl = (size_t)s->d.num_lights;
-  const struct { const void* table; size_t bytes; int slot; } parts[7] = {
-      {s->d.lights, nl * sizeof(vpt_light), 0}, {s->d.light_cdf, (size_t)s->m.num_cdf * sizeof(float), 1}, {s->d.light_rec, 8 * nl * sizeof(float4), 2},
-      {s->d.light_prims, 20 * nl * sizeof(float4), 3}, {s->d.light_index, nl * sizeof(DCdfIndex), 4},
-      {s->d.light_index_pool, (size_t)s->m.num_pool * sizeof(float), 4}, {s->d.light_guide, (size_t)s->m.num_guide * sizeof(int2), 5}};
-  for (int k = 0; k < 6; k++) out[k] = 14695981039346656037ull;
-  std::vector<unsigned char> host;
-  for (const auto& p : parts) {
-    host.resize(p.bytes);
-    if (p.bytes) HIP_TRY(hipMemcpy(host.data(), p.table, p.bytes, hipMemcpyDeviceToHost));
-    uint64_t hash = out[p.slot];
-    for (unsigned char b : host) hash = (hash ^ b) * 1099511628211ull;
-    out[p.slot] = hash;
-  }
-  return VPT_OK;
-}
-
-int vpt_scene_get_bvh(vpt_scene* s, vpt_bvh_node* scene_nodes, int scene_capacity, vpt_bvh_node* shape_nodes, int64_t shape_capacity) {
-  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  REQUIRE(!scene_nodes || scene_capacity >= s->d.num_scene_nodes, "scene_capacity %d < %d scene bvh nodes", scene_capacity, s->d.num_scene_nodes);
-  REQUIRE(!shape_nodes || shape_capacity >= s->num_shape_nodes, "shape_capacity %lld < %lld shape bvh nodes", (long long)shape_capacity, s->num_shape_nodes);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (scene_nodes && s->d.num_scene_nodes) HIP_TRY(hipMemcpy(scene_nodes, s->d.scene_nodes, (size_t)s->d.num_scene_nodes * sizeof(vpt_bvh_node), hipMemcpyDeviceToHost));
-  if (shape_nodes && s->num_shape_nodes) HIP_TRY(hipMemcpy(shape_nodes, s->d.shape_nodes, (size_t)s->num_shape_nodes * sizeof(vpt_bvh_node), hipMemcpyDeviceToHost));
-  return VPT_OK;
-}
-
-// the BVHs built anew (vpt_bvh_rebuild.hip); the render side follows: stack sizes, the HBM part of the stacks, light_prims
+// the BVHs built anew (vpt_bvh_rebuild.hip), the set of instances changed (vpt_instance_update.hip), the shape list changed (vpt_shape_update.hip)
 int vpt_scene_rebuild_bvh(vpt_scene* s, const vpt_bvh_rebuild* what) { return vpt_scene_rebuild_bvh_quality(s, what, VPT_BVH_MIDDLE); }
 int vpt_scene_rebuild_bvh_quality(vpt_scene* s, const vpt_bvh_rebuild* what, int quality) {
-  if (!s || !what) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  if (quality != VPT_BVH_MIDDLE && quality != VPT_BVH_SAH) return vpt_set_error(VPT_ERR_INVALID_ARG, "unknown bvh quality %d", quality);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call replaces
-  bvh_rebuild_stacks st;
-  if (int rc = bvh_rebuild_apply(*s, *what, st, quality)) return rc;
-  if (!st.rebuilt) return VPT_OK;
-  if (st.stack_spill4 != s->stack_spill4) s->spill_lanes = 0;   // the HBM part is sized per entry: made anew by the next launch
-  s->stack_cap = st.stack_cap, s->stack_lds4 = st.stack_lds4, s->stack_spill4 = st.stack_spill4;
-  if (int rc = light_setup(s)) return rc;   // light_prims read the leaf records, which have moved
-  s->sched.forget();
-  return VPT_OK;
+  return edit_scene(s, what, [quality](resident& r, const vpt_bvh_rebuild& w, edit_outcome& out) { return bvh_rebuild_apply(r, w, out, quality); });
 }
-// the set of instances changed (vpt_instance_update.hip); the render side follows: stack sizes, the kernel instances, light_prims
-int vpt_scene_update_instances(vpt_scene* s, const vpt_instance_edit* edit) {
-  if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call replaces
-  bvh_rebuild_stacks     st;
-  instance_update_result res;
-  if (int rc = instance_update_apply(*s, *edit, st, res)) return rc;
-  if (!st.rebuilt) return VPT_OK;
-  if (st.stack_spill4 != s->stack_spill4) s->spill_lanes = 0;   // the HBM part is sized per entry: made anew by the next launch
-  s->stack_cap = st.stack_cap, s->stack_lds4 = st.stack_lds4, s->stack_spill4 = st.stack_spill4;
-  s->curves = res.curves;
-  if (int rc = light_setup(s)) return rc;   // light_prims name instances and hold world-space normals
-  if (res.lights_rebuilt)
-    if (int rc = medium_setup(s)) return rc;   // the medium records sit behind the light records, which were made anew
-  s->sched.forget();
-  return VPT_OK;
-}
-// the shape list changed (vpt_shape_update.hip); the render side follows: stack sizes, the kernel instances, light_prims
-int vpt_scene_update_shapes(vpt_scene* s, const vpt_shape_edit* edit) {
-  if (!s || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the tables this call replaces
-  bvh_rebuild_stacks  st;
-  shape_update_result res;
-  if (int rc = shape_update_apply(*s, *edit, st, res)) return rc;
-  if (!st.rebuilt) return VPT_OK;
-  if (st.stack_spill4 != s->stack_spill4) s->spill_lanes = 0;   // the HBM part is sized per entry: made anew by the next launch
-  s->stack_cap = st.stack_cap, s->stack_lds4 = st.stack_lds4, s->stack_spill4 = st.stack_spill4;
-  s->curves = res.curves;
-  if (int rc = light_setup(s)) return rc;   // light_prims read the leaf records through the shape table: both are new
-  if (res.lights_rebuilt)
-    if (int rc = medium_setup(s)) return rc;   // the medium records sit behind the light records, which were made anew
-  s->sched.forget();
-  return VPT_OK;
-}
-// FNV-1a over the tables laid out in shape order, read back from the device (include/vpt.h names the eight groups)
-int vpt_scene_shape_tables_hash(vpt_scene* s, uint64_t out[8]) {
-  if (!s || !out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t slots = s->h.prim_slot.size();
-  const struct { const void* table; size_t bytes; int slot; } parts[12] = {{s->d.shapes, (size_t)s->d.num_shapes * sizeof(DShape), 0},
-      {s->d.positions, (size_t)s->num_positions * sizeof(float4), 1}, {s->d.normals, (size_t)s->num_normals * sizeof(float4), 1},
-      {s->d.texcoords, (size_t)s->num_texcoords * sizeof(float2), 1}, {s->d.colors, (size_t)s->num_colors * sizeof(float4), 1},
-      {s->d.elems, slots * sizeof(int4), 2}, {s->d.leaf_prims, (4 * slots + 8) * sizeof(float4), 3}, {s->d.leaf_attrs, 6 * slots * sizeof(float4), 4},
-      {s->d.tri_prims, s->d.tri_prims ? (3 * slots + 8) * sizeof(float4) : 0, 5}, {s->d.tri_attrs, s->d.tri_attrs ? 4 * slots * sizeof(float4) : 0, 5},
-      {s->d.shape_nodes, (size_t)s->num_shape_nodes * sizeof(vpt_bvh_node), 6}, {s->d.shape_wnodes, (size_t)s->num_shape_wnodes * sizeof(float4), 7}};
-  for (int k = 0; k < 8; k++) out[k] = 14695981039346656037ull;
-  std::vector<unsigned char> host;
-  for (const auto& p : parts) {
-    host.resize(p.bytes);
-    if (p.bytes) HIP_TRY(hipMemcpy(host.data(), p.table, p.bytes, hipMemcpyDeviceToHost));
-    uint64_t hash = out[p.slot];
-    for (unsigned char b : host) hash = (hash ^ b) * 1099511628211ull;
-    out[p.slot] = hash;
-  }
-  if (!s->d.tri_prims) out[5] = 0;
-  return VPT_OK;
-}
-int vpt_scene_get_shape_counts(vpt_scene* s, int32_t* num_shapes, int64_t* num_elements, int64_t* num_vertices) {
-  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  if (num_shapes) *num_shapes = s->d.num_shapes;
-  if (num_elements) *num_elements = (int64_t)s->h.prim_slot.size();
-  if (num_vertices) *num_vertices = s->num_positions;
-  return VPT_OK;
-}
-int vpt_scene_get_instances(vpt_scene* s, vpt_instance* out, int capacity, int* num_instances) {
-  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  if (num_instances) *num_instances = s->d.num_instances;
-  if (!out) return VPT_OK;
-  REQUIRE(capacity >= s->d.num_instances, "capacity %d < %d instances", capacity, s->d.num_instances);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<DInstance> host((size_t)s->d.num_instances);
-  if (!host.empty()) HIP_TRY(hipMemcpy(host.data(), s->d.instances, host.size() * sizeof(DInstance), hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < host.size(); i++) {
-    static_assert(sizeof(vpt_frame) == 3 * sizeof(float4), "a packed frame is the frame's twelve floats in order");
-    memcpy(&out[i].frame, host[i].fwd, sizeof(vpt_frame));
-    out[i].shape = host[i].shape, out[i].material = host[i].material;
-  }
-  return VPT_OK;
-}
-// FNV-1a over the tables keyed by instance id, read back from the device: instances, scene_enter, slot_of_instance, scene_prims
-int vpt_scene_instance_tables_hash(vpt_scene* s, uint64_t out[4]) {
-  if (!s || !out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t ni = (size_t)s->d.num_instances, np = (size_t)s->d.num_scene_prims;
-  const struct { const void* table; size_t bytes; } parts[4] = {{s->d.instances, ni * sizeof(DInstance)}, {s->d.scene_enter, 6 * np * sizeof(float4)},
-      {s->d.slot_of_instance, ni * sizeof(int)}, {s->d.scene_prims, np * sizeof(int)}};
-  std::vector<unsigned char> host;
-  for (int k = 0; k < 4; k++) {
-    host.resize(parts[k].bytes);
-    if (parts[k].bytes) HIP_TRY(hipMemcpy(host.data(), parts[k].table, parts[k].bytes, hipMemcpyDeviceToHost));
-    uint64_t hash = 14695981039346656037ull;
-    for (unsigned char b : host) hash = (hash ^ b) * 1099511628211ull;
-    out[k] = hash;
-  }
-  return VPT_OK;
-}
-int vpt_scene_get_bvh_counts(vpt_scene* s, int32_t* scene_nodes, int64_t* shape_nodes, int64_t* shape_node_offsets) {
-  if (!s || !scene_nodes || !shape_nodes) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  *scene_nodes = s->d.num_scene_nodes, *shape_nodes = s->num_shape_nodes;
-  if (shape_node_offsets)
-    for (int i = 0; i < s->d.num_shapes; i++) shape_node_offsets[i] = s->m.shapes[(size_t)i].node_offset;
-  return VPT_OK;
-}
-// the shapes' order is read from the leaf records themselves (the element id in p0.w of every slot): what the traversal reports
-int vpt_scene_get_bvh_prims(vpt_scene* s, int32_t* scene_prims, int capacity, int32_t* shape_prims, int64_t shape_capacity) {
-  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  const long long slots = (long long)s->h.prim_slot.size();
-  REQUIRE(!scene_prims || capacity >= s->d.num_scene_prims, "capacity %d < %d scene bvh primitives", capacity, s->d.num_scene_prims);
-  REQUIRE(!shape_prims || shape_capacity >= slots, "shape_capacity %lld < %lld shape bvh primitives", (long long)shape_capacity, slots);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (scene_prims && s->d.num_scene_prims) HIP_TRY(hipMemcpy(scene_prims, s->d.scene_prims, (size_t)s->d.num_scene_prims * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (shape_prims && slots)
-    HIP_TRY(hipMemcpy2D(shape_prims, sizeof(int32_t), (const char*)s->d.leaf_prims + 12, 4 * sizeof(float4), sizeof(int32_t), (size_t)slots, hipMemcpyDeviceToHost));
-  return VPT_OK;
-}
-
-// what the last vpt_scene_update on this handle launched and sent (profiles/tools/scene_update_measure.py)
-int vpt_scene_update_stats(const vpt_scene* s, int* launches, int64_t* bytes, float* device_ms) {
-  if (!s || !launches || !bytes || !device_ms) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  *launches = s->last_launches, *bytes = s->last_bytes, *device_ms = s->last_ms;
-  return VPT_OK;
-}
+int vpt_scene_update_instances(vpt_scene* s, const vpt_instance_edit* edit) { return edit_scene(s, edit, instance_update_apply); }
+int vpt_scene_update_shapes(vpt_scene* s, const vpt_shape_edit* edit) { return edit_scene(s, edit, shape_update_apply); }
 
 int vpt_last_wave_costs(vpt_scene* s, unsigned* ticks, int capacity, int* count) {
   if (!s || !count || capacity < 0 || (capacity > 0 && !ticks)) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");

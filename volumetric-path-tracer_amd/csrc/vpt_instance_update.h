@@ -4,16 +4,10 @@
 #include "vpt_bvh_rebuild.h"
 #include "vpt_resident.h"
 
-// what the render side of the handle takes over beside the stack sizes
-struct instance_update_result {
-  bool curves = false;           // some instanced shape of the new list holds points or lines (VPT_FEAT_CURVES)
-  bool lights_rebuilt = false;   // the light tables were made anew: light_prims and the medium records sit in fresh allocations
-};
-
 // Validates `edit` against the scene (nothing is written before it has passed), renumbers the instances on the current device and
 // gathers the new instance table, builds the scene BVH over it, decides the traversal limits from the new tree and the shapes' kept
 // ones (VPT_ERR_UNSUPPORTED: the scene is as it was), and only then swaps tables, counts and mirrors; the light tables follow through
-// light_update_apply.  stacks.rebuilt = false for an edit with all counts zero: nothing was launched or sent.  Returns after the
+// light_update_apply.  `out` is untouched by an edit with all counts zero: nothing was launched or sent.  Returns after the
 // device has finished; r.refit.ready is cleared, r.varying_media and r.light_features follow.  The caller runs the light setup and,
 // when the lights were rebuilt, the medium setup afterwards.
-int instance_update_apply(resident& r, const vpt_instance_edit& edit, bvh_rebuild_stacks& stacks, instance_update_result& result);
+int instance_update_apply(resident& r, const vpt_instance_edit& edit, edit_outcome& out);

@@ -22,9 +22,6 @@
 
 namespace {
 
-constexpr int BLOCK = 256;
-inline unsigned blocks_for(long long n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 // every old instance stays and keeps its record, until iu_mark_kernel says otherwise
 __global__ void iu_fill_kernel(int n_old, int* __restrict__ keep, int* __restrict__ set_src) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -72,15 +69,6 @@ __global__ void iu_gather_kernel(int n_old, int n_add, int n_kept, int n_set, co
   new_table[8 * to + part] = from[part];
 }
 
-#define IU_LAUNCH(r, kernel, n, ...)                                                     \
-  do {                                                                                   \
-    if ((n) > 0) {                                                                       \
-      hipLaunchKernelGGL(kernel, dim3(blocks_for(n)), dim3(BLOCK), 0, 0, __VA_ARGS__);   \
-      HIP_TRY(hipGetLastError());                                                        \
-      (r).last_launches++;                                                               \
-    }                                                                                    \
-  } while (0)
-
 // the record creation uploads for an instance (build_instances, vpt_scene_prep.cpp)
 DInstance record_of(const vpt_instance& in, int shape_flags) {
   DInstance d = {};
@@ -92,8 +80,7 @@ DInstance record_of(const vpt_instance& in, int shape_flags) {
 int validate_edit(const resident& r, const vpt_instance_edit& e) {
   const DScene&       d = r.d;
   const edit_mirrors& m = r.m;
-  static const char some = 0;   // check_ids wants a payload beside the ids: the removal list has none
-  if (int rc = check_ids("remove", e.num_remove, e.remove_ids, &some, d.num_instances)) return rc;
+  if (int rc = check_ids("remove", e.num_remove, e.remove_ids, d.num_instances)) return rc;
   if (int rc = check_ids("set", e.num_set, e.set_ids, e.set, d.num_instances)) return rc;
   REQUIRE(e.num_add >= 0 && (e.num_add == 0 || e.add), "edit: add list is null or has a negative count");
   REQUIRE((long long)d.num_instances - e.num_remove + e.num_add <= 0x7fffffffLL, "edit: more than 2^31 instances");
@@ -121,11 +108,10 @@ int validate_edit(const resident& r, const vpt_instance_edit& e) {
 
 }  // namespace
 
-int instance_update_apply(resident& r, const vpt_instance_edit& e, bvh_rebuild_stacks& stacks, instance_update_result& result) {
+int instance_update_apply(resident& r, const vpt_instance_edit& e, edit_outcome& out) {
   DScene&       d = r.d;
   host_mirrors& h = r.h;
   edit_mirrors& m = r.m;
-  stacks.rebuilt = false;
   if (int rc = validate_edit(r, e)) return rc;   // every refusal about the request happens here: nothing has been written
   if (e.num_remove == 0 && e.num_set == 0 && e.num_add == 0) return VPT_OK;
   if (int rc = begin_update(r)) return rc;
@@ -153,13 +139,11 @@ int instance_update_apply(resident& r, const vpt_instance_edit& e, bvh_rebuild_s
   std::vector<DInstance> records((size_t)n_staged);
   for (int i = 0; i < e.num_set; i++) records[(size_t)i] = record_of(e.set[i], m.shape_flags[(size_t)e.set[i].shape]);
   for (int i = 0; i < e.num_add; i++) records[(size_t)e.num_set + (size_t)i] = record_of(e.add[i], m.shape_flags[(size_t)e.add[i].shape]);
-  const size_t at_remove = 0, at_set = (at_remove + 4 * (size_t)e.num_remove + 15) & ~(size_t)15, at_records = (at_set + 4 * (size_t)e.num_set + 15) & ~(size_t)15;
-  std::vector<char> block(at_records + records.size() * sizeof(DInstance), 0);
-  if (e.num_remove) memcpy(block.data() + at_remove, e.remove_ids, 4 * (size_t)e.num_remove);
-  if (e.num_set) memcpy(block.data() + at_set, e.set_ids, 4 * (size_t)e.num_set);
-  if (n_staged) memcpy(block.data() + at_records, records.data(), records.size() * sizeof(DInstance));
+  staged_block pay;
+  const size_t at_remove = pay.add(e.remove_ids, 4 * (size_t)e.num_remove), at_set = pay.add(e.set_ids, 4 * (size_t)e.num_set);
+  const size_t at_records = pay.add(records.data(), records.size() * sizeof(DInstance));
   device_buffer d_block, d_keep, d_scan, d_set_src, d_new_of_old, d_scan_temp, n_instances;
-  if (int rc = send(r, d_block, block)) return rc;
+  if (int rc = send(r, d_block, pay.host)) return rc;
   if (int rc = d_keep.allocate(((size_t)n_old + 1) * sizeof(int))) return rc;
   if (int rc = d_scan.allocate(((size_t)n_old + 1) * sizeof(int))) return rc;
   if (int rc = d_set_src.allocate((size_t)n_old * sizeof(int))) return rc;
@@ -171,8 +155,8 @@ int instance_update_apply(resident& r, const vpt_instance_edit& e, bvh_rebuild_s
 
   // 1. renumbering: keep flags from the removal list, their exclusive scan = the new id of every survivor
   const char* staged = d_block.get<char>();
-  IU_LAUNCH(r, iu_fill_kernel, n_old, n_old, d_keep.get<int>(), d_set_src.get<int>());
-  IU_LAUNCH(r, iu_mark_kernel, e.num_remove + e.num_set, n_old, e.num_remove, (const int*)(staged + at_remove), e.num_set, (const int*)(staged + at_set), d_keep.get<int>(),
+  LAUNCH(r, iu_fill_kernel, n_old, n_old, d_keep.get<int>(), d_set_src.get<int>());
+  LAUNCH(r, iu_mark_kernel, e.num_remove + e.num_set, n_old, e.num_remove, (const int*)(staged + at_remove), e.num_set, (const int*)(staged + at_set), d_keep.get<int>(),
       d_set_src.get<int>());
   if (n_old > 0) {
     size_t scan_bytes = 0;
@@ -182,7 +166,7 @@ int instance_update_apply(resident& r, const vpt_instance_edit& e, bvh_rebuild_s
     r.last_launches++;
   }
   // 2. the new instance table: survivors gathered, set and added records from the staged block
-  IU_LAUNCH(r, iu_gather_kernel, 8LL * ((long long)n_old + e.num_add), n_old, e.num_add, n_kept, e.num_set, d_keep.get<int>(), d_scan.get<int>(), d_set_src.get<int>(),
+  LAUNCH(r, iu_gather_kernel, 8LL * ((long long)n_old + e.num_add), n_old, e.num_add, n_kept, e.num_set, d_keep.get<int>(), d_scan.get<int>(), d_set_src.get<int>(),
       (const float4*)d.instances, (const float4*)(staged + at_records), n_instances.get<float4>(), d_new_of_old.get<int>());
 
   // 3. the scene BVH over ALL instances of the new list, the read-back of its nodes and primitive order, and the traversal limits by
@@ -209,21 +193,19 @@ int instance_update_apply(resident& r, const vpt_instance_edit& e, bvh_rebuild_s
   scene_level_swap(r, lv, t);
   h.inst_shape = inst_shape, m.inst_material = inst_material, m.inst_flags = inst_flags;
   m.textured.assign((size_t)d.num_materials, 0);
-  result.curves = false;
+  out.curves = false;
   for (int i = 0; i < n_new; i++) {
     m.textured[(size_t)inst_material[(size_t)i]] = 1;
-    result.curves = result.curves || (inst_flags[(size_t)i] & (VPT_SHP_POINTS | VPT_SHP_LINES)) != 0;
+    out.curves = out.curves || (inst_flags[(size_t)i] & (VPT_SHP_POINTS | VPT_SHP_LINES)) != 0;
   }
   r.varying_media = prep_media_vary(m.materials.data(), d.num_materials, m.inst_material.data(), m.inst_flags.data(), n_new);
-  stacks.rebuilt = true, stacks.stack_cap = t.stack_cap, stacks.stack_lds4 = t.stack_lds4, stacks.stack_spill4 = t.stack_spill4;
+  out.changed = out.topology = true, out.stack_cap = t.stack_cap, out.stack_lds4 = t.stack_lds4, out.stack_spill4 = t.stack_spill4;
 
   // 4. the lights of the new list: a survivor keeps its CDF and search structures under its new id
   const vpt_scene_edit none = {};
-  if (int rc = light_update_apply(r, none, &result.lights_rebuilt, nullptr, nullptr, &light_old_of_new)) return rc;
-  if (!result.lights_rebuilt)   // the same lights under the same ids: a `set` may still have moved one
+  if (int rc = light_update_apply(r, none, &out.lights_rebuilt, nullptr, nullptr, &light_old_of_new)) return rc;
+  if (!out.lights_rebuilt)   // the same lights under the same ids: a `set` may still have moved one
     if (int rc = upd_light_records(r, d.shapes)) return rc;
-  HIP_TRY(hipEventRecord(r.upd_ev1, 0));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipEventElapsedTime(&r.last_ms, r.upd_ev0, r.upd_ev1));
-  return VPT_OK;
+  if (int rc = mark_end(r)) return rc;
+  return finish_update(r);
 }

@@ -176,15 +176,6 @@ __global__ void lit_records_kernel(float4* __restrict__ rec, const vpt_light* __
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-constexpr int BLOCK = 256;
-inline unsigned blocks_for(long long n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
-#define LAUNCHED(u)                \
-  do {                             \
-    HIP_TRY(hipGetLastError());    \
-    (u).last_launches++;           \
-  } while (0)
-
 // The layout build_lights gives the index of an n-entry CDF that starts at `at` of the pool: the level offsets and sizes, and where
 // the pool continues.  false: no index (more than 8 levels).
 bool index_layout(long long n, long long at, DCdfIndex& ix, index_fill& f) {
@@ -202,10 +193,6 @@ bool index_layout(long long n, long long at, DCdfIndex& ix, index_fill& f) {
   return true;
 }
 
-int move(void* to, const void* from, size_t bytes) {
-  if (bytes) HIP_TRY(hipMemcpy(to, from, bytes, hipMemcpyDeviceToDevice));
-  return VPT_OK;
-}
 struct entry {   // one light of the new list
   vpt_light l;
   int  from;        // its place in the old list, -1: new
@@ -290,10 +277,10 @@ int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, cons
       jobs.push_back({en.l.cdf_offset, sh.elem_offset, sh.vertex_offset, sh.num_elems, sh.is_triangles ? JOB_TRIANGLES : JOB_QUADS});
       job_light.push_back(l);
     } else if (en.l.cdf_len == 0) {   // an environment without a texture
-    } else if (int rc = move(cdf + en.l.cdf_offset, d.light_cdf + old[(size_t)en.from].cdf_offset, (size_t)en.l.cdf_len * sizeof(float))) return rc;
+    } else if (int rc = copy_on_device(cdf + en.l.cdf_offset, d.light_cdf + old[(size_t)en.from].cdf_offset, (size_t)en.l.cdf_len * sizeof(float))) return rc;
   }
   const int njobs = (int)jobs.size();
-  std::vector<job_result> results((size_t)njobs);
+  std::vector<job_result> results;
   if (njobs > 0) {
     if (int rc = send(r, r.d_jobs, jobs)) return rc;
     if (int rc = r.d_result.allocate((size_t)njobs * sizeof(job_result))) return rc;
@@ -311,11 +298,12 @@ int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, cons
       if (jobs[(size_t)k].kind == JOB_TEXELS) {
         if (int rc = launch_texel_weights(r, (*envs)[(size_t)env_of[(size_t)job_light[(size_t)k]]], cdf + jobs[(size_t)k].cdf_offset)) return rc;
       }
-    if (getenv("VPT_LIGHTS_PLAIN")) hipLaunchKernelGGL(lit_scan_plain_kernel, dim3(blocks_for(njobs)), dim3(BLOCK), 0, 0, d_jobs, njobs, cdf, r.d_result.get<job_result>());
-    else hipLaunchKernelGGL(lit_scan_wave_kernel, dim3((unsigned)njobs), dim3(64), 0, 0, d_jobs, cdf, r.d_result.get<job_result>());
-    LAUNCHED(r);
-    HIP_TRY(hipMemcpy(results.data(), r.d_result.get(), results.size() * sizeof(job_result), hipMemcpyDeviceToHost));
-    r.last_bytes += (long long)(results.size() * sizeof(job_result));
+    if (getenv("VPT_LIGHTS_PLAIN")) LAUNCH(r, lit_scan_plain_kernel, njobs, d_jobs, njobs, cdf, r.d_result.get<job_result>());
+    else {
+      hipLaunchKernelGGL(lit_scan_wave_kernel, dim3((unsigned)njobs), dim3(64), 0, 0, d_jobs, cdf, r.d_result.get<job_result>());
+      LAUNCHED(r);
+    }
+    if (int rc = fetch(r, results, r.d_result.get(), (size_t)njobs)) return rc;
   }
 
   // 3. the search structures: a light whose CDF moved keeps its index with the offsets rebased, a recomputed one gets build_lights'
@@ -356,16 +344,12 @@ int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, cons
     float* pool  = pool_buf.get<float>();
     int2*  guide = guide_buf.get<int2>() + ix.guide_offset;
     if (en.recompute) {
-      hipLaunchKernelGGL(lit_index_levels_kernel, dim3(blocks_for(f.end - f.offset[0])), dim3(BLOCK), 0, 0, pool, f, cdf + en.l.cdf_offset, en.l.cdf_len);
-      LAUNCHED(r);
-      if (ix.guide_buckets > 0) {
-        hipLaunchKernelGGL(lit_guide_kernel, dim3(blocks_for(ix.guide_buckets)), dim3(BLOCK), 0, 0, guide, ix.guide_buckets, ix.guide_scale, cdf + en.l.cdf_offset, en.l.cdf_len);
-        LAUNCHED(r);
-      }
+      LAUNCH(r, lit_index_levels_kernel, f.end - f.offset[0], pool, f, cdf + en.l.cdf_offset, en.l.cdf_len);
+      LAUNCH(r, lit_guide_kernel, ix.guide_buckets, guide, ix.guide_buckets, ix.guide_scale, cdf + en.l.cdf_offset, en.l.cdf_len);
     } else {
       const DCdfIndex& was = u.light_index[(size_t)en.from];
-      if (int rc = move(pool + f.offset[0], d.light_index_pool + was.offset[0], (size_t)(f.end - f.offset[0]) * sizeof(float))) return rc;
-      if (int rc = move(guide, d.light_guide + was.guide_offset, (size_t)ix.guide_buckets * sizeof(int2))) return rc;
+      if (int rc = copy_on_device(pool + f.offset[0], d.light_index_pool + was.offset[0], (size_t)(f.end - f.offset[0]) * sizeof(float))) return rc;
+      if (int rc = copy_on_device(guide, d.light_guide + was.guide_offset, (size_t)ix.guide_buckets * sizeof(int2))) return rc;
     }
   }
 
@@ -384,12 +368,8 @@ int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, cons
     if (env_of[(size_t)l] >= 0) {
       if (int rc = send(r, rec_buf.get<float4>() + 8 * (size_t)l, (*envs)[(size_t)env_of[(size_t)l]].record, 8)) return rc;
     } else if (list[(size_t)l].l.instance < 0 && list[(size_t)l].l.sdf < 0)
-      if (int rc = move(rec_buf.get<float4>() + 8 * (size_t)l, d.light_rec + 8 * (size_t)list[(size_t)l].from, 8 * sizeof(float4))) return rc;
-  if (nl > 0) {
-    hipLaunchKernelGGL(lit_records_kernel, dim3(blocks_for(nl)), dim3(BLOCK), 0, 0, rec_buf.get<float4>(), lights_buf.get<vpt_light>(), r.d_tags.get<int>(), nl, cdf,
-        d.instances, d.shapes, envs ? 1 : 0);
-    LAUNCHED(r);
-  }
+      if (int rc = copy_on_device(rec_buf.get<float4>() + 8 * (size_t)l, d.light_rec + 8 * (size_t)list[(size_t)l].from, 8 * sizeof(float4))) return rc;
+  LAUNCH(r, lit_records_kernel, nl, rec_buf.get<float4>(), lights_buf.get<vpt_light>(), r.d_tags.get<int>(), nl, cdf, d.instances, d.shapes, envs ? 1 : 0);
   HIP_TRY(hipDeviceSynchronize());   // nothing reads the old tables any more
 
   // 5. the handle

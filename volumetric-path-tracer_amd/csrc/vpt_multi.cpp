@@ -255,6 +255,15 @@ void download_part(vpt_multi* m, int i, float* image_rgba, int32_t* hits, uint64
   }
   p.mirror_sum = part_checksum(p, image_rgba, hits, rng), p.mirrored = true;
 }
+// One edit on every device.  Every device holds the same scene and validation is the same on each, so the first one's refusal is
+// everyone's: an edit the first device refuses has changed none.
+template <typename Edit, typename F>
+int edit_parts(vpt_multi* m, const Edit* edit, F f) {
+  if (!m || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  for (auto& p : m->parts)
+    if (int rc = f(p.scene, edit)) return rc;
+  return VPT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -316,54 +325,16 @@ void vpt_multi_destroy(vpt_multi* m) {
   delete m;
 }
 
-int vpt_multi_update(vpt_multi* m, const vpt_scene_edit* edit) {
-  if (!m || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  // every device holds the same scene: an edit the first one refuses has changed none
-  for (auto& p : m->parts)
-    if (int rc = vpt_scene_update(p.scene, edit)) return rc;
-  return VPT_OK;
-}
-
-int vpt_multi_update_lights(vpt_multi* m, const vpt_scene_edit* edit) {
-  if (!m || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  for (auto& p : m->parts)   // as vpt_multi_update: validation is the same on every device
-    if (int rc = vpt_scene_update_lights(p.scene, edit)) return rc;
-  return VPT_OK;
-}
-
-int vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit) {
-  if (!m || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  for (auto& p : m->parts)   // as vpt_multi_update: validation is the same on every device
-    if (int rc = vpt_scene_update_textures(p.scene, edit)) return rc;
-  return VPT_OK;
-}
-
-int vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit) {
-  if (!m || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  for (auto& p : m->parts)   // as vpt_multi_update: validation is the same on every device
-    if (int rc = vpt_scene_update_volumes(p.scene, edit)) return rc;
-  return VPT_OK;
-}
-
+int vpt_multi_update(vpt_multi* m, const vpt_scene_edit* edit) { return edit_parts(m, edit, vpt_scene_update); }
+int vpt_multi_update_lights(vpt_multi* m, const vpt_scene_edit* edit) { return edit_parts(m, edit, vpt_scene_update_lights); }
+int vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit) { return edit_parts(m, edit, vpt_scene_update_textures); }
+int vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit) { return edit_parts(m, edit, vpt_scene_update_volumes); }
 int vpt_multi_rebuild_bvh(vpt_multi* m, const vpt_bvh_rebuild* what) { return vpt_multi_rebuild_bvh_quality(m, what, VPT_BVH_MIDDLE); }
 int vpt_multi_rebuild_bvh_quality(vpt_multi* m, const vpt_bvh_rebuild* what, int quality) {
-  if (!m || !what) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  for (auto& p : m->parts)   // as vpt_multi_update: every device holds the same scene, so the first one's refusal is everyone's
-    if (int rc = vpt_scene_rebuild_bvh_quality(p.scene, what, quality)) return rc;
-  return VPT_OK;
+  return edit_parts(m, what, [quality](vpt_scene* s, const vpt_bvh_rebuild* w) { return vpt_scene_rebuild_bvh_quality(s, w, quality); });
 }
-int vpt_multi_update_instances(vpt_multi* m, const vpt_instance_edit* edit) {
-  if (!m || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  for (auto& p : m->parts)   // as vpt_multi_update: every device holds the same scene, so the first one's refusal is everyone's
-    if (int rc = vpt_scene_update_instances(p.scene, edit)) return rc;
-  return VPT_OK;
-}
-int vpt_multi_update_shapes(vpt_multi* m, const vpt_shape_edit* edit) {
-  if (!m || !edit) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  for (auto& p : m->parts)   // as vpt_multi_update: every device holds the same scene, so the first one's refusal is everyone's
-    if (int rc = vpt_scene_update_shapes(p.scene, edit)) return rc;
-  return VPT_OK;
-}
+int vpt_multi_update_instances(vpt_multi* m, const vpt_instance_edit* edit) { return edit_parts(m, edit, vpt_scene_update_instances); }
+int vpt_multi_update_shapes(vpt_multi* m, const vpt_shape_edit* edit) { return edit_parts(m, edit, vpt_scene_update_shapes); }
 
 int vpt_multi_device_count(const vpt_multi* m) { return m ? (int)m->parts.size() : 0; }
 

@@ -1,6 +1,7 @@
 // vpt_resident.h — the part of a vpt_scene that the edits of a resident scene work on (include/vpt.h: vpt_scene_update, _lights,
 // _textures, _volumes, and vpt_scene_rebuild_bvh): the tables on the device, their host mirrors, and what an edit keeps between calls.  vpt_capi.hip's
-// vpt_scene is a `resident` plus its render side (schedule, staging, stacks); the four update units see only this.
+// vpt_scene is a `resident` plus its render side (schedule, staging, stacks); the update units and the read-backs of
+// vpt_scene_inspect.hip see only this.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -58,3 +59,16 @@ struct resident {
   float      last_ms       = 0;   // device time between the two events (stream 0)
   hipEvent_t upd_ev0 = nullptr, upd_ev1 = nullptr;   // made by the first edit, destroyed by vpt_scene_destroy
 };
+
+// What an edit did that the render side of the handle must follow (vpt_capi.hip: edit_scene, which hands it to the unit's *_apply).
+// The stacks and `curves` start as the handle's own values: a unit that leaves them alone leaves them as they are.
+struct edit_outcome {
+  bool changed        = false;   // false: nothing was launched or sent, the counters of vpt_scene_update_stats are the last edit's
+  bool lights_rebuilt = false;   // the light tables were made anew: light_prims and the medium records sit in fresh allocations
+  bool topology       = false;   // trees or lists were replaced, not refitted: the four values below are the new scene's
+  int  stack_cap, stack_lds4, stack_spill4;   // the traversal stacks (vpt_scene_prep.h: prep_quad_nodes_and_stacks)
+  bool curves;                   // some instanced shape holds points or lines (VPT_FEAT_CURVES)
+};
+
+// the resident part of a handle (not null), for a unit that sees no more of it: vpt_capi.hip defines it
+const resident& resident_of(const vpt_scene* s);

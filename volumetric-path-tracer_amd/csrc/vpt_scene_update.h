@@ -7,7 +7,8 @@
 // stream 0; returns after the device has finished.  r.d.scene_root_*, the mirrors of what was edited and r.varying_media follow.
 // lights: the caller rebuilds the light tables afterwards (vpt_scene_update_lights, vpt_light_update.h), so an emission that
 // switches between zero and non-zero and moved vertices of a light's shape pass validation.
-int scene_update_apply(resident& r, const vpt_scene_edit& edit, bool lights = false);
+// out.changed: true for every edit that passes validation, one without entries included - the counters of vpt_scene_update_stats start again.
+int scene_update_apply(resident& r, const vpt_scene_edit& edit, edit_outcome& out, bool lights = false);
 
 // Pieces of the refit that vpt_scene_rebuild_bvh (vpt_bvh_rebuild.hip) runs on tables it has made and not yet handed to the scene:
 // the same kernels, launched on stream 0 and counted in r.last_launches.  `shapes`, `shape_nodes`, `enter`: device tables of the

@@ -229,9 +229,6 @@ __global__ void upd_light_records_kernel(float4* __restrict__ light_rec, const v
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-constexpr int BLOCK = 256;
-inline unsigned blocks_for(long long n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 // internal nodes by depth.  validate() made every child index larger than its parent's, so one forward pass gives every depth.
 void make_levels(const vpt_bvh_node* nodes, int count, bvh_levels& lv, std::vector<int>& order) {
   lv.first.clear(), lv.offset = (long long)order.size();
@@ -329,27 +326,9 @@ int validate_edit(const resident& r, const vpt_scene_edit& e, bool lights) {
   return VPT_OK;
 }
 
-#define LAUNCH(u, kernel, n, ...)                                                                     \
-  do {                                                                                                \
-    if ((n) > 0) {                                                                                    \
-      hipLaunchKernelGGL(kernel, dim3(blocks_for(n)), dim3(BLOCK), 0, 0, __VA_ARGS__);                \
-      HIP_TRY(hipGetLastError());                                                                     \
-      (u).last_launches++;                                                                            \
-    }                                                                                                 \
-  } while (0)
-
-// The edit's bulk payload (moved vertices, instance frames) goes to the device in ONE copy: collected at 16-byte aligned offsets of a
-// host block, sent to the staging buffer, read by the scatter kernels that follow on stream 0 - no synchronisation in between.
-struct payload {
-  std::vector<char> host;
-  size_t add(const void* src, size_t bytes) {
-    const size_t at = (host.size() + 15) & ~(size_t)15;
-    host.resize(at + bytes);
-    memcpy(host.data() + at, src, bytes);
-    return at;
-  }
-};
-int stage(resident& u, const payload& p) {
+// The edit's bulk payload (moved vertices, instance frames) in its one block to the staging buffer the handle keeps: read by the
+// scatter kernels that follow on stream 0 - no synchronisation in between.
+int stage(resident& u, const staged_block& p) {
   if (p.host.size() > u.stage_bytes) {
     u.stage_bytes = 0;
     if (int rc = u.d_stage.allocate(p.host.size())) return rc;   // the call began with the device idle: nothing reads the buffer that goes
@@ -376,8 +355,7 @@ int refit_internal_levels(resident& u, float4* nodes, long long base, const bvh_
     top_levels t = {};
     for (int l = 0; l <= top; l++) t.first[l] = lv.first[(size_t)l];
     hipLaunchKernelGGL(upd_refit_top_kernel, dim3(1), dim3(UPD_TOP_WIDTH), 0, 0, nodes, base, order, t, top);
-    HIP_TRY(hipGetLastError());
-    u.last_launches++;
+    LAUNCHED(u);
   }
   return VPT_OK;
 }
@@ -407,8 +385,9 @@ int upd_light_records(resident& r, const DShape* shapes) {
   return VPT_OK;
 }
 
-int scene_update_apply(resident& r, const vpt_scene_edit& e, bool lights) {
+int scene_update_apply(resident& r, const vpt_scene_edit& e, edit_outcome& out, bool lights) {
   if (int rc = validate_edit(r, e, lights)) return rc;   // every refusal happens here: nothing has been written
+  out.changed = true;   // (an edit without entries too: it starts the counters again)
   const bool refit = e.num_instances > 0 || e.num_shapes > 0;
   if (refit && !r.refit.ready)
     if (int rc = refit_tables_init(r, r.refit)) return rc;
@@ -443,7 +422,7 @@ int scene_update_apply(resident& r, const vpt_scene_edit& e, bool lights) {
   if (!refit) return VPT_OK;
 
   // the bulk payload in one copy: positions / normals of the edited shapes, frames of the edited instances
-  payload pay;
+  staged_block pay;
   std::vector<size_t> at_pos((size_t)e.num_shapes, 0), at_nrm((size_t)e.num_shapes, 0);
   for (int i = 0; i < e.num_shapes; i++) {
     const size_t bytes = (size_t)h.shape_vertices[(size_t)e.shape_ids[i]] * 12;
@@ -490,14 +469,12 @@ int scene_update_apply(resident& r, const vpt_scene_edit& e, bool lights) {
   LAUNCH(r, upd_refit_scene_leaves_kernel, d.num_scene_nodes, scene_nodes, d.num_scene_nodes, d.scene_prims, u.d_inst_box.get<float4>());
   if (int rc = refit_internal_levels(r, scene_nodes, 0, u.scene_levels)) return rc;
   LAUNCH(r, upd_quad_gather_kernel, u.scene_quads, mut(d.scene_wnodes), u.d_quad_slots.get<int4>(), (int)u.scene_quads, d.scene_nodes, 0LL);
-  HIP_TRY(hipEventRecord(r.upd_ev1, 0));
+  if (int rc = mark_end(r)) return rc;
   if (d.num_scene_nodes > 0) {   // the six scene_root_* floats the kernels receive by value
     vpt_bvh_node root;
     HIP_TRY(hipMemcpy(&root, d.scene_nodes, sizeof(root), hipMemcpyDeviceToHost));
     d.scene_root_lo_x = root.bbox_min[0], d.scene_root_lo_y = root.bbox_min[1], d.scene_root_lo_z = root.bbox_min[2];
     d.scene_root_hi_x = root.bbox_max[0], d.scene_root_hi_y = root.bbox_max[1], d.scene_root_hi_z = root.bbox_max[2];
   }
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipEventElapsedTime(&r.last_ms, r.upd_ev0, r.upd_ev1));
-  return VPT_OK;
+  return finish_update(r);
 }

@@ -4,17 +4,11 @@
 #include "vpt_bvh_rebuild.h"
 #include "vpt_resident.h"
 
-// what the render side of the handle takes over beside the stack sizes
-struct shape_update_result {
-  bool curves = false;           // some instanced shape of the new list holds points or lines (VPT_FEAT_CURVES)
-  bool lights_rebuilt = false;   // the light tables were made anew: light_prims and the medium records sit in fresh allocations
-};
-
 // Validates `edit` against the scene (nothing is written before it has passed), lays the pools out for the new shape list, moves the
 // untouched shapes' parts device to device, makes vertices, elements, trees and leaf records of the `set` and added shapes on the
 // device, decides the traversal limits from the new trees and what the handle keeps of the others (VPT_ERR_UNSUPPORTED: the scene is
-// as it was), and only then swaps tables, counts and mirrors; the light tables follow through light_update_apply.  stacks.rebuilt =
-// false for an edit with all counts zero: nothing was launched or sent.  Returns after the device has finished; r.refit.ready is
+// as it was), and only then swaps tables, counts and mirrors; the light tables follow through light_update_apply.  `out` is
+// untouched by an edit with all counts zero: nothing was launched or sent.  Returns after the device has finished; r.refit.ready is
 // cleared, r.varying_media and r.light_features follow.  The caller runs the light setup and, when the lights were rebuilt, the
 // medium setup afterwards.
-int shape_update_apply(resident& r, const vpt_shape_edit& edit, bvh_rebuild_stacks& stacks, shape_update_result& result);
+int shape_update_apply(resident& r, const vpt_shape_edit& edit, edit_outcome& out);

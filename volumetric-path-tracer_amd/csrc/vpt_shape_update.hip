@@ -25,9 +25,6 @@
 
 namespace {
 
-constexpr int BLOCK = 256;
-inline unsigned blocks_for(long long n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 enum { SU_QUADS = 0, SU_TRIANGLES = 1, SU_POINTS = 2, SU_LINES = 3 };   // the form of a shape's index list
 
 // ---- kernels --------------------------------------------------------------------------------------------------------------
@@ -147,15 +144,6 @@ __global__ void su_instance_shapes_kernel(DInstance* __restrict__ instances, int
   instances[i].shape = m.x, instances[i].shape_flags = m.y;
 }
 
-#define SU_LAUNCH(r, kernel, n, ...)                                                     \
-  do {                                                                                   \
-    if ((n) > 0) {                                                                       \
-      hipLaunchKernelGGL(kernel, dim3(blocks_for(n)), dim3(BLOCK), 0, 0, __VA_ARGS__);   \
-      HIP_TRY(hipGetLastError());                                                        \
-      (r).last_launches++;                                                               \
-    }                                                                                    \
-  } while (0)
-
 // ---- host -----------------------------------------------------------------------------------------------------------------
 struct mesh {   // one `set` or added shape: what the edit says of it, and where its arrays sit in the staged block
   const vpt_shape_data* s = nullptr;
@@ -168,27 +156,6 @@ struct mesh {   // one `set` or added shape: what the edit says of it, and where
   std::vector<int>          prims;
 };
 
-struct block {   // the payload: every array at a 16-byte aligned offset of one host block
-  std::vector<char> host;
-  size_t add(const void* src, size_t bytes) {
-    const size_t at = (host.size() + 15) & ~(size_t)15;
-    host.resize(at + bytes);
-    if (bytes) memcpy(host.data() + at, src, bytes);
-    return at;
-  }
-};
-
-template <typename T>
-int fetch(resident& r, std::vector<T>& out, const void* dev, size_t count) {   // device to host, counted
-  out.resize(count);
-  if (count) HIP_TRY(hipMemcpy(out.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost));
-  r.last_bytes += (long long)(count * sizeof(T));
-  return VPT_OK;
-}
-int copy_on_device(void* to, const void* from, size_t bytes) {
-  if (bytes) HIP_TRY(hipMemcpy(to, from, bytes, hipMemcpyDeviceToDevice));
-  return VPT_OK;
-}
 
 // validate()'s rules for one shape of the edit
 int check_mesh(const vpt_shape_data& s, const char* list, int i, mesh& m) {
@@ -220,8 +187,7 @@ struct shape_sizes { long long len[P_COUNT]; };
 int validate_edit(const resident& r, const vpt_shape_edit& e, std::vector<mesh>& meshes) {
   const DScene&       d = r.d;
   const host_mirrors& h = r.h;
-  static const char some = 0;   // check_ids wants a payload beside the ids: the removal list has none
-  if (int rc = check_ids("remove", e.num_remove, e.remove_ids, &some, d.num_shapes)) return rc;
+  if (int rc = check_ids("remove", e.num_remove, e.remove_ids, d.num_shapes)) return rc;
   if (int rc = check_ids("set", e.num_set, e.set_ids, e.set, d.num_shapes)) return rc;
   REQUIRE(e.num_add >= 0 && (e.num_add == 0 || e.add), "edit: add list is null or has a negative count");
   REQUIRE((long long)d.num_shapes - e.num_remove + e.num_add <= 0x7fffffffLL, "edit: more than 2^31 shapes");
@@ -240,11 +206,10 @@ int validate_edit(const resident& r, const vpt_shape_edit& e, std::vector<mesh>&
 
 }  // namespace
 
-int shape_update_apply(resident& r, const vpt_shape_edit& e, bvh_rebuild_stacks& stacks, shape_update_result& result) {
+int shape_update_apply(resident& r, const vpt_shape_edit& e, edit_outcome& out) {
   DScene&       d = r.d;
   host_mirrors& h = r.h;
   edit_mirrors& m = r.m;
-  stacks.rebuilt = false;
   std::vector<mesh> meshes;
   if (int rc = validate_edit(r, e, meshes)) return rc;   // every refusal about the request happens here: nothing has been written
   if (e.num_remove == 0 && e.num_set == 0 && e.num_add == 0) return VPT_OK;
@@ -316,7 +281,7 @@ int shape_update_apply(resident& r, const vpt_shape_edit& e, bvh_rebuild_stacks&
   }
 
   // ---- the payload of the `set` and added shapes in one copy ------------------------------------------------------------------------
-  block pay;
+  staged_block pay;
   int   most_elems = 0;
   for (mesh& ms : meshes) {
     const vpt_shape_data& s  = *ms.s;
@@ -380,20 +345,20 @@ int shape_update_apply(resident& r, const vpt_shape_edit& e, bvh_rebuild_stacks&
     const vpt_shape_data& s  = *ms.s;
     const DShape&         o  = shapes[(size_t)j];
     const int             nv = s.num_vertices, n = ms.num_elems;
-    SU_LAUNCH(r, su_float3_kernel, nv, n_positions.get<float4>() + o.vertex_offset, (const float*)(staged + ms.at_pos), nv);
-    if (ms.flags & VPT_SHP_NORMALS) SU_LAUNCH(r, su_float3_kernel, nv, n_normals.get<float4>() + o.normal_offset, (const float*)(staged + ms.at_nrm), nv);
+    LAUNCH(r, su_float3_kernel, nv, n_positions.get<float4>() + o.vertex_offset, (const float*)(staged + ms.at_pos), nv);
+    if (ms.flags & VPT_SHP_NORMALS) LAUNCH(r, su_float3_kernel, nv, n_normals.get<float4>() + o.normal_offset, (const float*)(staged + ms.at_nrm), nv);
     if (ms.flags & VPT_SHP_TEXCOORDS)
       if (int rc = copy_on_device(n_texcoords.get<float2>() + o.texcoord_offset, staged + ms.at_tc, 8 * (size_t)nv)) return rc;
     if (ms.flags & VPT_SHP_COLORS)
       if (int rc = copy_on_device(n_colors.get<float4>() + o.color_offset, staged + ms.at_col, 16 * (size_t)nv)) return rc;
     const float* rad = ms.kind ? (const float*)(staged + ms.at_rad) : nullptr;
-    SU_LAUNCH(r, su_elems_kernel, n, n_elems.get<int4>() + o.elem_offset, (const int*)(staged + ms.at_idx), n, ms.form);
-    SU_LAUNCH(r, su_element_boxes_kernel, n, n, n_elems.get<int4>() + o.elem_offset, n_positions.get<float4>() + o.vertex_offset, rad, ms.kind, d_boxes.get<float>());
+    LAUNCH(r, su_elems_kernel, n, n_elems.get<int4>() + o.elem_offset, (const int*)(staged + ms.at_idx), n, ms.form);
+    LAUNCH(r, su_element_boxes_kernel, n, n, n_elems.get<int4>() + o.elem_offset, n_positions.get<float4>() + o.vertex_offset, rad, ms.kind, d_boxes.get<float>());
     if (int rc = bvh_build_core(core, d_boxes.get<float>(), 6, n, &ms.count, &r.last_launches)) return rc;
     if (int rc = ms.nodes.allocate((size_t)ms.count * sizeof(vpt_bvh_node))) return rc;
     if (int rc = copy_on_device(ms.nodes.get(), core.nodes(), (size_t)ms.count * sizeof(vpt_bvh_node))) return rc;
     const su_shape on_device = {n, ms.kind, o.elem_offset, o.leaf_offset, o.vertex_offset, o.normal_offset, o.texcoord_offset};
-    SU_LAUNCH(r, su_leaf_records_kernel, 4LL * n, on_device, core.primitives(), n_elems.get<int4>(), n_positions.get<float4>(), n_normals.get<float4>(),
+    LAUNCH(r, su_leaf_records_kernel, 4LL * n, on_device, core.primitives(), n_elems.get<int4>(), n_positions.get<float4>(), n_normals.get<float4>(),
         n_texcoords.get<float2>(), rad, n_leaf_prims.get<float4>(), n_leaf_attrs.get<float4>(), compact ? n_tri_prims.get<float4>() : nullptr,
         compact ? n_tri_attrs.get<float4>() : nullptr);
     if (int rc = fetch(r, ms.h_nodes, ms.nodes.get(), (size_t)ms.count)) return rc;
@@ -409,7 +374,7 @@ int shape_update_apply(resident& r, const vpt_shape_edit& e, bvh_rebuild_stacks&
   if (compact && !compact_kept)
     for (const shape_run& run : runs) {
       const long long first = new_at[P_ELEMS][(size_t)run.first_new], count = new_at[P_ELEMS][(size_t)run.first_new + (size_t)run.count] - first;
-      SU_LAUNCH(r, su_compact_kernel, 4 * count, first, count, n_leaf_prims.get<float4>(), n_leaf_attrs.get<float4>(), n_tri_prims.get<float4>(), n_tri_attrs.get<float4>());
+      LAUNCH(r, su_compact_kernel, 4 * count, first, count, n_leaf_prims.get<float4>(), n_leaf_attrs.get<float4>(), n_tri_prims.get<float4>(), n_tri_attrs.get<float4>());
     }
 
   // ---- 4. the node pool at its new size: new trees and, device to device, the untouched ones ---------------------------------------
@@ -452,7 +417,7 @@ int shape_update_apply(resident& r, const vpt_shape_edit& e, bvh_rebuild_stacks&
   if (int rc = n_instances.allocate((size_t)ninst * sizeof(DInstance))) return rc;
   if (int rc = copy_on_device(n_instances.get(), d.instances, (size_t)ninst * sizeof(DInstance))) return rc;
   if (int rc = send(r, d_map, shape_map)) return rc;
-  SU_LAUNCH(r, su_instance_shapes_kernel, ninst, n_instances.get<DInstance>(), ninst, d_map.get<int2>(), n_old);
+  LAUNCH(r, su_instance_shapes_kernel, ninst, n_instances.get<DInstance>(), ninst, d_map.get<int2>(), n_old);
 
   const bool  scene_built = e.num_set > 0;
   scene_level lv;
@@ -553,22 +518,20 @@ int shape_update_apply(resident& r, const vpt_shape_edit& e, bvh_rebuild_stacks&
   }
   h.prim_slot = std::move(prim_slot), h.shape_elems = std::move(shape_elems), h.shape_elem_offset = std::move(shape_elem_offset), h.shape_vertices = std::move(shape_vertices);
   h.inst_shape = inst_shape, m.inst_flags = inst_flags, m.shapes = t.shapes, m.shape_flags = flags;
-  result.curves = false;
-  for (int i = 0; i < ninst; i++) result.curves = result.curves || (inst_flags[(size_t)i] & (VPT_SHP_POINTS | VPT_SHP_LINES)) != 0;
+  out.curves = false;
+  for (int i = 0; i < ninst; i++) out.curves = out.curves || (inst_flags[(size_t)i] & (VPT_SHP_POINTS | VPT_SHP_LINES)) != 0;
   r.varying_media = prep_media_vary(m.materials.data(), d.num_materials, m.inst_material.data(), m.inst_flags.data(), ninst);
-  stacks.rebuilt = true, stacks.stack_cap = t.stack_cap, stacks.stack_lds4 = t.stack_lds4, stacks.stack_spill4 = t.stack_spill4;
+  out.changed = out.topology = true, out.stack_cap = t.stack_cap, out.stack_lds4 = t.stack_lds4, out.stack_spill4 = t.stack_spill4;
 
   // ---- 6. the lights of the new scene: a light on a replaced shape gets a CDF of the new length and the kind of its new tree --------
   const vpt_scene_edit none = {};
-  if (int rc = light_update_apply(r, none, &result.lights_rebuilt, nullptr, nullptr, &light_old_of_new)) return rc;
-  if (!result.lights_rebuilt) {   // the same lights: their records name shapes, whose table is new
+  if (int rc = light_update_apply(r, none, &out.lights_rebuilt, nullptr, nullptr, &light_old_of_new)) return rc;
+  if (!out.lights_rebuilt) {   // the same lights: their records name shapes, whose table is new
     if (int rc = upd_light_records(r, d.shapes)) return rc;
     m.shape_lit.assign((size_t)n_new, 0);
     for (const vpt_light& l : m.lights)
       if (l.instance >= 0) m.shape_lit[(size_t)h.inst_shape[(size_t)l.instance]] = 1;
   }
-  HIP_TRY(hipEventRecord(r.upd_ev1, 0));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipEventElapsedTime(&r.last_ms, r.upd_ev0, r.upd_ev1));
-  return VPT_OK;
+  if (int rc = mark_end(r)) return rc;
+  return finish_update(r);
 }

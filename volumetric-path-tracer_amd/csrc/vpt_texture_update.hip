@@ -35,8 +35,7 @@ __global__ void tex_weights_byte_kernel(const uchar4* __restrict__ texels, const
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-constexpr int   BLOCK = 256;
-constexpr float pif   = (float)3.14159265358979323846;
+constexpr float pif = (float)3.14159265358979323846;
 
 int validate_edit(const DScene& d, const edit_mirrors& m, const vpt_texture_edit& e) {
   if (int rc = check_ids("environment", e.num_environments, e.environment_ids, e.environments, d.num_environments)) return rc;
@@ -74,20 +73,17 @@ int validate_edit(const DScene& d, const edit_mirrors& m, const vpt_texture_edit
 }  // namespace
 
 int launch_texel_weights(resident& r, const env_light& env, float* cdf) {
-  const int      n      = env.cdf_len;
-  const unsigned blocks = (unsigned)(((long long)n + BLOCK - 1) / BLOCK);
-  if (env.is_float) hipLaunchKernelGGL(tex_weights_float_kernel, dim3(blocks), dim3(BLOCK), 0, 0, (const float4*)env.texels, env.sin_row, env.width, n, cdf);
-  else hipLaunchKernelGGL(tex_weights_byte_kernel, dim3(blocks), dim3(BLOCK), 0, 0, (const uchar4*)env.texels, env.sin_row, env.width, n, cdf);
-  HIP_TRY(hipGetLastError());
-  r.last_launches++;
+  const int n = env.cdf_len;   // (> 0: validation refuses an emissive environment whose texture has no texels)
+  if (env.is_float) LAUNCH(r, tex_weights_float_kernel, n, (const float4*)env.texels, env.sin_row, env.width, n, cdf);
+  else LAUNCH(r, tex_weights_byte_kernel, n, (const uchar4*)env.texels, env.sin_row, env.width, n, cdf);
   return VPT_OK;
 }
 
-int texture_update_apply(resident& r, const vpt_texture_edit& e, bool* rebuilt) {
-  *rebuilt = false;
+int texture_update_apply(resident& r, const vpt_texture_edit& e, edit_outcome& out) {
   DScene&       d = r.d;
   edit_mirrors& m = r.m;
   if (int rc = validate_edit(d, m, e)) return rc;   // every refusal happens here: nothing has been written
+  out.changed = true;   // (an edit without entries too: it starts the counters again)
   if (int rc = begin_update(r)) return rc;
 
   // 1. textures: in place where the room is the same, else at the end of a pool that grows
@@ -171,11 +167,10 @@ int texture_update_apply(resident& r, const vpt_texture_edit& e, bool* rebuilt) 
         if (envs[k].recompute) envs[k].sin_row = r.d_sin.get<float>() + at[k];
     }
     HIP_TRY(hipEventRecord(r.upd_ev0, 0));
-    if (int rc = light_update_apply(r, vpt_scene_edit{}, rebuilt, &envs)) return rc;   // no vertex moved
-    HIP_TRY(hipEventRecord(r.upd_ev1, 0));
-    HIP_TRY(hipEventSynchronize(r.upd_ev1));
-    HIP_TRY(hipEventElapsedTime(&r.last_ms, r.upd_ev0, r.upd_ev1));
-    if (!*rebuilt)   // the list stays: of the records only the frames of a textured environment can have changed (build_lights)
+    if (int rc = light_update_apply(r, vpt_scene_edit{}, &out.lights_rebuilt, &envs)) return rc;   // no vertex moved
+    if (int rc = mark_end(r)) return rc;
+    if (int rc = finish_update(r)) return rc;
+    if (!out.lights_rebuilt)   // the list stays: of the records only the frames of a textured environment can have changed (build_lights)
       for (int l = 0; l < d.num_lights; l++) {
         const vpt_light& lt = m.lights[(size_t)l];
         if (lt.instance >= 0 || lt.sdf >= 0 || m.light_kind[(size_t)l] != VPT_LIGHT_ENV_TEX) continue;

@@ -5,6 +5,6 @@
 
 // Validates `edit` and prepares its bakes (nothing a scene owns is written before both have passed), then writes voxels, the three
 // small tables and every SDF record, and - when the SDF lights change - rebuilds the light tables through light_update_apply
-// (*rebuilt).  A voxel pool that grows is allocated anew and takes its predecessor's place in r.tables.  r's counters
+// (out.lights_rebuilt).  A voxel pool that grows is allocated anew and takes its predecessor's place in r.tables.  r's counters
 // (vpt_scene_update_stats) describe this call.  Stream 0 of r.device; the device has finished when the call returns.
-int volume_update_apply(resident& r, const vpt_volume_edit& edit, bool* rebuilt);
+int volume_update_apply(resident& r, const vpt_volume_edit& edit, edit_outcome& out);

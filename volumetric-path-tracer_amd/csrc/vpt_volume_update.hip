@@ -30,8 +30,6 @@ __global__ void vol_region_kernel(float* __restrict__ grid, int w, int h, int lo
   grid[at] = v;
 }
 
-constexpr int BLOCK = 256;
-
 // of dimensions already known to be >= 0 and to multiply to less than 2^31 (voxel_count_ok)
 long long product(const int32_t v[3]) { return (long long)v[0] * v[1] * v[2]; }
 // whd >= 0 with a product below 2^31, factor by factor: every partial product stays below 2^62, so nothing overflows on the way
@@ -92,8 +90,7 @@ int validate_edit(const DScene& d, const edit_mirrors& m, const vpt_volume_edit&
 
 }  // namespace
 
-int volume_update_apply(resident& r, const vpt_volume_edit& e, bool* rebuilt) {
-  *rebuilt = false;
+int volume_update_apply(resident& r, const vpt_volume_edit& e, edit_outcome& out) {
   DScene&       d = r.d;
   edit_mirrors& m = r.m;
   if (int rc = validate_edit(d, m, e)) return rc;
@@ -106,6 +103,7 @@ int volume_update_apply(resident& r, const vpt_volume_edit& e, bool* rebuilt) {
     bakes[(size_t)i] = std::make_unique<bake_job>();
     if (int rc = bake_prepare(r.device, e.volumes[i].bake, entry, *bakes[(size_t)i])) return rc;
   }
+  out.changed = true;   // (an edit without entries too: it starts the counters again and sends every SDF record)
   if (int rc = begin_update(r)) return rc;
 
   // 1. volumes: in place where whd stays, else at the end of a pool that grows
@@ -138,13 +136,11 @@ int volume_update_apply(resident& r, const vpt_volume_edit& e, bool* rebuilt) {
       continue;
     }
     const long long n = product(src.region_whd);
-    if (n == 0) continue;
-    hipLaunchKernelGGL(vol_region_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, 0, grid, v.whd[0], v.whd[1], src.region_lo[0], src.region_lo[1],
-        src.region_lo[2], src.region_whd[0], src.region_whd[1], (unsigned)n, src.mode, stage.get<float>() + src.offset);
-    HIP_TRY(hipGetLastError());
-    r.last_launches++, r.last_bytes += n * (long long)sizeof(float);
+    LAUNCH(r, vol_region_kernel, n, grid, v.whd[0], v.whd[1], src.region_lo[0], src.region_lo[1], src.region_lo[2], src.region_whd[0], src.region_whd[1], (unsigned)n,
+        src.mode, stage.get<float>() + src.offset);
+    r.last_bytes += n * (long long)sizeof(float);
   }
-  HIP_TRY(hipEventRecord(r.upd_ev1, 0));
+  if (int rc = mark_end(r)) return rc;
 
   // 2. the small tables as the edit leaves them, and every record from them
   std::vector<vpt_volume_instance> vol_instances = m.vol_instances;
@@ -174,11 +170,8 @@ int volume_update_apply(resident& r, const vpt_volume_edit& e, bool* rebuilt) {
 
   // 3. the lights: only when the SDF lights of the edited scene are others, or one of them has another whd
   if (lights_differ) {
-    if (int rc = light_update_apply(r, vpt_scene_edit{}, rebuilt, nullptr, &resized)) return rc;   // no vertex moved
-    HIP_TRY(hipEventRecord(r.upd_ev1, 0));
+    if (int rc = light_update_apply(r, vpt_scene_edit{}, &out.lights_rebuilt, nullptr, &resized)) return rc;   // no vertex moved
+    if (int rc = mark_end(r)) return rc;   // again: the time includes the rebuild
   }
-  HIP_TRY(hipEventSynchronize(r.upd_ev1));
-  HIP_TRY(hipEventElapsedTime(&r.last_ms, r.upd_ev0, r.upd_ev1));
-  HIP_TRY(hipDeviceSynchronize());
-  return VPT_OK;
+  return finish_update(r);
 }
