@@ -435,6 +435,19 @@ int advance_adaptive(vpt_session* s, int nsamples) {
   return tonemap_display(s);
 }
 
+// one of the edits of a resident scene - apply(scene, edit) is its vpt_scene_* entry point - then a reset
+template <class Edit, class Apply>
+int session_edit(vpt_session* s, const Edit* edit, Apply apply) {
+  REQUIRE(s && edit, "null argument");
+  begin_call(s);
+  if (int rc = apply(s->scene, edit)) return rc;   // a refused edit has changed nothing, here or there
+  int     launches = 0;
+  int64_t bytes    = 0;
+  float   ms       = 0;
+  if (vpt_scene_update_stats(s->scene, &launches, &bytes, &ms) == VPT_OK) s->launches += launches, s->up += bytes;
+  return reset(s, s->p);
+}
+
 }  // namespace
 
 extern "C" {
@@ -524,33 +537,16 @@ int vpt_session_set_display(vpt_session* s, const vpt_display_params* display) {
   return tonemap_display(s);
 }
 
-// one of the edits of a resident scene (which: 0 vpt_scene_update, 1 _lights, 2 _textures, 3 _volumes, 4 vpt_scene_rebuild_bvh,
-// 5 vpt_scene_update_instances, 6 vpt_scene_update_shapes), then a reset
-static int session_edit(vpt_session* s, const void* edit, int which, int quality = VPT_BVH_MIDDLE) {
-  REQUIRE(s && edit, "null argument");
-  begin_call(s);
-  if (int rc = which == 6 ? vpt_scene_update_shapes(s->scene, (const vpt_shape_edit*)edit)
-               : which == 5 ? vpt_scene_update_instances(s->scene, (const vpt_instance_edit*)edit)
-               : which == 4 ? vpt_scene_rebuild_bvh_quality(s->scene, (const vpt_bvh_rebuild*)edit, quality)
-               : which == 3 ? vpt_scene_update_volumes(s->scene, (const vpt_volume_edit*)edit)
-               : which == 2 ? vpt_scene_update_textures(s->scene, (const vpt_texture_edit*)edit)
-               : which == 1 ? vpt_scene_update_lights(s->scene, (const vpt_scene_edit*)edit)
-                            : vpt_scene_update(s->scene, (const vpt_scene_edit*)edit))
-    return rc;   // a refused edit has changed nothing, here or there
-  int     launches = 0;
-  int64_t bytes    = 0;
-  float   ms       = 0;
-  if (vpt_scene_update_stats(s->scene, &launches, &bytes, &ms) == VPT_OK) s->launches += launches, s->up += bytes;
-  return reset(s, s->p);
+int vpt_session_edit(vpt_session* s, const vpt_scene_edit* edit) { return session_edit(s, edit, vpt_scene_update); }
+int vpt_session_edit_lights(vpt_session* s, const vpt_scene_edit* edit) { return session_edit(s, edit, vpt_scene_update_lights); }
+int vpt_session_edit_textures(vpt_session* s, const vpt_texture_edit* edit) { return session_edit(s, edit, vpt_scene_update_textures); }
+int vpt_session_edit_volumes(vpt_session* s, const vpt_volume_edit* edit) { return session_edit(s, edit, vpt_scene_update_volumes); }
+int vpt_session_rebuild_bvh(vpt_session* s, const vpt_bvh_rebuild* what) { return vpt_session_rebuild_bvh_quality(s, what, VPT_BVH_MIDDLE); }
+int vpt_session_rebuild_bvh_quality(vpt_session* s, const vpt_bvh_rebuild* what, int quality) {
+  return session_edit(s, what, [quality](vpt_scene* scene, const vpt_bvh_rebuild* w) { return vpt_scene_rebuild_bvh_quality(scene, w, quality); });
 }
-int vpt_session_edit(vpt_session* s, const vpt_scene_edit* edit) { return session_edit(s, edit, 0); }
-int vpt_session_edit_lights(vpt_session* s, const vpt_scene_edit* edit) { return session_edit(s, edit, 1); }
-int vpt_session_edit_textures(vpt_session* s, const vpt_texture_edit* edit) { return session_edit(s, edit, 2); }
-int vpt_session_edit_volumes(vpt_session* s, const vpt_volume_edit* edit) { return session_edit(s, edit, 3); }
-int vpt_session_rebuild_bvh(vpt_session* s, const vpt_bvh_rebuild* what) { return session_edit(s, what, 4); }
-int vpt_session_rebuild_bvh_quality(vpt_session* s, const vpt_bvh_rebuild* what, int quality) { return session_edit(s, what, 4, quality); }
-int vpt_session_edit_instances(vpt_session* s, const vpt_instance_edit* edit) { return session_edit(s, edit, 5); }
-int vpt_session_edit_shapes(vpt_session* s, const vpt_shape_edit* edit) { return session_edit(s, edit, 6); }
+int vpt_session_edit_instances(vpt_session* s, const vpt_instance_edit* edit) { return session_edit(s, edit, vpt_scene_update_instances); }
+int vpt_session_edit_shapes(vpt_session* s, const vpt_shape_edit* edit) { return session_edit(s, edit, vpt_scene_update_shapes); }
 
 int vpt_session_get_display(vpt_session* s, uint8_t* rgba8, float* display_f) {
   REQUIRE(s, "null session");

@@ -1,0 +1,282 @@
+"""The edits of a resident scene as Python holds them - what HostScene's setters fill and update_*() hands out, what DeviceScene,
+MultiDeviceScene and RenderSession apply.  Every class has empty() and to_abi(): (the struct of include/vpt.h, the objects that keep
+the arrays it points into alive across the call)."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from ._abi import (INSTANCE, MESH_ELEMENTS, MESH_FLOATS, VOXELS_REPLACE, VptBakeDesc, VptBvhRebuild, VptCamera, VptEnvironment, VptError,
+                   VptInstanceEdit, VptMaterial, VptSceneEdit, VptSdf, VptShapeData, VptShapeEdit, VptTexture, VptTextureEdit, VptVolumeEdit,
+                   VptVolumeInstance, VptVolumeSource, _address)
+
+
+def mesh(positions, triangles=None, quads=None, points=None, lines=None, normals=None, texcoords=None, colors=None, radius=None) -> dict:
+    """one shape as vpt_shape_data takes it: a dictionary of contiguous float32 / int32 arrays, None (or empty) for what the shape has not"""
+    given = dict(positions=positions, triangles=triangles, quads=quads, points=points, lines=lines, normals=normals, texcoords=texcoords, colors=colors, radius=radius)
+    out = {}
+    for key, width in MESH_FLOATS.items():
+        a = given[key]
+        out[key] = None if a is None or len(a) == 0 else np.ascontiguousarray(a, np.float32).reshape((-1, width) if width else (-1,)).copy()
+    for key, width in MESH_ELEMENTS.items():
+        a = given[key]
+        out[key] = None if a is None or len(a) == 0 else np.ascontiguousarray(a, np.int32).reshape((-1, width) if width else (-1,)).copy()
+    return out
+
+
+class BvhRebuild:
+    """What vpt_scene_rebuild_bvh takes (include/vpt.h: vpt_bvh_rebuild): the shapes whose BVHs are built anew, and whether the scene
+    BVH is (it is whenever a shape is named).  HostScene.rebuild_bvh makes one; DeviceScene.rebuild_bvh / MultiDeviceScene.rebuild_bvh /
+    RenderSession.rebuild_bvh apply it.  quality: BVH_MIDDLE (0, the reference's highquality = false) or BVH_SAH (1, split_sah: the rule
+    at vpt_build_bvh_quality in include/vpt.h), carried to the device with the request."""
+
+    def __init__(self, shapes=(), scene: bool = True, *, quality: int = 0):
+        self.shapes, self.scene, self.quality = tuple(int(i) for i in shapes), bool(scene), int(quality)
+
+    def empty(self) -> bool:
+        return not self.shapes and not self.scene
+
+    def to_abi(self):
+        """(VptBvhRebuild, the array it points into: keep it alive across the call)"""
+        ids = (C.c_int32 * max(1, len(self.shapes)))(*self.shapes)
+        return VptBvhRebuild(len(self.shapes), C.cast(ids, C.POINTER(C.c_int32)) if self.shapes else None, int(self.scene)), ids
+
+
+# ---- the two list edits: remove / set / add over the instances or over the shapes ------------------------------------------------------
+class _ListEdit:
+    """`set`, a dictionary current id -> item that replaces those entries; `remove`, current ids erased after that (ids close up); `add`,
+    a list of items appended after the survivors.  A subclass says what an item is (_item), how items are packed into records
+    (_records), which struct takes them (ABI) and what besides the records has to stay alive (_kept)."""
+    ABI = None
+
+    def __init__(self, remove=(), set=None, add=()):
+        self.remove = tuple(int(i) for i in remove)
+        self.set = {int(k): self._item(v) for k, v in dict(set or {}).items()}
+        self.add = [self._item(v) for v in add]
+
+    def empty(self) -> bool:
+        return not (self.remove or self.set or self.add)
+
+    def _kept(self) -> list:
+        return []
+
+    def to_abi(self):
+        """(the struct, the arrays it points into: keep them alive across the call)"""
+        remove, set_ids = np.array(self.remove, np.int32), np.array(list(self.set.keys()), np.int32)
+        set_rec, add_rec = self._records(list(self.set.values())), self._records(self.add)
+        ptr = lambda a, n: _address(a) if n else None   # (a record array of no items still has one unused element)
+        abi = self.ABI(len(remove), ptr(remove, len(remove)), len(set_ids), ptr(set_ids, len(set_ids)), ptr(set_rec, len(set_ids)),
+                       len(self.add), ptr(add_rec, len(self.add)))
+        return abi, [remove, set_ids, set_rec, add_rec] + self._kept()
+
+
+class InstanceEdit(_ListEdit):
+    """What vpt_scene_update_instances takes (include/vpt.h: vpt_instance_edit): `set`, a dictionary current id -> (frame (12,) float32,
+    shape, material) that replaces those instances; `remove`, current ids erased after that (ids close up); `add`, a list of (frame,
+    shape, material) appended after the survivors.  HostScene.update_instances makes one; DeviceScene.update_instances /
+    MultiDeviceScene.update_instances / RenderSession.edit_instances apply it."""
+    ABI = VptInstanceEdit
+
+    @staticmethod
+    def _item(v):
+        return np.ascontiguousarray(v[0], np.float32).reshape(12).copy(), int(v[1]), int(v[2])
+
+    @staticmethod
+    def _records(items) -> np.ndarray:
+        out = np.zeros(len(items), INSTANCE)
+        for i, (frame, shape, material) in enumerate(items):
+            out[i] = (frame, shape, material)
+        return out
+
+
+class ShapeEdit(_ListEdit):
+    """What vpt_scene_update_shapes takes (include/vpt.h: vpt_shape_edit): `set`, a dictionary current id -> mesh (the dictionary mesh()
+    makes) that replaces those shapes whole; `remove`, current ids erased after that (ids close up, the instances' shape ids follow; no
+    instance may name a removed shape); `add`, a list of meshes appended after the survivors.  HostScene.update_shapes makes one;
+    DeviceScene.update_shapes / MultiDeviceScene.update_shapes / RenderSession.edit_shapes apply it.
+    Importing an object into a running scene is a ShapeEdit followed by an InstanceEdit: add_shape(...) returns the id the shape has after
+    update_shapes(); once that edit is handed out, add_instance(frame, id, material) and update_instances() put it in place."""
+    ABI = VptShapeEdit
+
+    @staticmethod
+    def _item(v):
+        return mesh(**v)
+
+    @staticmethod
+    def _records(meshes):
+        out = (VptShapeData * max(len(meshes), 1))()
+        ptr = lambda a: None if a is None else a.ctypes.data
+        for rec, m in zip(out, meshes):
+            rec.num_vertices = 0 if m["positions"] is None else len(m["positions"])
+            for key in MESH_FLOATS:
+                setattr(rec, key, ptr(m[key]))
+            for key in MESH_ELEMENTS:
+                setattr(rec, "num_" + key, 0 if m[key] is None else len(m[key]))
+                setattr(rec, key, ptr(m[key]))
+        return out
+
+    def _kept(self) -> list:
+        return [self.set, self.add]   # the meshes the records point into
+
+
+# ---- the three dictionary edits, id -> value, and the packing they share ---------------------------------------------------------------
+def _structs(d: dict, T):
+    """the values of a dictionary as a ctypes array of T (one unused element where the dictionary is empty)"""
+    return (T * max(1, len(d)))(*d.values())
+
+
+def _frames(d: dict) -> np.ndarray:
+    return np.ascontiguousarray(np.array([np.asarray(f, np.float32).reshape(12) for f in d.values()], np.float32).reshape(-1, 12))
+
+
+def _table(keep: list, d: dict, payload):
+    """one id -> value table of an edit, its values packed in `payload`: (count, address of the ids, address of the payload); both
+    arrays join `keep`"""
+    ids = np.array(list(d.keys()), np.int32)
+    keep += [ids, payload]
+    return len(d), ids.ctypes.data, _address(payload)
+
+
+class SceneEdit:
+    """What vpt_scene_update takes (include/vpt.h: vpt_scene_edit), as dictionaries id -> value: cameras (VptCamera), instances and
+    environments ((12,) float32 frames x, y, z, o), materials (VptMaterial), shapes ((positions, normals or None) as (n, 3) float32).
+    HostScene's setters fill one; DeviceScene.update / MultiDeviceScene.update apply it."""
+
+    def __init__(self, cameras=None, instances=None, environments=None, materials=None, shapes=None):
+        self.cameras, self.instances, self.environments = dict(cameras or {}), dict(instances or {}), dict(environments or {})
+        self.materials, self.shapes = dict(materials or {}), dict(shapes or {})
+
+    def empty(self) -> bool:
+        return not (self.cameras or self.instances or self.environments or self.materials or self.shapes)
+
+    def merge(self, other: "SceneEdit") -> "SceneEdit":
+        """this edit followed by `other` (later values win)"""
+        out = SceneEdit(self.cameras, self.instances, self.environments, self.materials, self.shapes)
+        for name in ("cameras", "instances", "environments", "materials"):
+            getattr(out, name).update(getattr(other, name))
+        for k, (pos, nrm) in other.shapes.items():
+            out.shapes[k] = (pos, nrm if nrm is not None or k not in out.shapes else out.shapes[k][1])
+        return out
+
+    def to_abi(self):
+        """(VptSceneEdit, objects that keep its arrays alive)"""
+        keep, abi = [], VptSceneEdit()
+        abi.num_cameras, abi.camera_ids, abi.cameras = _table(keep, self.cameras, _structs(self.cameras, VptCamera))
+        abi.num_instances, abi.instance_ids, abi.instance_frames = _table(keep, self.instances, _frames(self.instances))
+        abi.num_environments, abi.environment_ids, abi.environment_frames = _table(keep, self.environments, _frames(self.environments))
+        abi.num_materials, abi.material_ids, abi.materials = _table(keep, self.materials, _structs(self.materials, VptMaterial))
+        n = len(self.shapes)
+        pos, nrm = (C.c_void_p * max(1, n))(), (C.c_void_p * max(1, n))()
+        for i, (p, q) in enumerate(self.shapes.values()):
+            p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+            keep.append(p)
+            pos[i] = p.ctypes.data
+            if q is not None:
+                q = np.ascontiguousarray(q, np.float32).reshape(-1, 3)
+                if q.shape != p.shape:
+                    raise VptError("normals of a shape edit must match its positions")
+                keep.append(q)
+                nrm[i] = q.ctypes.data
+        abi.num_shapes, abi.shape_ids, abi.shape_positions = _table(keep, self.shapes, pos)
+        abi.shape_normals = _address(nrm)
+        return abi, keep + [nrm]
+
+
+class TextureEdit:
+    """What vpt_scene_update_textures takes (include/vpt.h: vpt_texture_edit), as dictionaries id -> value: environments
+    (VptEnvironment: frame, emission, emission_tex) and textures ((texels (h, w, 4) float32 or uint8, linear)).  HostScene's
+    set_environment / set_texture fill one; DeviceScene.update_textures / MultiDeviceScene.update_textures apply it."""
+
+    def __init__(self, environments=None, textures=None):
+        self.environments, self.textures = dict(environments or {}), dict(textures or {})
+
+    def empty(self) -> bool:
+        return not (self.environments or self.textures)
+
+    def payload_bytes(self) -> int:
+        """bytes of the edit itself as vpt_scene_update_stats counts them: texels, 24 per texture entry, 112 per environment entry"""
+        return sum(np.asarray(t).nbytes + 24 for t, _ in self.textures.values()) + 112 * len(self.environments)
+
+    def to_abi(self):
+        """(VptTextureEdit, objects that keep its arrays alive)"""
+        keep, abi = [], VptTextureEdit()
+        entries = (VptTexture * max(1, len(self.textures)))()
+        pool = {True: [], False: []}
+        count = {True: 0, False: 0}
+        for k, (texels, linear) in enumerate(self.textures.values()):
+            texels = np.ascontiguousarray(texels)
+            if texels.ndim != 3 or texels.shape[2] != 4 or texels.dtype not in (np.float32, np.uint8):
+                raise VptError("texels of a texture edit are (h, w, 4) float32 or uint8")
+            is_float = texels.dtype == np.float32
+            entries[k] = VptTexture(texels.shape[1], texels.shape[0], int(bool(linear)), int(is_float), count[is_float])
+            pool[is_float].append(texels.reshape(-1, 4))
+            count[is_float] += texels.shape[0] * texels.shape[1]
+        texels_f = np.ascontiguousarray(np.concatenate(pool[True])) if pool[True] else np.zeros((0, 4), np.float32)
+        texels_b = np.ascontiguousarray(np.concatenate(pool[False])) if pool[False] else np.zeros((0, 4), np.uint8)
+        abi.num_environments, abi.environment_ids, abi.environments = _table(keep, self.environments, _structs(self.environments, VptEnvironment))
+        abi.num_textures, abi.texture_ids, abi.textures = _table(keep, self.textures, entries)
+        abi.num_texels_f, abi.texels_f = len(texels_f), texels_f.ctypes.data
+        abi.num_texels_b, abi.texels_b = len(texels_b), texels_b.ctypes.data
+        return abi, keep + [texels_f, texels_b]
+
+
+@dataclass
+class VolumeSource:
+    """One volume entry of a VolumeEdit (include/vpt.h: vpt_volume_source): whd (w, h, d) and res of the volume AFTER the edit, the box
+    region_lo .. region_lo + region_whd it writes, the mode, and where the values come from: voxels (a float32 array of shape region
+    (d, h, w)), or a bake (positions (n, 3), triangles (m, 3), origin, step: the grid of bake_sdf_grid over whd)."""
+    whd: tuple
+    res: float
+    region_lo: tuple
+    region_whd: tuple
+    mode: int = VOXELS_REPLACE
+    voxels: Optional[np.ndarray] = None
+    bake: Optional[tuple] = None   # (positions, triangles, origin, step)
+
+
+class VolumeEdit:
+    """What vpt_scene_update_volumes takes (include/vpt.h: vpt_volume_edit), as dictionaries id -> value: vol_instances
+    (VptVolumeInstance), sdfs (VptSdf) and volumes (VolumeSource).  HostScene's set_volume_instance / set_sdf / set_volume /
+    bake_volume fill one; DeviceScene.update_volumes / MultiDeviceScene.update_volumes / RenderSession.edit_volumes apply it."""
+
+    def __init__(self, vol_instances=None, sdfs=None, volumes=None):
+        self.vol_instances, self.sdfs, self.volumes = dict(vol_instances or {}), dict(sdfs or {}), dict(volumes or {})
+
+    def empty(self) -> bool:
+        return not (self.vol_instances or self.sdfs or self.volumes)
+
+    def to_abi(self):
+        """(VptVolumeEdit, objects that keep its arrays alive)"""
+        keep, abi = [], VptVolumeEdit()
+        entries = (VptVolumeSource * max(1, len(self.volumes)))()
+        pool, count = [], 0
+        for k, src in enumerate(self.volumes.values()):
+            e = entries[k]
+            e.whd[:], e.res = [int(v) for v in src.whd], float(src.res)
+            e.region_lo[:], e.region_whd[:], e.mode = [int(v) for v in src.region_lo], [int(v) for v in src.region_whd], int(src.mode)
+            if src.bake is not None:
+                positions, triangles, origin, step = src.bake
+                positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+                triangles = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+                desc = VptBakeDesc(len(positions), positions.ctypes.data, len(triangles), triangles.ctypes.data)
+                desc.whd[:] = [int(v) for v in src.whd]
+                desc.origin[:] = [float(v) for v in np.broadcast_to(np.asarray(origin, np.float32), (3,))]
+                desc.step[:] = [float(v) for v in np.broadcast_to(np.asarray(step, np.float32), (3,))]
+                keep += [positions, triangles, desc]
+                e.offset, e.bake = -1, C.addressof(desc)
+            else:
+                voxels = np.ascontiguousarray(src.voxels, np.float32)
+                if voxels.shape != tuple(int(v) for v in src.region_whd)[::-1]:
+                    raise VptError(f"voxels of a volume edit have the region's shape (d, h, w) = {tuple(src.region_whd)[::-1]}, got {voxels.shape}")
+                e.offset, e.bake = count, None
+                pool.append(voxels.reshape(-1))
+                count += voxels.size
+        voxels = np.ascontiguousarray(np.concatenate(pool)) if pool else np.zeros(0, np.float32)
+        abi.num_vol_instances, abi.vol_instance_ids, abi.vol_instances = _table(keep, self.vol_instances, _structs(self.vol_instances, VptVolumeInstance))
+        abi.num_sdfs, abi.sdf_ids, abi.sdfs = _table(keep, self.sdfs, _structs(self.sdfs, VptSdf))
+        abi.num_volumes, abi.volume_ids, abi.volumes = _table(keep, self.volumes, entries)
+        abi.num_voxels, abi.voxels = len(voxels), voxels.ctypes.data
+        return abi, keep + [voxels]

@@ -1,0 +1,205 @@
+"""RenderSession: a progressive render whose state, image and display stay on the GPU."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from ._abi import (DENOISE_ITERATIONS, DENOISE_SIGMA_ALBEDO, DENOISE_SIGMA_LUMINANCE, DENOISE_SIGMA_NORMAL, VptAdaptive, VptDenoise, VptPick,
+                   VptSessionParams, _Handle, _check, _edit_call, _p, hip)
+from .device import DeviceScene, DisplayParams, PathtraceParams, PathtraceState
+from .edits import BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, TextureEdit, VolumeEdit
+
+
+class RenderSession(_Handle):
+    """vpt_session (include/vpt.h): a progressive render of one camera whose state, linear image and display stay on the GPU of `dev`
+    (a DeviceScene).  reset() is the reference's reset_display (preview included), advance(n) renders n more samples and refreshes the
+    display; display() / image() / state() fetch.  While it lives, `dev` must not be used from another thread."""
+    _free = staticmethod(hip.vpt_session_destroy)
+
+    def __init__(self, dev: "DeviceScene", params: PathtraceParams, pratio: int = 8, display: Optional[DisplayParams] = None,
+                 denoise: bool = False, guide_samples: int = 16, iterations: int = DENOISE_ITERATIONS,
+                 sigma_luminance: float = DENOISE_SIGMA_LUMINANCE, sigma_normal: float = DENOISE_SIGMA_NORMAL,
+                 sigma_albedo: float = DENOISE_SIGMA_ALBEDO, adaptive=None):
+        self.dev, self.handle, self.adaptive = dev, None, None
+        self._filter = VptDenoise(iterations, sigma_luminance, sigma_normal, sigma_albedo)
+        abi = self._abi(params, pratio, display or DisplayParams(), denoise, guide_samples)
+        out = _p()
+        _check(hip.vpt_session_create(dev.handle, C.byref(abi), C.byref(out)), "vpt_session_create")
+        self.handle = out
+        if adaptive is not None:  # (threshold, min_samples, step)
+            self.set_adaptive(*adaptive)
+
+    def set_adaptive(self, threshold: Optional[float], min_samples: int = 16, step: int = 32) -> None:
+        """vpt_session_set_adaptive: adaptive sampling with these settings from now on (params.samples is the per-pixel cap), and a
+        reset; set_adaptive(None) switches it off.  A refused call leaves the session as it was."""
+        if threshold is None:
+            _check(hip.vpt_session_set_adaptive(self.handle, None), "vpt_session_set_adaptive")
+            self.adaptive = None
+            return
+        ad = VptAdaptive(threshold, min_samples, step)
+        _check(hip.vpt_session_set_adaptive(self.handle, C.byref(ad)), "vpt_session_set_adaptive")
+        self.adaptive = (threshold, min_samples, step)
+
+    def progress(self):
+        """adaptive mode: (rounds run since the reset, samples taken, pixels still rendering)"""
+        n, rendered, active = C.c_int(0), C.c_int64(0), C.c_int(0)
+        _check(hip.vpt_session_progress(self.handle, C.byref(n), C.byref(rendered), C.byref(active)), "vpt_session_progress")
+        return n.value, rendered.value, active.value
+
+    def converged(self) -> bool:
+        """adaptive mode: no pixel is still rendering"""
+        return self.progress()[2] == 0
+
+    def hits(self) -> np.ndarray:
+        """adaptive mode: the samples every pixel has taken, (h, w) int32"""
+        w, h = self.size
+        out = np.zeros((h, w), np.int32)
+        _check(hip.vpt_session_get_hits(self.handle, out.ctypes.data), "vpt_session_get_hits")
+        return out
+
+    def noise(self):
+        """adaptive mode, after an advance: (se2, variance), (h, w) float32 each - the squared standard error of every pixel's mean
+        luminance over its rounds, and its box3, which the filter is handed from the second round on"""
+        w, h = self.size
+        se2, var = np.zeros((h, w), np.float32), np.zeros((h, w), np.float32)
+        _check(hip.vpt_session_get_noise(self.handle, se2.ctypes.data, var.ctypes.data), "vpt_session_get_noise")
+        return se2, var
+
+    def adaptive_stats(self):
+        """adaptive mode, after an advance: the Welford (mean, m2) of every pixel's rounds, (h, w) float32 each"""
+        w, h = self.size
+        mean, m2 = np.zeros((h, w), np.float32), np.zeros((h, w), np.float32)
+        _check(hip.vpt_session_get_adaptive_stats(self.handle, mean.ctypes.data, m2.ctypes.data), "vpt_session_get_adaptive_stats")
+        return mean, m2
+
+    def _abi(self, params, pratio, display, denoise, guide_samples) -> VptSessionParams:
+        self.params, self.pratio, self.display_params, self.denoise, self.guide_samples = params, pratio, display, denoise, guide_samples
+        return VptSessionParams(params.to_abi(), pratio, display.to_abi(), int(denoise), self._filter, guide_samples)
+
+    def reset(self, params: Optional[PathtraceParams] = None, pratio: Optional[int] = None, display: Optional[DisplayParams] = None,
+              denoise: Optional[bool] = None, guide_samples: Optional[int] = None) -> None:
+        """reset_display; any argument given replaces the session's (a new size re-allocates)"""
+        if params is None and pratio is None and display is None and denoise is None and guide_samples is None:
+            _check(hip.vpt_session_reset(self.handle, None), "vpt_session_reset")
+            return
+        pick = lambda new, old: old if new is None else new
+        old = (self.params, self.pratio, self.display_params, self.denoise, self.guide_samples)
+        abi = self._abi(pick(params, old[0]), pick(pratio, old[1]), pick(display, old[2]), pick(denoise, old[3]), pick(guide_samples, old[4]))
+        rc = hip.vpt_session_reset(self.handle, C.byref(abi))
+        if rc != 0:
+            self.params, self.pratio, self.display_params, self.denoise, self.guide_samples = old
+        _check(rc, "vpt_session_reset")
+
+    def advance(self, nsamples: int = 1) -> int:
+        """min(nsamples, params.samples - samples) more samples, then image and display; returns the samples reached.  In adaptive
+        mode: ceil(nsamples / step) whole rounds over the pixels still rendering; returns the largest hit count."""
+        _check(hip.vpt_session_advance(self.handle, nsamples), "vpt_session_advance")
+        return self.samples
+
+    def set_display(self, display: DisplayParams) -> None:
+        """tone-maps the image held again; nothing renders"""
+        abi = display.to_abi()
+        _check(hip.vpt_session_set_display(self.handle, C.byref(abi)), "vpt_session_set_display")
+        self.display_params = display
+
+    def edit(self, edit: SceneEdit) -> None:
+        """vpt_scene_update on the session's scene with the SceneEdit of HostScene.update_bvh(), then a reset; a refused edit
+        leaves the session as it was"""
+        _edit_call(self.handle, "vpt_session_edit", edit)
+
+    def edit_lights(self, edit: SceneEdit) -> None:
+        """edit() through vpt_scene_update_lights, with the SceneEdit of HostScene.update_lights()"""
+        _edit_call(self.handle, "vpt_session_edit_lights", edit)
+
+    def edit_textures(self, edit: TextureEdit) -> None:
+        """edit() through vpt_scene_update_textures, with the TextureEdit of HostScene.update_textures()"""
+        _edit_call(self.handle, "vpt_session_edit_textures", edit)
+
+    def edit_volumes(self, edit: VolumeEdit) -> None:
+        """edit() through vpt_scene_update_volumes, with the VolumeEdit of HostScene.update_volumes()"""
+        _edit_call(self.handle, "vpt_session_edit_volumes", edit)
+
+    def rebuild_bvh(self, rebuild: "BvhRebuild") -> None:
+        """vpt_scene_rebuild_bvh on the session's scene with the BvhRebuild of HostScene.rebuild_bvh(), then a reset"""
+        _edit_call(self.handle, "vpt_session_rebuild_bvh_quality", rebuild, rebuild.quality)
+
+    def edit_instances(self, edit: InstanceEdit) -> None:
+        """vpt_scene_update_instances on the session's scene with the InstanceEdit of HostScene.update_instances(), then a reset; a
+        refused edit leaves the session as it was"""
+        _edit_call(self.handle, "vpt_session_edit_instances", edit)
+
+    def edit_shapes(self, edit: ShapeEdit) -> None:
+        """vpt_scene_update_shapes on the session's scene with the ShapeEdit of HostScene.update_shapes(), then a reset; a refused edit
+        leaves the session as it was"""
+        _edit_call(self.handle, "vpt_session_edit_shapes", edit)
+
+    @property
+    def size(self):
+        w, h = C.c_int(), C.c_int()
+        _check(hip.vpt_session_size(self.handle, C.byref(w), C.byref(h)), "vpt_session_size")
+        return w.value, h.value
+
+    @property
+    def samples(self) -> int:
+        return hip.vpt_session_samples(self.handle)
+
+    def display(self, as_bytes: bool = True) -> np.ndarray:
+        """the display: (h, w, 4) uint8 (4 B per pixel fetched) or, with as_bytes False, float32 (16 B)"""
+        w, h = self.size
+        out = np.zeros((h, w, 4), np.uint8 if as_bytes else np.float32)
+        _check(hip.vpt_session_get_display(self.handle, out.ctypes.data if as_bytes else None, None if as_bytes else out.ctypes.data),
+               "vpt_session_get_display")
+        return out
+
+    def image(self, denoised: bool = False) -> np.ndarray:
+        """the linear image (the preview after a reset, get_render after an advance), unfiltered; denoised: the filtered one"""
+        w, h = self.size
+        out = np.zeros((h, w, 4), np.float32)
+        if denoised:
+            _check(hip.vpt_session_get_denoised(self.handle, out.ctypes.data), "vpt_session_get_denoised")
+        else:
+            _check(hip.vpt_session_get_image(self.handle, out.ctypes.data), "vpt_session_get_image")
+        return out
+
+    def state(self) -> PathtraceState:
+        w, h = self.size
+        st = PathtraceState(w, h, 0, np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.int32), np.zeros((h, w, 2), np.uint64))
+        n = C.c_int(0)
+        _check(hip.vpt_session_get_state(self.handle, st.image.ctypes.data, st.hits.ctypes.data, st.rngs.ctypes.data, C.byref(n)),
+               "vpt_session_get_state")
+        st.samples = n.value
+        return st
+
+    def guides(self):
+        """denoise = True: the guides the filter reads, (normal, albedo) as resolved (h, w, 4) float32 images; albedo None for the
+        implicit shaders"""
+        w, h = self.size
+        has_albedo = self.params.shader not in ("implicit", "implicit_normal")
+        normal, albedo = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32) if has_albedo else None
+        _check(hip.vpt_session_get_guides(self.handle, normal.ctypes.data, albedo.ctypes.data if has_albedo else None), "vpt_session_get_guides")
+        return normal, albedo
+
+    def pick(self, x: int, y: int) -> Optional[dict]:
+        """what is under pixel (x, y) of the frame on display (vpt_session_pick): None on a miss, else a dict of instance, element,
+        shape, material, u, v, distance.  24 bytes cross PCIe; the first pick or ids() after a reset makes the id frame."""
+        out = VptPick()
+        _check(hip.vpt_session_pick(self.handle, x, y, C.byref(out)), "vpt_session_pick")
+        if not out.hit:
+            return None
+        return {name: getattr(out, name) for name in ("instance", "element", "shape", "material", "u", "v", "distance")}
+
+    def ids(self):
+        """the id frame (vpt_session_get_ids): (ids, uvt) = (h, w, 2) int32 {instance, element} (-1 on a miss) and (h, w, 3) float32
+        {u, v, distance} of the rays through the pixel centres, in vpt_intersect's format"""
+        w, h = self.size
+        ids, uvt = np.zeros((h, w, 2), np.int32), np.zeros((h, w, 3), np.float32)
+        _check(hip.vpt_session_get_ids(self.handle, ids.ctypes.data, uvt.ctypes.data), "vpt_session_get_ids")
+        return ids, uvt
+
+    def stats(self):
+        """(kernel launches, bytes to the device, bytes to the host) of the last call on the session"""
+        n, up, down = C.c_int(0), C.c_int64(0), C.c_int64(0)
+        _check(hip.vpt_session_stats(self.handle, C.byref(n), C.byref(up), C.byref(down)), "vpt_session_stats")
+        return n.value, up.value, down.value

@@ -1,5 +1,6 @@
 """Import helper: the package directory is named `volumetric-path-tracer_amd` (a dash is not a
-valid Python identifier), so it is loaded by path and registered as module `vpt_amd`."""
+valid Python identifier), so it is loaded by path and registered as package `vpt_amd`; its modules import each other relatively and
+become `vpt_amd._abi`, `vpt_amd.edits`, ... through `submodule_search_locations`."""
 import importlib.util
 import os
 import sys
