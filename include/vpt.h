@@ -666,6 +666,91 @@ int vpt_scene_shape_tables_hash(vpt_scene* scene, uint64_t out[8]);
 /* the number of shapes and the entries of the pooled element and vertex tables as the device holds them; any pointer may be NULL */
 int vpt_scene_get_shape_counts(vpt_scene* scene, int32_t* num_shapes, int64_t* num_elements, int64_t* num_vertices);
 
+/* ---- subdivision surfaces of a resident scene: re-tesselated on the device ---------------------------------------
+ * The last member of the reference's scene_data that was frozen at load time: `subdivs`.  A subdivision surface is edited through a
+ * cage of tens of vertices and a displacement amount; tesselate_surface (yocto_pathtrace.cpp:1230-1273) turns them into the vertices
+ * of its shape.  The integer half of that work (catmullclark topology, split_facevarying, the per-vertex face lists) is done once on the
+ * host and attached to the scene as a PLAN; afterwards only the cage's floats move, and the float half runs on the device into the
+ * resident vertex pools, followed by the refit of vpt_scene_update and, for a shape a light uses, the rebuild of vpt_scene_update_lights.
+ *
+ * The plan (vpt_subdiv_plan; libvpt_host.so makes it: vpth_scene_subdiv_plan_item).  Every index in it is checked on the host at attach:
+ *  - settings: the shape id, subdivisions, smooth, displacement, displacement_tex (-1: none);
+ *  - cage floats: positions (float3) and - read only when subdivisions == 0 - the cage's own normals (float3, or none).  The cage's
+ *    texcoords are not part of it: the shape's texcoords do not depend on positions or displacement, they stay as they are resident;
+ *  - levels: one vpt_subdiv_level (dim 3) per subdivision, level k + 1 taking the refined vertices of level k;
+ *  - quads: the cage's quadspos after the last level (int4; the cage's own for subdivisions == 0), read by quads_normals when the
+ *    subdiv is smooth and subdivisions > 0;
+ *  - verts: split_facevarying's table, int3 per shape vertex {position, normal or -1, texcoord or -1} - indices into the refined
+ *    positions, and into the normals: quads_normals' (one per refined position) for a smooth subdiv with subdivisions > 0, the cage's
+ *    for subdivisions == 0;
+ *  - triangles_normals reads the shape's triangles where they are resident (the element table); its per-vertex face lists are built by
+ *    the library at attach, from one read-back of the shape's elements, whenever displacement_tex >= 0.
+ * vpt_scene_attach_subdiv validates the plan (VPT_ERR_INVALID_ARG, scene untouched: a null array with a count, a negative count, a
+ * level whose num_vertices is not the refined count of the one before, any index out of range, a float that is not finite) and checks
+ * it against the resident shape: it holds triangles, num_vertices is its vertex count, the number of triangles quads_to_triangles makes
+ * of `quads` (two per quad, one where z == w) is its element count, normals are present exactly when the plan's settings produce them
+ * (below), texcoords exactly when verts[].z >= 0, displacement_tex names a texture of the scene, and no other plan names the shape.
+ * Then it uploads the tables in ONE allocation with the plan's scratch (vpt_scene_update_stats: the bytes sent, no launch; the
+ * allocation's size is what the plan holds in HBM - DESIGN.md §25 has the formula).  It renders nothing and changes no table of the
+ * scene.  *subdiv_id_out names the plan from then on.  vpt_scene_detach_subdiv frees it; ids of other plans stay.
+ * vpt_scene_subdiv_count: the plans attached.  vpt_scene_subdiv_shape: the shape a plan edits now, -1 for an id that is not attached.
+ *
+ * The edit (vpt_subdiv_edit): per named plan a new cage (num_cage_positions float3) or NULL to keep the one the device holds, and a
+ * displacement amount or NaN to keep it (displacement NULL keeps all).  An entry that keeps both is valid: it tesselates again from
+ * what the device holds NOW, the displacement texture's texels included - how a vpt_scene_update_textures reaches the mesh.
+ * Contract: after the call every table on the device holds the bytes it would hold after the host mirror's tesselate_surface on the
+ * edited subdiv, vpt_scene_update with that shape's shape_positions / shape_normals, and vpt_scene_update_lights when a light's
+ * instance uses the shape.  The topology stays; renders, vpt_intersect, vpt_kat, vpt_scene_get_bvh, vpt_scene_shape_tables_hash and
+ * vpt_scene_light_tables_hash give that path's bits.  (The one difference: the parent's path refuses a tesselated vertex that is not
+ * finite - 0 / 0 for a cage vertex no face names; here only the cage's floats are checked, and such a vertex is written as it is.)
+ * On the device, per named plan, stream 0:
+ *  1. the levels through the points and averaging kernels of vpt_subdivide_vertices; consecutive levels that refine to at most 256
+ *     vertices run in one launch of one workgroup (same device functions, __syncthreads() between passes and levels); VPT_UPDATE_NO_FUSE
+ *     in the environment, read per call, gives every level its two launches - same bits;
+ *  2. quads_normals when smooth and subdivisions > 0;
+ *  3. the gather through `verts`, one thread per shape vertex: positions and normals as float3 into the plan's staging buffers;
+ *  4. when displacement != 0 and displacement_tex >= 0: triangles_normals if the shape has no normals so far, the displacement through
+ *     the scene's OWN tables (the shape's resident texcoords, the resident texture record and texels), triangles_normals again when smooth;
+ *  5. vpt_scene_update's scatter, leaf records, refit and everything behind it, reading the staging buffers where it reads the
+ *     uploaded payload otherwise; then vpt_scene_update_lights' rebuild when a light's instance uses one of the shapes.
+ * Which pools a shape has follows the settings: normals are present when smooth, for subdivisions > 0; for subdivisions == 0 they are
+ * the cage's own (present when it has some) while not displaced, and present when smooth while displaced.
+ * Refusals, scene untouched.  VPT_ERR_INVALID_ARG (the message names the entry): a null list with a count, a negative count, an id out
+ * of range, repeated or not attached, a float that is not finite (NaN in `displacement` means keep).  VPT_ERR_UNSUPPORTED: a
+ * displacement switched between zero and non-zero on a plan with subdivisions == 0 whose cage has normals while it is not smooth (or
+ * has none while it is smooth): the shape would gain or lose its normals - that edit is vpt_scene_update_shapes'; and a displaced plan
+ * whose shape has no texcoords.  There is no field for subdivisions, smooth, the cage's topology or texcoords: they change counts or
+ * pools.  Device failures, synchronisation and the launch-schedule record: as vpt_scene_update.
+ * Living with the other edits.  A plan stores the shape id only and reads pool offsets, the texture record and the shape's elements'
+ * place at edit time.  vpt_scene_update_shapes: a `set` or removed shape drops its plan (its id then answers "not attached"); the
+ * plans of the survivors follow the renumbering.  vpt_scene_rebuild_bvh leaves plans alone (the element table keeps its order; the
+ * refit tables are made anew).  vpt_scene_update: a plain vertex edit of a subdiv's shape is allowed; the next subdiv edit overwrites
+ * it.  vpt_scene_update_textures: a later subdiv edit reads the new texels, also after the pool has grown and moved.
+ * What crosses PCIe per edit: 12 B per cage vertex of an entry with a new cage, and what vpt_scene_update itself sends for an edit
+ * without vertices - nothing else; the constant per named plan is 0 B (settings and table addresses travel as kernel arguments).
+ * vpt_scene_update_stats reports launches, bytes and device time of the whole call, refit and light rebuild included. */
+typedef struct vpt_subdiv_level vpt_subdiv_level;   /* below, with vpt_subdivide_vertices */
+typedef struct vpt_subdiv_plan {
+  int32_t shape, subdivisions, smooth;
+  float   displacement;
+  int32_t displacement_tex;                                       /* -1: none */
+  int32_t num_cage_positions; const float* cage_positions;        /* float3 */
+  int32_t num_cage_normals;   const float* cage_normals;          /* float3; 0 / NULL: the cage has none */
+  int32_t num_levels;         const vpt_subdiv_level* levels;     /* == subdivisions */
+  int32_t num_quads;          const int32_t* quads;               /* int4: quadspos after the last level */
+  int32_t num_vertices;       const int32_t* verts;               /* int3 per shape vertex: position, normal or -1, texcoord or -1 */
+} vpt_subdiv_plan;
+int vpt_scene_attach_subdiv(vpt_scene* scene, const vpt_subdiv_plan* plan, int* subdiv_id_out);
+int vpt_scene_detach_subdiv(vpt_scene* scene, int subdiv_id);
+int vpt_scene_subdiv_count(const vpt_scene* scene);
+int vpt_scene_subdiv_shape(const vpt_scene* scene, int subdiv_id);
+typedef struct vpt_subdiv_edit {
+  int32_t num; const int32_t* subdiv_ids;
+  const float* const* cage_positions;   /* per entry: the cage's float3 array, or NULL (keep); the list itself may be NULL (keep all) */
+  const float* displacement;            /* per entry; the array may be NULL (keep all); NaN = keep one    */
+} vpt_subdiv_edit;
+int vpt_scene_update_subdivs(vpt_scene* scene, const vpt_subdiv_edit* edit);
+
 /* ---- the drop-in for pathtrace_samples() --------------------------------------------
  * Host, row-major (idx = j*width + i) caller-owned state, exactly pathtrace_state
  * (yocto_pathtrace.h:57-64): image float4[w*h], hits int32[w*h], rng {u64 state, u64 inc}[w*h].
@@ -718,6 +803,12 @@ int  vpt_multi_rebuild_bvh_quality(vpt_multi* m, const vpt_bvh_rebuild* what, in
 int  vpt_multi_update_instances(vpt_multi* m, const vpt_instance_edit* edit);
 /* vpt_scene_update_shapes in the same way: every device lays out its own pools and builds its own trees; they are equal by construction */
 int  vpt_multi_update_shapes(vpt_multi* m, const vpt_shape_edit* edit);
+/* vpt_scene_attach_subdiv / _detach_subdiv / _update_subdivs in the same way: every device holds its own copy of a plan under the same
+ * id (the devices take the same calls in the same order, so their ids agree; VPT_ERR_HIP if they ever do not) */
+int  vpt_multi_attach_subdiv(vpt_multi* m, const vpt_subdiv_plan* plan, int* subdiv_id_out);
+int  vpt_multi_detach_subdiv(vpt_multi* m, int subdiv_id);
+int  vpt_multi_subdiv_shape(const vpt_multi* m, int subdiv_id);   /* of devices[0] */
+int  vpt_multi_update_subdivs(vpt_multi* m, const vpt_subdiv_edit* edit);
 int  vpt_multi_device_count(const vpt_multi* m);
 /* how vpt_multi_get_render moves the parts: "rccl", "peer-copy" (several devices, no RCCL) or "local" (one device) */
 const char* vpt_multi_transport(const vpt_multi* m);
@@ -1050,6 +1141,8 @@ int  vpt_session_rebuild_bvh_quality(vpt_session* session, const vpt_bvh_rebuild
 int  vpt_session_edit_instances(vpt_session* session, const vpt_instance_edit* edit);
 /* vpt_scene_update_shapes, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_edit_shapes(vpt_session* session, const vpt_shape_edit* edit);
+/* vpt_scene_update_subdivs, then a reset; a refused edit leaves the session as it was (plans are attached on the session's scene handle) */
+int  vpt_session_edit_subdivs(vpt_session* session, const vpt_subdiv_edit* edit);
 int  vpt_session_get_display(vpt_session* session, uint8_t* rgba8, float* display_f);
 int  vpt_session_get_image(vpt_session* session, float* linear);
 int  vpt_session_get_denoised(vpt_session* session, float* linear);

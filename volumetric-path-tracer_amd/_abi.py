@@ -175,6 +175,26 @@ class VptShapeEdit(C.Structure):  # vpt_shape_edit
 
 assert C.sizeof(VptShapeData) == 112 and C.sizeof(VptShapeEdit) == 56
 
+
+class VptSubdivLevel(C.Structure):  # vpt_subdiv_level
+    _fields_ = [("dim", C.c_int32), ("num_vertices", C.c_int32), ("num_edges", C.c_int32), ("num_faces", C.c_int32), ("num_new_faces", C.c_int32),
+                ("edges", C.c_void_p), ("faces", C.c_void_p), ("new_faces", C.c_void_p), ("valence", C.c_void_p), ("offsets", C.c_void_p),
+                ("items", C.c_void_p), ("num_items", C.c_int64)]
+
+
+class VptSubdivPlan(C.Structure):  # vpt_subdiv_plan
+    _fields_ = [("shape", C.c_int32), ("subdivisions", C.c_int32), ("smooth", C.c_int32), ("displacement", C.c_float), ("displacement_tex", C.c_int32),
+                ("num_cage_positions", C.c_int32), ("cage_positions", C.c_void_p), ("num_cage_normals", C.c_int32), ("cage_normals", C.c_void_p),
+                ("num_levels", C.c_int32), ("levels", C.c_void_p), ("num_quads", C.c_int32), ("quads", C.c_void_p),
+                ("num_vertices", C.c_int32), ("verts", C.c_void_p)]
+
+
+class VptSubdivEdit(C.Structure):  # vpt_subdiv_edit
+    _fields_ = [("num", C.c_int32), ("subdiv_ids", C.c_void_p), ("cage_positions", C.c_void_p), ("displacement", C.c_void_p)]
+
+
+assert C.sizeof(VptSubdivLevel) == 80 and C.sizeof(VptSubdivPlan) == 96 and C.sizeof(VptSubdivEdit) == 32
+
 MESH_FLOATS = {"positions": 3, "normals": 3, "texcoords": 2, "colors": 4, "radius": 0}     # floats per vertex (0: a plain array)
 MESH_ELEMENTS = {"triangles": 3, "quads": 4, "points": 0, "lines": 2}                        # indices per element
 
@@ -223,6 +243,16 @@ hip.vpt_scene_instance_tables_hash.argtypes = [_p, _p]
 hip.vpt_scene_update_shapes.argtypes = [_p, C.POINTER(VptShapeEdit)]
 hip.vpt_multi_update_shapes.argtypes = [_p, C.POINTER(VptShapeEdit)]
 hip.vpt_session_edit_shapes.argtypes = [_p, C.POINTER(VptShapeEdit)]
+hip.vpt_scene_attach_subdiv.argtypes = [_p, C.POINTER(VptSubdivPlan), C.POINTER(C.c_int)]
+hip.vpt_multi_attach_subdiv.argtypes = [_p, C.POINTER(VptSubdivPlan), C.POINTER(C.c_int)]
+hip.vpt_scene_detach_subdiv.argtypes = [_p, C.c_int]
+hip.vpt_multi_detach_subdiv.argtypes = [_p, C.c_int]
+hip.vpt_scene_subdiv_count.argtypes = [_p]
+hip.vpt_scene_subdiv_shape.argtypes = [_p, C.c_int]
+hip.vpt_multi_subdiv_shape.argtypes = [_p, C.c_int]
+hip.vpt_scene_update_subdivs.argtypes = [_p, C.POINTER(VptSubdivEdit)]
+hip.vpt_multi_update_subdivs.argtypes = [_p, C.POINTER(VptSubdivEdit)]
+hip.vpt_session_edit_subdivs.argtypes = [_p, C.POINTER(VptSubdivEdit)]
 hip.vpt_scene_shape_tables_hash.argtypes = [_p, _p]
 hip.vpt_scene_get_shape_counts.argtypes = [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
 hip.vpt_scene_get_bvh_counts.argtypes = [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _p]
@@ -332,6 +362,11 @@ host.vpth_scene_rebuild_bvh_quality.argtypes = [_p, _p, C.c_int, C.c_int, C.c_in
 host.vpth_scene_edit_instances.argtypes = [_p, _p, C.c_int, _p, _p, C.c_int, _p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_scene_edit_shapes.argtypes = [_p, _p, C.c_int, _p, _p, C.c_int, _p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_scene_update_lights.argtypes = [_p, C.c_char_p, C.c_int]
+host.vpth_scene_subdiv_count.argtypes = [_p]
+host.vpth_scene_get_subdiv.argtypes = [_p, C.c_int, _p, C.POINTER(C.c_float)]
+host.vpth_scene_subdiv_plan_item.argtypes = [_p, C.c_int, C.c_int, _p, C.c_int64]
+host.vpth_scene_subdiv_plan_item.restype = C.c_int64
+host.vpth_scene_set_subdiv.argtypes = [_p, C.c_int, _p, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int]
 host.vpth_scene_free.restype = None
 host.vpth_scene_get_environment.argtypes = [_p, C.c_int, C.POINTER(VptEnvironment)]
 host.vpth_scene_set_environment.argtypes = [_p, C.c_int, C.POINTER(VptEnvironment), C.c_char_p, C.c_int]

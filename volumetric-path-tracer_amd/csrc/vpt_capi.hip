@@ -27,6 +27,7 @@
 #include "vpt_schedule.h"
 #include "vpt_scene_prep.h"
 #include "vpt_scene_update.h"
+#include "vpt_subdiv_update.h"
 #include "vpt_shape_update.h"
 #include "vpt_texture_update.h"
 #include "vpt_volume_update.h"
@@ -405,6 +406,7 @@ int vpt_scene_record_bytes(const vpt_scene* s, int* leaf_bytes, int* attribute_b
 const resident& resident_of(const vpt_scene* s) { return *s; }   // for vpt_scene_inspect.hip, which reads the tables back
 
 static bool moves_geometry(const vpt_scene_edit& e) { return e.num_instances > 0 || e.num_shapes > 0; }
+static bool moves_geometry(const vpt_subdiv_edit& e) { return e.num > 0; }
 static bool writes_materials(const vpt_scene_edit& e) { return e.num_materials > 0; }
 template <typename Edit> static bool moves_geometry(const Edit&) { return false; }   // environments, textures, volumes, SDFs
 template <typename Edit> static bool writes_materials(const Edit&) { return false; }
@@ -455,6 +457,26 @@ int vpt_scene_rebuild_bvh_quality(vpt_scene* s, const vpt_bvh_rebuild* what, int
 }
 int vpt_scene_update_instances(vpt_scene* s, const vpt_instance_edit* edit) { return edit_scene(s, edit, instance_update_apply); }
 int vpt_scene_update_shapes(vpt_scene* s, const vpt_shape_edit* edit) { return edit_scene(s, edit, shape_update_apply); }
+// the subdivision surfaces (vpt_subdiv_update.hip): a plan attached or freed changes no table of the scene - the render side owes it nothing
+int vpt_scene_attach_subdiv(vpt_scene* s, const vpt_subdiv_plan* plan, int* subdiv_id_out) {
+  if (!s || !plan) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  return subdiv_attach(*s, *plan, subdiv_id_out);
+}
+int vpt_scene_detach_subdiv(vpt_scene* s, int subdiv_id) {
+  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());   // nothing reads the plan's tables when they go
+  return subdiv_detach(*s, subdiv_id);
+}
+int vpt_scene_subdiv_count(const vpt_scene* s) {
+  if (!s) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  int n = 0;
+  for (const subdiv_plan_dev& p : s->subdivs) n += p.shape >= 0;
+  return n;
+}
+int vpt_scene_subdiv_shape(const vpt_scene* s, int subdiv_id) { return s && subdiv_id >= 0 && subdiv_id < (int)s->subdivs.size() ? s->subdivs[(size_t)subdiv_id].shape : -1; }
+int vpt_scene_update_subdivs(vpt_scene* s, const vpt_subdiv_edit* edit) { return edit_scene(s, edit, subdiv_update_apply); }
 
 int vpt_last_wave_costs(vpt_scene* s, unsigned* ticks, int capacity, int* count) {
   if (!s || !count || capacity < 0 || (capacity > 0 && !ticks)) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad argument");

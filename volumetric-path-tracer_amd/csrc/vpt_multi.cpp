@@ -335,6 +335,26 @@ int vpt_multi_rebuild_bvh_quality(vpt_multi* m, const vpt_bvh_rebuild* what, int
 }
 int vpt_multi_update_instances(vpt_multi* m, const vpt_instance_edit* edit) { return edit_parts(m, edit, vpt_scene_update_instances); }
 int vpt_multi_update_shapes(vpt_multi* m, const vpt_shape_edit* edit) { return edit_parts(m, edit, vpt_scene_update_shapes); }
+int vpt_multi_update_subdivs(vpt_multi* m, const vpt_subdiv_edit* edit) { return edit_parts(m, edit, vpt_scene_update_subdivs); }
+int vpt_multi_attach_subdiv(vpt_multi* m, const vpt_subdiv_plan* plan, int* subdiv_id_out) {
+  if (!m || !plan || !subdiv_id_out) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  int first = -1;
+  for (auto& p : m->parts) {
+    int id = -1;
+    if (int rc = vpt_scene_attach_subdiv(p.scene, plan, &id)) return rc;
+    if (first < 0) first = id;
+    if (id != first) return vpt_set_error(VPT_ERR_HIP, "multi: the devices number the plan differently (%d, %d)", first, id);
+  }
+  *subdiv_id_out = first;
+  return VPT_OK;
+}
+int vpt_multi_detach_subdiv(vpt_multi* m, int subdiv_id) {
+  if (!m) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  for (auto& p : m->parts)
+    if (int rc = vpt_scene_detach_subdiv(p.scene, subdiv_id)) return rc;
+  return VPT_OK;
+}
+int vpt_multi_subdiv_shape(const vpt_multi* m, int subdiv_id) { return m && !m->parts.empty() ? vpt_scene_subdiv_shape(m->parts[0].scene, subdiv_id) : -1; }
 
 int vpt_multi_device_count(const vpt_multi* m) { return m ? (int)m->parts.size() : 0; }
 

@@ -8,6 +8,7 @@
 
 #include "vpt_device_buffer.h"
 #include "vpt_scene_prep.h"
+#include "vpt_subdiv.h"
 
 // The internal nodes of one BVH by depth: nodes of depth l are order[first[l] .. first[l + 1]) of refit_tables::d_order (ids
 // local to the BVH).  A refit walks the levels deepest first.
@@ -30,6 +31,27 @@ struct refit_tables {
   device_buffer d_inst_box;     // 2 float4 per instance: transform_bbox(frame, shape root box)
 };
 
+// One attached tesselation plan (include/vpt.h: vpt_scene_attach_subdiv; vpt_subdiv_update.hip): the settings, and ONE allocation that
+// holds the uploaded tables, the cage's floats as the device keeps them, and the scratch of an edit - so an edit allocates nothing.
+// Every pointer below points into `block`.  shape < 0: a free slot (the plan was detached, or its shape was replaced or removed).
+struct subdiv_plan_dev {
+  int   shape = -1, subdivisions = 0, smooth = 0, displacement_tex = -1;
+  float displacement = 0;
+  int   num_cage = 0, num_cage_normals = 0, num_refined = 0, num_quads = 0, num_vertices = 0;   // num_refined: positions after the last level
+  std::vector<subdiv_level_dev> levels;
+  device_buffer block;
+  size_t        block_bytes = 0;
+  float*      cage         = nullptr;   // float3 x num_cage
+  const float* cage_normals = nullptr;  // float3 x num_cage_normals
+  const int4* quads        = nullptr;   // the final quadspos, with quads_normals' face lists (smooth and subdivisions > 0)
+  const int * quad_offsets = nullptr, *quad_items = nullptr;
+  const int * verts        = nullptr;   // int3 x num_vertices
+  const int * tri_offsets  = nullptr, *tri_items = nullptr;   // triangles_normals' face lists (displacement_tex >= 0)
+  float *buf0 = nullptr, *buf1 = nullptr, *tverts = nullptr;  // float3 x the widest level each
+  float *refined_normals = nullptr;     // float3 x num_refined
+  float *stage_pos = nullptr, *stage_nrm = nullptr, *stage_tmp = nullptr;   // float3 x num_vertices each
+};
+
 inline int most_of(const std::vector<int>& v) { return v.empty() ? 0 : std::max(0, *std::max_element(v.begin(), v.end())); }
 
 struct resident {
@@ -48,6 +70,7 @@ struct resident {
   int          light_features  = 0;      // VPT_FEAT_* bits this scene's lights need from the mesh kernels
   bool         varying_media   = false;  // prep_media_vary of m.materials: K1's general instance, which carries a path's medium in registers
   refit_tables refit;
+  std::vector<subdiv_plan_dev> subdivs;   // the attached tesselation plans by subdiv id (vpt_subdiv_update.hip)
   // buffers of an edit on its way to the tables, kept from call to call
   device_buffer d_stage;   // vpt_scene_update: moved vertices and frames
   size_t        stage_bytes = 0;

@@ -8,7 +8,14 @@
 // lights: the caller rebuilds the light tables afterwards (vpt_scene_update_lights, vpt_light_update.h), so an emission that
 // switches between zero and non-zero and moved vertices of a light's shape pass validation.
 // out.changed: true for every edit that passes validation, one without entries included - the counters of vpt_scene_update_stats start again.
-int scene_update_apply(resident& r, const vpt_scene_edit& edit, edit_outcome& out, bool lights = false);
+// staged: null, or the second source of moved vertices - per entry of edit.shape_ids the float3 positions and the float3 normals (or
+// null) where a caller has ALREADY made them on the device, on stream 0 (vpt_subdiv_update.hip).  edit.shape_positions / shape_normals
+// are not read then.  Such a caller has validated its own input and begun the update itself (begin_update, the first event, its own
+// launches and sends): the counters go on, and the scatter, the refit and everything behind it run as for an uploaded payload.
+struct staged_vertices {
+  std::vector<const float*> positions, normals;
+};
+int scene_update_apply(resident& r, const vpt_scene_edit& edit, edit_outcome& out, bool lights = false, const staged_vertices* staged = nullptr);
 
 // Pieces of the refit that vpt_scene_rebuild_bvh (vpt_bvh_rebuild.hip) runs on tables it has made and not yet handed to the scene:
 // the same kernels, launched on stream 0 and counted in r.last_launches.  `shapes`, `shape_nodes`, `enter`: device tables of the

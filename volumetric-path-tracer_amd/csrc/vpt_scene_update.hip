@@ -286,7 +286,7 @@ int refit_tables_init(const resident& r, refit_tables& u) {
   return VPT_OK;
 }
 
-int validate_edit(const resident& r, const vpt_scene_edit& e, bool lights) {
+int validate_edit(const resident& r, const vpt_scene_edit& e, bool lights, const staged_vertices* on_device) {
   const DScene&       d = r.d;
   const host_mirrors& h = r.h;
   const edit_mirrors& u = r.m;
@@ -294,7 +294,7 @@ int validate_edit(const resident& r, const vpt_scene_edit& e, bool lights) {
   if (int rc = check_ids("instance", e.num_instances, e.instance_ids, e.instance_frames, d.num_instances)) return rc;
   if (int rc = check_ids("environment", e.num_environments, e.environment_ids, e.environment_frames, d.num_environments)) return rc;
   if (int rc = check_ids("material", e.num_materials, e.material_ids, e.materials, d.num_materials)) return rc;
-  if (int rc = check_ids("shape", e.num_shapes, e.shape_ids, e.shape_positions, d.num_shapes)) return rc;
+  if (int rc = check_ids("shape", e.num_shapes, e.shape_ids, on_device ? (const void*)e.shape_ids : (const void*)e.shape_positions, d.num_shapes)) return rc;
   for (int i = 0; i < e.num_cameras; i++) {
     const vpt_camera& c = e.cameras[i];
     REQUIRE(finite_all(c.frame.x, 12) && finite_all(&c.lens, 5), "edit: camera entry %d: a value is not finite", i);
@@ -313,9 +313,14 @@ int validate_edit(const resident& r, const vpt_scene_edit& e, bool lights) {
   for (int i = 0; i < e.num_shapes; i++) {
     const int id = e.shape_ids[i];
     const size_t n = 3 * (size_t)h.shape_vertices[(size_t)id];
-    REQUIRE(e.shape_positions[i], "edit: shape entry %d: null positions", i);
-    REQUIRE(finite_all(e.shape_positions[i], n), "edit: shape entry %d: a position is not finite", i);
-    const float* nrm = e.shape_normals ? e.shape_normals[i] : nullptr;
+    if (on_device) {   // made on the device from input its maker has checked; the pools are the maker's to match
+      REQUIRE(on_device->positions[(size_t)i] && (on_device->normals[(size_t)i] == nullptr) == (u.shapes[(size_t)id].normal_offset < 0),
+          "edit: shape entry %d: staged vertices do not match the pools of shape %d", i, id);
+    } else {
+      REQUIRE(e.shape_positions[i], "edit: shape entry %d: null positions", i);
+      REQUIRE(finite_all(e.shape_positions[i], n), "edit: shape entry %d: a position is not finite", i);
+    }
+    const float* nrm = !on_device && e.shape_normals ? e.shape_normals[i] : nullptr;
     if (nrm) {
       REQUIRE(u.shapes[(size_t)id].normal_offset >= 0, "edit: shape entry %d: shape %d has no normals", i, id);
       REQUIRE(finite_all(nrm, n), "edit: shape entry %d: a normal is not finite", i);
@@ -385,13 +390,14 @@ int upd_light_records(resident& r, const DShape* shapes) {
   return VPT_OK;
 }
 
-int scene_update_apply(resident& r, const vpt_scene_edit& e, edit_outcome& out, bool lights) {
-  if (int rc = validate_edit(r, e, lights)) return rc;   // every refusal happens here: nothing has been written
+int scene_update_apply(resident& r, const vpt_scene_edit& e, edit_outcome& out, bool lights, const staged_vertices* on_device) {
+  if (int rc = validate_edit(r, e, lights, on_device)) return rc;   // every refusal happens here: nothing has been written
   out.changed = true;   // (an edit without entries too: it starts the counters again)
   const bool refit = e.num_instances > 0 || e.num_shapes > 0;
   if (refit && !r.refit.ready)
     if (int rc = refit_tables_init(r, r.refit)) return rc;
-  if (int rc = begin_update(r)) return rc;
+  if (!on_device)
+    if (int rc = begin_update(r)) return rc;
   DScene&             d = r.d;
   const host_mirrors& h = r.h;
   edit_mirrors&       m = r.m;
@@ -425,6 +431,7 @@ int scene_update_apply(resident& r, const vpt_scene_edit& e, edit_outcome& out, 
   staged_block pay;
   std::vector<size_t> at_pos((size_t)e.num_shapes, 0), at_nrm((size_t)e.num_shapes, 0);
   for (int i = 0; i < e.num_shapes; i++) {
+    if (on_device) break;   // the second source: the vertices are on the device already
     const size_t bytes = (size_t)h.shape_vertices[(size_t)e.shape_ids[i]] * 12;
     at_pos[(size_t)i] = pay.add(e.shape_positions[i], bytes);
     if (e.shape_normals && e.shape_normals[i]) at_nrm[(size_t)i] = pay.add(e.shape_normals[i], bytes);
@@ -439,7 +446,7 @@ int scene_update_apply(resident& r, const vpt_scene_edit& e, edit_outcome& out, 
   if (int rc = stage(r, pay)) return rc;
   const char*         staged = r.d_stage.get<char>();
   const refit_tables& u      = r.refit;
-  HIP_TRY(hipEventRecord(r.upd_ev0, 0));
+  if (!on_device) HIP_TRY(hipEventRecord(r.upd_ev0, 0));
 
   // 1. edited shapes: vertices, leaf records, shape BVH, its quad nodes
   float4* shape_nodes = mut(d.shape_nodes);
@@ -447,9 +454,10 @@ int scene_update_apply(resident& r, const vpt_scene_edit& e, edit_outcome& out, 
     const int     id = e.shape_ids[i];
     const DShape& sh = m.shapes[(size_t)id];
     const int     nv = h.shape_vertices[(size_t)id];
-    LAUNCH(r, upd_scatter_vertices_kernel, nv, mut(d.positions) + sh.vertex_offset, (const float*)(staged + at_pos[(size_t)i]), nv);
-    if (e.shape_normals && e.shape_normals[i])
-      LAUNCH(r, upd_scatter_vertices_kernel, nv, mut(d.normals) + sh.normal_offset, (const float*)(staged + at_nrm[(size_t)i]), nv);
+    const float* src_pos = on_device ? on_device->positions[(size_t)i] : (const float*)(staged + at_pos[(size_t)i]);
+    const float* src_nrm = on_device ? on_device->normals[(size_t)i] : e.shape_normals && e.shape_normals[i] ? (const float*)(staged + at_nrm[(size_t)i]) : nullptr;
+    LAUNCH(r, upd_scatter_vertices_kernel, nv, mut(d.positions) + sh.vertex_offset, src_pos, nv);
+    if (src_nrm) LAUNCH(r, upd_scatter_vertices_kernel, nv, mut(d.normals) + sh.normal_offset, src_nrm, nv);
     LAUNCH(r, upd_leaf_records_kernel, sh.num_elems, sh, d.elems, d.positions, d.normals, mut(d.leaf_prims), mut(d.leaf_attrs), mut(d.tri_prims), mut(d.tri_attrs));
     LAUNCH(r, upd_refit_shape_leaves_kernel, sh.num_nodes, shape_nodes, (long long)sh.node_offset, sh.num_nodes, d.leaf_prims, (long long)sh.leaf_offset);
     if (int rc = refit_internal_levels(r, shape_nodes, sh.node_offset, u.shape_levels[(size_t)id])) return rc;

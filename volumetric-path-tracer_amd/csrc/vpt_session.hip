@@ -547,6 +547,7 @@ int vpt_session_rebuild_bvh_quality(vpt_session* s, const vpt_bvh_rebuild* what,
 }
 int vpt_session_edit_instances(vpt_session* s, const vpt_instance_edit* edit) { return session_edit(s, edit, vpt_scene_update_instances); }
 int vpt_session_edit_shapes(vpt_session* s, const vpt_shape_edit* edit) { return session_edit(s, edit, vpt_scene_update_shapes); }
+int vpt_session_edit_subdivs(vpt_session* s, const vpt_subdiv_edit* edit) { return session_edit(s, edit, vpt_scene_update_subdivs); }
 
 int vpt_session_get_display(vpt_session* s, uint8_t* rgba8, float* display_f) {
   REQUIRE(s, "null session");

@@ -21,6 +21,7 @@
 #include "vpt_scene_update.h"
 #include "vpt_shape_layout.h"
 #include "vpt_shape_update.h"
+#include "vpt_subdiv_update.h"
 #include "vpt_update_helpers.h"
 
 namespace {
@@ -518,6 +519,7 @@ int shape_update_apply(resident& r, const vpt_shape_edit& e, edit_outcome& out) 
   }
   h.prim_slot = std::move(prim_slot), h.shape_elems = std::move(shape_elems), h.shape_elem_offset = std::move(shape_elem_offset), h.shape_vertices = std::move(shape_vertices);
   h.inst_shape = inst_shape, m.inst_flags = inst_flags, m.shapes = t.shapes, m.shape_flags = flags;
+  subdiv_plans_follow_shapes(r, new_of_old, is_set);   // a replaced or removed shape drops its tesselation plan, the others are renumbered
   out.curves = false;
   for (int i = 0; i < ninst; i++) out.curves = out.curves || (inst_flags[(size_t)i] & (VPT_SHP_POINTS | VPT_SHP_LINES)) != 0;
   r.varying_media = prep_media_vary(m.materials.data(), d.num_materials, m.inst_material.data(), m.inst_flags.data(), ninst);

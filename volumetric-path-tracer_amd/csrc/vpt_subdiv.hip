@@ -30,6 +30,7 @@
 #include "vpt_device_buffer.h"
 #include "vpt_error.h"
 #include "vpt_scene.hip.h"
+#include "vpt_subdiv.h"
 
 namespace {
 
@@ -52,11 +53,9 @@ __device__ inline vecD<D> divs(const vecD<D>& a, float b) {
   return r;
 }
 
+// refined vertex i of a level (the caller checked i < nv + ne + nf): the two kernels and the fused form share it
 template <int D>
-__global__ void __launch_bounds__(256) subdiv_points_kernel(int nv, int ne, int nf, const vecD<D>* __restrict__ vert, const int2* __restrict__ edges,
-    const int4* __restrict__ faces, vecD<D>* __restrict__ tverts) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nv + ne + nf) return;
+__device__ inline void refined_point(int i, int nv, int ne, const vecD<D>* vert, const int2* edges, const int4* faces, vecD<D>* tverts) {
   if (i < nv) tverts[i] = vert[i];
   else if (i < nv + ne) {
     int2 e    = edges[i - nv];
@@ -66,12 +65,17 @@ __global__ void __launch_bounds__(256) subdiv_points_kernel(int nv, int ne, int 
     tverts[i] = q.z != q.w ? divs(add(add(add(vert[q.x], vert[q.y]), vert[q.z]), vert[q.w]), 4.0f) : divs(add(add(vert[q.x], vert[q.y]), vert[q.z]), 3.0f);
   }
 }
-
 template <int D>
-__global__ void __launch_bounds__(256) subdiv_average_kernel(int nt, const vecD<D>* __restrict__ tverts, const int4* __restrict__ tquads,
-    const int* __restrict__ valence, const int* __restrict__ offsets, const int* __restrict__ items, vecD<D>* __restrict__ out) {
-  int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= nt) return;
+__global__ void __launch_bounds__(256) subdiv_points_kernel(int nv, int ne, int nf, const vecD<D>* __restrict__ vert, const int2* __restrict__ edges,
+    const int4* __restrict__ faces, vecD<D>* __restrict__ tverts) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nv + ne + nf) return;
+  refined_point<D>(i, nv, ne, vert, edges, faces, tverts);
+}
+
+// the averaging and correction of refined vertex v (the caller checked v < nt)
+template <int D>
+__device__ inline void averaged_vertex(int v, const vecD<D>* tverts, const int4* tquads, const int* valence, const int* offsets, const int* items, vecD<D>* out) {
   vecD<D> avert;
 #pragma unroll
   for (int k = 0; k < D; k++) avert.v[k] = 0.0f;
@@ -97,18 +101,40 @@ __global__ void __launch_bounds__(256) subdiv_average_kernel(int nt, const vecD<
   }
   out[v] = avert;
 }
+template <int D>
+__global__ void __launch_bounds__(256) subdiv_average_kernel(int nt, const vecD<D>* __restrict__ tverts, const int4* __restrict__ tquads,
+    const int* __restrict__ valence, const int* __restrict__ offsets, const int* __restrict__ items, vecD<D>* __restrict__ out) {
+  int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nt) return;
+  averaged_vertex<D>(v, tverts, tquads, valence, offsets, items, out);
+}
+// consecutive narrow levels by one workgroup (vpt_subdiv.h): no pointer is __restrict__ here - a level reads what the last one wrote
+__global__ void __launch_bounds__(SUBDIV_FUSE_WIDTH) subdiv_fused_kernel(subdiv_fused_levels lv, const vecD<3>* vert, vecD<3>* tverts, vecD<3>* buf0, vecD<3>* buf1) {
+  const int t = (int)threadIdx.x;
+  for (int l = 0; l < lv.count; l++) {
+    const subdiv_level_dev& L = lv.L[l];
+    const int nt  = L.nv + L.ne + L.nf;
+    vecD<3>*  out = (l & 1) ? buf1 : buf0;
+    if (t < nt) refined_point<3>(t, L.nv, L.ne, vert, L.edges, L.faces, tverts);
+    __syncthreads();   // every refined point is written before an average reads its neighbours'
+    if (t < nt) averaged_vertex<3>(t, tverts, L.tquads, L.valence, L.offsets, L.items, out);
+    __syncthreads();   // the level is complete before the next one reads it and overwrites tverts
+    vert = out;
+  }
+}
 
 // ---- normals and displacement ------------------------------------------------------------------------------------------------
 __device__ inline float tri_area(f3 p0, f3 p1, f3 p2) { return length(cross(p1 - p0, p2 - p0)) / 2; }   // yocto_geometry.h:506-510
 __device__ inline f3 ld_f3(const float* p, int i) { return mk3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
 // items[offsets[v] .. offsets[v + 1]): the faces that add to vertex v, once per corner that is v, in face order
-__global__ void __launch_bounds__(256) vertex_normals_kernel(int nv, int corners, const float* __restrict__ pos, const int* __restrict__ faces,
+// (stride: ints per face in `faces`, >= corners)
+__global__ void __launch_bounds__(256) vertex_normals_kernel(int nv, int corners, int stride, const float* __restrict__ pos, const int* __restrict__ faces,
     const int* __restrict__ offsets, const int* __restrict__ items, float* __restrict__ normals) {
   int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= nv) return;
   f3 n = mk3(0, 0, 0);
   for (int k = offsets[v]; k < offsets[v + 1]; k++) {
-    const int* f = faces + (long long)corners * items[k];
+    const int* f = faces + (long long)stride * items[k];
     f3    p0 = ld_f3(pos, f[0]), p1 = ld_f3(pos, f[1]), p2 = ld_f3(pos, f[2]);
     f3    normal;
     float area;
@@ -125,11 +151,11 @@ __global__ void __launch_bounds__(256) vertex_normals_kernel(int nv, int corners
   n = normalize(n);
   normals[3 * v] = n.x, normals[3 * v + 1] = n.y, normals[3 * v + 2] = n.z;
 }
-__global__ void __launch_bounds__(256) displace_kernel(DScene sc, int nv, int byte_texture, float displacement, const float* __restrict__ pos,
+__global__ void __launch_bounds__(256) displace_kernel(DScene sc, int texture, int nv, int byte_texture, float displacement, const float* __restrict__ pos,
     const float* __restrict__ nrm, const float* __restrict__ uv, float* __restrict__ out) {
   int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= nv) return;
-  f4    texel = eval_texture(sc, 0, mk2(uv[2 * v], uv[2 * v + 1]), true);
+  f4    texel = eval_texture(sc, texture, mk2(uv[2 * v], uv[2 * v + 1]), true);
   float disp  = (texel.x + texel.y + texel.z) / 3;   // mean(xyz(.)), yocto_pathtrace.cpp:1262
   if (byte_texture) disp -= 0.5f;
   f3 p = ld_f3(pos, v) + ld_f3(nrm, v) * displacement * disp;
@@ -158,9 +184,8 @@ int run_level(const vpt_subdiv_level& L, const float* vertices, float* new_verti
       put(buf[4], (const int4*)L.faces, (size_t)L.num_faces, &d_faces) || put(buf[5], (const int4*)L.new_faces, (size_t)L.num_new_faces, &d_tquads) ||
       put(buf[6], L.valence, (size_t)nt, &d_val) || put(buf[7], L.offsets, (size_t)nt + 1, &d_off) || put(buf[8], L.items, (size_t)L.num_items, &d_items))
     return VPT_ERR_HIP;
-  const int blocks = (nt + 255) / 256;
-  hipLaunchKernelGGL(subdiv_points_kernel<D>, dim3(blocks), dim3(256), 0, 0, L.num_vertices, L.num_edges, L.num_faces, d_vert, d_edges, d_faces, d_tverts);
-  hipLaunchKernelGGL(subdiv_average_kernel<D>, dim3(blocks), dim3(256), 0, 0, nt, d_tverts, d_tquads, d_val, d_off, d_items, d_out);
+  const subdiv_level_dev dev = {L.num_vertices, L.num_edges, L.num_faces, d_edges, d_faces, d_tquads, d_val, d_off, d_items};
+  subdiv_launch_level(D, dev, (const float*)d_vert, (float*)d_tverts, (float*)d_out, 0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(new_vertices, d_out, (size_t)nt * sizeof(vecD<D>), hipMemcpyDeviceToHost));
   return VPT_OK;
@@ -168,18 +193,58 @@ int run_level(const vpt_subdiv_level& L, const float* vertices, float* new_verti
 
 }  // namespace
 
-extern "C" int vpt_subdivide_vertices(int device, const vpt_subdiv_level* level, const float* vertices, float* new_vertices) {
-  if (!level) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  const vpt_subdiv_level& L = *level;
-  if ((L.dim != 2 && L.dim != 3) || L.num_vertices < 0 || L.num_edges < 0 || L.num_faces < 0 || L.num_new_faces < 0 || L.num_items < 0 ||
-      (long long)L.num_vertices + L.num_edges + L.num_faces > (1ll << 30))
-    return vpt_set_error(VPT_ERR_INVALID_ARG, "bad level sizes");
+// ---- the launchers (vpt_subdiv.h) ---------------------------------------------------------------------------------------------
+template <int D>
+static int launch_level(const subdiv_level_dev& L, const float* vert, float* tverts, float* out, hipStream_t stream) {
+  const int nt = refined_vertices(L), blocks = (nt + 255) / 256;
+  if (nt <= 0) return 0;
+  hipLaunchKernelGGL(subdiv_points_kernel<D>, dim3(blocks), dim3(256), 0, stream, L.nv, L.ne, L.nf, (const vecD<D>*)vert, L.edges, L.faces, (vecD<D>*)tverts);
+  hipLaunchKernelGGL(subdiv_average_kernel<D>, dim3(blocks), dim3(256), 0, stream, nt, (const vecD<D>*)tverts, L.tquads, L.valence, L.offsets, L.items, (vecD<D>*)out);
+  return 2;
+}
+int subdiv_launch_level(int dim, const subdiv_level_dev& L, const float* vert, float* tverts, float* out, hipStream_t stream) {
+  return dim == 3 ? launch_level<3>(L, vert, tverts, out, stream) : launch_level<2>(L, vert, tverts, out, stream);
+}
+int subdiv_launch_levels_fused(const subdiv_fused_levels& levels, const float* vert, float* tverts, float* buf0, float* buf1, hipStream_t stream) {
+  if (levels.count <= 0) return 0;
+  hipLaunchKernelGGL(subdiv_fused_kernel, dim3(1), dim3(SUBDIV_FUSE_WIDTH), 0, stream, levels, (const vecD<3>*)vert, (vecD<3>*)tverts, (vecD<3>*)buf0, (vecD<3>*)buf1);
+  return 1;
+}
+int subdiv_launch_normals(int num_vertices, int corners, int stride, const float* positions, const int* faces, const int* offsets, const int* items,
+    float* normals, hipStream_t stream) {
+  if (num_vertices <= 0) return 0;
+  hipLaunchKernelGGL(vertex_normals_kernel, dim3((num_vertices + 255) / 256), dim3(256), 0, stream, num_vertices, corners, stride, positions, faces, offsets, items, normals);
+  return 1;
+}
+int subdiv_launch_displace(const DScene& sc, int texture, int byte_texture, float displacement, int num_vertices, const float* positions, const float* normals,
+    const float* uv, float* out, hipStream_t stream) {
+  if (num_vertices <= 0) return 0;
+  hipLaunchKernelGGL(displace_kernel, dim3((num_vertices + 255) / 256), dim3(256), 0, stream, sc, texture, num_vertices, byte_texture, displacement, positions, normals, uv, out);
+  return 1;
+}
+// topology (integers, host): per vertex the faces that add to it - once per corner, in face order, as the reference's loop reaches them
+int subdiv_face_lists(int num_vertices, int num_faces, int corners, int stride, const int32_t* faces, std::vector<int>& offsets, std::vector<int>& items) {
+  offsets.assign((size_t)num_vertices + 1, 0), items.clear();
+  auto adds = [&](const int32_t* f, int c) { return !(corners == 4 && c == 3 && f[2] == f[3]); };   // `if (q.z != q.w)` of quads_normals
+  for (int i = 0; i < num_faces; i++)
+    for (int c = 0; c < corners; c++) {
+      int v = faces[(size_t)stride * i + c];
+      if (v < 0 || v >= num_vertices) return vpt_set_error(VPT_ERR_INVALID_ARG, "face %d refers to vertex %d", i, v);
+      if (adds(faces + (size_t)stride * i, c)) offsets[(size_t)v + 1]++;
+    }
+  for (int v = 0; v < num_vertices; v++) offsets[(size_t)v + 1] += offsets[(size_t)v];
+  items.resize((size_t)offsets[(size_t)num_vertices]);
+  std::vector<int> fill(offsets.begin(), offsets.end() - 1);
+  for (int i = 0; i < num_faces; i++)
+    for (int c = 0; c < corners; c++)
+      if (adds(faces + (size_t)stride * i, c)) items[(size_t)fill[(size_t)faces[(size_t)stride * i + c]]++] = i;
+  return VPT_OK;
+}
+
+// every index the kernels will follow, checked on the host: a fault on the device can take the whole node down.  The caller has
+// checked the sizes and that the tables are not null.
+int subdiv_check_level_indices(const vpt_subdiv_level& L) {
   const int nt = L.num_vertices + L.num_edges + L.num_faces;
-  if (nt == 0) return VPT_OK;   // an attribute the cage does not have (no texture coordinates): nothing to refine
-  if (!vertices || !new_vertices) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  if (!L.valence || !L.offsets || (L.num_edges && !L.edges) || (L.num_faces && !L.faces) || (L.num_new_faces && !L.new_faces) || (L.num_items && !L.items))
-    return vpt_set_error(VPT_ERR_INVALID_ARG, "null table");
-  // every index the kernels will follow is checked here: a fault on the device can take the whole node down
   for (int i = 0; i < 2 * L.num_edges; i++)
     if (L.edges[i] < 0 || L.edges[i] >= L.num_vertices) return vpt_set_error(VPT_ERR_INVALID_ARG, "edge %d refers to vertex %d", i / 2, L.edges[i]);
   for (int i = 0; i < 4 * L.num_faces; i++)
@@ -193,6 +258,21 @@ extern "C" int vpt_subdivide_vertices(int device, const vpt_subdiv_level* level,
     for (int k = a; k < b; k++)
       if (L.items[k] < 0 || L.items[k] >= (val == 2 ? L.num_new_faces : nt)) return vpt_set_error(VPT_ERR_INVALID_ARG, "item %d of vertex %d out of range", k - a, v);
   }
+  return VPT_OK;
+}
+
+extern "C" int vpt_subdivide_vertices(int device, const vpt_subdiv_level* level, const float* vertices, float* new_vertices) {
+  if (!level) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  const vpt_subdiv_level& L = *level;
+  if ((L.dim != 2 && L.dim != 3) || L.num_vertices < 0 || L.num_edges < 0 || L.num_faces < 0 || L.num_new_faces < 0 || L.num_items < 0 ||
+      (long long)L.num_vertices + L.num_edges + L.num_faces > (1ll << 30))
+    return vpt_set_error(VPT_ERR_INVALID_ARG, "bad level sizes");
+  const int nt = L.num_vertices + L.num_edges + L.num_faces;
+  if (nt == 0) return VPT_OK;   // an attribute the cage does not have (no texture coordinates): nothing to refine
+  if (!vertices || !new_vertices) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  if (!L.valence || !L.offsets || (L.num_edges && !L.edges) || (L.num_faces && !L.faces) || (L.num_new_faces && !L.new_faces) || (L.num_items && !L.items))
+    return vpt_set_error(VPT_ERR_INVALID_ARG, "null table");
+  if (int rc = subdiv_check_level_indices(L)) return rc;
   if (hipSetDevice(device) != hipSuccess) return vpt_set_error(VPT_ERR_NO_DEVICE, "no device %d", device);
   return L.dim == 3 ? run_level<3>(L, vertices, new_vertices) : run_level<2>(L, vertices, new_vertices);
 }
@@ -203,21 +283,8 @@ extern "C" int vpt_vertex_normals(int device, int32_t num_vertices, const float*
     return vpt_set_error(VPT_ERR_INVALID_ARG, "bad mesh sizes");
   if (num_vertices == 0) return VPT_OK;
   if (!positions || !normals || (num_faces && !faces)) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  // topology (integers, host): per vertex the faces that add to it - once per corner, in face order, as the reference's loop reaches them
-  std::vector<int> offsets((size_t)num_vertices + 1, 0), items;
-  auto adds = [&](const int32_t* f, int c) { return !(corners == 4 && c == 3 && f[2] == f[3]); };   // `if (q.z != q.w)` of quads_normals
-  for (int i = 0; i < num_faces; i++)
-    for (int c = 0; c < corners; c++) {
-      int v = faces[(size_t)corners * i + c];
-      if (v < 0 || v >= num_vertices) return vpt_set_error(VPT_ERR_INVALID_ARG, "face %d refers to vertex %d", i, v);
-      if (adds(faces + (size_t)corners * i, c)) offsets[(size_t)v + 1]++;
-    }
-  for (int v = 0; v < num_vertices; v++) offsets[(size_t)v + 1] += offsets[(size_t)v];
-  items.resize((size_t)offsets[(size_t)num_vertices]);
-  std::vector<int> fill(offsets.begin(), offsets.end() - 1);
-  for (int i = 0; i < num_faces; i++)
-    for (int c = 0; c < corners; c++)
-      if (adds(faces + (size_t)corners * i, c)) items[(size_t)fill[(size_t)faces[(size_t)corners * i + c]]++] = i;
+  std::vector<int> offsets, items;
+  if (int rc = subdiv_face_lists(num_vertices, num_faces, corners, corners, faces, offsets, items)) return rc;
   if (hipSetDevice(device) != hipSuccess) return vpt_set_error(VPT_ERR_NO_DEVICE, "no device %d", device);
   device_buffer buf[5];   // freed on every path
   float *d_pos = nullptr, *d_nrm = nullptr;
@@ -226,7 +293,7 @@ extern "C" int vpt_vertex_normals(int device, int32_t num_vertices, const float*
       put(buf[2], (const int*)faces, (size_t)num_faces * corners, &d_faces) || put(buf[3], offsets.data(), offsets.size(), &d_off) ||
       put(buf[4], items.data(), items.size(), &d_items))
     return VPT_ERR_HIP;
-  hipLaunchKernelGGL(vertex_normals_kernel, dim3((num_vertices + 255) / 256), dim3(256), 0, 0, num_vertices, corners, d_pos, d_faces, d_off, d_items, d_nrm);
+  subdiv_launch_normals(num_vertices, corners, corners, d_pos, d_faces, d_off, d_items, d_nrm, 0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(normals, d_nrm, (size_t)num_vertices * 12, hipMemcpyDeviceToHost));
   return VPT_OK;
@@ -261,7 +328,7 @@ extern "C" int vpt_displace_vertices(int device, const vpt_texture* texture, con
     return VPT_ERR_HIP;
   DScene sc = {};   // the one table eval_texture follows: textures[0] over its texel pool and the decode table
   sc.num_textures = 1, sc.textures = d_tex, sc.texels_f = d_texf, sc.texels_b = d_texb, sc.srgb_lut = d_lut;
-  hipLaunchKernelGGL(displace_kernel, dim3((num_vertices + 255) / 256), dim3(256), 0, 0, sc, num_vertices, t.is_float ? 0 : 1, displacement, d_pos, d_nrm, d_uv, d_out);
+  subdiv_launch_displace(sc, 0, t.is_float ? 0 : 1, displacement, num_vertices, d_pos, d_nrm, d_uv, d_out, 0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(new_positions, d_out, (size_t)num_vertices * 12, hipMemcpyDeviceToHost));
   return VPT_OK;

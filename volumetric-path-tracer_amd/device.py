@@ -10,7 +10,7 @@ import numpy as np
 
 from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SHADER_NAMES, VptAdaptive, VptAovPlanes, VptDisplay, VptError, VptLayout, VptParams,
                    VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, _counted, _edit_call, _p, hip, host)
-from .edits import BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, TextureEdit, VolumeEdit
+from .edits import BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit
 
 if TYPE_CHECKING:
     from .host_scene import HostScene
@@ -66,6 +66,31 @@ def device_count() -> int:
     return hip.vpt_device_count()
 
 
+def _attach_subdiv(owner, attach, index: int, plan: SubdivPlan) -> int:
+    """`plan` attached through vpt_scene_attach_subdiv / vpt_multi_attach_subdiv on owner.handle; owner._subdiv_ids[index] = its id there"""
+    abi, keep = plan.to_abi()
+    out = C.c_int(-1)
+    _check(attach(owner.handle, C.byref(abi), C.byref(out)), "vpt_scene_attach_subdiv")
+    del keep
+    owner._subdiv_ids[int(index)] = out.value
+    return out.value
+
+
+def _subdiv_edit_call(owner, attach, shape_of_plan, handle, name: str, edit: SubdivEdit) -> None:
+    """the edit entry point `name` on `handle` (a scene, multi-device scene or session) with a SubdivEdit: every named subdiv whose plan
+    the scene behind `owner` (a DeviceScene or MultiDeviceScene) does not hold - never attached, or dropped since by update_shapes -
+    is attached first, then the edit goes out under the plans' ids"""
+    for index in edit.subdivs:
+        have = owner._subdiv_ids.get(index)
+        if have is None or shape_of_plan(owner.handle, have) != edit.shape_of.get(index, -2):
+            if edit.plan_of is None:
+                raise VptError(f"{name}: subdiv {index} has no plan on the device and the edit names no source of one (attach_subdiv first)")
+            _attach_subdiv(owner, attach, index, edit.plan_of(index))
+    abi, keep = edit.to_abi(owner._subdiv_ids)
+    _check(getattr(hip, name)(handle, C.byref(abi)), name)
+    del keep
+
+
 class DeviceScene(_Handle):
     """vpt_scene: the scene resident in one GPU's HBM."""
     _free = staticmethod(hip.vpt_scene_destroy)
@@ -76,6 +101,7 @@ class DeviceScene(_Handle):
         _check(hip.vpt_scene_create_curves(scene.desc, scene.curves, device, C.byref(out)), "vpt_scene_create")
         self.handle = out
         self.device = device
+        self._subdiv_ids = {}   # subdiv of the host scene -> the id of its plan on the device (attach_subdiv)
 
     # -- the drop-in for pathtrace_samples(): host state in, host state out ---------------------
     def pathtrace_samples(self, state: PathtraceState, params: PathtraceParams, count: int = 1) -> None:
@@ -245,6 +271,26 @@ class DeviceScene(_Handle):
         HostScene.update_shapes()."""
         _edit_call(self.handle, "vpt_scene_update_shapes", edit)
 
+    def attach_subdiv(self, index: int, plan: SubdivPlan) -> int:
+        """vpt_scene_attach_subdiv (include/vpt.h): the tesselation plan of the host scene's subdiv `index` uploaded once; nothing
+        renders, no table of the scene changes.  Returns the plan's id on the device (update_subdivs keeps the map)."""
+        return _attach_subdiv(self, hip.vpt_scene_attach_subdiv, index, plan)
+
+    def detach_subdiv(self, index: int) -> None:
+        """vpt_scene_detach_subdiv: frees the plan of the host scene's subdiv `index`"""
+        _check(hip.vpt_scene_detach_subdiv(self.handle, self._subdiv_ids.pop(index)), "vpt_scene_detach_subdiv")
+
+    def subdiv_count(self) -> int:
+        """the plans attached (vpt_scene_subdiv_count)"""
+        return hip.vpt_scene_subdiv_count(self.handle)
+
+    def update_subdivs(self, edit: SubdivEdit) -> None:
+        """vpt_scene_update_subdivs (include/vpt.h): the named subdivs tesselated again on the device from the edit's cages and
+        displacements, into the resident vertex pools; refit and lights follow.  A named subdiv without a plan on the device gets one
+        first (edit.plan_of).  Afterwards the handle renders the bits of a DeviceScene made from the host scene after the same
+        HostScene.set_subdiv() and update_subdivs()."""
+        _subdiv_edit_call(self, hip.vpt_scene_attach_subdiv, hip.vpt_scene_subdiv_shape, self.handle, "vpt_scene_update_subdivs", edit)
+
     def shape_tables_hash(self):
         """FNV-1a of the eight groups of tables laid out in shape order (vpt_scene_shape_tables_hash): shapes, vertex pools, elems,
         leaf_prims, leaf_attrs, the compact records (0: none), shape nodes, shape quad nodes"""
@@ -396,6 +442,15 @@ class MultiDeviceScene(_Handle):
         out = _p()
         _check(hip.vpt_multi_create_curves(scene.desc, scene.curves, devs, len(devices), C.byref(out)), "vpt_multi_create")
         self.handle = out
+        self._subdiv_ids = {}   # subdiv of the host scene -> the id of its plan on every device
+
+    def attach_subdiv(self, index: int, plan: SubdivPlan) -> int:
+        """vpt_multi_attach_subdiv: DeviceScene.attach_subdiv on every device (the same id on each)"""
+        return _attach_subdiv(self, hip.vpt_multi_attach_subdiv, index, plan)
+
+    def update_subdivs(self, edit: SubdivEdit) -> None:
+        """vpt_multi_update_subdivs: DeviceScene.update_subdivs with the same edit on every device"""
+        _subdiv_edit_call(self, hip.vpt_multi_attach_subdiv, hip.vpt_multi_subdiv_shape, self.handle, "vpt_multi_update_subdivs", edit)
 
     def update(self, edit: SceneEdit) -> None:
         """vpt_multi_update: the same edit on every device; the resident tile state is left as it is"""

@@ -10,8 +10,8 @@ from typing import Optional
 import numpy as np
 
 from ._abi import (INSTANCE, MESH_ELEMENTS, MESH_FLOATS, VOXELS_REPLACE, VptBakeDesc, VptBvhRebuild, VptCamera, VptEnvironment, VptError,
-                   VptInstanceEdit, VptMaterial, VptSceneEdit, VptSdf, VptShapeData, VptShapeEdit, VptTexture, VptTextureEdit, VptVolumeEdit,
-                   VptVolumeInstance, VptVolumeSource, _address)
+                   VptInstanceEdit, VptMaterial, VptSceneEdit, VptSdf, VptShapeData, VptShapeEdit, VptSubdivEdit, VptSubdivLevel, VptSubdivPlan,
+                   VptTexture, VptTextureEdit, VptVolumeEdit, VptVolumeInstance, VptVolumeSource, _address)
 
 
 def mesh(positions, triangles=None, quads=None, points=None, lines=None, normals=None, texcoords=None, colors=None, radius=None) -> dict:
@@ -120,6 +120,72 @@ class ShapeEdit(_ListEdit):
 
     def _kept(self) -> list:
         return [self.set, self.add]   # the meshes the records point into
+
+
+# ---- subdivision surfaces: the plan that is attached once, and the edit of cages and displacements ---------------------------------------
+LEVEL_TABLES = {"edges": 2, "faces": 4, "new_faces": 4, "valence": 0, "offsets": 0, "items": 0}   # int32 per entry (0: a plain array)
+
+
+class SubdivPlan:
+    """What vpt_scene_attach_subdiv takes (include/vpt.h: vpt_subdiv_plan): the settings of a subdiv, its cage's floats and the integer
+    half of its tesselation - `levels`, a list of dictionaries of the int32 tables of LEVEL_TABLES (one vpt_subdiv_level each, dim 3),
+    `quads` (n, 4) after the last level and `verts` (m, 3), split_facevarying's table.  HostScene.subdiv_plan makes one."""
+
+    def __init__(self, shape, subdivisions, smooth, displacement, displacement_tex, cage_positions, cage_normals, levels, quads, verts):
+        self.shape, self.subdivisions, self.smooth = int(shape), int(subdivisions), bool(smooth)
+        self.displacement, self.displacement_tex = float(displacement), int(displacement_tex)
+        self.cage_positions = np.ascontiguousarray(cage_positions, np.float32).reshape(-1, 3)
+        self.cage_normals = np.ascontiguousarray(cage_normals, np.float32).reshape(-1, 3)
+        self.levels = [{k: np.ascontiguousarray(L[k], np.int32).reshape((-1, w) if w else (-1,)) for k, w in LEVEL_TABLES.items()} for L in levels]
+        self.quads = np.ascontiguousarray(quads, np.int32).reshape(-1, 4)
+        self.verts = np.ascontiguousarray(verts, np.int32).reshape(-1, 3)
+
+    def to_abi(self):
+        """(VptSubdivPlan, the arrays it points into: keep them alive across the call)"""
+        levels = (VptSubdivLevel * max(1, len(self.levels)))()
+        nv = len(self.cage_positions)
+        for rec, L in zip(levels, self.levels):
+            rec.dim, rec.num_vertices, rec.num_edges, rec.num_faces, rec.num_new_faces = 3, nv, len(L["edges"]), len(L["faces"]), len(L["new_faces"])
+            for k in LEVEL_TABLES:
+                setattr(rec, k, L[k].ctypes.data)
+            rec.num_items = len(L["items"])
+            nv = nv + rec.num_edges + rec.num_faces
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        abi = VptSubdivPlan(self.shape, self.subdivisions, int(self.smooth), self.displacement, self.displacement_tex,
+                            len(self.cage_positions), ptr(self.cage_positions), len(self.cage_normals), ptr(self.cage_normals),
+                            len(self.levels), C.addressof(levels) if self.levels else None, len(self.quads), ptr(self.quads), len(self.verts), ptr(self.verts))
+        return abi, [levels, self]
+
+
+class SubdivEdit:
+    """What vpt_scene_update_subdivs takes (include/vpt.h: vpt_subdiv_edit), as a dictionary subdiv id -> (cage positions (n, 3) float32
+    or None: keep, displacement or None: keep); an entry (None, None) tesselates again from what the device holds.  `shape_of`: subdiv
+    id -> the shape it edits, `plan_of`: a function subdiv id -> SubdivPlan - how DeviceScene.update_subdivs, MultiDeviceScene.update_subdivs
+    and RenderSession.edit_subdivs attach a named subdiv's plan on first use.  HostScene.set_subdiv fills one, update_subdivs() hands it out."""
+
+    def __init__(self, subdivs=None, shape_of=None, plan_of=None):
+        self.subdivs = {int(k): (None if p is None else np.ascontiguousarray(p, np.float32).reshape(-1, 3).copy(), None if d is None else float(d))
+                        for k, (p, d) in dict(subdivs or {}).items()}
+        self.shape_of, self.plan_of = dict(shape_of or {}), plan_of
+
+    def empty(self) -> bool:
+        return not self.subdivs
+
+    def payload_bytes(self) -> int:
+        """bytes of the edit itself as vpt_scene_update_stats counts them: 12 per cage vertex of an entry with a new cage"""
+        return sum(p.nbytes for p, _ in self.subdivs.values() if p is not None)
+
+    def to_abi(self, ids=None):
+        """(VptSubdivEdit, objects that keep its arrays alive); ids: subdiv id -> the id its plan has on the device (None: the same)"""
+        n = len(self.subdivs)
+        names = np.array([k if ids is None else ids[k] for k in self.subdivs], np.int32)
+        cages, amounts = (C.c_void_p * max(1, n))(), np.full(max(1, n), np.nan, np.float32)
+        for i, (p, d) in enumerate(self.subdivs.values()):
+            cages[i] = None if p is None else p.ctypes.data
+            if d is not None:
+                amounts[i] = d
+        abi = VptSubdivEdit(n, names.ctypes.data if n else None, C.addressof(cages), amounts.ctypes.data)
+        return abi, [names, cages, amounts, self.subdivs]
 
 
 # ---- the three dictionary edits, id -> value, and the packing they share ---------------------------------------------------------------

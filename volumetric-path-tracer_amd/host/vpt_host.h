@@ -224,6 +224,17 @@ struct subdiv_level {
 };
 void catmullclark_topology(const vector<vec4i>& quads, int num_vertices, bool lock_boundary, subdiv_level& level);
 void subdivide_vertices(const subdiv_level& level, int dim, const vector<float>& verts, vector<float>& out);
+// The integer half of one subdiv's tesselate_surface as the tesselation itself made it (the plan of vpt_scene_attach_subdiv,
+// include/vpt.h): the position levels in order, quadspos after the last level, and split_facevarying's table - per shape vertex the
+// indices {position, normal or -1, texcoord or -1} it was copied from.
+struct subdiv_plan_host {
+  vector<subdiv_level> levels;
+  vector<vec4i>        quads;
+  vector<vec3i>        verts;
+};
+// tesselate_surface of subdiv `index` as it is now (host arithmetic) into `shape` - the scene's own shape or a copy; plan: null, or
+// where the run records its integer half.  One code path: the table the shape is gathered through IS the plan's.
+void tesselate_subdiv(const scene_data& scene, int index, shape_data& shape, subdiv_plan_host* plan = nullptr);
 // Extension: the same with every float stage on GPU `device` - the per-level vertex arithmetic (edge and face points, the
 // averaging pass in face order, the correction pass: vpt_subdivide_vertices), the smooth normals before and after the
 // displacement (vpt_vertex_normals) and the displacement itself (vpt_displace_vertices); the integer work - topology,

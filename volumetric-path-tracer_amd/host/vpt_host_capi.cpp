@@ -18,6 +18,7 @@ struct host_scene {
   pathtrace_lights lights;
   std::unique_ptr<flat_scene> flat = std::make_unique<flat_scene>();
   std::set<int> edited_instances, edited_shapes;   // since the last vpth_scene_update_bvh
+  vector<std::unique_ptr<subdiv_plan_host>> plans;   // per subdiv, made when first asked for (vpth_scene_subdiv_plan_item)
 };
 void set_error(char* err, int errlen, const string& msg) {
   if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", msg.c_str());
@@ -352,6 +353,119 @@ int vpth_scene_update_lights(void* hh, char* err, int errlen) {
     auto flat = std::make_unique<flat_scene>();
     flatten_scene(*flat, h.scene, h.bvh, h.lights);
     h.flat = std::move(flat);
+    return 0;
+  } catch (const std::exception& e) {
+    return set_error(err, errlen, e.what()), -1;
+  }
+}
+// ---- subdivision surfaces (the host side of vpt_scene_attach_subdiv / vpt_scene_update_subdivs, include/vpt.h) ------------------
+int vpth_scene_subdiv_count(void* hh) { return (int)((host_scene*)hh)->scene.subdivs.size(); }
+// settings: {shape, subdivisions, smooth, catmullclark, displacement_tex}; -1 for a bad id
+int vpth_scene_get_subdiv(void* hh, int id, int32_t* settings, float* displacement) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (id < 0 || id >= (int)sc.subdivs.size() || !settings || !displacement) return -1;
+  auto& s = sc.subdivs[id];
+  settings[0] = s.shape, settings[1] = s.subdivisions, settings[2] = s.smooth, settings[3] = s.catmullclark, settings[4] = s.displacement_tex;
+  *displacement = s.displacement;
+  return 0;
+}
+// One array of subdiv `id`, copied to `out` when it fits `capacity` bytes; returns its size in bytes, -1 for a bad id or kind.
+// The cage: 0 positions (float3), 1 normals (float3), 2 texcoords (float2), 3 quadspos, 4 quadsnorm, 5 quadstexcoord (int4).
+// The plan (made by tesselate_subdiv on first use, kept until subdivisions or smooth change): 6 verts (int3 per shape vertex), 7 the
+// quads after the last level (int4); of level L = 0 .. subdivisions - 1, kind 16 + 8 L + k: k = 0 sizes {num_vertices, num_edges,
+// num_faces, num_new_faces, num_items} (int32), 1 edges, 2 faces, 3 new_faces, 4 valence, 5 offsets, 6 items.
+int64_t vpth_scene_subdiv_plan_item(void* hh, int id, int kind, void* out, int64_t capacity) {
+  try {
+    auto& h = *(host_scene*)hh;
+    if (id < 0 || id >= (int)h.scene.subdivs.size() || kind < 0) return -1;
+    auto& s = h.scene.subdivs[id];
+    if (kind > 5 && s.shape < 0) return -1;   // its shape was removed: there is nothing to plan
+    const void* src = nullptr;
+    int64_t     n   = 0;
+    int32_t     sizes[5];
+    auto        of = [&](const auto& v) { src = v.data(), n = (int64_t)(v.size() * sizeof(v[0])); };
+    if (kind <= 5) {
+      switch (kind) {
+        case 0: of(s.positions); break;
+        case 1: of(s.normals); break;
+        case 2: of(s.texcoords); break;
+        case 3: of(s.quadspos); break;
+        case 4: of(s.quadsnorm); break;
+        case 5: of(s.quadstexcoord); break;
+      }
+    } else {
+      if (h.plans.size() != h.scene.subdivs.size()) h.plans.clear(), h.plans.resize(h.scene.subdivs.size());
+      if (!h.plans[id]) {   // into a copy of the shape: asking for the plan changes nothing of the scene
+        auto plan = std::make_unique<subdiv_plan_host>();
+        auto copy = h.scene.shapes.at((size_t)s.shape);
+        tesselate_subdiv(h.scene, id, copy, plan.get());
+        h.plans[id] = std::move(plan);
+      }
+      auto& plan = *h.plans[id];
+      if (kind == 6) of(plan.verts);
+      else if (kind == 7) of(plan.quads);
+      else if (kind >= 16 && (kind - 16) / 8 < (int)plan.levels.size() && (kind - 16) % 8 <= 6) {
+        auto& L = plan.levels[(size_t)(kind - 16) / 8];
+        switch ((kind - 16) % 8) {
+          case 0:
+            sizes[0] = L.nv, sizes[1] = L.ne, sizes[2] = L.nf, sizes[3] = (int32_t)L.tquads.size(), sizes[4] = (int32_t)L.items.size();
+            src = sizes, n = sizeof(sizes);
+            break;
+          case 1: of(L.edges); break;
+          case 2: of(L.faces); break;
+          case 3: of(L.tquads); break;
+          case 4: of(L.valence); break;
+          case 5: of(L.offsets); break;
+          case 6: of(L.items); break;
+        }
+      } else return -1;
+    }
+    if (out && capacity >= n && n > 0) memcpy(out, src, (size_t)n);
+    return n;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+// The kept cage edited - positions (float3 x the cage's count) unless null, displacement unless NaN, subdivisions / smooth unless < 0 -
+// and the mirror's tesselate_surface run on it: the shape holds the new mesh.  *resized: 0 when the shape kept its vertex and triangle
+// counts and its pools - the descriptor's copy of positions and normals is current and the shape waits for vpth_scene_update_bvh
+// (and _update_lights) like any vertex edit; 1 when it did not: the descriptor and the BVH wait for vpth_scene_edit_shapes with the
+// shape's arrays as a `set` entry.  A refused call leaves the scene as it was.
+int vpth_scene_set_subdiv(void* hh, int id, const float* positions, float displacement, int subdivisions, int smooth, int* resized, char* err, int errlen) {
+  try {
+    auto& h = *(host_scene*)hh;
+    if (id < 0 || id >= (int)h.scene.subdivs.size() || !resized) return set_error(err, errlen, "subdiv id out of range or null pointer"), -1;
+    auto& s = h.scene.subdivs[id];
+    if (s.shape < 0) return set_error(err, errlen, "the subdiv's shape was removed"), -1;
+    if (positions)
+      for (size_t k = 0; k < 3 * s.positions.size(); k++)
+        if (!std::isfinite(positions[k])) return set_error(err, errlen, "a cage position is not finite"), -1;
+    if (std::isinf(displacement)) return set_error(err, errlen, "the displacement is not finite"), -1;
+    if (subdivisions > 10) return set_error(err, errlen, "more than 10 subdivisions"), -1;
+    auto was = s;
+    if (positions) memcpy((void*)s.positions.data(), positions, 12 * s.positions.size());
+    if (!std::isnan(displacement)) s.displacement = displacement;
+    if (subdivisions >= 0) s.subdivisions = subdivisions;
+    if (smooth >= 0) s.smooth = smooth != 0;
+    auto  topology = s.subdivisions != was.subdivisions || s.smooth != was.smooth;
+    auto& shape    = h.scene.shapes.at((size_t)s.shape);
+    auto  made     = shape;
+    try {
+      tesselate_subdiv(h.scene, id, made);
+    } catch (...) {
+      s = was;
+      throw;
+    }
+    *resized = made.positions.size() != shape.positions.size() || made.normals.size() != shape.normals.size() || made.triangles.size() != shape.triangles.size() ||
+               made.texcoords.size() != shape.texcoords.size() || topology;
+    shape = std::move(made);
+    if (topology && h.plans.size() == h.scene.subdivs.size()) h.plans[id] = nullptr;
+    if (!*resized) {
+      auto& flat = *h.flat;
+      memcpy((void*)(flat.positions.data() + flat.shapes[s.shape].position_offset), shape.positions.data(), 12 * shape.positions.size());
+      if (!shape.normals.empty()) memcpy((void*)(flat.normals.data() + flat.shapes[s.shape].normal_offset), shape.normals.data(), 12 * shape.normals.size());
+      h.edited_shapes.insert(s.shape);
+    }
     return 0;
   } catch (const std::exception& e) {
     return set_error(err, errlen, e.what()), -1;

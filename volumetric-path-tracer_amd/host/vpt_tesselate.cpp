@@ -268,7 +268,8 @@ struct triple_hash {   // std::hash<vec3i> of yocto_shape.h:386-395 (only lookup
 struct triple_eq {
   bool operator()(const vec3i& a, const vec3i& b) const { return a.x == b.x && a.y == b.y && a.z == b.z; }
 };
-void split_facevarying(shape_data& shape, const subdiv_data& subdiv) {
+// (returns the table the three copy loops read: per shape vertex its {position, normal, texcoord} indices)
+vector<vec3i> split_facevarying(shape_data& shape, const subdiv_data& subdiv) {
   auto vert_map = std::unordered_map<vec3i, int, triple_hash, triple_eq>{};
   auto verts    = vector<vec3i>{};
   shape.quads.resize(subdiv.quadspos.size());
@@ -300,6 +301,7 @@ void split_facevarying(shape_data& shape, const subdiv_data& subdiv) {
     shape.texcoords.resize(verts.size());
     for (size_t i = 0; i < verts.size(); i++) shape.texcoords[i] = subdiv.texcoords[(size_t)verts[i].z];
   }
+  return verts;
 }
 
 // eval_texture(texture, uv, as_linear = true) (yocto_scene.cpp:128-161, lookup_texture :112-125): tiled bilinear lookup, 8-bit
@@ -344,7 +346,7 @@ void check_cage(const subdiv_data& subdiv) {   // the reference trusts its files
 
 // where the float work of tesselate_surface runs: the host loops above, or the device kernels of csrc/vpt_subdiv.hip
 struct tess_ops {
-  std::function<void(vector<vec4i>&, vector<float>&, int, bool)>                           level;             // one Catmull-Clark level on (quads, flat vertex floats)
+  std::function<void(vector<vec4i>&, vector<float>&, int, bool, subdiv_level*)>            level;             // one Catmull-Clark level on (quads, flat vertex floats); its topology to the last argument unless null
   std::function<vector<vec3f>(const vector<vec4i>&, const vector<vec3f>&)>                 normals_of_quads;
   std::function<vector<vec3f>(const vector<vec3i>&, const vector<vec3f>&)>                 normals_of_triangles;
   std::function<void(const texture_data&, float, const shape_data&, vector<vec3f>&)>       displace;          // positions out
@@ -359,19 +361,20 @@ void displace_host(const texture_data& displacement_tex, float displacement, con
   }
 }
 // tesselate_surface, yocto_pathtrace.cpp:1228-1273
-void tesselate_surface(shape_data& shape, const subdiv_data& subdiv_, const scene_data& scene, const tess_ops& ops) {
+void tesselate_surface(shape_data& shape, const subdiv_data& subdiv_, const scene_data& scene, const tess_ops& ops, subdiv_plan_host* plan = nullptr) {
   auto& level = ops.level;
   auto subdiv = subdiv_;
   check_cage(subdiv);
   if (subdiv.subdivisions != 0) {
     auto flat = vector<float>(subdiv.positions.size() * 3);
     memcpy(flat.data(), subdiv.positions.data(), flat.size() * 4);
-    for (auto l = 0; l < subdiv.subdivisions; l++) level(subdiv.quadspos, flat, 3, false);
+    if (plan) plan->levels.assign((size_t)subdiv.subdivisions, {});
+    for (auto l = 0; l < subdiv.subdivisions; l++) level(subdiv.quadspos, flat, 3, false, plan ? &plan->levels[(size_t)l] : nullptr);
     subdiv.positions.resize(flat.size() / 3);
     memcpy((void*)subdiv.positions.data(), flat.data(), flat.size() * 4);
     flat.assign(subdiv.texcoords.size() * 2, 0.0f);
     memcpy(flat.data(), subdiv.texcoords.data(), flat.size() * 4);
-    for (auto l = 0; l < subdiv.subdivisions; l++) level(subdiv.quadstexcoord, flat, 2, true);
+    for (auto l = 0; l < subdiv.subdivisions; l++) level(subdiv.quadstexcoord, flat, 2, true, nullptr);
     subdiv.texcoords.resize(flat.size() / 2);
     memcpy((void*)subdiv.texcoords.data(), flat.data(), flat.size() * 4);
     if (subdiv.smooth) {
@@ -382,7 +385,11 @@ void tesselate_surface(shape_data& shape, const subdiv_data& subdiv_, const scen
       subdiv.quadsnorm = {};
     }
   }
-  split_facevarying(shape, subdiv);
+  auto verts = split_facevarying(shape, subdiv);
+  if (plan) {
+    if (subdiv.subdivisions == 0) plan->levels.clear();
+    plan->quads = subdiv.quadspos, plan->verts = std::move(verts);
+  }
   shape.triangles.clear();   // quads_to_triangles, yocto_shape.cpp:2565-2573
   shape.triangles.reserve(shape.quads.size() * 2);
   for (auto& q : shape.quads) {
@@ -404,10 +411,24 @@ void tesselate_surface(shape_data& shape, const subdiv_data& subdiv_, const scen
 }
 }  // namespace
 
+static tess_ops host_ops() {
+  auto level = [](vector<vec4i>& quads, vector<float>& verts, int dim, bool lock, subdiv_level* keep) {
+    auto L = subdiv_level{};
+    catmullclark_topology(quads, (int)(verts.size() / (size_t)dim), lock, L);
+    auto next = vector<float>{};
+    subdivide_vertices(L, dim, verts, next);
+    verts = std::move(next);
+    quads = L.tquads;
+    if (keep) *keep = std::move(L);
+  };
+  return tess_ops{level, quads_normals, triangles_normals, displace_host};
+}
 void tesselate_surfaces(scene_data& scene) {
-  auto ops = tess_ops{[](vector<vec4i>& quads, vector<float>& verts, int dim, bool lock) { tesselate_catmullclark(quads, verts, dim, lock); },
-      quads_normals, triangles_normals, displace_host};
+  auto ops = host_ops();
   for (auto& subdiv : scene.subdivs) tesselate_surface(scene.shapes.at((size_t)subdiv.shape), subdiv, scene, ops);
+}
+void tesselate_subdiv(const scene_data& scene, int index, shape_data& shape, subdiv_plan_host* plan) {
+  tesselate_surface(shape, scene.subdivs.at((size_t)index), scene, host_ops(), plan);
 }
 
 // the same stages one at a time (tests, profiles/tools/tesselation_timing.py): device < 0 host, else that GPU
@@ -441,7 +462,7 @@ vector<vec3f> displace_vertices(const texture_data& tex, float displacement, con
 }
 
 void tesselate_surfaces_device(scene_data& scene, int device) {
-  auto level = [device](vector<vec4i>& quads, vector<float>& verts, int dim, bool lock) {
+  auto level = [device](vector<vec4i>& quads, vector<float>& verts, int dim, bool lock, subdiv_level*) {
     auto L = subdiv_level{};
     catmullclark_topology(quads, (int)(verts.size() / (size_t)dim), lock, L);
     auto next = vector<float>((size_t)(L.nv + L.ne + L.nf) * dim);

@@ -13,7 +13,8 @@ from ._abi import (BVH_MIDDLE, BVH_NODE, BVH_SAH, LIGHT, MESH_ELEMENTS, MESH_FLO
                    VptEnvironment, VptError, VptMaterial, VptSceneDescBvh, VptSceneDescLights, VptSdf, VptVolumeInstance, _Handle, _check, _filled,
                    _host_call, hip, host)
 from .device import PathtraceParams, PathtraceState
-from .edits import BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, TextureEdit, VolumeEdit, VolumeSource, mesh
+from .edits import (LEVEL_TABLES, BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, VolumeSource,
+                    mesh)
 
 
 def build_bvh(bboxes: np.ndarray, device: Optional[int] = 0, *, quality: int = 0):
@@ -168,14 +169,16 @@ def bake_sdf(positions: np.ndarray, faces: np.ndarray, whd, padding: int = 2, de
 # began, so a change that renumbers or relies on a list waits until the edit over that list is handed out.  Kind of call -> the pending
 # state that refuses it, asked in this order:
 #   "edit": a SceneEdit that holds anything; "geometry": one that holds instance frames or shape vertices (cameras, materials and
-#   environment frames name lists nothing renumbers); "instances" / "shapes": an InstanceEdit / ShapeEdit that holds anything.
+#   environment frames name lists nothing renumbers); "instances" / "shapes": an InstanceEdit / ShapeEdit that holds anything;
+#   "subdivs": a SubdivEdit that holds anything (its shapes wait for update_bvh like moved vertices).
 # Texture and volume edits name lists of their own and wait for nothing; set_camera, set_material, set_environment_frame are never refused.
-_REFUSED_WHILE = {"vertices": ("instances", "shapes"),            # set_instance_frame, set_shape_positions
-                  "rebuild": ("edit", "instances", "shapes"),      # rebuild_bvh
-                  "instances": ("geometry", "shapes"),             # add_instance, remove_instances, set_instance, update_instances
-                  "shapes": ("geometry", "instances")}             # add_shape, set_shape, remove_shapes, update_shapes
+_REFUSED_WHILE = {"vertices": ("instances", "shapes"),                       # set_instance_frame, set_shape_positions, set_subdiv (cage, displacement)
+                  "rebuild": ("edit", "subdivs", "instances", "shapes"),      # rebuild_bvh
+                  "instances": ("geometry", "subdivs", "shapes"),             # add_instance, remove_instances, set_instance, update_instances
+                  "shapes": ("geometry", "subdivs", "instances")}             # add_shape, set_shape, remove_shapes, update_shapes, set_subdiv (level, smooth)
 _HAND_OUT = {"edit": "edit out with update_bvh()", "geometry": "edit out with update_bvh()",
-             "instances": "instance changes out with update_instances()", "shapes": "shape changes out with update_shapes()"}
+             "instances": "instance changes out with update_instances()", "shapes": "shape changes out with update_shapes()",
+             "subdivs": "subdiv changes out with update_subdivs()"}
 
 
 class HostScene(_Handle):
@@ -190,7 +193,7 @@ class HostScene(_Handle):
             raise VptError(f"HostScene: unknown bvh_quality {bvh_quality!r}")
         # the pending edits: what the setters noted since the matching update_*() handed the last one out
         self._edit, self._inst_edit, self._shape_edit = SceneEdit(), InstanceEdit(), ShapeEdit()
-        self._texture_edit, self._volume_edit = TextureEdit(), VolumeEdit()
+        self._texture_edit, self._volume_edit, self._subdiv_edit = TextureEdit(), VolumeEdit(), SubdivEdit()
         self._lazy_bakes = []   # (volume, VolumeSource) of bake_volume whose host copy is not baked yet
         self.handle = _host_call(host.vpth_scene_load_ex, os.fsencode(filename), -1 if tess_device is None else tess_device, size=1024, handle=True)
         self.filename = filename
@@ -241,7 +244,7 @@ class HostScene(_Handle):
     def _may(self, what: str, kind: str, why: str = "") -> None:
         """VptError unless a call of `kind` (_REFUSED_WHILE) may go ahead: the message names the update_*() to call first"""
         pending = {"edit": not self._edit.empty(), "geometry": bool(self._edit.instances or self._edit.shapes),
-                   "instances": not self._inst_edit.empty(), "shapes": not self._shape_edit.empty()}
+                   "instances": not self._inst_edit.empty(), "shapes": not self._shape_edit.empty(), "subdivs": not self._subdiv_edit.empty()}
         for blocker in _REFUSED_WHILE[kind]:
             if pending[blocker]:
                 raise VptError(f"{what}: hand the pending {_HAND_OUT[blocker]} first" + (why if blocker == "geometry" else ""))
@@ -479,6 +482,88 @@ class HostScene(_Handle):
         abi, keep = edit.to_abi()
         _host_call(host.vpth_scene_edit_shapes, self.handle, abi.remove_ids, abi.num_remove, abi.set_ids, abi.set, abi.num_set, abi.add, abi.num_add)
         del keep
+        return edit
+
+    # -- subdivision surfaces (the host side of vpt_scene_attach_subdiv / vpt_scene_update_subdivs): the scene keeps the cages it was
+    #    tesselated from.  set_subdiv edits a cage or a setting and runs the mirror's tesselate_surface; a change of cage positions or
+    #    displacement is noted in the pending SubdivEdit, which update_subdivs() hands out after update_bvh and make_lights; a change of
+    #    subdivisions or smooth - or any that gives the shape other counts or pools - is noted as a `set` of the pending ShapeEdit ------
+    _SUBDIV_CAGE = {"positions": (0, np.float32, 3), "normals": (1, np.float32, 3), "texcoords": (2, np.float32, 2),
+                    "quadspos": (3, np.int32, 4), "quadsnorm": (4, np.int32, 4), "quadstexcoord": (5, np.int32, 4)}
+
+    def _subdiv_item(self, index: int, kind: int, dtype, width: int) -> np.ndarray:
+        a = _filled(lambda ptr, n: host.vpth_scene_subdiv_plan_item(self.handle, index, kind, ptr, n), lambda n: np.zeros(n // 4, dtype),
+                    f"subdiv {index}: out of range, or its shape was removed")
+        return a.reshape((-1, width) if width else (-1,))
+
+    def subdiv(self, index: int) -> dict:
+        """subdiv `index` as the scene keeps it: id, shape, subdivisions, smooth, catmullclark, displacement, displacement_tex and the
+        cage - positions, normals (n, 3), texcoords (n, 2) float32, quadspos, quadsnorm, quadstexcoord (m, 4) int32 (copies)"""
+        settings, displacement = np.zeros(5, np.int32), C.c_float()
+        if host.vpth_scene_get_subdiv(self.handle, index, settings.ctypes.data, C.byref(displacement)) != 0:
+            raise VptError(f"subdiv {index} out of range")
+        out = {"id": index, "shape": int(settings[0]), "subdivisions": int(settings[1]), "smooth": bool(settings[2]), "catmullclark": bool(settings[3]),
+               "displacement": displacement.value, "displacement_tex": int(settings[4])}
+        out.update({name: self._subdiv_item(index, kind, dtype, width) for name, (kind, dtype, width) in self._SUBDIV_CAGE.items()})
+        return out
+
+    def subdivs(self) -> list:
+        """every subdiv of the scene, as subdiv() returns it"""
+        return [self.subdiv(i) for i in range(host.vpth_scene_subdiv_count(self.handle))]
+
+    def subdiv_plan(self, index: int) -> SubdivPlan:
+        """the tesselation plan of subdiv `index` as it is now (include/vpt.h: vpt_subdiv_plan), recorded by the mirror's own
+        tesselate_surface: what DeviceScene attaches before the subdiv's first edit"""
+        s = self.subdiv(index)
+        levels = [{name: self._subdiv_item(index, 16 + 8 * l + k, np.int32, width) for k, (name, width) in enumerate(LEVEL_TABLES.items(), 1)}
+                  for l in range(s["subdivisions"])]
+        normals = s["normals"] if len(s["quadsnorm"]) else s["normals"][:0]   # (normals no face names are not the shape's)
+        return SubdivPlan(s["shape"], s["subdivisions"], s["smooth"], s["displacement"], s["displacement_tex"], s["positions"], normals, levels,
+                          self._subdiv_item(index, 7, np.int32, 4), self._subdiv_item(index, 6, np.int32, 3))
+
+    def set_subdiv(self, index: int, positions=None, displacement: Optional[float] = None, subdivisions: Optional[int] = None,
+                   smooth: Optional[bool] = None) -> None:
+        """the cage's positions ((n, 3), same count), the displacement amount, the level or the smooth flag of subdiv `index` (None: as it
+        is): the mirror re-tesselates its shape at once.  positions / displacement are applied to a resident scene by update_subdivs()
+        and DeviceScene.update_subdivs; subdivisions / smooth change the shape's counts or pools and leave through update_shapes() as a
+        `set` of the shape - so does a displacement switched between zero and non-zero where that adds or drops the shape's normals."""
+        s = self.subdiv(index)
+        if s["shape"] < 0:
+            raise VptError(f"set_subdiv: the shape of subdiv {index} was removed")
+        amount = s["displacement"] if displacement is None else float(displacement)
+        normals_now = lambda d: s["smooth"] if d != 0 and s["displacement_tex"] >= 0 else len(s["quadsnorm"]) > 0
+        reshapes = subdivisions is not None or smooth is not None or (s["subdivisions"] == 0 and normals_now(amount) != normals_now(s["displacement"]))
+        if reshapes:
+            pend = self._begin_shape_change("set_subdiv")
+            if s["shape"] in pend.remove:
+                raise VptError(f"set_subdiv: shape {s['shape']} is also removed")
+        else:
+            self._may("set_subdiv", "vertices")
+        if positions is not None:
+            positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+            if positions.shape != s["positions"].shape:
+                raise VptError(f"set_subdiv: the cage of subdiv {index} has {len(s['positions'])} positions, got {len(positions)}")
+        resized = C.c_int(0)
+        _host_call(host.vpth_scene_set_subdiv, self.handle, index, None if positions is None else positions.ctypes.data,
+                   C.c_float(np.nan if displacement is None else displacement), -1 if subdivisions is None else int(subdivisions),
+                   -1 if smooth is None else int(bool(smooth)), C.byref(resized))
+        if resized.value or reshapes:
+            arrays = self.shape_arrays(s["shape"])
+            self._shape_edit.set[s["shape"]] = self._check_mesh("set_subdiv", mesh(**arrays))
+            return
+        was = self._subdiv_edit.subdivs.get(index, (None, None))
+        self._subdiv_edit.subdivs[index] = (was[0] if positions is None else positions.copy(), was[1] if displacement is None else float(displacement))
+        self._subdiv_edit.shape_of[index] = s["shape"]
+
+    def update_subdivs(self) -> SubdivEdit:
+        """update_bvh and make_lights of the host library over the shapes set_subdiv re-tesselated since the last call: desc / stats()
+        describe the edited scene afterwards.  Returns the SubdivEdit for DeviceScene.update_subdivs."""
+        edit, self._subdiv_edit = self._subdiv_edit, SubdivEdit()
+        if edit.empty():
+            return edit
+        _host_call(host.vpth_scene_update_bvh, self.handle)
+        _host_call(host.vpth_scene_update_lights, self.handle)
+        edit.plan_of = self.subdiv_plan
         return edit
 
     # -- environments and textures (the host side of vpt_scene_update_textures): the setters change the scene and note the change in

@@ -8,8 +8,8 @@ import numpy as np
 
 from ._abi import (DENOISE_ITERATIONS, DENOISE_SIGMA_ALBEDO, DENOISE_SIGMA_LUMINANCE, DENOISE_SIGMA_NORMAL, VptAdaptive, VptDenoise, VptPick,
                    VptSessionParams, _Handle, _check, _edit_call, _p, hip)
-from .device import DeviceScene, DisplayParams, PathtraceParams, PathtraceState
-from .edits import BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, TextureEdit, VolumeEdit
+from .device import DeviceScene, DisplayParams, PathtraceParams, PathtraceState, _subdiv_edit_call
+from .edits import BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, SubdivEdit, TextureEdit, VolumeEdit
 
 
 class RenderSession(_Handle):
@@ -134,6 +134,11 @@ class RenderSession(_Handle):
         """vpt_scene_update_shapes on the session's scene with the ShapeEdit of HostScene.update_shapes(), then a reset; a refused edit
         leaves the session as it was"""
         _edit_call(self.handle, "vpt_session_edit_shapes", edit)
+
+    def edit_subdivs(self, edit: SubdivEdit) -> None:
+        """vpt_scene_update_subdivs on the session's scene with the SubdivEdit of HostScene.update_subdivs(), then a reset; plans are
+        attached on the session's DeviceScene as DeviceScene.update_subdivs attaches them; a refused edit leaves the session as it was"""
+        _subdiv_edit_call(self.dev, hip.vpt_scene_attach_subdiv, hip.vpt_scene_subdiv_shape, self.handle, "vpt_session_edit_subdivs", edit)
 
     @property
     def size(self):
