@@ -871,7 +871,8 @@ int vpt_resolve_srgb8_device(const vpt_layout* layout, const void* d_tiles_all_r
  * padding slots and other ranks' slots are never touched.
  * Contract: from equal hits / rng a plane has the bits of `image` after vpt_render_device with the matching debug shader, hits and rng
  * are equal afterwards, and any batching of nsamples gives the same bits in every plane.  With params->samples == 1, ids / uvt are
- * those of vpt_intersect on the pixel-centre rays.  The pass reports what intersect_bvh sees: no SDF, no voxel grid.
+ * those of vpt_intersect on the pixel-centre rays.  The pass reports what intersect_bvh sees: no SDF, no voxel grid
+ * (those: vpt_render_sdf_aov_device, below).
  * vpt_render_aov_device: asynchronous on `stream`, one plain launch (no schedule, no pilot, no tile splitting); it allocates nothing
  * beyond what vpt_render_device would; nsamples == 0 is a no-op; params->shader is ignored.  VPT_ERR_INVALID_ARG when every plane is
  * null or uvt is given without ids.  The planes must be distinct buffers that do not overlap each other, hits or rng: each is updated
@@ -895,6 +896,54 @@ int vpt_resolve_ids_device(const vpt_layout* layout, const void* d_ids, const vo
                            void* d_uvt_rowmajor, void* stream);
 int vpt_render_aov(vpt_scene* scene, const vpt_params* params, int nsamples, int width, int height,
                    const vpt_aov_planes* planes, int32_t* hits, uint64_t* rng, int* samples_io);
+
+/* ---- first-hit AOVs of the implicit shaders: one sphere-traced pass -------------------------------------------
+ * The implicit counterpart of the pass above: what the SDF side of a scene - voxel-grid instances and analytic SDFs - shows under a
+ * pixel.  shade_implicit_normal draws no random number after the camera ray (yocto_pathtrace.cpp:538-562), so per sample and slot ->
+ * pixel (px, py) vpt_render_sdf_aov_device draws u, v and the lens sample exactly as vpt_render_device does (the pixel-centre branch
+ * of params->samples == 1 draws no jitter), evaluates eval_camera, runs ONE spheretrace(scene, ray, params->spheretrace_maxiter)
+ * (cpp:289-307, the march of the implicit kernels step for step) and gives every plane that is not null this sample's value:
+ *   normal   float4 per slot, sums: {normal * 0.5 + 0.5, 1} on a hit - what `implicit_normal` adds to `image` -, {0,0,0,0} on a miss;
+ *            the normal is eval_sdf_normal of the hit's grid instance or analytic SDF at (position, t), position = o + d * t
+ *   albedo   float4 per slot, sums: {color of the hit's material (vol_instances[i].material / sdfs[j].material, no texture), 1} on a
+ *            hit, {0,0,0,0} on a miss
+ *   depth    float4 per slot, sums: {t, 0, 0, 1} on a hit, {0,0,0,0} on a miss
+ *   ids      int32 x2 per slot: {vol_instance, sdf}, spheretrace_result's pair - exactly one of them >= 0 on a hit, {-1, -1} on a miss
+ *   hit      float4 per slot: {position.xyz, t} of the same hit, zeros on a miss.  ids / hit are written only by the sample that
+ *            finds hits[slot] == 0 - the state's first sample; later samples leave them alone, so they do not depend on batching.
+ * A FIRST hit is reported whatever the opacity of its material: `implicit` may step through a surface of opacity < 1 with a random
+ * draw, this pass draws nothing after the camera ray and reports the surface it meets first.  A sample's value that is not finite
+ * counts as zeros, decided per plane as for `image` (cpp:1087-1089).  hits and rng advance exactly as under `implicit_normal`.  The
+ * planes are tile-major in the layout's slots like `image` (the float planes resolve through vpt_resolve_device, ids / hit through
+ * vpt_resolve_sdf_ids_device); padding slots and other ranks' slots are never touched.  A scene with no grid instance and no SDF is
+ * not an error: every sample is a miss.
+ * Contract: from equal hits / rng, `normal` has the bits of `image` after vpt_render_device with `implicit_normal`, hits and rng are
+ * equal afterwards, and any batching of nsamples gives the same bits in every plane.  With params->samples == 1, ids and hit.w are
+ * vpt_spheretrace's {instance, sdf} and t on the pixel-centre rays.
+ * vpt_render_sdf_aov_device: asynchronous on `stream`, one plain launch (no schedule, no pilot, no tile splitting, no watchdog: a
+ * launch ends after at most nsamples x (spheretrace_maxiter + 1) rounds of the march); it allocates nothing; nsamples == 0 is a
+ * no-op; params->shader is ignored.  VPT_ERR_INVALID_ARG (the message names the argument) when every plane is null, hit is given
+ * without ids, two planes share a buffer, hits / rng / params / layout is null, or params->spheretrace_maxiter is outside
+ * [0, 1 << 20] (the range vpt_kat accepts); VPT_ERR_UNSUPPORTED when the scene's SDF records exceed the 64 KiB the implicit kernels
+ * copy to LDS.  The planes must not overlap each other, hits or rng (a partial overlap is the caller's to avoid).
+ * vpt_resolve_sdf_ids_device: the gathered ids / hit of ALL ranks ([nranks][slots]) -> row-major; d_hit and d_hit_rowmajor null together.
+ * vpt_render_sdf_aov: the same on host arrays, with vpt_render_aov's contract - `planes` holds HOST pointers to row-major planes (in
+ * and out: the float planes are sums), hits / rng are those of a row-major pathtrace_state; min(nsamples, params->samples -
+ * *samples_io) samples, a no-op at the cap.  Synchronous; buffers owned by the call.  Arguments are checked before a device is
+ * looked for, the scene last. */
+typedef struct vpt_sdf_aov_planes {
+  void* normal;     /* float4 per slot (pixel), or NULL */
+  void* albedo;
+  void* depth;
+  void* ids;        /* int32 x2 */
+  void* hit;        /* float4; needs ids */
+} vpt_sdf_aov_planes;
+int vpt_render_sdf_aov_device(vpt_scene* scene, const vpt_params* params, const vpt_layout* layout, int nsamples,
+                              const vpt_sdf_aov_planes* planes, void* d_hits, void* d_rng, void* stream);
+int vpt_resolve_sdf_ids_device(const vpt_layout* layout, const void* d_ids, const void* d_hit, void* d_ids_rowmajor,
+                               void* d_hit_rowmajor, void* stream);
+int vpt_render_sdf_aov(vpt_scene* scene, const vpt_params* params, int nsamples, int width, int height,
+                       const vpt_sdf_aov_planes* planes, int32_t* hits, uint64_t* rng, int* samples_io);
 
 /* ---- adaptive sampling: every pixel renders until its noise meets a target ---------------------------
  * A pixel that stops after k samples holds exactly the state k consecutive reference calls leave (image, rng, hits == k):
@@ -1165,7 +1214,7 @@ int  vpt_session_stats(const vpt_session* session, int* launches, int64_t* bytes
  *                element).  x / y outside the frame: VPT_ERR_INVALID_ARG.
  *   get_ids      the whole frame, row-major: ids int32 x2 and uvt float x3 per pixel, either pointer nullable, not both.
  * pick and get_ids return VPT_ERR_UNSUPPORTED when the session's shader is implicit or implicit_normal: what the user sees there
- * is not what the mesh BVH holds. */
+ * is not what the mesh BVH holds (vpt_session_pick_sdf / vpt_session_get_sdf_ids, below, serve those sessions). */
 typedef struct vpt_pick {
   int32_t hit;                  /* 0 / 1 */
   int32_t instance, element;
@@ -1175,6 +1224,29 @@ typedef struct vpt_pick {
 int  vpt_session_get_guides(vpt_session* session, float* normal, float* albedo);
 int  vpt_session_pick(vpt_session* session, int x, int y, vpt_pick* out);
 int  vpt_session_get_ids(vpt_session* session, int32_t* ids, float* uvt);
+/* ---- what is under a pixel of an implicit session ---------------------------------------------------------------
+ * The counterpart of pick / get_ids for a session whose shader is implicit or implicit_normal.  The id frame: {vol_instance, sdf}
+ * and {position, t} of every pixel, vpt_spheretrace's ids and t on the rays through the pixel centres at full resolution - one
+ * sample of vpt_render_sdf_aov_device with samples = 1 over hits / rng of its own, initialised on the device, then
+ * vpt_resolve_sdf_ids_device.  It is made by the first pick_sdf or get_sdf_ids after a reset (3 launches, buffers sized by the
+ * layout's slots and allocated then) and kept until the next reset.  Every edit resets, so it never names a grid instance or an SDF
+ * the scene no longer holds.
+ *   pick_sdf     the hit under pixel (x, y): one launch that packs the 48 bytes below and one copy of them.  volume and material
+ *                are those of the resident vol_instances[vol_instance] or sdfs[sdf] (volume -1 for an analytic SDF); normal is
+ *                eval_sdf_normal of that record at (position, distance): the bits VPT_KAT_SDF_NORMAL gives.  On a miss hit = 0,
+ *                the four ids are -1 and the floats 0.  x / y outside the frame: VPT_ERR_INVALID_ARG.
+ *   get_sdf_ids  the whole frame, row-major: ids int32 x2 and hit float x4 per pixel, either pointer nullable, not both.
+ * Both return VPT_ERR_UNSUPPORTED under a mesh shader (use vpt_session_pick / vpt_session_get_ids there). */
+typedef struct vpt_sdf_pick {
+  int32_t hit;                  /* 0 / 1 */
+  int32_t vol_instance, sdf;    /* exactly one >= 0 on a hit */
+  int32_t volume, material;
+  float   distance;
+  float   position[3];
+  float   normal[3];
+} vpt_sdf_pick;
+int  vpt_session_pick_sdf(vpt_session* session, int x, int y, vpt_sdf_pick* out);
+int  vpt_session_get_sdf_ids(vpt_session* session, int32_t* ids, float* hit);
 /* ---- adaptive sampling in a session ------------------------------------------------------------------------
  * vpt_session_set_adaptive adopts the settings and resets; NULL switches the mode off (and resets).  Checked like
  * vpt_render_adaptive: threshold finite and >= 0, step >= 1, 1 <= min_samples <= render.samples (VPT_ERR_INVALID_ARG; a refused

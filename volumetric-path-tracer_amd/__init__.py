@@ -17,7 +17,7 @@ from .edits import (BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, SubdivEdit, 
                     mesh)
 from .device import (AdaptiveRun, DeviceScene, DisplayParams, MultiDeviceScene, PathtraceParams, PathtraceState, box3_device,   # noqa: F401
                      device_count, layout_pixel_index, layout_slots, make_state_jump, resolve_device, resolve_hits_device, resolve_ids_device,
-                     resolve_srgb8_device, selftest_reciprocal, state_download, state_init_device, state_upload)
+                     resolve_sdf_ids_device, resolve_srgb8_device, selftest_reciprocal, state_download, state_init_device, state_upload)
 from .host_scene import (BakedVolume, HostScene, bake_sdf, bake_sdf_grid, bake_triangles, build_bvh, catmullclark, displace_vertices,   # noqa: F401
                          fit_volume, save_volume, vertex_normals)
 from .session import RenderSession   # noqa: F401

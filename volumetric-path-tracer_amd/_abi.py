@@ -68,6 +68,18 @@ class VptPick(C.Structure):  # vpt_pick
                 ("u", C.c_float), ("v", C.c_float), ("distance", C.c_float)]
 
 
+SDF_AOV_PLANES = ("normal", "albedo", "depth", "ids", "hit")
+
+
+class VptSdfAovPlanes(C.Structure):  # vpt_sdf_aov_planes: any of them None
+    _fields_ = [(name, C.c_void_p) for name in SDF_AOV_PLANES]
+
+
+class VptSdfPick(C.Structure):  # vpt_sdf_pick
+    _fields_ = [("hit", C.c_int32), ("vol_instance", C.c_int32), ("sdf", C.c_int32), ("volume", C.c_int32), ("material", C.c_int32),
+                ("distance", C.c_float), ("position", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
 class VptFrame(C.Structure):  # vpt_frame: x, y, z, o
     _fields_ = [("x", C.c_float * 3), ("y", C.c_float * 3), ("z", C.c_float * 3), ("o", C.c_float * 3)]
 
@@ -315,6 +327,11 @@ hip.vpt_render_aov.argtypes = [_p, C.POINTER(VptParams), C.c_int, C.c_int, C.c_i
 hip.vpt_session_get_guides.argtypes = [_p, _p, _p]
 hip.vpt_session_pick.argtypes = [_p, C.c_int, C.c_int, C.POINTER(VptPick)]
 hip.vpt_session_get_ids.argtypes = [_p, _p, _p]
+hip.vpt_render_sdf_aov_device.argtypes = [_p, C.POINTER(VptParams), C.POINTER(VptLayout), C.c_int, C.POINTER(VptSdfAovPlanes), _p, _p, _p]
+hip.vpt_resolve_sdf_ids_device.argtypes = [C.POINTER(VptLayout), _p, _p, _p, _p, _p]
+hip.vpt_render_sdf_aov.argtypes = [_p, C.POINTER(VptParams), C.c_int, C.c_int, C.c_int, C.POINTER(VptSdfAovPlanes), _p, _p, C.POINTER(C.c_int)]
+hip.vpt_session_pick_sdf.argtypes = [_p, C.c_int, C.c_int, C.POINTER(VptSdfPick)]
+hip.vpt_session_get_sdf_ids.argtypes = [_p, _p, _p]
 hip.vpt_last_kernel_ms.argtypes = [_p, C.POINTER(C.c_float)]
 hip.vpt_intersect.argtypes = [_p, C.c_int, _p, C.c_int, _p, _p]
 hip.vpt_build_bvh.argtypes = [C.c_int, _p, C.c_int, _p, C.c_int, C.POINTER(C.c_int), _p]

@@ -10,14 +10,7 @@
 //  * the general leaf and attribute records, as the debug shaders read them.
 #pragma once
 #include "vpt_mesh_kernel.hip.h"
-
-// one sample's value into a sum plane; a value that is not finite counts as zeros (K1's finish, cpp:1087-1089), decided per plane
-VPT_DEV void aov_add(float4* __restrict__ plane, int slot, f3 v, float alpha) {
-  f4 rad = mk4(v.x, v.y, v.z, alpha);
-  if (!(isfinite(rad.x) && isfinite(rad.y) && isfinite(rad.z) && isfinite(rad.w))) rad = mk4(0, 0, 0, 0);
-  const float4 a = plane[slot];
-  plane[slot] = make_float4(a.x + rad.x, a.y + rad.y, a.z + rad.z, a.w + rad.w);
-}
+#include "vpt_aov_add.hip.h"   // aov_add: one sample's value into a sum plane
 
 template <bool SPILL, bool CURVES>
 __global__ void vpt_aov_kernel(DScene sc, DParams pr, aov_planes pl, int* __restrict__ hits, ulonglong2* __restrict__ rngs, stack_cfg stack) {

@@ -16,6 +16,7 @@
 #include "vpt_error.h"
 #include "vpt_kernels.hip.h"   // slot_to_pixel
 #include "vpt_rng_jump.h"
+#include "vpt_sdf_aov.h"   // vpt_sdf_pick_device
 #include "vpt_srgb.hip.h"
 
 namespace {
@@ -211,6 +212,11 @@ struct vpt_session {
   long long                i_pixels = 0, i_slots = 0;     // what they were allocated for (0: nothing)
   bool                     ids_valid = false;
   std::vector<vpt_instance> instances;                    // the scene's instance table as of the id frame: a pick's shape and material
+  // the id frame of an implicit session (pick_sdf, get_sdf_ids): the same life, the planes of vpt_render_sdf_aov_device
+  device_buffer q_hits, q_rng, q_ids, q_hit;              // the state and the planes of its one-sample pass, tile-major
+  device_buffer sdf_ids, sdf_hit, sdf_pick;               // row-major; the 48 bytes of a pick
+  long long     q_pixels = 0, q_slots = 0;                // what they were allocated for (0: nothing)
+  bool          sdf_ids_valid = false;
   // what the last call cost
   int     launches = 0;
   int64_t up = 0, down = 0;
@@ -262,7 +268,7 @@ int check_session_adaptive(const vpt_adaptive* a, int samples) {
 }
 
 int allocate(vpt_session* s, int width, int height, int pw, int ph, bool denoise) {
-  s->width = s->height = 0, s->denoise_allocated = false, s->r_pixels = 0, s->i_pixels = s->i_slots = 0;   // a new frame: the lazily made buffers go with the old one
+  s->width = s->height = 0, s->denoise_allocated = false, s->r_pixels = 0, s->i_pixels = s->i_slots = 0, s->q_pixels = s->q_slots = 0;   // a new frame: the lazily made buffers go with the old one
   const vpt_layout lay = {width, height, 8, 8, 0, 1}, play = {pw, ph, 8, 8, 0, 1};
   const long long  slots = vpt_layout_slots(&lay), pslots = vpt_layout_slots(&play);
   if (slots < 0 || pslots < 0) return VPT_ERR_INVALID_ARG;
@@ -351,6 +357,35 @@ int ensure_ids(vpt_session* s) {
   return VPT_OK;
 }
 
+// the id frame of an implicit session (include/vpt.h: vpt_session_pick_sdf): one sample of the sphere-traced first-hit pass in the
+// pixel-centre branch at full resolution over a state of its own
+int ensure_sdf_ids(vpt_session* s) {
+  REQUIRE(s->width > 0, "the session holds no frame (a reset failed)");
+  if (!implicit_shader(s->p.render.shader))
+    return vpt_set_error(VPT_ERR_UNSUPPORTED, "the session renders a mesh shader: use vpt_session_pick / vpt_session_get_ids");
+  if (s->sdf_ids_valid) return VPT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t n = (size_t)s->width * s->height, slots = (size_t)vpt_layout_slots(&s->lay);
+  if (s->q_pixels != (long long)n || s->q_slots != (long long)slots) {   // one entry per tile-major SLOT, as ensure_ids
+    s->q_pixels = s->q_slots = 0;
+    using sized = std::pair<device_buffer*, size_t>;
+    const sized frame[] = {{&s->q_hits, slots * 4}, {&s->q_rng, slots * 16}, {&s->q_ids, slots * 8}, {&s->q_hit, slots * 16}, {&s->sdf_ids, n * 8},
+        {&s->sdf_hit, n * 16}, {&s->sdf_pick, sizeof(vpt_sdf_pick)}};
+    for (auto& [b, bytes] : frame)
+      if (int rc = b->allocate(bytes)) return rc;
+    s->q_pixels = (long long)n, s->q_slots = (long long)slots;
+  }
+  vpt_params p = s->p.render;
+  p.samples    = 1;
+  if (int rc = state_init(&s->lay, nullptr, s->q_hits.get(), s->q_rng.get(), s->st)) return rc;
+  const vpt_sdf_aov_planes planes = {nullptr, nullptr, nullptr, s->q_ids.get(), s->q_hit.get()};
+  if (int rc = vpt_render_sdf_aov_device(s->scene, &p, &s->lay, 1, &planes, s->q_hits.get(), s->q_rng.get(), s->st)) return rc;
+  if (int rc = vpt_resolve_sdf_ids_device(&s->lay, s->q_ids.get(), s->q_hit.get(), s->sdf_ids.get(), s->sdf_hit.get(), s->st)) return rc;
+  s->launches += 3;
+  s->sdf_ids_valid = true;
+  return VPT_OK;
+}
+
 int reset(vpt_session* s, const vpt_session_params& np) {
   vpt_camera cam;
   if (int rc = vpt_scene_get_camera(s->scene, np.render.camera, &cam)) return rc;
@@ -364,7 +399,7 @@ int reset(vpt_session* s, const vpt_session_params& np) {
   drop_run(s);                            // an adaptive run ends here; the first advance makes the next
   if (width != s->width || height != s->height || pw != s->pw || ph != s->ph || (np.denoise != 0) != s->denoise_allocated)
     if (int rc = allocate(s, width, height, pw, ph, np.denoise != 0)) return rc;
-  s->p = np, s->samples = 0, s->a = 0, s->filtered_valid = false, s->has_albedo = false, s->ids_valid = false;
+  s->p = np, s->samples = 0, s->a = 0, s->filtered_valid = false, s->has_albedo = false, s->ids_valid = false, s->sdf_ids_valid = false;
   if (np.denoise) {
     if (implicit_shader(np.render.shader)) {
       if (int rc = render_guide(s, VPT_SHADER_IMPLICIT_NORMAL, s->normal.get())) return rc;
@@ -662,6 +697,37 @@ int vpt_session_pick(vpt_session* s, int x, int y, vpt_pick* out) {
   HIP_TRY(hipStreamSynchronize(s->st));
   *out = {rec.hit, rec.instance, rec.element, -1, -1, rec.u, rec.v, rec.distance};
   if (rec.hit && (size_t)rec.instance < s->instances.size()) out->shape = s->instances[(size_t)rec.instance].shape, out->material = s->instances[(size_t)rec.instance].material;
+  return VPT_OK;
+}
+
+int vpt_session_get_sdf_ids(vpt_session* s, int32_t* ids, float* hit) {
+  REQUIRE(s, "null session");
+  REQUIRE(ids || hit, "null ids and hit: nothing to fetch");
+  HIP_TRY(hipSetDevice(s->device));
+  begin_call(s);
+  if (int rc = ensure_sdf_ids(s)) return rc;
+  const size_t n = (size_t)s->width * s->height;
+  if (ids)
+    if (int rc = fetch(s, ids, s->sdf_ids, n * 8)) return rc;
+  if (hit)
+    if (int rc = fetch(s, hit, s->sdf_hit, n * 16)) return rc;
+  HIP_TRY(hipStreamSynchronize(s->st));
+  return VPT_OK;
+}
+
+int vpt_session_pick_sdf(vpt_session* s, int x, int y, vpt_sdf_pick* out) {
+  static_assert(sizeof(vpt_sdf_pick) == 48, "the 48 bytes of a pick");
+  REQUIRE(s && out, "null argument");
+  REQUIRE(s->width > 0, "the session holds no frame (a reset failed)");
+  REQUIRE(x >= 0 && x < s->width && y >= 0 && y < s->height, "pixel (%d, %d) outside the %d x %d frame", x, y, s->width, s->height);
+  HIP_TRY(hipSetDevice(s->device));
+  begin_call(s);
+  if (int rc = ensure_sdf_ids(s)) return rc;
+  if (int rc = vpt_sdf_pick_device(s->scene, s->sdf_ids.get(), s->sdf_hit.get(), (long long)y * s->width + x, s->sdf_pick.get(), s->st)) return rc;
+  s->launches++;
+  HIP_TRY(hipMemcpyAsync(out, s->sdf_pick.get(), sizeof(vpt_sdf_pick), hipMemcpyDeviceToHost, s->st));
+  s->down += (int64_t)sizeof(vpt_sdf_pick);
+  HIP_TRY(hipStreamSynchronize(s->st));
   return VPT_OK;
 }
 

@@ -8,7 +8,7 @@ from typing import TYPE_CHECKING, Optional
 
 import numpy as np
 
-from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SHADER_NAMES, VptAdaptive, VptAovPlanes, VptDisplay, VptError, VptLayout, VptParams,
+from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SDF_AOV_PLANES, SHADER_NAMES, VptAdaptive, VptAovPlanes, VptSdfAovPlanes, VptDisplay, VptError, VptLayout, VptParams,
                    VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, _counted, _edit_call, _p, hip, host)
 from .edits import BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit
 
@@ -185,6 +185,43 @@ class DeviceScene(_Handle):
         abi, pl, samples = params.to_abi(), VptAovPlanes(**{k: a.ctypes.data for k, a in out.items()}), C.c_int(state.samples)
         _check(hip.vpt_render_aov(self.handle, C.byref(abi), count, state.width, state.height, C.byref(pl), state.hits.ctypes.data,
                                   state.rngs.ctypes.data, C.byref(samples)), "vpt_render_aov")
+        state.samples = samples.value
+        return out
+
+    def render_sdf_aov_device(self, params: PathtraceParams, layout: VptLayout, nsamples: int, planes: dict, d_hits: int, d_rng: int,
+                              stream: int = 0) -> None:
+        """vpt_render_sdf_aov_device on this rank's tile-major slots: `planes` maps names of SDF_AOV_PLANES to raw device pointers"""
+        unknown = set(planes) - set(SDF_AOV_PLANES)
+        if unknown:
+            raise VptError(f"unknown SDF AOV plane {sorted(unknown)[0]!r}: expected one of {SDF_AOV_PLANES}")
+        abi, pl = params.to_abi(), VptSdfAovPlanes(**{k: v for k, v in planes.items() if v})
+        _check(hip.vpt_render_sdf_aov_device(self.handle, C.byref(abi), C.byref(layout), nsamples, C.byref(pl), d_hits, d_rng, stream),
+               "vpt_render_sdf_aov_device")
+
+    def render_sdf_aovs(self, state: PathtraceState, params: PathtraceParams, nsamples: int = 1, planes=SDF_AOV_PLANES,
+                        into: Optional[dict] = None) -> dict:
+        """the sphere-traced first-hit pass (vpt_render_sdf_aov, include/vpt.h) over the hits / rngs of `state` (its image is left alone):
+        `nsamples` more samples, at most params.samples in all, every camera ray marched once for every plane named in `planes`.  Returns
+        {name: array}: the sums normal / albedo / depth as (h, w, 4) float32 - divide by state.samples, as get_render does - and ids
+        (h, w, 2) int32 {vol_instance, sdf}, hit (h, w, 4) float32 {position, t} of the state's first sample.  `into`: the dict an earlier
+        call returned, to go on from (batching is exact)."""
+        out = {}
+        for name in planes:
+            if name not in SDF_AOV_PLANES:
+                raise VptError(f"unknown SDF AOV plane {name!r}: expected one of {SDF_AOV_PLANES}")
+            tail, dtype = ((2,), np.int32) if name == "ids" else ((4,), np.float32)
+            shape = (state.height, state.width) + tail
+            a = into.get(name) if into else None
+            if a is None:
+                a = np.zeros(shape, dtype)
+            elif a.shape != shape or a.dtype != dtype or not a.flags["C_CONTIGUOUS"]:
+                raise VptError(f"plane {name!r}: expected a contiguous {np.dtype(dtype).name} array of shape {shape}")
+            out[name] = a
+        for a in (state.hits, state.rngs):
+            assert a.flags["C_CONTIGUOUS"]
+        abi, pl, samples = params.to_abi(), VptSdfAovPlanes(**{k: a.ctypes.data for k, a in out.items()}), C.c_int(state.samples)
+        _check(hip.vpt_render_sdf_aov(self.handle, C.byref(abi), nsamples, state.width, state.height, C.byref(pl), state.hits.ctypes.data,
+                                      state.rngs.ctypes.data, C.byref(samples)), "vpt_render_sdf_aov")
         state.samples = samples.value
         return out
 
@@ -557,6 +594,11 @@ def resolve_srgb8_device(layout: VptLayout, d_tiles_all: int, samples: int, d_rg
 def resolve_ids_device(layout: VptLayout, d_ids_all: int, d_uvt_all: Optional[int], d_ids_rows: int, d_uvt_rows: Optional[int], stream: int = 0):
     """vpt_resolve_ids_device: the ids / uvt planes of all ranks, tile-major -> row-major (the uvt pair None together)"""
     _check(hip.vpt_resolve_ids_device(C.byref(layout), d_ids_all, d_uvt_all, d_ids_rows, d_uvt_rows, stream), "vpt_resolve_ids_device")
+
+
+def resolve_sdf_ids_device(layout: VptLayout, d_ids_all: int, d_hit_all: Optional[int], d_ids_rows: int, d_hit_rows: Optional[int], stream: int = 0):
+    """vpt_resolve_sdf_ids_device: the ids / hit planes of all ranks, tile-major -> row-major (the hit pair None together)"""
+    _check(hip.vpt_resolve_sdf_ids_device(C.byref(layout), d_ids_all, d_hit_all, d_ids_rows, d_hit_rows, stream), "vpt_resolve_sdf_ids_device")
 
 
 def state_init_device(layout: VptLayout, d_image: int, d_hits: int, d_rng: int, stream: int = 0) -> None:

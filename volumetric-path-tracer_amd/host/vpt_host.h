@@ -316,6 +316,20 @@ struct pathtrace_aov_images {
 };
 pathtrace_aov_images pathtrace_aovs(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights, const pathtrace_params& params,
     int samples = 16, unsigned planes = aov_all);
+// Extension: the first-hit AOVs of the implicit shaders in one sphere-traced pass (include/vpt.h: vpt_render_sdf_aov), as pathtrace_aovs:
+// a fresh make_state, `samples` samples, every camera ray marched once through spheretrace(scene, ray, params.spheretrace_maxiter).
+// normal has the bits of get_render after `samples` passes of `implicit_normal`; albedo is the hit material's colour; depth is {mean t
+// over the samples, 0, 0, coverage}; ids / hit are {vol_instance, sdf} and {position, t} of each pixel's first sample ({-1, -1} and
+// zeros on a miss).  A first hit is reported whatever its material's opacity.  params.shader is ignored; meshes are not seen.
+// `planes`: which of them to render (sdf_aov_ids brings hit along); the others are left empty.
+enum sdf_aov_plane : unsigned { sdf_aov_normal = 1, sdf_aov_albedo = 2, sdf_aov_depth = 4, sdf_aov_ids = 8, sdf_aov_all = 15 };
+struct pathtrace_sdf_aov_images {
+  color_image   normal = {}, albedo = {}, depth = {};
+  vector<vec2i> ids = {};
+  vector<vec4f> hit = {};
+};
+pathtrace_sdf_aov_images pathtrace_sdf_aovs(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights,
+    const pathtrace_params& params, int samples = 16, unsigned planes = sdf_aov_all);
 // The two guide renders of `params`' camera and resolution: a fresh make_state, `samples` passes of the `normal` and the `color` shader,
 // get_render - for the mesh shaders both out of one pathtrace_aovs pass (the same bits).  For the implicit shaders: `implicit_normal`
 // through pathtrace_samples, and no albedo (left empty).

@@ -765,6 +765,38 @@ pathtrace_aov_images pathtrace_aovs(const scene_data& scene, const bvh_scene& bv
   return out;
 }
 
+pathtrace_sdf_aov_images pathtrace_sdf_aovs(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights,
+    const pathtrace_params& params, int samples, unsigned planes) {
+  if (samples < 1) throw std::invalid_argument{"aov samples must be >= 1"};
+  if ((planes & sdf_aov_all) == 0) throw std::invalid_argument{"no aov plane asked for"};
+  auto handle = (vpt_scene*)nullptr;
+  {
+    auto lock = std::lock_guard{cache_mutex};
+    handle    = single_scene(scene, bvh, lights);
+  }
+  auto p    = params;
+  p.shader  = pathtrace_shader_type::implicit_normal, p.samples = samples;
+  auto state = make_state(scene, p);
+  auto n     = (size_t)state.width * state.height;
+  auto out   = pathtrace_sdf_aov_images{};
+  auto abi   = vpt_sdf_aov_planes{};
+  auto sums  = [&](unsigned bit, color_image& image) -> void* {
+    if (!(planes & bit)) return nullptr;
+    image = color_image{state.width, state.height, true, vector<vec4f>(n)};
+    return image.pixels.data();
+  };
+  abi.normal = sums(sdf_aov_normal, out.normal), abi.albedo = sums(sdf_aov_albedo, out.albedo), abi.depth = sums(sdf_aov_depth, out.depth);
+  if (planes & sdf_aov_ids) out.ids.resize(n), out.hit.resize(n), abi.ids = out.ids.data(), abi.hit = out.hit.data();
+  static_assert(sizeof(vec2i) == 8 && sizeof(vec4f) == 16, "plane layout");
+  auto pabi = to_abi(p);
+  if (vpt_render_sdf_aov(handle, &pabi, samples, state.width, state.height, &abi, state.hits.data(), (uint64_t*)state.rngs.data(), &state.samples) != VPT_OK)
+    throw std::runtime_error{string{"vpt_render_sdf_aov: "} + vpt_last_error()};
+  auto scale = 1.0f / (float)state.samples;   // get_render
+  for (auto image : {&out.normal, &out.albedo, &out.depth})
+    for (auto& q : image->pixels) q = {q.x * scale, q.y * scale, q.z * scale, q.w * scale};
+  return out;
+}
+
 void pathtrace_release(const scene_data& scene) {
   auto lock = std::lock_guard{cache_mutex};
   device_cache().erase(&scene);

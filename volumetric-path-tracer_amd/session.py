@@ -7,7 +7,7 @@ from typing import Optional
 import numpy as np
 
 from ._abi import (DENOISE_ITERATIONS, DENOISE_SIGMA_ALBEDO, DENOISE_SIGMA_LUMINANCE, DENOISE_SIGMA_NORMAL, VptAdaptive, VptDenoise, VptPick,
-                   VptSessionParams, _Handle, _check, _edit_call, _p, hip)
+                   VptSdfPick, VptSessionParams, _Handle, _check, _edit_call, _p, hip)
 from .device import DeviceScene, DisplayParams, PathtraceParams, PathtraceState, _subdiv_edit_call
 from .edits import BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, SubdivEdit, TextureEdit, VolumeEdit
 
@@ -202,6 +202,26 @@ class RenderSession(_Handle):
         ids, uvt = np.zeros((h, w, 2), np.int32), np.zeros((h, w, 3), np.float32)
         _check(hip.vpt_session_get_ids(self.handle, ids.ctypes.data, uvt.ctypes.data), "vpt_session_get_ids")
         return ids, uvt
+
+    def pick_sdf(self, x: int, y: int) -> Optional[dict]:
+        """what is under pixel (x, y) of an implicit session's frame (vpt_session_pick_sdf): None on a miss, else a dict of vol_instance,
+        sdf (exactly one >= 0), volume (-1 for an analytic SDF), material, distance, position, normal.  48 bytes cross PCIe; the first
+        pick_sdf or sdf_ids() after a reset makes the id frame."""
+        out = VptSdfPick()
+        _check(hip.vpt_session_pick_sdf(self.handle, x, y, C.byref(out)), "vpt_session_pick_sdf")
+        if not out.hit:
+            return None
+        pick = {name: getattr(out, name) for name in ("vol_instance", "sdf", "volume", "material", "distance")}
+        pick["position"], pick["normal"] = np.array(out.position[:], np.float32), np.array(out.normal[:], np.float32)
+        return pick
+
+    def sdf_ids(self):
+        """the id frame of an implicit session (vpt_session_get_sdf_ids): (ids, hit) = (h, w, 2) int32 {vol_instance, sdf} (-1, -1 on a
+        miss) and (h, w, 4) float32 {position, t} of the rays through the pixel centres (zeros on a miss)"""
+        w, h = self.size
+        ids, hit = np.zeros((h, w, 2), np.int32), np.zeros((h, w, 4), np.float32)
+        _check(hip.vpt_session_get_sdf_ids(self.handle, ids.ctypes.data, hit.ctypes.data), "vpt_session_get_sdf_ids")
+        return ids, hit
 
     def stats(self):
         """(kernel launches, bytes to the device, bytes to the host) of the last call on the session"""
