@@ -487,6 +487,50 @@ int vpt_scene_get_volumes(vpt_scene* scene, vpt_volume* volumes, int volume_capa
 /* the voxels of one volume as the device holds them (x + y*W + z*W*H); capacity in voxels, at least the volume's W*H*D */
 int vpt_scene_get_voxels(vpt_scene* scene, int volume, float* voxels, int64_t capacity);
 
+/* ---- sculpting the voxel grids of a resident scene with analytic SDF brushes ------------------------------------------
+ * An edit of its own: vpt_volume_source keeps its layout and its two modes.  A stamp is an analytic brush (a vpt_sdf; its material is
+ * ignored), an op and a blend width; an entry names a volume, a box of its voxels, the grid those voxels are sampled on and a run of the
+ * edit's stamps - a stroke.  The kernel evaluates the brushes where the voxels live: no voxel crosses PCIe in either direction, a stroke
+ * of any length reads and writes each voxel of its region once.  whd and res never change, so no record, no light table and no pool
+ * layout is touched: only the voxels inside each entry's region change, every other voxel keeps its bits.
+ * The rule, written once in csrc/vpt_sculpt_rule.h (compiled by the kernel and by the host mirror, host/vpt_sculpt.cpp, both with
+ * -ffp-contract=off: float32, nothing fused, every sum in the order that header writes, division and square root the IEEE operations):
+ *  - Sample point.  Voxel (i, j, k) is sampled at origin + (float)i * step per axis: vpt_bake_sdf's rule and the same voxel space as a
+ *    bake.  Stored values are distances in that space, as a bake's are.
+ *  - Brush distance.  f(transform_point(brush.frame, sample)), the reference's sdf.f(transform_point(sdf.frame, p)) (yocto_sdfs.cpp:21),
+ *    f one of the six sd_* as yocto_sceneio.cpp:3684-3730 binds them (the table at vpt_sdf), with the reference's ternary abs / min / max
+ *    (yocto_math.h:1354-1356) in the reference's term order.
+ *  - Combination, a the resident value, b the brush distance, k = blend.  REPLACE: b.  With k == 0: UNION (a < b) ? a : b; SUBTRACT
+ *    (-b > a) ? -b : a, the reference's op_subtraction(brush, resident) (yocto_sdfs.h:87); INTERSECT (a > b) ? a : b - selects, never
+ *    fminf / fmaxf: a NaN resident value is replaced by UNION and INTERSECT and kept with its bits by SUBTRACT.  With k > 0 the polynomial
+ *    smooth minimum  m = (x < y) ? x : y; d = x - y; ad = d < 0 ? -d : d; t = k - ad; h = (t > 0 ? t : 0) / k;
+ *    smin = m - ((h * h) * k) * 0.25f:  UNION smin(a, b), SUBTRACT -smin(b, -a), INTERSECT -smin(-a, -b).  REPLACE ignores blend.
+ *  - A stroke.  The stamps first_stamp .. first_stamp + num_stamps of an entry are applied to each voxel in list order,
+ *    v = op_s(v, brush_s(sample)): a stroke of N stamps equals N one-stamp edits bit for bit.  Every voxel of the region evaluates every
+ *    stamp.  Entries run in order, and a volume id may repeat: the launches are ordered on one stream.
+ *  - Validation before anything is written (VPT_ERR_INVALID_ARG, the message names the entry or the stamp, the scene is untouched): the
+ *    volume id in range; the region inside the resident whd; the stamp range inside the edit's list; type 0..5 and op 0..3; every float
+ *    finite (frame, whd, p, origin, step, blend) and blend >= 0.  An entry whose region voxels x num_stamps exceeds 2^36 is refused with
+ *    VPT_ERR_UNSUPPORTED (split the stroke): one launch on a shared GPU stays short.
+ *  - An entry with an empty region or no stamps launches nothing.  vpt_scene_update_stats afterwards: launches = one per entry that is
+ *    neither; bytes = VPT_SCULPT_RECORD_BYTES per stamp of the edit's list, uploaded in one copy when anything is launched (0 otherwise) -
+ *    not one voxel.  An edit without entries starts the counters again at (0, 0).
+ *  - Synchronisation, the VPT_ERR_HIP semantics and the forgetting of the launch-schedule record: those of vpt_scene_update. */
+enum { VPT_SCULPT_REPLACE = 0, VPT_SCULPT_UNION = 1, VPT_SCULPT_SUBTRACT = 2, VPT_SCULPT_INTERSECT = 3 };
+#define VPT_SCULPT_RECORD_BYTES 80   /* one stamp as the device reads it: frame, four parameters, type | op << 8, blend */
+typedef struct vpt_sculpt_stamp { vpt_sdf brush; int32_t op; float blend; } vpt_sculpt_stamp;
+typedef struct vpt_sculpt_entry {
+  int32_t volume;
+  int32_t region_lo[3], region_whd[3];  /* the box of voxels this entry changes */
+  float   origin[3], step[3];           /* voxel (i, j, k) is sampled at origin + (i, j, k) * step */
+  int32_t first_stamp, num_stamps;      /* its stroke inside edit->stamps */
+} vpt_sculpt_entry;
+typedef struct vpt_sculpt_edit {
+  int32_t num_entries; const vpt_sculpt_entry* entries;
+  int32_t num_stamps;  const vpt_sculpt_stamp* stamps;
+} vpt_sculpt_edit;
+int vpt_scene_sculpt_volumes(vpt_scene* scene, const vpt_sculpt_edit* edit);
+
 /* ---- the BVHs of a resident scene built anew on the device ------------------------------------------------------------
  * The four edits above keep a tree's topology as creation left it: vpt_scene_update is the reference's update_bvh, a refit.  After a
  * real deformation, or after instances have been rearranged, boxes and renders stay correct but the tree no longer fits the geometry.
@@ -796,6 +840,8 @@ int  vpt_multi_update_lights(vpt_multi* m, const vpt_scene_edit* edit);
 int  vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit);
 /* vpt_scene_update_volumes in the same way (a bake entry is prepared and baked once per device) */
 int  vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit);
+/* vpt_scene_sculpt_volumes in the same way: the same stamps run on every device */
+int  vpt_multi_sculpt_volumes(vpt_multi* m, const vpt_sculpt_edit* edit);
 /* vpt_scene_rebuild_bvh in the same way: every device builds its own trees; the arrays are equal by construction */
 int  vpt_multi_rebuild_bvh(vpt_multi* m, const vpt_bvh_rebuild* what);
 int  vpt_multi_rebuild_bvh_quality(vpt_multi* m, const vpt_bvh_rebuild* what, int quality);   /* vpt_scene_rebuild_bvh_quality on every device */
@@ -1183,6 +1229,8 @@ int  vpt_session_edit_lights(vpt_session* session, const vpt_scene_edit* edit);
 int  vpt_session_edit_textures(vpt_session* session, const vpt_texture_edit* edit);
 /* vpt_scene_update_volumes, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_edit_volumes(vpt_session* session, const vpt_volume_edit* edit);
+/* vpt_scene_sculpt_volumes, then a reset; a refused edit leaves the session as it was */
+int  vpt_session_sculpt_volumes(vpt_session* session, const vpt_sculpt_edit* edit);
 /* vpt_scene_rebuild_bvh, then a reset (the picture is the same, its accumulation restarts as after the session's other edits); a refused call leaves the session as it was */
 int  vpt_session_rebuild_bvh(vpt_session* session, const vpt_bvh_rebuild* what);
 int  vpt_session_rebuild_bvh_quality(vpt_session* session, const vpt_bvh_rebuild* what, int quality);   /* vpt_scene_rebuild_bvh_quality, then a reset */

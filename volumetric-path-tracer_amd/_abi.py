@@ -142,8 +142,25 @@ class VptVolumeEdit(C.Structure):  # vpt_volume_edit
                 ("num_voxels", C.c_int64), ("voxels", C.c_void_p)]
 
 
+class VptSculptStamp(C.Structure):  # vpt_sculpt_stamp
+    _fields_ = [("brush", VptSdf), ("op", C.c_int32), ("blend", C.c_float)]
+
+
+class VptSculptEntry(C.Structure):  # vpt_sculpt_entry
+    _fields_ = [("volume", C.c_int32), ("region_lo", C.c_int32 * 3), ("region_whd", C.c_int32 * 3), ("origin", C.c_float * 3), ("step", C.c_float * 3),
+                ("first_stamp", C.c_int32), ("num_stamps", C.c_int32)]
+
+
+class VptSculptEdit(C.Structure):  # vpt_sculpt_edit
+    _fields_ = [("num_entries", C.c_int32), ("entries", C.c_void_p), ("num_stamps", C.c_int32), ("stamps", C.c_void_p)]
+
+
+assert C.sizeof(VptSculptStamp) == 92 and C.sizeof(VptSculptEntry) == 60 and C.sizeof(VptSculptEdit) == 32
+
 SDF_TYPES = ["bbox", "box", "capped_cone", "plane", "sphere", "torus"]
 VOXELS_REPLACE, VOXELS_UNION = 0, 1
+SCULPT_REPLACE, SCULPT_UNION, SCULPT_SUBTRACT, SCULPT_INTERSECT = 0, 1, 2, 3
+SCULPT_RECORD_BYTES = 80   # VPT_SCULPT_RECORD_BYTES: one stamp as the device reads it
 MATERIAL_TYPES = ["matte", "glossy", "reflective", "transparent", "refractive", "subsurface", "volumetric", "gltfpbr"]
 
 
@@ -235,7 +252,10 @@ hip.vpt_session_edit_textures.argtypes = [_p, C.POINTER(VptTextureEdit)]
 hip.vpt_scene_update_volumes.argtypes = [_p, C.POINTER(VptVolumeEdit)]
 hip.vpt_multi_update_volumes.argtypes = [_p, C.POINTER(VptVolumeEdit)]
 hip.vpt_session_edit_volumes.argtypes = [_p, C.POINTER(VptVolumeEdit)]
-hip.vpt_scene_get_volumes.argtypes = [_p, _p, C.c_int, _p, C.c_int, _p, C.c_int]
+hip.vpt_scene_sculpt_volumes.argtypes = [_p, C.POINTER(VptSculptEdit)]
+hip.vpt_multi_sculpt_volumes.argtypes = [_p, C.POINTER(VptSculptEdit)]
+hip.vpt_session_sculpt_volumes.argtypes = [_p, C.POINTER(VptSculptEdit)]
+hip.vpt_scene_get_volumes.argtypes =[_p, _p, C.c_int, _p, C.c_int, _p, C.c_int]
 hip.vpt_scene_get_voxels.argtypes = [_p, C.c_int, _p, C.c_int64]
 hip.vpt_scene_get_lights.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int), _p, C.c_int64, C.POINTER(C.c_int64)]
 hip.vpt_scene_light_tables_hash.argtypes = [_p, _p]
@@ -397,6 +417,9 @@ host.vpth_scene_get_sdf.argtypes = [_p, C.c_int, C.POINTER(VptSdf)]
 host.vpth_scene_set_sdf.argtypes = [_p, C.c_int, C.POINTER(VptSdf), C.c_char_p, C.c_int]
 host.vpth_scene_set_volume.argtypes = [_p, C.c_int, _p, C.c_float, _p, _p, C.c_int, _p, C.c_char_p, C.c_int]
 host.vpth_scene_update_volumes.argtypes = [_p, C.c_char_p, C.c_int]
+host.vpth_scene_sculpt_volume.argtypes = [_p, C.POINTER(VptSculptEntry), _p, C.c_int, C.c_char_p, C.c_int]
+host.vpth_sculpt_eval.argtypes = [C.POINTER(VptSdf), _p, C.c_int, _p]
+host.vpth_sculpt_combine.argtypes = [C.c_int, C.c_float, _p, _p, C.c_int, _p]
 host.vpth_scene_desc.argtypes = [_p]
 host.vpth_scene_desc.restype = _p
 host.vpth_scene_curves.argtypes = [_p]

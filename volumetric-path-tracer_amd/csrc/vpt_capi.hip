@@ -30,6 +30,7 @@
 #include "vpt_subdiv_update.h"
 #include "vpt_shape_update.h"
 #include "vpt_texture_update.h"
+#include "vpt_sculpt.h"
 #include "vpt_volume_update.h"
 
 static std::string& g_error_text() {   // the message of the last failure on the calling thread (vpt_last_error)
@@ -450,6 +451,8 @@ int vpt_scene_update_lights(vpt_scene* s, const vpt_scene_edit* edit) {
 // the light tables follow when an environment's light does / when the SDF lights do
 int vpt_scene_update_textures(vpt_scene* s, const vpt_texture_edit* edit) { return edit_scene(s, edit, texture_update_apply); }
 int vpt_scene_update_volumes(vpt_scene* s, const vpt_volume_edit* edit) { return edit_scene(s, edit, volume_update_apply); }
+// voxels alone, from analytic brushes evaluated where they live (vpt_sculpt.hip)
+int vpt_scene_sculpt_volumes(vpt_scene* s, const vpt_sculpt_edit* edit) { return edit_scene(s, edit, sculpt_apply); }
 // the BVHs built anew (vpt_bvh_rebuild.hip), the set of instances changed (vpt_instance_update.hip), the shape list changed (vpt_shape_update.hip)
 int vpt_scene_rebuild_bvh(vpt_scene* s, const vpt_bvh_rebuild* what) { return vpt_scene_rebuild_bvh_quality(s, what, VPT_BVH_MIDDLE); }
 int vpt_scene_rebuild_bvh_quality(vpt_scene* s, const vpt_bvh_rebuild* what, int quality) {

@@ -10,7 +10,7 @@ import numpy as np
 
 from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SDF_AOV_PLANES, SHADER_NAMES, VptAdaptive, VptAovPlanes, VptSdfAovPlanes, VptDisplay, VptError, VptLayout, VptParams,
                    VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, _counted, _edit_call, _p, hip, host)
-from .edits import BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit
+from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit
 
 if TYPE_CHECKING:
     from .host_scene import HostScene
@@ -247,6 +247,11 @@ class DeviceScene(_Handle):
         the resident pool.  Afterwards the handle renders the bits of a DeviceScene made from the host scene after the same edit and
         update_volumes()."""
         _edit_call(self.handle, "vpt_scene_update_volumes", edit)
+
+    def sculpt_volumes(self, edit: SculptEdit) -> None:
+        """vpt_scene_sculpt_volumes (include/vpt.h): strokes of analytic brushes evaluated on the device over boxes of the resident voxels -
+        a few hundred bytes cross PCIe, not one voxel.  edit: what HostScene.update_sculpts() returns."""
+        _edit_call(self.handle, "vpt_scene_sculpt_volumes", edit)
 
     def get_volumes(self):
         """(volumes, vol_instances, sdfs) as the device holds them, ctypes arrays of VptVolume, VptVolumeInstance, VptSdf
@@ -504,6 +509,10 @@ class MultiDeviceScene(_Handle):
     def update_volumes(self, edit: VolumeEdit) -> None:
         """vpt_multi_update_volumes: DeviceScene.update_volumes with the same edit on every device"""
         _edit_call(self.handle, "vpt_multi_update_volumes", edit)
+
+    def sculpt_volumes(self, edit: SculptEdit) -> None:
+        """vpt_multi_sculpt_volumes: DeviceScene.sculpt_volumes with the same edit on every device"""
+        _edit_call(self.handle, "vpt_multi_sculpt_volumes", edit)
 
     def rebuild_bvh(self, rebuild: "BvhRebuild") -> None:
         """vpt_multi_rebuild_bvh: DeviceScene.rebuild_bvh on every device (each builds its own trees: equal by construction)"""

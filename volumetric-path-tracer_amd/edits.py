@@ -9,9 +9,9 @@ from typing import Optional
 
 import numpy as np
 
-from ._abi import (INSTANCE, MESH_ELEMENTS, MESH_FLOATS, VOXELS_REPLACE, VptBakeDesc, VptBvhRebuild, VptCamera, VptEnvironment, VptError,
-                   VptInstanceEdit, VptMaterial, VptSceneEdit, VptSdf, VptShapeData, VptShapeEdit, VptSubdivEdit, VptSubdivLevel, VptSubdivPlan,
-                   VptTexture, VptTextureEdit, VptVolumeEdit, VptVolumeInstance, VptVolumeSource, _address)
+from ._abi import (INSTANCE, MESH_ELEMENTS, MESH_FLOATS, SCULPT_RECORD_BYTES, VOXELS_REPLACE, VptBakeDesc, VptBvhRebuild, VptCamera, VptEnvironment,
+                   VptError, VptInstanceEdit, VptMaterial, VptSceneEdit, VptSculptEdit, VptSculptEntry, VptSculptStamp, VptSdf, VptShapeData, VptShapeEdit,
+                   VptSubdivEdit, VptSubdivLevel, VptSubdivPlan, VptTexture, VptTextureEdit, VptVolumeEdit, VptVolumeInstance, VptVolumeSource, _address)
 
 
 def mesh(positions, triangles=None, quads=None, points=None, lines=None, normals=None, texcoords=None, colors=None, radius=None) -> dict:
@@ -346,3 +346,64 @@ class VolumeEdit:
         abi.num_volumes, abi.volume_ids, abi.volumes = _table(keep, self.volumes, entries)
         abi.num_voxels, abi.voxels = len(voxels), voxels.ctypes.data
         return abi, keep + [voxels]
+
+
+# ---- sculpting: strokes of analytic brushes over boxes of voxels --------------------------------------------------------------------------
+@dataclass
+class Stamp:
+    """One stamp of a stroke (include/vpt.h: vpt_sculpt_stamp): an analytic brush (a VptSdf; its material is ignored), the op -
+    SCULPT_REPLACE / SCULPT_UNION / SCULPT_SUBTRACT / SCULPT_INTERSECT - and the blend width (0: the reference's selects; > 0: the
+    polynomial smooth minimum over that width)."""
+    brush: VptSdf
+    op: int
+    blend: float = 0.0
+
+    def to_abi(self) -> VptSculptStamp:
+        out = VptSculptStamp(op=int(self.op), blend=float(self.blend))
+        C.memmove(C.byref(out.brush), C.byref(self.brush), C.sizeof(VptSdf))
+        return out
+
+
+@dataclass
+class SculptEntry:
+    """One entry of a SculptEdit (include/vpt.h: vpt_sculpt_entry): the volume, the box region_lo .. region_lo + region_whd of its voxels
+    (each (x, y, z)), the grid they are sampled on - voxel (i, j, k) at origin + (i, j, k) * step - and the stroke: Stamps in order."""
+    volume: int
+    region_lo: tuple
+    region_whd: tuple
+    origin: tuple
+    step: tuple
+    stamps: list
+
+
+class SculptEdit:
+    """What vpt_scene_sculpt_volumes takes (include/vpt.h: vpt_sculpt_edit): a list of SculptEntry, applied in order; a volume may be
+    named more than once.  HostScene.sculpt_volume fills one, update_sculpts() hands it out; DeviceScene.sculpt_volumes /
+    MultiDeviceScene.sculpt_volumes / RenderSession.edit_sculpts apply it."""
+
+    def __init__(self, entries=()):
+        self.entries = list(entries)
+
+    def empty(self) -> bool:
+        return not self.entries
+
+    def payload_bytes(self) -> int:
+        """bytes of the edit itself as vpt_scene_update_stats counts them: SCULPT_RECORD_BYTES per stamp when anything is launched"""
+        launched = any(len(e.stamps) and all(int(v) > 0 for v in e.region_whd) for e in self.entries)
+        return SCULPT_RECORD_BYTES * sum(len(e.stamps) for e in self.entries) if launched else 0
+
+    def to_abi(self):
+        """(VptSculptEdit, the arrays it points into: keep them alive across the call)"""
+        count = sum(len(e.stamps) for e in self.entries)
+        entries, stamps = (VptSculptEntry * max(1, len(self.entries)))(), (VptSculptStamp * max(1, count))()
+        first = 0
+        for rec, e in zip(entries, self.entries):
+            rec.volume, rec.first_stamp, rec.num_stamps = int(e.volume), first, len(e.stamps)
+            rec.region_lo[:], rec.region_whd[:] = [int(v) for v in e.region_lo], [int(v) for v in e.region_whd]
+            rec.origin[:] = [float(v) for v in np.broadcast_to(np.asarray(e.origin, np.float32), (3,))]
+            rec.step[:] = [float(v) for v in np.broadcast_to(np.asarray(e.step, np.float32), (3,))]
+            for s in e.stamps:
+                stamps[first] = s.to_abi()
+                first += 1
+        abi = VptSculptEdit(len(self.entries), C.addressof(entries) if self.entries else None, count, C.addressof(stamps) if count else None)
+        return abi, [entries, stamps]

@@ -426,6 +426,12 @@ baked_volume bake_volume(const vector<vec3f>& positions, const vector<vec3i>& tr
 // the binary .sdf layout load_volume reads: int32 w h d, float res, 16 floats (the identity; no reader uses them), the voxels
 bool save_volume(const string& filename, const volume_data& vol, string& error);
 
+// ---- sculpting a voxel grid with analytic SDF brushes (include/vpt.h: vpt_scene_sculpt_volumes; host/vpt_sculpt.cpp) -------------
+// the host mirror of one entry: the rule header (csrc/vpt_sculpt_rule.h) in a plain loop over the entry's region of `volume`, its
+// stamps taken from `stamps` (the edit's list of `num_stamps`) - the same bits as the device.  Refuses what the C-ABI refuses, in its
+// words (false, `error` set, the volume untouched); entry.volume is the caller's to resolve.
+bool sculpt_volume(volume_data& volume, const vpt_sculpt_entry& entry, const vpt_sculpt_stamp* stamps, int num_stamps, string& error);
+
 // ---- flattening to the C-ABI ----------------------------------------------------------------
 struct flat_scene {
   vpt_scene_desc desc = {};

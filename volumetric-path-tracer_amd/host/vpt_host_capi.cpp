@@ -622,6 +622,17 @@ int vpth_scene_set_volume(void* hh, int id, const int32_t* whd, float res, const
       }
   return 0;
 }
+// One entry of a vpt_sculpt_edit applied to the scene's copy of volume entry->volume by the host mirror (host/vpt_sculpt.cpp), its stamps
+// taken from `stamps` (the edit's list of `num_stamps`).  The rules of vpt_scene_sculpt_volumes; a refused call writes nothing.
+int vpth_scene_sculpt_volume(void* hh, const vpt_sculpt_entry* entry, const vpt_sculpt_stamp* stamps, int num_stamps, char* err, int errlen) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (!entry) return set_error(err, errlen, "sculpt: null entry"), -1;
+  if (entry->volume < 0 || entry->volume >= (int)sc.volumes.size())
+    return set_error(err, errlen, "sculpt: entry 0: volume " + std::to_string(entry->volume) + " out of range (" + std::to_string(sc.volumes.size()) + ")"), -1;
+  auto error = string{};
+  if (!sculpt_volume(sc.volumes[entry->volume], *entry, stamps, num_stamps, error)) return set_error(err, errlen, error), -1;
+  return 0;
+}
 // make_lights of the scene as the setters above left it (an SDF is a light iff its material is emissive), then the flattened descriptor again
 int vpth_scene_update_volumes(void* hh, char* err, int errlen) { return vpth_scene_update_lights(hh, err, errlen); }
 void vpth_scene_free(void* h) { delete (host_scene*)h; }

@@ -10,11 +10,11 @@ from typing import Optional
 import numpy as np
 
 from ._abi import (BVH_MIDDLE, BVH_NODE, BVH_SAH, LIGHT, MESH_ELEMENTS, MESH_FLOATS, SDF_TYPES, VOXELS_REPLACE, VptBakeStats, VptCamera,
-                   VptEnvironment, VptError, VptMaterial, VptSceneDescBvh, VptSceneDescLights, VptSdf, VptVolumeInstance, _Handle, _check, _filled,
-                   _host_call, hip, host)
+                   VptEnvironment, VptError, VptMaterial, VptSceneDescBvh, VptSceneDescLights, VptSculptEntry, VptSdf, VptVolumeInstance, _Handle,
+                   _check, _filled, _host_call, hip, host)
 from .device import PathtraceParams, PathtraceState
-from .edits import (LEVEL_TABLES, BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, VolumeSource,
-                    mesh)
+from .edits import (LEVEL_TABLES, BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan,
+                    TextureEdit, VolumeEdit, VolumeSource, mesh)
 
 
 def build_bvh(bboxes: np.ndarray, device: Optional[int] = 0, *, quality: int = 0):
@@ -172,6 +172,8 @@ def bake_sdf(positions: np.ndarray, faces: np.ndarray, whd, padding: int = 2, de
 #   environment frames name lists nothing renumbers); "instances" / "shapes": an InstanceEdit / ShapeEdit that holds anything;
 #   "subdivs": a SubdivEdit that holds anything (its shapes wait for update_bvh like moved vertices).
 # Texture and volume edits name lists of their own and wait for nothing; set_camera, set_material, set_environment_frame are never refused.
+# A volume's voxels have two ledgers, the VolumeEdit and the SculptEdit: a volume pending in one is refused by the setters of the other
+# (_note_volume, sculpt_volume), since each ledger is applied to the device as a whole and in its own call.
 _REFUSED_WHILE = {"vertices": ("instances", "shapes"),                       # set_instance_frame, set_shape_positions, set_subdiv (cage, displacement)
                   "rebuild": ("edit", "subdivs", "instances", "shapes"),      # rebuild_bvh
                   "instances": ("geometry", "subdivs", "shapes"),             # add_instance, remove_instances, set_instance, update_instances
@@ -194,6 +196,7 @@ class HostScene(_Handle):
         # the pending edits: what the setters noted since the matching update_*() handed the last one out
         self._edit, self._inst_edit, self._shape_edit = SceneEdit(), InstanceEdit(), ShapeEdit()
         self._texture_edit, self._volume_edit, self._subdiv_edit = TextureEdit(), VolumeEdit(), SubdivEdit()
+        self._sculpt_edit = SculptEdit()
         self._lazy_bakes = []   # (volume, VolumeSource) of bake_volume whose host copy is not baked yet
         self.handle = _host_call(host.vpth_scene_load_ex, os.fsencode(filename), -1 if tess_device is None else tess_device, size=1024, handle=True)
         self.filename = filename
@@ -670,6 +673,8 @@ class HostScene(_Handle):
     def _note_volume(self, index: int, src: VolumeSource) -> None:
         if index in self._volume_edit.volumes:
             raise VptError(f"volume {index} is already in the pending edit: hand it out with update_volumes() first")
+        if any(e.volume == index for e in self._sculpt_edit.entries):
+            raise VptError(f"volume {index} has sculpts pending: hand them out with update_sculpts() first")
         self._volume_edit.volumes[index] = src
 
     def set_volume(self, index: int, voxels, res: Optional[float] = None, region=None, mode: int = VOXELS_REPLACE) -> None:
@@ -731,6 +736,40 @@ class HostScene(_Handle):
         the edited volumes, instances, SDFs, light list and CDFs.  Returns the VolumeEdit for DeviceScene.update_volumes."""
         _host_call(host.vpth_scene_update_volumes, self.handle)
         edit, self._volume_edit = self._volume_edit, VolumeEdit()
+        return edit
+
+    # -- sculpting (the host side of vpt_scene_sculpt_volumes): sculpt_volume applies a stroke to the scene's copy through the host mirror
+    #    at once and notes it in the pending SculptEdit, which update_sculpts() hands out ----------------------------------------------
+    def sculpt_volume(self, index: int, stamps, region=None, origin=None, step=None) -> SculptEntry:
+        """a stroke - Stamps in order - over the voxels of volume `index` by the rule of vpt_scene_sculpt_volumes: each voxel (i, j, k)
+        of the region is sampled at origin + (i, j, k) * step and taken through every stamp.  region None: the whole grid, else (lo, whd),
+        each (x, y, z); origin / step None: bake_volume's defaults (origin 0, step = res * W / (W - 1) per axis: the grid's local frame
+        divided by scalef).  Returns the entry it noted.  A refused call changes nothing."""
+        index = int(index)
+        if index in self._volume_edit.volumes:
+            raise VptError(f"sculpt_volume: volume {index} is in the pending volume edit: hand it out with update_volumes() first")
+        old, res = self.volume(index)
+        whd = old.shape[::-1]
+        if origin is None:
+            origin = np.zeros(3, np.float32)
+        if step is None:
+            step = np.array([np.float32(res) * np.float32(w) / np.float32(max(1, w - 1)) for w in whd], np.float32)
+        lo, size = ((0, 0, 0), whd) if region is None else region
+        stamps = [s if isinstance(s, Stamp) else Stamp(*s) for s in stamps]
+        entry = SculptEntry(index, tuple(int(v) for v in lo), tuple(int(v) for v in size),
+                            tuple(float(v) for v in np.broadcast_to(np.asarray(origin, np.float32), (3,))),
+                            tuple(float(v) for v in np.broadcast_to(np.asarray(step, np.float32), (3,))), stamps)
+        abi, keep = SculptEdit([entry]).to_abi()
+        _host_call(host.vpth_scene_sculpt_volume, self.handle, C.cast(abi.entries, C.POINTER(VptSculptEntry)), abi.stamps, abi.num_stamps)
+        del keep
+        self._sculpt_edit.entries.append(entry)
+        return entry
+
+    def update_sculpts(self) -> SculptEdit:
+        """the flattened descriptor of the scene as sculpt_volume left it (no light, no record changes: whd and res stay).  Returns the
+        SculptEdit for DeviceScene.sculpt_volumes."""
+        _host_call(host.vpth_scene_update_volumes, self.handle)
+        edit, self._sculpt_edit = self._sculpt_edit, SculptEdit()
         return edit
 
     def lights(self):

@@ -7,9 +7,9 @@ from typing import Optional
 import numpy as np
 
 from ._abi import (DENOISE_ITERATIONS, DENOISE_SIGMA_ALBEDO, DENOISE_SIGMA_LUMINANCE, DENOISE_SIGMA_NORMAL, VptAdaptive, VptDenoise, VptPick,
-                   VptSdfPick, VptSessionParams, _Handle, _check, _edit_call, _p, hip)
+                   VptError, VptSdf, VptSdfPick, VptSessionParams, _Handle, _check, _edit_call, _p, hip)
 from .device import DeviceScene, DisplayParams, PathtraceParams, PathtraceState, _subdiv_edit_call
-from .edits import BvhRebuild, InstanceEdit, SceneEdit, ShapeEdit, SubdivEdit, TextureEdit, VolumeEdit
+from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, TextureEdit, VolumeEdit
 
 
 class RenderSession(_Handle):
@@ -120,6 +120,48 @@ class RenderSession(_Handle):
     def edit_volumes(self, edit: VolumeEdit) -> None:
         """edit() through vpt_scene_update_volumes, with the VolumeEdit of HostScene.update_volumes()"""
         _edit_call(self.handle, "vpt_session_edit_volumes", edit)
+
+    def edit_sculpts(self, edit: SculptEdit) -> None:
+        """vpt_scene_sculpt_volumes on the session's scene with the SculptEdit of HostScene.update_sculpts(), then a reset; a refused edit
+        leaves the session as it was"""
+        _edit_call(self.handle, "vpt_session_sculpt_volumes", edit)
+
+    def sculpt_at(self, host, x: int, y: int, brush: VptSdf, op: int, blend: float = 0.0, region_margin: int = 2) -> SculptEntry:
+        """The editor's gesture: one stamp of `brush` where the ray through pixel (x, y) hits a voxel grid.  pick_sdf(x, y) names the grid
+        instance and the hit (a miss or a hit on an analytic SDF raises VptError); the hit is taken into that instance's voxel space,
+        transform_point(instance.frame, position) / scalef; the brush keeps its frame's axes and gets the origin that puts its local origin
+        at the hit; the region is the box around the ball that holds the brush (a plane: the whole grid), widened by blend and by
+        region_margin voxels and clipped to the grid.  Then host.sculpt_volume, host.update_sculpts() and edit_sculpts: `host` is the
+        HostScene the session's scene was made from.  Returns the entry it made.  The arithmetic of this helper carries no bit contract:
+        the entry it makes goes to the host mirror and to the device alike."""
+        pick = self.pick_sdf(x, y)
+        if pick is None:
+            raise VptError(f"sculpt_at: the ray through pixel ({x}, {y}) hits nothing")
+        if pick["vol_instance"] < 0:
+            raise VptError(f"sculpt_at: pixel ({x}, {y}) shows analytic SDF {pick['sdf']}, not a voxel grid")
+        inst = host.volume_instance(pick["vol_instance"])
+        to_grid = np.array([inst.frame.x[:], inst.frame.y[:], inst.frame.z[:], inst.frame.o[:]], np.float64)
+        centre = (pick["position"].astype(np.float64) @ to_grid[:3] + to_grid[3]) / float(inst.scalef)
+        voxels, res = host.volume(pick["volume"])
+        whd = np.array(voxels.shape[::-1])
+        step = np.array([np.float32(res) * np.float32(w) / np.float32(max(1, w - 1)) for w in whd], np.float64)
+        placed = VptSdf()
+        C.memmove(C.byref(placed), C.byref(brush), C.sizeof(VptSdf))
+        axes = np.array([brush.frame.x[:], brush.frame.y[:], brush.frame.z[:]], np.float64)
+        placed.frame.o[:] = [float(v) for v in -(centre @ axes)]
+        q, size = [float(v) for v in brush.p], [float(v) for v in brush.whd]
+        reach = {0: float(np.linalg.norm(q[1:4])) + abs(q[0]), 1: float(np.linalg.norm(size)), 2: float(np.hypot(q[0], max(abs(q[1]), abs(q[2])))),
+                 3: np.inf, 4: abs(q[0]), 5: abs(q[0]) + abs(q[1])}.get(int(brush.type), np.inf)
+        stretch = np.linalg.svd(axes, compute_uv=False).min()   # a local ball of radius r lies inside a voxel-space ball of r / stretch
+        reach = (reach + float(blend)) / stretch if stretch > 0 else np.inf
+        if np.isfinite(reach):
+            lo = np.clip(np.floor((centre - reach) / step).astype(np.int64) - region_margin, 0, whd)
+            hi = np.clip(np.ceil((centre + reach) / step).astype(np.int64) + region_margin + 1, lo, whd)
+        else:
+            lo, hi = np.zeros(3, np.int64), whd
+        entry = host.sculpt_volume(pick["volume"], [Stamp(placed, op, blend)], region=(tuple(lo), tuple(hi - lo)))
+        self.edit_sculpts(host.update_sculpts())
+        return entry
 
     def rebuild_bvh(self, rebuild: "BvhRebuild") -> None:
         """vpt_scene_rebuild_bvh on the session's scene with the BvhRebuild of HostScene.rebuild_bvh(), then a reset"""
