@@ -1439,9 +1439,13 @@ int vpt_displace_vertices(int device, const vpt_texture* texture, const void* te
  *  - Value.  voxel = s * sqrt(d2): d2 the smallest squared distance from the sample point p to any kept triangle, s = -1 if
  *    dot(p - c, n) < 0 and +1 otherwise, c the closest point of the winning triangle, n the pseudonormal of the feature c lies on
  *    (Baerentzen & Aanaes 2005): the face, one of its three edges or one of its three vertices.  A point on the surface gives +0.
+ *  - Distance.  Where c lies on an edge or a vertex, d2 = dot(p - c, p - c) summed x, y, z left to right.  Where it lies on the face,
+ *    d2 = h * h with h = dot(p - a, n), a the triangle's first corner and n its unit face normal from the table below (float32, x, y, z
+ *    left to right), and s is the sign of h: the height over the plane, which does not depend on where in the face c was found
+ *    (the face's c is not read: on a narrow triangle its three areas cancel and |p - c| near the face was off by more than 1e-6).
  *  - Closest point.  The seven-region test of Ericson, Real-Time Collision Detection §5.1.5, float32, nothing fused, regions tested in
  *    the order vertex A, vertex B, edge AB, vertex C, edge AC, edge BC, face with the book's comparisons (<= 0, >= 0); the two edge
- *    parameters and the face's 1 / (va + vb + vc) are IEEE divisions; d2 = dot(p - c, p - c) summed x, y, z left to right.
+ *    parameters and the face's 1 / (va + vb + vc) are IEEE divisions.
  *  - Winner.  The lexicographic minimum of (d2, triangle index in the caller's order): the value depends on no visiting order, BVH
  *    shape or thread count.  A candidate whose d2 is NaN never wins (its comparisons are false).
  *  - Dropped triangles.  A triangle whose float32 cross product (b - a) x (c - a), unfused, is exactly {0, 0, 0} takes no part in

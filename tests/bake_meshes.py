@@ -68,6 +68,86 @@ def torus(nu=40, nv=40, major=0.6, minor=0.25):
     return verts.astype(F), np.array(tris, np.int32)
 
 
+def spiky(height, subdivisions=0, radius=0.35):
+    """an icosphere with every face replaced by three triangles that meet at a new vertex, the face's centroid pushed out to
+    radius * (1 + height): acute convex apexes, concave valleys along the old edges, saddles at the old vertices.  Not convex:
+    confirm its winding with sdf_exact.winding, not with check_outward."""
+    verts, tris = icosphere(subdivisions, radius)
+    v = verts.astype(np.float64)
+    mid = v[tris].mean(axis=1)
+    mid *= radius * (1 + height) / np.linalg.norm(mid, axis=1, keepdims=True)
+    out = []
+    for i, (a, b, c) in enumerate(tris):
+        m = len(v) + i
+        out += [(a, b, m), (b, c, m), (c, a, m)]
+    return np.concatenate([v, mid]).astype(F), np.array(out, np.int32)
+
+
+def fan_spike(k, apex, r=0.3):
+    """a tetrahedron on the base B0 B1 B2 (in z = -0.4, on a circle of radius r at the angles pi/2 + i 2 pi / 3) whose edge B0 B1
+    carries k - 1 extra points: the side (apex, B0, B1) is a fan of k triangles from the apex, the base a fan of k triangles from
+    B2, the two other sides stay whole.  2 k + 2 triangles; the apex and B2 see many narrow angles on one side and one wide angle
+    on the others, which is what tells angle weights from plain sums."""
+    ang = np.pi / 2 + np.arange(3) * (2 * np.pi / 3)
+    base = np.stack([r * np.cos(ang), r * np.sin(ang), np.full(3, -0.4)], axis=1)
+    rail = [base[0] + (base[1] - base[0]) * (j / k) for j in range(k + 1)]   # B0, the extra points, B1
+    rail[k] = base[1]
+    verts = np.array([np.asarray(apex, np.float64), base[2]] + rail)
+    A, B2, P = 0, 1, lambda j: 2 + j   # noqa: E731
+    tris = [(A, P(j), P(j + 1)) for j in range(k)] + [(B2, P(j + 1), P(j)) for j in range(k)] + [(A, P(k), B2), (A, B2, P(0))]
+    return verts.astype(F), np.array(tris, np.int32)
+
+
+BIPYRAMID_TURN = (0.37, -0.52, 0.29)   # a fixed generic rotation, as a rotation vector (axis * angle in radians)
+
+
+def rotation(vector):
+    """the rotation matrix of a rotation vector (Rodrigues)"""
+    w = np.asarray(vector, np.float64)
+    t = np.linalg.norm(w)
+    k = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) / t
+    return np.eye(3) + np.sin(t) * k + (1 - np.cos(t)) * (k @ k)
+
+
+def flat_bipyramid(n=720, h=0.02, turn=None, scale=1.0, offset=0.0):
+    """a rim of n points on the unit circle in z = 0 and the apexes (0, 0, +-h): 2 n needle triangles (n = 720: about 1 : 115) that
+    meet at the rim under less than 3 degrees.  turn / scale / offset: the same mesh rotated by the rotation vector, then scaled,
+    then moved - with BIPYRAMID_TURN, 1000 and 1000 the stress case of DESIGN.md §16's pruning margin."""
+    ang = np.arange(n) * (2 * np.pi / n)
+    verts = np.concatenate([np.stack([np.cos(ang), np.sin(ang), np.zeros(n)], axis=1), [[0, 0, h], [0, 0, -h]]])
+    top, bottom = n, n + 1
+    tris = [(i, (i + 1) % n, top) for i in range(n)] + [((i + 1) % n, i, bottom) for i in range(n)]
+    if turn is not None:
+        verts = verts @ rotation(turn).T
+    return (verts * scale + offset).astype(F), np.array(tris, np.int32)
+
+
+# the meshes with teeth: name -> (generator, offset of the grid).  On a box every feature is a right angle and a wrong pseudonormal
+# still gives the right sign; on these it does not (tests/test_bake_sdf_host.py).
+TOOTHED = {
+    "spiky_1.0": (lambda: spiky(1.0, 0, 0.35), 0.0137),
+    "spiky_2.0": (lambda: spiky(2.0, 0, 0.25), 0.0137),
+    "spiky_0.8_fine": (lambda: spiky(0.8, 1, 0.4), 0.0171),   # with 0.0137 a point of the 21^3 grid lies 2.6e-6 from the surface
+    "fan_8": (lambda: fan_spike(8, (0.55, 0.1, 0.8)), 0.0137),
+    "fan_16": (lambda: fan_spike(16, (0.8, 0.3, 0.5)), 0.0137),
+}
+
+
+def toothed_grid(name, whd):
+    """(origin, step) of the grid over [-1, 1]^3 moved by the mesh's offset, whd an int or (w, h, d): no sample point within 1e-5 of the
+    surface at 21^3 and 25^3, which the tests assert from the float64 reference before they compare a sign"""
+    whd = np.broadcast_to(np.asarray(whd), (3,))
+    return F(-1 + TOOTHED[name][1]), (2 / (whd - 1)).astype(F)
+
+
+def bipyramid_grid(scale=1.0, offset=0.0):
+    """(whd, origin, step) of the 24^3 grid around flat_bipyramid: for the unit copy a slab around the disc, 23 steps over
+    [-1.1, 1.1] in x and y and over [-0.12, 0.12] in z (three layers cut the inside); for a turned copy a cube"""
+    if scale == 1.0 and offset == 0.0:
+        return 24, F([-1.1 + 0.0137, -1.1 + 0.0137, -0.12 + 0.00137]), F([2.2 / 23, 2.2 / 23, 0.24 / 23])
+    return 24, F((-1.1 + 0.0137) * scale + offset), F(2.2 * scale / 23)
+
+
 def bits(a):
     return np.ascontiguousarray(a, F).view(np.uint32)
 

@@ -1,7 +1,8 @@
 """vpt_bake_sdf on the GPU (include/vpt.h): the kernel's BVH walk must give the bits of the host mirror, which runs the same rule
 header over every triangle - on grids that are no multiple of the 4^3 brick, on a single voxel, on a tree as deep as the stack
-allows; the BVH form must give the bits of the brute form (VPT_BAKE_BRUTE=1), also with coordinates near 1000 where the pruning
-margin matters; a tree deeper than the stack is refused before any launch; a baked grid renders like the reference renders it;
+allows, on meshes with acute apexes, lopsided fans and needle triangles (the host tests hold the mirror to an exact float64 reference on
+them); the BVH form must give the bits of the brute form (VPT_BAKE_BRUTE=1), also with coordinates near 1000 where the pruning
+margin matters, and on 1 440 needle triangles turned out of the axes; a tree deeper than the stack is refused before any launch; a baked grid renders like the reference renders it;
 and the CLI writes the file the Python API writes."""
 import ctypes as C
 import os
@@ -10,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from bake_meshes import F, bits, box_mesh, icosphere, torus, write_volume_scene
+from bake_meshes import BIPYRAMID_TURN, TOOTHED, F, bipyramid_grid, bits, box_mesh, flat_bipyramid, icosphere, toothed_grid, torus, write_volume_scene
 from conftest import ROOT
 from synth_scenes import chain_geometry
 
@@ -72,6 +73,41 @@ def test_bvh_equals_brute(vpt, monkeypatch, scale, offset):
     lx, ly, lz = (x - offset) / scale, (y - offset) / scale, (z - offset) / scale
     exact = np.hypot(np.hypot(lx, ly) - 0.6, lz) - 0.25
     assert np.abs(bvh / scale - exact).max() < 0.01 and np.array_equal((bvh < 0)[np.abs(exact) > 0.01], (exact < 0)[np.abs(exact) > 0.01])
+
+
+def toothed_case(case):
+    """(verts, tris, whd, origin, step)"""
+    if case == "bipyramid":
+        return (*flat_bipyramid(), *bipyramid_grid())
+    name, whd = {"spiky": ("spiky_1.0", 21), "fan": ("fan_16", (25, 21, 19))}[case]   # (25, 21, 19): lanes outside the grid on every axis
+    return (*TOOTHED[name][0](), whd, *toothed_grid(name, whd))
+
+
+@pytest.mark.parametrize("case", ["spiky", "fan", "bipyramid"])
+def test_toothed_meshes_equal_mirror(vpt, case):
+    dev, ref, stats = both(vpt, *toothed_case(case))
+    assert np.array_equal(bits(dev), bits(ref))
+    assert (dev < 0).sum() >= 30 and np.isfinite(dev).all()
+
+
+@pytest.mark.parametrize("rim", [720, 1000])
+@pytest.mark.parametrize("turn,scale,offset", [(None, 1.0, 0.0), (BIPYRAMID_TURN, 1000.0, 1000.0)])
+def test_bvh_equals_brute_on_needles(vpt, monkeypatch, turn, scale, offset, rim):
+    """the flat bipyramid, and its copy turned out of the axes, scaled by 1000 and moved by 1000: DESIGN.md §16's own stress case for
+    the pruning margin, slivers seen from far away with coordinates where reach = 2^-14 M is 0.13.  A rim of 720 points (1 440
+    needles of 1 : 115) gives a tree of 863 nodes; the rim of 1 000 (2 000 needles of 1 : 159) is there for a tree of more than 1 000."""
+    verts, tris = flat_bipyramid(rim, turn=turn, scale=scale, offset=offset)
+    whd, origin, step = bipyramid_grid(scale, offset)
+    monkeypatch.delenv("VPT_BAKE_BRUTE", raising=False)
+    bvh, s_bvh = vpt.bake_sdf_grid(verts, tris, whd, origin, step, device=0)
+    monkeypatch.setenv("VPT_BAKE_BRUTE", "1")
+    brute, s_brute = vpt.bake_sdf_grid(verts, tris, whd, origin, step, device=0)
+    assert s_bvh["bvh_nodes"] > (1000 if rim == 1000 else 800) and s_brute["bvh_nodes"] == 0 and s_bvh["launches"] == s_brute["launches"] == 1
+    assert s_bvh["dropped_triangles"] == s_brute["dropped_triangles"] == 0 and len(tris) == 2 * rim
+    differ = bits(bvh) != bits(brute)
+    print(f"rim {rim}, scale {scale}: {int(differ.sum())} voxels differ, {int((bvh < 0).sum())} inside, tree of {s_bvh['bvh_nodes']} nodes, depth {s_bvh['bvh_depth']}")
+    assert not differ.any()
+    assert (bvh < 0).sum() >= 30 and (bvh > 0).any() and np.isfinite(bvh).all()
 
 
 def test_deep_tree(vpt):

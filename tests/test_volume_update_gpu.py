@@ -12,8 +12,9 @@ import sys
 import numpy as np
 import pytest
 
+import sdf_exact as X
 import volume_edits as V
-from bake_meshes import bits, icosphere, write_volume_scene
+from bake_meshes import TOOTHED, bits, icosphere, toothed_grid, write_volume_scene
 from conftest import GOLDEN, ROOT
 
 pytestmark = pytest.mark.gpu
@@ -195,6 +196,43 @@ def test_bake_bytes_do_not_depend_on_the_grid(vpt, tmp_path):
         sent.append(A.update_stats()[1])
         assert np.array_equal(bits(A.get_voxels(0)), bits(vpt.bake_sdf_grid(verts, tris, n, origin, step, device=None)[0]))
     assert sent[0] == sent[1] and sent[0] < 8 ** 3 * 4 + 320 * 200
+
+
+FAN_REGION = ((7, 5, 3), (10, 9, 14))   # lo and size (x, y, z) in the 21^3 grid: no multiple of a brick, across brick borders, around the fan's inside
+
+
+@pytest.mark.parametrize("mode", [V.REPLACE, V.UNION])
+def test_a_fan_baked_into_a_region_has_the_mirrors_bits_and_the_exact_signs(vpt, tmp_path, mode):
+    """fan_spike(8) through HostScene.bake_volume into a region of a resident 21^3 grid that held a sphere's distance field (below the
+    baked values in part of the region, above them elsewhere): the mirror combined in numpy with the grid before the bake, bit for
+    bit; and in REPLACE mode the region's signs are the winding number's (tests/sdf_exact.py), no voxel within 1e-5 of the surface"""
+    verts, tris = TOOTHED["fan_8"][0]()
+    n = 21
+    origin, step = toothed_grid("fan_8", n)
+    origin = np.full(3, origin, F)
+    k = np.arange(n, dtype=F)
+    z, y, x = np.meshgrid(k, k, k, indexing="ij")
+    field = (np.sqrt((x - 10) ** 2 + (y - 10) ** 2 + (z - 8) ** 2) * F(0.1) - F(0.45)).astype(F)
+    vpt.save_volume(str(tmp_path / "field.sdf"), field, 0.05)
+    write_volume_scene(tmp_path / "scene.json", "field.sdf", np.array([[1, 0, 0], [0, 1, 0], [0, 0, 1], [0, 0, 0]], F), 1.0)
+    host = vpt.HostScene(str(tmp_path / "scene.json"))
+    A = vpt.DeviceScene(host, 0)
+    resident = A.get_voxels(0)
+    assert np.array_equal(bits(resident), bits(field))
+    host.bake_volume(0, verts, tris, origin=origin, step=step, region=FAN_REGION, mode=mode)
+    A.update_volumes(host.update_volumes())
+    got = A.get_voxels(0)
+    mirror, _ = vpt.bake_sdf_grid(verts, tris, n, origin, step, device=None)
+    want = resident.copy()
+    box, b = V.box_of(want, *FAN_REGION), V.box_of(mirror, *FAN_REGION)
+    assert ((box < b).sum() > 100 and (box > b).sum() > 100)   # a union keeps some voxels and replaces others
+    box[...] = V.union(box, b) if mode == V.UNION else b
+    assert np.array_equal(bits(got), bits(want))
+    assert not np.array_equal(bits(got), bits(resident)) and A.update_stats()[0] == 1
+    if mode == V.REPLACE:
+        exact, inside = X.signed_distance(X.sample_points(n, origin, step), verts, tris)
+        assert np.abs(exact).min() >= 1e-5 and V.box_of(inside, *FAN_REGION).sum() == inside.sum() >= 40
+        assert np.array_equal(np.signbit(V.box_of(got, *FAN_REGION)), V.box_of(inside, *FAN_REGION))
 
 
 def test_a_baked_sphere_renders_as_the_oracle_does(vpt, oracle, tmp_path):

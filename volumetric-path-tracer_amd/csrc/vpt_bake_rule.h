@@ -79,11 +79,26 @@ VPT_BAKE_HD vpt_bake_f3 vpt_bake_closest(vpt_bake_f3 p, vpt_bake_f3 a, vpt_bake_
 
 VPT_BAKE_HD vpt_bake_f3 vpt_bake_corner(const float* v) { return {v[0], v[1], v[2]}; }
 
-// squared distance from p to a record's triangle
-VPT_BAKE_HD float vpt_bake_distance2(vpt_bake_f3 p, const vpt_bake_record& r) {
+// squared distance from p to a record's triangle; *side: dot(p - c, n) with n the normal of the feature the closest point c lies on,
+// of which only the sign is read.  On an edge or a vertex d2 is |p - c|^2.  On the face it is the square of the height over the
+// plane, dot(p - a, unit face normal), which is also the side: there c comes from three areas that cancel (vb / (va + vb + vc)), and
+// on a narrow triangle it is off, in the plane, by some 1e-4 of the longest edge - which |p - c| turns into an error of the same
+// size for a point close to the face, while the height does not know c.
+VPT_BAKE_HD float vpt_bake_measure(vpt_bake_f3 p, const vpt_bake_record& r, float* side) {
   int         feature;
-  vpt_bake_f3 q = vpt_bake_sub(p, vpt_bake_closest(p, vpt_bake_corner(r.a), vpt_bake_corner(r.b), vpt_bake_corner(r.c), &feature));
+  vpt_bake_f3 a = vpt_bake_corner(r.a);
+  vpt_bake_f3 c = vpt_bake_closest(p, a, vpt_bake_corner(r.b), vpt_bake_corner(r.c), &feature);
+  if (feature == VPT_BAKE_FACE) {
+    float h = vpt_bake_dot(vpt_bake_sub(p, a), vpt_bake_corner(r.normals));
+    return *side = h, h * h;
+  }
+  vpt_bake_f3 q = vpt_bake_sub(p, c);
+  *side = vpt_bake_dot(q, vpt_bake_corner(r.normals + 3 * feature));
   return vpt_bake_dot(q, q);
+}
+VPT_BAKE_HD float vpt_bake_distance2(vpt_bake_f3 p, const vpt_bake_record& r) {
+  float side;
+  return vpt_bake_measure(p, r, &side);
 }
 
 // the winner so far: the lexicographic minimum of (d2, index).  A NaN d2 never wins: both comparisons are false.
@@ -101,10 +116,9 @@ VPT_BAKE_HD void vpt_bake_offer(vpt_bake_best& best, float d2, int32_t index, in
 VPT_BAKE_HD float vpt_bake_no_winner() { return INFINITY; }
 // the voxel's value from the winning record: sign by the pseudonormal of the feature the closest point lies on
 VPT_BAKE_HD float vpt_bake_value(vpt_bake_f3 p, const vpt_bake_record& r) {
-  int         feature;
-  vpt_bake_f3 q  = vpt_bake_sub(p, vpt_bake_closest(p, vpt_bake_corner(r.a), vpt_bake_corner(r.b), vpt_bake_corner(r.c), &feature));
-  float       d2 = vpt_bake_dot(q, q);
-  float       s  = vpt_bake_dot(q, vpt_bake_corner(r.normals + 3 * feature)) < 0.0f ? -1.0f : 1.0f;
+  float side;
+  float d2 = vpt_bake_measure(p, r, &side);
+  float s  = side < 0.0f ? -1.0f : 1.0f;
   return s * sqrtf(d2);
 }
 
