@@ -16,9 +16,6 @@ struct adaptive_buffers {
   int*    info;
 };
 
-// the kernels' view of a layout, validated, for code that moves a state and renders nothing (vpt_capi.hip)
-int vpt_layout_dparams(const vpt_layout* l, DParams& out);
-
 // n == 0: start (lum_prev from the entry image, active = slot owns a pixel and hits < cap, min / max of hits);
 // n >= 1: the pixels still active have just rendered their n-th round of m samples: update and decide (vpt.h).
 // Then the compaction of the active slots into b.lane_slot and their count into b.info[0].  Asynchronous on `st`.

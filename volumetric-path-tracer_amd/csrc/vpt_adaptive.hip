@@ -7,6 +7,7 @@
 #include <cstdint>
 #include "vpt_kernels.hip.h"
 #include "vpt_adaptive.h"
+#include "vpt_layout.h"   // vpt_layout_dparams
 
 namespace {
 constexpr int k_block = 256;   // four waves of 64 slots each

@@ -1,6 +1,7 @@
 // vpt_capi.hip — implementation of the C-ABI in include/vpt.h: upload of the scene tables vpt_scene_prep.cpp builds
-// (the device layout of vpt_device.h), kernel launches, state movement.  The kernels are declared in vpt_launch.h and
-// compiled in the kernel units it lists; this unit holds none of their bodies.  The launch schedule is vpt_schedule.hip's.
+// (the device layout of vpt_device.h), kernel launches.  The kernels are declared in vpt_launch.h and
+// compiled in the kernel units it lists; this unit holds none of their bodies.  The launch schedule is vpt_schedule.hip's,
+// the movement of a state between host arrays and tile-major slots vpt_layout.hip's.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see __graft_entry__.py).
 // There is NO CPU fallback in this library: without a gfx950 device every compute entry point
 // fails with VPT_ERR_NO_DEVICE.
@@ -22,6 +23,7 @@
 #include "vpt_error.h"
 #include "vpt_kat.h"
 #include "vpt_launch.h"
+#include "vpt_layout.h"
 #include "vpt_light_update.h"
 #include "vpt_resident.h"
 #include "vpt_schedule.h"
@@ -48,21 +50,13 @@ int vpt_set_error(int code, const char* fmt, ...) {
   return code;
 }
 
-// the image / hits / rng arrays of a pathtrace state on the device: in tile-major slots (what the kernels render into) or as
-// row-major pixels (what the host holds); two types, so that the two cannot be swapped in a call
-struct tile_state { void *image, *hits, *rng; };
-struct row_state { void *image, *hits, *rng; };
-
 struct vpt_scene : resident {   // the tables and what edits them (vpt_resident.h), and the render side
   int                        stack_cap = 16;    // binary-BVH walk of the implicit kernels' mesh-light pdf: refs only
   int                        stack_lds4 = 8, stack_spill4 = 0;   // quad-node traversal: (ref, t0) entries in LDS / in HBM
   device_buffer              spill;
   long long                  spill_lanes = 0;
   launch_schedule sched;   // per-wave costs, launch order, tile splitting (vpt_schedule.h)
-  // staging for the host-state entry point vpt_render()
-  device_buffer s_image, s_hits, s_rng;   // tile-major state
-  device_buffer r_image, r_hits, r_rng;   // row-major mirror
-  long long  staged_pixels = 0, staged_slots = 0;
+  layout_staging staging;   // of the host-state entry points vpt_render() and vpt_render_adaptive(): allocated once per frame size
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool       timed = false;
   device_buffer d_watchdog;   // unsigned: waves of the implicit kernel that gave up (must stay 0; vpt_implicit_kernel.hip.h)
@@ -82,25 +76,6 @@ int upload(vpt_scene* s, const T** out, const T* host, size_t count) {
 }
 template <typename T>
 int upload(vpt_scene* s, const T** out, const std::vector<T>& host) { return upload(s, out, host.data(), host.size()); }
-
-int make_dparams(const vpt_params* p, const vpt_layout* l, int nsamples, DParams& out) {
-  REQUIRE(p && l, "null params/layout");
-  REQUIRE(l->width > 0 && l->height > 0 && l->nranks > 0 && l->rank >= 0 && l->rank < l->nranks, "bad layout");
-  REQUIRE(l->width < 32768 && l->height < 32768, "frame side must be below 32768 pixels (the kernels keep a pixel's coordinates in one word; the reference's --resolution ends at 4096)");
-  REQUIRE(l->tile_w >= 8 && l->tile_h >= 8 && l->tile_w % 8 == 0 && l->tile_h % 8 == 0, "tile size must be a multiple of 8x8");
-  out = {};
-  out.camera = p->camera, out.shader = p->shader, out.bounces = p->bounces, out.noimplicit_mis = p->noimplicit_mis;
-  out.spheretrace_maxiter = p->spheretrace_maxiter, out.preview = p->samples == 1, out.nsamples = nsamples;
-  out.width = l->width, out.height = l->height, out.tile_w = l->tile_w, out.tile_h = l->tile_h;
-  out.tiles_x = (l->width + l->tile_w - 1) / l->tile_w, out.tiles_y = (l->height + l->tile_h - 1) / l->tile_h;
-  out.rank = l->rank, out.nranks = l->nranks;
-  long long tiles = (long long)out.tiles_x * out.tiles_y;
-  long long local = (tiles + l->nranks - 1) / l->nranks;   // every rank allocates the same count
-  long long slots = local * l->tile_w * l->tile_h;
-  REQUIRE(slots < (1LL << 31), "image too large");
-  out.nslots = (int)slots;
-  return VPT_OK;
-}
 
 // light_prims: corners and element normals of the single-leaf mesh lights, by the device's own eval_element_normal
 int light_setup(vpt_scene* s) {
@@ -122,11 +97,6 @@ int medium_setup(vpt_scene* s) {
 }
 
 }  // namespace
-
-int vpt_layout_dparams(const vpt_layout* l, DParams& out) {
-  vpt_params none = {};
-  return make_dparams(&none, l, 0, out);
-}
 
 extern "C" {
 
@@ -203,47 +173,6 @@ int vpt_scene_create_curves(const vpt_scene_desc* desc, const vpt_scene_curves* 
   *out = s;
   s    = nullptr;   // release the guard
   return VPT_OK;
-}
-
-int64_t vpt_layout_slots(const vpt_layout* layout) {
-  DParams pr;
-  if (vpt_layout_dparams(layout, pr) != VPT_OK) return -1;
-  return pr.nslots;
-}
-
-// The host <-> tile-major conversions go through a row-major device copy of the frame: `staged` (the scene handle's in vpt_render,
-// allocated once per frame size; on a download it still holds the uploaded frame), else allocated for the call and, on a download,
-// filled from the caller's arrays so that pixels owned by other ranks keep their values.  The host arrays are written only when !to_tiles.
-static int move_state(const vpt_layout* layout, bool to_tiles, float* image_rgba, int32_t* hits, uint64_t* rng, tile_state t,
-    const row_state* staged, hipStream_t st) {
-  if (!layout || !image_rgba || !hits || !rng || !t.image || !t.hits || !t.rng) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
-  if (layout->width <= 0 || layout->height <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad layout");
-  const size_t  n = (size_t)layout->width * layout->height;
-  device_buffer r_image, r_hits, r_rng;
-  if (!staged && (r_image.allocate(n * 16) || r_hits.allocate(n * 4) || r_rng.allocate(n * 16))) return VPT_ERR_HIP;
-  const row_state r = staged ? *staged : row_state{r_image.get(), r_hits.get(), r_rng.get()};
-  const struct { void *rows, *host; size_t bytes; } parts[3] = {{r.image, image_rgba, n * 16}, {r.hits, hits, n * 4}, {r.rng, rng, n * 16}};
-  if (to_tiles || !staged)
-    for (const auto& p : parts) HIP_TRY(hipMemcpyAsync(p.rows, p.host, p.bytes, hipMemcpyHostToDevice, st));
-  DParams pr;
-  if (int rc = vpt_layout_dparams(layout, pr)) return rc;
-  hipLaunchKernelGGL(vpt_permute_kernel, dim3((pr.nslots + 255) / 256), dim3(256), 0, st, pr, (int)to_tiles, (float4*)t.image, (int*)t.hits,
-      (ulonglong2*)t.rng, (float4*)r.image, (int*)r.hits, (ulonglong2*)r.rng);
-  HIP_TRY(hipGetLastError());
-  if (!to_tiles)
-    for (const auto& p : parts) HIP_TRY(hipMemcpyAsync(p.host, p.rows, p.bytes, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return VPT_OK;
-}
-
-int vpt_state_upload(const vpt_layout* layout, const float* image_rgba, const int32_t* hits, const uint64_t* rng,
-    void* d_image, void* d_hits, void* d_rng, void* stream) {
-  return move_state(layout, true, (float*)image_rgba, (int32_t*)hits, (uint64_t*)rng, {d_image, d_hits, d_rng}, nullptr, (hipStream_t)stream);
-}
-
-int vpt_state_download(const vpt_layout* layout, const void* d_image, const void* d_hits, const void* d_rng,
-    float* image_rgba, int32_t* hits, uint64_t* rng, void* stream) {
-  return move_state(layout, false, image_rgba, hits, rng, {(void*)d_image, (void*)d_hits, (void*)d_rng}, nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -521,15 +450,11 @@ int vpt_resolve_srgb8_device(const vpt_layout* layout, const void* d_tiles_all_r
 }  // extern "C"
 
 // the conditions on the planes of a first-hit pass (include/vpt.h), device or host pointers alike
-static int check_aov_planes(const vpt_aov_planes* p) {
+static int check_given(const vpt_aov_planes* p) {
   REQUIRE(p, "null planes");
-  REQUIRE(p->normal || p->albedo || p->texcoord || p->depth || p->ids || p->uvt, "planes: every plane is null, nothing to render");
-  REQUIRE(p->ids || !p->uvt, "planes: uvt is given without ids");
-  const void* const   given[6] = {p->normal, p->albedo, p->texcoord, p->depth, p->ids, p->uvt};
-  static const char* const name[6] = {"normal", "albedo", "texcoord", "depth", "ids", "uvt"};
-  for (int a = 0; a < 6; a++)   // the kernel updates each plane on its own: two of them in one buffer would lose updates
-    for (int b = a + 1; b < 6; b++) REQUIRE(!given[a] || given[a] != given[b], "planes: %s and %s share a buffer", name[a], name[b]);
-  return VPT_OK;
+  const void* const        given[6] = {p->normal, p->albedo, p->texcoord, p->depth, p->ids, p->uvt};
+  static const char* const name[6]  = {"normal", "albedo", "texcoord", "depth", "ids", "uvt"};
+  return check_plane_set(name, given, 6, 4, 5);
 }
 static aov_planes device_planes(const vpt_aov_planes& p) {
   return {(float4*)p.normal, (float4*)p.albedo, (float4*)p.texcoord, (float4*)p.depth, (int2*)p.ids, (float*)p.uvt};
@@ -539,7 +464,7 @@ extern "C" {
 
 int vpt_render_aov_device(vpt_scene* s, const vpt_params* params, const vpt_layout* layout, int nsamples, const vpt_aov_planes* planes,
     void* d_hits, void* d_rng, void* stream) {
-  if (int rc = check_aov_planes(planes)) return rc;
+  if (int rc = check_given(planes)) return rc;
   REQUIRE(s && params && layout && d_hits && d_rng, "null argument");
   REQUIRE(params->camera >= 0 && params->camera < s->d.num_cameras, "camera %d out of range", params->camera);
   REQUIRE(nsamples >= 0, "negative sample count");
@@ -566,19 +491,13 @@ int vpt_render_aov_device(vpt_scene* s, const vpt_params* params, const vpt_layo
 int vpt_resolve_ids_device(const vpt_layout* layout, const void* d_ids, const void* d_uvt, void* d_ids_rowmajor, void* d_uvt_rowmajor, void* stream) {
   REQUIRE(layout && d_ids && d_ids_rowmajor, "null argument");
   REQUIRE((d_uvt != nullptr) == (d_uvt_rowmajor != nullptr), "d_uvt and d_uvt_rowmajor must be null together");
-  DParams pr;
-  if (int rc = vpt_layout_dparams(layout, pr)) return rc;
-  const long long total = (long long)pr.nslots * pr.nranks;
-  REQUIRE(total < (1LL << 31), "image too large");
-  hipLaunchKernelGGL(vpt_resolve_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pr, (const int2*)d_ids,
-      (const float*)d_uvt, (int2*)d_ids_rowmajor, (float*)d_uvt_rowmajor);
-  HIP_TRY(hipGetLastError());
-  return VPT_OK;
+  const layout_plane planes[2] = {{(void*)d_ids, d_ids_rowmajor, 8}, {(void*)d_uvt, d_uvt_rowmajor, 12}};
+  return layout_copy(layout, LAYOUT_ALL_TILES_TO_ROWS, planes, d_uvt ? 2 : 1, (hipStream_t)stream);
 }
 
 int vpt_render_aov(vpt_scene* s, const vpt_params* params, int nsamples, int width, int height, const vpt_aov_planes* planes, int32_t* hits,
     uint64_t* rng, int* samples_io) {
-  if (int rc = check_aov_planes(planes)) return rc;
+  if (int rc = check_given(planes)) return rc;
   REQUIRE(params, "null params");
   REQUIRE(hits, "null hits");
   REQUIRE(rng, "null rng");
@@ -590,61 +509,27 @@ int vpt_render_aov(vpt_scene* s, const vpt_params* params, int nsamples, int wid
   const int todo = std::min(nsamples, params->samples - *samples_io);   // no-op once reached, as vpt_render
   if (todo <= 0) return VPT_OK;
   HIP_TRY(hipSetDevice(s->device));
-  const vpt_layout lay = {width, height, 8, 8, 0, 1};
-  DParams          pr;
-  if (int rc = vpt_layout_dparams(&lay, pr)) return rc;
-  const size_t slots = (size_t)pr.nslots, n = (size_t)width * height;
-  // per plane: bytes per entry, the host array, tile-major and row-major device copies
-  struct part { size_t bytes; void* host; device_buffer tiles, rows; };
-  part parts[8] = {{16, planes->normal}, {16, planes->albedo}, {16, planes->texcoord}, {16, planes->depth}, {8, planes->ids}, {12, planes->uvt},
-      {4, hits}, {16, rng}};
-  for (part& p : parts) {
-    if (!p.host) continue;
-    if (int rc = p.tiles.allocate(slots * p.bytes)) return rc;
-    if (int rc = p.rows.allocate(n * p.bytes)) return rc;
-    HIP_TRY(hipMemcpyAsync(p.rows.get(), p.host, n * p.bytes, hipMemcpyHostToDevice, nullptr));
-  }
-  const vpt_aov_planes tiles = {parts[0].tiles.get(), parts[1].tiles.get(), parts[2].tiles.get(), parts[3].tiles.get(), parts[4].tiles.get(), parts[5].tiles.get()};
-  const vpt_aov_planes rows  = {parts[0].rows.get(), parts[1].rows.get(), parts[2].rows.get(), parts[3].rows.get(), parts[4].rows.get(), parts[5].rows.get()};
-  auto permute = [&](int to_tiles) {
-    hipLaunchKernelGGL(vpt_aov_permute_kernel, dim3((pr.nslots + 255) / 256), dim3(256), 0, nullptr, pr, to_tiles, device_planes(tiles),
-        parts[6].tiles.get<int>(), parts[7].tiles.get<ulonglong2>(), device_planes(rows), parts[6].rows.get<int>(), parts[7].rows.get<ulonglong2>());
-  };
-  permute(1);
-  HIP_TRY(hipGetLastError());
-  if (int rc = vpt_render_aov_device(s, params, &lay, todo, &tiles, parts[6].tiles.get(), parts[7].tiles.get(), nullptr)) return rc;
-  permute(0);
-  HIP_TRY(hipGetLastError());
-  for (part& p : parts)
-    if (p.host) HIP_TRY(hipMemcpyAsync(p.host, p.rows.get(), n * p.bytes, hipMemcpyDeviceToHost, nullptr));
-  HIP_TRY(hipStreamSynchronize(nullptr));
+  const vpt_layout lay      = {width, height, 8, 8, 0, 1};
+  const host_plane parts[8] = {{planes->normal, 16}, {planes->albedo, 16}, {planes->texcoord, 16}, {planes->depth, 16}, {planes->ids, 8},
+      {planes->uvt, 12}, {hits, 4}, {rng, 16}};
+  if (int rc = layout_round_trip(lay, parts, 8, nullptr, [&](const vpt_layout* l, void* const* t) {
+        const vpt_aov_planes tiles = {t[0], t[1], t[2], t[3], t[4], t[5]};
+        return vpt_render_aov_device(s, params, l, todo, &tiles, t[6], t[7], nullptr);
+      }))
+    return rc;
   *samples_io += todo;
   return VPT_OK;
 }
 
 }  // extern "C"
 
-// vpt_render / vpt_render_adaptive: the host state through the scene handle's staging (one rank, 8x8 tiles; allocated once per frame
-// size), render(layout, tiles) on it, and back.  The row-major staging still holds the frame that was uploaded, and the
-// single-rank layout owns every pixel, so the download starts from it.
+// vpt_render / vpt_render_adaptive: the host state through the scene handle's staging (one rank, 8x8 tiles) and render(layout, tiles)
 template <typename Render>
-static int render_host_state(vpt_scene* s, int width, int height, float* image_rgba, int32_t* hits, uint64_t* rng, Render&& render) {
+static int render_staged(vpt_scene* s, int width, int height, float* image_rgba, int32_t* hits, uint64_t* rng, Render&& render) {
   HIP_TRY(hipSetDevice(s->device));
-  vpt_layout lay = {width, height, 8, 8, 0, 1};
-  long long  slots = vpt_layout_slots(&lay), pixels = (long long)width * height;
-  if (slots < 0) return VPT_ERR_INVALID_ARG;
-  if (s->staged_slots != slots || s->staged_pixels != pixels) {
-    s->staged_slots = s->staged_pixels = 0;
-    if (s->s_image.allocate((size_t)slots * 16) || s->s_hits.allocate((size_t)slots * 4) || s->s_rng.allocate((size_t)slots * 16) ||
-        s->r_image.allocate((size_t)pixels * 16) || s->r_hits.allocate((size_t)pixels * 4) || s->r_rng.allocate((size_t)pixels * 16))
-      return VPT_ERR_HIP;
-    s->staged_slots = slots, s->staged_pixels = pixels;
-  }
-  const tile_state t = {s->s_image.get(), s->s_hits.get(), s->s_rng.get()};
-  const row_state  r = {s->r_image.get(), s->r_hits.get(), s->r_rng.get()};
-  if (int rc = move_state(&lay, true, image_rgba, hits, rng, t, &r, nullptr)) return rc;
-  if (int rc = render(&lay, t)) return rc;
-  if (int rc = move_state(&lay, false, image_rgba, hits, rng, t, &r, nullptr)) return rc;
+  const vpt_layout lay      = {width, height, 8, 8, 0, 1};
+  const host_plane state[3] = {{image_rgba, 16}, {hits, 4}, {rng, 16}};
+  if (int rc = layout_round_trip(lay, state, 3, &s->staging, render)) return rc;
   return vpt_check_watchdog(s);
 }
 
@@ -828,8 +713,8 @@ int vpt_render_adaptive(vpt_scene* s, const vpt_params* params, const vpt_adapti
     if (hits[i] != hits[0]) return vpt_set_error(VPT_ERR_INVALID_ARG, "hits[] must be equal on entry (pixel %lld has %d, pixel 0 %d)", i, hits[i], hits[0]);
   *samples_io = hits[0];
   if (hits[0] >= params->samples) return VPT_OK;
-  if (int rc = render_host_state(s, width, height, image_rgba, hits, rng, [&](const vpt_layout* lay, tile_state t) {
-        return vpt_render_device_adaptive(s, params, a, lay, t.image, t.hits, t.rng, nullptr, nullptr, rendered);
+  if (int rc = render_staged(s, width, height, image_rgba, hits, rng, [&](const vpt_layout* lay, void* const* t) {
+        return vpt_render_device_adaptive(s, params, a, lay, t[0], t[1], t[2], nullptr, nullptr, rendered);
       }))
     return rc;
   *samples_io = *std::max_element(hits, hits + pixels);
@@ -844,8 +729,8 @@ int vpt_render(vpt_scene* s, const vpt_params* params, int nsamples, int width, 
   int todo = params->samples - *samples_io;   // no-op once reached, yocto_pathtrace.cpp:1055
   if (nsamples < todo) todo = nsamples;
   if (todo <= 0) return VPT_OK;
-  if (int rc = render_host_state(s, width, height, image_rgba, hits, rng, [&](const vpt_layout* lay, tile_state t) {
-        return vpt_render_device(s, params, lay, todo, t.image, t.hits, t.rng, nullptr);
+  if (int rc = render_staged(s, width, height, image_rgba, hits, rng, [&](const vpt_layout* lay, void* const* t) {
+        return vpt_render_device(s, params, lay, todo, t[0], t[1], t[2], nullptr);
       }))
     return rc;
   *samples_io += todo;

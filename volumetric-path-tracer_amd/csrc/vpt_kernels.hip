@@ -112,17 +112,7 @@ __global__ void vpt_reciprocal_selftest_kernel(unsigned long long* out) {
   if (skipped) atomicAdd(&out[1], skipped);
 }
 
-// ---- state layout conversion and output resolve ---------------------------------------------
-// row-major host-order arrays <-> this rank's tile-major slots (vpt_state_upload / _download)
-__global__ void vpt_permute_kernel(DParams pr, int to_tiles, float4* tiles_image, int* tiles_hits, ulonglong2* tiles_rng,
-    float4* rows_image, int* rows_hits, ulonglong2* rows_rng) {
-  int slot = blockIdx.x * blockDim.x + threadIdx.x;
-  int px, py;
-  if (slot >= pr.nslots || !slot_to_pixel(pr, slot, px, py)) return;
-  long long idx = (long long)py * pr.width + px;
-  if (to_tiles) tiles_image[slot] = rows_image[idx], tiles_hits[slot] = rows_hits[idx], tiles_rng[slot] = rows_rng[idx];
-  else rows_image[idx] = tiles_image[slot], rows_hits[idx] = tiles_hits[slot], rows_rng[idx] = tiles_rng[slot];
-}
+// ---- output resolve (the plain layout copies: vpt_layout.hip) ---------------------------------------------
 // get_render (cpp:1105-1116) over the gathered buffers of all ranks: [nranks][nslots] -> row-major * 1/samples
 __global__ void vpt_resolve_kernel(DParams pr, const float4* tiles_all, float scale, float4* rows_image) {
   int g = blockIdx.x * blockDim.x + threadIdx.x;   // global slot over all ranks

@@ -1,6 +1,6 @@
 // vpt_kernels.hip.h — what the render kernels share (slot map, roulette).  The render kernels themselves:
 // vpt_mesh_kernel.hip.h (K1, the seven mesh shaders), vpt_implicit_kernel.hip.h (K2, the two SDF shaders); the
-// elementwise state kernels: vpt_kernels.hip.  Their declarations and launch types: vpt_launch.h.
+// output resolves: vpt_kernels.hip; the copies between the two layouts: vpt_layout.hip.  Declarations and launch types: vpt_launch.h.
 #pragma once
 #include "vpt_launch.h"
 #include "vpt_scene.hip.h"

@@ -5,8 +5,9 @@
 //   vpt_k1_curves.hip                     K1 for scenes with points or lines, + vpt_intersect on them   vpt_k1_instances.hip.h)
 //   vpt_k1_simple.hip                     K1 for naive, eyelight and the debug shaders
 //   vpt_k2.hip                            K2 (vpt_implicit_kernel.hip.h)
-//   vpt_aov.hip                           the first-hit pass (vpt_aov_kernel.hip.h) and the layout kernels of its id planes
-//   vpt_kernels.hip                       vpt_intersect, the KAT kernel, the self-tests, light setup, launch schedule, state layout
+//   vpt_aov.hip                           the first-hit pass (vpt_aov_kernel.hip.h)
+//   vpt_kernels.hip                       vpt_intersect, the KAT kernel, the self-tests, light setup, launch schedule, output resolve
+// (the copies between row-major pixels and tile-major slots are one kernel of vpt_layout.hip, launched there: not declared here)
 // The launch bounds live here only: a definition inherits them from these declarations.
 #pragma once
 #include "vpt_device.h"
@@ -89,17 +90,10 @@ struct aov_planes {
 template <bool SPILL, bool CURVES>
 __global__ void __launch_bounds__(VPT_BLOCK, VPT_WAVES_PER_SIMD) vpt_aov_kernel(DScene sc, DParams pr, aov_planes pl, int* __restrict__ hits,
     ulonglong2* __restrict__ rngs, stack_cfg stack);
-// ids / uvt of all ranks ([nranks][nslots]) -> row-major (vpt_resolve_ids_device); uvt nullable
-__global__ void vpt_resolve_ids_kernel(DParams pr, const int2* ids_all, const float* uvt_all, int2* rows_ids, float* rows_uvt);
-// row-major host-order planes, hits and rng <-> this rank's tile-major slots (vpt_render_aov); null planes are skipped
-__global__ void vpt_aov_permute_kernel(DParams pr, int to_tiles, aov_planes tiles, int* tiles_hits, ulonglong2* tiles_rng, aov_planes rows,
-    int* rows_hits, ulonglong2* rows_rng);
 
-// ---- scene setup, launch schedule, state layout and output resolve (vpt_kernels.hip) -------------------------------------------
+// ---- scene setup, launch schedule and output resolve (vpt_kernels.hip) --------------------------------------------------------
 __global__ void vpt_light_setup_kernel(DScene sc, float4* out);
 __global__ void vpt_medium_setup_kernel(DScene sc, float4* out);
 __global__ void vpt_cost_average_kernel(const unsigned* __restrict__ cost, float* __restrict__ avg, unsigned* __restrict__ key, int n, float nsamples, float weight);
-__global__ void vpt_permute_kernel(DParams pr, int to_tiles, float4* tiles_image, int* tiles_hits, ulonglong2* tiles_rng,
-    float4* rows_image, int* rows_hits, ulonglong2* rows_rng);
 __global__ void vpt_resolve_kernel(DParams pr, const float4* tiles_all, float scale, float4* rows_image);
 __global__ void vpt_resolve_srgb8_kernel(DParams pr, const float4* tiles_all, float scale, uchar4* rows_rgba8);

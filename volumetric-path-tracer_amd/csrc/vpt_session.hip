@@ -11,10 +11,10 @@
 #include <utility>
 #include <vector>
 
-#include "vpt_adaptive.h"   // vpt_layout_dparams
 #include "vpt_device_buffer.h"
 #include "vpt_error.h"
 #include "vpt_kernels.hip.h"   // slot_to_pixel
+#include "vpt_layout.h"
 #include "vpt_rng_jump.h"
 #include "vpt_sdf_aov.h"   // vpt_sdf_pick_device
 #include "vpt_srgb.hip.h"
@@ -633,12 +633,9 @@ int vpt_session_get_state(vpt_session* s, float* image_rgba, int32_t* hits, uint
     if (int rc = s->r_rng.allocate(n * 16)) return rc;
     s->r_pixels = (long long)n;
   }
-  DParams pr;
-  if (int rc = vpt_layout_dparams(&s->lay, pr)) return rc;
   // the one-rank layout owns every pixel: the row-major staging is written in full
-  hipLaunchKernelGGL(vpt_permute_kernel, dim3((pr.nslots + 255) / 256), dim3(256), 0, s->st, pr, 0, s->s_image.get<float4>(), s->s_hits.get<int>(),
-      s->s_rng.get<ulonglong2>(), s->r_image.get<float4>(), s->r_hits.get<int>(), s->r_rng.get<ulonglong2>());
-  HIP_TRY(hipGetLastError());
+  const layout_plane state[3] = {{s->s_image.get(), s->r_image.get(), 16}, {s->s_hits.get(), s->r_hits.get(), 4}, {s->s_rng.get(), s->r_rng.get(), 16}};
+  if (int rc = layout_copy(&s->lay, LAYOUT_TILES_TO_ROWS, state, 3, s->st)) return rc;
   s->launches++;
   if (int rc = fetch(s, image_rgba, s->r_image, n * 16)) return rc;
   if (int rc = fetch(s, hits, s->r_hits, n * 4)) return rc;
