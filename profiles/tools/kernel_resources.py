@@ -59,7 +59,7 @@ def main():
     for r, name in zip(rows, names):
         if "rocprim" in name:
             continue
-        short = re.sub(r"\(.*", "", name)
+        short = re.sub(r"\(.*", "", name.replace("(anonymous namespace)::", ""))   # kernels of an unnamed namespace keep their names
         lines.append(f"{short:55s} VGPR {r.get('VGPRs', '?'):>4} AGPR {r.get('AGPRs', '?'):>3} SGPR {r.get('TotalSGPRs', r.get('SGPRs', '?')):>4} "
                      f"scratch {r.get('ScratchSize [bytes/lane]', '?'):>5} B/lane  occupancy {r.get('Occupancy [waves/SIMD]', '?')}  LDS {r.get('LDS Size [bytes/block]', '?')}")
     print("\n".join(sorted(lines)))

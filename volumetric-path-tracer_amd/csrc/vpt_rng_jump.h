@@ -1,5 +1,5 @@
 // vpt_rng_jump.h — make_state's per-pixel PCG32 seeds without the sequential master stream (include/vpt.h: vpt_state_init_device).
-// Compiled by the state-initialisation kernel (csrc/vpt_session.hip) and by the host library (make_state_jump): integers only, so
+// Compiled by the state-initialisation kernel (csrc/vpt_frame_stages.hip) and by the host library (make_state_jump): integers only, so
 // both give the bits of make_state (yocto_pathtrace.cpp:975-978, yocto_sampling.h:184-205).
 // PCG32's state update is the LCG  s' = A s + inc  (mod 2^64), so n steps are  s -> A^n s + inc (A^n - 1) / (A - 1):  the pair
 // (A^n, c_n) comes from square-and-multiply over the bits of n (Brown, "Random number generation with arbitrary strides", 1994).

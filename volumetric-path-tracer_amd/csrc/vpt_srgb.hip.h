@@ -1,5 +1,5 @@
 // vpt_srgb.hip.h — the 8-bit output stage on the device, shared by vpt_resolve_srgb8_device (vpt_kernels.hip) and
-// vpt_tonemap_device (vpt_session.hip): rgb_to_srgb (yocto_color.h:228-231) and float_to_byte (:207-211, clamp(int(a * 256), 0, 255)).
+// vpt_tonemap_device (vpt_frame_stages.hip): rgb_to_srgb (yocto_color.h:228-231) and float_to_byte (:207-211, clamp(int(a * 256), 0, 255)).
 // powf is ocml's here and glibc's in the reference: a byte can differ by one where the curve lands within an ulp of a multiple of
 // 1/256 (the parity pipeline keeps using the host routine, vpth_linear_to_srgb8).
 #pragma once
