@@ -1478,6 +1478,52 @@ typedef struct vpt_bake_stats { int32_t dropped_triangles, bvh_nodes, bvh_depth,
 int vpt_bake_sdf(int device, const vpt_bake_desc* desc, float* voxels /* x + y*W + z*W*H */, vpt_bake_stats* stats /* may be NULL */);
 int vpt_bake_feature_normals(const vpt_bake_desc* desc, float* normals /* 21 floats per triangle */, int32_t* kept /* 1/0 per triangle, may be NULL */);
 
+/* ---- a quad mesh out of a signed-distance voxel grid --------------------------------------------------------------
+ * The way back from vpt_bake_sdf and the sculpt: the iso surface of a grid as positions, normals and quads (naive surface nets), what
+ * vpt_shape_data takes.  The reference has no mesher: an extension.  The rule, which csrc/vpt_sdf_mesh_rule.h states operation by
+ * operation for the kernels (csrc/vpt_sdf_mesh.hip) and for the host mirror (host/vpt_sdf_mesh.cpp: the same bits; float32, unfused,
+ * IEEE divisions):
+ *  - Grid.  whd = (W, H, D), voxel (x, y, z) at voxels[x + y*W + z*W*H], sampled at origin + (float)i * step per axis (the bake's and the
+ *    sculpt's voxel space).  inside(v) = v < iso: a NaN voxel is outside.
+ *  - Cells.  Cell (x, y, z), 0 <= x < W-1 (and so on), has the corners (x+dx, y+dy, z+dz); it is active when 1 to 7 of them are inside.
+ *  - Vertex of an active cell.  The twelve edges in order: the four x-edges at (dy,dz) = (0,0), (1,0), (0,1), (1,1), the four y-edges at
+ *    (dz,dx) in the same order, the four z-edges at (dx,dy).  An edge from the lower corner a to the upper b crosses when inside(va) !=
+ *    inside(vb), at t = (iso - va) / (vb - va), and t = 0.5f if !(t >= 0 && t <= 1).  The crossing point in unit-cell coordinates is t
+ *    along the edge's axis and the edge's 0 / 1 offsets on the others; each coordinate is summed from 0 in edge order, u = sum /
+ *    (float)count, and the position per axis is origin + ((float)x + u) * step: add, multiply, add.
+ *  - Normal.  The gradient of the cell's trilinear interpolant at u (term order in the header), each component divided by its step, then
+ *    the reference's normalize (the vector itself when its length is 0).  A component that comes out NaN is written as +0.
+ *  - Ids.  A vertex's id is the rank of its cell among the active cells in voxel index order (x fastest).
+ *  - Quads.  The grid edge from voxel X along axis a emits one quad when inside(X) != inside(X + e_a) and, with (a, b, c) a cyclic
+ *    permutation of (x, y, z), 1 <= X_b <= dim_b - 2 and 1 <= X_c <= dim_c - 2 (all four cells around it exist).  Its corners are the
+ *    vertices of the cells X - e_b - e_c, X - e_c, X, X - e_b in that order when X is inside; when X + e_a is inside the first is kept
+ *    and the other three are reversed: the quads face out of the inside.  Quads are ordered by the owner voxel's index, then by axis.
+ *    A sign change on an edge at the border of the grid emits nothing: the mesh is open where the surface leaves the grid.
+ *  Every id and every float depends on no launch shape, block size or thread count.
+ *  - Validation, before any device call (VPT_ERR_INVALID_ARG, the message names the entry; the outputs and *stats untouched): non-null
+ *    desc, voxels and stats, whd >= 1 with a product < 2^31, origin, step and iso finite, every step > 0, capacities >= 0.
+ *  - Outputs.  stats->num_vertices / num_quads are set first.  positions / normals: float3 per vertex (normals may be NULL), quads: int4
+ *    per quad.  As with vpt_scene_get_lights, a NULL array is not written, and a capacity below the count of an array that is given is
+ *    VPT_ERR_INVALID_ARG with the counts set and nothing written.  positions and quads NULL: only the counts are made (classify and scan).
+ *    More than 2^31 - 1 quads: VPT_ERR_UNSUPPORTED.
+ *  - A grid with an axis of one voxel has no cells: 0 vertices, 0 quads, no kernel launched (stats->launches == 0), no device looked
+ *    for.  A grid without a sign change gives 0 / 0 as well: vpt_mesh_sdf finds that out from its host array (launches == 0, no device
+ *    looked for), vpt_scene_mesh_volume from its two counting launches (launches == 2).
+ *  - Synchronous.  launches: kernels and scans launched; device_ms: their time by HIP events.
+ * vpt_mesh_sdf takes the grid from host memory.  vpt_scene_mesh_volume takes volume `volume` of a resident scene where it lies in the
+ * voxel pool - no voxel crosses PCIe - and writes nothing to the scene.  desc NULL: iso 0, origin 0, step = res * W / (W - 1) per axis
+ * (W - 1 taken as 1 on an axis of one voxel), the space the renderer's lookup reads the grid in before scalef; a desc that is given carries the
+ * volume's whd.  region (nullable): a box of voxels inside the grid, meshed as a grid of its own - ids and order are those of the
+ * rule applied to the sub-grid alone - with its vertices in place: cell x of the region lies at origin + ((float)(lo + x) + u) * step.
+ * The host-array entry, the resident entry and the resident entry with a region of the whole grid give the same bytes. */
+typedef struct vpt_sdf_mesh_desc { int32_t whd[3]; float origin[3], step[3], iso; } vpt_sdf_mesh_desc;
+typedef struct vpt_sdf_mesh_region { int32_t lo[3], whd[3]; } vpt_sdf_mesh_region;
+typedef struct vpt_sdf_mesh_stats { int32_t num_vertices, num_quads, launches; float device_ms; } vpt_sdf_mesh_stats;
+int vpt_mesh_sdf(int device, const vpt_sdf_mesh_desc* desc, const float* voxels, float* positions, float* normals /* may be NULL */,
+                 int32_t vertex_capacity, int32_t* quads, int32_t quad_capacity, vpt_sdf_mesh_stats* stats);
+int vpt_scene_mesh_volume(vpt_scene* scene, int volume, const vpt_sdf_mesh_desc* desc /* may be NULL */, const vpt_sdf_mesh_region* region /* may be NULL */,
+                          float* positions, float* normals, int32_t vertex_capacity, int32_t* quads, int32_t quad_capacity, vpt_sdf_mesh_stats* stats);
+
 /* Device self-test of an arithmetic shortcut the kernels rely on for bit-exact parity: the reference divides
  * (1 / d per ray, yocto_bvh.cpp:806-808; 1 / det per triangle, yocto_geometry.h:690), the kernels use
  * v_rcp_f32 + one Newton step where every lane's operand has a biased exponent in 1..250.  Runs all 2^32 bit

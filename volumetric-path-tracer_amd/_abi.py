@@ -174,6 +174,21 @@ class VptBakeStats(C.Structure):  # vpt_bake_stats
                 ("device_ms", C.c_float)]
 
 
+class VptSdfMeshDesc(C.Structure):  # vpt_sdf_mesh_desc
+    _fields_ = [("whd", C.c_int32 * 3), ("origin", C.c_float * 3), ("step", C.c_float * 3), ("iso", C.c_float)]
+
+
+class VptSdfMeshRegion(C.Structure):  # vpt_sdf_mesh_region
+    _fields_ = [("lo", C.c_int32 * 3), ("whd", C.c_int32 * 3)]
+
+
+class VptSdfMeshStats(C.Structure):  # vpt_sdf_mesh_stats
+    _fields_ = [("num_vertices", C.c_int32), ("num_quads", C.c_int32), ("launches", C.c_int32), ("device_ms", C.c_float)]
+
+
+assert C.sizeof(VptSdfMeshDesc) == 40 and C.sizeof(VptSdfMeshRegion) == 24 and C.sizeof(VptSdfMeshStats) == 16
+
+
 class VptBvhRebuild(C.Structure):  # vpt_bvh_rebuild
     _fields_ = [("num_shapes", C.c_int32), ("shape_ids", C.POINTER(C.c_int32)), ("scene", C.c_int32)]
 
@@ -358,6 +373,9 @@ hip.vpt_build_bvh.argtypes = [C.c_int, _p, C.c_int, _p, C.c_int, C.POINTER(C.c_i
 hip.vpt_build_bvh_quality.argtypes = [C.c_int, _p, C.c_int, C.c_int, _p, C.c_int, C.POINTER(C.c_int), _p]
 hip.vpt_bake_sdf.argtypes = [C.c_int, C.POINTER(VptBakeDesc), _p, C.POINTER(VptBakeStats)]
 hip.vpt_bake_feature_normals.argtypes = [C.POINTER(VptBakeDesc), _p, _p]
+hip.vpt_mesh_sdf.argtypes = [C.c_int, C.POINTER(VptSdfMeshDesc), _p, _p, _p, C.c_int32, _p, C.c_int32, C.POINTER(VptSdfMeshStats)]
+hip.vpt_scene_mesh_volume.argtypes = [_p, C.c_int, C.POINTER(VptSdfMeshDesc), C.POINTER(VptSdfMeshRegion), _p, _p, C.c_int32, _p, C.c_int32,
+                                      C.POINTER(VptSdfMeshStats)]
 hip.vpt_last_wave_costs.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int)]
 hip.vpt_scene_record_bytes.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 hip.vpt_multi_create.argtypes = [_p, C.POINTER(C.c_int), C.c_int, C.POINTER(_p)]
@@ -441,6 +459,9 @@ host.vpth_bake_volume.argtypes = [_p, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int
 host.vpth_scene_get_volume.argtypes = [_p, C.c_int, _p, C.POINTER(C.c_float), _p, C.c_int64]
 host.vpth_scene_get_volume.restype = C.c_int64
 host.vpth_save_volume.argtypes = [C.c_char_p, _p, C.c_float, _p, C.c_char_p, C.c_int]
+host.vpth_mesh_sdf.argtypes = [C.POINTER(VptSdfMeshDesc), _p, C.POINTER(VptSdfMeshRegion), _p, _p, C.c_int32, _p, C.c_int32, C.POINTER(VptSdfMeshStats),
+                               C.c_char_p, C.c_int]
+host.vpth_save_mesh_ply.argtypes = [C.c_char_p, _p, _p, C.c_int, _p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_tonemap.argtypes = [C.c_int64, _p, C.c_float, C.c_int, C.c_int, _p, _p]
 host.vpth_upscale_preview.argtypes = [C.c_int, C.c_int, C.c_int, _p, C.c_int, C.c_int, _p]
 host.vpth_make_state_jump.argtypes = [C.c_int, C.c_int, _p]
@@ -500,6 +521,36 @@ def _counted(fn, handle, dtype, what: str, *tail) -> np.ndarray:
     _check(fn(handle, None, 0, C.byref(n), *tail), what)
     out = np.zeros(n.value, dtype)
     _check(fn(handle, out.ctypes.data if len(out) else None, len(out), C.byref(n), *tail), what)
+    return out
+
+
+def _mesh_desc(whd, origin, step, iso: float) -> VptSdfMeshDesc:
+    """vpt_sdf_mesh_desc of whd = (w, h, d); origin and step: three floats each, or one for every axis"""
+    f3 = lambda v: (C.c_float * 3)(*np.broadcast_to(np.asarray(v, np.float32), (3,)))
+    return VptSdfMeshDesc((C.c_int32 * 3)(*(int(v) for v in whd)), f3(origin), f3(step), float(iso))
+
+
+def _mesh_region(region):
+    """vpt_sdf_mesh_region of (lo, whd), each (x, y, z); None stays None"""
+    if region is None:
+        return None
+    lo, size = region
+    return VptSdfMeshRegion((C.c_int32 * 3)(*(int(v) for v in lo)), (C.c_int32 * 3)(*(int(v) for v in size)))
+
+
+def _meshed(call, stats=None) -> dict:
+    """the "ask the counts, then fill" outputs of vpt_mesh_sdf, vpt_scene_mesh_volume and vpth_mesh_sdf: call(positions, normals,
+    vertex_capacity, quads, quad_capacity, byref(stats)) raises what it refuses; the first call makes the counts, the second fills arrays of
+    those sizes.  Returns {"positions", "normals": (n, 3) float32, "quads": (m, 4) int32}, empty arrays for an empty mesh; `stats`: a dict
+    that receives the fields of vpt_sdf_mesh_stats as the last call left them."""
+    st = VptSdfMeshStats()
+    call(None, None, 0, None, 0, C.byref(st))
+    nv, nq = st.num_vertices, st.num_quads
+    out = {"positions": np.zeros((nv, 3), np.float32), "normals": np.zeros((nv, 3), np.float32), "quads": np.zeros((nq, 4), np.int32)}
+    if nv:
+        call(out["positions"].ctypes.data, out["normals"].ctypes.data, nv, out["quads"].ctypes.data if nq else None, nq, C.byref(st))
+    if stats is not None:
+        stats.update({name: getattr(st, name) for name, _ in VptSdfMeshStats._fields_})
     return out
 
 

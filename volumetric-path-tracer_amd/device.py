@@ -9,8 +9,8 @@ from typing import TYPE_CHECKING, Optional
 import numpy as np
 
 from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SDF_AOV_PLANES, SHADER_NAMES, VptAdaptive, VptAovPlanes, VptSdfAovPlanes, VptDisplay, VptError, VptLayout, VptParams,
-                   VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, _counted, _edit_call, _p, hip, host)
-from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit
+                   VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, _counted, _edit_call, _mesh_desc, _mesh_region, _meshed, _p, hip, host)
+from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, mesh
 
 if TYPE_CHECKING:
     from .host_scene import HostScene
@@ -270,6 +270,28 @@ class DeviceScene(_Handle):
         out = np.zeros((d, h, w), np.float32)
         _check(hip.vpt_scene_get_voxels(self.handle, index, out.ctypes.data, out.size), "vpt_scene_get_voxels")
         return out
+
+    def mesh_volume(self, index: int, iso: float = 0.0, origin=None, step=None, region=None, stats: Optional[dict] = None) -> dict:
+        """vpt_scene_mesh_volume (include/vpt.h): the iso surface of volume `index` as a quad mesh, made on the device from the voxels where
+        they lie in the resident pool - no voxel crosses PCIe, nothing of the scene changes.  origin / step None: bake_volume's defaults
+        (origin 0, step = res * W / (W - 1) per axis: the grid's local frame divided by scalef).  region = (lo, whd), each (x, y, z): that
+        box meshed as a grid of its own, its vertices in place.  Returns the mesh(...) dictionary HostScene.add_shape takes - the bits of
+        mesh_sdf(get_voxels(index), ...) and of HostScene.mesh_volume.  stats: a dict that receives num_vertices, num_quads, launches,
+        device_ms."""
+        desc = None
+        if not (iso == 0.0 and origin is None and step is None):
+            vols, _, _ = self.get_volumes()
+            if not 0 <= index < len(vols):
+                raise VptError(f"volume {index} out of range")
+            whd, res = tuple(vols[index].whd), np.float32(vols[index].res)
+            if step is None:
+                step = np.array([res * np.float32(w) / np.float32(max(1, w - 1)) for w in whd], np.float32)
+            desc = _mesh_desc(whd, np.zeros(3, np.float32) if origin is None else origin, step, iso)
+        box = _mesh_region(region)
+        call = lambda *out: _check(hip.vpt_scene_mesh_volume(self.handle, index, C.byref(desc) if desc else None, C.byref(box) if box else None, *out),
+                                   "vpt_scene_mesh_volume")
+        m = _meshed(call, stats)
+        return mesh(m["positions"], quads=m["quads"], normals=m["normals"])
 
     def get_lights(self):
         """(light list as a LIGHT array, CDF pool as float32) as the device holds them (vpt_scene_get_lights)"""

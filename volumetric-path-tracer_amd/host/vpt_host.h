@@ -432,6 +432,19 @@ bool save_volume(const string& filename, const volume_data& vol, string& error);
 // words (false, `error` set, the volume untouched); entry.volume is the caller's to resolve.
 bool sculpt_volume(volume_data& volume, const vpt_sculpt_entry& entry, const vpt_sculpt_stamp* stamps, int num_stamps, string& error);
 
+// ---- a quad mesh out of a signed-distance voxel grid (include/vpt.h: vpt_mesh_sdf; host/vpt_sdf_mesh.cpp) ---------------------------
+struct sdf_mesh {
+  vector<vec3f> positions = {}, normals = {};
+  vector<vec4i> quads     = {};
+};
+// the host mirror of vpt_mesh_sdf: the rule header (csrc/vpt_sdf_mesh_rule.h) in plain serial loops over the grid, or over `region` of it as
+// vpt_scene_mesh_volume takes one - the same bits as the device; throws std::invalid_argument with the C-ABI's words for what it refuses
+sdf_mesh mesh_sdf(const float* voxels, const vpt_sdf_mesh_desc& desc, const vpt_sdf_mesh_region* region = nullptr);
+// the same on GPU `device` (vpt_mesh_sdf); throws std::runtime_error with vpt_last_error() if that fails
+sdf_mesh mesh_sdf_device(const float* voxels, const vpt_sdf_mesh_desc& desc, int device);
+// positions, normals (unless empty) and quads as a binary little-endian PLY file, which load_shape reads back with the same bits
+bool save_mesh_ply(const string& filename, const sdf_mesh& mesh, string& error);
+
 // ---- flattening to the C-ABI ----------------------------------------------------------------
 struct flat_scene {
   vpt_scene_desc desc = {};

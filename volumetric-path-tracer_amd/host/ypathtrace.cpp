@@ -22,7 +22,10 @@
 // the bytes of the offline run with the same arguments: the same state, the same host 8-bit stage), --bake-sdf FILE (no scene is
 // rendered: the shape file is loaded through the host loader, baked by vpt_bake_sdf on GPU 0 - or by the host mirror with --bake-host,
 // same bytes - into a grid of --bake-res voxels per axis fitted around it with --bake-padding voxels to spare, and written to --output
-// as the binary .sdf the scene loader reads; `res` and a vol_instances entry that puts the grid where the shape was go to stdout).
+// as the binary .sdf the scene loader reads; `res` and a vol_instances entry that puts the grid where the shape was go to stdout),
+// --mesh-sdf FILE (no scene is rendered: the binary .sdf is meshed at --mesh-iso by vpt_mesh_sdf on GPU 0 - or by the host mirror with
+// --mesh-host, same bytes - in the grid's own space, origin 0 and step = res * W / (W - 1), and written to --output as a binary PLY of
+// positions, normals and quads; the counts go to stdout).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -78,6 +81,9 @@ const std::vector<std::pair<string, option>> options = {
     {"bake-res", {option::int_k, 1, 1024, "Baking: voxels per axis."}},
     {"bake-padding", {option::int_k, 0, 64, "Baking: voxels to spare around the shape on each side."}},
     {"bake-host", {option::bool_k, 1, 0, "Baking: run the host mirror instead of the GPU: same file."}},
+    {"mesh-sdf", {option::string_k, 1, 0, "Mesh this binary .sdf grid into quads written to --output (PLY); renders nothing. (extension)"}},
+    {"mesh-iso", {option::anyfloat_k, 1, 0, "Meshing: the iso value, inside is below it."}},
+    {"mesh-host", {option::bool_k, 1, 0, "Meshing: run the host mirror instead of the GPU: same file."}},
 };
 const option* find_option(const string& name) {
   for (auto& [n, o] : options)
@@ -252,6 +258,32 @@ int main(int argc, const char** argv) {
       printf("res: %.9g\n", baked.volume.res);
       printf("{\"name\": \"baked\", \"volume\": 0, \"material\": 0, \"scale\": %.9g, \"frame\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g]}\n",
           baked.instance.scalef, f.x.x, f.x.y, f.x.z, f.y.x, f.y.y, f.y.z, f.z.x, f.z.y, f.z.z, f.o.x, f.o.y, f.o.z);
+      return 0;
+    } catch (const std::exception& e) {
+      print_fatal(e.what());
+    }
+  }
+
+  for (auto name : {"mesh-iso", "mesh-host"})
+    if (values.count(name) && !values.count("mesh-sdf")) cli_error(string{"option "} + name + " needs --mesh-sdf");
+  if (values.count("mesh-sdf")) {
+    auto iso     = 0.0f;
+    auto on_host = false;
+    get_float("mesh-iso", iso), get_bool("mesh-host", on_host);
+    if (!values.count("output")) cli_error("missing value for output");
+    try {
+      auto error  = string{};
+      auto volume = volume_data{};
+      if (!load_volume(values["mesh-sdf"], volume, true, error)) print_fatal(error);
+      // the space the renderer's lookup reads the grid in before scalef: origin 0, step = res * W / (W - 1) per axis
+      auto desc = vpt_sdf_mesh_desc{{volume.whd.x, volume.whd.y, volume.whd.z}, {0, 0, 0}, {0, 0, 0}, iso};
+      for (auto k = 0; k < 3; k++) desc.step[k] = volume.res * (float)desc.whd[k] / (float)std::max(1, desc.whd[k] - 1);
+      auto t0   = std::chrono::steady_clock::now();
+      auto mesh = on_host ? mesh_sdf(volume.vol.data(), desc) : mesh_sdf_device(volume.vol.data(), desc, 0);
+      auto secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (!save_mesh_ply(output, mesh, error)) print_fatal(error);
+      printf("meshed: %d x %d x %d voxels at iso %.9g into %zu vertices and %zu quads in %.3f s (%s)\n", desc.whd[0], desc.whd[1], desc.whd[2], iso,
+          mesh.positions.size(), mesh.quads.size(), secs, on_host ? "host mirror" : "GPU 0");
       return 0;
     } catch (const std::exception& e) {
       print_fatal(e.what());

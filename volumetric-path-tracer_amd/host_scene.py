@@ -11,7 +11,7 @@ import numpy as np
 
 from ._abi import (BVH_MIDDLE, BVH_NODE, BVH_SAH, LIGHT, MESH_ELEMENTS, MESH_FLOATS, SDF_TYPES, VOXELS_REPLACE, VptBakeStats, VptCamera,
                    VptEnvironment, VptError, VptMaterial, VptSceneDescBvh, VptSceneDescLights, VptSculptEntry, VptSdf, VptVolumeInstance, _Handle,
-                   _check, _filled, _host_call, hip, host)
+                   _check, _filled, _host_call, _mesh_desc, _mesh_region, _meshed, hip, host)
 from .device import PathtraceParams, PathtraceState
 from .edits import (LEVEL_TABLES, BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan,
                     TextureEdit, VolumeEdit, VolumeSource, mesh)
@@ -163,6 +163,39 @@ def bake_sdf(positions: np.ndarray, faces: np.ndarray, whd, padding: int = 2, de
     _host_call(host.vpth_bake_volume, positions.ctypes.data, len(positions), triangles.ctypes.data, len(triangles), whd.ctypes.data, padding,
                -1 if device is None else device, voxels.ctypes.data, C.byref(res), frame.ctypes.data, C.byref(st))
     return BakedVolume(voxels.reshape(int(whd[2]), int(whd[1]), int(whd[0])), res.value, frame, 1.0, _bake_stats(st))
+
+
+def mesh_sdf(voxels: np.ndarray, origin, step, iso: float = 0.0, device: Optional[int] = 0, *, region=None, stats: Optional[dict] = None) -> dict:
+    """The iso surface of a signed-distance grid as a quad mesh by the rule of include/vpt.h (vpt_mesh_sdf: naive surface nets).  voxels:
+    (d, h, w) float32, voxel (i, j, k) sampled at origin + (i, j, k) * step (three floats each, or one for every axis); inside is
+    voxel < iso.  Returns the mesh(...) dictionary HostScene.add_shape takes: positions, normals (n, 3) float32 and quads (m, 4) int32 that
+    face out of the inside (None where the surface does not cross the grid).  device: GPU index, or None for the host mirror - the same
+    bits.  region = (lo, whd), each (x, y, z), host mirror only: that box meshed as a grid of its own, its vertices in place
+    (vpt_scene_mesh_volume's region).  stats: a dict that receives num_vertices, num_quads, launches, device_ms."""
+    voxels = np.ascontiguousarray(voxels, np.float32)
+    if voxels.ndim != 3:
+        raise VptError(f"expected (d, h, w) voxels, got {voxels.shape}")
+    desc, box = _mesh_desc(voxels.shape[::-1], origin, step, iso), _mesh_region(region)
+    if device is None:
+        call = lambda *out: _host_call(host.vpth_mesh_sdf, C.byref(desc), voxels.ctypes.data, C.byref(box) if box else None, *out)
+    elif box is not None:
+        raise VptError("mesh_sdf: a region is meshed by the host mirror (device=None) or out of a resident scene (DeviceScene.mesh_volume)")
+    else:
+        call = lambda *out: _check(hip.vpt_mesh_sdf(device, C.byref(desc), voxels.ctypes.data, *out), "vpt_mesh_sdf")
+    m = _meshed(call, stats)
+    return mesh(m["positions"], quads=m["quads"], normals=m["normals"])
+
+
+def save_mesh_ply(path: str, positions, quads, normals=None) -> None:
+    """positions, normals (unless None) and quads as a binary little-endian PLY file, which the scene loader reads back with the same bits"""
+    positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    quads = np.ascontiguousarray(np.zeros((0, 4)) if quads is None else quads, np.int32).reshape(-1, 4)
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if len(normals) != len(positions):
+            raise VptError("save_mesh_ply: one normal per vertex")
+    _host_call(host.vpth_save_mesh_ply, os.fsencode(path), positions.ctypes.data, None if normals is None else normals.ctypes.data, len(positions),
+               quads.ctypes.data, len(quads))
 
 
 # Which change of a HostScene may begin while which other is pending.  The ids of a pending edit name the lists as they were when it
@@ -771,6 +804,16 @@ class HostScene(_Handle):
         _host_call(host.vpth_scene_update_volumes, self.handle)
         edit, self._sculpt_edit = self._sculpt_edit, SculptEdit()
         return edit
+
+    def mesh_volume(self, index: int, iso: float = 0.0, origin=None, step=None, region=None, stats: Optional[dict] = None) -> dict:
+        """the host mirror of DeviceScene.mesh_volume on the scene's copy of volume `index` (pending bakes run first, as for volume()):
+        mesh_sdf(device=None) with bake_volume's defaults - origin 0, step = res * W / (W - 1) per axis"""
+        voxels, res = self.volume(index)
+        if origin is None:
+            origin = np.zeros(3, np.float32)
+        if step is None:
+            step = np.array([np.float32(res) * np.float32(w) / np.float32(max(1, w - 1)) for w in voxels.shape[::-1]], np.float32)
+        return mesh_sdf(voxels, origin, step, iso, device=None, region=region, stats=stats)
 
     def lights(self):
         """(light list as a LIGHT array, CDF pool as float32) of the descriptor (copies)"""

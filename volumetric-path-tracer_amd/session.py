@@ -163,6 +163,34 @@ class RenderSession(_Handle):
         self.edit_sculpts(host.update_sculpts())
         return entry
 
+    def mesh_volume(self, index: int, iso: float = 0.0, origin=None, step=None, region=None, stats: Optional[dict] = None) -> dict:
+        """DeviceScene.mesh_volume on the session's scene (vpt_scene_mesh_volume waits for the session's launches); the session goes on
+        as it was: nothing of the scene changes"""
+        return self.dev.mesh_volume(index, iso, origin, step, region, stats)
+
+    def volume_to_shape(self, host, vol_instance: int, material: int):
+        """The editor's gesture: the surface the sphere trace finds on grid instance `vol_instance` as a shape of quads, instanced where it
+        is.  The instance's grid is meshed on the device with step * scalef (the instance's lookup space); the mesh becomes a new shape
+        (host.add_shape, update_shapes, edit_shapes) and a new instance of it with `material` and the inverse of the grid instance's frame
+        (host.add_instance, update_instances, edit_instances): `host` is the HostScene the session's scene was made from.  Returns (shape
+        id, instance id).  The arithmetic of this helper carries no bit contract: the mesh it makes goes to the host mirror and to the
+        device alike."""
+        inst = host.volume_instance(vol_instance)
+        voxels, res = host.volume(inst.volume)
+        scale = np.float32(inst.scalef)
+        step = np.array([np.float32(res) * np.float32(w) / np.float32(max(1, w - 1)) * scale for w in voxels.shape[::-1]], np.float32)
+        m = self.mesh_volume(inst.volume, step=step)
+        if m["positions"] is None or m["quads"] is None:
+            raise VptError(f"volume_to_shape: the grid of volume instance {vol_instance} has no surface inside it")
+        to_grid = np.array([inst.frame.x[:], inst.frame.y[:], inst.frame.z[:], inst.frame.o[:]], np.float64)
+        axes = np.linalg.inv(to_grid[:3])   # world = (grid - o) @ inverse(axes)
+        frame = np.concatenate([axes, -(to_grid[3] @ axes)[None]]).astype(np.float32).reshape(12)
+        shape = host.add_shape(**m)
+        self.edit_shapes(host.update_shapes())
+        instance = host.add_instance(frame, shape, material)
+        self.edit_instances(host.update_instances())
+        return shape, instance
+
     def rebuild_bvh(self, rebuild: "BvhRebuild") -> None:
         """vpt_scene_rebuild_bvh on the session's scene with the BvhRebuild of HostScene.rebuild_bvh(), then a reset"""
         _edit_call(self.handle, "vpt_session_rebuild_bvh_quality", rebuild, rebuild.quality)
