@@ -57,7 +57,7 @@ def test_table_form_equals_register_form(vpt, monkeypatch, scene_file):
     """128 wide, 8 spp, 64 bounces: waves with lanes in different media, in none and entering one.  VPT_MEDIUM_REGS is read per launch."""
     host = vpt.HostScene(path(scene_file))
     dev = vpt.DeviceScene(host, 0)
-    # which instance a scene runs is decided by its lights (vpt_capi.hip: launch_mesh_instance): an emissive mesh of more than one
+    # which instance a scene runs is decided by its lights (vpt_render.hip: launch_mesh_instance): an emissive mesh of more than one
     # BVH leaf (more than four elements) makes sample_lights_pdf span trips - 03_volume_lobes has one, 03_volume has quads only.
     # No entry point names the instance; this is the rule of build_lights, restated, so that a change of the scenes shows here
     lights, _ = dev.get_lights()

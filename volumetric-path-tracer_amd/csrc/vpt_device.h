@@ -23,7 +23,7 @@
 #define VPT_FLOOR_SHIFT 4   // group_nodes() (vpt_mesh_kernel.hip.h): {csgn, slow} in the low 4 bits of the word a ray's state travels in, its pop floor above them
 
 // Scene features a kernel instance is compiled for (template parameter FEAT of the mesh kernels): code for a feature the
-// scene does not have costs registers in every path (the allocator serves the worst one), so vpt_capi.hip launches the
+// scene does not have costs registers in every path (the allocator serves the worst one), so vpt_render.hip launches the
 // instance without it - 03_volume, whose lights are quads and an environment: 622 -> 676 Msamples/s.
 enum { VPT_FEAT_COMPACT_TRIS = 8,   // not a light feature: the instance reads DScene::tri_prims / tri_attrs (scenes whose shapes all hold triangles)
        VPT_FEAT_LARGE_LIGHTS = 1,   // emissive meshes with a real BVH: sample_lights_pdf walks them with extra trips (ST_LPDF)

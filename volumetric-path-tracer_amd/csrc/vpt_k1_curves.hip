@@ -7,7 +7,7 @@ VPT_K1_CURVES_INSTANCES(VPT_K1_DEFINE, K_NAIVE)
 VPT_K1_CURVES_INSTANCES(VPT_K1_DEFINE, K_EYELIGHT)
 VPT_K1_CURVES_INSTANCES(VPT_K1_DEFINE, K_DEBUG)
 
-// vpt_intersect (vpt_capi.hip) for scenes with points or lines: the traversal of the VPT_FEAT_CURVES instances
+// vpt_intersect (vpt_probes.hip) for scenes with points or lines: the traversal of the VPT_FEAT_CURVES instances
 template <bool SPILL>
 __global__ void vpt_intersect_curves_kernel(DScene sc, int n, const float* rays, int instance, int* ids, float* uvt, stack_cfg stack) {
   extern __shared__ int lds_stack[];

@@ -1,5 +1,5 @@
-// vpt_launch.h — the kernels the host launches (vpt_capi.hip, vpt_schedule.hip): declarations only, with their launch bounds, the types of their
-// arguments and the launch constants both sides need.  vpt_capi.hip sees no kernel body: each kernel is defined, and its instances
+// vpt_launch.h — the kernels the host launches (vpt_render.hip, vpt_probes.hip, vpt_capi.hip, vpt_schedule.hip): declarations only, with their launch bounds, the types of their
+// arguments and the launch constants both sides need.  Those units see no kernel body: each kernel is defined, and its instances
 // instantiated, in exactly one kernel unit, so that a host-side edit recompiles no kernel and no kernel is compiled twice:
 //   vpt_k1_volpath.hip, vpt_k1_path.hip   K1 (vpt_mesh_kernel.hip.h) for the two path tracers        (the instance lists:
 //   vpt_k1_curves.hip                     K1 for scenes with points or lines, + vpt_intersect on them   vpt_k1_instances.hip.h)

@@ -439,7 +439,7 @@ VPT_DEV hit_t traverse(const DScene& sc, bool active, f3 wo, f3 wd, int only_ins
     int         gcur = pull(owner, cur), gsp = pull(owner, sp);
     const int   gwnb = pull(owner, wnb);
     // sign bits of the ray's direction, NaN-prone flag, pop floor of the ray's level (the stack depth at instance entry: the whole upper
-    // 28 bits, vpt_capi.hip checks at scene creation that the deepest worst case fits them)
+    // 28 bits, vpt_scene_prep.cpp checks at scene creation that the deepest worst case fits them)
     const int   gmisc = pull(owner, csgn | (slow ? 8 : 0) | (shape_base >= 0 ? shape_base : 0) << VPT_FLOOR_SHIFT);
     if (!gact) gcur = VPT_NONE;
     const int  gfloor = gmisc >> VPT_FLOOR_SHIFT, gcsgn = gmisc & 7;
@@ -772,7 +772,7 @@ VPT_DEV void mesh_kernel_body(const DScene& sc, const DParams& pr, float4* __res
   // (vpt_device.h) after the query, by the lanes that are in a medium - about a third of the trips - instead of staying in registers
   // through every BVH query.  Trip-spanning instances (HAS_LARGE) keep the medium a pending MIS evaluation enters in the high half
   // until the weight is finished.  MED_REGS: the general instance carries the ten values themselves, copied at the entry hit, for
-  // scenes whose media vary over the surface (vpt_capi.hip routes them here).
+  // scenes whose media vary over the surface (vpt_render.hip: launch_mesh_instance routes them here).
   constexpr bool MED_REGS = (FEAT & VPT_FEAT_ALL) == VPT_FEAT_ALL;
   unsigned med = 0;
   f3    med_density = mk3(0, 0, 0), med_scattering = mk3(0, 0, 0), med_emission = mk3(0, 0, 0);

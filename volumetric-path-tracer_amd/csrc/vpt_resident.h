@@ -1,5 +1,5 @@
 // vpt_resident.h — the part of a vpt_scene that the edits of a resident scene work on (include/vpt.h: vpt_scene_update, _lights,
-// _textures, _volumes, and vpt_scene_rebuild_bvh): the tables on the device, their host mirrors, and what an edit keeps between calls.  vpt_capi.hip's
+// _textures, _volumes, and vpt_scene_rebuild_bvh): the tables on the device, their host mirrors, and what an edit keeps between calls.  vpt_scene_handle.h's
 // vpt_scene is a `resident` plus its render side (schedule, staging, stacks); the update units and the read-backs of
 // vpt_scene_inspect.hip see only this.
 #pragma once
