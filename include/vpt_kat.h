@@ -38,6 +38,9 @@
  *  VPT_KAT_VOLUME         volume uvw[3]                                   (4)    value                                            (1)   eval_volume (yocto_sdfs.cpp:92-127)
  *  VPT_KAT_SDF_FUNCTION   sdf p[3] (in the sdf's local frame)             (4)    distance                                         (1)   sdf_data::f, i.e. sd_* of yocto_sdfs.h:43-80 as bound by
  *                                                                                                                                       yocto_sceneio.cpp:3684-3730
+ *
+ * On a scene with points or lines VPT_KAT_INTERSECT and VPT_KAT_SURFACE return VPT_ERR_UNSUPPORTED before anything is launched (their
+ * device functions are the instances that read every leaf record as a quad): vpt_intersect and the AOV pass reach those shapes.
  */
 #ifndef VPT_KAT_H_
 #define VPT_KAT_H_

@@ -58,6 +58,10 @@ int vpt_kat_strides(int op, int* in_stride, int* out_stride) {
 int vpt_kat(vpt_scene* s, int op, int iparam, int n, const float* in, float* out) {
   REQUIRE(s && n >= 0 && (n == 0 || (in && out)), "bad argument");
   REQUIRE(op >= 0 && op < VPT_KAT_OP_COUNT, "unknown KAT op %d", op);
+  // vpt_kat_kernel's traverse and eval_surface_point are the instances without VPT_FEAT_CURVES: they would read point and line leaf
+  // records as quads
+  if (s->curves && (op == VPT_KAT_INTERSECT || op == VPT_KAT_SURFACE))
+    return vpt_set_error(VPT_ERR_UNSUPPORTED, "KAT op %d on a scene with points or lines: vpt_intersect and the AOV pass (vpt_render_aov) are the ways in", op);
   if (n == 0) return VPT_OK;
   const int si = k_kat_strides[op][0], so = k_kat_strides[op][1];
   const DScene& D = s->d;
