@@ -51,8 +51,12 @@ typedef enum vpt_shader {
   VPT_SHADER_TEXCOORD        = 5,
   VPT_SHADER_COLOR           = 6,
   VPT_SHADER_IMPLICIT        = 7,
-  VPT_SHADER_IMPLICIT_NORMAL = 8
+  VPT_SHADER_IMPLICIT_NORMAL = 8,
+  /* ids 9 .. 15 name nothing and stay refused (VPT_ERR_UNKNOWN_SHADER, "sampler unknown"); the extension shaders start at 16 */
+  VPT_SHADER_VOLGRID         = 16  /* not the reference's: the voxel-grid instances as heterogeneous media ("the volgrid shader" below) */
 } vpt_shader;
+/* 1 for a shader id some kernel renders (0 .. 8 and 16), 0 for every other: what each entry point that takes vpt_params asks */
+int vpt_shader_known(int shader_id);
 
 /* material_type, yocto_scene.h:105-110 */
 typedef enum vpt_material_type {
@@ -530,6 +534,72 @@ typedef struct vpt_sculpt_edit {
   int32_t num_stamps;  const vpt_sculpt_stamp* stamps;
 } vpt_sculpt_edit;
 int vpt_scene_sculpt_volumes(vpt_scene* scene, const vpt_sculpt_edit* edit);
+
+/* ---- the volgrid shader: voxel grids as heterogeneous media (VPT_SHADER_VOLGRID) ------------------------------------
+ * The reference has no such shader: the rule is this project's and is written here.  The parts that more than one side computes - clean,
+ * the brick majorants, a grid instance's record, its density at a point - are csrc/vpt_volgrid_rule.h, compiled by the kernel (K3,
+ * csrc/vpt_volgrid_kernel.hip.h) and by the host mirror (host/vpt_volgrid.cpp), both with -ffp-contract=off.
+ *  - What it sees.  vol_instances as media, environments as background and light.  Mesh instances and analytic SDFs are ignored, as
+ *    `implicit` ignores meshes: there are no surfaces inside the media.
+ *  - Density of grid instance g at world point p.  pl = transform_point(instance.frame, p); bbox_size = volume.res * whd * scalef, as
+ *    eval_sdf (yocto_sdfs.cpp:30-49) maps a point into a grid.  Outside [0, bbox_size] the density is 0.  Inside, v = eval_volume(volume,
+ *    pl * 2 / bbox_size - 1), the reference's trilerp in its term order, and sigma = clean(v) / trdepth with clean(x) = x for a finite
+ *    positive x, 0 otherwise (NaN, +-Inf, negative values, zero) and trdepth that of the instance's material: a voxel value of 1 is a
+ *    mean free path of trdepth.  scalef scales the box, never the density.  A volgrid render (any entry point) of a scene where some grid
+ *    instance's material has trdepth <= 0 or not finite is refused with VPT_ERR_INVALID_ARG, the message names the instance, scene and
+ *    state stay untouched.
+ *  - The medium, from the same material.  Single-scattering albedo = scattering clamped to [0, 1] per channel; phase function
+ *    Henyey-Greenstein with g = scanisotropy (sample_phasefunction, eval_phasefunction: yocto_shading.h:1077-1102); emission is added at
+ *    every real collision; the extinction is grey, colour comes from the albedo.
+ *  - Majorants.  Per volume a table of brick maxima: brick (bx, by, bz) covers the cells [8 b, 8 b + 8) per axis of the W - 1 cells
+ *    between the nodes, and its value is the maximum of clean(node) over the nodes [8 b, min(8 b + 8, W - 1)] per axis.  A trilerp inside
+ *    the brick is a convex combination of those nodes up to rounding, so a tentative collision is real with probability
+ *    min(sigma / majorant, 1).  The tables are built on the device, by the first volgrid launch or query of a handle, and again before a
+ *    volgrid launch whenever the scene was edited since: a handle counts its edits, and those that write voxels (vpt_scene_update_volumes
+ *    with its bakes and pool growth, vpt_scene_sculpt_volumes) apart.  No other shader pays for them.
+ *  - Free flight of a ray (o, d): track.  The grid instances in index order; tmax = the nearest real collision so far, at first none.
+ *    Instance g: the ray is clipped against its box in local space (slab test; the parameter t stays the world's) and against tmax; the
+ *    bricks along it are walked in node coordinates.  A brick of majorant 0 is crossed without a draw.  In a brick of majorant m (as
+ *    extinction: m / trdepth) repeat: t += -log(1 - rand1f(rng)) / m; past the brick's exit: on to the next brick from the exit point (the
+ *    overshoot is discarded: the process has no memory); else rand1f(rng) < min(sigma(p) / m, 1) makes the collision real - tmax = t,
+ *    instance g, on to instance g + 1 - else it is null and the walk goes on.  The nearest real collision over all instances wins:
+ *    independent free flights per medium with the minimum taken are exact for a superposition of media, so instances may overlap and every
+ *    collision has one material.  A free flight that has taken VPT_VOLGRID_MAX_STEPS (2^20) tracking steps ends its path with nothing more
+ *    added and counts in the word vpt_check_watchdog reads.
+ *  - The path (the volume branch of shade_volpathtrace, yocto_pathtrace.cpp:653-683):
+ *      radiance = 0, weight = 1, hit = false
+ *      for bounce in [0, bounces):
+ *        ev = track(ray, rng);  escape: radiance += weight * eval_environment(ray.d), done
+ *        if bounce == 0: hit = true
+ *        radiance += weight * emission
+ *        E = the light-list entries with environment >= 0, in list order
+ *        if E is empty or noimplicit_mis:  incoming = sample_phasefunction(g, outgoing, rn), drawn as sample_scattering draws (rn.x,
+ *            rn.y, then the rnl nobody reads); weight *= albedo - no division: f / pdf is 1 by construction
+ *        else: rand1f < 0.5 ? the same draw : the environment branch of sample_lights for a uniformly chosen entry of E (ruv.x, ruv.y,
+ *            rel, rl as sample_lights draws them); weight *= albedo * (f / (0.5 f + 0.5 pdf_E)), f = eval_phasefunction(g, outgoing,
+ *            incoming), pdf_E = the environment branch of sample_lights_pdf summed over E, times 1 / |E|
+ *        weight zero or not finite: done
+ *        if bounce > 3: rr = min(1, max(weight)); if rr < 1 { rand1f >= rr: done; weight /= rr }
+ *        ray = (position, incoming)
+ *      return (radiance, hit ? 1 : 0)
+ *    The roulette is NOT the reference's min(0.99, .): with 0.99 a white furnace is never exact; with min(1, .) a medium of albedo 1 keeps
+ *    weight 1 for ever and `bounces` ends its paths.  The camera ray, the draws of a sample's jitter and lens, the preview branch of
+ *    samples == 1, the NaN guard and the accumulation into the state are pathtrace_samples', as in every shader here: the alpha channel
+ *    sums `hit`, hits[] counts the samples.
+ * VPT_VOLGRID_NO_BRICKS=1 (read per launch) walks every box with one majorant, the maximum of its volume's bricks: the A/B switch of the
+ * tests and the measurements - same distribution, other draws.
+ *
+ * vpt_scene_get_volgrid_majorants: the brick table of `volume` as the device holds it (built or rebuilt first if it is stale), x fastest;
+ * dims (nullable) receives the bricks per axis, out (nullable with capacity 0: the dims alone) their product of floats.
+ * vpt_scene_volgrid_density: at n world points (3 floats each) sigma[i] = the sum over the grid instances, in index order, of their
+ * densities, and instance[i] (nullable) = the first instance whose box holds the point, -1 if none does.  Refused like a render when a
+ * grid instance's material has no usable trdepth.
+ * vpt_scene_volgrid_stats: tracking steps taken by the handle's volgrid launches so far and the builds of its brick tables so far (either
+ * nullable); synchronous. */
+#define VPT_VOLGRID_MAX_STEPS (1 << 20)
+int vpt_scene_get_volgrid_majorants(vpt_scene* scene, int volume, float* out, int64_t capacity, int32_t dims[3]);
+int vpt_scene_volgrid_density(vpt_scene* scene, int n, const float* points, int32_t* instance, float* sigma);
+int vpt_scene_volgrid_stats(vpt_scene* scene, uint64_t* steps, int32_t* table_builds);
 
 /* ---- the BVHs of a resident scene built anew on the device ------------------------------------------------------------
  * The four edits above keep a tree's topology as creation left it: vpt_scene_update is the reference's update_bvh, a refit.  After a

@@ -18,8 +18,8 @@ from .edits import (BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, SculptEntry
 from .device import (AdaptiveRun, DeviceScene, DisplayParams, MultiDeviceScene, PathtraceParams, PathtraceState, box3_device,   # noqa: F401
                      device_count, layout_pixel_index, layout_slots, make_state_jump, resolve_device, resolve_hits_device, resolve_ids_device,
                      resolve_sdf_ids_device, resolve_srgb8_device, selftest_reciprocal, state_download, state_init_device, state_upload)
-from .host_scene import (BakedVolume, HostScene, bake_sdf, bake_sdf_grid, bake_triangles, build_bvh, catmullclark, displace_vertices,   # noqa: F401
-                         fit_volume, mesh_sdf, save_mesh_ply, save_volume, vertex_normals)
+from .host_scene import (BakedVolume, HostScene, bake_sdf, bake_sdf_grid, bake_triangles, build_bvh, catmullclark, density_from_sdf,   # noqa: F401
+                         displace_vertices, fit_volume, mesh_sdf, save_mesh_ply, save_volume, vertex_normals)
 from .session import RenderSession   # noqa: F401
 from .images import (denoise_device, denoise_render, denoise_scratch_bytes, encode_jpeg_q75, get_render, get_render_hits, half_variance,   # noqa: F401
                      half_variance_device, linear_to_srgb8, pathtrace_guides, tonemap_device, tonemap_image, upscale_device, upscale_preview)

@@ -11,6 +11,27 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 SHADER_NAMES = ["volpathtrace", "pathtrace", "naive", "eyelight", "normal", "texcoord", "color",
                 "implicit", "implicit_normal"]  # yocto_pathtrace.h:101-103
+# the shaders the reference does not have, beside its list: name -> id (include/vpt.h: ids 9 .. 15 name nothing)
+EXTENSION_SHADERS = {"volgrid": 16}
+
+
+def shader_id(name: str) -> int:
+    """the id of a shader name: the reference's by their place in SHADER_NAMES, the extensions' from EXTENSION_SHADERS"""
+    if name in SHADER_NAMES:
+        return SHADER_NAMES.index(name)
+    if name in EXTENSION_SHADERS:
+        return EXTENSION_SHADERS[name]
+    raise VptError("sampler unknown")  # reference: get_shader throws (cpp:947-950)
+
+
+def shader_name(ident: int) -> str:
+    """the name of a shader id; ids that name nothing (9 .. 15 among them) raise VptError("sampler unknown")"""
+    if 0 <= ident < len(SHADER_NAMES):
+        return SHADER_NAMES[ident]
+    for name, value in EXTENSION_SHADERS.items():
+        if value == ident:
+            return name
+    raise VptError("sampler unknown")
 
 
 class VptError(RuntimeError):
@@ -459,6 +480,11 @@ host.vpth_bake_volume.argtypes = [_p, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int
 host.vpth_scene_get_volume.argtypes = [_p, C.c_int, _p, C.POINTER(C.c_float), _p, C.c_int64]
 host.vpth_scene_get_volume.restype = C.c_int64
 host.vpth_save_volume.argtypes = [C.c_char_p, _p, C.c_float, _p, C.c_char_p, C.c_int]
+host.vpth_volgrid_majorants.argtypes = [_p, C.c_int, _p, C.c_int64, _p, C.c_char_p, C.c_int]
+host.vpth_volgrid_density.argtypes = [_p, C.c_int, _p, _p, _p, C.c_char_p, C.c_int]
+hip.vpt_scene_get_volgrid_majorants.argtypes = [_p, C.c_int, _p, C.c_int64, _p]
+hip.vpt_scene_volgrid_density.argtypes = [_p, C.c_int, _p, _p, _p]
+hip.vpt_scene_volgrid_stats.argtypes = [_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
 host.vpth_mesh_sdf.argtypes = [C.POINTER(VptSdfMeshDesc), _p, C.POINTER(VptSdfMeshRegion), _p, _p, C.c_int32, _p, C.c_int32, C.POINTER(VptSdfMeshStats),
                                C.c_char_p, C.c_int]
 host.vpth_save_mesh_ply.argtypes = [C.c_char_p, _p, _p, C.c_int, _p, C.c_int, C.c_char_p, C.c_int]

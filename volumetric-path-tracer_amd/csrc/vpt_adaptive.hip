@@ -302,10 +302,9 @@ int vpt_adaptive_run_create(vpt_scene* s, const vpt_params* params, const vpt_ad
   if (int rc = make_dparams(params, layout, 0, r->pr)) return rc;
   r->s = s, r->params = *params, r->a = *a, r->st = (hipStream_t)stream;
   r->img = (float4*)d_image, r->hit = (int*)d_hits, r->rng = (ulonglong2*)d_rng;
-  r->implicit = params->shader >= VPT_SHADER_IMPLICIT;
-  if (r->implicit)
-    if (int rc = implicit_lds(s)) return rc;
+  r->implicit = params->shader >= VPT_SHADER_IMPLICIT;   // K2 and K3: the kernels that report through the watchdog word
   HIP_TRY(hipSetDevice(s->device));
+  if (int rc = shader_setup(s, params, r->st)) return rc;   // (an edit ends a run's validity: what is set up here holds for its rounds)
   const DParams&   pr = r->pr;
   traversal_launch full;   // the spilled stacks are indexed by global lane: sized for the full layout, a compacted grid is never larger
   if (int rc = traversal_setup(s, pr.nslots, full)) return rc;

@@ -76,6 +76,7 @@ extern "C" {
 
 const char* vpt_last_error(void) { return g_error_text().c_str(); }
 const char* vpt_version(void) { return "vpt-mi355x 0.1 (gfx950)"; }
+int vpt_shader_known(int id) { return (id >= 0 && id <= VPT_SHADER_IMPLICIT_NORMAL) || id == VPT_SHADER_VOLGRID; }
 
 int vpt_device_count(void) {
   int n = 0;
@@ -167,6 +168,9 @@ static bool moves_geometry(const vpt_subdiv_edit& e) { return e.num > 0; }
 static bool writes_materials(const vpt_scene_edit& e) { return e.num_materials > 0; }
 template <typename Edit> static bool moves_geometry(const Edit&) { return false; }   // environments, textures, volumes, SDFs
 template <typename Edit> static bool writes_materials(const Edit&) { return false; }
+static bool writes_voxels(const vpt_volume_edit&) { return true; }   // voxels in place, baked into the pool, or moved into a grown pool
+static bool writes_voxels(const vpt_sculpt_edit&) { return true; }
+template <typename Edit> static bool writes_voxels(const Edit&) { return false; }
 
 // One edit, from the idle device it needs to what the render side owes it afterwards.  apply(resident&, edit, edit_outcome&): the
 // unit's work (vpt_resident.h says what it reports).
@@ -178,6 +182,8 @@ static int edit_scene(vpt_scene* s, const Edit* edit, Apply apply) {
   edit_outcome out = {false, false, false, s->stack_cap, s->stack_lds4, s->stack_spill4, s->curves};
   if (int rc = apply(*s, *edit, out)) return rc;
   if (!out.changed) return VPT_OK;   // an empty request: the schedule and the counters of the last edit stay
+  s->edit_generation++;                  // K3's tables (vpt_scene_handle.h: volgrid_tables) are made anew by the next volgrid launch
+  if (writes_voxels(*edit)) s->voxel_generation++;
   if (out.topology) {   // new trees or lists: the stack sizes and the kernel instances follow
     if (out.stack_spill4 != s->stack_spill4) s->spill_lanes = 0;   // the HBM part is sized per entry: made anew by the next launch
     s->stack_cap = out.stack_cap, s->stack_lds4 = out.stack_lds4, s->stack_spill4 = out.stack_spill4;

@@ -5,6 +5,7 @@
 //   vpt_k1_curves.hip                     K1 for scenes with points or lines, + vpt_intersect on them   vpt_k1_instances.hip.h)
 //   vpt_k1_simple.hip                     K1 for naive, eyelight and the debug shaders
 //   vpt_k2.hip                            K2 (vpt_implicit_kernel.hip.h)
+//   vpt_k3.hip                            K3 (vpt_volgrid_kernel.hip.h)
 //   vpt_aov.hip                           the first-hit pass (vpt_aov_kernel.hip.h)
 //   vpt_kernels.hip                       vpt_intersect, the KAT kernel, the self-tests, light setup, launch schedule, output resolve
 // (the copies between row-major pixels and tile-major slots are one kernel of vpt_layout.hip, launched there: not declared here)
@@ -66,6 +67,23 @@ __global__ void __launch_bounds__(VPT_BLOCK, VPT_K2_WAVES) vpt_render_kernel(DSc
 template <int SH, int FEAT>
 __global__ void __launch_bounds__(VPT_BLOCK, VPT_K2_WAVES) vpt_render_pilot_kernel(DScene sc, DParams pr, float4* __restrict__ image,
     int* __restrict__ hits, ulonglong2* __restrict__ rngs, int stack_cap, sched_cfg sched, unsigned* __restrict__ watchdog, unsigned long long watchdog_ticks);
+
+// ---- K3: the volgrid shader (vpt_volgrid_kernel.hip.h; instances: vpt_k3.hip) ---------------------------------------------------
+// K3's tables travel in an argument of their own: DScene stays byte for byte what the other kernels are compiled for
+struct vpt_volgrid_record;   // vpt_volgrid_rule.h
+struct volgrid_args {
+  const vpt_volgrid_record* recs;     // one per grid instance, in instance order
+  const float*              bricks;   // the brick pool: per volume its nbx * nby * nbz majorants (x fastest), then their maximum
+  int                       num_instances;
+  int                       num_env_lights;   // light-list entries with an environment
+  int                       no_bricks;        // VPT_VOLGRID_NO_BRICKS=1: one majorant per volume (the A/B switch of the tests and the measurements)
+  unsigned*                 watchdog;         // the handle's counter: free flights that ran into VPT_VOLGRID_MAX_STEPS
+  unsigned long long*       steps;            // tracking steps taken since the handle was made (vpt_scene_volgrid_stats)
+};
+#define VPT_K3_WAVES 4   // K3's waves per SIMD: 115 VGPRs and no scratch; at 5 (K2's) the allocator's 96 VGPRs leave 11 spilled, 48 bytes of scratch per lane
+template <bool PILOT>
+__global__ void __launch_bounds__(VPT_BLOCK, VPT_K3_WAVES) vpt_volgrid_kernel(DScene sc, DParams pr, volgrid_args va, float4* __restrict__ image,
+    int* __restrict__ hits, ulonglong2* __restrict__ rngs, sched_cfg sched);
 
 // ---- vpt_intersect, KAT, self-tests (vpt_kernels.hip, but for vpt_intersect_curves_kernel: vpt_k1_curves.hip) ----------------
 template <bool SPILL, bool COMPACT>

@@ -392,7 +392,7 @@ int vpt_multi_render(vpt_multi* m, const vpt_params* params, int nsamples, int w
   const bool on_device = !image_rgba && !hits && !rng;   // render on the resident state, move nothing
   if (!on_device && (!image_rgba || !hits || !rng)) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   if (width <= 0 || height <= 0) return vpt_set_error(VPT_ERR_INVALID_ARG, "bad image size");
-  if (params->shader < 0 || params->shader > VPT_SHADER_IMPLICIT_NORMAL) return vpt_set_error(VPT_ERR_UNKNOWN_SHADER, "sampler unknown");
+  if (!vpt_shader_known(params->shader)) return vpt_set_error(VPT_ERR_UNKNOWN_SHADER, "sampler unknown");
   if (on_device && (!m->resident || m->width != width || m->height != height || m->samples != *samples_io))
     return vpt_set_error(VPT_ERR_INVALID_ARG, "no %dx%d state with %d samples on the devices (vpt_multi_set_state first)", width, height, *samples_io);
   int todo = params->samples - *samples_io;   // no-op once reached, yocto_pathtrace.cpp:1055

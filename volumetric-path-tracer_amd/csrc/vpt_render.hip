@@ -68,8 +68,16 @@ static void launch_implicit_instance(const launch_ctx& L, bool is_pilot, dim3 gr
   else if (lean) launch(vpt_render_kernel<K, VPT_FEAT_SDF_LIGHTS>);
   else launch(vpt_render_kernel<K, VPT_FEAT_ALL>);
 }
+// K3: one instance and its pilot; LDS holds the records of the grid instances (volgrid_prepare has checked that they fit)
+static void launch_volgrid_instance(const launch_ctx& L, bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
+  const volgrid_args va  = volgrid_arguments(L.s);
+  const size_t       lds = (size_t)va.num_instances * 128;
+  if (is_pilot) hipLaunchKernelGGL(vpt_volgrid_kernel<true>, grid, dim3(VPT_BLOCK), lds, L.st, L.s->d, pr, va, L.img, L.hit, L.rng, sch);
+  else hipLaunchKernelGGL(vpt_volgrid_kernel<false>, grid, dim3(VPT_BLOCK), lds, L.st, L.s->d, pr, va, L.img, L.hit, L.rng, sch);
+}
 instance_launcher launcher_of(int shader) {
   switch (shader) {
+    case VPT_SHADER_VOLGRID: return launch_volgrid_instance;
     case VPT_SHADER_VOLPATHTRACE: return launch_mesh_instance<K_VOLPATH>;
     case VPT_SHADER_PATHTRACE: return launch_mesh_instance<K_PATH>;
     case VPT_SHADER_NAIVE: return launch_mesh_instance<K_NAIVE>;
@@ -113,9 +121,10 @@ int vpt_render_device(vpt_scene* s, const vpt_params* params, const vpt_layout* 
   // VPT_SPLIT=0): K2's launches hold two waves per wave slot at 1280 x 533, so the longest-first schedule ends well above both of
   // its bounds (226 ms against a longest wave of 192 and 191 of work per slot); the costliest tiles as partly filled waves - whose
   // scene rounds run in the group form: four lanes per ray - pack better.
+  // K3 (volgrid, id 16) is scheduled like K2: its waves have K2's character - chains of dependent steps whose length varies by orders of
+  // magnitude between tiles (its own occupancy: vpt_launch.h, VPT_K3_WAVES; the split policy reads K2.s tables for it)
   const bool k2 = params->shader >= VPT_SHADER_IMPLICIT;
-  if (k2)
-    if (int rc = implicit_lds(s)) return rc;   // the scene's SDF records must fit the kernel's LDS
+  if (int rc = shader_setup(s, params, st)) return rc;   // K2: the scene's SDF records must fit the kernel's LDS; K3: its refusals and tables
   const bool may_split = k2 ? split_mode() != 0
                             : !t.stack.spill && (split_mode() == 1 || split_forced_k() >= 0 ||
                                                  (split_mode() < 0 && (pr.nranks > 1 || (long long)t.grid.x < 3ll * s->sched.wave_slots(false))));

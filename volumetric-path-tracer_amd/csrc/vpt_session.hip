@@ -85,6 +85,9 @@ struct vpt_session {
 namespace {
 
 bool implicit_shader(int shader) { return shader == VPT_SHADER_IMPLICIT || shader == VPT_SHADER_IMPLICIT_NORMAL; }
+// the volgrid shader has no first hit on a surface: no guides to filter with, nothing to pick, no id frame
+bool volgrid_shader(int shader) { return shader == VPT_SHADER_VOLGRID; }
+const char* const k_volgrid_refusal = "the session renders the volgrid shader: a medium has no surface to filter by, to pick or to name";
 
 // what tells the two id frames apart
 struct id_frame_kind {
@@ -115,7 +118,7 @@ void frame_size(int resolution, float aspect, int& width, int& height) {
 
 int check_session_params(const vpt_session_params* p) {
   REQUIRE(p, "null session params");
-  if (p->render.shader < 0 || p->render.shader > VPT_SHADER_IMPLICIT_NORMAL) return vpt_set_error(VPT_ERR_UNKNOWN_SHADER, "sampler unknown");
+  if (!vpt_shader_known(p->render.shader)) return vpt_set_error(VPT_ERR_UNKNOWN_SHADER, "sampler unknown");
   REQUIRE(p->render.resolution >= 1 && p->render.resolution < 32768, "resolution %d outside 1..32767", p->render.resolution);
   REQUIRE(p->render.samples >= 1, "samples %d must be >= 1", p->render.samples);
   REQUIRE(p->render.bounces >= 0, "negative bounce count");
@@ -130,6 +133,7 @@ int check_session_params(const vpt_session_params* p) {
     REQUIRE(std::isfinite(f.sigma_normal) && f.sigma_normal > 0, "sigma_normal must be finite and > 0");
     REQUIRE(std::isfinite(f.sigma_albedo) && f.sigma_albedo > 0, "sigma_albedo must be finite and > 0");
     REQUIRE(p->guide_samples >= 1, "guide_samples %d must be >= 1", p->guide_samples);
+    if (volgrid_shader(p->render.shader)) return vpt_set_error(VPT_ERR_UNSUPPORTED, "denoise: %s", k_volgrid_refusal);
   }
   return VPT_OK;
 }
@@ -192,7 +196,7 @@ int filter_and_tonemap(vpt_session* s, const void* variance) {
 
 // after the implicit kernels ran: wait for them and read their watchdog's word (the mesh shaders have none: the call stays asynchronous)
 int check_implicit_watchdog(vpt_session* s) {
-  if (!implicit_shader(s->p.render.shader)) return VPT_OK;
+  if (!implicit_shader(s->p.render.shader) && !volgrid_shader(s->p.render.shader)) return VPT_OK;   // (K3 reports through the same word)
   HIP_TRY(hipStreamSynchronize(s->st));
   if (int rc = vpt_check_watchdog(s->scene)) return rc;
   s->down += 4;
@@ -227,6 +231,7 @@ int render_mesh_guides(vpt_session* s) {
 // sample of the kind's pass, its resolve; the state and the tile-major planes hold one entry per SLOT, the row-major ones per pixel.
 int ensure_id_frame(vpt_session* s, const id_frame_kind& k) {
   REQUIRE(s->width > 0, "the session holds no frame (a reset failed)");
+  if (volgrid_shader(s->p.render.shader)) return vpt_set_error(VPT_ERR_UNSUPPORTED, "%s", k_volgrid_refusal);
   if (implicit_shader(s->p.render.shader) != k.implicit) return vpt_set_error(VPT_ERR_UNSUPPORTED, "%s", k.refusal);
   id_frame& f = s->id_frames[k.implicit];
   if (f.valid) return VPT_OK;
@@ -477,6 +482,7 @@ int vpt_session_get_image(vpt_session* s, float* linear) {
 
 int vpt_session_get_denoised(vpt_session* s, float* linear) {
   REQUIRE(s && linear, "null argument");
+  if (volgrid_shader(s->p.render.shader)) return vpt_set_error(VPT_ERR_UNSUPPORTED, "denoise: %s", k_volgrid_refusal);
   REQUIRE(s->filtered_valid, "no filtered image: the session needs denoise = 1 and an advance since its last reset");
   begin_call(s);
   return fetch(s, {{linear, &s->filtered, pixels(s) * 16}});
@@ -502,6 +508,7 @@ int vpt_session_get_guides(vpt_session* s, float* normal, float* albedo) {
   REQUIRE(s, "null session");
   REQUIRE(normal || albedo, "null normal and albedo: nothing to fetch");
   REQUIRE(s->width > 0, "the session holds no frame (a reset failed)");
+  if (volgrid_shader(s->p.render.shader)) return vpt_set_error(VPT_ERR_UNSUPPORTED, "guides: %s", k_volgrid_refusal);
   REQUIRE(s->p.denoise, "no guides: the session needs denoise = 1");
   REQUIRE(!albedo || s->has_albedo, "no albedo guide: the implicit shaders have none");
   begin_call(s);

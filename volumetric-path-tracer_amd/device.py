@@ -9,7 +9,7 @@ from typing import TYPE_CHECKING, Optional
 import numpy as np
 
 from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SDF_AOV_PLANES, SHADER_NAMES, VptAdaptive, VptAovPlanes, VptSdfAovPlanes, VptDisplay, VptError, VptLayout, VptParams,
-                   VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, _counted, _edit_call, _mesh_desc, _mesh_region, _meshed, _p, hip, host)
+                   VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, shader_id, _counted, _edit_call, _mesh_desc, _mesh_region, _meshed, _p, hip, host)
 from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, mesh
 
 if TYPE_CHECKING:
@@ -29,9 +29,7 @@ class PathtraceParams:
     spheretrace_maxiter: int = 450
 
     def to_abi(self) -> VptParams:
-        if self.shader not in SHADER_NAMES:
-            raise VptError("sampler unknown")  # reference: get_shader throws (cpp:947-950)
-        return VptParams(self.camera, self.resolution, SHADER_NAMES.index(self.shader), self.samples,
+        return VptParams(self.camera, self.resolution, shader_id(self.shader), self.samples,   # an unknown name: VptError("sampler unknown")
                          self.bounces, int(self.noparallel), int(self.noimplicit_mis),
                          self.spheretrace_maxiter)
 
@@ -270,6 +268,31 @@ class DeviceScene(_Handle):
         out = np.zeros((d, h, w), np.float32)
         _check(hip.vpt_scene_get_voxels(self.handle, index, out.ctypes.data, out.size), "vpt_scene_get_voxels")
         return out
+
+    def volgrid_majorants(self, index: int) -> np.ndarray:
+        """the brick majorants of volume `index` as the device holds them for the volgrid shader (vpt_scene_get_volgrid_majorants), built
+        or rebuilt first when the scene was edited since: float32 of shape (nbz, nby, nbx) - the bits of HostScene.volgrid_majorants"""
+        dims = (C.c_int32 * 3)()
+        _check(hip.vpt_scene_get_volgrid_majorants(self.handle, index, None, 0, C.cast(dims, _p)), "vpt_scene_get_volgrid_majorants")
+        out = np.zeros((dims[2], dims[1], dims[0]), np.float32)
+        _check(hip.vpt_scene_get_volgrid_majorants(self.handle, index, out.ctypes.data, out.size, None), "vpt_scene_get_volgrid_majorants")
+        return out
+
+    def volgrid_density(self, points):
+        """the volgrid shader's extinction at world points ((n, 3) float32), evaluated on the device (vpt_scene_volgrid_density): (sigma,
+        instance) = (n,) float32 sums over the grid instances in index order, (n,) int32 first instance whose box holds the point or -1 -
+        the bits of HostScene.volgrid_density"""
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        sigma, instance = np.zeros(len(points), np.float32), np.full(len(points), -1, np.int32)
+        _check(hip.vpt_scene_volgrid_density(self.handle, len(points), points.ctypes.data, instance.ctypes.data, sigma.ctypes.data),
+               "vpt_scene_volgrid_density")
+        return sigma, instance
+
+    def volgrid_stats(self) -> dict:
+        """vpt_scene_volgrid_stats: tracking steps of this handle's volgrid launches so far, builds of its brick tables so far"""
+        steps, builds = C.c_uint64(0), C.c_int32(0)
+        _check(hip.vpt_scene_volgrid_stats(self.handle, C.byref(steps), C.byref(builds)), "vpt_scene_volgrid_stats")
+        return {"steps": steps.value, "table_builds": builds.value}
 
     def mesh_volume(self, index: int, iso: float = 0.0, origin=None, step=None, region=None, stats: Optional[dict] = None) -> dict:
         """vpt_scene_mesh_volume (include/vpt.h): the iso surface of volume `index` as a quad mesh, made on the device from the voxels where

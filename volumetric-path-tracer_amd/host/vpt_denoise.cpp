@@ -134,6 +134,7 @@ vector<float> half_variance(int width, int height, const vector<vec4f>& sum_a, i
 denoise_guides pathtrace_guides(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights, const pathtrace_params& params,
     int samples) {
   if (samples < 1) throw std::invalid_argument{"guide samples must be >= 1"};
+  if ((int)params.shader == 16) throw std::invalid_argument{"the volgrid shader has no guides: a medium has no surface normal and no albedo"};
   auto implicit = params.shader == pathtrace_shader_type::implicit || params.shader == pathtrace_shader_type::implicit_normal;
   auto render   = [&](pathtrace_shader_type shader) {
     auto p    = params;

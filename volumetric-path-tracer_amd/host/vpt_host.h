@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "vpt.h"
@@ -143,6 +144,15 @@ struct pathtrace_state {
 enum struct pathtrace_shader_type { volpathtrace, pathtrace, naive, eyelight, normal, texcoord, color, implicit, implicit_normal };
 inline const auto pathtrace_shader_names = vector<string>{"volpathtrace", "pathtrace", "naive",
     "eyelight", "normal", "texcoord", "color", "implicit", "implicit_normal"};
+// Extension: the shaders the reference does not have, beside its list - name and id (include/vpt.h: ids 9 .. 15 name nothing).
+// A pathtrace_params carries one as (pathtrace_shader_type)id.
+inline const auto pathtrace_extension_shaders = vector<std::pair<string, int>>{{"volgrid", 16}};
+inline bool pathtrace_shader_known(pathtrace_shader_type shader) {
+  if ((int)shader >= 0 && (int)shader <= (int)pathtrace_shader_type::implicit_normal) return true;
+  for (auto& [name, id] : pathtrace_extension_shaders)
+    if (id == (int)shader) return true;
+  return false;
+}
 struct pathtrace_params {
   int                   camera              = 0;
   int                   resolution          = 720;

@@ -812,7 +812,7 @@ void pathtrace_set_devices(const vector<int>& devices) {
 void pathtrace_samples(pathtrace_state& state, const scene_data& scene, const bvh_scene& bvh,
     const pathtrace_lights& lights, const pathtrace_params& params, int count) {
   if (state.samples >= params.samples) return;  // reference cpp:1055
-  if ((int)params.shader < 0 || (int)params.shader > (int)pathtrace_shader_type::implicit_normal)
+  if (!pathtrace_shader_known(params.shader))
     throw std::runtime_error{"sampler unknown"};  // reference cpp:947-950
   auto handle = (vpt_multi*)nullptr;
   {
@@ -861,7 +861,7 @@ color_image get_render(const pathtrace_state& state) {
 
 pathtrace_adaptive_stats pathtrace_adaptive(pathtrace_state& state, const scene_data& scene, const bvh_scene& bvh,
     const pathtrace_lights& lights, const pathtrace_params& params, const pathtrace_adaptive_params& adaptive) {
-  if ((int)params.shader < 0 || (int)params.shader > (int)pathtrace_shader_type::implicit_normal)
+  if (!pathtrace_shader_known(params.shader))
     throw std::runtime_error{"sampler unknown"};  // reference cpp:947-950
   auto handle = (vpt_scene*)nullptr;
   {

@@ -102,7 +102,8 @@ string usage() {
     text += line + o.usage + "\n";
     if (o.kind == option::shader_k) {
       text += "    with choices: ";
-      for (auto& s : pathtrace_shader_names) text += s + (&s == &pathtrace_shader_names.back() ? "\n" : ", ");
+      for (auto& s : pathtrace_shader_names) text += s + ", ";
+      for (auto& s : pathtrace_extension_shaders) text += s.first + (&s == &pathtrace_extension_shaders.back() ? "\n" : ", ");   // after the reference's names
     }
   }
   text += "  --help                        Prints help. (false)\n  --config <string>             Load configuration. (\"\")\n";
@@ -142,6 +143,7 @@ void check_value(const string& name, const option& o, const string& text) {
   } else if (o.kind == option::shader_k) {
     auto found = false;
     for (auto& s : pathtrace_shader_names) found = found || s == text;
+    for (auto& s : pathtrace_extension_shaders) found = found || s.first == text;
     if (!found) cli_error("bad value for " + name);
   }
 }
@@ -232,6 +234,9 @@ int main(int argc, const char** argv) {
   if (values.count("shader"))
     for (size_t k = 0; k < pathtrace_shader_names.size(); k++)
       if (pathtrace_shader_names[k] == values["shader"]) params.shader = (pathtrace_shader_type)k;
+  if (values.count("shader"))
+    for (auto& s : pathtrace_extension_shaders)
+      if (s.first == values["shader"]) params.shader = (pathtrace_shader_type)s.second;
 
   for (auto name : {"bake-res", "bake-padding", "bake-host"})
     if (values.count(name) && !values.count("bake-sdf")) cli_error(string{"option "} + name + " needs --bake-sdf");

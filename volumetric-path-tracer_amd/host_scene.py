@@ -186,6 +186,15 @@ def mesh_sdf(voxels: np.ndarray, origin, step, iso: float = 0.0, device: Optiona
     return mesh(m["positions"], quads=m["quads"], normals=m["normals"])
 
 
+def density_from_sdf(voxels: np.ndarray, width: float) -> np.ndarray:
+    """a signed-distance grid as a soft-edged cloud for the volgrid shader: clip(-sdf / width, 0, 1) in float32 - 1 from `width` inside
+    the surface on, 0 outside it.  A baked or sculpted volume becomes a medium with set_volume(index, density_from_sdf(voxels, width))."""
+    width = np.float32(width)
+    if not (np.isfinite(width) and width > 0):
+        raise VptError(f"density_from_sdf: width {width!r} must be finite and > 0")
+    return np.clip(-np.asarray(voxels, np.float32) / width, np.float32(0), np.float32(1)).astype(np.float32)
+
+
 def save_mesh_ply(path: str, positions, quads, normals=None) -> None:
     """positions, normals (unless None) and quads as a binary little-endian PLY file, which the scene loader reads back with the same bits"""
     positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
@@ -804,6 +813,22 @@ class HostScene(_Handle):
         _host_call(host.vpth_scene_update_volumes, self.handle)
         edit, self._sculpt_edit = self._sculpt_edit, SculptEdit()
         return edit
+
+    def volgrid_majorants(self, index: int) -> np.ndarray:
+        """the host mirror of DeviceScene.volgrid_majorants on the scene's copy of volume `index` (pending bakes run first): the volgrid
+        shader's brick majorants, float32 of shape (nbz, nby, nbx)"""
+        dims = (C.c_int32 * 3)()
+        _host_call(host.vpth_volgrid_majorants, self.desc, index, None, 0, C.cast(dims, C.c_void_p))
+        out = np.zeros((dims[2], dims[1], dims[0]), np.float32)
+        _host_call(host.vpth_volgrid_majorants, self.desc, index, out.ctypes.data, out.size, None)
+        return out
+
+    def volgrid_density(self, points):
+        """the host mirror of DeviceScene.volgrid_density: (sigma, instance) at world points ((n, 3) float32) of the scene as it stands"""
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        sigma, instance = np.zeros(len(points), np.float32), np.full(len(points), -1, np.int32)
+        _host_call(host.vpth_volgrid_density, self.desc, len(points), points.ctypes.data, instance.ctypes.data, sigma.ctypes.data)
+        return sigma, instance
 
     def mesh_volume(self, index: int, iso: float = 0.0, origin=None, step=None, region=None, stats: Optional[dict] = None) -> dict:
         """the host mirror of DeviceScene.mesh_volume on the scene's copy of volume `index` (pending bakes run first, as for volume()):

@@ -73,6 +73,8 @@ def pathtrace_guides(scene: HostScene, dev, params: PathtraceParams, samples: in
     """the two guide renders of denoise_render on `dev` (a DeviceScene or MultiDeviceScene of `scene`): (normal, albedo) as resolved
     (h, w, 4) float32 images - `samples` passes of the `normal` and the `color` shader over a fresh make_state; for the implicit
     shaders: `implicit_normal`, and albedo None"""
+    if params.shader == "volgrid":   # a medium has no first hit on a surface: nothing to guide a filter by
+        raise VptError("pathtrace_guides: the volgrid shader has no guides (no surface normal, no albedo)")
     implicit = params.shader in ("implicit", "implicit_normal")
     if not implicit and isinstance(dev, DeviceScene):  # both from one first-hit pass: the same rays traced once, the same bits
         p = PathtraceParams(params.camera, params.resolution, "normal", samples, params.bounces, params.noparallel, params.noimplicit_mis,

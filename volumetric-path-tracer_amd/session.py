@@ -251,6 +251,8 @@ class RenderSession(_Handle):
         """denoise = True: the guides the filter reads, (normal, albedo) as resolved (h, w, 4) float32 images; albedo None for the
         implicit shaders"""
         w, h = self.size
+        if self.params.shader == "volgrid":
+            raise VptError("guides: a volgrid session has none (vpt_session_get_guides: unsupported)")
         has_albedo = self.params.shader not in ("implicit", "implicit_normal")
         normal, albedo = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32) if has_albedo else None
         _check(hip.vpt_session_get_guides(self.handle, normal.ctypes.data, albedo.ctypes.data if has_albedo else None), "vpt_session_get_guides")
