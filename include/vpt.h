@@ -428,8 +428,8 @@ int vpt_scene_update_textures(vpt_scene* scene, const vpt_texture_edit* edit);
 
 /* ---- edits of volumes, grid instances and SDFs; baking into the resident voxel pool -----------------------------------
  * The `implicit` side of a resident scene: the voxel grids, the instances that place them and the analytic SDFs.  A struct of its own,
- * as for textures: vpt_scene_edit keeps its layout.  Counts stay fixed: no volume, instance or SDF is added or removed, so the LDS
- * budget of the implicit kernels' record copy, checked at creation, stays valid.
+ * as for textures: vpt_scene_edit keeps its layout.  Counts stay fixed: no volume, instance or SDF is added or removed by this call
+ * (that is vpt_scene_update_volume_set's, below), so the LDS budget of the implicit kernels' record copy stays as it was.
  * After vpt_scene_update_volumes(s, edit) every table on the device that a render, vpt_intersect or vpt_kat call reads holds what
  * vpt_scene_create would hold for the edited descriptor carrying the host's make_lights of the edited scene: every render is
  * bit-identical to a fresh handle's and vpt_scene_light_tables_hash equals a fresh handle's on all six tables.  The layout of the voxel
@@ -488,6 +488,9 @@ int vpt_scene_update_volumes(vpt_scene* scene, const vpt_volume_edit* edit);
  * entries, at least the scene's counts; a null array is skipped.  A volume's offset is the resident pool's. */
 int vpt_scene_get_volumes(vpt_scene* scene, vpt_volume* volumes, int volume_capacity, vpt_volume_instance* vol_instances, int instance_capacity,
                           vpt_sdf* sdfs, int sdf_capacity);
+/* how many volumes, grid instances and SDFs the handle holds now: counts[0..2].  vpt_scene_update_volume_set changes them, so a caller
+ * sizes the arrays of vpt_scene_get_volumes by this and not by the descriptor the handle was made from.  No device call. */
+int vpt_scene_count_implicit(vpt_scene* scene, int32_t counts[3]);
 /* the voxels of one volume as the device holds them (x + y*W + z*W*H); capacity in voxels, at least the volume's W*H*D */
 int vpt_scene_get_voxels(vpt_scene* scene, int volume, float* voxels, int64_t capacity);
 
@@ -534,6 +537,70 @@ typedef struct vpt_sculpt_edit {
   int32_t num_stamps;  const vpt_sculpt_stamp* stamps;
 } vpt_sculpt_edit;
 int vpt_scene_sculpt_volumes(vpt_scene* scene, const vpt_sculpt_edit* edit);
+
+/* ---- adding and removing volumes, grid instances and SDFs -------------------------------------------------------------
+ * The one thing vpt_scene_update_volumes leaves fixed: how many there are.  An edit of its own, because vpt_volume_edit keeps its layout;
+ * the contract is that of vpt_scene_update_instances and vpt_scene_update_shapes.  After vpt_scene_update_volume_set(s, edit) every table
+ * on the device holds the bytes vpt_scene_create would hold for the descriptor built as follows (renders are bit-identical to a fresh
+ * handle's, vpt_scene_light_tables_hash equals a fresh handle's on all six tables).
+ *  - Lists.  The three old lists with the removed entries erased and the added ones appended in the order given: survivors keep their
+ *    order and the ids close up (erase + push_back).  Removals are applied first, on current ids, then the adds.  There is no `set` list:
+ *    vpt_scene_update_volumes edits entries, before or after this call, on the ids that hold then.
+ *  - Renumbering.  A surviving grid instance's `volume` follows the new volume numbering.  An added instance names a volume of the NEW
+ *    list, so it may name a volume added by the same edit.
+ *  - Voxels.  A survivor keeps its voxels bit for bit.  A FROM_HOST volume holds voxels[offset .. offset + W*H*D) (whole grid, x fastest).
+ *    A FROM_BAKE volume holds the bits of vpt_bake_sdf for its descriptor, written by the bake kernel straight into its new place (also
+ *    under VPT_BAKE_BRUTE=1).  A FILL volume holds the bits of `fill` in every voxel (any float, a NaN's payload included).  A COPY volume
+ *    holds what volume copy_of (a CURRENT id) held before the call; the source may be removed by the same edit.
+ *  - Pool layout.  After an edit that adds or removes at least one volume the pool is exactly the volumes in id order with no gap between
+ *    them: vpt_scene_get_volumes reports offsets equal to the running sum of W*H*D, and the room earlier regrowths of
+ *    vpt_scene_update_volumes left unused is reclaimed.  The new pool is a fresh allocation filled by ONE launch, whatever the number of
+ *    volumes (then one bake launch per FROM_BAKE entry).  An edit that touches no volume leaves the pool alone.
+ *  - Records.  The evaluation records, inverse frames, bounding balls, the scene's ball and the plane count are prep_sdf_records' for all
+ *    records, as after vpt_scene_update_volumes; the device tables are allocated at their new lengths.  No grid instance and no SDF at all
+ *    is a valid scene (every `implicit` sample is a miss), and a scene created with none may gain its first.
+ *  - Lights.  make_lights of the new scene under the rule of vpt_scene_update_lights: vpt_light::sdf follows the new SDF numbering, mesh
+ *    and environment lights keep their CDFs, indices and guide tables (moved device to device).  With no change among the SDF lights
+ *    (none added, none removed, none renumbered) nothing of the lights is touched.
+ *  - The LDS budget of the implicit kernels' record copy is decided per launch: a scene that grew past it is refused at render time
+ *    (VPT_ERR_UNSUPPORTED), exactly as a fresh handle of the same descriptor is.
+ *  - volgrid.  The brick tables are indexed by volume: the next volgrid launch or query rebuilds them.
+ *  - Validation before anything is written (VPT_ERR_INVALID_ARG, the message names the entry, the scene is untouched): null lists with
+ *    non-zero counts, negative counts; ids out of range or repeated within a list; a removed volume that a surviving or added grid
+ *    instance still names; `volume` or `material` out of range in the new numbering; floats that are not finite and `type` outside 0..5
+ *    (the checks of vpt_scene_update_volumes); whd >= 0 with a product below 2^31, factor by factor; the pool's new total below 2^43
+ *    voxels, the reach of the one gather launch (and below 2^62 before that, so that no sum overflows);
+ *    offset + grid size inside `voxels`; an unknown source; copy_of out of range or a COPY whose whd differs from its source's; a bake
+ *    descriptor vpt_bake_sdf would refuse or whose whd is not the entry's.  A bake tree deeper than the kernel's stack gives
+ *    VPT_ERR_UNSUPPORTED, also before anything is written.
+ *  - Everything is built into buffers of the call; pointers, counts and mirrors are swapped after the last check.  A device failure after
+ *    validation (VPT_ERR_HIP) leaves the handle good for vpt_scene_destroy only.  An edit with all counts zero does nothing.
+ *  - vpt_scene_update_stats afterwards: launches = 1 gather (when a volume is added or removed and the new pool is not empty) + 1 per
+ *    non-empty bake + those of a light rebuild; bytes = 4 per voxel of the edit's payload (sent whole and once when a FROM_HOST entry names it: pack the grids tightly, as
+ *    VolumeSetEdit does) + 32 per segment of the gather's table + the three small
+ *    tables and the record tables at their new lengths (24 per volume, 60 + 112 per grid instance, 84 + 144 per SDF) + per bake its tree
+ *    and triangle records + what a light rebuild sends.  Nothing is proportional to the voxels of a surviving, baked, filled or copied
+ *    volume.
+ *  - Synchronisation, the VPT_ERR_HIP semantics and the forgetting of the launch-schedule record: those of vpt_scene_update. */
+enum { VPT_VOLUME_FROM_HOST = 0, VPT_VOLUME_FROM_BAKE = 1, VPT_VOLUME_FILL = 2, VPT_VOLUME_COPY = 3 };
+typedef struct vpt_volume_new {
+  int32_t whd[3]; float res;
+  int32_t source;                     /* one of the four above */
+  int64_t offset;                     /* FROM_HOST: first voxel inside edit->voxels (whole grid, x fastest) */
+  const struct vpt_bake_desc* bake;   /* FROM_BAKE: bake->whd == whd, the rules of vpt_bake_sdf */
+  float   fill;                       /* FILL: every voxel gets these bits */
+  int32_t copy_of;                    /* COPY: a CURRENT volume id; whd must equal that volume's */
+} vpt_volume_new;
+typedef struct vpt_volume_set_edit {
+  int32_t num_remove_vol_instances; const int32_t* remove_vol_instance_ids;       /* current ids */
+  int32_t num_remove_sdfs;          const int32_t* remove_sdf_ids;                /* current ids */
+  int32_t num_remove_volumes;       const int32_t* remove_volume_ids;             /* current ids */
+  int32_t num_add_volumes;          const vpt_volume_new* add_volumes;            /* appended after the survivors */
+  int32_t num_add_vol_instances;    const vpt_volume_instance* add_vol_instances; /* `volume` in the NEW numbering */
+  int32_t num_add_sdfs;             const vpt_sdf* add_sdfs;
+  int64_t num_voxels;               const float* voxels;                          /* the payload of the FROM_HOST entries */
+} vpt_volume_set_edit;
+int vpt_scene_update_volume_set(vpt_scene* scene, const vpt_volume_set_edit* edit);
 
 /* ---- the volgrid shader: voxel grids as heterogeneous media (VPT_SHADER_VOLGRID) ------------------------------------
  * The reference has no such shader: the rule is this project's and is written here.  The parts that more than one side computes - clean,
@@ -912,6 +979,8 @@ int  vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit);
 int  vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit);
 /* vpt_scene_sculpt_volumes in the same way: the same stamps run on every device */
 int  vpt_multi_sculpt_volumes(vpt_multi* m, const vpt_sculpt_edit* edit);
+/* vpt_scene_update_volume_set in the same way (a FROM_BAKE entry is prepared and baked once per device) */
+int  vpt_multi_update_volume_set(vpt_multi* m, const vpt_volume_set_edit* edit);
 /* vpt_scene_rebuild_bvh in the same way: every device builds its own trees; the arrays are equal by construction */
 int  vpt_multi_rebuild_bvh(vpt_multi* m, const vpt_bvh_rebuild* what);
 int  vpt_multi_rebuild_bvh_quality(vpt_multi* m, const vpt_bvh_rebuild* what, int quality);   /* vpt_scene_rebuild_bvh_quality on every device */
@@ -1301,6 +1370,9 @@ int  vpt_session_edit_textures(vpt_session* session, const vpt_texture_edit* edi
 int  vpt_session_edit_volumes(vpt_session* session, const vpt_volume_edit* edit);
 /* vpt_scene_sculpt_volumes, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_sculpt_volumes(vpt_session* session, const vpt_sculpt_edit* edit);
+/* vpt_scene_update_volume_set, then a reset (which drops both id frames: pick_sdf never names an entry that is gone); a refused edit
+ * leaves the session as it was */
+int  vpt_session_edit_volume_set(vpt_session* session, const vpt_volume_set_edit* edit);
 /* vpt_scene_rebuild_bvh, then a reset (the picture is the same, its accumulation restarts as after the session's other edits); a refused call leaves the session as it was */
 int  vpt_session_rebuild_bvh(vpt_session* session, const vpt_bvh_rebuild* what);
 int  vpt_session_rebuild_bvh_quality(vpt_session* session, const vpt_bvh_rebuild* what, int quality);   /* vpt_scene_rebuild_bvh_quality, then a reset */

@@ -14,7 +14,7 @@ device-resident state), ``session`` (RenderSession), ``images`` (denoise, tone m
 from ._abi import *   # noqa: F401,F403 - every structure, record dtype and constant, hip, host, VptError
 from ._abi import _check, _p   # noqa: F401 - the measuring tools under profiles/tools call the C-ABI directly
 from .edits import (BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan, TextureEdit,   # noqa: F401
-                    VolumeEdit, VolumeSource, mesh)
+                    VolumeEdit, VolumeNew, VolumeSetEdit, VolumeSource, mesh)
 from .device import (AdaptiveRun, DeviceScene, DisplayParams, MultiDeviceScene, PathtraceParams, PathtraceState, box3_device,   # noqa: F401
                      device_count, layout_pixel_index, layout_slots, make_state_jump, resolve_device, resolve_hits_device, resolve_ids_device,
                      resolve_sdf_ids_device, resolve_srgb8_device, selftest_reciprocal, state_download, state_init_device, state_upload)

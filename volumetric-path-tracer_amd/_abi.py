@@ -178,9 +178,25 @@ class VptSculptEdit(C.Structure):  # vpt_sculpt_edit
 
 assert C.sizeof(VptSculptStamp) == 92 and C.sizeof(VptSculptEntry) == 60 and C.sizeof(VptSculptEdit) == 32
 
+
+class VptVolumeNew(C.Structure):  # vpt_volume_new
+    _fields_ = [("whd", C.c_int32 * 3), ("res", C.c_float), ("source", C.c_int32), ("offset", C.c_int64), ("bake", C.c_void_p), ("fill", C.c_float),
+                ("copy_of", C.c_int32)]
+
+
+class VptVolumeSetEdit(C.Structure):  # vpt_volume_set_edit
+    _fields_ = [("num_remove_vol_instances", C.c_int32), ("remove_vol_instance_ids", C.c_void_p), ("num_remove_sdfs", C.c_int32), ("remove_sdf_ids", C.c_void_p),
+                ("num_remove_volumes", C.c_int32), ("remove_volume_ids", C.c_void_p), ("num_add_volumes", C.c_int32), ("add_volumes", C.c_void_p),
+                ("num_add_vol_instances", C.c_int32), ("add_vol_instances", C.c_void_p), ("num_add_sdfs", C.c_int32), ("add_sdfs", C.c_void_p),
+                ("num_voxels", C.c_int64), ("voxels", C.c_void_p)]
+
+
+assert C.sizeof(VptVolumeNew) == 48 and C.sizeof(VptVolumeSetEdit) == 112
+
 SDF_TYPES = ["bbox", "box", "capped_cone", "plane", "sphere", "torus"]
 VOXELS_REPLACE, VOXELS_UNION = 0, 1
 SCULPT_REPLACE, SCULPT_UNION, SCULPT_SUBTRACT, SCULPT_INTERSECT = 0, 1, 2, 3
+VOLUME_FROM_HOST, VOLUME_FROM_BAKE, VOLUME_FILL, VOLUME_COPY = 0, 1, 2, 3   # vpt_volume_new::source
 SCULPT_RECORD_BYTES = 80   # VPT_SCULPT_RECORD_BYTES: one stamp as the device reads it
 MATERIAL_TYPES = ["matte", "glossy", "reflective", "transparent", "refractive", "subsurface", "volumetric", "gltfpbr"]
 
@@ -291,7 +307,11 @@ hip.vpt_session_edit_volumes.argtypes = [_p, C.POINTER(VptVolumeEdit)]
 hip.vpt_scene_sculpt_volumes.argtypes = [_p, C.POINTER(VptSculptEdit)]
 hip.vpt_multi_sculpt_volumes.argtypes = [_p, C.POINTER(VptSculptEdit)]
 hip.vpt_session_sculpt_volumes.argtypes = [_p, C.POINTER(VptSculptEdit)]
+hip.vpt_scene_update_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
+hip.vpt_multi_update_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
+hip.vpt_session_edit_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
 hip.vpt_scene_get_volumes.argtypes =[_p, _p, C.c_int, _p, C.c_int, _p, C.c_int]
+hip.vpt_scene_count_implicit.argtypes = [_p, _p]
 hip.vpt_scene_get_voxels.argtypes = [_p, C.c_int, _p, C.c_int64]
 hip.vpt_scene_get_lights.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int), _p, C.c_int64, C.POINTER(C.c_int64)]
 hip.vpt_scene_light_tables_hash.argtypes = [_p, _p]
@@ -456,6 +476,7 @@ host.vpth_scene_get_sdf.argtypes = [_p, C.c_int, C.POINTER(VptSdf)]
 host.vpth_scene_set_sdf.argtypes = [_p, C.c_int, C.POINTER(VptSdf), C.c_char_p, C.c_int]
 host.vpth_scene_set_volume.argtypes = [_p, C.c_int, _p, C.c_float, _p, _p, C.c_int, _p, C.c_char_p, C.c_int]
 host.vpth_scene_update_volumes.argtypes = [_p, C.c_char_p, C.c_int]
+host.vpth_scene_edit_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit), C.c_char_p, C.c_int]
 host.vpth_scene_sculpt_volume.argtypes = [_p, C.POINTER(VptSculptEntry), _p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_sculpt_eval.argtypes = [C.POINTER(VptSdf), _p, C.c_int, _p]
 host.vpth_sculpt_combine.argtypes = [C.c_int, C.c_float, _p, _p, C.c_int, _p]

@@ -20,6 +20,7 @@
 #include "vpt_shape_update.h"
 #include "vpt_texture_update.h"
 #include "vpt_sculpt.h"
+#include "vpt_volume_set.h"
 #include "vpt_volume_update.h"
 
 static std::string& g_error_text() {   // the message of the last failure on the calling thread (vpt_last_error)
@@ -170,6 +171,7 @@ template <typename Edit> static bool moves_geometry(const Edit&) { return false;
 template <typename Edit> static bool writes_materials(const Edit&) { return false; }
 static bool writes_voxels(const vpt_volume_edit&) { return true; }   // voxels in place, baked into the pool, or moved into a grown pool
 static bool writes_voxels(const vpt_sculpt_edit&) { return true; }
+static bool writes_voxels(const vpt_volume_set_edit&) { return true; }   // a pool laid out anew, volumes under other ids: the brick tables are indexed by volume
 template <typename Edit> static bool writes_voxels(const Edit&) { return false; }
 
 // One edit, from the idle device it needs to what the render side owes it afterwards.  apply(resident&, edit, edit_outcome&): the
@@ -215,6 +217,8 @@ int vpt_scene_update_textures(vpt_scene* s, const vpt_texture_edit* edit) { retu
 int vpt_scene_update_volumes(vpt_scene* s, const vpt_volume_edit* edit) { return edit_scene(s, edit, volume_update_apply); }
 // voxels alone, from analytic brushes evaluated where they live (vpt_sculpt.hip)
 int vpt_scene_sculpt_volumes(vpt_scene* s, const vpt_sculpt_edit* edit) { return edit_scene(s, edit, sculpt_apply); }
+// volumes, grid instances and SDFs added and removed (vpt_volume_set.hip): the pool compacted by one gather, the lights following the SDFs
+int vpt_scene_update_volume_set(vpt_scene* s, const vpt_volume_set_edit* edit) { return edit_scene(s, edit, volume_set_apply); }
 // the BVHs built anew (vpt_bvh_rebuild.hip), the set of instances changed (vpt_instance_update.hip), the shape list changed (vpt_shape_update.hip)
 int vpt_scene_rebuild_bvh(vpt_scene* s, const vpt_bvh_rebuild* what) { return vpt_scene_rebuild_bvh_quality(s, what, VPT_BVH_MIDDLE); }
 int vpt_scene_rebuild_bvh_quality(vpt_scene* s, const vpt_bvh_rebuild* what, int quality) {

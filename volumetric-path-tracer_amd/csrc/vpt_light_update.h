@@ -35,5 +35,8 @@ struct env_light {
 // the mirrors up to date, all but the light mirrors - per instance of the new list its id in the old one, -1 for one that is new or
 // whose shape is another now: a surviving light keeps its CDF, index and guide table under its new id, and the tables are rebuilt
 // whenever a light's instance word moved, even where the list is the same by position.
+// old_sdf: null, or - after vpt_scene_update_volume_set (vpt_volume_set.h) has changed the number of SDFs and brought r.d and the
+// mirrors up to date, all but the light mirrors - per SDF of the new list its id in the old one, -1 for an added one: a surviving SDF
+// light is the old light under its new id, and the tables are rebuilt whenever a light's sdf word moved.
 int light_update_apply(resident& r, const vpt_scene_edit& edit, bool* rebuilt, const std::vector<env_light>* envs = nullptr,
-    const std::vector<char>* sdf_resized = nullptr, const std::vector<int>* old_instance = nullptr);
+    const std::vector<char>* sdf_resized = nullptr, const std::vector<int>* old_instance = nullptr, const std::vector<int>* old_sdf = nullptr);

@@ -203,7 +203,7 @@ struct entry {   // one light of the new list
 }  // namespace
 
 int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, const std::vector<env_light>* envs, const std::vector<char>* sdf_resized,
-    const std::vector<int>* old_instance) {
+    const std::vector<int>* old_instance, const std::vector<int>* old_sdf) {
   *rebuilt = false;
   DScene&             d = r.d;
   const host_mirrors& h = r.h;
@@ -214,7 +214,10 @@ int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, cons
   int old_instances = d.num_instances;   // (the instances were renumbered: the old list and the map name old ids)
   for (size_t l = 0; old_instance && l < old.size(); l++) old_instances = old[l].instance >= old_instances ? old[l].instance + 1 : old_instances;
   for (size_t i = 0; old_instance && i < old_instance->size(); i++) old_instances = (*old_instance)[i] >= old_instances ? (*old_instance)[i] + 1 : old_instances;
-  std::vector<int>  old_of_instance((size_t)old_instances, -1), old_of_sdf((size_t)d.num_sdfs, -1), old_of_env((size_t)d.num_environments, -1);
+  int old_sdfs = d.num_sdfs;   // (the same of the SDFs)
+  for (size_t l = 0; old_sdf && l < old.size(); l++) old_sdfs = old[l].sdf >= old_sdfs ? old[l].sdf + 1 : old_sdfs;
+  for (size_t i = 0; old_sdf && i < old_sdf->size(); i++) old_sdfs = (*old_sdf)[i] >= old_sdfs ? (*old_sdf)[i] + 1 : old_sdfs;
+  std::vector<int>  old_of_instance((size_t)old_instances, -1), old_of_sdf((size_t)old_sdfs, -1), old_of_env((size_t)d.num_environments, -1);
   std::vector<char> moved((size_t)d.num_shapes, 0);
   for (size_t l = 0; l < old.size(); l++) {
     if (old[l].instance >= 0) old_of_instance[(size_t)old[l].instance] = (int)l;
@@ -244,12 +247,16 @@ int light_update_apply(resident& r, const vpt_scene_edit& e, bool* rebuilt, cons
   } else
     for (size_t l = 0; l < old.size(); l++)   // the edit has no field for an environment's emission or texture
       if (old[l].instance < 0 && old[l].sdf < 0) list.push_back({old[l], (int)l, false, u.light_kind[l]});
-  for (int i = 0; i < d.num_sdfs; i++)
-    if (emissive(u.materials[(size_t)u.sdfs[(size_t)i].material])) list.push_back({{VPT_INVALID, VPT_INVALID, i, 1, 0}, old_of_sdf[(size_t)i], false, VPT_LIGHT_SDF});
+  for (int i = 0; i < d.num_sdfs; i++) {
+    if (!emissive(u.materials[(size_t)u.sdfs[(size_t)i].material])) continue;
+    const int was = old_sdf ? (*old_sdf)[(size_t)i] : i;   // -1: an added SDF
+    list.push_back({{VPT_INVALID, VPT_INVALID, i, 1, 0}, was >= 0 ? old_of_sdf[(size_t)was] : -1, false, VPT_LIGHT_SDF});
+  }
   bool same = list.size() == old.size();
   for (size_t l = 0; same && l < list.size(); l++) same = list[l].from == (int)l && !list[l].recompute && list[l].l.cdf_len == old[l].cdf_len;
   // the same lights by position may be other instance ids after a renumbering: vpt_light::instance, the records and light_prims name them
   for (size_t l = 0; same && old_instance && l < list.size(); l++) same = list[l].l.instance == old[l].instance;
+  for (size_t l = 0; same && old_sdf && l < list.size(); l++) same = list[l].l.sdf == old[l].sdf;   // the same of vpt_light::sdf
   for (size_t l = 0; same && sdf_resized && l < list.size(); l++) same = list[l].l.sdf < 0 || !(*sdf_resized)[(size_t)list[l].l.sdf];   // its one CDF entry is whd.x * whd.y
   env_of.resize(list.size(), -1);
   if (same) return VPT_OK;   // no consequence for the lights: the update has done all there is to do

@@ -330,6 +330,7 @@ int vpt_multi_update_lights(vpt_multi* m, const vpt_scene_edit* edit) { return e
 int vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit) { return edit_parts(m, edit, vpt_scene_update_textures); }
 int vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit) { return edit_parts(m, edit, vpt_scene_update_volumes); }
 int vpt_multi_sculpt_volumes(vpt_multi* m, const vpt_sculpt_edit* edit) { return edit_parts(m, edit, vpt_scene_sculpt_volumes); }
+int vpt_multi_update_volume_set(vpt_multi* m, const vpt_volume_set_edit* edit) { return edit_parts(m, edit, vpt_scene_update_volume_set); }
 int vpt_multi_rebuild_bvh(vpt_multi* m, const vpt_bvh_rebuild* what) { return vpt_multi_rebuild_bvh_quality(m, what, VPT_BVH_MIDDLE); }
 int vpt_multi_rebuild_bvh_quality(vpt_multi* m, const vpt_bvh_rebuild* what, int quality) {
   return edit_parts(m, what, [quality](vpt_scene* s, const vpt_bvh_rebuild* w) { return vpt_scene_rebuild_bvh_quality(s, w, quality); });

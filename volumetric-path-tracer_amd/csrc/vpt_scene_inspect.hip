@@ -67,6 +67,12 @@ int vpt_scene_get_volumes(vpt_scene* s, vpt_volume* volumes, int volume_capacity
   if (int rc = read_back(vol_instances, d.vol_instances, (size_t)d.num_vol_instances)) return rc;
   return read_back(sdfs, d.sdfs, (size_t)d.num_sdfs);
 }
+int vpt_scene_count_implicit(vpt_scene* s, int32_t counts[3]) {
+  if (!s || !counts) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
+  const DScene& d = resident_of(s).d;
+  counts[0] = d.num_volumes, counts[1] = d.num_vol_instances, counts[2] = d.num_sdfs;
+  return VPT_OK;
+}
 int vpt_scene_get_voxels(vpt_scene* s, int volume, float* voxels, int64_t capacity) {
   if (!s || !voxels) return vpt_set_error(VPT_ERR_INVALID_ARG, "null argument");
   const DScene& d = resident_of(s).d;

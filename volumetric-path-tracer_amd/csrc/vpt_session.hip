@@ -457,6 +457,7 @@ int vpt_session_edit_lights(vpt_session* s, const vpt_scene_edit* edit) { return
 int vpt_session_edit_textures(vpt_session* s, const vpt_texture_edit* edit) { return session_edit(s, edit, vpt_scene_update_textures); }
 int vpt_session_edit_volumes(vpt_session* s, const vpt_volume_edit* edit) { return session_edit(s, edit, vpt_scene_update_volumes); }
 int vpt_session_sculpt_volumes(vpt_session* s, const vpt_sculpt_edit* edit) { return session_edit(s, edit, vpt_scene_sculpt_volumes); }
+int vpt_session_edit_volume_set(vpt_session* s, const vpt_volume_set_edit* edit) { return session_edit(s, edit, vpt_scene_update_volume_set); }
 int vpt_session_rebuild_bvh(vpt_session* s, const vpt_bvh_rebuild* what) { return vpt_session_rebuild_bvh_quality(s, what, VPT_BVH_MIDDLE); }
 int vpt_session_rebuild_bvh_quality(vpt_session* s, const vpt_bvh_rebuild* what, int quality) {
   return session_edit(s, what, [quality](vpt_scene* scene, const vpt_bvh_rebuild* w) { return vpt_scene_rebuild_bvh_quality(scene, w, quality); });

@@ -10,7 +10,7 @@ import numpy as np
 
 from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SDF_AOV_PLANES, SHADER_NAMES, VptAdaptive, VptAovPlanes, VptSdfAovPlanes, VptDisplay, VptError, VptLayout, VptParams,
                    VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, shader_id, _counted, _edit_call, _mesh_desc, _mesh_region, _meshed, _p, hip, host)
-from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, mesh
+from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, VolumeSetEdit, mesh
 
 if TYPE_CHECKING:
     from .host_scene import HostScene
@@ -246,6 +246,12 @@ class DeviceScene(_Handle):
         update_volumes()."""
         _edit_call(self.handle, "vpt_scene_update_volumes", edit)
 
+    def update_volume_set(self, edit: VolumeSetEdit) -> None:
+        """vpt_scene_update_volume_set (include/vpt.h): volumes, grid instances and SDFs removed and added - the voxel pool laid out anew
+        by one gather on the device, baked additions written into it by the bake kernel, the lights following the SDFs - with the
+        VolumeSetEdit of HostScene.update_volume_set()."""
+        _edit_call(self.handle, "vpt_scene_update_volume_set", edit)
+
     def sculpt_volumes(self, edit: SculptEdit) -> None:
         """vpt_scene_sculpt_volumes (include/vpt.h): strokes of analytic brushes evaluated on the device over boxes of the resident voxels -
         a few hundred bytes cross PCIe, not one voxel.  edit: what HostScene.update_sculpts() returns."""
@@ -254,7 +260,9 @@ class DeviceScene(_Handle):
     def get_volumes(self):
         """(volumes, vol_instances, sdfs) as the device holds them, ctypes arrays of VptVolume, VptVolumeInstance, VptSdf
         (vpt_scene_get_volumes); a volume's offset is the resident pool's"""
-        nv, ni, ns = (self.host_scene.count_implicit(k) for k in ("volumes", "vol_instances", "sdfs"))
+        counts = (C.c_int32 * 3)()   # the handle's own: update_volume_set changes them
+        _check(hip.vpt_scene_count_implicit(self.handle, C.cast(counts, _p)), "vpt_scene_count_implicit")
+        nv, ni, ns = counts
         vols, insts, sdfs = (VptVolume * max(1, nv))(), (VptVolumeInstance * max(1, ni))(), (VptSdf * max(1, ns))()
         _check(hip.vpt_scene_get_volumes(self.handle, C.cast(vols, _p), nv, C.cast(insts, _p), ni, C.cast(sdfs, _p), ns), "vpt_scene_get_volumes")
         return list(vols)[:nv], list(insts)[:ni], list(sdfs)[:ns]
@@ -554,6 +562,10 @@ class MultiDeviceScene(_Handle):
     def update_volumes(self, edit: VolumeEdit) -> None:
         """vpt_multi_update_volumes: DeviceScene.update_volumes with the same edit on every device"""
         _edit_call(self.handle, "vpt_multi_update_volumes", edit)
+
+    def update_volume_set(self, edit: VolumeSetEdit) -> None:
+        """vpt_multi_update_volume_set: DeviceScene.update_volume_set with the same edit on every device"""
+        _edit_call(self.handle, "vpt_multi_update_volume_set", edit)
 
     def sculpt_volumes(self, edit: SculptEdit) -> None:
         """vpt_multi_sculpt_volumes: DeviceScene.sculpt_volumes with the same edit on every device"""

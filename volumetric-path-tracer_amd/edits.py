@@ -11,7 +11,8 @@ import numpy as np
 
 from ._abi import (INSTANCE, MESH_ELEMENTS, MESH_FLOATS, SCULPT_RECORD_BYTES, VOXELS_REPLACE, VptBakeDesc, VptBvhRebuild, VptCamera, VptEnvironment,
                    VptError, VptInstanceEdit, VptMaterial, VptSceneEdit, VptSculptEdit, VptSculptEntry, VptSculptStamp, VptSdf, VptShapeData, VptShapeEdit,
-                   VptSubdivEdit, VptSubdivLevel, VptSubdivPlan, VptTexture, VptTextureEdit, VptVolumeEdit, VptVolumeInstance, VptVolumeSource, _address)
+                   VptSubdivEdit, VptSubdivLevel, VptSubdivPlan, VptTexture, VptTextureEdit, VptVolumeEdit, VptVolumeInstance, VptVolumeNew, VptVolumeSetEdit,
+                   VptVolumeSource, VOLUME_FILL, VOLUME_FROM_BAKE, VOLUME_FROM_HOST, _address)
 
 
 def mesh(positions, triangles=None, quads=None, points=None, lines=None, normals=None, texcoords=None, colors=None, radius=None) -> dict:
@@ -346,6 +347,79 @@ class VolumeEdit:
         abi.num_volumes, abi.volume_ids, abi.volumes = _table(keep, self.volumes, entries)
         abi.num_voxels, abi.voxels = len(voxels), voxels.ctypes.data
         return abi, keep + [voxels]
+
+
+# ---- the set of volumes, grid instances and SDFs: remove / add over the three lists -----------------------------------------------------
+@dataclass
+class VolumeNew:
+    """One added volume of a VolumeSetEdit (include/vpt.h: vpt_volume_new): whd (w, h, d), res, and where the voxels come from - source
+    VOLUME_FROM_HOST: voxels, float32 of shape (d, h, w); VOLUME_FROM_BAKE: bake = (positions (n, 3), triangles (m, 3), origin, step), the
+    grid of bake_sdf_grid over whd; VOLUME_FILL: the bits of `fill` in every voxel; VOLUME_COPY: the voxels volume copy_of (a current id,
+    of the same whd) holds before the edit."""
+    whd: tuple
+    res: float
+    source: int = VOLUME_FROM_HOST
+    voxels: Optional[np.ndarray] = None
+    bake: Optional[tuple] = None
+    fill: float = 0.0
+    copy_of: int = -1
+
+
+class VolumeSetEdit:
+    """What vpt_scene_update_volume_set takes (include/vpt.h: vpt_volume_set_edit): current ids of grid instances, SDFs and volumes to
+    erase (the ids close up, a surviving instance's volume id follows), then volumes (VolumeNew), grid instances (VptVolumeInstance, their
+    `volume` in the NEW numbering) and SDFs (VptSdf) appended after the survivors.  HostScene's add_volume / remove_volumes /
+    add_volume_instance / remove_volume_instances / add_sdf / remove_sdfs fill one, update_volume_set() hands it out;
+    DeviceScene.update_volume_set / MultiDeviceScene.update_volume_set / RenderSession.edit_volume_set apply it."""
+
+    def __init__(self, remove_vol_instances=(), remove_sdfs=(), remove_volumes=(), add_volumes=(), add_vol_instances=(), add_sdfs=()):
+        self.remove_vol_instances = tuple(int(i) for i in remove_vol_instances)
+        self.remove_sdfs = tuple(int(i) for i in remove_sdfs)
+        self.remove_volumes = tuple(int(i) for i in remove_volumes)
+        self.add_volumes, self.add_vol_instances, self.add_sdfs = list(add_volumes), list(add_vol_instances), list(add_sdfs)
+
+    def empty(self) -> bool:
+        return not (self.remove_vol_instances or self.remove_sdfs or self.remove_volumes or self.add_volumes or self.add_vol_instances or self.add_sdfs)
+
+    def to_abi(self):
+        """(VptVolumeSetEdit, objects that keep its arrays alive)"""
+        keep, abi = [], VptVolumeSetEdit()
+        entries = (VptVolumeNew * max(1, len(self.add_volumes)))()
+        pool, count = [], 0
+        for e, new in zip(entries, self.add_volumes):
+            whd = tuple(int(v) for v in new.whd)
+            e.whd[:], e.res, e.source, e.fill, e.copy_of = whd, float(new.res), int(new.source), float(new.fill), int(new.copy_of)
+            if new.source == VOLUME_FILL:   # the bits as they are: a NaN keeps its payload
+                C.memmove(C.addressof(e) + VptVolumeNew.fill.offset, np.array([new.fill], np.float32).ctypes.data, 4)
+            if new.source == VOLUME_FROM_BAKE:
+                positions, triangles, origin, step = new.bake
+                positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+                triangles = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+                desc = VptBakeDesc(len(positions), positions.ctypes.data, len(triangles), triangles.ctypes.data)
+                desc.whd[:] = whd
+                desc.origin[:] = [float(v) for v in np.broadcast_to(np.asarray(origin, np.float32), (3,))]
+                desc.step[:] = [float(v) for v in np.broadcast_to(np.asarray(step, np.float32), (3,))]
+                keep += [positions, triangles, desc]
+                e.bake = C.addressof(desc)
+            elif new.source == VOLUME_FROM_HOST:
+                voxels = np.ascontiguousarray(new.voxels, np.float32)
+                if voxels.shape != whd[::-1]:
+                    raise VptError(f"voxels of an added volume have the shape (d, h, w) = {whd[::-1]}, got {voxels.shape}")
+                e.offset = count
+                pool.append(voxels.reshape(-1))
+                count += voxels.size
+        voxels = np.ascontiguousarray(np.concatenate(pool)) if pool else np.zeros(0, np.float32)
+        for name, ids in (("remove_vol_instance", self.remove_vol_instances), ("remove_sdf", self.remove_sdfs), ("remove_volume", self.remove_volumes)):
+            arr = np.array(ids, np.int32)
+            keep.append(arr)
+            setattr(abi, f"num_{name}s", len(arr))
+            setattr(abi, f"{name}_ids", arr.ctypes.data if len(arr) else None)
+        instances, sdfs = (VptVolumeInstance * max(1, len(self.add_vol_instances)))(*self.add_vol_instances), (VptSdf * max(1, len(self.add_sdfs)))(*self.add_sdfs)
+        abi.num_add_volumes, abi.add_volumes = len(self.add_volumes), C.addressof(entries) if self.add_volumes else None
+        abi.num_add_vol_instances, abi.add_vol_instances = len(self.add_vol_instances), C.addressof(instances) if self.add_vol_instances else None
+        abi.num_add_sdfs, abi.add_sdfs = len(self.add_sdfs), C.addressof(sdfs) if self.add_sdfs else None
+        abi.num_voxels, abi.voxels = len(voxels), voxels.ctypes.data if len(voxels) else None
+        return abi, keep + [entries, instances, sdfs, voxels]
 
 
 # ---- sculpting: strokes of analytic brushes over boxes of voxels --------------------------------------------------------------------------

@@ -635,6 +635,109 @@ int vpth_scene_sculpt_volume(void* hh, const vpt_sculpt_entry* entry, const vpt_
 }
 // make_lights of the scene as the setters above left it (an SDF is a light iff its material is emissive), then the flattened descriptor again
 int vpth_scene_update_volumes(void* hh, char* err, int errlen) { return vpth_scene_update_lights(hh, err, errlen); }
+// The host side of vpt_scene_update_volume_set (include/vpt.h) under its rules: the removed entries of the three lists erased (current
+// ids; survivors keep their order, ids close up, a surviving grid instance's volume id follows), then the added ones appended - an added
+// instance names a volume of the new list - then make_lights and the flattened descriptor again (its address changes).  A FROM_BAKE
+// volume gets zeros here: the caller writes the host mirror of the bake through vpth_scene_set_volume when the copy is read.  A refused
+// call changes nothing.
+int vpth_scene_edit_volume_set(void* hh, const vpt_volume_set_edit* e, char* err, int errlen) {
+  try {
+    auto& h  = *(host_scene*)hh;
+    auto& sc = h.scene;
+    if (!e) return set_error(err, errlen, "volume_set: null edit"), -1;
+    auto keep_of = [&](const char* what, int n, const int32_t* ids, size_t limit, vector<char>& keep) {
+      keep.assign(limit, 1);
+      if (n < 0 || (n > 0 && !ids)) throw std::invalid_argument{string{"volume_set: "} + what + " list is null or has a negative count"};
+      for (auto i = 0; i < n; i++) {
+        if (ids[i] < 0 || (size_t)ids[i] >= limit) throw std::invalid_argument{string{"volume_set: "} + what + " id " + std::to_string(ids[i]) + " out of range"};
+        if (!keep[(size_t)ids[i]]) throw std::invalid_argument{string{"volume_set: "} + what + " id " + std::to_string(ids[i]) + " repeated"};
+        keep[(size_t)ids[i]] = 0;
+      }
+    };
+    auto keep_inst = vector<char>{}, keep_sdf = vector<char>{}, keep_vol = vector<char>{};
+    keep_of("remove_vol_instance", e->num_remove_vol_instances, e->remove_vol_instance_ids, sc.vol_instances.size(), keep_inst);
+    keep_of("remove_sdf", e->num_remove_sdfs, e->remove_sdf_ids, sc.sdfs.size(), keep_sdf);
+    keep_of("remove_volume", e->num_remove_volumes, e->remove_volume_ids, sc.volumes.size(), keep_vol);
+    if (e->num_add_volumes < 0 || e->num_add_vol_instances < 0 || e->num_add_sdfs < 0 || e->num_voxels < 0 || (e->num_add_volumes > 0 && !e->add_volumes) ||
+        (e->num_add_vol_instances > 0 && !e->add_vol_instances) || (e->num_add_sdfs > 0 && !e->add_sdfs) || (e->num_voxels > 0 && !e->voxels))
+      return set_error(err, errlen, "volume_set: a list of additions is null or has a negative count"), -1;
+    auto new_volume = vector<int>(sc.volumes.size(), -1);
+    auto volumes    = vector<volume_data>{};
+    for (size_t i = 0; i < sc.volumes.size(); i++)
+      if (keep_vol[i]) new_volume[i] = (int)volumes.size(), volumes.push_back(sc.volumes[i]);
+    for (auto i = 0; i < e->num_add_volumes; i++) {
+      auto& n    = e->add_volumes[i];
+      auto  name = "volume_set: add_volume entry " + std::to_string(i);
+      if (!std::isfinite(n.res)) return set_error(err, errlen, name + ": res is not finite"), -1;
+      if (n.whd[0] < 0 || n.whd[1] < 0 || n.whd[2] < 0) return set_error(err, errlen, name + ": negative whd"), -1;
+      auto count = (int64_t)1;
+      for (auto k = 0; k < 3; k++) {
+        count *= n.whd[k];
+        if (count >= (1ll << 31)) return set_error(err, errlen, name + ": 2^31 voxels or more"), -1;
+      }
+      if (n.whd[0] == 0 || n.whd[1] == 0 || n.whd[2] == 0) count = 0;
+      auto& v = volumes.emplace_back();
+      v.whd = {n.whd[0], n.whd[1], n.whd[2]}, v.res = n.res;
+      if (n.source == VPT_VOLUME_FROM_HOST) {
+        if (n.offset < 0 || n.offset > e->num_voxels - count) return set_error(err, errlen, name + ": voxels out of range of the edit's payload"), -1;
+        v.vol.assign(e->voxels + n.offset, e->voxels + n.offset + count);
+      } else if (n.source == VPT_VOLUME_FROM_BAKE) {
+        v.vol.assign((size_t)count, 0.0f);
+      } else if (n.source == VPT_VOLUME_FILL) {
+        v.vol.assign((size_t)count, 0.0f);
+        for (auto& x : v.vol) memcpy(&x, &n.fill, 4);   // the bits, a NaN's payload included
+      } else if (n.source == VPT_VOLUME_COPY) {
+        if (n.copy_of < 0 || (size_t)n.copy_of >= sc.volumes.size()) return set_error(err, errlen, name + ": copy_of out of range"), -1;
+        auto& from = sc.volumes[(size_t)n.copy_of];
+        if (from.whd.x != n.whd[0] || from.whd.y != n.whd[1] || from.whd.z != n.whd[2]) return set_error(err, errlen, name + ": whd differs from its source's"), -1;
+        v.vol = from.vol;
+      } else
+        return set_error(err, errlen, name + ": source is not one of 0..3"), -1;
+    }
+    auto finite = [](const float* p, int n) {
+      for (auto k = 0; k < n; k++)
+        if (!std::isfinite(p[k])) return false;
+      return true;
+    };
+    auto instances = vector<volume_instance>{};
+    for (size_t i = 0; i < sc.vol_instances.size(); i++) {
+      if (!keep_inst[i]) continue;
+      auto inst = sc.vol_instances[i];
+      if (new_volume[(size_t)inst.volume] < 0)
+        return set_error(err, errlen, "volume_set: remove_volume: volume " + std::to_string(inst.volume) + " is still named by vol_instance " + std::to_string(i)), -1;
+      inst.volume = new_volume[(size_t)inst.volume];
+      instances.push_back(inst);
+    }
+    for (auto i = 0; i < e->num_add_vol_instances; i++) {
+      auto& in   = e->add_vol_instances[i];
+      auto  name = "volume_set: add_vol_instance entry " + std::to_string(i);
+      if (!finite((const float*)&in.frame, 12) || !std::isfinite(in.scalef)) return set_error(err, errlen, name + ": a value is not finite"), -1;
+      if (in.volume < 0 || (size_t)in.volume >= volumes.size()) return set_error(err, errlen, name + ": volume out of range"), -1;
+      if (in.material < 0 || (size_t)in.material >= sc.materials.size()) return set_error(err, errlen, name + ": material out of range"), -1;
+      auto& o = instances.emplace_back();
+      memcpy((void*)&o.frame, &in.frame, sizeof(vpt_frame));
+      o.volume = in.volume, o.material = in.material, o.scalef = in.scalef;
+    }
+    auto sdfs = vector<sdf_data>{};
+    for (size_t i = 0; i < sc.sdfs.size(); i++)
+      if (keep_sdf[i]) sdfs.push_back(sc.sdfs[i]);
+    for (auto i = 0; i < e->num_add_sdfs; i++) {
+      auto& in   = e->add_sdfs[i];
+      auto  name = "volume_set: add_sdf entry " + std::to_string(i);
+      if (!finite((const float*)&in.frame, 12) || !finite(in.whd, 3) || !finite(in.p, 4)) return set_error(err, errlen, name + ": a value is not finite"), -1;
+      if (in.type < 0 || in.type > VPT_SDF_TORUS) return set_error(err, errlen, name + ": type is not one of 0..5"), -1;
+      if (in.material < 0 || (size_t)in.material >= sc.materials.size()) return set_error(err, errlen, name + ": material out of range"), -1;
+      auto& s = sdfs.emplace_back();
+      memcpy((void*)&s.frame, &in.frame, sizeof(vpt_frame));
+      s.type = (sdf_type)in.type, s.material = in.material;
+      memcpy((void*)&s.whd, in.whd, 12), memcpy(s.p, in.p, 16);
+    }
+    sc.volumes = std::move(volumes), sc.vol_instances = std::move(instances), sc.sdfs = std::move(sdfs);
+    return vpth_scene_update_lights(hh, err, errlen);
+  } catch (const std::exception& ex) {
+    return set_error(err, errlen, ex.what()), -1;
+  }
+}
 void vpth_scene_free(void* h) { delete (host_scene*)h; }
 const vpt_scene_desc* vpth_scene_desc(void* h) { return &((host_scene*)h)->flat->desc; }
 const vpt_scene_curves* vpth_scene_curves(void* h) { return ((host_scene*)h)->flat->curves_or_null(); }   // null: no points or lines

@@ -9,12 +9,12 @@ from typing import Optional
 
 import numpy as np
 
-from ._abi import (BVH_MIDDLE, BVH_NODE, BVH_SAH, LIGHT, MESH_ELEMENTS, MESH_FLOATS, SDF_TYPES, VOXELS_REPLACE, VptBakeStats, VptCamera,
+from ._abi import (BVH_MIDDLE, BVH_NODE, BVH_SAH, LIGHT, MESH_ELEMENTS, MESH_FLOATS, SDF_TYPES, VOLUME_COPY, VOLUME_FILL, VOLUME_FROM_BAKE, VOLUME_FROM_HOST, VOXELS_REPLACE, VptBakeStats, VptCamera,
                    VptEnvironment, VptError, VptMaterial, VptSceneDescBvh, VptSceneDescLights, VptSculptEntry, VptSdf, VptVolumeInstance, _Handle,
                    _check, _filled, _host_call, _mesh_desc, _mesh_region, _meshed, hip, host)
 from .device import PathtraceParams, PathtraceState
 from .edits import (LEVEL_TABLES, BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan,
-                    TextureEdit, VolumeEdit, VolumeSource, mesh)
+                    TextureEdit, VolumeEdit, VolumeNew, VolumeSetEdit, VolumeSource, mesh)
 
 
 def build_bvh(bboxes: np.ndarray, device: Optional[int] = 0, *, quality: int = 0):
@@ -213,16 +213,21 @@ def save_mesh_ply(path: str, positions, quads, normals=None) -> None:
 #   "edit": a SceneEdit that holds anything; "geometry": one that holds instance frames or shape vertices (cameras, materials and
 #   environment frames name lists nothing renumbers); "instances" / "shapes": an InstanceEdit / ShapeEdit that holds anything;
 #   "subdivs": a SubdivEdit that holds anything (its shapes wait for update_bvh like moved vertices).
-# Texture and volume edits name lists of their own and wait for nothing; set_camera, set_material, set_environment_frame are never refused.
+# Texture and volume edits name lists of their own and wait for nothing of the above; set_camera, set_material, set_environment_frame are
+# never refused.  The implicit side has the same rule within itself: "volumes": a VolumeEdit or SculptEdit that holds anything - their ids
+# name the volumes, grid instances and SDFs as they are - and "volume_set": a VolumeSetEdit that holds anything, which renumbers all three.
 # A volume's voxels have two ledgers, the VolumeEdit and the SculptEdit: a volume pending in one is refused by the setters of the other
 # (_note_volume, sculpt_volume), since each ledger is applied to the device as a whole and in its own call.
 _REFUSED_WHILE = {"vertices": ("instances", "shapes"),                       # set_instance_frame, set_shape_positions, set_subdiv (cage, displacement)
                   "rebuild": ("edit", "subdivs", "instances", "shapes"),      # rebuild_bvh
                   "instances": ("geometry", "subdivs", "shapes"),             # add_instance, remove_instances, set_instance, update_instances
-                  "shapes": ("geometry", "subdivs", "instances")}             # add_shape, set_shape, remove_shapes, update_shapes, set_subdiv (level, smooth)
+                  "shapes": ("geometry", "subdivs", "instances"),             # add_shape, set_shape, remove_shapes, update_shapes, set_subdiv (level, smooth)
+                  "volume_entries": ("volume_set",),                          # set_volume_instance, set_sdf, set_volume, bake_volume, sculpt_volume
+                  "volume_set": ("volumes",)}                                 # add_volume, remove_volumes, add_volume_instance, ..., update_volume_set
 _HAND_OUT = {"edit": "edit out with update_bvh()", "geometry": "edit out with update_bvh()",
              "instances": "instance changes out with update_instances()", "shapes": "shape changes out with update_shapes()",
-             "subdivs": "subdiv changes out with update_subdivs()"}
+             "subdivs": "subdiv changes out with update_subdivs()", "volumes": "volume changes out with update_volumes() / update_sculpts()",
+             "volume_set": "additions and removals of volumes, grid instances and SDFs out with update_volume_set()"}
 
 
 class HostScene(_Handle):
@@ -238,7 +243,7 @@ class HostScene(_Handle):
         # the pending edits: what the setters noted since the matching update_*() handed the last one out
         self._edit, self._inst_edit, self._shape_edit = SceneEdit(), InstanceEdit(), ShapeEdit()
         self._texture_edit, self._volume_edit, self._subdiv_edit = TextureEdit(), VolumeEdit(), SubdivEdit()
-        self._sculpt_edit = SculptEdit()
+        self._sculpt_edit, self._volume_set_edit = SculptEdit(), VolumeSetEdit()
         self._lazy_bakes = []   # (volume, VolumeSource) of bake_volume whose host copy is not baked yet
         self.handle = _host_call(host.vpth_scene_load_ex, os.fsencode(filename), -1 if tess_device is None else tess_device, size=1024, handle=True)
         self.filename = filename
@@ -289,7 +294,8 @@ class HostScene(_Handle):
     def _may(self, what: str, kind: str, why: str = "") -> None:
         """VptError unless a call of `kind` (_REFUSED_WHILE) may go ahead: the message names the update_*() to call first"""
         pending = {"edit": not self._edit.empty(), "geometry": bool(self._edit.instances or self._edit.shapes),
-                   "instances": not self._inst_edit.empty(), "shapes": not self._shape_edit.empty(), "subdivs": not self._subdiv_edit.empty()}
+                   "instances": not self._inst_edit.empty(), "shapes": not self._shape_edit.empty(), "subdivs": not self._subdiv_edit.empty(),
+                   "volumes": not (self._volume_edit.empty() and self._sculpt_edit.empty()), "volume_set": not self._volume_set_edit.empty()}
         for blocker in _REFUSED_WHILE[kind]:
             if pending[blocker]:
                 raise VptError(f"{what}: hand the pending {_HAND_OUT[blocker]} first" + (why if blocker == "geometry" else ""))
@@ -672,6 +678,7 @@ class HostScene(_Handle):
 
     def set_volume_instance(self, index: int, frame=None, volume=None, material=None, scalef=None) -> None:
         """frame ((12,) float32: x, y, z, o), volume, material and / or scalef of a grid instance; None: as it was"""
+        self._may("set_volume_instance", "volume_entries")
         vi = self.volume_instance(index)
         if frame is not None:
             C.memmove(C.byref(vi.frame), np.ascontiguousarray(frame, np.float32).reshape(12).ctypes.data, 48)
@@ -692,7 +699,14 @@ class HostScene(_Handle):
 
     def set_sdf(self, index: int, sdf: Optional[VptSdf] = None, frame=None, type=None, material=None, whd=None, p=None) -> None:
         """an analytic SDF: a whole VptSdf, or the named fields of the one the scene holds (type: an index into SDF_TYPES or its name)"""
-        f = self.sdf(index) if sdf is None else sdf
+        self._may("set_sdf", "volume_entries")
+        f = self._sdf_of(self.sdf(index) if sdf is None else sdf, frame, type, material, whd, p)
+        _host_call(host.vpth_scene_set_sdf, self.handle, index, C.byref(f))
+        self._volume_edit.sdfs[index] = self.sdf(index)
+
+    @staticmethod
+    def _sdf_of(f: VptSdf, frame=None, type=None, material=None, whd=None, p=None) -> VptSdf:
+        """f with the named fields replaced (type: an index into SDF_TYPES or its name)"""
         if frame is not None:
             C.memmove(C.byref(f.frame), np.ascontiguousarray(frame, np.float32).reshape(12).ctypes.data, 48)
         if type is not None:
@@ -703,8 +717,7 @@ class HostScene(_Handle):
             f.whd[:] = [float(v) for v in whd]
         if p is not None:
             f.p[:] = ([float(v) for v in p] + [0.0] * 4)[:4]
-        _host_call(host.vpth_scene_set_sdf, self.handle, index, C.byref(f))
-        self._volume_edit.sdfs[index] = self.sdf(index)
+        return f
 
     def _write_volume(self, index: int, src: VolumeSource, voxels: np.ndarray) -> None:
         whd, lo, size = (np.array([int(v) for v in a], np.int32) for a in (src.whd, src.region_lo, src.region_whd))
@@ -713,6 +726,7 @@ class HostScene(_Handle):
                    int(src.mode), voxels.ctypes.data)
 
     def _note_volume(self, index: int, src: VolumeSource) -> None:
+        self._may("set_volume / bake_volume", "volume_entries")
         if index in self._volume_edit.volumes:
             raise VptError(f"volume {index} is already in the pending edit: hand it out with update_volumes() first")
         if any(e.volume == index for e in self._sculpt_edit.entries):
@@ -780,6 +794,147 @@ class HostScene(_Handle):
         edit, self._volume_edit = self._volume_edit, VolumeEdit()
         return edit
 
+    # -- the set of volumes, grid instances and SDFs (the host side of vpt_scene_update_volume_set): the add_* / remove_* calls note a
+    #    change, removals naming the lists as they are now; update_volume_set() applies them to the scene - remove, then add - runs
+    #    make_lights and hands the VolumeSetEdit out.  The ids of a pending VolumeEdit or SculptEdit name the old lists, so the two kinds of
+    #    change do not mix: each is handed out before the other begins --------------------------------------------------------------------
+    def _begin_volume_set_change(self, what: str) -> VolumeSetEdit:
+        self._may(what, "volume_set")
+        return self._volume_set_edit
+
+    def _note_removals(self, what: str, kind: str, pending: tuple, ids) -> tuple:
+        ids = [int(i) for i in ids]
+        for i in ids:
+            if not 0 <= i < self.count_implicit(kind):
+                raise VptError(f"{what}: id {i} out of range")
+        if len(set(ids)) != len(ids) or set(ids) & set(pending):
+            raise VptError(f"{what}: an id is repeated")
+        return pending + tuple(ids)
+
+    def add_volume(self, voxels=None, *, bake=None, fill=None, copy_of=None, whd=None, res=None) -> int:
+        """notes a new volume, appended at update_volume_set(); returns the id it has afterwards (given the removals noted so far).
+        Exactly one source: voxels, float32 of shape (d, h, w); bake = (positions, faces) or (positions, faces, origin, step), a mesh baked
+        on the device by the rule of vpt_bake_sdf into a grid of `whd` (origin / step: bake_volume's defaults) - the host copy runs the
+        host mirror of the bake only when it is read; fill, a float every voxel of `whd` gets; copy_of, a current volume id whose voxels
+        the new volume starts with.  res: the volume's (copy_of: the source's unless given)."""
+        pend = self._begin_volume_set_change("add_volume")
+        if sum(x is not None for x in (voxels, bake, fill, copy_of)) != 1:
+            raise VptError("add_volume: exactly one of voxels, bake, fill and copy_of says where the voxels come from")
+        if copy_of is not None:
+            whd, old_res = self._volume_shape(int(copy_of))
+            new = VolumeNew(whd, old_res if res is None else float(res), VOLUME_COPY, copy_of=int(copy_of))
+        else:
+            if res is None or not np.isfinite(res):
+                raise VptError("add_volume: a finite res is needed")
+            if voxels is not None:
+                voxels = np.ascontiguousarray(voxels, np.float32)
+                if voxels.ndim != 3 or (whd is not None and tuple(int(v) for v in _whd3(whd)) != voxels.shape[::-1]):
+                    raise VptError(f"add_volume: expected (d, h, w) voxels of whd, got {voxels.shape}")
+                new = VolumeNew(voxels.shape[::-1], float(res), VOLUME_FROM_HOST, voxels=voxels.copy())
+            else:
+                if whd is None:
+                    raise VptError("add_volume: a baked or filled volume needs whd")
+                whd = tuple(int(v) for v in _whd3(whd))
+                if min(whd) < 0 or whd[0] * whd[1] * whd[2] >= 2 ** 31:
+                    raise VptError(f"add_volume: bad whd {whd}")
+                if fill is not None:
+                    new = VolumeNew(whd, float(res), VOLUME_FILL, fill=fill)
+                else:
+                    positions, faces = bake[0], bake[1]
+                    origin = np.zeros(3, np.float32) if len(bake) < 3 or bake[2] is None else bake[2]
+                    step = (np.array([np.float32(res) * np.float32(w) / np.float32(max(1, w - 1)) for w in whd], np.float32)
+                            if len(bake) < 4 or bake[3] is None else bake[3])
+                    positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3).copy()
+                    new = VolumeNew(whd, float(res), VOLUME_FROM_BAKE, bake=(positions, bake_triangles(faces), np.asarray(origin, np.float32).copy(),
+                                                                              np.asarray(step, np.float32).copy()))
+        pend.add_volumes.append(new)
+        return self.count_implicit("volumes") - len(pend.remove_volumes) + len(pend.add_volumes) - 1
+
+    def _volume_shape(self, index: int):
+        """((w, h, d), res) of volume `index` without a copy of its voxels; a pending bake of that volume runs first (it may change both)"""
+        if any(k == index for k, _ in self._lazy_bakes):
+            self._run_bakes()
+        whd, res = np.zeros(3, np.int32), C.c_float()
+        if host.vpth_scene_get_volume(self.handle, index, whd.ctypes.data, C.byref(res), None, 0) < 0:
+            raise VptError(f"volume {index} out of range")
+        return tuple(int(v) for v in whd), res.value
+
+    def remove_volumes(self, ids) -> None:
+        """notes volumes (current ids) to erase at update_volume_set(): the survivors keep their order, the ids close up and the grid
+        instances' volume ids follow.  No grid instance that stays or is added may name a removed volume: update_volume_set() refuses it."""
+        pend = self._begin_volume_set_change("remove_volumes")
+        pend.remove_volumes = self._note_removals("remove_volumes", "volumes", pend.remove_volumes, ids)
+
+    def add_volume_instance(self, frame, volume: int, material: int, scalef: float = 1) -> int:
+        """notes a new grid instance, appended at update_volume_set(); `volume` is an id of the list as update_volume_set() leaves it (what
+        add_volume returned, or a survivor's new id).  Returns the id the instance has afterwards."""
+        pend = self._begin_volume_set_change("add_volume_instance")
+        frame = np.ascontiguousarray(frame, np.float32).reshape(-1)
+        if frame.size != 12 or not np.all(np.isfinite(frame)) or not np.isfinite(scalef):
+            raise VptError("add_volume_instance: a frame is twelve finite floats (x, y, z, o), scalef a finite one")
+        if not 0 <= int(volume) < self.count_implicit("volumes") - len(pend.remove_volumes) + len(pend.add_volumes):
+            raise VptError(f"add_volume_instance: volume {volume} out of range of the list after the edit")
+        if not 0 <= int(material) < self.count("materials"):
+            raise VptError(f"add_volume_instance: material {material} out of range")
+        vi = VptVolumeInstance(volume=int(volume), material=int(material), scalef=float(scalef))
+        C.memmove(C.byref(vi.frame), frame.ctypes.data, 48)
+        pend.add_vol_instances.append(vi)
+        return self.count_implicit("vol_instances") - len(pend.remove_vol_instances) + len(pend.add_vol_instances) - 1
+
+    def remove_volume_instances(self, ids) -> None:
+        """notes grid instances (current ids) to erase at update_volume_set()"""
+        pend = self._begin_volume_set_change("remove_volume_instances")
+        pend.remove_vol_instances = self._note_removals("remove_volume_instances", "vol_instances", pend.remove_vol_instances, ids)
+
+    def add_sdf(self, sdf: Optional[VptSdf] = None, frame=None, type=None, material=None, whd=None, p=None) -> int:
+        """notes a new analytic SDF, appended at update_volume_set(): a whole VptSdf, or one made of the named fields as set_sdf takes them
+        (frame: identity unless given).  Returns the id it has afterwards."""
+        pend = self._begin_volume_set_change("add_sdf")
+        f = VptSdf()
+        if sdf is not None:
+            C.memmove(C.byref(f), C.byref(sdf), C.sizeof(VptSdf))
+        else:
+            C.memmove(C.byref(f.frame), np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], np.float32).ctypes.data, 48)
+        f = self._sdf_of(f, frame, type, material, whd, p)
+        floats = np.frombuffer(bytes(f), np.float32)
+        if not (np.all(np.isfinite(floats[:12])) and np.all(np.isfinite(floats[14:21]))):
+            raise VptError("add_sdf: a value is not finite")
+        if not 0 <= f.type < len(SDF_TYPES) or not 0 <= f.material < self.count("materials"):
+            raise VptError(f"add_sdf: type {f.type} or material {f.material} out of range")
+        pend.add_sdfs.append(f)
+        return self.count_implicit("sdfs") - len(pend.remove_sdfs) + len(pend.add_sdfs) - 1
+
+    def remove_sdfs(self, ids) -> None:
+        """notes analytic SDFs (current ids) to erase at update_volume_set(); a light SDF behind them follows the new numbering"""
+        pend = self._begin_volume_set_change("remove_sdfs")
+        pend.remove_sdfs = self._note_removals("remove_sdfs", "sdfs", pend.remove_sdfs, ids)
+
+    def update_volume_set(self) -> VolumeSetEdit:
+        """the host side of vpt_scene_update_volume_set over what the add_* / remove_* calls noted since the last call: erase / push_back
+        on the scene's volumes, grid instances and SDFs, the instances' volume ids renumbered, make_lights; desc, lights() and stats()
+        describe the edited scene afterwards.  A baked addition holds zeros until the host copy is read (_run_bakes); a bake still
+        pending from before follows its volume to the new id, is dropped with a volume that goes, and runs first only where the edit
+        copies its volume.  Returns the VolumeSetEdit for DeviceScene.update_volume_set; an edit the host library refuses stays pending
+        and changes nothing."""
+        self._may("update_volume_set", "volume_set")
+        edit = self._volume_set_edit
+        if edit.empty():
+            return edit
+        if {k for k, _ in self._lazy_bakes} & {n.copy_of for n in edit.add_volumes if n.source == VOLUME_COPY}:
+            self._run_bakes()
+        count = self.count_implicit("volumes")
+        abi, keep = edit.to_abi()
+        _host_call(host.vpth_scene_edit_volume_set, self.handle, C.byref(abi))
+        del keep
+        self._volume_set_edit = VolumeSetEdit()
+        kept = [k for k in range(count) if k not in edit.remove_volumes]   # new id -> old id of the survivors
+        self._lazy_bakes = [(kept.index(k), src) for k, src in self._lazy_bakes if k in kept]
+        first = self.count_implicit("volumes") - len(edit.add_volumes)
+        for k, new in enumerate(edit.add_volumes):
+            if new.source == VOLUME_FROM_BAKE:
+                self._lazy_bakes.append((first + k, VolumeSource(tuple(new.whd), new.res, (0, 0, 0), tuple(new.whd), VOXELS_REPLACE, None, new.bake)))
+        return edit
+
     # -- sculpting (the host side of vpt_scene_sculpt_volumes): sculpt_volume applies a stroke to the scene's copy through the host mirror
     #    at once and notes it in the pending SculptEdit, which update_sculpts() hands out ----------------------------------------------
     def sculpt_volume(self, index: int, stamps, region=None, origin=None, step=None) -> SculptEntry:
@@ -788,6 +943,7 @@ class HostScene(_Handle):
         each (x, y, z); origin / step None: bake_volume's defaults (origin 0, step = res * W / (W - 1) per axis: the grid's local frame
         divided by scalef).  Returns the entry it noted.  A refused call changes nothing."""
         index = int(index)
+        self._may("sculpt_volume", "volume_entries")
         if index in self._volume_edit.volumes:
             raise VptError(f"sculpt_volume: volume {index} is in the pending volume edit: hand it out with update_volumes() first")
         old, res = self.volume(index)

@@ -9,7 +9,7 @@ import numpy as np
 from ._abi import (DENOISE_ITERATIONS, DENOISE_SIGMA_ALBEDO, DENOISE_SIGMA_LUMINANCE, DENOISE_SIGMA_NORMAL, VptAdaptive, VptDenoise, VptPick,
                    VptError, VptSdf, VptSdfPick, VptSessionParams, _Handle, _check, _edit_call, _p, hip)
 from .device import DeviceScene, DisplayParams, PathtraceParams, PathtraceState, _subdiv_edit_call
-from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, TextureEdit, VolumeEdit
+from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, TextureEdit, VolumeEdit, VolumeSetEdit
 
 
 class RenderSession(_Handle):
@@ -120,6 +120,11 @@ class RenderSession(_Handle):
     def edit_volumes(self, edit: VolumeEdit) -> None:
         """edit() through vpt_scene_update_volumes, with the VolumeEdit of HostScene.update_volumes()"""
         _edit_call(self.handle, "vpt_session_edit_volumes", edit)
+
+    def edit_volume_set(self, edit: VolumeSetEdit) -> None:
+        """edit() through vpt_scene_update_volume_set, with the VolumeSetEdit of HostScene.update_volume_set(); the reset drops both id
+        frames, so pick_sdf names the lists as the edit leaves them"""
+        _edit_call(self.handle, "vpt_session_edit_volume_set", edit)
 
     def edit_sculpts(self, edit: SculptEdit) -> None:
         """vpt_scene_sculpt_volumes on the session's scene with the SculptEdit of HostScene.update_sculpts(), then a reset; a refused edit
