@@ -661,11 +661,21 @@ int vpt_scene_update_volume_set(vpt_scene* scene, const vpt_volume_set_edit* edi
  * vpt_scene_volgrid_density: at n world points (3 floats each) sigma[i] = the sum over the grid instances, in index order, of their
  * densities, and instance[i] (nullable) = the first instance whose box holds the point, -1 if none does.  Refused like a render when a
  * grid instance's material has no usable trdepth.
+ * vpt_scene_volgrid_track: track(ray, rng) above on n given world rays (6 floats each: origin, unit direction) with n given PCG32 streams
+ * (state, inc), one lane per record, through the device functions K3 itself calls, compiled in K3's unit: event[i] = 0 escape, 1
+ * collision, 2 the flight ran into VPT_VOLGRID_MAX_STEPS; instance[i] and t[i] = the collision's grid instance and world parameter (-1 and
+ * FLT_MAX unless event[i] == 1); steps[i] = the tracking steps taken; rng_out (nullable) = the streams after the flight.  Tables are
+ * brought up to date as before a launch, VPT_VOLGRID_NO_BRICKS is honoured, the refusal of a medium without usable trdepth is a render's;
+ * the steps word of vpt_scene_volgrid_stats does not count these flights.  VPT_ERR_INVALID_ARG before anything is launched: n < 0, a null
+ * pointer other than rng_out when n > 0, a ray component that is not finite, a direction whose length is not within 1e-3 of 1.
  * vpt_scene_volgrid_stats: tracking steps taken by the handle's volgrid launches so far and the builds of its brick tables so far (either
  * nullable); synchronous. */
 #define VPT_VOLGRID_MAX_STEPS (1 << 20)
 int vpt_scene_get_volgrid_majorants(vpt_scene* scene, int volume, float* out, int64_t capacity, int32_t dims[3]);
 int vpt_scene_volgrid_density(vpt_scene* scene, int n, const float* points, int32_t* instance, float* sigma);
+int vpt_scene_volgrid_track(vpt_scene* scene, int n, const float* rays /* n x {o[3], d[3]} */, const uint64_t* rng_in /* n x {state, inc} */,
+                            int32_t* event /* 0 escape, 1 collision, 2 step bound reached */, int32_t* instance /* -1 unless event == 1 */,
+                            float* t /* flt_max unless event == 1 */, int32_t* steps, uint64_t* rng_out /* n x {state, inc}, nullable */);
 int vpt_scene_volgrid_stats(vpt_scene* scene, uint64_t* steps, int32_t* table_builds);
 
 /* ---- the BVHs of a resident scene built anew on the device ------------------------------------------------------------

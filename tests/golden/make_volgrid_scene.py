@@ -14,6 +14,7 @@ zoomed on the box's centre, for the sparse grid's block), an untextured environm
   overlap.json      two instances of the constant grid with materials of different trdepth, the second moved by (0.25, 0.25, 0)
   messy.json        9 x 17 x 30 nodes of a seeded pattern with NaN, +-Inf, negative values and zeros (tables and lookups, not renders)
   furnace_tex.json  the sparse grid and a texture for the environment (the tests replace its texels by one colour: a CDF light)
+  two_env.json      the sparse grid under two untextured environments of emission (0.25, 0.25, 0.25) each: two entries of the light list
 
 Grids are written from fixed formulas and a seeded numpy generator; numpy only."""
 import json
@@ -66,10 +67,10 @@ def camera(name, extent):
             "focus": 3.0, "aperture": 0.0}
 
 
-def scene(volumes, instances, materials=None, textures=None):
+def scene(volumes, instances, materials=None, textures=None, environments=None):
     out = {"asset": {"generator": "tests/golden/make_volgrid_scene.py", "version": "4.2"},
            "cameras": [camera("box", 1.25), camera("centre", 0.25)],
-           "environments": [{"name": "grey", "emission": [0.5, 0.5, 0.5]}],
+           "environments": environments or [{"name": "grey", "emission": [0.5, 0.5, 0.5]}],
            "materials": materials or [{"name": "medium", "type": "volumetric", "scattering": [0.8, 0.8, 0.8], "scanisotropy": 0.6, "trdepth": 1.0}],
            "volumes": [{"name": n, "uri": f"sdfs/{n}.sdf", "binary": True} for n in volumes],
            "vol_instances": instances}
@@ -98,6 +99,7 @@ def main():
         "overlap.json": scene(["constant"], [instance("thin", 0, 0), instance("thick", 0, 1, (0.25, 0.25, 0.0))], materials=two),
         "messy.json": scene(["messy", "sparse"], [instance("messy", 0), instance("cloud", 1)]),
         "furnace_tex.json": scene(["sparse"], [instance("cloud", 0)], textures=[{"name": "sky", "uri": "../shared_textures/texture2.hdr"}]),
+        "two_env.json": scene(["sparse"], [instance("cloud", 0)], environments=[{"name": n, "emission": [0.25, 0.25, 0.25]} for n in ("grey_a", "grey_b")]),
     }
     for name, content in scenes.items():
         with open(os.path.join(OUT, name), "w") as f:

@@ -505,6 +505,7 @@ host.vpth_volgrid_majorants.argtypes = [_p, C.c_int, _p, C.c_int64, _p, C.c_char
 host.vpth_volgrid_density.argtypes = [_p, C.c_int, _p, _p, _p, C.c_char_p, C.c_int]
 hip.vpt_scene_get_volgrid_majorants.argtypes = [_p, C.c_int, _p, C.c_int64, _p]
 hip.vpt_scene_volgrid_density.argtypes = [_p, C.c_int, _p, _p, _p]
+hip.vpt_scene_volgrid_track.argtypes = [_p, C.c_int, _p, _p, _p, _p, _p, _p, _p]
 hip.vpt_scene_volgrid_stats.argtypes = [_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
 host.vpth_mesh_sdf.argtypes = [C.POINTER(VptSdfMeshDesc), _p, C.POINTER(VptSdfMeshRegion), _p, _p, C.c_int32, _p, C.c_int32, C.POINTER(VptSdfMeshStats),
                                C.c_char_p, C.c_int]

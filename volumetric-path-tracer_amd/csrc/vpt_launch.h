@@ -84,6 +84,9 @@ struct volgrid_args {
 template <bool PILOT>
 __global__ void __launch_bounds__(VPT_BLOCK, VPT_K3_WAVES) vpt_volgrid_kernel(DScene sc, DParams pr, volgrid_args va, float4* __restrict__ image,
     int* __restrict__ hits, ulonglong2* __restrict__ rngs, sched_cfg sched);
+// the free-flight probe of vpt_scene_volgrid_track: one lane per record through K3's vg_start / vg_track_step (defined in vpt_k3.hip)
+__global__ void vpt_volgrid_track_kernel(DScene sc, volgrid_args va, int n, const float* __restrict__ rays, const ulonglong2* __restrict__ rng_in,
+    int* __restrict__ event, int* __restrict__ instance, float* __restrict__ t, int* __restrict__ steps, ulonglong2* __restrict__ rng_out);
 
 // ---- vpt_intersect, KAT, self-tests (vpt_kernels.hip, but for vpt_intersect_curves_kernel: vpt_k1_curves.hip) ----------------
 template <bool SPILL, bool COMPACT>

@@ -1,7 +1,7 @@
 // vpt_volgrid.hip — the host side of the volgrid shader (include/vpt.h: VPT_SHADER_VOLGRID): K3's tables - the records of the grid instances
 // as media, made on the host from the handle's mirrors, and the brick majorants of the volumes, reduced on the device from the voxels where
-// they lie - kept current against the handle's edit counters, the refusals of a volgrid render, and the two queries over a resident scene.
-// The arithmetic is csrc/vpt_volgrid_rule.h's; K3 itself is vpt_k3.hip's.
+// they lie - kept current against the handle's edit counters, the refusals of a volgrid render, the two queries over a resident scene, and the host side
+// of the free-flight probe (vpt_scene_volgrid_track).  The arithmetic is csrc/vpt_volgrid_rule.h's; K3 itself and the probe's kernel are vpt_k3.hip's.
 #include <cmath>
 #include <cstdlib>
 #include <vector>
@@ -149,6 +149,37 @@ int vpt_scene_volgrid_density(vpt_scene* s, int n, const float* points, int32_t*
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(sigma, d_sigma.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
   if (instance) HIP_TRY(hipMemcpy(instance, d_instance.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+
+int vpt_scene_volgrid_track(vpt_scene* s, int n, const float* rays, const uint64_t* rng_in, int32_t* event, int32_t* instance, float* t, int32_t* steps,
+    uint64_t* rng_out) {
+  REQUIRE(s && n >= 0 && (n == 0 || (rays && rng_in && event && instance && t && steps)), "bad argument");
+  for (int i = 0; i < n; i++) {
+    const float* r = rays + 6 * (size_t)i;
+    for (int k = 0; k < 6; k++) REQUIRE(std::isfinite(r[k]), "volgrid_track: ray %d has a component that is not finite", i);
+    const double len = std::sqrt((double)r[3] * r[3] + (double)r[4] * r[4] + (double)r[5] * r[5]);
+    REQUIRE(std::fabs(len - 1.0) <= 1e-3, "volgrid_track: ray %d has a direction of length %g (a unit vector within 1e-3 is needed)", i, len);
+  }
+  if (int rc = volgrid_prepare(s, nullptr)) return rc;
+  if (n == 0) return VPT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  device_buffer d_rays, d_rng, d_out;   // d_out: event, instance, t, steps - four planes of n words
+  if (int rc = d_rays.allocate((size_t)n * 24)) return rc;
+  if (int rc = d_rng.allocate((size_t)n * 32)) return rc;   // in, then out
+  if (int rc = d_out.allocate((size_t)n * 16)) return rc;
+  HIP_TRY(hipMemcpy(d_rays.get(), rays, (size_t)n * 24, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_rng.get(), rng_in, (size_t)n * 16, hipMemcpyHostToDevice));
+  int*        o  = d_out.get<int>();
+  ulonglong2* rg = d_rng.get<ulonglong2>();
+  hipLaunchKernelGGL(vpt_volgrid_track_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, s->d, volgrid_arguments(s), n, d_rays.get<const float>(),
+      (const ulonglong2*)rg, o, o + n, (float*)(o + 2 * (size_t)n), o + 3 * (size_t)n, rng_out ? rg + n : nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(event, o, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(instance, o + n, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(t, o + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(steps, o + 3 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (rng_out) HIP_TRY(hipMemcpy(rng_out, rg + n, (size_t)n * 16, hipMemcpyDeviceToHost));
   return VPT_OK;
 }
 

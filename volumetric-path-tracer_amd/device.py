@@ -296,6 +296,22 @@ class DeviceScene(_Handle):
                "vpt_scene_volgrid_density")
         return sigma, instance
 
+    def volgrid_track(self, rays, rngs):
+        """the volgrid shader's free flight on given world rays ((n, 6) float32: origin, unit direction) with given PCG32 streams ((n, 2)
+        uint64: state, inc), flown by the kernel's own tracking functions (vpt_scene_volgrid_track): (event, instance, t, steps, rngs_out)
+        = (n,) int32 0 escape / 1 collision / 2 step bound, (n,) int32 the collision's grid instance or -1, (n,) float32 its world
+        parameter or FLT_MAX, (n,) int32 tracking steps, (n, 2) uint64 the streams after the flight"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        rngs = np.ascontiguousarray(rngs, np.uint64).reshape(-1, 2)
+        if len(rays) != len(rngs):
+            raise VptError(f"volgrid_track: {len(rays)} rays but {len(rngs)} streams")
+        n = len(rays)
+        event, instance, steps = np.zeros(n, np.int32), np.full(n, -1, np.int32), np.zeros(n, np.int32)
+        t, rngs_out = np.zeros(n, np.float32), np.zeros((n, 2), np.uint64)
+        _check(hip.vpt_scene_volgrid_track(self.handle, n, rays.ctypes.data, rngs.ctypes.data, event.ctypes.data, instance.ctypes.data, t.ctypes.data,
+                                           steps.ctypes.data, rngs_out.ctypes.data), "vpt_scene_volgrid_track")
+        return event, instance, t, steps, rngs_out
+
     def volgrid_stats(self) -> dict:
         """vpt_scene_volgrid_stats: tracking steps of this handle's volgrid launches so far, builds of its brick tables so far"""
         steps, builds = C.c_uint64(0), C.c_int32(0)
