@@ -1140,6 +1140,58 @@ int vpt_resolve_sdf_ids_device(const vpt_layout* layout, const void* d_ids, cons
 int vpt_render_sdf_aov(vpt_scene* scene, const vpt_params* params, int nsamples, int width, int height,
                        const vpt_sdf_aov_planes* planes, int32_t* hits, uint64_t* rng, int* samples_io);
 
+/* ---- first-collision AOVs of the volgrid shader: one free flight per sample -------------------------------------
+ * The volgrid counterpart of the two passes above: what the media of a scene show under a pixel.  A medium has no first surface; it
+ * has a first COLLISION, and that is a random event.  Per sample and slot -> pixel (px, py) vpt_render_volgrid_aov_device draws u, v
+ * and the lens sample exactly as vpt_render_device with `volgrid` does (the pixel-centre branch of params->samples == 1 draws no
+ * jitter), evaluates eval_camera, flies ONE track(ray, rng) - bounce 0 of the volgrid path above, its draws taken from the pixel's
+ * stream as there - and gives every plane that is not null this sample's value:
+ *   opacity  float4 per slot, sums: {1, 1, 1, 1} on a collision, {0,0,0,0} on an escape or an aborted flight
+ *   albedo   float4 per slot, sums: {albedo of the colliding instance's record (scattering clamped to [0, 1]), 1}, zeros otherwise
+ *   depth    float4 per slot, sums: {t, 0, 0, 1}, zeros otherwise
+ *   normal   float4 per slot, sums: {n * 0.5 + 0.5, 1}, zeros otherwise.  n = -normalize(g), g the world gradient of the colliding
+ *            instance's voxel value at the collision point: the analytic derivative of the trilerp inside its cell over the eight
+ *            nodes, each through clean() first, at the node coordinates the density lookup computes, per axis times (whd - 1) / bbox,
+ *            rotated to the world by the record's frame (csrc/vpt_volgrid_rule.h: vpt_volgrid_normal, the operation order).  A
+ *            gradient of length 0 or one that is not finite gives n = 0: the value {0.5, 0.5, 0.5, 1}
+ *   ids      int32 x2 per slot: {vol_instance, volume} of the FIRST colliding sample of the state's chain
+ *   hit      float4 per slot: {position.xyz, t} of the same collision, position = o + d * t; needs ids.
+ * ids / hit: a slot that the launch finds at hits[slot] == 0 starts from {-1, -1} and zeros whatever the buffers hold, any other from
+ * what they hold; a colliding sample writes them only while the id is still {-1, -1}; a slot in which no sample has collided ends with
+ * {-1, -1} and zeros.  So the two planes do not depend on batching.  A sample's value that is not finite counts as zeros, decided per
+ * plane.  hits += nsamples; rng advances by the camera draws plus the flight's draws.  A flight that runs into VPT_VOLGRID_MAX_STEPS
+ * adds zeros and is counted in the handle's watchdog word, as in a render (vpt_check_watchdog).  The tracking steps of this pass are
+ * not counted by vpt_scene_volgrid_stats.  The planes are tile-major in the layout's slots like `image`; padding slots and other
+ * ranks' slots are never touched.  A scene without grid instances is not an error: every sample escapes.
+ * Contracts: (a) any batching of nsamples gives the same bits in every plane; (b) from equal hits / rng with nsamples == 1, opacity.w
+ * equals the alpha vpt_render_device with `volgrid` adds, for any bounces >= 1 (later samples differ: a path draws on after bounce
+ * 0); (c) with params->samples == 1 the event, the instance and t are vpt_scene_volgrid_track's on the pixel-centre rays with the same
+ * streams, and the stream afterwards is its rng_out; (d) VPT_VOLGRID_NO_BRICKS=1 is honoured; (e) a scene where some grid instance's
+ * material has no usable trdepth is refused as a volgrid render refuses it (VPT_ERR_INVALID_ARG, nothing touched).
+ * vpt_render_volgrid_aov_device: asynchronous on `stream`, one plain launch (no schedule, no pilot, no tile splitting); stale brick
+ * tables are rebuilt first, on `stream`, as before a volgrid render; nsamples == 0 is a no-op; params->shader is ignored.
+ * VPT_ERR_INVALID_ARG (the message names the argument) when every plane is null, hit is given without ids, two planes share a
+ * buffer, or hits / rng / params / layout is null.  The planes must not overlap each other, hits or rng.
+ * vpt_resolve_volgrid_ids_device: the gathered ids / hit of ALL ranks ([nranks][slots]) -> row-major; d_hit and d_hit_rowmajor null
+ * together (it is vpt_resolve_sdf_ids_device under the pass's name: the planes have the same entry sizes).
+ * vpt_render_volgrid_aov: the same on host arrays, with vpt_render_sdf_aov's contract - `planes` holds HOST pointers to row-major
+ * planes (in and out: the float planes are sums), hits / rng are those of a row-major pathtrace_state; min(nsamples, params->samples
+ * - *samples_io) samples, a no-op at the cap.  Synchronous; it ends with vpt_check_watchdog. */
+typedef struct vpt_volgrid_aov_planes {
+  void* opacity;    /* float4 per slot (pixel), or NULL */
+  void* albedo;
+  void* depth;
+  void* normal;
+  void* ids;        /* int32 x2 */
+  void* hit;        /* float4; needs ids */
+} vpt_volgrid_aov_planes;
+int vpt_render_volgrid_aov_device(vpt_scene* scene, const vpt_params* params, const vpt_layout* layout, int nsamples,
+                                  const vpt_volgrid_aov_planes* planes, void* d_hits, void* d_rng, void* stream);
+int vpt_resolve_volgrid_ids_device(const vpt_layout* layout, const void* d_ids, const void* d_hit, void* d_ids_rowmajor,
+                                   void* d_hit_rowmajor, void* stream);
+int vpt_render_volgrid_aov(vpt_scene* scene, const vpt_params* params, int nsamples, int width, int height,
+                           const vpt_volgrid_aov_planes* planes, int32_t* hits, uint64_t* rng, int* samples_io);
+
 /* ---- adaptive sampling: every pixel renders until its noise meets a target ---------------------------
  * A pixel that stops after k samples holds exactly the state k consecutive reference calls leave (image, rng, hits == k):
  * pixels are independent and batching is exact, so the numerical contract holds per pixel.  Rendering goes in rounds; each
@@ -1447,6 +1499,31 @@ typedef struct vpt_sdf_pick {
 } vpt_sdf_pick;
 int  vpt_session_pick_sdf(vpt_session* session, int x, int y, vpt_sdf_pick* out);
 int  vpt_session_get_sdf_ids(vpt_session* session, int32_t* ids, float* hit);
+/* ---- what is under a pixel of a volgrid session -----------------------------------------------------------------
+ * The counterpart of the two pairs above for a session whose shader is volgrid; pick, pick_sdf, get_ids, get_sdf_ids, get_guides and
+ * every denoise entry stay refused there.  The id frame: {vol_instance, volume} and {position, t} of the first collision of every
+ * pixel's chain of max(guide_samples, 1) free flights at full resolution over hits / rng of its own, initialised on the device:
+ * one sample of vpt_render_volgrid_aov_device with samples = 1 - the ray through the pixel centre -, then guide_samples - 1 jittered
+ * ones in a second launch, then vpt_resolve_volgrid_ids_device.  The centre ray's collision is the answer where it has one; thin
+ * smoke it flies through can still be picked by a later flight.  The frame is made by the first pick_volgrid or get_volgrid_ids
+ * after a reset (3 or 4 launches, the watchdog's word read once: 4 bytes) and kept until the next reset.  Every edit resets.
+ *   pick_volgrid     the collision under pixel (x, y): one launch that packs the 48 bytes below on the device and one copy of them -
+ *                    48 bytes cross PCIe per pick.  material is that of the resident vol_instances[vol_instance]; normal is the
+ *                    pass's normal at `position`, density the volgrid extinction of that instance alone there
+ *                    (vpt_scene_volgrid_density's term for it).  On a miss hit = 0, the three ids are -1 and the floats 0.
+ *                    x / y outside the frame: VPT_ERR_INVALID_ARG.
+ *   get_volgrid_ids  the whole frame, row-major: ids int32 x2 and hit float x4 per pixel, either pointer nullable, not both.
+ * Both return VPT_ERR_UNSUPPORTED under any other shader. */
+typedef struct vpt_volgrid_pick {
+  int32_t hit;                  /* 0 / 1 */
+  int32_t vol_instance, volume, material;
+  float   distance;
+  float   position[3];
+  float   normal[3];
+  float   density;
+} vpt_volgrid_pick;
+int  vpt_session_pick_volgrid(vpt_session* session, int x, int y, vpt_volgrid_pick* out);
+int  vpt_session_get_volgrid_ids(vpt_session* session, int32_t* ids, float* hit);
 /* ---- adaptive sampling in a session ------------------------------------------------------------------------
  * vpt_session_set_adaptive adopts the settings and resets; NULL switches the mode off (and resets).  Checked like
  * vpt_render_adaptive: threshold finite and >= 0, step >= 1, 1 <= min_samples <= render.samples (VPT_ERR_INVALID_ARG; a refused

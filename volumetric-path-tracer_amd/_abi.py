@@ -101,6 +101,18 @@ class VptSdfPick(C.Structure):  # vpt_sdf_pick
                 ("distance", C.c_float), ("position", C.c_float * 3), ("normal", C.c_float * 3)]
 
 
+VOLGRID_AOV_PLANES = ("opacity", "albedo", "depth", "normal", "ids", "hit")
+
+
+class VptVolgridAovPlanes(C.Structure):  # vpt_volgrid_aov_planes: any of them None
+    _fields_ = [(name, C.c_void_p) for name in VOLGRID_AOV_PLANES]
+
+
+class VptVolgridPick(C.Structure):  # vpt_volgrid_pick
+    _fields_ = [("hit", C.c_int32), ("vol_instance", C.c_int32), ("volume", C.c_int32), ("material", C.c_int32), ("distance", C.c_float),
+                ("position", C.c_float * 3), ("normal", C.c_float * 3), ("density", C.c_float)]
+
+
 class VptFrame(C.Structure):  # vpt_frame: x, y, z, o
     _fields_ = [("x", C.c_float * 3), ("y", C.c_float * 3), ("z", C.c_float * 3), ("o", C.c_float * 3)]
 
@@ -407,6 +419,11 @@ hip.vpt_render_sdf_aov_device.argtypes = [_p, C.POINTER(VptParams), C.POINTER(Vp
 hip.vpt_resolve_sdf_ids_device.argtypes = [C.POINTER(VptLayout), _p, _p, _p, _p, _p]
 hip.vpt_render_sdf_aov.argtypes = [_p, C.POINTER(VptParams), C.c_int, C.c_int, C.c_int, C.POINTER(VptSdfAovPlanes), _p, _p, C.POINTER(C.c_int)]
 hip.vpt_session_pick_sdf.argtypes = [_p, C.c_int, C.c_int, C.POINTER(VptSdfPick)]
+hip.vpt_render_volgrid_aov_device.argtypes = [_p, C.POINTER(VptParams), C.POINTER(VptLayout), C.c_int, C.POINTER(VptVolgridAovPlanes), _p, _p, _p]
+hip.vpt_resolve_volgrid_ids_device.argtypes = [C.POINTER(VptLayout), _p, _p, _p, _p, _p]
+hip.vpt_render_volgrid_aov.argtypes = [_p, C.POINTER(VptParams), C.c_int, C.c_int, C.c_int, C.POINTER(VptVolgridAovPlanes), _p, _p, C.POINTER(C.c_int)]
+hip.vpt_session_pick_volgrid.argtypes = [_p, C.c_int, C.c_int, C.POINTER(VptVolgridPick)]
+hip.vpt_session_get_volgrid_ids.argtypes = [_p, _p, _p]
 hip.vpt_session_get_sdf_ids.argtypes = [_p, _p, _p]
 hip.vpt_last_kernel_ms.argtypes = [_p, C.POINTER(C.c_float)]
 hip.vpt_intersect.argtypes = [_p, C.c_int, _p, C.c_int, _p, _p]
@@ -503,6 +520,7 @@ host.vpth_scene_get_volume.restype = C.c_int64
 host.vpth_save_volume.argtypes = [C.c_char_p, _p, C.c_float, _p, C.c_char_p, C.c_int]
 host.vpth_volgrid_majorants.argtypes = [_p, C.c_int, _p, C.c_int64, _p, C.c_char_p, C.c_int]
 host.vpth_volgrid_density.argtypes = [_p, C.c_int, _p, _p, _p, C.c_char_p, C.c_int]
+host.vpth_volgrid_gradient.argtypes = [_p, C.c_int, C.c_int, _p, _p, _p, _p, C.c_char_p, C.c_int]
 hip.vpt_scene_get_volgrid_majorants.argtypes = [_p, C.c_int, _p, C.c_int64, _p]
 hip.vpt_scene_volgrid_density.argtypes = [_p, C.c_int, _p, _p, _p]
 hip.vpt_scene_volgrid_track.argtypes = [_p, C.c_int, _p, _p, _p, _p, _p, _p, _p]

@@ -16,6 +16,7 @@
 #include "vpt_frame_stages.h"   // check_display, state_init, vpt_pick_device
 #include "vpt_layout.h"
 #include "vpt_sdf_aov.h"   // vpt_sdf_pick_device
+#include "vpt_volgrid_aov.h"   // vpt_volgrid_pick_device
 
 namespace {
 
@@ -75,7 +76,9 @@ struct vpt_session {
   vpt_adaptive_run* run      = nullptr;
   buffer_group      noise;                                // made by the advance that creates a run
   device_buffer     a_se2, a_var, a_hits, a_mean, a_m2;   // row-major planes of the run's statistics
-  id_frame                  id_frames[2];   // [0] ids / uvt of vpt_render_aov_device for a mesh session, [1] ids / hit of vpt_render_sdf_aov_device for an implicit one
+  // [0] ids / uvt of vpt_render_aov_device for a mesh session, [1] ids / hit of vpt_render_sdf_aov_device for an implicit one, [2] ids / hit
+  // of vpt_render_volgrid_aov_device for a volgrid one
+  id_frame                  id_frames[3];
   std::vector<vpt_instance> instances;   // the scene's instance table as of the mesh id frame: a pick's shape and material
   // what the last call cost
   int     launches = 0;
@@ -85,30 +88,45 @@ struct vpt_session {
 namespace {
 
 bool implicit_shader(int shader) { return shader == VPT_SHADER_IMPLICIT || shader == VPT_SHADER_IMPLICIT_NORMAL; }
-// the volgrid shader has no first hit on a surface: no guides to filter with, nothing to pick, no id frame
+// the volgrid shader has no first hit on a surface: no guides to filter with, no surface to pick; its id frame is that of first collisions
 bool volgrid_shader(int shader) { return shader == VPT_SHADER_VOLGRID; }
 const char* const k_volgrid_refusal = "the session renders the volgrid shader: a medium has no surface to filter by, to pick or to name";
+enum { FAMILY_MESH = 0, FAMILY_IMPLICIT = 1, FAMILY_VOLGRID = 2 };
+int shader_family(int shader) { return volgrid_shader(shader) ? FAMILY_VOLGRID : (implicit_shader(shader) ? FAMILY_IMPLICIT : FAMILY_MESH); }
 
-// what tells the two id frames apart
+// what tells the three id frames apart
 struct id_frame_kind {
-  bool        implicit;                // the shader family it accepts; the other one: VPT_ERR_UNSUPPORTED with `refusal`
+  int         family;                  // the shader family it accepts and its entry of id_frames; another one: VPT_ERR_UNSUPPORTED with `refusal`
   const char *refusal, *aux_name;      // the second plane: its name in a message,
   size_t      aux_bytes, pick_bytes;   // its bytes per entry; the bytes of a pick
-  int (*pass)(vpt_scene*, const vpt_params*, const vpt_layout*, void* d_ids, void* d_aux, void* d_hits, void* d_rng, void* stream);
+  // the frame's samples over a state at hits == 0; *launches grows by those beyond the first (guide_samples: the volgrid kind alone reads it)
+  int (*pass)(vpt_scene*, const vpt_params*, const vpt_layout*, int guide_samples, void* d_ids, void* d_aux, void* d_hits, void* d_rng, void* stream, int* launches);
   int (*resolve)(const vpt_layout*, const void* d_ids, const void* d_aux, void* d_ids_rowmajor, void* d_aux_rowmajor, void* stream);
   int (*pack)(const vpt_scene*, const void* d_ids_rowmajor, const void* d_aux_rowmajor, long long pixel, void* d_out, void* stream);
 };
-const id_frame_kind k_mesh_ids = {false, "the session renders an implicit shader: its picture is not what the mesh BVH holds",
-    "uvt", 12, 24, [](vpt_scene* scene, const vpt_params* p, const vpt_layout* lay, void* ids, void* uvt, void* hits, void* rng, void* st) {
+const id_frame_kind k_mesh_ids = {FAMILY_MESH, "the session renders an implicit shader: its picture is not what the mesh BVH holds",
+    "uvt", 12, 24, [](vpt_scene* scene, const vpt_params* p, const vpt_layout* lay, int, void* ids, void* uvt, void* hits, void* rng, void* st, int*) {
       const vpt_aov_planes planes = {nullptr, nullptr, nullptr, nullptr, ids, uvt};
       return vpt_render_aov_device(scene, p, lay, 1, &planes, hits, rng, st);
     }, vpt_resolve_ids_device, vpt_pick_device};
-const id_frame_kind k_sdf_ids = {true, "the session renders a mesh shader: use vpt_session_pick / vpt_session_get_ids",
-    "hit", 16, sizeof(vpt_sdf_pick), [](vpt_scene* scene, const vpt_params* p, const vpt_layout* lay, void* ids, void* hit, void* hits, void* rng, void* st) {
+const id_frame_kind k_sdf_ids = {FAMILY_IMPLICIT, "the session renders a mesh shader: use vpt_session_pick / vpt_session_get_ids",
+    "hit", 16, sizeof(vpt_sdf_pick), [](vpt_scene* scene, const vpt_params* p, const vpt_layout* lay, int, void* ids, void* hit, void* hits, void* rng, void* st, int*) {
       const vpt_sdf_aov_planes planes = {nullptr, nullptr, nullptr, ids, hit};
       return vpt_render_sdf_aov_device(scene, p, lay, 1, &planes, hits, rng, st);
     }, vpt_resolve_sdf_ids_device, vpt_sdf_pick_device};
 static_assert(sizeof(vpt_sdf_pick) == 48, "the 48 bytes of a pick");
+// the centre ray, then guide_samples - 1 jittered flights of the same chain in a second launch (include/vpt.h)
+const id_frame_kind k_volgrid_ids = {FAMILY_VOLGRID, "the session does not render the volgrid shader: use the pick and the id frame of its own shader",
+    "hit", 16, sizeof(vpt_volgrid_pick), [](vpt_scene* scene, const vpt_params* p, const vpt_layout* lay, int guide_samples, void* ids, void* hit, void* hits, void* rng, void* st, int* launches) {
+      const vpt_volgrid_aov_planes planes = {nullptr, nullptr, nullptr, nullptr, ids, hit};
+      if (int rc = vpt_render_volgrid_aov_device(scene, p, lay, 1, &planes, hits, rng, st)) return rc;
+      if (guide_samples <= 1) return (int)VPT_OK;
+      vpt_params jittered = *p;
+      jittered.samples = guide_samples;
+      ++*launches;
+      return vpt_render_volgrid_aov_device(scene, &jittered, lay, guide_samples - 1, &planes, hits, rng, st);
+    }, vpt_resolve_volgrid_ids_device, vpt_volgrid_pick_device};
+static_assert(sizeof(vpt_volgrid_pick) == 48, "the 48 bytes of a pick");
 
 // make_state's size rule (yocto_pathtrace.cpp:964-970)
 void frame_size(int resolution, float aspect, int& width, int& height) {
@@ -231,9 +249,9 @@ int render_mesh_guides(vpt_session* s) {
 // sample of the kind's pass, its resolve; the state and the tile-major planes hold one entry per SLOT, the row-major ones per pixel.
 int ensure_id_frame(vpt_session* s, const id_frame_kind& k) {
   REQUIRE(s->width > 0, "the session holds no frame (a reset failed)");
-  if (volgrid_shader(s->p.render.shader)) return vpt_set_error(VPT_ERR_UNSUPPORTED, "%s", k_volgrid_refusal);
-  if (implicit_shader(s->p.render.shader) != k.implicit) return vpt_set_error(VPT_ERR_UNSUPPORTED, "%s", k.refusal);
-  id_frame& f = s->id_frames[k.implicit];
+  if (shader_family(s->p.render.shader) != k.family)
+    return vpt_set_error(VPT_ERR_UNSUPPORTED, "%s", volgrid_shader(s->p.render.shader) ? k_volgrid_refusal : k.refusal);
+  id_frame& f = s->id_frames[k.family];
   if (f.valid) return VPT_OK;
   const size_t n = pixels(s), slots = (size_t)vpt_layout_slots(&s->lay);
   if (int rc = f.group.ensure((long long)n, (long long)slots,
@@ -243,10 +261,12 @@ int ensure_id_frame(vpt_session* s, const id_frame_kind& k) {
   vpt_params p = s->p.render;
   p.samples    = 1;
   if (int rc = state_init(&s->lay, nullptr, f.hits.get(), f.rng.get(), s->st)) return rc;
-  if (int rc = k.pass(s->scene, &p, &s->lay, f.t_ids.get(), f.t_aux.get(), f.hits.get(), f.rng.get(), s->st)) return rc;
+  if (int rc = k.pass(s->scene, &p, &s->lay, s->p.guide_samples, f.t_ids.get(), f.t_aux.get(), f.hits.get(), f.rng.get(), s->st, &s->launches)) return rc;
+  if (k.family == FAMILY_VOLGRID)   // an aborted flight is reported as a render reports it
+    if (int rc = check_implicit_watchdog(s)) return rc;
   if (int rc = k.resolve(&s->lay, f.t_ids.get(), f.t_aux.get(), f.ids.get(), f.aux.get(), s->st)) return rc;
   s->launches += 3;
-  if (!k.implicit) {   // the mesh kind alone: a pick's shape and material are those of the instance table as it stands now, read once per id frame
+  if (k.family == FAMILY_MESH) {   // the mesh kind alone: a pick's shape and material are those of the instance table as it stands now, read once per id frame
     int count = 0;
     if (int rc = vpt_scene_get_instances(s->scene, nullptr, 0, &count)) return rc;
     s->instances.resize((size_t)count);
@@ -270,7 +290,7 @@ int reset(vpt_session* s, const vpt_session_params& np) {
   drop_run(s);                            // an adaptive run ends here; the first advance makes the next
   if (width != s->width || height != s->height || pw != s->pw || ph != s->ph || (np.denoise != 0) != (s->normal.get() != nullptr))   // (the filter's buffers exist)
     if (int rc = allocate(s, width, height, pw, ph, np.denoise != 0)) return rc;
-  s->p = np, s->samples = 0, s->a = 0, s->filtered_valid = false, s->has_albedo = false, s->id_frames[0].valid = s->id_frames[1].valid = false;
+  s->p = np, s->samples = 0, s->a = 0, s->filtered_valid = false, s->has_albedo = false, s->id_frames[0].valid = s->id_frames[1].valid = s->id_frames[2].valid = false;
   if (np.denoise) {
     if (implicit_shader(np.render.shader)) {
       if (int rc = render_guide(s, VPT_SHADER_IMPLICIT_NORMAL, s->normal.get())) return rc;
@@ -355,7 +375,7 @@ int get_id_frame(vpt_session* s, const id_frame_kind& k, void* ids, void* aux) {
   HIP_TRY(hipSetDevice(s->device));
   begin_call(s);
   if (int rc = ensure_id_frame(s, k)) return rc;
-  const id_frame& f = s->id_frames[k.implicit];
+  const id_frame& f = s->id_frames[k.family];
   return fetch(s, {{ids, &f.ids, pixels(s) * 8}, {aux, &f.aux, pixels(s) * k.aux_bytes}});
 }
 
@@ -368,7 +388,7 @@ int pick_record(vpt_session* s, const id_frame_kind& k, int x, int y, void* reco
   HIP_TRY(hipSetDevice(s->device));
   begin_call(s);
   if (int rc = ensure_id_frame(s, k)) return rc;
-  const id_frame& f = s->id_frames[k.implicit];
+  const id_frame& f = s->id_frames[k.family];
   if (int rc = k.pack(s->scene, f.ids.get(), f.aux.get(), (long long)y * s->width + x, f.pick.get(), s->st)) return rc;
   s->launches++;
   return fetch(s, {{record, &f.pick, k.pick_bytes}});
@@ -532,6 +552,11 @@ int vpt_session_get_sdf_ids(vpt_session* s, int32_t* ids, float* hit) { return g
 
 // the record crosses as it is: vpt_sdf_pick_device packs a vpt_sdf_pick
 int vpt_session_pick_sdf(vpt_session* s, int x, int y, vpt_sdf_pick* out) { return pick_record(s, k_sdf_ids, x, y, out); }
+
+int vpt_session_get_volgrid_ids(vpt_session* s, int32_t* ids, float* hit) { return get_id_frame(s, k_volgrid_ids, ids, hit); }
+
+// the record crosses as it is: vpt_volgrid_pick_device packs a vpt_volgrid_pick
+int vpt_session_pick_volgrid(vpt_session* s, int x, int y, vpt_volgrid_pick* out) { return pick_record(s, k_volgrid_ids, x, y, out); }
 
 int vpt_session_set_adaptive(vpt_session* s, const vpt_adaptive* a) {
   REQUIRE(s, "null session");

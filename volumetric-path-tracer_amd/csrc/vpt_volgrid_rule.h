@@ -146,3 +146,58 @@ VPT_VOLGRID_HD float vpt_volgrid_density(const vpt_volgrid_record& rec, const fl
   if (!vpt_volgrid_locate(rec, px, py, pz, node)) return 0.0f;
   return vpt_volgrid_sigma_at(rec, voxels, node);
 }
+
+// ---- the first-collision pass (include/vpt.h: vpt_render_volgrid_aov_device): the collision cell and the density's gradient in it ----------
+// The eight nodes of the cell eval_volume reads at node coordinates (s, t, r), each through clean(), in the order v000 v100 v010 v001 v011
+// v101 v110 v111 of the trilerp above, and the fractions (u, v, w) inside it: one fetch for the whole gradient
+VPT_VOLGRID_HD void vpt_volgrid_cell(const float* vox, int W, int H, int D, float s, float t, float r, float node[8], float uvw[3]) {
+  int i = (int)s, j = (int)t, k = (int)r;
+  i = i > 0 ? (i < W - 1 ? i : W - 1) : 0, j = j > 0 ? (j < H - 1 ? j : H - 1) : 0, k = k > 0 ? (k < D - 1 ? k : D - 1) : 0;
+  const int ii = i + 1 < W - 1 ? i + 1 : W - 1, jj = j + 1 < H - 1 ? j + 1 : H - 1, kk = k + 1 < D - 1 ? k + 1 : D - 1;
+  uvw[0] = s - i, uvw[1] = t - j, uvw[2] = r - k;
+  const int WH = W * H, r0 = j * W + k * WH, r1 = jj * W + k * WH, r2 = j * W + kk * WH, r3 = jj * W + kk * WH;
+  node[0] = vpt_volgrid_clean(vox[i + r0]), node[1] = vpt_volgrid_clean(vox[ii + r0]);
+  node[2] = vpt_volgrid_clean(vox[i + r1]), node[3] = vpt_volgrid_clean(vox[i + r2]);
+  node[4] = vpt_volgrid_clean(vox[i + r3]), node[5] = vpt_volgrid_clean(vox[ii + r2]);
+  node[6] = vpt_volgrid_clean(vox[ii + r1]), node[7] = vpt_volgrid_clean(vox[ii + r3]);
+}
+// The analytic derivative of the trilerp of those eight nodes inside the cell, per unit of node coordinate: along x the four edge
+// differences weighted bilinearly in (v, w), and so on - THIS IS THE TERM ORDER.  A cell on the last node plane of an axis (ii == i) has
+// a zero difference along it.
+VPT_VOLGRID_HD void vpt_volgrid_cell_gradient(const float n[8], const float uvw[3], float grad[3]) {
+  const float u = uvw[0], v = uvw[1], w = uvw[2];
+  grad[0] = ((n[1] - n[0]) * (1 - v) * (1 - w) + (n[6] - n[2]) * v * (1 - w)) + ((n[5] - n[3]) * (1 - v) * w + (n[7] - n[4]) * v * w);
+  grad[1] = ((n[2] - n[0]) * (1 - u) * (1 - w) + (n[6] - n[1]) * u * (1 - w)) + ((n[4] - n[3]) * (1 - u) * w + (n[7] - n[5]) * u * w);
+  grad[2] = ((n[3] - n[0]) * (1 - u) * (1 - v) + (n[5] - n[1]) * u * (1 - v)) + ((n[4] - n[2]) * (1 - u) * v + (n[7] - n[6]) * u * v);
+}
+// The world gradient of a grid instance's voxel value from the cell gradient: per axis times (whd - 1) / bbox (node coordinates per unit
+// of the box), then the transpose of the frame's rotation (local = frame * world), summed from the left
+VPT_VOLGRID_HD void vpt_volgrid_world_gradient(const vpt_volgrid_record& rec, const float cell_grad[3], float grad[3]) {
+  float gl[3];
+  for (int k = 0; k < 3; k++) gl[k] = cell_grad[k] * ((float)(rec.whd[k] - 1) / rec.bbox[k]);
+  const float* f = rec.frame;
+  grad[0] = (gl[0] * f[0] + gl[1] * f[1]) + gl[2] * f[2];
+  grad[1] = (gl[0] * f[3] + gl[1] * f[4]) + gl[2] * f[5];
+  grad[2] = (gl[0] * f[6] + gl[1] * f[7]) + gl[2] * f[8];
+}
+// n = -normalize(grad); a gradient of length 0, or one that is not finite (its length included), gives n = 0
+VPT_VOLGRID_HD void vpt_volgrid_normal_of(const float grad[3], float n[3]) {
+  const float len = sqrtf((grad[0] * grad[0] + grad[1] * grad[1]) + grad[2] * grad[2]);
+  const bool  ok  = len > 0.0f && len <= 3.402823466e+38f;   // NaN: not ok
+  for (int k = 0; k < 3; k++) n[k] = ok ? -(grad[k] / len) : 0.0f;
+}
+// The pass's normal of grid instance `rec` at a world point and the world gradient behind it (nullable): false, n = 0 and gradient 0
+// outside the box.  The eight voxels of the cell are fetched once
+VPT_VOLGRID_HD bool vpt_volgrid_normal(const vpt_volgrid_record& rec, const float* voxels, float px, float py, float pz, float n[3], float* grad_out) {
+  float node[3], grad[3] = {0.0f, 0.0f, 0.0f};
+  const bool inside = vpt_volgrid_locate(rec, px, py, pz, node);
+  if (inside) {
+    float cell[8], uvw[3], cg[3];
+    vpt_volgrid_cell(voxels + rec.voxel_offset, rec.whd[0], rec.whd[1], rec.whd[2], node[0], node[1], node[2], cell, uvw);
+    vpt_volgrid_cell_gradient(cell, uvw, cg);
+    vpt_volgrid_world_gradient(rec, cg, grad);
+  }
+  vpt_volgrid_normal_of(grad, n);
+  if (grad_out) grad_out[0] = grad[0], grad_out[1] = grad[1], grad_out[2] = grad[2];
+  return inside;
+}

@@ -59,4 +59,21 @@ int vpth_volgrid_density(const vpt_scene_desc* d, int n, const float* points, in
   return 0;
 }
 
+// the first-collision pass's normal of grid instance `instance` at n world points (vpt_volgrid_normal): gradient[3 i ..] the world
+// gradient of its voxel value, normal[3 i ..] = -normalize(gradient) or 0 (either nullable), inside[i] (nullable) whether the box holds the point
+int vpth_volgrid_gradient(const vpt_scene_desc* d, int instance, int n, const float* points, float* gradient, float* normal, int32_t* inside, char* err,
+    int err_len) {
+  if (!d || n < 0 || (n > 0 && !points)) return fail(err, err_len, "bad argument", 0, 0, 0);
+  if (instance < 0 || instance >= d->num_vol_instances) return fail(err, err_len, "vol_instance %d out of range (%d)", instance, d->num_vol_instances, 0);
+  const vpt_volume_instance& vi  = d->vol_instances[instance];
+  const vpt_volgrid_record   rec = vpt_volgrid_make_record(vi, d->volumes[vi.volume], d->materials[vi.material], 0);
+  for (int i = 0; i < n; i++) {
+    float      nrm[3];
+    const bool in = vpt_volgrid_normal(rec, d->voxels, points[3 * i], points[3 * i + 1], points[3 * i + 2], nrm, gradient ? gradient + 3 * (size_t)i : nullptr);
+    if (normal) normal[3 * i] = nrm[0], normal[3 * i + 1] = nrm[1], normal[3 * i + 2] = nrm[2];
+    if (inside) inside[i] = in;
+  }
+  return 0;
+}
+
 }  // extern "C"

@@ -986,6 +986,16 @@ class HostScene(_Handle):
         _host_call(host.vpth_volgrid_density, self.desc, len(points), points.ctypes.data, instance.ctypes.data, sigma.ctypes.data)
         return sigma, instance
 
+    def volgrid_gradient(self, instance: int, points):
+        """the normal the volgrid first-collision pass writes (include/vpt.h: vpt_render_volgrid_aov_device) for grid instance `instance`
+        at world points ((n, 3) float32), from the rule header the kernel compiles: (gradient, normal, inside) - the world gradient of the
+        instance's voxel value (cleaned nodes), -normalize(gradient) or 0, and whether the instance's box holds the point"""
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        gradient, normal, inside = np.zeros((len(points), 3), np.float32), np.zeros((len(points), 3), np.float32), np.zeros(len(points), np.int32)
+        _host_call(host.vpth_volgrid_gradient, self.desc, instance, len(points), points.ctypes.data, gradient.ctypes.data, normal.ctypes.data,
+                   inside.ctypes.data)
+        return gradient, normal, inside.astype(bool)
+
     def mesh_volume(self, index: int, iso: float = 0.0, origin=None, step=None, region=None, stats: Optional[dict] = None) -> dict:
         """the host mirror of DeviceScene.mesh_volume on the scene's copy of volume `index` (pending bakes run first, as for volume()):
         mesh_sdf(device=None) with bake_volume's defaults - origin 0, step = res * W / (W - 1) per axis"""

@@ -94,6 +94,26 @@ def pathtrace_guides(scene: HostScene, dev, params: PathtraceParams, samples: in
     return render("implicit_normal" if implicit else "normal"), None if implicit else render("color")
 
 
+def pathtrace_volgrid_aovs(scene: HostScene, dev: DeviceScene, params: PathtraceParams, samples: int = 16, planes=("opacity", "albedo", "depth", "normal")):
+    """what the volgrid shader's media show, for compositing: `samples` first-collision samples (DeviceScene.render_volgrid_aovs) over a
+    fresh make_state of `scene`.  Returns {name: (h, w, 4) float32}: opacity, albedo and normal as means over all samples (opacity is the
+    alpha of a volgrid render; albedo and normal are premultiplied by it), depth as {the mean collision distance over the samples that
+    collided (0 where none did), 0, 0, the colliding fraction}; ids / hit, if named, as the pass leaves them."""
+    p = PathtraceParams(params.camera, params.resolution, "volgrid", samples, params.bounces, params.noparallel, params.noimplicit_mis,
+                        params.spheretrace_maxiter)
+    st = scene.make_state(p)
+    out = dev.render_volgrid_aovs(st, p, samples, planes)
+    scale = np.float32(np.float32(1.0) / np.float32(st.samples))
+    for name in out:
+        if name in ("opacity", "albedo", "normal"):
+            out[name] = out[name] * scale
+        elif name == "depth":
+            d = out[name]
+            mean = np.divide(d[..., 0], d[..., 3], out=np.zeros_like(d[..., 0]), where=d[..., 3] > 0)
+            out[name] = np.stack([mean, np.zeros_like(mean), np.zeros_like(mean), d[..., 3] * scale], axis=-1)
+    return out
+
+
 def denoise_scratch_bytes(width: int, height: int) -> int:
     n = hip.vpt_denoise_scratch_bytes(width, height)
     if n < 0:

@@ -7,7 +7,7 @@ from typing import Optional
 import numpy as np
 
 from ._abi import (DENOISE_ITERATIONS, DENOISE_SIGMA_ALBEDO, DENOISE_SIGMA_LUMINANCE, DENOISE_SIGMA_NORMAL, VptAdaptive, VptDenoise, VptPick,
-                   VptError, VptSdf, VptSdfPick, VptSessionParams, _Handle, _check, _edit_call, _p, hip)
+                   VptError, VptSdf, VptSdfPick, VptSessionParams, VptVolgridPick, _Handle, _check, _edit_call, _p, hip)
 from .device import DeviceScene, DisplayParams, PathtraceParams, PathtraceState, _subdiv_edit_call
 from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, TextureEdit, VolumeEdit, VolumeSetEdit
 
@@ -139,10 +139,10 @@ class RenderSession(_Handle):
         region_margin voxels and clipped to the grid.  Then host.sculpt_volume, host.update_sculpts() and edit_sculpts: `host` is the
         HostScene the session's scene was made from.  Returns the entry it made.  The arithmetic of this helper carries no bit contract:
         the entry it makes goes to the host mirror and to the device alike."""
-        pick = self.pick_sdf(x, y)
+        pick = self.pick_volgrid(x, y) if self.params.shader == "volgrid" else self.pick_sdf(x, y)   # a medium: its first collision
         if pick is None:
             raise VptError(f"sculpt_at: the ray through pixel ({x}, {y}) hits nothing")
-        if pick["vol_instance"] < 0:
+        if pick["vol_instance"] < 0:   # (a volgrid pick always names a grid instance)
             raise VptError(f"sculpt_at: pixel ({x}, {y}) shows analytic SDF {pick['sdf']}, not a voxel grid")
         inst = host.volume_instance(pick["vol_instance"])
         to_grid = np.array([inst.frame.x[:], inst.frame.y[:], inst.frame.z[:], inst.frame.o[:]], np.float64)
@@ -298,6 +298,27 @@ class RenderSession(_Handle):
         w, h = self.size
         ids, hit = np.zeros((h, w, 2), np.int32), np.zeros((h, w, 4), np.float32)
         _check(hip.vpt_session_get_sdf_ids(self.handle, ids.ctypes.data, hit.ctypes.data), "vpt_session_get_sdf_ids")
+        return ids, hit
+
+    def pick_volgrid(self, x: int, y: int) -> Optional[dict]:
+        """what is under pixel (x, y) of a volgrid session's frame (vpt_session_pick_volgrid): None where none of the frame's flights
+        collided, else a dict of vol_instance, volume, material, distance, position, normal, density - the first collision of the pixel's
+        flights, the centre ray's where it has one.  48 bytes cross PCIe; the first pick_volgrid or volgrid_ids() after a reset makes the
+        id frame."""
+        out = VptVolgridPick()
+        _check(hip.vpt_session_pick_volgrid(self.handle, x, y, C.byref(out)), "vpt_session_pick_volgrid")
+        if not out.hit:
+            return None
+        pick = {name: getattr(out, name) for name in ("vol_instance", "volume", "material", "distance", "density")}
+        pick["position"], pick["normal"] = np.array(out.position[:], np.float32), np.array(out.normal[:], np.float32)
+        return pick
+
+    def volgrid_ids(self):
+        """the id frame of a volgrid session (vpt_session_get_volgrid_ids): (ids, hit) = (h, w, 2) int32 {vol_instance, volume} (-1, -1
+        where no flight collided) and (h, w, 4) float32 {position, t} of each pixel's first collision (zeros where none)"""
+        w, h = self.size
+        ids, hit = np.zeros((h, w, 2), np.int32), np.zeros((h, w, 4), np.float32)
+        _check(hip.vpt_session_get_volgrid_ids(self.handle, ids.ctypes.data, hit.ctypes.data), "vpt_session_get_volgrid_ids")
         return ids, hit
 
     def stats(self):
