@@ -538,6 +538,65 @@ typedef struct vpt_sculpt_edit {
 } vpt_sculpt_edit;
 int vpt_scene_sculpt_volumes(vpt_scene* scene, const vpt_sculpt_edit* edit);
 
+/* ---- filtering the voxel grids of a resident scene: remap, blur, noise --------------------------------------------------
+ * The fourth edit of the voxel pool, in the shape of the sculpt: an entry names a volume, a box of its voxels, the sample space of those
+ * voxels (the sculpt's: voxel (i, j, k) at origin + (float)i * step per axis) and a run of the edit's ops, applied in list order.  A baked
+ * or sculpted distance becomes a density, a density is softened or broken up, where the voxels live: no voxel crosses PCIe in either
+ * direction.  whd and res never change, so no record, no light table and no pool layout is touched: only the voxels inside each entry's
+ * region change, every other voxel of the pool keeps its bits.  Entries run in order on one stream, and a volume id may repeat.
+ * The rule, written once in csrc/vpt_filter_rule.h (compiled by the kernels and by the host mirror, host/vpt_filter.cpp, both with
+ * -ffp-contract=off: float32, nothing fused, every sum in the order that header writes, division the IEEE operation; no libm function
+ * but floorf, which is exact):
+ *  - VPT_FILTER_REMAP, p = {divisor, scale, offset, lo, hi}:  t = v / divisor; t = t * scale; t = t + offset; t = t > lo ? t : lo;
+ *    t = t < hi ? t : hi.  The clamps are selects: a NaN voxel becomes lo.  density_from_sdf(v, width) of the Python package is
+ *    {width, -1, 0, 0, 1} (as numbers; the sign of a zero and the fate of a NaN are this rule's).
+ *  - VPT_FILTER_BLUR, count = the radius R (1..VPT_FILTER_MAX_RADIUS nodes), p[0..R] = the weights w.  The weights are part of the op:
+ *    device and mirror read the same bits (libvpt_host.so's vpth_filter_gaussian_weights makes them from a sigma: exp(-i^2 / (2 sigma^2))
+ *    in float64, normalised so that w0 + 2 sum wi = 1, rounded to float32).  Separable, x then y then z; one pass at a node is
+ *    s = w[0] * c; for i = 1..R: s = s + w[i] * (a[-i] + a[+i]), the indices clamped to the VOLUME's [0, W - 1] (clamp to the edge of
+ *    the volume, not of the region).  The x pass reads the volume as it was before the op, the y pass x-pass results, the z pass y-pass
+ *    results - each exists wherever a later pass needs it, also outside the region.  NaN and Inf propagate as the arithmetic gives; a
+ *    pass's result that is a NaN is stored as the quiet NaN 0x7fc00000 (so is a NOISE op's): which NaN an operation returns is the
+ *    processor's choice, that it returns one is not.
+ *  - VPT_FILTER_NOISE, p = {gain, frequency x, y, z, persistence}, count = octaves (1..VPT_FILTER_MAX_OCTAVES), seed:
+ *    v' = v + gain * (fbm(q) - 0.5f), q = sample * frequency per axis;  fbm: sum = 0, a = 1, per octave o: sum = sum + a * vnoise(q, seed + o);
+ *    q = q * 2; a = a * persistence.  vnoise is lattice value noise: cell = floorf(x), f = x - cell, fade (f * f) * (3.0f - 2.0f * f), the
+ *    eight lattice values combined in the term order of the volgrid shader's trilerp (csrc/vpt_volgrid_rule.h), a lattice value
+ *    (hash >> 8) * 2^-24 of the 32-bit integer hash the header writes out (multiplies, xors and shifts).
+ *  - Runs.  Consecutive pointwise ops (REMAP, NOISE) of an entry are ONE launch that reads and writes each voxel of the region once; a
+ *    BLUR is a launch of its own into a scratch buffer the handle keeps and grows, followed by the launch that moves the scratch into
+ *    place (the scratch is what makes "as it was before the op" true across workgroups).  A list of N ops equals N one-op edits bit for bit.
+ *  - Validation before anything is written (VPT_ERR_INVALID_ARG, the message names the entry or the op, the scene is untouched): the
+ *    volume id in range; the region inside the resident whd; the op range inside the edit's list; type 0..2; every float the op reads and
+ *    origin and step finite; divisor != 0; lo <= hi; R in 1..4; octaves in 1..8; a NOISE op whose |q| can reach 2^22 at its last octave over
+ *    the entry's region.  An entry of more than 2^30 region voxels is refused with VPT_ERR_UNSUPPORTED.
+ *  - An entry with an empty region or no ops launches nothing.  vpt_scene_update_stats afterwards: launches = one per run of pointwise ops
+ *    + two per BLUR; bytes = VPT_FILTER_RECORD_BYTES per op of the edit's list, uploaded in one copy when anything is launched (0
+ *    otherwise) - not one voxel.  An edit without entries starts the counters again at (0, 0).
+ *  - Synchronisation, the VPT_ERR_HIP semantics and the forgetting of the launch-schedule record: those of vpt_scene_update.  The volgrid
+ *    shader's brick majorants follow as after every voxel edit. */
+enum { VPT_FILTER_REMAP = 0, VPT_FILTER_BLUR = 1, VPT_FILTER_NOISE = 2 };
+#define VPT_FILTER_MAX_RADIUS 4
+#define VPT_FILTER_MAX_OCTAVES 8
+#define VPT_FILTER_RECORD_BYTES 48   /* one op as the device reads it: type, count, seed, eight parameters */
+typedef struct vpt_filter_op {
+  int32_t  type;    /* VPT_FILTER_* */
+  int32_t  count;   /* BLUR: the radius R; NOISE: the octaves; REMAP: unused */
+  uint32_t seed;    /* NOISE */
+  float    p[8];    /* REMAP {divisor, scale, offset, lo, hi}; BLUR w[0..R]; NOISE {gain, frequency[3], persistence} */
+} vpt_filter_op;
+typedef struct vpt_filter_entry {
+  int32_t volume;
+  int32_t region_lo[3], region_whd[3];  /* the box of voxels this entry changes */
+  float   origin[3], step[3];           /* voxel (i, j, k) is sampled at origin + (i, j, k) * step */
+  int32_t first_op, num_ops;            /* its run inside edit->ops */
+} vpt_filter_entry;
+typedef struct vpt_filter_edit {
+  int32_t num_entries; const vpt_filter_entry* entries;
+  int32_t num_ops;     const vpt_filter_op* ops;
+} vpt_filter_edit;
+int vpt_scene_filter_volumes(vpt_scene* scene, const vpt_filter_edit* edit);
+
 /* ---- adding and removing volumes, grid instances and SDFs -------------------------------------------------------------
  * The one thing vpt_scene_update_volumes leaves fixed: how many there are.  An edit of its own, because vpt_volume_edit keeps its layout;
  * the contract is that of vpt_scene_update_instances and vpt_scene_update_shapes.  After vpt_scene_update_volume_set(s, edit) every table
@@ -989,6 +1048,8 @@ int  vpt_multi_update_textures(vpt_multi* m, const vpt_texture_edit* edit);
 int  vpt_multi_update_volumes(vpt_multi* m, const vpt_volume_edit* edit);
 /* vpt_scene_sculpt_volumes in the same way: the same stamps run on every device */
 int  vpt_multi_sculpt_volumes(vpt_multi* m, const vpt_sculpt_edit* edit);
+/* vpt_scene_filter_volumes in the same way: the same ops run on every device */
+int  vpt_multi_filter_volumes(vpt_multi* m, const vpt_filter_edit* edit);
 /* vpt_scene_update_volume_set in the same way (a FROM_BAKE entry is prepared and baked once per device) */
 int  vpt_multi_update_volume_set(vpt_multi* m, const vpt_volume_set_edit* edit);
 /* vpt_scene_rebuild_bvh in the same way: every device builds its own trees; the arrays are equal by construction */
@@ -1432,6 +1493,8 @@ int  vpt_session_edit_textures(vpt_session* session, const vpt_texture_edit* edi
 int  vpt_session_edit_volumes(vpt_session* session, const vpt_volume_edit* edit);
 /* vpt_scene_sculpt_volumes, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_sculpt_volumes(vpt_session* session, const vpt_sculpt_edit* edit);
+/* vpt_scene_filter_volumes, then a reset; a refused edit leaves the session as it was */
+int  vpt_session_filter_volumes(vpt_session* session, const vpt_filter_edit* edit);
 /* vpt_scene_update_volume_set, then a reset (which drops both id frames: pick_sdf never names an entry that is gone); a refused edit
  * leaves the session as it was */
 int  vpt_session_edit_volume_set(vpt_session* session, const vpt_volume_set_edit* edit);

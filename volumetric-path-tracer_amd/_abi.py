@@ -191,6 +191,22 @@ class VptSculptEdit(C.Structure):  # vpt_sculpt_edit
 assert C.sizeof(VptSculptStamp) == 92 and C.sizeof(VptSculptEntry) == 60 and C.sizeof(VptSculptEdit) == 32
 
 
+class VptFilterOp(C.Structure):  # vpt_filter_op
+    _fields_ = [("type", C.c_int32), ("count", C.c_int32), ("seed", C.c_uint32), ("p", C.c_float * 8)]
+
+
+class VptFilterEntry(C.Structure):  # vpt_filter_entry
+    _fields_ = [("volume", C.c_int32), ("region_lo", C.c_int32 * 3), ("region_whd", C.c_int32 * 3), ("origin", C.c_float * 3), ("step", C.c_float * 3),
+                ("first_op", C.c_int32), ("num_ops", C.c_int32)]
+
+
+class VptFilterEdit(C.Structure):  # vpt_filter_edit
+    _fields_ = [("num_entries", C.c_int32), ("entries", C.c_void_p), ("num_ops", C.c_int32), ("ops", C.c_void_p)]
+
+
+assert C.sizeof(VptFilterOp) == 44 and C.sizeof(VptFilterEntry) == 60 and C.sizeof(VptFilterEdit) == 32
+
+
 class VptVolumeNew(C.Structure):  # vpt_volume_new
     _fields_ = [("whd", C.c_int32 * 3), ("res", C.c_float), ("source", C.c_int32), ("offset", C.c_int64), ("bake", C.c_void_p), ("fill", C.c_float),
                 ("copy_of", C.c_int32)]
@@ -210,6 +226,9 @@ VOXELS_REPLACE, VOXELS_UNION = 0, 1
 SCULPT_REPLACE, SCULPT_UNION, SCULPT_SUBTRACT, SCULPT_INTERSECT = 0, 1, 2, 3
 VOLUME_FROM_HOST, VOLUME_FROM_BAKE, VOLUME_FILL, VOLUME_COPY = 0, 1, 2, 3   # vpt_volume_new::source
 SCULPT_RECORD_BYTES = 80   # VPT_SCULPT_RECORD_BYTES: one stamp as the device reads it
+FILTER_REMAP, FILTER_BLUR, FILTER_NOISE = 0, 1, 2
+FILTER_MAX_RADIUS, FILTER_MAX_OCTAVES = 4, 8
+FILTER_RECORD_BYTES = 48   # VPT_FILTER_RECORD_BYTES: one op as the device reads it
 MATERIAL_TYPES = ["matte", "glossy", "reflective", "transparent", "refractive", "subsurface", "volumetric", "gltfpbr"]
 
 
@@ -319,6 +338,9 @@ hip.vpt_session_edit_volumes.argtypes = [_p, C.POINTER(VptVolumeEdit)]
 hip.vpt_scene_sculpt_volumes.argtypes = [_p, C.POINTER(VptSculptEdit)]
 hip.vpt_multi_sculpt_volumes.argtypes = [_p, C.POINTER(VptSculptEdit)]
 hip.vpt_session_sculpt_volumes.argtypes = [_p, C.POINTER(VptSculptEdit)]
+hip.vpt_scene_filter_volumes.argtypes = [_p, C.POINTER(VptFilterEdit)]
+hip.vpt_multi_filter_volumes.argtypes = [_p, C.POINTER(VptFilterEdit)]
+hip.vpt_session_filter_volumes.argtypes = [_p, C.POINTER(VptFilterEdit)]
 hip.vpt_scene_update_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
 hip.vpt_multi_update_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
 hip.vpt_session_edit_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
@@ -497,6 +519,9 @@ host.vpth_scene_edit_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit), C.c
 host.vpth_scene_sculpt_volume.argtypes = [_p, C.POINTER(VptSculptEntry), _p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_sculpt_eval.argtypes = [C.POINTER(VptSdf), _p, C.c_int, _p]
 host.vpth_sculpt_combine.argtypes = [C.c_int, C.c_float, _p, _p, C.c_int, _p]
+host.vpth_scene_filter_volume.argtypes = [_p, C.POINTER(VptFilterEntry), _p, C.c_int, C.c_char_p, C.c_int]
+host.vpth_filter_voxels.argtypes = [_p, _p, C.POINTER(VptFilterEntry), _p, C.c_int, C.c_char_p, C.c_int]
+host.vpth_filter_gaussian_weights.argtypes = [C.c_float, C.c_int, _p]
 host.vpth_scene_desc.argtypes = [_p]
 host.vpth_scene_desc.restype = _p
 host.vpth_scene_curves.argtypes = [_p]

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "vpt_bvh_rebuild.h"
+#include "vpt_filter.h"
 #include "vpt_instance_update.h"
 #include "vpt_light_update.h"
 #include "vpt_scene_handle.h"
@@ -171,6 +172,7 @@ template <typename Edit> static bool moves_geometry(const Edit&) { return false;
 template <typename Edit> static bool writes_materials(const Edit&) { return false; }
 static bool writes_voxels(const vpt_volume_edit&) { return true; }   // voxels in place, baked into the pool, or moved into a grown pool
 static bool writes_voxels(const vpt_sculpt_edit&) { return true; }
+static bool writes_voxels(const vpt_filter_edit&) { return true; }
 static bool writes_voxels(const vpt_volume_set_edit&) { return true; }   // a pool laid out anew, volumes under other ids: the brick tables are indexed by volume
 template <typename Edit> static bool writes_voxels(const Edit&) { return false; }
 
@@ -217,6 +219,8 @@ int vpt_scene_update_textures(vpt_scene* s, const vpt_texture_edit* edit) { retu
 int vpt_scene_update_volumes(vpt_scene* s, const vpt_volume_edit* edit) { return edit_scene(s, edit, volume_update_apply); }
 // voxels alone, from analytic brushes evaluated where they live (vpt_sculpt.hip)
 int vpt_scene_sculpt_volumes(vpt_scene* s, const vpt_sculpt_edit* edit) { return edit_scene(s, edit, sculpt_apply); }
+// voxels alone again, remapped, blurred and broken up with noise where they live (vpt_filter.hip)
+int vpt_scene_filter_volumes(vpt_scene* s, const vpt_filter_edit* edit) { return edit_scene(s, edit, filter_apply); }
 // volumes, grid instances and SDFs added and removed (vpt_volume_set.hip): the pool compacted by one gather, the lights following the SDFs
 int vpt_scene_update_volume_set(vpt_scene* s, const vpt_volume_set_edit* edit) { return edit_scene(s, edit, volume_set_apply); }
 // the BVHs built anew (vpt_bvh_rebuild.hip), the set of instances changed (vpt_instance_update.hip), the shape list changed (vpt_shape_update.hip)

@@ -11,7 +11,7 @@ import numpy as np
 from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SDF_AOV_PLANES, SHADER_NAMES, VOLGRID_AOV_PLANES, VptAdaptive, VptAovPlanes, VptSdfAovPlanes,
                    VptVolgridAovPlanes, VptDisplay, VptError, VptLayout, VptParams,
                    VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, shader_id, _counted, _edit_call, _mesh_desc, _mesh_region, _meshed, _p, hip, host)
-from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, VolumeSetEdit, mesh
+from .edits import BvhRebuild, FilterEdit, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, VolumeSetEdit, mesh
 
 if TYPE_CHECKING:
     from .host_scene import HostScene
@@ -295,6 +295,11 @@ class DeviceScene(_Handle):
         """vpt_scene_sculpt_volumes (include/vpt.h): strokes of analytic brushes evaluated on the device over boxes of the resident voxels -
         a few hundred bytes cross PCIe, not one voxel.  edit: what HostScene.update_sculpts() returns."""
         _edit_call(self.handle, "vpt_scene_sculpt_volumes", edit)
+
+    def filter_volumes(self, edit: FilterEdit) -> None:
+        """vpt_scene_filter_volumes (include/vpt.h): remaps, blurs and noise run on the device over boxes of the resident voxels - 48 bytes
+        per op cross PCIe, not one voxel.  edit: what HostScene.update_filters() returns."""
+        _edit_call(self.handle, "vpt_scene_filter_volumes", edit)
 
     def get_volumes(self):
         """(volumes, vol_instances, sdfs) as the device holds them, ctypes arrays of VptVolume, VptVolumeInstance, VptSdf
@@ -625,6 +630,10 @@ class MultiDeviceScene(_Handle):
     def sculpt_volumes(self, edit: SculptEdit) -> None:
         """vpt_multi_sculpt_volumes: DeviceScene.sculpt_volumes with the same edit on every device"""
         _edit_call(self.handle, "vpt_multi_sculpt_volumes", edit)
+
+    def filter_volumes(self, edit: FilterEdit) -> None:
+        """vpt_multi_filter_volumes: DeviceScene.filter_volumes with the same edit on every device"""
+        _edit_call(self.handle, "vpt_multi_filter_volumes", edit)
 
     def rebuild_bvh(self, rebuild: "BvhRebuild") -> None:
         """vpt_multi_rebuild_bvh: DeviceScene.rebuild_bvh on every device (each builds its own trees: equal by construction)"""

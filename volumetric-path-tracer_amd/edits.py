@@ -9,7 +9,8 @@ from typing import Optional
 
 import numpy as np
 
-from ._abi import (INSTANCE, MESH_ELEMENTS, MESH_FLOATS, SCULPT_RECORD_BYTES, VOXELS_REPLACE, VptBakeDesc, VptBvhRebuild, VptCamera, VptEnvironment,
+from ._abi import (FILTER_BLUR, FILTER_MAX_RADIUS, FILTER_NOISE, FILTER_RECORD_BYTES, FILTER_REMAP, INSTANCE, MESH_ELEMENTS, MESH_FLOATS, SCULPT_RECORD_BYTES,
+                   VOXELS_REPLACE, VptFilterEdit, VptFilterEntry, VptFilterOp, host, VptBakeDesc, VptBvhRebuild, VptCamera, VptEnvironment,
                    VptError, VptInstanceEdit, VptMaterial, VptSceneEdit, VptSculptEdit, VptSculptEntry, VptSculptStamp, VptSdf, VptShapeData, VptShapeEdit,
                    VptSubdivEdit, VptSubdivLevel, VptSubdivPlan, VptTexture, VptTextureEdit, VptVolumeEdit, VptVolumeInstance, VptVolumeNew, VptVolumeSetEdit,
                    VptVolumeSource, VOLUME_FILL, VOLUME_FROM_BAKE, VOLUME_FROM_HOST, _address)
@@ -481,3 +482,88 @@ class SculptEdit:
                 first += 1
         abi = VptSculptEdit(len(self.entries), C.addressof(entries) if self.entries else None, count, C.addressof(stamps) if count else None)
         return abi, [entries, stamps]
+
+
+# ---- filtering: remap, blur and noise over boxes of voxels --------------------------------------------------------------------------------
+@dataclass
+class FilterOp:
+    """One op of a filter (include/vpt.h: vpt_filter_op).  Made by the constructors below: remap, to_density, blur, noise."""
+    type: int
+    count: int = 0
+    seed: int = 0
+    p: tuple = ()
+
+    @staticmethod
+    def remap(divisor: float, scale: float, offset: float, lo: float, hi: float) -> "FilterOp":
+        """t = v / divisor; t = t * scale; t = t + offset, then clamped to [lo, hi] by selects (a NaN voxel becomes lo)"""
+        return FilterOp(FILTER_REMAP, p=(divisor, scale, offset, lo, hi))
+
+    @staticmethod
+    def to_density(width: float) -> "FilterOp":
+        """density_from_sdf(v, width) as a remap: 1 from `width` inside the surface on, 0 outside it"""
+        return FilterOp.remap(width, -1.0, 0.0, 0.0, 1.0)
+
+    @staticmethod
+    def blur(sigma: float, radius: int) -> "FilterOp":
+        """a separable Gaussian blur of `radius` nodes (1..FILTER_MAX_RADIUS); the weights are made by the host library from `sigma`"""
+        w = np.zeros(FILTER_MAX_RADIUS + 1, np.float32)
+        if host.vpth_filter_gaussian_weights(float(sigma), int(radius), w.ctypes.data) != 0:
+            raise VptError(f"FilterOp.blur: sigma {sigma!r} must be finite and > 0, radius {radius!r} one of 1..{FILTER_MAX_RADIUS}")
+        return FilterOp(FILTER_BLUR, count=int(radius), p=tuple(float(v) for v in w[:int(radius) + 1]))
+
+    @staticmethod
+    def noise(gain: float, frequency, persistence: float = 0.5, octaves: int = 4, seed: int = 0) -> "FilterOp":
+        """v + gain * (fbm(sample * frequency) - 0.5): fractal lattice value noise of `octaves` (1..FILTER_MAX_OCTAVES); frequency: three
+        floats, or one for every axis"""
+        f = tuple(float(v) for v in np.broadcast_to(np.asarray(frequency, np.float32), (3,)))
+        return FilterOp(FILTER_NOISE, count=int(octaves), seed=int(seed) & 0xffffffff, p=(gain, *f, persistence))
+
+    def to_abi(self) -> VptFilterOp:
+        out = VptFilterOp(type=int(self.type), count=int(self.count), seed=int(self.seed))
+        out.p[:len(self.p)] = [float(v) for v in self.p]
+        return out
+
+
+@dataclass
+class FilterEntry:
+    """One entry of a FilterEdit (include/vpt.h: vpt_filter_entry): the volume, the box region_lo .. region_lo + region_whd of its voxels
+    (each (x, y, z)), the grid they are sampled on - voxel (i, j, k) at origin + (i, j, k) * step - and the FilterOps, applied in order."""
+    volume: int
+    region_lo: tuple
+    region_whd: tuple
+    origin: tuple
+    step: tuple
+    ops: list
+
+
+class FilterEdit:
+    """What vpt_scene_filter_volumes takes (include/vpt.h: vpt_filter_edit): a list of FilterEntry, applied in order; a volume may be
+    named more than once.  HostScene.filter_volume fills one, update_filters() hands it out; DeviceScene.filter_volumes /
+    MultiDeviceScene.filter_volumes / RenderSession.edit_filters apply it."""
+
+    def __init__(self, entries=()):
+        self.entries = list(entries)
+
+    def empty(self) -> bool:
+        return not self.entries
+
+    def payload_bytes(self) -> int:
+        """bytes of the edit itself as vpt_scene_update_stats counts them: FILTER_RECORD_BYTES per op when anything is launched"""
+        launched = any(len(e.ops) and all(int(v) > 0 for v in e.region_whd) for e in self.entries)
+        return FILTER_RECORD_BYTES * sum(len(e.ops) for e in self.entries) if launched else 0
+
+    def to_abi(self):
+        """(VptFilterEdit, the arrays it points into: keep them alive across the call)"""
+        count = sum(len(e.ops) for e in self.entries)
+        entries, ops = (VptFilterEntry * max(1, len(self.entries)))(), (VptFilterOp * max(1, count))()
+        first = 0
+        for rec, e in zip(entries, self.entries):
+            rec.volume, rec.first_op, rec.num_ops = int(e.volume), first, len(e.ops)
+            rec.region_lo[:], rec.region_whd[:] = [int(v) for v in e.region_lo], [int(v) for v in e.region_whd]
+            rec.origin[:] = [float(v) for v in np.broadcast_to(np.asarray(e.origin, np.float32), (3,))]
+            rec.step[:] = [float(v) for v in np.broadcast_to(np.asarray(e.step, np.float32), (3,))]
+            for op in e.ops:
+                ops[first] = op.to_abi()
+                first += 1
+        abi = VptFilterEdit(len(self.entries), C.addressof(entries) if self.entries else None, count, C.addressof(ops) if count else None)
+        return abi, [entries, ops]

@@ -442,6 +442,15 @@ bool save_volume(const string& filename, const volume_data& vol, string& error);
 // words (false, `error` set, the volume untouched); entry.volume is the caller's to resolve.
 bool sculpt_volume(volume_data& volume, const vpt_sculpt_entry& entry, const vpt_sculpt_stamp* stamps, int num_stamps, string& error);
 
+// ---- filtering a voxel grid: remap, blur, noise (include/vpt.h: vpt_scene_filter_volumes; host/vpt_filter.cpp) ----------------------
+// the host mirror of one entry on a host array of whd voxels (x fastest): the rule header (csrc/vpt_filter_rule.h) in plain loops over the
+// entry's region, its ops taken from `ops` (the edit's list of `num_ops`) in order - the same bits as the device.  Refuses what the C-ABI
+// refuses, in its words (false, `error` set, the voxels untouched); entry.volume is the caller's to resolve.
+bool filter_voxels(float* voxels, const int32_t whd[3], const vpt_filter_entry& entry, const vpt_filter_op* ops, int num_ops, string& error);
+// w[0..radius] of a BLUR op from a sigma: exp(-i^2 / (2 sigma^2)) in float64, normalised so that w0 + 2 sum wi = 1, rounded to float32;
+// false for a sigma that is not finite and > 0 or a radius outside 1..VPT_FILTER_MAX_RADIUS
+bool filter_gaussian_weights(float sigma, int radius, float* weights);
+
 // ---- a quad mesh out of a signed-distance voxel grid (include/vpt.h: vpt_mesh_sdf; host/vpt_sdf_mesh.cpp) ---------------------------
 struct sdf_mesh {
   vector<vec3f> positions = {}, normals = {};

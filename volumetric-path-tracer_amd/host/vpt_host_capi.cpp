@@ -633,6 +633,20 @@ int vpth_scene_sculpt_volume(void* hh, const vpt_sculpt_entry* entry, const vpt_
   if (!sculpt_volume(sc.volumes[entry->volume], *entry, stamps, num_stamps, error)) return set_error(err, errlen, error), -1;
   return 0;
 }
+// One entry of a vpt_filter_edit applied to the scene's copy of volume entry->volume by the host mirror (host/vpt_filter.cpp), its ops taken
+// from `ops` (the edit's list of `num_ops`).  The rules of vpt_scene_filter_volumes; a refused call writes nothing.
+int vpth_scene_filter_volume(void* hh, const vpt_filter_entry* entry, const vpt_filter_op* ops, int num_ops, char* err, int errlen) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (!entry) return set_error(err, errlen, "filter: null entry"), -1;
+  if (entry->volume < 0 || entry->volume >= (int)sc.volumes.size())
+    return set_error(err, errlen, "filter: entry 0: volume " + std::to_string(entry->volume) + " out of range (" + std::to_string(sc.volumes.size()) + ")"), -1;
+  auto&         v      = sc.volumes[entry->volume];
+  const int32_t whd[3] = {v.whd.x, v.whd.y, v.whd.z};
+  if (v.vol.size() < (size_t)whd[0] * (size_t)whd[1] * (size_t)whd[2]) return set_error(err, errlen, "filter: entry 0: the volume holds fewer voxels than its whd"), -1;
+  auto error = string{};
+  if (!filter_voxels(v.vol.data(), whd, *entry, ops, num_ops, error)) return set_error(err, errlen, error), -1;
+  return 0;
+}
 // make_lights of the scene as the setters above left it (an SDF is a light iff its material is emissive), then the flattened descriptor again
 int vpth_scene_update_volumes(void* hh, char* err, int errlen) { return vpth_scene_update_lights(hh, err, errlen); }
 // The host side of vpt_scene_update_volume_set (include/vpt.h) under its rules: the removed entries of the three lists erased (current

@@ -10,10 +10,10 @@ from typing import Optional
 import numpy as np
 
 from ._abi import (BVH_MIDDLE, BVH_NODE, BVH_SAH, LIGHT, MESH_ELEMENTS, MESH_FLOATS, SDF_TYPES, VOLUME_COPY, VOLUME_FILL, VOLUME_FROM_BAKE, VOLUME_FROM_HOST, VOXELS_REPLACE, VptBakeStats, VptCamera,
-                   VptEnvironment, VptError, VptMaterial, VptSceneDescBvh, VptSceneDescLights, VptSculptEntry, VptSdf, VptVolumeInstance, _Handle,
+                   VptEnvironment, VptError, VptMaterial, VptSceneDescBvh, VptFilterEntry, VptSceneDescLights, VptSculptEntry, VptSdf, VptVolumeInstance, _Handle,
                    _check, _filled, _host_call, _mesh_desc, _mesh_region, _meshed, hip, host)
 from .device import PathtraceParams, PathtraceState
-from .edits import (LEVEL_TABLES, BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan,
+from .edits import (LEVEL_TABLES, BvhRebuild, FilterEdit, FilterEntry, FilterOp, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan,
                     TextureEdit, VolumeEdit, VolumeNew, VolumeSetEdit, VolumeSource, mesh)
 
 
@@ -214,19 +214,19 @@ def save_mesh_ply(path: str, positions, quads, normals=None) -> None:
 #   environment frames name lists nothing renumbers); "instances" / "shapes": an InstanceEdit / ShapeEdit that holds anything;
 #   "subdivs": a SubdivEdit that holds anything (its shapes wait for update_bvh like moved vertices).
 # Texture and volume edits name lists of their own and wait for nothing of the above; set_camera, set_material, set_environment_frame are
-# never refused.  The implicit side has the same rule within itself: "volumes": a VolumeEdit or SculptEdit that holds anything - their ids
+# never refused.  The implicit side has the same rule within itself: "volumes": a VolumeEdit, SculptEdit or FilterEdit that holds anything - their ids
 # name the volumes, grid instances and SDFs as they are - and "volume_set": a VolumeSetEdit that holds anything, which renumbers all three.
-# A volume's voxels have two ledgers, the VolumeEdit and the SculptEdit: a volume pending in one is refused by the setters of the other
-# (_note_volume, sculpt_volume), since each ledger is applied to the device as a whole and in its own call.
+# A volume's voxels have three ledgers, the VolumeEdit, the SculptEdit and the FilterEdit: a volume pending in one is refused by the setters
+# of the others (_note_volume, sculpt_volume, filter_volume), since each ledger is applied to the device as a whole and in its own call.
 _REFUSED_WHILE = {"vertices": ("instances", "shapes"),                       # set_instance_frame, set_shape_positions, set_subdiv (cage, displacement)
                   "rebuild": ("edit", "subdivs", "instances", "shapes"),      # rebuild_bvh
                   "instances": ("geometry", "subdivs", "shapes"),             # add_instance, remove_instances, set_instance, update_instances
                   "shapes": ("geometry", "subdivs", "instances"),             # add_shape, set_shape, remove_shapes, update_shapes, set_subdiv (level, smooth)
-                  "volume_entries": ("volume_set",),                          # set_volume_instance, set_sdf, set_volume, bake_volume, sculpt_volume
+                  "volume_entries": ("volume_set",),                          # set_volume_instance, set_sdf, set_volume, bake_volume, sculpt_volume, filter_volume
                   "volume_set": ("volumes",)}                                 # add_volume, remove_volumes, add_volume_instance, ..., update_volume_set
 _HAND_OUT = {"edit": "edit out with update_bvh()", "geometry": "edit out with update_bvh()",
              "instances": "instance changes out with update_instances()", "shapes": "shape changes out with update_shapes()",
-             "subdivs": "subdiv changes out with update_subdivs()", "volumes": "volume changes out with update_volumes() / update_sculpts()",
+             "subdivs": "subdiv changes out with update_subdivs()", "volumes": "volume changes out with update_volumes() / update_sculpts() / update_filters()",
              "volume_set": "additions and removals of volumes, grid instances and SDFs out with update_volume_set()"}
 
 
@@ -243,7 +243,7 @@ class HostScene(_Handle):
         # the pending edits: what the setters noted since the matching update_*() handed the last one out
         self._edit, self._inst_edit, self._shape_edit = SceneEdit(), InstanceEdit(), ShapeEdit()
         self._texture_edit, self._volume_edit, self._subdiv_edit = TextureEdit(), VolumeEdit(), SubdivEdit()
-        self._sculpt_edit, self._volume_set_edit = SculptEdit(), VolumeSetEdit()
+        self._sculpt_edit, self._volume_set_edit, self._filter_edit = SculptEdit(), VolumeSetEdit(), FilterEdit()
         self._lazy_bakes = []   # (volume, VolumeSource) of bake_volume whose host copy is not baked yet
         self.handle = _host_call(host.vpth_scene_load_ex, os.fsencode(filename), -1 if tess_device is None else tess_device, size=1024, handle=True)
         self.filename = filename
@@ -295,7 +295,7 @@ class HostScene(_Handle):
         """VptError unless a call of `kind` (_REFUSED_WHILE) may go ahead: the message names the update_*() to call first"""
         pending = {"edit": not self._edit.empty(), "geometry": bool(self._edit.instances or self._edit.shapes),
                    "instances": not self._inst_edit.empty(), "shapes": not self._shape_edit.empty(), "subdivs": not self._subdiv_edit.empty(),
-                   "volumes": not (self._volume_edit.empty() and self._sculpt_edit.empty()), "volume_set": not self._volume_set_edit.empty()}
+                   "volumes": not (self._volume_edit.empty() and self._sculpt_edit.empty() and self._filter_edit.empty()), "volume_set": not self._volume_set_edit.empty()}
         for blocker in _REFUSED_WHILE[kind]:
             if pending[blocker]:
                 raise VptError(f"{what}: hand the pending {_HAND_OUT[blocker]} first" + (why if blocker == "geometry" else ""))
@@ -731,6 +731,8 @@ class HostScene(_Handle):
             raise VptError(f"volume {index} is already in the pending edit: hand it out with update_volumes() first")
         if any(e.volume == index for e in self._sculpt_edit.entries):
             raise VptError(f"volume {index} has sculpts pending: hand them out with update_sculpts() first")
+        if any(e.volume == index for e in self._filter_edit.entries):
+            raise VptError(f"volume {index} has filters pending: hand them out with update_filters() first")
         self._volume_edit.volumes[index] = src
 
     def set_volume(self, index: int, voxels, res: Optional[float] = None, region=None, mode: int = VOXELS_REPLACE) -> None:
@@ -946,6 +948,8 @@ class HostScene(_Handle):
         self._may("sculpt_volume", "volume_entries")
         if index in self._volume_edit.volumes:
             raise VptError(f"sculpt_volume: volume {index} is in the pending volume edit: hand it out with update_volumes() first")
+        if any(e.volume == index for e in self._filter_edit.entries):
+            raise VptError(f"sculpt_volume: volume {index} has filters pending: hand them out with update_filters() first")
         old, res = self.volume(index)
         whd = old.shape[::-1]
         if origin is None:
@@ -968,6 +972,40 @@ class HostScene(_Handle):
         SculptEdit for DeviceScene.sculpt_volumes."""
         _host_call(host.vpth_scene_update_volumes, self.handle)
         edit, self._sculpt_edit = self._sculpt_edit, SculptEdit()
+        return edit
+
+    # -- filtering (the host side of vpt_scene_filter_volumes): filter_volume applies the ops to the scene's copy through the host mirror
+    #    at once and notes them in the pending FilterEdit, which update_filters() hands out ---------------------------------------------
+    def filter_volume(self, index: int, ops, region=None, origin=None, step=None) -> FilterEntry:
+        """FilterOps in order over the voxels of volume `index` by the rule of vpt_scene_filter_volumes.  region None: the whole grid, else
+        (lo, whd), each (x, y, z); origin / step None: bake_volume's defaults (what a NOISE op samples).  Returns the entry it noted.  A
+        refused call changes nothing."""
+        index = int(index)
+        self._may("filter_volume", "volume_entries")
+        if index in self._volume_edit.volumes:
+            raise VptError(f"filter_volume: volume {index} is in the pending volume edit: hand it out with update_volumes() first")
+        if any(e.volume == index for e in self._sculpt_edit.entries):
+            raise VptError(f"filter_volume: volume {index} has sculpts pending: hand them out with update_sculpts() first")
+        whd, res = self._volume_shape(index)
+        if origin is None:
+            origin = np.zeros(3, np.float32)
+        if step is None:
+            step = np.array([np.float32(res) * np.float32(w) / np.float32(max(1, w - 1)) for w in whd], np.float32)
+        lo, size = ((0, 0, 0), whd) if region is None else region
+        entry = FilterEntry(index, tuple(int(v) for v in lo), tuple(int(v) for v in size),
+                            tuple(float(v) for v in np.broadcast_to(np.asarray(origin, np.float32), (3,))),
+                            tuple(float(v) for v in np.broadcast_to(np.asarray(step, np.float32), (3,))), list(ops))
+        abi, keep = FilterEdit([entry]).to_abi()
+        _host_call(host.vpth_scene_filter_volume, self.handle, C.cast(abi.entries, C.POINTER(VptFilterEntry)), abi.ops, abi.num_ops)
+        del keep
+        self._filter_edit.entries.append(entry)
+        return entry
+
+    def update_filters(self) -> FilterEdit:
+        """the flattened descriptor of the scene as filter_volume left it (no light, no record changes: whd and res stay).  Returns the
+        FilterEdit for DeviceScene.filter_volumes."""
+        _host_call(host.vpth_scene_update_volumes, self.handle)
+        edit, self._filter_edit = self._filter_edit, FilterEdit()
         return edit
 
     def volgrid_majorants(self, index: int) -> np.ndarray:

@@ -9,7 +9,7 @@ import numpy as np
 from ._abi import (DENOISE_ITERATIONS, DENOISE_SIGMA_ALBEDO, DENOISE_SIGMA_LUMINANCE, DENOISE_SIGMA_NORMAL, VptAdaptive, VptDenoise, VptPick,
                    VptError, VptSdf, VptSdfPick, VptSessionParams, VptVolgridPick, _Handle, _check, _edit_call, _p, hip)
 from .device import DeviceScene, DisplayParams, PathtraceParams, PathtraceState, _subdiv_edit_call
-from .edits import BvhRebuild, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, TextureEdit, VolumeEdit, VolumeSetEdit
+from .edits import BvhRebuild, FilterEdit, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, TextureEdit, VolumeEdit, VolumeSetEdit
 
 
 class RenderSession(_Handle):
@@ -130,6 +130,11 @@ class RenderSession(_Handle):
         """vpt_scene_sculpt_volumes on the session's scene with the SculptEdit of HostScene.update_sculpts(), then a reset; a refused edit
         leaves the session as it was"""
         _edit_call(self.handle, "vpt_session_sculpt_volumes", edit)
+
+    def edit_filters(self, edit: FilterEdit) -> None:
+        """vpt_scene_filter_volumes on the session's scene with the FilterEdit of HostScene.update_filters(), then a reset; a refused edit
+        leaves the session as it was"""
+        _edit_call(self.handle, "vpt_session_filter_volumes", edit)
 
     def sculpt_at(self, host, x: int, y: int, brush: VptSdf, op: int, blend: float = 0.0, region_margin: int = 2) -> SculptEntry:
         """The editor's gesture: one stamp of `brush` where the ray through pixel (x, y) hits a voxel grid.  pick_sdf(x, y) names the grid
