@@ -676,7 +676,7 @@ int vpt_scene_update_volume_set(vpt_scene* scene, const vpt_volume_set_edit* edi
  *    state stay untouched.
  *  - The medium, from the same material.  Single-scattering albedo = scattering clamped to [0, 1] per channel; phase function
  *    Henyey-Greenstein with g = scanisotropy (sample_phasefunction, eval_phasefunction: yocto_shading.h:1077-1102); emission is added at
- *    every real collision; the extinction is grey, colour comes from the albedo.
+ *    every real collision; the extinction is grey, colour comes from the albedo (coloured extinction: vpt_scene_set_volgrid_color below).
  *  - Majorants.  Per volume a table of brick maxima: brick (bx, by, bz) covers the cells [8 b, 8 b + 8) per axis of the W - 1 cells
  *    between the nodes, and its value is the maximum of clean(node) over the nodes [8 b, min(8 b + 8, W - 1)] per axis.  A trilerp inside
  *    the brick is a convex combination of those nodes up to rounding, so a tentative collision is real with probability
@@ -736,6 +736,53 @@ int vpt_scene_volgrid_track(vpt_scene* scene, int n, const float* rays /* n x {o
                             int32_t* event /* 0 escape, 1 collision, 2 step bound reached */, int32_t* instance /* -1 unless event == 1 */,
                             float* t /* flt_max unless event == 1 */, int32_t* steps, uint64_t* rng_out /* n x {state, inc}, nullable */);
 int vpt_scene_volgrid_stats(vpt_scene* scene, uint64_t* steps, int32_t* table_builds);
+
+/* ---- coloured extinction in the volgrid shader ------------------------------------------------------------------------
+ * A switch of the resident scene, off when it is made: vpt_scene_set_volgrid_color(scene, on).  It is an edit like any other (launches are
+ * waited for, the edit count moves, K3's tables are made anew, the launch-schedule record is forgotten; setting the value it has is an
+ * empty edit).  With it on every volgrid render, session advance and adaptive round of the handle runs the coloured variant of K3; with
+ * it off nothing differs from a handle that never had it on.  No shader id is added and no existing struct changes.
+ *  - The rule.  The extinction of grid instance g for channel c is sigma_c(p) = k_c * clean(v) / trdepth with k_c = -log(clamp(color_c,
+ *    0.0001, 1)) of the instance's material - eval_material's density of the reference's homogeneous medium (NaN clamps to 0.0001).
+ *    kmax = max_c k_c, a_c = k_c / kmax (0 when kmax == 0).  The CARRIER of g is the grey medium kmax * clean(v) / trdepth: the grey rule
+ *    above with trdepth_eff = trdepth / kmax (one float32 division).  An instance with kmax == 0 (colour 1 in every channel), or whose
+ *    trdepth_eff is not finite, is transparent: its coloured record has whd = 0, track() misses its box and spends no draw on it.
+ *  - The path is the grey path with `track` flown on the carriers and one step added after "if bounce == 0: hit = true", at every
+ *    carrier collision in instance g with path weight w:
+ *        s = max_c(w_c a_c), n = max_c(w_c (1 - a_c));  not (s + n > 0): done
+ *        P = s / (s + n);  n == 0: a scatter, and NO random number is drawn;  else u = rand1f(rng)
+ *        u < P: scatter: w_c *= a_c / P, then the grey rule's collision as it stands (emission with the new w, albedo, phase or MIS,
+ *               roulette, bounce + 1)
+ *        else   pass: w_c *= (1 - a_c) / (1 - P); ray = (position, the same direction), a new free flight; bounce does not move
+ *    (csrc/vpt_volgrid_rule.h: vpt_volgrid_event is the operation order.)  The carrier's own null collisions are the same for all
+ *    channels and carry no weight; chromatic nulls happen at carrier collisions only, so no weight is ever attached to a tracking step
+ *    and the per-instance walk with the nearest collision winning stays exact for overlapping media of different colours.  A path that
+ *    has passed VPT_VOLGRID_MAX_PASSES times ends like a flight that ran into VPT_VOLGRID_MAX_STEPS: nothing more is added and it counts
+ *    in the word vpt_check_watchdog reads.  Alpha (`hit`) is set by the first carrier collision of a sample's camera flight, before the
+ *    event is decided: the opacity of the densest channel; for equal channels it is the grey alpha.  With equal channels a = (1, 1, 1),
+ *    no event draws, and the render is bit for bit the grey render of the scene with every trdepth replaced by its trdepth_eff.
+ *  - What stays grey.  vpt_scene_volgrid_density (rho / trdepth; a channel's value is that times k_c), vpt_scene_volgrid_track, the
+ *    first-collision pass (vpt_render_volgrid_aov_device) with a session's pick_volgrid, its id frame and sculpt_at: they keep meaning
+ *    the grey flight whatever the switch says.  vpt_multi_* handles have no switch: they render grey.
+ * vpt_scene_get_volgrid_color: the switch.
+ * vpt_scene_get_volgrid_chroma: per grid instance, in index order, 32 bytes as the device holds them (tables brought up to date first,
+ * whatever the switch says): float a[3], kmax, trdepth_eff, int32 whd[3] of the coloured record (0 for a transparent instance, whose
+ * trdepth_eff is the material's trdepth); count (nullable) receives the number of instances, out is nullable with capacity 0.
+ * vpt_scene_volgrid_track_color: the coloured flight on n given rays and streams, as vpt_scene_volgrid_track takes them and with its
+ * argument checks, one lane per record, through the device functions the coloured kernel calls, compiled in its unit, reading the
+ * coloured tables whatever the switch says.  From w = (1, 1, 1) it flies carrier flights and events until event[i] = 1 a scatter (weight =
+ * w after a_c / P, instance the collision's, t the sum of the flights' parameters along the ray), 0 an escape (weight = w at the escape),
+ * or 2 an abort (a flight at VPT_VOLGRID_MAX_STEPS, VPT_VOLGRID_MAX_PASSES passes, or weights without a positive channel); instance = -1
+ * and t = FLT_MAX unless event is 1.  passes[i], steps[i]: passes taken and tracking steps over all flights (saturating).
+ * vpt_scene_volgrid_color_stats: passes taken by the handle's coloured launches so far; synchronous.
+ * vpt_session_set_volgrid_color: the switch of the session's scene, then a reset, as after an edit. */
+#define VPT_VOLGRID_MAX_PASSES (1 << 16)
+int vpt_scene_set_volgrid_color(vpt_scene* scene, int on);
+int vpt_scene_get_volgrid_color(const vpt_scene* scene);
+int vpt_scene_get_volgrid_chroma(vpt_scene* scene, void* out /* capacity x 32 bytes */, int capacity, int* count);
+int vpt_scene_volgrid_track_color(vpt_scene* scene, int n, const float* rays, const uint64_t* rng_in, int32_t* event, int32_t* instance, float* t,
+                                  float* weight /* 3 n */, int32_t* passes, int32_t* steps, uint64_t* rng_out /* nullable */);
+int vpt_scene_volgrid_color_stats(vpt_scene* scene, uint64_t* passes);
 
 /* ---- the BVHs of a resident scene built anew on the device ------------------------------------------------------------
  * The four edits above keep a tree's topology as creation left it: vpt_scene_update is the reference's update_bvh, a refit.  After a
@@ -1495,6 +1542,9 @@ int  vpt_session_edit_volumes(vpt_session* session, const vpt_volume_edit* edit)
 int  vpt_session_sculpt_volumes(vpt_session* session, const vpt_sculpt_edit* edit);
 /* vpt_scene_filter_volumes, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_filter_volumes(vpt_session* session, const vpt_filter_edit* edit);
+/* vpt_scene_set_volgrid_color, then a reset.  The session stays a volgrid session: its pick, id frame and first-collision pass keep
+ * meaning the grey flight */
+int  vpt_session_set_volgrid_color(vpt_session* session, int on);
 /* vpt_scene_update_volume_set, then a reset (which drops both id frames: pick_sdf never names an entry that is gone); a refused edit
  * leaves the session as it was */
 int  vpt_session_edit_volume_set(vpt_session* session, const vpt_volume_set_edit* edit);

@@ -250,5 +250,14 @@ int vpt_scene_subdiv_count(const vpt_scene* s) {
 }
 int vpt_scene_subdiv_shape(const vpt_scene* s, int subdiv_id) { return s && subdiv_id >= 0 && subdiv_id < (int)s->subdivs.size() ? s->subdivs[(size_t)subdiv_id].shape : -1; }
 int vpt_scene_update_subdivs(vpt_scene* s, const vpt_subdiv_edit* edit) { return edit_scene(s, edit, subdiv_update_apply); }
+// the coloured variant of K3 for this handle's volgrid launches: no table of the resident changes, the render side's tables follow the edit count
+int vpt_scene_set_volgrid_color(vpt_scene* s, int on) {
+  const bool want = on != 0;
+  return edit_scene(s, &want, [s](resident&, const bool& w, edit_outcome& out) {
+    out.changed      = s->volgrid.color != w;
+    s->volgrid.color = w;
+    return VPT_OK;
+  });
+}
 
 }  // extern "C"

@@ -87,6 +87,22 @@ __global__ void __launch_bounds__(VPT_BLOCK, VPT_K3_WAVES) vpt_volgrid_kernel(DS
 // the free-flight probe of vpt_scene_volgrid_track: one lane per record through K3's vg_start / vg_track_step (defined in vpt_k3.hip)
 __global__ void vpt_volgrid_track_kernel(DScene sc, volgrid_args va, int n, const float* __restrict__ rays, const ulonglong2* __restrict__ rng_in,
     int* __restrict__ event, int* __restrict__ instance, float* __restrict__ t, int* __restrict__ steps, ulonglong2* __restrict__ rng_out);
+// K3's coloured variant (include/vpt.h: vpt_scene_set_volgrid_color; instances: vpt_k3_color.hip).  Its volgrid_args name the COLOURED
+// records (the carrier media) beside the shared brick pool; what colour adds travels in an argument of its own, so that volgrid_args
+// stays byte for byte what K3 is compiled for
+struct vpt_volgrid_chroma;   // vpt_volgrid_rule.h
+struct volgrid_color_args {
+  const vpt_volgrid_chroma* chroma;   // one per grid instance, in instance order
+  unsigned long long*       passes;   // passes taken since the handle was made (vpt_scene_volgrid_color_stats)
+};
+template <bool PILOT>
+__global__ void __launch_bounds__(VPT_BLOCK, VPT_K3_WAVES) vpt_volgrid_color_kernel(DScene sc, DParams pr, volgrid_args va, volgrid_color_args vc,
+    float4* __restrict__ image, int* __restrict__ hits, ulonglong2* __restrict__ rngs, sched_cfg sched);
+// the probe of vpt_scene_volgrid_track_color: one lane per record flies flights and events until a scatter, an escape or an abort, through
+// the device functions the coloured kernel calls (defined in vpt_k3_color.hip)
+__global__ void vpt_volgrid_track_color_kernel(DScene sc, volgrid_args va, volgrid_color_args vc, int n, const float* __restrict__ rays,
+    const ulonglong2* __restrict__ rng_in, int* __restrict__ event, int* __restrict__ instance, float* __restrict__ t, float* __restrict__ weight,
+    int* __restrict__ passes, int* __restrict__ steps, ulonglong2* __restrict__ rng_out);
 
 // ---- vpt_intersect, KAT, self-tests (vpt_kernels.hip, but for vpt_intersect_curves_kernel: vpt_k1_curves.hip) ----------------
 template <bool SPILL, bool COMPACT>

@@ -69,7 +69,16 @@ static void launch_implicit_instance(const launch_ctx& L, bool is_pilot, dim3 gr
   else launch(vpt_render_kernel<K, VPT_FEAT_ALL>);
 }
 // K3: one instance and its pilot; LDS holds the records of the grid instances (volgrid_prepare has checked that they fit)
+// (a handle with vpt_scene_set_volgrid_color on: the coloured variant over the carrier records, the chroma rows in LDS behind them)
 static void launch_volgrid_instance(const launch_ctx& L, bool is_pilot, dim3 grid, const DParams& pr, const sched_cfg& sch) {
+  if (L.s->volgrid.color) {
+    const volgrid_args       va  = volgrid_color_arguments(L.s);
+    const volgrid_color_args vc  = volgrid_chroma_arguments(L.s);
+    const size_t             lds = (size_t)va.num_instances * (128 + 16);
+    if (is_pilot) hipLaunchKernelGGL(vpt_volgrid_color_kernel<true>, grid, dim3(VPT_BLOCK), lds, L.st, L.s->d, pr, va, vc, L.img, L.hit, L.rng, sch);
+    else hipLaunchKernelGGL(vpt_volgrid_color_kernel<false>, grid, dim3(VPT_BLOCK), lds, L.st, L.s->d, pr, va, vc, L.img, L.hit, L.rng, sch);
+    return;
+  }
   const volgrid_args va  = volgrid_arguments(L.s);
   const size_t       lds = (size_t)va.num_instances * 128;
   if (is_pilot) hipLaunchKernelGGL(vpt_volgrid_kernel<true>, grid, dim3(VPT_BLOCK), lds, L.st, L.s->d, pr, va, L.img, L.hit, L.rng, sch);

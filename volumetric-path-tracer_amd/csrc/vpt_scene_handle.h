@@ -14,6 +14,10 @@
 struct volgrid_tables {
   unsigned long long built_edits = 0, built_voxels = 0;   // vpt_scene::edit_generation / voxel_generation they were built at (0: never)
   device_buffer      recs, bricks, steps;                 // vpt_volgrid_record per grid instance; the brick pool; the step counter
+  device_buffer      color_recs, chroma, passes;          // the coloured variant's: the carrier records, vpt_volgrid_chroma per grid instance, the pass counter
+  bool               color = false;                       // vpt_scene_set_volgrid_color
+  unsigned long long built_color = 0;                     // edit_generation the coloured tables were built at: only a handle with the switch on, a
+                                                          // read-back of them or the coloured probe builds them - a grey handle never pays for them
   std::vector<int>   brick_offset;                        // per volume: its table in the pool (nbx * nby * nbz majorants, then their maximum)
   long long          num_bricks = 0;                      // floats of the pool
   int                num_env_lights = 0;
@@ -73,6 +77,9 @@ int implicit_lds(const vpt_scene* s, size_t* bytes = nullptr);
 int volgrid_prepare(vpt_scene* s, hipStream_t st);
 // the kernel argument of a prepared handle
 volgrid_args volgrid_arguments(const vpt_scene* s);
+// the two arguments of the coloured variant: K3's with the coloured records in place of the grey ones, and what colour adds
+volgrid_args       volgrid_color_arguments(const vpt_scene* s);
+volgrid_color_args volgrid_chroma_arguments(const vpt_scene* s);
 // what a shader's kernel needs of the scene before its launches: K2 room for the SDF records in LDS, K3 its tables, K1 nothing
 inline int shader_setup(vpt_scene* s, const vpt_params* p, hipStream_t st) {
   if (p->shader == VPT_SHADER_VOLGRID) return volgrid_prepare(s, st);

@@ -478,6 +478,12 @@ int vpt_session_edit_textures(vpt_session* s, const vpt_texture_edit* edit) { re
 int vpt_session_edit_volumes(vpt_session* s, const vpt_volume_edit* edit) { return session_edit(s, edit, vpt_scene_update_volumes); }
 int vpt_session_sculpt_volumes(vpt_session* s, const vpt_sculpt_edit* edit) { return session_edit(s, edit, vpt_scene_sculpt_volumes); }
 int vpt_session_filter_volumes(vpt_session* s, const vpt_filter_edit* edit) { return session_edit(s, edit, vpt_scene_filter_volumes); }
+int vpt_session_set_volgrid_color(vpt_session* s, int on) {   // no edit's counters to add: the switch launches and sends nothing
+  REQUIRE(s, "null session");
+  begin_call(s);
+  if (int rc = vpt_scene_set_volgrid_color(s->scene, on)) return rc;
+  return reset(s, s->p);
+}
 int vpt_session_edit_volume_set(vpt_session* s, const vpt_volume_set_edit* edit) { return session_edit(s, edit, vpt_scene_update_volume_set); }
 int vpt_session_rebuild_bvh(vpt_session* s, const vpt_bvh_rebuild* what) { return vpt_session_rebuild_bvh_quality(s, what, VPT_BVH_MIDDLE); }
 int vpt_session_rebuild_bvh_quality(vpt_session* s, const vpt_bvh_rebuild* what, int quality) {

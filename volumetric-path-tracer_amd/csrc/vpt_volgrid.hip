@@ -54,6 +54,8 @@ int check_media(const vpt_scene* s) {
   }
   REQUIRE(s->m.vol_instances.size() * sizeof(vpt_volgrid_record) <= 64 * 1024, "volgrid: %d grid instances exceed the kernel's LDS copy of their records (512)",
       (int)s->m.vol_instances.size());
+  REQUIRE(!s->volgrid.color || s->m.vol_instances.size() * (sizeof(vpt_volgrid_record) + sizeof(vpt_volgrid_chroma)) <= 64 * 1024,
+      "volgrid: %d grid instances exceed the coloured kernel's LDS copy of their records and chroma rows (455)", (int)s->m.vol_instances.size());
   return VPT_OK;
 }
 
@@ -103,11 +105,40 @@ int sync_tables(vpt_scene* s, hipStream_t st) {
   return VPT_OK;
 }
 
+// the coloured variant's tables beside them - the carrier records and the chroma rows, over the same brick tables - for a handle with the
+// switch on, a read-back or the coloured probe: a grey handle never builds them
+int sync_color_tables(vpt_scene* s, hipStream_t st) {
+  if (int rc = sync_tables(s, st)) return rc;
+  volgrid_tables& t = s->volgrid;
+  if (t.built_color == s->edit_generation) return VPT_OK;
+  if (!t.passes.get()) {
+    if (int rc = t.passes.allocate(8)) return rc;
+    HIP_TRY(hipMemsetAsync(t.passes.get(), 0, 8, st));
+  }
+  const size_t n = s->m.vol_instances.size();
+  std::vector<vpt_volgrid_record> recs(n);
+  std::vector<vpt_volgrid_chroma> chroma(n);
+  for (size_t g = 0; g < n; g++) {
+    const vpt_volume_instance& vi  = s->m.vol_instances[g];
+    const vpt_material&        mat = s->m.materials[(size_t)vi.material];
+    chroma[g] = vpt_volgrid_make_chroma(mat);
+    recs[g]   = vpt_volgrid_make_color_record(vi, s->m.volumes[(size_t)vi.volume], mat, t.brick_offset[(size_t)vi.volume], chroma[g]);
+  }
+  if (int rc = t.color_recs.allocate(n * sizeof(vpt_volgrid_record))) return rc;
+  if (int rc = t.chroma.allocate(n * sizeof(vpt_volgrid_chroma))) return rc;
+  if (n > 0) {
+    HIP_TRY(hipMemcpy(t.color_recs.get(), recs.data(), n * sizeof(vpt_volgrid_record), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t.chroma.get(), chroma.data(), n * sizeof(vpt_volgrid_chroma), hipMemcpyHostToDevice));
+  }
+  t.built_color = s->edit_generation;
+  return VPT_OK;
+}
+
 }  // namespace
 
 int volgrid_prepare(vpt_scene* s, hipStream_t st) {
   if (int rc = check_media(s)) return rc;
-  return sync_tables(s, st);
+  return s->volgrid.color ? sync_color_tables(s, st) : sync_tables(s, st);
 }
 
 volgrid_args volgrid_arguments(const vpt_scene* s) {
@@ -115,6 +146,26 @@ volgrid_args volgrid_arguments(const vpt_scene* s) {
   const char* e = getenv("VPT_VOLGRID_NO_BRICKS");
   return {t.recs.get<const vpt_volgrid_record>(), t.bricks.get<const float>(), s->d.num_vol_instances, t.num_env_lights, e && e[0] == '1' ? 1 : 0,
       s->d_watchdog.get<unsigned>(), t.steps.get<unsigned long long>()};
+}
+
+volgrid_args volgrid_color_arguments(const vpt_scene* s) {
+  volgrid_args va = volgrid_arguments(s);
+  va.recs = s->volgrid.color_recs.get<const vpt_volgrid_record>();
+  return va;
+}
+volgrid_color_args volgrid_chroma_arguments(const vpt_scene* s) {
+  return {s->volgrid.chroma.get<const vpt_volgrid_chroma>(), s->volgrid.passes.get<unsigned long long>()};
+}
+
+// the checks of a probe's rays (vpt_scene_volgrid_track, vpt_scene_volgrid_track_color)
+static int check_rays(const char* who, int n, const float* rays) {
+  for (int i = 0; i < n; i++) {
+    const float* r = rays + 6 * (size_t)i;
+    for (int k = 0; k < 6; k++) REQUIRE(std::isfinite(r[k]), "%s: ray %d has a component that is not finite", who, i);
+    const double len = std::sqrt((double)r[3] * r[3] + (double)r[4] * r[4] + (double)r[5] * r[5]);
+    REQUIRE(std::fabs(len - 1.0) <= 1e-3, "%s: ray %d has a direction of length %g (a unit vector within 1e-3 is needed)", who, i, len);
+  }
+  return VPT_OK;
 }
 
 extern "C" {
@@ -155,12 +206,7 @@ int vpt_scene_volgrid_density(vpt_scene* s, int n, const float* points, int32_t*
 int vpt_scene_volgrid_track(vpt_scene* s, int n, const float* rays, const uint64_t* rng_in, int32_t* event, int32_t* instance, float* t, int32_t* steps,
     uint64_t* rng_out) {
   REQUIRE(s && n >= 0 && (n == 0 || (rays && rng_in && event && instance && t && steps)), "bad argument");
-  for (int i = 0; i < n; i++) {
-    const float* r = rays + 6 * (size_t)i;
-    for (int k = 0; k < 6; k++) REQUIRE(std::isfinite(r[k]), "volgrid_track: ray %d has a component that is not finite", i);
-    const double len = std::sqrt((double)r[3] * r[3] + (double)r[4] * r[4] + (double)r[5] * r[5]);
-    REQUIRE(std::fabs(len - 1.0) <= 1e-3, "volgrid_track: ray %d has a direction of length %g (a unit vector within 1e-3 is needed)", i, len);
-  }
+  if (int rc = check_rays("volgrid_track", n, rays)) return rc;
   if (int rc = volgrid_prepare(s, nullptr)) return rc;
   if (n == 0) return VPT_OK;
   HIP_TRY(hipSetDevice(s->device));
@@ -180,6 +226,65 @@ int vpt_scene_volgrid_track(vpt_scene* s, int n, const float* rays, const uint64
   HIP_TRY(hipMemcpy(t, o + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(steps, o + 3 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));
   if (rng_out) HIP_TRY(hipMemcpy(rng_out, rg + n, (size_t)n * 16, hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+
+int vpt_scene_volgrid_track_color(vpt_scene* s, int n, const float* rays, const uint64_t* rng_in, int32_t* event, int32_t* instance, float* t, float* weight,
+    int32_t* passes, int32_t* steps, uint64_t* rng_out) {
+  REQUIRE(s && n >= 0 && (n == 0 || (rays && rng_in && event && instance && t && weight && passes && steps)), "bad argument");
+  if (int rc = check_rays("volgrid_track_color", n, rays)) return rc;
+  if (int rc = volgrid_prepare(s, nullptr)) return rc;
+  if (int rc = sync_color_tables(s, nullptr)) return rc;
+  if (n == 0) return VPT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  device_buffer d_rays, d_rng, d_out;   // d_out: event, instance, t, passes, steps, weight (3) - eight planes of n words
+  if (int rc = d_rays.allocate((size_t)n * 24)) return rc;
+  if (int rc = d_rng.allocate((size_t)n * 32)) return rc;   // in, then out
+  if (int rc = d_out.allocate((size_t)n * 32)) return rc;
+  HIP_TRY(hipMemcpy(d_rays.get(), rays, (size_t)n * 24, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_rng.get(), rng_in, (size_t)n * 16, hipMemcpyHostToDevice));
+  int*         o  = d_out.get<int>();
+  const size_t N  = (size_t)n;
+  ulonglong2*  rg = d_rng.get<ulonglong2>();
+  hipLaunchKernelGGL(vpt_volgrid_track_color_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, s->d, volgrid_color_arguments(s),
+      volgrid_chroma_arguments(s), n, d_rays.get<const float>(), (const ulonglong2*)rg, o, o + N, (float*)(o + 2 * N), (float*)(o + 5 * N), o + 3 * N, o + 4 * N,
+      rng_out ? rg + n : nullptr);
+  HIP_TRY(hipGetLastError());
+  void* const dst[5] = {event, instance, t, passes, steps};
+  for (int k = 0; k < 5; k++) HIP_TRY(hipMemcpy(dst[k], o + k * N, N * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(weight, o + 5 * N, N * 12, hipMemcpyDeviceToHost));
+  if (rng_out) HIP_TRY(hipMemcpy(rng_out, rg + n, N * 16, hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+
+int vpt_scene_get_volgrid_color(const vpt_scene* s) { return s && s->volgrid.color ? 1 : 0; }
+
+int vpt_scene_get_volgrid_chroma(vpt_scene* s, void* out, int capacity, int* count) {
+  REQUIRE(s && capacity >= 0 && (capacity == 0 || out), "bad argument");
+  if (int rc = sync_color_tables(s, nullptr)) return rc;
+  const int n = s->d.num_vol_instances;
+  if (count) *count = n;
+  if (!out) return VPT_OK;
+  REQUIRE(capacity >= n, "capacity %d < %d grid instances", capacity, n);
+  std::vector<vpt_volgrid_record> recs((size_t)n);
+  std::vector<vpt_volgrid_chroma> chroma((size_t)n);
+  HIP_TRY(hipDeviceSynchronize());
+  if (n > 0) {
+    HIP_TRY(hipMemcpy(recs.data(), s->volgrid.color_recs.get(), (size_t)n * sizeof(vpt_volgrid_record), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(chroma.data(), s->volgrid.chroma.get(), (size_t)n * sizeof(vpt_volgrid_chroma), hipMemcpyDeviceToHost));
+  }
+  for (int g = 0; g < n; g++) ((vpt_volgrid_chroma_row*)out)[g] = vpt_volgrid_make_chroma_row(chroma[(size_t)g], recs[(size_t)g]);
+  return VPT_OK;
+}
+
+int vpt_scene_volgrid_color_stats(vpt_scene* s, uint64_t* passes) {
+  REQUIRE(s && passes, "null argument");
+  *passes = 0;
+  if (s->volgrid.passes.get()) {
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(passes, s->volgrid.passes.get(), 8, hipMemcpyDeviceToHost));
+  }
   return VPT_OK;
 }
 

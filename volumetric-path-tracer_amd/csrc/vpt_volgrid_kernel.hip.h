@@ -154,19 +154,28 @@ VPT_DEV float vg_env_pdf(const DScene& sc, int num_env, f3 position, f3 directio
   return sum * ((float)1 / (float)num_env);
 }
 
-__device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DParams& pr, const volgrid_args& va, float4* __restrict__ image,
-    int* __restrict__ hits, ulonglong2* __restrict__ rngs, const sched_cfg& sched) {
+// COLOR: the coloured variant (include/vpt.h: vpt_scene_set_volgrid_color).  va.recs are then the coloured records - the
+// carrier media, flown by the same vg_start / vg_track_step - vc names the chroma rows, copied into LDS behind the records, and the
+// shading block decides the event of csrc/vpt_volgrid_rule.h at every carrier collision: a scatter goes on as K3's collision does, a pass
+// puts the lane straight back into V_TRACK with a fresh walk from the collision point - no camera work, no phase work, bounce unmoved.
+// No weight is attached to a tracking step, so the per-instance walk with the nearest collision winning stays exact.
+template <bool COLOR>
+__device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DParams& pr, const volgrid_args& va, const volgrid_color_args* vc,
+    float4* __restrict__ image, int* __restrict__ hits, ulonglong2* __restrict__ rngs, const sched_cfg& sched) {
   extern __shared__ int4 lds_recs4[];
   // the records, copied once into LDS (read at every tracking step)
   {
     const int4* src = (const int4*)va.recs;
     const int   n4  = va.num_instances * (int)(sizeof(vpt_volgrid_record) / sizeof(int4));
     for (int i = threadIdx.x; i < n4; i += VPT_BLOCK) lds_recs4[i] = src[i];
+    if constexpr (COLOR)   // one int4 per instance behind them
+      for (int i = threadIdx.x; i < va.num_instances; i += VPT_BLOCK) lds_recs4[n4 + i] = ((const int4*)vc->chroma)[i];
   }
   __shared__ unsigned long long s_wave_start;   // the start stamp, parked in LDS (clock_ticks, vpt_math.hip.h)
   if (threadIdx.x == 0) s_wave_start = clock_ticks(blockIdx.x);
   __syncthreads();
   const vpt_volgrid_record* recs = (const vpt_volgrid_record*)lds_recs4;
+  [[maybe_unused]] const vpt_volgrid_chroma* chroma = (const vpt_volgrid_chroma*)(recs + va.num_instances);   // COLOR only
   const unsigned long long  wave_start = s_wave_start;
   const int wave = sched.order ? sched.order[blockIdx.x] : (int)blockIdx.x;
 
@@ -197,6 +206,8 @@ __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DPar
   vg_walk w;
   vg_start(w);
   unsigned long long steps = 0;
+  [[maybe_unused]] int                passes = 0;         // COLOR: of the path in flight
+  [[maybe_unused]] unsigned           passes_total = 0;   // COLOR: of the lane since it last added them to the handle's counter
 
   while (true) {
     const unsigned long long tracking = __builtin_amdgcn_ballot_w64(mode == V_TRACK);
@@ -224,47 +235,68 @@ __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DPar
       const vpt_volgrid_record& rec = recs[w.hit_g];
       const f3 position = ro + rd * w.tmax, outgoing = -rd;
       const f3 albedo = mk3(rec.albedo[0], rec.albedo[1], rec.albedo[2]);
-      if (bounce == 0) hit = 1;
-      radiance = radiance + weight * mk3(rec.emission[0], rec.emission[1], rec.emission[2]);
-      f3 incoming;
-      if (!mis) {   // as sample_scattering draws: rn, then the rnl nobody reads (yocto_pathtrace.cpp:665)
-        f2 rn;
-        rn.x = rand1f(rng);
-        rn.y = rand1f(rng);
-        (void)rand1f(rng);
-        incoming = sample_phasefunction(rec.g, outgoing, rn);
-        weight   = weight * albedo;   // no division: f / pdf is 1 by construction
-      } else {
-        if (rand1f(rng) < 0.5f) {
+      if (bounce == 0) hit = 1;   // (COLOR: the first carrier collision of the camera flight, before the event: the densest channel's opacity)
+      bool scatter = true;
+      if constexpr (COLOR) {
+        const vpt_volgrid_chroma& ch = chroma[w.hit_g];
+        float wv[3] = {weight.x, weight.y, weight.z};
+        const float u  = vpt_volgrid_event_draws(ch.a, wv) ? rand1f(rng) : 0.0f;
+        const int   ev = vpt_volgrid_event(ch.a, wv, u, wv, nullptr);
+        weight = mk3(wv[0], wv[1], wv[2]);
+        if (ev == VPT_VOLGRID_END) scatter = false, finish = true;
+        else if (ev == VPT_VOLGRID_PASS) {
+          scatter = false;
+          passes++, passes_total++;
+          if (passes_total == 0x80000000u) atomicAdd(vc->passes, (unsigned long long)passes_total), passes_total = 0;   // one register, never wrapped
+          if (passes >= VPT_VOLGRID_MAX_PASSES) aborted++, finish = true;   // as a flight that ran into its step bound
+          else {
+            ro = position, mode = V_TRACK;
+            vg_start(w);
+          }
+        }
+      }
+      if (scatter) {
+        radiance = radiance + weight * mk3(rec.emission[0], rec.emission[1], rec.emission[2]);
+        f3 incoming;
+        if (!mis) {   // as sample_scattering draws: rn, then the rnl nobody reads (yocto_pathtrace.cpp:665)
           f2 rn;
           rn.x = rand1f(rng);
           rn.y = rand1f(rng);
           (void)rand1f(rng);
           incoming = sample_phasefunction(rec.g, outgoing, rn);
-        } else {   // as sample_lights draws: ruv, rel, rl
-          f2 ruv;
-          ruv.x = rand1f(rng);
-          ruv.y = rand1f(rng);
-          const float rel = rand1f(rng);
-          const float rl  = rand1f(rng);
-          incoming = vg_sample_env(sc, vg_env_light(sc, sample_uniform(va.num_env_lights, rl)), rel, ruv);
+          weight   = weight * albedo;   // no division: f / pdf is 1 by construction
+        } else {
+          if (rand1f(rng) < 0.5f) {
+            f2 rn;
+            rn.x = rand1f(rng);
+            rn.y = rand1f(rng);
+            (void)rand1f(rng);
+            incoming = sample_phasefunction(rec.g, outgoing, rn);
+          } else {   // as sample_lights draws: ruv, rel, rl
+            f2 ruv;
+            ruv.x = rand1f(rng);
+            ruv.y = rand1f(rng);
+            const float rel = rand1f(rng);
+            const float rl  = rand1f(rng);
+            incoming = vg_sample_env(sc, vg_env_light(sc, sample_uniform(va.num_env_lights, rl)), rel, ruv);
+          }
+          const float f = eval_phasefunction(rec.g, outgoing, incoming);
+          weight = weight * (albedo * (f / (0.5f * f + 0.5f * vg_env_pdf(sc, va.num_env_lights, position, incoming))));
         }
-        const float f = eval_phasefunction(rec.g, outgoing, incoming);
-        weight = weight * (albedo * (f / (0.5f * f + 0.5f * vg_env_pdf(sc, va.num_env_lights, position, incoming))));
-      }
-      if (is_zero3(weight) || !finite3(weight)) finish = true;
-      else if (bounce > 3) {   // min(1, .): a medium of albedo 1 keeps its weight for ever (include/vpt.h: not the reference's 0.99)
-        const float rr = fmin_(1.0f, max3(weight));
-        if (rr < 1) {
-          if (rand1f(rng) >= rr) finish = true;
-          else weight = weight / rr;
+        if (is_zero3(weight) || !finite3(weight)) finish = true;
+        else if (bounce > 3) {   // min(1, .): a medium of albedo 1 keeps its weight for ever (include/vpt.h: not the reference's 0.99)
+          const float rr = fmin_(1.0f, max3(weight));
+          if (rr < 1) {
+            if (rand1f(rng) >= rr) finish = true;
+            else weight = weight / rr;
+          }
         }
-      }
-      bounce++;
-      if (bounce >= nb) finish = true;
-      if (!finish) {
-        ro = position, rd = incoming, mode = V_TRACK;
-        vg_start(w);
+        bounce++;
+        if (bounce >= nb) finish = true;
+        if (!finish) {
+          ro = position, rd = incoming, mode = V_TRACK;
+          vg_start(w);
+        }
       }
     }
     if (finish) {
@@ -291,6 +323,7 @@ __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DPar
         ro = ray.o, rd = ray.d;
         radiance = mk3(0, 0, 0), weight = mk3(1, 1, 1), hit = 0;
         bounce = 0, mode = V_TRACK;
+        if constexpr (COLOR) passes = 0;
         vg_start(w);
         if (nb <= 0) mode = V_ESCAPE, weight = mk3(0, 0, 0);   // no bounce allowed: the loop body never runs (radiance 0, no hit)
       }
@@ -305,6 +338,8 @@ __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DPar
     r_out.x = rng.state, r_out.y = rng.inc;
     rngs[slot] = r_out;
     if (va.steps) atomicAdd(va.steps, steps);
+    if constexpr (COLOR)
+      atomicAdd(vc->passes, (unsigned long long)passes_total);
   }
   if (sched.cost && threadIdx.x == 0) {
     unsigned long long dt = clock_ticks(__float_as_int(acc.x)) - wave_start;   // after the last sample was accumulated
@@ -317,5 +352,11 @@ __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DPar
 template <bool PILOT>
 __global__ void vpt_volgrid_kernel(DScene sc, DParams pr, volgrid_args va, float4* __restrict__ image, int* __restrict__ hits,
     ulonglong2* __restrict__ rngs, sched_cfg sched) {
-  volgrid_kernel_body(sc, pr, va, image, hits, rngs, sched);
+  volgrid_kernel_body<false>(sc, pr, va, nullptr, image, hits, rngs, sched);
+}
+// the coloured variant, render and pilot (launch bounds: vpt_launch.h; instances: vpt_k3_color.hip)
+template <bool PILOT>
+__global__ void vpt_volgrid_color_kernel(DScene sc, DParams pr, volgrid_args va, volgrid_color_args vc, float4* __restrict__ image, int* __restrict__ hits,
+    ulonglong2* __restrict__ rngs, sched_cfg sched) {
+  volgrid_kernel_body<true>(sc, pr, va, &vc, image, hits, rngs, sched);
 }

@@ -147,6 +147,92 @@ VPT_VOLGRID_HD float vpt_volgrid_density(const vpt_volgrid_record& rec, const fl
   return vpt_volgrid_sigma_at(rec, voxels, node);
 }
 
+// ---- coloured extinction (include/vpt.h: vpt_scene_set_volgrid_color) -----------------------------------------------------
+// sigma_c(p) = k_c rho(p) / trdepth with k_c = -log(clamp(color_c, 1e-4, 1)), the density of the reference's homogeneous medium
+// (eval_material).  Within an instance the channels differ by constants: the carrier kmax rho / trdepth is a grey medium of
+// trdepth / kmax, flown by the grey free flight, and a carrier collision is real for channel c with probability a_c = k_c / kmax.
+struct vpt_volgrid_chroma {
+  float a[3];   // k_c / kmax in [0, 1]; exactly 1 for the largest channel; 0 for a transparent instance
+  float kmax;   // max_c k_c; 0: the instance is transparent
+};
+static_assert(sizeof(vpt_volgrid_chroma) == 16, "a chroma row is one float4");
+// what vpt_scene_get_volgrid_chroma and vpth_volgrid_chroma answer per grid instance: the chroma row and what the coloured record holds
+struct vpt_volgrid_chroma_row {
+  float   a[3], kmax;
+  float   trdepth_eff;   // trdepth / kmax; the material's trdepth for a transparent instance
+  int32_t whd[3];        // the coloured record's: 0 for a transparent instance
+};
+static_assert(sizeof(vpt_volgrid_chroma_row) == 32, "a chroma read-back row");
+
+// Made on the host only (device and mirror hold the same logf).  clamp = min(max(x, lo), hi) with the ternaries of yocto_math.h (NaN: lo);
+// k_c = 0 - logf(.), so that colour 1 gives +0; kmax by `k > kmax ? k : kmax` from 0; a_c = k_c / kmax, one division each
+inline vpt_volgrid_chroma vpt_volgrid_make_chroma(const vpt_material& mat) {
+  vpt_volgrid_chroma ch = {{0.0f, 0.0f, 0.0f}, 0.0f};
+  float k[3];
+  for (int c = 0; c < 3; c++) {
+    float x = mat.color[c];
+    x       = x > 0.0001f ? x : 0.0001f;
+    x       = x < 1.0f ? x : 1.0f;
+    k[c]    = 0.0f - logf(x);
+    ch.kmax = k[c] > ch.kmax ? k[c] : ch.kmax;
+  }
+  for (int c = 0; c < 3; c++) ch.a[c] = ch.kmax > 0.0f ? k[c] / ch.kmax : 0.0f;
+  return ch;
+}
+// The coloured record: the grey one with the carrier's trdepth (one float32 division).  A transparent instance (kmax == 0, or a carrier
+// trdepth that is not finite) gets whd = 0 and keeps the material's trdepth: the box clip of the free flight misses it without a draw
+inline vpt_volgrid_record vpt_volgrid_make_color_record(const vpt_volume_instance& vi, const vpt_volume& vol, const vpt_material& mat, int brick_offset,
+    const vpt_volgrid_chroma& ch) {
+  vpt_volgrid_record r   = vpt_volgrid_make_record(vi, vol, mat, brick_offset);
+  const float        eff = ch.kmax > 0.0f ? r.trdepth / ch.kmax : 0.0f;
+  if (vpt_volgrid_trdepth_ok(eff)) r.trdepth = eff;
+  else r.whd[0] = r.whd[1] = r.whd[2] = 0;
+  return r;
+}
+inline vpt_volgrid_chroma_row vpt_volgrid_make_chroma_row(const vpt_volgrid_chroma& ch, const vpt_volgrid_record& color_rec) {
+  return {{ch.a[0], ch.a[1], ch.a[2]}, ch.kmax, color_rec.trdepth, {color_rec.whd[0], color_rec.whd[1], color_rec.whd[2]}};
+}
+
+// The event at a carrier collision with path weight w (history-aware probabilities, Kutz et al. 2017) - THIS IS ITS OPERATION ORDER:
+//   s = max(max(w0 a0, w1 a1), w2 a2)     n = max(max(w0 (1 - a0), w1 (1 - a1)), w2 (1 - a2))
+//   not (s + n > 0): END (weights all zero, or a sum that is not a number; `>` drops a NaN product, the path's own finite check ends those)
+//   P = s / (s + n)
+//   n == 0, or u < P: SCATTER, w_c = w_c * (a_c / P)       else: PASS, w_c = w_c * ((1 - a_c) / (1 - P))
+// With n == 0 (equal channels among them) P is s / s = 1 and a_c / 1 = a_c: the same formula, and u is not read - the caller draws none
+// (vpt_volgrid_event_draws).  P rounds to 1 only where u < P always holds, so 1 - P is never 0 on the PASS side.
+enum { VPT_VOLGRID_PASS = 0, VPT_VOLGRID_SCATTER = 1, VPT_VOLGRID_END = 2 };
+VPT_VOLGRID_HD void vpt_volgrid_event_sn(const float a[3], const float w[3], float& s, float& n) {
+  const float s0 = w[0] * a[0], s1 = w[1] * a[1], s2 = w[2] * a[2];
+  const float n0 = w[0] * (1.0f - a[0]), n1 = w[1] * (1.0f - a[1]), n2 = w[2] * (1.0f - a[2]);
+  s = s0 > s1 ? s0 : s1, s = s > s2 ? s : s2;
+  n = n0 > n1 ? n0 : n1, n = n > n2 ? n : n2;
+}
+// whether the event reads a random number
+VPT_VOLGRID_HD bool vpt_volgrid_event_draws(const float a[3], const float w[3]) {
+  float s, n;
+  vpt_volgrid_event_sn(a, w, s, n);
+  return s + n > 0.0f && n != 0.0f;
+}
+// the event; out (may alias w) receives the weight after it, unchanged on END; prob (nullable) receives P
+VPT_VOLGRID_HD int vpt_volgrid_event(const float a[3], const float w[3], float u, float out[3], float* prob) {
+  float s, n;
+  vpt_volgrid_event_sn(a, w, s, n);
+  if (prob) *prob = 0.0f;
+  if (!(s + n > 0.0f)) {
+    out[0] = w[0], out[1] = w[1], out[2] = w[2];
+    return VPT_VOLGRID_END;
+  }
+  const float P = s / (s + n);
+  if (prob) *prob = P;
+  if (n == 0.0f || u < P) {
+    out[0] = w[0] * (a[0] / P), out[1] = w[1] * (a[1] / P), out[2] = w[2] * (a[2] / P);
+    return VPT_VOLGRID_SCATTER;
+  }
+  const float q = 1.0f - P;
+  out[0] = w[0] * ((1.0f - a[0]) / q), out[1] = w[1] * ((1.0f - a[1]) / q), out[2] = w[2] * ((1.0f - a[2]) / q);
+  return VPT_VOLGRID_PASS;
+}
+
 // ---- the first-collision pass (include/vpt.h: vpt_render_volgrid_aov_device): the collision cell and the density's gradient in it ----------
 // The eight nodes of the cell eval_volume reads at node coordinates (s, t, r), each through clean(), in the order v000 v100 v010 v001 v011
 // v101 v110 v111 of the trilerp above, and the fractions (u, v, w) inside it: one fetch for the whole gradient

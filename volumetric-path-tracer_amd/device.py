@@ -8,7 +8,7 @@ from typing import TYPE_CHECKING, Optional
 
 import numpy as np
 
-from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SDF_AOV_PLANES, SHADER_NAMES, VOLGRID_AOV_PLANES, VptAdaptive, VptAovPlanes, VptSdfAovPlanes,
+from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SDF_AOV_PLANES, SHADER_NAMES, VOLGRID_AOV_PLANES, VOLGRID_CHROMA, VptAdaptive, VptAovPlanes, VptSdfAovPlanes,
                    VptVolgridAovPlanes, VptDisplay, VptError, VptLayout, VptParams,
                    VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, shader_id, _counted, _edit_call, _mesh_desc, _mesh_region, _meshed, _p, hip, host)
 from .edits import BvhRebuild, FilterEdit, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, VolumeSetEdit, mesh
@@ -355,6 +355,47 @@ class DeviceScene(_Handle):
         _check(hip.vpt_scene_volgrid_track(self.handle, n, rays.ctypes.data, rngs.ctypes.data, event.ctypes.data, instance.ctypes.data, t.ctypes.data,
                                            steps.ctypes.data, rngs_out.ctypes.data), "vpt_scene_volgrid_track")
         return event, instance, t, steps, rngs_out
+
+    def set_volgrid_color(self, on: bool) -> None:
+        """vpt_scene_set_volgrid_color (include/vpt.h): coloured extinction, k_c = -log(clamp(color_c, 1e-4, 1)) per channel of every grid
+        instance's material, for this handle's volgrid renders, session advances and adaptive rounds; off (the default): grey, as ever"""
+        _check(hip.vpt_scene_set_volgrid_color(self.handle, 1 if on else 0), "vpt_scene_set_volgrid_color")
+
+    @property
+    def volgrid_color(self) -> bool:
+        return bool(hip.vpt_scene_get_volgrid_color(self.handle))
+
+    def volgrid_chroma(self) -> np.ndarray:
+        """the coloured variant's table as the device holds it (vpt_scene_get_volgrid_chroma), whatever the switch says: one VOLGRID_CHROMA
+        row per grid instance - a (3,), kmax, trdepth_eff, whd (3,) of the coloured record - the bits of HostScene.volgrid_chroma"""
+        count = C.c_int(0)
+        _check(hip.vpt_scene_get_volgrid_chroma(self.handle, None, 0, C.byref(count)), "vpt_scene_get_volgrid_chroma")
+        out = np.zeros(count.value, VOLGRID_CHROMA)
+        _check(hip.vpt_scene_get_volgrid_chroma(self.handle, out.ctypes.data, len(out), None), "vpt_scene_get_volgrid_chroma")
+        return out
+
+    def volgrid_track_color(self, rays, rngs):
+        """the coloured flight on given rays and streams (as volgrid_track takes them), flown by the coloured kernel's own device functions
+        from w = (1, 1, 1) until a scatter, an escape or an abort (vpt_scene_volgrid_track_color), on the coloured tables whatever the
+        switch says: (event, instance, t, weight, passes, steps, rngs_out) = (n,) int32 0 escape / 1 scatter / 2 abort, (n,) int32 the
+        scatter's grid instance or -1, (n,) float32 its parameter along the ray or FLT_MAX, (n, 3) float32 the weight at the event, (n,)
+        int32 passes taken, (n,) int32 tracking steps over all flights, (n, 2) uint64 the streams afterwards"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        rngs = np.ascontiguousarray(rngs, np.uint64).reshape(-1, 2)
+        if len(rays) != len(rngs):
+            raise VptError(f"volgrid_track_color: {len(rays)} rays but {len(rngs)} streams")
+        n = len(rays)
+        event, instance, passes, steps = np.zeros(n, np.int32), np.full(n, -1, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        t, weight, rngs_out = np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 2), np.uint64)
+        _check(hip.vpt_scene_volgrid_track_color(self.handle, n, rays.ctypes.data, rngs.ctypes.data, event.ctypes.data, instance.ctypes.data, t.ctypes.data,
+                                                 weight.ctypes.data, passes.ctypes.data, steps.ctypes.data, rngs_out.ctypes.data), "vpt_scene_volgrid_track_color")
+        return event, instance, t, weight, passes, steps, rngs_out
+
+    def volgrid_color_passes(self) -> int:
+        """vpt_scene_volgrid_color_stats: passes taken by this handle's coloured volgrid launches so far"""
+        passes = C.c_uint64(0)
+        _check(hip.vpt_scene_volgrid_color_stats(self.handle, C.byref(passes)), "vpt_scene_volgrid_color_stats")
+        return passes.value
 
     def volgrid_stats(self) -> dict:
         """vpt_scene_volgrid_stats: tracking steps of this handle's volgrid launches so far, builds of its brick tables so far"""

@@ -180,6 +180,9 @@ struct color_image {
 };
 
 pathtrace_state  make_state(const scene_data& scene, const pathtrace_params& params);
+// Extension: coloured extinction for every later volgrid render, adaptive run and progressive session (include/vpt.h:
+// vpt_scene_set_volgrid_color), on one GPU - a render over several devices with it on throws; off by default
+void pathtrace_set_volgrid_color(bool on);
 // `quality`: VPT_BVH_MIDDLE (the reference's highquality = false, what every caller of the reference uses) or VPT_BVH_SAH (highquality =
 // true: split_sah, the rule at vpt_build_bvh_quality in include/vpt.h), for every tree of the scene; another value throws
 // std::invalid_argument.  The host build is the plain form of the rule: 45 passes over a node's primitives.

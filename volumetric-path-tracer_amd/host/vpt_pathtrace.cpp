@@ -716,6 +716,11 @@ device_entry& cached_entry(const scene_data& scene, const bvh_scene& bvh, const 
   }
   return *entry;
 }
+// pathtrace_set_volgrid_color: coloured extinction for the volgrid renders of the single-device copies (cache_mutex held)
+bool& volgrid_color_flag() {
+  static auto on = false;
+  return on;
+}
 // the copy of `scene` on the first device alone (cache_mutex held), made on first use: pathtrace_adaptive, pathtrace_aovs
 vpt_scene* single_scene(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights) {
   auto& entry = cached_entry(scene, bvh, lights);
@@ -728,6 +733,8 @@ vpt_scene* single_scene(const scene_data& scene, const bvh_scene& bvh, const pat
       throw std::runtime_error{string{"vpt_scene_create_curves: "} + vpt_last_error()};
     }
   }
+  if ((vpt_scene_get_volgrid_color(entry.single) != 0) != volgrid_color_flag() && vpt_scene_set_volgrid_color(entry.single, volgrid_color_flag()) != VPT_OK)
+    throw std::runtime_error{string{"vpt_scene_set_volgrid_color: "} + vpt_last_error()};
   return entry.single;
 }
 }  // namespace
@@ -809,11 +816,34 @@ void pathtrace_set_devices(const vector<int>& devices) {
   device_cache().clear();
 }
 
+void pathtrace_set_volgrid_color(bool on) {
+  auto lock = std::lock_guard{cache_mutex};
+  volgrid_color_flag() = on;
+}
+
 void pathtrace_samples(pathtrace_state& state, const scene_data& scene, const bvh_scene& bvh,
     const pathtrace_lights& lights, const pathtrace_params& params, int count) {
   if (state.samples >= params.samples) return;  // reference cpp:1055
   if (!pathtrace_shader_known(params.shader))
     throw std::runtime_error{"sampler unknown"};  // reference cpp:947-950
+  static_assert(sizeof(rng_state) == 16 && sizeof(vec4f) == 16, "state layout");
+  if ((int)params.shader == VPT_SHADER_VOLGRID) {   // coloured extinction is a switch of a single-device handle: vpt_multi_* renders grey
+    auto single = (vpt_scene*)nullptr;
+    {
+      auto lock = std::lock_guard{cache_mutex};
+      if (volgrid_color_flag()) {
+        if (device_list().size() > 1) throw std::runtime_error{"coloured volgrid extinction renders on one GPU"};
+        single = single_scene(scene, bvh, lights);
+      }
+    }
+    if (single) {
+      auto abi = to_abi(params);
+      if (vpt_render(single, &abi, count, state.width, state.height, (float*)state.image.data(), state.hits.data(), (uint64_t*)state.rngs.data(),
+              &state.samples) != VPT_OK)
+        throw std::runtime_error{string{"vpt_render: "} + vpt_last_error()};
+      return;
+    }
+  }
   auto handle = (vpt_multi*)nullptr;
   {
     auto  lock  = std::lock_guard{cache_mutex};

@@ -59,6 +59,31 @@ int vpth_volgrid_density(const vpt_scene_desc* d, int n, const float* points, in
   return 0;
 }
 
+// the coloured variant's chroma rows (include/vpt.h: vpt_scene_get_volgrid_chroma), one vpt_volgrid_chroma_row of 32 bytes per grid instance
+// in index order; count (nullable) receives their number, out is nullable with capacity 0
+int vpth_volgrid_chroma(const vpt_scene_desc* d, void* out, int capacity, int32_t* count, char* err, int err_len) {
+  if (!d || capacity < 0 || (capacity > 0 && !out)) return fail(err, err_len, "bad argument", 0, 0, 0);
+  if (count) *count = d->num_vol_instances;
+  if (!out) return 0;
+  if (capacity < d->num_vol_instances) return fail(err, err_len, "capacity %d < %d grid instances", capacity, d->num_vol_instances, 0);
+  for (int g = 0; g < d->num_vol_instances; g++) {
+    const vpt_volume_instance& vi = d->vol_instances[g];
+    const vpt_volgrid_chroma   ch = vpt_volgrid_make_chroma(d->materials[vi.material]);
+    ((vpt_volgrid_chroma_row*)out)[g] = vpt_volgrid_make_chroma_row(ch, vpt_volgrid_make_color_record(vi, d->volumes[vi.volume], d->materials[vi.material], 0, ch));
+  }
+  return 0;
+}
+
+// the event of a carrier collision (csrc/vpt_volgrid_rule.h: vpt_volgrid_event) on n rows {a[3], w[3], u}: kind[i] = 0 pass, 1 scatter, 2 end,
+// out[3 i ..] the weight after it, prob[i] = P, draws[i] = whether the event reads u
+void vpth_volgrid_event(int n, const float* rows, int32_t* kind, float* out, float* prob, int32_t* draws) {
+  for (int i = 0; i < n; i++) {
+    const float* r = rows + 7 * (size_t)i;
+    draws[i] = vpt_volgrid_event_draws(r, r + 3);
+    kind[i]  = vpt_volgrid_event(r, r + 3, r[6], out + 3 * (size_t)i, prob + i);
+  }
+}
+
 // the first-collision pass's normal of grid instance `instance` at n world points (vpt_volgrid_normal): gradient[3 i ..] the world
 // gradient of its voxel value, normal[3 i ..] = -normalize(gradient) or 0 (either nullable), inside[i] (nullable) whether the box holds the point
 int vpth_volgrid_gradient(const vpt_scene_desc* d, int instance, int n, const float* points, float* gradient, float* normal, int32_t* inside, char* err,

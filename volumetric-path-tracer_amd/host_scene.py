@@ -9,7 +9,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._abi import (BVH_MIDDLE, BVH_NODE, BVH_SAH, LIGHT, MESH_ELEMENTS, MESH_FLOATS, SDF_TYPES, VOLUME_COPY, VOLUME_FILL, VOLUME_FROM_BAKE, VOLUME_FROM_HOST, VOXELS_REPLACE, VptBakeStats, VptCamera,
+from ._abi import (BVH_MIDDLE, BVH_NODE, BVH_SAH, LIGHT, MESH_ELEMENTS, MESH_FLOATS, SDF_TYPES, VOLGRID_CHROMA, VOLUME_COPY, VOLUME_FILL, VOLUME_FROM_BAKE, VOLUME_FROM_HOST, VOXELS_REPLACE, VptBakeStats, VptCamera,
                    VptEnvironment, VptError, VptMaterial, VptSceneDescBvh, VptFilterEntry, VptSceneDescLights, VptSculptEntry, VptSdf, VptVolumeInstance, _Handle,
                    _check, _filled, _host_call, _mesh_desc, _mesh_region, _meshed, hip, host)
 from .device import PathtraceParams, PathtraceState
@@ -1023,6 +1023,14 @@ class HostScene(_Handle):
         sigma, instance = np.zeros(len(points), np.float32), np.full(len(points), -1, np.int32)
         _host_call(host.vpth_volgrid_density, self.desc, len(points), points.ctypes.data, instance.ctypes.data, sigma.ctypes.data)
         return sigma, instance
+
+    def volgrid_chroma(self) -> np.ndarray:
+        """the host mirror of DeviceScene.volgrid_chroma: one VOLGRID_CHROMA row per grid instance of the scene as it stands"""
+        count = C.c_int32(0)
+        _host_call(host.vpth_volgrid_chroma, self.desc, None, 0, C.byref(count))
+        out = np.zeros(count.value, VOLGRID_CHROMA)
+        _host_call(host.vpth_volgrid_chroma, self.desc, out.ctypes.data, len(out), None)
+        return out
 
     def volgrid_gradient(self, instance: int, points):
         """the normal the volgrid first-collision pass writes (include/vpt.h: vpt_render_volgrid_aov_device) for grid instance `instance`
