@@ -784,6 +784,56 @@ int vpt_scene_volgrid_track_color(vpt_scene* scene, int n, const float* rays, co
                                   float* weight /* 3 n */, int32_t* passes, int32_t* steps, uint64_t* rng_out /* nullable */);
 int vpt_scene_volgrid_color_stats(vpt_scene* scene, uint64_t* passes);
 
+/* ---- next-event estimation in the volgrid shader: ratio-tracked shadow flights -----------------------------------------
+ * A switch of the resident scene, off when it is made: vpt_scene_set_volgrid_nee(scene, on), in every respect like
+ * vpt_scene_set_volgrid_color: an edit like any other (launches are waited for, the edit count moves, the launch-schedule record is
+ * forgotten; setting the value it has is an empty edit), vpt_params stays byte for byte, and with it off nothing differs from a handle
+ * that never had it on.  With it on every volgrid render, session advance and adaptive round of the handle runs the NEE variant of K3.
+ * The two switches together are refused with VPT_ERR_UNSUPPORTED, whichever is set second, and the scene stays as it was.
+ *  - transmittance(ray, rng): ratio tracking over the brick majorants of the grey rule above.  T = 1.  The grid instances in index
+ *    order; each box clipped as `track` clips it, but against no tmax; the bricks walked as `track` walks them - the same node
+ *    coordinates, the same exits, the same nudge of 4e-5 of a cell.  A brick of majorant 0 is crossed without a draw.  In a brick of
+ *    majorant m (as extinction: its value / trdepth): t += -log(1 - rand1f(rng)) / m; past the brick's exit the flight goes on from the
+ *    exit point; otherwise T *= 1 - min(sigma(p) / m, 1) (csrc/vpt_volgrid_rule.h: vpt_volgrid_ratio_step) with NO second draw, and
+ *    T == 0 ends the flight at once.  Overlapping instances multiply.  A flight that has taken VPT_VOLGRID_MAX_STEPS steps returns T = 0
+ *    and counts in the word vpt_check_watchdog reads.
+ *  - The path.  E = the light-list entries with an environment, pdf_E the mixture pdf of the grey rule's MIS branch:
+ *        radiance = 0, weight = 1, esc_w = 1, hit = false
+ *        for bounce in [0, bounces):
+ *          ev = track(ray, rng);  an escape: radiance += weight * esc_w * eval_environment(ray.d), done
+ *          if bounce == 0: hit = true
+ *          radiance += weight * emission
+ *          if E is not empty and not noimplicit_mis and bounce + 1 < bounces:                        -- the light half
+ *            draw ruv.x, ruv.y, rel, rl as sample_lights draws them; wl = the environment branch for the entry sample_uniform(|E|, rl)
+ *            f = eval_phasefunction(g, outgoing, wl); p = pdf_E(position, wl)
+ *            c = (f + p > 0) ? weight * albedo * eval_environment(wl) * (f / (f + p)) : 0
+ *            if c is neither zero nor not finite: radiance += c * transmittance((position, wl), rng)
+ *          draw rn.x, rn.y, rnl as sample_scattering draws them; incoming = sample_phasefunction(g, outgoing, rn); weight *= albedo
+ *          esc_w = (the light half ran) ? f_i / (f_i + pdf_E(position, incoming)) : 1, f_i = eval_phasefunction(g, outgoing, incoming)
+ *          weight zero or not finite: done;  the roulette of the grey rule (bounce > 3, min(1, max(weight)))
+ *          ray = (position, incoming)
+ *    The light sample and the phase sample are two estimators of the same direct light, combined by the balance heuristic; the gate
+ *    bounce + 1 < bounces keeps the expectation that of the grey rule's truncated path (a light sample at the last allowed collision
+ *    would be light through one scattering too many).  noimplicit_mis means no light sampling at all: it switches the light half off.
+ *    WITH BOTH HALVES OFF - E empty, noimplicit_mis, or at the last allowed collision - a vertex draws exactly what the grey rule's
+ *    noimplicit_mis branch draws (rn.x, rn.y, rnl) and esc_w is 1: such a path is the grey path bit for bit.  Alpha, hits[], the camera
+ *    draws, the preview branch and the NaN guard are the grey rule's.
+ *  - What stays as it is: vpt_scene_volgrid_track, the first-collision pass and picking (they do not light); vpt_multi_* handles have
+ *    no switch.
+ * vpt_scene_get_volgrid_nee: the switch.
+ * vpt_scene_volgrid_transmittance: transmittance() on n given rays and streams, as vpt_scene_volgrid_track takes them and with its
+ * argument checks, one lane per record, through the device function the NEE kernel itself calls, compiled in its unit, on the grey tables
+ * (brought up to date first) whatever the switches say; VPT_VOLGRID_NO_BRICKS is honoured.  T[i] in [0, 1]; steps[i] the tracking steps
+ * of the flight (VPT_VOLGRID_MAX_STEPS: the flight ran into the bound, T[i] = 0).  No stats word counts it.
+ * vpt_scene_volgrid_nee_stats: shadow flights flown by the handle's NEE launches so far, and their tracking steps (either nullable) -
+ * these steps are no part of vpt_scene_volgrid_stats' word; synchronous.
+ * vpt_session_set_volgrid_nee: the switch of the session's scene, then a reset, as after an edit. */
+int vpt_scene_set_volgrid_nee(vpt_scene* scene, int on);
+int vpt_scene_get_volgrid_nee(const vpt_scene* scene);
+int vpt_scene_volgrid_transmittance(vpt_scene* scene, int n, const float* rays /* n x {o, d} */, const uint64_t* rng_in /* n x {state, inc} */,
+                                    float* T, int32_t* steps, uint64_t* rng_out /* n x {state, inc}, nullable */);
+int vpt_scene_volgrid_nee_stats(vpt_scene* scene, uint64_t* flights, uint64_t* steps);
+
 /* ---- the BVHs of a resident scene built anew on the device ------------------------------------------------------------
  * The four edits above keep a tree's topology as creation left it: vpt_scene_update is the reference's update_bvh, a refit.  After a
  * real deformation, or after instances have been rearranged, boxes and renders stay correct but the tree no longer fits the geometry.
@@ -1545,6 +1595,8 @@ int  vpt_session_filter_volumes(vpt_session* session, const vpt_filter_edit* edi
 /* vpt_scene_set_volgrid_color, then a reset.  The session stays a volgrid session: its pick, id frame and first-collision pass keep
  * meaning the grey flight */
 int  vpt_session_set_volgrid_color(vpt_session* session, int on);
+/* vpt_scene_set_volgrid_nee, then a reset; a refusal (coloured extinction is on) leaves the session as it was */
+int  vpt_session_set_volgrid_nee(vpt_session* session, int on);
 /* vpt_scene_update_volume_set, then a reset (which drops both id frames: pick_sdf never names an entry that is gone); a refused edit
  * leaves the session as it was */
 int  vpt_session_edit_volume_set(vpt_session* session, const vpt_volume_set_edit* edit);

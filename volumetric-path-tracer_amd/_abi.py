@@ -559,6 +559,11 @@ hip.vpt_scene_get_volgrid_chroma.argtypes = [_p, _p, C.c_int, C.POINTER(C.c_int)
 hip.vpt_scene_volgrid_track_color.argtypes = [_p, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p]
 hip.vpt_scene_volgrid_color_stats.argtypes = [_p, C.POINTER(C.c_uint64)]
 hip.vpt_session_set_volgrid_color.argtypes = [_p, C.c_int]
+hip.vpt_scene_set_volgrid_nee.argtypes = [_p, C.c_int]
+hip.vpt_scene_get_volgrid_nee.argtypes = [_p]
+hip.vpt_scene_volgrid_transmittance.argtypes = [_p, C.c_int, _p, _p, _p, _p, _p]
+hip.vpt_scene_volgrid_nee_stats.argtypes = [_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+hip.vpt_session_set_volgrid_nee.argtypes = [_p, C.c_int]
 # a row of vpt_scene_get_volgrid_chroma / vpth_volgrid_chroma (csrc/vpt_volgrid_rule.h: vpt_volgrid_chroma_row)
 VOLGRID_CHROMA = np.dtype([("a", np.float32, 3), ("kmax", np.float32), ("trdepth_eff", np.float32), ("whd", np.int32, 3)])
 host.vpth_mesh_sdf.argtypes = [C.POINTER(VptSdfMeshDesc), _p, C.POINTER(VptSdfMeshRegion), _p, _p, C.c_int32, _p, C.c_int32, C.POINTER(VptSdfMeshStats),

@@ -253,9 +253,22 @@ int vpt_scene_update_subdivs(vpt_scene* s, const vpt_subdiv_edit* edit) { return
 // the coloured variant of K3 for this handle's volgrid launches: no table of the resident changes, the render side's tables follow the edit count
 int vpt_scene_set_volgrid_color(vpt_scene* s, int on) {
   const bool want = on != 0;
+  REQUIRE(s, "null argument");
+  if (want && s->volgrid.nee) return vpt_set_error(VPT_ERR_UNSUPPORTED, "volgrid: coloured extinction cannot be combined with next-event estimation (vpt_scene_set_volgrid_nee is on)");
   return edit_scene(s, &want, [s](resident&, const bool& w, edit_outcome& out) {
     out.changed      = s->volgrid.color != w;
     s->volgrid.color = w;
+    return VPT_OK;
+  });
+}
+// the NEE variant of K3 for this handle's volgrid launches, in every respect like the switch above; the two together are refused
+int vpt_scene_set_volgrid_nee(vpt_scene* s, int on) {
+  const bool want = on != 0;
+  REQUIRE(s, "null argument");
+  if (want && s->volgrid.color) return vpt_set_error(VPT_ERR_UNSUPPORTED, "volgrid: next-event estimation cannot be combined with coloured extinction (vpt_scene_set_volgrid_color is on)");
+  return edit_scene(s, &want, [s](resident&, const bool& w, edit_outcome& out) {
+    out.changed    = s->volgrid.nee != w;
+    s->volgrid.nee = w;
     return VPT_OK;
   });
 }

@@ -103,6 +103,25 @@ __global__ void __launch_bounds__(VPT_BLOCK, VPT_K3_WAVES) vpt_volgrid_color_ker
 __global__ void vpt_volgrid_track_color_kernel(DScene sc, volgrid_args va, volgrid_color_args vc, int n, const float* __restrict__ rays,
     const ulonglong2* __restrict__ rng_in, int* __restrict__ event, int* __restrict__ instance, float* __restrict__ t, float* __restrict__ weight,
     int* __restrict__ passes, int* __restrict__ steps, ulonglong2* __restrict__ rng_out);
+// K3's NEE variant (include/vpt.h: vpt_scene_set_volgrid_nee; instances: vpt_k3_nee.hip): the grey records and tables of K3; the two
+// counters it adds travel in an argument of their own, so that volgrid_args stays byte for byte what K3 is compiled for
+struct volgrid_nee_args {
+  unsigned long long* flights;   // shadow flights flown since the handle was made (vpt_scene_volgrid_nee_stats)
+  unsigned long long* steps;     // their tracking steps: not part of volgrid_args::steps
+};
+// its waves per SIMD: at 4 the parked vertex does not fit under 128 VGPRs (10 spilled, 44 bytes of scratch per lane without the packed
+// float32 instructions, 36 and 88 bytes with them); at 3 it takes 146 of 168 and has no scratch.  -DVPT_K3_NEE_WAVES=4 on
+// the unit's compile line gives the other row of that table
+#ifndef VPT_K3_NEE_WAVES
+#define VPT_K3_NEE_WAVES 3
+#endif
+template <bool PILOT>
+__global__ void __launch_bounds__(VPT_BLOCK, VPT_K3_NEE_WAVES) vpt_volgrid_nee_kernel(DScene sc, DParams pr, volgrid_args va, volgrid_nee_args vn,
+    float4* __restrict__ image, int* __restrict__ hits, ulonglong2* __restrict__ rngs, sched_cfg sched);
+// the probe of vpt_scene_volgrid_transmittance: one lane per record flies one shadow flight through the NEE kernel's vg_nee_step (defined
+// in vpt_k3_nee.hip)
+__global__ void vpt_volgrid_transmittance_kernel(DScene sc, volgrid_args va, int n, const float* __restrict__ rays, const ulonglong2* __restrict__ rng_in,
+    float* __restrict__ T, int* __restrict__ steps, ulonglong2* __restrict__ rng_out);
 
 // ---- vpt_intersect, KAT, self-tests (vpt_kernels.hip, but for vpt_intersect_curves_kernel: vpt_k1_curves.hip) ----------------
 template <bool SPILL, bool COMPACT>

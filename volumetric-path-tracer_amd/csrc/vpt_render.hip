@@ -81,6 +81,12 @@ static void launch_volgrid_instance(const launch_ctx& L, bool is_pilot, dim3 gri
   }
   const volgrid_args va  = volgrid_arguments(L.s);
   const size_t       lds = (size_t)va.num_instances * 128;
+  if (L.s->volgrid.nee) {   // vpt_scene_set_volgrid_nee: the NEE variant over K3's own records and tables
+    const volgrid_nee_args vn = volgrid_nee_arguments(L.s);
+    if (is_pilot) hipLaunchKernelGGL(vpt_volgrid_nee_kernel<true>, grid, dim3(VPT_BLOCK), lds, L.st, L.s->d, pr, va, vn, L.img, L.hit, L.rng, sch);
+    else hipLaunchKernelGGL(vpt_volgrid_nee_kernel<false>, grid, dim3(VPT_BLOCK), lds, L.st, L.s->d, pr, va, vn, L.img, L.hit, L.rng, sch);
+    return;
+  }
   if (is_pilot) hipLaunchKernelGGL(vpt_volgrid_kernel<true>, grid, dim3(VPT_BLOCK), lds, L.st, L.s->d, pr, va, L.img, L.hit, L.rng, sch);
   else hipLaunchKernelGGL(vpt_volgrid_kernel<false>, grid, dim3(VPT_BLOCK), lds, L.st, L.s->d, pr, va, L.img, L.hit, L.rng, sch);
 }

@@ -18,6 +18,8 @@ struct volgrid_tables {
   bool               color = false;                       // vpt_scene_set_volgrid_color
   unsigned long long built_color = 0;                     // edit_generation the coloured tables were built at: only a handle with the switch on, a
                                                           // read-back of them or the coloured probe builds them - a grey handle never pays for them
+  device_buffer      nee_counters;                        // the NEE variant's: shadow flights, then their steps (two 64-bit words)
+  bool               nee = false;                         // vpt_scene_set_volgrid_nee
   std::vector<int>   brick_offset;                        // per volume: its table in the pool (nbx * nby * nbz majorants, then their maximum)
   long long          num_bricks = 0;                      // floats of the pool
   int                num_env_lights = 0;
@@ -80,6 +82,8 @@ volgrid_args volgrid_arguments(const vpt_scene* s);
 // the two arguments of the coloured variant: K3's with the coloured records in place of the grey ones, and what colour adds
 volgrid_args       volgrid_color_arguments(const vpt_scene* s);
 volgrid_color_args volgrid_chroma_arguments(const vpt_scene* s);
+// what the NEE variant takes beside K3's own argument: its two counters
+volgrid_nee_args volgrid_nee_arguments(const vpt_scene* s);
 // what a shader's kernel needs of the scene before its launches: K2 room for the SDF records in LDS, K3 its tables, K1 nothing
 inline int shader_setup(vpt_scene* s, const vpt_params* p, hipStream_t st) {
   if (p->shader == VPT_SHADER_VOLGRID) return volgrid_prepare(s, st);

@@ -484,6 +484,12 @@ int vpt_session_set_volgrid_color(vpt_session* s, int on) {   // no edit's count
   if (int rc = vpt_scene_set_volgrid_color(s->scene, on)) return rc;
   return reset(s, s->p);
 }
+int vpt_session_set_volgrid_nee(vpt_session* s, int on) {   // as the colour switch above
+  REQUIRE(s, "null session");
+  begin_call(s);
+  if (int rc = vpt_scene_set_volgrid_nee(s->scene, on)) return rc;
+  return reset(s, s->p);
+}
 int vpt_session_edit_volume_set(vpt_session* s, const vpt_volume_set_edit* edit) { return session_edit(s, edit, vpt_scene_update_volume_set); }
 int vpt_session_rebuild_bvh(vpt_session* s, const vpt_bvh_rebuild* what) { return vpt_session_rebuild_bvh_quality(s, what, VPT_BVH_MIDDLE); }
 int vpt_session_rebuild_bvh_quality(vpt_session* s, const vpt_bvh_rebuild* what, int quality) {

@@ -136,8 +136,20 @@ int sync_color_tables(vpt_scene* s, hipStream_t st) {
 
 }  // namespace
 
+// the NEE variant's two counters, made when the first launch or probe of the handle needs them
+static int sync_nee_counters(vpt_scene* s, hipStream_t st) {
+  volgrid_tables& t = s->volgrid;
+  if (t.nee_counters.get()) return VPT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  if (int rc = t.nee_counters.allocate(16)) return rc;
+  HIP_TRY(hipMemsetAsync(t.nee_counters.get(), 0, 16, st));
+  return VPT_OK;
+}
+
 int volgrid_prepare(vpt_scene* s, hipStream_t st) {
   if (int rc = check_media(s)) return rc;
+  if (s->volgrid.nee)
+    if (int rc = sync_nee_counters(s, st)) return rc;
   return s->volgrid.color ? sync_color_tables(s, st) : sync_tables(s, st);
 }
 
@@ -157,7 +169,12 @@ volgrid_color_args volgrid_chroma_arguments(const vpt_scene* s) {
   return {s->volgrid.chroma.get<const vpt_volgrid_chroma>(), s->volgrid.passes.get<unsigned long long>()};
 }
 
-// the checks of a probe's rays (vpt_scene_volgrid_track, vpt_scene_volgrid_track_color)
+volgrid_nee_args volgrid_nee_arguments(const vpt_scene* s) {
+  unsigned long long* c = s->volgrid.nee_counters.get<unsigned long long>();
+  return {c, c + 1};
+}
+
+// the checks of a probe's rays (vpt_scene_volgrid_track, vpt_scene_volgrid_track_color, vpt_scene_volgrid_transmittance)
 static int check_rays(const char* who, int n, const float* rays) {
   for (int i = 0; i < n; i++) {
     const float* r = rays + 6 * (size_t)i;
@@ -254,6 +271,45 @@ int vpt_scene_volgrid_track_color(vpt_scene* s, int n, const float* rays, const 
   for (int k = 0; k < 5; k++) HIP_TRY(hipMemcpy(dst[k], o + k * N, N * 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(weight, o + 5 * N, N * 12, hipMemcpyDeviceToHost));
   if (rng_out) HIP_TRY(hipMemcpy(rng_out, rg + n, N * 16, hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+
+int vpt_scene_volgrid_transmittance(vpt_scene* s, int n, const float* rays, const uint64_t* rng_in, float* T, int32_t* steps, uint64_t* rng_out) {
+  REQUIRE(s && n >= 0 && (n == 0 || (rays && rng_in && T && steps)), "bad argument");
+  if (int rc = check_rays("volgrid_transmittance", n, rays)) return rc;
+  if (int rc = check_media(s)) return rc;
+  if (int rc = sync_tables(s, nullptr)) return rc;   // the grey tables, whatever the handle's switches say
+  if (n == 0) return VPT_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  device_buffer d_rays, d_rng, d_out;   // d_out: T, steps - two planes of n words
+  if (int rc = d_rays.allocate((size_t)n * 24)) return rc;
+  if (int rc = d_rng.allocate((size_t)n * 32)) return rc;   // in, then out
+  if (int rc = d_out.allocate((size_t)n * 8)) return rc;
+  HIP_TRY(hipMemcpy(d_rays.get(), rays, (size_t)n * 24, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_rng.get(), rng_in, (size_t)n * 16, hipMemcpyHostToDevice));
+  float*      o  = d_out.get<float>();
+  ulonglong2* rg = d_rng.get<ulonglong2>();
+  hipLaunchKernelGGL(vpt_volgrid_transmittance_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, s->d, volgrid_arguments(s), n,
+      d_rays.get<const float>(), (const ulonglong2*)rg, o, (int*)(o + (size_t)n), rng_out ? rg + n : nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(T, o, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(steps, o + (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (rng_out) HIP_TRY(hipMemcpy(rng_out, rg + n, (size_t)n * 16, hipMemcpyDeviceToHost));
+  return VPT_OK;
+}
+
+int vpt_scene_get_volgrid_nee(const vpt_scene* s) { return s && s->volgrid.nee ? 1 : 0; }
+
+int vpt_scene_volgrid_nee_stats(vpt_scene* s, uint64_t* flights, uint64_t* steps) {
+  REQUIRE(s, "null argument");
+  uint64_t both[2] = {0, 0};
+  if (s->volgrid.nee_counters.get()) {
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(both, s->volgrid.nee_counters.get(), 16, hipMemcpyDeviceToHost));
+  }
+  if (flights) *flights = both[0];
+  if (steps) *steps = both[1];
   return VPT_OK;
 }
 

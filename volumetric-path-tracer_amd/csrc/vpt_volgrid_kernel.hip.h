@@ -40,6 +40,8 @@
 #define VPT_K3_SHADE_AT 20   // lanes waiting for the shading block before the wave runs it
 
 enum { V_NEW = 0, V_TRACK = 1, V_COLLIDE = 2, V_ESCAPE = 3, V_ABORT = 4, V_DONE = 5 };
+// the NEE variant's (below): in a shadow flight; a shadow flight that has crossed the medium or reached T == 0; one that ran into its step bound
+enum { V_SHADOW = 6, V_LIT = 7, V_SHADOW_ABORT = 8 };
 
 // a free flight in progress
 struct vg_walk {
@@ -121,6 +123,94 @@ VPT_DEV int vg_track_step(const DScene& sc, const volgrid_args& va, const vpt_vo
   return V_TRACK;
 }
 
+// One tracking step of a NEE kernel (include/vpt.h: vpt_scene_set_volgrid_nee): ONE body for the two kinds of flight a lane can be in, so
+// that a round of VPT_K3_STEPS serves track lanes and shadow lanes in the same instructions.  Entering an instance, locating the brick, its
+// exit, the exponential draw and the 4e-5 nudge are vg_track_step's, statement for statement (a track lane of this function draws and
+// computes what vg_track_step does, bit for bit); only what a tentative collision means is selected per lane:
+//   mode == V_TRACK    the second draw decides whether it is real, and a real one clips the rest of the flight (w.tmax)
+//   mode == V_SHADOW   ratio tracking: T *= 1 - min(sigma / m, 1), no second draw; w.tmax is never set, so every box is clipped against
+//                      FLT_MAX - against no tmax - and the flight crosses every instance; T == 0 ends it at once
+// Returns `mode` while the flight goes on.  A shadow flight ends V_LIT (instances exhausted, or T == 0) or V_SHADOW_ABORT (the step bound).
+VPT_DEV int vg_nee_step(const DScene& sc, const volgrid_args& va, const vpt_volgrid_record* recs, f3 ro, f3 rd, rng_t& rng, vg_walk& w, int mode, float& T) {
+  const bool shadow = mode == V_SHADOW;
+  if (w.steps >= VPT_VOLGRID_MAX_STEPS) return shadow ? V_SHADOW_ABORT : V_ABORT;
+  w.steps++;
+  if (!(w.t < w.t_end)) {   // enter the next instance (a shadow lane: w.tmax is FLT_MAX for the whole flight)
+    w.g++;
+    if (w.g >= va.num_instances) return shadow ? V_LIT : (w.hit_g >= 0 ? V_COLLIDE : V_ESCAPE);
+    const vpt_volgrid_record& rec = recs[w.g];
+    float ol[3], dl[3];
+    vpt_volgrid_to_local(rec.frame, ro.x, ro.y, ro.z, ol);
+    vpt_volgrid_vector_to_local(rec.frame, rd.x, rd.y, rd.z, dl);
+    float t0 = 0, t1 = w.tmax;
+    bool  miss = rec.whd[0] <= 0 || rec.whd[1] <= 0 || rec.whd[2] <= 0;
+    for (int k = 0; k < 3; k++) {
+      if (dl[k] == 0) miss = miss || !(ol[k] >= 0 && ol[k] <= rec.bbox[k]);
+      else {
+        const float ta = (0 - ol[k]) / dl[k], tb = (rec.bbox[k] - ol[k]) / dl[k];
+        t0 = fmax_(t0, fmin_(ta, tb)), t1 = fmin_(t1, fmax_(ta, tb));
+      }
+    }
+    w.t = w.t_end = 0;
+    if (!miss && t0 < t1) {
+      w.t = t0, w.t_end = t1;
+      w.dn = mk3(dl[0] / rec.bbox[0] * (rec.whd[0] - 1), dl[1] / rec.bbox[1] * (rec.whd[1] - 1), dl[2] / rec.bbox[2] * (rec.whd[2] - 1));
+    }
+    return mode;
+  }
+  const vpt_volgrid_record& rec = recs[w.g];
+  const int nbx = vpt_volgrid_bricks(rec.whd[0]), nby = vpt_volgrid_bricks(rec.whd[1]), nbz = vpt_volgrid_bricks(rec.whd[2]);
+  float texit = w.t_end, mj;
+  if (va.no_bricks) mj = va.bricks[rec.brick_offset + nbx * nby * nbz];
+  else {
+    float pl[3], node[3];
+    const f3 p = ro + rd * w.t;
+    vpt_volgrid_to_local(rec.frame, p.x, p.y, p.z, pl);
+    int b[3];
+    const float dn[3] = {w.dn.x, w.dn.y, w.dn.z};
+    const int   nb[3] = {nbx, nby, nbz};
+    for (int k = 0; k < 3; k++) {
+      node[k] = vpt_volgrid_node_coord(pl[k], rec.bbox[k], rec.whd[k]);
+      b[k]    = vpt_volgrid_brick_of(node[k], nb[k]);
+      if (dn[k] < 0 && b[k] > 0 && node[k] == (float)(b[k] * VPT_VOLGRID_BRICK)) b[k]--;
+      if (dn[k] > 0) texit = fmin_(texit, w.t + ((float)((b[k] + 1) * VPT_VOLGRID_BRICK) - node[k]) / dn[k]);
+      else if (dn[k] < 0) texit = fmin_(texit, w.t + ((float)(b[k] * VPT_VOLGRID_BRICK) - node[k]) / dn[k]);
+    }
+    mj = va.bricks[rec.brick_offset + b[0] + nbx * (b[1] + nby * b[2])];
+  }
+  if (mj > 0) {
+    const float m  = mj / rec.trdepth;
+    const float tn = w.t + -logf(1 - rand1f(rng)) / m;
+    if (tn < texit) {   // a tentative collision inside the brick
+      w.t = tn;
+      const f3    p     = ro + rd * tn;
+      const float sigma = vpt_volgrid_density(rec, sc.voxels, p.x, p.y, p.z);
+      const float real  = fmin_(sigma / m, 1.0f);   // the probability that it is real
+      if (shadow) {
+        T = vpt_volgrid_ratio_step(T, real);
+        if (T == 0) return V_LIT;
+      } else if (rand1f(rng) < real) w.tmax = tn, w.hit_g = w.g, w.t_end = tn;
+      return mode;
+    }
+  }
+  if (!(texit > w.t)) {
+    const float dmax = fmax_(fabs_(w.dn.x), fmax_(fabs_(w.dn.y), fabs_(w.dn.z)));
+    texit = dmax > 0 ? fmin_(w.t_end, w.t + (4e-5f / dmax + w.t * 2.4e-7f)) : w.t_end;
+  }
+  w.t = texit;
+  return mode;
+}
+// transmittance(ray, rng) (include/vpt.h) as one loop: what a shadow lane of the NEE kernel computes over its rounds, for the probe.
+// Returns T; `aborted` says that the flight ran into VPT_VOLGRID_MAX_STEPS (T is then 0)
+VPT_DEV float vg_transmittance(const DScene& sc, const volgrid_args& va, const vpt_volgrid_record* recs, f3 ro, f3 rd, rng_t& rng, vg_walk& w, bool& aborted) {
+  float T = 1.0f;
+  vg_start(w);
+  int mode = V_SHADOW;
+  while (mode == V_SHADOW) mode = vg_nee_step(sc, va, recs, ro, rd, rng, w, mode, T);
+  aborted = mode == V_SHADOW_ABORT;
+  return aborted ? 0.0f : T;
+}
+
 // the light-list entries with an environment, in list order: the k-th of them
 VPT_DEV int vg_env_light(const DScene& sc, int k) {
   int l = 0;
@@ -159,9 +249,18 @@ VPT_DEV float vg_env_pdf(const DScene& sc, int num_env, f3 position, f3 directio
 // shading block decides the event of csrc/vpt_volgrid_rule.h at every carrier collision: a scatter goes on as K3's collision does, a pass
 // puts the lane straight back into V_TRACK with a fresh walk from the collision point - no camera work, no phase work, bounce unmoved.
 // No weight is attached to a tracking step, so the per-instance walk with the nearest collision winning stays exact.
-template <bool COLOR>
+//
+// NEE: next-event estimation with ratio-tracked shadow flights (include/vpt.h: vpt_scene_set_volgrid_nee).  At a collision
+// the light half draws a direction towards an environment and the lane flies a SHADOW FLIGHT there before it draws its phase direction:
+// a second kind of flight in the same rounds (mode V_SHADOW beside V_TRACK, one step body for both: vg_nee_step).  For its duration the
+// half-shaded vertex is parked in registers - the pending contribution c, T, the outgoing direction, esc_w - ro is the collision point
+// and rd the light direction; w.hit_g keeps naming the collision's instance (a shadow walk never writes it).  A flight that has left
+// V_SHADOW waits for the shading block like any other lane; there c * T is added, the phase direction drawn, and the lane is back in
+// V_TRACK.  The lane's draws stay serial in its own stream in the rule's order: light half, flight, phase half.
+template <bool COLOR, bool NEE = false>
 __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DParams& pr, const volgrid_args& va, const volgrid_color_args* vc,
-    float4* __restrict__ image, int* __restrict__ hits, ulonglong2* __restrict__ rngs, const sched_cfg& sched) {
+    float4* __restrict__ image, int* __restrict__ hits, ulonglong2* __restrict__ rngs, const sched_cfg& sched, const volgrid_nee_args* vn = nullptr) {
+  static_assert(!(COLOR && NEE), "a coloured shadow flight is not built");
   extern __shared__ int4 lds_recs4[];
   // the records, copied once into LDS (read at every tracking step)
   {
@@ -208,13 +307,28 @@ __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DPar
   unsigned long long steps = 0;
   [[maybe_unused]] int                passes = 0;         // COLOR: of the path in flight
   [[maybe_unused]] unsigned           passes_total = 0;   // COLOR: of the lane since it last added them to the handle's counter
+  // NEE: the parked vertex of a shadow flight - the pending contribution, T, the outgoing direction of the phase draw that follows - and
+  // the MIS weight an escape of the flight in progress carries (1 unless the light half ran at the vertex it left)
+  [[maybe_unused]] f3                 park_c = mk3(0, 0, 0), park_out = mk3(0, 0, 1);
+  [[maybe_unused]] float              T = 1, esc_w = 1;
+  [[maybe_unused]] unsigned long long shadow_steps = 0;     // NEE: of the lane, added to the handle's counters once at the end
+  [[maybe_unused]] unsigned           shadow_flights = 0;   // (flushed before it can wrap)
 
   while (true) {
-    const unsigned long long tracking = __builtin_amdgcn_ballot_w64(mode == V_TRACK);
-    const unsigned long long waiting  = __builtin_amdgcn_ballot_w64(mode != V_TRACK && mode != V_DONE);
+    unsigned long long tracking = __builtin_amdgcn_ballot_w64(mode == V_TRACK);
+    unsigned long long waiting  = __builtin_amdgcn_ballot_w64(mode != V_TRACK && mode != V_DONE);
+    if constexpr (NEE) {   // a shadow lane counts as tracking
+      const unsigned long long shadowing = __builtin_amdgcn_ballot_w64(mode == V_SHADOW);
+      tracking |= shadowing, waiting &= ~shadowing;
+    }
     if ((tracking | waiting) == 0) break;   // every lane V_DONE
 
     if (tracking != 0 && __popcll(waiting) < shade_at) {
+      if constexpr (NEE) {
+        for (int k = 0; k < VPT_K3_STEPS; k++)
+          if (mode == V_TRACK || mode == V_SHADOW) mode = vg_nee_step(sc, va, recs, ro, rd, rng, w, mode, T);
+        continue;
+      }
       for (int k = 0; k < VPT_K3_STEPS; k++)
         if (mode == V_TRACK) mode = vg_track_step(sc, va, recs, ro, rd, rng, w);
       continue;
@@ -222,6 +336,10 @@ __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DPar
 
     // ---- shading block: the lanes that wait for it ---------------------------------------------------
     bool finish = false;
+    [[maybe_unused]] bool vertex = false, lit = false;   // NEE: the phase half of a vertex is due; its light half ran
+    [[maybe_unused]] f3   vpos = ro, vout = park_out;    // NEE: that vertex - after a shadow flight the parked one
+    if constexpr (NEE)
+      if (mode == V_ESCAPE) weight = weight * esc_w;   // the phase sample's share of the sky (the path ends here: weight is read once more)
     if (mode == V_ESCAPE) {
       radiance = radiance + weight * eval_environment(sc, rd);
       steps += w.steps;
@@ -237,6 +355,30 @@ __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DPar
       const f3 albedo = mk3(rec.albedo[0], rec.albedo[1], rec.albedo[2]);
       if (bounce == 0) hit = 1;   // (COLOR: the first carrier collision of the camera flight, before the event: the densest channel's opacity)
       bool scatter = true;
+      if constexpr (NEE) {   // the rule's collision in place of K3's below: emission, the light half; then a shadow flight or the phase half
+        scatter  = false;
+        radiance = radiance + weight * mk3(rec.emission[0], rec.emission[1], rec.emission[2]);
+        vertex = true, vpos = position, vout = outgoing;
+        if (mis && bounce + 1 < nb) {   // a light sample at the last allowed collision would be light through one scattering too many
+          lit = true;
+          f2 ruv;   // as sample_lights draws: ruv, rel, rl
+          ruv.x = rand1f(rng);
+          ruv.y = rand1f(rng);
+          const float rel = rand1f(rng);
+          const float rl  = rand1f(rng);
+          const f3    wl  = vg_sample_env(sc, vg_env_light(sc, sample_uniform(va.num_env_lights, rl)), rel, ruv);
+          const float f   = eval_phasefunction(rec.g, outgoing, wl);
+          const float p   = vg_env_pdf(sc, va.num_env_lights, position, wl);
+          const f3    c   = f + p > 0 ? weight * albedo * eval_environment(sc, wl) * (f / (f + p)) : mk3(0, 0, 0);
+          if (!is_zero3(c) && finite3(c)) {   // fly: park the vertex, the lane's ray is the shadow ray
+            park_c = c, park_out = outgoing, T = 1;
+            ro = position, rd = wl, mode = V_SHADOW, vertex = false;
+            const int hit_g = w.hit_g;
+            vg_start(w);
+            w.hit_g = hit_g;
+          }
+        }
+      }
       if constexpr (COLOR) {
         const vpt_volgrid_chroma& ch = chroma[w.hit_g];
         float wv[3] = {weight.x, weight.y, weight.z};
@@ -299,6 +441,43 @@ __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DPar
         }
       }
     }
+    if constexpr (NEE) {
+      if (mode == V_LIT || mode == V_SHADOW_ABORT) {   // the shadow flight is back: its result, then the phase half of the parked vertex
+        shadow_steps += w.steps;
+        if (++shadow_flights == 0x80000000u) atomicAdd(vn->flights, (unsigned long long)shadow_flights), shadow_flights = 0;
+        if (mode == V_SHADOW_ABORT) aborted++, T = 0;
+        radiance = radiance + park_c * T;
+        vertex = true, lit = true;   // vpos = ro, vout = park_out: as initialised
+      }
+      if (vertex) {
+        const vpt_volgrid_record& rec = recs[w.hit_g];
+        f2 rn;   // as sample_scattering draws: rn, then the rnl nobody reads
+        rn.x = rand1f(rng);
+        rn.y = rand1f(rng);
+        (void)rand1f(rng);
+        const f3 incoming = sample_phasefunction(rec.g, vout, rn);
+        weight = weight * mk3(rec.albedo[0], rec.albedo[1], rec.albedo[2]);
+        esc_w  = 1;
+        if (lit) {
+          const float fi = eval_phasefunction(rec.g, vout, incoming);
+          esc_w = fi / (fi + vg_env_pdf(sc, va.num_env_lights, vpos, incoming));
+        }
+        if (is_zero3(weight) || !finite3(weight)) finish = true;
+        else if (bounce > 3) {
+          const float rr = fmin_(1.0f, max3(weight));
+          if (rr < 1) {
+            if (rand1f(rng) >= rr) finish = true;
+            else weight = weight / rr;
+          }
+        }
+        bounce++;
+        if (bounce >= nb) finish = true;
+        if (!finish) {   // (else `finish` below makes the lane V_NEW, a returned shadow lane too)
+          ro = vpos, rd = incoming, mode = V_TRACK;
+          vg_start(w);
+        }
+      }
+    }
     if (finish) {
       f4 rad = mk4(radiance.x, radiance.y, radiance.z, hit);
       if (!(isfinite(rad.x) && isfinite(rad.y) && isfinite(rad.z) && isfinite(rad.w))) rad = mk4(0, 0, 0, 0);
@@ -324,6 +503,7 @@ __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DPar
         radiance = mk3(0, 0, 0), weight = mk3(1, 1, 1), hit = 0;
         bounce = 0, mode = V_TRACK;
         if constexpr (COLOR) passes = 0;
+        if constexpr (NEE) esc_w = 1;
         vg_start(w);
         if (nb <= 0) mode = V_ESCAPE, weight = mk3(0, 0, 0);   // no bounce allowed: the loop body never runs (radiance 0, no hit)
       }
@@ -340,6 +520,10 @@ __device__ __forceinline__ void volgrid_kernel_body(const DScene& sc, const DPar
     if (va.steps) atomicAdd(va.steps, steps);
     if constexpr (COLOR)
       atomicAdd(vc->passes, (unsigned long long)passes_total);
+    if constexpr (NEE) {
+      atomicAdd(vn->steps, shadow_steps);
+      atomicAdd(vn->flights, (unsigned long long)shadow_flights);
+    }
   }
   if (sched.cost && threadIdx.x == 0) {
     unsigned long long dt = clock_ticks(__float_as_int(acc.x)) - wave_start;   // after the last sample was accumulated
@@ -359,4 +543,10 @@ template <bool PILOT>
 __global__ void vpt_volgrid_color_kernel(DScene sc, DParams pr, volgrid_args va, volgrid_color_args vc, float4* __restrict__ image, int* __restrict__ hits,
     ulonglong2* __restrict__ rngs, sched_cfg sched) {
   volgrid_kernel_body<true>(sc, pr, va, &vc, image, hits, rngs, sched);
+}
+// the NEE variant, render and pilot (launch bounds: vpt_launch.h; instances: vpt_k3_nee.hip)
+template <bool PILOT>
+__global__ void vpt_volgrid_nee_kernel(DScene sc, DParams pr, volgrid_args va, volgrid_nee_args vn, float4* __restrict__ image, int* __restrict__ hits,
+    ulonglong2* __restrict__ rngs, sched_cfg sched) {
+  volgrid_kernel_body<false, true>(sc, pr, va, nullptr, image, hits, rngs, sched, &vn);
 }

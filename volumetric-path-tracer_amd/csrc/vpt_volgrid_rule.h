@@ -233,6 +233,11 @@ VPT_VOLGRID_HD int vpt_volgrid_event(const float a[3], const float w[3], float u
   return VPT_VOLGRID_PASS;
 }
 
+// ---- next-event estimation (include/vpt.h: vpt_scene_set_volgrid_nee) -----------------------------------------------------
+// One tentative collision of a ratio-tracked shadow flight: `real` = min(sigma / m, 1), the probability that a delta-tracking flight would
+// have taken it for real, is the share of the flight's weight that stops here.  One subtraction, one product; real == 1 gives exactly 0
+VPT_VOLGRID_HD float vpt_volgrid_ratio_step(float T, float real) { return T * (1.0f - real); }
+
 // ---- the first-collision pass (include/vpt.h: vpt_render_volgrid_aov_device): the collision cell and the density's gradient in it ----------
 // The eight nodes of the cell eval_volume reads at node coordinates (s, t, r), each through clean(), in the order v000 v100 v010 v001 v011
 // v101 v110 v111 of the trilerp above, and the fractions (u, v, w) inside it: one fetch for the whole gradient

@@ -397,6 +397,36 @@ class DeviceScene(_Handle):
         _check(hip.vpt_scene_volgrid_color_stats(self.handle, C.byref(passes)), "vpt_scene_volgrid_color_stats")
         return passes.value
 
+    def set_volgrid_nee(self, on: bool) -> None:
+        """vpt_scene_set_volgrid_nee (include/vpt.h): next-event estimation for this handle's volgrid renders, session advances and adaptive
+        rounds - a ratio-tracked shadow flight towards a sampled environment at every collision, the path itself going on by the phase
+        function; off (the default): one-sample MIS, as ever.  Refused while coloured extinction is on"""
+        _check(hip.vpt_scene_set_volgrid_nee(self.handle, 1 if on else 0), "vpt_scene_set_volgrid_nee")
+
+    @property
+    def volgrid_nee(self) -> bool:
+        return bool(hip.vpt_scene_get_volgrid_nee(self.handle))
+
+    def volgrid_transmittance(self, rays, rngs):
+        """one ratio-tracked shadow flight per ray and stream (as volgrid_track takes them), flown by the NEE kernel's own device function
+        (vpt_scene_volgrid_transmittance): (T, steps, rngs_out) = (n,) float32 in [0, 1], (n,) int32 tracking steps, (n, 2) uint64 the
+        streams afterwards"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        rngs = np.ascontiguousarray(rngs, np.uint64).reshape(-1, 2)
+        if len(rays) != len(rngs):
+            raise VptError(f"volgrid_transmittance: {len(rays)} rays but {len(rngs)} streams")
+        n = len(rays)
+        T, steps, rngs_out = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros((n, 2), np.uint64)
+        _check(hip.vpt_scene_volgrid_transmittance(self.handle, n, rays.ctypes.data, rngs.ctypes.data, T.ctypes.data, steps.ctypes.data,
+                                                   rngs_out.ctypes.data), "vpt_scene_volgrid_transmittance")
+        return T, steps, rngs_out
+
+    def volgrid_nee_stats(self) -> dict:
+        """vpt_scene_volgrid_nee_stats: shadow flights of this handle's NEE launches so far, and their tracking steps"""
+        flights, steps = C.c_uint64(0), C.c_uint64(0)
+        _check(hip.vpt_scene_volgrid_nee_stats(self.handle, C.byref(flights), C.byref(steps)), "vpt_scene_volgrid_nee_stats")
+        return {"flights": flights.value, "steps": steps.value}
+
     def volgrid_stats(self) -> dict:
         """vpt_scene_volgrid_stats: tracking steps of this handle's volgrid launches so far, builds of its brick tables so far"""
         steps, builds = C.c_uint64(0), C.c_int32(0)

@@ -183,6 +183,9 @@ pathtrace_state  make_state(const scene_data& scene, const pathtrace_params& par
 // Extension: coloured extinction for every later volgrid render, adaptive run and progressive session (include/vpt.h:
 // vpt_scene_set_volgrid_color), on one GPU - a render over several devices with it on throws; off by default
 void pathtrace_set_volgrid_color(bool on);
+// Extension: next-event estimation with ratio-tracked shadow flights for the same renders (include/vpt.h: vpt_scene_set_volgrid_nee), on
+// one GPU as well; the two together are refused by the render that follows; off by default
+void pathtrace_set_volgrid_nee(bool on);
 // `quality`: VPT_BVH_MIDDLE (the reference's highquality = false, what every caller of the reference uses) or VPT_BVH_SAH (highquality =
 // true: split_sah, the rule at vpt_build_bvh_quality in include/vpt.h), for every tree of the scene; another value throws
 // std::invalid_argument.  The host build is the plain form of the rule: 45 passes over a node's primitives.

@@ -721,6 +721,11 @@ bool& volgrid_color_flag() {
   static auto on = false;
   return on;
 }
+// pathtrace_set_volgrid_nee: next-event estimation for the same renders (cache_mutex held)
+bool& volgrid_nee_flag() {
+  static auto on = false;
+  return on;
+}
 // the copy of `scene` on the first device alone (cache_mutex held), made on first use: pathtrace_adaptive, pathtrace_aovs
 vpt_scene* single_scene(const scene_data& scene, const bvh_scene& bvh, const pathtrace_lights& lights) {
   auto& entry = cached_entry(scene, bvh, lights);
@@ -733,8 +738,12 @@ vpt_scene* single_scene(const scene_data& scene, const bvh_scene& bvh, const pat
       throw std::runtime_error{string{"vpt_scene_create_curves: "} + vpt_last_error()};
     }
   }
+  if (!volgrid_nee_flag() && vpt_scene_get_volgrid_nee(entry.single) != 0 && vpt_scene_set_volgrid_nee(entry.single, 0) != VPT_OK)   // off first: the two exclude each other
+    throw std::runtime_error{string{"vpt_scene_set_volgrid_nee: "} + vpt_last_error()};
   if ((vpt_scene_get_volgrid_color(entry.single) != 0) != volgrid_color_flag() && vpt_scene_set_volgrid_color(entry.single, volgrid_color_flag()) != VPT_OK)
     throw std::runtime_error{string{"vpt_scene_set_volgrid_color: "} + vpt_last_error()};
+  if (volgrid_nee_flag() && vpt_scene_get_volgrid_nee(entry.single) == 0 && vpt_scene_set_volgrid_nee(entry.single, 1) != VPT_OK)
+    throw std::runtime_error{string{"vpt_scene_set_volgrid_nee: "} + vpt_last_error()};
   return entry.single;
 }
 }  // namespace
@@ -821,6 +830,11 @@ void pathtrace_set_volgrid_color(bool on) {
   volgrid_color_flag() = on;
 }
 
+void pathtrace_set_volgrid_nee(bool on) {
+  auto lock = std::lock_guard{cache_mutex};
+  volgrid_nee_flag() = on;
+}
+
 void pathtrace_samples(pathtrace_state& state, const scene_data& scene, const bvh_scene& bvh,
     const pathtrace_lights& lights, const pathtrace_params& params, int count) {
   if (state.samples >= params.samples) return;  // reference cpp:1055
@@ -831,8 +845,8 @@ void pathtrace_samples(pathtrace_state& state, const scene_data& scene, const bv
     auto single = (vpt_scene*)nullptr;
     {
       auto lock = std::lock_guard{cache_mutex};
-      if (volgrid_color_flag()) {
-        if (device_list().size() > 1) throw std::runtime_error{"coloured volgrid extinction renders on one GPU"};
+      if (volgrid_color_flag() || volgrid_nee_flag()) {
+        if (device_list().size() > 1) throw std::runtime_error{"coloured volgrid extinction and volgrid next-event estimation render on one GPU"};
         single = single_scene(scene, bvh, lights);
       }
     }

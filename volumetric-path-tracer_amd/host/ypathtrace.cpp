@@ -82,6 +82,7 @@ const std::vector<std::pair<string, option>> options = {
     {"bake-padding", {option::int_k, 0, 64, "Baking: voxels to spare around the shape on each side."}},
     {"bake-host", {option::bool_k, 1, 0, "Baking: run the host mirror instead of the GPU: same file."}},
     {"volgrid-color", {option::bool_k, 1, 0, "volgrid shader: coloured extinction from the materials' color, on one GPU. (extension)"}},
+    {"volgrid-nee", {option::bool_k, 1, 0, "volgrid shader: next-event estimation with ratio-tracked shadow rays, on one GPU. (extension)"}},
     {"mesh-sdf", {option::string_k, 1, 0, "Mesh this binary .sdf grid into quads written to --output (PLY); renders nothing. (extension)"}},
     {"mesh-iso", {option::anyfloat_k, 1, 0, "Meshing: the iso value, inside is below it."}},
     {"mesh-host", {option::bool_k, 1, 0, "Meshing: run the host mirror instead of the GPU: same file."}},
@@ -245,6 +246,13 @@ int main(int argc, const char** argv) {
   if (volgrid_color && gpus > 1) cli_error("option volgrid-color renders on one GPU: it cannot be combined with gpus " + std::to_string(gpus));
   if (volgrid_color && progressive) cli_error("option volgrid-color cannot be combined with progressive");
   pathtrace_set_volgrid_color(volgrid_color);
+  auto volgrid_nee = false;
+  get_bool("volgrid-nee", volgrid_nee);
+  if (volgrid_nee && (int)params.shader != VPT_SHADER_VOLGRID) cli_error("option volgrid-nee needs --shader volgrid");
+  if (volgrid_nee && gpus > 1) cli_error("option volgrid-nee renders on one GPU: it cannot be combined with gpus " + std::to_string(gpus));
+  if (volgrid_nee && progressive) cli_error("option volgrid-nee cannot be combined with progressive");
+  if (volgrid_nee && volgrid_color) cli_error("option volgrid-nee cannot be combined with volgrid-color");
+  pathtrace_set_volgrid_nee(volgrid_nee);
 
   for (auto name : {"bake-res", "bake-padding", "bake-host"})
     if (values.count(name) && !values.count("bake-sdf")) cli_error(string{"option "} + name + " needs --bake-sdf");

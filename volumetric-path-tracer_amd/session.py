@@ -141,6 +141,10 @@ class RenderSession(_Handle):
         edit.  The session stays a volgrid session: pick_volgrid, volgrid_ids and sculpt_at keep meaning the grey flight."""
         _check(hip.vpt_session_set_volgrid_color(self.handle, 1 if on else 0), "vpt_session_set_volgrid_color")
 
+    def set_volgrid_nee(self, on: bool) -> None:
+        """vpt_session_set_volgrid_nee (include/vpt.h): DeviceScene.set_volgrid_nee on the session's scene, then a reset, as after an edit"""
+        _check(hip.vpt_session_set_volgrid_nee(self.handle, 1 if on else 0), "vpt_session_set_volgrid_nee")
+
     def sculpt_at(self, host, x: int, y: int, brush: VptSdf, op: int, blend: float = 0.0, region_margin: int = 2) -> SculptEntry:
         """The editor's gesture: one stamp of `brush` where the ray through pixel (x, y) hits a voxel grid.  pick_sdf(x, y) names the grid
         instance and the hit (a miss or a hit on an analytic SDF raises VptError); the hit is taken into that instance's voxel space,
