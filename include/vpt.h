@@ -597,6 +597,49 @@ typedef struct vpt_filter_edit {
 } vpt_filter_edit;
 int vpt_scene_filter_volumes(vpt_scene* scene, const vpt_filter_edit* edit);
 
+/* ---- smoke that moves: a stable-fluids step over four volumes of a resident scene -----------------------------------------
+ * The fifth edit of the voxel pool and the first over several volumes: a density and the three components of a velocity, four different
+ * volumes of equal whd (the velocities are typically added with VPT_VOLUME_FILL and named by no grid instance).  One step of Stam's
+ * Stable Fluids on a collocated node grid; velocities are node spacings per unit time, so the rule has no cell size.  No voxel crosses
+ * PCIe; only the four volumes change.  The rule, written once in csrc/vpt_fluid_rule.h (compiled by the kernels and by the host mirror,
+ * host/vpt_fluid.cpp, both with -ffp-contract=off: float32, nothing fused, sums in the order written; clamps are selects, so a NaN
+ * coordinate becomes 0; a result that is a NaN is stored as 0x7fc00000).  Per step, open_faces bit 0..5 = the faces -x, +x, -y, +y, -z, +z:
+ *  1. Force.  Per node and component c: u_c = u_c * keep_velocity; u_c = u_c + (dt * lift[c]) * rho, rho read before its own decay;
+ *     then rho = rho * keep_density.
+ *  2. Walls.  At a node on a closed face the velocity component normal to that face becomes +0.0f; open faces are left alone.
+ *  3. Advect.  The four fields by the velocity after 2.: q_c = (float)i_c - dt * u_c, clamped to [0, W_c - 1] by selects; the new value is
+ *     vpt_volgrid_trilerp(field, W, H, D, q) (csrc/vpt_volgrid_rule.h: the renderer's lookup).  All four read the state before the advection.
+ *  4. Walls.
+ *  5. Divergence.  d = 0.5f * ((u[i+1] - u[i-1]) + (v[j+1] - v[j-1]) + (w[k+1] - w[k-1])), indices clamped to the volume.
+ *  6. Pressure.  p = 0, then `iterations` Jacobi sweeps: s = p[-x] + p[+x]; s = s + p[-y]; s = s + p[+y]; s = s + p[-z]; s = s + p[+z];
+ *     s = s - d; p' = s * (1.0f / 6.0f).  A neighbour outside the volume across a closed face is the clamped node (Neumann), across an
+ *     open face 0.0f (Dirichlet).
+ *  7. Project.  u = u - 0.5f * (p[i+1] - p[i-1]), likewise v and w, with 6.'s neighbours; then walls.
+ * `steps` repetitions run in one call without a host round trip.  The device fuses launches (force + walls; the move of the advected
+ * fields into place + walls; project + walls; K Jacobi sweeps of an 8^3 tile in LDS, K = VPT_FLUID_BLOCK = 1 | 2 | 4, default 2) and
+ * leaves these bits whichever K runs.
+ *  - Validation before anything is written (VPT_ERR_INVALID_ARG, the message names the field, the scene is untouched): an id out of range;
+ *    two of the four ids equal; unequal whd; a float that is not finite; steps < 0; iterations outside 0..VPT_FLUID_MAX_ITERATIONS;
+ *    open_faces outside 0..63.  More than 2^30 nodes: VPT_ERR_UNSUPPORTED.
+ *  - steps == 0, or volumes without nodes, launch nothing.  vpt_scene_update_stats afterwards: launches = steps * (5 + the Jacobi
+ *    launches: iterations / K of K sweeps and the remainder at smaller K); bytes = VPT_FLUID_RECORD_BYTES, the step as the kernels get it
+ *    in their argument block, when anything is launched (0 otherwise) - not one voxel.
+ *  - Synchronisation, the VPT_ERR_HIP semantics and the forgetting of the launch-schedule record: those of vpt_scene_update.  The volgrid
+ *    shader's brick majorants follow as after every voxel edit. */
+#define VPT_FLUID_MAX_ITERATIONS 1024
+#define VPT_FLUID_RECORD_BYTES 48
+typedef struct vpt_fluid_step {
+  int32_t density;       /* volume ids: four different volumes of equal whd */
+  int32_t velocity[3];
+  int32_t steps;         /* repetitions of the whole step in this call */
+  int32_t iterations;    /* Jacobi sweeps per step */
+  int32_t open_faces;    /* bit 0..5: -x, +x, -y, +y, -z, +z */
+  float   dt;
+  float   lift[3];       /* the force per unit of density */
+  float   keep_density, keep_velocity;   /* what a step leaves of each before it moves them */
+} vpt_fluid_step;
+int vpt_scene_fluid_step(vpt_scene* scene, const vpt_fluid_step* step);
+
 /* ---- adding and removing volumes, grid instances and SDFs -------------------------------------------------------------
  * The one thing vpt_scene_update_volumes leaves fixed: how many there are.  An edit of its own, because vpt_volume_edit keeps its layout;
  * the contract is that of vpt_scene_update_instances and vpt_scene_update_shapes.  After vpt_scene_update_volume_set(s, edit) every table
@@ -1592,6 +1635,8 @@ int  vpt_session_edit_volumes(vpt_session* session, const vpt_volume_edit* edit)
 int  vpt_session_sculpt_volumes(vpt_session* session, const vpt_sculpt_edit* edit);
 /* vpt_scene_filter_volumes, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_filter_volumes(vpt_session* session, const vpt_filter_edit* edit);
+/* vpt_scene_fluid_step, then a reset; a refused edit leaves the session as it was */
+int  vpt_session_fluid_step(vpt_session* session, const vpt_fluid_step* step);
 /* vpt_scene_set_volgrid_color, then a reset.  The session stays a volgrid session: its pick, id frame and first-collision pass keep
  * meaning the grey flight */
 int  vpt_session_set_volgrid_color(vpt_session* session, int on);

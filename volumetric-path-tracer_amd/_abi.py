@@ -207,6 +207,14 @@ class VptFilterEdit(C.Structure):  # vpt_filter_edit
 assert C.sizeof(VptFilterOp) == 44 and C.sizeof(VptFilterEntry) == 60 and C.sizeof(VptFilterEdit) == 32
 
 
+class VptFluidStep(C.Structure):  # vpt_fluid_step
+    _fields_ = [("density", C.c_int32), ("velocity", C.c_int32 * 3), ("steps", C.c_int32), ("iterations", C.c_int32), ("open_faces", C.c_int32),
+                ("dt", C.c_float), ("lift", C.c_float * 3), ("keep_density", C.c_float), ("keep_velocity", C.c_float)]
+
+
+assert C.sizeof(VptFluidStep) == 52
+
+
 class VptVolumeNew(C.Structure):  # vpt_volume_new
     _fields_ = [("whd", C.c_int32 * 3), ("res", C.c_float), ("source", C.c_int32), ("offset", C.c_int64), ("bake", C.c_void_p), ("fill", C.c_float),
                 ("copy_of", C.c_int32)]
@@ -229,6 +237,10 @@ SCULPT_RECORD_BYTES = 80   # VPT_SCULPT_RECORD_BYTES: one stamp as the device re
 FILTER_REMAP, FILTER_BLUR, FILTER_NOISE = 0, 1, 2
 FILTER_MAX_RADIUS, FILTER_MAX_OCTAVES = 4, 8
 FILTER_RECORD_BYTES = 48   # VPT_FILTER_RECORD_BYTES: one op as the device reads it
+FLUID_MAX_ITERATIONS = 1024
+FLUID_RECORD_BYTES = 48   # VPT_FLUID_RECORD_BYTES: a step as the kernels get it
+FLUID_DEFAULT_BLOCK = 2   # sweeps per Jacobi launch unless VPT_FLUID_BLOCK says 1, 2 or 4 (csrc/vpt_fluid.hip)
+FLUID_OPEN_ALL = 63       # vpt_fluid_step::open_faces: bit 0..5 = -x, +x, -y, +y, -z, +z
 MATERIAL_TYPES = ["matte", "glossy", "reflective", "transparent", "refractive", "subsurface", "volumetric", "gltfpbr"]
 
 
@@ -341,6 +353,8 @@ hip.vpt_session_sculpt_volumes.argtypes = [_p, C.POINTER(VptSculptEdit)]
 hip.vpt_scene_filter_volumes.argtypes = [_p, C.POINTER(VptFilterEdit)]
 hip.vpt_multi_filter_volumes.argtypes = [_p, C.POINTER(VptFilterEdit)]
 hip.vpt_session_filter_volumes.argtypes = [_p, C.POINTER(VptFilterEdit)]
+hip.vpt_scene_fluid_step.argtypes = [_p, C.POINTER(VptFluidStep)]
+hip.vpt_session_fluid_step.argtypes = [_p, C.POINTER(VptFluidStep)]
 hip.vpt_scene_update_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
 hip.vpt_multi_update_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
 hip.vpt_session_edit_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
@@ -522,6 +536,9 @@ host.vpth_sculpt_combine.argtypes = [C.c_int, C.c_float, _p, _p, C.c_int, _p]
 host.vpth_scene_filter_volume.argtypes = [_p, C.POINTER(VptFilterEntry), _p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_filter_voxels.argtypes = [_p, _p, C.POINTER(VptFilterEntry), _p, C.c_int, C.c_char_p, C.c_int]
 host.vpth_filter_gaussian_weights.argtypes = [C.c_float, C.c_int, _p]
+host.vpth_scene_fluid_step.argtypes = [_p, C.POINTER(VptFluidStep), C.c_char_p, C.c_int]
+host.vpth_fluid_step.argtypes = [_p, _p, _p, _p, _p, C.POINTER(VptFluidStep), C.c_char_p, C.c_int]
+host.vpth_fluid_stage.argtypes = [C.c_int, _p, _p, _p, _p, _p, _p, _p, C.POINTER(VptFluidStep), C.c_char_p, C.c_int]
 host.vpth_scene_desc.argtypes = [_p]
 host.vpth_scene_desc.restype = _p
 host.vpth_scene_curves.argtypes = [_p]

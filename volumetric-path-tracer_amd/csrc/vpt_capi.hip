@@ -13,6 +13,7 @@
 
 #include "vpt_bvh_rebuild.h"
 #include "vpt_filter.h"
+#include "vpt_fluid.h"
 #include "vpt_instance_update.h"
 #include "vpt_light_update.h"
 #include "vpt_scene_handle.h"
@@ -173,6 +174,7 @@ template <typename Edit> static bool writes_materials(const Edit&) { return fals
 static bool writes_voxels(const vpt_volume_edit&) { return true; }   // voxels in place, baked into the pool, or moved into a grown pool
 static bool writes_voxels(const vpt_sculpt_edit&) { return true; }
 static bool writes_voxels(const vpt_filter_edit&) { return true; }
+static bool writes_voxels(const vpt_fluid_step&) { return true; }
 static bool writes_voxels(const vpt_volume_set_edit&) { return true; }   // a pool laid out anew, volumes under other ids: the brick tables are indexed by volume
 template <typename Edit> static bool writes_voxels(const Edit&) { return false; }
 
@@ -221,6 +223,8 @@ int vpt_scene_update_volumes(vpt_scene* s, const vpt_volume_edit* edit) { return
 int vpt_scene_sculpt_volumes(vpt_scene* s, const vpt_sculpt_edit* edit) { return edit_scene(s, edit, sculpt_apply); }
 // voxels alone again, remapped, blurred and broken up with noise where they live (vpt_filter.hip)
 int vpt_scene_filter_volumes(vpt_scene* s, const vpt_filter_edit* edit) { return edit_scene(s, edit, filter_apply); }
+// the voxels of four volumes at once: a density moved by a velocity, one stable-fluids step after another (vpt_fluid.hip)
+int vpt_scene_fluid_step(vpt_scene* s, const vpt_fluid_step* step) { return edit_scene(s, step, fluid_apply); }
 // volumes, grid instances and SDFs added and removed (vpt_volume_set.hip): the pool compacted by one gather, the lights following the SDFs
 int vpt_scene_update_volume_set(vpt_scene* s, const vpt_volume_set_edit* edit) { return edit_scene(s, edit, volume_set_apply); }
 // the BVHs built anew (vpt_bvh_rebuild.hip), the set of instances changed (vpt_instance_update.hip), the shape list changed (vpt_shape_update.hip)

@@ -1,0 +1,106 @@
+// vpt_fluid_rule.h — the rule of vpt_scene_fluid_step (include/vpt.h), written once: one step of Stam's Stable Fluids on a collocated node
+// grid, stage by stage at one node.  Compiled by the fluid kernels (csrc/vpt_fluid.hip) and by the host mirror (host/vpt_fluid.cpp), both
+// with -ffp-contract=off: float32 throughout, nothing fused, every sum in the order written here - so both give the same bits, and THIS
+// FILE IS THE CONTRACT'S OPERATION ORDER.  Velocities are node spacings per unit time: there is no cell size.  A result that is a NaN is
+// stored as 0x7fc00000 (vpt_filter_one_nan, csrc/vpt_filter_rule.h); the back-trace reads the grid through vpt_volgrid_trilerp, the
+// function the renderer reads it with (csrc/vpt_volgrid_rule.h).
+#pragma once
+#include "vpt_filter_rule.h"
+#include "vpt_volgrid_rule.h"
+
+#define VPT_FLUID_HD VPT_FILTER_HD
+
+// what the kernels get as an argument and the mirror reads: VPT_FLUID_RECORD_BYTES, made on the host by vpt_fluid_make_record
+struct vpt_fluid_record {
+  int32_t  w, h, d;
+  uint32_t open;      // bit 0 .. 5: the faces -x, +x, -y, +y, -z, +z are open
+  float    dt;
+  float    force[3];  // dt * lift[c], one float32 product each
+  float    keep_density, keep_velocity;
+  int32_t  iterations, unused;
+};
+static_assert(sizeof(vpt_fluid_record) == VPT_FLUID_RECORD_BYTES, "include/vpt.h states the size of a step's record");
+
+inline vpt_fluid_record vpt_fluid_make_record(const int32_t whd[3], const vpt_fluid_step& s) {
+  return {whd[0], whd[1], whd[2], (uint32_t)s.open_faces, s.dt, {s.dt * s.lift[0], s.dt * s.lift[1], s.dt * s.lift[2]}, s.keep_density, s.keep_velocity,
+      s.iterations, 0};
+}
+VPT_FLUID_HD bool vpt_fluid_open(uint32_t open, int axis, int side) { return (open >> (2 * axis + side)) & 1u; }   // side 0: the low face
+
+// ---- 1. force: the velocity decays and is lifted by the density as it was, then the density decays ----------------------------------
+VPT_FLUID_HD float vpt_fluid_force(float u, float keep_velocity, float force, float rho) {
+  u = u * keep_velocity;
+  u = u + force * rho;
+  return vpt_filter_one_nan(u);
+}
+VPT_FLUID_HD float vpt_fluid_decay(float rho, float keep_density) { return vpt_filter_one_nan(rho * keep_density); }
+
+// ---- 2. walls: the component normal to a closed face, at node i of the W along its axis ---------------------------------------------
+VPT_FLUID_HD float vpt_fluid_wall(float u, int i, int W, uint32_t open, int axis) {
+  const bool closed = (i == 0 && !vpt_fluid_open(open, axis, 0)) || (i == W - 1 && !vpt_fluid_open(open, axis, 1));
+  return closed ? 0.0f : u;
+}
+
+// ---- 3. advect: where node i came from along one axis; the clamps are selects, a NaN becomes 0 ---------------------------------------
+VPT_FLUID_HD float vpt_fluid_backtrace(int i, float dt, float u, int W) {
+  float q = (float)i - dt * u;
+  q       = q > 0.0f ? q : 0.0f;
+  q       = q < (float)(W - 1) ? q : (float)(W - 1);
+  return q;
+}
+VPT_FLUID_HD float vpt_fluid_advect(const float* field, int W, int H, int D, float qx, float qy, float qz) {
+  return vpt_filter_one_nan(vpt_volgrid_trilerp(field, W, H, D, qx, qy, qz));
+}
+
+// ---- 5. divergence from the three central differences, each u[i + 1] - u[i - 1] with the indices clamped to the volume ----------------
+VPT_FLUID_HD float vpt_fluid_divergence(float du, float dv, float dw) { return vpt_filter_one_nan(0.5f * ((du + dv) + dw)); }
+
+// ---- 6. / 7. the pressure's neighbours ------------------------------------------------------------------------------------------------
+// p at the neighbour `step` words from p[at]; outside: that neighbour lies across a face of the volume - the clamped node, which is the
+// node itself, behind a closed face (Neumann), 0 behind an open one (Dirichlet).  p[at + step] is read only inside the volume, so `p` may
+// as well be a tile in LDS whose positions outside the volume hold nothing.
+VPT_FLUID_HD float vpt_fluid_near(const float* p, int at, int step, bool outside, bool open) { return outside ? (open ? 0.0f : p[at]) : p[at + step]; }
+
+// one Jacobi sweep at node (i, j, k) of the volume, p[at] its value, sx / sy / sz the strides of `p`, d the divergence there
+VPT_FLUID_HD float vpt_fluid_jacobi(const float* p, int at, int sx, int sy, int sz, int i, int j, int k, const vpt_fluid_record& g, float d) {
+  float s = vpt_fluid_near(p, at, -sx, i == 0, vpt_fluid_open(g.open, 0, 0)) + vpt_fluid_near(p, at, sx, i == g.w - 1, vpt_fluid_open(g.open, 0, 1));
+  s       = s + vpt_fluid_near(p, at, -sy, j == 0, vpt_fluid_open(g.open, 1, 0));
+  s       = s + vpt_fluid_near(p, at, sy, j == g.h - 1, vpt_fluid_open(g.open, 1, 1));
+  s       = s + vpt_fluid_near(p, at, -sz, k == 0, vpt_fluid_open(g.open, 2, 0));
+  s       = s + vpt_fluid_near(p, at, sz, k == g.d - 1, vpt_fluid_open(g.open, 2, 1));
+  s       = s - d;
+  return vpt_filter_one_nan(s * (1.0f / 6.0f));
+}
+// a velocity component minus half the pressure difference along its axis (node i of W, stride `step`)
+VPT_FLUID_HD float vpt_fluid_project(float u, const float* p, int at, int step, int i, int W, uint32_t open, int axis) {
+  const float hi = vpt_fluid_near(p, at, step, i == W - 1, vpt_fluid_open(open, axis, 1));
+  const float lo = vpt_fluid_near(p, at, -step, i == 0, vpt_fluid_open(open, axis, 0));
+  return vpt_filter_one_nan(u - 0.5f * (hi - lo));
+}
+
+// ---- what both sides refuse, in the same words ------------------------------------------------------------------------------------------
+constexpr long long VPT_FLUID_MAX_NODES = 1ll << 30;
+// null, or what is wrong with step `s` over `num_volumes` volumes whose sizes whd_of(id) answers; *unsupported: the size guard refused it
+template <typename WhdOf>
+inline const char* vpt_fluid_step_fault(const vpt_fluid_step& s, int num_volumes, WhdOf whd_of, bool* unsupported) {
+  *unsupported = false;
+  const int32_t ids[4] = {s.density, s.velocity[0], s.velocity[1], s.velocity[2]};
+  for (int a = 0; a < 4; a++) {
+    if (ids[a] < 0 || ids[a] >= num_volumes) return a == 0 ? "density: volume id out of range" : "velocity: volume id out of range";
+    for (int b = 0; b < a; b++)
+      if (ids[a] == ids[b]) return "density and velocity: two of the four volume ids are equal";
+  }
+  const int32_t* whd = whd_of(ids[0]);
+  for (int a = 1; a < 4; a++)
+    for (int k = 0; k < 3; k++)
+      if (whd_of(ids[a])[k] != whd[k]) return "velocity: a volume's whd is not the density's";
+  if (!std::isfinite(s.dt)) return "dt is not finite";
+  if (!vpt_filter_finite(s.lift, 3)) return "lift is not finite";
+  if (!std::isfinite(s.keep_density)) return "keep_density is not finite";
+  if (!std::isfinite(s.keep_velocity)) return "keep_velocity is not finite";
+  if (s.steps < 0) return "steps is negative";
+  if (s.iterations < 0 || s.iterations > VPT_FLUID_MAX_ITERATIONS) return "iterations is not one of 0..1024";
+  if (s.open_faces < 0 || s.open_faces > 63) return "open_faces has bits above the six faces";
+  if ((long long)whd[0] * whd[1] * whd[2] > VPT_FLUID_MAX_NODES) return *unsupported = true, "more than 2^30 nodes in a volume";
+  return nullptr;
+}

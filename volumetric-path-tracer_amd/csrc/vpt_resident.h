@@ -78,6 +78,8 @@ struct resident {
   device_buffer d_sin;     // sin((j + 0.5f) * pif / height) per row of the recomputed environments, made on the host
   device_buffer d_filter_scratch;   // vpt_scene_filter_volumes: a blur's results in region order, until the launch that moves them into place
   size_t        filter_scratch_bytes = 0;
+  device_buffer d_fluid_scratch;    // vpt_scene_fluid_step: the four advected fields until they are moved into place, then the divergence and the two pressures
+  size_t        fluid_scratch_bytes = 0;
   // what the last edit did (vpt_scene_update_stats): begin_update (vpt_update_helpers.h) starts them, launches and sends count themselves
   int        last_launches = 0;
   long long  last_bytes    = 0;

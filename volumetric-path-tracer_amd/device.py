@@ -11,7 +11,7 @@ import numpy as np
 from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SDF_AOV_PLANES, SHADER_NAMES, VOLGRID_AOV_PLANES, VOLGRID_CHROMA, VptAdaptive, VptAovPlanes, VptSdfAovPlanes,
                    VptVolgridAovPlanes, VptDisplay, VptError, VptLayout, VptParams,
                    VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, shader_id, _counted, _edit_call, _mesh_desc, _mesh_region, _meshed, _p, hip, host)
-from .edits import BvhRebuild, FilterEdit, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, VolumeSetEdit, mesh
+from .edits import BvhRebuild, FilterEdit, FluidStep, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, VolumeSetEdit, mesh
 
 if TYPE_CHECKING:
     from .host_scene import HostScene
@@ -300,6 +300,11 @@ class DeviceScene(_Handle):
         """vpt_scene_filter_volumes (include/vpt.h): remaps, blurs and noise run on the device over boxes of the resident voxels - 48 bytes
         per op cross PCIe, not one voxel.  edit: what HostScene.update_filters() returns."""
         _edit_call(self.handle, "vpt_scene_filter_volumes", edit)
+
+    def fluid_step(self, step: FluidStep) -> None:
+        """vpt_scene_fluid_step (include/vpt.h): `step.steps` Stable Fluids steps over the resident density and velocity volumes - 48
+        bytes cross PCIe, not one voxel.  step: one of what HostScene.update_fluid() returns."""
+        _edit_call(self.handle, "vpt_scene_fluid_step", step)
 
     def get_volumes(self):
         """(volumes, vol_instances, sdfs) as the device holds them, ctypes arrays of VptVolume, VptVolumeInstance, VptSdf

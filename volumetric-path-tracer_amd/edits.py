@@ -9,7 +9,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._abi import (FILTER_BLUR, FILTER_MAX_RADIUS, FILTER_NOISE, FILTER_RECORD_BYTES, FILTER_REMAP, INSTANCE, MESH_ELEMENTS, MESH_FLOATS, SCULPT_RECORD_BYTES,
+from ._abi import (FILTER_BLUR, FILTER_MAX_RADIUS, FILTER_NOISE, FILTER_RECORD_BYTES, FILTER_REMAP, FLUID_DEFAULT_BLOCK, FLUID_RECORD_BYTES, VptFluidStep, INSTANCE, MESH_ELEMENTS, MESH_FLOATS, SCULPT_RECORD_BYTES,
                    VOXELS_REPLACE, VptFilterEdit, VptFilterEntry, VptFilterOp, host, VptBakeDesc, VptBvhRebuild, VptCamera, VptEnvironment,
                    VptError, VptInstanceEdit, VptMaterial, VptSceneEdit, VptSculptEdit, VptSculptEntry, VptSculptStamp, VptSdf, VptShapeData, VptShapeEdit,
                    VptSubdivEdit, VptSubdivLevel, VptSubdivPlan, VptTexture, VptTextureEdit, VptVolumeEdit, VptVolumeInstance, VptVolumeNew, VptVolumeSetEdit,
@@ -567,3 +567,40 @@ class FilterEdit:
                 first += 1
         abi = VptFilterEdit(len(self.entries), C.addressof(entries) if self.entries else None, count, C.addressof(ops) if count else None)
         return abi, [entries, ops]
+
+
+# ---- a stable-fluids step over four volumes ---------------------------------------------------------------------------------------------
+@dataclass
+class FluidStep:
+    """What vpt_scene_fluid_step takes (include/vpt.h: vpt_fluid_step): the density's volume id, the three of the velocity (four
+    different volumes of equal whd, velocities in node spacings per unit time), `steps` repetitions of one Stable Fluids step with
+    `iterations` Jacobi sweeps each, and open_faces, bit 0..5 = -x, +x, -y, +y, -z, +z (a closed face is a wall).  HostScene.fluid_step
+    applies and notes one, update_fluid() hands them out; DeviceScene.fluid_step / RenderSession.edit_fluid apply one."""
+    density: int
+    velocity: tuple
+    steps: int = 1
+    iterations: int = 20
+    open_faces: int = 0
+    dt: float = 1.0
+    lift: tuple = (0.0, 0.0, 0.0)
+    keep_density: float = 1.0
+    keep_velocity: float = 1.0
+
+    def volumes(self) -> tuple:
+        return (int(self.density), *(int(v) for v in self.velocity))
+
+    def payload_bytes(self, nodes: int = 1) -> int:
+        """bytes of the step itself as vpt_scene_update_stats counts them: FLUID_RECORD_BYTES when anything is launched"""
+        return FLUID_RECORD_BYTES if self.steps > 0 and nodes > 0 else 0
+
+    def launches(self, block: int = FLUID_DEFAULT_BLOCK) -> int:
+        """launches as vpt_scene_update_stats counts them at `block` sweeps per Jacobi launch (VPT_FLUID_BLOCK): per step force, advect,
+        place, divergence and project, iterations // block Jacobi launches and the remainder at smaller blocks"""
+        return self.steps * (5 + self.iterations // block + bin(self.iterations % block).count("1"))
+
+    def to_abi(self):
+        """(VptFluidStep, nothing to keep alive)"""
+        abi = VptFluidStep(density=int(self.density), steps=int(self.steps), iterations=int(self.iterations), open_faces=int(self.open_faces),
+                           dt=float(self.dt), keep_density=float(self.keep_density), keep_velocity=float(self.keep_velocity))
+        abi.velocity[:], abi.lift[:] = [int(v) for v in self.velocity], [float(v) for v in self.lift]
+        return abi, []

@@ -1,0 +1,134 @@
+// vpt_fluid.cpp — a stable-fluids step on the CPU: the rule of include/vpt.h (vpt_scene_fluid_step) through the same header as the
+// kernels (csrc/vpt_fluid_rule.h), one stage after another in plain serial loops over the whole grid - the statement the kernels are held
+// to bit for bit.  Every stage is a function of its own, so that the tests can hold each to float64.
+#include <algorithm>
+#include <cstdio>
+
+#include "vpt_fluid_rule.h"
+#include "vpt_host.h"
+
+namespace vpt {
+
+namespace {
+
+// f[0] the density, f[1..3] the velocity; every loop x fastest
+template <typename Node>
+void each_node(const vpt_fluid_record& g, Node node) {
+  for (auto k = 0; k < g.d; k++)
+    for (auto j = 0; j < g.h; j++)
+      for (auto i = 0; i < g.w; i++) node(i, j, k, i + g.w * (j + g.h * k));
+}
+size_t nodes_of(const vpt_fluid_record& g) { return (size_t)g.w * (size_t)g.h * (size_t)g.d; }
+
+void force(float* const f[4], const vpt_fluid_record& g) {
+  each_node(g, [&](int, int, int, int at) {
+    const auto rho = f[0][at];
+    for (auto c = 0; c < 3; c++) f[1 + c][at] = vpt_fluid_force(f[1 + c][at], g.keep_velocity, g.force[c], rho);
+    f[0][at] = vpt_fluid_decay(rho, g.keep_density);
+  });
+}
+void walls(float* const f[4], const vpt_fluid_record& g) {
+  each_node(g, [&](int i, int j, int k, int at) {
+    f[1][at] = vpt_fluid_wall(f[1][at], i, g.w, g.open, 0);
+    f[2][at] = vpt_fluid_wall(f[2][at], j, g.h, g.open, 1);
+    f[3][at] = vpt_fluid_wall(f[3][at], k, g.d, g.open, 2);
+  });
+}
+void advect(float* const f[4], const vpt_fluid_record& g) {
+  vector<float> old[4];
+  for (auto c = 0; c < 4; c++) old[c].assign(f[c], f[c] + nodes_of(g));
+  each_node(g, [&](int i, int j, int k, int at) {
+    const auto qx = vpt_fluid_backtrace(i, g.dt, old[1][at], g.w), qy = vpt_fluid_backtrace(j, g.dt, old[2][at], g.h), qz = vpt_fluid_backtrace(k, g.dt, old[3][at], g.d);
+    for (auto c = 0; c < 4; c++) f[c][at] = vpt_fluid_advect(old[c].data(), g.w, g.h, g.d, qx, qy, qz);
+  });
+}
+void divergence(const float* const f[4], const vpt_fluid_record& g, float* div) {
+  const int sy = g.w, sz = g.w * g.h;
+  each_node(g, [&](int i, int j, int k, int at) {
+    const auto du = f[1][at + (vpt_filter_clamp(i + 1, g.w) - i)] - f[1][at + (vpt_filter_clamp(i - 1, g.w) - i)];
+    const auto dv = f[2][at + (vpt_filter_clamp(j + 1, g.h) - j) * sy] - f[2][at + (vpt_filter_clamp(j - 1, g.h) - j) * sy];
+    const auto dw = f[3][at + (vpt_filter_clamp(k + 1, g.d) - k) * sz] - f[3][at + (vpt_filter_clamp(k - 1, g.d) - k) * sz];
+    div[at] = vpt_fluid_divergence(du, dv, dw);
+  });
+}
+void pressure(const vpt_fluid_record& g, const float* div, float* p) {
+  auto from = vector<float>(nodes_of(g), 0.0f), to = from;
+  for (auto n = 0; n < g.iterations; n++) {
+    each_node(g, [&](int i, int j, int k, int at) { to[at] = vpt_fluid_jacobi(from.data(), at, 1, g.w, g.w * g.h, i, j, k, g, div[at]); });
+    from.swap(to);
+  }
+  std::copy(from.begin(), from.end(), p);
+}
+void project(float* const f[4], const vpt_fluid_record& g, const float* p) {
+  each_node(g, [&](int i, int j, int k, int at) {
+    f[1][at] = vpt_fluid_project(f[1][at], p, at, 1, i, g.w, g.open, 0);
+    f[2][at] = vpt_fluid_project(f[2][at], p, at, g.w, j, g.h, g.open, 1);
+    f[3][at] = vpt_fluid_project(f[3][at], p, at, g.w * g.h, k, g.d, g.open, 2);
+  });
+  walls(f, g);
+}
+
+// the step's fault with the ids left to the caller: the four arrays are four volumes of `whd`
+const char* fault_of(const int32_t whd[3], vpt_fluid_step s) {
+  if (whd[0] < 0 || whd[1] < 0 || whd[2] < 0) return "bad volume size";
+  s.density = 0, s.velocity[0] = 1, s.velocity[1] = 2, s.velocity[2] = 3;
+  bool unsupported;
+  return vpt_fluid_step_fault(s, 4, [&](int) { return whd; }, &unsupported);
+}
+
+}  // namespace
+
+bool fluid_stage(int stage, float* const f[4], float* p, float* div, const int32_t whd[3], const vpt_fluid_step& s, string& error) {
+  if (auto fault = fault_of(whd, s)) return error = string{"fluid: "} + fault, false;
+  const auto g = vpt_fluid_make_record(whd, s);
+  switch (stage) {
+    case 0: force(f, g); break;
+    case 1: walls(f, g); break;
+    case 2: advect(f, g); break;
+    case 3: divergence(f, g, div); break;
+    case 4: pressure(g, div, p); break;
+    case 5: project(f, g, p); break;
+    default: return error = "fluid: stage is not one of 0..5", false;
+  }
+  return true;
+}
+
+bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& s, string& error) {
+  if (auto fault = fault_of(whd, s)) return error = string{"fluid: "} + fault, false;
+  const auto g = vpt_fluid_make_record(whd, s);
+  auto       div = vector<float>(nodes_of(g)), p = div;
+  for (auto n = 0; n < s.steps && nodes_of(g) > 0; n++) {
+    force(f, g), walls(f, g);
+    advect(f, g), walls(f, g);
+    divergence(f, g, div.data());
+    pressure(g, div.data(), p.data());
+    project(f, g, p.data());
+  }
+  return true;
+}
+
+}  // namespace vpt
+
+extern "C" {
+
+// the host mirror on four host arrays of whd[0] * whd[1] * whd[2] nodes (x fastest); the step's volume ids are ignored.  A refused call writes nothing.
+int vpth_fluid_step(float* density, float* u, float* v, float* w, const int32_t* whd, const vpt_fluid_step* step, char* err, int errlen) {
+  auto         error = vpt::string{};
+  float* const f[4]  = {density, u, v, w};
+  if (!density || !u || !v || !w || !whd || !step) error = "fluid: null argument";
+  else if (vpt::fluid_step(f, whd, *step, error)) return 0;
+  if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", error.c_str());
+  return -1;
+}
+// one stage of the rule alone: 0 force, 1 walls, 2 advect, 3 divergence (into div), 4 pressure (div -> p, step->iterations sweeps from 0),
+// 5 project (reads p) and walls.  p and div are read or written by stages 3 .. 5 only
+int vpth_fluid_stage(int stage, float* density, float* u, float* v, float* w, float* p, float* div, const int32_t* whd, const vpt_fluid_step* step, char* err, int errlen) {
+  auto         error = vpt::string{};
+  float* const f[4]  = {density, u, v, w};
+  if (!density || !u || !v || !w || !whd || !step || (stage >= 3 && !div) || (stage >= 4 && !p)) error = "fluid: null argument";
+  else if (vpt::fluid_stage(stage, f, p, div, whd, *step, error)) return 0;
+  if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", error.c_str());
+  return -1;
+}
+
+}  // extern "C"

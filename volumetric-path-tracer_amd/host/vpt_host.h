@@ -457,6 +457,14 @@ bool filter_voxels(float* voxels, const int32_t whd[3], const vpt_filter_entry& 
 // false for a sigma that is not finite and > 0 or a radius outside 1..VPT_FILTER_MAX_RADIUS
 bool filter_gaussian_weights(float sigma, int radius, float* weights);
 
+// ---- a stable-fluids step over four voxel grids (include/vpt.h: vpt_scene_fluid_step; host/vpt_fluid.cpp) ---------------------------------
+// the host mirror on four host arrays of whd nodes (x fastest), f[0] the density, f[1..3] the velocity: the rule header
+// (csrc/vpt_fluid_rule.h) in plain serial loops, step.steps times - the same bits as the device.  Refuses what the C-ABI refuses, in its
+// words (false, `error` set, the arrays untouched); the step's volume ids are the caller's to resolve.
+bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& step, string& error);
+// one stage alone: 0 force, 1 walls, 2 advect, 3 divergence (into div), 4 pressure (div -> p), 5 project (reads p) and walls
+bool fluid_stage(int stage, float* const f[4], float* p, float* div, const int32_t whd[3], const vpt_fluid_step& step, string& error);
+
 // ---- a quad mesh out of a signed-distance voxel grid (include/vpt.h: vpt_mesh_sdf; host/vpt_sdf_mesh.cpp) ---------------------------
 struct sdf_mesh {
   vector<vec3f> positions = {}, normals = {};

@@ -7,6 +7,7 @@
 #include <memory>
 #include <set>
 
+#include "vpt_fluid_rule.h"
 #include "vpt_host.h"
 
 using namespace vpt;
@@ -645,6 +646,26 @@ int vpth_scene_filter_volume(void* hh, const vpt_filter_entry* entry, const vpt_
   if (v.vol.size() < (size_t)whd[0] * (size_t)whd[1] * (size_t)whd[2]) return set_error(err, errlen, "filter: entry 0: the volume holds fewer voxels than its whd"), -1;
   auto error = string{};
   if (!filter_voxels(v.vol.data(), whd, *entry, ops, num_ops, error)) return set_error(err, errlen, error), -1;
+  return 0;
+}
+// vpt_scene_fluid_step applied to the scene's copies of the step's four volumes by the host mirror (host/vpt_fluid.cpp).  The rules of
+// vpt_scene_fluid_step; a refused call writes nothing.
+int vpth_scene_fluid_step(void* hh, const vpt_fluid_step* step, char* err, int errlen) {
+  auto& sc = ((host_scene*)hh)->scene;
+  if (!step) return set_error(err, errlen, "fluid: null step"), -1;
+  auto whds = vector<int32_t>{};
+  for (auto& v : sc.volumes) whds.insert(whds.end(), {v.whd.x, v.whd.y, v.whd.z});
+  bool unsupported;
+  if (auto fault = vpt_fluid_step_fault(*step, (int)sc.volumes.size(), [&](int id) { return whds.data() + 3 * id; }, &unsupported))
+    return set_error(err, errlen, string{"fluid: "} + fault), -1;
+  float* f[4];
+  for (auto a = 0; a < 4; a++) {
+    auto& v = sc.volumes[a ? step->velocity[a - 1] : step->density];
+    if (v.vol.size() < (size_t)v.whd.x * (size_t)v.whd.y * (size_t)v.whd.z) return set_error(err, errlen, "fluid: a volume holds fewer voxels than its whd"), -1;
+    f[a] = v.vol.data();
+  }
+  auto error = string{};
+  if (!fluid_step(f, whds.data() + 3 * step->density, *step, error)) return set_error(err, errlen, error), -1;
   return 0;
 }
 // make_lights of the scene as the setters above left it (an SDF is a light iff its material is emissive), then the flattened descriptor again

@@ -13,7 +13,7 @@ from ._abi import (BVH_MIDDLE, BVH_NODE, BVH_SAH, LIGHT, MESH_ELEMENTS, MESH_FLO
                    VptEnvironment, VptError, VptMaterial, VptSceneDescBvh, VptFilterEntry, VptSceneDescLights, VptSculptEntry, VptSdf, VptVolumeInstance, _Handle,
                    _check, _filled, _host_call, _mesh_desc, _mesh_region, _meshed, hip, host)
 from .device import PathtraceParams, PathtraceState
-from .edits import (LEVEL_TABLES, BvhRebuild, FilterEdit, FilterEntry, FilterOp, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan,
+from .edits import (LEVEL_TABLES, BvhRebuild, FilterEdit, FilterEntry, FilterOp, FluidStep, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan,
                     TextureEdit, VolumeEdit, VolumeNew, VolumeSetEdit, VolumeSource, mesh)
 
 
@@ -218,6 +218,7 @@ def save_mesh_ply(path: str, positions, quads, normals=None) -> None:
 # name the volumes, grid instances and SDFs as they are - and "volume_set": a VolumeSetEdit that holds anything, which renumbers all three.
 # A volume's voxels have three ledgers, the VolumeEdit, the SculptEdit and the FilterEdit: a volume pending in one is refused by the setters
 # of the others (_note_volume, sculpt_volume, filter_volume), since each ledger is applied to the device as a whole and in its own call.
+# The pending FluidSteps are a fourth, over four volumes each: fluid_step refuses a volume pending in the three, and they one pending in it.
 _REFUSED_WHILE = {"vertices": ("instances", "shapes"),                       # set_instance_frame, set_shape_positions, set_subdiv (cage, displacement)
                   "rebuild": ("edit", "subdivs", "instances", "shapes"),      # rebuild_bvh
                   "instances": ("geometry", "subdivs", "shapes"),             # add_instance, remove_instances, set_instance, update_instances
@@ -226,7 +227,7 @@ _REFUSED_WHILE = {"vertices": ("instances", "shapes"),                       # s
                   "volume_set": ("volumes",)}                                 # add_volume, remove_volumes, add_volume_instance, ..., update_volume_set
 _HAND_OUT = {"edit": "edit out with update_bvh()", "geometry": "edit out with update_bvh()",
              "instances": "instance changes out with update_instances()", "shapes": "shape changes out with update_shapes()",
-             "subdivs": "subdiv changes out with update_subdivs()", "volumes": "volume changes out with update_volumes() / update_sculpts() / update_filters()",
+             "subdivs": "subdiv changes out with update_subdivs()", "volumes": "volume changes out with update_volumes() / update_sculpts() / update_filters() / update_fluid()",
              "volume_set": "additions and removals of volumes, grid instances and SDFs out with update_volume_set()"}
 
 
@@ -244,6 +245,7 @@ class HostScene(_Handle):
         self._edit, self._inst_edit, self._shape_edit = SceneEdit(), InstanceEdit(), ShapeEdit()
         self._texture_edit, self._volume_edit, self._subdiv_edit = TextureEdit(), VolumeEdit(), SubdivEdit()
         self._sculpt_edit, self._volume_set_edit, self._filter_edit = SculptEdit(), VolumeSetEdit(), FilterEdit()
+        self._fluid_steps = []   # the FluidSteps fluid_step applied since update_fluid()
         self._lazy_bakes = []   # (volume, VolumeSource) of bake_volume whose host copy is not baked yet
         self.handle = _host_call(host.vpth_scene_load_ex, os.fsencode(filename), -1 if tess_device is None else tess_device, size=1024, handle=True)
         self.filename = filename
@@ -295,7 +297,7 @@ class HostScene(_Handle):
         """VptError unless a call of `kind` (_REFUSED_WHILE) may go ahead: the message names the update_*() to call first"""
         pending = {"edit": not self._edit.empty(), "geometry": bool(self._edit.instances or self._edit.shapes),
                    "instances": not self._inst_edit.empty(), "shapes": not self._shape_edit.empty(), "subdivs": not self._subdiv_edit.empty(),
-                   "volumes": not (self._volume_edit.empty() and self._sculpt_edit.empty() and self._filter_edit.empty()), "volume_set": not self._volume_set_edit.empty()}
+                   "volumes": not (self._volume_edit.empty() and self._sculpt_edit.empty() and self._filter_edit.empty() and not self._fluid_steps), "volume_set": not self._volume_set_edit.empty()}
         for blocker in _REFUSED_WHILE[kind]:
             if pending[blocker]:
                 raise VptError(f"{what}: hand the pending {_HAND_OUT[blocker]} first" + (why if blocker == "geometry" else ""))
@@ -733,6 +735,7 @@ class HostScene(_Handle):
             raise VptError(f"volume {index} has sculpts pending: hand them out with update_sculpts() first")
         if any(e.volume == index for e in self._filter_edit.entries):
             raise VptError(f"volume {index} has filters pending: hand them out with update_filters() first")
+        self._no_fluid_pending("set_volume / bake_volume", index)
         self._volume_edit.volumes[index] = src
 
     def set_volume(self, index: int, voxels, res: Optional[float] = None, region=None, mode: int = VOXELS_REPLACE) -> None:
@@ -950,6 +953,7 @@ class HostScene(_Handle):
             raise VptError(f"sculpt_volume: volume {index} is in the pending volume edit: hand it out with update_volumes() first")
         if any(e.volume == index for e in self._filter_edit.entries):
             raise VptError(f"sculpt_volume: volume {index} has filters pending: hand them out with update_filters() first")
+        self._no_fluid_pending("sculpt_volume", index)
         old, res = self.volume(index)
         whd = old.shape[::-1]
         if origin is None:
@@ -986,6 +990,7 @@ class HostScene(_Handle):
             raise VptError(f"filter_volume: volume {index} is in the pending volume edit: hand it out with update_volumes() first")
         if any(e.volume == index for e in self._sculpt_edit.entries):
             raise VptError(f"filter_volume: volume {index} has sculpts pending: hand them out with update_sculpts() first")
+        self._no_fluid_pending("filter_volume", index)
         whd, res = self._volume_shape(index)
         if origin is None:
             origin = np.zeros(3, np.float32)
@@ -1007,6 +1012,35 @@ class HostScene(_Handle):
         _host_call(host.vpth_scene_update_volumes, self.handle)
         edit, self._filter_edit = self._filter_edit, FilterEdit()
         return edit
+
+    # -- a stable-fluids step (the host side of vpt_scene_fluid_step): fluid_step applies the step to the scene's copies of the four volumes
+    #    through the host mirror at once and notes it, update_fluid() hands the noted steps out --------------------------------------------
+    def _no_fluid_pending(self, what: str, index: int) -> None:
+        if any(index in s.volumes() for s in self._fluid_steps):
+            raise VptError(f"{what}: volume {index} has fluid steps pending: hand them out with update_fluid() first")
+
+    def fluid_step(self, step: FluidStep) -> FluidStep:
+        """`step.steps` Stable Fluids steps over the density and velocity volumes `step` names, by the rule of vpt_scene_fluid_step.
+        Returns the step it noted.  A refused call changes nothing."""
+        self._may("fluid_step", "volume_entries")
+        for index in step.volumes():
+            if index in self._volume_edit.volumes:
+                raise VptError(f"fluid_step: volume {index} is in the pending volume edit: hand it out with update_volumes() first")
+            if any(e.volume == index for e in self._sculpt_edit.entries):
+                raise VptError(f"fluid_step: volume {index} has sculpts pending: hand them out with update_sculpts() first")
+            if any(e.volume == index for e in self._filter_edit.entries):
+                raise VptError(f"fluid_step: volume {index} has filters pending: hand them out with update_filters() first")
+        self._run_bakes()
+        _host_call(host.vpth_scene_fluid_step, self.handle, C.byref(step.to_abi()[0]))
+        self._fluid_steps.append(step)
+        return step
+
+    def update_fluid(self) -> list:
+        """the flattened descriptor of the scene as fluid_step left it (no light, no record changes: whd and res stay).  Returns the
+        FluidSteps in order, each for DeviceScene.fluid_step."""
+        _host_call(host.vpth_scene_update_volumes, self.handle)
+        steps, self._fluid_steps = self._fluid_steps, []
+        return steps
 
     def volgrid_majorants(self, index: int) -> np.ndarray:
         """the host mirror of DeviceScene.volgrid_majorants on the scene's copy of volume `index` (pending bakes run first): the volgrid
