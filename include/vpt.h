@@ -640,6 +640,45 @@ typedef struct vpt_fluid_step {
 } vpt_fluid_step;
 int vpt_scene_fluid_step(vpt_scene* scene, const vpt_fluid_step* step);
 
+/* ---- the pressure of a fluid step by multigrid ---------------------------------------------------------------------------
+ * vpt_scene_fluid_step_solver is vpt_scene_fluid_step with stage 6 chosen by `solver`.  A null solver, or kind VPT_FLUID_JACOBI, is
+ * vpt_scene_fluid_step bit for bit and launch for launch (the other fields of the solver are then not read).  With VPT_FLUID_MULTIGRID
+ * stage 6 is `cycles` V-cycles of an aggregation multigrid with Galerkin coarse operators from p = 0; step->iterations is validated as
+ * before and not used.  The rule, in csrc/vpt_fluid_rule.h beside the rest (float32, nothing fused, sums in the order written):
+ *  - Levels.  Level 0 is the volume (w, h, d); level l + 1 has (n + 1) / 2 nodes per axis; the coarsest level is the first whose every
+ *    axis is <= 8 (it may be level 0).  Index I of level l covers c = min(2^l, n0 - I 2^l) nodes of level 0 along its axis.
+ *  - Operator at node (I, J, K) of level l: face weights wx = cy[J] cz[K], wy = cx[I] cz[K], wz = cx[I] cy[J], each the product of two
+ *    int -> float conversions.  S = 0 + the sum over -x, +x, -y, +y, -z, +z, in this order, of w_axis * p[neighbour] for the neighbours
+ *    inside the level; D = 0 + the sum in the same order of w_axis over the directions whose neighbour is inside or whose face is open (a
+ *    closed face adds nothing).  The level's equation is D p - S = s_l b_l with b_0 = -d, s_0 = 1, s_{l+1} = s_l * 1.5f: at level 0 it has
+ *    the fixed point of stage 6's Jacobi, and 1.5 is the over-correction piecewise-constant aggregation needs.
+ *  - Smoother: red-black Gauss-Seidel, colour (I + J + K) & 1.  A half-sweep sets every node of one colour to (S + s_l * b) / D by a
+ *    correctly rounded division; a node with D == 0 keeps its value.  A pre-sweep is colour 0 then 1, a post-sweep colour 1 then 0.
+ *  - Down: `smooth` pre-sweeps; r = b - (D * p - S) / s_l; b_{l+1}[I, J, K] = 0 + the sum of r over the children (2I + a, 2J + b, 2K + c)
+ *    that exist, a fastest, then b, then c; p_{l+1} = 0.
+ *  - Coarsest: `coarse_sweeps` pre-sweeps from the incoming guess.
+ *  - Up: p[i, j, k] = p[i, j, k] + p_{l+1}[i / 2, j / 2, k / 2], then `smooth` post-sweeps.
+ *  Every value stored is a vpt_filter_one_nan: a NaN is 0x7fc00000.
+ *  - Validation before anything is written (VPT_ERR_INVALID_ARG, the message names the field): what vpt_scene_fluid_step refuses; kind not
+ *    one of the two; with VPT_FLUID_MULTIGRID cycles outside 0..64, smooth outside 1..4, coarse_sweeps outside 1..64.
+ *  - vpt_scene_update_stats: bytes as vpt_scene_fluid_step.  launches = steps * (5 + cycles * V), where with L the index of the coarsest
+ *    level and the 2 * smooth half-sweeps of a smoothing run H to a launch (H = VPT_FLUID_MG_BLOCK = 2 | 4, default in csrc/vpt_fluid.hip;
+ *    a remainder of 2 takes one launch more: A = (2 * smooth + H - 1) / H), V = 1 for L = 0 and L * (2 A + 1) + 1 otherwise: per level
+ *    above the coarsest the pre-smoothing, the restriction and the post-smoothing (the prolongation is its first launch's staging), and
+ *    one launch for the coarsest level.  The bits do not depend on H. */
+#define VPT_FLUID_JACOBI 0
+#define VPT_FLUID_MULTIGRID 1
+#define VPT_FLUID_MAX_CYCLES 64
+#define VPT_FLUID_MAX_SMOOTH 4
+#define VPT_FLUID_MAX_COARSE_SWEEPS 64
+typedef struct vpt_fluid_solver {
+  int32_t kind;          /* VPT_FLUID_JACOBI = 0, VPT_FLUID_MULTIGRID = 1 */
+  int32_t cycles;        /* 0..64 */
+  int32_t smooth;        /* 1..4 */
+  int32_t coarse_sweeps; /* 1..64 */
+} vpt_fluid_solver;      /* 16 bytes */
+int vpt_scene_fluid_step_solver(vpt_scene* scene, const vpt_fluid_step* step, const vpt_fluid_solver* solver);
+
 /* ---- adding and removing volumes, grid instances and SDFs -------------------------------------------------------------
  * The one thing vpt_scene_update_volumes leaves fixed: how many there are.  An edit of its own, because vpt_volume_edit keeps its layout;
  * the contract is that of vpt_scene_update_instances and vpt_scene_update_shapes.  After vpt_scene_update_volume_set(s, edit) every table
@@ -1637,6 +1676,8 @@ int  vpt_session_sculpt_volumes(vpt_session* session, const vpt_sculpt_edit* edi
 int  vpt_session_filter_volumes(vpt_session* session, const vpt_filter_edit* edit);
 /* vpt_scene_fluid_step, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_fluid_step(vpt_session* session, const vpt_fluid_step* step);
+/* vpt_scene_fluid_step_solver, then a reset; a refused edit leaves the session as it was */
+int  vpt_session_fluid_step_solver(vpt_session* session, const vpt_fluid_step* step, const vpt_fluid_solver* solver);
 /* vpt_scene_set_volgrid_color, then a reset.  The session stays a volgrid session: its pick, id frame and first-collision pass keep
  * meaning the grey flight */
 int  vpt_session_set_volgrid_color(vpt_session* session, int on);

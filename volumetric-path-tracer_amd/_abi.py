@@ -215,6 +215,13 @@ class VptFluidStep(C.Structure):  # vpt_fluid_step
 assert C.sizeof(VptFluidStep) == 52
 
 
+class VptFluidSolver(C.Structure):  # vpt_fluid_solver
+    _fields_ = [("kind", C.c_int32), ("cycles", C.c_int32), ("smooth", C.c_int32), ("coarse_sweeps", C.c_int32)]
+
+
+assert C.sizeof(VptFluidSolver) == 16
+
+
 class VptVolumeNew(C.Structure):  # vpt_volume_new
     _fields_ = [("whd", C.c_int32 * 3), ("res", C.c_float), ("source", C.c_int32), ("offset", C.c_int64), ("bake", C.c_void_p), ("fill", C.c_float),
                 ("copy_of", C.c_int32)]
@@ -241,6 +248,9 @@ FLUID_MAX_ITERATIONS = 1024
 FLUID_RECORD_BYTES = 48   # VPT_FLUID_RECORD_BYTES: a step as the kernels get it
 FLUID_DEFAULT_BLOCK = 2   # sweeps per Jacobi launch unless VPT_FLUID_BLOCK says 1, 2 or 4 (csrc/vpt_fluid.hip)
 FLUID_OPEN_ALL = 63       # vpt_fluid_step::open_faces: bit 0..5 = -x, +x, -y, +y, -z, +z
+FLUID_JACOBI, FLUID_MULTIGRID = 0, 1   # vpt_fluid_solver::kind
+FLUID_MAX_CYCLES, FLUID_MAX_SMOOTH, FLUID_MAX_COARSE_SWEEPS = 64, 4, 64
+FLUID_DEFAULT_MG_BLOCK = 2   # half-sweeps per smoothing launch unless VPT_FLUID_MG_BLOCK says 2 or 4 (csrc/vpt_fluid.hip)
 MATERIAL_TYPES = ["matte", "glossy", "reflective", "transparent", "refractive", "subsurface", "volumetric", "gltfpbr"]
 
 
@@ -355,6 +365,8 @@ hip.vpt_multi_filter_volumes.argtypes = [_p, C.POINTER(VptFilterEdit)]
 hip.vpt_session_filter_volumes.argtypes = [_p, C.POINTER(VptFilterEdit)]
 hip.vpt_scene_fluid_step.argtypes = [_p, C.POINTER(VptFluidStep)]
 hip.vpt_session_fluid_step.argtypes = [_p, C.POINTER(VptFluidStep)]
+hip.vpt_scene_fluid_step_solver.argtypes = [_p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver)]
+hip.vpt_session_fluid_step_solver.argtypes = [_p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver)]
 hip.vpt_scene_update_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
 hip.vpt_multi_update_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
 hip.vpt_session_edit_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
@@ -538,6 +550,9 @@ host.vpth_filter_voxels.argtypes = [_p, _p, C.POINTER(VptFilterEntry), _p, C.c_i
 host.vpth_filter_gaussian_weights.argtypes = [C.c_float, C.c_int, _p]
 host.vpth_scene_fluid_step.argtypes = [_p, C.POINTER(VptFluidStep), C.c_char_p, C.c_int]
 host.vpth_fluid_step.argtypes = [_p, _p, _p, _p, _p, C.POINTER(VptFluidStep), C.c_char_p, C.c_int]
+host.vpth_scene_fluid_step_solver.argtypes = [_p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver), C.c_char_p, C.c_int]
+host.vpth_fluid_step_solver.argtypes = [_p, _p, _p, _p, _p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver), C.c_char_p, C.c_int]
+host.vpth_fluid_multigrid_pressure.argtypes = [_p, _p, _p, C.c_int, C.POINTER(VptFluidSolver), C.c_char_p, C.c_int]
 host.vpth_fluid_stage.argtypes = [C.c_int, _p, _p, _p, _p, _p, _p, _p, C.POINTER(VptFluidStep), C.c_char_p, C.c_int]
 host.vpth_scene_desc.argtypes = [_p]
 host.vpth_scene_desc.restype = _p

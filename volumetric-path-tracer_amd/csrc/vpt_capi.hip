@@ -224,7 +224,10 @@ int vpt_scene_sculpt_volumes(vpt_scene* s, const vpt_sculpt_edit* edit) { return
 // voxels alone again, remapped, blurred and broken up with noise where they live (vpt_filter.hip)
 int vpt_scene_filter_volumes(vpt_scene* s, const vpt_filter_edit* edit) { return edit_scene(s, edit, filter_apply); }
 // the voxels of four volumes at once: a density moved by a velocity, one stable-fluids step after another (vpt_fluid.hip)
-int vpt_scene_fluid_step(vpt_scene* s, const vpt_fluid_step* step) { return edit_scene(s, step, fluid_apply); }
+int vpt_scene_fluid_step(vpt_scene* s, const vpt_fluid_step* step) { return vpt_scene_fluid_step_solver(s, step, nullptr); }
+int vpt_scene_fluid_step_solver(vpt_scene* s, const vpt_fluid_step* step, const vpt_fluid_solver* solver) {   // stage 6 by multigrid, if asked
+  return edit_scene(s, step, [solver](resident& r, const vpt_fluid_step& st, edit_outcome& out) { return fluid_apply(r, st, solver, out); });
+}
 // volumes, grid instances and SDFs added and removed (vpt_volume_set.hip): the pool compacted by one gather, the lights following the SDFs
 int vpt_scene_update_volume_set(vpt_scene* s, const vpt_volume_set_edit* edit) { return edit_scene(s, edit, volume_set_apply); }
 // the BVHs built anew (vpt_bvh_rebuild.hip), the set of instances changed (vpt_instance_update.hip), the shape list changed (vpt_shape_update.hip)

@@ -8,4 +8,7 @@
 // Jacobi sweeps between two of the scratch's fields (K sweeps a launch, K from VPT_FLUID_BLOCK) and project + walls.  Only the voxels of
 // the four volumes change: no table, no mirror, no light.  r's counters (vpt_scene_update_stats) describe this call; the device has
 // finished when the call returns.
-int fluid_apply(resident& r, const vpt_fluid_step& step, edit_outcome& out);
+// solver (include/vpt.h: vpt_scene_fluid_step_solver): null or VPT_FLUID_JACOBI, the above; VPT_FLUID_MULTIGRID, solver->cycles V-cycles in
+// the Jacobi launches' place, the levels above the volume in r.d_fluid_mg (grown to three fields a level), VPT_FLUID_MG_BLOCK half-sweeps
+// a smoothing launch.
+int fluid_apply(resident& r, const vpt_fluid_step& step, const vpt_fluid_solver* solver, edit_outcome& out);

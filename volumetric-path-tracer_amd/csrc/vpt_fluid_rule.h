@@ -78,6 +78,70 @@ VPT_FLUID_HD float vpt_fluid_project(float u, const float* p, int at, int step, 
   return vpt_filter_one_nan(u - 0.5f * (hi - lo));
 }
 
+// ---- 6'. the pressure by multigrid (include/vpt.h: vpt_scene_fluid_step_solver): aggregation, Galerkin coarse operators -----------------
+// one level as the kernels get it and the mirror reads it: its own size, the volume's, its index and its factor s_l
+struct vpt_fluid_mg_level {
+  int32_t  w, h, d;      // nodes of this level
+  int32_t  w0, h0, d0;   // nodes of level 0
+  int32_t  l;
+  uint32_t open;
+  float    s;            // s_0 = 1, s_{l+1} = s_l * 1.5f
+};
+constexpr int VPT_FLUID_MG_COARSEST = 8;   // the coarsest level is the first whose every axis is <= this
+constexpr int VPT_FLUID_MG_MAX_LEVELS = 32;
+VPT_FLUID_HD bool vpt_fluid_mg_coarsest(const vpt_fluid_mg_level& g) {
+  return g.w <= VPT_FLUID_MG_COARSEST && g.h <= VPT_FLUID_MG_COARSEST && g.d <= VPT_FLUID_MG_COARSEST;
+}
+inline vpt_fluid_mg_level vpt_fluid_mg_level0(const vpt_fluid_record& g) { return {g.w, g.h, g.d, g.w, g.h, g.d, 0, g.open, 1.0f}; }
+inline vpt_fluid_mg_level vpt_fluid_mg_coarser(const vpt_fluid_mg_level& g) {
+  return {(g.w + 1) / 2, (g.h + 1) / 2, (g.d + 1) / 2, g.w0, g.h0, g.d0, g.l + 1, g.open, g.s * 1.5f};
+}
+// the levels of a volume, finest first; returns how many (the coarsest is the last)
+inline int vpt_fluid_mg_levels(const vpt_fluid_record& g, vpt_fluid_mg_level out[VPT_FLUID_MG_MAX_LEVELS]) {
+  int n  = 1;
+  out[0] = vpt_fluid_mg_level0(g);
+  while (!vpt_fluid_mg_coarsest(out[n - 1])) out[n] = vpt_fluid_mg_coarser(out[n - 1]), n++;
+  return n;
+}
+// how many nodes of level 0 index I of level l covers along an axis of n0 nodes
+VPT_FLUID_HD float vpt_fluid_mg_cover(int I, int l, int n0) {
+  const int left = n0 - (I << l);
+  return (float)(left < (1 << l) ? left : (1 << l));
+}
+// the right-hand side as stored: level 0 keeps stage 5's d, and b_0 = -d
+VPT_FLUID_HD float vpt_fluid_mg_b(const vpt_fluid_mg_level& g, float stored) { return g.l == 0 ? -stored : stored; }
+VPT_FLUID_HD int   vpt_fluid_mg_colour(int I, int J, int K) { return (I + J + K) & 1; }
+
+// S and D at node (I, J, K) of level g.  at[0..5]: where in `p` its neighbours -x, +x, -y, +y, -z, +z lie; one outside the level is not read
+VPT_FLUID_HD void vpt_fluid_mg_sums(const float* p, const int at[6], int I, int J, int K, const vpt_fluid_mg_level& g, float& S, float& D) {
+  const float cx = vpt_fluid_mg_cover(I, g.l, g.w0), cy = vpt_fluid_mg_cover(J, g.l, g.h0), cz = vpt_fluid_mg_cover(K, g.l, g.d0);
+  const float wgt[3]    = {cy * cz, cx * cz, cx * cy};
+  const bool  inside[6] = {I > 0, I < g.w - 1, J > 0, J < g.h - 1, K > 0, K < g.d - 1};
+  S = 0.0f, D = 0.0f;
+  for (int n = 0; n < 6; n++) {
+    if (inside[n]) S = S + wgt[n >> 1] * p[at[n]];
+    if (inside[n] || ((g.open >> n) & 1u)) D = D + wgt[n >> 1];
+  }
+}
+// a half-sweep's new value at a node of its colour: `was` where D == 0; sb = s_l * b
+VPT_FLUID_HD float vpt_fluid_mg_scaled(const vpt_fluid_mg_level& g, float stored) { return g.s * vpt_fluid_mg_b(g, stored); }
+VPT_FLUID_HD float vpt_fluid_mg_relax(float S, float D, float sb, float was) { return D == 0.0f ? was : vpt_filter_one_nan((S + sb) / D); }
+// the residual in b's units at a node whose value is `centre`
+VPT_FLUID_HD float vpt_fluid_mg_residual(float S, float D, float centre, float b, float s) { return vpt_filter_one_nan(b - (D * centre - S) / s); }
+// the prolongation: a node's value plus its parent's
+VPT_FLUID_HD float vpt_fluid_mg_correct(float fine, float parent) { return vpt_filter_one_nan(fine + parent); }
+
+// null, or what is wrong with the solver (null: the Jacobi of stage 6)
+inline const char* vpt_fluid_solver_fault(const vpt_fluid_solver* s) {
+  if (!s || s->kind == VPT_FLUID_JACOBI) return nullptr;
+  if (s->kind != VPT_FLUID_MULTIGRID) return "solver: kind is not one of VPT_FLUID_JACOBI, VPT_FLUID_MULTIGRID";
+  if (s->cycles < 0 || s->cycles > VPT_FLUID_MAX_CYCLES) return "solver: cycles is not one of 0..64";
+  if (s->smooth < 1 || s->smooth > VPT_FLUID_MAX_SMOOTH) return "solver: smooth is not one of 1..4";
+  if (s->coarse_sweeps < 1 || s->coarse_sweeps > VPT_FLUID_MAX_COARSE_SWEEPS) return "solver: coarse_sweeps is not one of 1..64";
+  return nullptr;
+}
+inline bool vpt_fluid_multigrid(const vpt_fluid_solver* s) { return s && s->kind == VPT_FLUID_MULTIGRID; }
+
 // ---- what both sides refuse, in the same words ------------------------------------------------------------------------------------------
 constexpr long long VPT_FLUID_MAX_NODES = 1ll << 30;
 // null, or what is wrong with step `s` over `num_volumes` volumes whose sizes whd_of(id) answers; *unsupported: the size guard refused it

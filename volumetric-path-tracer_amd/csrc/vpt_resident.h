@@ -80,6 +80,8 @@ struct resident {
   size_t        filter_scratch_bytes = 0;
   device_buffer d_fluid_scratch;    // vpt_scene_fluid_step: the four advected fields until they are moved into place, then the divergence and the two pressures
   size_t        fluid_scratch_bytes = 0;
+  device_buffer d_fluid_mg;         // vpt_scene_fluid_step_solver: p, its ping-pong partner and b of every multigrid level above the volume
+  size_t        fluid_mg_bytes = 0;
   // what the last edit did (vpt_scene_update_stats): begin_update (vpt_update_helpers.h) starts them, launches and sends count themselves
   int        last_launches = 0;
   long long  last_bytes    = 0;

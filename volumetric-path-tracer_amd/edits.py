@@ -9,7 +9,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._abi import (FILTER_BLUR, FILTER_MAX_RADIUS, FILTER_NOISE, FILTER_RECORD_BYTES, FILTER_REMAP, FLUID_DEFAULT_BLOCK, FLUID_RECORD_BYTES, VptFluidStep, INSTANCE, MESH_ELEMENTS, MESH_FLOATS, SCULPT_RECORD_BYTES,
+from ._abi import (FILTER_BLUR, FILTER_MAX_RADIUS, FILTER_NOISE, FILTER_RECORD_BYTES, FILTER_REMAP, FLUID_DEFAULT_BLOCK, FLUID_DEFAULT_MG_BLOCK, FLUID_JACOBI, FLUID_MULTIGRID, FLUID_RECORD_BYTES, VptFluidSolver, VptFluidStep, INSTANCE, MESH_ELEMENTS, MESH_FLOATS, SCULPT_RECORD_BYTES,
                    VOXELS_REPLACE, VptFilterEdit, VptFilterEntry, VptFilterOp, host, VptBakeDesc, VptBvhRebuild, VptCamera, VptEnvironment,
                    VptError, VptInstanceEdit, VptMaterial, VptSceneEdit, VptSculptEdit, VptSculptEntry, VptSculptStamp, VptSdf, VptShapeData, VptShapeEdit,
                    VptSubdivEdit, VptSubdivLevel, VptSubdivPlan, VptTexture, VptTextureEdit, VptVolumeEdit, VptVolumeInstance, VptVolumeNew, VptVolumeSetEdit,
@@ -571,6 +571,31 @@ class FilterEdit:
 
 # ---- a stable-fluids step over four volumes ---------------------------------------------------------------------------------------------
 @dataclass
+class FluidSolver:
+    """How a FluidStep solves its pressure (include/vpt.h: vpt_fluid_solver): kind FLUID_JACOBI is the step's own `iterations` sweeps,
+    FLUID_MULTIGRID `cycles` V-cycles with `smooth` red-black sweeps before and after each coarser level and `coarse_sweeps` on the
+    coarsest - the step's `iterations` is then not used."""
+    kind: int = FLUID_MULTIGRID
+    cycles: int = 3
+    smooth: int = 2
+    coarse_sweeps: int = 16
+
+    def launches(self, step: "FluidStep", whd, block: int = FLUID_DEFAULT_MG_BLOCK) -> int:
+        """launches of `step` over volumes of `whd` as vpt_scene_update_stats counts them at `block` half-sweeps per smoothing launch
+        (VPT_FLUID_MG_BLOCK): the formula of include/vpt.h"""
+        if self.kind == FLUID_JACOBI:
+            return step.launches()
+        levels, dims = 0, [int(n) for n in whd]
+        while max(dims) > 8:
+            levels, dims = levels + 1, [(n + 1) // 2 for n in dims]
+        smoothing = (2 * self.smooth + block - 1) // block
+        return step.steps * (5 + self.cycles * (levels * (2 * smoothing + 1) + 1)) if min(whd) > 0 else 0
+
+    def to_abi(self):
+        return VptFluidSolver(int(self.kind), int(self.cycles), int(self.smooth), int(self.coarse_sweeps))
+
+
+@dataclass
 class FluidStep:
     """What vpt_scene_fluid_step takes (include/vpt.h: vpt_fluid_step): the density's volume id, the three of the velocity (four
     different volumes of equal whd, velocities in node spacings per unit time), `steps` repetitions of one Stable Fluids step with
@@ -585,6 +610,7 @@ class FluidStep:
     lift: tuple = (0.0, 0.0, 0.0)
     keep_density: float = 1.0
     keep_velocity: float = 1.0
+    solver: Optional[FluidSolver] = None   # None: the `iterations` Jacobi sweeps; HostScene.fluid_step notes the solver it ran here
 
     def volumes(self) -> tuple:
         return (int(self.density), *(int(v) for v in self.velocity))

@@ -59,6 +59,65 @@ void pressure(const vpt_fluid_record& g, const float* div, float* p) {
   }
   std::copy(from.begin(), from.end(), p);
 }
+
+// ---- the pressure by multigrid: the V-cycle of include/vpt.h over the rule header's functions, a level at a time, in place ---------------
+template <typename Node>
+void each_node(const vpt_fluid_mg_level& g, Node node) {
+  for (auto k = 0; k < g.d; k++)
+    for (auto j = 0; j < g.h; j++)
+      for (auto i = 0; i < g.w; i++) node(i, j, k, i + g.w * (j + g.h * k));
+}
+void mg_sums(const vpt_fluid_mg_level& g, const float* p, int i, int j, int k, int at, float& S, float& D) {
+  const int near[6] = {at - 1, at + 1, at - g.w, at + g.w, at - g.w * g.h, at + g.w * g.h};
+  vpt_fluid_mg_sums(p, near, i, j, k, g, S, D);
+}
+void mg_half_sweep(const vpt_fluid_mg_level& g, const float* b, float* p, int colour) {
+  each_node(g, [&](int i, int j, int k, int at) {
+    if (vpt_fluid_mg_colour(i, j, k) != colour) return;
+    float S, D;
+    mg_sums(g, p, i, j, k, at, S, D);
+    p[at] = vpt_fluid_mg_relax(S, D, vpt_fluid_mg_scaled(g, b[at]), p[at]);
+  });
+}
+void mg_sweeps(const vpt_fluid_mg_level& g, const float* b, float* p, int sweeps, int first) {
+  for (auto n = 0; n < sweeps; n++) mg_half_sweep(g, b, p, first), mg_half_sweep(g, b, p, first ^ 1);
+}
+struct mg_fields {
+  vector<float> p, b;   // of the levels above 0
+};
+void mg_cycle(const vpt_fluid_mg_level* levels, int count, int l, const float* b, float* p, vector<mg_fields>& coarse, const vpt_fluid_solver& s) {
+  const auto& g = levels[l];
+  if (l == count - 1) return mg_sweeps(g, b, p, s.coarse_sweeps, 0);
+  mg_sweeps(g, b, p, s.smooth, 0);
+  const auto& c    = levels[l + 1];
+  auto&       next = coarse[(size_t)l + 1];
+  next.p.assign((size_t)c.w * c.h * c.d, 0.0f);
+  next.b.assign(next.p.size(), 0.0f);
+  auto r = vector<float>((size_t)g.w * g.h * g.d);
+  each_node(g, [&](int i, int j, int k, int at) {
+    float S, D;
+    mg_sums(g, p, i, j, k, at, S, D);
+    r[at] = vpt_fluid_mg_residual(S, D, p[at], vpt_fluid_mg_b(g, b[at]), g.s);
+  });
+  each_node(c, [&](int I, int J, int K, int at) {
+    auto sum = 0.0f;
+    for (auto z = 2 * K; z < 2 * K + 2 && z < g.d; z++)
+      for (auto y = 2 * J; y < 2 * J + 2 && y < g.h; y++)
+        for (auto x = 2 * I; x < 2 * I + 2 && x < g.w; x++) sum = sum + r[x + g.w * (y + g.h * z)];
+    next.b[at] = vpt_filter_one_nan(sum);
+  });
+  mg_cycle(levels, count, l + 1, next.b.data(), next.p.data(), coarse, s);
+  each_node(g, [&](int i, int j, int k, int at) { p[at] = vpt_fluid_mg_correct(p[at], next.p[(i / 2) + c.w * ((j / 2) + c.h * (k / 2))]); });
+  mg_sweeps(g, b, p, s.smooth, 1);
+}
+void pressure_multigrid(const vpt_fluid_record& g, const vpt_fluid_solver& s, const float* div, float* p) {
+  vpt_fluid_mg_level levels[VPT_FLUID_MG_MAX_LEVELS];
+  const auto         count  = vpt_fluid_mg_levels(g, levels);
+  auto               coarse = vector<mg_fields>((size_t)count);
+  std::fill(p, p + nodes_of(g), 0.0f);
+  for (auto n = 0; n < s.cycles; n++) mg_cycle(levels, count, 0, div, p, coarse, s);
+}
+
 void project(float* const f[4], const vpt_fluid_record& g, const float* p) {
   each_node(g, [&](int i, int j, int k, int at) {
     f[1][at] = vpt_fluid_project(f[1][at], p, at, 1, i, g.w, g.open, 0);
@@ -93,17 +152,31 @@ bool fluid_stage(int stage, float* const f[4], float* p, float* div, const int32
   return true;
 }
 
-bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& s, string& error) {
+bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& s, const vpt_fluid_solver* solver, string& error) {
   if (auto fault = fault_of(whd, s)) return error = string{"fluid: "} + fault, false;
+  if (auto fault = vpt_fluid_solver_fault(solver)) return error = string{"fluid: "} + fault, false;
   const auto g = vpt_fluid_make_record(whd, s);
   auto       div = vector<float>(nodes_of(g)), p = div;
   for (auto n = 0; n < s.steps && nodes_of(g) > 0; n++) {
     force(f, g), walls(f, g);
     advect(f, g), walls(f, g);
     divergence(f, g, div.data());
-    pressure(g, div.data(), p.data());
+    if (vpt_fluid_multigrid(solver)) pressure_multigrid(g, *solver, div.data(), p.data());
+    else pressure(g, div.data(), p.data());
     project(f, g, p.data());
   }
+  return true;
+}
+bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& s, string& error) { return fluid_step(f, whd, s, nullptr, error); }
+
+bool fluid_multigrid_pressure(const float* div, float* p, const int32_t whd[3], int open_faces, const vpt_fluid_solver& solver, string& error) {
+  auto step = vpt_fluid_step{};
+  step.open_faces = open_faces;
+  if (auto fault = fault_of(whd, step)) return error = string{"fluid: "} + fault, false;
+  if (auto fault = vpt_fluid_solver_fault(&solver)) return error = string{"fluid: "} + fault, false;
+  if (!vpt_fluid_multigrid(&solver)) return error = "fluid: solver: kind is not VPT_FLUID_MULTIGRID", false;
+  const auto g = vpt_fluid_make_record(whd, step);
+  if (nodes_of(g) > 0) pressure_multigrid(g, solver, div, p);
   return true;
 }
 
@@ -112,11 +185,23 @@ bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& s
 extern "C" {
 
 // the host mirror on four host arrays of whd[0] * whd[1] * whd[2] nodes (x fastest); the step's volume ids are ignored.  A refused call writes nothing.
-int vpth_fluid_step(float* density, float* u, float* v, float* w, const int32_t* whd, const vpt_fluid_step* step, char* err, int errlen) {
+int vpth_fluid_step_solver(float* density, float* u, float* v, float* w, const int32_t* whd, const vpt_fluid_step* step, const vpt_fluid_solver* solver, char* err,
+    int errlen) {
   auto         error = vpt::string{};
   float* const f[4]  = {density, u, v, w};
   if (!density || !u || !v || !w || !whd || !step) error = "fluid: null argument";
-  else if (vpt::fluid_step(f, whd, *step, error)) return 0;
+  else if (vpt::fluid_step(f, whd, *step, solver, error)) return 0;
+  if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", error.c_str());
+  return -1;
+}
+int vpth_fluid_step(float* density, float* u, float* v, float* w, const int32_t* whd, const vpt_fluid_step* step, char* err, int errlen) {
+  return vpth_fluid_step_solver(density, u, v, w, whd, step, nullptr, err, errlen);
+}
+// stage 6 alone by multigrid (include/vpt.h: vpt_scene_fluid_step_solver): div -> p, `solver->cycles` V-cycles from 0
+int vpth_fluid_multigrid_pressure(const float* div, float* p, const int32_t* whd, int open_faces, const vpt_fluid_solver* solver, char* err, int errlen) {
+  auto error = vpt::string{};
+  if (!div || !p || !whd || !solver) error = "fluid: null argument";
+  else if (vpt::fluid_multigrid_pressure(div, p, whd, open_faces, *solver, error)) return 0;
   if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", error.c_str());
   return -1;
 }

@@ -462,6 +462,10 @@ bool filter_gaussian_weights(float sigma, int radius, float* weights);
 // (csrc/vpt_fluid_rule.h) in plain serial loops, step.steps times - the same bits as the device.  Refuses what the C-ABI refuses, in its
 // words (false, `error` set, the arrays untouched); the step's volume ids are the caller's to resolve.
 bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& step, string& error);
+// the same with stage 6 by `solver` (include/vpt.h: vpt_scene_fluid_step_solver; null: the Jacobi)
+bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& step, const vpt_fluid_solver* solver, string& error);
+// stage 6 alone by multigrid: p from the divergence `div` of a volume of whd nodes
+bool fluid_multigrid_pressure(const float* div, float* p, const int32_t whd[3], int open_faces, const vpt_fluid_solver& solver, string& error);
 // one stage alone: 0 force, 1 walls, 2 advect, 3 divergence (into div), 4 pressure (div -> p), 5 project (reads p) and walls
 bool fluid_stage(int stage, float* const f[4], float* p, float* div, const int32_t whd[3], const vpt_fluid_step& step, string& error);
 

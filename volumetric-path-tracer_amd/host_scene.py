@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Optional
 
 import numpy as np
@@ -13,7 +13,7 @@ from ._abi import (BVH_MIDDLE, BVH_NODE, BVH_SAH, LIGHT, MESH_ELEMENTS, MESH_FLO
                    VptEnvironment, VptError, VptMaterial, VptSceneDescBvh, VptFilterEntry, VptSceneDescLights, VptSculptEntry, VptSdf, VptVolumeInstance, _Handle,
                    _check, _filled, _host_call, _mesh_desc, _mesh_region, _meshed, hip, host)
 from .device import PathtraceParams, PathtraceState
-from .edits import (LEVEL_TABLES, BvhRebuild, FilterEdit, FilterEntry, FilterOp, FluidStep, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan,
+from .edits import (LEVEL_TABLES, BvhRebuild, FilterEdit, FilterEntry, FilterOp, FluidSolver, FluidStep, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan,
                     TextureEdit, VolumeEdit, VolumeNew, VolumeSetEdit, VolumeSource, mesh)
 
 
@@ -1019,9 +1019,10 @@ class HostScene(_Handle):
         if any(index in s.volumes() for s in self._fluid_steps):
             raise VptError(f"{what}: volume {index} has fluid steps pending: hand them out with update_fluid() first")
 
-    def fluid_step(self, step: FluidStep) -> FluidStep:
-        """`step.steps` Stable Fluids steps over the density and velocity volumes `step` names, by the rule of vpt_scene_fluid_step.
-        Returns the step it noted.  A refused call changes nothing."""
+    def fluid_step(self, step: FluidStep, solver: Optional[FluidSolver] = None) -> FluidStep:
+        """`step.steps` Stable Fluids steps over the density and velocity volumes `step` names, by the rule of vpt_scene_fluid_step, the
+        pressure by `solver` (vpt_scene_fluid_step_solver; default: the step's own, else its Jacobi sweeps).  Returns the step it noted,
+        which carries the solver.  A refused call changes nothing."""
         self._may("fluid_step", "volume_entries")
         for index in step.volumes():
             if index in self._volume_edit.volumes:
@@ -1031,7 +1032,9 @@ class HostScene(_Handle):
             if any(e.volume == index for e in self._filter_edit.entries):
                 raise VptError(f"fluid_step: volume {index} has filters pending: hand them out with update_filters() first")
         self._run_bakes()
-        _host_call(host.vpth_scene_fluid_step, self.handle, C.byref(step.to_abi()[0]))
+        if solver is not None:
+            step = replace(step, solver=solver)
+        _host_call(host.vpth_scene_fluid_step_solver, self.handle, C.byref(step.to_abi()[0]), C.byref(step.solver.to_abi()) if step.solver else None)
         self._fluid_steps.append(step)
         return step
 
