@@ -679,6 +679,36 @@ typedef struct vpt_fluid_solver {
 } vpt_fluid_solver;      /* 16 bytes */
 int vpt_scene_fluid_step_solver(vpt_scene* scene, const vpt_fluid_step* step, const vpt_fluid_solver* solver);
 
+/* ---- smoke that keeps its shape: MacCormack advection and vorticity confinement ------------------------------------------
+ * vpt_scene_fluid_step_detail is vpt_scene_fluid_step_solver with stage 3 chosen by detail->advection and a stage 2b switched on by
+ * detail->vorticity > 0.  A null detail, or {VPT_FLUID_SEMI_LAGRANGIAN, 0}, is vpt_scene_fluid_step_solver bit for bit and launch for
+ * launch.  The rule, in csrc/vpt_fluid_rule.h beside the rest (float32, nothing fused, sums in the order written, clamps as selects, every
+ * stored value a vpt_filter_one_nan); a difference d_c a is a[+1] - a[-1] along component c with the indices clamped to the volume, as in
+ * stage 5:
+ *  2b. Confinement, after stage 2, every node reading the velocity stage 2 left.  omega = 0.5f * (d_y w - d_z v, d_z u - d_x w,
+ *      d_x v - d_y u); m = sqrtf((omega_x^2 + omega_y^2) + omega_z^2); eta_c = 0.5f * d_c m; N_c = eta_c / (sqrtf((eta_x^2 + eta_y^2) +
+ *      eta_z^2) + 1e-12f), a correctly rounded division; f = N x omega, each component a difference of two products; u_c = u_c + k * f_c
+ *      with k = dt * vorticity, one float32 product made on the host.  Then walls.
+ *  3.  With VPT_FLUID_MACCORMACK, per field phi of the four, all four reading the state before the advection, the velocity after 2. or
+ *      2b. giving both traces: hat = stage 3's value (the back-trace q, vpt_volgrid_trilerp, a NaN stored as 0x7fc00000); bar =
+ *      vpt_volgrid_trilerp(hat, r) with r_c = (float)i_c + dt * u_c clamped like q; phi' = hat + 0.5f * (phi - bar); then phi' =
+ *      phi' < lo ? lo : phi', phi' = phi' > hi ? hi : phi', lo and hi the least and the greatest of the eight corners of phi the first
+ *      trilerp read, taken by selects (v < lo ? v : lo, v > hi ? v : hi) from v000 on in the order v100, v010, v001, v011, v101, v110, v111.
+ *      Stage 4 follows as before.
+ *  - Validation before anything is written (VPT_ERR_INVALID_ARG, the message names the field, the scene is untouched): what
+ *    vpt_scene_fluid_step_solver refuses, in its words; advection not one of the two; vorticity not finite or negative.
+ *  - vpt_scene_update_stats: launches = vpt_scene_fluid_step_solver's + steps with VPT_FLUID_MACCORMACK (the second pass; the confinement
+ *    takes the force launch's place and adds none); bytes = VPT_FLUID_RECORD_BYTES + VPT_FLUID_DETAIL_BYTES when a detail that is not off
+ *    launches anything, else as before. */
+#define VPT_FLUID_SEMI_LAGRANGIAN 0
+#define VPT_FLUID_MACCORMACK      1
+#define VPT_FLUID_DETAIL_BYTES    8
+typedef struct vpt_fluid_detail {
+  int32_t advection;   /* VPT_FLUID_SEMI_LAGRANGIAN | VPT_FLUID_MACCORMACK */
+  float   vorticity;   /* confinement strength eps >= 0; 0: none */
+} vpt_fluid_detail;
+int vpt_scene_fluid_step_detail(vpt_scene* scene, const vpt_fluid_step* step, const vpt_fluid_solver* solver, const vpt_fluid_detail* detail);
+
 /* ---- adding and removing volumes, grid instances and SDFs -------------------------------------------------------------
  * The one thing vpt_scene_update_volumes leaves fixed: how many there are.  An edit of its own, because vpt_volume_edit keeps its layout;
  * the contract is that of vpt_scene_update_instances and vpt_scene_update_shapes.  After vpt_scene_update_volume_set(s, edit) every table
@@ -1678,6 +1708,8 @@ int  vpt_session_filter_volumes(vpt_session* session, const vpt_filter_edit* edi
 int  vpt_session_fluid_step(vpt_session* session, const vpt_fluid_step* step);
 /* vpt_scene_fluid_step_solver, then a reset; a refused edit leaves the session as it was */
 int  vpt_session_fluid_step_solver(vpt_session* session, const vpt_fluid_step* step, const vpt_fluid_solver* solver);
+/* vpt_scene_fluid_step_detail, then a reset; a refused edit leaves the session as it was */
+int  vpt_session_fluid_step_detail(vpt_session* session, const vpt_fluid_step* step, const vpt_fluid_solver* solver, const vpt_fluid_detail* detail);
 /* vpt_scene_set_volgrid_color, then a reset.  The session stays a volgrid session: its pick, id frame and first-collision pass keep
  * meaning the grey flight */
 int  vpt_session_set_volgrid_color(vpt_session* session, int on);

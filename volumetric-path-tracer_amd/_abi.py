@@ -222,6 +222,13 @@ class VptFluidSolver(C.Structure):  # vpt_fluid_solver
 assert C.sizeof(VptFluidSolver) == 16
 
 
+class VptFluidDetail(C.Structure):  # vpt_fluid_detail
+    _fields_ = [("advection", C.c_int32), ("vorticity", C.c_float)]
+
+
+assert C.sizeof(VptFluidDetail) == 8
+
+
 class VptVolumeNew(C.Structure):  # vpt_volume_new
     _fields_ = [("whd", C.c_int32 * 3), ("res", C.c_float), ("source", C.c_int32), ("offset", C.c_int64), ("bake", C.c_void_p), ("fill", C.c_float),
                 ("copy_of", C.c_int32)]
@@ -251,6 +258,8 @@ FLUID_OPEN_ALL = 63       # vpt_fluid_step::open_faces: bit 0..5 = -x, +x, -y, +
 FLUID_JACOBI, FLUID_MULTIGRID = 0, 1   # vpt_fluid_solver::kind
 FLUID_MAX_CYCLES, FLUID_MAX_SMOOTH, FLUID_MAX_COARSE_SWEEPS = 64, 4, 64
 FLUID_DEFAULT_MG_BLOCK = 2   # half-sweeps per smoothing launch unless VPT_FLUID_MG_BLOCK says 2 or 4 (csrc/vpt_fluid.hip)
+FLUID_SEMI_LAGRANGIAN, FLUID_MACCORMACK = 0, 1   # vpt_fluid_detail::advection
+FLUID_DETAIL_BYTES = 8   # VPT_FLUID_DETAIL_BYTES: a detail as the kernels get it
 MATERIAL_TYPES = ["matte", "glossy", "reflective", "transparent", "refractive", "subsurface", "volumetric", "gltfpbr"]
 
 
@@ -367,6 +376,8 @@ hip.vpt_scene_fluid_step.argtypes = [_p, C.POINTER(VptFluidStep)]
 hip.vpt_session_fluid_step.argtypes = [_p, C.POINTER(VptFluidStep)]
 hip.vpt_scene_fluid_step_solver.argtypes = [_p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver)]
 hip.vpt_session_fluid_step_solver.argtypes = [_p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver)]
+hip.vpt_scene_fluid_step_detail.argtypes = [_p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver), C.POINTER(VptFluidDetail)]
+hip.vpt_session_fluid_step_detail.argtypes = [_p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver), C.POINTER(VptFluidDetail)]
 hip.vpt_scene_update_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
 hip.vpt_multi_update_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
 hip.vpt_session_edit_volume_set.argtypes = [_p, C.POINTER(VptVolumeSetEdit)]
@@ -552,6 +563,9 @@ host.vpth_scene_fluid_step.argtypes = [_p, C.POINTER(VptFluidStep), C.c_char_p, 
 host.vpth_fluid_step.argtypes = [_p, _p, _p, _p, _p, C.POINTER(VptFluidStep), C.c_char_p, C.c_int]
 host.vpth_scene_fluid_step_solver.argtypes = [_p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver), C.c_char_p, C.c_int]
 host.vpth_fluid_step_solver.argtypes = [_p, _p, _p, _p, _p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver), C.c_char_p, C.c_int]
+host.vpth_scene_fluid_step_detail.argtypes = [_p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver), C.POINTER(VptFluidDetail), C.c_char_p, C.c_int]
+host.vpth_fluid_step_detail.argtypes = [_p, _p, _p, _p, _p, C.POINTER(VptFluidStep), C.POINTER(VptFluidSolver), C.POINTER(VptFluidDetail), C.c_char_p, C.c_int]
+host.vpth_fluid_detail_stage.argtypes = [C.c_int, _p, _p, _p, _p, _p, C.POINTER(VptFluidStep), C.POINTER(VptFluidDetail), C.c_char_p, C.c_int]
 host.vpth_fluid_multigrid_pressure.argtypes = [_p, _p, _p, C.c_int, C.POINTER(VptFluidSolver), C.c_char_p, C.c_int]
 host.vpth_fluid_stage.argtypes = [C.c_int, _p, _p, _p, _p, _p, _p, _p, C.POINTER(VptFluidStep), C.c_char_p, C.c_int]
 host.vpth_scene_desc.argtypes = [_p]

@@ -226,7 +226,10 @@ int vpt_scene_filter_volumes(vpt_scene* s, const vpt_filter_edit* edit) { return
 // the voxels of four volumes at once: a density moved by a velocity, one stable-fluids step after another (vpt_fluid.hip)
 int vpt_scene_fluid_step(vpt_scene* s, const vpt_fluid_step* step) { return vpt_scene_fluid_step_solver(s, step, nullptr); }
 int vpt_scene_fluid_step_solver(vpt_scene* s, const vpt_fluid_step* step, const vpt_fluid_solver* solver) {   // stage 6 by multigrid, if asked
-  return edit_scene(s, step, [solver](resident& r, const vpt_fluid_step& st, edit_outcome& out) { return fluid_apply(r, st, solver, out); });
+  return vpt_scene_fluid_step_detail(s, step, solver, nullptr);
+}
+int vpt_scene_fluid_step_detail(vpt_scene* s, const vpt_fluid_step* step, const vpt_fluid_solver* solver, const vpt_fluid_detail* detail) {   // and stages 2b and 3
+  return edit_scene(s, step, [=](resident& r, const vpt_fluid_step& st, edit_outcome& out) { return fluid_apply(r, st, solver, detail, out); });
 }
 // volumes, grid instances and SDFs added and removed (vpt_volume_set.hip): the pool compacted by one gather, the lights following the SDFs
 int vpt_scene_update_volume_set(vpt_scene* s, const vpt_volume_set_edit* edit) { return edit_scene(s, edit, volume_set_apply); }

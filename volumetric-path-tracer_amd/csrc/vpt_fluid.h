@@ -11,4 +11,7 @@
 // solver (include/vpt.h: vpt_scene_fluid_step_solver): null or VPT_FLUID_JACOBI, the above; VPT_FLUID_MULTIGRID, solver->cycles V-cycles in
 // the Jacobi launches' place, the levels above the volume in r.d_fluid_mg (grown to three fields a level), VPT_FLUID_MG_BLOCK half-sweeps
 // a smoothing launch.
-int fluid_apply(resident& r, const vpt_fluid_step& step, const vpt_fluid_solver* solver, edit_outcome& out);
+// detail (include/vpt.h: vpt_scene_fluid_step_detail): null or off, the above.  vorticity > 0: the confinement launch takes the force
+// launch's place and leaves the fields in the scratch, the advection goes from there back into the pool and the move runs in place.
+// VPT_FLUID_MACCORMACK: one launch more after the advection, and the scratch grown to eight fields.
+int fluid_apply(resident& r, const vpt_fluid_step& step, const vpt_fluid_solver* solver, const vpt_fluid_detail* detail, edit_outcome& out);

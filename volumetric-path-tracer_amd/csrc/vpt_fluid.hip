@@ -4,7 +4,9 @@
 // kernels - force + walls, the advection into scratch, its move into place + walls, the divergence, the temporally blocked Jacobi sweep
 // of one 8 x 8 x 8 tile per workgroup through LDS, and project + walls - and, for vpt_scene_fluid_step_solver, the three kernels of a
 // multigrid V-cycle in the Jacobi's place: a temporally blocked red-black smoother that prolongs as it stages, the residual and its
-// restriction in one launch, and the coarsest level in one workgroup.
+// restriction in one launch, and the coarsest level in one workgroup.  For vpt_scene_fluid_step_detail two more: the
+// vorticity confinement, a two-level stencil of one 8 x 8 x 8 tile through LDS that applies the force as it stages, and the second pass
+// of the MacCormack advection.
 #include <cstdlib>
 
 #include "vpt_error.h"
@@ -296,6 +298,101 @@ __global__ __launch_bounds__(BLOCK) void fluid_project_kernel(fluid_fields f, co
   f.f[3][idx] = vpt_fluid_wall(vpt_fluid_project(f.f[3][idx], p, at, g.w * g.h, k, g.d, g.open, 2), k, g.d, g.open, 2);
 }
 
+// ---- what vpt_scene_fluid_step_detail adds (include/vpt.h) -------------------------------------------------------------------
+// Stage 2b, and with FORCE stages 1 and 2 before it in the same launch: a two-level stencil through LDS.  The new velocity at a node needs
+// m = |omega| at its six neighbours and omega needs the velocity at theirs, so a workgroup that makes one 8 x 8 x 8 tile reads the
+// velocity of the 12^3 positions around it (halo 2).
+//  1. Stage the three components of the 12^3 positions.  With FORCE what is staged is wall(force(u, rho)) of the fields as the last step
+//     left them - stages 1 and 2 per position, the way the multigrid's smoother prolongs while it stages - and this launch takes
+//     fluid_force_kernel's place; the lanes of the 8^3 centre store the decayed density as they pass.  A position outside the volume is
+//     NOT a node: it is staged as 0 and never computed or read below, since vpt_fluid_difference clamps on the node's VOLUME coordinates.
+//  2. Phase A: m at the nodes of the 10^3 region, into LDS.  omega is NOT kept: 3 x 10^3 words more, for what phase B makes again from twelve
+//     LDS reads of the staged tile.
+//  3. Phase B: omega again at the nodes of the 8^3 centre, eta from m, N x omega, the new velocity and its walls.
+// Other workgroups' halos still read `f`, so everything goes to `out`, the scratch: never in place.
+// LDS layout: the components dense at l = tx + 12 (ty + 12 tz), no padding; a lane's items are l = base + tid + 256 n over whole z-slabs of
+// a phase's region with the rim masked, as in fluid_jacobi_kernel: the 32 lanes of a group read consecutive words for every neighbour.  m
+// dense at 10^3: the active lanes of a group map to strictly increasing words less than 32 apart.
+template <bool FORCE>
+__global__ __launch_bounds__(BLOCK) void fluid_confine_kernel(fluid_fields f, fluid_fields out, vpt_fluid_record g, float strength, unsigned tiles_x, unsigned tiles_y) {
+  constexpr int T = 12, PLANE = T * T, CELLS = T * T * T, TM = T - 2;
+  __shared__ float ubuf[3 * CELLS];   // 20 736 bytes, and 4 000 of m
+  __shared__ float mbuf[TM * TM * TM];
+  const int      tid = (int)threadIdx.x;
+  const unsigned bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, bz = blockIdx.x / (tiles_x * tiles_y);
+  const int      x0 = 8 * (int)bx - 2, y0 = 8 * (int)by - 2, z0 = 8 * (int)bz - 2;   // tile position 0 in the volume
+  const float *  ub = ubuf, *vb = ubuf + CELLS, *wb = ubuf + 2 * CELLS;
+
+  for (int l = tid; l < CELLS; l += BLOCK) {
+    const int  tx = l % T, ty = (l / T) % T, tz = l / PLANE;
+    const int  gx = x0 + tx, gy = y0 + ty, gz = z0 + tz;
+    const bool node = gx >= 0 && gx < g.w && gy >= 0 && gy < g.h && gz >= 0 && gz < g.d;
+    float      u = 0.0f, v = 0.0f, w = 0.0f;
+    if (node) {
+      const int  at = gx + g.w * (gy + g.h * gz);
+      const bool centre = tx >= 2 && tx < T - 2 && ty >= 2 && ty < T - 2 && tz >= 2 && tz < T - 2;
+      u = f.f[1][at], v = f.f[2][at], w = f.f[3][at];
+      if (FORCE) {
+        const float rho = f.f[0][at];
+        u = vpt_fluid_wall(vpt_fluid_force(u, g.keep_velocity, g.force[0], rho), gx, g.w, g.open, 0);
+        v = vpt_fluid_wall(vpt_fluid_force(v, g.keep_velocity, g.force[1], rho), gy, g.h, g.open, 1);
+        w = vpt_fluid_wall(vpt_fluid_force(w, g.keep_velocity, g.force[2], rho), gz, g.d, g.open, 2);
+        if (centre) out.f[0][at] = vpt_fluid_decay(rho, g.keep_density);
+      } else if (centre) {
+        out.f[0][at] = f.f[0][at];
+      }
+    }
+    ubuf[l] = u, ubuf[CELLS + l] = v, ubuf[2 * CELLS + l] = w;
+  }
+  __syncthreads();
+
+  for (int l = PLANE + tid; l < (T - 1) * PLANE; l += BLOCK) {
+    const int tx = l % T, ty = (l / T) % T, tz = l / PLANE;
+    const int gx = x0 + tx, gy = y0 + ty, gz = z0 + tz;
+    if (tx < 1 || tx >= T - 1 || ty < 1 || ty >= T - 1 || gx < 0 || gx >= g.w || gy < 0 || gy >= g.h || gz < 0 || gz >= g.d) continue;
+    float omega[3];
+    vpt_fluid_curl(ub, vb, wb, l, 1, T, PLANE, gx, gy, gz, g, omega);
+    mbuf[(tx - 1) + TM * ((ty - 1) + TM * (tz - 1))] = vpt_fluid_length(omega);
+  }
+  __syncthreads();
+
+  for (int l = 2 * PLANE + tid; l < (T - 2) * PLANE; l += BLOCK) {
+    const int tx = l % T, ty = (l / T) % T, tz = l / PLANE;
+    const int gx = x0 + tx, gy = y0 + ty, gz = z0 + tz;
+    if (tx < 2 || tx >= T - 2 || ty < 2 || ty >= T - 2 || gx >= g.w || gy >= g.h || gz >= g.d) continue;   // (the centre starts inside the volume)
+    float omega[3], force[3];
+    vpt_fluid_curl(ub, vb, wb, l, 1, T, PLANE, gx, gy, gz, g, omega);
+    const int ml = (tx - 1) + TM * ((ty - 1) + TM * (tz - 1));
+    vpt_fluid_confinement(vpt_fluid_difference(mbuf, ml, 1, gx, g.w), vpt_fluid_difference(mbuf, ml, TM, gy, g.h), vpt_fluid_difference(mbuf, ml, TM * TM, gz, g.d), omega,
+        force);
+    const int at = gx + g.w * (gy + g.h * gz);
+    out.f[1][at] = vpt_fluid_wall(vpt_fluid_confine(ub[l], strength, force[0]), gx, g.w, g.open, 0);
+    out.f[2][at] = vpt_fluid_wall(vpt_fluid_confine(vb[l], strength, force[1]), gy, g.h, g.open, 1);
+    out.f[3][at] = vpt_fluid_wall(vpt_fluid_confine(wb[l], strength, force[2]), gz, g.d, g.open, 2);
+  }
+}
+
+// Stage 3's second pass with VPT_FLUID_MACCORMACK; the first is fluid_advect_kernel, which left `hat`.  One lane per node and plain
+// loads, as there: one back-trace and one forward trace, then per field the eight corners of `f` at the back-trace - the first pass's,
+// loaded again for their least and greatest, which gives the first pass's value too - the eight of `hat` at the forward trace, and the
+// node's own.  f, hat and out are three different sets of buffers.
+__global__ __launch_bounds__(BLOCK) void fluid_maccormack_kernel(fluid_fields f, fluid_fields hat, fluid_fields out, vpt_fluid_record g, unsigned n) {
+  const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  int i, j, k;
+  node_of(g, idx, i, j, k);
+  const float u = f.f[1][idx], v = f.f[2][idx], w = f.f[3][idx];
+  const float qx = vpt_fluid_backtrace(i, g.dt, u, g.w), qy = vpt_fluid_backtrace(j, g.dt, v, g.h), qz = vpt_fluid_backtrace(k, g.dt, w, g.d);
+  const float rx = vpt_fluid_foretrace(i, g.dt, u, g.w), ry = vpt_fluid_foretrace(j, g.dt, v, g.h), rz = vpt_fluid_foretrace(k, g.dt, w, g.d);
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    float       lo, hi;
+    const float first = vpt_fluid_advect_bounds(f.f[c], g.w, g.h, g.d, qx, qy, qz, lo, hi);
+    const float bar   = vpt_volgrid_trilerp(hat.f[c], g.w, g.h, g.d, rx, ry, rz);
+    out.f[c][idx] = vpt_fluid_maccormack(first, f.f[c][idx], bar, lo, hi);
+  }
+}
+
 int validate_step(const DScene& d, const edit_mirrors& m, const vpt_fluid_step& s) {
   bool unsupported;
   if (const char* fault = vpt_fluid_step_fault(s, d.num_volumes, [&](int id) { return m.volumes[(size_t)id].whd; }, &unsupported))
@@ -329,6 +426,20 @@ int mg_block() {
   const char* e = getenv("VPT_FLUID_MG_BLOCK");
   if (e && (e[0] == '2' || e[0] == '4') && !e[1]) return e[0] - '0';
   return DEFAULT_MG_BLOCK;
+}
+
+// stages 1 and 2 in the confinement launch's staging unless VPT_FLUID_CONFINE_FUSED = 0 asks for fluid_force_kernel and a launch more
+bool confine_fused() {
+  const char* e = getenv("VPT_FLUID_CONFINE_FUSED");
+  return !(e && e[0] == '0' && !e[1]);
+}
+int launch_confine(resident& r, bool fused, const fluid_fields& f, const fluid_fields& out, const vpt_fluid_record& g, float strength) {
+  const unsigned nbx = (unsigned)(g.w + 7) / 8, nby = (unsigned)(g.h + 7) / 8, nbz = (unsigned)(g.d + 7) / 8;
+  const dim3     blocks(nbx * nby * nbz), lanes(BLOCK);
+  if (fused) hipLaunchKernelGGL(fluid_confine_kernel<true>, blocks, lanes, 0, 0, f, out, g, strength, nbx, nby);
+  else hipLaunchKernelGGL(fluid_confine_kernel<false>, blocks, lanes, 0, 0, f, out, g, strength, nbx, nby);
+  LAUNCHED(r);
+  return VPT_OK;
 }
 
 struct mg_fields {
@@ -370,19 +481,22 @@ int mg_cycle(resident& r, const vpt_fluid_mg_level* levels, int count, mg_fields
 
 }  // namespace
 
-int fluid_apply(resident& r, const vpt_fluid_step& s, const vpt_fluid_solver* solver, edit_outcome& out) {
+int fluid_apply(resident& r, const vpt_fluid_step& s, const vpt_fluid_solver* solver, const vpt_fluid_detail* detail, edit_outcome& out) {
   DScene& d = r.d;
   if (int rc = validate_step(d, r.m, s)) return rc;
   if (const char* fault = vpt_fluid_solver_fault(solver)) return vpt_set_error(VPT_ERR_INVALID_ARG, "fluid: %s", fault);
+  if (const char* fault = vpt_fluid_detail_fault(detail)) return vpt_set_error(VPT_ERR_INVALID_ARG, "fluid: %s", fault);
   out.changed = true;   // (a step that launches nothing too: it starts the counters again)
   if (int rc = begin_update(r)) return rc;
   const vpt_volume&      rho = r.m.volumes[(size_t)s.density];
   const vpt_fluid_record g   = vpt_fluid_make_record(rho.whd, s);
   const long long        n   = (long long)g.w * g.h * g.d;
   const bool             any = s.steps > 0 && n > 0;
-  if (any && 4 * (size_t)n * sizeof(float) > r.fluid_scratch_bytes) {
-    if (int rc = r.d_fluid_scratch.allocate(4 * (size_t)n * sizeof(float))) return r.fluid_scratch_bytes = 0, rc;
-    r.fluid_scratch_bytes = 4 * (size_t)n * sizeof(float);
+  const bool             confines = vpt_fluid_confines(detail), maccormack = vpt_fluid_maccormacks(detail);
+  const size_t           fields = maccormack ? 8 : 4;   // the second pass reads the fields, the first pass's and writes a third set
+  if (any && fields * (size_t)n * sizeof(float) > r.fluid_scratch_bytes) {
+    if (int rc = r.d_fluid_scratch.allocate(fields * (size_t)n * sizeof(float))) return r.fluid_scratch_bytes = 0, rc;
+    r.fluid_scratch_bytes = fields * (size_t)n * sizeof(float);
   }
   // the multigrid's levels above 0: p, its partner and b of each, sized from the level's own whd (halves round up)
   vpt_fluid_mg_level levels[VPT_FLUID_MG_MAX_LEVELS];
@@ -396,11 +510,15 @@ int fluid_apply(resident& r, const vpt_fluid_step& s, const vpt_fluid_solver* so
   HIP_TRY(hipEventRecord(r.upd_ev0, 0));
   if (any) {
     r.last_bytes += (long long)sizeof(vpt_fluid_record);   // the step, in the kernels' argument block
+    if (confines || maccormack) r.last_bytes += (long long)sizeof(vpt_fluid_detail_record);
+    const vpt_fluid_detail_record detailed = vpt_fluid_make_detail(s, detail);
     float* const       pool = mut(d.voxels);
     const fluid_fields f    = {{pool + rho.offset, pool + r.m.volumes[(size_t)s.velocity[0]].offset, pool + r.m.volumes[(size_t)s.velocity[1]].offset,
         pool + r.m.volumes[(size_t)s.velocity[2]].offset}};
     float* const       sc   = r.d_fluid_scratch.get<float>();
     const fluid_fields scratch = {{sc, sc + n, sc + 2 * n, sc + 3 * n}};
+    const fluid_fields second  = {{sc + 4 * n, sc + 5 * n, sc + 6 * n, sc + 7 * n}};   // (with MacCormack only)
+    const bool         fused   = confine_fused();
     float *div = sc, *p = sc + n, *q = sc + 2 * n;   // once the advected fields are in place the scratch is free: d and the two p
     const int block = jacobi_block(), half_sweeps = mg_block();
     mg_fields at[VPT_FLUID_MG_MAX_LEVELS];
@@ -411,9 +529,21 @@ int fluid_apply(resident& r, const vpt_fluid_step& s, const vpt_fluid_solver* so
       next += 3 * nodes;
     }
     for (int step = 0; step < s.steps; step++) {
-      LAUNCH(r, fluid_force_kernel, n, f, g, (unsigned)n);
-      LAUNCH(r, fluid_advect_kernel, n, f, scratch, g, (unsigned)n);
-      LAUNCH(r, fluid_place_kernel, n, f, scratch, g, (unsigned)n);
+      if (!confines || !fused) LAUNCH(r, fluid_force_kernel, n, f, g, (unsigned)n);
+      if (confines) {   // the fields after 2b are in the scratch: the advection goes from there back into the pool, and place runs in place
+        if (int rc = launch_confine(r, fused, f, scratch, g, detailed.k)) return rc;
+        if (maccormack) {
+          LAUNCH(r, fluid_advect_kernel, n, scratch, second, g, (unsigned)n);
+          LAUNCH(r, fluid_maccormack_kernel, n, scratch, second, f, g, (unsigned)n);
+        } else {
+          LAUNCH(r, fluid_advect_kernel, n, scratch, f, g, (unsigned)n);
+        }
+        LAUNCH(r, fluid_place_kernel, n, f, f, g, (unsigned)n);
+      } else {
+        LAUNCH(r, fluid_advect_kernel, n, f, scratch, g, (unsigned)n);
+        if (maccormack) LAUNCH(r, fluid_maccormack_kernel, n, f, scratch, second, g, (unsigned)n);
+        LAUNCH(r, fluid_place_kernel, n, f, maccormack ? second : scratch, g, (unsigned)n);
+      }
       LAUNCH(r, fluid_divergence_kernel, n, f, div, p, g, (unsigned)n);
       if (count) {   // `cycles` V-cycles from the p = 0 the divergence launch stored; level 0 lives in the scratch
         at[0] = {p, q, div};

@@ -52,6 +52,80 @@ VPT_FLUID_HD float vpt_fluid_advect(const float* field, int W, int H, int D, flo
   return vpt_filter_one_nan(vpt_volgrid_trilerp(field, W, H, D, qx, qy, qz));
 }
 
+// ---- 2b. / 3'. what vpt_scene_fluid_step_detail adds (include/vpt.h): vorticity confinement and the MacCormack advection ----------------
+// the detail as the kernels get it: VPT_FLUID_DETAIL_BYTES, made on the host by vpt_fluid_make_detail (a null detail: off)
+struct vpt_fluid_detail_record {
+  int32_t advection;
+  float   k;   // dt * vorticity, one float32 product
+};
+static_assert(sizeof(vpt_fluid_detail_record) == VPT_FLUID_DETAIL_BYTES, "include/vpt.h states the size of a detail's record");
+inline vpt_fluid_detail_record vpt_fluid_make_detail(const vpt_fluid_step& s, const vpt_fluid_detail* d) {
+  return {d ? d->advection : VPT_FLUID_SEMI_LAGRANGIAN, d ? s.dt * d->vorticity : 0.0f};
+}
+inline bool vpt_fluid_confines(const vpt_fluid_detail* d) { return d && d->vorticity > 0.0f; }
+inline bool vpt_fluid_maccormacks(const vpt_fluid_detail* d) { return d && d->advection == VPT_FLUID_MACCORMACK; }
+// null, or what is wrong with the detail (null: off)
+inline const char* vpt_fluid_detail_fault(const vpt_fluid_detail* d) {
+  if (!d) return nullptr;
+  if (d->advection != VPT_FLUID_SEMI_LAGRANGIAN && d->advection != VPT_FLUID_MACCORMACK)
+    return "detail: advection is not one of VPT_FLUID_SEMI_LAGRANGIAN, VPT_FLUID_MACCORMACK";
+  if (!std::isfinite(d->vorticity) || d->vorticity < 0.0f) return "detail: vorticity is not finite or is negative";
+  return nullptr;
+}
+
+// a[+1] - a[-1] along one axis at node i of the W along it, `step` words between neighbours, the indices clamped to the volume: a[at +- step]
+// is read only inside the volume, so `a` may as well be a tile in LDS whose positions outside the volume hold nothing
+VPT_FLUID_HD float vpt_fluid_difference(const float* a, int at, int step, int i, int W) {
+  return a[at + (vpt_filter_clamp(i + 1, W) - i) * step] - a[at + (vpt_filter_clamp(i - 1, W) - i) * step];
+}
+// omega at node (i, j, k) of the volume: u, v, w the three components at strides sx, sy, sz, [at] the node
+VPT_FLUID_HD void vpt_fluid_curl(const float* u, const float* v, const float* w, int at, int sx, int sy, int sz, int i, int j, int k, const vpt_fluid_record& g,
+    float omega[3]) {
+  omega[0] = 0.5f * (vpt_fluid_difference(w, at, sy, j, g.h) - vpt_fluid_difference(v, at, sz, k, g.d));
+  omega[1] = 0.5f * (vpt_fluid_difference(u, at, sz, k, g.d) - vpt_fluid_difference(w, at, sx, i, g.w));
+  omega[2] = 0.5f * (vpt_fluid_difference(v, at, sx, i, g.w) - vpt_fluid_difference(u, at, sy, j, g.h));
+}
+VPT_FLUID_HD float vpt_fluid_length(const float a[3]) { return sqrtf((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]); }
+// N x omega from the three clamped differences of m = |omega| and the node's own omega
+VPT_FLUID_HD void vpt_fluid_confinement(float dmx, float dmy, float dmz, const float omega[3], float f[3]) {
+  const float eta[3] = {0.5f * dmx, 0.5f * dmy, 0.5f * dmz};
+  const float len    = vpt_fluid_length(eta) + 1e-12f;
+  const float N[3]   = {eta[0] / len, eta[1] / len, eta[2] / len};
+  f[0] = N[1] * omega[2] - N[2] * omega[1];
+  f[1] = N[2] * omega[0] - N[0] * omega[2];
+  f[2] = N[0] * omega[1] - N[1] * omega[0];
+}
+VPT_FLUID_HD float vpt_fluid_confine(float u, float k, float f) { return vpt_filter_one_nan(u + k * f); }
+
+// where node i goes along one axis: vpt_fluid_backtrace with the other sign
+VPT_FLUID_HD float vpt_fluid_foretrace(int i, float dt, float u, int W) {
+  float r = (float)i + dt * u;
+  r       = r > 0.0f ? r : 0.0f;
+  r       = r < (float)(W - 1) ? r : (float)(W - 1);
+  return r;
+}
+// vpt_fluid_advect, restated from vpt_volgrid_trilerp (the same i, ii, j, jj, k, kk, the same sum), that also answers the least and the
+// greatest of the eight corners it loaded, by selects in the order of the sum's terms
+VPT_FLUID_HD float vpt_fluid_advect_bounds(const float* vox, int W, int H, int D, float s, float t, float r, float& lo, float& hi) {
+  int i = (int)s, j = (int)t, k = (int)r;
+  i = i > 0 ? (i < W - 1 ? i : W - 1) : 0, j = j > 0 ? (j < H - 1 ? j : H - 1) : 0, k = k > 0 ? (k < D - 1 ? k : D - 1) : 0;
+  const int   ii = i + 1 < W - 1 ? i + 1 : W - 1, jj = j + 1 < H - 1 ? j + 1 : H - 1, kk = k + 1 < D - 1 ? k + 1 : D - 1;
+  const float u = s - i, v = t - j, w = r - k;
+  const int   WH = W * H, r0 = j * W + k * WH, r1 = jj * W + k * WH, r2 = j * W + kk * WH, r3 = jj * W + kk * WH;
+  const float c[8] = {vox[i + r0], vox[ii + r0], vox[i + r1], vox[i + r2], vox[i + r3], vox[ii + r2], vox[ii + r1], vox[ii + r3]};   // v000 v100 v010 v001 v011 v101 v110 v111
+  lo = hi = c[0];
+  for (int n = 1; n < 8; n++) lo = c[n] < lo ? c[n] : lo, hi = c[n] > hi ? c[n] : hi;
+  return vpt_filter_one_nan(c[0] * (1 - u) * (1 - v) * (1 - w) + c[1] * u * (1 - v) * (1 - w) + c[2] * (1 - u) * v * (1 - w) + c[3] * (1 - u) * (1 - v) * w +
+                            c[4] * (1 - u) * v * w + c[5] * u * (1 - v) * w + c[6] * u * v * (1 - w) + c[7] * u * v * w);
+}
+// the corrected value: hat the first pass's, own the node's before the advection, bar the first pass's traced forward again
+VPT_FLUID_HD float vpt_fluid_maccormack(float hat, float own, float bar, float lo, float hi) {
+  float v = hat + 0.5f * (own - bar);
+  v       = v < lo ? lo : v;
+  v       = v > hi ? hi : v;
+  return vpt_filter_one_nan(v);
+}
+
 // ---- 5. divergence from the three central differences, each u[i + 1] - u[i - 1] with the indices clamped to the volume ----------------
 VPT_FLUID_HD float vpt_fluid_divergence(float du, float dv, float dw) { return vpt_filter_one_nan(0.5f * ((du + dv) + dw)); }
 

@@ -494,6 +494,9 @@ int vpt_session_fluid_step(vpt_session* s, const vpt_fluid_step* step) { return 
 int vpt_session_fluid_step_solver(vpt_session* s, const vpt_fluid_step* step, const vpt_fluid_solver* solver) {
   return session_edit(s, step, [solver](vpt_scene* scene, const vpt_fluid_step* st) { return vpt_scene_fluid_step_solver(scene, st, solver); });
 }
+int vpt_session_fluid_step_detail(vpt_session* s, const vpt_fluid_step* step, const vpt_fluid_solver* solver, const vpt_fluid_detail* detail) {
+  return session_edit(s, step, [=](vpt_scene* scene, const vpt_fluid_step* st) { return vpt_scene_fluid_step_detail(scene, st, solver, detail); });
+}
 int vpt_session_edit_volume_set(vpt_session* s, const vpt_volume_set_edit* edit) { return session_edit(s, edit, vpt_scene_update_volume_set); }
 int vpt_session_rebuild_bvh(vpt_session* s, const vpt_bvh_rebuild* what) { return vpt_session_rebuild_bvh_quality(s, what, VPT_BVH_MIDDLE); }
 int vpt_session_rebuild_bvh_quality(vpt_session* s, const vpt_bvh_rebuild* what, int quality) {

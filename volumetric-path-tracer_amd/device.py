@@ -11,7 +11,7 @@ import numpy as np
 from ._abi import (AOV_PLANES, BVH_NODE, INSTANCE, LIGHT, SDF_AOV_PLANES, SHADER_NAMES, VOLGRID_AOV_PLANES, VOLGRID_CHROMA, VptAdaptive, VptAovPlanes, VptSdfAovPlanes,
                    VptVolgridAovPlanes, VptDisplay, VptError, VptLayout, VptParams,
                    VptSdf, VptVolume, VptVolumeInstance, _Handle, _check, shader_id, _counted, _edit_call, _mesh_desc, _mesh_region, _meshed, _p, hip, host)
-from .edits import BvhRebuild, FilterEdit, FluidSolver, FluidStep, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, VolumeSetEdit, mesh
+from .edits import BvhRebuild, FilterEdit, FluidDetail, FluidSolver, FluidStep, InstanceEdit, SceneEdit, SculptEdit, ShapeEdit, SubdivEdit, SubdivPlan, TextureEdit, VolumeEdit, VolumeSetEdit, mesh
 
 if TYPE_CHECKING:
     from .host_scene import HostScene
@@ -301,12 +301,13 @@ class DeviceScene(_Handle):
         per op cross PCIe, not one voxel.  edit: what HostScene.update_filters() returns."""
         _edit_call(self.handle, "vpt_scene_filter_volumes", edit)
 
-    def fluid_step(self, step: FluidStep, solver: Optional[FluidSolver] = None) -> None:
-        """vpt_scene_fluid_step_solver (include/vpt.h): `step.steps` Stable Fluids steps over the resident density and velocity volumes -
-        48 bytes cross PCIe, not one voxel.  step: one of what HostScene.update_fluid() returns.  solver: how the pressure is solved,
-        the step's own (what the host scene ran it with) unless given; neither: the step's Jacobi sweeps."""
-        solver = solver or step.solver
-        _edit_call(self.handle, "vpt_scene_fluid_step_solver", step, C.byref(solver.to_abi()) if solver else None)
+    def fluid_step(self, step: FluidStep, solver: Optional[FluidSolver] = None, detail: Optional[FluidDetail] = None) -> None:
+        """vpt_scene_fluid_step_detail (include/vpt.h): `step.steps` Stable Fluids steps over the resident density and velocity volumes -
+        48 bytes cross PCIe (56 with a detail), not one voxel.  step: one of what HostScene.update_fluid() returns.  solver: how the
+        pressure is solved, the step's own (what the host scene ran it with) unless given; neither: the step's Jacobi sweeps.  detail:
+        MacCormack advection and vorticity confinement, the step's own unless given; neither: none."""
+        solver, detail = solver or step.solver, detail or step.detail
+        _edit_call(self.handle, "vpt_scene_fluid_step_detail", step, C.byref(solver.to_abi()) if solver else None, C.byref(detail.to_abi()) if detail else None)
 
     def get_volumes(self):
         """(volumes, vol_instances, sdfs) as the device holds them, ctypes arrays of VptVolume, VptVolumeInstance, VptSdf

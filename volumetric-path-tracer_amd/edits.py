@@ -9,7 +9,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._abi import (FILTER_BLUR, FILTER_MAX_RADIUS, FILTER_NOISE, FILTER_RECORD_BYTES, FILTER_REMAP, FLUID_DEFAULT_BLOCK, FLUID_DEFAULT_MG_BLOCK, FLUID_JACOBI, FLUID_MULTIGRID, FLUID_RECORD_BYTES, VptFluidSolver, VptFluidStep, INSTANCE, MESH_ELEMENTS, MESH_FLOATS, SCULPT_RECORD_BYTES,
+from ._abi import (FILTER_BLUR, FILTER_MAX_RADIUS, FILTER_NOISE, FILTER_RECORD_BYTES, FILTER_REMAP, FLUID_DEFAULT_BLOCK, FLUID_DEFAULT_MG_BLOCK, FLUID_DETAIL_BYTES, FLUID_JACOBI, FLUID_MACCORMACK, FLUID_MULTIGRID, FLUID_RECORD_BYTES, FLUID_SEMI_LAGRANGIAN, VptFluidDetail, VptFluidSolver, VptFluidStep, INSTANCE, MESH_ELEMENTS, MESH_FLOATS, SCULPT_RECORD_BYTES,
                    VOXELS_REPLACE, VptFilterEdit, VptFilterEntry, VptFilterOp, host, VptBakeDesc, VptBvhRebuild, VptCamera, VptEnvironment,
                    VptError, VptInstanceEdit, VptMaterial, VptSceneEdit, VptSculptEdit, VptSculptEntry, VptSculptStamp, VptSdf, VptShapeData, VptShapeEdit,
                    VptSubdivEdit, VptSubdivLevel, VptSubdivPlan, VptTexture, VptTextureEdit, VptVolumeEdit, VptVolumeInstance, VptVolumeNew, VptVolumeSetEdit,
@@ -596,6 +596,29 @@ class FluidSolver:
 
 
 @dataclass
+class FluidDetail:
+    """What a FluidStep does against its own blur (include/vpt.h: vpt_fluid_detail): advection FLUID_MACCORMACK corrects and limits stage 3
+    with a second pass, vorticity > 0 adds the confinement force of stage 2b with that strength.  The defaults are off: the step as it
+    is without a detail."""
+    advection: int = FLUID_SEMI_LAGRANGIAN
+    vorticity: float = 0.0
+
+    def off(self) -> bool:
+        return self.advection == FLUID_SEMI_LAGRANGIAN and not self.vorticity > 0
+
+    def launches(self, step: "FluidStep", whd, solver: Optional[FluidSolver] = None, block: Optional[int] = None) -> int:
+        """launches of `step` over volumes of `whd` with this detail as vpt_scene_update_stats counts them: the step's with its pressure
+        (by `solver`, default the step's own; `block` as FluidSolver.launches or FluidStep.launches take it) and one more per step for
+        MacCormack's second pass - the confinement takes the force launch's place"""
+        solver = solver or step.solver
+        plain = solver.launches(step, whd, *([block] if block else [])) if solver else step.launches(*([block] if block else []))
+        return plain + (step.steps if self.advection == FLUID_MACCORMACK and min(whd) > 0 else 0)
+
+    def to_abi(self):
+        return VptFluidDetail(int(self.advection), float(self.vorticity))
+
+
+@dataclass
 class FluidStep:
     """What vpt_scene_fluid_step takes (include/vpt.h: vpt_fluid_step): the density's volume id, the three of the velocity (four
     different volumes of equal whd, velocities in node spacings per unit time), `steps` repetitions of one Stable Fluids step with
@@ -611,13 +634,16 @@ class FluidStep:
     keep_density: float = 1.0
     keep_velocity: float = 1.0
     solver: Optional[FluidSolver] = None   # None: the `iterations` Jacobi sweeps; HostScene.fluid_step notes the solver it ran here
+    detail: Optional[FluidDetail] = None   # None: semi-Lagrangian, no confinement; HostScene.fluid_step notes the detail it ran here
 
     def volumes(self) -> tuple:
         return (int(self.density), *(int(v) for v in self.velocity))
 
     def payload_bytes(self, nodes: int = 1) -> int:
-        """bytes of the step itself as vpt_scene_update_stats counts them: FLUID_RECORD_BYTES when anything is launched"""
-        return FLUID_RECORD_BYTES if self.steps > 0 and nodes > 0 else 0
+        """bytes of the step itself as vpt_scene_update_stats counts them: FLUID_RECORD_BYTES when anything is launched, and
+        FLUID_DETAIL_BYTES with a detail that is not off"""
+        detail = FLUID_DETAIL_BYTES if self.detail and not self.detail.off() else 0
+        return FLUID_RECORD_BYTES + detail if self.steps > 0 and nodes > 0 else 0
 
     def launches(self, block: int = FLUID_DEFAULT_BLOCK) -> int:
         """launches as vpt_scene_update_stats counts them at `block` sweeps per Jacobi launch (VPT_FLUID_BLOCK): per step force, advect,

@@ -42,6 +42,45 @@ void advect(float* const f[4], const vpt_fluid_record& g) {
     for (auto c = 0; c < 4; c++) f[c][at] = vpt_fluid_advect(old[c].data(), g.w, g.h, g.d, qx, qy, qz);
   });
 }
+// stage 2b: every node reads the velocity as stage 2 left it; m = |omega| over the whole grid first, then the force
+void confine(float* const f[4], const vpt_fluid_record& g, float strength) {
+  vector<float> old[3];
+  for (auto c = 0; c < 3; c++) old[c].assign(f[1 + c], f[1 + c] + nodes_of(g));
+  auto       m  = vector<float>(nodes_of(g));
+  const auto sy = g.w, sz = g.w * g.h;
+  each_node(g, [&](int i, int j, int k, int at) {
+    float omega[3];
+    vpt_fluid_curl(old[0].data(), old[1].data(), old[2].data(), at, 1, sy, sz, i, j, k, g, omega);
+    m[at] = vpt_fluid_length(omega);
+  });
+  each_node(g, [&](int i, int j, int k, int at) {
+    float omega[3], push[3];
+    vpt_fluid_curl(old[0].data(), old[1].data(), old[2].data(), at, 1, sy, sz, i, j, k, g, omega);
+    vpt_fluid_confinement(vpt_fluid_difference(m.data(), at, 1, i, g.w), vpt_fluid_difference(m.data(), at, sy, j, g.h), vpt_fluid_difference(m.data(), at, sz, k, g.d), omega,
+        push);
+    for (auto c = 0; c < 3; c++) f[1 + c][at] = vpt_fluid_confine(old[c][at], strength, push[c]);
+  });
+  walls(f, g);
+}
+// stage 3 with VPT_FLUID_MACCORMACK: the first pass over the whole grid, then the corrected and limited second
+void advect_maccormack(float* const f[4], const vpt_fluid_record& g) {
+  vector<float> old[4], hat[4];
+  for (auto c = 0; c < 4; c++) old[c].assign(f[c], f[c] + nodes_of(g)), hat[c].resize(nodes_of(g));
+  each_node(g, [&](int i, int j, int k, int at) {
+    const auto qx = vpt_fluid_backtrace(i, g.dt, old[1][at], g.w), qy = vpt_fluid_backtrace(j, g.dt, old[2][at], g.h), qz = vpt_fluid_backtrace(k, g.dt, old[3][at], g.d);
+    for (auto c = 0; c < 4; c++) hat[c][at] = vpt_fluid_advect(old[c].data(), g.w, g.h, g.d, qx, qy, qz);
+  });
+  each_node(g, [&](int i, int j, int k, int at) {
+    const auto qx = vpt_fluid_backtrace(i, g.dt, old[1][at], g.w), qy = vpt_fluid_backtrace(j, g.dt, old[2][at], g.h), qz = vpt_fluid_backtrace(k, g.dt, old[3][at], g.d);
+    const auto rx = vpt_fluid_foretrace(i, g.dt, old[1][at], g.w), ry = vpt_fluid_foretrace(j, g.dt, old[2][at], g.h), rz = vpt_fluid_foretrace(k, g.dt, old[3][at], g.d);
+    for (auto c = 0; c < 4; c++) {
+      float      lo, hi;
+      const auto first = vpt_fluid_advect_bounds(old[c].data(), g.w, g.h, g.d, qx, qy, qz, lo, hi);
+      const auto bar   = vpt_volgrid_trilerp(hat[c].data(), g.w, g.h, g.d, rx, ry, rz);
+      f[c][at] = vpt_fluid_maccormack(first, old[c][at], bar, lo, hi);
+    }
+  });
+}
 void divergence(const float* const f[4], const vpt_fluid_record& g, float* div) {
   const int sy = g.w, sz = g.w * g.h;
   each_node(g, [&](int i, int j, int k, int at) {
@@ -152,14 +191,30 @@ bool fluid_stage(int stage, float* const f[4], float* p, float* div, const int32
   return true;
 }
 
-bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& s, const vpt_fluid_solver* solver, string& error) {
+bool fluid_detail_stage(int stage, float* const f[4], const int32_t whd[3], const vpt_fluid_step& s, const vpt_fluid_detail& detail, string& error) {
+  if (auto fault = fault_of(whd, s)) return error = string{"fluid: "} + fault, false;
+  if (auto fault = vpt_fluid_detail_fault(&detail)) return error = string{"fluid: "} + fault, false;
+  const auto g = vpt_fluid_make_record(whd, s);
+  switch (stage) {
+    case 0: confine(f, g, vpt_fluid_make_detail(s, &detail).k); break;
+    case 1: advect_maccormack(f, g); break;
+    default: return error = "fluid: detail stage is not one of 0, 1", false;
+  }
+  return true;
+}
+
+bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& s, const vpt_fluid_solver* solver, const vpt_fluid_detail* detail, string& error) {
   if (auto fault = fault_of(whd, s)) return error = string{"fluid: "} + fault, false;
   if (auto fault = vpt_fluid_solver_fault(solver)) return error = string{"fluid: "} + fault, false;
+  if (auto fault = vpt_fluid_detail_fault(detail)) return error = string{"fluid: "} + fault, false;
   const auto g = vpt_fluid_make_record(whd, s);
   auto       div = vector<float>(nodes_of(g)), p = div;
   for (auto n = 0; n < s.steps && nodes_of(g) > 0; n++) {
     force(f, g), walls(f, g);
-    advect(f, g), walls(f, g);
+    if (vpt_fluid_confines(detail)) confine(f, g, vpt_fluid_make_detail(s, detail).k);
+    if (vpt_fluid_maccormacks(detail)) advect_maccormack(f, g);
+    else advect(f, g);
+    walls(f, g);
     divergence(f, g, div.data());
     if (vpt_fluid_multigrid(solver)) pressure_multigrid(g, *solver, div.data(), p.data());
     else pressure(g, div.data(), p.data());
@@ -167,7 +222,10 @@ bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& s
   }
   return true;
 }
-bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& s, string& error) { return fluid_step(f, whd, s, nullptr, error); }
+bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& s, const vpt_fluid_solver* solver, string& error) {
+  return fluid_step(f, whd, s, solver, nullptr, error);
+}
+bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& s, string& error) { return fluid_step(f, whd, s, nullptr, nullptr, error); }
 
 bool fluid_multigrid_pressure(const float* div, float* p, const int32_t whd[3], int open_faces, const vpt_fluid_solver& solver, string& error) {
   auto step = vpt_fluid_step{};
@@ -185,17 +243,31 @@ bool fluid_multigrid_pressure(const float* div, float* p, const int32_t whd[3], 
 extern "C" {
 
 // the host mirror on four host arrays of whd[0] * whd[1] * whd[2] nodes (x fastest); the step's volume ids are ignored.  A refused call writes nothing.
-int vpth_fluid_step_solver(float* density, float* u, float* v, float* w, const int32_t* whd, const vpt_fluid_step* step, const vpt_fluid_solver* solver, char* err,
-    int errlen) {
+int vpth_fluid_step_detail(float* density, float* u, float* v, float* w, const int32_t* whd, const vpt_fluid_step* step, const vpt_fluid_solver* solver,
+    const vpt_fluid_detail* detail, char* err, int errlen) {
   auto         error = vpt::string{};
   float* const f[4]  = {density, u, v, w};
   if (!density || !u || !v || !w || !whd || !step) error = "fluid: null argument";
-  else if (vpt::fluid_step(f, whd, *step, solver, error)) return 0;
+  else if (vpt::fluid_step(f, whd, *step, solver, detail, error)) return 0;
   if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", error.c_str());
   return -1;
 }
+int vpth_fluid_step_solver(float* density, float* u, float* v, float* w, const int32_t* whd, const vpt_fluid_step* step, const vpt_fluid_solver* solver, char* err,
+    int errlen) {
+  return vpth_fluid_step_detail(density, u, v, w, whd, step, solver, nullptr, err, errlen);
+}
 int vpth_fluid_step(float* density, float* u, float* v, float* w, const int32_t* whd, const vpt_fluid_step* step, char* err, int errlen) {
   return vpth_fluid_step_solver(density, u, v, w, whd, step, nullptr, err, errlen);
+}
+// one stage of vpt_scene_fluid_step_detail's rule alone: 0 stage 2b and its walls (whatever detail->vorticity), 1 stage 3 with VPT_FLUID_MACCORMACK
+int vpth_fluid_detail_stage(int stage, float* density, float* u, float* v, float* w, const int32_t* whd, const vpt_fluid_step* step, const vpt_fluid_detail* detail, char* err,
+    int errlen) {
+  auto         error = vpt::string{};
+  float* const f[4]  = {density, u, v, w};
+  if (!density || !u || !v || !w || !whd || !step || !detail) error = "fluid: null argument";
+  else if (vpt::fluid_detail_stage(stage, f, whd, *step, *detail, error)) return 0;
+  if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", error.c_str());
+  return -1;
 }
 // stage 6 alone by multigrid (include/vpt.h: vpt_scene_fluid_step_solver): div -> p, `solver->cycles` V-cycles from 0
 int vpth_fluid_multigrid_pressure(const float* div, float* p, const int32_t* whd, int open_faces, const vpt_fluid_solver* solver, char* err, int errlen) {

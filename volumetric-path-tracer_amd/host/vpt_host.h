@@ -464,6 +464,10 @@ bool filter_gaussian_weights(float sigma, int radius, float* weights);
 bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& step, string& error);
 // the same with stage 6 by `solver` (include/vpt.h: vpt_scene_fluid_step_solver; null: the Jacobi)
 bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& step, const vpt_fluid_solver* solver, string& error);
+// and with stages 2b and 3 by `detail` (include/vpt.h: vpt_scene_fluid_step_detail; null: neither)
+bool fluid_step(float* const f[4], const int32_t whd[3], const vpt_fluid_step& step, const vpt_fluid_solver* solver, const vpt_fluid_detail* detail, string& error);
+// one stage of the detail alone: 0 the confinement and its walls, 1 the MacCormack advection
+bool fluid_detail_stage(int stage, float* const f[4], const int32_t whd[3], const vpt_fluid_step& step, const vpt_fluid_detail& detail, string& error);
 // stage 6 alone by multigrid: p from the divergence `div` of a volume of whd nodes
 bool fluid_multigrid_pressure(const float* div, float* p, const int32_t whd[3], int open_faces, const vpt_fluid_solver& solver, string& error);
 // one stage alone: 0 force, 1 walls, 2 advect, 3 divergence (into div), 4 pressure (div -> p), 5 project (reads p) and walls

@@ -650,7 +650,7 @@ int vpth_scene_filter_volume(void* hh, const vpt_filter_entry* entry, const vpt_
 }
 // vpt_scene_fluid_step applied to the scene's copies of the step's four volumes by the host mirror (host/vpt_fluid.cpp).  The rules of
 // vpt_scene_fluid_step; a refused call writes nothing.
-int vpth_scene_fluid_step_solver(void* hh, const vpt_fluid_step* step, const vpt_fluid_solver* solver, char* err, int errlen) {
+int vpth_scene_fluid_step_detail(void* hh, const vpt_fluid_step* step, const vpt_fluid_solver* solver, const vpt_fluid_detail* detail, char* err, int errlen) {
   auto& sc = ((host_scene*)hh)->scene;
   if (!step) return set_error(err, errlen, "fluid: null step"), -1;
   auto whds = vector<int32_t>{};
@@ -665,8 +665,11 @@ int vpth_scene_fluid_step_solver(void* hh, const vpt_fluid_step* step, const vpt
     f[a] = v.vol.data();
   }
   auto error = string{};
-  if (!fluid_step(f, whds.data() + 3 * step->density, *step, solver, error)) return set_error(err, errlen, error), -1;
+  if (!fluid_step(f, whds.data() + 3 * step->density, *step, solver, detail, error)) return set_error(err, errlen, error), -1;
   return 0;
+}
+int vpth_scene_fluid_step_solver(void* hh, const vpt_fluid_step* step, const vpt_fluid_solver* solver, char* err, int errlen) {
+  return vpth_scene_fluid_step_detail(hh, step, solver, nullptr, err, errlen);
 }
 int vpth_scene_fluid_step(void* hh, const vpt_fluid_step* step, char* err, int errlen) { return vpth_scene_fluid_step_solver(hh, step, nullptr, err, errlen); }
 // make_lights of the scene as the setters above left it (an SDF is a light iff its material is emissive), then the flattened descriptor again

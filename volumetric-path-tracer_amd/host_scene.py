@@ -13,7 +13,7 @@ from ._abi import (BVH_MIDDLE, BVH_NODE, BVH_SAH, LIGHT, MESH_ELEMENTS, MESH_FLO
                    VptEnvironment, VptError, VptMaterial, VptSceneDescBvh, VptFilterEntry, VptSceneDescLights, VptSculptEntry, VptSdf, VptVolumeInstance, _Handle,
                    _check, _filled, _host_call, _mesh_desc, _mesh_region, _meshed, hip, host)
 from .device import PathtraceParams, PathtraceState
-from .edits import (LEVEL_TABLES, BvhRebuild, FilterEdit, FilterEntry, FilterOp, FluidSolver, FluidStep, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan,
+from .edits import (LEVEL_TABLES, BvhRebuild, FilterEdit, FilterEntry, FilterOp, FluidDetail, FluidSolver, FluidStep, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, SubdivPlan,
                     TextureEdit, VolumeEdit, VolumeNew, VolumeSetEdit, VolumeSource, mesh)
 
 
@@ -1019,10 +1019,11 @@ class HostScene(_Handle):
         if any(index in s.volumes() for s in self._fluid_steps):
             raise VptError(f"{what}: volume {index} has fluid steps pending: hand them out with update_fluid() first")
 
-    def fluid_step(self, step: FluidStep, solver: Optional[FluidSolver] = None) -> FluidStep:
+    def fluid_step(self, step: FluidStep, solver: Optional[FluidSolver] = None, detail: Optional[FluidDetail] = None) -> FluidStep:
         """`step.steps` Stable Fluids steps over the density and velocity volumes `step` names, by the rule of vpt_scene_fluid_step, the
-        pressure by `solver` (vpt_scene_fluid_step_solver; default: the step's own, else its Jacobi sweeps).  Returns the step it noted,
-        which carries the solver.  A refused call changes nothing."""
+        pressure by `solver` (vpt_scene_fluid_step_solver; default: the step's own, else its Jacobi sweeps), advection and confinement
+        by `detail` (vpt_scene_fluid_step_detail; default: the step's own, else neither).  Returns the step it noted, which carries the
+        solver and the detail.  A refused call changes nothing."""
         self._may("fluid_step", "volume_entries")
         for index in step.volumes():
             if index in self._volume_edit.volumes:
@@ -1034,7 +1035,10 @@ class HostScene(_Handle):
         self._run_bakes()
         if solver is not None:
             step = replace(step, solver=solver)
-        _host_call(host.vpth_scene_fluid_step_solver, self.handle, C.byref(step.to_abi()[0]), C.byref(step.solver.to_abi()) if step.solver else None)
+        if detail is not None:
+            step = replace(step, detail=detail)
+        _host_call(host.vpth_scene_fluid_step_detail, self.handle, C.byref(step.to_abi()[0]), C.byref(step.solver.to_abi()) if step.solver else None,
+                   C.byref(step.detail.to_abi()) if step.detail else None)
         self._fluid_steps.append(step)
         return step
 

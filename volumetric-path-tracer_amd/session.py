@@ -9,7 +9,7 @@ import numpy as np
 from ._abi import (DENOISE_ITERATIONS, DENOISE_SIGMA_ALBEDO, DENOISE_SIGMA_LUMINANCE, DENOISE_SIGMA_NORMAL, VptAdaptive, VptDenoise, VptPick,
                    VptError, VptSdf, VptSdfPick, VptSessionParams, VptVolgridPick, _Handle, _check, _edit_call, _p, hip)
 from .device import DeviceScene, DisplayParams, PathtraceParams, PathtraceState, _subdiv_edit_call
-from .edits import BvhRebuild, FilterEdit, FluidSolver, FluidStep, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, TextureEdit, VolumeEdit, VolumeSetEdit
+from .edits import BvhRebuild, FilterEdit, FluidDetail, FluidSolver, FluidStep, InstanceEdit, SceneEdit, SculptEdit, SculptEntry, ShapeEdit, Stamp, SubdivEdit, TextureEdit, VolumeEdit, VolumeSetEdit
 
 
 class RenderSession(_Handle):
@@ -136,11 +136,11 @@ class RenderSession(_Handle):
         leaves the session as it was"""
         _edit_call(self.handle, "vpt_session_filter_volumes", edit)
 
-    def edit_fluid(self, step: FluidStep, solver: Optional[FluidSolver] = None) -> None:
-        """vpt_scene_fluid_step_solver on the session's scene with a FluidStep of HostScene.update_fluid(), then a reset; a refused edit
-        leaves the session as it was.  solver: as DeviceScene.fluid_step"""
-        solver = solver or step.solver
-        _edit_call(self.handle, "vpt_session_fluid_step_solver", step, C.byref(solver.to_abi()) if solver else None)
+    def edit_fluid(self, step: FluidStep, solver: Optional[FluidSolver] = None, detail: Optional[FluidDetail] = None) -> None:
+        """vpt_scene_fluid_step_detail on the session's scene with a FluidStep of HostScene.update_fluid(), then a reset; a refused edit
+        leaves the session as it was.  solver, detail: as DeviceScene.fluid_step"""
+        solver, detail = solver or step.solver, detail or step.detail
+        _edit_call(self.handle, "vpt_session_fluid_step_detail", step, C.byref(solver.to_abi()) if solver else None, C.byref(detail.to_abi()) if detail else None)
 
     def set_volgrid_color(self, on: bool) -> None:
         """vpt_session_set_volgrid_color (include/vpt.h): DeviceScene.set_volgrid_color on the session's scene, then a reset, as after an
